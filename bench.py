@@ -30,7 +30,9 @@ library. `cpu_baseline` times the CPU oracle (oracle/, OpenMP, mulx/adcx/adox Mo
 when that takes about two minutes or less (2^24: yes), else on bounded samples with a fitted extrapolation, marked so. The
 oracle is the checker/baseline only; the timed path never touches it. `--check` proves once more with fixed blinding and
 compares proof.json byte for byte with the expected proof (oracle/closed_form.py: oracle H polynomial + MSMs in the
-exponent, any size); a mismatch makes the exit code 3.
+exponent, any size); a mismatch makes the exit code 3. `--dump-outputs DIR` writes the proof and public signals the last
+timed step returned as DIR/*.npy, with the fixed blinding of --check in the warm-up and timed steps, so that two builds can be
+compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -43,6 +45,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+GROTH16_FIXED = bytes(range(1, 32)) + bytes(range(31, 62))      # r, s (31 bytes each) of --check and --dump-outputs
 
 
 def parse():
@@ -77,7 +80,30 @@ def parse():
     ap.add_argument("--pmc-summary", default=None, help="summary of rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload "
                     "(tools/pmc_summary.py, made in the same gpurun call by tools/run_r4_prof.sh): `roofline.traffic` is then what those "
                     "passes counted; without it the newest committed profiles/r*_pmc_summary.json is read and labelled as such")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller -- every point of proof.json and "
+                         "the public signals -- as DIR/<key>.npy (float64, each 254-bit value as 8 little-endian 32-bit limbs: exact). The "
+                         "blinding of the warm-up and timed steps is then the fixed one of --check, so the same arguments give the same "
+                         "arrays on every run and every build")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory, out):
+    """--dump-outputs: the (proof.json, public.json) of the last timed step as DIR/<key>.npy, one array per point key of the proof
+    (pi_a, pi_b, ...; the shape of its JSON nesting plus an axis of 8 limbs) and DIR/public.npy"""
+    import numpy as np
+
+    def limbs(v):
+        return [limbs(x) for x in v] if isinstance(v, list) else [(int(v) >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+    proof_json, public_json = out
+    arrays = {k: v for k, v in json.loads(proof_json).items() if isinstance(v, list)}
+    arrays["public"] = json.loads(public_json)
+    os.makedirs(directory, exist_ok=True)
+    for name, value in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.array(limbs(value), dtype=np.float64))
 
 
 def cpu_share():
@@ -328,16 +354,21 @@ def bench_ultra(args, dev, ug, synth, torch, dist, backend, rank, world, local_r
         t0 = time.perf_counter()
         prover = ug.UltraGrothProver(zkey)
         create_s = time.perf_counter() - t0
+        if args.dump_outputs:
+            ug.set_test_blinding(b"".join(FIXED))
         for _ in range(args.warmup):
             prover.prove(uwtns)
         msm_ms = fft_ms = 0.0
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            prover.prove(uwtns)
+            out = prover.prove(uwtns)
             m, f, _ = prover.last_timings()
             msm_ms += m
             fft_ms += f
         elapsed = time.perf_counter() - t0                 # THE timed region: K whole calls, one after the other
+        if args.dump_outputs:
+            ug.set_test_blinding(b"")
+            dump_outputs(args.dump_outputs, out)
         # the region ran in the library's default configuration (the H branch of the final round beside its witness products:
         # stream times of the two parts stretch and overlap); the MSM | FFT split of the metric comes from K more calls with the
         # branch behind the products
@@ -509,18 +540,22 @@ def bench_ultra(args, dev, ug, synth, torch, dist, backend, rank, world, local_r
         dist.barrier()
         torch.cuda.synchronize()
 
+    if args.dump_outputs:
+        ug.set_test_blinding(b"".join(FIXED))
     for _ in range(args.warmup):
         step()
     barrier()
     msm_ms = fft_ms = 0.0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
         m, f, _ = prover.last_timings()
         msm_ms += m
         fft_ms += f
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        ug.set_test_blinding(b"")
     t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if cuda else "cpu")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     chk = None
@@ -532,6 +567,8 @@ def bench_ultra(args, dev, ug, synth, torch, dist, backend, rank, world, local_r
     dist.barrier()
     dist.destroy_process_group()          # before rank 0's host-side comparison (the CPU oracle proves the circuit): nobody waits in a collective
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
         if args.check:
             ok = chk == expected()
             workload += " [check: %s]" % ("bit-exact" if ok else "MISMATCH")
@@ -552,7 +589,7 @@ def main():
         raise SystemExit("launch N > 1 with: python -m torch.distributed.run --nnodes=1 --nproc-per-node N "
                          "--master-addr 127.0.0.1 --master-port P bench.py --gpus N ...")
 
-    if args.check:
+    if args.check or args.dump_outputs:
         os.environ["ULTRAGROTH_TEST_HOOKS"] = "1"       # fixed blinding for the comparison (only honoured when set before load)
     import torch
     import ultragroth_amd as ug
@@ -765,6 +802,8 @@ def main():
     out = None
     load()
     os.environ["ULTRAGROTH_OVERLAP"] = str(timed_overlap)
+    if args.dump_outputs:
+        ug.set_test_blinding(GROTH16_FIXED)
     for _ in range(args.warmup):
         out = step()
     for which in range(4):
@@ -788,6 +827,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     board = sampler.stop() if sampler else None
+    timed_out = out                             # (rank 0: what the last timed step returned)
+    if args.dump_outputs:
+        ug.set_test_blinding(b"")
     m1, f1, _ = prover.last_timings()
     msm_ms, fft_ms = m1 - m0, f1 - f0
     if dist is not None:
@@ -860,10 +902,10 @@ def main():
 
     chk = None
     if args.check:                              # one more step on EVERY rank (it contains collectives), fixed blinding
-        ug.set_test_blinding(bytes(range(1, 32)) + bytes(range(31, 62)))
+        ug.set_test_blinding(GROTH16_FIXED)
         chk = step()
         if single:                              # ... and once more through the reference's entry point, witness in host memory
-            ug.set_test_blinding(bytes(range(1, 32)) + bytes(range(31, 62)))
+            ug.set_test_blinding(GROTH16_FIXED)
             if prover.prove(wtns) != chk:
                 chk = ("groth16_prover_prove differs from the phase calls", "")
         ug.set_test_blinding(b"")
@@ -937,6 +979,8 @@ def main():
 
     rc = 0
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_out)
         (acc_ms, launches, entries), (g2_ms, g2_launches, g2_entries), (ntt_ms, ntt_launches, ntt_points) = kstats[:3]
         grp_ms, grp_launches, grp_entries = kstats[3]                          # A | B1 | C in one launch (three products per entry)
         n_local = (layouts[0].witness[1] - layouts[0].witness[0]) if not single else info["nVars"]
@@ -1093,7 +1137,7 @@ def main():
             if zkey is None:                     # N > 1: only now, and only on rank 0, the whole zkey is made (for its coefficient section)
                 zkey = synth.build_circuit(dev, log_domain, mix=args.mix, g1_only=args.g1_only)[0]
             exp = closed_form.groth16_expected(zkey, wtns, synth.SEEDS, synth.g1_generator_record(), synth.g2_generator_record(),
-                                               int.from_bytes(bytes(range(1, 32)), "little"), int.from_bytes(bytes(range(31, 62)), "little"),
+                                               int.from_bytes(GROTH16_FIXED[:31], "little"), int.from_bytes(GROTH16_FIXED[31:], "little"),
                                                g1_only=args.g1_only,
                                                b_zero_mask=synth.b_zero_mask(info["nVars"], args.b_zero) if (single and args.b_zero) else None)
             ok = (chk[0], chk[1]) == exp

@@ -1,14 +1,28 @@
 """CPU tests of the oracle itself: pinned to the reference's fixture, SURVEY.md Appendix A and the reference's own
-field layer (oracle/_ref, built from /root/reference/build when that tree is present)."""
+field layer -- the answers oracle/_ref (oracle/Makefile `ref`) gives on these tests' inputs, stored in
+tests/golden/ref_field_vectors.npz by tests/golden/make_ref_field_vectors.py."""
 import hashlib
 import json
+import os
 import random
 
+import numpy as np
 import pytest
 
 import oracle as O
 from oracle import pairing
-from conftest import fixed_rs
+from conftest import GOLDEN, fixed_rs
+
+
+@pytest.fixture(scope="module")
+def ref_vectors():
+    with np.load(os.path.join(GOLDEN, "ref_field_vectors.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _ints(rows):
+    """(n, 32) little-endian rows -> list of python ints"""
+    return [O.from_le(bytes(r)) for r in rows]
 
 
 def _sec(buf, ftype, sid):
@@ -58,11 +72,14 @@ def test_h_polynomial_known_answers(zkey, wtns):
 
 
 @pytest.mark.parametrize("which,mod,name", [(O.FR, O.R_MOD, "fr"), (O.FQ, O.Q_MOD, "fq")])
-def test_field_against_python_and_reference(which, mod, name):
+def test_field_against_python_and_reference(which, mod, name, ref_vectors):
     rng = random.Random(which)
     R = 1 << 256
     Rinv = pow(R, -1, mod)
     vals = [0, 1, 2, mod - 1, mod - 2, R % mod, (R * R) % mod] + [rng.randrange(mod) for _ in range(200)]
+    # the reference's own code (build/f{r,q}*.cpp + GMP) on these very operands
+    ref = {op: _ints(ref_vectors["%s_%s" % (name, op)]) for op in ("vals", "mul", "add", "sub", "neg", "to_mont", "from_mont", "inv")}
+    assert ref["vals"] == vals
     for i, a in enumerate(vals):
         b = vals[(7 * i + 3) % len(vals)]
         assert O.f_op("mul", which, a, b) == a * b * Rinv % mod
@@ -71,19 +88,19 @@ def test_field_against_python_and_reference(which, mod, name):
         assert O.f_op("neg", which, a) == (-a) % mod
         assert O.f_op("to_mont", which, a) == a * R % mod
         assert O.f_op("from_mont", which, a) == a * Rinv % mod
-        if O.ref is not None:                       # the reference's own code (build/f{r,q}*.cpp + GMP)
-            assert O.ref_op(name, "mul", a, b) == O.f_op("mul", which, a, b)
-            assert O.ref_op(name, "add", a, b) == O.f_op("add", which, a, b)
-            assert O.ref_op(name, "sub", a, b) == O.f_op("sub", which, a, b)
-            assert O.ref_op(name, "neg", a) == O.f_op("neg", which, a)
-            assert O.ref_op(name, "to_mont", a) == O.f_op("to_mont", which, a)
-            assert O.ref_op(name, "from_mont", a) == O.f_op("from_mont", which, a)
-            if a and i < 40:
-                assert O.ref_op(name, "inv", a) == O.f_op("inv", which, a)
+        assert ref["mul"][i] == O.f_op("mul", which, a, b)
+        assert ref["add"][i] == O.f_op("add", which, a, b)
+        assert ref["sub"][i] == O.f_op("sub", which, a, b)
+        assert ref["neg"][i] == O.f_op("neg", which, a)
+        assert ref["to_mont"][i] == O.f_op("to_mont", which, a)
+        assert ref["from_mont"][i] == O.f_op("from_mont", which, a)
+        if a and i < 40:
+            assert ref["inv"][i] == O.f_op("inv", which, a)
     # operands >= q in the top limb (unreduced inputs, as fromMpz can hand to toMontgomery)
-    if O.ref is not None:
-        for a in (mod, mod + 5, (1 << 256) - 1, (1 << 255) + 12345):
-            assert O.ref_op(name, "to_mont", a) == O.f_op("to_mont", which, a)
+    unreduced = [mod, mod + 5, (1 << 256) - 1, (1 << 255) + 12345]
+    assert _ints(ref_vectors[name + "_unreduced"]) == unreduced
+    for a, want in zip(unreduced, _ints(ref_vectors[name + "_unreduced_to_mont"])):
+        assert want == O.f_op("to_mont", which, a)
 
 
 @pytest.mark.parametrize("which,mod", [(O.FR, O.R_MOD), (O.FQ, O.Q_MOD)])
@@ -145,37 +162,37 @@ def test_keccak256_vectors():
     assert O.keccak256(b"abc").hex() == "4e03657aea45a94fc7d47ba826c8d667c0d1e6e33a64a036ec44f58fa12d6c45"
 
 
-needs_ref = pytest.mark.skipif(O.ref is None or not hasattr(O.ref, "ref_lookup_row"), reason="oracle/_ref (reference field layer) not built")
-
-
-@needs_ref
-def test_lookup_row_against_the_reference_overloads():
+def test_lookup_row_against_the_reference_overloads(ref_vectors):
     """compute_lookup's table row (src/ultra_groth.cpp:72-79) against the reference's own RawFr: `frequencies[i]` is a
     uint32_t that binds to mul(int, Element) (build/fr.hpp:251), so values >= 2^31 enter as freq - 2^32 + r"""
     rng = random.Random(77)
     R = 1 << 256
+    ref_inv, ref_prod = _ints(ref_vectors["lookup_inv"]), _ints(ref_vectors["lookup_prod"])
+    ref_in = list(zip(ref_vectors["lookup_i"].tolist(), ref_vectors["lookup_f"].tolist(), _ints(ref_vectors["lookup_rand"])))
+    assert len(ref_in) == 61
     for t in range(60):
         rand = rng.randrange(O.R_MOD)
         i = rng.choice([0, 1, 2, 255, 65535, rng.randrange(1 << 20)])
         f = rng.choice([0, 1, 7, (1 << 31) - 1, 1 << 31, (1 << 31) + 5, (1 << 32) - 1, rng.randrange(1 << 32)])
+        assert ref_in[t] == (i, f, rand * R % O.R_MOD)
         got = O.lookup_row(i, f, rand * R % O.R_MOD)
-        assert got == O.ref_lookup_row(i, f, rand * R % O.R_MOD)
+        assert got == (ref_inv[t], ref_prod[t])
         s = (i + rand) % O.R_MOD
         inv = pow(s, -1, O.R_MOD) if s else 0
         signed = f - (1 << 32) if f >= (1 << 31) else f
         assert got == (inv, signed * inv % O.R_MOD)
     # i + rand = 0: mpz_invert leaves 0, and so do we
-    assert O.lookup_row(5, 9, (O.R_MOD - 5) * R % O.R_MOD) == O.ref_lookup_row(5, 9, (O.R_MOD - 5) * R % O.R_MOD) == (0, 0)
+    assert ref_in[60] == (5, 9, (O.R_MOD - 5) * R % O.R_MOD)
+    assert O.lookup_row(5, 9, (O.R_MOD - 5) * R % O.R_MOD) == (ref_inv[60], ref_prod[60]) == (0, 0)
 
 
-@needs_ref
-def test_derive_challenge_against_the_reference_code(zkey):
+def test_derive_challenge_against_the_reference_code(zkey, ref_vectors):
     """derive_challenge (src/ultra_groth.cpp:33-58): big-endian x || y, the reference's Keccak-256, reduction mod r"""
     a = _sec(zkey, "zkey", 5)
-    for k in range(0, 400, 7):
+    ks = [k for k in range(0, 400, 7) if a[64 * k:64 * k + 64] != bytes(64)]
+    assert ref_vectors["challenge_k"].tolist() == ks
+    for k, want in zip(ks, _ints(ref_vectors["challenge"])):
         rec = a[64 * k:64 * k + 64]
-        if rec == bytes(64):
-            continue
         x, y = O.mont_decode(rec[:32]), O.mont_decode(rec[32:])
         exp = int.from_bytes(O.keccak256(x.to_bytes(32, "big") + y.to_bytes(32, "big")), "big") % O.R_MOD
-        assert O.derive_challenge(rec) == O.ref_derive_challenge(rec) == exp
+        assert O.derive_challenge(rec) == want == exp
