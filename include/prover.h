@@ -134,6 +134,11 @@ int ug_prover_last_upload_ms(void *prover_object, double *upload_ms);
  * 1 = the tables are in use (or the prover has none to wait for), 0 = still being built; wait != 0 blocks until they are;
  * -1 = error. ULTRAGROTH_TABLES_BG=0 makes create wait as it did before. */
 int ug_prover_tables_ready(void *prover_object, int wait);
+/* The window-table plan of a created prover's schedule group `group` (0 = witness, 1 = H; a Groth16 prover with sparse B has a
+ * group 2 for B1 / B2; an UltraGroth prover has 0 = witness, 1 = first-round aux, 2 = final aux, 3 = H): *c = window width
+ * (0: classic windows), *stride, *bytes = the additional memory its tables take, *ready = 1 once the proofs use them.
+ * ULTRAGROTH_TABLES_BUDGET caps the sum of the bytes. Returns PROVER_ERROR for a group the prover does not have. */
+int ug_prover_table_plan(void *prover_object, int group, int *c, int *stride, unsigned long long *bytes, int *ready);
 
 /* ---- resident multi-circuit prover ---------------------------------------------------------------------
  * The GPU form of FullProver's map<circuit, Prover> (src/fullprover.cpp:21-63; its HTTP shell and witness calculator

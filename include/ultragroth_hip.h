@@ -35,6 +35,9 @@
  *                      ULTRAGROTH_TABLES=0|1|2    fixed-base window tables: never | created provers (default) | one-shot calls too
  *                      ULTRAGROTH_OVERLAP=0|1|2   H branch behind / beside (default since round 5) the witness products on one device
  *                                                 (0: one kernel on the chip at a time, for clean per-kernel times)
+ *                      ULTRAGROTH_TABLES_BUDGET=g  the most HBM, in GiB, the window tables of a created prover may take (unset: the
+ *                                                 free memory less the workspace reserve; 0 acts like ULTRAGROTH_TABLES=0). Below what
+ *                                                 full tables take, ug_plan_window_tables picks strided tables or none per group
  *                      ULTRAGROTH_TABLES_BG=0     groth16_prover_create waits for its window tables (default: returns once the zkey is
  *                                                 resident; the tables are built in pieces between proofs, include/prover.h)
  *                      ULTRAGROTH_GRAPH=1         the device part of a created prover's proof recorded once per witness buffer and
@@ -124,6 +127,29 @@ int      ug_bases_precompute(ug_bases* b, int c);
 /* give the tables' memory back (the set keeps its n points; schedules must then be built without tables) */
 int      ug_bases_drop_tables(ug_bases* b);
 int      ug_bases_table_window(const ug_bases* b);          /* width of the tables held, 0 = none */
+/* STRIDED TABLES: with stride s in [1, W], W = ceil(255/c), a set holds T = ceil(W/s) tables 2^(s c j) * P_i, j < T. A digit of
+ * window w goes to bucket set w mod s and reads table w / s (d 2^(c w) P = 2^(c (w mod s)) (d T_(w/s))): s bucket sets per product,
+ * combined on the host by a Horner of s steps. s = 1 is the plain table form above; s = W is one table (the points alone) at the
+ * table-mode widths. A schedule of ug_schedule_build_tables_strided(.., c, s) needs bases of the same width AND stride, and no
+ * bucket classes (they need one bucket set per product). ug_bases_tables_bytes_strided: the additional memory (T - 1) n records;
+ * ug_bases_table_stride: the stride of the tables held, 0 = none. The plain calls are the s = 1 case. */
+int      ug_bases_create_tables_strided_g1(ug_ctx* ctx, const void* host_points, uint64_t n, uint64_t global_first, int table_c, int stride,
+                                           ug_bases** out);
+int      ug_bases_create_tables_strided_g2(ug_ctx* ctx, const void* host_points, uint64_t n, uint64_t global_first, int table_c, int stride,
+                                           ug_bases** out);
+int      ug_bases_precompute_strided(ug_bases* b, int c, int stride);
+uint64_t ug_bases_tables_bytes_strided(uint64_t n, int g2, int c, int stride);
+int      ug_bases_table_stride(const ug_bases* b);
+/* WINDOW-TABLE PLAN (host only, no device needed): one entry per group of base sets that share a schedule -- its scalars per
+ * schedule and the points of its G1 and G2 sets. A group qualifies with 2^14 <= scalars <= 2^26. When full tables for every
+ * qualifying group fit budget_bytes, every such group gets c = ug_msm_table_window(scalars), stride 1. Otherwise each group gets
+ * none (c = 0, stride 0) or one (c, stride), the choice that minimises the summed modelled MSM cost (G2 products weighted by their
+ * cost against G1) within the budget; scalars * W <= 2^30 and stride * 2^(c-1) <= 2^24 buckets per product hold for every
+ * choice. bytes: the additional memory of the group's
+ * tables. Deterministic; the sum of the bytes never exceeds the budget. */
+typedef struct { uint64_t scalars, g1_points, g2_points; } ug_table_group;
+typedef struct { int c, stride; uint64_t bytes; } ug_table_choice;
+int      ug_plan_window_tables(const ug_table_group* groups, int n_groups, uint64_t budget_bytes, ug_table_choice* out);
 /* DEFERRED TABLE BUILDS (cold start of a created prover): after ug_ctx_defer_tables(ctx, 1) the sets made by
  * ug_bases_create_tables_* / ug_bases_create_group_g1 on this context hold their points only and remember the width: nothing
  * is queued, not even the tables' memory is allocated. ug_bases_tables_step(set, max_points, &remaining) builds the tables of the next max_points points on the
@@ -195,6 +221,8 @@ int  ug_ctx_trim(ug_ctx* ctx);
 int  ug_schedule_build(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count);
 /* the same for base sets that hold window tables of width c (ug_bases_precompute); count <= 2^27 */
 int  ug_schedule_build_tables(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int c);
+/* ... for strided tables of width c and stride s (ug_bases_create_tables_strided_g1) */
+int  ug_schedule_build_tables_strided(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int c, int stride);
 /* BUCKET CLASSES (a many-device prover that shards the witness products by bucket instead of by base point; DESIGN.md section 7,
  * no counterpart in the reference): every later build of the schedule keeps only the (scalar, window) digits whose bucket
  * b = |digit| - 1 has b mod 2^q_log in [first_residue, first_residue + residues) -- except the lowest `specials` (<= 64) bucket ids
@@ -233,6 +261,9 @@ int  ug_msm_batch_enqueue(ug_ctx* ctx, int count, const ug_bases* const* bases, 
  * group's. ug_bases_destroy / _precompute / _drop_tables / _table_window accept a group. */
 int  ug_bases_create_group_g1(ug_ctx* ctx, int members, const void* const* host_points, const uint64_t* n, const uint64_t* first,
                               uint64_t group_first, uint64_t slots, int table_c, ug_bases** out);
+/* ... with strided tables (stride in [1, ceil(255 / table_c)]) */
+int  ug_bases_create_group_strided_g1(ug_ctx* ctx, int members, const void* const* host_points, const uint64_t* n, const uint64_t* first,
+                                      uint64_t group_first, uint64_t slots, int table_c, int stride, ug_bases** out);
 int  ug_bases_members(const ug_bases* bases);
 /* 1 when every one of the n records of `record_bytes` bytes at host_points is the point at infinity (all zero): such a set's products
  * are the point at infinity, no kernel runs for them (ug_bases_create_* mark the set themselves), and a prover keeps it out of a

@@ -220,6 +220,16 @@ class _ProverBase:
             raise ProverError(PROVER_ERROR, "ug_prover_tables_ready failed")
         return rc == 1
 
+    def table_plan(self):
+        """ug_prover_table_plan for every schedule group of the prover: a list of (c, stride, bytes, ready) -- c = 0: classic
+        windows; ready: the proofs use the tables"""
+        L, plan, g = load(), [], 0
+        c, st, b, r = C.c_int(), C.c_int(), C.c_ulonglong(), C.c_int()
+        while L.ug_prover_table_plan(self._h, g, C.byref(c), C.byref(st), C.byref(b), C.byref(r)) == PROVER_OK:
+            plan.append((c.value, st.value, b.value, bool(r.value)))
+            g += 1
+        return plan
+
     def close(self):
         if getattr(self, "_h", None):
             getattr(load(), self._destroy)(self._h)
@@ -598,6 +608,29 @@ class ShardedUltraGrothProver(ShardedGroth16Prover):
 # ---------------------------------------------------------------------------------------------------
 # inner ABI (include/ultragroth_hip.h)
 
+class _TableGroup(C.Structure):
+    _fields_ = [("scalars", C.c_uint64), ("g1_points", C.c_uint64), ("g2_points", C.c_uint64)]
+
+
+class _TableChoice(C.Structure):
+    _fields_ = [("c", C.c_int), ("stride", C.c_int), ("bytes", C.c_uint64)]
+
+
+def tables_bytes(n, g2, c, stride=1):
+    """ug_bases_tables_bytes_strided: the device memory window tables of width c and this stride add to n points"""
+    return load().ug_bases_tables_bytes_strided(n, 1 if g2 else 0, c, stride)
+
+
+def plan_window_tables(groups, budget):
+    """ug_plan_window_tables (host only): groups = [(scalars, g1_points, g2_points), ...] -> [(c, stride, bytes), ...] within
+    `budget` bytes (c = 0: classic windows)"""
+    k = len(groups)
+    arr = (_TableGroup * max(k, 1))(*[_TableGroup(*g) for g in groups])
+    out = (_TableChoice * max(k, 1))()
+    _check(load().ug_plan_window_tables(arr, k, budget, out))
+    return [(out[i].c, out[i].stride, out[i].bytes) for i in range(k)]
+
+
 class Device:
     """A ug_ctx plus convenience wrappers in the reference's byte formats."""
 
@@ -618,17 +651,21 @@ class Device:
             pass
 
     # -- raw handles
-    def bases(self, points, n, g2=False, global_first=0, table_c=0):
-        """table_c: also precompute the fixed-base window tables of that width (ug_bases_precompute)"""
+    def bases(self, points, n, g2=False, global_first=0, table_c=0, table_stride=1):
+        """table_c: also precompute the fixed-base window tables of that width (ug_bases_precompute; with table_stride > 1
+        the strided tables of ug_bases_precompute_strided)"""
         h = C.c_void_p()
         fn = self._L.ug_bases_create_g2 if g2 else self._L.ug_bases_create_g1
         _check(fn(self._h, points, n, global_first, C.byref(h)))
         b = _Handle(h, self._L.ug_bases_destroy, self)
         if table_c:
-            _check(self._L.ug_bases_precompute(h, table_c))
+            if table_stride == 1:
+                _check(self._L.ug_bases_precompute(h, table_c))
+            else:
+                _check(self._L.ug_bases_precompute_strided(h, table_c, table_stride))
         return b
 
-    def bases_group(self, members, group_first, slots, table_c=0):
+    def bases_group(self, members, group_first, slots, table_c=0, table_stride=1):
         """ug_bases_create_group_g1: members = [(points bytes, n, first scalar index), ...] (2 or 3 G1 sets sharing their scalars)"""
         k = len(members)
         keep = [_buf(bytes(p)) if not isinstance(p, C.Array) else p for p, _, _ in members]
@@ -636,7 +673,11 @@ class Device:
         ns = (C.c_uint64 * k)(*[n for _, n, _ in members])
         firsts = (C.c_uint64 * k)(*[f for _, _, f in members])
         h = C.c_void_p()
-        _check(self._L.ug_bases_create_group_g1(self._h, k, hosts, ns, firsts, group_first, slots, table_c, C.byref(h)))
+        if table_stride == 1:
+            _check(self._L.ug_bases_create_group_g1(self._h, k, hosts, ns, firsts, group_first, slots, table_c, C.byref(h)))
+        else:
+            _check(self._L.ug_bases_create_group_strided_g1(self._h, k, hosts, ns, firsts, group_first, slots, table_c, table_stride,
+                                                            C.byref(h)))
         g = _Handle(h, self._L.ug_bases_destroy, self)
         g.members = k
         return g
@@ -669,14 +710,17 @@ class Device:
         c = np.ascontiguousarray(chunks, dtype=np.uint32)
         _check(self._L.ug_dvec_apply_lookup(dvec.h, w.ctypes.data, p.ctypes.data, len(w), c.ctypes.data, len(c), table, lookup_size))
 
-    def schedule(self, dvec, first, count, table_c=0, classes=None):
-        """classes (ug_schedule_set_classes): (q_log, first_residue, residues, specials, special_first, special_count)"""
+    def schedule(self, dvec, first, count, table_c=0, classes=None, table_stride=1):
+        """classes (ug_schedule_set_classes): (q_log, first_residue, residues, specials, special_first, special_count);
+        table_c / table_stride: a schedule for (strided) window tables"""
         h = C.c_void_p()
         _check(self._L.ug_schedule_create(self._h, C.byref(h)))
         s = _Handle(h, self._L.ug_schedule_destroy, self)
         if classes is not None:
             _check(self._L.ug_schedule_set_classes(h, *classes))
-        if table_c:
+        if table_c and table_stride != 1:
+            _check(self._L.ug_schedule_build_tables_strided(h, dvec.h, first, count, table_c, table_stride))
+        elif table_c:
             _check(self._L.ug_schedule_build_tables(h, dvec.h, first, count, table_c))
         else:
             _check(self._L.ug_schedule_build(h, dvec.h, first, count))
@@ -684,6 +728,9 @@ class Device:
 
     def table_window(self, n):
         return self._L.ug_msm_table_window(n)
+
+    def tables_bytes(self, n, g2, c, s=1):
+        return tables_bytes(n, g2, c, s)
 
     def mem_info(self):
         f, t = C.c_uint64(), C.c_uint64()

@@ -27,6 +27,9 @@ INNER_SYMBOLS = [
     "ug_bases_drop_tables", "ug_bases_table_window", "ug_schedule_trim", "ug_ctx_trim",
     "ug_ctx_defer_tables", "ug_bases_tables_alloc", "ug_bases_tables_adopt", "ug_bases_tables_step", "ug_bases_tables_ready",
     "ug_graph_begin", "ug_graph_end", "ug_graph_abort", "ug_graph_valid", "ug_graph_nodes", "ug_graph_launch", "ug_graph_destroy",
+    "ug_bases_create_tables_strided_g1", "ug_bases_create_tables_strided_g2", "ug_bases_create_group_strided_g1",
+    "ug_bases_precompute_strided", "ug_schedule_build_tables_strided", "ug_bases_tables_bytes_strided", "ug_bases_table_stride",
+    "ug_plan_window_tables",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify"]        # include/verifier.h
 OUTER_SYMBOLS = [
@@ -42,6 +45,7 @@ OUTER_SYMBOLS = [
     "ug_registry_create", "ug_registry_load", "ug_registry_load_file", "ug_registry_prove", "ug_registry_evict", "ug_registry_info",
     "ug_registry_destroy",
     "ug_test_set_blinding", "ug_prover_last_timings", "ug_prover_kernel_stats", "ug_prover_last_upload_ms", "ug_prover_tables_ready",
+    "ug_prover_table_plan",
     "ug_groth16_prover_create_sharded", "ug_groth16_prover_create_sharded_range", "ug_groth16_prover_create_sharded_slices",
     "ug_groth16_shard_ranges", "ug_groth16_balanced_witness_range", "ug_groth16_prover_load_witness_part",
     "ug_groth16_shard_layout", "ug_groth16_prover_create_sharded_layout",
@@ -134,6 +138,15 @@ def load():
     L.ug_bases_precompute.argtypes = [vp, C.c_int]
     L.ug_ctx_mem_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.ug_schedule_build_tables.argtypes = [vp, vp, u64, u64, C.c_int]
+    for n in ("ug_bases_create_tables_strided_g1", "ug_bases_create_tables_strided_g2"):
+        getattr(L, n).argtypes = [vp, vp, u64, u64, C.c_int, C.c_int, pp]
+    L.ug_bases_create_group_strided_g1.argtypes = [vp, C.c_int, vp, vp, vp, u64, u64, C.c_int, C.c_int, pp]
+    L.ug_bases_precompute_strided.argtypes = [vp, C.c_int, C.c_int]
+    L.ug_schedule_build_tables_strided.argtypes = [vp, vp, u64, u64, C.c_int, C.c_int]
+    L.ug_bases_tables_bytes_strided.argtypes = [u64, C.c_int, C.c_int, C.c_int]; L.ug_bases_tables_bytes_strided.restype = u64
+    L.ug_bases_table_window.argtypes = [vp]
+    L.ug_bases_table_stride.argtypes = [vp]
+    L.ug_plan_window_tables.argtypes = [vp, C.c_int, u64, vp]
     L.ug_dvec_create.argtypes = [vp, u64, pp]
     L.ug_dvec_upload.argtypes = [vp, vp, u64]
     L.ug_dvec_upload_idle.argtypes = [vp, vp, u64]
@@ -191,6 +204,7 @@ def load():
     L.ug_prover_kernel_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_double), pull, pull, C.c_int]
     L.ug_prover_last_upload_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.ug_prover_tables_ready.argtypes = [vp, C.c_int]
+    L.ug_prover_table_plan.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), pull, C.POINTER(C.c_int)]
     L.ug_registry_create.argtypes = [pp, C.c_int, ull, vp, ull]
     L.ug_registry_load.argtypes = [vp, C.c_char_p, vp, ull, vp, ull]
     L.ug_registry_load_file.argtypes = [vp, C.c_char_p, vp, ull]

@@ -83,6 +83,8 @@ constexpr u32 MSM_MAX_SPECIALS = 64;     // (one wave sums a window's special bu
 // How a scalar's window digits become (bucket key, entry) pairs: the kernel argument of the digit-making kernels (sort.hip)
 struct DigitPlan {
     u64 n; int c, windows; u32 buckets, sentinel; int tables;      // buckets: per set; sentinel = total_buckets(): the key of a digit that is not kept
+    u64 set_map, table_map;                                        // window tables: digit w goes to bucket set w mod stride and reads
+                                                                   // table w / stride -- 4-bit field w of each map (<= 16 windows)
     int q_log; u32 r0, cnt, specials, sp_lo, sp_hi, special_base;  // bucket classes (q_log = 0: none); special_base = first special bucket id
 };
 
@@ -93,12 +95,16 @@ struct MsmGeometry {
     u32 buckets = 0;    // per bucket set: 2^(c-1), with classes 2^(c-1-q_log)
     bool tables = false;  // fixed-base window tables: digit j of scalar i multiplies 2^(c j) P_i, read from table j, so
                           // every digit of every window lands in ONE bucket set (no Horner, 1/windows of the reduction)
+    int stride = 1;       // strided tables (tables mode): table j holds 2^(stride c j) P_i, T = ceil(windows / stride) of them; digit w
+                          // goes to bucket set w mod stride and reads table w / stride, since d 2^(c w) P = 2^(c (w mod s)) (d T_(w / s)):
+                          // `stride` bucket sets, a Horner of `stride` steps on the host. stride = 1: one set; stride = windows: one table
     BucketClasses cls;
     static MsmGeometry choose(u64 n, int force_c = 0);
-    static MsmGeometry choose_tables(u64 n, int c);
+    static MsmGeometry choose_tables(u64 n, int c, int stride = 1);   // validates 1 <= stride <= windows
     static int table_window(u64 n);                                    // cost-model window width for the tables mode
+    static int table_count(int c, int stride) { const int w = (255 + c - 1) / c; return (w + stride - 1) / stride; }
     void set_classes(const BucketClasses& k);                          // after choose / choose_tables (divides `buckets`)
-    int window_sets() const { return tables ? 1 : windows; }           // Horner steps on the host
+    int window_sets() const { return tables ? stride : windows; }      // Horner steps on the host
     int class_sets() const { return cls.on() ? (int)cls.cnt : 1; }
     int bucket_windows() const { return window_sets() * class_sets(); }      // bucket sets the reduction sees: set (w, j) = w * class_sets + j
     u64 special_buckets() const { return cls.on() ? (u64)window_sets() * cls.specials : 0; }     // ids behind the regular sets
@@ -110,6 +116,9 @@ struct MsmGeometry {
     DigitPlan digit_plan() const {
         DigitPlan d;
         d.n = n; d.c = c; d.windows = windows; d.buckets = buckets; d.sentinel = (u32)total_buckets(); d.tables = tables ? 1 : 0;
+        d.set_map = 0; d.table_map = 0;
+        if (tables)
+            for (int w = 0; w < windows && w < 16; w++) { d.set_map |= (u64)(w % stride) << (4 * w); d.table_map |= (u64)(w / stride) << (4 * w); }
         d.q_log = cls.q_log; d.r0 = cls.r0; d.cnt = cls.on() ? cls.cnt : 1; d.specials = cls.on() ? cls.specials : 0;
         d.sp_lo = cls.sp_lo; d.sp_hi = cls.sp_hi; d.special_base = (u32)((u64)bucket_windows() * buckets);
         return d;
@@ -117,6 +126,9 @@ struct MsmGeometry {
 };
 constexpr int TABLE_INDEX_BITS = 27;                                   // entry = index | table << 27 | sign << 31
 constexpr int TABLE_MIN_C = 16, TABLE_MAX_C = 24;                      // <= 16 tables (4 bits), <= 2^23 buckets
+// Modelled cost of one MSM of n scalars in mixed additions (msm.hip): classic windows (tables = false), or window tables of
+// width c and the given stride
+double msm_model_cost(u64 n, int c, bool tables, int stride = 1);
 
 struct HeavyBucket { u32 bucket, first_seg, last_seg, pad; };  // a bucket cut into many segment pieces
 
@@ -247,9 +259,10 @@ G2XYZZ msm_g2(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_ba
 void convert_points_g1(u32* pts, u64 n, hipStream_t stream);
 void convert_points_g2(u32* pts, u64 n, hipStream_t stream);
 
-// pts = `tables` tables of n records, table 0 filled: table j = 2^(c j) * table 0 (fixed-base window tables)
+// pts = `tables` tables of n records, table 0 filled: table j = 2^(doublings j) * table 0 (fixed-base window tables: doublings =
+// stride * c)
 // (first, count: only the tables of the points [first, first + count) -- one piece of a deferred build; default: all of them)
-void build_window_tables(bool g2, u32* pts, u64 n, int c, int tables, hipStream_t stream, u64 first = 0, u64 count = ~(u64)0);
+void build_window_tables(bool g2, u32* pts, u64 n, int doublings, int tables, hipStream_t stream, u64 first = 0, u64 count = ~(u64)0);
 
 // bench / test tooling: out[i] = (seed + i) * G as zkey-format records (device buffer); G given as a host record
 void synth_points(bool g2, u32* out_dev, const u32* gen_record_host, u64 seed, u64 n, hipStream_t stream);

@@ -22,7 +22,7 @@
 //      bucket_fixup / medium_bucket / heavy_partial + heavy_final   add the pieces of cut buckets (a lane, a wave or
 //                            workgroup tasks per bucket: witnesses are full of 0/1 values, i.e. million-entry buckets)
 //   6. bucket_chunk_reduce   running-sum trick on chunks of up to 32 buckets + ec_sum_groups / ec_sum_wave tree
-//   7. host                  Horner over the window sums (none with window tables), affine conversion
+//   7. host                  Horner over the window sums (none with window tables, `stride` steps with strided ones), affine conversion
 // Steps 5b-6 run once for all products of a curve queued together (msm_enqueue_multi).
 //
 // Arithmetic volume dominates: each of the n * windows gathered bases costs one mixed addition
@@ -34,6 +34,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include "dev_common.hpp"
 #include "internal.hpp"
 #include "segmap.hpp"
@@ -677,8 +678,8 @@ __global__ void interleave_records_kernel(u32* __restrict__ dst, const u32* __re
 }
 
 // ---- fixed-base window tables ------------------------------------------------------------------------------
-// pts holds `tables` tables of n affine records; table 0 is given, table j = 2^(c j) * table 0. A lane carries K
-// consecutive points through c doublings per table and shares one field inversion among them for the conversion
+// pts holds `tables` tables of n affine records; table 0 is given, table j = 2^(c j) * table 0 (c: the doublings between two
+// tables, stride * window width for strided tables). A lane carries K consecutive points through c doublings per table and shares one field inversion among them for the conversion
 // back to affine (Montgomery's trick); infinity stays (0,0) in every table.
 // (the launch covers the points [first, end) of the n: a whole set at once, or one piece of a deferred build)
 template <class Cfg, int K>
@@ -782,14 +783,18 @@ int segment_log(u64 total_entries) {
 // when the average bucket is longer than a lane's segment -- such buckets are cut into pieces that a single lane adds
 // up afterwards (measured at 2^20..2^24 with tools/run_tablec.sh: +4 % of the entry cost per segment length by which
 // the average bucket exceeds one segment; e.g. 2^22, c = 20 -> 22: 48.2 -> 45.9 ms per proof).
-double msm_cost(u64 n, int c, bool tables) {
+// Strided tables (stride s): s bucket sets, each with 1/s of the entries.
+double msm_cost(u64 n, int c, bool tables, int stride = 1) {
     const int windows = (255 + c - 1) / c;
     const double entries = (double)windows * (double)n, buckets = (double)((u64)1 << (c - 1));
-    const double per_bucket = (tables ? entries : (double)n) / buckets;
+    const double sets = tables ? (double)stride : (double)windows;
+    const double per_bucket = entries / (sets * buckets);
     const double over = per_bucket / (double)((u64)1 << segment_log((u64)entries)) - 1.0;
-    return entries * (1.0 + (over > 0 ? 0.04 * over : 0.0)) + 4.0 * buckets * (tables ? 1.0 : (double)windows);
+    return entries * (1.0 + (over > 0 ? 0.04 * over : 0.0)) + 4.0 * buckets * sets;
 }
 }  // namespace
+
+double msm_model_cost(u64 n, int c, bool tables, int stride) { return msm_cost(n, c, tables, stride); }
 
 MsmGeometry MsmGeometry::choose(u64 n, int force_c) {
     MsmGeometry g;
@@ -828,12 +833,15 @@ int MsmGeometry::table_window(u64 n) {
     }
     return c;
 }
-MsmGeometry MsmGeometry::choose_tables(u64 n, int c) {
+MsmGeometry MsmGeometry::choose_tables(u64 n, int c, int stride) {
     if (c < TABLE_MIN_C || c > TABLE_MAX_C) throw std::invalid_argument("msm: table window width outside [16, 24]");
     MsmGeometry g;
     g.n = n; g.c = c; g.tables = true;
     g.windows = (255 + c - 1) / c;
     g.buckets = 1u << (c - 1);
+    if (stride < 1 || stride > g.windows)
+        throw std::invalid_argument("msm: table stride " + std::to_string(stride) + " outside [1, " + std::to_string(g.windows) + "]");
+    g.stride = stride;
     return g;
 }
 
@@ -841,6 +849,7 @@ void MsmGeometry::set_classes(const BucketClasses& k) {
     cls = BucketClasses();
     if (!k.on()) return;
     if (k.q_log > 8) throw std::invalid_argument("msm: more than 256 bucket classes");
+    if (tables && stride > 1) throw std::invalid_argument("msm: bucket classes need one bucket set per product (table stride 1)");
     const u32 Q = 1u << k.q_log;
     if (k.cnt < 1 || k.r0 + k.cnt > Q) throw std::invalid_argument("msm: bucket residues outside [0, 2^q_log)");
     if (k.specials > MSM_MAX_SPECIALS) throw std::invalid_argument("msm: more than 64 special buckets");
@@ -1313,15 +1322,15 @@ void synth_points(bool g2, u32* out_dev, const u32* gen_record_host, u64 seed, u
     else synth_points_run<G1Cfg>(out_dev, gen_record_host, seed, n, stream);
 }
 
-void build_window_tables(bool g2, u32* pts, u64 n, int c, int tables, hipStream_t stream, u64 first, u64 count) {
+void build_window_tables(bool g2, u32* pts, u64 n, int doublings, int tables, hipStream_t stream, u64 first, u64 count) {
     if (!n || tables < 2) return;
     if (first > n) first = n;
     const u64 end = count > n - first ? n : first + count, m = end - first;
     if (!m) return;
     if (g2) {
-        hipLaunchKernelGGL((window_tables_kernel<G2Cfg, 2>), dim3((unsigned)(((m + 1) / 2 + 127) / 128)), dim3(128), 0, stream, pts, n, c, tables, first, end);
+        hipLaunchKernelGGL((window_tables_kernel<G2Cfg, 2>), dim3((unsigned)(((m + 1) / 2 + 127) / 128)), dim3(128), 0, stream, pts, n, doublings, tables, first, end);
     } else {
-        hipLaunchKernelGGL((window_tables_kernel<G1Cfg, 4>), dim3((unsigned)(((m + 3) / 4 + 127) / 128)), dim3(128), 0, stream, pts, n, c, tables, first, end);
+        hipLaunchKernelGGL((window_tables_kernel<G1Cfg, 4>), dim3((unsigned)(((m + 3) / 4 + 127) / 128)), dim3(128), 0, stream, pts, n, doublings, tables, first, end);
     }
     UG_KERNEL_CHECK();
 }

@@ -255,6 +255,7 @@ struct DeviceProver {
     ug_dvec* wB = nullptr;
     ug_schedule* sB = nullptr;
     int tableB = 0;              // window width of the compacted sets' tables (0: classic windows)
+    int strideB = 1;             // ... and their stride
     ug_hpoly* hp = nullptr;
     ug_dvec *w = nullptr, *h = nullptr, *aux = nullptr;
     ug_dvec* w2 = nullptr;       // second witness buffer (Groth16): the next proof's witness is staged here while a proof runs
@@ -346,12 +347,17 @@ struct WitnessLease {
 // sets that share one schedule (they must share the window width). Tables are built when ULTRAGROTH_TABLES is not
 // "0", a group has at least 2^14 scalars (below that the classic windows are cheaper) and everything fits the free
 // device memory with room left for schedules, buckets and NTT vectors; otherwise the classic path runs.
+// A created prover on one device (not a rank, not the registry, not a one-shot call) goes further when full tables do not fit
+// (or exceed ULTRAGROTH_TABLES_BUDGET): ug_plan_window_tables gives each group strided tables or none, whichever the cost
+// model prefers within the budget.
 struct TableGroup {
     std::vector<ug_bases*> g1, g2;     // sets of the group with their point counts
     std::vector<uint64_t> n1, n2;
     uint64_t scalars = 0;              // scalars per schedule
     int* c = nullptr;                  // out: window width, 0 = classic
+    int* stride = nullptr;             // out: table stride (1 unless the plan is strided)
 };
+struct TableChoice { int c = 0, stride = 1; };
 constexpr uint64_t TABLES_MIN_SCALARS = (uint64_t)1 << 14, TABLES_MAX_SCALARS = (uint64_t)1 << 26;
 
 thread_local bool g_oneShotProver = false;      // create + one prove + destroy (groth16_prover, the CLIs): tables cannot pay
@@ -377,10 +383,57 @@ uint64_t tablesNeed(const std::vector<TableGroup>& groups, std::vector<int>& wid
     if (workspaceOut) *workspaceOut = workspace;
     return need;
 }
+// ULTRAGROTH_TABLES_BUDGET=<GiB>: the most a created prover's tables may take (~0: unset)
+uint64_t tablesBudgetFromEnv() {
+    const char* e = getenv("ULTRAGROTH_TABLES_BUDGET");
+    if (!e || !e[0]) return ~(uint64_t)0;
+    const double gib = atof(e);
+    return gib <= 0 ? 0 : (uint64_t)(gib * (double)((uint64_t)1 << 30));
+}
+// what the bucket arrays of a strided plan may take beyond the schedule workspace: up to 2^24 buckets per product
+// (ug_plan_window_tables), 144 bytes per G1 bucket, 288 per G2 bucket, for every qualifying group
+uint64_t stridedBucketReserve(const std::vector<TableGroup>& groups) {
+    uint64_t r = 0;
+    for (const TableGroup& g : groups) {
+        if (g.scalars < TABLES_MIN_SCALARS || g.scalars > TABLES_MAX_SCALARS) continue;
+        uint64_t p1 = 0, p2 = 0;
+        for (uint64_t n : g.n1) p1 += n;
+        for (uint64_t n : g.n2) p2 += n;
+        r += ((uint64_t)1 << 24) * (144 * ((p1 + g.scalars - 1) / g.scalars) + 288 * ((p2 + g.scalars - 1) / g.scalars));
+    }
+    return r;
+}
+// the strided plan of ug_plan_window_tables for these groups within `budget` bytes
+std::vector<TableChoice> planStrided(const std::vector<TableGroup>& groups, uint64_t budget) {
+    std::vector<ug_table_group> in(groups.size());
+    std::vector<ug_table_choice> out(groups.size());
+    for (size_t k = 0; k < groups.size(); k++) {
+        in[k].scalars = groups[k].scalars; in[k].g1_points = 0; in[k].g2_points = 0;
+        for (uint64_t n : groups[k].n1) in[k].g1_points += n;
+        for (uint64_t n : groups[k].n2) in[k].g2_points += n;
+    }
+    if (!groups.empty()) ugCheck(ug_plan_window_tables(in.data(), (int)in.size(), budget, out.data()));
+    std::vector<TableChoice> plan(groups.size());
+    for (size_t k = 0; k < groups.size(); k++) if (out[k].c) { plan[k].c = out[k].c; plan[k].stride = out[k].stride; }
+    return plan;
+}
+void tracePlan(const std::vector<TableGroup>& groups, const std::vector<TableChoice>& plan, uint64_t budget) {
+    static const bool on = getenv("ULTRAGROTH_TRACE") && atoi(getenv("ULTRAGROTH_TRACE")) != 0;
+    if (!on) return;
+    for (size_t k = 0; k < plan.size(); k++) {
+        uint64_t bytes = 0;
+        for (uint64_t n : groups[k].n1) bytes += ug_bases_tables_bytes_strided(n, 0, plan[k].c, plan[k].stride);
+        for (uint64_t n : groups[k].n2) bytes += ug_bases_tables_bytes_strided(n, 1, plan[k].c, plan[k].stride);
+        fprintf(stderr, "[tables] group %zu: %llu scalars, c = %d, stride = %d, %.2f GiB (budget %.2f GiB)\n", k,
+                (unsigned long long)groups[k].scalars, plan[k].c, plan[k].c ? plan[k].stride : 0, (double)bytes / (double)((uint64_t)1 << 30),
+                budget == ~(uint64_t)0 ? -1.0 : (double)budget / (double)((uint64_t)1 << 30));
+    }
+}
 // builds the tables when the environment allows them and `need + workspace` fits the free device memory and `limit`
-// (bytes the caller is ready to spend, ~0 = no limit of its own); returns the bytes taken (0: classic windows stay)
-uint64_t planWindowTables(ug_ctx* ctx, std::vector<TableGroup>& groups, uint64_t limit = ~(uint64_t)0, bool force = false) {
-    for (auto& g : groups) *g.c = 0;
+// (bytes the caller is ready to spend, ~0 = no limit of its own); returns the bytes taken (0: classic windows stay).
+// strided: the created prover's plan (ug_plan_window_tables within min(free - workspace, ULTRAGROTH_TABLES_BUDGET, limit))
+uint64_t planWindowTables(ug_ctx* ctx, std::vector<TableGroup>& groups, uint64_t limit = ~(uint64_t)0, bool force = false, bool strided = false) {
+    for (auto& g : groups) { *g.c = 0; if (g.stride) *g.stride = 1; }
     const char* e = getenv("ULTRAGROTH_TABLES");
     if (e && e[0] == '0') return 0;
     if (!force && (g_registryCreate || (g_oneShotProver && !(e && e[0] == '2')))) return 0;     // "2": tables even for one-shot calls
@@ -390,17 +443,29 @@ uint64_t planWindowTables(ug_ctx* ctx, std::vector<TableGroup>& groups, uint64_t
     if (!need) return 0;
     uint64_t freeB = 0, totalB = 0;
     ugCheck(ug_ctx_mem_info(ctx, &freeB, &totalB));
-    if (need + workspace > freeB || need > limit) return 0;
+    std::vector<TableChoice> plan(groups.size());
+    if (strided) {
+        workspace += stridedBucketReserve(groups);
+        uint64_t budget = freeB > workspace ? freeB - workspace : 0;
+        budget = std::min(std::min(budget, limit), tablesBudgetFromEnv());
+        plan = planStrided(groups, budget);
+        tracePlan(groups, plan, budget);
+    } else {
+        if (need + workspace > freeB || need > limit) return 0;
+        for (size_t k = 0; k < groups.size(); k++) plan[k].c = width[k];
+    }
     uint64_t taken = 0;
     for (size_t k = 0; k < groups.size(); k++) {
-        if (!width[k]) continue;
+        const int c = plan[k].c, st = plan[k].stride;
+        if (!c) continue;
         bool ok = true;
-        for (ug_bases* b : groups[k].g1) ok = ok && ug_bases_precompute(b, width[k]) == 0;
-        for (ug_bases* b : groups[k].g2) ok = ok && ug_bases_precompute(b, width[k]) == 0;
+        for (ug_bases* b : groups[k].g1) ok = ok && ug_bases_precompute_strided(b, c, st) == 0;
+        for (ug_bases* b : groups[k].g2) ok = ok && ug_bases_precompute_strided(b, c, st) == 0;
         if (ok) {
-            *groups[k].c = width[k];
-            for (uint64_t n : groups[k].n1) taken += ug_bases_tables_bytes(n, 0, width[k]);
-            for (uint64_t n : groups[k].n2) taken += ug_bases_tables_bytes(n, 1, width[k]);
+            *groups[k].c = c;
+            if (groups[k].stride) *groups[k].stride = st;
+            for (uint64_t n : groups[k].n1) taken += ug_bases_tables_bytes_strided(n, 0, c, st);
+            for (uint64_t n : groups[k].n2) taken += ug_bases_tables_bytes_strided(n, 1, c, st);
         } else {                               // a group left half built gives its memory back and keeps the classic windows
             for (ug_bases* b : groups[k].g1) ug_bases_drop_tables(b);
             for (ug_bases* b : groups[k].g2) ug_bases_drop_tables(b);
@@ -411,9 +476,9 @@ uint64_t planWindowTables(ug_ctx* ctx, std::vector<TableGroup>& groups, uint64_t
 // The same decision taken BEFORE the base sets exist (only their sizes are known): widths[k] = the table width of group k,
 // or 0. `otherBytes` = what the caller is still going to allocate besides the tables (the points themselves, matrix,
 // vectors). With the widths known, every set is created together with its tables (ug_bases_create_tables_*), whose build
-// overlaps the upload of the next section.
-std::vector<int> planTableWidthsAhead(ug_ctx* ctx, const std::vector<TableGroup>& groups, uint64_t otherBytes) {
-    std::vector<int> none(groups.size(), 0);
+// overlaps the upload of the next section. strided: as for planWindowTables.
+std::vector<TableChoice> planTableWidthsAhead(ug_ctx* ctx, const std::vector<TableGroup>& groups, uint64_t otherBytes, bool strided = false) {
+    std::vector<TableChoice> none(groups.size());
     const char* e = getenv("ULTRAGROTH_TABLES");
     if (e && e[0] == '0') return none;
     if (g_registryCreate || (g_oneShotProver && !(e && e[0] == '2'))) return none;
@@ -423,8 +488,17 @@ std::vector<int> planTableWidthsAhead(ug_ctx* ctx, const std::vector<TableGroup>
     if (!need) return none;
     uint64_t freeB = 0, totalB = 0;
     ugCheck(ug_ctx_mem_info(ctx, &freeB, &totalB));
+    if (strided) {
+        workspace += stridedBucketReserve(groups);
+        const uint64_t budget = std::min(freeB > workspace + otherBytes ? freeB - workspace - otherBytes : 0, tablesBudgetFromEnv());
+        std::vector<TableChoice> plan = planStrided(groups, budget);
+        tracePlan(groups, plan, budget);
+        return plan;
+    }
     if (need + workspace + otherBytes > freeB) return none;
-    return width;
+    std::vector<TableChoice> plan(groups.size());
+    for (size_t k = 0; k < groups.size(); k++) plan[k].c = width[k];
+    return plan;
 }
 bool fusedGroups() {
     const char* e = getenv("ULTRAGROTH_FUSED");
@@ -433,7 +507,7 @@ bool fusedGroups() {
 // The witness products of one schedule, queued on ctx (results after ug_ctx_collect): the G1 sets -- as the interleaved group
 // d.G when the prover holds one (outC null: a two-member group), else d.A, d.B1 and, with outC, d.C shifted by shiftC --
 // and the G2 set d.B2; g2First queues the G2 product ahead of the G1 ones.
-void buildSchedule(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int tableC);
+void buildSchedule(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int tableC, int stride = 1);
 void enqueueWitnessProducts(DeviceProver& d, ug_ctx* ctx, const ug_schedule* sw, uint8_t* outA, uint8_t* outB1, uint8_t* outB2, uint8_t* outC,
                             int64_t shiftC, bool g2First, const ug_dvec* witness = nullptr) {
     if (d.Bc2) {
@@ -449,7 +523,7 @@ void enqueueWitnessProducts(DeviceProver& d, ug_ctx* ctx, const ug_schedule* sw,
             ugCheck(ug_msm_batch_enqueue(ctx, 1, setA, sw, nullptr, outsA));
         }
         ugCheck(ug_dvec_gather_index(d.wB, witness, d.bIdx));
-        buildSchedule(d.sB, d.wB, 0, ug_dvec_size(d.wB), d.tableB);
+        buildSchedule(d.sB, d.wB, 0, ug_dvec_size(d.wB), d.tableB, d.strideB);
         const ug_bases* sets[2] = {d.Bc1, d.Bc2};
         void* outsB[2] = {outB1, outB2};
         ugCheck(ug_msm_batch_enqueue(ctx, 2, sets, d.sB, nullptr, outsB));
@@ -482,8 +556,8 @@ void enqueueWitnessProducts(DeviceProver& d, ug_ctx* ctx, const ug_schedule* sw,
     }
     if (!g2First) g2();
 }
-void buildSchedule(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int tableC) {
-    if (tableC) ugCheck(ug_schedule_build_tables(s, scalars, first, count, tableC));
+void buildSchedule(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int tableC, int stride) {
+    if (tableC) ugCheck(ug_schedule_build_tables_strided(s, scalars, first, count, tableC, stride));
     else ugCheck(ug_schedule_build(s, scalars, first, count));
 }
 
@@ -567,6 +641,21 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
     virtual std::vector<TableGroup> tableGroups() = 0;
     uint64_t tablesWouldTake() { std::vector<TableGroup> g = tableGroups(); std::vector<int> w; return tablesNeed(g, w, nullptr); }
     virtual bool tablesReady(bool /*wait*/) { return true; }       // (provers that build their tables in the background override)
+    virtual int pendingWidth(int /*group*/) const { return 0; }    // width of a group's tables still being built (tableBuilder)
+    // the plan of schedule group `group` (ug_prover_table_plan): false when there is no such group
+    bool tablePlan(int group, int* c, int* stride, uint64_t* bytes, int* ready) {
+        std::vector<TableGroup> g = tableGroups();
+        if (group < 0 || group >= (int)g.size()) return false;
+        const int pending = pendingWidth(group);
+        const int inUse = *g[group].c;
+        const int w = inUse ? inUse : pending;
+        const int st = w ? (g[group].stride ? *g[group].stride : 1) : 0;
+        uint64_t b = 0;
+        for (uint64_t n : g[group].n1) b += ug_bases_tables_bytes_strided(n, 0, w, st);
+        for (uint64_t n : g[group].n2) b += ug_bases_tables_bytes_strided(n, 1, w, st);
+        *c = w; *stride = st; *bytes = w ? b : 0; *ready = (!w || inUse) ? 1 : 0;
+        return true;
+    }
     bool buildTables(uint64_t limit) {
         if (tableBytes) return true;
         std::lock_guard<std::mutex> turn(proveMutex);
@@ -787,16 +876,22 @@ private:
         sparseB_ = !(haveLayout_ && layout_.qLog) && groupG1_ && nw <= maxRange_ && sparseBSupport(pB1, pB2, nw, bSupport, b1c, b2c);
         nB_ = sparseB_ ? bSupport.size() : 0;
         if (sparseB_ && wr_.lo) for (uint32_t& i : bSupport) i += (uint32_t)wr_.lo;          // signal numbers of the whole witness
-        std::vector<int> ahead = planTableWidthsAhead(d_.ctx, tableGroups(), otherBytes);
-        ahead.resize(3, 0);
+        // (the created prover on one device plans strided tables when full ones do not fit; ranks, the registry and one-shot calls
+        // keep all or nothing)
+        const bool strided = g_deferTables && !g_oneShotProver && !g_registryCreate && count == 1 && !haveLayout_ && !src.sliced;
+        std::vector<TableChoice> plan = planTableWidthsAhead(d_.ctx, tableGroups(), otherBytes, strided);
+        plan.resize(3);
+        std::vector<int> ahead(3), aheadS(3);
+        for (int k = 0; k < 3; k++) { ahead[k] = plan[k].c; aheadS[k] = plan[k].stride; }
         bool withTables = true;
         if (bgTables_ && (ahead[0] || ahead[1])) {
             ugCheck(ug_ctx_defer_tables(d_.ctx, 1));
             ugCheck(ug_ctx_defer_tables(d_.ctx2, 1));
         } else bgTables_ = false;
-        auto create = [&](ug_ctx* ctx, bool g2, const uint8_t* pts, uint64_t n, uint64_t first, int width, ug_bases** out) {
+        auto create = [&](ug_ctx* ctx, bool g2, const uint8_t* pts, uint64_t n, uint64_t first, int width, int stride, ug_bases** out) {
             if (width && withTables) {
-                int rc = g2 ? ug_bases_create_tables_g2(ctx, pts, n, first, width, out) : ug_bases_create_tables_g1(ctx, pts, n, first, width, out);
+                int rc = g2 ? ug_bases_create_tables_strided_g2(ctx, pts, n, first, width, stride, out)
+                            : ug_bases_create_tables_strided_g1(ctx, pts, n, first, width, stride, out);
                 if (rc == UG_OK) return;
                 withTables = false;                 // memory ran short after all: this set and the rest without tables
             }
@@ -808,13 +903,13 @@ private:
             const void* hosts[2] = {pA, pC};
             const uint64_t counts[2] = {nw, cHi - cLo}, firsts[2] = {wr_.lo, cLo + hdr_.nPublic + 1};
             int rc = UG_ERROR;
-            if (ahead[0]) rc = ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, ahead[0], &d_.G);
+            if (ahead[0]) rc = ug_bases_create_group_strided_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G);
             if (rc != UG_OK) {
                 if (ahead[0]) withTables = false;
                 ugCheck(ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G));
             }
-            create(d_.ctx, false, b1c.data(), nB_, 0, ahead[2], &d_.Bc1);
-            create(d_.ctx, true, b2c.data(), nB_, 0, ahead[2], &d_.Bc2);
+            create(d_.ctx, false, b1c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc1);
+            create(d_.ctx, true, b2c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc2);
             ugCheck(ug_index_create(d_.ctx, bSupport.data(), nB_, &d_.bIdx));
             ugCheck(ug_dvec_create(d_.ctx, nB_, &d_.wB));
             ugCheck(ug_schedule_create(d_.ctx, &d_.sB));
@@ -824,21 +919,21 @@ private:
             const void* hosts[3] = {pA, pB1, pC};
             const uint64_t counts[3] = {nw, nw, cHi - cLo}, firsts[3] = {wr_.lo, wr_.lo, cLo + hdr_.nPublic + 1};
             int rc = UG_ERROR;
-            if (ahead[0]) rc = ug_bases_create_group_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, ahead[0], &d_.G);
+            if (ahead[0]) rc = ug_bases_create_group_strided_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G);
             if (rc != UG_OK) {
                 if (ahead[0]) withTables = false;           // memory ran short after all
                 ugCheck(ug_bases_create_group_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G));
             }
         } else {
-            create(d_.ctx, false, pA, nw, wr_.lo, ahead[0], &d_.A);
-            create(d_.ctx, false, pB1, nw, wr_.lo, ahead[0], &d_.B1);
+            create(d_.ctx, false, pA, nw, wr_.lo, ahead[0], aheadS[0], &d_.A);
+            create(d_.ctx, false, pB1, nw, wr_.lo, ahead[0], aheadS[0], &d_.B1);
         }
         traceStep("create: G1 sets of the witness uploaded");
-        if (!sparseB_) create(d_.ctx, true, pB2, nw, wr_.lo, ahead[0], &d_.B2);
+        if (!sparseB_) create(d_.ctx, true, pB2, nw, wr_.lo, ahead[0], aheadS[0], &d_.B2);
         traceStep("create: B2 uploaded");
-        if (!d_.G) create(d_.ctx, false, pC, cHi - cLo, cLo, ahead[0], &d_.C);
+        if (!d_.G) create(d_.ctx, false, pC, cHi - cLo, cLo, ahead[0], aheadS[0], &d_.C);
         const bool group0 = withTables && ahead[0];
-        create(d_.ctx2, false, pH, nh, hr_.lo, ahead[1], &d_.H);
+        create(d_.ctx2, false, pH, nh, hr_.lo, ahead[1], aheadS[1], &d_.H);
         traceStep("create: H uploaded");
         const bool group1 = withTables && ahead[1];
         const bool group2 = sparseB_ && withTables && ahead[2];
@@ -849,10 +944,12 @@ private:
         tableW_ = group0 ? ahead[0] : 0;
         tableH_ = group1 ? ahead[1] : 0;
         d_.tableB = group2 ? ahead[2] : 0;
-        if (group0) tableBytes += (d_.G ? ug_bases_tables_bytes((sparseB_ ? 2 : 3) * nw, 0, tableW_) : ug_bases_tables_bytes(nw, 0, tableW_) * 2 + ug_bases_tables_bytes(cHi - cLo, 0, tableW_)) +
-                                  (sparseB_ ? 0 : ug_bases_tables_bytes(nw, 1, tableW_));
-        if (group1) tableBytes += ug_bases_tables_bytes(nh, 0, tableH_);
-        if (group2) tableBytes += ug_bases_tables_bytes(nB_, 0, d_.tableB) + ug_bases_tables_bytes(nB_, 1, d_.tableB);
+        strideW_ = aheadS[0]; strideH_ = aheadS[1]; d_.strideB = aheadS[2];
+        auto bytes = [](uint64_t n, int g2, int c, int st) { return ug_bases_tables_bytes_strided(n, g2, c, st); };
+        if (group0) tableBytes += (d_.G ? bytes((sparseB_ ? 2 : 3) * nw, 0, tableW_, strideW_) : bytes(nw, 0, tableW_, strideW_) * 2 + bytes(cHi - cLo, 0, tableW_, strideW_)) +
+                                  (sparseB_ ? 0 : bytes(nw, 1, tableW_, strideW_));
+        if (group1) tableBytes += bytes(nh, 0, tableH_, strideH_);
+        if (group2) tableBytes += bytes(nB_, 0, d_.tableB, d_.strideB) + bytes(nB_, 1, d_.tableB, d_.strideB);
         if (bgTables_) {          // classic windows until tableBuilder() has finished them
             pendingW_.store(tableW_); pendingH_.store(tableH_); pendingB_.store(d_.tableB);
             tableW_ = tableH_ = 0; d_.tableB = 0;
@@ -896,6 +993,14 @@ public:
         // pieces of about 10 ms: the G1 table kernel makes ~60 k points per ms, the G2 one ~20 k (2^24: 840 ms for 50 M points of
         // the A | B1 | C group, 836 ms for 16.7 M points of B2)
         const uint64_t pieceG1 = (uint64_t)1 << 19, pieceG2 = (uint64_t)3 << 16;
+        // (pieces are sized by doublings: a point of a full set takes (W - 1) c of them, one of a strided set (T - 1) s c -- no more)
+        auto piece = [&](const ug_bases* b) {
+            const uint64_t base = (b == d_.B2 || b == d_.Bc2) ? pieceG2 : pieceG1;
+            const int c = ug_bases_table_window(b), st = ug_bases_table_stride(b);
+            if (!c || st <= 1) return base;
+            const int w = (255 + c - 1) / c, t = (w + st - 1) / st;
+            return t > 1 ? base * (uint64_t)(w - 1) / ((uint64_t)(t - 1) * (uint64_t)st) : base;
+        };
         try {
             // The tables' memory (72 GiB at 2^24) is not allocated by create either: the first allocation of tens of GiB on a device
             // can take a second (seen: 36 GiB in 1.09 s on a box fresh from boot, 0.3 ms afterwards) and holds up every other HIP
@@ -940,7 +1045,7 @@ public:
                         // the gap between two calls): a proof on the tables is 20 ms faster, so finishing the build pays
                         const int pieces = (wantTurn_.load() > 0 || !builderHadLast_.load()) ? 4 : 1;
                         uint64_t left = 1;
-                        for (int i = 0; i < pieces && left; i++) ugCheck(ug_bases_tables_step(b, (b == d_.B2 || b == d_.Bc2) ? pieceG2 : pieceG1, &left));
+                        for (int i = 0; i < pieces && left; i++) ugCheck(ug_bases_tables_step(b, piece(b), &left));
                         builderHadLast_.store(true);
                         if (!left) break;
                     }
@@ -973,10 +1078,10 @@ public:
         if (d_.G || (!d_.A && groupG1_)) { groups[0].g1 = {d_.G}; groups[0].n1 = {3 * (wr_.hi - wr_.lo)}; }      // (also before the sets exist)
         else { groups[0].g1 = {d_.A, d_.B1, d_.C}; groups[0].n1 = {wr_.hi - wr_.lo, wr_.hi - wr_.lo, cHi_ - cLo_}; }
         groups[0].g2 = {d_.B2}; groups[0].n2 = {wr_.hi - wr_.lo};
-        groups[0].scalars = wr_.hi - wr_.lo; groups[0].c = &tableW_;
+        groups[0].scalars = wr_.hi - wr_.lo; groups[0].c = &tableW_; groups[0].stride = &strideW_;
         if (wr_.hi - wr_.lo > maxRange_) groups[0].scalars = 0;          // proved in pieces: classic windows per piece
         groups[1].g1 = {d_.H}; groups[1].n1 = {hr_.hi - hr_.lo};
-        groups[1].scalars = hr_.hi - hr_.lo; groups[1].c = &tableH_;
+        groups[1].scalars = hr_.hi - hr_.lo; groups[1].c = &tableH_; groups[1].stride = &strideH_;
         if (hr_.hi - hr_.lo > maxRange_) groups[1].scalars = 0;
         if (sparseB_) {               // the group of the witness holds [A | C] only; B1 and B2 live compacted, with a schedule of their own
             groups[0].g1 = {d_.G}; groups[0].n1 = {2 * (wr_.hi - wr_.lo)};
@@ -984,9 +1089,12 @@ public:
             groups.resize(3);
             groups[2].g1 = {d_.Bc1}; groups[2].n1 = {nB_};
             groups[2].g2 = {d_.Bc2}; groups[2].n2 = {nB_};
-            groups[2].scalars = nB_; groups[2].c = &d_.tableB;
+            groups[2].scalars = nB_; groups[2].c = &d_.tableB; groups[2].stride = &d_.strideB;
         }
         return groups;
+    }
+    int pendingWidth(int group) const override {
+        return group == 0 ? pendingW_.load() : group == 1 ? pendingH_.load() : group == 2 ? pendingB_.load() : 0;
     }
     void trimWorkspaces() override {
         TurnRequest mine(wantTurn_);
@@ -1114,7 +1222,7 @@ public:
             uint64_t n = std::min<uint64_t>(maxRange_, wr_.hi - lo);
             uint8_t* out = (lo == wr_.lo) ? partials : part;
             memset(part, 0, sizeof part);
-            buildSchedule(d_.sw, wCur_, lo, n, tableW_);
+            buildSchedule(d_.sw, wCur_, lo, n, tableW_, strideW_);
             // S1-S4 (src/groth16.cpp:55,58,61,64): A, B1, B2, C over the witness schedule, queued back to back
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, out, out + 64, out + 128, out + 256, (int64_t)hdr_.nPublic + 1, false, wCur_);
             ugCheck(ug_ctx_collect(d_.ctx));
@@ -1144,7 +1252,7 @@ public:
             return;
         }
         QueueGuard inFlight(d_.ctx);
-        buildSchedule(d_.sw, wCur_, wr_.lo, n, tableW_);
+        buildSchedule(d_.sw, wCur_, wr_.lo, n, tableW_, strideW_);
         enqueueWitnessProducts(d_, d_.ctx, d_.sw, queuedParts_, queuedParts_ + 64, queuedParts_ + 128, queuedParts_ + 256,
                                (int64_t)hdr_.nPublic + 1, false, wCur_);
         inFlight.done();
@@ -1178,7 +1286,7 @@ public:
             uint64_t n = std::min<uint64_t>(maxRange_, hr_.hi - lo);
             uint8_t* out = (lo == hr_.lo) ? partials : part;
             memset(part, 0, sizeof part);
-            buildSchedule(d_.sh, d_.h, lo, n, tableH_);
+            buildSchedule(d_.sh, d_.h, lo, n, tableH_, strideH_);
             const ug_bases* sets[1] = {d_.H};
             void* outs[1] = {out + 320};
             ugCheck(ug_msm_batch(d_.ctx2, 1, sets, d_.sh, nullptr, outs));                     // S10 :154
@@ -1260,12 +1368,12 @@ public:
         // queued products write to runParts_, a member, so that a replay finds the same addresses)
         auto queueAll = [&] {
             uint8_t* out = runParts_;
-            buildSchedule(d_.sw, wCur_, wr_.lo, nw, tableW_);
+            buildSchedule(d_.sw, wCur_, wr_.lo, nw, tableW_, strideW_);
             // S1-S4 (src/groth16.cpp:55,58,61,64): A, B1, B2, C over the witness schedule, queued back to back
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, out, out + 64, out + 128, out + 256, (int64_t)hdr_.nPublic + 1, overlap == 2, wCur_);
             if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));                                          // S5-S9 :66-148
-            buildSchedule(d_.sh, d_.h, hr_.lo, nh, tableH_);
+            buildSchedule(d_.sh, d_.h, hr_.lo, nh, tableH_, strideH_);
             if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             const ug_bases* sets[1] = {d_.H};
             void* outs[1] = {out + 320};
@@ -1407,6 +1515,7 @@ private:
     static constexpr uint64_t MAX_RANGE = (uint64_t)1 << 26;       // 2^26 scalars * <= 16 windows < 2^31 entries
     uint64_t maxRange_ = MAX_RANGE;    // ULTRAGROTH_MAX_RANGE lowers it (tests: the piecewise path without a 2^27 circuit)
     int tableW_ = 0, tableH_ = 0;      // window widths of the fixed-base tables (0: classic windows), planWindowTables
+    int strideW_ = 1, strideH_ = 1;    // ... and their strides (set with the plan; the widths follow once the tables are in use)
     std::atomic<int> pendingW_{0}, pendingH_{0}, pendingB_{0};      // ... of tables that are still being built (tableBuilder)
     bool sparseB_ = false;             // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
     uint64_t nB_ = 0;
@@ -1588,7 +1697,8 @@ private:
         ugCheck(ug_index_create(d_.ctx, roundIdx_.data(), roundIdx_.size(), &d_.roundIdx));
         ugCheck(ug_index_create(d_.ctx, finalIdx_.data(), finalIdx_.size(), &d_.finalIdx));
         std::vector<TableGroup> groups = tableGroups();
-        tableBytes = planWindowTables(d_.ctx, groups);
+        // (strided plans for the created prover on one device; ranks and one-shot calls keep all or nothing)
+        tableBytes = planWindowTables(d_.ctx, groups, ~(uint64_t)0, false, count == 1 && !src.sliced && !g_oneShotProver);
     }
 
 public:
@@ -1597,17 +1707,18 @@ public:
         const uint64_t nw = wr_.hi - wr_.lo;
         if (d_.G) { groups[0].g1 = {d_.G}; groups[0].n1 = {2 * nw}; } else { groups[0].g1 = {d_.A, d_.B1}; groups[0].n1 = {nw, nw}; }
         groups[0].g2 = {d_.B2}; groups[0].n2 = {nw};
-        groups[0].scalars = nw; groups[0].c = &tableW_;
+        groups[0].scalars = nw; groups[0].c = &tableW_; groups[0].stride = &strideW_;
         groups[1].g1 = {d_.roundC}; groups[1].n1 = {roundIdx_.size()}; groups[1].scalars = roundIdx_.size(); groups[1].c = &tableC1_;
         groups[2].g1 = {d_.C}; groups[2].n1 = {finalIdx_.size()}; groups[2].scalars = finalIdx_.size(); groups[2].c = &tableC2_;
         groups[3].g1 = {d_.H}; groups[3].n1 = {hr_.hi - hr_.lo}; groups[3].scalars = hr_.hi - hr_.lo; groups[3].c = &tableH_;
+        groups[1].stride = &strideC1_; groups[2].stride = &strideC2_; groups[3].stride = &strideH_;
         if (sparseB_) {               // A alone over the witness schedule; B1 and B2 compacted, with a schedule of their own
             groups[0].g1 = {d_.A}; groups[0].n1 = {nw};
             groups[0].g2.clear(); groups[0].n2.clear();
             groups.resize(5);
             groups[4].g1 = {d_.Bc1}; groups[4].n1 = {nB_};
             groups[4].g2 = {d_.Bc2}; groups[4].n2 = {nB_};
-            groups[4].scalars = nB_; groups[4].c = &d_.tableB;
+            groups[4].scalars = nB_; groups[4].c = &d_.tableB; groups[4].stride = &d_.strideB;
         }
         return groups;
     }
@@ -1704,7 +1815,7 @@ public:
         if (!witnessLoaded_) throw std::invalid_argument("no witness loaded");
         ugCheck(ug_dvec_gather_index(d_.aux, wCur_, d_.roundIdx));
         mark("round gather");
-        buildSchedule(d_.saux, d_.aux, 0, roundIdx_.size(), tableC1_);
+        buildSchedule(d_.saux, d_.aux, 0, roundIdx_.size(), tableC1_, strideC1_);
         ugCheck(ug_msm_g1(d_.ctx, d_.roundC, d_.saux, 0, out64));
         mark("round MSM");
     }
@@ -1745,13 +1856,13 @@ public:
         if (!committed_) throw std::invalid_argument("the round commitment has not been applied");
         if (witnessQueued_) throw std::invalid_argument("witness products are queued on this prover (ug_groth16_prover_witness_msm_end)");
         memset(partials, 0, UG_GROTH16_PARTIALS_SIZE);
-        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, tableW_);
+        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, tableW_, strideW_);
         enqueueWitnessProducts(d_, d_.ctx, d_.sw, partials, partials + 64, partials + 128, nullptr, 0, false, wCur_);      // MSM1-3 :201,214,227
         ugCheck(ug_ctx_collect(d_.ctx));
         mark("A, B1, B2 MSMs");
         ugCheck(ug_dvec_gather_index(d_.aux, wCur_, d_.finalIdx));                           // :439-445
         mark("final gather");
-        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), tableC2_);
+        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), tableC2_, strideC2_);
         ugCheck(ug_msm_g1(d_.ctx, d_.C, d_.saux, 0, partials + 256));                       // MSM4 :234
         mark("C MSM");
     }
@@ -1781,10 +1892,10 @@ public:
     }
     // MSM1-3 (:201,214,227), the gather of the final witnesses (:439-445) and MSM4 (:234), queued on the witness stream
     void queueFinalRoundProducts(uint8_t* sums) {
-        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, tableW_);
+        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, tableW_, strideW_);
         enqueueWitnessProducts(d_, d_.ctx, d_.sw, sums, sums + 64, sums + 128, nullptr, 0, false, wCur_);
         ugCheck(ug_dvec_gather_index(d_.aux, wCur_, d_.finalIdx));
-        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), tableC2_);
+        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), tableC2_, strideC2_);
         const ug_bases* setC[1] = {d_.C};
         void* outC[1] = {sums + 256};
         ugCheck(ug_msm_batch_enqueue(d_.ctx, 1, setC, d_.saux, nullptr, outC));
@@ -1817,7 +1928,7 @@ public:
     // MSM5 (:322) on this rank's slice of h (which must be in d_.h); only the H record of partials is written
     void runHMsm(uint8_t* partials) override {
         memset(partials, 0, UG_GROTH16_PARTIALS_SIZE);
-        buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, tableH_);
+        buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, tableH_, strideH_);
         ugCheck(ug_msm_g1(d_.ctx2, d_.H, d_.sh, 0, partials + 320));
         mark("H MSM");
         collectTimings(witnessQueued_ == 1 ? 2 : 3);          // (queued witness products: their stream is read when they are collected)
@@ -1904,7 +2015,7 @@ public:
             const char* ov = getenv("ULTRAGROTH_OVERLAP");
             if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));      // (default: beside, as for Groth16)
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));
-            buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, tableH_);
+            buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, tableH_, strideH_);
             const ug_bases* setH[1] = {d_.H};
             void* outH[1] = {sums + 320};
             ugCheck(ug_msm_batch_enqueue(d_.ctx2, 1, setH, d_.sh, nullptr, outH));
@@ -1971,6 +2082,7 @@ private:
     bool witnessLoaded_ = false, committed_ = false, haveRoundScalar_ = false, trace_ = false, haveHpoly_ = true;
     std::chrono::steady_clock::time_point tPhase_;
     int tableW_ = 0, tableC1_ = 0, tableC2_ = 0, tableH_ = 0;      // fixed-base table widths per schedule group (0: classic)
+    int strideW_ = 1, strideC1_ = 1, strideC2_ = 1, strideH_ = 1;  // ... and their strides
     bool sparseB_ = false;             // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
     uint64_t nB_ = 0;
     DeviceProver d_;
@@ -2940,6 +3052,15 @@ int ug_prover_tables_ready(void* prover_object, int wait) {
     if (!prover_object) return -1;
     try { return static_cast<ProverBase*>(prover_object)->tablesReady(wait != 0) ? 1 : 0; }
     catch (...) { return -1; }
+}
+int ug_prover_table_plan(void* prover_object, int group, int* c, int* stride, unsigned long long* bytes, int* ready) {
+    if (!prover_object || !c || !stride || !bytes || !ready) return PROVER_ERROR;
+    try {
+        uint64_t b = 0;
+        if (!static_cast<ProverBase*>(prover_object)->tablePlan(group, c, stride, &b, ready)) return PROVER_ERROR;
+        *bytes = b;
+        return PROVER_OK;
+    } catch (...) { return PROVER_ERROR; }
 }
 int ug_prover_last_upload_ms(void* prover_object, double* upload_ms) {
     if (!prover_object || !upload_ms) return PROVER_ERROR;

@@ -72,11 +72,11 @@ __device__ __forceinline__ bool scalar_geq_r(const u32* s) {
     return true;
 }
 // The bucket key of a digit of magnitude mag >= 1 in window w of scalar i, or the sentinel when this schedule does not keep it.
-// Without classes: set w (one set in all with window tables), bucket mag - 1. With classes (internal.hpp: BucketClasses): the
-// lowest bucket ids are kept by scalar range and get ids behind the regular sets, the others by the residue of the bucket id.
-__device__ __forceinline__ u32 digit_key(const DigitPlan& d, int w, u32 mag, u64 i) {
+// Without classes: set wset (the window w; with window tables w mod stride, one set in all at stride 1), bucket mag - 1. With
+// classes (internal.hpp: BucketClasses): the lowest bucket ids are kept by scalar range and get ids behind the regular sets, the
+// others by the residue of the bucket id.
+__device__ __forceinline__ u32 digit_key(const DigitPlan& d, u32 wset, u32 mag, u64 i) {
     const u32 b = mag - 1;
-    const u32 wset = d.tables ? 0u : (u32)w;
     if (d.q_log == 0) return wset * d.buckets + b;
     if (b < d.specials) return (i >= d.sp_lo && i < d.sp_hi) ? d.special_base + wset * d.specials + b : d.sentinel;
     const u32 j = (b & ((1u << d.q_log) - 1)) - d.r0;          // (unsigned: residues below r0 wrap to large values)
@@ -113,14 +113,17 @@ __device__ __forceinline__ void recode_scalar(const u32* scalars, u64 i, const D
         const int bit = w * c, word = bit >> 5, sh = bit & 31;
         const u64 two = (u64)s[word] | ((u64)s[word + 1] << 32);
         const u32 raw = ((u32)(two >> sh) & mask) + carry;
-        const u32 tag = d.tables ? (u32)w << TABLE_INDEX_BITS : 0u;
+        // window tables: bucket set w mod stride, table w / stride, looked up in the plan's maps (no division per window; the
+        // same for every lane)
+        const u32 wset = d.tables ? (u32)(d.set_map >> (4 * w)) & 15u : (u32)w;
+        const u32 tag = d.tables ? ((u32)(d.table_map >> (4 * w)) & 15u) << TABLE_INDEX_BITS : 0u;
         u32 key, val;
         if (raw > half) {                             // negative digit raw - 2^c, carry into the next window
             const u32 mag = full - raw;               // 0 when the window was all ones and a carry came in
             carry = 1;
-            key = mag ? digit_key(d, w, mag, i) : d.sentinel;
+            key = mag ? digit_key(d, wset, mag, i) : d.sentinel;
             val = (u32)i | tag | 0x80000000u;
-        } else { carry = 0; key = raw ? digit_key(d, w, raw, i) : d.sentinel; val = (u32)i | tag; }
+        } else { carry = 0; key = raw ? digit_key(d, wset, raw, i) : d.sentinel; val = (u32)i | tag; }
         f(w, key, val);
     };
     if constexpr (CW != 0) {

@@ -1,6 +1,7 @@
 // ug_api.hip -- implementation of the inner C-ABI declared in include/ultragroth_hip.h.
 // Owns device memory, the stream and the reusable workspaces; translates between the reference's byte
 // formats and the device forms; catches every exception at the boundary.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -157,12 +158,14 @@ struct ug_ctx {
 struct ug_bases {
     ug_ctx* ctx; bool g2; u64 n; u64 global_first; u32* pts;
     int table_c = 0;          // window width of the precomputed tables (0: none, pts holds the n points only)
+    int table_stride = 1;     // ... and their stride: table j = 2^(stride c j) P (MsmGeometry::stride)
     int members = 1;          // > 1: a group -- n = slots * members records, record slot * members + m is member m's point of
     u64 slots = 0;            //      scalar global_first + slot (ug_bases_create_group_g1)
     bool empty = false;       // every record is the point at infinity (e.g. the B2 section of a circuit without B-side wires): its
                               // products are the point at infinity and no kernel is launched for them
     u64 tables_built = ~(u64)0;   // deferred build (ug_ctx_defer_tables): points [0, tables_built) have their tables; >= n: all of them
     int deferred_c = 0;           // ... the width the set will get: until ug_bases_tables_adopt the set holds its n points only
+    int deferred_stride = 1;      // ... and the stride
     bool tables_usable() const { return !table_c || tables_built >= n; }
 };
 struct ug_dvec {
@@ -405,13 +408,13 @@ static bool host_all_zero(const void* p, size_t bytes) {
     for (; i < bytes; i++) if (b[i]) return false;
     return true;
 }
-static int bases_create(ug_ctx* c, const void* host, u64 n, u64 global_first, bool g2, int table_c, ug_bases** out) {
+static int bases_create(ug_ctx* c, const void* host, u64 n, u64 global_first, bool g2, int table_c, int stride, ug_bases** out) {
     UG_TRY
     if (!c || !out || (!host && n)) throw std::invalid_argument("null argument");
     c->use();
-    int windows = 1;
+    int windows = 1;                                          // (the number of tables: ceil(W / stride))
     if (table_c) {
-        windows = MsmGeometry::choose_tables(n, table_c).windows;      // validates the width
+        windows = MsmGeometry::table_count(table_c, MsmGeometry::choose_tables(n, table_c, stride).stride);      // validates width and stride
         if (n > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("window tables need at most 2^27 points per set");
     }
     ug_bases* b = new ug_bases{c, g2, n, global_first, nullptr, 0};
@@ -432,25 +435,31 @@ static int bases_create(ug_ctx* c, const void* host, u64 n, u64 global_first, bo
                 u32* p = pts + off / 4;
                 if (g2) convert_points_g2(p, len / rec, st); else convert_points_g1(p, len / rec, st);
             }, /*fresh*/ true);
-            if (table_c && !defer) build_window_tables(g2, pts, n, table_c, windows, c->stream);
+            if (table_c && !defer) build_window_tables(g2, pts, n, table_c * stride, windows, c->stream);
         } catch (...) { hipFree(b->pts); delete b; throw; }
     }
-    if (defer) b->deferred_c = table_c; else b->table_c = table_c;
+    if (defer) { b->deferred_c = table_c; b->deferred_stride = stride; } else if (table_c) { b->table_c = table_c; b->table_stride = stride; }
     *out = b;
     UG_CATCH
 }
-int ug_bases_create_g1(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, ug_bases** out) { return bases_create(c, host, n, gf, false, 0, out); }
-int ug_bases_create_g2(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, ug_bases** out) { return bases_create(c, host, n, gf, true, 0, out); }
-int ug_bases_create_tables_g1(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, ug_bases** out) { return bases_create(c, host, n, gf, false, table_c, out); }
-int ug_bases_create_tables_g2(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, ug_bases** out) { return bases_create(c, host, n, gf, true, table_c, out); }
+int ug_bases_create_g1(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, ug_bases** out) { return bases_create(c, host, n, gf, false, 0, 1, out); }
+int ug_bases_create_g2(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, ug_bases** out) { return bases_create(c, host, n, gf, true, 0, 1, out); }
+int ug_bases_create_tables_g1(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, ug_bases** out) { return bases_create(c, host, n, gf, false, table_c, 1, out); }
+int ug_bases_create_tables_g2(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, ug_bases** out) { return bases_create(c, host, n, gf, true, table_c, 1, out); }
+int ug_bases_create_tables_strided_g1(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, int stride, ug_bases** out) {
+    return bases_create(c, host, n, gf, false, table_c, stride, out);
+}
+int ug_bases_create_tables_strided_g2(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, int stride, ug_bases** out) {
+    return bases_create(c, host, n, gf, true, table_c, stride, out);
+}
 
 // A group of `members` (2 or 3) G1 sets that are always multiplied by the same scalars, as ONE array of members-point
 // records (msm.hip: segment_accumulate_group_kernel). Member m brings n[m] points; its first point belongs to the scalar
 // with global index first[m]. The group covers the scalars [group_first, group_first + slots); slots a member has no point
 // for hold infinity. With table_c the window tables are built over the interleaved array (a plain G1 array of slots * members
 // points as far as the table kernel is concerned), queued on the context's stream as for ug_bases_create_tables_g1.
-int ug_bases_create_group_g1(ug_ctx* c, int members, const void* const* host, const uint64_t* n, const uint64_t* first,
-                             uint64_t group_first, uint64_t slots, int table_c, ug_bases** out) {
+int ug_bases_create_group_strided_g1(ug_ctx* c, int members, const void* const* host, const uint64_t* n, const uint64_t* first,
+                                     uint64_t group_first, uint64_t slots, int table_c, int stride, ug_bases** out) {
     UG_TRY
     if (!c || !out || !host || !n || !first) throw std::invalid_argument("null argument");
     if (members < 2 || members > 3) throw std::invalid_argument("a base group has 2 or 3 members");
@@ -460,7 +469,7 @@ int ug_bases_create_group_g1(ug_ctx* c, int members, const void* const* host, co
     }
     c->use();
     int windows = 1;
-    if (table_c) windows = MsmGeometry::choose_tables(slots, table_c).windows;      // validates the width
+    if (table_c) windows = MsmGeometry::table_count(table_c, MsmGeometry::choose_tables(slots, table_c, stride).stride);      // validates width and stride
     if (slots > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("a base group holds at most 2^27 scalars");
     ug_bases* b = new ug_bases{c, false, slots * (u64)members, group_first, nullptr, 0};
     b->members = members; b->slots = slots;
@@ -495,52 +504,142 @@ int ug_bases_create_group_g1(ug_ctx* c, int members, const void* const* host, co
                 interleave_points_g1(pts, stage + off / 4, len / 64, members, m, slot0 + off / 64, st);
             }, /*fresh*/ true);
         }
-        if (table_c && b->n && !defer) build_window_tables(false, pts, b->n, table_c, windows, c->stream);
+        if (table_c && b->n && !defer) build_window_tables(false, pts, b->n, table_c * stride, windows, c->stream);
     } catch (...) { hipFree(stage); hipFree(b->pts); delete b; throw; }
     c->deferred_free.push_back(stage);      // (not hipFree here: it would wait for the table build just queued, and the caller's next
                                             // section could no longer be uploaded beside it)
-    if (defer) b->deferred_c = table_c; else b->table_c = table_c;
+    if (defer) { b->deferred_c = table_c; b->deferred_stride = stride; } else if (table_c) { b->table_c = table_c; b->table_stride = stride; }
     *out = b;
     UG_CATCH
+}
+int ug_bases_create_group_g1(ug_ctx* c, int members, const void* const* host, const uint64_t* n, const uint64_t* first,
+                             uint64_t group_first, uint64_t slots, int table_c, ug_bases** out) {
+    return ug_bases_create_group_strided_g1(c, members, host, n, first, group_first, slots, table_c, 1, out);
 }
 int ug_bases_members(const ug_bases* b) { return b ? b->members : 0; }
 int ug_points_all_infinity(const void* host_points, uint64_t n, uint64_t record_bytes) {
     return (host_points && n) ? (host_all_zero(host_points, (size_t)n * (size_t)record_bytes) ? 1 : 0) : 0;
 }
 int ug_msm_table_window(uint64_t n) { return MsmGeometry::table_window(n); }
-uint64_t ug_bases_tables_bytes(uint64_t n, int g2, int c) {
-    if (c < TABLE_MIN_C || c > TABLE_MAX_C) return 0;
-    return (uint64_t)((255 + c - 1) / c - 1) * n * (g2 ? 128 : 64);
+uint64_t ug_bases_tables_bytes(uint64_t n, int g2, int c) { return ug_bases_tables_bytes_strided(n, g2, c, 1); }
+uint64_t ug_bases_tables_bytes_strided(uint64_t n, int g2, int c, int stride) {
+    if (c < TABLE_MIN_C || c > TABLE_MAX_C || stride < 1 || stride > (255 + c - 1) / c) return 0;
+    return (uint64_t)(MsmGeometry::table_count(c, stride) - 1) * n * (g2 ? 128 : 64);
 }
-int ug_bases_precompute(ug_bases* b, int c) {
+// WINDOW-TABLE PLAN under a memory budget (host only). Everything fits: every qualifying group gets the cost-model width at stride
+// 1 (what the provers chose before there was a plan). Otherwise each group gets none or one (c, stride), the choice that minimises
+// the summed modelled cost within the budget: an exact multiple-choice knapsack over the groups' Pareto fronts (bytes against
+// cost), deterministic for equal inputs.
+namespace {
+constexpr u64 PLAN_MIN_SCALARS = (u64)1 << 14, PLAN_MAX_SCALARS = (u64)1 << 26;
+constexpr u64 PLAN_MAX_ENTRIES = (u64)1 << 30;          // scalars * windows of one schedule
+constexpr u64 PLAN_MAX_BUCKETS = (u64)1 << 24;          // stride * 2^(c-1): a strided schedule's buckets per product stay within
+                                                        // twice those of the widest full set (the caller reserves their memory)
+constexpr double PLAN_G2_WEIGHT = 3.0;                  // a G2 addition against a G1 one: Fq2 products cost three Fq products
+struct PlanOption { u64 bytes; double cost; int c, stride; };
+bool plan_qualifies(const ug_table_group& g) { return g.scalars >= PLAN_MIN_SCALARS && g.scalars <= PLAN_MAX_SCALARS; }
+u64 plan_bytes(const ug_table_group& g, int c, int stride) {
+    return ug_bases_tables_bytes_strided(g.g1_points, 0, c, stride) + ug_bases_tables_bytes_strided(g.g2_points, 1, c, stride);
+}
+// modelled cost of a group's products: per product the MSM cost, G2 products weighted
+double plan_cost(const ug_table_group& g, int c, int stride) {
+    if (!g.scalars) return 0;
+    const double products = ((double)g.g1_points + PLAN_G2_WEIGHT * (double)g.g2_points) / (double)g.scalars;
+    return products * (c ? msm_model_cost(g.scalars, c, true, stride) : msm_model_cost(g.scalars, MsmGeometry::choose(g.scalars).c, false));
+}
+// options sorted by bytes, each strictly cheaper than every option before it
+void pareto(std::vector<PlanOption>& v) {
+    std::stable_sort(v.begin(), v.end(), [](const PlanOption& a, const PlanOption& b) { return a.bytes != b.bytes ? a.bytes < b.bytes : a.cost < b.cost; });
+    std::vector<PlanOption> keep;
+    for (const PlanOption& o : v) if (keep.empty() || o.cost < keep.back().cost) keep.push_back(o);
+    v.swap(keep);
+}
+}  // namespace
+int ug_plan_window_tables(const ug_table_group* groups, int n_groups, uint64_t budget, ug_table_choice* out) {
+    UG_TRY
+    if (n_groups < 0 || (n_groups && (!groups || !out))) throw std::invalid_argument("null argument");
+    u64 full = 0;
+    for (int k = 0; k < n_groups; k++) {
+        out[k] = ug_table_choice{0, 0, 0};
+        if (!plan_qualifies(groups[k])) continue;
+        const int c = MsmGeometry::table_window(groups[k].scalars);
+        out[k] = ug_table_choice{c, 1, plan_bytes(groups[k], c, 1)};
+        full += out[k].bytes;
+    }
+    if (full <= budget) return UG_OK;
+    // a state of the knapsack: bytes, cost and the option taken in every group so far
+    struct State { u64 bytes; double cost; std::vector<int> pick; };
+    std::vector<State> front{State{0, 0.0, {}}};
+    std::vector<std::vector<PlanOption>> opts(n_groups);
+    for (int k = 0; k < n_groups; k++) {
+        const ug_table_group& g = groups[k];
+        std::vector<PlanOption>& o = opts[k];
+        o.push_back(PlanOption{0, plan_cost(g, 0, 0), 0, 0});
+        if (plan_qualifies(g) && (g.g1_points || g.g2_points)) {
+            for (int c = TABLE_MIN_C; c <= TABLE_MAX_C; c++) {
+                const int windows = (255 + c - 1) / c;
+                if (g.scalars * (u64)windows > PLAN_MAX_ENTRIES) continue;
+                for (int st = 1; MsmGeometry::table_count(c, st) > 1; st++) {      // (one table would be the classic windows)
+                    const u64 bytes = plan_bytes(g, c, st);
+                    if (bytes > budget || (u64)st << (c - 1) > PLAN_MAX_BUCKETS) continue;
+                    o.push_back(PlanOption{bytes, plan_cost(g, c, st), c, st});
+                }
+            }
+        }
+        pareto(o);
+        std::vector<State> next;
+        for (const State& st : front)
+            for (size_t j = 0; j < o.size(); j++) {
+                if (st.bytes + o[j].bytes > budget) break;               // (o is sorted by bytes)
+                State n = st;
+                n.bytes += o[j].bytes; n.cost += o[j].cost; n.pick.push_back((int)j);
+                next.push_back(std::move(n));
+            }
+        std::stable_sort(next.begin(), next.end(), [](const State& a, const State& b) { return a.bytes != b.bytes ? a.bytes < b.bytes : a.cost < b.cost; });
+        front.clear();
+        for (State& st : next) if (front.empty() || st.cost < front.back().cost) front.push_back(std::move(st));
+    }
+    // the front is sorted by bytes with falling cost: its last state is the cheapest within the budget
+    const State& best = front.back();
+    for (int k = 0; k < n_groups; k++) {
+        const PlanOption& o = opts[k][best.pick[k]];
+        out[k] = ug_table_choice{o.c, o.stride, o.bytes};
+    }
+    UG_CATCH
+}
+int ug_bases_precompute(ug_bases* b, int c) { return ug_bases_precompute_strided(b, c, 1); }
+int ug_bases_precompute_strided(ug_bases* b, int c, int stride) {
     UG_TRY
     if (!b) throw std::invalid_argument("null argument");
     if (b->table_c) throw std::invalid_argument("bases already hold window tables");
-    MsmGeometry g = MsmGeometry::choose_tables(b->n, c);             // validates c
+    MsmGeometry g = MsmGeometry::choose_tables(b->n, c, stride);     // validates c and the stride
+    const int tables = MsmGeometry::table_count(c, stride);
     if ((b->members > 1 ? b->slots : b->n) > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("window tables need at most 2^27 points per set");
     ug_ctx* ctx = b->ctx;
     ctx->use();
     if (b->n) {
         size_t rec = b->g2 ? 128 : 64;
         u32* all = nullptr;
-        if (hipMalloc(&all, (size_t)g.windows * b->n * rec) != hipSuccess) {
+        if (hipMalloc(&all, (size_t)tables * b->n * rec) != hipSuccess) {
             (void)hipGetLastError();
             throw std::runtime_error("not enough device memory for the window tables");
         }
         UG_HIP(hipMemcpyAsync(all, b->pts, (size_t)b->n * rec, hipMemcpyDeviceToDevice, ctx->stream));
-        build_window_tables(b->g2, all, b->n, c, g.windows, ctx->stream);
+        build_window_tables(b->g2, all, b->n, c * g.stride, tables, ctx->stream);
         UG_HIP(hipStreamSynchronize(ctx->stream));
         alloc_epoch_bump();                          // (captured launch sequences that read the old array are stale now)
         hipFree(b->pts);
         b->pts = all;
     }
     b->table_c = c;
+    b->table_stride = stride;
     UG_CATCH
 }
 int ug_bases_drop_tables(ug_bases* b) {
     UG_TRY
     if (!b) throw std::invalid_argument("null argument");
     b->deferred_c = 0;                               // (a deferred build that has not got its room yet is simply called off)
+    b->deferred_stride = 1;
     if (!b->table_c) return UG_OK;
     ug_ctx* ctx = b->ctx;
     ctx->use();
@@ -553,9 +652,11 @@ int ug_bases_drop_tables(ug_bases* b) {
     hipFree(b->pts);
     b->pts = small;
     b->table_c = 0;
+    b->table_stride = 1;
     UG_CATCH
 }
 int ug_bases_table_window(const ug_bases* b) { return b ? b->table_c : 0; }
+int ug_bases_table_stride(const ug_bases* b) { return b && b->table_c ? b->table_stride : 0; }
 // DEFERRED TABLE BUILDS (cold start of a created prover). After ug_ctx_defer_tables(ctx, 1) the sets made on the context with a
 // table width get the room for their tables and table 0, nothing else: ug_bases_tables_step builds the tables of the next
 // `max_points` points on the context's stream and WAITS for them (a bounded piece of device time: the caller interleaves the
@@ -576,7 +677,7 @@ int ug_bases_tables_alloc(ug_bases* b, void** mem) {
     *mem = nullptr;
     if (!b->deferred_c || !b->n) return UG_OK;                       // nothing deferred (or nothing to build)
     b->ctx->use();
-    const int windows = MsmGeometry::choose_tables(b->n, b->deferred_c).windows;
+    const int windows = MsmGeometry::table_count(b->deferred_c, b->deferred_stride);
     if (hipMalloc(mem, (size_t)windows * b->n * (b->g2 ? 128 : 64)) != hipSuccess) {
         (void)hipGetLastError();
         *mem = nullptr;
@@ -599,7 +700,9 @@ int ug_bases_tables_adopt(ug_bases* b, void* mem) {
         b->pts = static_cast<u32*>(mem);
     }
     b->table_c = b->deferred_c;
+    b->table_stride = b->deferred_stride;
     b->deferred_c = 0;
+    b->deferred_stride = 1;
     b->tables_built = b->n ? 0 : ~(u64)0;
     UG_CATCH
 }
@@ -611,11 +714,11 @@ int ug_bases_tables_step(ug_bases* b, uint64_t max_points, uint64_t* remaining) 
         ug_ctx* c = b->ctx;
         c->use();
         const u64 first = b->tables_built, count = max_points < b->n - first ? max_points : b->n - first;
-        const int windows = MsmGeometry::choose_tables(b->n, b->table_c).windows;
+        const int windows = MsmGeometry::table_count(b->table_c, b->table_stride);
         // (a group is one array of n = slots * members records; a lane of the table kernel carries 4 (G1) / 2 (G2) consecutive
         // points, so pieces start at multiples of 4)
         const u64 take = count >= b->n - first ? b->n - first : (count + 3) / 4 * 4;
-        build_window_tables(b->g2, b->pts, b->n, b->table_c, windows, c->stream, first, take);
+        build_window_tables(b->g2, b->pts, b->n, b->table_c * b->table_stride, windows, c->stream, first, take);
         UG_HIP(hipStreamSynchronize(c->stream));
         b->tables_built = first + take >= b->n ? ~(u64)0 : first + take;
     }
@@ -883,13 +986,16 @@ int ug_schedule_build(ug_schedule* s, const ug_dvec* scalars, uint64_t first, ui
     UG_CATCH
 }
 int ug_schedule_build_tables(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int c) {
+    return ug_schedule_build_tables_strided(s, scalars, first, count, c, 1);
+}
+int ug_schedule_build_tables_strided(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int c, int stride) {
     UG_TRY
     if (!s || !scalars) throw std::invalid_argument("null argument");
     if (first + count > scalars->n) throw std::invalid_argument("schedule range outside the scalar vector");
     ug_ctx* ctx = s->ctx;
     ctx->use();
     fault_point(UG_FAULT_SCHEDULE_BUILD);
-    MsmGeometry g = MsmGeometry::choose_tables(count, c);
+    MsmGeometry g = MsmGeometry::choose_tables(count, c, stride);
     g.set_classes(s->classes_for(first, count));
     ScopedTimer tm(ctx, &ctx->msm_ms);
     s->first = first;
@@ -944,6 +1050,9 @@ static void check_tables(const ug_bases* b, const ug_schedule* s) {
     if (s->sched.geo.tables && s->sched.geo.c != b->table_c)
         throw std::invalid_argument("schedule built for window tables of width " + std::to_string(s->sched.geo.c) +
                                     " but the bases hold " + (b->table_c ? "tables of width " + std::to_string(b->table_c) : std::string("no tables")));
+    if (s->sched.geo.tables && s->sched.geo.stride != b->table_stride)
+        throw std::invalid_argument("schedule built for window tables of stride " + std::to_string(s->sched.geo.stride) +
+                                    " but the bases hold tables of stride " + std::to_string(b->table_stride));
 }
 int ug_msm_g1(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_shift, void* out) {
     UG_TRY
