@@ -117,6 +117,22 @@ int ultra_groth_prover_zkey_file(const char *zkey_file_path,
  * library first looks (tests, bench.py --check, smoke()); otherwise it changes nothing and returns PROVER_ERROR. */
 int ug_test_set_blinding(const void *bytes, unsigned long long n);
 
+/* BATCHED PROOFS: `count` witnesses (wtns file buffers) proved in one call; proof_buffers[b] / public_buffers[b] receive what
+ * groth16_prover_prove returns for witness b, byte for byte, sized as there (proof_sizes[b], public_sizes[b]). A bad witness
+ * fails the whole call with the code and message groth16_prover_prove gives for it, prefixed "witness <b>: ", and no output is
+ * written. A created Groth16 prover checks every witness before any work is queued; other handles check each one when its
+ * proof starts. A short buffer anywhere gives PROVER_ERROR_SHORT_BUFFER with every needed
+ * size written back into proof_sizes / public_sizes. Blinding is drawn in witness order: r0, s0, r1, s1, ... (ug_test_set_blinding).
+ * A created Groth16 prover on one device proves up to 16 witnesses per device pass -- one schedule, one accumulation launch per
+ * product and one set of tails for all of them (include/ultragroth_hip.h: ug_schedule_build_vectors, ug_plan_proof_batch); any
+ * other handle (UltraGroth, ULTRAGROTH_DEVICES, sharded ranks) proves them one after the other with the same outputs.
+ * ug_prover_last_timings reports the whole call. */
+int ug_groth16_prover_prove_batch(void *prover_object, int count,
+                                  const void *const *wtns_buffers, const unsigned long long *wtns_sizes,
+                                  char *const *proof_buffers, unsigned long long *proof_sizes,
+                                  char *const *public_buffers, unsigned long long *public_sizes,
+                                  char *error_msg, unsigned long long error_msg_maxsize);
+
 /* Device milliseconds of the last prove on this prover object: MSM part, H-polynomial ("FFT") part, and
  * host wall-clock milliseconds of the whole prove call. */
 int ug_prover_last_timings(void *prover_object, double *msm_ms, double *fft_ms, double *total_ms);

@@ -150,6 +150,17 @@ int      ug_bases_table_stride(const ug_bases* b);
 typedef struct { uint64_t scalars, g1_points, g2_points; } ug_table_group;
 typedef struct { int c, stride; uint64_t bytes; } ug_table_choice;
 int      ug_plan_window_tables(const ug_table_group* groups, int n_groups, uint64_t budget_bytes, ug_table_choice* out);
+/* BATCH PLAN (host only, no device needed): how many witnesses one device pass of a batched proof takes (ug_schedule_build_vectors).
+ * One entry per schedule of the prover -- its scalars and its window tables (c = 0: classic windows; else width c, stride) --,
+ * the circuit's signals and H domain, the free device bytes and the witnesses requested. Returns V with 1 <= V <=
+ * min(requested, UG_BATCH_MAX): the largest V for which every schedule's V-vector form keeps V * scalars * ceil(255 / c) <= 2^30
+ * pairs, fewer than 2^31 buckets and at most 127 bucket sets (one result block), and for which V witness and h vectors, V-fold
+ * sort buffers (64 bytes per pair) and V-fold bucket arrays (732 bytes per bucket) fit free_bytes. Deterministic. 0 on bad
+ * arguments. */
+#define UG_BATCH_MAX 16
+typedef struct { uint64_t scalars; int c, stride; } ug_batch_schedule;
+int      ug_plan_proof_batch(const ug_batch_schedule* schedules, int n_schedules, uint64_t n_vars, uint64_t domain, uint64_t free_bytes,
+                             int requested);
 /* DEFERRED TABLE BUILDS (cold start of a created prover): after ug_ctx_defer_tables(ctx, 1) the sets made by
  * ug_bases_create_tables_* / ug_bases_create_group_g1 on this context hold their points only and remember the width: nothing
  * is queued, not even the tables' memory is allocated. ug_bases_tables_step(set, max_points, &remaining) builds the tables of the next max_points points on the
@@ -185,6 +196,8 @@ int  ug_dvec_gather(ug_dvec* out, const ug_dvec* src, const uint32_t* host_index
 int  ug_index_create(ug_ctx* ctx, const uint32_t* host_index, uint64_t n, ug_index** out);
 void ug_index_destroy(ug_index* index);
 int  ug_dvec_gather_index(ug_dvec* out, const ug_dvec* src, const ug_index* index);
+/* the same into out[out_first, out_first + index size): vector v of a batched sparse-B schedule at v * its vector stride */
+int  ug_dvec_gather_index_at(ug_dvec* out, uint64_t out_first, const ug_dvec* src, const ug_index* index);
 /* dst[index[i]] = values[i] for i < n; indices must be distinct (UltraGroth lookup signals written back into the
  * witness, src/ultra_groth.cpp:99-105) */
 int  ug_dvec_scatter(ug_dvec* dst, const uint32_t* host_index, const void* host_values, uint64_t n);
@@ -223,6 +236,18 @@ int  ug_schedule_build(ug_schedule* s, const ug_dvec* scalars, uint64_t first, u
 int  ug_schedule_build_tables(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int c);
 /* ... for strided tables of width c and stride s (ug_bases_create_tables_strided_g1) */
 int  ug_schedule_build_tables_strided(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int c, int stride);
+/* SEVERAL SCALAR VECTORS in one schedule (batched proofs: the witnesses of several proofs multiply the same bases): `vectors`
+ * (1 .. 16) vectors of `count` scalars each, vector v at scalars [first + v * vector_stride, .. + count), vector_stride >= count;
+ * every vector stands for the same global indices [first, first + count). table_c = 0: classic windows; otherwise window tables
+ * of width table_c and stride `stride`. vectors = 1 is exactly ug_schedule_build / ug_schedule_build_tables_strided. Vector v's
+ * digits go to bucket sets of its own, so ONE sort, one accumulation launch per product and one set of tails serve all of them.
+ * Every product over such a schedule -- ug_msm_g1 / _g2, ug_msm_batch, ug_msm_batch_enqueue, ug_msm_group_enqueue,
+ * ug_msm_witness_enqueue -- writes `vectors` CONSECUTIVE records into each of its outputs, record v = the product over vector v
+ * (64 bytes each for G1, 128 for G2). Limits (the call fails otherwise): vectors * count * ceil(255 / c) <= 2^30 digits, fewer
+ * than 2^31 buckets over all vectors, and at most 127 bucket sets over all vectors (classic windows: vectors * windows). No
+ * bucket classes (ug_schedule_set_classes). ug_plan_proof_batch sizes V for a prover. */
+int  ug_schedule_build_vectors(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int vectors, uint64_t vector_stride,
+                               int table_c, int stride);
 /* BUCKET CLASSES (a many-device prover that shards the witness products by bucket instead of by base point; DESIGN.md section 7,
  * no counterpart in the reference): every later build of the schedule keeps only the (scalar, window) digits whose bucket
  * b = |digit| - 1 has b mod 2^q_log in [first_residue, first_residue + residues) -- except the lowest `specials` (<= 64) bucket ids

@@ -153,6 +153,27 @@ class _ProverBase:
             raise ProverError(rc, err.value.decode(errors="replace"))
         return proof.raw.split(b"\0", 1)[0].decode(), pub.raw.split(b"\0", 1)[0].decode()
 
+    def prove_batch(self, wtns_list, proof_size=None, public_size=None):
+        """ug_groth16_prover_prove_batch: [(proof_json, public_json), ...], one pair per witness, each what prove() returns for it
+        (several witnesses per device pass on a created Groth16 prover, one after the other on any other handle)"""
+        k = len(wtns_list)
+        keep = [bytes(w) for w in wtns_list]
+        wb = (C.c_char_p * max(k, 1))(*keep)
+        ws = (C.c_ulonglong * max(k, 1))(*[len(w) for w in keep])
+        psz = (C.c_ulonglong * max(k, 1))(*([self._proof_size() if proof_size is None else proof_size] * k))
+        qsz = (C.c_ulonglong * max(k, 1))(*([self._public_size if public_size is None else public_size] * k))
+        proofs = [C.create_string_buffer(max(psz[i], 1)) for i in range(k)]
+        pubs = [C.create_string_buffer(max(qsz[i], 1)) for i in range(k)]
+        pb = (C.c_void_p * max(k, 1))(*[C.cast(b, C.c_void_p) for b in proofs])
+        qb = (C.c_void_p * max(k, 1))(*[C.cast(b, C.c_void_p) for b in pubs])
+        err = C.create_string_buffer(1024)
+        rc = load().ug_groth16_prover_prove_batch(self._h, k, wb, ws, pb, psz, qb, qsz, err, len(err) - 1)
+        if rc != PROVER_OK:
+            e = ProverError(rc, err.value.decode(errors="replace"))
+            e.proof_sizes, e.public_sizes = list(psz[:k]), list(qsz[:k])
+            raise e
+        return [(p.raw.split(b"\0", 1)[0].decode(), q.raw.split(b"\0", 1)[0].decode()) for p, q in zip(proofs, pubs)]
+
     # the phases of a proof on a witness that stays resident in HBM (include/prover.h: ug_groth16_prover_load_witness / _run /
     # _finish; bench.py times run + finish): available on every prover object
     def load_witness(self, wtns):
@@ -631,6 +652,24 @@ def plan_window_tables(groups, budget):
     return [(out[i].c, out[i].stride, out[i].bytes) for i in range(k)]
 
 
+BATCH_MAX = 16          # include/ultragroth_hip.h: UG_BATCH_MAX
+
+
+class _BatchSchedule(C.Structure):
+    _fields_ = [("scalars", C.c_uint64), ("c", C.c_int), ("stride", C.c_int)]
+
+
+def plan_proof_batch(schedules, n_vars, domain, free_bytes, requested):
+    """ug_plan_proof_batch (host only): schedules = [(scalars, c, stride), ...] (c = 0: classic windows) -> witnesses per device
+    pass, 1 <= V <= min(requested, BATCH_MAX)"""
+    k = len(schedules)
+    arr = (_BatchSchedule * max(k, 1))(*[_BatchSchedule(*s) for s in schedules])
+    v = load().ug_plan_proof_batch(arr, k, n_vars, domain, free_bytes, requested)
+    if v < 1:
+        raise ValueError("ug_plan_proof_batch: bad arguments")
+    return v
+
+
 class Device:
     """A ug_ctx plus convenience wrappers in the reference's byte formats."""
 
@@ -683,8 +722,9 @@ class Device:
         return g
 
     def msm_group(self, group, schedule):
-        """the K sums of a base group over a schedule (ug_msm_group_enqueue + ug_ctx_collect): K affine records"""
-        outs = [C.create_string_buffer(64) for _ in range(group.members)]
+        """the K sums of a base group over a schedule (ug_msm_group_enqueue + ug_ctx_collect): K affine records (V records each
+        over a schedule of V vectors)"""
+        outs = [C.create_string_buffer(64 * getattr(schedule, "vectors", 1)) for _ in range(group.members)]
         arr = (C.c_void_p * group.members)(*[C.cast(o, C.c_void_p) for o in outs])
         _check(self._L.ug_msm_group_enqueue(self._h, group.h, schedule.h, arr))
         _check(self._L.ug_ctx_collect(self._h))
@@ -726,6 +766,28 @@ class Device:
             _check(self._L.ug_schedule_build(h, dvec.h, first, count))
         return s
 
+    def schedule_vectors(self, dvec, first, count, vectors, vector_stride, table_c=0, table_stride=1):
+        """ug_schedule_build_vectors: `vectors` scalar vectors of `count` scalars, vector v at first + v * vector_stride; products
+        over the schedule return `vectors` consecutive records"""
+        h = C.c_void_p()
+        _check(self._L.ug_schedule_create(self._h, C.byref(h)))
+        s = _Handle(h, self._L.ug_schedule_destroy, self)
+        _check(self._L.ug_schedule_build_vectors(h, dvec.h, first, count, vectors, vector_stride, table_c, table_stride))
+        s.vectors = vectors
+        return s
+
+    def gather_index_at(self, out, out_first, src, host_index):
+        """ug_index_create + ug_dvec_gather_index_at: out[out_first + i] = src[host_index[i]]"""
+        import numpy as np
+        idx = np.ascontiguousarray(host_index, dtype=np.uint32)
+        h = C.c_void_p()
+        _check(self._L.ug_index_create(self._h, idx.ctypes.data, len(idx), C.byref(h)))
+        try:
+            _check(self._L.ug_dvec_gather_index_at(out.h, out_first, src.h, h))
+            _check(self._L.ug_ctx_sync(self._h))
+        finally:
+            self._L.ug_index_destroy(h)
+
     def table_window(self, n):
         return self._L.ug_msm_table_window(n)
 
@@ -738,7 +800,7 @@ class Device:
         return f.value, t.value
 
     def msm(self, bases, schedule, index_shift=0, g2=False):
-        out = C.create_string_buffer(128 if g2 else 64)
+        out = C.create_string_buffer((128 if g2 else 64) * getattr(schedule, "vectors", 1))
         fn = self._L.ug_msm_g2 if g2 else self._L.ug_msm_g1
         _check(fn(self._h, bases.h, schedule.h, index_shift, out))
         return out.raw
@@ -747,7 +809,7 @@ class Device:
         """ug_msm_batch: several products over one schedule with one host synchronisation; bases_list holds
         (bases handle, is_g2) pairs; returns the affine records"""
         n = len(bases_list)
-        outs = [C.create_string_buffer(128 if g2 else 64) for _, g2 in bases_list]
+        outs = [C.create_string_buffer((128 if g2 else 64) * getattr(schedule, "vectors", 1)) for _, g2 in bases_list]
         arr_b = (C.c_void_p * n)(*[b.h for b, _ in bases_list])
         arr_o = (C.c_void_p * n)(*[C.cast(o, C.c_void_p) for o in outs])
         arr_s = (C.c_int64 * n)(*index_shifts) if index_shifts is not None else None

@@ -29,7 +29,7 @@ INNER_SYMBOLS = [
     "ug_graph_begin", "ug_graph_end", "ug_graph_abort", "ug_graph_valid", "ug_graph_nodes", "ug_graph_launch", "ug_graph_destroy",
     "ug_bases_create_tables_strided_g1", "ug_bases_create_tables_strided_g2", "ug_bases_create_group_strided_g1",
     "ug_bases_precompute_strided", "ug_schedule_build_tables_strided", "ug_bases_tables_bytes_strided", "ug_bases_table_stride",
-    "ug_plan_window_tables",
+    "ug_plan_window_tables", "ug_schedule_build_vectors", "ug_dvec_gather_index_at", "ug_plan_proof_batch",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify"]        # include/verifier.h
 OUTER_SYMBOLS = [
@@ -57,6 +57,7 @@ OUTER_SYMBOLS = [
     "ug_groth16_prover_run_witness_msm", "ug_groth16_prover_run_h_msm", "ug_groth16_prover_hpoly_chain",
     "ug_groth16_prover_hpoly_combine", "ug_groth16_prover_h_range",
     "ug_groth16_prover_witness_msm_begin", "ug_groth16_prover_witness_msm_end",
+    "ug_groth16_prover_prove_batch",
 ]
 
 
@@ -147,6 +148,9 @@ def load():
     L.ug_bases_table_window.argtypes = [vp]
     L.ug_bases_table_stride.argtypes = [vp]
     L.ug_plan_window_tables.argtypes = [vp, C.c_int, u64, vp]
+    L.ug_schedule_build_vectors.argtypes = [vp, vp, u64, u64, C.c_int, u64, C.c_int, C.c_int]
+    L.ug_dvec_gather_index_at.argtypes = [vp, u64, vp, vp]
+    L.ug_plan_proof_batch.argtypes = [vp, C.c_int, u64, u64, u64, C.c_int]
     L.ug_dvec_create.argtypes = [vp, u64, pp]
     L.ug_dvec_upload.argtypes = [vp, vp, u64]
     L.ug_dvec_upload_idle.argtypes = [vp, vp, u64]
@@ -193,6 +197,7 @@ def load():
         getattr(L, n).argtypes = [pp, C.c_char_p, vp, ull]
     for n in ("groth16_prover_prove", "ultra_groth_prover_prove"):
         getattr(L, n).argtypes = [vp, vp, ull, vp, pull, vp, pull, vp, ull]
+    L.ug_groth16_prover_prove_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, ull]
     for n in ("groth16_prover_destroy", "ultra_groth_prover_destroy"):
         getattr(L, n).argtypes = [vp]; getattr(L, n).restype = None
     for n in ("groth16_prover", "ultra_groth_prover"):

@@ -86,6 +86,10 @@ struct DigitPlan {
     u64 set_map, table_map;                                        // window tables: digit w goes to bucket set w mod stride and reads
                                                                    // table w / stride -- 4-bit field w of each map (<= 16 windows)
     int q_log; u32 r0, cnt, specials, sp_lo, sp_hi, special_base;  // bucket classes (q_log = 0: none); special_base = first special bucket id
+    // several scalar vectors (MsmGeometry::vectors > 1; read only by the kernels' vector instantiations): padded scalar i is
+    // element j = i - v vec_count of vector v = i / vec_count (a multiply-high by vec_magic, no division), read at
+    // (v vec_stride + j); its digits go to bucket sets v vec_sets + wset and its entries keep the index j
+    u32 vec_count, vec_magic; int vec_shift; u32 vec_sets; u64 vec_stride;
 };
 
 struct MsmGeometry {
@@ -99,14 +103,23 @@ struct MsmGeometry {
                           // goes to bucket set w mod stride and reads table w / stride, since d 2^(c w) P = 2^(c (w mod s)) (d T_(w / s)):
                           // `stride` bucket sets, a Horner of `stride` steps on the host. stride = 1: one set; stride = windows: one table
     BucketClasses cls;
+    // Several scalar vectors over the same bases (batched proofs): `vectors` vectors of `n / vectors` scalars each, vector v at
+    // scalar offset v * vec_stride. Vector v's digits go to bucket sets v * window_sets() + wset, so a product's result block
+    // holds the window sets of every vector, one vector after the other, and the host makes one Horner per vector. n counts the
+    // scalars of all vectors. (set_vectors after choose / choose_tables; no bucket classes.)
+    int vectors = 1;
+    u64 vec_stride = 0;
     static MsmGeometry choose(u64 n, int force_c = 0);
     static MsmGeometry choose_tables(u64 n, int c, int stride = 1);   // validates 1 <= stride <= windows
     static int table_window(u64 n);                                    // cost-model window width for the tables mode
     static int table_count(int c, int stride) { const int w = (255 + c - 1) / c; return (w + stride - 1) / stride; }
     void set_classes(const BucketClasses& k);                          // after choose / choose_tables (divides `buckets`)
+    void set_vectors(int v, u64 stride);                               // after choose / choose_tables (n: the scalars per vector)
+    u64 vector_count() const { return n / (u64)vectors; }
     int window_sets() const { return tables ? stride : windows; }      // Horner steps on the host
     int class_sets() const { return cls.on() ? (int)cls.cnt : 1; }
-    int bucket_windows() const { return window_sets() * class_sets(); }      // bucket sets the reduction sees: set (w, j) = w * class_sets + j
+    int bucket_windows() const { return window_sets() * class_sets() * vectors; }  // bucket sets the reduction sees: set (w, j) = w * class_sets + j
+                                                                                   // (vectors: set (v, w) = v * window_sets + w)
     u64 special_buckets() const { return cls.on() ? (u64)window_sets() * cls.specials : 0; }     // ids behind the regular sets
     u64 total_buckets() const { return (u64)bucket_windows() * buckets + special_buckets(); }
     // points of a product's result block: S1 per set; with classes also S0 per set and one weighted sum of the specials per window
@@ -121,9 +134,17 @@ struct MsmGeometry {
             for (int w = 0; w < windows && w < 16; w++) { d.set_map |= (u64)(w % stride) << (4 * w); d.table_map |= (u64)(w / stride) << (4 * w); }
         d.q_log = cls.q_log; d.r0 = cls.r0; d.cnt = cls.on() ? cls.cnt : 1; d.specials = cls.on() ? cls.specials : 0;
         d.sp_lo = cls.sp_lo; d.sp_hi = cls.sp_hi; d.special_base = (u32)((u64)bucket_windows() * buckets);
+        d.vec_count = (u32)vector_count(); d.vec_magic = 0; d.vec_shift = 0; d.vec_sets = (u32)window_sets(); d.vec_stride = vec_stride;
+        if (vectors > 1) {     // i / vec_count = (mulhi(i, magic) + i) >> shift for every i < 2^32 (round-up reciprocal)
+            int l = 0;
+            while (((u64)1 << l) < (u64)d.vec_count) l++;
+            d.vec_magic = (u32)((((u64)1 << 32) * (((u64)1 << l) - d.vec_count)) / d.vec_count + 1);
+            d.vec_shift = l;
+        }
         return d;
     }
 };
+constexpr int MSM_MAX_VECTORS = 16;                                   // scalar vectors of one schedule (batched proofs)
 constexpr int TABLE_INDEX_BITS = 27;                                   // entry = index | table << 27 | sign << 31
 constexpr int TABLE_MIN_C = 16, TABLE_MAX_C = 24;                      // <= 16 tables (4 bits), <= 2^23 buckets
 // Modelled cost of one MSM of n scalars in mixed additions (msm.hip): classic windows (tables = false), or window tables of
@@ -222,9 +243,11 @@ struct MsmPending {
     bool g2 = false;
     bool empty = true;           // nothing was queued: the sum is the point at infinity
     int c = 0, window_sets = 0, class_sets = 1;
+    int vectors = 1;             // the block holds the window sets of `vectors` scalar vectors, one after the other
     BucketClasses cls;           // cls.on(): the block holds [S1 per set | S0 per set | specials per window] (MsmGeometry::result_points)
     u32* host = nullptr;
 };
+constexpr int MSM_G2_PT_WORDS = 72;                 // words of a G2 XYZZ point in a result block (msm.hip: G2Cfg)
 constexpr size_t MSM_PENDING_WORDS = 128 * 72;      // room for the largest result block (<= 127 G2 points); the LAST word
                                                     // receives the schedule's failure flag (meta[7])
 MsmPending msm_enqueue_g1(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream,
@@ -246,8 +269,9 @@ void msm_enqueue_group_g1(const MsmSchedule& s, MsmWorkspace& ws, int members, c
                           MsmStats* stats, u32* const* pinned_host, MsmPending* pend, int phase = MSM_PHASE_ALL);
 // 64-byte records of one member set -> record (slot0 + i) * members + member of a group array
 void interleave_points_g1(u32* dst, const u32* src, u64 n, int members, int member, u64 slot0, hipStream_t stream);
-G1XYZZ msm_collect_g1(const MsmPending& p);
-G2XYZZ msm_collect_g2(const MsmPending& p);
+// (vector: which scalar vector's sum, below p.vectors)
+G1XYZZ msm_collect_g1(const MsmPending& p, int vector = 0);
+G2XYZZ msm_collect_g2(const MsmPending& p, int vector = 0);
 
 // sum over the schedule's scalars (local index i) of scalar_i * base[i + delta]; bases is a device array
 // of n_bases packed affine records in device Montgomery form ((0,0) = infinity); entries whose base

@@ -862,6 +862,22 @@ void MsmGeometry::set_classes(const BucketClasses& k) {
     if ((size_t)result_points() * 72 > MSM_PENDING_WORDS - 1) throw std::invalid_argument("msm: too many bucket sets for one result block");
 }
 
+static_assert(G2Cfg::PT_WORDS == MSM_G2_PT_WORDS, "internal.hpp: MSM_G2_PT_WORDS");
+void MsmGeometry::set_vectors(int v, u64 stride) {
+    vectors = 1; vec_stride = 0;
+    if (v == 1) return;
+    if (v < 1 || v > MSM_MAX_VECTORS) throw std::invalid_argument("msm: vectors outside [1, " + std::to_string(MSM_MAX_VECTORS) + "]");
+    if (cls.on()) throw std::invalid_argument("msm: bucket classes cannot be combined with several scalar vectors");
+    if (stride < n) throw std::invalid_argument("msm: vector stride below the scalars per vector");
+    if (n == 0) throw std::invalid_argument("msm: several vectors of no scalars");
+    const u64 total = n * (u64)v;
+    if (total * (u64)windows > ((u64)1 << 30)) throw std::invalid_argument("msm: vectors * n * windows exceeds 2^30 entries");
+    if ((u64)window_sets() * (u64)v * buckets >= ((u64)1 << 31)) throw std::invalid_argument("msm: more than 2^31 buckets over all vectors");
+    if ((size_t)window_sets() * (size_t)v * MSM_G2_PT_WORDS > MSM_PENDING_WORDS - 1)
+        throw std::invalid_argument("msm: too many bucket sets over all vectors for one result block");
+    vectors = v; vec_stride = stride; n = total;
+}
+
 // ---- schedule -----------------------------------------------------------------------------------------------
 void MsmSchedule::reserve(const MsmGeometry& g) {
     u64 total = g.n * g.windows;
@@ -891,7 +907,7 @@ void MsmSchedule::build(const u32* scalars_dev, const MsmGeometry& g, hipStream_
     // limits first: reserve() hands `total` to the sort as an int
     // (2^30: a look-back status word of the sort carries a 30-bit pair count, sort.hip -- one bin may hold every pair)
     if (g.n * (u64)g.windows > ((u64)1 << 30)) throw std::invalid_argument("msm: n * windows exceeds 2^30 entries");
-    if (g.n > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("msm: more than 2^27 scalars in one schedule");
+    if (g.vector_count() > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("msm: more than 2^27 scalars in one schedule");
     geo = g;
     reserve(g);
     log_seg = segment_log(g.expected_entries());
@@ -1015,7 +1031,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const 
     for (int j = 0; j < count; j++) {
         pend[j] = MsmPending();
         pend[j].g2 = Cfg::PT_WORDS == G2Cfg::PT_WORDS;
-        pend[j].c = g.c; pend[j].window_sets = g.window_sets(); pend[j].class_sets = g.class_sets(); pend[j].cls = g.cls;
+        pend[j].c = g.c; pend[j].window_sets = g.window_sets(); pend[j].class_sets = g.class_sets(); pend[j].cls = g.cls; pend[j].vectors = g.vectors;
         pend[j].host = pinned_host[j];
         if (g.n == 0 || n_bases[group ? 0 : j] == 0) continue;
         if ((size_t)g.result_points() * Cfg::PT_WORDS > MSM_PENDING_WORDS - 1) throw std::logic_error("msm: result block too large");
@@ -1153,14 +1169,17 @@ MsmPending msm_enqueue(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases,
 // window's sum is put together from its owned residues' sets: a digit in residue r = r0 + j, local bucket k, has the magnitude
 // Q (k + 1) - m_j with m_j = Q - 1 - r0 - j, so the window's sum is  Q * sum_j S1_j  -  sum_j m_j S0_j  +  the specials' sum;
 // m_j falls by one per set, so the middle term is m_last * (sum of all S0) plus the running sums of S0_0 .. S0_(cnt-2).
+// Several scalar vectors (vector < p.vectors): vector v's sets follow those of the vectors before it.
 template <class Cfg>
-XYZZ<typename Cfg::F> msm_collect(const MsmPending& p) {
+XYZZ<typename Cfg::F> msm_collect(const MsmPending& p, int vector = 0) {
     typedef typename Cfg::F F;
     XYZZ<F> acc = xyzz_inf<F>();
     if (p.empty) return acc;
     if (p.host[MSM_PENDING_WORDS - 1]) throw std::runtime_error("msm: the schedule's sort gave up waiting for a tile (look-back timeout)");
+    if (vector < 0 || vector >= p.vectors) throw std::logic_error("msm: vector index");
     const int sets = p.window_sets * p.class_sets;
-    auto point = [&](int idx) { return Cfg::from_words(p.host + (size_t)idx * Cfg::PT_WORDS, 1); };
+    const u32* block = p.host + (size_t)vector * sets * Cfg::PT_WORDS;
+    auto point = [&](int idx) { return Cfg::from_words(block + (size_t)idx * Cfg::PT_WORDS, 1); };
     for (int w = p.window_sets - 1; w >= 0; w--) {
         for (int k = 0; k < p.c; k++) acc = xyzz_dbl(acc);
         if (!p.cls.on()) { acc = xyzz_add(acc, point(w)); continue; }
@@ -1273,8 +1292,8 @@ void msm_enqueue_group_g1(const MsmSchedule& s, MsmWorkspace& ws, int members, c
     const int64_t d[MSM_MAX_BATCH] = {delta, delta, delta, delta};
     msm_enqueue_multi<G1Cfg>(s, ws, members, b, n, d, stream, stats, pinned_host, pend, members, phase);
 }
-G1XYZZ msm_collect_g1(const MsmPending& p) { return msm_collect<G1Cfg>(p); }
-G2XYZZ msm_collect_g2(const MsmPending& p) { return msm_collect<G2Cfg>(p); }
+G1XYZZ msm_collect_g1(const MsmPending& p, int vector) { return msm_collect<G1Cfg>(p, vector); }
+G2XYZZ msm_collect_g2(const MsmPending& p, int vector) { return msm_collect<G2Cfg>(p, vector); }
 
 G1XYZZ msm_g1(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream, MsmStats* stats) {
     return msm_run<G1Cfg>(s, ws, bases, n_bases, delta, stream, stats);

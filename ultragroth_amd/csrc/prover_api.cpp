@@ -507,9 +507,12 @@ bool fusedGroups() {
 // The witness products of one schedule, queued on ctx (results after ug_ctx_collect): the G1 sets -- as the interleaved group
 // d.G when the prover holds one (outC null: a two-member group), else d.A, d.B1 and, with outC, d.C shifted by shiftC --
 // and the G2 set d.B2; g2First queues the G2 product ahead of the G1 ones.
+// A batch (vectors > 1: sw holds `vectors` witnesses, `witness` them at witnessStride signals apart) writes `vectors` records into
+// every output; with sparse B the B scalars of witness v are gathered into wBBatch at v * (compacted size).
 void buildSchedule(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int tableC, int stride = 1);
 void enqueueWitnessProducts(DeviceProver& d, ug_ctx* ctx, const ug_schedule* sw, uint8_t* outA, uint8_t* outB1, uint8_t* outB2, uint8_t* outC,
-                            int64_t shiftC, bool g2First, const ug_dvec* witness = nullptr) {
+                            int64_t shiftC, bool g2First, const ug_dvec* witness = nullptr, int vectors = 1, uint64_t witnessStride = 0,
+                            ug_dvec* wBBatch = nullptr) {
     if (d.Bc2) {
         // sparse B: [A | C] over the witness schedule; the B scalars gathered by signal number, a schedule over them, B1 and B2
         // over that one (src/groth16.cpp:58,61 with the points at infinity left out: the sums are the same)
@@ -522,8 +525,20 @@ void enqueueWitnessProducts(DeviceProver& d, ug_ctx* ctx, const ug_schedule* sw,
             void* outsA[1] = {outA};
             ugCheck(ug_msm_batch_enqueue(ctx, 1, setA, sw, nullptr, outsA));
         }
-        ugCheck(ug_dvec_gather_index(d.wB, witness, d.bIdx));
-        buildSchedule(d.sB, d.wB, 0, ug_dvec_size(d.wB), d.tableB, d.strideB);
+        if (vectors > 1) {
+            const uint64_t nB = ug_dvec_size(d.wB);
+            for (int v = 0; v < vectors; v++) {
+                ug_dvec* wv = nullptr;            // (a view: the queued gather keeps the address, not the view)
+                ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(witness) + (uint64_t)v * witnessStride * 32, witnessStride, &wv));
+                const int rc = ug_dvec_gather_index_at(wBBatch, (uint64_t)v * nB, wv, d.bIdx);
+                ug_dvec_destroy(wv);
+                ugCheck(rc);
+            }
+            ugCheck(ug_schedule_build_vectors(d.sB, wBBatch, 0, nB, vectors, nB, d.tableB, d.strideB));
+        } else {
+            ugCheck(ug_dvec_gather_index(d.wB, witness, d.bIdx));
+            buildSchedule(d.sB, d.wB, 0, ug_dvec_size(d.wB), d.tableB, d.strideB);
+        }
         const ug_bases* sets[2] = {d.Bc1, d.Bc2};
         void* outsB[2] = {outB1, outB2};
         ugCheck(ug_msm_batch_enqueue(ctx, 2, sets, d.sB, nullptr, outsB));
@@ -629,6 +644,21 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
         bracket.begin();
         prove(wtns, wtnsSize, proof, pub);
         bracket.end();
+    }
+    // k proofs in one call (ug_groth16_prover_prove_batch): outputs as k proveTurn calls in order. This form proves them one
+    // after the other, each witness checked when its proof starts (an error names its position; the proofs before it have run);
+    // Groth16Prover checks every witness first and runs several witnesses per device pass.
+    virtual void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
+                            std::vector<std::string>& pubs) {
+        proofs.assign(k, std::string()); pubs.assign(k, std::string());
+        for (int b = 0; b < k; b++) {
+            const std::string at = "witness " + std::to_string(b) + ": ";
+            try {
+                proveTurn(wtns[b], sizes[b], proofs[b], pubs[b]);
+            } catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
+            catch (ShortBufferException&) { throw; }
+            catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
+        }
     }
     virtual unsigned long long proofBufferMinSize() const = 0;
     virtual unsigned long long publicBufferMinSize() const = 0;
@@ -1097,6 +1127,7 @@ public:
         return group == 0 ? pendingW_.load() : group == 1 ? pendingH_.load() : group == 2 ? pendingB_.load() : 0;
     }
     void trimWorkspaces() override {
+        std::lock_guard<std::mutex> batch(batchMutex_);     // (a batch call owns the batch buffers it stages into)
         TurnRequest mine(wantTurn_);
         std::lock_guard<std::mutex> turn(proveMutex);
         dropGraphs();                                   // (they hold pointers into what goes now)
@@ -1104,6 +1135,7 @@ public:
         if (d_.sB) ug_schedule_trim(d_.sB);
         ug_ctx_trim(d_.ctx); ug_ctx_trim(d_.ctx2);
         witness_.trim(wCur_);
+        releaseBatch();
     }
 
     const ZkeyHeader& header() const { return hdr_; }
@@ -1493,6 +1525,173 @@ public:
         finishWith(partials, r, s, terms.get(), proof, pub, &publicPart);
     }
 
+    // ---- batched proofs (ug_groth16_prover_prove_batch) ----
+    // Every witness is parsed and checked first: a bad one fails the call before anything is queued. Then each device pass takes
+    // up to ug_plan_proof_batch witnesses, under the prover's turn as a single proof: ONE V-vector witness schedule and its
+    // products, one ug_hpoly_run per witness into V slices of the batch h buffer, ONE V-vector H schedule and product, one
+    // collect per context. r and s are drawn in witness order (r0, s0, r1, s1, ...) and their multiples of delta formed on host
+    // threads beside the device work. A pass of one witness, or a circuit proved in pieces, takes the single-proof path.
+    void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
+                    std::vector<std::string>& pubs) override {
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<const uint8_t*> data((size_t)k);
+        for (int b = 0; b < k; b++) {
+            const std::string at = "witness " + std::to_string(b) + ": ";
+            try {
+                BinFile f(wtns[b], sizes[b], "wtns", 2);
+                data[(size_t)b] = witnessData(f);
+            } catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
+            catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
+        }
+        proofs.assign((size_t)k, std::string()); pubs.assign((size_t)k, std::string());
+        // the batch buffers belong to one batch call at a time; the witnesses of a pass are copied into them BEFORE the pass takes
+        // the prover's turn (as a single proof stages its witness), so another caller's kernels may run meanwhile
+        std::lock_guard<std::mutex> batchLock(batchMutex_);
+        double msm = 0, fft = 0;
+        for (int b0 = 0; b0 < k;) {
+            int V = 1;
+            {
+                std::unique_lock<std::mutex> turn;
+                { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
+                V = batchPerPass(k - b0);
+                if (V > 1) reserveBatch(V);
+            }
+            if (V <= 1) {                                   // the single-proof path
+                proveOneInBatch(wtns[b0], sizes[b0], proofs[(size_t)b0], pubs[(size_t)b0], msm, fft);
+                b0++;
+                continue;
+            }
+            stageBatch(data.data() + b0, V);                // (no turn held: nothing queued reads the batch buffers)
+            std::unique_lock<std::mutex> turn;
+            { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
+            callerHasTheTurn();
+            V = std::min(V, batchPerPass(V));               // (the table plan may have changed meanwhile: the rest is staged again)
+            if (V <= 1) continue;
+            std::vector<uint8_t> r((size_t)V * 32), sb((size_t)V * 32);
+            for (int v = 0; v < V; v++) { drawBlinding(&r[(size_t)v * 32]); drawBlinding(&sb[(size_t)v * 32]); }      // S11, in witness order
+            std::vector<std::future<BlindingTerms>> terms;
+            for (int v = 0; v < V; v++)
+                terms.push_back(std::async(std::launch::async, [&, v] { return blindingTerms(hdr_, &r[(size_t)v * 32], &sb[(size_t)v * 32]); }));
+            std::vector<uint8_t> parts((size_t)V * UG_GROTH16_PARTIALS_SIZE);
+            runBatch(V, parts.data());                      // (the futures join in their destructors if this throws)
+            msm += m1_ + m2_; fft += f1_ + f2_;
+            turn.unlock();
+            for (int v = 0; v < V; v++) {
+                const uint8_t* w = data[(size_t)(b0 + v)];
+                const std::vector<uint8_t> publicPart(w, w + ((size_t)hdr_.nPublic + 1) * 32);
+                finishWith(&parts[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &r[(size_t)v * 32], &sb[(size_t)v * 32], terms[(size_t)v].get(),
+                           proofs[(size_t)(b0 + v)], pubs[(size_t)(b0 + v)], &publicPart);
+            }
+            b0 += V;
+        }
+        // the call's figures for ug_prover_last_timings, written under the turn as every proof writes them
+        TurnRequest mine(wantTurn_);
+        std::lock_guard<std::mutex> turn(proveMutex);
+        m1_ = msm; f1_ = fft; m2_ = f2_ = 0;
+        totalMs_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    // one witness of a batch on the single-proof path (proveTurn), its device times added to msm / fft while it holds the turn
+    void proveOneInBatch(const void* wtns, unsigned long long wtnsSize, std::string& proof, std::string& pub, double& msm, double& fft) {
+        WitnessLease lease(witness_);
+        stage(*lease, wtns, wtnsSize);
+        std::unique_lock<std::mutex> turn;
+        { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
+        callerHasTheTurn();
+        adopt(*lease);
+        proveLoaded(proof, pub, [&] {
+            msm += m1_ + m2_; fft += f1_ + f2_;
+            turn.unlock();
+        });
+    }
+    // witnesses per device pass for up to `requested` (proveMutex held: the schedules' current table plan)
+    int batchPerPass(int requested) {
+        const uint64_t nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
+        if (requested <= 1 || nw > maxRange_ || nh > maxRange_ || !haveHpoly_ || count_ > 1 || haveLayout_) return 1;
+        std::vector<ug_batch_schedule> sch;
+        sch.push_back(ug_batch_schedule{nw, tableW_, strideW_});
+        sch.push_back(ug_batch_schedule{nh, tableH_, strideH_});
+        if (sparseB_) sch.push_back(ug_batch_schedule{nB_, d_.tableB, d_.strideB});
+        uint64_t freeB = 0, totalB = 0;
+        ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
+        for (ug_dvec* v : {wBatch_, hBatch_, wBBatch_}) if (v) freeB += ug_dvec_size(v) * 32;      // (reused or replaced)
+        // window tables the background builder has still to take into use keep their room: a batch that lands before them must
+        // not take the memory they are planned in (their allocation would fail and the prover stay on classic windows)
+        uint64_t pending = 0;
+        for (int g = 0; g < 3; g++) {
+            int c = 0, st = 0, ready = 1;
+            uint64_t bytes = 0;
+            if (tablePlan(g, &c, &st, &bytes, &ready) && !ready) pending += bytes;
+        }
+        freeB = freeB > pending ? freeB - pending : 0;
+        const int V = ug_plan_proof_batch(sch.data(), (int)sch.size(), hdr_.nVars, hdr_.domainSize, freeB, requested);
+        if (V < 1) throw std::logic_error("batch plan failed");
+        return V;
+    }
+    // batch buffer of at least n elements (a smaller one is replaced)
+    void ensureBatch(ug_dvec*& v, ug_ctx* ctx, uint64_t n) {
+        if (v && ug_dvec_size(v) >= n) return;
+        ug_dvec_destroy(v); v = nullptr;
+        ugCheck(ug_dvec_create(ctx, n, &v));
+    }
+    void releaseBatch() { ug_dvec_destroy(wBatch_); ug_dvec_destroy(hBatch_); ug_dvec_destroy(wBBatch_); wBatch_ = hBatch_ = wBBatch_ = nullptr; }
+    // the batch buffers for V witnesses (proveMutex held: an allocation may not happen while kernels of a proof are queued)
+    void reserveBatch(int V) {
+        ensureBatch(wBatch_, d_.ctx, (uint64_t)V * hdr_.nVars);
+        ensureBatch(hBatch_, d_.ctx2, (uint64_t)V * hdr_.domainSize);
+        if (d_.Bc2) ensureBatch(wBBatch_, d_.ctx, (uint64_t)V * nB_);
+    }
+    // the V witnesses into the batch witness buffer, on the uploader's own streams (batchMutex_ held, no turn: the last pass
+    // that read the buffer has been collected)
+    void stageBatch(const uint8_t* const* data, int V) {
+        const uint64_t nv = hdr_.nVars;
+        for (int v = 0; v < V; v++) {
+            ug_dvec* view = nullptr;
+            ugCheck(ug_dvec_wrap(d_.ctx, (uint8_t*)ug_dvec_device_ptr(wBatch_) + (uint64_t)v * nv * 32, nv, &view));
+            const int rc = ug_dvec_upload_idle(view, data[v], nv);
+            ug_dvec_destroy(view);
+            ugCheck(rc);
+        }
+    }
+    // one device pass of the V staged witnesses; parts = V blocks A | B1 | B2 | C | H as run() leaves them
+    void runBatch(int V, uint8_t* parts) {
+        const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize, nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
+        const char* ov = getenv("ULTRAGROTH_OVERLAP");
+        const int overlap = ov ? atoi(ov) : 1;
+        resetTimings();
+        std::vector<uint8_t> outA((size_t)V * 64), outB1((size_t)V * 64), outB2((size_t)V * 128), outC((size_t)V * 64), outH((size_t)V * 64);
+        std::vector<ug_dvec*> views;
+        struct Views { std::vector<ug_dvec*>& v; ~Views() { for (ug_dvec* x : v) ug_dvec_destroy(x); } } viewsGuard{views};
+        auto view = [&](ug_ctx* ctx, ug_dvec* of, uint64_t first, uint64_t n) {
+            views.push_back(nullptr);
+            ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(of) + first * 32, n, &views.back()));
+            return views.back();
+        };
+        {
+            QueueGuard inFlight(d_.ctx, d_.ctx2);
+            ugCheck(ug_schedule_build_vectors(d_.sw, wBatch_, wr_.lo, nw, V, nv, tableW_, strideW_));
+            enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), outC.data(), (int64_t)hdr_.nPublic + 1,
+                                   overlap == 2, wBatch_, V, nv, wBBatch_);
+            if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
+            for (int v = 0; v < V; v++)
+                ugCheck(ug_hpoly_run(d_.hp, view(d_.ctx2, wBatch_, (uint64_t)v * nv, nv), view(d_.ctx2, hBatch_, (uint64_t)v * dom, dom)));
+            ugCheck(ug_schedule_build_vectors(d_.sh, hBatch_, hr_.lo, nh, V, dom, tableH_, strideH_));
+            if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
+            const ug_bases* sets[1] = {d_.H};
+            void* outs[1] = {outH.data()};
+            ugCheck(ug_msm_batch_enqueue(d_.ctx2, 1, sets, d_.sh, nullptr, outs));
+            ugCheck(ug_ctx_collect(d_.ctx2));
+            ugCheck(ug_ctx_collect(d_.ctx));
+            inFlight.done();
+        }
+        collectTimings(3);
+        for (int v = 0; v < V; v++) {
+            uint8_t* p = parts + (size_t)v * UG_GROTH16_PARTIALS_SIZE;
+            memset(p, 0, UG_GROTH16_PARTIALS_SIZE);
+            memcpy(p, &outA[(size_t)v * 64], 64); memcpy(p + 64, &outB1[(size_t)v * 64], 64); memcpy(p + 128, &outB2[(size_t)v * 128], 128);
+            memcpy(p + 256, &outC[(size_t)v * 64], 64); memcpy(p + 320, &outH[(size_t)v * 64], 64);
+        }
+    }
+
     unsigned long long proofBufferMinSize() const override { return PROOF_MIN_GROTH16; }
     unsigned long long publicBufferMinSize() const override { return publicMin(hdr_.nPublic); }
     void timings(double* msm, double* fft, double* total) const override {
@@ -1548,8 +1747,10 @@ private:
     std::vector<GraphSlot> graphs_;
     std::vector<std::pair<const ug_dvec*, int>> warm_;
     bool statsOn_ = false;
+    ug_dvec *wBatch_ = nullptr, *hBatch_ = nullptr, *wBBatch_ = nullptr;      // batched proofs: V witnesses / h vectors / sparse-B scalars
+    std::mutex batchMutex_;            // one batch call at a time owns them (lock order: batchMutex_ -> witness lease -> proveMutex)
 public:
-    ~Groth16Prover() override { stopTableBuilder(); dropGraphs(); }      // (before d_ goes: both refer to its contexts)
+    ~Groth16Prover() override { stopTableBuilder(); dropGraphs(); releaseBatch(); }      // (before d_ goes: both refer to its contexts)
 };
 
 // =================================================================================================================
@@ -2928,6 +3129,49 @@ int ultra_groth_prover_prove(void* prover_object, const void* wtns_buffer, unsig
                              unsigned long long error_msg_maxsize) {
     return proveImpl(prover_object, wtns_buffer, wtns_size, proof_buffer, proof_size, public_buffer,
                                        public_size, error_msg, error_msg_maxsize);
+}
+
+int ug_groth16_prover_prove_batch(void* prover_object, int count, const void* const* wtns_buffers, const unsigned long long* wtns_sizes,
+                                  char* const* proof_buffers, unsigned long long* proof_sizes, char* const* public_buffers,
+                                  unsigned long long* public_sizes, char* error_msg, unsigned long long error_msg_maxsize) {
+    API_TRY
+    if (prover_object == NULL) throw std::invalid_argument("Null prover object");
+    if (count < 0) throw std::invalid_argument("Negative witness count");
+    if (count && (!wtns_buffers || !wtns_sizes || !proof_buffers || !proof_sizes || !public_buffers || !public_sizes))
+        throw std::invalid_argument("Null batch argument");
+    for (int b = 0; b < count; b++)
+        if (!wtns_buffers[b] || !proof_buffers[b] || !public_buffers[b])
+            throw std::invalid_argument("Null buffer of witness " + std::to_string(b));
+    ProverBase* prover = static_cast<ProverBase*>(prover_object);
+    // the minimum sizes first, for every witness: a short buffer anywhere fails the call with every needed size written back
+    bool shortMin = false;
+    for (int b = 0; b < count; b++)
+        shortMin |= proof_sizes[b] < prover->proofBufferMinSize() || public_sizes[b] < prover->publicBufferMinSize();
+    if (shortMin) {
+        for (int b = 0; b < count; b++) {
+            proof_sizes[b] = std::max<unsigned long long>(proof_sizes[b], prover->proofBufferMinSize());
+            public_sizes[b] = std::max<unsigned long long>(public_sizes[b], prover->publicBufferMinSize());
+        }
+        throw ShortBufferException("Proof or public buffer is too short. Minimum sizes: " + std::to_string(prover->proofBufferMinSize()) +
+                                   ", " + std::to_string(prover->publicBufferMinSize()));
+    }
+    std::vector<std::string> proofs, pubs;
+    prover->proveBatch(count, wtns_buffers, wtns_sizes, proofs, pubs);
+    int shortAt = -1;
+    for (int b = 0; b < count; b++)
+        if (proof_sizes[b] < proofs[(size_t)b].length() || public_sizes[b] < pubs[(size_t)b].length()) { shortAt = b; break; }
+    if (shortAt >= 0) {
+        for (int b = 0; b < count; b++) {
+            proof_sizes[b] = std::max<unsigned long long>(proof_sizes[b], proofs[(size_t)b].length());
+            public_sizes[b] = std::max<unsigned long long>(public_sizes[b], pubs[(size_t)b].length());
+        }
+        throw ShortBufferException("Proof or public buffer of witness " + std::to_string(shortAt) + " is too short");
+    }
+    for (int b = 0; b < count; b++) {
+        std::strncpy(proof_buffers[b], proofs[(size_t)b].c_str(), proof_sizes[b]);
+        std::strncpy(public_buffers[b], pubs[(size_t)b].c_str(), public_sizes[b]);
+    }
+    API_CATCH
 }
 
 void groth16_prover_destroy(void* prover_object) { delete static_cast<ProverBase*>(prover_object); }

@@ -87,7 +87,9 @@ __device__ __forceinline__ u32 digit_key(const DigitPlan& d, u32 wset, u32 mag, 
 // CW: the window width as a compile-time constant (0: taken from the plan). The widths the provers use at size (22: window
 // tables of 2^24 points; 20: classic windows and many-GPU ranks) get an unrolled window loop with static limb indices -- the
 // runtime form indexes the scalar's limbs dynamically, a chain of selects per window.
-template <int CW, class Fn>
+// VEC: the schedule covers several scalar vectors (DigitPlan::vec_*): scalar i is element j of vector v, its digits go to the
+// bucket sets of vector v and its entries carry j. The single-vector instantiation never reads those fields.
+template <int CW, bool VEC, class Fn>
 __device__ __forceinline__ void recode_scalar(const u32* scalars, u64 i, const DigitPlan& d, Fn&& f) {
     const int windows = CW ? (255 + CW - 1) / CW : d.windows;
     if (i >= d.n) {                                   // padding of the last tile
@@ -95,7 +97,17 @@ __device__ __forceinline__ void recode_scalar(const u32* scalars, u64 i, const D
         return;
     }
     u32 s[10];
-    load8(s, scalars + i * 8);
+    u32 set0 = 0;                                     // VEC: first bucket set of the scalar's vector
+    if constexpr (VEC) {
+        const u32 i32 = (u32)i;                       // (n * windows <= 2^30)
+        const u32 v = (u32)(((u64)__umulhi(i32, d.vec_magic) + i32) >> d.vec_shift);
+        const u32 j = i32 - v * d.vec_count;
+        set0 = v * d.vec_sets;
+        i = j;
+        load8(s, scalars + ((u64)v * d.vec_stride + j) * 8);
+    } else {
+        load8(s, scalars + i * 8);
+    }
     s[8] = 0; s[9] = 0;
     // the group has order r: scalars >= r (never produced by a well-formed witness) are reduced
     for (int it = 0; it < 6 && scalar_geq_r(s); it++) {
@@ -115,7 +127,8 @@ __device__ __forceinline__ void recode_scalar(const u32* scalars, u64 i, const D
         const u32 raw = ((u32)(two >> sh) & mask) + carry;
         // window tables: bucket set w mod stride, table w / stride, looked up in the plan's maps (no division per window; the
         // same for every lane)
-        const u32 wset = d.tables ? (u32)(d.set_map >> (4 * w)) & 15u : (u32)w;
+        u32 wset = d.tables ? (u32)(d.set_map >> (4 * w)) & 15u : (u32)w;
+        if constexpr (VEC) wset += set0;
         const u32 tag = d.tables ? ((u32)(d.table_map >> (4 * w)) & 15u) << TABLE_INDEX_BITS : 0u;
         u32 key, val;
         if (raw > half) {                             // negative digit raw - 2^c, carry into the next window
@@ -134,10 +147,11 @@ __device__ __forceinline__ void recode_scalar(const u32* scalars, u64 i, const D
     }
 }
 
+template <bool VEC>
 __global__ void digit_pairs_kernel(const u32* scalars, DigitPlan d, u32* keys, u32* vals) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d.n) return;
-    recode_scalar<0>(scalars, i, d, [&](int w, u32 key, u32 val) { keys[(u64)w * d.n + i] = key; vals[(u64)w * d.n + i] = val; });
+    recode_scalar<0, VEC>(scalars, i, d, [&](int w, u32 key, u32 val) { keys[(u64)w * d.n + i] = key; vals[(u64)w * d.n + i] = val; });
 }
 
 struct SortHistArgs {
@@ -151,7 +165,7 @@ struct SortHistArgs {
 };
 
 // counts per pass and bin; a grid-stride loop, counters in LDS, one global atomic per (workgroup, pass, bin)
-template <int CW>
+template <int CW, bool VEC>
 __global__ __launch_bounds__(SORT_THREADS) void radix_hist_kernel(SortHistArgs a) {
     __shared__ u32 h[4 * SORT_MAX_BINS];
     for (int i = threadIdx.x; i < 4 * SORT_MAX_BINS; i += SORT_THREADS) h[i] = 0;
@@ -169,7 +183,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_hist_kernel(SortHistArgs a
     if (a.scalars) {
         const u64 lanes = a.n_padded / (u64)a.plan.windows;       // one scalar (all its windows) per lane turn
         for (u64 i = (u64)blockIdx.x * SORT_THREADS + threadIdx.x; i < lanes; i += stride)
-            recode_scalar<CW>(a.scalars, i, a.plan, [&](int, u32 key, u32) { count(key); });
+            recode_scalar<CW, VEC>(a.scalars, i, a.plan, [&](int, u32 key, u32) { count(key); });
     } else {
         for (u64 i = (u64)blockIdx.x * SORT_THREADS + threadIdx.x; i < a.n_padded; i += stride) count(i < a.n_pairs ? a.keys_in[i] : 0xffffffffu);
     }
@@ -189,7 +203,7 @@ __global__ void radix_scan_kernel(u32* hist, int passes, u32* n_valid_out) {
 }
 
 constexpr int LBW = 4;     // look-back window: the status words of four predecessors are read per turn (8 and 16 measured in round 3: no gain)
-template <bool FROM_SCALARS, int CW>
+template <bool FROM_SCALARS, int CW, bool VEC>
 __global__ __launch_bounds__(SORT_THREADS) void radix_pass_kernel(SortPassArgs a) {
     extern __shared__ u32 lds[];
     const int ipt = a.ipt;
@@ -230,7 +244,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_pass_kernel(SortPassArgs a
         for (int sc = 0; sc < a.spl; sc++) {
             const u64 i = ((u64)tile * SORT_THREADS + tid) * (u64)a.spl + (u64)sc;
             const int j0 = sc * a.plan.windows;
-            recode_scalar<CW>(a.scalars, i, a.plan, [&](int w, u32 k, u32 v) {
+            recode_scalar<CW, VEC>(a.scalars, i, a.plan, [&](int w, u32 k, u32 v) {
 #pragma unroll
                 for (int j = 0; j < SORT_MAX_IPT; j++) if (j == j0 + w) { key[j] = k; val[j] = v; }
             });
@@ -368,7 +382,8 @@ int radix_plan(int bits, int* shift, int* bins_log) {
 
 void digit_pairs(const u32* scalars, const DigitPlan& plan, u32* keys, u32* vals, hipStream_t stream) {
     if (!plan.n) return;
-    hipLaunchKernelGGL(digit_pairs_kernel, dim3((unsigned)((plan.n + 255) / 256)), dim3(256), 0, stream, scalars, plan, keys, vals);
+    if (plan.vec_magic) hipLaunchKernelGGL(digit_pairs_kernel<true>, dim3((unsigned)((plan.n + 255) / 256)), dim3(256), 0, stream, scalars, plan, keys, vals);
+    else hipLaunchKernelGGL(digit_pairs_kernel<false>, dim3((unsigned)((plan.n + 255) / 256)), dim3(256), 0, stream, scalars, plan, keys, vals);
     UG_KERNEL_CHECK();
 }
 
@@ -400,6 +415,7 @@ int RadixSorter::sort(const u32* scalars, const MsmGeometry& geo, u32 sentinel, 
                       u32* const buf_keys[2], u32* const buf_vals[2], u32* error_flag, hipStream_t stream, u32* n_valid_out, bool* dropped_out) {
     const int windows = geo.windows;
     const DigitPlan plan = geo.digit_plan();
+    const bool vec = geo.vectors > 1;
     // measurement switches (-DUG_MEASURE builds): pairs per lane of the pair-form passes, scalars per lane of the fused first pass
 #ifndef UG_SORT_IPT_DEFAULT
 #define UG_SORT_IPT_DEFAULT 16
@@ -441,9 +457,13 @@ int RadixSorter::sort(const u32* scalars, const MsmGeometry& geo, u32 sentinel, 
         unsigned blocks = (unsigned)std::min<u64>((lanes + SORT_THREADS - 1) / SORT_THREADS, 2048);
         if (!blocks) blocks = 1;
         const int cw = fused ? (plan.c == 22 || plan.c == 20 ? plan.c : 0) : 0;
-        if (cw == 22) hipLaunchKernelGGL(radix_hist_kernel<22>, dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
-        else if (cw == 20) hipLaunchKernelGGL(radix_hist_kernel<20>, dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
-        else hipLaunchKernelGGL(radix_hist_kernel<0>, dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
+        if (vec) {
+            if (cw == 22) hipLaunchKernelGGL((radix_hist_kernel<22, true>), dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
+            else if (cw == 20) hipLaunchKernelGGL((radix_hist_kernel<20, true>), dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
+            else hipLaunchKernelGGL((radix_hist_kernel<0, true>), dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
+        } else if (cw == 22) hipLaunchKernelGGL((radix_hist_kernel<22, false>), dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
+        else if (cw == 20) hipLaunchKernelGGL((radix_hist_kernel<20, false>), dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
+        else hipLaunchKernelGGL((radix_hist_kernel<0, false>), dim3(blocks), dim3(SORT_THREADS), 0, stream, h);
         UG_KERNEL_CHECK();
         hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(64), 0, stream, hist, passes, drop ? n_valid_out : (u32*)nullptr);
         UG_KERNEL_CHECK();
@@ -486,17 +506,24 @@ int RadixSorter::sort(const u32* scalars, const MsmGeometry& geo, u32 sentinel, 
                 if ((size_t)cap < lds)
                     throw std::runtime_error("radix sort: a tile of " + std::to_string(SORT_THREADS) + " lanes x " + std::to_string(a.ipt) + " pairs needs " +
                                              std::to_string((lds + 1023) / 1024) + " KiB of LDS per workgroup, the device grants " + std::to_string(cap / 1024) + " KiB");
-                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 20>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 22>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 20, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 22, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 20, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<true, 22, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+                UG_HIP(hipFuncSetAttribute((const void*)radix_pass_kernel<false, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
                 if (dev >= 0 && dev < 64) allowed[dev].store(true, std::memory_order_release);
             }
         }
-        if (!first_fused) hipLaunchKernelGGL((radix_pass_kernel<false, 0>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
-        else if (cw == 22) hipLaunchKernelGGL((radix_pass_kernel<true, 22>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
-        else if (cw == 20) hipLaunchKernelGGL((radix_pass_kernel<true, 20>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
-        else hipLaunchKernelGGL((radix_pass_kernel<true, 0>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+        if (!first_fused) hipLaunchKernelGGL((radix_pass_kernel<false, 0, false>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+        else if (vec) {
+            if (cw == 22) hipLaunchKernelGGL((radix_pass_kernel<true, 22, true>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+            else if (cw == 20) hipLaunchKernelGGL((radix_pass_kernel<true, 20, true>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+            else hipLaunchKernelGGL((radix_pass_kernel<true, 0, true>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+        } else if (cw == 22) hipLaunchKernelGGL((radix_pass_kernel<true, 22, false>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+        else if (cw == 20) hipLaunchKernelGGL((radix_pass_kernel<true, 20, false>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
+        else hipLaunchKernelGGL((radix_pass_kernel<true, 0, false>), dim3(grid), dim3(SORT_THREADS), lds, stream, a);
         UG_KERNEL_CHECK();
         cur = dst;
     }

@@ -607,6 +607,45 @@ int ug_plan_window_tables(const ug_table_group* groups, int n_groups, uint64_t b
     }
     UG_CATCH
 }
+// Witnesses per device pass of a batched proof (include/ultragroth_hip.h): the largest V <= min(requested, 16) for which every
+// schedule group's V-vector schedule keeps its limits and the V-fold buffers fit the free bytes
+namespace {
+constexpr u64 BATCH_PAIR_BYTES = 64;      // per (scalar, window) pair: four sort arrays (16) + accumulation slots of 3 G1 and 1 G2 products
+constexpr u64 BATCH_BUCKET_BYTES = 732;   // per bucket: start, count, list (12) + points of 3 G1 (3 x 144) and 1 G2 (288) products
+u64 batch_bytes(const ug_batch_schedule* s, int n, uint64_t n_vars, uint64_t domain, int v) {
+    u64 bytes = (u64)v * (n_vars + domain) * 32;                                  // witness and h vectors
+    for (int k = 0; k < n; k++) {
+        if (!s[k].scalars) continue;
+        const MsmGeometry g = s[k].c ? MsmGeometry::choose_tables(s[k].scalars, s[k].c, s[k].stride) : MsmGeometry::choose(s[k].scalars);
+        bytes += (u64)v * (g.n * (u64)g.windows * BATCH_PAIR_BYTES + (u64)g.window_sets() * g.buckets * BATCH_BUCKET_BYTES);
+    }
+    return bytes;
+}
+bool batch_fits(const ug_batch_schedule* s, int n, int v) {
+    for (int k = 0; k < n; k++) {
+        if (!s[k].scalars) continue;
+        const MsmGeometry g = s[k].c ? MsmGeometry::choose_tables(s[k].scalars, s[k].c, s[k].stride) : MsmGeometry::choose(s[k].scalars);
+        if (g.n > ((u64)1 << TABLE_INDEX_BITS)) return false;
+        if ((u64)v * g.n * (u64)g.windows > PLAN_MAX_ENTRIES) return false;                 // pairs of one schedule (sort, u32 counts)
+        if ((u64)v * g.window_sets() * g.buckets >= ((u64)1 << 31)) return false;          // bucket ids below the u32 sentinel
+        if ((size_t)v * g.window_sets() * MSM_G2_PT_WORDS > MSM_PENDING_WORDS - 1) return false;      // one result block per product
+    }
+    return true;
+}
+}  // namespace
+int ug_plan_proof_batch(const ug_batch_schedule* schedules, int n_schedules, uint64_t n_vars, uint64_t domain, uint64_t free_bytes,
+                        int requested) {
+    try {
+        if (n_schedules < 0 || (n_schedules && !schedules)) return 0;
+        for (int k = 0; k < n_schedules; k++) {
+            const ug_batch_schedule& b = schedules[k];
+            if (b.c && (b.c < TABLE_MIN_C || b.c > TABLE_MAX_C || b.stride < 1 || b.stride > (255 + b.c - 1) / b.c)) return 0;
+        }
+        int v = requested < 1 ? 1 : requested > UG_BATCH_MAX ? UG_BATCH_MAX : requested;
+        while (v > 1 && (!batch_fits(schedules, n_schedules, v) || batch_bytes(schedules, n_schedules, n_vars, domain, v) > free_bytes)) v--;
+        return v;
+    } catch (...) { return 0; }
+}
 int ug_bases_precompute(ug_bases* b, int c) { return ug_bases_precompute_strided(b, c, 1); }
 int ug_bases_precompute_strided(ug_bases* b, int c, int stride) {
     UG_TRY
@@ -850,6 +889,15 @@ int ug_dvec_gather_index(ug_dvec* out, const ug_dvec* src, const ug_index* index
     gather_elements(out->data, src->data, index->data, index->n, src->n, c->stream);      // queued; the stream orders its users
     UG_CATCH
 }
+int ug_dvec_gather_index_at(ug_dvec* out, uint64_t out_first, const ug_dvec* src, const ug_index* index) {
+    UG_TRY
+    if (!out || !src || !index) throw std::invalid_argument("null argument");
+    if (out_first > out->n || index->n > out->n - out_first) throw std::invalid_argument("gather outside the output vector");
+    ug_ctx* c = out->ctx;
+    c->use();
+    gather_elements(out->data + out_first * 8, src->data, index->data, index->n, src->n, c->stream);
+    UG_CATCH
+}
 int ug_dvec_scatter(ug_dvec* dst, const uint32_t* host_index, const void* host_values, uint64_t n) {
     UG_TRY
     if (!dst || ((!host_index || !host_values) && n)) throw std::invalid_argument("null argument");
@@ -1003,6 +1051,33 @@ int ug_schedule_build_tables_strided(ug_schedule* s, const ug_dvec* scalars, uin
     tm.stop();
     UG_CATCH
 }
+// V scalar vectors of `count` scalars, vector v at first + v * vector_stride, in ONE schedule (batched proofs): every product
+// over it writes V records (internal.hpp: MsmGeometry::vectors)
+int ug_schedule_build_vectors(ug_schedule* s, const ug_dvec* scalars, uint64_t first, uint64_t count, int vectors, uint64_t vector_stride,
+                              int table_c, int stride) {
+    UG_TRY
+    if (!s || !scalars) throw std::invalid_argument("null argument");
+    if (vectors < 1 || vectors > MSM_MAX_VECTORS) throw std::invalid_argument("vectors outside [1, " + std::to_string(MSM_MAX_VECTORS) + "]");
+    if (vectors == 1) {
+        ug_ctx* c = s->ctx;
+        c->use();
+        return table_c ? ug_schedule_build_tables_strided(s, scalars, first, count, table_c, stride) : ug_schedule_build(s, scalars, first, count);
+    }
+    if (vector_stride < count) throw std::invalid_argument("vector stride below the scalars per vector");
+    if (first > scalars->n || (uint64_t)(vectors - 1) * vector_stride + count > scalars->n - first)
+        throw std::invalid_argument("schedule range outside the scalar vector");
+    if (s->cls.on()) throw std::invalid_argument("bucket classes cannot be combined with several scalar vectors");
+    ug_ctx* ctx = s->ctx;
+    ctx->use();
+    fault_point(UG_FAULT_SCHEDULE_BUILD);
+    MsmGeometry g = table_c ? MsmGeometry::choose_tables(count, table_c, stride) : MsmGeometry::choose(count);
+    g.set_vectors(vectors, vector_stride);
+    ScopedTimer tm(ctx, &ctx->msm_ms);
+    s->first = first;
+    s->sched.build(scalars->data + first * 8, g, ctx->stream);
+    tm.stop();
+    UG_CATCH
+}
 // Bucket classes for every later build of this schedule (include/ultragroth_hip.h; csrc/internal.hpp: BucketClasses)
 int ug_schedule_set_classes(ug_schedule* s, int q_log, uint32_t first_residue, uint32_t residues, uint32_t specials,
                             uint64_t special_first, uint64_t special_count) {
@@ -1060,6 +1135,7 @@ int ug_msm_g1(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_
     if (b->g2) throw std::invalid_argument("ug_msm_g1 called with G2 bases");
     if (b->members > 1) throw std::invalid_argument("a base group is multiplied with ug_msm_group_enqueue");
     check_tables(b, s);
+    if (s->sched.geo.vectors > 1) return ug_msm_batch(c, 1, &b, s, &index_shift, &out);      // (V records)
     c->use();
     ScopedTimer tm(c, &c->msm_ms);
     int64_t delta = (int64_t)s->first - index_shift - (int64_t)b->global_first;
@@ -1075,6 +1151,7 @@ int ug_msm_g2(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_
     if (!c || !b || !s || !out) throw std::invalid_argument("null argument");
     if (!b->g2) throw std::invalid_argument("ug_msm_g2 called with G1 bases");
     check_tables(b, s);
+    if (s->sched.geo.vectors > 1) return ug_msm_batch(c, 1, &b, s, &index_shift, &out);      // (V records)
     c->use();
     ScopedTimer tm(c, &c->msm_ms);
     int64_t delta = (int64_t)s->first - index_shift - (int64_t)b->global_first;
@@ -1231,10 +1308,11 @@ int ug_ctx_collect(ug_ctx* c) {
     std::vector<ug_ctx::QueuedMsm> done;
     done.swap(c->pending_msm);                                  // whatever happens below, nothing stays queued
     sync_and_resolve(c);
-    for (auto& q : done) {
-        if (q.g2) affine_out_g2((uint8_t*)q.out, msm_collect_g2(q.pend));
-        else affine_out_g1((uint8_t*)q.out, msm_collect_g1(q.pend));
-    }
+    for (auto& q : done)
+        for (int v = 0; v < q.pend.vectors; v++) {         // a schedule of V scalar vectors: V consecutive records
+            if (q.g2) affine_out_g2((uint8_t*)q.out + (size_t)v * 128, msm_collect_g2(q.pend, v));
+            else affine_out_g1((uint8_t*)q.out + (size_t)v * 64, msm_collect_g1(q.pend, v));
+        }
     UG_CATCH
 }
 // A caller that queued work (ug_msm_batch_enqueue, schedules, ug_hpoly_run) and then failed before ug_ctx_collect: waits for
