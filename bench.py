@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- proofs/s of the Groth16 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--log-domain 24] [--mix U|C]
+    python bench.py --gpus N --steps K --warmup W [--log-domain 24] [--mix U|C] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line; every figure that takes
+work or runs of its own beside the headline (cold start, un-overlapped steps, the reference's call from host memory, counter
+child runs, CPU baseline) comes with --full only.
 
 A step is one proof of a seeded synthetic circuit (ultragroth_amd/synth.py, shapes of SURVEY.md section 8d): the whole hot
 path S1-S13 of src/groth16.cpp:48-203 -- the five MSMs and the H-polynomial block on the device, blinding and JSON on the
@@ -10,7 +14,7 @@ host -- on a CREATED prover with the witness ALREADY RESIDENT IN HBM when the ti
 after the other from one host thread: `value` = K / their wall time, `ms_per_step` its inverse, and `msm_ms_per_proof` /
 `fft_ms_per_proof` are the device times of the MSM and FFT parts of exactly those K steps. Default workload: configs[2] of
 BASELINE.json, the 2^24-constraint circuit with full G1+G2 MSMs that the 10x target is quoted on.
-Beside it, outside that region (N = 1): `prove_call_ms_per_step` = the same K proofs through `groth16_prover_prove` with the
+Beside it, outside that region (N = 1, --full): `prove_call_ms_per_step` = the same K proofs through `groth16_prover_prove` with the
 .wtns in HOST memory, one call after the other (SURVEY.md section 8(d)'s "ms/proof": parse + PCIe copy of the witness, 512 MiB
 at 2^24, + device + host; `witness_upload_ms_per_proof` is the copy's share), and `pipelined_proofs_per_s` = the K calls issued
 from `--host-threads` threads on the one prover object (the reference's prover keeps no per-proof state, so its callers may;
@@ -26,8 +30,10 @@ scaling of one proof). `comm` records what the live process group is (backend, w
 
 Rank 0 prints ONE JSON line. `roofline` is for the bucket-accumulation kernel that takes most of a step, the other large
 kernels beside it under `roofline.kernels`; all are measured in this run with HIP events on the launch stream inside the
-library. `cpu_baseline` times the CPU oracle (oracle/, OpenMP, mulx/adcx/adox Montgomery) on the benchmarked circuit itself
-when that takes about two minutes or less (2^24: yes), else on bounded samples with a fitted extrapolation, marked so. The
+library (a plain run takes the launch times from the K timed steps and reads the counter traffic from the committed summary;
+--full takes them from K un-overlapped steps and two counter child runs). `cpu_baseline` (--full) times the CPU oracle
+(oracle/, OpenMP, mulx/adcx/adox Montgomery) on the benchmarked circuit itself when that takes about two minutes or less
+(2^24: yes), else on bounded samples with a fitted extrapolation, marked so. The
 oracle is the checker/baseline only; the timed path never touches it. `--check` proves once more with fixed blinding and
 compares proof.json byte for byte with the expected proof (oracle/closed_form.py: oracle H polynomial + MSMs in the
 exponent, any size); a mismatch makes the exit code 3. `--dump-outputs DIR` writes the proof and public signals the last
@@ -70,8 +76,13 @@ def parse():
                          "launch times of `roofline` are then taken from K un-overlapped steps right after the region, same process, same prover")
     ap.add_argument("--no-pmc", action="store_true", help="do not start the two rocprofv3 --pmc child runs that measure `roofline.traffic` "
                                                           "(then the committed summary is read and labelled as such)")
-    ap.add_argument("--bare", action="store_true", help="(for the counter child runs) only the warm-up and the K steps: no extra figures, "
-                                                        "no CPU baseline, no counter children")
+    ap.add_argument("--full", action="store_true", help="every figure beside the headline, each of which takes work or runs of its own: "
+                    "the cold start's first proof, the un-overlapped steps for the MSM | FFT split and the roofline's launch times, the "
+                    "reference's call with the .wtns in host memory (one and several host threads), the counter child runs, the CPU "
+                    "baseline (N = 1); UltraGroth: the un-overlapped and the pipelined calls. Without it a run only sets up, warms up, "
+                    "times the K steps and prints the line")
+    ap.add_argument("--bare", action="store_true", help="(for the counter child runs) no extra figures, no CPU baseline, no counter "
+                                                        "children; with --full the un-overlapped steps still run")
     ap.add_argument("--ultra", action="store_true", help="BASELINE.json configs[4]: UltraGroth two-round prove (single GPU)")
     ap.add_argument("--replicas", action="store_true", help="N > 1: after the sharded steps, also time the OTHER way to use a node -- every "
                     "rank a whole prover of its own, proving its own proofs, no exchange at all -- and report it as the extra key "
@@ -88,6 +99,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.bare or not args.full:
+        args.no_pmc = args.no_cpu_baseline = True
     return args
 
 
@@ -370,10 +383,10 @@ def bench_ultra(args, dev, ug, synth, torch, dist, backend, rank, world, local_r
             ug.set_test_blinding(b"")
             dump_outputs(args.dump_outputs, out)
         # the region ran in the library's default configuration (the H branch of the final round beside its witness products:
-        # stream times of the two parts stretch and overlap); the MSM | FFT split of the metric comes from K more calls with the
-        # branch behind the products
+        # stream times of the two parts stretch and overlap); with --full the MSM | FFT split of the metric comes from K more
+        # calls with the branch behind the products
         unoverlapped_ms = None
-        if os.environ.get("ULTRAGROTH_OVERLAP", "1") != "0":
+        if args.full and os.environ.get("ULTRAGROTH_OVERLAP", "1") != "0":
             keep = os.environ.get("ULTRAGROTH_OVERLAP")
             os.environ["ULTRAGROTH_OVERLAP"] = "0"
             prover.prove(uwtns)
@@ -390,7 +403,7 @@ def bench_ultra(args, dev, ug, synth, torch, dist, backend, rank, world, local_r
             else:
                 os.environ["ULTRAGROTH_OVERLAP"] = keep
         pipelined_s = None
-        if args.host_threads > 1:
+        if args.full and args.host_threads > 1:
             # an extra figure, as on the Groth16 line: the K calls from several host threads on the one prover object (the .uwtns
             # of a waiting call is staged while a proof runs)
             todo = iter(range(args.steps))
@@ -594,8 +607,6 @@ def main():
     import torch
     import ultragroth_amd as ug
     from ultragroth_amd import synth
-    if args.bare:
-        args.no_pmc = args.no_cpu_baseline = True
     # the K timed steps at N = 1 run in the fastest honest configuration of the library: the H branch beside the witness
     # products (ULTRAGROTH_OVERLAP, read by the library per proof); N > 1 drives the two streams itself (phase calls)
     if world == 1 and args.ultra and args.overlap:
@@ -634,10 +645,11 @@ def main():
         t0 = time.perf_counter()
         prover = ug.Groth16Prover(zkey)          # groth16_prover_create: the reference's own entry point
         create_s = time.perf_counter() - t0
-        # cold start: create does not wait for the window tables; the first proof (the reference's call, .wtns in host memory)
-        # goes at once, on the classic windows beside the table kernels; the timed region below runs on the finished tables
+        # cold start: create does not wait for the window tables; with --full the first proof (the reference's call, .wtns in
+        # host memory) goes at once, on the classic windows beside the table kernels; the timed region below runs on the
+        # finished tables
         first_proof_s = tables_s = None
-        if not args.bare:
+        if args.full and not args.bare:
             prover.prove(wtns)
             first_proof_s = time.perf_counter() - t0
         prover.tables_ready(wait=True)
@@ -839,7 +851,7 @@ def main():
 
     kstats_region = [prover.kernel_stats(which=w) for w in range(4)]      # of the K timed steps only (reset after the warm-up)
     kstats, clean_ms, clean_split = kstats_region, None, None
-    if timed_overlap:
+    if timed_overlap and args.full:
         # The region ran with the H branch BESIDE the witness products: launches of the two streams share the chip and their
         # event-pair times stretch. The launch durations the roofline is computed from are therefore taken from K more steps with
         # the branch BEHIND the products (one kernel on the chip at a time), right here: same process, same prover, same witness.
@@ -859,12 +871,12 @@ def main():
         kstats = [prover.kernel_stats(which=w) for w in range(4)]
         os.environ["ULTRAGROTH_OVERLAP"] = str(timed_overlap)
 
-    # ---- extra figures (N = 1), outside the contract's region: the same K proofs through groth16_prover_prove with the .wtns
-    # in HOST memory -- SURVEY.md section 8(d)'s "ms/proof": parse + PCIe copy + device + host -- one call after the other, and
-    # from `--host-threads` threads on the one prover object (the witness copy of a call runs beside the kernels of the other)
+    # ---- extra figures (N = 1, --full), outside the contract's region: the same K proofs through groth16_prover_prove with the
+    # .wtns in HOST memory -- SURVEY.md section 8(d)'s "ms/proof": parse + PCIe copy + device + host -- one call after the other,
+    # and from `--host-threads` threads on the one prover object (the witness copy of a call runs beside the kernels of the other)
     host_threads = max(1, args.host_threads) if single else 1
     prove_call_ms = upload_ms = pipelined_s = None
-    if single and not args.bare:
+    if single and args.full and not args.bare:
         prover.prove(wtns)
         t1 = time.perf_counter()
         upload_ms = 0.0
@@ -1067,8 +1079,10 @@ def main():
         roofline["note"] = ("the kernel with the largest share of a step; integer-issue-bound kernels: issue_bound gives modmul work against the "
                             "v_mad_u64_u32 peak (DESIGN.md)")
         roofline["launch_times_from"] = ("K steps with the H branch behind the witness products (one kernel on the chip at a time), right after the "
-                                         "timed region: same process, same prover" if timed_overlap else "the K timed steps themselves")
-        if timed_overlap:
+                                         "timed region: same process, same prover" if clean_ms is not None else
+                                         "the K timed steps themselves" + (" (the H branch beside the witness products: the launch times stretch; "
+                                                                           "--full takes them from K un-overlapped steps)" if timed_overlap else ""))
+        if clean_ms is not None:
             roofline["launch_ms_in_timed_region"] = {n: kstats_region[i][0] for i, n in
                                                      ((3, "segment_accumulate_group_kernel<%d>" % grp_members), (1, "segment_accumulate_kernel<G2Cfg>"),
                                                       (0, "segment_accumulate_kernel<G1Cfg>"), (2, "ntt_pass_kernel")) if kstats_region[i][1]}
@@ -1105,8 +1119,10 @@ def main():
             "msm_ms_per_proof": msm_ms / args.steps, "fft_ms_per_proof": fft_ms / args.steps,
             "unoverlapped_ms_per_step": clean_ms,
             "split_region": (("device time of the MSM (S1-S4, S10) and FFT (S5-S9) parts of the K un-overlapped steps right after the timed region "
-                              "(in the region the two parts run beside each other and their stream times stretch)" if timed_overlap else
-                              "device time of the MSM (S1-S4, S10) and FFT (S5-S9) parts of the K timed steps themselves") if single else
+                              "(in the region the two parts run beside each other and their stream times stretch)" if clean_split is not None else
+                              "device time of the MSM (S1-S4, S10) and FFT (S5-S9) parts of the K timed steps themselves" +
+                              ("; the two parts run beside each other there, so their stream times stretch and their sum exceeds the step "
+                               "(--full splits K un-overlapped steps instead)" if timed_overlap else "")) if single else
                              "stream time of rank 0's MSM and FFT parts over the K timed steps; its chains run on a second stream BESIDE "
                              "its witness MSMs, so the two overlap and their sum exceeds the step"),
             "comm": comm,
@@ -1120,8 +1136,9 @@ def main():
             "create_s": create_s, "zkey_bytes": zkey_bytes, "zkey_ingest_gbs": zkey_bytes / create_s / 1e9,
             "time_to_first_proof_s": first_proof_s if single else None, "tables_in_use_after_s": tables_s if single else None,
             "cold_start": ("groth16_prover_create returns once the zkey is resident (create_s); time_to_first_proof_s = create + one "
-                           "groth16_prover_prove at once (classic windows, beside the window-table kernels, which run on a stream of their own); "
-                           "tables_in_use_after_s = when the tables were finished and adopted; the timed region runs on them") if single else None,
+                           "groth16_prover_prove at once (classic windows, beside the window-table kernels, which run on a stream of their own; "
+                           "--full only); tables_in_use_after_s = when the tables were finished and adopted; the timed region runs on them")
+                          if single else None,
             "host_peak_rss_gb": round(__import__("resource").getrusage(__import__("resource").RUSAGE_SELF).ru_maxrss / 1048576.0, 2),
             "roofline": roofline,
         }
@@ -1132,6 +1149,9 @@ def main():
             res["cpu_baseline_note"] = "measured at N = 1 only (run contract); see the N = 1 line of the same build"
         elif not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(dev, args, log_domain, (zkey, wtns) if zkey is not None else None)
+        else:
+            res["cpu_baseline"] = None
+            res["cpu_baseline_note"] = "not measured in this run (--full without --no-cpu-baseline measures it)"
         if args.check:
             from oracle import closed_form
             if zkey is None:                     # N > 1: only now, and only on rank 0, the whole zkey is made (for its coefficient section)

@@ -467,16 +467,50 @@ def test_bench_ultragroth_sharded_path_over_rccl_with_one_rank():
     assert "section-range shard x1, H-poly chains split over ranks" in d["config"]["parallelism"]
 
 
+def test_bench_plain_line_one_gpu(tmp_path):
+    """`python bench.py` as the driver runs it at N = 1 without --full (here at 2^16 so that it takes seconds): exactly one
+    JSON line with the contract's keys; the K timed steps run one after the other on the resident witness, and nothing that
+    needs work or runs of its own beside them is measured (cold start, un-overlapped steps, the call from host memory, counter
+    children, CPU baseline); --dump-outputs writes the proof and public signals of the last timed step"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-domain", "16",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert key in d, key
+    assert d["metric"] == "proofs/s" and d["unit"] == "proofs/s" and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["higher_is_better"] is True and d["dtype"] == "u32x9 (29-bit limbs, 254-bit modular integers)"
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert d["config"]["overlap"] == 1 and "ULTRAGROTH_OVERLAP=1" in d["value_definition"] and "resident" in d["value_definition"]
+    assert d["msm_ms_per_proof"] > 0 and d["fft_ms_per_proof"] > 0
+    for key in ("unoverlapped_ms_per_step", "prove_call_ms_per_step", "api_value", "pipelined_proofs_per_s", "time_to_first_proof_s",
+                "cpu_baseline"):
+        assert d[key] is None, key
+    assert d["tables_in_use_after_s"] > 0
+    rf = d["roofline"]
+    assert rf["launches"] % 3 == 0 and rf["launch_times_from"].startswith("the K timed steps themselves")
+    assert "launch_ms_in_timed_region" not in rf and not (rf["traffic_source"] or "").startswith("measured in this run")
+    assert sorted(p.name for p in out.iterdir()) == ["pi_a.npy", "pi_b.npy", "pi_c.npy", "public.npy"]
+    assert np.load(out / "pi_a.npy").shape == (3, 8)
+
+
 def test_bench_line_contract_one_gpu():
-    """`python bench.py` as the driver runs it at N = 1 (here at 2^16 so that it takes seconds): exactly one JSON line
-    with the contract's keys, the `roofline` and `cpu_baseline` objects; the K timed steps run one after the other on the
-    resident witness, the PCIe-inclusive call and the two-thread figure come as extra keys; `--check` bit-exact (a mismatch
-    would make the exit code 3); the CPU baseline is measured at the benchmarked size, not extrapolated"""
+    """`python bench.py --full` at N = 1 (here at 2^16 so that it takes seconds): exactly one JSON line with the contract's
+    keys, the `roofline` and `cpu_baseline` objects; the K timed steps run one after the other on the resident witness, the
+    PCIe-inclusive call and the two-thread figure come as extra keys; `--check` bit-exact (a mismatch would make the exit
+    code 3); the CPU baseline is measured at the benchmarked size, not extrapolated"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-domain", "16",
-                        "--check"], capture_output=True, text=True, timeout=600)
+                        "--full", "--check"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
