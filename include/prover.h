@@ -117,15 +117,21 @@ int ultra_groth_prover_zkey_file(const char *zkey_file_path,
  * library first looks (tests, bench.py --check, smoke()); otherwise it changes nothing and returns PROVER_ERROR. */
 int ug_test_set_blinding(const void *bytes, unsigned long long n);
 
-/* BATCHED PROOFS: `count` witnesses (wtns file buffers) proved in one call; proof_buffers[b] / public_buffers[b] receive what
- * groth16_prover_prove returns for witness b, byte for byte, sized as there (proof_sizes[b], public_sizes[b]). A bad witness
- * fails the whole call with the code and message groth16_prover_prove gives for it, prefixed "witness <b>: ", and no output is
- * written. A created Groth16 prover checks every witness before any work is queued; other handles check each one when its
- * proof starts. A short buffer anywhere gives PROVER_ERROR_SHORT_BUFFER with every needed
- * size written back into proof_sizes / public_sizes. Blinding is drawn in witness order: r0, s0, r1, s1, ... (ug_test_set_blinding).
- * A created Groth16 prover on one device proves up to 16 witnesses per device pass -- one schedule, one accumulation launch per
- * product and one set of tails for all of them (include/ultragroth_hip.h: ug_schedule_build_vectors, ug_plan_proof_batch); any
- * other handle (UltraGroth, ULTRAGROTH_DEVICES, sharded ranks) proves them one after the other with the same outputs.
+/* BATCHED PROOFS: `count` witnesses (wtns / uwtns file buffers) proved in one call; proof_buffers[b] / public_buffers[b] receive
+ * what groth16_prover_prove (ultra_groth_prover_prove for an UltraGroth handle) returns for witness b, byte for byte, sized as
+ * there (proof_sizes[b], public_sizes[b]). A bad witness fails the whole call with the code and message the single prove gives
+ * for it, prefixed "witness <b>: ", and no output is written. A created Groth16 or UltraGroth prover checks every witness before
+ * any work is queued (UltraGroth: also the lookup lists -- "chunk index outside the lookup table" -- which a single proof meets
+ * only when it completes the lookup); other handles check each one when its proof starts. A short buffer anywhere gives
+ * PROVER_ERROR_SHORT_BUFFER with every needed size written back into proof_sizes / public_sizes.
+ * Blinding is drawn in witness order (ug_test_set_blinding): r0, s0, r1, s1, ... for Groth16; rk0, r0, s0, rk1, r1, s1, ... for
+ * UltraGroth (round randomness, then r and s, per witness); the scalars of a device pass are drawn when the pass starts.
+ * A created prover on one device, unsharded and with its coefficient matrix, proves up to 16 witnesses per device pass -- one
+ * schedule, one accumulation launch per product and one set of tails for all of them (include/ultragroth_hip.h:
+ * ug_schedule_build_vectors, ug_plan_proof_batch). For UltraGroth a pass is: one round-commitment product over the V gathered
+ * round sets, the V challenges on the host, ONE lookup completion for all V witnesses (ug_dvec_complete_lookup_vectors), then the
+ * final round's products once over V vectors (ug_plan_proof_batch_aux sizes V). Handles that still prove one after the other, with
+ * the same outputs: ULTRAGROTH_DEVICES provers of either protocol, sharded ranks, registry circuits.
  * ug_prover_last_timings reports the whole call. */
 int ug_groth16_prover_prove_batch(void *prover_object, int count,
                                   const void *const *wtns_buffers, const unsigned long long *wtns_sizes,

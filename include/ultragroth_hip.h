@@ -161,6 +161,11 @@ int      ug_plan_window_tables(const ug_table_group* groups, int n_groups, uint6
 typedef struct { uint64_t scalars; int c, stride; } ug_batch_schedule;
 int      ug_plan_proof_batch(const ug_batch_schedule* schedules, int n_schedules, uint64_t n_vars, uint64_t domain, uint64_t free_bytes,
                              int requested);
+/* The same for a prover whose pass keeps aux_bytes_per_witness more device bytes per witness (UltraGroth: the gathered round /
+ * final scalars and the lookup staging): V * aux_bytes_per_witness is added to the memory the V-fold buffers must fit. With
+ * aux_bytes_per_witness = 0 it returns what ug_plan_proof_batch returns; more aux bytes never give a larger V. */
+int      ug_plan_proof_batch_aux(const ug_batch_schedule* schedules, int n_schedules, uint64_t n_vars, uint64_t domain,
+                                 uint64_t aux_bytes_per_witness, uint64_t free_bytes, int requested);
 /* DEFERRED TABLE BUILDS (cold start of a created prover): after ug_ctx_defer_tables(ctx, 1) the sets made by
  * ug_bases_create_tables_* / ug_bases_create_group_g1 on this context hold their points only and remember the width: nothing
  * is queued, not even the tables' memory is allocated. ug_bases_tables_step(set, max_points, &remaining) builds the tables of the next max_points points on the
@@ -213,6 +218,28 @@ int  ug_dvec_apply_lookup(ug_dvec* dst, const uint32_t* w_idx, const uint32_t* p
  * prod[i] = frequencies[i] * inv2[i], plain integers, (1 + 2 L) * 32 bytes of host memory -- the `table` argument of
  * ug_dvec_apply_lookup. Row index and frequency follow the reference's (int, Element) overloads (>= 2^31: value - 2^32). */
 int  ug_fr_lookup_table(ug_ctx* ctx, const void* rand_plain, const uint32_t* frequencies, uint64_t lookup_size, void* table_out);
+/* VECTOR FORMS of the two calls above: the lookup completion of the V witnesses of a batched proof (1 <= V <= UG_BATCH_MAX),
+ * whose lists may differ in content and length. lists[v] = the host arrays of witness v; vector v of dst is dst[v * vector_stride,
+ * (v + 1) * vector_stride) and every w_idx of witness v must lie below vector_stride. Each call makes ONE staged upload of the
+ * concatenated lists, one launch per kernel over all vectors, and ends with one host wait. "Last write wins" holds within each
+ * witness as in ug_dvec_apply_lookup; the scratch that decides it is per vector. At V = 1 the results are byte-identical to the
+ * single calls. Indices out of range fail the whole call with nothing written (the messages of ug_dvec_apply_lookup).
+ *   ug_fr_lookup_tables            tables_out[v] = the table of (rands_plain + 32 v, lists[v].frequencies), (1 + 2 L_v) * 32 bytes;
+ *                                  only frequencies / lookup_size of the lists are read
+ *   ug_dvec_apply_lookup_vectors   the writes of every witness with host tables[v] (frequencies are not read)
+ *   ug_dvec_complete_lookup_vectors  both in one call: the tables are made on the device, used there, and copied to
+ *                                  tables_out[v] (may be NULL: not copied) -- still one upload and one host wait
+ * ug_lookup_vectors_bytes: the device bytes such a call takes for these lists (staging and the per-vector scratch). */
+typedef struct {
+    const uint32_t* frequencies; uint64_t lookup_size;
+    const uint32_t* chunks; uint64_t n_chunks;
+    const uint32_t *w_idx, *p_idx; uint64_t n;
+} ug_lookup_lists;
+int  ug_fr_lookup_tables(ug_ctx* ctx, int vectors, const void* rands_plain, const ug_lookup_lists* lists, void* const* tables_out);
+int  ug_dvec_apply_lookup_vectors(ug_dvec* dst, uint64_t vector_stride, int vectors, const ug_lookup_lists* lists, const void* const* tables);
+int  ug_dvec_complete_lookup_vectors(ug_dvec* dst, uint64_t vector_stride, int vectors, const void* rands_plain,
+                                     const ug_lookup_lists* lists, void* const* tables_out);
+uint64_t ug_lookup_vectors_bytes(uint64_t vector_stride, const ug_lookup_lists* lists, int vectors);
 /* non-owning view of n 32-byte elements already in device memory (e.g. a torch / RCCL buffer) */
 int  ug_dvec_wrap(ug_ctx* ctx, void* device_ptr, uint64_t n, ug_dvec** out);
 uint64_t ug_dvec_size(const ug_dvec* v);

@@ -155,7 +155,7 @@ class _ProverBase:
 
     def prove_batch(self, wtns_list, proof_size=None, public_size=None):
         """ug_groth16_prover_prove_batch: [(proof_json, public_json), ...], one pair per witness, each what prove() returns for it
-        (several witnesses per device pass on a created Groth16 prover, one after the other on any other handle)"""
+        (several witnesses per device pass on a created Groth16 or UltraGroth prover, one after the other on any other handle)"""
         k = len(wtns_list)
         keep = [bytes(w) for w in wtns_list]
         wb = (C.c_char_p * max(k, 1))(*keep)
@@ -670,6 +670,40 @@ def plan_proof_batch(schedules, n_vars, domain, free_bytes, requested):
     return v
 
 
+def plan_proof_batch_aux(schedules, n_vars, domain, aux_bytes_per_witness, free_bytes, requested):
+    """ug_plan_proof_batch_aux (host only): plan_proof_batch with aux_bytes_per_witness more device bytes per witness of a pass"""
+    k = len(schedules)
+    arr = (_BatchSchedule * max(k, 1))(*[_BatchSchedule(*s) for s in schedules])
+    v = load().ug_plan_proof_batch_aux(arr, k, n_vars, domain, aux_bytes_per_witness, free_bytes, requested)
+    if v < 1:
+        raise ValueError("ug_plan_proof_batch_aux: bad arguments")
+    return v
+
+
+class _LookupLists(C.Structure):
+    _fields_ = [("frequencies", C.c_void_p), ("lookup_size", C.c_uint64), ("chunks", C.c_void_p), ("n_chunks", C.c_uint64),
+                ("w_idx", C.c_void_p), ("p_idx", C.c_void_p), ("n", C.c_uint64)]
+
+
+def _lookup_lists(lists):
+    """lists = [dict(freq=, chunks=, w_idx=, p_idx=, lookup_size=) ...] (numpy uint32 arrays; freq or the index lists may be
+    missing) -> (ug_lookup_lists array, the arrays it points into)"""
+    import numpy as np
+    keep, arr = [], (_LookupLists * len(lists))()
+    for v, l in enumerate(lists):
+        a = {k: np.ascontiguousarray(l.get(k, ()), dtype=np.uint32) for k in ("freq", "chunks", "w_idx", "p_idx")}
+        keep.append(a)
+        arr[v] = _LookupLists(a["freq"].ctypes.data, l.get("lookup_size", len(a["freq"])), a["chunks"].ctypes.data, len(a["chunks"]),
+                              a["w_idx"].ctypes.data, a["p_idx"].ctypes.data, len(a["w_idx"]))
+    return arr, keep
+
+
+def lookup_vectors_bytes(vector_stride, lists):
+    """ug_lookup_vectors_bytes (host only): device bytes a vector lookup call takes for these lists"""
+    arr, _keep = _lookup_lists(lists)
+    return load().ug_lookup_vectors_bytes(vector_stride, arr, len(lists))
+
+
 class Device:
     """A ug_ctx plus convenience wrappers in the reference's byte formats."""
 
@@ -749,6 +783,39 @@ class Device:
         w = np.ascontiguousarray(w_idx, dtype=np.uint32); p = np.ascontiguousarray(p_idx, dtype=np.uint32)
         c = np.ascontiguousarray(chunks, dtype=np.uint32)
         _check(self._L.ug_dvec_apply_lookup(dvec.h, w.ctypes.data, p.ctypes.data, len(w), c.ctypes.data, len(c), table, lookup_size))
+
+    def lookup_table(self, rand_plain, freq):
+        """ug_fr_lookup_table: [rand | inv2 | prod] as bytes for a 32-byte plain challenge and uint32 frequencies"""
+        import numpy as np
+        f = np.ascontiguousarray(freq, dtype=np.uint32)
+        out = C.create_string_buffer((1 + 2 * len(f)) * 32)
+        _check(self._L.ug_fr_lookup_table(self._h, rand_plain, f.ctypes.data, len(f), out))
+        return out.raw
+
+    def lookup_tables(self, rands_plain, freqs):
+        """ug_fr_lookup_tables: the tables of V challenges (V * 32 bytes) and V frequency lists, one device call"""
+        arr, _keep = _lookup_lists([dict(freq=f) for f in freqs])
+        outs = [C.create_string_buffer((1 + 2 * len(f)) * 32) for f in freqs]
+        ptrs = (C.c_void_p * len(outs))(*[C.cast(o, C.c_void_p) for o in outs])
+        _check(self._L.ug_fr_lookup_tables(self._h, len(freqs), rands_plain, arr, ptrs))
+        return [o.raw for o in outs]
+
+    def apply_lookup_vectors(self, dvec, vector_stride, lists, tables):
+        """ug_dvec_apply_lookup_vectors: apply_lookup for V witnesses, vector v of dvec at v * vector_stride; lists = [dict(w_idx=,
+        p_idx=, chunks=, lookup_size=) ...], tables = V byte strings"""
+        arr, _keep = _lookup_lists(lists)
+        bufs = [_buf(bytes(t)) for t in tables]
+        ptrs = (C.c_void_p * len(bufs))(*[C.cast(b, C.c_void_p) for b in bufs])
+        _check(self._L.ug_dvec_apply_lookup_vectors(dvec.h, vector_stride, len(lists), arr, ptrs))
+
+    def complete_lookup_vectors(self, dvec, vector_stride, rands_plain, lists, want_tables=True):
+        """ug_dvec_complete_lookup_vectors: tables and writes of V witnesses in one call; lists = [dict(freq=, chunks=, w_idx=,
+        p_idx=) ...]; returns the V tables (or None)"""
+        arr, _keep = _lookup_lists(lists)
+        outs = [C.create_string_buffer((1 + 2 * len(l["freq"])) * 32) for l in lists]
+        ptrs = (C.c_void_p * len(outs))(*[C.cast(o, C.c_void_p) for o in outs])
+        _check(self._L.ug_dvec_complete_lookup_vectors(dvec.h, vector_stride, len(lists), rands_plain, arr, ptrs if want_tables else None))
+        return [o.raw for o in outs] if want_tables else None
 
     def schedule(self, dvec, first, count, table_c=0, classes=None, table_stride=1):
         """classes (ug_schedule_set_classes): (q_log, first_residue, residues, specials, special_first, special_count);

@@ -30,6 +30,8 @@ INNER_SYMBOLS = [
     "ug_bases_create_tables_strided_g1", "ug_bases_create_tables_strided_g2", "ug_bases_create_group_strided_g1",
     "ug_bases_precompute_strided", "ug_schedule_build_tables_strided", "ug_bases_tables_bytes_strided", "ug_bases_table_stride",
     "ug_plan_window_tables", "ug_schedule_build_vectors", "ug_dvec_gather_index_at", "ug_plan_proof_batch",
+    "ug_plan_proof_batch_aux", "ug_fr_lookup_tables", "ug_dvec_apply_lookup_vectors", "ug_dvec_complete_lookup_vectors",
+    "ug_lookup_vectors_bytes",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify"]        # include/verifier.h
 OUTER_SYMBOLS = [
@@ -151,6 +153,11 @@ def load():
     L.ug_schedule_build_vectors.argtypes = [vp, vp, u64, u64, C.c_int, u64, C.c_int, C.c_int]
     L.ug_dvec_gather_index_at.argtypes = [vp, u64, vp, vp]
     L.ug_plan_proof_batch.argtypes = [vp, C.c_int, u64, u64, u64, C.c_int]
+    L.ug_plan_proof_batch_aux.argtypes = [vp, C.c_int, u64, u64, u64, u64, C.c_int]
+    L.ug_fr_lookup_tables.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.ug_dvec_apply_lookup_vectors.argtypes = [vp, u64, C.c_int, vp, vp]
+    L.ug_dvec_complete_lookup_vectors.argtypes = [vp, u64, C.c_int, vp, vp, vp]
+    L.ug_lookup_vectors_bytes.argtypes = [u64, vp, C.c_int]; L.ug_lookup_vectors_bytes.restype = u64
     L.ug_dvec_create.argtypes = [vp, u64, pp]
     L.ug_dvec_upload.argtypes = [vp, vp, u64]
     L.ug_dvec_upload_idle.argtypes = [vp, vp, u64]

@@ -232,6 +232,50 @@ __global__ void lookup_table_kernel(u32* table, const u32* freq, u64 L) {
     store8(table + (1 + L + i) * 8, o);
 }
 
+// ---- the same for the V witnesses of a batched proof: one launch each over all vectors (blockIdx.y = vector) ----
+// Kernels of their own, so that the single-witness ones above keep their code. `stage` is the one staging buffer of the call and
+// vec[v] says where witness v's lists and table lie in it (LookupVec, internal.hpp). Vector v of dst starts at v * stride
+// elements and owns last[v * stride, (v + 1) * stride): "last write wins" holds within a witness, never across two.
+__global__ void lookup_tables_vec_kernel(u32* stage, const LookupVec* vec) {
+    const LookupVec d = vec[blockIdx.y];
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    u32* table = stage + d.t_off;
+    u32 rw[8];
+    load8(rw, stage + d.r_off);                                // the challenge, plain integer
+    if (i == 0) store8(table, rw);                             // table[0] = rand (also of an empty table)
+    if (i >= d.L) return;
+    Fr rand = from_normal<FrParams>(rw);
+    Fr sum = cond_sub_q(mul(add(fr_set_int((u32)i), rand), fp_one<FrParams>()));
+    Fr inv_i = limbs_all_zero(sum) ? fp_zero<FrParams>() : inv(sum);
+    u32 o[8];
+    to_normal(o, inv_i);
+    store8(table + (1 + i) * 8, o);
+    to_normal(o, mul(fr_set_int(stage[d.f_off + i]), inv_i));
+    store8(table + (1 + d.L + i) * 8, o);
+}
+__global__ void lookup_mark_vec_kernel(u32* last, const u32* stage, const LookupVec* vec, u64 stride) {
+    const LookupVec d = vec[blockIdx.y];
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n) atomicMax(&last[(u64)blockIdx.y * stride + stage[d.w_off + i]], (u32)i + 1);
+}
+__global__ void lookup_write_vec_kernel(u32* dst, const u32* last, const u32* stage, const LookupVec* vec, u64 stride) {
+    const LookupVec d = vec[blockIdx.y];
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d.n) return;
+    const u64 j = (u64)blockIdx.y * stride + stage[d.w_off + i];
+    if (last[j] != (u32)i + 1) return;
+    const u64 p = stage[d.p_off + i];
+    u64 t = p == 0 ? 0 : p <= d.n_chunks ? 1 + (u64)stage[d.c_off + p - 1] : p - d.n_chunks;      // element of the witness's table
+    u32 w[8];
+    load8(w, stage + d.t_off + t * 8);
+    store8(dst + j * 8, w);
+}
+__global__ void lookup_clear_vec_kernel(u32* last, const u32* stage, const LookupVec* vec, u64 stride) {
+    const LookupVec d = vec[blockIdx.y];
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < d.n) last[(u64)blockIdx.y * stride + stage[d.w_off + i]] = 0;
+}
+
 template <class T> void dev_alloc(T*& p, size_t bytes) { if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
 inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
 
@@ -338,6 +382,22 @@ void apply_lookup(u32* dst, u32* last_scratch, const u32* w_idx, const u32* p_id
 void lookup_table(u32* table_dev, const u32* freq_dev, u64 L, hipStream_t stream) {
     if (!L) return;
     hipLaunchKernelGGL(lookup_table_kernel, dim3(grid_for(L, 128)), dim3(128), 0, stream, table_dev, freq_dev, L);
+    UG_KERNEL_CHECK();
+}
+void lookup_tables_vectors(u32* stage, const LookupVec* vec_dev, int vectors, u64 max_L, hipStream_t stream) {
+    if (vectors < 1) return;
+    hipLaunchKernelGGL(lookup_tables_vec_kernel, dim3(grid_for(max_L ? max_L : 1, 128), (unsigned)vectors), dim3(128), 0, stream, stage, vec_dev);
+    UG_KERNEL_CHECK();
+}
+void apply_lookup_vectors(u32* dst, u64 stride, u32* last_scratch, const u32* stage, const LookupVec* vec_dev, int vectors, u64 max_n,
+                          hipStream_t stream) {
+    if (vectors < 1 || !max_n) return;
+    const dim3 grid(grid_for(max_n, 256), (unsigned)vectors);
+    hipLaunchKernelGGL(lookup_mark_vec_kernel, grid, dim3(256), 0, stream, last_scratch, stage, vec_dev, stride);
+    UG_KERNEL_CHECK();
+    hipLaunchKernelGGL(lookup_write_vec_kernel, grid, dim3(256), 0, stream, dst, last_scratch, stage, vec_dev, stride);
+    UG_KERNEL_CHECK();
+    hipLaunchKernelGGL(lookup_clear_vec_kernel, grid, dim3(256), 0, stream, last_scratch, stage, vec_dev, stride);
     UG_KERNEL_CHECK();
 }
 void f_op_mont256(int which, int op, u32* out, const u32* a, const u32* b, u64 n, hipStream_t stream) {

@@ -323,5 +323,13 @@ void scatter_elements(u32* dst, const u32* index_dev, const u32* values_dev, u64
 void lookup_table(u32* table_dev, const u32* freq_dev, u64 L, hipStream_t stream);
 void apply_lookup(u32* dst, u32* last_scratch, const u32* w_idx, const u32* p_idx, u64 n, const u32* chunks, u64 n_chunks,
                   const u32* table, hipStream_t stream);
+// The vector forms (a batched proof): witness v's lists and table inside ONE staging buffer, at these offsets in u32 words
+// (r_off: its challenge, 8 words; t_off: its table of 1 + 2 L elements; r_off and t_off multiples of 8).
+struct LookupVec { u64 n, n_chunks, L, w_off, p_off, c_off, f_off, r_off, t_off; };
+// fills every witness's table from its challenge and frequencies (table[0] = the challenge), one launch
+void lookup_tables_vectors(u32* stage, const LookupVec* vec_dev, int vectors, u64 max_L, hipStream_t stream);
+// apply_lookup for every witness, vector v of dst at v * stride elements; last_scratch: vectors * stride zeroed u32
+void apply_lookup_vectors(u32* dst, u64 stride, u32* last_scratch, const u32* stage, const LookupVec* vec_dev, int vectors, u64 max_n,
+                          hipStream_t stream);
 
 }  // namespace ug

@@ -647,7 +647,7 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
     }
     // k proofs in one call (ug_groth16_prover_prove_batch): outputs as k proveTurn calls in order. This form proves them one
     // after the other, each witness checked when its proof starts (an error names its position; the proofs before it have run);
-    // Groth16Prover checks every witness first and runs several witnesses per device pass.
+    // Groth16Prover and UltraGrothProver check every witness first and run several witnesses per device pass.
     virtual void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
                             std::vector<std::string>& pubs) {
         proofs.assign(k, std::string()); pubs.assign(k, std::string());
@@ -1046,6 +1046,12 @@ public:
                 }
                 ug_bases* all[8] = {d_.G, d_.A, d_.B1, d_.C, d_.B2, d_.H, d_.Bc1, d_.Bc2};
                 void* mem[8] = {nullptr};
+                // (when the room of a later set cannot be had, or a swap fails, the blocks that no set has adopted go back: the
+                // build of such a set is called off, and ug_bases_tables_adopt frees the block of a set without a deferred build)
+                struct Room {
+                    ug_bases** all; void** mem;
+                    ~Room() { for (int k = 0; k < 8; k++) if (mem[k]) { ug_bases_drop_tables(all[k]); ug_bases_tables_adopt(all[k], mem[k]); } }
+                } room{all, mem};
                 for (int k = 0; k < 8; k++) if (all[k]) ugCheck(ug_bases_tables_alloc(all[k], &mem[k]));
                 for (int k = 0; k < 8; k++) {
                     if (!all[k]) continue;
@@ -1824,6 +1830,7 @@ private:
         const uint64_t M = hdr_.nVars, N = hdr_.domainSize;
         const Ranges rg = shardRanges(M, N, hdr_.numIndexesC1, hdr_.numIndexesC2, rank, count);
         wr_ = rg.w; hr_ = rg.h;
+        batchable_ = count == 1 && !src.sliced && !g_registryCreate;      // (proveBatch: ranks and registry circuits go one by one)
         const Range c1 = rg.c1, c2 = rg.c2;
         const uint8_t *coefs = src.coefs, *pA = src.pA, *pB1 = src.pB1, *pB2 = src.pB2, *pRoundC = src.pRoundC, *pFinalC = src.pFinalC,
                       *pH = src.pH, *idx1 = src.idx1, *idx2 = src.idx2;
@@ -1924,11 +1931,13 @@ public:
         return groups;
     }
     void trimWorkspaces() override {
+        std::lock_guard<std::mutex> batch(batchMutex_);     // (a batch call owns the batch buffers it stages into)
         std::lock_guard<std::mutex> turn(proveMutex);
         ug_schedule_trim(d_.sw); ug_schedule_trim(d_.sh); ug_schedule_trim(d_.saux);
         if (d_.sB) ug_schedule_trim(d_.sB);
         ug_ctx_trim(d_.ctx); ug_ctx_trim(d_.ctx2);
         witness_.trim(wCur_);
+        releaseBatch();
     }
 
     const ZkeyHeader& header() const { return hdr_; }
@@ -1938,6 +1947,12 @@ public:
     void stage(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) {
         std::lock_guard<std::mutex> st(witness_.stageMutex);
         auto tLoad0 = std::chrono::steady_clock::now();
+        const uint8_t* signals0 = parseWitness(sl, wtns, wtnsSize);
+        ugCheck(ug_dvec_upload_idle(sl.buf, signals0, hdr_.nVars));
+        sl.uploadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLoad0).count();
+    }
+    // the .uwtns checked against the circuit, its lists and public signals copied into sl; returns the signals (in the caller's buffer)
+    const uint8_t* parseWitness(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) const {
         BinFile f(wtns, wtnsSize, "wtns", 2);
         WtnsHeader wh = loadWtnsHeader(f);
         if (hdr_.nVars != wh.nVars)
@@ -1955,8 +1970,7 @@ public:
         sl.chunks = u32Section(3); sl.freq = u32Section(4); sl.wIdx = u32Section(5); sl.pIdx = u32Section(6);
         if (sl.wIdx.size() != sl.pIdx.size()) throw std::range_error("uwtns: wtns_indxs and push_indxs differ in length");
         sl.publicPart.assign(signals0, signals0 + ((size_t)hdr_.nPublic + 1) * 32);
-        ugCheck(ug_dvec_upload_idle(sl.buf, signals0, M));
-        sl.uploadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLoad0).count();
+        return signals0;
     }
     // A rank of a many-device prover (MultiUltraGrothProver): the .uwtns parsed as stage() does, but only the signals
     // [lo, hi) copied over this rank's PCIe link, into the current buffer -- the rest arrives from the peers' HBM
@@ -2029,14 +2043,11 @@ public:
         G1XYZZ commit = xyzz_add(g1FromRecord(total64), xyzz_mul_scalar_w4(g1FromRecord(hdr_.delta1), rkw_));   // final_delta1
         g1ToRecord(commit64, commit);
     }
-    // on EVERY rank, with the blinded commitment: Fiat-Shamir challenge and the lookup signals it determines
-    void applyCommitment(const uint8_t* commit64) override {
-        if (!witnessLoaded_) throw std::invalid_argument("no witness loaded");
-        memcpy(commitRec_, commit64, 64);
-        // derive_challenge (:33-58): keccak256(x_BE32 || y_BE32) as a big-endian integer
+    // derive_challenge (:33-58): keccak256(x_BE32 || y_BE32) of the blinded commitment as a big-endian integer
+    static Fr deriveChallenge(const uint8_t* commit64) {
         u32 cx[8], cy[8], w8[8];
-        memcpy(w8, commitRec_, 32); to_normal(cx, from_mont256<FqParams>(w8));
-        memcpy(w8, commitRec_ + 32, 32); to_normal(cy, from_mont256<FqParams>(w8));
+        memcpy(w8, commit64, 32); to_normal(cx, from_mont256<FqParams>(w8));
+        memcpy(w8, commit64 + 32, 32); to_normal(cy, from_mont256<FqParams>(w8));
         uint8_t buf[64], ch[32];
         for (int i = 0; i < 32; i++) {
             buf[i] = (uint8_t)(cx[7 - (i >> 2)] >> (24 - 8 * (i & 3)));
@@ -2045,7 +2056,13 @@ public:
         keccak256(ch, buf, 64);
         u32 chw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < 32; i++) chw[7 - (i >> 2)] |= (u32)ch[i] << (24 - 8 * (i & 3));
-        Fr rand = from_normal<FrParams>(chw);              // reduces values >= r, like fromMpz + toMontgomery
+        return from_normal<FrParams>(chw);                 // reduces values >= r, like fromMpz + toMontgomery
+    }
+    // on EVERY rank, with the blinded commitment: Fiat-Shamir challenge and the lookup signals it determines
+    void applyCommitment(const uint8_t* commit64) override {
+        if (!witnessLoaded_) throw std::invalid_argument("no witness loaded");
+        memcpy(commitRec_, commit64, 64);
+        Fr rand = deriveChallenge(commitRec_);
         mark("commit + challenge");
         // compute_lookup (:62-106): the new values are written into the device copy of the witness (last write wins)
         applyLookup(publicPart_, chunks_, freq_, wIdx_, pIdx_, rand);
@@ -2151,21 +2168,29 @@ public:
     struct HostTerms { BlindingTerms b; G1XYZZ roundTerm; };
     HostTerms hostTerms(const uint8_t r[32], const uint8_t s[32]) {
         if (!haveRoundScalar_) throw std::invalid_argument("finish on a rank that did not close the round");
+        return hostTermsFor(rkw_, r, s);
+    }
+    HostTerms hostTermsFor(const u32 rk[8], const uint8_t r[32], const uint8_t s[32]) const {
         HostTerms t;
-        auto fr = std::async(std::launch::async, [&] { return xyzz_mul_scalar_w4(g1FromRecord(hdr_.roundDelta1), rkw_); });   // :386-388
+        auto fr = std::async(std::launch::async, [&] { return xyzz_mul_scalar_w4(g1FromRecord(hdr_.roundDelta1), rk); });   // :386-388
         t.b = blindingTerms(hdr_, r, s);
         t.roundTerm = fr.get();
         return t;
     }
     void finishWith(const uint8_t* sums, const uint8_t r[32], const uint8_t s[32], const HostTerms& t, std::string& proof,
                     std::string& pub) {
+        finishWith(sums, r, s, t, commitRec_, publicPart_, proof, pub);
+        mark("blinding + JSON");
+    }
+    // (with the commitment and the public signals of one witness of a batch: touches nothing of the prover's per-proof state)
+    void finishWith(const uint8_t* sums, const uint8_t r[32], const uint8_t s[32], const HostTerms& t, const uint8_t* commitRec,
+                    const std::vector<uint8_t>& publicPart, std::string& proof, std::string& pub) const {
         uint8_t A[64], B[128], C[64];
         blind(A, B, C, sums, sums + 64, sums + 128, sums + 256, sums + 320, hdr_, r, s, t.b, &t.roundTerm);
         // keys pi_a, pi_b, pi_f, pi_r, protocol (src/ultra_groth.cpp:476-513)
-        proof = "{\"pi_a\":" + g1Json(A) + ",\"pi_b\":" + g2Json(B) + ",\"pi_f\":" + g1Json(C) + ",\"pi_r\":" + g1Json(commitRec_) +
+        proof = "{\"pi_a\":" + g1Json(A) + ",\"pi_b\":" + g2Json(B) + ",\"pi_f\":" + g1Json(C) + ",\"pi_r\":" + g1Json(commitRec) +
                 ",\"protocol\":\"ultragroth\"}";
-        pub = publicJson(publicPart_.data(), hdr_.nPublic, hdr_.randIndx);                  // prover.cpp:89-105
-        mark("blinding + JSON");
+        pub = publicJson(publicPart.data(), hdr_.nPublic, hdr_.randIndx);                   // prover.cpp:89-105
     }
 
     // (every caller comes through proveTurn, which this class overrides; kept for the interface)
@@ -2182,10 +2207,16 @@ public:
         std::lock_guard<std::mutex> turn(proveMutex);
         AroundGuard bracket(around);
         bracket.begin();
+        proveStaged(*lease, proof, pub);
+        totalMs_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        bracket.end();
+    }
+    // one whole proof of a staged witness (proveMutex held)
+    void proveStaged(StagedWitness& staged, std::string& proof, std::string& pub) {
         // ULTRAGROTH_TRACE=1: host wall-clock per phase on stderr (where the non-MSM, non-FFT time of a proof goes)
         trace_ = getenv("ULTRAGROTH_TRACE") && atoi(getenv("ULTRAGROTH_TRACE")) != 0;
         if (!haveHpoly_) throw std::invalid_argument("this rank was created without the coefficient matrix");
-        adopt(*lease);
+        adopt(staged);
         QueueGuard inFlight(d_.ctx, d_.ctx2);            // (declared before `terms`: the host threads join first, then the device is drained)
         uint8_t part[64], commit[64];
         roundCommit(part);
@@ -2226,10 +2257,247 @@ public:
         }
         inFlight.done();
         finishWith(sums, r, s, terms.get(), proof, pub);
-        totalMs_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        bracket.end();
     }
 
+    // ---- batched proofs (ug_groth16_prover_prove_batch) ----
+    // As Groth16Prover::proveBatch: every witness is parsed and checked first -- also its lookup lists, which a single proof
+    // checks only when it completes the lookup -- so a bad one fails the call before anything is queued. Each device pass
+    // then takes up to batchPerPass witnesses under the prover's turn (runBatch). The blinding of the whole call is drawn in
+    // witness order, rk, r, s per witness, a pass's scalars up front. A pass of one witness is the single-proof path; ranks
+    // of a sharded prover and registry circuits prove one after the other (ProverBase::proveBatch).
+    void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
+                    std::vector<std::string>& pubs) override {
+        if (!batchable_ || !haveHpoly_) { ProverBase::proveBatch(k, wtns, sizes, proofs, pubs); return; }
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<StagedWitness> in((size_t)k);
+        std::vector<const uint8_t*> signals((size_t)k);
+        for (int b = 0; b < k; b++) {
+            const std::string at = "witness " + std::to_string(b) + ": ";
+            try {
+                signals[(size_t)b] = parseWitness(in[(size_t)b], wtns[b], sizes[b]);
+                checkLookupLists(in[(size_t)b]);
+            } catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
+            catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
+        }
+        proofs.assign((size_t)k, std::string()); pubs.assign((size_t)k, std::string());
+        // the batch buffers belong to one batch call at a time; a pass's signals are copied into them BEFORE the pass takes the
+        // prover's turn (nothing queued reads them then), so another caller's kernels may run meanwhile
+        std::lock_guard<std::mutex> batchLock(batchMutex_);
+        double msm = 0, fft = 0;
+        for (int b0 = 0; b0 < k;) {
+            int V = 1;
+            {
+                std::lock_guard<std::mutex> turn(proveMutex);       // (allocations only under the turn)
+                V = batchPerPass(k - b0, &in[(size_t)b0]);
+                if (V > 1) reserveBatch(V);
+            }
+            if (V <= 1) {                                   // the single-proof path
+                WitnessLease lease(witness_);
+                stage(*lease, wtns[b0], sizes[b0]);
+                std::lock_guard<std::mutex> turn(proveMutex);
+                proveStaged(*lease, proofs[(size_t)b0], pubs[(size_t)b0]);
+                msm += msmMs_; fft += fftMs_;
+                b0++;
+                continue;
+            }
+            stageBatch(&signals[(size_t)b0], V);
+            std::unique_lock<std::mutex> turn(proveMutex);
+            // S: the pass's blinding, in witness order (round randomness :173, then r and s :345-346), and the multiples of the
+            // deltas that need only them on host threads beside the device work
+            std::vector<uint8_t> rk((size_t)V * 32), r((size_t)V * 32), s((size_t)V * 32);
+            for (int v = 0; v < V; v++) { drawBlinding(&rk[(size_t)v * 32]); drawBlinding(&r[(size_t)v * 32]); drawBlinding(&s[(size_t)v * 32]); }
+            std::vector<std::array<u32, 8>> rkw((size_t)V);
+            for (int v = 0; v < V; v++) memcpy(rkw[(size_t)v].data(), &rk[(size_t)v * 32], 32);
+            std::vector<std::future<HostTerms>> terms;
+            for (int v = 0; v < V; v++)
+                terms.push_back(std::async(std::launch::async, [&, v] { return hostTermsFor(rkw[(size_t)v].data(), &r[(size_t)v * 32], &s[(size_t)v * 32]); }));
+            std::vector<uint8_t> sums((size_t)V * UG_GROTH16_PARTIALS_SIZE), commits((size_t)V * 64);
+            runBatch(V, &in[(size_t)b0], rkw, sums.data(), commits.data());      // (the futures join in their destructors if this throws)
+            msm += msmMs_; fft += fftMs_;
+            turn.unlock();
+            for (int v = 0; v < V; v++)
+                finishWith(&sums[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &r[(size_t)v * 32], &s[(size_t)v * 32], terms[(size_t)v].get(),
+                           &commits[(size_t)v * 64], in[(size_t)(b0 + v)].publicPart, proofs[(size_t)(b0 + v)], pubs[(size_t)(b0 + v)]);
+            b0 += V;
+        }
+        // the call's figures for ug_prover_last_timings, written under the turn as every proof writes them
+        std::lock_guard<std::mutex> turn(proveMutex);
+        msmMs_ = msm; fftMs_ = fft;
+        totalMs_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+
+private:
+    // what ug_dvec_apply_lookup refuses, found before anything is queued (its messages, in its order)
+    void checkLookupLists(const StagedWitness& w) const {
+        const uint64_t L = w.freq.size(), total = 1 + w.chunks.size() + 2 * L;
+        for (uint32_t c : w.chunks) if (c >= L) throw std::range_error("uwtns: chunk index outside the lookup table");
+        for (size_t i = 0; i < w.wIdx.size(); i++)
+            if (w.wIdx[i] >= hdr_.nVars || w.pIdx[i] >= total) throw std::range_error("uwtns: lookup index out of range");
+    }
+    static ug_lookup_lists listsOf(const StagedWitness& w) {
+        return ug_lookup_lists{w.freq.data(), w.freq.size(), w.chunks.data(), w.chunks.size(), w.wIdx.data(), w.pIdx.data(), w.wIdx.size()};
+    }
+    // witnesses per device pass for the next `requested` of a call (proveMutex held): ug_plan_proof_batch_aux over the five
+    // schedules, with the gathered aux scalars and the lookup staging counted per witness
+    int batchPerPass(int requested, const StagedWitness* next) {
+        const uint64_t nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo, nC1 = roundIdx_.size(), nC2 = finalIdx_.size();
+        if (requested <= 1 || !nC1 || !nC2 || !nw || !nh) return 1;
+        std::vector<ug_batch_schedule> sch;
+        sch.push_back(ug_batch_schedule{nw, tableW_, strideW_});
+        sch.push_back(ug_batch_schedule{nC1, tableC1_, strideC1_});
+        sch.push_back(ug_batch_schedule{nC2, tableC2_, strideC2_});
+        sch.push_back(ug_batch_schedule{nh, tableH_, strideH_});
+        if (sparseB_) sch.push_back(ug_batch_schedule{nB_, d_.tableB, d_.strideB});
+        uint64_t freeB = 0, totalB = 0;
+        ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
+        for (ug_dvec* v : {wBatch_, hBatch_, auxBatch_, wBBatch_}) if (v) freeB += ug_dvec_size(v) * 32;      // (reused or replaced)
+        // window tables that are not in use yet keep their room (none today: this prover builds its tables at create)
+        uint64_t pending = 0;
+        for (int g = 0; g < 5; g++) {
+            int c = 0, st = 0, ready = 1;
+            uint64_t bytes = 0;
+            if (tablePlan(g, &c, &st, &bytes, &ready) && !ready) pending += bytes;
+        }
+        freeB = freeB > pending ? freeB - pending : 0;
+        // per witness beyond the signal and h vectors: the larger of the two gathered sets (one aux buffer serves both rounds),
+        // the sparse-B scalars, and the lookup call's staging and scratch (the largest lists among the witnesses to come)
+        uint64_t lookup = 0;
+        for (int v = 0; v < requested; v++) {
+            const ug_lookup_lists l = listsOf(next[v]);
+            lookup = std::max(lookup, ug_lookup_vectors_bytes(hdr_.nVars, &l, 1));
+        }
+        const uint64_t aux = (std::max(nC1, nC2) + nB_) * 32 + lookup;
+        const int V = ug_plan_proof_batch_aux(sch.data(), (int)sch.size(), hdr_.nVars, hdr_.domainSize, aux, freeB, requested);
+        if (V < 1) throw std::logic_error("batch plan failed");
+        return V;
+    }
+    void ensureBatch(ug_dvec*& v, ug_ctx* ctx, uint64_t n) {
+        if (v && ug_dvec_size(v) >= n) return;
+        ug_dvec_destroy(v); v = nullptr;
+        ugCheck(ug_dvec_create(ctx, n, &v));
+    }
+    void releaseBatch() {
+        for (ug_dvec** v : {&wBatch_, &hBatch_, &auxBatch_, &wBBatch_}) { ug_dvec_destroy(*v); *v = nullptr; }
+    }
+    // the batch buffers for V witnesses (proveMutex held: an allocation may not happen while kernels of a proof are queued)
+    void reserveBatch(int V) {
+        ensureBatch(wBatch_, d_.ctx, (uint64_t)V * hdr_.nVars);
+        ensureBatch(hBatch_, d_.ctx2, (uint64_t)V * hdr_.domainSize);
+        ensureBatch(auxBatch_, d_.ctx, (uint64_t)V * std::max(roundIdx_.size(), finalIdx_.size()));
+        if (d_.Bc2) ensureBatch(wBBatch_, d_.ctx, (uint64_t)V * nB_);
+    }
+    // the V signal vectors into the batch witness buffer, on the uploader's own streams (batchMutex_ held, no turn: the last pass
+    // that read the buffer has been collected)
+    void stageBatch(const uint8_t* const* signals, int V) {
+        std::lock_guard<std::mutex> st(witness_.stageMutex);
+        const uint64_t nv = hdr_.nVars;
+        for (int v = 0; v < V; v++) {
+            ug_dvec* view = nullptr;
+            ugCheck(ug_dvec_wrap(d_.ctx, (uint8_t*)ug_dvec_device_ptr(wBatch_) + (uint64_t)v * nv * 32, nv, &view));
+            const int rc = ug_dvec_upload_idle(view, signals[v], nv);
+            ug_dvec_destroy(view);
+            ugCheck(rc);
+        }
+    }
+    // One device pass of the V staged witnesses (proveMutex held). sums = V blocks A | B1 | B2 | C | H as a single proof leaves
+    // them, commits = the V blinded round commitments (pi_r); in[v].publicPart receives witness v's lookup writes.
+    void runBatch(int V, StagedWitness* in, const std::vector<std::array<u32, 8>>& rkw, uint8_t* sums, uint8_t* commits) {
+        const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize, nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
+        const uint64_t nC1 = roundIdx_.size(), nC2 = finalIdx_.size();
+        ugCheck(ug_ctx_timings(d_.ctx, nullptr, nullptr, 1)); ugCheck(ug_ctx_timings(d_.ctx2, nullptr, nullptr, 1));
+        std::vector<uint8_t> outR((size_t)V * 64), outA((size_t)V * 64), outB1((size_t)V * 64), outB2((size_t)V * 128), outC((size_t)V * 64),
+            outH((size_t)V * 64);
+        std::vector<ug_dvec*> views;
+        struct Views { std::vector<ug_dvec*>& v; ~Views() { for (ug_dvec* x : v) ug_dvec_destroy(x); } } viewsGuard{views};
+        auto view = [&](ug_ctx* ctx, ug_dvec* of, uint64_t first, uint64_t n) {
+            views.push_back(nullptr);
+            ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(of) + first * 32, n, &views.back()));
+            return views.back();
+        };
+        std::vector<ug_dvec*> wv((size_t)V);
+        for (int v = 0; v < V; v++) wv[(size_t)v] = view(d_.ctx, wBatch_, (uint64_t)v * nv, nv);
+        QueueGuard inFlight(d_.ctx, d_.ctx2);
+        // round 1 (execute_round :161-184): V gathers of the round set, ONE schedule over them, ONE product -> V records
+        for (int v = 0; v < V; v++) ugCheck(ug_dvec_gather_index_at(auxBatch_, (uint64_t)v * nC1, wv[(size_t)v], d_.roundIdx));
+        ugCheck(ug_schedule_build_vectors(d_.saux, auxBatch_, 0, nC1, V, nC1, tableC1_, strideC1_));
+        {
+            const ug_bases* set[1] = {d_.roundC};
+            void* out[1] = {outR.data()};
+            ugCheck(ug_msm_batch_enqueue(d_.ctx, 1, set, d_.saux, nullptr, out));
+        }
+        ugCheck(ug_ctx_collect(d_.ctx));
+        // host: the V blinded commitments (:176) on host threads, their Fiat-Shamir challenges (:33-58)
+        {
+            const G1XYZZ delta1 = g1FromRecord(hdr_.delta1);
+            std::vector<std::future<void>> jobs;
+            for (int v = 0; v < V; v++)
+                jobs.push_back(std::async(std::launch::async, [&, v] {
+                    g1ToRecord(commits + (size_t)v * 64, xyzz_add(g1FromRecord(&outR[(size_t)v * 64]), xyzz_mul_scalar_w4(delta1, rkw[(size_t)v].data())));
+                }));
+            for (auto& j : jobs) j.get();
+        }
+        // lookup completion (compute_lookup :62-106) of all V witnesses: one call, one host wait. The tables come back to the
+        // host only when a public signal takes a value of one (the challenge itself, push[0], is known here).
+        std::vector<uint8_t> rands((size_t)V * 32);
+        std::vector<ug_lookup_lists> lists((size_t)V);
+        bool needTables = false;
+        for (int v = 0; v < V; v++) {
+            putPlain(&rands[(size_t)v * 32], deriveChallenge(commits + (size_t)v * 64));
+            lists[(size_t)v] = listsOf(in[v]);
+            for (size_t i = 0; i < in[v].wIdx.size() && !needTables; i++) needTables = in[v].wIdx[i] <= hdr_.nPublic && in[v].pIdx[i] != 0;
+        }
+        std::vector<std::vector<uint8_t>> tables;
+        std::vector<void*> tablePtrs;
+        if (needTables)
+            for (int v = 0; v < V; v++) {
+                tables.emplace_back((2 * in[v].freq.size() + 1) * 32);
+                tablePtrs.push_back(tables.back().data());
+            }
+        ugCheck(ug_dvec_complete_lookup_vectors(wBatch_, nv, V, rands.data(), lists.data(), needTables ? tablePtrs.data() : nullptr));
+        for (int v = 0; v < V; v++) {                     // the same writes for the public signals, in order (applyLookup)
+            const StagedWitness& w = in[v];
+            const uint64_t Cn = w.chunks.size();
+            for (size_t i = 0; i < w.wIdx.size(); i++) {
+                if (w.wIdx[i] > hdr_.nPublic) continue;
+                const uint64_t p = w.pIdx[i];
+                const uint64_t t = p == 0 ? 0 : p <= Cn ? 1 + (uint64_t)w.chunks[p - 1] : p - Cn;
+                memcpy(in[v].publicPart.data() + (size_t)w.wIdx[i] * 32, t == 0 ? &rands[(size_t)v * 32] : tables[(size_t)v].data() + t * 32, 32);
+            }
+        }
+        // final round (execute_final_round :187-399): MSM1-3 over ONE V-vector witness schedule, V gathers of the final set and
+        // MSM4 over ONE schedule, the FFT block per witness into V slices of the h buffer, MSM5 over ONE schedule; one host wait
+        ugCheck(ug_schedule_build_vectors(d_.sw, wBatch_, wr_.lo, nw, V, nv, tableW_, strideW_));
+        enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), nullptr, 0, false, wBatch_, V, nv, wBBatch_);
+        for (int v = 0; v < V; v++) ugCheck(ug_dvec_gather_index_at(auxBatch_, (uint64_t)v * nC2, wv[(size_t)v], d_.finalIdx));
+        ugCheck(ug_schedule_build_vectors(d_.saux, auxBatch_, 0, nC2, V, nC2, tableC2_, strideC2_));
+        {
+            const ug_bases* set[1] = {d_.C};
+            void* out[1] = {outC.data()};
+            ugCheck(ug_msm_batch_enqueue(d_.ctx, 1, set, d_.saux, nullptr, out));
+        }
+        const char* ov = getenv("ULTRAGROTH_OVERLAP");
+        if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));          // (default: beside, as a single proof)
+        for (int v = 0; v < V; v++)
+            ugCheck(ug_hpoly_run(d_.hp, view(d_.ctx2, wBatch_, (uint64_t)v * nv, nv), view(d_.ctx2, hBatch_, (uint64_t)v * dom, dom)));
+        ugCheck(ug_schedule_build_vectors(d_.sh, hBatch_, hr_.lo, nh, V, dom, tableH_, strideH_));
+        {
+            const ug_bases* set[1] = {d_.H};
+            void* out[1] = {outH.data()};
+            ugCheck(ug_msm_batch_enqueue(d_.ctx2, 1, set, d_.sh, nullptr, out));
+        }
+        ugCheck(ug_ctx_collect(d_.ctx2));
+        ugCheck(ug_ctx_collect(d_.ctx));
+        inFlight.done();
+        collectTimings(3);
+        for (int v = 0; v < V; v++) {
+            uint8_t* p = sums + (size_t)v * UG_GROTH16_PARTIALS_SIZE;
+            memset(p, 0, UG_GROTH16_PARTIALS_SIZE);
+            memcpy(p, &outA[(size_t)v * 64], 64); memcpy(p + 64, &outB1[(size_t)v * 64], 64); memcpy(p + 128, &outB2[(size_t)v * 128], 128);
+            memcpy(p + 256, &outC[(size_t)v * 64], 64); memcpy(p + 320, &outH[(size_t)v * 64], 64);
+        }
+    }
+
+public:
     unsigned long long proofBufferMinSize() const override { return PROOF_MIN_ULTRA; }
     unsigned long long publicBufferMinSize() const override { return publicMin((unsigned long long)hdr_.nPublic - 1); }
     void timings(double* msm, double* fft, double* total) const override {
@@ -2291,8 +2559,13 @@ private:
     double m1_ = 0, f1_ = 0, m2_ = 0, f2_ = 0;                     // device ms per stream (witness stream, H branch)
     int witnessQueued_ = 0;                                        // witnessMsmBegin .. witnessMsmEnd
     uint8_t queuedParts_[UG_GROTH16_PARTIALS_SIZE] = {};
+    bool batchable_ = false;                                       // a created prover on one device (proveBatch)
+    // batched proofs: V signal vectors / h vectors / gathered round or final scalars / sparse-B scalars
+    ug_dvec *wBatch_ = nullptr, *hBatch_ = nullptr, *auxBatch_ = nullptr, *wBBatch_ = nullptr;
+    std::mutex batchMutex_;            // one batch call at a time owns them (lock order: batchMutex_ -> witness lease -> proveMutex)
 public:
     ug_ctx* ctx2() { return d_.ctx2; }                             // the H branch's context
+    ~UltraGrothProver() override { releaseBatch(); }               // (before d_ goes: the buffers refer to its contexts)
 };
 
 

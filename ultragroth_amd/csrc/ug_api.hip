@@ -646,6 +646,18 @@ int ug_plan_proof_batch(const ug_batch_schedule* schedules, int n_schedules, uin
         return v;
     } catch (...) { return 0; }
 }
+// ... for a prover whose pass holds more per witness than the witness and h vectors (UltraGroth: gathered aux scalars, lookup
+// staging): the same limits, with V * aux_bytes_per_witness counted in the memory model. aux_bytes_per_witness = 0 is
+// ug_plan_proof_batch.
+int ug_plan_proof_batch_aux(const ug_batch_schedule* schedules, int n_schedules, uint64_t n_vars, uint64_t domain,
+                            uint64_t aux_bytes_per_witness, uint64_t free_bytes, int requested) {
+    try {
+        int v = ug_plan_proof_batch(schedules, n_schedules, n_vars, domain, free_bytes, requested);
+        while (v > 1 && ((u64)v * aux_bytes_per_witness > free_bytes ||
+                         batch_bytes(schedules, n_schedules, n_vars, domain, v) > free_bytes - (u64)v * aux_bytes_per_witness)) v--;
+        return v;
+    } catch (...) { return 0; }
+}
 int ug_bases_precompute(ug_bases* b, int c) { return ug_bases_precompute_strided(b, c, 1); }
 int ug_bases_precompute_strided(ug_bases* b, int c, int stride) {
     UG_TRY
@@ -960,6 +972,116 @@ int ug_fr_lookup_table(ug_ctx* c, const void* rand_plain, const uint32_t* freque
     UG_HIP(hipMemcpyAsync(table_out, table, tbytes, hipMemcpyDeviceToHost, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));
     UG_CATCH
+}
+// ---- the vector forms: V witnesses of a batched proof (include/ultragroth_hip.h) ----
+// One staging buffer per call: [LookupVec x V | challenges | tables given by the caller | frequencies, w_idx, p_idx, chunks of
+// every witness] goes up in ONE copy; tables made on the device follow behind it. One table launch, one mark / write / clear
+// sequence over all vectors, one copy back of the tables, one host wait.
+namespace {
+void lookup_vectors(ug_ctx* c, ug_dvec* dst, uint64_t stride, int V, const void* rands, const ug_lookup_lists* lists,
+                    const void* const* tables_in, void* const* tables_out) {
+    if (!c || !lists || V < 1 || V > UG_BATCH_MAX) throw std::invalid_argument(V < 1 || V > UG_BATCH_MAX ? "vectors outside 1 .. UG_BATCH_MAX" : "null argument");
+    if (!rands && !tables_in) throw std::invalid_argument("null argument");
+    if (dst && (stride > dst->n || (uint64_t)V * stride > dst->n)) throw std::invalid_argument("lookup vectors outside the vector");
+    uint64_t max_n = 0, max_L = 0;
+    for (int v = 0; v < V; v++) {
+        const ug_lookup_lists& l = lists[v];
+        if ((!l.frequencies && l.lookup_size && rands) || (tables_in && !tables_in[v]) || (tables_out && !tables_out[v]))
+            throw std::invalid_argument("null argument");
+        max_L = std::max<uint64_t>(max_L, l.lookup_size);
+        if (!dst) continue;
+        if (((!l.w_idx || !l.p_idx) && l.n) || (!l.chunks && l.n_chunks)) throw std::invalid_argument("null argument");
+        if (l.n >= 0xffffffffull) throw std::invalid_argument("too many lookup writes");
+        const uint64_t total = 1 + l.n_chunks + 2 * l.lookup_size;
+        for (uint64_t j = 0; j < l.n_chunks; j++)
+            if (l.chunks[j] >= l.lookup_size) throw std::range_error("uwtns: chunk index outside the lookup table");
+        for (uint64_t i = 0; i < l.n; i++)
+            if (l.w_idx[i] >= stride || l.p_idx[i] >= total) throw std::range_error("uwtns: lookup index out of range");
+        max_n = std::max<uint64_t>(max_n, l.n);
+    }
+    c->use();
+    // the layout, in u32 words (descriptors, challenges and tables are multiples of 8 words: 32-byte elements stay aligned)
+    const uint64_t descWords = ((uint64_t)V * sizeof(LookupVec) / 4 + 7) / 8 * 8;
+    std::vector<LookupVec> vec((size_t)V);
+    uint64_t at = descWords;
+    for (int v = 0; v < V; v++) { vec[(size_t)v].r_off = at; at += 8; }
+    auto tablesAt = [&](uint64_t from) {
+        for (int v = 0; v < V; v++) { vec[(size_t)v].t_off = from; from += (1 + 2 * lists[v].lookup_size) * 8; }
+        return from;
+    };
+    if (tables_in) at = tablesAt(at);
+    for (int v = 0; v < V; v++) {
+        const ug_lookup_lists& l = lists[v];
+        LookupVec& d = vec[(size_t)v];
+        d.L = l.lookup_size; d.n = dst ? l.n : 0; d.n_chunks = dst ? l.n_chunks : 0;
+        d.f_off = at; at += rands ? d.L : 0;
+        d.w_off = at; at += d.n;
+        d.p_off = at; at += d.n;
+        d.c_off = at; at += d.n_chunks;
+    }
+    const uint64_t upWords = at;
+    uint64_t tablesFirst = 0, tablesWords = 0;             // tables made here: behind what goes up
+    if (!tables_in) { tablesFirst = (at + 7) / 8 * 8; at = tablesAt(tablesFirst); tablesWords = at - tablesFirst; }
+    std::vector<u32> host((size_t)upWords, 0);
+    memcpy(host.data(), vec.data(), (size_t)V * sizeof(LookupVec));
+    for (int v = 0; v < V; v++) {
+        const ug_lookup_lists& l = lists[v];
+        const LookupVec& d = vec[(size_t)v];
+        if (rands) memcpy(&host[d.r_off], (const uint8_t*)rands + (size_t)v * 32, 32);
+        if (tables_in) memcpy(&host[d.t_off], tables_in[v], (size_t)(1 + 2 * d.L) * 32);
+        if (rands && d.L) memcpy(&host[d.f_off], l.frequencies, (size_t)d.L * 4);
+        if (d.n) { memcpy(&host[d.w_off], l.w_idx, (size_t)d.n * 4); memcpy(&host[d.p_off], l.p_idx, (size_t)d.n * 4); }
+        if (d.n_chunks) memcpy(&host[d.c_off], l.chunks, (size_t)d.n_chunks * 4);
+    }
+    if (dst && max_n && c->lookup_last_n < (uint64_t)V * stride) {
+        if (c->lookup_last) hipFree(c->lookup_last);
+        c->lookup_last = nullptr; c->lookup_last_n = 0;
+        UG_HIP(hipMalloc(&c->lookup_last, (size_t)V * stride * 4));
+        UG_HIP(hipMemsetAsync(c->lookup_last, 0, (size_t)V * stride * 4, c->stream));
+        c->lookup_last_n = (uint64_t)V * stride;
+    }
+    u32* stage = c->stage_for_lookup((size_t)std::max(at, upWords) * 4);
+    const LookupVec* vecDev = reinterpret_cast<const LookupVec*>(stage);
+    UG_HIP(hipMemcpyAsync(stage, host.data(), (size_t)upWords * 4, hipMemcpyHostToDevice, c->stream));
+    if (rands) lookup_tables_vectors(stage, vecDev, V, max_L, c->stream);
+    if (dst) apply_lookup_vectors(dst->data, stride, c->lookup_last, stage, vecDev, V, max_n, c->stream);
+    std::vector<u32> back;
+    if (tables_out && rands) {
+        back.resize((size_t)tablesWords);
+        UG_HIP(hipMemcpyAsync(back.data(), stage + tablesFirst, (size_t)tablesWords * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    UG_HIP(hipStreamSynchronize(c->stream));
+    if (tables_out && rands)
+        for (int v = 0; v < V; v++)
+            memcpy(tables_out[v], &back[(size_t)(vec[(size_t)v].t_off - tablesFirst)], (size_t)(1 + 2 * vec[(size_t)v].L) * 32);
+}
+}  // namespace
+int ug_fr_lookup_tables(ug_ctx* c, int vectors, const void* rands_plain, const ug_lookup_lists* lists, void* const* tables_out) {
+    UG_TRY
+    if (!rands_plain || !tables_out) throw std::invalid_argument("null argument");
+    lookup_vectors(c, nullptr, 0, vectors, rands_plain, lists, nullptr, tables_out);
+    UG_CATCH
+}
+int ug_dvec_apply_lookup_vectors(ug_dvec* dst, uint64_t vector_stride, int vectors, const ug_lookup_lists* lists, const void* const* tables) {
+    UG_TRY
+    if (!dst || !tables) throw std::invalid_argument("null argument");
+    lookup_vectors(dst->ctx, dst, vector_stride, vectors, nullptr, lists, tables, nullptr);
+    UG_CATCH
+}
+int ug_dvec_complete_lookup_vectors(ug_dvec* dst, uint64_t vector_stride, int vectors, const void* rands_plain, const ug_lookup_lists* lists,
+                                    void* const* tables_out) {
+    UG_TRY
+    if (!dst || !rands_plain) throw std::invalid_argument("null argument");
+    lookup_vectors(dst->ctx, dst, vector_stride, vectors, rands_plain, lists, nullptr, tables_out);
+    UG_CATCH
+}
+uint64_t ug_lookup_vectors_bytes(uint64_t vector_stride, const ug_lookup_lists* lists, int vectors) {
+    if (!lists || vectors < 1) return 0;
+    uint64_t bytes = 0;
+    for (int v = 0; v < vectors; v++)
+        bytes += sizeof(LookupVec) + 64 + 4 * vector_stride + 4 * (lists[v].lookup_size + 2 * lists[v].n + lists[v].n_chunks) +
+                 32 * (1 + 2 * lists[v].lookup_size);
+    return bytes;
 }
 uint64_t ug_dvec_size(const ug_dvec* v) { return v ? v->n : 0; }
 void* ug_dvec_device_ptr(const ug_dvec* v) { return v ? v->data : nullptr; }

@@ -302,6 +302,33 @@ def build_ultra_witness(log_domain, mix="C", seed=0x5EED0005, lookup_log=8):
     return _ultra_witness(log_domain, mix, seed, lookup_log, idx2, rng)[0]
 
 
+def build_ultra_witnesses(log_domain, count, seed=0x5EED0005, lookup_log=8, witness_seed=0x7000):
+    """`count` distinct .uwtns for build_ultra_circuit(log_domain, seed=seed): the lookup index lists (sections 5, 6) of
+    build_ultra_witness, and signals (uniform / circom-like alternating), chunks and frequencies drawn per witness from
+    witness_seed + 16 b."""
+    nvars = (1 << log_domain) - 1
+    r_le = R_MOD.to_bytes(32, "little")
+    _, idx2, rng = _ultra_index_lists(log_domain, seed)
+    lookup, n_chunks = 1 << lookup_log, max(nvars // 8, 1)
+    rng.integers(0, lookup, size=n_chunks, dtype=np.uint32); rng.integers(0, 1 << 20, size=lookup, dtype=np.uint32)   # (the base witness's draws)
+    n_push = 2 * lookup + n_chunks + 1
+    targets = rng.permutation(idx2)[:min(n_push - 1, len(idx2))]
+    w_idx = np.concatenate([np.array([2], dtype=np.uint32), targets]).astype("<u4")
+    p_idx = np.concatenate([np.array([0], dtype=np.uint32), 1 + rng.permutation(n_push - 1)[:len(targets)].astype(np.uint32)]).astype("<u4")
+    out = []
+    for b in range(count):
+        ws = witness_seed + 16 * b
+        w = scalars(nvars, "UC"[b % 2], ws)
+        w[0] = (1, 0, 0, 0)
+        g = np.random.Generator(np.random.PCG64(ws + 1))
+        chunks = g.integers(0, lookup, size=n_chunks, dtype=np.uint32).astype("<u4")
+        freq = g.integers(0, 1 << 20, size=lookup, dtype=np.uint32).astype("<u4")
+        uw = [(1, struct.pack("<I", 32) + r_le + struct.pack("<I", nvars)), (2, w.tobytes()), (3, chunks.tobytes()),
+              (4, freq.tobytes()), (5, w_idx.tobytes()), (6, p_idx.tobytes())]
+        out.append(b"wtns" + struct.pack("<II", 2, len(uw)) + b"".join(_section(i, p) for i, p in uw))
+    return out
+
+
 def build_ultra_circuit(dev, log_domain, mix="C", seed=0x5EED0005, lookup_log=8, b_zero=0.0):
     """UltraGroth (protocol 1337) zkey + .uwtns of the same shapes: SURVEY.md section 8(d) config 5.
 
