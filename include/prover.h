@@ -117,6 +117,30 @@ int ultra_groth_prover_zkey_file(const char *zkey_file_path,
  * library first looks (tests, bench.py --check, smoke()); otherwise it changes nothing and returns PROVER_ERROR. */
 int ug_test_set_blinding(const void *bytes, unsigned long long n);
 
+/* ZKEY VALIDATION. A truncated download, a flipped bit, a faulty setup tool or a key for another curve gives proofs that never
+ * verify, and nothing says why. With ULTRAGROTH_VALIDATE=1|2 in the environment when a prover is created -- every *_create*
+ * call here, the one-shot calls and their _zkey_file forms, ULTRAGROTH_DEVICES provers, the *_create_sharded* forms, and
+ * ug_registry_load* including the registry's reload of an evicted circuit -- every base point is checked on the device as it is
+ * uploaded (include/ultragroth_hip.h, ug_ctx_check_points): level 1 the field range of the raw coordinates and the curve equation,
+ * level 2 also that each G2 point lies in the subgroup of order r (a scalar multiplication per point: seconds at 2^24). Checked:
+ * the header's points, sections 5 (A), 6 (B1), 7 (B2), 8 (C), 9 (H) of a Groth16 key, sections 5, 6, 7, 8 (C1), 9 (C2), 12 (H) of
+ * an UltraGroth key. A bad key fails the creation with PROVER_ERROR and
+ *     zkey: section <id> point <index>: <reason>          (index: the point's place in that section of the zkey, also for a
+ *     zkey: header point <name>: <reason>                  rank's slice and for the compacted B sets)
+ * with <reason> one of "coordinate not below the field modulus", "not on the curve", "not in the subgroup of order r" and <name>
+ * one of alpha1, beta1, beta2, gamma2, delta1, delta2, round_delta1, round_delta2; no prover object is returned and nothing
+ * stays allocated on the device. Unset or 0 (the default) nothing is checked and nothing changes; any other value than 0, 1, 2
+ * fails the creation with "ULTRAGROTH_VALIDATE must be 0, 1 or 2, ..." (a mistyped setting never switches the check off silently).
+ *
+ * ug_zkey_check is the same check without a prover: it parses the key, streams the header's points and every point section --
+ * section 3 (IC) as well, when the key has one -- through a bounded device buffer on `device` and keeps nothing (each call makes
+ * and destroys a context of its own: a stream and 64 MiB of pinned staging, an admission step's price, not a per-proof one). PROVER_OK: a clean key. PROVER_ERROR
+ * with the message above and *fault filled (fault may be NULL): a bad point; section 2 = the header, index = the place of the
+ * point in the list of names above. PROVER_ERROR with the loaders' messages and fault->reason = 0: a key that cannot be parsed. */
+typedef struct { int section; unsigned long long index; int reason; } ug_zkey_fault;
+int ug_zkey_check(const void *zkey_buffer, unsigned long long zkey_size, int device, int level, ug_zkey_fault *fault,
+                  char *error_msg, unsigned long long error_msg_maxsize);
+
 /* BATCHED PROOFS: `count` witnesses (wtns / uwtns file buffers) proved in one call; proof_buffers[b] / public_buffers[b] receive
  * what groth16_prover_prove (ultra_groth_prover_prove for an UltraGroth handle) returns for witness b, byte for byte, sized as
  * there (proof_sizes[b], public_sizes[b]). A bad witness fails the whole call with the code and message the single prove gives

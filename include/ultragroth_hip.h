@@ -32,6 +32,10 @@
  *
  *   deployment         ULTRAGROTH_DEVICE=n        device of a prover made by the reference's create calls (default 0)
  *                      ULTRAGROTH_DEVICES=a,b,..  one proof sharded over the listed devices behind the reference's API
+ *                      ULTRAGROTH_VALIDATE=0|1|2  check every base point of a zkey on the device while a prover is created: 0 / unset
+ *                                                 never (default) | 1 field range and curve equation | 2 also the G2 points'
+ *                                                 membership of the order-r subgroup (include/prover.h: a bad key is refused)
+ *                                                 (any other value fails the creation)
  *                      ULTRAGROTH_TABLES=0|1|2    fixed-base window tables: never | created provers (default) | one-shot calls too
  *                      ULTRAGROTH_OVERLAP=0|1|2   H branch behind / beside (default since round 5) the witness products on one device
  *                                                 (0: one kernel on the chip at a time, for clean per-kernel times)
@@ -183,6 +187,34 @@ int      ug_bases_tables_step(ug_bases* b, uint64_t max_points, uint64_t* remain
 int      ug_bases_tables_ready(const ug_bases* b);
 int      ug_ctx_mem_info(ug_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 void ug_bases_destroy(ug_bases* b);
+
+/* POINT VALIDATION (check.hip). A zkey record is checked as it arrives, Montgomery R = 2^256, before anything reduces it. The
+ * all-zero record is the point at infinity and passes; any other record breaks the FIRST of these rules that applies:
+ *   UG_POINT_UNREDUCED      a coordinate (any of the four Fq components of a G2 point) is >= q as a raw 256-bit integer
+ *   UG_POINT_OFF_CURVE      y^2 != x^3 + 3 (G1), y^2 != x^3 + 3/(9+u) over Fq2 (G2)
+ *   UG_POINT_OFF_SUBGROUP   level 2, G2 only: [r]P is not the point at infinity (the twist has cofactor 2q - r) */
+#define UG_POINT_OK 0
+#define UG_POINT_UNREDUCED 1
+#define UG_POINT_OFF_CURVE 2
+#define UG_POINT_OFF_SUBGROUP 3
+typedef struct { uint64_t index; int reason; } ug_point_fault;
+/* n zkey-format records in HOST memory, staged through the context as an upload is; level 1 = rules 1-2, level 2 = also rule 3.
+ * UG_OK when the check ran (out->reason = UG_POINT_OK: every point passed; else the LOWEST bad index and the first rule it
+ * breaks); UG_ERROR only for bad arguments / device errors. Keeps nothing resident. */
+int  ug_points_check(ug_ctx* ctx, int g2, const void* host_points, uint64_t n, int level, ug_point_fault* out);
+/* As ug_ctx_defer_tables: after ug_ctx_check_points(ctx, level), every ug_bases_create_* / ug_bases_create_group_* on this
+ * context checks its records at that level (0 = off, the default), each upload chunk behind its own DMA and before its
+ * conversion. A bad point fails the creation with UG_ERROR, ug_last_error() = "point <global index>: <reason text>" (global
+ * index = global_first + position) or "member <m> point <index>: ..." for a group (index = first[m] + position), *out
+ * untouched, every device byte of the half-made set freed and no table build started. The reason texts are
+ * "coordinate not below the field modulus", "not on the curve", "not in the subgroup of order r". */
+int  ug_ctx_check_points(ug_ctx* ctx, int level);
+/* What the last ug_bases_create_* / ug_bases_create_group_* on this context found, as numbers (callers that translate the index
+ * need not read the message): out->reason = UG_POINT_OK when that creation met no bad point (whatever else it may have failed
+ * on), else the fault its message names; *member (may be NULL) = the group member, -1 for a plain set. */
+int  ug_ctx_last_point_fault(const ug_ctx* ctx, int* member, ug_point_fault* out);
+/* the fixed reason text of UG_POINT_UNREDUCED / _OFF_CURVE / _OFF_SUBGROUP ("" for anything else) */
+const char* ug_point_reason_text(int reason);
 
 /* device vectors of n 32-byte elements */
 int  ug_dvec_create(ug_ctx* ctx, uint64_t n, ug_dvec** out);

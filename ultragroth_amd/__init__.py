@@ -99,6 +99,33 @@ def ultra_groth_public_size_for_zkey_buf(zkey):
 
 
 # ---------------------------------------------------------------------------------------------------
+# zkey validation (include/prover.h: ug_zkey_check; include/ultragroth_hip.h: ug_points_check)
+UG_POINT_OK, UG_POINT_UNREDUCED, UG_POINT_OFF_CURVE, UG_POINT_OFF_SUBGROUP = 0, 1, 2, 3
+
+
+class _PointFault(C.Structure):
+    _fields_ = [("index", C.c_uint64), ("reason", C.c_int)]
+
+
+class _ZkeyFault(C.Structure):
+    _fields_ = [("section", C.c_int), ("index", C.c_ulonglong), ("reason", C.c_int)]
+
+
+def zkey_check(zkey, level=2, device=0):
+    """ug_zkey_check: None for a key whose every point passes, else (section, index, reason, message) -- section 2 is the header,
+    reason one of UG_POINT_*. A key that cannot be parsed raises ProverError with the loaders' message."""
+    fault = _ZkeyFault()
+    err = C.create_string_buffer(1024)
+    rc = load().ug_zkey_check(zkey, len(zkey), device, level, C.byref(fault), err, len(err) - 1)
+    if rc == PROVER_OK:
+        return None
+    msg = err.value.decode(errors="replace")
+    if fault.reason == UG_POINT_OK:
+        raise ProverError(rc, msg)
+    return fault.section, fault.index, fault.reason, msg
+
+
+# ---------------------------------------------------------------------------------------------------
 # verifier mirror (src/verifier.h)
 VERIFIER_VALID_PROOF, VERIFIER_INVALID_PROOF, VERIFIER_ERROR = 0, 1, 2
 
@@ -722,6 +749,16 @@ class Device:
             self.close()
         except Exception:
             pass
+
+    def check_points(self, points, n, g2=False, level=1):
+        """ug_points_check over n zkey-format records: None when every point passes, else (index, reason) of the lowest bad one"""
+        f = _PointFault()
+        _check(self._L.ug_points_check(self._h, 1 if g2 else 0, points, n, level, C.byref(f)))
+        return None if f.reason == UG_POINT_OK else (f.index, f.reason)
+
+    def check_on_create(self, level):
+        """ug_ctx_check_points: the sets created on this device from now on check their records (0: off)"""
+        _check(self._L.ug_ctx_check_points(self._h, level))
 
     # -- raw handles
     def bases(self, points, n, g2=False, global_first=0, table_c=0, table_stride=1):

@@ -31,7 +31,7 @@ INNER_SYMBOLS = [
     "ug_bases_precompute_strided", "ug_schedule_build_tables_strided", "ug_bases_tables_bytes_strided", "ug_bases_table_stride",
     "ug_plan_window_tables", "ug_schedule_build_vectors", "ug_dvec_gather_index_at", "ug_plan_proof_batch",
     "ug_plan_proof_batch_aux", "ug_fr_lookup_tables", "ug_dvec_apply_lookup_vectors", "ug_dvec_complete_lookup_vectors",
-    "ug_lookup_vectors_bytes",
+    "ug_lookup_vectors_bytes", "ug_points_check", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify"]        # include/verifier.h
 OUTER_SYMBOLS = [
@@ -59,7 +59,7 @@ OUTER_SYMBOLS = [
     "ug_groth16_prover_run_witness_msm", "ug_groth16_prover_run_h_msm", "ug_groth16_prover_hpoly_chain",
     "ug_groth16_prover_hpoly_combine", "ug_groth16_prover_h_range",
     "ug_groth16_prover_witness_msm_begin", "ug_groth16_prover_witness_msm_end",
-    "ug_groth16_prover_prove_batch",
+    "ug_groth16_prover_prove_batch", "ug_zkey_check",
 ]
 
 
@@ -140,6 +140,11 @@ def load():
     L.ug_bases_tables_bytes.argtypes = [u64, C.c_int, C.c_int]; L.ug_bases_tables_bytes.restype = u64
     L.ug_bases_precompute.argtypes = [vp, C.c_int]
     L.ug_ctx_mem_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.ug_points_check.argtypes = [vp, C.c_int, vp, u64, C.c_int, vp]
+    L.ug_ctx_check_points.argtypes = [vp, C.c_int]
+    L.ug_ctx_last_point_fault.argtypes = [vp, vp, vp]
+    L.ug_point_reason_text.argtypes = [C.c_int]; L.ug_point_reason_text.restype = C.c_char_p
+    L.ug_zkey_check.argtypes = [vp, ull, C.c_int, C.c_int, vp, vp, ull]
     L.ug_schedule_build_tables.argtypes = [vp, vp, u64, u64, C.c_int]
     for n in ("ug_bases_create_tables_strided_g1", "ug_bases_create_tables_strided_g2"):
         getattr(L, n).argtypes = [vp, vp, u64, u64, C.c_int, C.c_int, pp]

@@ -291,6 +291,11 @@ void build_window_tables(bool g2, u32* pts, u64 n, int doublings, int tables, hi
 // bench / test tooling: out[i] = (seed + i) * G as zkey-format records (device buffer); G given as a host record
 void synth_points(bool g2, u32* out_dev, const u32* gen_record_host, u64 seed, u64 n, hipStream_t stream);
 
+// ---- check.hip ----------------------------------------------------------------------------------------
+// n RAW zkey records on the device (before convert_points_*): every bad one does atomicMin(*fault, (index0 + i) << 2 | reason),
+// reason = the first of UG_POINT_UNREDUCED / _OFF_CURVE / _OFF_SUBGROUP (G2, level 2 only) it breaks. *fault starts as all ones.
+void check_points(bool g2, const u32* pts, u64 n, u64 index0, int level, unsigned long long* fault, hipStream_t stream);
+
 // ---- hpoly.hip ----------------------------------------------------------------------------------------
 struct CoefMatrix {
     u64 ncoefs = 0; u32 domain = 0; int logn = 0;

@@ -57,6 +57,71 @@ void ugCheck(int rc) {
     if (rc != UG_OK) throw std::runtime_error(ug_last_error());
 }
 
+// ---- ULTRAGROTH_VALIDATE: the base points of a zkey checked on the device while a prover is created (check.hip) ---------------
+// Read when a prover is created; unset or 0 takes exactly the path without it (no call below does anything then). The contexts
+// of the prover get ug_ctx_check_points(level), so every set checks its records behind their DMA; the fault the inner layer
+// remembers on the context (ug_ctx_last_point_fault) is turned into "zkey: section <id> point <index>: ..." with the index the
+// point has in its zkey section -- whatever slice, group or compacted set it was uploaded in.
+// A value other than 0, 1 or 2 fails the creation: a mistyped setting must not switch the check off without a word.
+int validateLevel() {
+    const char* e = getenv("ULTRAGROTH_VALIDATE");
+    if (!e || !e[0]) return 0;
+    if (e[1] || e[0] < '0' || e[0] > '2') throw std::invalid_argument(std::string("ULTRAGROTH_VALIDATE must be 0, 1 or 2, not \"") + e + "\"");
+    return e[0] - '0';
+}
+class ZkeyPointFault : public std::invalid_argument {
+public:
+    explicit ZkeyPointFault(const std::string& m) : std::invalid_argument(m) {}
+};
+// where the records of a set (a member of a group) come from: record j is point sliceFirst + j of zkey section `section` (point
+// support[j] for a compacted set) and was given the index idFirst + j by the create call
+struct PointOrigin { int section; uint64_t sliceFirst, idFirst; const uint32_t* support; };
+// rc of a ug_bases_create_* call on ctx: throws when a point failed its check (origins: one per member); every other failure is the caller's
+void throwIfPointFault(ug_ctx* ctx, int rc, const PointOrigin* origins, int members = 1) {
+    if (rc == UG_OK) return;
+    ug_point_fault f;
+    int m = -1;
+    const bool bad = ug_ctx_last_point_fault(ctx, &m, &f) == UG_OK && f.reason != UG_POINT_OK;
+    if (!bad) return;
+    const PointOrigin& o = origins[m >= 0 && m < members ? m : 0];
+    const uint64_t j = f.index - o.idFirst;
+    const uint64_t at = o.support ? o.support[j] : o.sliceFirst + j;
+    throw ZkeyPointFault("zkey: section " + std::to_string(o.section) + " point " + std::to_string(at) + ": " + ug_point_reason_text(f.reason));
+}
+void ugCheckPoints(ug_ctx* ctx, int rc, const PointOrigin& origin) { throwIfPointFault(ctx, rc, &origin); ugCheck(rc); }
+// The header's points (section 2) through the same kernels, with small n: no second implementation on the host. Index = place in
+// this list; the first bad one in that order is reported.
+const char* const HEADER_POINT_NAMES[8] = {"alpha1", "beta1", "beta2", "gamma2", "delta1", "delta2", "round_delta1", "round_delta2"};
+// false: clean; true: *which / *reason say what is wrong
+bool headerPointFault(ug_ctx* ctx, const ZkeyHeader& h, bool ultra, int level, int* which, int* reason) {
+    const uint8_t* g1[4] = {h.alpha1, h.beta1, h.delta1, h.roundDelta1};
+    const uint8_t* g2[4] = {h.beta2, h.gamma2, h.delta2, h.roundDelta2};
+    static const int g1Index[4] = {0, 1, 4, 6}, g2Index[4] = {2, 3, 5, 7};
+    const int n = ultra ? 4 : 3;
+    uint8_t rec1[4 * 64], rec2[4 * 128];
+    for (int k = 0; k < n; k++) { memcpy(rec1 + 64 * k, g1[k], 64); memcpy(rec2 + 128 * k, g2[k], 128); }
+    ug_point_fault f1, f2;
+    ugCheck(ug_points_check(ctx, 0, rec1, (uint64_t)n, level, &f1));
+    ugCheck(ug_points_check(ctx, 1, rec2, (uint64_t)n, level, &f2));
+    if (f1.reason == UG_POINT_OK && f2.reason == UG_POINT_OK) return false;
+    const int i1 = f1.reason != UG_POINT_OK ? g1Index[f1.index] : 99, i2 = f2.reason != UG_POINT_OK ? g2Index[f2.index] : 99;
+    *which = i1 < i2 ? i1 : i2;
+    *reason = i1 < i2 ? f1.reason : f2.reason;
+    return true;
+}
+std::string headerFaultMessage(int which, int reason) {
+    return std::string("zkey: header point ") + HEADER_POINT_NAMES[which] + ": " + ug_point_reason_text(reason);
+}
+// at the start of a prover's creation, its contexts just made: switches their creation checks on and checks the header
+void validateOnCreate(ug_ctx* ctx, ug_ctx* ctx2, const ZkeyHeader& h, bool ultra) {
+    const int level = validateLevel();
+    if (!level) return;
+    ugCheck(ug_ctx_check_points(ctx, level));
+    if (ctx2) ugCheck(ug_ctx_check_points(ctx2, level));
+    int which = 0, reason = 0;
+    if (headerPointFault(ctx, h, ultra, level, &which, &reason)) throw ZkeyPointFault(headerFaultMessage(which, reason));
+}
+
 // Work queued on the prover's contexts must not outlive a failing call: the queued MSMs hold pointers into the caller's
 // stack frame and the kernels read the leased witness buffer. Armed while a call has work in flight; on unwind it waits
 // for the device and drops what was queued (ug_ctx_abandon), before the witness lease and the turn are given back.
@@ -888,6 +953,7 @@ private:
             if (v >= 1 && v < MAX_RANGE) maxRange_ = v;
         }
         cLo_ = cLo; cHi_ = cHi;
+        validateOnCreate(d_.ctx, d_.ctx2, hdr_, false);          // ULTRAGROTH_VALIDATE (nothing when unset)
         // Window tables are decided ahead, from the sizes alone, so that every set is created WITH its tables: the table
         // kernel of one section runs while the next section is uploaded (zkey ingest: the 0.25 s of copies disappear
         // behind the 2.4 s of table building at 2^24).
@@ -918,28 +984,37 @@ private:
             ugCheck(ug_ctx_defer_tables(d_.ctx, 1));
             ugCheck(ug_ctx_defer_tables(d_.ctx2, 1));
         } else bgTables_ = false;
-        auto create = [&](ug_ctx* ctx, bool g2, const uint8_t* pts, uint64_t n, uint64_t first, int width, int stride, ug_bases** out) {
+        // (section: the zkey section the records are a slice of, from its point `first` on -- or, compacted, the points support[j])
+        auto create = [&](ug_ctx* ctx, bool g2, const uint8_t* pts, uint64_t n, uint64_t first, int width, int stride, ug_bases** out,
+                          int section, const uint32_t* support = nullptr) {
+            const PointOrigin from = {section, first, first, support};
             if (width && withTables) {
                 int rc = g2 ? ug_bases_create_tables_strided_g2(ctx, pts, n, first, width, stride, out)
                             : ug_bases_create_tables_strided_g1(ctx, pts, n, first, width, stride, out);
                 if (rc == UG_OK) return;
+                throwIfPointFault(ctx, rc, &from);       // (a bad point is no reason to try again)
                 withTables = false;                 // memory ran short after all: this set and the rest without tables
             }
-            ugCheck(g2 ? ug_bases_create_g2(ctx, pts, n, first, out) : ug_bases_create_g1(ctx, pts, n, first, out));
+            ugCheckPoints(ctx, g2 ? ug_bases_create_g2(ctx, pts, n, first, out) : ug_bases_create_g1(ctx, pts, n, first, out), from);
         };
+        const uint64_t cFirst = cLo + hdr_.nPublic + 1;          // the scalar of this rank's first C point
+        const PointOrigin fromA = {5, wr_.lo, wr_.lo, nullptr}, fromB1 = {6, wr_.lo, wr_.lo, nullptr}, fromCg = {8, cLo, cFirst, nullptr};
         traceStep("create: contexts made, point sets next");
         if (groupG1_ && sparseB_) {
             // [A | C]; B1 and B2 as compacted sets over the signals that have a real B point
             const void* hosts[2] = {pA, pC};
-            const uint64_t counts[2] = {nw, cHi - cLo}, firsts[2] = {wr_.lo, cLo + hdr_.nPublic + 1};
+            const uint64_t counts[2] = {nw, cHi - cLo}, firsts[2] = {wr_.lo, cFirst};
+            const PointOrigin from[2] = {fromA, fromCg};
             int rc = UG_ERROR;
-            if (ahead[0]) rc = ug_bases_create_group_strided_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G);
+            if (ahead[0]) { rc = ug_bases_create_group_strided_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G); throwIfPointFault(d_.ctx, rc, from, 2); }
             if (rc != UG_OK) {
                 if (ahead[0]) withTables = false;
-                ugCheck(ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G));
+                rc = ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G);
+                throwIfPointFault(d_.ctx, rc, from, 2);
+                ugCheck(rc);
             }
-            create(d_.ctx, false, b1c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc1);
-            create(d_.ctx, true, b2c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc2);
+            create(d_.ctx, false, b1c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc1, 6, bSupport.data());
+            create(d_.ctx, true, b2c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc2, 7, bSupport.data());
             ugCheck(ug_index_create(d_.ctx, bSupport.data(), nB_, &d_.bIdx));
             ugCheck(ug_dvec_create(d_.ctx, nB_, &d_.wB));
             ugCheck(ug_schedule_create(d_.ctx, &d_.sB));
@@ -947,23 +1022,26 @@ private:
         } else if (groupG1_) {
             // A, B1 and C (with its index shift folded into the slot numbers) as one interleaved group
             const void* hosts[3] = {pA, pB1, pC};
-            const uint64_t counts[3] = {nw, nw, cHi - cLo}, firsts[3] = {wr_.lo, wr_.lo, cLo + hdr_.nPublic + 1};
+            const uint64_t counts[3] = {nw, nw, cHi - cLo}, firsts[3] = {wr_.lo, wr_.lo, cFirst};
+            const PointOrigin from[3] = {fromA, fromB1, fromCg};
             int rc = UG_ERROR;
-            if (ahead[0]) rc = ug_bases_create_group_strided_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G);
+            if (ahead[0]) { rc = ug_bases_create_group_strided_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G); throwIfPointFault(d_.ctx, rc, from, 3); }
             if (rc != UG_OK) {
                 if (ahead[0]) withTables = false;           // memory ran short after all
-                ugCheck(ug_bases_create_group_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G));
+                rc = ug_bases_create_group_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G);
+                throwIfPointFault(d_.ctx, rc, from, 3);
+                ugCheck(rc);
             }
         } else {
-            create(d_.ctx, false, pA, nw, wr_.lo, ahead[0], aheadS[0], &d_.A);
-            create(d_.ctx, false, pB1, nw, wr_.lo, ahead[0], aheadS[0], &d_.B1);
+            create(d_.ctx, false, pA, nw, wr_.lo, ahead[0], aheadS[0], &d_.A, 5);
+            create(d_.ctx, false, pB1, nw, wr_.lo, ahead[0], aheadS[0], &d_.B1, 6);
         }
         traceStep("create: G1 sets of the witness uploaded");
-        if (!sparseB_) create(d_.ctx, true, pB2, nw, wr_.lo, ahead[0], aheadS[0], &d_.B2);
+        if (!sparseB_) create(d_.ctx, true, pB2, nw, wr_.lo, ahead[0], aheadS[0], &d_.B2, 7);
         traceStep("create: B2 uploaded");
-        if (!d_.G) create(d_.ctx, false, pC, cHi - cLo, cLo, ahead[0], aheadS[0], &d_.C);
+        if (!d_.G) create(d_.ctx, false, pC, cHi - cLo, cLo, ahead[0], aheadS[0], &d_.C, 8);
         const bool group0 = withTables && ahead[0];
-        create(d_.ctx2, false, pH, nh, hr_.lo, ahead[1], aheadS[1], &d_.H);
+        create(d_.ctx2, false, pH, nh, hr_.lo, ahead[1], aheadS[1], &d_.H, 9);
         traceStep("create: H uploaded");
         const bool group1 = withTables && ahead[1];
         const bool group2 = sparseB_ && withTables && ahead[2];
@@ -1863,15 +1941,18 @@ private:
         // many-GPU prover drives it beside its queued witness products (witnessMsmBegin), and ULTRAGROTH_OVERLAP=1 lets it run
         // beside them on one GPU as well; by default the second stream is ordered behind the first on the device
         ugCheck(ug_ctx_create(&d_.ctx2, device));
+        validateOnCreate(d_.ctx, d_.ctx2, hdr_, true);           // ULTRAGROTH_VALIDATE (nothing when unset)
+        const PointOrigin fromA = {5, wr_.lo, wr_.lo, nullptr}, fromB1 = {6, wr_.lo, wr_.lo, nullptr}, fromB2 = {7, wr_.lo, wr_.lo, nullptr};
         {   // SPARSE B (DeviceProver, sparseBSupport): as for Groth16 -- B1 and B2 compacted over the signals with a real B point
             std::vector<uint32_t> bSupport;
             std::vector<uint8_t> b1c, b2c;
             sparseB_ = count == 1 && !src.sliced && sparseBSupport(pB1, pB2, wr_.hi - wr_.lo, bSupport, b1c, b2c);
             nB_ = sparseB_ ? bSupport.size() : 0;
             if (sparseB_) {
-                ugCheck(ug_bases_create_g1(d_.ctx, pA, wr_.hi - wr_.lo, wr_.lo, &d_.A));
-                ugCheck(ug_bases_create_g1(d_.ctx, b1c.data(), nB_, 0, &d_.Bc1));
-                ugCheck(ug_bases_create_g2(d_.ctx, b2c.data(), nB_, 0, &d_.Bc2));
+                const PointOrigin fromBc1 = {6, 0, 0, bSupport.data()}, fromBc2 = {7, 0, 0, bSupport.data()};      // (one rank: signal numbers)
+                ugCheckPoints(d_.ctx, ug_bases_create_g1(d_.ctx, pA, wr_.hi - wr_.lo, wr_.lo, &d_.A), fromA);
+                ugCheckPoints(d_.ctx, ug_bases_create_g1(d_.ctx, b1c.data(), nB_, 0, &d_.Bc1), fromBc1);
+                ugCheckPoints(d_.ctx, ug_bases_create_g2(d_.ctx, b2c.data(), nB_, 0, &d_.Bc2), fromBc2);
                 ugCheck(ug_index_create(d_.ctx, bSupport.data(), nB_, &d_.bIdx));
                 ugCheck(ug_dvec_create(d_.ctx, nB_, &d_.wB));
                 ugCheck(ug_schedule_create(d_.ctx, &d_.sB));
@@ -1881,17 +1962,20 @@ private:
         } else if (fusedGroups()) {                     // A and B1 share the witness scalars: one interleaved group
             const void* hosts[2] = {pA, pB1};
             const uint64_t counts[2] = {wr_.hi - wr_.lo, wr_.hi - wr_.lo}, firsts[2] = {wr_.lo, wr_.lo};
-            ugCheck(ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, wr_.hi - wr_.lo, 0, &d_.G));
+            const PointOrigin from[2] = {fromA, fromB1};
+            const int rc = ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, wr_.hi - wr_.lo, 0, &d_.G);
+            throwIfPointFault(d_.ctx, rc, from, 2);
+            ugCheck(rc);
         } else {
-            ugCheck(ug_bases_create_g1(d_.ctx, pA, wr_.hi - wr_.lo, wr_.lo, &d_.A));
-            ugCheck(ug_bases_create_g1(d_.ctx, pB1, wr_.hi - wr_.lo, wr_.lo, &d_.B1));
+            ugCheckPoints(d_.ctx, ug_bases_create_g1(d_.ctx, pA, wr_.hi - wr_.lo, wr_.lo, &d_.A), fromA);
+            ugCheckPoints(d_.ctx, ug_bases_create_g1(d_.ctx, pB1, wr_.hi - wr_.lo, wr_.lo, &d_.B1), fromB1);
         }
-        if (!sparseB_) ugCheck(ug_bases_create_g2(d_.ctx, pB2, wr_.hi - wr_.lo, wr_.lo, &d_.B2));
+        if (!sparseB_) ugCheckPoints(d_.ctx, ug_bases_create_g2(d_.ctx, pB2, wr_.hi - wr_.lo, wr_.lo, &d_.B2), fromB2);
         // the round / final sets are multiplied with GATHERED scalars (position k of the slice's index list), so their
         // slices count from 0
-        ugCheck(ug_bases_create_g1(d_.ctx, pFinalC, c2.hi - c2.lo, 0, &d_.C));
-        ugCheck(ug_bases_create_g1(d_.ctx, pRoundC, c1.hi - c1.lo, 0, &d_.roundC));
-        ugCheck(ug_bases_create_g1(d_.ctx2, pH, hr_.hi - hr_.lo, hr_.lo, &d_.H));
+        ugCheckPoints(d_.ctx, ug_bases_create_g1(d_.ctx, pFinalC, c2.hi - c2.lo, 0, &d_.C), PointOrigin{9, c2.lo, 0, nullptr});
+        ugCheckPoints(d_.ctx, ug_bases_create_g1(d_.ctx, pRoundC, c1.hi - c1.lo, 0, &d_.roundC), PointOrigin{8, c1.lo, 0, nullptr});
+        ugCheckPoints(d_.ctx2, ug_bases_create_g1(d_.ctx2, pH, hr_.hi - hr_.lo, hr_.lo, &d_.H), PointOrigin{12, hr_.lo, hr_.lo, nullptr});
         if (haveHpoly_ && !d_.hp) ugCheck(ug_hpoly_create(d_.ctx2, coefs, hdr_.nCoefs, hdr_.domainSize, hdr_.nVars, &d_.hp));
         ugCheck(ug_dvec_create(d_.ctx, M, &d_.w));
         wCur_ = d_.w;
@@ -3498,6 +3582,48 @@ int ultra_groth_prover_zkey_file(const char* zkey_file_path, const void* wtns_bu
 
 // ---- additions ----------------------------------------------------------------------------------------------
 int ug_test_set_blinding(const void* bytes, unsigned long long n) { return setRandomOverride(bytes, (size_t)n) ? PROVER_OK : PROVER_ERROR; }
+
+// The standalone check: no prover, nothing resident. Header first, then the point sections in ascending order, each streamed
+// through the bounded device buffer of ug_points_check. Section 3 (IC), which no prover uploads, is checked too.
+int ug_zkey_check(const void* zkey_buffer, unsigned long long zkey_size, int device, int level, ug_zkey_fault* fault, char* error_msg,
+                  unsigned long long error_msg_maxsize) {
+    if (fault) { fault->section = 0; fault->index = 0; fault->reason = UG_POINT_OK; }
+    API_TRY
+    if (zkey_buffer == NULL) throw std::invalid_argument("Null zkey buffer");
+    if (level != 1 && level != 2) throw std::invalid_argument("check level must be 1 or 2");
+    BinFile f(zkey_buffer, zkey_size, "zkey", 1);
+    if (f.sectionSize(1) < 4) throw std::invalid_argument("zkey: section 1 is too short");
+    uint32_t protocol = 0;
+    memcpy(&protocol, f.sectionData(1), 4);
+    const bool ultra = protocol == 1337;
+    const ZkeyHeader h = loadZkeyHeader(f, ultra);
+    if (!h.rIsBn254) throw std::invalid_argument("zkey curve not supported");
+    if (h.nVars < h.nPublic + 1) throw std::invalid_argument("zkey header: nVars smaller than nPublic + 1");
+    const uint64_t M = h.nVars, N = h.domainSize;
+    struct Sec { int id; int g2; uint64_t n; };
+    // (section 3 is no prover's business, so no loader says how long it must be: every whole record it holds is checked)
+    std::vector<Sec> secs = {{5, 0, M}, {6, 0, M}, {7, 1, M}};
+    if (f.hasSection(3)) secs.insert(secs.begin(), {3, 0, f.sectionSize(3) / 64});      // (provers never read it: a key without it is a key)
+    if (ultra) { secs.push_back({8, 0, h.numIndexesC1}); secs.push_back({9, 0, h.numIndexesC2}); secs.push_back({12, 0, N}); }
+    else { secs.push_back({8, 0, M - h.nPublic - 1}); secs.push_back({9, 0, N}); }
+    std::vector<const uint8_t*> data;
+    for (const Sec& sc : secs) data.push_back(checkedSection(f, (uint32_t)sc.id, sc.n * (sc.g2 ? 128 : 64)));      // every size before any device work
+    struct Ctx { ug_ctx* c = nullptr; ~Ctx() { ug_ctx_destroy(c); } } ctx;
+    ugCheck(ug_ctx_create(&ctx.c, device));
+    int which = 0, reason = 0;
+    if (headerPointFault(ctx.c, h, ultra, level, &which, &reason)) {
+        if (fault) { fault->section = 2; fault->index = (unsigned long long)which; fault->reason = reason; }
+        throw ZkeyPointFault(headerFaultMessage(which, reason));
+    }
+    for (size_t k = 0; k < secs.size(); k++) {
+        ug_point_fault pf;
+        ugCheck(ug_points_check(ctx.c, secs[k].g2, data[k], secs[k].n, level, &pf));
+        if (pf.reason == UG_POINT_OK) continue;
+        if (fault) { fault->section = secs[k].id; fault->index = pf.index; fault->reason = pf.reason; }
+        throw ZkeyPointFault("zkey: section " + std::to_string(secs[k].id) + " point " + std::to_string(pf.index) + ": " + ug_point_reason_text(pf.reason));
+    }
+    API_CATCH
+}
 
 int ug_registry_create(void** registry, int device, unsigned long long hbm_budget_bytes, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY

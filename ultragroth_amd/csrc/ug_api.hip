@@ -134,6 +134,11 @@ struct ug_ctx {
     hipEvent_t side_fork = nullptr, side_join = nullptr;
     bool defer_tables = false;             // ug_ctx_defer_tables: sets are created with room for their window tables, which are
                                            // then built piece by piece (ug_bases_tables_step)
+    int check_level = 0;                   // ug_ctx_check_points: the sets created on this context check their records (check.hip)
+    unsigned long long* check_word = nullptr;   // ... the fault word of the check in flight (device memory) and the stream it is
+    hipStream_t check_stream = nullptr;         //     armed and read on: the context's own may hold the previous set's table build
+    ug_point_fault last_fault = {0, UG_POINT_OK};   // what the last creation on this context found (ug_ctx_last_point_fault) ...
+    int last_fault_member = -1;                      // ... and in which member of a group (-1: a plain set)
     ug_graph* recording = nullptr;         // the stream is being captured into this graph (ug_graph_begin .. ug_graph_end)
     std::vector<ug_graph*> launched;       // graphs launched on this stream whose event pairs are not accounted yet (resolve_spans)
     NttPlan raw_ntt;                       // cache for ug_fr_ntt
@@ -222,6 +227,35 @@ void host_to_device(ug_ctx* c, void* dst, const void* src, size_t bytes, const S
     UG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     if (after) after(0, bytes, c->stream);
     UG_HIP(hipStreamSynchronize(c->stream));
+}
+// ---- point validation (check.hip): the fault word of a context ----
+// a creation found a bad point: remembered on the context (the outer layer asks for it instead of reading the message), then thrown
+[[noreturn]] void throw_point_fault(ug_ctx* c, int member, const ug_point_fault& f) {
+    c->last_fault = f; c->last_fault_member = member;
+    throw std::runtime_error((member >= 0 ? "member " + std::to_string(member) + " point " : std::string("point ")) + std::to_string(f.index) + ": " +
+                             ug_point_reason_text(f.reason));
+}
+// all ones = clean; returns when the word is set (the upload lanes' kernels that follow run on other streams)
+void check_arm(ug_ctx* c) {
+    if (!c->check_stream) UG_HIP(hipStreamCreateWithFlags(&c->check_stream, hipStreamNonBlocking));
+    if (!c->check_word) UG_HIP(hipMalloc(&c->check_word, 8));
+    UG_HIP(hipMemsetAsync(c->check_word, 0xff, 8, c->check_stream));
+    UG_HIP(hipStreamSynchronize(c->check_stream));
+}
+// after every kernel that may have written the word has completed
+ug_point_fault check_read(ug_ctx* c) {
+    unsigned long long w = 0;
+    UG_HIP(hipMemcpyAsync(&w, c->check_word, 8, hipMemcpyDeviceToHost, c->check_stream));
+    UG_HIP(hipStreamSynchronize(c->check_stream));
+    ug_point_fault f;
+    f.index = w == ~0ull ? 0 : (uint64_t)(w >> 2);
+    f.reason = w == ~0ull ? UG_POINT_OK : (int)(w & 3);
+    return f;
+}
+void check_release(ug_ctx* c) {
+    if (c->check_word) hipFree(c->check_word);
+    if (c->check_stream) hipStreamDestroy(c->check_stream);
+    c->check_word = nullptr; c->check_stream = nullptr;
 }
 // Test hook (ug_test_inject_fault): the `after`-th next pass through fault point `site` throws. Only in processes started
 // with ULTRAGROTH_TEST_HOOKS=1 (the same gate as the blinding hook); otherwise fault_point() is one relaxed load.
@@ -366,6 +400,7 @@ void ug_ctx_destroy(ug_ctx* c) {
     c->ws_g1.release(); c->ws_g2.release(); c->raw_ntt.release(); c->uploader.release();
     if (c->lookup_last) hipFree(c->lookup_last);
     if (c->lookup_stage) hipFree(c->lookup_stage);
+    check_release(c);
     for (auto& sp : c->spans_free) { hipEventDestroy(sp.e0); hipEventDestroy(sp.e1); }
     for (auto& sp : c->spans_pending) { hipEventDestroy(sp.e0); hipEventDestroy(sp.e1); }
     if (c->order_event) hipEventDestroy(c->order_event);
@@ -412,6 +447,7 @@ static int bases_create(ug_ctx* c, const void* host, u64 n, u64 global_first, bo
     UG_TRY
     if (!c || !out || (!host && n)) throw std::invalid_argument("null argument");
     c->use();
+    c->last_fault = {0, UG_POINT_OK}; c->last_fault_member = -1;
     int windows = 1;                                          // (the number of tables: ceil(W / stride))
     if (table_c) {
         windows = MsmGeometry::table_count(table_c, MsmGeometry::choose_tables(n, table_c, stride).stride);      // validates width and stride
@@ -431,10 +467,18 @@ static int bases_create(ug_ctx* c, const void* host, u64 n, u64 global_first, bo
         // each chunk's records are converted to the device form behind its own DMA (chunks are whole records: 8 MiB / 128)
         u32* pts = b->pts;
         try {
-            host_to_device(c, pts, host, bytes, [pts, rec, g2](size_t off, size_t len, hipStream_t st) {
+            const int level = c->check_level;                  // (0: exactly the path without the check)
+            unsigned long long* word = nullptr;
+            if (level) { check_arm(c); word = c->check_word; }
+            host_to_device(c, pts, host, bytes, [pts, rec, g2, level, word, global_first](size_t off, size_t len, hipStream_t st) {
                 u32* p = pts + off / 4;
+                if (level) check_points(g2, p, len / rec, global_first + off / rec, level, word, st);      // the raw records, before they are reduced
                 if (g2) convert_points_g2(p, len / rec, st); else convert_points_g1(p, len / rec, st);
             }, /*fresh*/ true);
+            if (level) {                                       // (the upload has waited for every chunk: one read, and no table build for a bad set)
+                const ug_point_fault f = check_read(c);
+                if (f.reason != UG_POINT_OK) throw_point_fault(c, -1, f);
+            }
             if (table_c && !defer) build_window_tables(g2, pts, n, table_c * stride, windows, c->stream);
         } catch (...) { hipFree(b->pts); delete b; throw; }
     }
@@ -462,6 +506,7 @@ int ug_bases_create_group_strided_g1(ug_ctx* c, int members, const void* const* 
                                      uint64_t group_first, uint64_t slots, int table_c, int stride, ug_bases** out) {
     UG_TRY
     if (!c || !out || !host || !n || !first) throw std::invalid_argument("null argument");
+    c->last_fault = {0, UG_POINT_OK}; c->last_fault_member = -1;
     if (members < 2 || members > 3) throw std::invalid_argument("a base group has 2 or 3 members");
     for (int m = 0; m < members; m++) {
         if (!host[m] && n[m]) throw std::invalid_argument("null argument");
@@ -494,15 +539,23 @@ int ug_bases_create_group_strided_g1(ug_ctx* c, int members, const void* const* 
         }
         trace_step("group: table 0 cleared");
         u32* pts = b->pts;
+        const int level = c->check_level;
         for (int m = 0; m < members; m++) {
             trace_step("group: member upload");
             // chunks of whole records: converted to the device form and moved to their slots behind their own DMA
             if (!n[m]) continue;
-            const u64 slot0 = first[m] - group_first;
+            const u64 slot0 = first[m] - group_first, first_m = first[m];
+            unsigned long long* word = nullptr;
+            if (level) { check_arm(c); word = c->check_word; }
             host_to_device(c, stage, host[m], (size_t)n[m] * 64, [=](size_t off, size_t len, hipStream_t st) {
+                if (level) check_points(false, stage + off / 4, len / 64, first_m + off / 64, level, word, st);
                 convert_points_g1(stage + off / 4, len / 64, st);
                 interleave_points_g1(pts, stage + off / 4, len / 64, members, m, slot0 + off / 64, st);
             }, /*fresh*/ true);
+            if (level) {                                       // per member (its upload has waited for every chunk), so that the member can be named
+                const ug_point_fault f = check_read(c);
+                if (f.reason != UG_POINT_OK) throw_point_fault(c, m, f);
+            }
         }
         if (table_c && b->n && !defer) build_window_tables(false, pts, b->n, table_c * stride, windows, c->stream);
     } catch (...) { hipFree(stage); hipFree(b->pts); delete b; throw; }
@@ -517,6 +570,56 @@ int ug_bases_create_group_g1(ug_ctx* c, int members, const void* const* host, co
     return ug_bases_create_group_strided_g1(c, members, host, n, first, group_first, slots, table_c, 1, out);
 }
 int ug_bases_members(const ug_bases* b) { return b ? b->members : 0; }
+
+// POINT VALIDATION (check.hip). The records go through a bounded device buffer, piece by piece, each piece staged as an upload is
+// (the check kernel of a chunk queued behind its DMA); the fault word is read once, after the last piece.
+int ug_points_check(ug_ctx* c, int g2, const void* host_points, uint64_t n, int level, ug_point_fault* out) {
+    UG_TRY
+    if (!c || !out || (!host_points && n)) throw std::invalid_argument("null argument");
+    if (level != 1 && level != 2) throw std::invalid_argument("check level must be 1 or 2");
+    c->use();
+    out->index = 0; out->reason = UG_POINT_OK;
+    if (!n) return UG_OK;
+    const size_t rec = g2 ? 128 : 64;
+    const u64 piece = ((u64)64 << 20) / rec;                   // 64 MiB of records at a time
+    u32* buf = nullptr;
+    if (hipMalloc(&buf, (size_t)(n < piece ? n : piece) * rec) != hipSuccess) { (void)hipGetLastError(); throw std::runtime_error("not enough device memory for the point check"); }
+    try {
+        check_arm(c);
+        unsigned long long* word = c->check_word;
+        const bool is_g2 = g2 != 0;
+        for (u64 done = 0; done < n; done += piece) {
+            const u64 m = n - done < piece ? n - done : piece;
+            host_to_device(c, buf, static_cast<const uint8_t*>(host_points) + done * rec, (size_t)m * rec,
+                           [=](size_t off, size_t len, hipStream_t st) { check_points(is_g2, buf + off / 4, len / rec, done + off / rec, level, word, st); },
+                           /*fresh*/ true);      // (buf is this call's own, and every upload returns with its kernels done)
+        }
+        *out = check_read(c);
+    } catch (...) { hipFree(buf); if (!c->check_level) check_release(c); throw; }
+    hipFree(buf);
+    if (!c->check_level) check_release(c);                     // nothing stays resident
+    UG_CATCH
+}
+const char* ug_point_reason_text(int reason) {
+    return reason == UG_POINT_UNREDUCED ? "coordinate not below the field modulus"
+         : reason == UG_POINT_OFF_CURVE ? "not on the curve"
+         : reason == UG_POINT_OFF_SUBGROUP ? "not in the subgroup of order r" : "";
+}
+int ug_ctx_last_point_fault(const ug_ctx* c, int* member, ug_point_fault* out) {
+    if (!c || !out) return fail("null argument");
+    *out = c->last_fault;
+    if (member) *member = c->last_fault_member;
+    return UG_OK;
+}
+int ug_ctx_check_points(ug_ctx* c, int level) {
+    UG_TRY
+    if (!c) throw std::invalid_argument("null argument");
+    if (level < 0 || level > 2) throw std::invalid_argument("check level must be 0, 1 or 2");
+    c->use();
+    c->check_level = level;
+    if (level) check_arm(c); else check_release(c);            // (the word is the context's from here on: a failing creation leaves no trace)
+    UG_CATCH
+}
 int ug_points_all_infinity(const void* host_points, uint64_t n, uint64_t record_bytes) {
     return (host_points && n) ? (host_all_zero(host_points, (size_t)n * (size_t)record_bytes) ? 1 : 0) : 0;
 }
