@@ -303,6 +303,9 @@ constexpr uint32_t SHARD_SPECIALS = 16;      // digits 1 .. 16 of every window a
 // 2 x 16 + 1 points per result block), 128 at most
 inline int shardQLog(int B) { int q = 4; while (q < 7 && (1 << q) < 16 * B) q++; return q; }
 
+// the window tables of one schedule group (TableGroup below): width (0: classic windows) and stride (1 unless the plan is strided)
+struct TableChoice { int c = 0, stride = 1; };
+
 // ---- common device-side state of a prover -------------------------------------------------------------------
 struct DeviceProver {
     ug_ctx* ctx = nullptr;
@@ -319,8 +322,7 @@ struct DeviceProver {
     ug_index* bIdx = nullptr;
     ug_dvec* wB = nullptr;
     ug_schedule* sB = nullptr;
-    int tableB = 0;              // window width of the compacted sets' tables (0: classic windows)
-    int strideB = 1;             // ... and their stride
+    TableChoice planB;           // the tables of the compacted sets
     ug_hpoly* hp = nullptr;
     ug_dvec *w = nullptr, *h = nullptr, *aux = nullptr;
     ug_dvec* w2 = nullptr;       // second witness buffer (Groth16): the next proof's witness is staged here while a proof runs
@@ -406,6 +408,49 @@ struct WitnessLease {
     StagedWitness& operator*() { return b[slot]; }
 };
 
+// ---- the buffers of a batched call (proveBatch): the vectors of V witnesses side by side ------------------------------
+// Sized by the pass (ensure, under the prover's turn: no allocation while kernels of a proof are queued), kept between the
+// calls, given back by trimWorkspaces. The ones a prover does not need stay null.
+struct BatchBuffers {
+    ug_dvec *w = nullptr, *h = nullptr;      // V signal vectors / h vectors
+    ug_dvec* aux = nullptr;                  // UltraGroth: V vectors of gathered round or final scalars
+    ug_dvec* wB = nullptr;                   // sparse B: V vectors of gathered B scalars
+    std::mutex mutex;                        // one batch call at a time owns them (lock order: this -> witness lease -> proveMutex)
+    ~BatchBuffers() { release(); }           // (a prover declares its BatchBuffers after its DeviceProver: they go before the contexts)
+    // a buffer of at least n elements (a smaller one is replaced)
+    static void ensure(ug_dvec*& v, ug_ctx* ctx, uint64_t n) {
+        if (v && ug_dvec_size(v) >= n) return;
+        ug_dvec_destroy(v); v = nullptr;
+        ugCheck(ug_dvec_create(ctx, n, &v));
+    }
+    void release() { for (ug_dvec** v : {&w, &h, &aux, &wB}) { ug_dvec_destroy(*v); *v = nullptr; } }
+    uint64_t bytesHeld() const {
+        uint64_t b = 0;
+        for (const ug_dvec* v : {w, h, aux, wB}) if (v) b += ug_dvec_size(v) * 32;
+        return b;
+    }
+    // views of parts of a vector, destroyed on scope exit (what was queued on a view keeps the address, not the view)
+    struct DeviceViews {
+        std::vector<ug_dvec*> made;
+        DeviceViews() = default;
+        DeviceViews(const DeviceViews&) = delete;
+        DeviceViews& operator=(const DeviceViews&) = delete;
+        ~DeviceViews() { for (ug_dvec* x : made) ug_dvec_destroy(x); }
+        ug_dvec* view(ug_ctx* ctx, const ug_dvec* of, uint64_t first, uint64_t n) {
+            made.push_back(nullptr);
+            ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(of) + first * 32, n, &made.back()));
+            return made.back();
+        }
+    };
+    // V signal vectors of nVars elements into w, on the uploader's own streams. The caller holds `mutex` and no turn: the last
+    // pass that read w has been collected. The uploader is the context's, so the copies take the stage mutex as a single proof's.
+    void stage(ug_ctx* ctx, std::mutex& stageMutex, const uint8_t* const* signals, int V, uint64_t nVars) {
+        std::lock_guard<std::mutex> st(stageMutex);
+        DeviceViews views;
+        for (int v = 0; v < V; v++) ugCheck(ug_dvec_upload_idle(views.view(ctx, w, (uint64_t)v * nVars, nVars), signals[v], nVars));
+    }
+};
+
 // ---- fixed-base window tables ---------------------------------------------------------------------------------
 // A zkey's points never change between proofs, so a created prover may trade HBM for work: with tables 2^(c j) P_i
 // every window digit of an MSM lands in one bucket set (ultragroth_hip.h: ug_bases_precompute). A group is the base
@@ -419,10 +464,8 @@ struct TableGroup {
     std::vector<ug_bases*> g1, g2;     // sets of the group with their point counts
     std::vector<uint64_t> n1, n2;
     uint64_t scalars = 0;              // scalars per schedule
-    int* c = nullptr;                  // out: window width, 0 = classic
-    int* stride = nullptr;             // out: table stride (1 unless the plan is strided)
+    TableChoice* plan = nullptr;       // out: the prover's choice for the group (the stride is set with the plan, the width once the tables are in use)
 };
-struct TableChoice { int c = 0, stride = 1; };
 constexpr uint64_t TABLES_MIN_SCALARS = (uint64_t)1 << 14, TABLES_MAX_SCALARS = (uint64_t)1 << 26;
 
 thread_local bool g_oneShotProver = false;      // create + one prove + destroy (groth16_prover, the CLIs): tables cannot pay
@@ -430,7 +473,9 @@ thread_local bool g_oneShotProver = false;      // create + one prove + destroy 
 thread_local bool g_registryCreate = false;     // the resident multi-circuit prover decides about tables itself, after create
 
 thread_local bool g_deferTables = false;        // set around groth16_prover_create's constructor call: the one prover that may hand out
-                                                // proofs before its window tables exist (every caller of it goes through proveTurn)
+                                                // proofs before its window tables exist. Its prove calls go through proveTurn and share
+                                                // the turn with the table builder; the phase calls (run, witnessMsmBegin, hpolyChain, ...)
+                                                // take no turn, so a phase caller has to wait for tablesReady first
 
 // what the tables of all groups would take (0: no group qualifies) and the schedule workspace they imply
 uint64_t tablesNeed(const std::vector<TableGroup>& groups, std::vector<int>& width, uint64_t* workspaceOut) {
@@ -498,7 +543,7 @@ void tracePlan(const std::vector<TableGroup>& groups, const std::vector<TableCho
 // (bytes the caller is ready to spend, ~0 = no limit of its own); returns the bytes taken (0: classic windows stay).
 // strided: the created prover's plan (ug_plan_window_tables within min(free - workspace, ULTRAGROTH_TABLES_BUDGET, limit))
 uint64_t planWindowTables(ug_ctx* ctx, std::vector<TableGroup>& groups, uint64_t limit = ~(uint64_t)0, bool force = false, bool strided = false) {
-    for (auto& g : groups) { *g.c = 0; if (g.stride) *g.stride = 1; }
+    for (auto& g : groups) *g.plan = TableChoice();
     const char* e = getenv("ULTRAGROTH_TABLES");
     if (e && e[0] == '0') return 0;
     if (!force && (g_registryCreate || (g_oneShotProver && !(e && e[0] == '2')))) return 0;     // "2": tables even for one-shot calls
@@ -527,8 +572,7 @@ uint64_t planWindowTables(ug_ctx* ctx, std::vector<TableGroup>& groups, uint64_t
         for (ug_bases* b : groups[k].g1) ok = ok && ug_bases_precompute_strided(b, c, st) == 0;
         for (ug_bases* b : groups[k].g2) ok = ok && ug_bases_precompute_strided(b, c, st) == 0;
         if (ok) {
-            *groups[k].c = c;
-            if (groups[k].stride) *groups[k].stride = st;
+            *groups[k].plan = plan[k];
             for (uint64_t n : groups[k].n1) taken += ug_bases_tables_bytes_strided(n, 0, c, st);
             for (uint64_t n : groups[k].n2) taken += ug_bases_tables_bytes_strided(n, 1, c, st);
         } else {                               // a group left half built gives its memory back and keeps the classic windows
@@ -592,17 +636,13 @@ void enqueueWitnessProducts(DeviceProver& d, ug_ctx* ctx, const ug_schedule* sw,
         }
         if (vectors > 1) {
             const uint64_t nB = ug_dvec_size(d.wB);
-            for (int v = 0; v < vectors; v++) {
-                ug_dvec* wv = nullptr;            // (a view: the queued gather keeps the address, not the view)
-                ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(witness) + (uint64_t)v * witnessStride * 32, witnessStride, &wv));
-                const int rc = ug_dvec_gather_index_at(wBBatch, (uint64_t)v * nB, wv, d.bIdx);
-                ug_dvec_destroy(wv);
-                ugCheck(rc);
-            }
-            ugCheck(ug_schedule_build_vectors(d.sB, wBBatch, 0, nB, vectors, nB, d.tableB, d.strideB));
+            BatchBuffers::DeviceViews views;
+            for (int v = 0; v < vectors; v++)
+                ugCheck(ug_dvec_gather_index_at(wBBatch, (uint64_t)v * nB, views.view(ctx, witness, (uint64_t)v * witnessStride, witnessStride), d.bIdx));
+            ugCheck(ug_schedule_build_vectors(d.sB, wBBatch, 0, nB, vectors, nB, d.planB.c, d.planB.stride));
         } else {
             ugCheck(ug_dvec_gather_index(d.wB, witness, d.bIdx));
-            buildSchedule(d.sB, d.wB, 0, ug_dvec_size(d.wB), d.tableB, d.strideB);
+            buildSchedule(d.sB, d.wB, 0, ug_dvec_size(d.wB), d.planB.c, d.planB.stride);
         }
         const ug_bases* sets[2] = {d.Bc1, d.Bc2};
         void* outsB[2] = {outB1, outB2};
@@ -689,6 +729,17 @@ bool sparseBSupport(const uint8_t* pB1, const uint8_t* pB2, uint64_t n, std::vec
     return true;
 }
 
+// fn() for witness b of a batched call: what it throws names the witness ("witness <b>: ..."). A wrong witness length keeps its
+// type, a short output buffer passes as it is (its message names the witness already), everything else becomes a runtime_error.
+template <class Fn>
+void atWitness(int b, Fn&& fn) {
+    const std::string at = "witness " + std::to_string(b) + ": ";
+    try { fn(); }
+    catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
+    catch (ShortBufferException&) { throw; }
+    catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
+}
+
 struct ProverBase {        // what the extern "C" layer stores behind the opaque handle
     std::mutex proveMutex;
     virtual ~ProverBase() {}
@@ -716,14 +767,7 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
     virtual void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
                             std::vector<std::string>& pubs) {
         proofs.assign(k, std::string()); pubs.assign(k, std::string());
-        for (int b = 0; b < k; b++) {
-            const std::string at = "witness " + std::to_string(b) + ": ";
-            try {
-                proveTurn(wtns[b], sizes[b], proofs[b], pubs[b]);
-            } catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
-            catch (ShortBufferException&) { throw; }
-            catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
-        }
+        for (int b = 0; b < k; b++) atWitness(b, [&] { proveTurn(wtns[b], sizes[b], proofs[b], pubs[b]); });
     }
     virtual unsigned long long proofBufferMinSize() const = 0;
     virtual unsigned long long publicBufferMinSize() const = 0;
@@ -742,14 +786,32 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
         std::vector<TableGroup> g = tableGroups();
         if (group < 0 || group >= (int)g.size()) return false;
         const int pending = pendingWidth(group);
-        const int inUse = *g[group].c;
+        const int inUse = g[group].plan->c;
         const int w = inUse ? inUse : pending;
-        const int st = w ? (g[group].stride ? *g[group].stride : 1) : 0;
+        const int st = w ? g[group].plan->stride : 0;
         uint64_t b = 0;
         for (uint64_t n : g[group].n1) b += ug_bases_tables_bytes_strided(n, 0, w, st);
         for (uint64_t n : g[group].n2) b += ug_bases_tables_bytes_strided(n, 1, w, st);
         *c = w; *stride = st; *bytes = w ? b : 0; *ready = (!w || inUse) ? 1 : 0;
         return true;
+    }
+    // what the window tables that are planned but not in use yet will take: a batch that lands before them must leave them their
+    // room (their allocation would fail and the prover stay on classic windows)
+    uint64_t pendingTableBytes() {
+        uint64_t pending = 0;
+        const int groups = (int)tableGroups().size();
+        for (int g = 0; g < groups; g++) {
+            int c = 0, st = 0, ready = 1;
+            uint64_t bytes = 0;
+            if (tablePlan(g, &c, &st, &bytes, &ready) && !ready) pending += bytes;
+        }
+        return pending;
+    }
+    // the schedules of a device pass for ug_plan_proof_batch, one per group in the groups' order, with their current table plan
+    std::vector<ug_batch_schedule> batchSchedules() {
+        std::vector<ug_batch_schedule> sch;
+        for (const TableGroup& g : tableGroups()) sch.push_back(ug_batch_schedule{g.scalars, g.plan->c, g.plan->stride});
+        return sch;
     }
     bool buildTables(uint64_t limit) {
         if (tableBytes) return true;
@@ -765,7 +827,7 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
         for (auto& grp : g) {
             for (ug_bases* b : grp.g1) ug_bases_drop_tables(b);
             for (ug_bases* b : grp.g2) ug_bases_drop_tables(b);
-            *grp.c = 0;
+            grp.plan->c = 0;
         }
         tableBytes = 0;
     }
@@ -800,6 +862,73 @@ const uint8_t* checkedSection(const BinFile& f, uint32_t id, uint64_t needBytes)
     if (f.sectionSize(id) < needBytes)
         throw std::range_error("Section " + std::to_string(id) + " is shorter than the header implies");
     return f.sectionData(id);
+}
+// a header-only zkey container of `protocol` (1: Groth16, 1337: UltraGroth) around a caller's header section, so that the one
+// header parser serves the sliced creates as well
+std::vector<uint8_t> miniZkey(const void* header, unsigned long long headerSize, uint32_t protocol) {
+    std::vector<uint8_t> mini = {'z', 'k', 'e', 'y'};
+    auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) mini.push_back((uint8_t)(v >> (8 * k))); };
+    auto put64 = [&](uint64_t v) { for (int k = 0; k < 8; k++) mini.push_back((uint8_t)(v >> (8 * k))); };
+    put32(1); put32(3);
+    put32(1); put64(4); put32(protocol);
+    put32(2); put64(headerSize);
+    mini.insert(mini.end(), static_cast<const uint8_t*>(header), static_cast<const uint8_t*>(header) + headerSize);
+    put32(4); put64(0);
+    return mini;
+}
+// the n slices of a sliced create: each must hold this rank's range (a short buffer would be read past its end)
+void checkSlices(const char* const* what, const uint64_t* need, const uint8_t* const* ptr, const unsigned long long* sliceBytes, int n) {
+    for (int k = 0; k < n; k++) {
+        if (need[k] && !ptr[k]) throw std::invalid_argument(std::string("Null ") + what[k] + " slice");
+        if (sliceBytes && sliceBytes[k] < need[k])
+            throw std::invalid_argument(std::string(what[k]) + " slice is shorter than this rank's range: " + std::to_string(sliceBytes[k]) +
+                                        " bytes, needed " + std::to_string(need[k]));
+    }
+}
+// the end of both provers' trimWorkspaces (the batch lock and the turn held): the schedules' and contexts' workspaces, the
+// witness buffer that is not the current one, the batch buffers
+void trimDeviceWorkspaces(DeviceProver& d, WitnessBuffers& witness, const ug_dvec* current, BatchBuffers& batch) {
+    for (ug_schedule* s : {d.sw, d.sh, d.saux, d.sB}) if (s) ug_schedule_trim(s);
+    ug_ctx_trim(d.ctx); ug_ctx_trim(d.ctx2);
+    witness.trim(current);
+    batch.release();
+}
+
+// The pass loop of a batched call (proveBatch of Groth16Prover and UltraGrothProver). `c` is the prover's
+// BatchCall: the call's arguments, what parsing kept of every witness, the device times so far. Every witness is parsed and
+// checked first: a bad one fails the call before anything is queued. Then each device pass takes up to perPass witnesses: their
+// vectors are copied into the batch buffers BEFORE the pass takes the prover's turn (as a single proof stages its witness:
+// nothing queued reads the buffers then), so another caller's kernels may run meanwhile; runPass draws the pass's blinding in
+// witness order, starts the host terms and runs the device part; finishPass blinds and serialises outside the turn. A pass of
+// one witness takes the single-proof path.
+template <class P>
+void proveBatchInPasses(P& p, typename P::BatchCall& c, int k) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int b = 0; b < k; b++) atWitness(b, [&] { p.parseForBatch(c, b); });
+    c.proofs.assign((size_t)k, std::string()); c.pubs.assign((size_t)k, std::string());
+    std::lock_guard<std::mutex> batchLock(p.batch_.mutex);         // the batch buffers belong to one batch call at a time
+    for (int b0 = 0; b0 < k;) {
+        int V = 1;
+        {
+            auto turn = p.takeTurn(false);                          // (allocations only under the turn)
+            V = p.perPass(c, k - b0, b0);
+            if (V > 1) p.reserveBatch(V);
+        }
+        if (V <= 1) { p.proveOneOfBatch(c, b0++); continue; }       // the single-proof path
+        p.stagePass(c, b0, V);
+        auto turn = p.takeTurn(true);
+        // the table plan may have changed meanwhile (Groth16Prover's tableBuilder): the rest is staged again. A no-op for
+        // UltraGrothProver, whose tables never change after create.
+        V = std::min(V, p.perPass(c, V, b0));
+        if (V <= 1) continue;
+        auto pass = p.runPass(c, b0, V);
+        turn.unlock();
+        p.finishPass(c, b0, V, pass);
+        b0 += V;
+    }
+    // the call's figures for ug_prover_last_timings, written under the turn as every proof writes them
+    auto turn = p.takeTurn(false);
+    p.setBatchTimings(c.msm, c.fft, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 }  // namespace
@@ -875,16 +1004,7 @@ public:
         : rank_(rank), count_(count) {
         if (layout) layout_ = *layout;
         haveLayout_ = layout != nullptr;
-        // a header-only container so that the one header parser serves both forms
-        std::vector<uint8_t> mini;
-        auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) mini.push_back((uint8_t)(v >> (8 * k))); };
-        auto put64 = [&](uint64_t v) { for (int k = 0; k < 8; k++) mini.push_back((uint8_t)(v >> (8 * k))); };
-        mini.insert(mini.end(), {'z', 'k', 'e', 'y'});
-        put32(1); put32(3);
-        put32(1); put64(4); put32(1);
-        put32(2); put64(headerSize);
-        mini.insert(mini.end(), static_cast<const uint8_t*>(header), static_cast<const uint8_t*>(header) + headerSize);
-        put32(4); put64(0);
+        const std::vector<uint8_t> mini = miniZkey(header, headerSize, 1);
         BinFile f(mini.data(), mini.size(), "zkey", 1);
         hdr_ = loadZkeyHeader(f, false);
         if (!hdr_.rIsBn254) throw std::invalid_argument("zkey curve not supported");
@@ -913,16 +1033,11 @@ private:
         const uint64_t cLo = rg.c.lo, cHi = rg.c.hi;
         if (!src.sliced) {                       // whole sections: step to this rank's slice
             pA += wr_.lo * 64; pB1 += wr_.lo * 64; pB2 += wr_.lo * 128; pC += cLo * 64; pH += hr_.lo * 64;
-        } else {                                 // slices: each must hold the points of this rank's range (a short buffer would be read past its end)
+        } else {                                 // slices: each must hold the points of this rank's range
             const uint64_t need[5] = {(wr_.hi - wr_.lo) * 64, (wr_.hi - wr_.lo) * 64, (wr_.hi - wr_.lo) * 128, (cHi - cLo) * 64, (hr_.hi - hr_.lo) * 64};
             const uint8_t* ptr[5] = {pA, pB1, pB2, pC, pH};
             static const char* const what[5] = {"points_a", "points_b1", "points_b2", "points_c", "points_h"};
-            for (int k = 0; k < 5; k++) {
-                if (need[k] && !ptr[k]) throw std::invalid_argument(std::string("Null ") + what[k] + " slice");
-                if (src.sliceBytes && src.sliceBytes[k] < need[k])
-                    throw std::invalid_argument(std::string(what[k]) + " slice is shorter than this rank's range: " + std::to_string(src.sliceBytes[k]) +
-                                                " bytes, needed " + std::to_string(need[k]));
-            }
+            checkSlices(what, need, ptr, src.sliceBytes, 5);
             if (src.haveCoefs && !src.coefs && src.nCoefs) throw std::invalid_argument("Null coefficient records");
         }
 
@@ -977,20 +1092,18 @@ private:
         const bool strided = g_deferTables && !g_oneShotProver && !g_registryCreate && count == 1 && !haveLayout_ && !src.sliced;
         std::vector<TableChoice> plan = planTableWidthsAhead(d_.ctx, tableGroups(), otherBytes, strided);
         plan.resize(3);
-        std::vector<int> ahead(3), aheadS(3);
-        for (int k = 0; k < 3; k++) { ahead[k] = plan[k].c; aheadS[k] = plan[k].stride; }
         bool withTables = true;
-        if (bgTables_ && (ahead[0] || ahead[1])) {
+        if (bgTables_ && (plan[0].c || plan[1].c)) {
             ugCheck(ug_ctx_defer_tables(d_.ctx, 1));
             ugCheck(ug_ctx_defer_tables(d_.ctx2, 1));
         } else bgTables_ = false;
         // (section: the zkey section the records are a slice of, from its point `first` on -- or, compacted, the points support[j])
-        auto create = [&](ug_ctx* ctx, bool g2, const uint8_t* pts, uint64_t n, uint64_t first, int width, int stride, ug_bases** out,
+        auto create = [&](ug_ctx* ctx, bool g2, const uint8_t* pts, uint64_t n, uint64_t first, const TableChoice& t, ug_bases** out,
                           int section, const uint32_t* support = nullptr) {
             const PointOrigin from = {section, first, first, support};
-            if (width && withTables) {
-                int rc = g2 ? ug_bases_create_tables_strided_g2(ctx, pts, n, first, width, stride, out)
-                            : ug_bases_create_tables_strided_g1(ctx, pts, n, first, width, stride, out);
+            if (t.c && withTables) {
+                int rc = g2 ? ug_bases_create_tables_strided_g2(ctx, pts, n, first, t.c, t.stride, out)
+                            : ug_bases_create_tables_strided_g1(ctx, pts, n, first, t.c, t.stride, out);
                 if (rc == UG_OK) return;
                 throwIfPointFault(ctx, rc, &from);       // (a bad point is no reason to try again)
                 withTables = false;                 // memory ran short after all: this set and the rest without tables
@@ -1006,15 +1119,15 @@ private:
             const uint64_t counts[2] = {nw, cHi - cLo}, firsts[2] = {wr_.lo, cFirst};
             const PointOrigin from[2] = {fromA, fromCg};
             int rc = UG_ERROR;
-            if (ahead[0]) { rc = ug_bases_create_group_strided_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G); throwIfPointFault(d_.ctx, rc, from, 2); }
+            if (plan[0].c) { rc = ug_bases_create_group_strided_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, plan[0].c, plan[0].stride, &d_.G); throwIfPointFault(d_.ctx, rc, from, 2); }
             if (rc != UG_OK) {
-                if (ahead[0]) withTables = false;
+                if (plan[0].c) withTables = false;
                 rc = ug_bases_create_group_g1(d_.ctx, 2, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G);
                 throwIfPointFault(d_.ctx, rc, from, 2);
                 ugCheck(rc);
             }
-            create(d_.ctx, false, b1c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc1, 6, bSupport.data());
-            create(d_.ctx, true, b2c.data(), nB_, 0, ahead[2], aheadS[2], &d_.Bc2, 7, bSupport.data());
+            create(d_.ctx, false, b1c.data(), nB_, 0, plan[2], &d_.Bc1, 6, bSupport.data());
+            create(d_.ctx, true, b2c.data(), nB_, 0, plan[2], &d_.Bc2, 7, bSupport.data());
             ugCheck(ug_index_create(d_.ctx, bSupport.data(), nB_, &d_.bIdx));
             ugCheck(ug_dvec_create(d_.ctx, nB_, &d_.wB));
             ugCheck(ug_schedule_create(d_.ctx, &d_.sB));
@@ -1025,42 +1138,42 @@ private:
             const uint64_t counts[3] = {nw, nw, cHi - cLo}, firsts[3] = {wr_.lo, wr_.lo, cFirst};
             const PointOrigin from[3] = {fromA, fromB1, fromCg};
             int rc = UG_ERROR;
-            if (ahead[0]) { rc = ug_bases_create_group_strided_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, ahead[0], aheadS[0], &d_.G); throwIfPointFault(d_.ctx, rc, from, 3); }
+            if (plan[0].c) { rc = ug_bases_create_group_strided_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, plan[0].c, plan[0].stride, &d_.G); throwIfPointFault(d_.ctx, rc, from, 3); }
             if (rc != UG_OK) {
-                if (ahead[0]) withTables = false;           // memory ran short after all
+                if (plan[0].c) withTables = false;           // memory ran short after all
                 rc = ug_bases_create_group_g1(d_.ctx, 3, hosts, counts, firsts, wr_.lo, nw, 0, &d_.G);
                 throwIfPointFault(d_.ctx, rc, from, 3);
                 ugCheck(rc);
             }
         } else {
-            create(d_.ctx, false, pA, nw, wr_.lo, ahead[0], aheadS[0], &d_.A, 5);
-            create(d_.ctx, false, pB1, nw, wr_.lo, ahead[0], aheadS[0], &d_.B1, 6);
+            create(d_.ctx, false, pA, nw, wr_.lo, plan[0], &d_.A, 5);
+            create(d_.ctx, false, pB1, nw, wr_.lo, plan[0], &d_.B1, 6);
         }
         traceStep("create: G1 sets of the witness uploaded");
-        if (!sparseB_) create(d_.ctx, true, pB2, nw, wr_.lo, ahead[0], aheadS[0], &d_.B2, 7);
+        if (!sparseB_) create(d_.ctx, true, pB2, nw, wr_.lo, plan[0], &d_.B2, 7);
         traceStep("create: B2 uploaded");
-        if (!d_.G) create(d_.ctx, false, pC, cHi - cLo, cLo, ahead[0], aheadS[0], &d_.C, 8);
-        const bool group0 = withTables && ahead[0];
-        create(d_.ctx2, false, pH, nh, hr_.lo, ahead[1], aheadS[1], &d_.H, 9);
+        if (!d_.G) create(d_.ctx, false, pC, cHi - cLo, cLo, plan[0], &d_.C, 8);
+        const bool group0 = withTables && plan[0].c;
+        create(d_.ctx2, false, pH, nh, hr_.lo, plan[1], &d_.H, 9);
         traceStep("create: H uploaded");
-        const bool group1 = withTables && ahead[1];
-        const bool group2 = sparseB_ && withTables && ahead[2];
-        if (ahead[0] && !group0) {
+        const bool group1 = withTables && plan[1].c;
+        const bool group2 = sparseB_ && withTables && plan[2].c;
+        if (plan[0].c && !group0) {
             for (ug_bases* b : {d_.G, d_.A, d_.B1, d_.B2, d_.C}) if (b) ug_bases_drop_tables(b);
         }
-        if (sparseB_ && ahead[2] && !group2) { ug_bases_drop_tables(d_.Bc1); ug_bases_drop_tables(d_.Bc2); }
-        tableW_ = group0 ? ahead[0] : 0;
-        tableH_ = group1 ? ahead[1] : 0;
-        d_.tableB = group2 ? ahead[2] : 0;
-        strideW_ = aheadS[0]; strideH_ = aheadS[1]; d_.strideB = aheadS[2];
-        auto bytes = [](uint64_t n, int g2, int c, int st) { return ug_bases_tables_bytes_strided(n, g2, c, st); };
-        if (group0) tableBytes += (d_.G ? bytes((sparseB_ ? 2 : 3) * nw, 0, tableW_, strideW_) : bytes(nw, 0, tableW_, strideW_) * 2 + bytes(cHi - cLo, 0, tableW_, strideW_)) +
-                                  (sparseB_ ? 0 : bytes(nw, 1, tableW_, strideW_));
-        if (group1) tableBytes += bytes(nh, 0, tableH_, strideH_);
-        if (group2) tableBytes += bytes(nB_, 0, d_.tableB, d_.strideB) + bytes(nB_, 1, d_.tableB, d_.strideB);
+        if (sparseB_ && plan[2].c && !group2) { ug_bases_drop_tables(d_.Bc1); ug_bases_drop_tables(d_.Bc2); }
+        // (the stride is set with the plan; the width follows once the tables are in use)
+        planW_ = TableChoice{group0 ? plan[0].c : 0, plan[0].stride};
+        planH_ = TableChoice{group1 ? plan[1].c : 0, plan[1].stride};
+        d_.planB = TableChoice{group2 ? plan[2].c : 0, plan[2].stride};
+        auto bytes = [](uint64_t n, int g2, const TableChoice& t) { return ug_bases_tables_bytes_strided(n, g2, t.c, t.stride); };
+        if (group0) tableBytes += (d_.G ? bytes((sparseB_ ? 2 : 3) * nw, 0, planW_) : bytes(nw, 0, planW_) * 2 + bytes(cHi - cLo, 0, planW_)) +
+                                  (sparseB_ ? 0 : bytes(nw, 1, planW_));
+        if (group1) tableBytes += bytes(nh, 0, planH_);
+        if (group2) tableBytes += bytes(nB_, 0, d_.planB) + bytes(nB_, 1, d_.planB);
         if (bgTables_) {          // classic windows until tableBuilder() has finished them
-            pendingW_.store(tableW_); pendingH_.store(tableH_); pendingB_.store(d_.tableB);
-            tableW_ = tableH_ = 0; d_.tableB = 0;
+            TableChoice* const mine[3] = {&planW_, &planH_, &d_.planB};
+            for (int g = 0; g < 3; g++) { pending_[g].store(mine[g]->c); mine[g]->c = 0; }
         }
         if (haveHpoly_ && !d_.hp) ugCheck(ug_hpoly_create(d_.ctx2, coefs, hdr_.nCoefs, hdr_.domainSize, hdr_.nVars, &d_.hp));
         ugCheck(ug_dvec_create(d_.ctx, M, &d_.w));
@@ -1073,7 +1186,7 @@ private:
             // Bucket classes: this rank's witness schedule keeps its residues' entries only. They exist for the window-table form
             // (ONE bucket set per product, so that a class is a slice of it): without the tables every window would bring its own
             // sets of every owned residue, and the result blocks would not hold them.
-            if (!tableW_) throw TablesUnavailable("a bucket-class layout needs the fixed-base window tables (device memory short, or ULTRAGROTH_TABLES=0)");
+            if (!planW_.c) throw TablesUnavailable("a bucket-class layout needs the fixed-base window tables (device memory short, or ULTRAGROTH_TABLES=0)");
             if (layout_.sp.lo > layout_.sp.hi || layout_.sp.hi > M) throw std::invalid_argument("special-bucket range outside [0, nVars]");
             ugCheck(ug_schedule_set_classes(d_.sw, layout_.qLog, layout_.r0, layout_.cnt, SHARD_SPECIALS, layout_.sp.lo, layout_.sp.hi - layout_.sp.lo));
         }
@@ -1097,6 +1210,14 @@ public:
     // proof then waits ~10 ms; the tables arrive after ~190 proofs at 2^24 instead of never), and never two in a row while
     // somebody waits
     void callerHasTheTurn() { builderHadLast_.store(false); turnsTaken_.fetch_add(1); }
+    // the prover's turn for a caller (the table builder steps back); forProof: the turn of a proof or a device pass, which the
+    // builder counts (callerHasTheTurn), not one that only plans, adopts a witness or writes figures
+    std::unique_lock<std::mutex> takeTurn(bool forProof) {
+        std::unique_lock<std::mutex> turn;
+        { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
+        if (forProof) callerHasTheTurn();
+        return turn;
+    }
     void tableBuilder() {
         // pieces of about 10 ms: the G1 table kernel makes ~60 k points per ms, the G2 one ~20 k (2^24: 840 ms for 50 M points of
         // the A | B1 | C group, 836 ms for 16.7 M points of B2)
@@ -1144,9 +1265,10 @@ public:
             }
             for (int group = 0; group < 3; group++) {
                 ug_bases* sets[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-                if (group == 0) { if (!pendingW_.load()) continue; sets[0] = d_.G; sets[1] = d_.A; sets[2] = d_.B1; sets[3] = d_.C; sets[4] = d_.B2; }
-                else if (group == 1) { if (!pendingH_.load()) continue; sets[0] = d_.H; }
-                else { if (!pendingB_.load()) continue; sets[0] = d_.Bc1; sets[4] = d_.Bc2; }
+                if (!pending_[group].load()) continue;
+                if (group == 0) { sets[0] = d_.G; sets[1] = d_.A; sets[2] = d_.B1; sets[3] = d_.C; sets[4] = d_.B2; }
+                else if (group == 1) sets[0] = d_.H;
+                else { sets[0] = d_.Bc1; sets[4] = d_.Bc2; }
                 for (ug_bases* b : sets) {
                     if (!b) continue;
                     for (;;) {
@@ -1165,9 +1287,8 @@ public:
                     }
                 }
                 std::lock_guard<std::mutex> turn(proveMutex);             // a proof boundary: the next proof uses the tables
-                if (group == 0) { tableW_ = pendingW_.load(); pendingW_.store(0); }
-                else if (group == 1) { tableH_ = pendingH_.load(); pendingH_.store(0); }
-                else { d_.tableB = pendingB_.load(); pendingB_.store(0); }
+                (group == 0 ? planW_ : group == 1 ? planH_ : d_.planB).c = pending_[group].load();      // (in use before it stops
+                pending_[group].store(0);                                                                   // being pending: tablePlan)
                 dropGraphs();
                 traceStep(group == 0 ? "window tables of the witness sets in use" : group == 1 ? "window tables of H in use" : "window tables of the B sets in use");
             }
@@ -1185,17 +1306,17 @@ public:
         while (wait && !builderDone_.load() && !stopBuilder_.load()) std::this_thread::sleep_for(std::chrono::milliseconds(1));
         // (no turn taken: a query must not wait for the builder's pieces; the error string is complete once builderDone_ is set)
         if (wait && builderDone_.load() && !builderError_.empty()) throw std::runtime_error("window tables: " + builderError_);
-        return !pendingW_.load() && !pendingH_.load() && !pendingB_.load();
+        return !pending_[0].load() && !pending_[1].load() && !pending_[2].load();
     }
     std::vector<TableGroup> tableGroups() override {
         std::vector<TableGroup> groups(2);
         if (d_.G || (!d_.A && groupG1_)) { groups[0].g1 = {d_.G}; groups[0].n1 = {3 * (wr_.hi - wr_.lo)}; }      // (also before the sets exist)
         else { groups[0].g1 = {d_.A, d_.B1, d_.C}; groups[0].n1 = {wr_.hi - wr_.lo, wr_.hi - wr_.lo, cHi_ - cLo_}; }
         groups[0].g2 = {d_.B2}; groups[0].n2 = {wr_.hi - wr_.lo};
-        groups[0].scalars = wr_.hi - wr_.lo; groups[0].c = &tableW_; groups[0].stride = &strideW_;
+        groups[0].scalars = wr_.hi - wr_.lo; groups[0].plan = &planW_;
         if (wr_.hi - wr_.lo > maxRange_) groups[0].scalars = 0;          // proved in pieces: classic windows per piece
         groups[1].g1 = {d_.H}; groups[1].n1 = {hr_.hi - hr_.lo};
-        groups[1].scalars = hr_.hi - hr_.lo; groups[1].c = &tableH_; groups[1].stride = &strideH_;
+        groups[1].scalars = hr_.hi - hr_.lo; groups[1].plan = &planH_;
         if (hr_.hi - hr_.lo > maxRange_) groups[1].scalars = 0;
         if (sparseB_) {               // the group of the witness holds [A | C] only; B1 and B2 live compacted, with a schedule of their own
             groups[0].g1 = {d_.G}; groups[0].n1 = {2 * (wr_.hi - wr_.lo)};
@@ -1203,23 +1324,17 @@ public:
             groups.resize(3);
             groups[2].g1 = {d_.Bc1}; groups[2].n1 = {nB_};
             groups[2].g2 = {d_.Bc2}; groups[2].n2 = {nB_};
-            groups[2].scalars = nB_; groups[2].c = &d_.tableB; groups[2].stride = &d_.strideB;
+            groups[2].scalars = nB_; groups[2].plan = &d_.planB;
         }
         return groups;
     }
-    int pendingWidth(int group) const override {
-        return group == 0 ? pendingW_.load() : group == 1 ? pendingH_.load() : group == 2 ? pendingB_.load() : 0;
-    }
+    int pendingWidth(int group) const override { return group >= 0 && group < 3 ? pending_[group].load() : 0; }
     void trimWorkspaces() override {
-        std::lock_guard<std::mutex> batch(batchMutex_);     // (a batch call owns the batch buffers it stages into)
+        std::lock_guard<std::mutex> batch(batch_.mutex);    // (a batch call owns the batch buffers it stages into)
         TurnRequest mine(wantTurn_);
         std::lock_guard<std::mutex> turn(proveMutex);
         dropGraphs();                                   // (they hold pointers into what goes now)
-        ug_schedule_trim(d_.sw); ug_schedule_trim(d_.sh);
-        if (d_.sB) ug_schedule_trim(d_.sB);
-        ug_ctx_trim(d_.ctx); ug_ctx_trim(d_.ctx2);
-        witness_.trim(wCur_);
-        releaseBatch();
+        trimDeviceWorkspaces(d_, witness_, wCur_, batch_);
     }
 
     const ZkeyHeader& header() const { return hdr_; }
@@ -1239,8 +1354,7 @@ public:
         if (witnessQueued_ == 1) throw std::invalid_argument("the queued witness products still read the witness (ug_groth16_prover_witness_msm_end)");
         WitnessLease lease(witness_);
         stage(*lease, wtns, wtnsSize);
-        std::unique_lock<std::mutex> turn;
-        { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
+        std::unique_lock<std::mutex> turn = takeTurn(false);
         adopt(*lease);
     }
     // staging: parse the .wtns and copy the witness into the leased buffer; needs no turn on the device, only the
@@ -1280,9 +1394,7 @@ public:
         traceStep("witness staged");
         std::unique_lock<std::mutex> card;
         if (device) card = std::unique_lock<std::mutex>(*device);
-        std::unique_lock<std::mutex> turn;
-        { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
-        callerHasTheTurn();
+        std::unique_lock<std::mutex> turn = takeTurn(true);
         traceStep("turn on the device");
         AroundGuard bracket(around);
         bracket.begin();
@@ -1338,7 +1450,7 @@ public:
             uint64_t n = std::min<uint64_t>(maxRange_, wr_.hi - lo);
             uint8_t* out = (lo == wr_.lo) ? partials : part;
             memset(part, 0, sizeof part);
-            buildSchedule(d_.sw, wCur_, lo, n, tableW_, strideW_);
+            buildSchedule(d_.sw, wCur_, lo, n, planW_.c, planW_.stride);
             // S1-S4 (src/groth16.cpp:55,58,61,64): A, B1, B2, C over the witness schedule, queued back to back
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, out, out + 64, out + 128, out + 256, (int64_t)hdr_.nPublic + 1, false, wCur_);
             ugCheck(ug_ctx_collect(d_.ctx));
@@ -1368,7 +1480,7 @@ public:
             return;
         }
         QueueGuard inFlight(d_.ctx);
-        buildSchedule(d_.sw, wCur_, wr_.lo, n, tableW_, strideW_);
+        buildSchedule(d_.sw, wCur_, wr_.lo, n, planW_.c, planW_.stride);
         enqueueWitnessProducts(d_, d_.ctx, d_.sw, queuedParts_, queuedParts_ + 64, queuedParts_ + 128, queuedParts_ + 256,
                                (int64_t)hdr_.nPublic + 1, false, wCur_);
         inFlight.done();
@@ -1402,7 +1514,7 @@ public:
             uint64_t n = std::min<uint64_t>(maxRange_, hr_.hi - lo);
             uint8_t* out = (lo == hr_.lo) ? partials : part;
             memset(part, 0, sizeof part);
-            buildSchedule(d_.sh, d_.h, lo, n, tableH_, strideH_);
+            buildSchedule(d_.sh, d_.h, lo, n, planH_.c, planH_.stride);
             const ug_bases* sets[1] = {d_.H};
             void* outs[1] = {out + 320};
             ugCheck(ug_msm_batch(d_.ctx2, 1, sets, d_.sh, nullptr, outs));                     // S10 :154
@@ -1484,12 +1596,12 @@ public:
         // queued products write to runParts_, a member, so that a replay finds the same addresses)
         auto queueAll = [&] {
             uint8_t* out = runParts_;
-            buildSchedule(d_.sw, wCur_, wr_.lo, nw, tableW_, strideW_);
+            buildSchedule(d_.sw, wCur_, wr_.lo, nw, planW_.c, planW_.stride);
             // S1-S4 (src/groth16.cpp:55,58,61,64): A, B1, B2, C over the witness schedule, queued back to back
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, out, out + 64, out + 128, out + 256, (int64_t)hdr_.nPublic + 1, overlap == 2, wCur_);
             if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));                                          // S5-S9 :66-148
-            buildSchedule(d_.sh, d_.h, hr_.lo, nh, tableH_, strideH_);
+            buildSchedule(d_.sh, d_.h, hr_.lo, nh, planH_.c, planH_.stride);
             if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             const ug_bases* sets[1] = {d_.H};
             void* outs[1] = {out + 320};
@@ -1586,9 +1698,7 @@ public:
     // one whole proof (S1-S13) of the witness that is already resident (loadWitness): what prove does after its staging --
     // r and s drawn first, the multiples that need only them formed on host threads beside the device work
     void proveResident(std::string& proof, std::string& pub) override {
-        std::unique_lock<std::mutex> turn;
-        { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
-        callerHasTheTurn();
+        std::unique_lock<std::mutex> turn = takeTurn(true);
         if (!witnessLoaded_ || !witnessComplete_) throw std::invalid_argument("no witness loaded");
         proveLoaded(proof, pub);
     }
@@ -1610,132 +1720,82 @@ public:
     }
 
     // ---- batched proofs (ug_groth16_prover_prove_batch) ----
-    // Every witness is parsed and checked first: a bad one fails the call before anything is queued. Then each device pass takes
-    // up to ug_plan_proof_batch witnesses, under the prover's turn as a single proof: ONE V-vector witness schedule and its
-    // products, one ug_hpoly_run per witness into V slices of the batch h buffer, ONE V-vector H schedule and product, one
-    // collect per context. r and s are drawn in witness order (r0, s0, r1, s1, ...) and their multiples of delta formed on host
-    // threads beside the device work. A pass of one witness, or a circuit proved in pieces, takes the single-proof path.
+    // proveBatchInPasses with these parts. A device pass of V witnesses runs under the prover's turn as a single proof: ONE
+    // V-vector witness schedule and its products, one ug_hpoly_run per witness into V slices of the batch h buffer, ONE V-vector H
+    // schedule and product, one collect per context. r and s are drawn in witness order (r0, s0, r1, s1, ...) and their multiples
+    // of delta formed on host threads beside the device work. A circuit proved in pieces takes the single-proof path.
+    struct BatchCall {
+        const void* const* wtns; const unsigned long long* sizes;
+        std::vector<std::string>& proofs; std::vector<std::string>& pubs;
+        std::vector<const uint8_t*> data;          // the witness section of every .wtns
+        double msm = 0, fft = 0;
+    };
+    struct BatchPass {                             // (terms last: the host threads join before what they read goes)
+        std::vector<uint8_t> r, s, parts;
+        std::vector<std::future<BlindingTerms>> terms;
+    };
     void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
                     std::vector<std::string>& pubs) override {
-        auto t0 = std::chrono::steady_clock::now();
-        std::vector<const uint8_t*> data((size_t)k);
-        for (int b = 0; b < k; b++) {
-            const std::string at = "witness " + std::to_string(b) + ": ";
-            try {
-                BinFile f(wtns[b], sizes[b], "wtns", 2);
-                data[(size_t)b] = witnessData(f);
-            } catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
-            catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
-        }
-        proofs.assign((size_t)k, std::string()); pubs.assign((size_t)k, std::string());
-        // the batch buffers belong to one batch call at a time; the witnesses of a pass are copied into them BEFORE the pass takes
-        // the prover's turn (as a single proof stages its witness), so another caller's kernels may run meanwhile
-        std::lock_guard<std::mutex> batchLock(batchMutex_);
-        double msm = 0, fft = 0;
-        for (int b0 = 0; b0 < k;) {
-            int V = 1;
-            {
-                std::unique_lock<std::mutex> turn;
-                { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
-                V = batchPerPass(k - b0);
-                if (V > 1) reserveBatch(V);
-            }
-            if (V <= 1) {                                   // the single-proof path
-                proveOneInBatch(wtns[b0], sizes[b0], proofs[(size_t)b0], pubs[(size_t)b0], msm, fft);
-                b0++;
-                continue;
-            }
-            stageBatch(data.data() + b0, V);                // (no turn held: nothing queued reads the batch buffers)
-            std::unique_lock<std::mutex> turn;
-            { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
-            callerHasTheTurn();
-            V = std::min(V, batchPerPass(V));               // (the table plan may have changed meanwhile: the rest is staged again)
-            if (V <= 1) continue;
-            std::vector<uint8_t> r((size_t)V * 32), sb((size_t)V * 32);
-            for (int v = 0; v < V; v++) { drawBlinding(&r[(size_t)v * 32]); drawBlinding(&sb[(size_t)v * 32]); }      // S11, in witness order
-            std::vector<std::future<BlindingTerms>> terms;
-            for (int v = 0; v < V; v++)
-                terms.push_back(std::async(std::launch::async, [&, v] { return blindingTerms(hdr_, &r[(size_t)v * 32], &sb[(size_t)v * 32]); }));
-            std::vector<uint8_t> parts((size_t)V * UG_GROTH16_PARTIALS_SIZE);
-            runBatch(V, parts.data());                      // (the futures join in their destructors if this throws)
-            msm += m1_ + m2_; fft += f1_ + f2_;
-            turn.unlock();
-            for (int v = 0; v < V; v++) {
-                const uint8_t* w = data[(size_t)(b0 + v)];
-                const std::vector<uint8_t> publicPart(w, w + ((size_t)hdr_.nPublic + 1) * 32);
-                finishWith(&parts[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &r[(size_t)v * 32], &sb[(size_t)v * 32], terms[(size_t)v].get(),
-                           proofs[(size_t)(b0 + v)], pubs[(size_t)(b0 + v)], &publicPart);
-            }
-            b0 += V;
-        }
-        // the call's figures for ug_prover_last_timings, written under the turn as every proof writes them
-        TurnRequest mine(wantTurn_);
-        std::lock_guard<std::mutex> turn(proveMutex);
-        m1_ = msm; f1_ = fft; m2_ = f2_ = 0;
-        totalMs_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        BatchCall c{wtns, sizes, proofs, pubs, std::vector<const uint8_t*>((size_t)k)};
+        proveBatchInPasses(*this, c, k);
     }
-    // one witness of a batch on the single-proof path (proveTurn), its device times added to msm / fft while it holds the turn
-    void proveOneInBatch(const void* wtns, unsigned long long wtnsSize, std::string& proof, std::string& pub, double& msm, double& fft) {
+    void parseForBatch(BatchCall& c, int b) const {
+        BinFile f(c.wtns[b], c.sizes[b], "wtns", 2);
+        c.data[(size_t)b] = witnessData(f);
+    }
+    // one witness of a batch on the single-proof path (proveTurn), its device times added while it holds the turn
+    void proveOneOfBatch(BatchCall& c, int b) {
         WitnessLease lease(witness_);
-        stage(*lease, wtns, wtnsSize);
-        std::unique_lock<std::mutex> turn;
-        { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
-        callerHasTheTurn();
+        stage(*lease, c.wtns[b], c.sizes[b]);
+        std::unique_lock<std::mutex> turn = takeTurn(true);
         adopt(*lease);
-        proveLoaded(proof, pub, [&] {
-            msm += m1_ + m2_; fft += f1_ + f2_;
+        proveLoaded(c.proofs[(size_t)b], c.pubs[(size_t)b], [&] {
+            c.msm += m1_ + m2_; c.fft += f1_ + f2_;
             turn.unlock();
         });
     }
     // witnesses per device pass for up to `requested` (proveMutex held: the schedules' current table plan)
-    int batchPerPass(int requested) {
+    int perPass(const BatchCall&, int requested, int /*b0*/) {
         const uint64_t nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
         if (requested <= 1 || nw > maxRange_ || nh > maxRange_ || !haveHpoly_ || count_ > 1 || haveLayout_) return 1;
-        std::vector<ug_batch_schedule> sch;
-        sch.push_back(ug_batch_schedule{nw, tableW_, strideW_});
-        sch.push_back(ug_batch_schedule{nh, tableH_, strideH_});
-        if (sparseB_) sch.push_back(ug_batch_schedule{nB_, d_.tableB, d_.strideB});
+        const std::vector<ug_batch_schedule> sch = batchSchedules();
         uint64_t freeB = 0, totalB = 0;
         ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
-        for (ug_dvec* v : {wBatch_, hBatch_, wBBatch_}) if (v) freeB += ug_dvec_size(v) * 32;      // (reused or replaced)
-        // window tables the background builder has still to take into use keep their room: a batch that lands before them must
-        // not take the memory they are planned in (their allocation would fail and the prover stay on classic windows)
-        uint64_t pending = 0;
-        for (int g = 0; g < 3; g++) {
-            int c = 0, st = 0, ready = 1;
-            uint64_t bytes = 0;
-            if (tablePlan(g, &c, &st, &bytes, &ready) && !ready) pending += bytes;
-        }
+        freeB += batch_.bytesHeld();                                  // (reused or replaced)
+        const uint64_t pending = pendingTableBytes();                 // (the background builder's tables keep their room)
         freeB = freeB > pending ? freeB - pending : 0;
         const int V = ug_plan_proof_batch(sch.data(), (int)sch.size(), hdr_.nVars, hdr_.domainSize, freeB, requested);
         if (V < 1) throw std::logic_error("batch plan failed");
         return V;
     }
-    // batch buffer of at least n elements (a smaller one is replaced)
-    void ensureBatch(ug_dvec*& v, ug_ctx* ctx, uint64_t n) {
-        if (v && ug_dvec_size(v) >= n) return;
-        ug_dvec_destroy(v); v = nullptr;
-        ugCheck(ug_dvec_create(ctx, n, &v));
-    }
-    void releaseBatch() { ug_dvec_destroy(wBatch_); ug_dvec_destroy(hBatch_); ug_dvec_destroy(wBBatch_); wBatch_ = hBatch_ = wBBatch_ = nullptr; }
     // the batch buffers for V witnesses (proveMutex held: an allocation may not happen while kernels of a proof are queued)
     void reserveBatch(int V) {
-        ensureBatch(wBatch_, d_.ctx, (uint64_t)V * hdr_.nVars);
-        ensureBatch(hBatch_, d_.ctx2, (uint64_t)V * hdr_.domainSize);
-        if (d_.Bc2) ensureBatch(wBBatch_, d_.ctx, (uint64_t)V * nB_);
+        BatchBuffers::ensure(batch_.w, d_.ctx, (uint64_t)V * hdr_.nVars);
+        BatchBuffers::ensure(batch_.h, d_.ctx2, (uint64_t)V * hdr_.domainSize);
+        if (d_.Bc2) BatchBuffers::ensure(batch_.wB, d_.ctx, (uint64_t)V * nB_);
     }
-    // the V witnesses into the batch witness buffer, on the uploader's own streams (batchMutex_ held, no turn: the last pass
-    // that read the buffer has been collected)
-    void stageBatch(const uint8_t* const* data, int V) {
-        const uint64_t nv = hdr_.nVars;
+    void stagePass(const BatchCall& c, int b0, int V) { batch_.stage(d_.ctx, witness_.stageMutex, c.data.data() + b0, V, hdr_.nVars); }
+    BatchPass runPass(BatchCall& c, int /*b0*/, int V) {
+        BatchPass p;
+        p.r.resize((size_t)V * 32); p.s.resize((size_t)V * 32); p.parts.resize((size_t)V * UG_GROTH16_PARTIALS_SIZE);
+        for (int v = 0; v < V; v++) { drawBlinding(&p.r[(size_t)v * 32]); drawBlinding(&p.s[(size_t)v * 32]); }      // S11, in witness order
         for (int v = 0; v < V; v++) {
-            ug_dvec* view = nullptr;
-            ugCheck(ug_dvec_wrap(d_.ctx, (uint8_t*)ug_dvec_device_ptr(wBatch_) + (uint64_t)v * nv * 32, nv, &view));
-            const int rc = ug_dvec_upload_idle(view, data[v], nv);
-            ug_dvec_destroy(view);
-            ugCheck(rc);
+            const uint8_t *r = &p.r[(size_t)v * 32], *s = &p.s[(size_t)v * 32];      // (by value: `p` may move when it is returned, its buffers stay)
+            p.terms.push_back(std::async(std::launch::async, [this, r, s] { return blindingTerms(hdr_, r, s); }));
+        }
+        runBatch(V, p.parts.data());                    // (the futures join in their destructors if this throws)
+        c.msm += m1_ + m2_; c.fft += f1_ + f2_;
+        return p;
+    }
+    void finishPass(BatchCall& c, int b0, int V, BatchPass& p) {
+        for (int v = 0; v < V; v++) {
+            const uint8_t* w = c.data[(size_t)(b0 + v)];
+            const std::vector<uint8_t> publicPart(w, w + ((size_t)hdr_.nPublic + 1) * 32);
+            finishWith(&p.parts[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &p.r[(size_t)v * 32], &p.s[(size_t)v * 32], p.terms[(size_t)v].get(),
+                       c.proofs[(size_t)(b0 + v)], c.pubs[(size_t)(b0 + v)], &publicPart);
         }
     }
+    void setBatchTimings(double msm, double fft, double total) { m1_ = msm; f1_ = fft; m2_ = f2_ = 0; totalMs_ = total; }
     // one device pass of the V staged witnesses; parts = V blocks A | B1 | B2 | C | H as run() leaves them
     void runBatch(int V, uint8_t* parts) {
         const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize, nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
@@ -1743,22 +1803,16 @@ public:
         const int overlap = ov ? atoi(ov) : 1;
         resetTimings();
         std::vector<uint8_t> outA((size_t)V * 64), outB1((size_t)V * 64), outB2((size_t)V * 128), outC((size_t)V * 64), outH((size_t)V * 64);
-        std::vector<ug_dvec*> views;
-        struct Views { std::vector<ug_dvec*>& v; ~Views() { for (ug_dvec* x : v) ug_dvec_destroy(x); } } viewsGuard{views};
-        auto view = [&](ug_ctx* ctx, ug_dvec* of, uint64_t first, uint64_t n) {
-            views.push_back(nullptr);
-            ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(of) + first * 32, n, &views.back()));
-            return views.back();
-        };
+        BatchBuffers::DeviceViews views;
         {
             QueueGuard inFlight(d_.ctx, d_.ctx2);
-            ugCheck(ug_schedule_build_vectors(d_.sw, wBatch_, wr_.lo, nw, V, nv, tableW_, strideW_));
+            ugCheck(ug_schedule_build_vectors(d_.sw, batch_.w, wr_.lo, nw, V, nv, planW_.c, planW_.stride));
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), outC.data(), (int64_t)hdr_.nPublic + 1,
-                                   overlap == 2, wBatch_, V, nv, wBBatch_);
+                                   overlap == 2, batch_.w, V, nv, batch_.wB);
             if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             for (int v = 0; v < V; v++)
-                ugCheck(ug_hpoly_run(d_.hp, view(d_.ctx2, wBatch_, (uint64_t)v * nv, nv), view(d_.ctx2, hBatch_, (uint64_t)v * dom, dom)));
-            ugCheck(ug_schedule_build_vectors(d_.sh, hBatch_, hr_.lo, nh, V, dom, tableH_, strideH_));
+                ugCheck(ug_hpoly_run(d_.hp, views.view(d_.ctx2, batch_.w, (uint64_t)v * nv, nv), views.view(d_.ctx2, batch_.h, (uint64_t)v * dom, dom)));
+            ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
             if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             const ug_bases* sets[1] = {d_.H};
             void* outs[1] = {outH.data()};
@@ -1797,9 +1851,8 @@ public:
 private:
     static constexpr uint64_t MAX_RANGE = (uint64_t)1 << 26;       // 2^26 scalars * <= 16 windows < 2^31 entries
     uint64_t maxRange_ = MAX_RANGE;    // ULTRAGROTH_MAX_RANGE lowers it (tests: the piecewise path without a 2^27 circuit)
-    int tableW_ = 0, tableH_ = 0;      // window widths of the fixed-base tables (0: classic windows), planWindowTables
-    int strideW_ = 1, strideH_ = 1;    // ... and their strides (set with the plan; the widths follow once the tables are in use)
-    std::atomic<int> pendingW_{0}, pendingH_{0}, pendingB_{0};      // ... of tables that are still being built (tableBuilder)
+    TableChoice planW_, planH_;        // fixed-base tables of the witness and H groups (planWindowTables; the B group's: d_.planB)
+    std::atomic<int> pending_[3] = {{0}, {0}, {0}};      // per group: width of tables that are still being built (tableBuilder)
     bool sparseB_ = false;             // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
     uint64_t nB_ = 0;
     bool bgTables_ = false;
@@ -1831,10 +1884,9 @@ private:
     std::vector<GraphSlot> graphs_;
     std::vector<std::pair<const ug_dvec*, int>> warm_;
     bool statsOn_ = false;
-    ug_dvec *wBatch_ = nullptr, *hBatch_ = nullptr, *wBBatch_ = nullptr;      // batched proofs: V witnesses / h vectors / sparse-B scalars
-    std::mutex batchMutex_;            // one batch call at a time owns them (lock order: batchMutex_ -> witness lease -> proveMutex)
 public:
-    ~Groth16Prover() override { stopTableBuilder(); dropGraphs(); releaseBatch(); }      // (before d_ goes: both refer to its contexts)
+    BatchBuffers batch_;               // batched proofs (declared after d_: it goes first)
+    ~Groth16Prover() override { stopTableBuilder(); dropGraphs(); }      // (before d_ goes: both refer to its contexts)
 };
 
 // =================================================================================================================
@@ -1880,15 +1932,7 @@ public:
     // from the header section and this rank's slices (ug_ultra_groth_prover_create_sharded_slices)
     UltraGrothProver(const void* header, unsigned long long headerSize, const Sources& slices, int device, int rank, int count) {
         if (count < 1 || rank < 0 || rank >= count) throw std::invalid_argument("invalid shard rank / count");
-        std::vector<uint8_t> mini;             // a header-only container, so that the one header parser serves both forms
-        auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) mini.push_back((uint8_t)(v >> (8 * k))); };
-        auto put64 = [&](uint64_t v) { for (int k = 0; k < 8; k++) mini.push_back((uint8_t)(v >> (8 * k))); };
-        mini.insert(mini.end(), {'z', 'k', 'e', 'y'});
-        put32(1); put32(3);
-        put32(1); put64(4); put32(1337);
-        put32(2); put64(headerSize);
-        mini.insert(mini.end(), static_cast<const uint8_t*>(header), static_cast<const uint8_t*>(header) + headerSize);
-        put32(4); put64(0);
+        const std::vector<uint8_t> mini = miniZkey(header, headerSize, 1337);
         BinFile f(mini.data(), mini.size(), "zkey", 1);
         hdr_ = loadZkeyHeader(f, true);
         hdr_.nCoefs = slices.nCoefs;
@@ -1916,18 +1960,13 @@ private:
         if (!src.sliced) {                       // whole sections: step to this rank's slices
             pA += wr_.lo * 64; pB1 += wr_.lo * 64; pB2 += wr_.lo * 128; pRoundC += c1.lo * 64; pFinalC += c2.lo * 64; pH += hr_.lo * 64;
             idx1 += c1.lo * 4; idx2 += c2.lo * 4;
-        } else {                                 // slices: each must hold this rank's range (a short buffer would be read past its end)
+        } else {                                 // slices: each must hold this rank's range
             const uint64_t need[8] = {(wr_.hi - wr_.lo) * 64, (wr_.hi - wr_.lo) * 64, (wr_.hi - wr_.lo) * 128, (c1.hi - c1.lo) * 64,
                                       (c2.hi - c2.lo) * 64, (hr_.hi - hr_.lo) * 64, (c1.hi - c1.lo) * 4, (c2.hi - c2.lo) * 4};
             const uint8_t* ptr[8] = {pA, pB1, pB2, pRoundC, pFinalC, pH, idx1, idx2};
             static const char* const what[8] = {"points_a", "points_b1", "points_b2", "points_round_c", "points_final_c", "points_h",
                                                 "round_indexes", "final_round_indexes"};
-            for (int k = 0; k < 8; k++) {
-                if (need[k] && !ptr[k]) throw std::invalid_argument(std::string("Null ") + what[k] + " slice");
-                if (src.sliceBytes && src.sliceBytes[k] < need[k])
-                    throw std::invalid_argument(std::string(what[k]) + " slice is shorter than this rank's range: " + std::to_string(src.sliceBytes[k]) +
-                                                " bytes, needed " + std::to_string(need[k]));
-            }
+            checkSlices(what, need, ptr, src.sliceBytes, 8);
             if (src.haveCoefs && !src.coefs && src.nCoefs) throw std::invalid_argument("Null coefficient records");
         }
         roundIdx_.resize(c1.hi - c1.lo); finalIdx_.resize(c2.hi - c2.lo);
@@ -1999,29 +2038,24 @@ public:
         const uint64_t nw = wr_.hi - wr_.lo;
         if (d_.G) { groups[0].g1 = {d_.G}; groups[0].n1 = {2 * nw}; } else { groups[0].g1 = {d_.A, d_.B1}; groups[0].n1 = {nw, nw}; }
         groups[0].g2 = {d_.B2}; groups[0].n2 = {nw};
-        groups[0].scalars = nw; groups[0].c = &tableW_; groups[0].stride = &strideW_;
-        groups[1].g1 = {d_.roundC}; groups[1].n1 = {roundIdx_.size()}; groups[1].scalars = roundIdx_.size(); groups[1].c = &tableC1_;
-        groups[2].g1 = {d_.C}; groups[2].n1 = {finalIdx_.size()}; groups[2].scalars = finalIdx_.size(); groups[2].c = &tableC2_;
-        groups[3].g1 = {d_.H}; groups[3].n1 = {hr_.hi - hr_.lo}; groups[3].scalars = hr_.hi - hr_.lo; groups[3].c = &tableH_;
-        groups[1].stride = &strideC1_; groups[2].stride = &strideC2_; groups[3].stride = &strideH_;
+        groups[0].scalars = nw; groups[0].plan = &planW_;
+        groups[1].g1 = {d_.roundC}; groups[1].n1 = {roundIdx_.size()}; groups[1].scalars = roundIdx_.size(); groups[1].plan = &planC1_;
+        groups[2].g1 = {d_.C}; groups[2].n1 = {finalIdx_.size()}; groups[2].scalars = finalIdx_.size(); groups[2].plan = &planC2_;
+        groups[3].g1 = {d_.H}; groups[3].n1 = {hr_.hi - hr_.lo}; groups[3].scalars = hr_.hi - hr_.lo; groups[3].plan = &planH_;
         if (sparseB_) {               // A alone over the witness schedule; B1 and B2 compacted, with a schedule of their own
             groups[0].g1 = {d_.A}; groups[0].n1 = {nw};
             groups[0].g2.clear(); groups[0].n2.clear();
             groups.resize(5);
             groups[4].g1 = {d_.Bc1}; groups[4].n1 = {nB_};
             groups[4].g2 = {d_.Bc2}; groups[4].n2 = {nB_};
-            groups[4].scalars = nB_; groups[4].c = &d_.tableB; groups[4].stride = &d_.strideB;
+            groups[4].scalars = nB_; groups[4].plan = &d_.planB;
         }
         return groups;
     }
     void trimWorkspaces() override {
-        std::lock_guard<std::mutex> batch(batchMutex_);     // (a batch call owns the batch buffers it stages into)
+        std::lock_guard<std::mutex> batch(batch_.mutex);    // (a batch call owns the batch buffers it stages into)
         std::lock_guard<std::mutex> turn(proveMutex);
-        ug_schedule_trim(d_.sw); ug_schedule_trim(d_.sh); ug_schedule_trim(d_.saux);
-        if (d_.sB) ug_schedule_trim(d_.sB);
-        ug_ctx_trim(d_.ctx); ug_ctx_trim(d_.ctx2);
-        witness_.trim(wCur_);
-        releaseBatch();
+        trimDeviceWorkspaces(d_, witness_, wCur_, batch_);
     }
 
     const ZkeyHeader& header() const { return hdr_; }
@@ -2114,7 +2148,7 @@ public:
         if (!witnessLoaded_) throw std::invalid_argument("no witness loaded");
         ugCheck(ug_dvec_gather_index(d_.aux, wCur_, d_.roundIdx));
         mark("round gather");
-        buildSchedule(d_.saux, d_.aux, 0, roundIdx_.size(), tableC1_, strideC1_);
+        buildSchedule(d_.saux, d_.aux, 0, roundIdx_.size(), planC1_.c, planC1_.stride);
         ugCheck(ug_msm_g1(d_.ctx, d_.roundC, d_.saux, 0, out64));
         mark("round MSM");
     }
@@ -2158,13 +2192,13 @@ public:
         if (!committed_) throw std::invalid_argument("the round commitment has not been applied");
         if (witnessQueued_) throw std::invalid_argument("witness products are queued on this prover (ug_groth16_prover_witness_msm_end)");
         memset(partials, 0, UG_GROTH16_PARTIALS_SIZE);
-        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, tableW_, strideW_);
+        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, planW_.c, planW_.stride);
         enqueueWitnessProducts(d_, d_.ctx, d_.sw, partials, partials + 64, partials + 128, nullptr, 0, false, wCur_);      // MSM1-3 :201,214,227
         ugCheck(ug_ctx_collect(d_.ctx));
         mark("A, B1, B2 MSMs");
         ugCheck(ug_dvec_gather_index(d_.aux, wCur_, d_.finalIdx));                           // :439-445
         mark("final gather");
-        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), tableC2_, strideC2_);
+        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), planC2_.c, planC2_.stride);
         ugCheck(ug_msm_g1(d_.ctx, d_.C, d_.saux, 0, partials + 256));                       // MSM4 :234
         mark("C MSM");
     }
@@ -2194,10 +2228,10 @@ public:
     }
     // MSM1-3 (:201,214,227), the gather of the final witnesses (:439-445) and MSM4 (:234), queued on the witness stream
     void queueFinalRoundProducts(uint8_t* sums) {
-        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, tableW_, strideW_);
+        buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, planW_.c, planW_.stride);
         enqueueWitnessProducts(d_, d_.ctx, d_.sw, sums, sums + 64, sums + 128, nullptr, 0, false, wCur_);
         ugCheck(ug_dvec_gather_index(d_.aux, wCur_, d_.finalIdx));
-        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), tableC2_, strideC2_);
+        buildSchedule(d_.saux, d_.aux, 0, finalIdx_.size(), planC2_.c, planC2_.stride);
         const ug_bases* setC[1] = {d_.C};
         void* outC[1] = {sums + 256};
         ugCheck(ug_msm_batch_enqueue(d_.ctx, 1, setC, d_.saux, nullptr, outC));
@@ -2230,7 +2264,7 @@ public:
     // MSM5 (:322) on this rank's slice of h (which must be in d_.h); only the H record of partials is written
     void runHMsm(uint8_t* partials) override {
         memset(partials, 0, UG_GROTH16_PARTIALS_SIZE);
-        buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, tableH_, strideH_);
+        buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, planH_.c, planH_.stride);
         ugCheck(ug_msm_g1(d_.ctx2, d_.H, d_.sh, 0, partials + 320));
         mark("H MSM");
         collectTimings(witnessQueued_ == 1 ? 2 : 3);          // (queued witness products: their stream is read when they are collected)
@@ -2331,7 +2365,7 @@ public:
             const char* ov = getenv("ULTRAGROTH_OVERLAP");
             if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));      // (default: beside, as for Groth16)
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));
-            buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, tableH_, strideH_);
+            buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, planH_.c, planH_.stride);
             const ug_bases* setH[1] = {d_.H};
             void* outH[1] = {sums + 320};
             ugCheck(ug_msm_batch_enqueue(d_.ctx2, 1, setH, d_.sh, nullptr, outH));
@@ -2344,73 +2378,68 @@ public:
     }
 
     // ---- batched proofs (ug_groth16_prover_prove_batch) ----
-    // As Groth16Prover::proveBatch: every witness is parsed and checked first -- also its lookup lists, which a single proof
-    // checks only when it completes the lookup -- so a bad one fails the call before anything is queued. Each device pass
-    // then takes up to batchPerPass witnesses under the prover's turn (runBatch). The blinding of the whole call is drawn in
-    // witness order, rk, r, s per witness, a pass's scalars up front. A pass of one witness is the single-proof path; ranks
-    // of a sharded prover and registry circuits prove one after the other (ProverBase::proveBatch).
+    // As Groth16Prover::proveBatch, proveBatchInPasses with these parts. Parsing also checks a witness's lookup lists, which a
+    // single proof checks only when it completes the lookup. The blinding of the whole call is drawn in witness order, rk, r, s
+    // per witness, a pass's scalars up front. Ranks of a sharded prover and registry circuits prove one after the other
+    // (ProverBase::proveBatch).
+    struct BatchCall {
+        const void* const* wtns; const unsigned long long* sizes;
+        std::vector<std::string>& proofs; std::vector<std::string>& pubs;
+        std::vector<StagedWitness> in;             // the lists and public signals of every .uwtns (publicPart receives the lookup writes)
+        std::vector<const uint8_t*> signals;       // ... and its signals, in the caller's buffer
+        double msm = 0, fft = 0;
+    };
+    struct BatchPass {                             // (terms last: the host threads join before what they read goes)
+        std::vector<uint8_t> r, s, sums, commits;
+        std::vector<std::array<u32, 8>> rkw;
+        std::vector<std::future<HostTerms>> terms;
+    };
     void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
                     std::vector<std::string>& pubs) override {
         if (!batchable_ || !haveHpoly_) { ProverBase::proveBatch(k, wtns, sizes, proofs, pubs); return; }
-        auto t0 = std::chrono::steady_clock::now();
-        std::vector<StagedWitness> in((size_t)k);
-        std::vector<const uint8_t*> signals((size_t)k);
-        for (int b = 0; b < k; b++) {
-            const std::string at = "witness " + std::to_string(b) + ": ";
-            try {
-                signals[(size_t)b] = parseWitness(in[(size_t)b], wtns[b], sizes[b]);
-                checkLookupLists(in[(size_t)b]);
-            } catch (InvalidWitnessLengthException& e) { throw InvalidWitnessLengthException(at + e.what()); }
-            catch (std::exception& e) { throw std::runtime_error(at + e.what()); }
-        }
-        proofs.assign((size_t)k, std::string()); pubs.assign((size_t)k, std::string());
-        // the batch buffers belong to one batch call at a time; a pass's signals are copied into them BEFORE the pass takes the
-        // prover's turn (nothing queued reads them then), so another caller's kernels may run meanwhile
-        std::lock_guard<std::mutex> batchLock(batchMutex_);
-        double msm = 0, fft = 0;
-        for (int b0 = 0; b0 < k;) {
-            int V = 1;
-            {
-                std::lock_guard<std::mutex> turn(proveMutex);       // (allocations only under the turn)
-                V = batchPerPass(k - b0, &in[(size_t)b0]);
-                if (V > 1) reserveBatch(V);
-            }
-            if (V <= 1) {                                   // the single-proof path
-                WitnessLease lease(witness_);
-                stage(*lease, wtns[b0], sizes[b0]);
-                std::lock_guard<std::mutex> turn(proveMutex);
-                proveStaged(*lease, proofs[(size_t)b0], pubs[(size_t)b0]);
-                msm += msmMs_; fft += fftMs_;
-                b0++;
-                continue;
-            }
-            stageBatch(&signals[(size_t)b0], V);
-            std::unique_lock<std::mutex> turn(proveMutex);
-            // S: the pass's blinding, in witness order (round randomness :173, then r and s :345-346), and the multiples of the
-            // deltas that need only them on host threads beside the device work
-            std::vector<uint8_t> rk((size_t)V * 32), r((size_t)V * 32), s((size_t)V * 32);
-            for (int v = 0; v < V; v++) { drawBlinding(&rk[(size_t)v * 32]); drawBlinding(&r[(size_t)v * 32]); drawBlinding(&s[(size_t)v * 32]); }
-            std::vector<std::array<u32, 8>> rkw((size_t)V);
-            for (int v = 0; v < V; v++) memcpy(rkw[(size_t)v].data(), &rk[(size_t)v * 32], 32);
-            std::vector<std::future<HostTerms>> terms;
-            for (int v = 0; v < V; v++)
-                terms.push_back(std::async(std::launch::async, [&, v] { return hostTermsFor(rkw[(size_t)v].data(), &r[(size_t)v * 32], &s[(size_t)v * 32]); }));
-            std::vector<uint8_t> sums((size_t)V * UG_GROTH16_PARTIALS_SIZE), commits((size_t)V * 64);
-            runBatch(V, &in[(size_t)b0], rkw, sums.data(), commits.data());      // (the futures join in their destructors if this throws)
-            msm += msmMs_; fft += fftMs_;
-            turn.unlock();
-            for (int v = 0; v < V; v++)
-                finishWith(&sums[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &r[(size_t)v * 32], &s[(size_t)v * 32], terms[(size_t)v].get(),
-                           &commits[(size_t)v * 64], in[(size_t)(b0 + v)].publicPart, proofs[(size_t)(b0 + v)], pubs[(size_t)(b0 + v)]);
-            b0 += V;
-        }
-        // the call's figures for ug_prover_last_timings, written under the turn as every proof writes them
-        std::lock_guard<std::mutex> turn(proveMutex);
-        msmMs_ = msm; fftMs_ = fft;
-        totalMs_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        BatchCall c{wtns, sizes, proofs, pubs, std::vector<StagedWitness>((size_t)k), std::vector<const uint8_t*>((size_t)k)};
+        proveBatchInPasses(*this, c, k);
     }
+    void parseForBatch(BatchCall& c, int b) const {
+        c.signals[(size_t)b] = parseWitness(c.in[(size_t)b], c.wtns[b], c.sizes[b]);
+        checkLookupLists(c.in[(size_t)b]);
+    }
+    std::unique_lock<std::mutex> takeTurn(bool /*forProof*/) { return std::unique_lock<std::mutex>(proveMutex); }
+    void proveOneOfBatch(BatchCall& c, int b) {
+        WitnessLease lease(witness_);
+        stage(*lease, c.wtns[b], c.sizes[b]);
+        std::lock_guard<std::mutex> turn(proveMutex);
+        proveStaged(*lease, c.proofs[(size_t)b], c.pubs[(size_t)b]);
+        c.msm += msmMs_; c.fft += fftMs_;
+    }
+    void stagePass(const BatchCall& c, int b0, int V) { batch_.stage(d_.ctx, witness_.stageMutex, &c.signals[(size_t)b0], V, hdr_.nVars); }
+    // S: the pass's blinding, in witness order (round randomness :173, then r and s :345-346), and the multiples of the deltas
+    // that need only them on host threads beside the device work
+    BatchPass runPass(BatchCall& c, int b0, int V) {
+        BatchPass p;
+        p.r.resize((size_t)V * 32); p.s.resize((size_t)V * 32); p.rkw.resize((size_t)V);
+        p.sums.resize((size_t)V * UG_GROTH16_PARTIALS_SIZE); p.commits.resize((size_t)V * 64);
+        for (int v = 0; v < V; v++) {
+            uint8_t rk[32];
+            drawBlinding(rk); drawBlinding(&p.r[(size_t)v * 32]); drawBlinding(&p.s[(size_t)v * 32]);
+            memcpy(p.rkw[(size_t)v].data(), rk, 32);
+        }
+        for (int v = 0; v < V; v++) {
+            const u32* rk = p.rkw[(size_t)v].data();                  // (by value: `p` may move when it is returned, its buffers stay)
+            const uint8_t *r = &p.r[(size_t)v * 32], *s = &p.s[(size_t)v * 32];
+            p.terms.push_back(std::async(std::launch::async, [this, rk, r, s] { return hostTermsFor(rk, r, s); }));
+        }
+        runBatch(V, &c.in[(size_t)b0], p.rkw, p.sums.data(), p.commits.data());      // (the futures join in their destructors if this throws)
+        c.msm += msmMs_; c.fft += fftMs_;
+        return p;
+    }
+    void finishPass(BatchCall& c, int b0, int V, BatchPass& p) {
+        for (int v = 0; v < V; v++)
+            finishWith(&p.sums[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &p.r[(size_t)v * 32], &p.s[(size_t)v * 32], p.terms[(size_t)v].get(),
+                       &p.commits[(size_t)v * 64], c.in[(size_t)(b0 + v)].publicPart, c.proofs[(size_t)(b0 + v)], c.pubs[(size_t)(b0 + v)]);
+    }
+    void setBatchTimings(double msm, double fft, double total) { msmMs_ = msm; fftMs_ = fft; totalMs_ = total; }
 
-private:
     // what ug_dvec_apply_lookup refuses, found before anything is queued (its messages, in its order)
     void checkLookupLists(const StagedWitness& w) const {
         const uint64_t L = w.freq.size(), total = 1 + w.chunks.size() + 2 * L;
@@ -2421,33 +2450,22 @@ private:
     static ug_lookup_lists listsOf(const StagedWitness& w) {
         return ug_lookup_lists{w.freq.data(), w.freq.size(), w.chunks.data(), w.chunks.size(), w.wIdx.data(), w.pIdx.data(), w.wIdx.size()};
     }
-    // witnesses per device pass for the next `requested` of a call (proveMutex held): ug_plan_proof_batch_aux over the five
-    // schedules, with the gathered aux scalars and the lookup staging counted per witness
-    int batchPerPass(int requested, const StagedWitness* next) {
-        const uint64_t nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo, nC1 = roundIdx_.size(), nC2 = finalIdx_.size();
-        if (requested <= 1 || !nC1 || !nC2 || !nw || !nh) return 1;
-        std::vector<ug_batch_schedule> sch;
-        sch.push_back(ug_batch_schedule{nw, tableW_, strideW_});
-        sch.push_back(ug_batch_schedule{nC1, tableC1_, strideC1_});
-        sch.push_back(ug_batch_schedule{nC2, tableC2_, strideC2_});
-        sch.push_back(ug_batch_schedule{nh, tableH_, strideH_});
-        if (sparseB_) sch.push_back(ug_batch_schedule{nB_, d_.tableB, d_.strideB});
+    // witnesses per device pass for the next `requested` of a call, from witness b0 on (proveMutex held): ug_plan_proof_batch_aux
+    // over the five schedules, with the gathered aux scalars and the lookup staging counted per witness
+    int perPass(const BatchCall& c, int requested, int b0) {
+        const uint64_t nC1 = roundIdx_.size(), nC2 = finalIdx_.size();
+        if (requested <= 1 || !nC1 || !nC2 || wr_.hi == wr_.lo || hr_.hi == hr_.lo) return 1;
+        const std::vector<ug_batch_schedule> sch = batchSchedules();
         uint64_t freeB = 0, totalB = 0;
         ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
-        for (ug_dvec* v : {wBatch_, hBatch_, auxBatch_, wBBatch_}) if (v) freeB += ug_dvec_size(v) * 32;      // (reused or replaced)
-        // window tables that are not in use yet keep their room (none today: this prover builds its tables at create)
-        uint64_t pending = 0;
-        for (int g = 0; g < 5; g++) {
-            int c = 0, st = 0, ready = 1;
-            uint64_t bytes = 0;
-            if (tablePlan(g, &c, &st, &bytes, &ready) && !ready) pending += bytes;
-        }
+        freeB += batch_.bytesHeld();                                  // (reused or replaced)
+        const uint64_t pending = pendingTableBytes();                 // (none today: this prover builds its tables at create)
         freeB = freeB > pending ? freeB - pending : 0;
         // per witness beyond the signal and h vectors: the larger of the two gathered sets (one aux buffer serves both rounds),
         // the sparse-B scalars, and the lookup call's staging and scratch (the largest lists among the witnesses to come)
         uint64_t lookup = 0;
         for (int v = 0; v < requested; v++) {
-            const ug_lookup_lists l = listsOf(next[v]);
+            const ug_lookup_lists l = listsOf(c.in[(size_t)(b0 + v)]);
             lookup = std::max(lookup, ug_lookup_vectors_bytes(hdr_.nVars, &l, 1));
         }
         const uint64_t aux = (std::max(nC1, nC2) + nB_) * 32 + lookup;
@@ -2455,33 +2473,12 @@ private:
         if (V < 1) throw std::logic_error("batch plan failed");
         return V;
     }
-    void ensureBatch(ug_dvec*& v, ug_ctx* ctx, uint64_t n) {
-        if (v && ug_dvec_size(v) >= n) return;
-        ug_dvec_destroy(v); v = nullptr;
-        ugCheck(ug_dvec_create(ctx, n, &v));
-    }
-    void releaseBatch() {
-        for (ug_dvec** v : {&wBatch_, &hBatch_, &auxBatch_, &wBBatch_}) { ug_dvec_destroy(*v); *v = nullptr; }
-    }
     // the batch buffers for V witnesses (proveMutex held: an allocation may not happen while kernels of a proof are queued)
     void reserveBatch(int V) {
-        ensureBatch(wBatch_, d_.ctx, (uint64_t)V * hdr_.nVars);
-        ensureBatch(hBatch_, d_.ctx2, (uint64_t)V * hdr_.domainSize);
-        ensureBatch(auxBatch_, d_.ctx, (uint64_t)V * std::max(roundIdx_.size(), finalIdx_.size()));
-        if (d_.Bc2) ensureBatch(wBBatch_, d_.ctx, (uint64_t)V * nB_);
-    }
-    // the V signal vectors into the batch witness buffer, on the uploader's own streams (batchMutex_ held, no turn: the last pass
-    // that read the buffer has been collected)
-    void stageBatch(const uint8_t* const* signals, int V) {
-        std::lock_guard<std::mutex> st(witness_.stageMutex);
-        const uint64_t nv = hdr_.nVars;
-        for (int v = 0; v < V; v++) {
-            ug_dvec* view = nullptr;
-            ugCheck(ug_dvec_wrap(d_.ctx, (uint8_t*)ug_dvec_device_ptr(wBatch_) + (uint64_t)v * nv * 32, nv, &view));
-            const int rc = ug_dvec_upload_idle(view, signals[v], nv);
-            ug_dvec_destroy(view);
-            ugCheck(rc);
-        }
+        BatchBuffers::ensure(batch_.w, d_.ctx, (uint64_t)V * hdr_.nVars);
+        BatchBuffers::ensure(batch_.h, d_.ctx2, (uint64_t)V * hdr_.domainSize);
+        BatchBuffers::ensure(batch_.aux, d_.ctx, (uint64_t)V * std::max(roundIdx_.size(), finalIdx_.size()));
+        if (d_.Bc2) BatchBuffers::ensure(batch_.wB, d_.ctx, (uint64_t)V * nB_);
     }
     // One device pass of the V staged witnesses (proveMutex held). sums = V blocks A | B1 | B2 | C | H as a single proof leaves
     // them, commits = the V blinded round commitments (pi_r); in[v].publicPart receives witness v's lookup writes.
@@ -2491,19 +2488,13 @@ private:
         ugCheck(ug_ctx_timings(d_.ctx, nullptr, nullptr, 1)); ugCheck(ug_ctx_timings(d_.ctx2, nullptr, nullptr, 1));
         std::vector<uint8_t> outR((size_t)V * 64), outA((size_t)V * 64), outB1((size_t)V * 64), outB2((size_t)V * 128), outC((size_t)V * 64),
             outH((size_t)V * 64);
-        std::vector<ug_dvec*> views;
-        struct Views { std::vector<ug_dvec*>& v; ~Views() { for (ug_dvec* x : v) ug_dvec_destroy(x); } } viewsGuard{views};
-        auto view = [&](ug_ctx* ctx, ug_dvec* of, uint64_t first, uint64_t n) {
-            views.push_back(nullptr);
-            ugCheck(ug_dvec_wrap(ctx, (uint8_t*)ug_dvec_device_ptr(of) + first * 32, n, &views.back()));
-            return views.back();
-        };
+        BatchBuffers::DeviceViews views;
         std::vector<ug_dvec*> wv((size_t)V);
-        for (int v = 0; v < V; v++) wv[(size_t)v] = view(d_.ctx, wBatch_, (uint64_t)v * nv, nv);
+        for (int v = 0; v < V; v++) wv[(size_t)v] = views.view(d_.ctx, batch_.w, (uint64_t)v * nv, nv);
         QueueGuard inFlight(d_.ctx, d_.ctx2);
         // round 1 (execute_round :161-184): V gathers of the round set, ONE schedule over them, ONE product -> V records
-        for (int v = 0; v < V; v++) ugCheck(ug_dvec_gather_index_at(auxBatch_, (uint64_t)v * nC1, wv[(size_t)v], d_.roundIdx));
-        ugCheck(ug_schedule_build_vectors(d_.saux, auxBatch_, 0, nC1, V, nC1, tableC1_, strideC1_));
+        for (int v = 0; v < V; v++) ugCheck(ug_dvec_gather_index_at(batch_.aux, (uint64_t)v * nC1, wv[(size_t)v], d_.roundIdx));
+        ugCheck(ug_schedule_build_vectors(d_.saux, batch_.aux, 0, nC1, V, nC1, planC1_.c, planC1_.stride));
         {
             const ug_bases* set[1] = {d_.roundC};
             void* out[1] = {outR.data()};
@@ -2537,7 +2528,7 @@ private:
                 tables.emplace_back((2 * in[v].freq.size() + 1) * 32);
                 tablePtrs.push_back(tables.back().data());
             }
-        ugCheck(ug_dvec_complete_lookup_vectors(wBatch_, nv, V, rands.data(), lists.data(), needTables ? tablePtrs.data() : nullptr));
+        ugCheck(ug_dvec_complete_lookup_vectors(batch_.w, nv, V, rands.data(), lists.data(), needTables ? tablePtrs.data() : nullptr));
         for (int v = 0; v < V; v++) {                     // the same writes for the public signals, in order (applyLookup)
             const StagedWitness& w = in[v];
             const uint64_t Cn = w.chunks.size();
@@ -2550,10 +2541,10 @@ private:
         }
         // final round (execute_final_round :187-399): MSM1-3 over ONE V-vector witness schedule, V gathers of the final set and
         // MSM4 over ONE schedule, the FFT block per witness into V slices of the h buffer, MSM5 over ONE schedule; one host wait
-        ugCheck(ug_schedule_build_vectors(d_.sw, wBatch_, wr_.lo, nw, V, nv, tableW_, strideW_));
-        enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), nullptr, 0, false, wBatch_, V, nv, wBBatch_);
-        for (int v = 0; v < V; v++) ugCheck(ug_dvec_gather_index_at(auxBatch_, (uint64_t)v * nC2, wv[(size_t)v], d_.finalIdx));
-        ugCheck(ug_schedule_build_vectors(d_.saux, auxBatch_, 0, nC2, V, nC2, tableC2_, strideC2_));
+        ugCheck(ug_schedule_build_vectors(d_.sw, batch_.w, wr_.lo, nw, V, nv, planW_.c, planW_.stride));
+        enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), nullptr, 0, false, batch_.w, V, nv, batch_.wB);
+        for (int v = 0; v < V; v++) ugCheck(ug_dvec_gather_index_at(batch_.aux, (uint64_t)v * nC2, wv[(size_t)v], d_.finalIdx));
+        ugCheck(ug_schedule_build_vectors(d_.saux, batch_.aux, 0, nC2, V, nC2, planC2_.c, planC2_.stride));
         {
             const ug_bases* set[1] = {d_.C};
             void* out[1] = {outC.data()};
@@ -2562,8 +2553,8 @@ private:
         const char* ov = getenv("ULTRAGROTH_OVERLAP");
         if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));          // (default: beside, as a single proof)
         for (int v = 0; v < V; v++)
-            ugCheck(ug_hpoly_run(d_.hp, view(d_.ctx2, wBatch_, (uint64_t)v * nv, nv), view(d_.ctx2, hBatch_, (uint64_t)v * dom, dom)));
-        ugCheck(ug_schedule_build_vectors(d_.sh, hBatch_, hr_.lo, nh, V, dom, tableH_, strideH_));
+            ugCheck(ug_hpoly_run(d_.hp, views.view(d_.ctx2, batch_.w, (uint64_t)v * nv, nv), views.view(d_.ctx2, batch_.h, (uint64_t)v * dom, dom)));
+        ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
         {
             const ug_bases* set[1] = {d_.H};
             void* out[1] = {outH.data()};
@@ -2634,8 +2625,7 @@ private:
     u32 rkw_[8] = {0};
     bool witnessLoaded_ = false, committed_ = false, haveRoundScalar_ = false, trace_ = false, haveHpoly_ = true;
     std::chrono::steady_clock::time_point tPhase_;
-    int tableW_ = 0, tableC1_ = 0, tableC2_ = 0, tableH_ = 0;      // fixed-base table widths per schedule group (0: classic)
-    int strideW_ = 1, strideC1_ = 1, strideC2_ = 1, strideH_ = 1;  // ... and their strides
+    TableChoice planW_, planC1_, planC2_, planH_;                  // fixed-base tables per schedule group (the B group's: d_.planB)
     bool sparseB_ = false;             // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
     uint64_t nB_ = 0;
     DeviceProver d_;
@@ -2645,11 +2635,9 @@ private:
     uint8_t queuedParts_[UG_GROTH16_PARTIALS_SIZE] = {};
     bool batchable_ = false;                                       // a created prover on one device (proveBatch)
     // batched proofs: V signal vectors / h vectors / gathered round or final scalars / sparse-B scalars
-    ug_dvec *wBatch_ = nullptr, *hBatch_ = nullptr, *auxBatch_ = nullptr, *wBBatch_ = nullptr;
-    std::mutex batchMutex_;            // one batch call at a time owns them (lock order: batchMutex_ -> witness lease -> proveMutex)
 public:
+    BatchBuffers batch_;                                           // batched proofs (declared after d_: it goes first)
     ug_ctx* ctx2() { return d_.ctx2; }                             // the H branch's context
-    ~UltraGrothProver() override { releaseBatch(); }               // (before d_ goes: the buffers refer to its contexts)
 };
 
 
