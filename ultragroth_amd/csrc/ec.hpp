@@ -74,27 +74,58 @@ template <class F> UG_HD XYZZ<F> xyzz_dbl(const XYZZ<F>& p) {
     return r;
 }
 
-// p + (x2, y2), (x2, y2) affine and not infinity (madd-2008-s), all exceptional cases handled
-template <class F> UG_HD XYZZ<F> xyzz_madd(const XYZZ<F>& p, const F& x2, const F& y2) {
-    if (is_inf(p)) return xyzz_from_affine(x2, y2);
-    F u2 = mulk<8>(x2, p.zz);                       // < 1.1
-    F s2 = mulk<8>(y2, p.zzz);                      // < 1.1
-    F pp_ = sub<7>(u2, p.x);                        // P  < 8.1
-    F rr_ = sub<4>(s2, p.y);                        // R  < 5.1
+// Where the zz / zzz of an accumulating point live. The mixed addition needs them at its two ends only -- for U2, S2 and for
+// the last two products -- so an accumulator may park them outside the register file between the two (msm.hip keeps the G2
+// accumulator's in LDS). A tail gives: is_inf(); zz() / zzz(), the first reads; zz_after(v) / zzz_after(v), the second reads,
+// which a parked tail must not start before v is known (else the value would sit in registers across the whole formula);
+// put(zz, zzz). This one keeps both in registers: every read is the member itself.
+template <class F> struct TailRegs {
+    F zz_, zzz_;
+    UG_HD bool is_inf() const { return limbs_all_zero(zz_); }
+    UG_HD const F& zz() const { return zz_; }
+    UG_HD const F& zzz() const { return zzz_; }
+    UG_HD const F& zz_after(const F&) const { return zz_; }
+    UG_HD const F& zzz_after(const F&) const { return zzz_; }
+    UG_HD void put(const F& zz, const F& zzz) { zz_ = zz; zzz_ = zzz; }
+};
+
+// (x, y, tail) += (x2, y2), (x2, y2) affine and not infinity (madd-2008-s), all exceptional cases handled
+template <class F, class Tail> UG_HD void xyzz_madd_at(F& x, F& y, Tail& tail, const F& x2, const F& y2) {
+    if (tail.is_inf()) { x = x2; y = y2; tail.put(field_one((F*)0), field_one((F*)0)); return; }      // xyzz_from_affine
+    F u2 = mulk<8>(x2, tail.zz());                  // < 1.1
+    F s2 = mulk<8>(y2, tail.zzz());                 // < 1.1
+    F pp_ = sub<7>(u2, x);                          // P  < 8.1
+    F rr_ = sub<4>(s2, y);                          // R  < 5.1
     F pp = sqrk<9>(pp_);                            // PP < 1.92
     F r2 = sqrk<6>(rr_);                            // R^2 < 1.5
     if (is_zero_small(pp)) {
-        if (is_zero_small(r2)) return xyzz_dbl_affine(x2, y2);
-        return xyzz_inf<F>();
+        if (is_zero_small(r2)) {
+            XYZZ<F> d = xyzz_dbl_affine(x2, y2);
+            x = d.x; y = d.y; tail.put(d.zz, d.zzz);
+        } else {
+            x = field_zero((F*)0); y = field_zero((F*)0); tail.put(field_zero((F*)0), field_zero((F*)0));     // xyzz_inf
+        }
+        return;
     }
-    XYZZ<F> r;
     F ppp = mulk<8>(pp_, pp);                       // < 1.52
-    F q = mulk<8>(p.x, pp);                         // < 1.41
-    r.x = sub_b_2c_5q(r2, ppp, q);                  // R^2 - PPP - 2Q + 5q  < 1.5 + 5 = 6.5   (PPP + 2Q < 4.4)
-    F t = sub<7>(q, r.x);                           // < 8.41
-    r.y = mul_subk<9, 2>(rr_, t, p.y, ppp);         // R t - Y PPP, one reduction: < (43 + 46 + 8 + 6)/170 + 1 = 1.6
-    r.zz = mulk<8>(p.zz, pp);
-    r.zzz = mulk<8>(p.zzz, ppp);
+    F q = mulk<8>(x, pp);                           // < 1.41
+    F x3 = sub_b_2c_5q(r2, ppp, q);                 // R^2 - PPP - 2Q + 5q  < 1.5 + 5 = 6.5   (PPP + 2Q < 4.4)
+    F t = sub<7>(q, x3);                            // < 8.41
+    y = mul_subk<9, 2>(rr_, t, y, ppp);             // R t - Y PPP, one reduction: < (43 + 46 + 8 + 6)/170 + 1 = 1.6
+    x = x3;
+    F zz3 = mulk<8>(tail.zz_after(pp), pp);
+    F zzz3 = mulk<8>(tail.zzz_after(ppp), ppp);
+    tail.put(zz3, zzz3);
+}
+
+// p + (x2, y2): the same with every coordinate in registers
+template <class F> UG_HD XYZZ<F> xyzz_madd(const XYZZ<F>& p, const F& x2, const F& y2) {
+    XYZZ<F> r;
+    r.x = p.x; r.y = p.y;
+    TailRegs<F> tail;
+    tail.put(p.zz, p.zzz);
+    xyzz_madd_at(r.x, r.y, tail, x2, y2);
+    r.zz = tail.zz_; r.zzz = tail.zzz_;
     return r;
 }
 

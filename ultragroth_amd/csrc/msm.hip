@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include "dev_common.hpp"
 #include "internal.hpp"
 #include "segmap.hpp"
@@ -49,9 +50,50 @@ constexpr u32 MEDIUM_MAX = 4096;      // up to this many pieces: one wave per bu
 constexpr u32 HEAVY_TASK = 1024;      // pieces summed by one workgroup of the heavy path
 constexpr int CHUNK = 32;             // buckets per running-sum chunk, at most (reduce_chunk)
 
+constexpr int ACC_BLOCK = 256;        // lanes per workgroup of segment_accumulate_kernel
+
+// ---- an accumulator's zz / zzz parked in LDS (the other implementation of ec.hpp's TailRegs) --------------------------
+// Word w of a lane's zz is at slot[w * ACC_BLOCK], its zzz behind the zz: 4-byte accesses a whole wave makes to consecutive
+// words, free of bank conflicts. Every slot is private to its lane, so no barrier is needed and a lane that leaves the kernel
+// early never touches the area. The mixed addition reads each coordinate twice, at its two ends, and holds neither between
+// them: the second reads go through an address the compiler sees only once `v` is known, so it can neither reuse the first
+// read's registers nor start the second read early.
+typedef __attribute__((address_space(3))) u32 lds_u32;
+template <class P> __device__ __forceinline__ void lds_get(Fp<P>& r, const lds_u32* p) {
+#pragma unroll
+    for (int i = 0; i < NL; i++) r.l[i] = p[i * ACC_BLOCK];
+}
+template <class P> __device__ __forceinline__ void lds_get(Fp2<P>& r, const lds_u32* p) { lds_get(r.a, p); lds_get(r.b, p + NL * ACC_BLOCK); }
+template <class P> __device__ __forceinline__ void lds_set(lds_u32* p, const Fp<P>& v) {
+#pragma unroll
+    for (int i = 0; i < NL; i++) p[i * ACC_BLOCK] = v.l[i];
+}
+template <class P> __device__ __forceinline__ void lds_set(lds_u32* p, const Fp2<P>& v) { lds_set(p, v.a); lds_set(p + NL * ACC_BLOCK, v.b); }
+template <class P> __device__ __forceinline__ u32 last_limb(const Fp<P>& v) { return v.l[NL - 1]; }
+template <class P> __device__ __forceinline__ u32 last_limb(const Fp2<P>& v) { return v.b.l[NL - 1]; }
+template <class F> struct TailLds {
+    static constexpr int WORDS = sizeof(F) / sizeof(u32);       // of one coordinate
+    static constexpr int AREA_WORDS = 2 * WORDS * ACC_BLOCK;    // of a workgroup
+    lds_u32* slot;                                              // the workgroup's area + threadIdx.x
+    __device__ __forceinline__ lds_u32* after(const F& v) const {
+        lds_u32* p = slot;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(p) : "v"(last_limb(v)));
+#endif
+        return p;
+    }
+    __device__ __forceinline__ F zz() const { F r; lds_get(r, slot); return r; }
+    __device__ __forceinline__ F zzz() const { F r; lds_get(r, slot + WORDS * ACC_BLOCK); return r; }
+    __device__ __forceinline__ F zz_after(const F& v) const { F r; lds_get(r, after(v)); return r; }
+    __device__ __forceinline__ F zzz_after(const F& v) const { F r; lds_get(r, after(v) + WORDS * ACC_BLOCK); return r; }
+    __device__ __forceinline__ bool is_inf() const { return limbs_all_zero(zz()); }
+    __device__ __forceinline__ void put(const F& zz, const F& zzz) { lds_set(slot, zz); lds_set(slot + WORDS * ACC_BLOCK, zzz); }
+};
+
 // ---- curve configurations -------------------------------------------------------------------------
 struct G1Cfg {
     typedef Fq F;
+    typedef TailRegs<F> AccTail;            // the accumulate kernel's zz / zzz: in registers
     static constexpr int AFF_WORDS = 16, PT_WORDS = 36, BLOCK = 256, ACC_WAVES = 3;      // accumulate kernel: 168 VGPRs, 3 waves/SIMD
     static constexpr bool PREFETCH = true;  // (4 waves at 128 VGPRs without the prefetch registers: 18.1 vs 15.2 ms)
     static __device__ __forceinline__ bool load_affine(const u32* p, F& x, F& y) {
@@ -99,8 +141,10 @@ struct G1Cfg {
 };
 struct G2Cfg {
     typedef Fq2 F;
-    static constexpr int AFF_WORDS = 32, PT_WORDS = 72, BLOCK = 128, ACC_WAVES = 2;      // 256 VGPRs with ~30 spilled registers beat 1 wave/SIMD at 392 (41.5 vs 43.4 ms)
-    static constexpr bool PREFETCH = false; // ... once the 32 prefetch registers are given up; the second wave hides the gather
+    typedef TailLds<F> AccTail;             // the accumulate kernel's zz / zzz: 36 words per lane, 36 KiB of LDS per workgroup
+    static constexpr int AFF_WORDS = 32, PT_WORDS = 72, BLOCK = 128, ACC_WAVES = 2;      // 250 VGPRs, no spills, with zz / zzz in LDS (39.0 ms; 41.2 with them in registers and 30 spilled)
+    static constexpr bool PREFETCH = false; // the second wave hides the gather: the 32 prefetch registers bring 28 spills back (step 132.5 vs 130.9 ms;
+                                            // 1 wave/SIMD with the prefetch: 136.9), profiles/g2_lds_tail_ab.txt
     static __device__ __forceinline__ bool load_affine(const u32* p, F& x, F& y) {
         u32 w[32];
         load8(w, p); load8(w + 8, p + 8); load8(w + 16, p + 16); load8(w + 24, p + 24);
@@ -266,7 +310,7 @@ __global__ __launch_bounds__(1024) void transpose_entries_kernel(const u32* __re
 }
 
 template <class Cfg>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Cfg::ACC_WAVES, Cfg::ACC_WAVES))) void segment_accumulate_kernel(const u32* __restrict__ bases, u64 n_bases, int64_t delta,
+__global__ __launch_bounds__(ACC_BLOCK) __attribute__((amdgpu_waves_per_eu(Cfg::ACC_WAVES, Cfg::ACC_WAVES))) void segment_accumulate_kernel(const u32* __restrict__ bases, u64 n_bases, int64_t delta,
                                                                  const u32* __restrict__ keys, const u32* __restrict__ tkeys,
                                                                  const u32* __restrict__ tvals, const u32* __restrict__ meta, int log_a, int log_b,
                                                                  u32* __restrict__ bucket_pts, u32* __restrict__ slot_pts) {
@@ -283,13 +327,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Cfg::ACC_WA
     u32 cur = tkeys[tbase];
     bool first_run = true;
     const bool start_open = lo > 0 && keys[lo - 1] == cur;
-    XYZZ<F> acc = xyzz_inf<F>();
+    // the accumulator: x, y in registers, zz / zzz where the configuration keeps them
+    F ax = field_zero((F*)0), ay = field_zero((F*)0);
+    typename Cfg::AccTail tail;
+    if constexpr (std::is_same<typename Cfg::AccTail, TailLds<F>>::value) {
+        __shared__ u32 tail_area[TailLds<F>::AREA_WORDS];
+        tail.slot = (lds_u32*)tail_area + threadIdx.x;
+    }
+    tail.put(field_zero((F*)0), field_zero((F*)0));
+    auto store_acc = [&](u32* dst) {
+        XYZZ<F> p;
+        p.x = ax; p.y = ay; p.zz = tail.zz(); p.zzz = tail.zzz();
+        Cfg::to_words(dst, p, 1);
+    };
     // entry = scalar index | table << 27 | sign << 31; table j of a base set starts j * n_bases records in
     const u32 IDX_MASK = (1u << TABLE_INDEX_BITS) - 1;
     auto close_run = [&](u32 key) {                // the previous run ended inside the segment
         u32* dst = (first_run && start_open) ? slot_pts + (size_t)(2 * t) * Cfg::PT_WORDS : bucket_pts + (size_t)cur * Cfg::PT_WORDS;
-        Cfg::to_words(dst, acc, 1);
-        acc = xyzz_inf<F>();
+        store_acc(dst);
+        ax = field_zero((F*)0); ay = field_zero((F*)0);
+        tail.put(field_zero((F*)0), field_zero((F*)0));
         cur = key;
         first_run = false;
     };
@@ -313,7 +370,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Cfg::ACC_WA
                 if (nin) Cfg::load_raw(raw, bases + ((u64)((nval >> TABLE_INDEX_BITS) & 15u) * n_bases + (u64)nidx) * Cfg::AFF_WORDS);
             }
             if (key != cur) close_run(key);
-            if (valid) acc = xyzz_madd(acc, x, y);
+            if (valid) xyzz_madd_at(ax, ay, tail, x, y);
         }
     } else {
         // no prefetch registers: a second resident wave hides the gather instead
@@ -325,7 +382,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Cfg::ACC_WA
                          Cfg::load_affine(bases + ((u64)((val >> TABLE_INDEX_BITS) & 15u) * n_bases + (u64)idx) * Cfg::AFF_WORDS, x, y);
             if (valid && (val >> 31)) y = neg<1>(y);
             if (key != cur) close_run(key);
-            if (valid) acc = xyzz_madd(acc, x, y);
+            if (valid) xyzz_madd_at(ax, ay, tail, x, y);
         }
     }
     const bool end_open = hi < n_valid && keys[hi] == cur;
@@ -333,7 +390,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Cfg::ACC_WA
     if (first_run && start_open) dst = slot_pts + (size_t)(2 * t) * Cfg::PT_WORDS;
     else if (end_open) dst = slot_pts + (size_t)(2 * t + 1) * Cfg::PT_WORDS;
     else dst = bucket_pts + (size_t)cur * Cfg::PT_WORDS;
-    Cfg::to_words(dst, acc, 1);
+    store_acc(dst);
 }
 
 // The same walk for a GROUP of K G1 base sets that are multiplied by the same scalars (A, B1 and C of a Groth16 proof, A and
@@ -1079,7 +1136,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const 
         const int j = live[q];
         int slot = stats ? stats->begin(stream, g.n * g.windows) : -1;
         if (nseg) {
-            hipLaunchKernelGGL(segment_accumulate_kernel<Cfg>, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, stream,
+            hipLaunchKernelGGL(segment_accumulate_kernel<Cfg>, dim3((unsigned)((nseg + ACC_BLOCK - 1) / ACC_BLOCK)), dim3(ACC_BLOCK), 0, stream,
                                bases[j], n_bases[j], delta[j], s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail,
                                ws.bucket_pts + q * bucket_stride, ws.slot_pts + q * slot_stride);
             UG_KERNEL_CHECK();
