@@ -27,6 +27,44 @@ int groth16_verify(const char *proof, const char *inputs, const char *verificati
  * IC_rand; the length error reads "len(inputs) != len(vk.IC)" (src/ultra_groth.cpp:585-587). */
 int ultra_groth_verify(const char *proof, const char *inputs, const char *verification_key, char *error_msg, unsigned long error_msg_maxsize);
 
+/* ---- additions: many proofs under one key --------------------------------------------------------------------------
+ * verdicts[i] is what groth16_verify / ultra_groth_verify returns for (proofs[i], inputs[i], verification_key), with one
+ * exception: small-exponent batching accepts a batch that holds an invalid proof with probability at most 2^-128 (the
+ * proofs are combined with 128-bit scalars drawn from the system's random source for every call, never from the inputs).
+ * One Miller loop per proof and the scalar multiples run on `device` (ultragroth_amd/csrc/pairing.hip); the host adds
+ * three (four) Miller loops and ONE final exponentiation per accepted pass of up to 65536 proofs. A rejected pass is
+ * searched down its tree of partial products, kept from the device pass: two more checks per level and bad proof, and the
+ * single-proof verifier for the at most 16 proofs of a failing node at the bottom.
+ * A proof that does not parse, or whose input count is wrong, gets VERIFIER_ERROR; one with a point off its curve
+ * VERIFIER_INVALID_PROOF, both without a pairing. A proof whose pi_b is on the twist but outside the subgroup of order r
+ * is not batched (the pairing is not bilinear in the scalar there): the single-proof verifier decides, and it decides
+ * every proof when the key itself holds such a point.
+ * device < 0: the same protocol on host threads, no GPU needed.
+ * Returns VERIFIER_ERROR for null arguments, count < 0, a key that does not parse (the single call's messages) or a device
+ * error; verdicts is then untouched. Else VERIFIER_VALID_PROOF when every verdict is, else VERIFIER_INVALID_PROOF with
+ * error_msg = "proof <first bad index>: <reason>". count == 0 is valid. stats may be NULL. */
+typedef struct {
+    unsigned long long batch_checks;   /* final exponentiations of batch equations (1 per accepted pass)              */
+    unsigned long long single_checks;  /* proofs handed to the single-proof verifier                                  */
+    unsigned long long off_subgroup;   /* ... of which because pi_b is outside the subgroup                           */
+    double device_ms, host_ms;         /* wall time of the device passes (uploads and downloads included); the rest   */
+} ug_verify_batch_stats;
+int ug_groth16_verify_batch(int device, int count, const char *const *proofs, const char *const *inputs,
+                            const char *verification_key, int *verdicts, ug_verify_batch_stats *stats,
+                            char *error_msg, unsigned long error_msg_maxsize);
+int ug_ultra_groth_verify_batch(int device, int count, const char *const *proofs, const char *const *inputs,
+                                const char *verification_key, int *verdicts, ug_verify_batch_stats *stats,
+                                char *error_msg, unsigned long error_msg_maxsize);
+/* milliseconds of the last device pass of this process: miller_batch_kernel, the Fq12 tree, the G1 tree */
+void ug_verify_batch_kernel_ms(double ms[3]);
+
+/* Test hooks, live only in a process started with ULTRAGROTH_TEST_HOOKS=1 (else they return 1 and write nothing).
+ * ug_test_verify_batch_trace: for proof `index` of the last batch call, if it was batched, its scalar r (128 bits) and
+ * f = miller(pi_b, r pi_a) as 12 x 9 limbs of 29 bits (canonical, Montgomery radix 2^261). ug_test_miller: the host's
+ * Miller loop of one pair given as zkey records (Montgomery radix 2^256), in the same form. */
+int ug_test_verify_batch_trace(int index, unsigned int scalar[4], unsigned int f[108]);
+int ug_test_miller(const unsigned char g1[64], const unsigned char g2[128], unsigned int f[108]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,35 @@ def ultra_groth_verify(proof, inputs, verification_key):
     return _verify(load().ultra_groth_verify, proof, inputs, verification_key)
 
 
+def _verify_batch(name, proofs, inputs, verification_key, device):
+    import json
+    from ._lib import VerifyBatchStats
+    enc = lambda v: v if isinstance(v, bytes) else (v if isinstance(v, str) else json.dumps(v)).encode()
+    if len(proofs) != len(inputs):
+        raise ValueError("as many inputs as proofs")
+    n = len(proofs)
+    pa = (C.c_char_p * max(n, 1))(*[enc(p) for p in proofs])
+    ia = (C.c_char_p * max(n, 1))(*[enc(p) for p in inputs])
+    verdicts = (C.c_int * max(n, 1))(*([-1] * max(n, 1)))
+    stats, err = VerifyBatchStats(), C.create_string_buffer(512)
+    rc = getattr(load(), name)(device, n, pa, ia, enc(verification_key), verdicts, C.byref(stats), err, 511)
+    if rc == VERIFIER_ERROR:
+        raise VerifierError(err.value.decode(errors="replace"))
+    return list(verdicts[:n]), {f: getattr(stats, f) for f, _ in VerifyBatchStats._fields_}
+
+
+def groth16_verify_batch(proofs, inputs, verification_key, device=0):
+    """ug_groth16_verify_batch (include/verifier.h): many proofs under one key, one Miller loop each on `device` (host threads for
+    device < 0) and one final exponentiation for a batch that holds. Returns (verdicts, stats): verdicts[i] is VERIFIER_VALID_PROOF,
+    VERIFIER_INVALID_PROOF or VERIFIER_ERROR, what groth16_verify says of proof i alone; stats is the call's ug_verify_batch_stats
+    as a dict. VerifierError for a key that does not parse or a device error."""
+    return _verify_batch("ug_groth16_verify_batch", proofs, inputs, verification_key, device)
+
+
+def ultra_groth_verify_batch(proofs, inputs, verification_key, device=0):
+    return _verify_batch("ug_ultra_groth_verify_batch", proofs, inputs, verification_key, device)
+
+
 class _ProverBase:
     _create = _prove = _destroy = _public_size_fn = None
     _proof_size = staticmethod(groth16_proof_size)

@@ -33,7 +33,14 @@ INNER_SYMBOLS = [
     "ug_plan_proof_batch_aux", "ug_fr_lookup_tables", "ug_dvec_apply_lookup_vectors", "ug_dvec_complete_lookup_vectors",
     "ug_lookup_vectors_bytes", "ug_points_check", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
 ]
-VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify"]        # include/verifier.h
+VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/verifier.h
+                    "ug_groth16_verify_batch", "ug_ultra_groth_verify_batch", "ug_verify_batch_kernel_ms",
+                    "ug_test_verify_batch_trace", "ug_test_miller"]
+
+
+class VerifyBatchStats(C.Structure):
+    _fields_ = [("batch_checks", C.c_ulonglong), ("single_checks", C.c_ulonglong), ("off_subgroup", C.c_ulonglong),
+                ("device_ms", C.c_double), ("host_ms", C.c_double)]
 OUTER_SYMBOLS = [
     "groth16_public_size_for_zkey_buf", "ultra_groth_public_size_for_zkey_buf",
     "groth16_public_size_for_zkey_file", "ultra_groth_public_size_for_zkey_file",
@@ -194,8 +201,13 @@ def load():
     L.ug_synth_points.argtypes = [vp, C.c_int, vp, u64, u64, vp]
     L.ug_ctx_timings.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]
     L.ug_ctx_kernel_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), C.c_int]
-    for n in VERIFIER_SYMBOLS:
+    for n in ("groth16_verify", "ultra_groth_verify"):
         getattr(L, n).argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ulong]
+    for n in ("ug_groth16_verify_batch", "ug_ultra_groth_verify_batch"):
+        getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_char_p, vp, vp, C.c_char_p, C.c_ulong]
+    L.ug_verify_batch_kernel_ms.argtypes = [vp]; L.ug_verify_batch_kernel_ms.restype = None
+    L.ug_test_verify_batch_trace.argtypes = [C.c_int, vp, vp]
+    L.ug_test_miller.argtypes = [vp, vp, vp]
     # outer API (include/prover.h)
     for n in ("groth16_public_size_for_zkey_buf", "ultra_groth_public_size_for_zkey_buf"):
         getattr(L, n).argtypes = [vp, ull, pull, vp, ull]

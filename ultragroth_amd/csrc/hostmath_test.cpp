@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include <cstdint>
 #include "ec.hpp"
+#include "pairing.hpp"
 #include "segmap.hpp"
 
 using namespace ug;
@@ -229,6 +230,18 @@ int ugt_segmap_check(uint64_t n_valid, uint64_t total, int log_a, int log_b) {
     if (n_valid > total) return 7;
     if (t > SegMap::max_segments(total, log_a, log_b)) return 8;        // the host's grid / slot bound covers every segment
     if (m.first_entry(t) < n_valid) return 9;
+    return 0;
+}
+
+// pairing.hpp under the range assertions: the Miller loop of one pair (zkey records in; neither may be infinity), the value
+// as 12 x 9 limbs, canonical device form. The lazy column sums of the Fq12 products check their headroom in this build.
+int ugt_miller(uint32_t out[108], const uint8_t g1[64], const uint8_t g2[128]) {
+    static const pr::PairingConsts kc = pr::pairing_consts();
+    Fq x, y; Fq2 qx, qy;
+    if (!g1_load(g1, x, y) || !g2_load(g2, qx, qy)) return 1;
+    const pr::G1A pt{pr::F1{x}, pr::F1{y}, false};
+    const pr::G2A q{pr::F2{pr::F1{qx.a}, pr::F1{qx.b}}, pr::F2{pr::F1{qy.a}, pr::F1{qy.b}}, false};
+    pr::f12_store(out, pr::miller(kc, q, pt));
     return 0;
 }
 

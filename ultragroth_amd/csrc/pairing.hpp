@@ -1,0 +1,265 @@
+// pairing.hpp -- the optimal-ate Miller loop of BN254 on F29 field elements, shared by the host verifier
+// (verifier_api.cpp) and the batch-verification kernels (pairing.hip).
+//
+// Fq12 = Fq[w]/(w^12 - 18 w^6 + 82) as 12 coefficients (u = w^6 - 9), D-type twist (x, y) -> (x w^2, y w^3), Miller loop
+// over 6t+2 with affine G2 steps and the two Frobenius lines at the end: the pairing restated from the definition, see the
+// header comment of verifier_api.cpp. Every value is canonical ([0, q), device Montgomery form), so a result does not depend
+// on where it was computed: the device's f equals the host's limb for limb.
+//
+// The small constants the formulas need (3, 9, 18, 82 and the Frobenius coefficients of the twist) travel in a
+// PairingConsts: a kernel argument on the device, part of consts() on the host.
+#pragma once
+#include "ec.hpp"
+
+namespace ug {
+namespace pr {
+
+// ---- canonical field wrappers (always in [0, q), device Montgomery form) -------------------------------------------
+struct F1 { Fq v; };
+UG_HD F1 f1_zero() { return F1{fp_zero<FqParams>()}; }
+UG_HD F1 f1_one() { return F1{canon(fp_one<FqParams>())}; }
+// sums and differences of canonical values are below 2q, products of canonical values are strict and below 2q:
+// one conditional subtraction restores [0, q)
+UG_HD F1 operator+(const F1& a, const F1& b) { return F1{cond_sub_q(norm_strict(add(a.v, b.v)))}; }
+UG_HD F1 operator-(const F1& a, const F1& b) { return F1{cond_sub_q(norm_strict(sub<1>(a.v, b.v)))}; }
+UG_HD F1 operator*(const F1& a, const F1& b) { return F1{cond_sub_q(mul(a.v, b.v))}; }
+UG_HD F1 operator-(const F1& a) { return F1{cond_sub_q(norm_strict(neg<1>(a.v)))}; }
+UG_HD bool is0(const F1& a) { return limbs_all_zero(a.v); }
+UG_HD bool operator==(const F1& a, const F1& b) {
+    u32 o = 0;
+    for (int i = 0; i < NL; i++) o |= a.v.l[i] ^ b.v.l[i];
+    return o == 0;
+}
+UG_HD F1 f1_inv(const F1& a) { return F1{canon(inv(a.v))}; }
+UG_HD F1 f1_small(u32 k) { u32 w[8] = {k, 0, 0, 0, 0, 0, 0, 0}; return F1{canon(from_normal<FqParams>(w))}; }
+
+struct F2 { F1 a, b; };                                            // a + b u, u^2 = -1
+UG_HD F2 f2_zero() { return F2{f1_zero(), f1_zero()}; }
+UG_HD F2 operator+(const F2& x, const F2& y) { return F2{x.a + y.a, x.b + y.b}; }
+UG_HD F2 operator-(const F2& x, const F2& y) { return F2{x.a - y.a, x.b - y.b}; }
+UG_HD F2 operator-(const F2& x) { return F2{-x.a, -x.b}; }
+UG_HD F2 operator*(const F2& x, const F2& y) { return F2{x.a * y.a - x.b * y.b, x.a * y.b + x.b * y.a}; }
+UG_HD F2 f2_scale(const F2& x, const F1& k) { return F2{x.a * k, x.b * k}; }
+UG_HD F2 f2_conj(const F2& x) { return F2{x.a, -x.b}; }
+UG_HD bool is0(const F2& x) { return is0(x.a) && is0(x.b); }
+UG_HD bool operator==(const F2& x, const F2& y) { return x.a == y.a && x.b == y.b; }
+UG_HD F2 f2_inv(const F2& x) {
+    F1 n = f1_inv(x.a * x.a + x.b * x.b);
+    return F2{x.a * n, -(x.b * n)};
+}
+
+struct PairingConsts {
+    F1 k3, k9, k18, k82;
+    F2 g12, g13;           // xi^((p-1)/3), xi^((p-1)/2)
+    F1 g22, g23;           // xi^((p^2-1)/3), xi^((p^2-1)/2) (both in Fq)
+};
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// the constants on the host: a decimal literal -> value mod q
+inline F1 f1_from_digits(const char* s) {
+    const F1 ten = f1_small(10);
+    F1 acc = f1_zero();
+    for (; *s; s++) acc = acc * ten + f1_small((u32)(*s - '0'));
+    return acc;
+}
+inline PairingConsts pairing_consts() {
+    PairingConsts k;
+    k.k3 = f1_small(3); k.k9 = f1_small(9); k.k18 = f1_small(18); k.k82 = f1_small(82);
+    k.g12 = F2{f1_from_digits("21575463638280843010398324269430826099269044274347216827212613867836435027261"),
+               f1_from_digits("10307601595873709700152284273816112264069230130616436755625194854815875713954")};
+    k.g13 = F2{f1_from_digits("2821565182194536844548159561693502659359617185244120367078079554186484126554"),
+               f1_from_digits("3505843767911556378687030309984248845540243509899259641013678093033130930403")};
+    k.g22 = f1_from_digits("21888242871839275220042445260109153167277707414472061641714758635765020556616");
+    k.g23 = f1_from_digits("21888242871839275222246405745257275088696311157297823662689037894645226208582");
+    return k;
+}
+#endif
+
+// ---- Fq12, 12 coefficients in w ----------------------------------------------------------------------------------------
+struct F12 { F1 c[12]; };
+UG_HD F12 f12_one() { F12 r; for (int i = 0; i < 12; i++) r.c[i] = f1_zero(); r.c[0] = f1_one(); return r; }
+// Products are accumulated lazily: up to 6 limb-column products of canonical operands share one Montgomery reduction
+// ((6 * 9 + 9) * 2^58 < 2^64 per column; 6 q^2 / 2^261 + q < 2q for the value), so a full product costs 144 column
+// products and ~40 reductions instead of 144 of each.
+struct LazySum {
+    u64 c[2 * NL];
+    int terms;
+    F1 total;
+    UG_HD LazySum() : terms(0), total(f1_zero()) { cols_zero(c); }
+    UG_HD void flush() {
+        if (!terms) return;
+        total = total + F1{cond_sub_q(redc<FqParams>(c))};
+        cols_zero(c);
+        terms = 0;
+    }
+    UG_HD void add(const F1& x, const F1& y) {
+        if (terms == 6) flush();
+#if defined(UG_CHECK_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
+        // room for this product's 9 and the reduction's 9 column terms of (2^29 + 16)^2 each
+        for (int k = 0; k < 2 * NL; k++)
+            if (c[k] > ~(u64)0 - 18 * (((u64)1 << LB) + 16) * (((u64)1 << LB) + 16)) { fprintf(stderr, "UG_CHECK_BOUNDS: column overflow in LazySum\n"); abort(); }
+        UG_BOUND(x.v, 1, "LazySum operand");
+        UG_BOUND(y.v, 1, "LazySum operand");
+#endif
+        cols_mul(c, x.v, y.v);
+        terms++;
+    }
+    UG_HD F1 value() { flush(); return total; }
+};
+// The loops over coefficients stay loops on the device (an Fq12 value is 108 words, three of them do not fit the register
+// file beside a column sum): the values live in private memory, the 81 multiply-adds per 18 words read keep that cheap.
+UG_HD F12 f12_reduce(const PairingConsts& kc, F1* t) {            // w^12 = 18 w^6 - 82
+#pragma unroll 1
+    for (int k = 22; k >= 12; k--) {
+        if (is0(t[k])) continue;
+        t[k - 6] = t[k - 6] + kc.k18 * t[k];
+        t[k - 12] = t[k - 12] - kc.k82 * t[k];
+    }
+    F12 r;
+    for (int i = 0; i < 12; i++) r.c[i] = t[i];
+    return r;
+}
+UG_HD F12 f12_mul(const PairingConsts& kc, const F12& a, const F12& b) {
+    bool za[12], zb[12];
+    for (int i = 0; i < 12; i++) { za[i] = is0(a.c[i]); zb[i] = is0(b.c[i]); }
+    F1 t[23];
+#pragma unroll 1
+    for (int k = 0; k < 23; k++) {
+        LazySum sum;
+#pragma unroll 1
+        for (int i = (k > 11 ? k - 11 : 0); i <= (k < 11 ? k : 11); i++)
+            if (!za[i] && !zb[k - i]) sum.add(a.c[i], b.c[k - i]);
+        t[k] = sum.value();
+    }
+    return f12_reduce(kc, t);
+}
+UG_HD F12 f12_sqr(const PairingConsts& kc, const F12& a) {
+    F1 t[23];
+#pragma unroll 1
+    for (int k = 0; k < 23; k++) {
+        LazySum cross;                                              // sum over i < j, i + j = k  (at most 6 pairs)
+#pragma unroll 1
+        for (int i = (k > 11 ? k - 11 : 0); 2 * i < k; i++) cross.add(a.c[i], a.c[k - i]);
+        F1 s = cross.value();
+        t[k] = s + s;
+        if (!(k & 1)) t[k] = t[k] + a.c[k >> 1] * a.c[k >> 1];
+    }
+    return f12_reduce(kc, t);
+}
+// (a + b u) w^k with u = w^6 - 9, added into f
+UG_HD void f12_add_embedded(const PairingConsts& kc, F12& f, const F2& c, int k) {
+    f.c[k] = f.c[k] + (c.a - kc.k9 * c.b);
+    f.c[k + 6] = f.c[k + 6] + c.b;
+}
+
+// ---- curve points, affine with an infinity flag -----------------------------------------------------------------------
+struct G1A { F1 x, y; bool inf; };
+struct G2A { F2 x, y; bool inf; };
+
+UG_HD G2A g2_inf() { return G2A{f2_zero(), f2_zero(), true}; }
+// One Miller step: l = the line through the twist points r and t (the tangent when they are equal) evaluated at the G1
+// point pt, then r <- r + t. Line and sum share the slope, so a step costs one Fq2 inversion.
+UG_HD void miller_step(const PairingConsts& kc, G2A& r, const G2A& t, const G1A& pt, F12& l) {
+    for (int i = 0; i < 12; i++) l.c[i] = f1_zero();
+    F2 m = f2_zero();
+    bool sloped = true, tangent = false;
+    if (!(r.x == t.x)) m = (t.y - r.y) * f2_inv(t.x - r.x);
+    else if (r.y == t.y && !is0(r.y)) { m = f2_scale(r.x * r.x, kc.k3) * f2_inv(r.y + r.y); tangent = true; }
+    else sloped = false;
+    if (sloped) {                                                   // -yP + (m xP) w + (y1 - m x1) w^3
+        l.c[0] = -pt.y;
+        f12_add_embedded(kc, l, f2_scale(m, pt.x), 1);
+        f12_add_embedded(kc, l, r.y - m * r.x, 3);
+    } else {                                                        // vertical: xP - x1 w^2
+        l.c[0] = pt.x;
+        f12_add_embedded(kc, l, -r.x, 2);
+    }
+    if (r.inf) { r = t; return; }
+    if (t.inf) return;
+    if (!sloped) { r = g2_inf(); return; }
+    F2 x = tangent ? m * m - (r.x + r.x) : m * m - r.x - t.x;
+    r = G2A{x, m * (r.x - x) - r.y, false};
+}
+
+constexpr u64 ATE_LOOP_LOW = 0x9d797039be763ba8ull;                 // 6 t + 2 = 2^64 + this = 29793968203157093288
+
+// the Miller function f_{6t+2,Q}(P) times the two Frobenius lines; q and pt are not infinity
+UG_HD F12 miller(const PairingConsts& kc, const G2A& q, const G1A& pt) {
+    F12 f = f12_one();
+    G2A r = q;
+    const G2A q1{f2_conj(q.x) * kc.g12, f2_conj(q.y) * kc.g13, false};
+    const G2A nq2{f2_scale(q.x, kc.g22), -f2_scale(q.y, kc.g23), false};
+    // steps 2j and 2j + 1 are the doubling and the addition of bit 63 - j (bit 64 is the leading one), 128 and 129 the
+    // Frobenius lines: one loop body, so that the device code holds each product once
+#pragma unroll 1
+    for (int s = 0; s < 130; s++) {
+        const bool dbl = s < 128 && !(s & 1);
+        if (s < 128 && (s & 1) && !((ATE_LOOP_LOW >> (63 - (s >> 1))) & 1)) continue;
+        const G2A t = dbl ? r : s < 128 ? q : s == 128 ? q1 : nq2;
+        F12 l;
+        if (dbl) f = f12_sqr(kc, f);
+        miller_step(kc, r, t, pt, l);
+        f = f12_mul(kc, f, l);
+    }
+    return f;
+}
+
+// ---- batch verification (verifier_api.cpp, pairing.hip) ----------------------------------------------------------------
+// Records in memory: an Fq value is its 9 limbs; a G1 point 18 words (x, y; canonical; all zero = infinity), a G2 point 36
+// (x.a, x.b, y.a, y.b), an XYZZ sum 36 (x, y, zz, zzz as ec.hpp leaves them), an Fq12 value 108.
+constexpr int F12_WORDS = 12 * NL, G1_WORDS = 2 * NL, G2_WORDS = 4 * NL, XYZZ_WORDS = 4 * NL;
+
+UG_HD F1 f1_load(const u32* p) { return F1{fp_from<FqParams>(p)}; }
+UG_HD void fq_store(u32* p, const Fq& a) { for (int i = 0; i < NL; i++) p[i] = a.l[i]; }
+UG_HD bool words_all_zero(const u32* p, int n) { u32 o = 0; for (int i = 0; i < n; i++) o |= p[i]; return o == 0; }
+UG_HD void f12_load(F12& f, const u32* p) { for (int i = 0; i < 12; i++) f.c[i] = f1_load(p + i * NL); }
+UG_HD void f12_store(u32* p, const F12& f) { for (int i = 0; i < 12; i++) fq_store(p + i * NL, f.c[i].v); }
+UG_HD G1XYZZ xyzz_load(const u32* p) {
+    G1XYZZ r;
+    r.x = fp_from<FqParams>(p); r.y = fp_from<FqParams>(p + NL); r.zz = fp_from<FqParams>(p + 2 * NL); r.zzz = fp_from<FqParams>(p + 3 * NL);
+    return r;
+}
+UG_HD void xyzz_store(u32* p, const G1XYZZ& v) { fq_store(p, v.x); fq_store(p + NL, v.y); fq_store(p + 2 * NL, v.zz); fq_store(p + 3 * NL, v.zzz); }
+
+// One proof's leaves: f = miller(B, r A) (1 when a point of the pair is infinity, the rule of pairing_check) and r G_s for
+// its k G1 points (C; or pi_f and pi_r). r is 128 bits, 4 words.
+UG_HD void batch_leaf(const PairingConsts& kc, const u32* a, const u32* b, const u32* g, int k, const u32* r, u32* f_out, u32* g_out) {
+    Fq ax = fp_zero<FqParams>(), ay = ax;
+    bool a_live = false;
+#pragma unroll 1
+    for (int s = 0; s <= k; s++) {                                  // s = 0: A, s >= 1: the G1 points -- one copy of the ladder
+        const u32* p = s ? g + (s - 1) * G1_WORDS : a;
+        G1XYZZ acc = xyzz_inf<Fq>();
+        if (!words_all_zero(p, G1_WORDS))
+            acc = xyzz_mul_scalar(xyzz_from_affine(fp_from<FqParams>(p), fp_from<FqParams>(p + NL)), r, 128);
+        if (s) xyzz_store(g_out + (s - 1) * XYZZ_WORDS, acc);
+        else if (!is_inf(acc)) { xyzz_to_affine(ax, ay, acc); a_live = true; }
+    }
+    F12 f = f12_one();
+    if (a_live && !words_all_zero(b, G2_WORDS)) {
+        const G2A q{F2{f1_load(b), f1_load(b + NL)}, F2{f1_load(b + 2 * NL), f1_load(b + 3 * NL)}, false};
+        f = miller(kc, q, G1A{F1{ax}, F1{ay}, false});
+    }
+    f12_store(f_out, f);
+}
+// a node of the product tree: the product of its two children, or the left one alone (right == nullptr: an odd last node)
+UG_HD void f12_node(const PairingConsts& kc, const u32* left, const u32* right, u32* out) {
+    F12 x;
+    f12_load(x, left);
+    if (right) { F12 y; f12_load(y, right); x = f12_mul(kc, x, y); }
+    f12_store(out, x);
+}
+UG_HD void g1_node(const u32* left, const u32* right, u32* out) {
+    G1XYZZ x = xyzz_load(left);
+    if (right) x = xyzz_add(x, xyzz_load(right));
+    xyzz_store(out, x);
+}
+// nodes of the whole tree over n leaves: level 0 has n, each level above half of the one below, rounded up, down to one root
+inline size_t tree_nodes(size_t n) {
+    size_t t = n;
+    while (n > 1) { n = (n + 1) / 2; t += n; }
+    return t;
+}
+
+}  // namespace pr
+}  // namespace ug

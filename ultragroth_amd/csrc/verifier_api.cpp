@@ -15,40 +15,34 @@
 // answer. Final exponentiation: with G = (f^(p^2) f)^((p^4 - p^2 + 1)/r) the full power f^((p^12-1)/r) equals
 // conj(G)/G (conj = the p^6 Frobenius, w -> -w), which is 1 exactly when G lies in Fq6, i.e. when its odd coefficients
 // vanish: one 761-bit exponentiation, no Fq12 inversion.
+#include <sys/random.h>
+#include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <future>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 #include "ec.hpp"
 #include "host_util.hpp"
+#include "pairing.hpp"
+#include "pairing_dev.hpp"
+#include "../../include/ultragroth_hip.h"
 #include "../../include/verifier.h"
 
 using namespace ug;
+using namespace ug::pr;
 using ughost::keccak256;
 
 namespace {
 
-// ---- canonical field wrappers (always in [0, q), device Montgomery form) -------------------------------------------
-struct F1 { Fq v; };
-F1 f1_zero() { return F1{fp_zero<FqParams>()}; }
-F1 f1_one() { return F1{canon(fp_one<FqParams>())}; }
-// sums and differences of canonical values are below 2q, products of canonical values are strict and below 2q:
-// one conditional subtraction restores [0, q)
-F1 operator+(const F1& a, const F1& b) { return F1{cond_sub_q(norm_strict(add(a.v, b.v)))}; }
-F1 operator-(const F1& a, const F1& b) { return F1{cond_sub_q(norm_strict(sub<1>(a.v, b.v)))}; }
-F1 operator*(const F1& a, const F1& b) { return F1{cond_sub_q(mul(a.v, b.v))}; }
-F1 operator-(const F1& a) { return F1{cond_sub_q(norm_strict(neg<1>(a.v)))}; }
-bool is0(const F1& a) { return limbs_all_zero(a.v); }
-bool operator==(const F1& a, const F1& b) {
-    for (int i = 0; i < NL; i++) if (a.v.l[i] != b.v.l[i]) return false;
-    return true;
-}
-F1 f1_inv(const F1& a) { return F1{canon(inv(a.v))}; }
-F1 f1_small(u32 k) { u32 w[8] = {k, 0, 0, 0, 0, 0, 0, 0}; return F1{canon(from_normal<FqParams>(w))}; }
-
+// ---- field wrappers, Fq12, G2 steps and the Miller loop: pairing.hpp (shared with the device) -------------------------
 // decimal string -> value mod q (E.f1.fromString); anything but digits is an error
 F1 f1_from_decimal(const std::string& s) {
     if (s.empty()) throw std::invalid_argument("not a number");
@@ -62,170 +56,22 @@ F1 f1_from_decimal(const std::string& s) {
 }
 void f1_to_plain(u32 out[8], const F1& a) { to_normal(out, a.v); }
 
-struct F2 { F1 a, b; };                                            // a + b u, u^2 = -1
-F2 f2_zero() { return F2{f1_zero(), f1_zero()}; }
-F2 operator+(const F2& x, const F2& y) { return F2{x.a + y.a, x.b + y.b}; }
-F2 operator-(const F2& x, const F2& y) { return F2{x.a - y.a, x.b - y.b}; }
-F2 operator-(const F2& x) { return F2{-x.a, -x.b}; }
-F2 operator*(const F2& x, const F2& y) { return F2{x.a * y.a - x.b * y.b, x.a * y.b + x.b * y.a}; }
-F2 f2_scale(const F2& x, const F1& k) { return F2{x.a * k, x.b * k}; }
-F2 f2_conj(const F2& x) { return F2{x.a, -x.b}; }
-bool is0(const F2& x) { return is0(x.a) && is0(x.b); }
-bool operator==(const F2& x, const F2& y) { return x.a == y.a && x.b == y.b; }
-F2 f2_inv(const F2& x) {
-    F1 n = f1_inv(x.a * x.a + x.b * x.b);
-    return F2{x.a * n, -(x.b * n)};
-}
-
-// ---- Fq12, 12 coefficients in w ----------------------------------------------------------------------------------------
-struct F12 { F1 c[12]; };
-F12 f12_one() { F12 r; for (auto& x : r.c) x = f1_zero(); r.c[0] = f1_one(); return r; }
-// Products are accumulated lazily: up to 6 limb-column products of canonical operands share one Montgomery reduction
-// ((6 * 9 + 9) * 2^58 < 2^64 per column; 6 q^2 / 2^261 + q < 2q for the value), so a full product costs 144 column
-// products and ~40 reductions instead of 144 of each.
-struct LazySum {
-    u64 c[2 * NL];
-    int terms = 0;
-    F1 total = f1_zero();
-    LazySum() { cols_zero(c); }
-    void flush() {
-        if (!terms) return;
-        total = total + F1{cond_sub_q(redc<FqParams>(c))};
-        cols_zero(c);
-        terms = 0;
-    }
-    void add(const F1& x, const F1& y) {
-        if (terms == 6) flush();
-        cols_mul(c, x.v, y.v);
-        terms++;
-    }
-    F1 value() { flush(); return total; }
-};
-F12 f12_reduce(F1* t) {                                            // w^12 = 18 w^6 - 82
-    static const F1 k18 = f1_small(18), k82 = f1_small(82);
-    for (int k = 22; k >= 12; k--) {
-        if (is0(t[k])) continue;
-        t[k - 6] = t[k - 6] + k18 * t[k];
-        t[k - 12] = t[k - 12] - k82 * t[k];
-    }
-    F12 r;
-    for (int i = 0; i < 12; i++) r.c[i] = t[i];
-    return r;
-}
-F12 f12_mul(const F12& a, const F12& b) {
-    bool za[12], zb[12];
-    for (int i = 0; i < 12; i++) { za[i] = is0(a.c[i]); zb[i] = is0(b.c[i]); }
-    F1 t[23];
-    for (int k = 0; k < 23; k++) {
-        LazySum sum;
-        for (int i = (k > 11 ? k - 11 : 0); i <= (k < 11 ? k : 11); i++)
-            if (!za[i] && !zb[k - i]) sum.add(a.c[i], b.c[k - i]);
-        t[k] = sum.value();
-    }
-    return f12_reduce(t);
-}
-F12 f12_sqr(const F12& a) {
-    F1 t[23];
-    for (int k = 0; k < 23; k++) {
-        LazySum cross;                                              // sum over i < j, i + j = k  (at most 6 pairs)
-        for (int i = (k > 11 ? k - 11 : 0); 2 * i < k; i++) cross.add(a.c[i], a.c[k - i]);
-        F1 s = cross.value();
-        t[k] = s + s;
-        if (!(k & 1)) t[k] = t[k] + a.c[k >> 1] * a.c[k >> 1];
-    }
-    return f12_reduce(t);
-}
-// (a + b u) w^k with u = w^6 - 9, added into f
-void f12_add_embedded(F12& f, const F2& c, int k) {
-    static const F1 k9 = f1_small(9);
-    f.c[k] = f.c[k] + (c.a - k9 * c.b);
-    f.c[k + 6] = f.c[k + 6] + c.b;
-}
-
-// ---- curve points, affine with an infinity flag -----------------------------------------------------------------------
-struct G1A { F1 x, y; bool inf; };
-struct G2A { F2 x, y; bool inf; };
-
 bool g1_on_curve(const G1A& p) { return p.inf || p.y * p.y == p.x * p.x * p.x + f1_small(3); }
 bool g2_on_curve(const G2A& q) {
     if (q.inf) return true;
     static const F2 b = f2_scale(f2_inv(F2{f1_small(9), f1_small(1)}), f1_small(3));     // 3 / (9 + u)
     return q.y * q.y == q.x * q.x * q.x + b;
 }
-G2A g2_dbl(const G2A& p) {
-    if (p.inf || is0(p.y)) return G2A{f2_zero(), f2_zero(), true};
-    F2 m = f2_scale(p.x * p.x, f1_small(3)) * f2_inv(p.y + p.y);
-    F2 x = m * m - (p.x + p.x);
-    return G2A{x, m * (p.x - x) - p.y, false};
-}
-G2A g2_add(const G2A& p, const G2A& q) {
-    if (p.inf) return q;
-    if (q.inf) return p;
-    if (p.x == q.x) {
-        if (p.y == q.y) return g2_dbl(p);
-        return G2A{f2_zero(), f2_zero(), true};
-    }
-    F2 m = (q.y - p.y) * f2_inv(q.x - p.x);
-    F2 x = m * m - p.x - q.x;
-    return G2A{x, m * (p.x - x) - p.y, false};
-}
-// line through the twist points t1, t2 (tangent when equal), evaluated at the G1 point pt
-F12 line(const G2A& t1, const G2A& t2, const G1A& pt) {
-    F12 f;
-    for (auto& x : f.c) x = f1_zero();
-    F2 m;
-    if (!(t1.x == t2.x)) m = (t2.y - t1.y) * f2_inv(t2.x - t1.x);
-    else if (t1.y == t2.y && !is0(t1.y)) m = f2_scale(t1.x * t1.x, f1_small(3)) * f2_inv(t1.y + t1.y);
-    else {                                                          // vertical: xP - x1 w^2
-        f.c[0] = pt.x;
-        f12_add_embedded(f, -t1.x, 2);
-        return f;
-    }
-    f.c[0] = -pt.y;                                                 // -yP + (m xP) w + (y1 - m x1) w^3
-    f12_add_embedded(f, f2_scale(m, pt.x), 1);
-    f12_add_embedded(f, t1.y - m * t1.x, 3);
-    return f;
-}
 
-struct Consts {
-    F2 g12, g13;           // xi^((p-1)/3), xi^((p-1)/2)
-    F1 g22, g23;           // xi^((p^2-1)/3), xi^((p^2-1)/2) (both in Fq)
+struct Consts : PairingConsts {
     F1 gamma[12];          // gamma^k, gamma = 82^((p-1)/6): the p^2 Frobenius maps w^k to gamma^k w^k
-    Consts() {
-        g12 = F2{f1_from_decimal("21575463638280843010398324269430826099269044274347216827212613867836435027261"),
-                 f1_from_decimal("10307601595873709700152284273816112264069230130616436755625194854815875713954")};
-        g13 = F2{f1_from_decimal("2821565182194536844548159561693502659359617185244120367078079554186484126554"),
-                 f1_from_decimal("3505843767911556378687030309984248845540243509899259641013678093033130930403")};
-        g22 = f1_from_decimal("21888242871839275220042445260109153167277707414472061641714758635765020556616");
-        g23 = f1_from_decimal("21888242871839275222246405745257275088696311157297823662689037894645226208582");
+    Consts() : PairingConsts(pairing_consts()) {
         F1 g = f1_from_decimal("21888242871839275220042445260109153167277707414472061641714758635765020556617");
         gamma[0] = f1_one();
         for (int k = 1; k < 12; k++) gamma[k] = gamma[k - 1] * g;
     }
 };
 const Consts& consts() { static const Consts c; return c; }
-
-constexpr unsigned __int128 ATE_LOOP = ((unsigned __int128)1 << 64) + 0x9d797039be763ba8ull;       // 6 t + 2 = 29793968203157093288
-
-F12 miller(const G2A& q, const G1A& pt) {
-    const Consts& k = consts();
-    F12 f = f12_one();
-    G2A r = q;
-    for (int i = 63; i >= 0; i--) {                                 // bit 64 is the leading one
-        f = f12_mul(f12_sqr(f), line(r, r, pt));
-        r = g2_dbl(r);
-        if ((ATE_LOOP >> i) & 1) {
-            f = f12_mul(f, line(r, q, pt));
-            r = g2_add(r, q);
-        }
-    }
-    G2A q1{f2_conj(q.x) * k.g12, f2_conj(q.y) * k.g13, false};
-    G2A nq2{f2_scale(q.x, k.g22), -f2_scale(q.y, k.g23), false};
-    f = f12_mul(f, line(r, q1, pt));
-    r = g2_add(r, q1);
-    f = f12_mul(f, line(r, nq2, pt));
-    return f;
-}
 
 // (p^4 - p^2 + 1) / r, 761 bits, little-endian words
 const u32 HARD_EXPONENT[24] = {
@@ -241,13 +87,13 @@ bool final_exponentiation_is_one(const F12& f) {
     const Consts& k = consts();
     F12 fp2;
     for (int i = 0; i < 12; i++) fp2.c[i] = f.c[i] * k.gamma[i];
-    const F12 base = f12_mul(fp2, f);
+    const F12 base = f12_mul(k, fp2, f);
     F12 g = f12_one();
     bool started = false;
     for (int i = 760; i >= 0; i--) {
-        if (started) g = f12_sqr(g);
+        if (started) g = f12_sqr(k, g);
         if ((HARD_EXPONENT[i >> 5] >> (i & 31)) & 1) {
-            g = started ? f12_mul(g, base) : base;
+            g = started ? f12_mul(k, g, base) : base;
             started = true;
         }
     }
@@ -260,10 +106,10 @@ bool pairing_check(const std::vector<G1A>& a, const std::vector<G2A>& b) {
     std::vector<std::future<F12>> parts;
     for (size_t i = 0; i < a.size(); i++) {
         if (a[i].inf || b[i].inf) continue;                         // src/groth16.cpp:679-681
-        parts.push_back(std::async(std::launch::async, [&, i] { return miller(b[i], a[i]); }));
+        parts.push_back(std::async(std::launch::async, [&, i] { return miller(consts(), b[i], a[i]); }));
     }
     F12 acc = f12_one();
-    for (auto& p : parts) acc = f12_mul(acc, p.get());
+    for (auto& p : parts) acc = f12_mul(consts(), acc, p.get());
     return final_exponentiation_is_one(acc);
 }
 
@@ -588,6 +434,350 @@ int ultra_groth_verify(const char* proof, const char* inputs, const char* verifi
         copy_error(error_msg, error_msg_maxsize, "unknown error");
         return VERIFIER_ERROR;
     }
+}
+
+}  // extern "C"
+
+// ==== batch verification (include/verifier.h: ug_groth16_verify_batch, ug_ultra_groth_verify_batch) ======================
+// Small-exponent batching. For proofs i under one key and random 128-bit r_i, the single equations raised to r_i multiply to
+//     prod_i e(r_i A_i, B_i) * e(-S alpha, beta) * e(-vkX_S, gamma) * e(-sum r_i C_i, delta) == 1,     S = sum r_i,
+//     vkX_S = S IC_0 + sum_j (sum_i r_i pub_ij) IC_{j+1}   (UltraGroth: + (sum_i r_i challenge_i) IC_rand, two G1 sums),
+// which holds when every proof is valid and fails, except with probability 2^-128, when one is not. The per-proof Miller
+// loop and the r_i multiples are the device pass (pairing.hip; pairing.hpp on host threads for device < 0); both come back as
+// complete binary trees of partial products / sums, and the scalar sums are kept as prefix sums, so the same check can be
+// made for the range of any tree node: a rejected batch is searched from the root down to nodes of at most LEAF proofs,
+// which go to the single-proof verifier. Proofs whose B is outside the order-r subgroup never enter the batch (the pairing
+// is not bilinear in the scalar there); the single verifier judges them, as it does every proof when the key itself has a
+// point off its curve or a G2 point outside the subgroup.
+namespace {
+
+constexpr size_t LEAF = 16;
+
+template <class Fn> void parallel_for(size_t n, const Fn& fn) {
+    const size_t threads = std::min<size_t>(n, std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency())));
+    if (threads <= 1) { for (size_t i = 0; i < n; i++) fn(i); return; }
+    std::atomic<size_t> next{0};
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < threads; t++)
+        pool.emplace_back([&] { for (size_t i = next++; i < n; i = next++) fn(i); });
+    for (auto& t : pool) t.join();
+}
+
+struct BatchKey {
+    bool ultra = false;
+    G1A alpha, ic_rand;
+    G2A beta, gamma, delta[2];             // delta[s] pairs with the proofs' G1 point s: (C) or (pi_f, pi_r)
+    std::vector<G1A> ic;
+    int k() const { return ultra ? 2 : 1; }
+};
+struct BatchProof {
+    G1A a, g[2];
+    G2A b;
+    Inputs in;
+    u32 challenge[8];
+};
+enum State { DONE, SINGLE, BATCH };
+
+bool g2_in_subgroup(const G2A& q) {
+    if (q.inf) return true;
+    Fq2 x, y;
+    x.a = q.x.a.v; x.b = q.x.b.v; y.a = q.y.a.v; y.b = q.y.b.v;
+    return is_inf(xyzz_mul_scalar(xyzz_from_affine(x, y), FrParams::q32, 254));
+}
+void g1_words(u32* out, const G1A& p) {                            // all zero = infinity
+    if (p.inf) { memset(out, 0, G1_WORDS * sizeof(u32)); return; }
+    fq_store(out, p.x.v); fq_store(out + NL, p.y.v);
+}
+void g2_words(u32* out, const G2A& q) {
+    if (q.inf) { memset(out, 0, G2_WORDS * sizeof(u32)); return; }
+    fq_store(out, q.x.a.v); fq_store(out + NL, q.x.b.v); fq_store(out + 2 * NL, q.y.a.v); fq_store(out + 3 * NL, q.y.b.v);
+}
+Fr fr_from_plain(const u32* w8) { return canon(from_normal<FrParams>(w8)); }
+
+struct BatchTrace {
+    std::mutex m;
+    double kernel_ms[3] = {0, 0, 0};       // the last device pass of the process: Miller kernel, Fq12 tree, G1 tree
+    std::vector<int> index;                // ULTRAGROTH_TEST_HOOKS=1: the last call's batched proofs, their scalars and f_i
+    std::vector<u32> r, f;
+} g_trace;
+
+// one pass: the proofs idx[0..m) of the call, their trees and prefix sums
+struct Pass {
+    const BatchKey& key;
+    size_t m, cols;
+    int k;
+    std::vector<u32> f_tree, g_tree;
+    std::vector<Fr> prefix;                // (m + 1) x cols: S, t_0 .. t_{nPublic-1}, [t_rand]
+    std::vector<size_t> level_off, level_size;
+    unsigned long long checks = 0;
+
+    Pass(const BatchKey& key_, size_t m_) : key(key_), m(m_), cols(key_.ic.size() + (key_.ultra ? 1 : 0)), k(key_.k()) {
+        size_t off = 0;
+        for (size_t n = m;; n = (n + 1) / 2) { level_off.push_back(off); level_size.push_back(n); off += n; if (n <= 1) break; }
+        f_tree.resize(off * F12_WORDS);
+        g_tree.resize(off * k * XYZZ_WORDS);
+    }
+    // the batch equation over the proofs of node j of `level`
+    bool node_ok(size_t level, size_t j) {
+        checks++;
+        const size_t lo = j << level, hi = std::min(m, (j + 1) << level), node = level_off[level] + j;
+        std::vector<std::vector<u32>> sc(cols, std::vector<u32>(8));
+        for (size_t c = 0; c < cols; c++) to_normal(sc[c].data(), sub<1>(prefix[hi * cols + c], prefix[lo * cols + c]));
+        std::vector<G1A> g1;
+        std::vector<G2A> g2;
+        g1.push_back(g1_neg(from_xyzz(xyzz_mul_scalar_w4(to_xyzz(key.alpha), sc[0].data()))));
+        g2.push_back(key.beta);
+        G1XYZZ vkx = xyzz_mul_scalar_w4(to_xyzz(key.ic[0]), sc[0].data());
+        for (size_t c = 1; c < key.ic.size(); c++) vkx = xyzz_add(vkx, xyzz_mul_scalar_w4(to_xyzz(key.ic[c]), sc[c].data()));
+        if (key.ultra) vkx = xyzz_add(vkx, xyzz_mul_scalar_w4(to_xyzz(key.ic_rand), sc[cols - 1].data()));
+        g1.push_back(g1_neg(from_xyzz(vkx)));
+        g2.push_back(key.gamma);
+        for (int s = 0; s < k; s++) {
+            g1.push_back(g1_neg(from_xyzz(xyzz_load(&g_tree[(node * k + s) * XYZZ_WORDS]))));
+            g2.push_back(key.delta[s]);
+        }
+        std::vector<std::future<F12>> parts;
+        for (size_t i = 0; i < g1.size(); i++) {
+            if (g1[i].inf || g2[i].inf) continue;
+            parts.push_back(std::async(std::launch::async, [&, i] { return miller(consts(), g2[i], g1[i]); }));
+        }
+        F12 acc;
+        f12_load(acc, &f_tree[node * F12_WORDS]);
+        for (auto& p : parts) acc = f12_mul(consts(), acc, p.get());
+        return final_exponentiation_is_one(acc);
+    }
+    // node j of `level` failed: the positions (within the pass) that the single verifier has to judge
+    void walk(size_t level, size_t j, std::vector<size_t>& suspects) {
+        const size_t lo = j << level, hi = std::min(m, (j + 1) << level);
+        if (hi - lo <= LEAF || level == 0) { for (size_t i = lo; i < hi; i++) suspects.push_back(i); return; }
+        if (2 * j + 1 >= level_size[level - 1]) { walk(level - 1, 2 * j, suspects); return; }      // copied up: the same value
+        for (size_t c = 2 * j; c <= 2 * j + 1; c++)
+            if (!node_ok(level - 1, c)) walk(level - 1, c, suspects);
+    }
+    void host_trees(const u32* a, const u32* b, const u32* g, const u32* r) {
+        const PairingConsts& kc = consts();
+        parallel_for(m, [&](size_t i) {
+            batch_leaf(kc, a + i * G1_WORDS, b + i * G2_WORDS, g + i * k * G1_WORDS, k, r + i * 4, &f_tree[i * F12_WORDS], &g_tree[i * k * XYZZ_WORDS]);
+        });
+        for (size_t l = 0; l + 1 < level_size.size(); l++) {
+            const size_t n_src = level_size[l];
+            const u32* fs = &f_tree[level_off[l] * F12_WORDS];
+            const u32* gs = &g_tree[level_off[l] * k * XYZZ_WORDS];
+            u32* fd = &f_tree[level_off[l + 1] * F12_WORDS];
+            u32* gd = &g_tree[level_off[l + 1] * k * XYZZ_WORDS];
+            parallel_for(level_size[l + 1], [&](size_t j) {
+                const bool pair = 2 * j + 1 < n_src;
+                f12_node(kc, fs + 2 * j * F12_WORDS, pair ? fs + (2 * j + 1) * F12_WORDS : nullptr, fd + j * F12_WORDS);
+                for (int s = 0; s < k; s++)
+                    g1_node(gs + (2 * j * k + s) * XYZZ_WORDS, pair ? gs + ((2 * j + 1) * k + s) * XYZZ_WORDS : nullptr, gd + (j * k + s) * XYZZ_WORDS);
+            });
+        }
+    }
+};
+
+struct Ctx {                               // a device context for the subgroup check of the B points
+    ug_ctx* c = nullptr;
+    explicit Ctx(int device) { if (ug_ctx_create(&c, device) != UG_OK) throw std::runtime_error(ug_last_error()); }
+    ~Ctx() { if (c) ug_ctx_destroy(c); }
+};
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int verify_batch(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                 int* verdicts, ug_verify_batch_stats* stats_out, char* error_msg, unsigned long error_msg_maxsize) {
+    try {
+        const auto t_start = std::chrono::steady_clock::now();
+        if (count < 0 || !verification_key || (count > 0 && (!proofs || !inputs || !verdicts))) throw std::invalid_argument("null argument");
+        auto single = ultra ? ultra_groth_verify : groth16_verify;
+        ug_verify_batch_stats stats = {0, 0, 0, 0.0, 0.0};
+        BatchKey key;
+        key.ultra = ultra;
+        if (ultra) {
+            UltraKey k = parse_ultra_key(verification_key);
+            key.alpha = k.alpha; key.ic_rand = k.ic_rand; key.beta = k.beta; key.gamma = k.gamma;
+            key.delta[0] = k.final_delta; key.delta[1] = k.round_delta; key.ic = k.ic;
+        } else {
+            Groth16Key k = parse_key(verification_key);
+            key.alpha = k.alpha; key.ic_rand = G1A{f1_zero(), f1_zero(), true}; key.beta = k.beta; key.gamma = k.gamma;
+            key.delta[0] = k.delta; key.delta[1] = k.delta; key.ic = k.ic;
+        }
+        bool key_ok = g1_on_curve(key.alpha) && g1_on_curve(key.ic_rand);
+        for (const G1A& p : key.ic) key_ok = key_ok && g1_on_curve(p);
+        for (const G2A* q : {&key.beta, &key.gamma, &key.delta[0], &key.delta[1]}) key_ok = key_ok && g2_on_curve(*q) && g2_in_subgroup(*q);
+
+        const size_t n = (size_t)count;
+        std::vector<int> verdict(n, VERIFIER_ERROR);
+        std::vector<State> state(n, key_ok ? BATCH : SINGLE);
+        std::vector<BatchProof> parsed(key_ok ? n : 0);
+        std::vector<std::string> message(n);
+        // 1. parse; what the single call would answer before any pairing is answered here
+        if (key_ok) parallel_for(n, [&](size_t i) {
+            state[i] = DONE;
+            try {
+                if (!proofs[i] || !inputs[i]) throw std::invalid_argument("null argument");
+                BatchProof& p = parsed[i];
+                if (ultra) { UltraProof u = parse_ultra_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.final_commit; p.g[1] = u.round_commit; }
+                else { Groth16Proof u = parse_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.c; p.g[1] = G1A{f1_zero(), f1_zero(), true}; }
+                p.in = parse_inputs(inputs[i]);
+                if (p.in.plain.size() + 1 != key.ic.size()) throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
+                if (!g1_on_curve(p.a) || !g1_on_curve(p.g[0]) || !g1_on_curve(p.g[1]) || !g2_on_curve(p.b)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
+                if (ultra) derive_challenge_plain(p.challenge, p.g[1]);
+                state[i] = BATCH;
+            } catch (std::exception& e) { message[i] = e.what(); }
+        });
+        // 2. B outside the subgroup: out of the batch
+        std::vector<size_t> cand;
+        for (size_t i = 0; i < n; i++) if (state[i] == BATCH) cand.push_back(i);
+        if (device < 0) {
+            parallel_for(cand.size(), [&](size_t c) { if (!g2_in_subgroup(parsed[cand[c]].b)) state[cand[c]] = SINGLE; });
+        } else if (!cand.empty()) {
+            const auto t0 = std::chrono::steady_clock::now();
+            std::vector<u32> rec(cand.size() * 32, 0);             // zkey records: Montgomery R = 2^256, all zero = infinity
+            parallel_for(cand.size(), [&](size_t c) {
+                const G2A& q = parsed[cand[c]].b;
+                if (q.inf) return;
+                to_mont256(&rec[c * 32], q.x.a.v); to_mont256(&rec[c * 32 + 8], q.x.b.v);
+                to_mont256(&rec[c * 32 + 16], q.y.a.v); to_mont256(&rec[c * 32 + 24], q.y.b.v);
+            });
+            Ctx ctx(device);
+            for (size_t start = 0; start < cand.size();) {         // the check names the lowest bad index: go on behind it
+                ug_point_fault fault = {0, UG_POINT_OK};
+                if (ug_points_check(ctx.c, 1, &rec[start * 32], cand.size() - start, 2, &fault) != UG_OK) throw std::runtime_error(ug_last_error());
+                if (fault.reason == UG_POINT_OK) break;
+                state[cand[start + fault.index]] = SINGLE;
+                start += fault.index + 1;
+            }
+            stats.device_ms += ms_since(t0);
+        }
+        std::vector<size_t> idx;
+        for (size_t i : cand) { if (state[i] == BATCH) idx.push_back(i); else stats.off_subgroup++; }
+        // 3. the batch, in passes
+        const bool hooks = ughost::testHooksEnabled();
+        if (hooks) { std::lock_guard<std::mutex> lock(g_trace.m); g_trace.index.clear(); g_trace.r.clear(); g_trace.f.clear(); }
+        for (size_t first = 0; first < idx.size(); first += PAIRING_PASS) {
+            const size_t m = std::min<size_t>(PAIRING_PASS, idx.size() - first);
+            Pass pass(key, m);
+            const int k = pass.k;
+            std::vector<u32> r(m * 4), a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS);
+            for (size_t got = 0; got < r.size() * sizeof(u32);) {
+                const ssize_t w = getrandom((uint8_t*)r.data() + got, r.size() * sizeof(u32) - got, 0);
+                if (w <= 0) throw std::runtime_error("getrandom failed");
+                got += (size_t)w;
+            }
+            for (size_t i = 0; i < m; i++) if (!(r[4 * i] | r[4 * i + 1] | r[4 * i + 2] | r[4 * i + 3])) r[4 * i] = 1;       // (2^-128)
+            pass.prefix.assign((m + 1) * pass.cols, fp_zero<FrParams>());
+            std::vector<Fr> term(m * pass.cols);
+            parallel_for(m, [&](size_t i) {
+                const BatchProof& p = parsed[idx[first + i]];
+                g1_words(&a[i * G1_WORDS], p.a);
+                g2_words(&b[i * G2_WORDS], p.b);
+                for (int s = 0; s < k; s++) g1_words(&g[(i * k + s) * G1_WORDS], p.g[s]);
+                const u32 rw[8] = {r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], 0, 0, 0, 0};
+                const Fr rf = fr_from_plain(rw);
+                Fr* t = &term[i * pass.cols];
+                t[0] = rf;
+                for (size_t c = 0; c < p.in.plain.size(); c++) t[1 + c] = canon(mul(rf, fr_from_plain(p.in.plain[c].data())));
+                if (ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
+            });
+            for (size_t i = 0; i < m; i++)
+                for (size_t c = 0; c < pass.cols; c++)
+                    pass.prefix[(i + 1) * pass.cols + c] = canon(add(pass.prefix[i * pass.cols + c], term[i * pass.cols + c]));
+            if (device < 0) pass.host_trees(a.data(), b.data(), g.data(), r.data());
+            else {
+                const auto t0 = std::chrono::steady_clock::now();
+                PairingBatch pb;
+                pb.n = (int)m; pb.k = k; pb.a = a.data(); pb.b = b.data(); pb.g = g.data(); pb.r = r.data();
+                pb.f_tree = pass.f_tree.data(); pb.g_tree = pass.g_tree.data();
+                pairing_batch_device(device, consts(), pb);
+                stats.device_ms += ms_since(t0);
+                { std::lock_guard<std::mutex> lock(g_trace.m); for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = pb.kernel_ms[t]; }
+            }
+            if (hooks) {
+                std::lock_guard<std::mutex> lock(g_trace.m);
+                for (size_t i = 0; i < m; i++) g_trace.index.push_back((int)idx[first + i]);
+                g_trace.r.insert(g_trace.r.end(), r.begin(), r.end());
+                g_trace.f.insert(g_trace.f.end(), pass.f_tree.begin(), pass.f_tree.begin() + m * F12_WORDS);
+            }
+            const size_t top = pass.level_size.size() - 1;
+            std::vector<size_t> suspects;
+            if (!pass.node_ok(top, 0)) pass.walk(top, 0, suspects);
+            for (size_t i = 0; i < m; i++) { verdict[idx[first + i]] = VERIFIER_VALID_PROOF; state[idx[first + i]] = DONE; }
+            for (size_t s : suspects) state[idx[first + s]] = SINGLE;
+            stats.batch_checks += pass.checks;
+        }
+        // 4. whatever is left to the single verifier, on the host threads
+        std::vector<size_t> singles;
+        for (size_t i = 0; i < n; i++) if (state[i] == SINGLE) singles.push_back(i);
+        parallel_for(singles.size(), [&](size_t s) {
+            const size_t i = singles[s];
+            char msg[256] = {0};
+            verdict[i] = single(proofs[i], inputs[i], verification_key, msg, sizeof msg - 1);
+            if (verdict[i] == VERIFIER_ERROR) message[i] = msg;
+        });
+        stats.single_checks = singles.size();
+        int rc = VERIFIER_VALID_PROOF;
+        for (size_t i = 0; i < n; i++) {
+            verdicts[i] = verdict[i];
+            if (verdict[i] != VERIFIER_VALID_PROOF && rc == VERIFIER_VALID_PROOF) {
+                rc = VERIFIER_INVALID_PROOF;
+                char text[320];
+                snprintf(text, sizeof text, "proof %zu: %s", i, verdict[i] == VERIFIER_ERROR ? message[i].c_str() : "invalid proof");
+                copy_error(error_msg, error_msg_maxsize, text);
+            }
+        }
+        stats.host_ms = ms_since(t_start) - stats.device_ms;
+        if (stats_out) *stats_out = stats;
+        return rc;
+    } catch (std::exception& e) {
+        copy_error(error_msg, error_msg_maxsize, e.what());
+        return VERIFIER_ERROR;
+    } catch (...) {
+        copy_error(error_msg, error_msg_maxsize, "unknown error");
+        return VERIFIER_ERROR;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ug_groth16_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                            int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    return verify_batch(false, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+}
+int ug_ultra_groth_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                                int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    return verify_batch(true, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+}
+
+void ug_verify_batch_kernel_ms(double ms[3]) {
+    std::lock_guard<std::mutex> lock(g_trace.m);
+    for (int t = 0; t < 3; t++) ms[t] = g_trace.kernel_ms[t];
+}
+
+// ULTRAGROTH_TEST_HOOKS=1 only (else 1 is returned and nothing is written)
+int ug_test_verify_batch_trace(int index, unsigned int scalar[4], unsigned int f[108]) {
+    if (!ughost::testHooksEnabled()) return 1;
+    std::lock_guard<std::mutex> lock(g_trace.m);
+    const auto it = std::find(g_trace.index.begin(), g_trace.index.end(), index);
+    if (it == g_trace.index.end()) return 1;
+    const size_t at = (size_t)(it - g_trace.index.begin());
+    if (scalar) memcpy(scalar, &g_trace.r[at * 4], 4 * sizeof(u32));
+    if (f) memcpy(f, &g_trace.f[at * F12_WORDS], F12_WORDS * sizeof(u32));
+    return 0;
+}
+int ug_test_miller(const unsigned char g1[64], const unsigned char g2[128], unsigned int f[108]) {
+    if (!ughost::testHooksEnabled() || !g1 || !g2 || !f) return 1;
+    u32 w[48];
+    memcpy(w, g1, 64); memcpy(w + 16, g2, 128);
+    if (words_all_zero(w, 16) || words_all_zero(w + 16, 32)) return 1;
+    auto ld = [&](int at) { return F1{canon(from_mont256<FqParams>(w + at))}; };
+    const G1A pt{ld(0), ld(8), false};
+    const G2A q{F2{ld(16), ld(24)}, F2{ld(32), ld(40)}, false};
+    f12_store(f, miller(consts(), q, pt));
+    return 0;
 }
 
 }  // extern "C"
