@@ -1112,6 +1112,61 @@ def test_sharded_ultragroth_queued_final_round(device, world, chain_first):
             p.close()
 
 
+def test_sharded_ultragroth_queued_state_guards(device):
+    """the guards of the queued state are one implementation for both rank types (RankProver): an UltraGroth rank refuses
+    witness_msm_end without begin, a second witness_msm_begin and load_witness while its products are queued, with the messages
+    the Groth16 ranks give (test_witness_products_queued_beside_the_h_branch); the refused calls leave the proof alone -- finished
+    from both ranks' partials it is the oracle's byte for byte"""
+    import torch
+    import ultragroth_amd as ug
+    from ultragroth_amd import synth
+    zkey, uwtns, info = synth.build_ultra_circuit(device, 10)
+    rk, r, s = bytes(range(1, 32)), bytes(range(40, 71)), bytes(range(80, 111))
+    exp = O.ultra_groth_prove(zkey, uwtns, int.from_bytes(rk, "little"), int.from_bytes(r, "little"), int.from_bytes(s, "little"))
+    world, n_dom = 2, info["domainSize"]
+    ranks = [ug.ShardedUltraGrothProver(zkey, 0, k, world) for k in range(world)]
+    full = torch.empty((3, n_dom, 32), dtype=torch.uint8, device="cuda")
+    try:
+        ug.set_test_blinding(rk + r + s)
+        try:
+            for p in ranks:
+                p.load_witness(uwtns)
+            with pytest.raises(ug.ProverError, match="no witness products queued"):
+                ranks[1].witness_msm_end()
+            total = bytes(64)
+            for p in ranks:
+                total = ug.ShardedUltraGrothProver.add_records(total, p.round_commit())
+            commitment = ranks[0].round_finish(total)
+            for p in ranks:
+                p.apply_commitment(commitment)
+            for p in ranks:
+                p.witness_msm_begin()
+            with pytest.raises(ug.ProverError, match="already queued"):
+                ranks[1].witness_msm_begin()
+            with pytest.raises(ug.ProverError, match="still read the witness"):
+                ranks[0].load_witness(uwtns)
+            for k in range(3):
+                ranks[k % world].hpoly_chain(k, full[k].data_ptr())
+            acc = None
+            for p in ranks:
+                first, cnt, _ = p.h_range()
+                bufs = [full[k, first:first + cnt].contiguous() for k in range(3)]
+                torch.cuda.synchronize()
+                p.hpoly_combine(*(b.data_ptr() for b in bufs))
+                hpart = p.run_h_msm()
+                part = p.witness_msm_end()[:320] + hpart[320:384]
+                acc = part if acc is None else ug.ShardedGroth16Prover.add_partials(acc, part)
+            with pytest.raises(ug.ProverError, match="no witness products queued"):
+                ranks[0].witness_msm_end()
+            got = ranks[0].finish(acc)
+        finally:
+            ug.set_test_blinding(b"")
+        assert got == exp
+    finally:
+        for p in ranks:
+            p.close()
+
+
 @pytest.mark.parametrize("world", [3, 4])
 def test_sharded_ultragroth_from_slices(device, world):
     """ug_ultra_groth_prover_create_sharded_slices: every rank from the header section and ITS slices of the six point sections and

@@ -156,6 +156,13 @@ void checkBufferSizes(unsigned long long proofCalc, const unsigned long long* pr
         throw ShortBufferException("Public buffer is too short. " + type + " size: " + std::to_string(publicCalc) +
                                    ", actual size: " + std::to_string(*publicSize));
 }
+// the two texts of a finished proof into the caller's buffers, once they are known to fit
+void returnProof(const std::string& proof, const std::string& pub, char* proofBuffer, const unsigned long long* proofSize,
+                 char* publicBuffer, const unsigned long long* publicSize) {
+    checkBufferSizes(proof.length(), proofSize, pub.length(), publicSize, "Required");
+    std::strncpy(proofBuffer, proof.c_str(), *proofSize);
+    std::strncpy(publicBuffer, pub.c_str(), *publicSize);
+}
 
 // ---- host curve helpers on reference-format records ---------------------------------------------------
 G1XYZZ g1FromRecord(const uint8_t* rec) {
@@ -472,10 +479,13 @@ thread_local bool g_oneShotProver = false;      // create + one prove + destroy 
 
 thread_local bool g_registryCreate = false;     // the resident multi-circuit prover decides about tables itself, after create
 
-thread_local bool g_deferTables = false;        // set around groth16_prover_create's constructor call: the one prover that may hand out
-                                                // proofs before its window tables exist. Its prove calls go through proveTurn and share
-                                                // the turn with the table builder; the phase calls (run, witnessMsmBegin, hpolyChain, ...)
-                                                // take no turn, so a phase caller has to wait for tablesReady first
+thread_local bool g_deferTables = false;        // set by newGroth16Prover around the constructor call of an unsharded created prover: the
+                                                // one prover that may hand out proofs before its window tables exist. NOT every caller
+                                                // of such a prover goes through proveTurn: prove, proveResident, proveBatch, loadWitness,
+                                                // trimWorkspaces and kernelStats share the turn with the table builder, but the phase
+                                                // calls (run, runWitnessMsm, witnessMsmBegin / End, runHMsm, hpolyChain, hpolyCombine) are
+                                                // reachable on the same handle and take no turn. Nothing enforces it: a phase caller
+                                                // must wait for tablesReady(true) first, as bench.py and the tests do
 
 // what the tables of all groups would take (0: no group qualifies) and the schedule workspace they imply
 uint64_t tablesNeed(const std::vector<TableGroup>& groups, std::vector<int>& width, uint64_t* workspaceOut) {
@@ -885,14 +895,148 @@ void checkSlices(const char* const* what, const uint64_t* need, const uint8_t* c
                                         " bytes, needed " + std::to_string(need[k]));
     }
 }
-// the end of both provers' trimWorkspaces (the batch lock and the turn held): the schedules' and contexts' workspaces, the
-// witness buffer that is not the current one, the batch buffers
-void trimDeviceWorkspaces(DeviceProver& d, WitnessBuffers& witness, const ug_dvec* current, BatchBuffers& batch) {
-    for (ug_schedule* s : {d.sw, d.sh, d.saux, d.sB}) if (s) ug_schedule_trim(s);
-    ug_ctx_trim(d.ctx); ug_ctx_trim(d.ctx2);
-    witness.trim(current);
-    batch.release();
-}
+// ---- a device prover as a RANK of a sharded or many-device proof ---------------------------------------
+// The base of Groth16Prover and UltraGrothProver: the state both keep per circuit and per proof, and the phases that read
+// nothing else -- the H branch on the second stream (hpolyChain, hpolyCombine, hRange), the end of the queued witness products
+// (witnessMsmEnd, witnessMsmAbandon), the device times, the check of a witness file against the circuit, loadWitness. Where the
+// two provers differ, a hook says so:
+//   requireWitnessForH   what the H branch needs first: the whole witness (Groth16) / the applied round commitment (UltraGroth)
+//   stage, adopt         the two halves of a witness load (a .wtns / a .uwtns with its lookup lists)
+//   takeTurn             Groth16Prover's turn makes its table builder step back
+//   witnessMsmAbandon    Groth16Prover also drops the r and s it drew when the products were queued
+//   dropReplays          Groth16Prover's recorded launch sequences point into workspaces that trimWorkspaces gives back
+class RankProver : public ProverBase {
+public:
+    // the prover's turn for a caller; forProof: the turn of a proof or a device pass, not one that only plans, adopts a witness or
+    // writes figures
+    virtual std::unique_lock<std::mutex> takeTurn(bool /*forProof*/) { return std::unique_lock<std::mutex>(proveMutex); }
+    const ZkeyHeader& header() const { return hdr_; }
+    // the whole witness section of a .wtns / .uwtns buffer, checked against the circuit (src/prover.cpp:183-196)
+    const uint8_t* checkedWitness(const BinFile& f) const {
+        WtnsHeader wh = loadWtnsHeader(f);
+        if (hdr_.nVars != wh.nVars)
+            throw InvalidWitnessLengthException("Invalid witness length. Circuit: " + std::to_string(hdr_.nVars) +
+                                                ", witness: " + std::to_string(wh.nVars));
+        if (!wh.primeIsBn254) throw std::invalid_argument("different wtns curve");
+        return checkedSection(f, 2, (uint64_t)hdr_.nVars * 32);
+    }
+    // phase call (the caller drives the phases of one proof from one thread and holds no lock): staged like a proof's
+    void loadWitness(const void* wtns, unsigned long long wtnsSize) override {
+        witnessNotQueued();
+        WitnessLease lease(witness_);
+        stage(*lease, wtns, wtnsSize);
+        std::unique_lock<std::mutex> turn = takeTurn(false);
+        adopt(*lease);
+    }
+    // witnessMsmBegin .. witnessMsmEnd: begin (the derived class's) queues the rank's witness products on the witness stream and
+    // returns without a host wait; end waits for them (queued == 2: complete already, nothing to collect)
+    void witnessMsmEnd(uint8_t* partials) override {
+        if (!witnessQueued_) throw std::invalid_argument("no witness products queued (ug_groth16_prover_witness_msm_begin)");
+        const int how = witnessQueued_;
+        witnessQueued_ = 0;
+        if (how == 1) {
+            QueueGuard inFlight(d_.ctx);
+            ugCheck(ug_ctx_collect(d_.ctx));
+            inFlight.done();
+            collectTimings(1);
+        }
+        memcpy(partials, queuedParts_, UG_GROTH16_PARTIALS_SIZE);
+    }
+    // a begun proof is given up: wait for the device, drop the queued products (no result is written)
+    virtual void witnessMsmAbandon() {
+        if (witnessQueued_ == 1) ug_ctx_abandon(d_.ctx);
+        witnessQueued_ = 0;
+    }
+    // device time per stream since the witness was loaded; which: 1 = witness stream, 2 = H branch (each waits for its stream).
+    // A stream's figures are touched only by the host thread that drives it (a many-device rank may run its chains from a second
+    // thread, see include/prover.h)
+    void collectTimings(int which) {
+        if (which & 1) ugCheck(ug_ctx_timings(d_.ctx, &m1_, &f1_, 0));
+        if (which & 2) ugCheck(ug_ctx_timings(d_.ctx2, &m2_, &f2_, 0));
+    }
+    // one chain of the H polynomial into a caller's device vector; complete when the call returns (collectTimings waits for the
+    // H stream: the caller sends the vector on)
+    void hpolyChain(int which, void* deviceOut) override {
+        requireWitnessForH();
+        if (!haveHpoly_) throw std::invalid_argument("this rank was created without the coefficient matrix");
+        ug_dvec* v = nullptr;
+        ugCheck(ug_dvec_wrap(d_.ctx2, deviceOut, hdr_.domainSize, &v));
+        int rc = ug_hpoly_chain(d_.hp, wCur_, which, v);
+        ug_dvec_destroy(v);
+        ugCheck(rc);
+        collectTimings(2);
+    }
+    void hpolyCombine(void* da, void* db, void* dc) override {
+        uint64_t cnt = hr_.hi - hr_.lo;
+        if (!cnt) return;                            // (a chain rank of a bucket-class layout takes no part in the H product)
+        ug_dvec *a = nullptr, *b = nullptr, *c = nullptr;
+        ugCheck(ug_dvec_wrap(d_.ctx2, da, cnt, &a));
+        ugCheck(ug_dvec_wrap(d_.ctx2, db, cnt, &b));
+        ugCheck(ug_dvec_wrap(d_.ctx2, dc, cnt, &c));
+        int rc = ug_hpoly_combine(d_.hp, a, b, c, hr_.lo, cnt, d_.h);
+        ug_dvec_destroy(a); ug_dvec_destroy(b); ug_dvec_destroy(c);
+        ugCheck(rc);
+        collectTimings(2);
+    }
+    void hRange(unsigned long long* first, unsigned long long* count, unsigned long long* domain) const override {
+        if (first) *first = hr_.lo;
+        if (count) *count = hr_.hi - hr_.lo;
+        if (domain) *domain = hdr_.domainSize;
+    }
+    void timings(double* msm, double* fft, double* total) const override {
+        if (msm) *msm = m1_ + m2_;
+        if (fft) *fft = f1_ + f2_;
+        if (total) *total = totalMs_;
+    }
+    // the figures of a batched call (proveBatchInPasses), written under the turn as every proof writes them
+    void setBatchTimings(double msm, double fft, double total) { m1_ = msm; f1_ = fft; m2_ = f2_ = 0; totalMs_ = total; }
+    ug_ctx* ctx() override { return d_.ctx; }
+    ug_ctx* ctx2() { return d_.ctx2; }              // the H branch's context (its stream orders hpolyChain / hpolyCombine / runHMsm)
+    // a many-device prover collects a rank's witness from its peers: the vector the device part reads and this rank's range of it
+    ug_dvec* witnessVec() { return wCur_; }
+    Range witnessRange() const { return wr_; }
+    // the schedules' and contexts' workspaces, the witness buffer that is not the current one, the batch buffers
+    void trimWorkspaces() override {
+        std::lock_guard<std::mutex> batch(batch_.mutex);    // (a batch call owns the batch buffers it stages into)
+        std::unique_lock<std::mutex> turn = takeTurn(false);
+        dropReplays();                                  // (they hold pointers into what goes now)
+        for (ug_schedule* s : {d_.sw, d_.sh, d_.saux, d_.sB}) if (s) ug_schedule_trim(s);
+        ug_ctx_trim(d_.ctx); ug_ctx_trim(d_.ctx2);
+        witness_.trim(wCur_);
+        batch_.release();
+    }
+
+protected:
+    virtual void requireWitnessForH() const = 0;
+    // staging: parse the witness file and copy the signals into the leased buffer; needs no turn on the device, only the uploader
+    // (one copy at a time)
+    virtual void stage(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) = 0;
+    // the staged witness becomes the prover's (proveMutex held)
+    virtual void adopt(StagedWitness& sl) = 0;
+    virtual void dropReplays() {}
+    // a witness load is refused while queued products read the witness
+    void witnessNotQueued() const {
+        if (witnessQueued_ == 1) throw std::invalid_argument("the queued witness products still read the witness (ug_groth16_prover_witness_msm_end)");
+    }
+
+    ZkeyHeader hdr_;
+    std::vector<uint8_t> vk_, publicPart_;          // the verification-key points hdr_ refers to; signals 0 .. nPublic of the loaded witness
+    Range wr_{0, 0}, hr_{0, 0};                     // this rank's witness scalars (and A / B1 / B2 points) and h scalars (and H points)
+    TableChoice planW_, planH_;                     // fixed-base tables of the witness and H groups (the B group's: d_.planB)
+    bool sparseB_ = false;                          // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
+    uint64_t nB_ = 0;
+    bool haveHpoly_ = true;
+    DeviceProver d_;
+    ug_dvec* wCur_ = nullptr;                       // the witness the device part reads: one of the two buffers (d_.w, d_.w2 own them)
+    WitnessBuffers witness_;
+    double m1_ = 0, f1_ = 0, m2_ = 0, f2_ = 0, totalMs_ = 0;      // device ms of the MSM / FFT parts per stream (witness stream, H branch)
+    // witnessMsmBegin .. witnessMsmEnd: the queued products write here (the queue holds these addresses until it is collected)
+    int witnessQueued_ = 0;                         // 1: queued on the witness stream, 2: already complete in queuedParts_
+    uint8_t queuedParts_[UG_GROTH16_PARTIALS_SIZE] = {};
+public:
+    BatchBuffers batch_;                            // batched proofs (declared after d_: it goes before the contexts; what a derived
+                                                    // class owns -- Groth16Prover's builder thread and graphs -- goes before both)
+};
 
 // The pass loop of a batched call (proveBatch of Groth16Prover and UltraGrothProver). `c` is the prover's
 // BatchCall: the call's arguments, what parsing kept of every witness, the device times so far. Every witness is parsed and
@@ -934,7 +1078,7 @@ void proveBatchInPasses(P& p, typename P::BatchCall& c, int k) {
 }  // namespace
 
 // =================================================================================================================
-class Groth16Prover : public ProverBase {
+class Groth16Prover : public RankProver {
 public:
     // What a prover is made from: the zkey header (section 2), the coefficient records and the five point sections --
     // whole sections of a zkey buffer, or (sliced) only this rank's slice of each, so that a rank of a many-GPU prover
@@ -1212,7 +1356,7 @@ public:
     void callerHasTheTurn() { builderHadLast_.store(false); turnsTaken_.fetch_add(1); }
     // the prover's turn for a caller (the table builder steps back); forProof: the turn of a proof or a device pass, which the
     // builder counts (callerHasTheTurn), not one that only plans, adopts a witness or writes figures
-    std::unique_lock<std::mutex> takeTurn(bool forProof) {
+    std::unique_lock<std::mutex> takeTurn(bool forProof) override {
         std::unique_lock<std::mutex> turn;
         { TurnRequest mine(wantTurn_); turn = std::unique_lock<std::mutex>(proveMutex); }
         if (forProof) callerHasTheTurn();
@@ -1329,47 +1473,19 @@ public:
         return groups;
     }
     int pendingWidth(int group) const override { return group >= 0 && group < 3 ? pending_[group].load() : 0; }
-    void trimWorkspaces() override {
-        std::lock_guard<std::mutex> batch(batch_.mutex);    // (a batch call owns the batch buffers it stages into)
-        TurnRequest mine(wantTurn_);
-        std::lock_guard<std::mutex> turn(proveMutex);
-        dropGraphs();                                   // (they hold pointers into what goes now)
-        trimDeviceWorkspaces(d_, witness_, wCur_, batch_);
-    }
-
-    const ZkeyHeader& header() const { return hdr_; }
+    void dropReplays() override { dropGraphs(); }
     bool sparseB() const { return sparseB_; }
 
-    // the whole witness section of a .wtns buffer, checked against the circuit (src/prover.cpp:183-196)
-    const uint8_t* witnessData(const BinFile& f) const {
-        WtnsHeader wh = loadWtnsHeader(f);
-        if (hdr_.nVars != wh.nVars)
-            throw InvalidWitnessLengthException("Invalid witness length. Circuit: " + std::to_string(hdr_.nVars) +
-                                                ", witness: " + std::to_string(wh.nVars));
-        if (!wh.primeIsBn254) throw std::invalid_argument("different wtns curve");
-        return checkedSection(f, 2, (uint64_t)hdr_.nVars * 32);
-    }
-    // phase call (the caller drives the phases of one proof from one thread and holds no lock): staged like a proof's
-    void loadWitness(const void* wtns, unsigned long long wtnsSize) override {
-        if (witnessQueued_ == 1) throw std::invalid_argument("the queued witness products still read the witness (ug_groth16_prover_witness_msm_end)");
-        WitnessLease lease(witness_);
-        stage(*lease, wtns, wtnsSize);
-        std::unique_lock<std::mutex> turn = takeTurn(false);
-        adopt(*lease);
-    }
-    // staging: parse the .wtns and copy the witness into the leased buffer; needs no turn on the device, only the
-    // uploader (one copy at a time)
-    void stage(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) {
+    void stage(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) override {
         std::lock_guard<std::mutex> st(witness_.stageMutex);
         auto u0 = std::chrono::steady_clock::now();
         BinFile f(wtns, wtnsSize, "wtns", 2);
-        const uint8_t* data = witnessData(f);
+        const uint8_t* data = checkedWitness(f);
         sl.publicPart.assign(data, data + ((size_t)hdr_.nPublic + 1) * 32);
         ugCheck(ug_dvec_upload_idle(sl.buf, data, hdr_.nVars));
         sl.uploadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
     }
-    // the staged witness becomes the prover's (proveMutex held)
-    void adopt(StagedWitness& sl) {
+    void adopt(StagedWitness& sl) override {
         wCur_ = sl.buf;
         publicPart_.swap(sl.publicPart);
         uploadMs = sl.uploadMs;
@@ -1415,14 +1531,8 @@ public:
     void loadWitnessPart(const void* wtns, unsigned long long wtnsSize, int part) override {
         auto t0 = std::chrono::steady_clock::now();
         BinFile f(wtns, wtnsSize, "wtns", 2);
-        WtnsHeader wh = loadWtnsHeader(f);
-        if (hdr_.nVars != wh.nVars)
-            throw InvalidWitnessLengthException("Invalid witness length. Circuit: " + std::to_string(hdr_.nVars) +
-                                                ", witness: " + std::to_string(wh.nVars));
-        if (!wh.primeIsBn254) throw std::invalid_argument("different wtns curve");
-        const uint8_t* data = checkedSection(f, 2, (uint64_t)hdr_.nVars * 32);
-        if (part == 0 && witnessQueued_ == 1)      // (part 1 lies outside the range the queued products read, and goes to the other stream)
-            throw std::invalid_argument("the queued witness products still read the witness (ug_groth16_prover_witness_msm_end)");
+        const uint8_t* data = checkedWitness(f);
+        if (part == 0) witnessNotQueued();         // (part 1 lies outside the range the queued products read, and goes to the other stream)
         if (part == 0) {
             resetTimings();
             publicPart_.assign(data, data + ((size_t)hdr_.nPublic + 1) * 32);
@@ -1486,22 +1596,8 @@ public:
         inFlight.done();
         witnessQueued_ = 1;
     }
-    void witnessMsmEnd(uint8_t* partials) override {
-        if (!witnessQueued_) throw std::invalid_argument("no witness products queued (ug_groth16_prover_witness_msm_begin)");
-        const int how = witnessQueued_;
-        witnessQueued_ = 0;
-        if (how == 1) {
-            QueueGuard inFlight(d_.ctx);
-            ugCheck(ug_ctx_collect(d_.ctx));
-            inFlight.done();
-            collectTimings(1);
-        }
-        memcpy(partials, queuedParts_, UG_GROTH16_PARTIALS_SIZE);
-    }
-    // a begun proof is given up: wait for the device, drop the queued products (no result is written)
-    void witnessMsmAbandon() {
-        if (witnessQueued_ == 1) ug_ctx_abandon(d_.ctx);
-        witnessQueued_ = 0;
+    void witnessMsmAbandon() override {
+        RankProver::witnessMsmAbandon();
         if (earlyTerms_.valid()) { earlyTerms_.wait(); earlyTerms_ = std::future<BlindingTerms>(); }     // the abandoned proof's r, s are dropped with it
     }
     // S10 on this rank's slice of h (which must be in d_.h); only the H record of partials is written
@@ -1523,42 +1619,12 @@ public:
         inFlight.done();
         if (standalone) collectTimings(2);
     }
-    // device time per branch since the witness was loaded; each branch's figures are touched only by the host thread that
-    // drives that branch (a sharded rank runs its chains from a second thread, see include/prover.h)
-    void collectTimings(int which) {
-        if (which & 1) ugCheck(ug_ctx_timings(d_.ctx, &m1_, &f1_, 0));
-        if (which & 2) ugCheck(ug_ctx_timings(d_.ctx2, &m2_, &f2_, 0));
-    }
     void resetTimings() {
         ugCheck(ug_ctx_timings(d_.ctx, nullptr, nullptr, 1)); ugCheck(ug_ctx_timings(d_.ctx2, nullptr, nullptr, 1));
         m1_ = f1_ = m2_ = f2_ = 0;
     }
-    void hpolyChain(int which, void* deviceOut) override {
+    void requireWitnessForH() const override {
         if (!witnessLoaded_ || !witnessComplete_) throw std::invalid_argument("the whole witness has not been loaded");
-        if (!haveHpoly_) throw std::invalid_argument("this rank was created without the coefficient matrix");
-        ug_dvec* v = nullptr;
-        ugCheck(ug_dvec_wrap(d_.ctx2, deviceOut, hdr_.domainSize, &v));
-        int rc = ug_hpoly_chain(d_.hp, wCur_, which, v);
-        ug_dvec_destroy(v);
-        ugCheck(rc);
-        collectTimings(2);
-    }
-    void hpolyCombine(void* da, void* db, void* dc) override {
-        uint64_t cnt = hr_.hi - hr_.lo;
-        if (!cnt) return;                            // (a chain rank of a bucket-class layout takes no part in the H product)
-        ug_dvec *a = nullptr, *b = nullptr, *c = nullptr;
-        ugCheck(ug_dvec_wrap(d_.ctx2, da, cnt, &a));
-        ugCheck(ug_dvec_wrap(d_.ctx2, db, cnt, &b));
-        ugCheck(ug_dvec_wrap(d_.ctx2, dc, cnt, &c));
-        int rc = ug_hpoly_combine(d_.hp, a, b, c, hr_.lo, cnt, d_.h);
-        ug_dvec_destroy(a); ug_dvec_destroy(b); ug_dvec_destroy(c);
-        ugCheck(rc);
-        collectTimings(2);
-    }
-    void hRange(unsigned long long* first, unsigned long long* count, unsigned long long* domain) const override {
-        if (first) *first = hr_.lo;
-        if (count) *count = hr_.hi - hr_.lo;
-        if (domain) *domain = hdr_.domainSize;
     }
 
     // S1-S10 on this rank's slices with the H-polynomial block computed locally (replicated when sharded): everything is
@@ -1741,7 +1807,7 @@ public:
     }
     void parseForBatch(BatchCall& c, int b) const {
         BinFile f(c.wtns[b], c.sizes[b], "wtns", 2);
-        c.data[(size_t)b] = witnessData(f);
+        c.data[(size_t)b] = checkedWitness(f);
     }
     // one witness of a batch on the single-proof path (proveTurn), its device times added while it holds the turn
     void proveOneOfBatch(BatchCall& c, int b) {
@@ -1795,7 +1861,6 @@ public:
                        c.proofs[(size_t)(b0 + v)], c.pubs[(size_t)(b0 + v)], &publicPart);
         }
     }
-    void setBatchTimings(double msm, double fft, double total) { m1_ = msm; f1_ = fft; m2_ = f2_ = 0; totalMs_ = total; }
     // one device pass of the V staged witnesses; parts = V blocks A | B1 | B2 | C | H as run() leaves them
     void runBatch(int V, uint8_t* parts) {
         const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize, nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
@@ -1832,17 +1897,8 @@ public:
 
     unsigned long long proofBufferMinSize() const override { return PROOF_MIN_GROTH16; }
     unsigned long long publicBufferMinSize() const override { return publicMin(hdr_.nPublic); }
-    void timings(double* msm, double* fft, double* total) const override {
-        if (msm) *msm = m1_ + m2_;
-        if (fft) *fft = f1_ + f2_;
-        if (total) *total = totalMs_;
-    }
-    ug_ctx* ctx() override { return d_.ctx; }
-    ug_ctx* ctx2() { return d_.ctx2; }              // the H branch's context (its stream orders hpolyChain / hpolyCombine / runHMsm)
-    // a many-device prover collects a chain rank's witness from its peers: the vector the device part reads, this rank's range of
-    // it, and the word that the rest has arrived (on the H branch's stream, as loadWitnessPart(.., 1) leaves it)
-    ug_dvec* witnessVec() { return wCur_; }
-    Range witnessRange() const { return wr_; }
+    // a many-device prover collects a chain rank's witness from its peers (witnessVec, witnessRange): the word that the rest has
+    // arrived (on the H branch's stream, as loadWitnessPart(.., 1) leaves it)
     void witnessGathered() {
         if (!witnessLoaded_) throw std::invalid_argument("the rank's own part of the witness comes first");
         witnessComplete_ = true;
@@ -1851,10 +1907,7 @@ public:
 private:
     static constexpr uint64_t MAX_RANGE = (uint64_t)1 << 26;       // 2^26 scalars * <= 16 windows < 2^31 entries
     uint64_t maxRange_ = MAX_RANGE;    // ULTRAGROTH_MAX_RANGE lowers it (tests: the piecewise path without a 2^27 circuit)
-    TableChoice planW_, planH_;        // fixed-base tables of the witness and H groups (planWindowTables; the B group's: d_.planB)
     std::atomic<int> pending_[3] = {{0}, {0}, {0}};      // per group: width of tables that are still being built (tableBuilder)
-    bool sparseB_ = false;             // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
-    uint64_t nB_ = 0;
     bool bgTables_ = false;
     std::thread builder_;
     std::atomic<bool> stopBuilder_{false}, builderDone_{false};
@@ -1865,19 +1918,9 @@ private:
     int rank_, count_;
     ShardLayout layout_;               // this rank's part of a many-device layout (haveLayout_), else unused
     bool haveLayout_ = false;
-    ZkeyHeader hdr_;
-    std::vector<uint8_t> vk_, publicPart_;
-    Range wr_{0, 0}, hr_{0, 0};
     uint64_t cLo_ = 0, cHi_ = 0;       // this rank's slice of the C section
-    DeviceProver d_;
-    bool witnessLoaded_ = false, witnessComplete_ = false, haveHpoly_ = true;
+    bool witnessLoaded_ = false, witnessComplete_ = false;
     bool groupG1_ = true;              // A | B1 | C kept as one interleaved group (not when a member is all infinity, or ULTRAGROTH_FUSED=0)
-    ug_dvec* wCur_ = nullptr;          // the witness the device part reads: one of the two buffers (d_.w, d_.w2 own them)
-    WitnessBuffers witness_;
-    double m1_ = 0, f1_ = 0, m2_ = 0, f2_ = 0, totalMs_ = 0;      // device ms of the MSM / FFT parts per stream
-    // witnessMsmBegin .. witnessMsmEnd: the queued products write here (the queue holds these addresses until it is collected)
-    int witnessQueued_ = 0;            // 1: queued on the witness stream, 2: already complete in queuedParts_
-    uint8_t queuedParts_[UG_GROTH16_PARTIALS_SIZE] = {};
     uint8_t earlyR_[32] = {}, earlyS_[32] = {};
     std::future<BlindingTerms> earlyTerms_;
     uint8_t runParts_[UG_GROTH16_PARTIALS_SIZE] = {};       // where run()'s queued products write (fixed: a replayed graph's too)
@@ -1885,12 +1928,11 @@ private:
     std::vector<std::pair<const ug_dvec*, int>> warm_;
     bool statsOn_ = false;
 public:
-    BatchBuffers batch_;               // batched proofs (declared after d_: it goes first)
-    ~Groth16Prover() override { stopTableBuilder(); dropGraphs(); }      // (before d_ goes: both refer to its contexts)
+    ~Groth16Prover() override { stopTableBuilder(); dropGraphs(); }      // (before RankProver's d_ goes: both refer to its contexts)
 };
 
 // =================================================================================================================
-class UltraGrothProver : public ProverBase {
+class UltraGrothProver : public RankProver {
 public:
     // What a prover is made from: whole sections of a zkey buffer, or (sliced) only this rank's slice of each point section
     // and of the two index lists, so that a rank of a many-GPU prover never holds the whole zkey in host memory
@@ -2052,17 +2094,9 @@ public:
         }
         return groups;
     }
-    void trimWorkspaces() override {
-        std::lock_guard<std::mutex> batch(batch_.mutex);    // (a batch call owns the batch buffers it stages into)
-        std::lock_guard<std::mutex> turn(proveMutex);
-        trimDeviceWorkspaces(d_, witness_, wCur_, batch_);
-    }
 
-    const ZkeyHeader& header() const { return hdr_; }
-
-    // Staging: parse the .uwtns and copy the signals into the leased buffer -- no turn on the device needed, so the witness
-    // of a waiting call is copied while another proof runs (as Groth16Prover::proveTurn).
-    void stage(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) {
+    // (the witness of a waiting call is copied while another proof runs, as Groth16Prover::proveTurn)
+    void stage(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) override {
         std::lock_guard<std::mutex> st(witness_.stageMutex);
         auto tLoad0 = std::chrono::steady_clock::now();
         const uint8_t* signals0 = parseWitness(sl, wtns, wtnsSize);
@@ -2072,13 +2106,7 @@ public:
     // the .uwtns checked against the circuit, its lists and public signals copied into sl; returns the signals (in the caller's buffer)
     const uint8_t* parseWitness(StagedWitness& sl, const void* wtns, unsigned long long wtnsSize) const {
         BinFile f(wtns, wtnsSize, "wtns", 2);
-        WtnsHeader wh = loadWtnsHeader(f);
-        if (hdr_.nVars != wh.nVars)
-            throw InvalidWitnessLengthException("Invalid witness length. Circuit: " + std::to_string(hdr_.nVars) +
-                                                ", witness: " + std::to_string(wh.nVars));
-        if (!wh.primeIsBn254) throw std::invalid_argument("different wtns curve");
-        const uint64_t M = hdr_.nVars;
-        const uint8_t* signals0 = checkedSection(f, 2, M * 32);       // the reference copies these (prover.cpp:283-285);
+        const uint8_t* signals0 = checkedWitness(f);                  // the reference copies these (prover.cpp:283-285);
                                                                       // here the copy lives in HBM and is patched there
         auto u32Section = [&](uint32_t id) {
             std::vector<uint32_t> v(f.sectionSize(id) >> 2);
@@ -2094,36 +2122,19 @@ public:
     // [lo, hi) copied over this rank's PCIe link, into the current buffer -- the rest arrives from the peers' HBM
     // (witnessVec / ug_dvec_copy_via), after which witnessGathered() makes the witness the prover's. One thread, no turn.
     void loadWitnessSlice(const void* wtns, unsigned long long wtnsSize, uint64_t lo, uint64_t hi) {
-        if (witnessQueued_ == 1) throw std::invalid_argument("the queued witness products still read the witness (ug_groth16_prover_witness_msm_end)");
+        witnessNotQueued();
         auto tLoad0 = std::chrono::steady_clock::now();
-        BinFile f(wtns, wtnsSize, "wtns", 2);
-        WtnsHeader wh = loadWtnsHeader(f);
-        if (hdr_.nVars != wh.nVars)
-            throw InvalidWitnessLengthException("Invalid witness length. Circuit: " + std::to_string(hdr_.nVars) +
-                                                ", witness: " + std::to_string(wh.nVars));
-        if (!wh.primeIsBn254) throw std::invalid_argument("different wtns curve");
-        const uint64_t M = hdr_.nVars;
-        if (lo > hi || hi > M) throw std::invalid_argument("witness slice outside [0, nVars]");
-        const uint8_t* signals0 = checkedSection(f, 2, M * 32);
-        auto u32Section = [&](uint32_t id) {
-            std::vector<uint32_t> v(f.sectionSize(id) >> 2);
-            memcpy(v.data(), f.sectionData(id), v.size() * 4);
-            return v;
-        };
         StagedWitness sl;
         sl.buf = wCur_;
-        sl.chunks = u32Section(3); sl.freq = u32Section(4); sl.wIdx = u32Section(5); sl.pIdx = u32Section(6);
-        if (sl.wIdx.size() != sl.pIdx.size()) throw std::range_error("uwtns: wtns_indxs and push_indxs differ in length");
-        sl.publicPart.assign(signals0, signals0 + ((size_t)hdr_.nPublic + 1) * 32);
+        const uint8_t* signals0 = parseWitness(sl, wtns, wtnsSize);
+        if (lo > hi || hi > hdr_.nVars) throw std::invalid_argument("witness slice outside [0, nVars]");
         if (hi > lo) ugCheck(ug_dvec_upload_range(wCur_, signals0 + lo * 32, lo, hi - lo, nullptr));
         sl.uploadMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLoad0).count();
         adopt(sl);
         witnessLoaded_ = false;                      // (until the peers' slices are here: witnessGathered)
     }
-    ug_dvec* witnessVec() { return wCur_; }
     void witnessGathered() { witnessLoaded_ = true; }
-    // the staged witness becomes the prover's (proveMutex held)
-    void adopt(StagedWitness& sl) {
+    void adopt(StagedWitness& sl) override {
         wCur_ = sl.buf;
         chunks_.swap(sl.chunks); freq_.swap(sl.freq); wIdx_.swap(sl.wIdx); pIdx_.swap(sl.pIdx);
         publicPart_.swap(sl.publicPart);
@@ -2135,13 +2146,6 @@ public:
     }
     // ---- phases (a sharded proof calls them one by one, see include/prover.h; proveTurn() below strings them together) ----
     // (the caller drives the phases of one proof from one thread and holds no lock)
-    void loadWitness(const void* wtns, unsigned long long wtnsSize) override {
-        if (witnessQueued_ == 1) throw std::invalid_argument("the queued witness products still read the witness (ug_groth16_prover_witness_msm_end)");
-        WitnessLease lease(witness_);
-        stage(*lease, wtns, wtnsSize);
-        std::lock_guard<std::mutex> turn(proveMutex);
-        adopt(*lease);
-    }
 
     // round 1: this rank's part of the commitment to the round witnesses (ultra_groth.cpp:415-419, execute_round :161-184)
     void roundCommit(uint8_t* out64) override {
@@ -2213,19 +2217,6 @@ public:
         inFlight.done();
         witnessQueued_ = 1;
     }
-    void witnessMsmEnd(uint8_t* partials) override {
-        if (!witnessQueued_) throw std::invalid_argument("no witness products queued (ug_groth16_prover_witness_msm_begin)");
-        witnessQueued_ = 0;
-        QueueGuard inFlight(d_.ctx);
-        ugCheck(ug_ctx_collect(d_.ctx));
-        inFlight.done();
-        collectTimings(1);
-        memcpy(partials, queuedParts_, UG_GROTH16_PARTIALS_SIZE);
-    }
-    void witnessMsmAbandon() {
-        if (witnessQueued_ == 1) ug_ctx_abandon(d_.ctx);
-        witnessQueued_ = 0;
-    }
     // MSM1-3 (:201,214,227), the gather of the final witnesses (:439-445) and MSM4 (:234), queued on the witness stream
     void queueFinalRoundProducts(uint8_t* sums) {
         buildSchedule(d_.sw, wCur_, wr_.lo, wr_.hi - wr_.lo, planW_.c, planW_.stride);
@@ -2236,30 +2227,8 @@ public:
         void* outC[1] = {sums + 256};
         ugCheck(ug_msm_batch_enqueue(d_.ctx, 1, setC, d_.saux, nullptr, outC));
     }
-    void hpolyChain(int which, void* deviceOut) override {
+    void requireWitnessForH() const override {
         if (!committed_) throw std::invalid_argument("the round commitment has not been applied");
-        if (!haveHpoly_) throw std::invalid_argument("this rank was created without the coefficient matrix");
-        ug_dvec* v = nullptr;
-        ugCheck(ug_dvec_wrap(d_.ctx2, deviceOut, hdr_.domainSize, &v));
-        int rc = ug_hpoly_chain(d_.hp, wCur_, which, v);
-        ug_dvec_destroy(v);
-        ugCheck(rc);
-        ugCheck(ug_ctx_sync(d_.ctx2));               // the vector is complete when the call returns (the caller sends it on)
-    }
-    void hpolyCombine(void* da, void* db, void* dc) override {
-        uint64_t cnt = hr_.hi - hr_.lo;
-        ug_dvec *a = nullptr, *b = nullptr, *c = nullptr;
-        ugCheck(ug_dvec_wrap(d_.ctx2, da, cnt, &a));
-        ugCheck(ug_dvec_wrap(d_.ctx2, db, cnt, &b));
-        ugCheck(ug_dvec_wrap(d_.ctx2, dc, cnt, &c));
-        int rc = ug_hpoly_combine(d_.hp, a, b, c, hr_.lo, cnt, d_.h);
-        ug_dvec_destroy(a); ug_dvec_destroy(b); ug_dvec_destroy(c);
-        ugCheck(rc);
-    }
-    void hRange(unsigned long long* first, unsigned long long* count, unsigned long long* domain) const override {
-        if (first) *first = hr_.lo;
-        if (count) *count = hr_.hi - hr_.lo;
-        if (domain) *domain = hdr_.domainSize;
     }
     // MSM5 (:322) on this rank's slice of h (which must be in d_.h); only the H record of partials is written
     void runHMsm(uint8_t* partials) override {
@@ -2268,12 +2237,6 @@ public:
         ugCheck(ug_msm_g1(d_.ctx2, d_.H, d_.sh, 0, partials + 320));
         mark("H MSM");
         collectTimings(witnessQueued_ == 1 ? 2 : 3);          // (queued witness products: their stream is read when they are collected)
-    }
-    // device time of both streams since the witness was adopted; which: 1 = witness stream, 2 = H branch (each waits for its stream)
-    void collectTimings(int which) {
-        if (which & 1) ugCheck(ug_ctx_timings(d_.ctx, &m1_, &f1_, 0));
-        if (which & 2) ugCheck(ug_ctx_timings(d_.ctx2, &m2_, &f2_, 0));
-        msmMs_ = m1_ + m2_; fftMs_ = f1_ + f2_;
     }
     // on the rank that ran roundFinish, with the summed partials: r and s (:345-346), the blinded proof, the JSON texts
     void finish(const uint8_t* sums, std::string& proof, std::string& pub) override {
@@ -2404,13 +2367,12 @@ public:
         c.signals[(size_t)b] = parseWitness(c.in[(size_t)b], c.wtns[b], c.sizes[b]);
         checkLookupLists(c.in[(size_t)b]);
     }
-    std::unique_lock<std::mutex> takeTurn(bool /*forProof*/) { return std::unique_lock<std::mutex>(proveMutex); }
     void proveOneOfBatch(BatchCall& c, int b) {
         WitnessLease lease(witness_);
         stage(*lease, c.wtns[b], c.sizes[b]);
         std::lock_guard<std::mutex> turn(proveMutex);
         proveStaged(*lease, c.proofs[(size_t)b], c.pubs[(size_t)b]);
-        c.msm += msmMs_; c.fft += fftMs_;
+        c.msm += m1_ + m2_; c.fft += f1_ + f2_;
     }
     void stagePass(const BatchCall& c, int b0, int V) { batch_.stage(d_.ctx, witness_.stageMutex, &c.signals[(size_t)b0], V, hdr_.nVars); }
     // S: the pass's blinding, in witness order (round randomness :173, then r and s :345-346), and the multiples of the deltas
@@ -2430,7 +2392,7 @@ public:
             p.terms.push_back(std::async(std::launch::async, [this, rk, r, s] { return hostTermsFor(rk, r, s); }));
         }
         runBatch(V, &c.in[(size_t)b0], p.rkw, p.sums.data(), p.commits.data());      // (the futures join in their destructors if this throws)
-        c.msm += msmMs_; c.fft += fftMs_;
+        c.msm += m1_ + m2_; c.fft += f1_ + f2_;
         return p;
     }
     void finishPass(BatchCall& c, int b0, int V, BatchPass& p) {
@@ -2438,7 +2400,6 @@ public:
             finishWith(&p.sums[(size_t)v * UG_GROTH16_PARTIALS_SIZE], &p.r[(size_t)v * 32], &p.s[(size_t)v * 32], p.terms[(size_t)v].get(),
                        &p.commits[(size_t)v * 64], c.in[(size_t)(b0 + v)].publicPart, c.proofs[(size_t)(b0 + v)], c.pubs[(size_t)(b0 + v)]);
     }
-    void setBatchTimings(double msm, double fft, double total) { msmMs_ = msm; fftMs_ = fft; totalMs_ = total; }
 
     // what ug_dvec_apply_lookup refuses, found before anything is queued (its messages, in its order)
     void checkLookupLists(const StagedWitness& w) const {
@@ -2575,12 +2536,6 @@ public:
 public:
     unsigned long long proofBufferMinSize() const override { return PROOF_MIN_ULTRA; }
     unsigned long long publicBufferMinSize() const override { return publicMin((unsigned long long)hdr_.nPublic - 1); }
-    void timings(double* msm, double* fft, double* total) const override {
-        if (msm) *msm = msmMs_;
-        if (fft) *fft = fftMs_;
-        if (total) *total = totalMs_;
-    }
-    ug_ctx* ctx() override { return d_.ctx; }
 
 private:
     static void putPlain(uint8_t* dst, const Fr& v) { u32 w[8]; to_normal(w, v); memcpy(dst, w, 32); }
@@ -2606,8 +2561,6 @@ private:
         }
     }
 
-    ZkeyHeader hdr_;
-    std::vector<uint8_t> vk_;
     void mark(const char* what) {
         if (!trace_) return;
         ug_ctx_sync(d_.ctx); ug_ctx_sync(d_.ctx2);
@@ -2617,27 +2570,12 @@ private:
     }
     std::vector<uint32_t> roundIdx_, finalIdx_;                    // this rank's slices of the zkey's two index lists
     std::vector<uint32_t> chunks_, freq_, wIdx_, pIdx_;            // uwtns sections 3-6 of the loaded witness
-    ug_dvec* wCur_ = nullptr;                                      // the witness the device part reads and patches (d_.w, d_.w2 own the two buffers)
-    WitnessBuffers witness_;
-    std::vector<uint8_t> publicPart_;                              // signals 0..nPublic, patched by the lookup writes
-    Range wr_{0, 0}, hr_{0, 0};
-    uint8_t commitRec_[64] = {0};
+    uint8_t commitRec_[64] = {0};                                  // (publicPart_ of the base is patched by the lookup writes)
     u32 rkw_[8] = {0};
-    bool witnessLoaded_ = false, committed_ = false, haveRoundScalar_ = false, trace_ = false, haveHpoly_ = true;
+    bool witnessLoaded_ = false, committed_ = false, haveRoundScalar_ = false, trace_ = false;
     std::chrono::steady_clock::time_point tPhase_;
-    TableChoice planW_, planC1_, planC2_, planH_;                  // fixed-base tables per schedule group (the B group's: d_.planB)
-    bool sparseB_ = false;             // B1 / B2 kept compacted over the signals with a real B point (DeviceProver)
-    uint64_t nB_ = 0;
-    DeviceProver d_;
-    double msmMs_ = 0, fftMs_ = 0, totalMs_ = 0;
-    double m1_ = 0, f1_ = 0, m2_ = 0, f2_ = 0;                     // device ms per stream (witness stream, H branch)
-    int witnessQueued_ = 0;                                        // witnessMsmBegin .. witnessMsmEnd
-    uint8_t queuedParts_[UG_GROTH16_PARTIALS_SIZE] = {};
+    TableChoice planC1_, planC2_;                                  // fixed-base tables of the round and final groups
     bool batchable_ = false;                                       // a created prover on one device (proveBatch)
-    // batched proofs: V signal vectors / h vectors / gathered round or final scalars / sparse-B scalars
-public:
-    BatchBuffers batch_;                                           // batched proofs (declared after d_: it goes first)
-    ug_ctx* ctx2() { return d_.ctx2; }                             // the H branch's context
 };
 
 
@@ -2677,8 +2615,8 @@ std::vector<int> devicesFromEnv() {
 // rank that also runs chains gets fewer points (the same split bench.py makes for its ranks). (End of round 3: a chain is 5.9 ms
 // since the tiled mat-vec, 7.1 before; with 0.063 / 0.063 / 0.080 a chain rank of eight ended after 21.1 ms, a plain one after
 // 22.1: per point a rank's products cost 6.0 ms per million on top of 4.5 ms that do not depend on the slice.)
+static const double CHAIN_SHARE[3] = {0.058, 0.058, 0.070};
 std::vector<Range> balancedWitnessRanges(uint64_t nVars, int count) {
-    static const double CHAIN_SHARE[3] = {0.058, 0.058, 0.070};
     std::vector<double> extra(count, 0.0), share(count);
     for (int c = 0; c < 3; c++) extra[c % count] += CHAIN_SHARE[c];
     double base = 1.0, tot = 0;
@@ -2707,7 +2645,6 @@ std::vector<Range> balancedWitnessRanges(uint64_t nVars, int count) {
 // share: every rank recodes all scalars of its range, and the kernels behind the accumulation have their latency floor); its H
 // product H_FIXED + H_PART * its share of h. With five ranks or more the chain ranks take no part of the H product at all.
 constexpr double CLASS_FIXED = 0.027, H_FIXED = 0.014, H_PART = 0.175;
-static const double CHAIN_SHARE_CLASSES[3] = {0.058, 0.058, 0.070};
 // device memory a rank needs for the window tables of n witness points and their schedules (planTableWidthsAhead's arithmetic)
 uint64_t classTablesNeed(uint64_t n) {
     if (n < TABLES_MIN_SCALARS || n > TABLES_MAX_SCALARS) return ~(uint64_t)0;
@@ -2752,7 +2689,7 @@ std::vector<ShardLayout> shardLayouts(uint64_t M, uint64_t N, int R, int P) {
     }
     // who takes part in the H product, and every rank's share of the witness entries
     std::vector<double> chain(R, 0.0), hs(R, 0.0), f(R, 0.0);
-    for (int c = 0; c < 3; c++) chain[c % R] += CHAIN_SHARE_CLASSES[c];
+    for (int c = 0; c < 3; c++) chain[c % R] += CHAIN_SHARE[c];
     int takers = 0;
     for (int k = 0; k < R; k++) if (R < 5 || !out[k].chains) takers++;
     double total = 1.0;
@@ -2813,14 +2750,125 @@ std::vector<ShardLayout> shardLayouts(uint64_t M, uint64_t N, int R, int P) {
     return out;
 }
 
-class MultiGroth16Prover : public ProverBase {
+// What MultiGroth16Prover and MultiUltraGrothProver share (Rank: Groth16Prover / UltraGrothProver): the ranks, the evaluation
+// vectors of the three chains with every rank's slices of them, the figures of the last proof, and the FINAL ROUND of a proof --
+// the part that runs the same phases of RankProver on every rank, with the only edges between the ranks.
+template <class Rank>
+class MultiProver : public ProverBase {
+public:
+    ~MultiProver() override {
+        for (auto& s : slices_) for (ug_dvec* v : s.v) ug_dvec_destroy(v);
+        for (ug_dvec* v : full_) ug_dvec_destroy(v);
+    }
+    void timings(double* msm, double* fft, double* total) const override {      // the slowest rank's device time per part
+        if (msm) *msm = msm_;
+        if (fft) *fft = fft_;
+        if (total) *total = total_;
+    }
+    ug_ctx* ctx() override { return ranks_[0]->ctx(); }
+    std::vector<TableGroup> tableGroups() override { return {}; }
+    void trimWorkspaces() override { for (auto& r : ranks_) r->trimWorkspaces(); }
+
+protected:
+    typedef std::function<void(int)> PerRank;
+    // the end of a constructor, the ranks made: the evaluation vectors of the three chains (on the devices of ranks k mod R, on
+    // the H branch's stream) and every rank's slices of them
+    void makeChainVectors(const ZkeyHeader& h) {
+        nPublic_ = h.nPublic; domain_ = h.domainSize; nVars_ = h.nVars;
+        const int R = (int)ranks_.size();
+        for (int c = 0; c < 3; c++) ugCheck(ug_dvec_create(ranks_[c % R]->ctx2(), domain_, &full_[c]));
+        slices_.resize(R);
+        for (int k = 0; k < R; k++) {
+            unsigned long long first = 0, cnt = 0;
+            ranks_[k]->hRange(&first, &cnt, nullptr);
+            for (int c = 0; c < 3; c++) ugCheck(ug_dvec_create(ranks_[k]->ctx2(), cnt ? cnt : 1, &slices_[k].v[c]));
+        }
+    }
+    // body(k) on one host thread per rank; every rank's failure is kept and the first in rank order rethrown once all have ended
+    void everyRank(const PerRank& body) {
+        const int R = (int)ranks_.size();
+        std::vector<std::exception_ptr> errs(R);
+        std::vector<std::thread> th;
+        for (int k = 0; k < R; k++) th.emplace_back([&, k] { try { body(k); } catch (...) { errs[k] = std::current_exception(); } });
+        for (auto& t : th) t.join();
+        for (auto& e : errs) if (e) std::rethrow_exception(e);
+    }
+    // THE FINAL ROUND, on every rank at once (everyRank); sums = the ranks' partial blocks added. On every rank both streams are
+    // busy: the witness products are queued and left to run (witnessMsmBegin); the rank's chains, the copies of its slices of the
+    // three evaluation vectors, its combine and its H product go to its second stream meanwhile. The only edges between ranks
+    // are the three "chain c is complete" events: a rank that waits for them spends that time on its witness products.
+    //   before(k)         what rank k needs before its products may be queued (its witness scalars / the round commitment)
+    //   beforeChains(k)   optional; what a chain rank needs on top of that before its chains (Groth16: the rest of the witness),
+    //                     called when the products are already queued unless the chain goes first
+    // A rank that fails -- in a callable or a phase -- tells the chains it owes as failed, so that no rank waits for a chain that
+    // will not come, and gives up its queued products.
+    void finalRound(const PerRank& before, const PerRank& beforeChains, uint8_t* sums) {
+        const int R = (int)ranks_.size();
+        std::vector<std::array<uint8_t, UG_GROTH16_PARTIALS_SIZE>> parts(R);
+        std::promise<void> chainDone[3];
+        std::shared_future<void> chainReady[3];
+        for (int c = 0; c < 3; c++) chainReady[c] = chainDone[c].get_future().share();
+        // with many ranks most of them wait for the chains: a chain rank then runs its chain first, alone (a chain beside the
+        // products gets ~40 % of the chip whatever the stream priorities say, 17 ms instead of 7 at 2^24 / 8 ranks); with few
+        // ranks it runs beside the products (bench.py: UG_BENCH_CHAIN_ORDER)
+        const bool chainFirst = R >= 5;
+        everyRank([&](int k) {
+            Rank& p = *ranks_[k];
+            bool told[3] = {false, false, false};
+            try {
+                before(k);
+                if (!chainFirst) p.witnessMsmBegin();
+                if (k < 3 && beforeChains) beforeChains(k);
+                for (int c = k; c < 3; c += R) {                        // chains k, k + R, ... of the three
+                    p.hpolyChain(c, ug_dvec_device_ptr(full_[c]));
+                    told[c] = true;
+                    chainDone[c].set_value();
+                }
+                if (chainFirst) p.witnessMsmBegin();
+                for (int c = 0; c < 3; c++) chainReady[c].get();        // (a chain rank's failure is rethrown here)
+                unsigned long long first = 0, cnt = 0;
+                p.hRange(&first, &cnt, nullptr);
+                for (int c = 0; c < 3 && cnt; c++) ugCheck(ug_dvec_copy(slices_[k].v[c], 0, full_[c], first, cnt));
+                p.hpolyCombine(ug_dvec_device_ptr(slices_[k].v[0]), ug_dvec_device_ptr(slices_[k].v[1]), ug_dvec_device_ptr(slices_[k].v[2]));
+                uint8_t hpart[UG_GROTH16_PARTIALS_SIZE];
+                p.runHMsm(hpart);
+                p.witnessMsmEnd(parts[k].data());
+                memcpy(parts[k].data() + 320, hpart + 320, 64);
+            } catch (...) {
+                for (int c = k; c < 3; c += R)
+                    if (!told[c]) chainDone[c].set_exception(std::current_exception());
+                p.witnessMsmAbandon();
+                throw;
+            }
+        });
+        for (int k = 1; k < R; k++)
+            if (ug_groth16_partials_add(parts[0].data(), parts[k].data()) != PROVER_OK) throw std::runtime_error("partial sum failed");
+        memcpy(sums, parts[0].data(), UG_GROTH16_PARTIALS_SIZE);
+    }
+    // rank 0 blinds and serialises; the figures of the proof that began at t0
+    void finishProof(const uint8_t* sums, std::string& proof, std::string& pub, std::chrono::steady_clock::time_point t0) {
+        ranks_[0]->finish(sums, proof, pub);
+        msm_ = fft_ = 0;
+        for (auto& r : ranks_) { double m = 0, f = 0; r->timings(&m, &f, nullptr); msm_ = std::max(msm_, m); fft_ = std::max(fft_, f); }
+        total_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+
+    struct Slices { ug_dvec* v[3] = {nullptr, nullptr, nullptr}; };
+    std::vector<std::unique_ptr<Rank>> ranks_;
+    ug_dvec* full_[3] = {nullptr, nullptr, nullptr};
+    std::vector<Slices> slices_;
+    uint32_t nPublic_ = 0, domain_ = 0;
+    uint64_t nVars_ = 0;
+    double msm_ = 0, fft_ = 0, total_ = 0;
+};
+
+class MultiGroth16Prover : public MultiProver<Groth16Prover> {
 public:
     MultiGroth16Prover(const void* zkey, unsigned long long zkeySize, const std::vector<int>& devices) {
         const int R = (int)devices.size();
         BinFile f(zkey, zkeySize, "zkey", 1);
         ZkeyHeader h = loadZkeyHeader(f, false);
         if (!h.rIsBn254) throw std::invalid_argument("zkey curve not supported");
-        nPublic_ = h.nPublic; domain_ = h.domainSize; nVars_ = h.nVars;
         // the layout (shardLayouts): base-point ranges, unless ULTRAGROTH_SHARD asks for bucket classes (PxB, or auto: when the
         // tables of a group's range fit the devices, asked from the first one); if a class rank then cannot build its tables after
         // all, everything is created once more with base-point ranges
@@ -2862,35 +2910,13 @@ public:
             if (P == R || !tablesOrMemory) std::rethrow_exception(failure);
             P = R;
         }
-        // the evaluation vectors of the three chains (on the devices of ranks k mod R) and every rank's slices of them
-        for (int c = 0; c < 3; c++) {
-            ugCheck(ug_dvec_create(ranks_[c % R]->ctx2(), domain_, &full_[c]));
-        }
-        slices_.resize(R);
-        for (int k = 0; k < R; k++) {
-            unsigned long long first = 0, cnt = 0;
-            ranks_[k]->hRange(&first, &cnt, nullptr);
-            for (int c = 0; c < 3; c++) ugCheck(ug_dvec_create(ranks_[k]->ctx2(), cnt ? cnt : 1, &slices_[k].v[c]));
-        }
-    }
-    ~MultiGroth16Prover() override {
-        for (auto& s : slices_) for (ug_dvec* v : s.v) ug_dvec_destroy(v);
-        for (ug_dvec* v : full_) ug_dvec_destroy(v);
+        makeChainVectors(h);
     }
     void prove(const void* wtns, unsigned long long wtnsSize, std::string& proof, std::string& pub) override {
         const auto t0 = std::chrono::steady_clock::now();
         const int R = (int)ranks_.size();
         // checked once here (every rank checks again): the reference's error for a wrong witness comes before any device work
-        { BinFile f(wtns, wtnsSize, "wtns", 2); (void)ranks_[0]->witnessData(f); }
-        std::vector<std::array<uint8_t, UG_GROTH16_PARTIALS_SIZE>> parts(R);
-        std::vector<std::exception_ptr> errs(R);
-        // One host thread per rank, and on every rank both streams busy: the witness products are queued first and left to
-        // run (witnessMsmBegin); the rank's chains, the copies of its slices of the three evaluation vectors, its combine and
-        // its H product go to its second, high-priority stream meanwhile. The only edges between ranks are the three "chain c
-        // is complete" events: a rank that waits for them spends that time on its witness products.
-        std::promise<void> chainDone[3];
-        std::shared_future<void> chainReady[3];
-        for (int c = 0; c < 3; c++) chainReady[c] = chainDone[c].get_future().share();
+        { BinFile f(wtns, wtnsSize, "wtns", 2); (void)ranks_[0]->checkedWitness(f); }
         // THE WITNESS ON A NODE: every rank copies its own slice of the scalars over its own PCIe link (all links at once); a
         // chain rank, whose mat-vec reads the WHOLE witness, then collects the other slices from its peers' HBM over xGMI
         // (ug_dvec_copy_via: hipMemcpyPeerAsync) instead of pulling all of it through its one link -- 512 MiB at 2^24: 9.4 ms by
@@ -2902,116 +2928,60 @@ public:
         std::vector<std::promise<void>> sliceUp(R);
         std::vector<std::shared_future<void>> sliceReady(R);
         for (int k = 0; k < R; k++) sliceReady[k] = sliceUp[k].get_future().share();
-        {
-            std::vector<std::thread> th;
-            for (int k = 0; k < R; k++)
-                th.emplace_back([&, k] {
-                    Groth16Prover& p = *ranks_[k];
-                    bool told[3] = {false, false, false};
-                    bool toldSlice = false;
-                    try {
-                        p.loadWitnessPart(wtns, wtnsSize, 0);
-                        toldSlice = true;
-                        sliceUp[k].set_value();
-                        // with many ranks most of them wait for the chains: a chain rank then runs its chain first, alone (a
-                        // chain beside the products gets ~40 % of the chip whatever the stream priorities say, 17 ms instead of
-                        // 7 at 2^24 / 8 ranks); with few ranks it runs beside the products (bench.py: UG_BENCH_CHAIN_ORDER)
-                        const bool chainFirst = R >= 5;
-                        if (!chainFirst) p.witnessMsmBegin();
-                        if (k < 3) {                                       // chains k, k + R, ... of the three
-                            if (gather) {
-                                uint64_t covered = 0;                      // [0, covered) of the witness is on this rank or on its way
-                                const Range mine = p.witnessRange();
-                                for (int q = 0; q < R; q++) {
-                                    const Range w = q == k ? mine : ranks_[q]->witnessRange();
-                                    const uint64_t lo = std::max(w.lo, covered);
-                                    if (w.hi <= lo) continue;
-                                    if (q != k && !(lo >= mine.lo && w.hi <= mine.hi)) {
-                                        sliceReady[q].get();               // (a peer's failed upload is rethrown here)
-                                        // the part of it this rank does not hold itself
-                                        const uint64_t a = lo, b = w.hi;
-                                        const uint64_t a1 = std::min(b, std::max(a, mine.lo)), b1 = std::max(a, std::min(b, mine.hi));
-                                        if (a1 > a) ugCheck(ug_dvec_copy_via(p.witnessVec(), a, ranks_[q]->witnessVec(), a, a1 - a, p.ctx2()));
-                                        if (b > b1) ugCheck(ug_dvec_copy_via(p.witnessVec(), std::max(b1, a), ranks_[q]->witnessVec(), std::max(b1, a), b - std::max(b1, a), p.ctx2()));
-                                    }
-                                    covered = std::max(covered, w.hi);
-                                }
-                                if (covered < nVars_) throw std::logic_error("the ranks' witness ranges do not cover the witness");
-                                p.witnessGathered();
-                            } else p.loadWitnessPart(wtns, wtnsSize, 1);
-                            for (int c = k; c < 3; c += R) {
-                                p.hpolyChain(c, ug_dvec_device_ptr(full_[c]));
-                                told[c] = true;
-                                chainDone[c].set_value();
-                            }
-                        }
-                        if (chainFirst) p.witnessMsmBegin();
-                        for (int c = 0; c < 3; c++) chainReady[c].get();    // (a chain rank's failure is rethrown here)
-                        unsigned long long first = 0, cnt = 0;
-                        p.hRange(&first, &cnt, nullptr);
-                        for (int c = 0; c < 3 && cnt; c++) ugCheck(ug_dvec_copy(slices_[k].v[c], 0, full_[c], first, cnt));
-                        p.hpolyCombine(ug_dvec_device_ptr(slices_[k].v[0]), ug_dvec_device_ptr(slices_[k].v[1]), ug_dvec_device_ptr(slices_[k].v[2]));
-                        uint8_t hpart[UG_GROTH16_PARTIALS_SIZE];
-                        p.runHMsm(hpart);
-                        p.witnessMsmEnd(parts[k].data());
-                        memcpy(parts[k].data() + 320, hpart + 320, 64);
-                    } catch (...) {
-                        errs[k] = std::current_exception();
-                        if (!toldSlice) sliceUp[k].set_exception(errs[k]);  // nobody may wait for a slice or a chain that will not come
-                        for (int c = k; c < 3; c += R)
-                            if (k < 3 && !told[c]) chainDone[c].set_exception(errs[k]);
-                        p.witnessMsmAbandon();
-                    }
-                });
-            for (auto& t : th) t.join();
-        }
-        for (auto& e : errs) if (e) std::rethrow_exception(e);
-        for (int k = 1; k < R; k++)
-            if (ug_groth16_partials_add(parts[0].data(), parts[k].data()) != PROVER_OK) throw std::runtime_error("partial sum failed");
-        ranks_[0]->finish(parts[0].data(), proof, pub);
-        msm_ = fft_ = 0;
-        for (auto& r : ranks_) { double m = 0, f = 0; r->timings(&m, &f, nullptr); msm_ = std::max(msm_, m); fft_ = std::max(fft_, f); }
-        total_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        // this rank's scalars; the slice is published (or its failure: nobody may wait for a slice that will not come)
+        auto ownSlice = [&](int k) {
+            try { ranks_[k]->loadWitnessPart(wtns, wtnsSize, 0); }
+            catch (...) { sliceUp[k].set_exception(std::current_exception()); throw; }
+            sliceUp[k].set_value();
+        };
+        // the rest of the witness on a chain rank
+        auto restOfWitness = [&](int k) {
+            Groth16Prover& p = *ranks_[k];
+            if (!gather) { p.loadWitnessPart(wtns, wtnsSize, 1); return; }
+            uint64_t covered = 0;                      // [0, covered) of the witness is on this rank or on its way
+            const Range mine = p.witnessRange();
+            for (int q = 0; q < R; q++) {
+                const Range w = q == k ? mine : ranks_[q]->witnessRange();
+                const uint64_t lo = std::max(w.lo, covered);
+                if (w.hi <= lo) continue;
+                if (q != k && !(lo >= mine.lo && w.hi <= mine.hi)) {
+                    sliceReady[q].get();               // (a peer's failed upload is rethrown here)
+                    // the part of it this rank does not hold itself
+                    const uint64_t a = lo, b = w.hi;
+                    const uint64_t a1 = std::min(b, std::max(a, mine.lo)), b1 = std::max(a, std::min(b, mine.hi));
+                    if (a1 > a) ugCheck(ug_dvec_copy_via(p.witnessVec(), a, ranks_[q]->witnessVec(), a, a1 - a, p.ctx2()));
+                    if (b > b1) ugCheck(ug_dvec_copy_via(p.witnessVec(), std::max(b1, a), ranks_[q]->witnessVec(), std::max(b1, a), b - std::max(b1, a), p.ctx2()));
+                }
+                covered = std::max(covered, w.hi);
+            }
+            if (covered < nVars_) throw std::logic_error("the ranks' witness ranges do not cover the witness");
+            p.witnessGathered();
+        };
+        uint8_t sums[UG_GROTH16_PARTIALS_SIZE];
+        finalRound(ownSlice, restOfWitness, sums);
+        finishProof(sums, proof, pub, t0);
     }
     unsigned long long proofBufferMinSize() const override { return PROOF_MIN_GROTH16; }
     unsigned long long publicBufferMinSize() const override { return publicMin(nPublic_); }
-    void timings(double* msm, double* fft, double* total) const override {      // the slowest rank's device time per part
-        if (msm) *msm = msm_;
-        if (fft) *fft = fft_;
-        if (total) *total = total_;
-    }
-    ug_ctx* ctx() override { return ranks_[0]->ctx(); }
-    std::vector<TableGroup> tableGroups() override { return {}; }
-    void trimWorkspaces() override { for (auto& r : ranks_) r->trimWorkspaces(); }
     int kernelStats(int which, double* avgMs, unsigned long long* launches, unsigned long long* entries, int reset) override {
         return ranks_[0]->kernelStats(which, avgMs, launches, entries, reset);
     }
-    int rankCount() const { return (int)ranks_.size(); }
 
 private:
-    struct Slices { ug_dvec* v[3] = {nullptr, nullptr, nullptr}; };
-    std::vector<std::unique_ptr<Groth16Prover>> ranks_;
     std::vector<ShardLayout> layouts_;
-    ug_dvec* full_[3] = {nullptr, nullptr, nullptr};
-    std::vector<Slices> slices_;
-    uint32_t nPublic_ = 0, domain_ = 0;
-    uint64_t nVars_ = 0;
-    double msm_ = 0, fft_ = 0, total_ = 0;
 };
 
 // The same for UltraGroth (src/ultra_groth.cpp:401-462): every rank keeps the whole witness and owns slices of the
 // witness-indexed sets, the round set, the final set and H. Per proof: the 64-byte parts of the round commitment are added on
 // the host, rank 0 closes the round (:173-176), every rank derives the challenge and completes its witness (:33-106), then
-// the final round runs as the Groth16 phases do (witness products queued, the H branch on its second stream beside them);
-// rank 0 blinds and serialises.
-class MultiUltraGrothProver : public ProverBase {
+// the final round runs (MultiProver::finalRound); rank 0 blinds and serialises.
+class MultiUltraGrothProver : public MultiProver<UltraGrothProver> {
 public:
     MultiUltraGrothProver(const void* zkey, unsigned long long zkeySize, const std::vector<int>& devices) {
         const int R = (int)devices.size();
         BinFile f(zkey, zkeySize, "zkey", 1);
         ZkeyHeader h = loadZkeyHeader(f, true);
         if (!h.rIsBn254) throw std::invalid_argument("zkey curve not supported");
-        nPublic_ = h.nPublic; domain_ = h.domainSize; nVars_ = h.nVars;
         ranks_.resize(R);
         const bool oneShot = g_oneShotProver;
         std::vector<std::future<void>> jobs;
@@ -3023,28 +2993,11 @@ public:
         std::exception_ptr failure;
         for (auto& j : jobs) { try { j.get(); } catch (...) { if (!failure) failure = std::current_exception(); } }
         if (failure) { ranks_.clear(); std::rethrow_exception(failure); }
-        for (int c = 0; c < 3; c++) ugCheck(ug_dvec_create(ranks_[c % R]->ctx2(), domain_, &full_[c]));      // (the H branch's stream)
-        slices_.resize(R);
-        for (int k = 0; k < R; k++) {
-            unsigned long long first = 0, cnt = 0;
-            ranks_[k]->hRange(&first, &cnt, nullptr);
-            for (int c = 0; c < 3; c++) ugCheck(ug_dvec_create(ranks_[k]->ctx2(), cnt ? cnt : 1, &slices_[k].v[c]));
-        }
-    }
-    ~MultiUltraGrothProver() override {
-        for (auto& s : slices_) for (ug_dvec* v : s.v) ug_dvec_destroy(v);
-        for (ug_dvec* v : full_) ug_dvec_destroy(v);
+        makeChainVectors(h);
     }
     void prove(const void* wtns, unsigned long long wtnsSize, std::string& proof, std::string& pub) override {
         const auto t0 = std::chrono::steady_clock::now();
         const int R = (int)ranks_.size();
-        std::vector<std::exception_ptr> errs(R);
-        auto everyRank = [&](const std::function<void(int)>& body) {
-            std::vector<std::thread> th;
-            for (int k = 0; k < R; k++) th.emplace_back([&, k] { try { body(k); } catch (...) { errs[k] = std::current_exception(); } });
-            for (auto& t : th) t.join();
-            for (auto& e : errs) if (e) std::rethrow_exception(e);
-        };
         // round 1: the commitment to the round witnesses, part by part. Every rank needs the whole witness (the lookup completion
         // rewrites signals anywhere in it): each copies ITS R-th over its own PCIe link, then collects the others from its peers'
         // HBM (peer copies over xGMI; 128 MiB at 2^22: 3.1 ms per rank through one link, ~0.9 ms this way).
@@ -3069,67 +3022,12 @@ public:
         for (int k = 1; k < R; k++) if (ug_g1_record_add(cparts[0].data(), cparts[k].data()) != PROVER_OK) throw std::runtime_error("partial sum failed");
         uint8_t commit[64];
         ranks_[0]->roundFinish(cparts[0].data(), commit);
-        // final round: as MultiGroth16Prover -- the witness products of every rank queued (witnessMsmBegin), its H branch driven
-        // beside them on its second stream; the only edges between the ranks are the three "chain c is complete" events
-        std::vector<std::array<uint8_t, UG_GROTH16_PARTIALS_SIZE>> parts(R);
-        std::promise<void> chainDone[3];
-        std::shared_future<void> chainReady[3];
-        for (int c = 0; c < 3; c++) chainReady[c] = chainDone[c].get_future().share();
-        everyRank([&](int k) {
-            UltraGrothProver& p = *ranks_[k];
-            bool told[3] = {false, false, false};
-            try {
-                p.applyCommitment(commit);
-                const bool chainFirst = R >= 5;                         // (see MultiGroth16Prover::prove)
-                if (!chainFirst) p.witnessMsmBegin();
-                for (int c = k; c < 3; c += R) {
-                    p.hpolyChain(c, ug_dvec_device_ptr(full_[c]));
-                    told[c] = true;
-                    chainDone[c].set_value();
-                }
-                if (chainFirst) p.witnessMsmBegin();
-                for (int c = 0; c < 3; c++) chainReady[c].get();        // (a chain rank's failure is rethrown here)
-                unsigned long long first = 0, cnt = 0;
-                p.hRange(&first, &cnt, nullptr);
-                for (int c = 0; c < 3; c++) ugCheck(ug_dvec_copy(slices_[k].v[c], 0, full_[c], first, cnt));
-                p.hpolyCombine(ug_dvec_device_ptr(slices_[k].v[0]), ug_dvec_device_ptr(slices_[k].v[1]), ug_dvec_device_ptr(slices_[k].v[2]));
-                uint8_t hpart[UG_GROTH16_PARTIALS_SIZE];
-                p.runHMsm(hpart);
-                p.witnessMsmEnd(parts[k].data());
-                memcpy(parts[k].data() + 320, hpart + 320, 64);
-            } catch (...) {
-                for (int c = k; c < 3; c += R)                          // nobody may wait for a chain that will not come
-                    if (!told[c]) chainDone[c].set_exception(std::current_exception());
-                p.witnessMsmAbandon();
-                throw;
-            }
-        });
-        for (int k = 1; k < R; k++)
-            if (ug_groth16_partials_add(parts[0].data(), parts[k].data()) != PROVER_OK) throw std::runtime_error("partial sum failed");
-        ranks_[0]->finish(parts[0].data(), proof, pub);
-        msm_ = fft_ = 0;
-        for (auto& r : ranks_) { double m = 0, f = 0; r->timings(&m, &f, nullptr); msm_ = std::max(msm_, m); fft_ = std::max(fft_, f); }
-        total_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        uint8_t sums[UG_GROTH16_PARTIALS_SIZE];
+        finalRound([&](int k) { ranks_[k]->applyCommitment(commit); }, PerRank(), sums);
+        finishProof(sums, proof, pub, t0);
     }
     unsigned long long proofBufferMinSize() const override { return PROOF_MIN_ULTRA; }
     unsigned long long publicBufferMinSize() const override { return publicMin((unsigned long long)nPublic_ - 1); }
-    void timings(double* msm, double* fft, double* total) const override {
-        if (msm) *msm = msm_;
-        if (fft) *fft = fft_;
-        if (total) *total = total_;
-    }
-    ug_ctx* ctx() override { return ranks_[0]->ctx(); }
-    std::vector<TableGroup> tableGroups() override { return {}; }
-    void trimWorkspaces() override { for (auto& r : ranks_) r->trimWorkspaces(); }
-
-private:
-    struct Slices { ug_dvec* v[3] = {nullptr, nullptr, nullptr}; };
-    std::vector<std::unique_ptr<UltraGrothProver>> ranks_;
-    ug_dvec* full_[3] = {nullptr, nullptr, nullptr};
-    std::vector<Slices> slices_;
-    uint32_t nPublic_ = 0, domain_ = 0;
-    uint64_t nVars_ = 0;
-    double msm_ = 0, fft_ = 0, total_ = 0;
 };
 
 ProverBase* newUltraGrothProver(const void* zkey, unsigned long long size) {
@@ -3385,9 +3283,7 @@ int proveImpl(void* prover_object, const void* wtns_buffer, unsigned long long w
         // of the next call is copied there while they wait)
         prover->proveTurn(wtns_buffer, wtns_size, stringProof, stringPublic);
     }
-    checkBufferSizes(stringProof.length(), proof_size, stringPublic.length(), public_size, "Required");
-    std::strncpy(proof_buffer, stringProof.c_str(), *proof_size);
-    std::strncpy(public_buffer, stringPublic.c_str(), *public_size);
+    returnProof(stringProof, stringPublic, proof_buffer, proof_size, public_buffer, public_size);
     API_CATCH
 }
 int publicSizeImpl(const void* zkey, unsigned long long size, bool ultra, unsigned long long* public_size, char* error_msg,
@@ -3648,9 +3544,7 @@ int ug_registry_prove(void* registry, const char* circuit, const void* wtns_buff
     if (public_size == NULL) throw std::invalid_argument("Null public size");
     std::string stringProof, stringPublic;
     static_cast<Registry*>(registry)->prove(circuit, wtns_buffer, wtns_size, stringProof, stringPublic, proof_size, public_size);
-    checkBufferSizes(stringProof.length(), proof_size, stringPublic.length(), public_size, "Required");
-    std::strncpy(proof_buffer, stringProof.c_str(), *proof_size);
-    std::strncpy(public_buffer, stringPublic.c_str(), *public_size);
+    returnProof(stringProof, stringPublic, proof_buffer, proof_size, public_buffer, public_size);
     API_CATCH
 }
 int ug_registry_evict(void* registry, const char* circuit, char* error_msg, unsigned long long error_msg_maxsize) {
@@ -3818,9 +3712,7 @@ int ug_groth16_prover_prove_resident(void* prover_object, char* proof_buffer, un
     checkBufferSizes(prover->proofBufferMinSize(), proof_size, prover->publicBufferMinSize(), public_size, "Minimum");
     std::string stringProof, stringPublic;
     prover->proveResident(stringProof, stringPublic);
-    checkBufferSizes(stringProof.length(), proof_size, stringPublic.length(), public_size, "Required");
-    std::strncpy(proof_buffer, stringProof.c_str(), *proof_size);
-    std::strncpy(public_buffer, stringPublic.c_str(), *public_size);
+    returnProof(stringProof, stringPublic, proof_buffer, proof_size, public_buffer, public_size);
     API_CATCH
 }
 int ug_groth16_prover_run(void* prover_object, void* partials_out, char* error_msg, unsigned long long error_msg_maxsize) {
@@ -3956,9 +3848,7 @@ int ug_groth16_prover_finish(void* prover_object, const void* partials_sum, char
     checkBufferSizes(prover->proofBufferMinSize(), proof_size, prover->publicBufferMinSize(), public_size, "Minimum");
     std::string stringProof, stringPublic;
     prover->finish(static_cast<const uint8_t*>(partials_sum), stringProof, stringPublic);
-    checkBufferSizes(stringProof.length(), proof_size, stringPublic.length(), public_size, "Required");
-    std::strncpy(proof_buffer, stringProof.c_str(), *proof_size);
-    std::strncpy(public_buffer, stringPublic.c_str(), *public_size);
+    returnProof(stringProof, stringPublic, proof_buffer, proof_size, public_buffer, public_size);
     API_CATCH
 }
 
