@@ -12,7 +12,7 @@
  *       (the base arrays are the zkey sections handed to makeProver, src/groth16.cpp:9-46,
  *        src/prover.cpp:162-178)
  *
- *   ug_hpoly_create / ug_hpoly_run
+ *   ug_hpoly_create / ug_hpoly_run / ug_hpoly_run_vectors
  *       FFT<Fr>(2 * domainSize) ctor            src/groth16.hpp:109
  *       the a/b/c block of Prover::prove        src/groth16.cpp:66-148
  *         (zero, sparse coefficient scatter-add, a o b, 3 x {ifft, root(.) twist, fft}, a o b - c,
@@ -51,6 +51,11 @@
  *                      ULTRAGROTH_SPARSE_B=0      keep B1 / B2 dense (default: when at most 3/4 of a circuit's B points are real, the prover
  *                                                 keeps only those, with a schedule of its own over their scalars: -15 % per proof at
  *                                                 2^24 with half of the B points at infinity, -26 % with three quarters)
+ *                      ULTRAGROTH_BATCH_HPOLY=1   a batched proof runs the H-polynomial block of a device pass as ONE
+ *                                                 ug_hpoly_run_vectors call, in launch groups as large as the memory left beside the
+ *                                                 pass allows (0 / unset, the default: once per witness; the same proofs either way;
+ *                                                 the FFT time of a pass falls 1.6-2.9x, the time per proof does not move, and 2^24
+ *                                                 is unmeasured: profiles/batch_hpoly_ab.txt)
  *                      ULTRAGROTH_TAILS=split     the G1 and G2 tails of the witness products side by side on two streams (exact; a wash)
  *                      ULTRAGROTH_FUSED=0         A, B1, C as separate base sets instead of one interleaved group
  *                      ULTRAGROTH_SHARD=PxB       many-device layout: P base-point ranges x B bucket classes
@@ -372,6 +377,7 @@ void ug_ctx_abandon(ug_ctx* ctx);
 int  ug_sort_plan(int bits, int shift[4], int bins_log[4]);
 #define UG_FAULT_HPOLY_RUN 1
 #define UG_FAULT_SCHEDULE_BUILD 2
+#define UG_FAULT_HPOLY_RESERVE 3       /* ug_hpoly_reserve_vectors, with three of the five new workspaces allocated */
 int  ug_test_inject_fault(int site, int after);
 
 /* coefs: n_coefs packed 44-byte records {u32 m, u32 c, u32 s, Fr coef} (zkey section 4 past its 4-byte
@@ -380,6 +386,25 @@ int  ug_hpoly_create(ug_ctx* ctx, const void* host_coefs, uint64_t n_coefs, uint
                      uint32_t n_vars, ug_hpoly** out);
 /* h (domain_size plain integers) from the witness (n_vars plain integers), all on the device */
 int  ug_hpoly_run(ug_hpoly* hp, const ug_dvec* witness, ug_dvec* h_out);
+/* The block for `vectors` witnesses in one call (1 <= vectors <= UG_BATCH_MAX; the V witnesses of a batched proof): vector v reads
+ * witness[v * witness_stride, + n_vars) and writes h_out[v * h_stride, + domain_size) -- byte for byte what ug_hpoly_run writes for
+ * that witness -- and nothing else of h_out (the gaps of a strided h_out keep their contents; as in the single call, a vector's h
+ * slice may serve as a work buffer before its result lands there). The vectors go in launch groups of the reserved size (the last
+ * one may be smaller): a group's matrix-vector products are ONE launch that reads every coefficient once per four witnesses, and
+ * each of its NTT passes is ONE launch over all its vectors. ug_hpoly_reserve_vectors gives the handle workspaces for `group`
+ * vectors side by side, ug_hpoly_vectors_bytes(domain_size, group) bytes = group * 5 * 32 * domain_size; a created handle has
+ * group 1 (run_vectors is then a loop of single-witness launches, and vectors = 1 queues exactly what ug_hpoly_run queues). A
+ * reservation waits for the context's stream. A larger one allocates before it frees: if it does not fit it fails with UG_ERROR
+ * and leaves the old one in use. A smaller one frees first, so that giving memory back never needs memory.
+ * ug_hpoly_group: the largest launch group of the last ug_hpoly_run_vectors call, min(vectors, reserved group) (before any such
+ * call: the reserved group). UG_ERROR with the reason in ug_last_error for: vectors outside 1 .. UG_BATCH_MAX, witness_stride <
+ * n_vars, h_stride < domain_size, a vector shorter than its last slice. No host wait; may be recorded (ug_graph_begin). The
+ * fault site UG_FAULT_HPOLY_RUN is passed once per witness. */
+int      ug_hpoly_run_vectors(ug_hpoly* hp, const ug_dvec* witness, uint64_t witness_stride, int vectors,
+                              ug_dvec* h_out, uint64_t h_stride);
+int      ug_hpoly_reserve_vectors(ug_hpoly* hp, int group);   /* workspaces for `group` vectors side by side; 1..UG_BATCH_MAX */
+int      ug_hpoly_group(const ug_hpoly* hp);                  /* vectors per launch group that the last run_vectors call used */
+uint64_t ug_hpoly_vectors_bytes(uint32_t domain_size, int group);
 /* The same block in two steps, for a prover sharded over GPUs: ug_hpoly_chain computes the coset evaluations of
  * ONE of the three polynomials (which = 0: A.w, 1: B.w, 2: (A.w) o (B.w)) -- ranks take different polynomials and
  * exchange slices -- and ug_hpoly_combine turns matching slices of the three vectors into h[first, first+count).

@@ -53,7 +53,7 @@ def set_test_blinding(data):
         raise ProverError(PROVER_ERROR, "test hooks are off: start the process with ULTRAGROTH_TEST_HOOKS=1")
 
 
-FAULT_HPOLY_RUN, FAULT_SCHEDULE_BUILD = 1, 2
+FAULT_HPOLY_RUN, FAULT_SCHEDULE_BUILD, FAULT_HPOLY_RESERVE = 1, 2, 3
 
 
 def inject_fault(site, after=1):
@@ -1013,7 +1013,33 @@ class _HPoly(_Handle):
         _check(self.dev._L.ug_hpoly_run(self.h, wtns_dvec.h, out.h))
         return out
 
+    def run_vectors(self, wtns_dvec, stride, vectors, out=None, h_stride=None):
+        """ug_hpoly_run_vectors: the block for `vectors` witnesses, witness v at element v * stride of wtns_dvec; h vector v at
+        element v * h_stride (default: the domain) of `out` (default: a fresh device vector), which is returned"""
+        h_stride = self.domain if h_stride is None else h_stride
+        if out is None:
+            out = self.dev.dvec(max(vectors, 1) * h_stride)
+        _check(self.dev._L.ug_hpoly_run_vectors(self.h, wtns_dvec.h, stride, vectors, out.h, h_stride))
+        return out
+
+    def reserve_vectors(self, g):
+        """ug_hpoly_reserve_vectors: workspaces for launch groups of g vectors (hpoly_vectors_bytes(domain, g) bytes)"""
+        _check(self.dev._L.ug_hpoly_reserve_vectors(self.h, g))
+
+    @property
+    def group(self):
+        """ug_hpoly_group: the largest launch group of the last run_vectors call (before any: the reserved group)"""
+        return self.dev._L.ug_hpoly_group(self.h)
+
     def debug_abc(self):
         bufs = [C.create_string_buffer(self.domain * 32) for _ in range(3)]
         _check(self.dev._L.ug_hpoly_debug_abc(self.h, *bufs))
         return [b.raw for b in bufs]
+
+
+HPoly = _HPoly
+
+
+def hpoly_vectors_bytes(domain, group):
+    """ug_hpoly_vectors_bytes: what the H-polynomial workspaces for launch groups of `group` vectors take"""
+    return load().ug_hpoly_vectors_bytes(domain, group)

@@ -21,7 +21,8 @@ INNER_SYMBOLS = [
     "ug_dvec_create", "ug_dvec_upload", "ug_dvec_upload_range", "ug_dvec_upload_idle", "ug_dvec_download", "ug_dvec_gather", "ug_dvec_scatter", "ug_dvec_apply_lookup", "ug_fr_lookup_table", "ug_index_create", "ug_index_destroy", "ug_dvec_gather_index", "ug_dvec_wrap", "ug_dvec_size", "ug_dvec_destroy",
     "ug_schedule_create", "ug_schedule_build", "ug_schedule_destroy", "ug_schedule_set_classes",
     "ug_msm_g1", "ug_msm_g2", "ug_msm_batch", "ug_msm_batch_enqueue", "ug_ctx_collect", "ug_ctx_wait",
-    "ug_hpoly_create", "ug_hpoly_run", "ug_hpoly_chain", "ug_hpoly_combine", "ug_hpoly_debug_abc", "ug_hpoly_destroy",
+    "ug_hpoly_create", "ug_hpoly_run", "ug_hpoly_run_vectors", "ug_hpoly_reserve_vectors", "ug_hpoly_group",
+    "ug_hpoly_vectors_bytes", "ug_hpoly_chain", "ug_hpoly_combine", "ug_hpoly_debug_abc", "ug_hpoly_destroy",
     "ug_fr_ntt", "ug_field_op", "ug_synth_points", "ug_ctx_timings", "ug_ctx_kernel_stats", "ug_ctx_abandon", "ug_test_inject_fault",
     "ug_bases_create_group_g1", "ug_bases_members", "ug_points_all_infinity", "ug_msm_group_enqueue", "ug_msm_witness_enqueue", "ug_dvec_device_ptr", "ug_dvec_copy", "ug_dvec_copy_via", "ug_sort_plan",
     "ug_bases_drop_tables", "ug_bases_table_window", "ug_schedule_trim", "ug_ctx_trim",
@@ -192,6 +193,10 @@ def load():
     L.ug_msm_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.ug_hpoly_create.argtypes = [vp, vp, u64, u32, u32, pp]
     L.ug_hpoly_run.argtypes = [vp, vp, vp]
+    L.ug_hpoly_run_vectors.argtypes = [vp, vp, u64, C.c_int, vp, u64]
+    L.ug_hpoly_reserve_vectors.argtypes = [vp, C.c_int]
+    L.ug_hpoly_group.argtypes = [vp]
+    L.ug_hpoly_vectors_bytes.argtypes = [u32, C.c_int]; L.ug_hpoly_vectors_bytes.restype = u64
     L.ug_hpoly_chain.argtypes = [vp, vp, C.c_int, vp]
     L.ug_hpoly_combine.argtypes = [vp, vp, vp, vp, u64, u64, vp]
     L.ug_hpoly_debug_abc.argtypes = [vp, vp, vp, vp]

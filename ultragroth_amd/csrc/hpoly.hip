@@ -10,6 +10,7 @@
 // that the first NTT pass reads contiguously.
 #include "dev_common.hpp"
 #include "internal.hpp"
+#include <type_traits>
 
 namespace ug {
 
@@ -116,6 +117,109 @@ __global__ __launch_bounds__(256) void matvec_tiled_kernel(u32* a_br, u32* b_br,
     store8((m ? b_br : a_br) + (size_t)pos * 8, w);
 }
 
+// ---- the same for the V witnesses of a batched proof (coef_matvec_vectors) ----
+// A lane still owns one row, and now sums it for a tile of VT witnesses: the row's signal ids and coefficients (36 bytes per entry,
+// the larger part of the kernel's traffic) are read and unpacked ONCE per tile, only the 32-byte witness gathers are per witness.
+// Every accumulator sees exactly the additions and contractions that matvec_row makes for its witness -- the same entries in the same
+// order, contracted after every 24th --, so the sums are the same bytes. `live` witnesses of the tile exist (the last tile of a
+// launch may be short); wtns is the tile's first witness, the next one wstride words on.
+// (the loop over the witnesses of a tile, unrolled by construction: a rolled loop would index the accumulators at run time and put
+// them into scratch memory)
+template <int I, int N, class F> __device__ __forceinline__ void for_each_vector(F&& f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>()); for_each_vector<I + 1, N>(f); }
+}
+template <int VT>
+__device__ __forceinline__ void matvec_row_vectors(Fr (&acc)[VT], u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns,
+                                                   u64 wstride, int live) {
+    u32 s = row_ptr[r], e = row_ptr[r + 1];
+#pragma unroll
+    for (int v = 0; v < VT; v++) acc[v] = fp_zero<FrParams>();
+    u32 since = 0;                                             // additions since the last contraction: a multiple of 4 here
+    for (u32 p = s; p < e; p += 4) {
+        const u32 cnt = e - p < 4 ? e - p : 4;
+        u32 sg[4];
+        Fr vq[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) sg[k] = (u32)k < cnt ? sig[p + k] : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            u32 vr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            if ((u32)k < cnt) load8(vr, val + (size_t)(p + k) * 8);
+            vq[k] = unpack256<FrParams>(vr);
+        }
+        for_each_vector<0, VT>([&](auto vc) __attribute__((always_inline)) {
+            constexpr int v = decltype(vc)::value;
+            if (v < live) {
+                const u32* w = wtns + (size_t)v * wstride;
+                u32 wr[4][8];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    if ((u32)k < cnt) load8(wr[k], w + (size_t)sg[k] * 8);
+                }
+                u32 sn = since;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    if ((u32)k < cnt) {
+                        acc[v] = add(acc[v], mul(unpack256<FrParams>(wr[k]), vq[k]));
+                        if (++sn == 24) { acc[v] = contract(acc[v]); sn = 0; }
+                    }
+                }
+            }
+        });
+        since = (since + cnt) % 24;
+    }
+#pragma unroll
+    for (int v = 0; v < VT; v++) acc[v] = contract(acc[v]);
+}
+
+// one lane per row and tile of witnesses (blockIdx.y), as matvec_kernel; out_stride and wstride in words
+template <int VT>
+__global__ __launch_bounds__(256) void matvec_vectors_kernel(u32* a_br, u32* b_br, u64 out_stride, const u32* row_ptr, const u32* sig,
+                                                             const u32* val, const u32* wtns, u64 wstride, int vectors, u32 domain, int logn) {
+    u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= 2 * domain) return;
+    const int v0 = (int)blockIdx.y * VT, live = vectors - v0 < VT ? vectors - v0 : VT;
+    Fr acc[VT];
+    matvec_row_vectors<VT>(acc, r, row_ptr, sig, val, wtns + (size_t)v0 * wstride, wstride, live);
+    u32 c = r >= domain ? r - domain : r;
+    u32* dst = (r >= domain ? b_br : a_br) + (size_t)bit_reverse(c, logn) * 8;
+    for_each_vector<0, VT>([&](auto vc) __attribute__((always_inline)) {
+        constexpr int v = decltype(vc)::value;
+        if (v < live) st_packed(dst + (size_t)(v0 + v) * out_stride, acc[v]);
+    });
+}
+// ... and as matvec_tiled_kernel: the 16 x 16 transposition through LDS once per witness of the tile, on the one LDS tile
+template <int VT>
+__global__ __launch_bounds__(256) void matvec_tiled_vectors_kernel(u32* a_br, u32* b_br, u64 out_stride, const u32* row_ptr, const u32* sig,
+                                                                   const u32* val, const u32* wtns, u64 wstride, int vectors, u32 domain,
+                                                                   int logn) {
+    __shared__ u32 tile[16][16 * 8 + 4];
+    const u32 tiles_per_matrix = domain >> 8;
+    const u32 m = blockIdx.x >= tiles_per_matrix ? 1u : 0u;
+    const u32 mid = blockIdx.x - m * tiles_per_matrix;
+    const u32 i = threadIdx.x >> 4, j = threadIdx.x & 15;
+    const u32 c = (i << (logn - 4)) | (mid << 4) | j;
+    const int v0 = (int)blockIdx.y * VT, live = vectors - v0 < VT ? vectors - v0 : VT;      // (the same for the whole workgroup)
+    Fr acc[VT];
+    matvec_row_vectors<VT>(acc, m * domain + c, row_ptr, sig, val, wtns + (size_t)v0 * wstride, wstride, live);
+    const u32 j2 = threadIdx.x >> 4, l = threadIdx.x & 15, i2 = bit_reverse(l, 4);
+    const u32 pos = (bit_reverse(j2, 4) << (logn - 4)) | (bit_reverse(mid, logn - 8) << 4) | l;
+    for_each_vector<0, VT>([&](auto vc) __attribute__((always_inline)) {
+        constexpr int v = decltype(vc)::value;
+        if (v < live) {
+            u32 w[8];
+            pack256(w, acc[v]);
+#pragma unroll
+            for (int k = 0; k < 8; k++) tile[i][j * 8 + k] = w[k];
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 8; k++) w[k] = tile[i2][j2 * 8 + k];
+            store8((m ? b_br : a_br) + (size_t)(v0 + v) * out_stride + (size_t)pos * 8, w);
+            __syncthreads();                                   // (the next witness of the tile writes the same LDS tile)
+        }
+    });
+}
+
 __global__ void mul_pointwise_kernel(u32* out, const u32* x, const u32* y, u64 n) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -129,6 +233,17 @@ __global__ void h_final_kernel(u32* h, const u32* a, const u32* b, const u32* c,
     u32 w[8];
     to_normal(w, u);
     store8(h + i * 8, w);
+}
+// h_final_kernel for several vectors (blockIdx.y): strides in words
+__global__ void h_final_vectors_kernel(u32* h, u64 h_stride, const u32* a, const u32* b, const u32* c, u64 in_stride, u64 n) {
+    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u64 in = (u64)blockIdx.y * in_stride + i * 8;
+    Fr t = mul(ld_packed<FrParams>(a + in), ld_packed<FrParams>(b + in));
+    Fr u = sub<6>(t, ld_packed<FrParams>(c + in));
+    u32 w[8];
+    to_normal(w, u);
+    store8(h + (u64)blockIdx.y * h_stride + i * 8, w);
 }
 __global__ void from_mont256_kernel(u32* out, const u32* in, u64 n) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -343,12 +458,29 @@ void coef_matvec(u32* a_br, u32* b_br, const CoefMatrix& m, const u32* wtns_dev,
                            a_br, b_br, m.row_ptr, m.sig, m.val, wtns_dev, m.domain, m.logn, mask);
     UG_KERNEL_CHECK();
 }
+void coef_matvec_vectors(u32* a_br, u32* b_br, u64 out_stride, const CoefMatrix& m, const u32* wtns_dev, u64 wtns_stride, int vectors,
+                         hipStream_t stream) {
+    if (vectors == 1) { coef_matvec(a_br, b_br, m, wtns_dev, 3, stream); return; }
+    const unsigned tiles = (unsigned)((vectors + MATVEC_VT - 1) / MATVEC_VT);
+    if (m.logn >= 8)
+        hipLaunchKernelGGL(matvec_tiled_vectors_kernel<MATVEC_VT>, dim3(2 * (m.domain >> 8), tiles), dim3(256), 0, stream,
+                           a_br, b_br, out_stride * 8, m.row_ptr, m.sig, m.val, wtns_dev, wtns_stride * 8, vectors, m.domain, m.logn);
+    else
+        hipLaunchKernelGGL(matvec_vectors_kernel<MATVEC_VT>, dim3(grid_for((u64)2 * m.domain, 256), tiles), dim3(256), 0, stream,
+                           a_br, b_br, out_stride * 8, m.row_ptr, m.sig, m.val, wtns_dev, wtns_stride * 8, vectors, m.domain, m.logn);
+    UG_KERNEL_CHECK();
+}
 void fr_mul_pointwise(u32* out, const u32* x, const u32* y, u64 n, hipStream_t stream) {
     hipLaunchKernelGGL(mul_pointwise_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, out, x, y, n);
     UG_KERNEL_CHECK();
 }
 void fr_h_final(u32* h, const u32* a, const u32* b, const u32* c, u64 n, hipStream_t stream) {
     hipLaunchKernelGGL(h_final_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream, h, a, b, c, n);
+    UG_KERNEL_CHECK();
+}
+void fr_h_final_vectors(u32* h, u64 h_stride, const u32* a, const u32* b, const u32* c, u64 in_stride, u64 n, int vectors, hipStream_t stream) {
+    hipLaunchKernelGGL(h_final_vectors_kernel, dim3(grid_for(n, 256), (unsigned)vectors), dim3(256), 0, stream, h, h_stride * 8, a, b, c,
+                       in_stride * 8, n);
     UG_KERNEL_CHECK();
 }
 void fr_from_mont256(u32* out, const u32* in, u64 n, hipStream_t stream) {

@@ -17,12 +17,18 @@ void bitrev_copy(u32* out, const u32* in, int logn, hipStream_t stream);
 //   in2    first pass: the transform's input element is in[i] * in2[i]
 //   work   intermediate passes run in place here (instead of on `in` / `out`)
 //   fin_a, fin_b   last pass: out[i] = plain integer of fin_a[i] * fin_b[i] - x[i] (32-byte plain, not device form)
-struct NttFusion { const u32* in2 = nullptr; u32* work = nullptr; const u32* fin_a = nullptr; const u32* fin_b = nullptr; };
+// The *_stride members matter only to a launch over several vectors (NttPlan::launch, vectors > 1): vector v of each buffer
+// starts v * stride elements after the pointer.
+struct NttFusion {
+    const u32* in2 = nullptr; u32* work = nullptr; const u32* fin_a = nullptr; const u32* fin_b = nullptr;
+    u64 in2_stride = 0, work_stride = 0, fin_a_stride = 0, fin_b_stride = 0;
+};
 
 // one pass of a transform as the host plans it (ntt.hip turns it into kernel arguments)
 struct NttPass {
     const u32* in; u32* out; const u32* tw; const u32* post; const u32* post_const; const u32* in2; const u32* fin_a; const u32* fin_b;
     int logn, s0, k, j, gather_bitrev, scatter_bitrev;
+    u64 in_stride, out_stride, in2_stride, fin_a_stride, fin_b_stride;      // elements between two vectors of each buffer (vectors > 1)
 };
 constexpr int NTT_MAX_PASSES = 8;
 
@@ -42,13 +48,16 @@ struct NttPlan {
     // fuse (optional): see NttFusion.
     void transform(u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
                    const u32* post, const u32* post_const, hipStream_t stream, struct MsmStats* stats = nullptr,
-                   const struct NttFusion* fuse = nullptr) const;
+                   const struct NttFusion* fuse = nullptr, int vectors = 1, u64 out_stride = 0, u64 in_stride = 0) const;
     // the same in two steps, for callers that run several transforms of this size side by side: passes() fills `list`
     // (NTT_MAX_PASSES entries) and returns the pass count -- the same for every transform of the plan --, launch() runs pass
-    // p of up to three such lists in one kernel launch (logn >= 1)
+    // p of up to three such lists in one kernel launch (logn >= 1).
+    // vectors > 1: the launch transforms `vectors` vectors per list (blockIdx.z), vector v of every data buffer v * its stride
+    // (out_stride, in_stride, the fusion's) elements after the list's pointer; the twiddles, post and post_const are shared.
+    // vectors = 1 is the launch of a single transform, the strides unread.
     int passes(NttPass* list, u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
-               const u32* post, const u32* post_const, const struct NttFusion* fuse = nullptr) const;
-    void launch(const NttPass* const* lists, int count, int p, hipStream_t stream, struct MsmStats* stats = nullptr) const;
+               const u32* post, const u32* post_const, const struct NttFusion* fuse = nullptr, u64 out_stride = 0, u64 in_stride = 0) const;
+    void launch(const NttPass* const* lists, int count, int p, hipStream_t stream, struct MsmStats* stats = nullptr, int vectors = 1) const;
     ~NttPlan() { release(); }
 };
 
@@ -312,10 +321,17 @@ struct CoefMatrix {
 
 // a_br[bitrev(c)] = sum coef * w  over m = 0 rows, b_br likewise for m = 1 (device form, packed)
 void coef_matvec(u32* a_br, u32* b_br, const CoefMatrix& m, const u32* wtns_dev, int mask, hipStream_t stream);   // mask bit 0: A rows, bit 1: B rows
+// the same for `vectors` witnesses in one launch: witness v at wtns_dev + v * wtns_stride elements, its results at a_br / b_br +
+// v * out_stride elements; every row's coefficients are read once per tile of MATVEC_VT witnesses. vectors = 1 is coef_matvec.
+constexpr int MATVEC_VT = 4;
+void coef_matvec_vectors(u32* a_br, u32* b_br, u64 out_stride, const CoefMatrix& m, const u32* wtns_dev, u64 wtns_stride, int vectors,
+                         hipStream_t stream);
 // out[i] = x[i] * y[i]
 void fr_mul_pointwise(u32* out, const u32* x, const u32* y, u64 n, hipStream_t stream);
 // h[i] = plain integer of (a[i] * b[i] - c[i])      (src/groth16.cpp:142-148)
 void fr_h_final(u32* h, const u32* a, const u32* b, const u32* c, u64 n, hipStream_t stream);
+// ... for `vectors` vectors in one launch: vector v of h at v * h_stride elements, of a, b and c at v * in_stride
+void fr_h_final_vectors(u32* h, u64 h_stride, const u32* a, const u32* b, const u32* c, u64 in_stride, u64 n, int vectors, hipStream_t stream);
 // element-wise format changes, n elements of 32 bytes
 void fr_from_mont256(u32* out, const u32* in, u64 n, hipStream_t stream);
 void fr_to_mont256(u32* out, const u32* in, u64 n, hipStream_t stream);

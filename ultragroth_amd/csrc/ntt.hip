@@ -118,12 +118,31 @@ template <int K> __device__ __forceinline__ void raw_subkq(u32* r, const u32* a,
 // contraction of the last loop takes (to < 2.01 q for packing) and the 170 q a Shoup product's operand may have.
 // up to three transforms of the same size in one launch (blockIdx.y picks one): the three chains of the H-polynomial block
 struct PassBatch { PassArgs a[3]; };
+// ... and of several vectors per transform (blockIdx.z picks one): the V witnesses of a batched H-polynomial block. Vector v of a
+// data buffer starts v * stride WORDS after the transform's pointer; tw, post and post_const are tables, shared by all vectors.
+// A kernel argument and an instantiation of their own (VECTORS), so that the launches of a single transform keep their code
+// and registers.
+struct PassStrides { u64 in, out, in2, fin_a, fin_b; };
+struct PassBatchVectors { PassBatch b; PassStrides s[3]; };
+template <bool VECTORS> struct PassParam { typedef PassBatch type; };
+template <> struct PassParam<true> { typedef PassBatchVectors type; };
+__device__ __forceinline__ const PassBatch& pass_batch(const PassBatch& b) { return b; }
+__device__ __forceinline__ const PassBatch& pass_batch(const PassBatchVectors& b) { return b.b; }
 
-template <bool SHOUP>
-__global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(PassBatch batch) {
+template <bool SHOUP, bool VECTORS>
+__global__ __launch_bounds__(NTT_THREADS) void ntt_pass_kernel(typename PassParam<VECTORS>::type batch) {
     constexpr int KQ = SHOUP ? 3 : 2;             // the twiddle products are below KQ q
     extern __shared__ u32 lds[];
-    const PassArgs& a = batch.a[blockIdx.y];
+    PassArgs moved;
+    if constexpr (VECTORS) {
+        moved = batch.b.a[blockIdx.y];
+        const PassStrides& s = batch.s[blockIdx.y];
+        const size_t v = blockIdx.z;
+        moved.in += v * s.in; moved.out += v * s.out;
+        if (moved.in2) moved.in2 += v * s.in2;
+        if (moved.fin_a) { moved.fin_a += v * s.fin_a; moved.fin_b += v * s.fin_b; }
+    }
+    const PassArgs& a = VECTORS ? moved : pass_batch(batch).a[blockIdx.y];
     const int E = 1 << (a.k + a.j);               // elements per workgroup
     const int tid = threadIdx.x, nth = blockDim.x;
     const u32 bid = blockIdx.x;
@@ -354,10 +373,9 @@ void NttPlan::init(int logn_, hipStream_t stream) {
     release();
     logn = logn_;
     // per device, and idempotent: set whenever a plan is made on the current device
-    UG_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (1 << NTT_MAX_LOG_TILE) * NL * 4));
-    UG_HIP(hipFuncSetAttribute((const void*)ntt_pass_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (1 << NTT_MAX_LOG_TILE) * NL * 4));
+    for (const void* kernel : {(const void*)ntt_pass_kernel<false, false>, (const void*)ntt_pass_kernel<true, false>,
+                               (const void*)ntt_pass_kernel<false, true>, (const void*)ntt_pass_kernel<true, true>})
+        UG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (1 << NTT_MAX_LOG_TILE) * NL * 4));
     // twiddle products in Shoup form (tuning knob UG_NTT_SHOUP=0: the Montgomery form of rounds 1-4; both are exact)
     {
         const char* e = getenv("UG_NTT_SHOUP");
@@ -426,7 +444,7 @@ void NttPlan::release() {
 // (then `in` is only read), else `in` itself for a scattering transform (which is clobbered) and `out` otherwise; the last
 // pass writes `out`.
 int NttPlan::passes(NttPass* list, u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
-                    const u32* post, const u32* post_const, const NttFusion* fuse) const {
+                    const u32* post, const u32* post_const, const NttFusion* fuse, u64 out_stride, u64 in_stride) const {
     const u32* in2 = fuse ? fuse->in2 : nullptr;
     u32* work = fuse ? fuse->work : nullptr;
     if (logn <= 0) throw std::invalid_argument("ntt: a pass list needs at least two points");
@@ -444,6 +462,7 @@ int NttPlan::passes(NttPass* list, u32* out, const u32* in, bool inverse, bool g
     }
     if (np == 1 && (gather_bitrev || scatter_bitrev) && out == in) throw std::invalid_argument("ntt: a single permuting pass must be out of place");
     u32* mid = work ? work : (scatter_bitrev ? const_cast<u32*>(in) : out);
+    const u64 mid_stride = work ? fuse->work_stride : (scatter_bitrev ? in_stride : out_stride);      // (the strides follow their buffers)
     if ((gather_bitrev || scatter_bitrev) && np > 1 && out == mid && scatter_bitrev) throw std::invalid_argument("ntt: the scattering pass must leave its work buffer");
     int s0 = 0;
     for (int p = 0; p < np; p++) {
@@ -454,6 +473,11 @@ int NttPlan::passes(NttPass* list, u32* out, const u32* in, bool inverse, bool g
         a.in2 = (p == 0) ? in2 : nullptr;
         a.fin_a = (last && fuse) ? fuse->fin_a : nullptr;
         a.fin_b = (last && fuse) ? fuse->fin_b : nullptr;
+        a.in_stride = (p == 0) ? in_stride : mid_stride;
+        a.out_stride = last ? out_stride : mid_stride;
+        a.in2_stride = a.in2 ? fuse->in2_stride : 0;
+        a.fin_a_stride = a.fin_a ? fuse->fin_a_stride : 0;
+        a.fin_b_stride = a.fin_b ? fuse->fin_b_stride : 0;
         a.tw = inverse ? tw_inv : tw_fwd; a.logn = logn; a.s0 = s0; a.k = stages[p];
         a.j = nj[p];
         if (s0 > 0 && a.j > s0) a.j = s0;
@@ -466,45 +490,55 @@ int NttPlan::passes(NttPass* list, u32* out, const u32* in, bool inverse, bool g
     return np;
 }
 
-// pass `p` of up to three transforms of this plan's size in ONE launch (their pass lists share the geometry)
-void NttPlan::launch(const NttPass* const* lists, int count, int p, hipStream_t stream, MsmStats* stats) const {
+// pass `p` of up to three transforms of this plan's size in ONE launch (their pass lists share the geometry); vectors > 1: of
+// that many vectors of each transform (the lists' strides), same geometry, blockIdx.z the vector
+void NttPlan::launch(const NttPass* const* lists, int count, int p, hipStream_t stream, MsmStats* stats, int vectors) const {
     if (count < 1 || count > 3) throw std::logic_error("ntt: batch size");
-    PassBatch b;
+    if (vectors < 1 || vectors > 65535) throw std::logic_error("ntt: vector count");
+    PassBatchVectors bv;
+    PassBatch& b = bv.b;
     for (int c = 0; c < count; c++) {
         const NttPass& n = lists[c][p];
         PassArgs& a = b.a[c];
         a.in = n.in; a.out = n.out; a.tw = n.tw; a.post = n.post; a.post_const = n.post_const; a.in2 = n.in2; a.fin_a = n.fin_a; a.fin_b = n.fin_b;
         a.logn = n.logn; a.s0 = n.s0; a.k = n.k; a.j = n.j; a.gather_bitrev = n.gather_bitrev; a.scatter_bitrev = n.scatter_bitrev;
+        bv.s[c] = PassStrides{n.in_stride * 8, n.out_stride * 8, n.in2_stride * 8, n.fin_a_stride * 8, n.fin_b_stride * 8};
 #ifdef UG_MEASURE
         static const int fuse_steps = getenv("UG_NTT_FUSE_STEPS") ? atoi(getenv("UG_NTT_FUSE_STEPS")) : 0;
         a.fuse_steps = fuse_steps;
 #endif
     }
-    for (int c = count; c < 3; c++) b.a[c] = b.a[0];
+    for (int c = count; c < 3; c++) { b.a[c] = b.a[0]; bv.s[c] = bv.s[0]; }
     const PassArgs& a = b.a[0];
     int E = 1 << (a.k + a.j);
     unsigned blocks = (unsigned)(((u64)1 << logn) >> (a.k + a.j));
     int threads = E / 4 > NTT_THREADS ? NTT_THREADS : (E / 4 < 64 ? 64 : E / 4);
     size_t lds = (size_t)E * NL * 4;
-    int slot = stats ? stats->begin(stream, ((u64)1 << logn) * (u64)count) : -1;
-    if (shoup) hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3(blocks, (unsigned)count), dim3(threads), lds, stream, b);
-    else hipLaunchKernelGGL(ntt_pass_kernel<false>, dim3(blocks, (unsigned)count), dim3(threads), lds, stream, b);
+    int slot = stats ? stats->begin(stream, ((u64)1 << logn) * (u64)count * (u64)vectors) : -1;
+    if (vectors > 1) {
+        const dim3 grid(blocks, (unsigned)count, (unsigned)vectors);
+        if (shoup) hipLaunchKernelGGL((ntt_pass_kernel<true, true>), grid, dim3(threads), lds, stream, bv);
+        else hipLaunchKernelGGL((ntt_pass_kernel<false, true>), grid, dim3(threads), lds, stream, bv);
+    } else if (shoup) hipLaunchKernelGGL((ntt_pass_kernel<true, false>), dim3(blocks, (unsigned)count), dim3(threads), lds, stream, b);
+    else hipLaunchKernelGGL((ntt_pass_kernel<false, false>), dim3(blocks, (unsigned)count), dim3(threads), lds, stream, b);
     UG_KERNEL_CHECK();
     if (stats) stats->end(slot, stream);
 }
 
 void NttPlan::transform(u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
-                        const u32* post, const u32* post_const, hipStream_t stream, MsmStats* stats, const NttFusion* fuse) const {
+                        const u32* post, const u32* post_const, hipStream_t stream, MsmStats* stats, const NttFusion* fuse,
+                        int vectors, u64 out_stride, u64 in_stride) const {
     if (logn == 0) {
         if (fuse && (fuse->in2 || fuse->fin_a)) throw std::invalid_argument("ntt: fused forms need at least two points");
+        if (vectors != 1) throw std::invalid_argument("ntt: a one-point transform takes one vector");
         if (out != in) UG_HIP(hipMemcpyAsync(out, in, 32, hipMemcpyDeviceToDevice, stream));
         return;   // size-1 transform is the identity (n^-1 = 1, omega_2^0 = 1)
     }
     if ((gather_bitrev || scatter_bitrev) && out == in) throw std::invalid_argument("ntt: permuting transform must be out of place");
     NttPass list[NTT_MAX_PASSES];
-    const int np = passes(list, out, in, inverse, gather_bitrev, scatter_bitrev, post, post_const, fuse);
+    const int np = passes(list, out, in, inverse, gather_bitrev, scatter_bitrev, post, post_const, fuse, out_stride, in_stride);
     const NttPass* one[1] = {list};
-    for (int p = 0; p < np; p++) launch(one, 1, p, stream, stats);
+    for (int p = 0; p < np; p++) launch(one, 1, p, stream, stats, vectors);
 }
 
 void bitrev_copy(u32* out, const u32* in, int logn, hipStream_t stream) {

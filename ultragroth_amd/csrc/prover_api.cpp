@@ -1004,7 +1004,40 @@ public:
         ug_ctx_trim(d_.ctx); ug_ctx_trim(d_.ctx2);
         witness_.trim(wCur_);
         batch_.release();
+        if (d_.hp && hpolyGroup_ > 1) { ugCheck(ug_hpoly_reserve_vectors(d_.hp, 1)); hpolyGroup_ = 1; }
     }
+
+    // ---- the H-polynomial block of a batched pass (proveBatchInPasses) ----
+    // ULTRAGROTH_BATCH_HPOLY=1: one ug_hpoly_run_vectors call per pass. Unset or 0 (the default until the 2^24 rounds are measured,
+    // DESIGN.md section 5.1): one ug_hpoly_run per witness, as before the vector form existed. The same proofs either way.
+    static bool batchHpolyOn() {
+        const char* e = getenv("ULTRAGROTH_BATCH_HPOLY");
+        return e && e[0] == '1';
+    }
+    // what the H block's workspaces hold beyond those of a single proof: a pass plans as if they were free (perPass);
+    // reserveForPass keeps them only while the planned pass has room for them
+    uint64_t hpolyHeldBytes() const { return hpolyGroup_ > 1 ? ug_hpoly_vectors_bytes(hdr_.domainSize, hpolyGroup_ - 1) : 0; }
+    // the block of the V staged witnesses into the V slices of the batch h buffer, on the H branch's stream
+    void hpolyOfBatch(BatchBuffers::DeviceViews& views, int V) {
+        const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize;
+        if (batchHpolyOn()) {
+            ugCheck(ug_hpoly_run_vectors(d_.hp, views.view(d_.ctx2, batch_.w, 0, (uint64_t)V * nv), nv, V,
+                                         views.view(d_.ctx2, batch_.h, 0, (uint64_t)V * dom), dom));
+            return;
+        }
+        for (int v = 0; v < V; v++)
+            ugCheck(ug_hpoly_run(d_.hp, views.view(d_.ctx2, batch_.w, (uint64_t)v * nv, nv), views.view(d_.ctx2, batch_.h, (uint64_t)v * dom, dom)));
+    }
+    // Workspaces for launch groups of `group` witnesses (the prover's turn held, nothing queued). Shrinking frees before it
+    // allocates (ug_hpoly_reserve_vectors); a larger group that does not fit after all gives way to a smaller one, which is only slower.
+    void setHpolyGroup(int group) {
+        if (!d_.hp || group == hpolyGroup_) return;
+        while (group > hpolyGroup_ && ug_hpoly_reserve_vectors(d_.hp, group) != UG_OK) group--;
+        if (group < hpolyGroup_) ugCheck(ug_hpoly_reserve_vectors(d_.hp, group));
+        hpolyGroup_ = group;
+    }
+    uint64_t batchKeep_ = 0;                        // bytes a pass plan leaves aside (reserveForPass asks what a group would cost the pass)
+    int hpolyGroup_ = 1;                            // the launch group d_.hp holds workspaces for
 
 protected:
     virtual void requireWitnessForH() const = 0;
@@ -1045,6 +1078,30 @@ public:
 // nothing queued reads the buffers then), so another caller's kernels may run meanwhile; runPass draws the pass's blinding in
 // witness order, starts the host terms and runs the device part; finishPass blinds and serialises outside the turn. A pass of
 // one witness takes the single-proof path.
+// The buffers of a pass of V and the launch group of its H-polynomial block (ug_hpoly_run_vectors), under the prover's turn. The
+// planner's answer for the pass is not touched; the group comes from what the pass leaves. Workspaces for V or more vectors that
+// a prover holds from an earlier pass stay as they are while the plan still grants V with them counted as taken -- a call whose
+// passes differ in size (20 witnesses: 16 and 4) allocates nothing after its first pass, and run_vectors uses min(V, group) of
+// them. Otherwise the held ones go back to one vector BEFORE the batch buffers grow (perPass planned V as if they were free),
+// and the group is the largest for which the same plan still grants V witnesses with the group's workspaces taken from the free
+// memory (the first workspace, the single proof's, exists anyway): at most V - 1 questions, asked only when the group changes.
+template <class P>
+void reserveForPass(P& p, typename P::BatchCall& c, int V, int b0) {
+    auto grantsWith = [&](int group) {
+        p.batchKeep_ = ug_hpoly_vectors_bytes(p.header().domainSize, group - 1);
+        const int fits = p.perPass(c, V, b0);
+        p.batchKeep_ = 0;
+        return fits >= V;
+    };
+    const bool on = P::batchHpolyOn();
+    if (on && p.hpolyGroup_ >= V && grantsWith(p.hpolyGroup_)) { p.reserveBatch(V); return; }
+    p.setHpolyGroup(1);
+    p.reserveBatch(V);
+    int group = on ? V : 1;
+    while (group > 1 && !grantsWith(group)) group--;
+    p.setHpolyGroup(group);
+}
+
 template <class P>
 void proveBatchInPasses(P& p, typename P::BatchCall& c, int k) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1056,7 +1113,7 @@ void proveBatchInPasses(P& p, typename P::BatchCall& c, int k) {
         {
             auto turn = p.takeTurn(false);                          // (allocations only under the turn)
             V = p.perPass(c, k - b0, b0);
-            if (V > 1) p.reserveBatch(V);
+            if (V > 1) reserveForPass(p, c, V, b0);
         }
         if (V <= 1) { p.proveOneOfBatch(c, b0++); continue; }       // the single-proof path
         p.stagePass(c, b0, V);
@@ -1827,7 +1884,8 @@ public:
         const std::vector<ug_batch_schedule> sch = batchSchedules();
         uint64_t freeB = 0, totalB = 0;
         ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
-        freeB += batch_.bytesHeld();                                  // (reused or replaced)
+        freeB += batch_.bytesHeld() + hpolyHeldBytes();               // (reused or replaced)
+        freeB = freeB > batchKeep_ ? freeB - batchKeep_ : 0;
         const uint64_t pending = pendingTableBytes();                 // (the background builder's tables keep their room)
         freeB = freeB > pending ? freeB - pending : 0;
         const int V = ug_plan_proof_batch(sch.data(), (int)sch.size(), hdr_.nVars, hdr_.domainSize, freeB, requested);
@@ -1875,8 +1933,7 @@ public:
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), outC.data(), (int64_t)hdr_.nPublic + 1,
                                    overlap == 2, batch_.w, V, nv, batch_.wB);
             if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
-            for (int v = 0; v < V; v++)
-                ugCheck(ug_hpoly_run(d_.hp, views.view(d_.ctx2, batch_.w, (uint64_t)v * nv, nv), views.view(d_.ctx2, batch_.h, (uint64_t)v * dom, dom)));
+            hpolyOfBatch(views, V);                                                             // S5-S9 of the V witnesses
             ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
             if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
             const ug_bases* sets[1] = {d_.H};
@@ -2419,7 +2476,8 @@ public:
         const std::vector<ug_batch_schedule> sch = batchSchedules();
         uint64_t freeB = 0, totalB = 0;
         ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
-        freeB += batch_.bytesHeld();                                  // (reused or replaced)
+        freeB += batch_.bytesHeld() + hpolyHeldBytes();               // (reused or replaced)
+        freeB = freeB > batchKeep_ ? freeB - batchKeep_ : 0;
         const uint64_t pending = pendingTableBytes();                 // (none today: this prover builds its tables at create)
         freeB = freeB > pending ? freeB - pending : 0;
         // per witness beyond the signal and h vectors: the larger of the two gathered sets (one aux buffer serves both rounds),
@@ -2513,8 +2571,7 @@ public:
         }
         const char* ov = getenv("ULTRAGROTH_OVERLAP");
         if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));          // (default: beside, as a single proof)
-        for (int v = 0; v < V; v++)
-            ugCheck(ug_hpoly_run(d_.hp, views.view(d_.ctx2, batch_.w, (uint64_t)v * nv, nv), views.view(d_.ctx2, batch_.h, (uint64_t)v * dom, dom)));
+        hpolyOfBatch(views, V);                                                          // the FFT block of the V witnesses
         ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
         {
             const ug_bases* set[1] = {d_.H};

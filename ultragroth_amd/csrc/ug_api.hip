@@ -194,7 +194,10 @@ struct ug_schedule {
 };
 struct ug_hpoly {
     ug_ctx* ctx; CoefMatrix mat; NttPlan ntt; u32 domain = 0, nvars = 0;
-    u32 *a = nullptr, *b = nullptr, *c = nullptr, *t = nullptr, *t2 = nullptr;     // domain elements each
+    u32 *a = nullptr, *b = nullptr, *c = nullptr, *t = nullptr, *t2 = nullptr;     // group * domain elements each: vector g of a launch
+                                                                                   // group works on [g * domain, (g + 1) * domain)
+    int group = 1;            // vectors side by side that the workspaces hold (ug_hpoly_reserve_vectors)
+    int last_group = 0;       // largest launch group of the last ug_hpoly_run_vectors call (0: none yet)
 };
 
 // A fixed launch sequence of one or two contexts of a device, captured once and replayed (ug_graph_*). It owns the event pairs
@@ -1595,67 +1598,149 @@ int ug_hpoly_create(ug_ctx* c, const void* host_coefs, uint64_t n_coefs, uint32_
     UG_CATCH
 }
 
-int ug_hpoly_run(ug_hpoly* hp, const ug_dvec* w, ug_dvec* h_out) {
-    UG_TRY
-    if (!hp || !w || !h_out) throw std::invalid_argument("null argument");
-    if (w->n < hp->nvars) throw std::invalid_argument("witness vector shorter than nVars");
-    if (h_out->n < hp->domain) throw std::invalid_argument("h vector shorter than the domain");
+namespace {
+// The H-polynomial block of g witnesses (1 <= g <= hp->group) queued on the context's stream: witness v at w + v * w_stride
+// elements, its h vector at h + v * h_stride. Every launch covers the g vectors (the matvec in tiles of witnesses, the NTT passes
+// with blockIdx.z); vector v works in slice v of the workspaces. g = 1 queues the launches of a single witness, no others.
+void hpoly_queue(ug_hpoly* hp, const u32* w, u64 w_stride, u32* h, u64 h_stride, int g) {
     ug_ctx* c = hp->ctx;
-    c->use();
-    fault_point(UG_FAULT_HPOLY_RUN);
-    ScopedTimer tm(c, &c->fft_ms);
     hipStream_t st = c->stream;
-    u64 n = hp->domain;
+    const u64 n = hp->domain;
     // S5-S6: a = A.w, b = B.w   (rows stored bit-reversed)            src/groth16.cpp:66-99
-    coef_matvec(hp->a, hp->b, hp->mat, w->data, 3, st);
+    coef_matvec_vectors(hp->a, hp->b, n, hp->mat, w, w_stride, g, st);
     if (hp->mat.logn == 0) {
         // one-point domain: every transform is the identity (n^-1 = 1, omega_2^0 = 1), nothing to fold into
-        fr_mul_pointwise(hp->c, hp->a, hp->b, n, st);
-        fr_h_final(h_out->data, hp->a, hp->b, hp->c, n, st);
-        tm.stop();
-        return UG_OK;
+        fr_mul_pointwise(hp->c, hp->a, hp->b, n * (u64)g, st);             // (the g slices of a, b and c are adjacent)
+        if (g == 1) fr_h_final(h, hp->a, hp->b, hp->c, n, st);
+        else fr_h_final_vectors(h, h_stride, hp->a, hp->b, hp->c, n, n, g, st);
+        return;
     }
     static const bool batched = !(measure_env("UG_NTT_BATCH") && atoi(measure_env("UG_NTT_BATCH")) == 0);      // A/B switch (-DUG_MEASURE)
     NttPass pa[NTT_MAX_PASSES], pb[NTT_MAX_PASSES], pc[NTT_MAX_PASSES];
-    NttFusion cinv; cinv.in2 = hp->b; cinv.work = hp->c;
-    NttFusion cfwd; cfwd.work = hp->c; cfwd.fin_a = hp->a; cfwd.fin_b = hp->b;
-    const int np = hp->ntt.passes(pc, hp->t2, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, &cinv);
+    NttFusion cinv; cinv.in2 = hp->b; cinv.work = hp->c; cinv.in2_stride = n; cinv.work_stride = n;
+    NttFusion cfwd; cfwd.work = hp->c; cfwd.fin_a = hp->a; cfwd.fin_b = hp->b; cfwd.work_stride = n; cfwd.fin_a_stride = n; cfwd.fin_b_stride = n;
+    const int np = hp->ntt.passes(pc, hp->t2, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, &cinv, n, n);
     if (batched && np > 1) {
         // The three chains side by side, pass by pass: ONE launch per pass index holds the same pass of all three transforms
         // (blockIdx.y), 7 launches instead of 18 for a three-pass size, and the ends of the launches fill with the other
         // chains' workgroups. Buffers: every first pass only READS a and b (chain c's forms a o b from them, S7 :100-108), so
         // chains a and b take their intermediate passes to work buffers (hp->t and the h vector, which is written last of
         // all) and scatter their twisted coefficients back into a and b; chain c works on hp->c and leaves them in hp->t2.
-        NttFusion wa; wa.work = hp->t;
-        NttFusion wb; wb.work = h_out->data;
-        hp->ntt.passes(pa, hp->a, hp->a, true, false, true, hp->ntt.twist, nullptr, &wa);      // S8 ifft + twist :110-128
-        hp->ntt.passes(pb, hp->b, hp->b, true, false, true, hp->ntt.twist, nullptr, &wb);
+        NttFusion wa; wa.work = hp->t; wa.work_stride = n;
+        NttFusion wb; wb.work = h; wb.work_stride = h_stride;
+        hp->ntt.passes(pa, hp->a, hp->a, true, false, true, hp->ntt.twist, nullptr, &wa, n, n);      // S8 ifft + twist :110-128
+        hp->ntt.passes(pb, hp->b, hp->b, true, false, true, hp->ntt.twist, nullptr, &wb, n, n);
         const NttPass* inv3[3] = {pa, pb, pc};
-        for (int p = 0; p < np; p++) hp->ntt.launch(inv3, 3, p, st, c->stat(2));
+        for (int p = 0; p < np; p++) hp->ntt.launch(inv3, 3, p, st, c->stat(2), g);
         // S8 fft :130-140, in place on a and b; chain c's last pass also forms h = a o b - c (S9 :142-148) from the FINISHED
         // a and b, so it goes after theirs
-        hp->ntt.passes(pa, hp->a, hp->a, false, false, false, nullptr, nullptr, nullptr);
-        hp->ntt.passes(pb, hp->b, hp->b, false, false, false, nullptr, nullptr, nullptr);
-        hp->ntt.passes(pc, h_out->data, hp->t2, false, false, false, nullptr, nullptr, &cfwd);
+        hp->ntt.passes(pa, hp->a, hp->a, false, false, false, nullptr, nullptr, nullptr, n, n);
+        hp->ntt.passes(pb, hp->b, hp->b, false, false, false, nullptr, nullptr, nullptr, n, n);
+        hp->ntt.passes(pc, h, hp->t2, false, false, false, nullptr, nullptr, &cfwd, h_stride, n);
         const NttPass* fwd3[3] = {pa, pb, pc};
-        for (int p = 0; p + 1 < np; p++) hp->ntt.launch(fwd3, 3, p, st, c->stat(2));
-        hp->ntt.launch(fwd3, 2, np - 1, st, c->stat(2));
+        for (int p = 0; p + 1 < np; p++) hp->ntt.launch(fwd3, 3, p, st, c->stat(2), g);
+        hp->ntt.launch(fwd3, 2, np - 1, st, c->stat(2), g);
         const NttPass* last[1] = {pc};
-        hp->ntt.launch(last, 1, np - 1, st, c->stat(2));
+        hp->ntt.launch(last, 1, np - 1, st, c->stat(2), g);
     } else {
         // S7 + the inverse half of the third chain: c = a o b is formed inside the first pass of its ifft (:100-108), whose
         // passes run on hp->c so that a and b stay intact; the twisted coefficients wait in hp->t2
-        hp->ntt.transform(hp->t2, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2), &cinv);
+        hp->ntt.transform(hp->t2, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2), &cinv, g, n, n);
         // S8: ifft, twist by omega_2n^i (with 1/n folded in), fft          :110-140
         u32* polys[2] = {hp->a, hp->b};
         for (int p = 0; p < 2; p++) {
-            hp->ntt.transform(hp->t, polys[p], /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2));
-            hp->ntt.transform(polys[p], hp->t, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2));
+            hp->ntt.transform(hp->t, polys[p], /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2), nullptr, g, n, n);
+            hp->ntt.transform(polys[p], hp->t, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), nullptr, g, n, n);
         }
         // the forward half of the third chain, with S9 (h = a o b - c, to plain integers, :142-148) inside its last pass
-        hp->ntt.transform(h_out->data, hp->t2, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), &cfwd);
+        hp->ntt.transform(h, hp->t2, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), &cfwd, g, h_stride, n);
+    }
+}
+}  // namespace
+
+int ug_hpoly_run(ug_hpoly* hp, const ug_dvec* w, ug_dvec* h_out) {
+    UG_TRY
+    if (!hp || !w || !h_out) throw std::invalid_argument("null argument");
+    if (w->n < hp->nvars) throw std::invalid_argument("witness vector shorter than nVars");
+    if (h_out->n < hp->domain) throw std::invalid_argument("h vector shorter than the domain");
+    if (!hp->group) throw std::runtime_error("the H-polynomial handle has no workspaces (a reservation failed): reserve again");
+    ug_ctx* c = hp->ctx;
+    c->use();
+    fault_point(UG_FAULT_HPOLY_RUN);
+    ScopedTimer tm(c, &c->fft_ms);
+    hpoly_queue(hp, w->data, 0, h_out->data, 0, 1);
+    tm.stop();
+    UG_CATCH
+}
+
+// The block for `vectors` witnesses (include/ultragroth_hip.h): launch groups of up to hp->group vectors, the last one smaller.
+int ug_hpoly_run_vectors(ug_hpoly* hp, const ug_dvec* w, uint64_t witness_stride, int vectors, ug_dvec* h_out, uint64_t h_stride) {
+    UG_TRY
+    if (!hp || !w || !h_out) throw std::invalid_argument("null argument");
+    if (vectors < 1 || vectors > UG_BATCH_MAX) throw std::invalid_argument("vectors outside 1 .. UG_BATCH_MAX");
+    if (witness_stride < hp->nvars) throw std::invalid_argument("witness stride below nVars");
+    if (h_stride < hp->domain) throw std::invalid_argument("h stride below the domain");
+    if (w->n < (u64)(vectors - 1) * witness_stride + hp->nvars) throw std::invalid_argument("witness vector shorter than its last slice");
+    if (h_out->n < (u64)(vectors - 1) * h_stride + hp->domain) throw std::invalid_argument("h vector shorter than its last slice");
+    if (!hp->group) throw std::runtime_error("the H-polynomial handle has no workspaces (a reservation failed): reserve again");
+    ug_ctx* c = hp->ctx;
+    c->use();
+    ScopedTimer tm(c, &c->fft_ms);
+    hp->last_group = vectors < hp->group ? vectors : hp->group;
+    for (int v0 = 0; v0 < vectors; v0 += hp->group) {
+        const int g = vectors - v0 < hp->group ? vectors - v0 : hp->group;
+        for (int v = 0; v < g; v++) fault_point(UG_FAULT_HPOLY_RUN);            // (once per witness, as a loop of ug_hpoly_run)
+        hpoly_queue(hp, w->data + (u64)v0 * witness_stride * 8, witness_stride, h_out->data + (u64)v0 * h_stride * 8, h_stride, g);
     }
     tm.stop();
+    UG_CATCH
+}
+uint64_t ug_hpoly_vectors_bytes(uint32_t domain_size, int group) {
+    return group < 1 ? 0 : (uint64_t)group * 5 * 32 * domain_size;
+}
+int ug_hpoly_group(const ug_hpoly* hp) { return !hp ? 0 : hp->last_group ? hp->last_group : hp->group; }
+// A larger group: new workspaces first, the old ones go only when all five exist, so a reservation that does not fit changes
+// nothing. A smaller group gives memory back, so the old ones go first (shedding memory must not need memory); what was just
+// freed is several times what the new ones take.
+int ug_hpoly_reserve_vectors(ug_hpoly* hp, int group) {
+    UG_TRY
+    if (!hp) throw std::invalid_argument("null argument");
+    if (group < 1 || group > UG_BATCH_MAX) throw std::invalid_argument("group outside 1 .. UG_BATCH_MAX");
+    if (group == hp->group) return UG_OK;
+    ug_ctx* c = hp->ctx;
+    c->use();
+    if (c->recording) throw std::invalid_argument("no reservation while a launch sequence is being recorded");
+    const size_t bytes = (size_t)group * hp->domain * 32;
+    u32** held[5] = {&hp->a, &hp->b, &hp->c, &hp->t, &hp->t2};
+    const bool shrink = group < hp->group;
+    if (shrink) {
+        UG_HIP(hipStreamSynchronize(c->stream));               // whatever was queued on the old workspaces has finished
+        alloc_epoch_bump();                                    // (recorded launch sequences point into them)
+        for (int k = 0; k < 5; k++) { hipFree(*held[k]); *held[k] = nullptr; }
+        hp->group = 0;                                         // (no workspaces until the five below exist: the run calls refuse)
+    }
+    u32* fresh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    try {
+        for (int k = 0; k < 5; k++) {
+            if (hipMalloc(&fresh[k], bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                fresh[k] = nullptr;
+                throw std::runtime_error("H-polynomial workspaces for " + std::to_string(group) + " vectors (" +
+                                         std::to_string(ug_hpoly_vectors_bytes(hp->domain, group)) + " bytes) do not fit the device memory");
+            }
+            if (k == 2) fault_point(UG_FAULT_HPOLY_RESERVE);           // (test hook: a failure with part of the workspaces allocated)
+        }
+    } catch (...) {
+        for (u32* f : fresh) if (f) hipFree(f);
+        throw;
+    }
+    if (!shrink) {
+        UG_HIP(hipStreamSynchronize(c->stream));
+        alloc_epoch_bump();
+        for (int k = 0; k < 5; k++) hipFree(*held[k]);
+    }
+    for (int k = 0; k < 5; k++) *held[k] = fresh[k];
+    hp->group = group;
     UG_CATCH
 }
 
@@ -1667,6 +1752,7 @@ int ug_hpoly_chain(ug_hpoly* hp, const ug_dvec* w, int which, ug_dvec* out) {
     if (which < 0 || which > 2) throw std::invalid_argument("polynomial index out of range");
     if (w->n < hp->nvars) throw std::invalid_argument("witness vector shorter than nVars");
     if (out->n < hp->domain) throw std::invalid_argument("output vector shorter than the domain");
+    if (!hp->group) throw std::runtime_error("the H-polynomial handle has no workspaces (a reservation failed): reserve again");
     ug_ctx* c = hp->ctx;
     c->use();
     ScopedTimer tm(c, &c->fft_ms);
@@ -1710,6 +1796,7 @@ int ug_hpoly_combine(ug_hpoly* hp, const ug_dvec* a, const ug_dvec* b, const ug_
 int ug_hpoly_debug_abc(ug_hpoly* hp, void* ha, void* hb, void* hc) {
     UG_TRY
     if (!hp) throw std::invalid_argument("null argument");
+    if (!hp->group) throw std::runtime_error("the H-polynomial handle has no workspaces (a reservation failed): reserve again");
     ug_ctx* c = hp->ctx;
     c->use();
     void* host[3] = {ha, hb, hc};
