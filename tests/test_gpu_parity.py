@@ -394,6 +394,55 @@ def test_msm_group_equals_single_products(device, zkey, wtns):
         device.bases_group([(A, n, 0)], 0, n)
 
 
+def test_msm_witness_equals_group_and_single(device):
+    """ug_msm_witness_enqueue (both accumulations, then the G2 tail on the side stream beside the G1 tail) == ug_msm_group_enqueue
+    + ug_msm_g2 on the same sets, byte for byte and twice over: 1000 walk points (many 32-entry segments: the fix-up kernels
+    run), groups of three and of two, uniform scalars and one scalar repeated (one heavy bucket per window), classic windows and
+    tables of width 16 on both sets, an all-infinity G2 set. The single and group products are compared with the oracle above.
+    A call that does not fit the queue fails with the depth message and leaves what was queued as it was."""
+    import ctypes as C
+    import ultragroth_amd as ug
+    from ultragroth_amd import synth
+    n = 1000
+    A, B, Cs = (bytes(synth.synth_points(device, n, seed)) for seed in (0x3301, 0x3303, 0x3305))
+    P2 = bytes(synth.synth_points(device, n, 0x3307, g2=True))
+    scalars = {"uniform": synth.scalars(n, "U", 0x3309).tobytes(), "equal": synth.scalars(1, "U", 0x330b).tobytes() * n}
+    for c in (0, 16):
+        groups = [device.bases_group([(A, n, 0), (B, n, 0), (Cs, n, 0)][:k], 0, n, table_c=c) for k in (3, 2)]
+        b2 = device.bases(P2, n, g2=True, table_c=c)
+        inf2 = device.bases(bytes(128 * n), n, g2=True, table_c=c)
+        for name, sc in scalars.items():
+            s = device.schedule(device.dvec(n, sc), 0, n, table_c=c)
+            for g in groups:
+                exp = device.msm_group(g, s) + [device.msm(b2, s, g2=True)]
+                assert bytes(64) not in exp and exp[-1] != bytes(128), (c, name)
+                assert device.msm_witness(g, b2, s) == exp, (c, name, g.members)
+                assert device.msm_witness(g, b2, s) == exp, (c, name, g.members)       # the workspaces and the side stream are reused
+            assert device.msm_witness(groups[0], inf2, s) == device.msm_group(groups[0], s) + [bytes(128)], (c, name)
+    # six products queued, then a witness call of 3 + 1: refused, and exactly the six stay queued -- two more fit, a ninth does not
+    L, s = device._L, device.schedule(device.dvec(n, scalars["uniform"]), 0, n)
+    group, b2 = device.bases_group([(A, n, 0), (B, n, 0), (Cs, n, 0)], 0, n), device.bases(P2, n, g2=True)
+    sets = [(device.bases(p, n), False) for p in (A, B, Cs)] + [(b2, True)]
+    queued = [sets[0], sets[3], sets[1], sets[2], sets[3], sets[0], sets[2], sets[3]]
+    exp = [device.msm(b, s, g2=g2) for b, g2 in queued]
+    outs = [C.create_string_buffer(128 if g2 else 64) for _, g2 in queued]
+
+    def enqueue(lo, hi):
+        arr_b = (C.c_void_p * (hi - lo))(*[b.h for b, _ in queued[lo:hi]])
+        arr_o = (C.c_void_p * (hi - lo))(*[C.cast(o, C.c_void_p) for o in outs[lo:hi]])
+        return L.ug_msm_batch_enqueue(device._h, hi - lo, arr_b, s.h, None, arr_o)
+    try:
+        assert enqueue(0, 6) == 0
+        with pytest.raises(ug.DeviceError, match="at most 8 products may be queued before ug_ctx_collect"):
+            device.msm_witness(group, b2, s)
+        assert enqueue(6, 8) == 0
+        assert enqueue(0, 1) != 0 and b"at most 8 products" in L.ug_last_error()
+    finally:
+        assert L.ug_ctx_collect(device._h) == 0
+    assert [o.raw for o in outs] == exp
+    assert device.msm_witness(group, b2, s) == exp[0:1] + exp[2:4] + exp[1:2]          # and the queue is empty again
+
+
 def test_hpoly_matches_oracle_and_known_answers(device, zkey, wtns):
     info = O.zkey_info(zkey)
     coefs = _sec(zkey, "zkey", 4)[4:]

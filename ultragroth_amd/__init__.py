@@ -830,6 +830,17 @@ class Device:
         _check(self._L.ug_ctx_collect(self._h))
         return [o.raw for o in outs]
 
+    def msm_witness(self, group, g2set, schedule):
+        """the witness products of a proof (ug_msm_witness_enqueue + ug_ctx_collect): the K sums of a base group, then the sum of
+        a G2 set over the same schedule -- K records of 64 bytes and one of 128 (V records each over a schedule of V vectors)"""
+        v = getattr(schedule, "vectors", 1)
+        outs = [C.create_string_buffer(64 * v) for _ in range(group.members)]
+        out2 = C.create_string_buffer(128 * v)
+        arr = (C.c_void_p * group.members)(*[C.cast(o, C.c_void_p) for o in outs])
+        _check(self._L.ug_msm_witness_enqueue(self._h, group.h, g2set.h, schedule.h, arr, out2))
+        _check(self._L.ug_ctx_collect(self._h))
+        return [o.raw for o in outs] + [out2.raw]
+
     def dvec(self, n, data=None):
         h = C.c_void_p()
         _check(self._L.ug_dvec_create(self._h, n, C.byref(h)))

@@ -137,6 +137,7 @@ def load():
     L.ug_bases_members.argtypes = [vp]
     L.ug_points_all_infinity.argtypes = [vp, u64, u64]
     L.ug_msm_group_enqueue.argtypes = [vp, vp, vp, vp]
+    L.ug_msm_witness_enqueue.argtypes = [vp, vp, vp, vp, vp, vp]
     L.ug_ctx_collect.argtypes = [vp]
     L.ug_dvec_device_ptr.argtypes = [vp]; L.ug_dvec_device_ptr.restype = vp
     L.ug_dvec_copy.argtypes = [vp, u64, vp, u64, u64]
@@ -191,6 +192,7 @@ def load():
     L.ug_msm_g1.argtypes = [vp, vp, vp, i64, vp]
     L.ug_msm_g2.argtypes = [vp, vp, vp, i64, vp]
     L.ug_msm_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.ug_msm_batch_enqueue.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.ug_hpoly_create.argtypes = [vp, vp, u64, u32, u32, pp]
     L.ug_hpoly_run.argtypes = [vp, vp, vp]
     L.ug_hpoly_run_vectors.argtypes = [vp, vp, u64, C.c_int, vp, u64]

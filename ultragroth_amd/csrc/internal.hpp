@@ -227,7 +227,6 @@ struct CapturedSpan { hipEvent_t e0 = nullptr, e1 = nullptr; u64 units = 0; };
 
 struct MsmStats {                 // HIP-event timing of one kernel's launches (bucket accumulation G1 / G2, NTT passes)
     static constexpr int SLOTS = 64;                // launches that may be in flight before collect()
-    static constexpr int MAX_BATCH = 8;             // MSMs queued back to back by ug_msm_batch
     hipEvent_t ev0[SLOTS] = {}, ev1[SLOTS] = {};
     u64 slot_entries[SLOTS] = {};
     int pending = 0;
@@ -259,34 +258,31 @@ struct MsmPending {
 constexpr int MSM_G2_PT_WORDS = 72;                 // words of a G2 XYZZ point in a result block (msm.hip: G2Cfg)
 constexpr size_t MSM_PENDING_WORDS = 128 * 72;      // room for the largest result block (<= 127 G2 points); the LAST word
                                                     // receives the schedule's failure flag (meta[7])
-MsmPending msm_enqueue_g1(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream,
-                          MsmStats* stats, u32* pinned_host);
-MsmPending msm_enqueue_g2(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream,
-                          MsmStats* stats, u32* pinned_host);
-// up to MSM_BATCH_MAX products over one schedule: one accumulation launch each, the latency-bound tail kernels once for all
-constexpr int MSM_BATCH_MAX = 4;
-void msm_enqueue_batch_g1(const MsmSchedule& s, MsmWorkspace& ws, int count, const u32* const* bases, const u64* n_bases, const int64_t* delta,
-                          hipStream_t stream, MsmStats* stats, u32* const* pinned_host, MsmPending* pend);
-// phase (msm_enqueue_batch_g2, msm_enqueue_group_g1): the whole call, or its two halves made one after the other with the same
-// arguments -- the accumulation launches, and everything behind them (on a stream that is ordered behind the accumulation)
+constexpr int MSM_QUEUE_DEPTH = 8;                  // products a context may hold queued before ug_ctx_collect (one pinned result block each)
+constexpr int MSM_BATCH_WIDTH = 4;                  // products of one msm_enqueue call
+// One call of msm_enqueue: `count` products over one schedule, product j the sum of scalar_i * bases[i + delta] over the schedule's
+// scalars (local index i; `bases`: n_bases packed affine records in device Montgomery form, (0,0) = infinity; entries whose base
+// index falls outside [0, n_bases) are skipped), its window sums going to `host`.
+// group = 2 or 3: the `count` = group products of ONE interleaved array of group-point records -- bases (n_bases: records per window
+// table) and delta are read from product 0 only, host from every product. G1 only.
+struct MsmCall {
+    struct Product { const u32* bases = nullptr; u64 n_bases = 0; int64_t delta = 0; u32* host = nullptr; };
+    int count = 0;
+    Product products[MSM_BATCH_WIDTH];
+    int group = 0;
+};
+// phase: the whole call, or its two halves made one after the other with the same arguments -- the accumulation launches, and
+// everything behind them (on a stream that is ordered behind the accumulation)
 constexpr int MSM_PHASE_ALL = 0, MSM_PHASE_ACCUMULATE = 1, MSM_PHASE_TAIL = 2;
-void msm_enqueue_batch_g2(const MsmSchedule& s, MsmWorkspace& ws, int count, const u32* const* bases, const u64* n_bases, const int64_t* delta,
-                          hipStream_t stream, MsmStats* stats, u32* const* pinned_host, MsmPending* pend, int phase = MSM_PHASE_ALL);
-// `members` (2 or 3) products over ONE interleaved array of members-point records (n_slots records per window table); pinned_host /
-// pend: one per member
-void msm_enqueue_group_g1(const MsmSchedule& s, MsmWorkspace& ws, int members, const u32* bases, u64 n_slots, int64_t delta, hipStream_t stream,
-                          MsmStats* stats, u32* const* pinned_host, MsmPending* pend, int phase = MSM_PHASE_ALL);
+// queues the call's kernels and result copies: one accumulation launch per product (one in all for a group), the latency-bound
+// tail kernels once for all of them; pend[j] describes product j's result block for msm_collect_*
+void msm_enqueue(bool g2, const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, MsmStats* stats, MsmPending* pend,
+                 int phase = MSM_PHASE_ALL);
 // 64-byte records of one member set -> record (slot0 + i) * members + member of a group array
 void interleave_points_g1(u32* dst, const u32* src, u64 n, int members, int member, u64 slot0, hipStream_t stream);
 // (vector: which scalar vector's sum, below p.vectors)
 G1XYZZ msm_collect_g1(const MsmPending& p, int vector = 0);
 G2XYZZ msm_collect_g2(const MsmPending& p, int vector = 0);
-
-// sum over the schedule's scalars (local index i) of scalar_i * base[i + delta]; bases is a device array
-// of n_bases packed affine records in device Montgomery form ((0,0) = infinity); entries whose base
-// index falls outside [0, n_bases) are skipped. Result is a host XYZZ point.
-G1XYZZ msm_g1(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream, MsmStats* stats);
-G2XYZZ msm_g2(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream, MsmStats* stats);
 
 // zkey affine records (reference Montgomery form, R = 2^256) -> device form, in place on the device
 void convert_points_g1(u32* pts, u64 n, hipStream_t stream);

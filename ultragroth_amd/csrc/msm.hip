@@ -1070,27 +1070,27 @@ namespace {
 // medium-bucket and tree-sum launches of A, B1, C become one launch each (- 0.3 ms per proof); the bucket reduction itself
 // is bound by its arithmetic (two full additions per bucket and a scalar multiple per chunk), not by latency, and gains
 // only through the longer chunks a batch allows (reduce_chunk).
-constexpr int MSM_MAX_BATCH = 4;
-// group: 0 = `count` separate base arrays; K = bases[0] is ONE interleaved array of K-member records (n_bases[0] slots; count
+// group: 0 = `count` separate base arrays; K = product 0 holds ONE interleaved array of K-member records (n_bases slots; count
 // == K): a single launch of segment_accumulate_group_kernel accumulates all K products
 // phase: MSM_PHASE_ALL, or the two halves of the same call made one after the other with the same arguments -- MSM_PHASE_ACCUMULATE
 // (the accumulation launches) and MSM_PHASE_TAIL (everything behind them, possibly on another stream that has been ordered behind
 // the accumulation): ug_msm_witness_enqueue runs the G1 and the G2 tails of a proof side by side
 template <class Cfg>
-void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const u32* const* bases, const u64* n_bases, const int64_t* delta,
-                       hipStream_t stream, MsmStats* stats, u32* const* pinned_host, MsmPending* pend, int group = 0, int phase = MSM_PHASE_ALL) {
+void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, MsmStats* stats, MsmPending* pend, int phase) {
+    const int count = call.count, group = call.group;
+    const MsmCall::Product* const p = call.products;
     const bool do_acc = phase != MSM_PHASE_TAIL, do_tail = phase != MSM_PHASE_ACCUMULATE;
     typedef typename Cfg::F F;
     const MsmGeometry& g = s.geo;
-    if (count < 1 || count > MSM_MAX_BATCH) throw std::logic_error("msm: batch size");
+    if (count < 1 || count > MSM_BATCH_WIDTH) throw std::logic_error("msm: batch size");
     // products without points (or an empty schedule) are the point at infinity and take no part
-    int live[MSM_MAX_BATCH], k = 0;
+    int live[MSM_BATCH_WIDTH], k = 0;
     for (int j = 0; j < count; j++) {
         pend[j] = MsmPending();
         pend[j].g2 = Cfg::PT_WORDS == G2Cfg::PT_WORDS;
         pend[j].c = g.c; pend[j].window_sets = g.window_sets(); pend[j].class_sets = g.class_sets(); pend[j].cls = g.cls; pend[j].vectors = g.vectors;
-        pend[j].host = pinned_host[j];
-        if (g.n == 0 || n_bases[group ? 0 : j] == 0) continue;
+        pend[j].host = p[j].host;
+        if (g.n == 0 || p[group ? 0 : j].n_bases == 0) continue;
         if ((size_t)g.result_points() * Cfg::PT_WORDS > MSM_PENDING_WORDS - 1) throw std::logic_error("msm: result block too large");
         pend[j].empty = false;
         live[k++] = j;
@@ -1119,8 +1119,8 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const 
             int slot = stats ? stats->begin(stream, g.n * g.windows * (u64)group) : -1;
             if (nseg) {
                 const dim3 grid((unsigned)((nseg + 255) / 256)), block(256);
-#define UG_GROUP_LAUNCH(K_) hipLaunchKernelGGL((segment_accumulate_group_kernel<K_>), grid, block, 0, stream, bases[0], n_bases[0], \
-                                                   delta[0], s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail, ws.bucket_pts, ws.slot_pts,   \
+#define UG_GROUP_LAUNCH(K_) hipLaunchKernelGGL((segment_accumulate_group_kernel<K_>), grid, block, 0, stream, p[0].bases, p[0].n_bases, \
+                                                   p[0].delta, s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail, ws.bucket_pts, ws.slot_pts,   \
                                                    bucket_stride, slot_stride UG_FOLD_ARG)
                 if (group == 3) UG_GROUP_LAUNCH(3);
                 else if (group == 2) UG_GROUP_LAUNCH(2);
@@ -1137,7 +1137,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const 
         int slot = stats ? stats->begin(stream, g.n * g.windows) : -1;
         if (nseg) {
             hipLaunchKernelGGL(segment_accumulate_kernel<Cfg>, dim3((unsigned)((nseg + ACC_BLOCK - 1) / ACC_BLOCK)), dim3(ACC_BLOCK), 0, stream,
-                               bases[j], n_bases[j], delta[j], s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail,
+                               p[j].bases, p[j].n_bases, p[j].delta, s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail,
                                ws.bucket_pts + q * bucket_stride, ws.slot_pts + q * slot_stride);
             UG_KERNEL_CHECK();
         }
@@ -1205,7 +1205,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const 
         UG_KERNEL_CHECK();
     }
     for (int q = 0; q < k; q++) {
-        u32* host = pinned_host[live[q]];
+        u32* host = p[live[q]].host;
         const size_t set_words = (size_t)windows * Cfg::PT_WORDS;
         UG_HIP(hipMemcpyAsync(host, cur + (size_t)q * set_words, set_words * 4, hipMemcpyDeviceToHost, stream));
         if (classes) UG_HIP(hipMemcpyAsync(host + set_words, cur + ((size_t)bw + (size_t)q * windows) * Cfg::PT_WORDS, set_words * 4, hipMemcpyDeviceToHost, stream));
@@ -1213,13 +1213,6 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, int count, const 
                                             (size_t)wsets * Cfg::PT_WORDS * 4, hipMemcpyDeviceToHost, stream));
         UG_HIP(hipMemcpyAsync(host + MSM_PENDING_WORDS - 1, s.meta + 7, 4, hipMemcpyDeviceToHost, stream));
     }
-}
-template <class Cfg>
-MsmPending msm_enqueue(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta,
-                       hipStream_t stream, MsmStats* stats, u32* pinned_host) {
-    MsmPending pend;
-    msm_enqueue_multi<Cfg>(s, ws, 1, &bases, &n_bases, &delta, stream, stats, &pinned_host, &pend);
-    return pend;
 }
 
 // Horner over the window sets, top first (one set with window tables). With bucket classes (internal.hpp: BucketClasses) a
@@ -1256,17 +1249,6 @@ XYZZ<typename Cfg::F> msm_collect(const MsmPending& p, int vector = 0) {
         acc = xyzz_add(acc, wsum);
     }
     return acc;
-}
-
-// the synchronous form: queue, wait, collect (result block in a caller-side buffer, not pinned: the copy then waits)
-template <class Cfg>
-XYZZ<typename Cfg::F> msm_run(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta,
-                              hipStream_t stream, MsmStats* stats) {
-    std::vector<u32> host(MSM_PENDING_WORDS);
-    MsmPending p = msm_enqueue<Cfg>(s, ws, bases, n_bases, delta, stream, stats, host.data());
-    UG_HIP(hipStreamSynchronize(stream));
-    if (stats) stats->collect();
-    return msm_collect<Cfg>(p);
 }
 }  // namespace
 
@@ -1329,35 +1311,14 @@ void MsmStats::collect() {
     pending = 0;
 }
 
-MsmPending msm_enqueue_g1(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream,
-                          MsmStats* stats, u32* pinned_host) { return msm_enqueue<G1Cfg>(s, ws, bases, n_bases, delta, stream, stats, pinned_host); }
-MsmPending msm_enqueue_g2(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream,
-                          MsmStats* stats, u32* pinned_host) { return msm_enqueue<G2Cfg>(s, ws, bases, n_bases, delta, stream, stats, pinned_host); }
-void msm_enqueue_batch_g1(const MsmSchedule& s, MsmWorkspace& ws, int count, const u32* const* bases, const u64* n_bases, const int64_t* delta,
-                          hipStream_t stream, MsmStats* stats, u32* const* pinned_host, MsmPending* pend) {
-    msm_enqueue_multi<G1Cfg>(s, ws, count, bases, n_bases, delta, stream, stats, pinned_host, pend);
-}
-void msm_enqueue_batch_g2(const MsmSchedule& s, MsmWorkspace& ws, int count, const u32* const* bases, const u64* n_bases, const int64_t* delta,
-                          hipStream_t stream, MsmStats* stats, u32* const* pinned_host, MsmPending* pend, int phase) {
-    msm_enqueue_multi<G2Cfg>(s, ws, count, bases, n_bases, delta, stream, stats, pinned_host, pend, 0, phase);
-}
-void msm_enqueue_group_g1(const MsmSchedule& s, MsmWorkspace& ws, int members, const u32* bases, u64 n_slots, int64_t delta, hipStream_t stream,
-                          MsmStats* stats, u32* const* pinned_host, MsmPending* pend, int phase) {
-    if (members < 2 || members > 3) throw std::invalid_argument("msm: a base group has 2 or 3 members");
-    const u32* b[MSM_MAX_BATCH] = {bases, bases, bases, bases};
-    const u64 n[MSM_MAX_BATCH] = {n_slots, n_slots, n_slots, n_slots};
-    const int64_t d[MSM_MAX_BATCH] = {delta, delta, delta, delta};
-    msm_enqueue_multi<G1Cfg>(s, ws, members, b, n, d, stream, stats, pinned_host, pend, members, phase);
+void msm_enqueue(bool g2, const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, MsmStats* stats, MsmPending* pend,
+                 int phase) {
+    if (call.group && (call.group < 2 || call.group > 3 || call.count != call.group)) throw std::invalid_argument("msm: a base group has 2 or 3 members");
+    if (!g2) msm_enqueue_multi<G1Cfg>(s, ws, call, stream, stats, pend, phase);
+    else msm_enqueue_multi<G2Cfg>(s, ws, call, stream, stats, pend, phase);
 }
 G1XYZZ msm_collect_g1(const MsmPending& p, int vector) { return msm_collect<G1Cfg>(p, vector); }
 G2XYZZ msm_collect_g2(const MsmPending& p, int vector) { return msm_collect<G2Cfg>(p, vector); }
-
-G1XYZZ msm_g1(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream, MsmStats* stats) {
-    return msm_run<G1Cfg>(s, ws, bases, n_bases, delta, stream, stats);
-}
-G2XYZZ msm_g2(const MsmSchedule& s, MsmWorkspace& ws, const u32* bases, u64 n_bases, int64_t delta, hipStream_t stream, MsmStats* stats) {
-    return msm_run<G2Cfg>(s, ws, bases, n_bases, delta, stream, stats);
-}
 
 namespace {
 template <class Cfg>

@@ -126,7 +126,7 @@ struct ug_ctx {
     // to its accumulator) the next time the stream is known to be idle -- ug_ctx_collect, ug_ctx_timings, ug_ctx_sync
     struct Span { hipEvent_t e0, e1; double* acc; };
     std::vector<Span> spans_free, spans_pending;
-    // MSMs queued by ug_msm_batch_enqueue whose results are still on their way (pinned_results slot k <-> pending_msm[k])
+    // the product queue: MSMs queued by ug_msm_*_enqueue whose results are still on their way (pinned_results block k <-> pending_msm[k])
     struct QueuedMsm { MsmPending pend; void* out; bool g2; };
     std::vector<QueuedMsm> pending_msm;
     hipEvent_t order_event = nullptr;      // ug_ctx_wait
@@ -154,7 +154,7 @@ struct ug_ctx {
         }
         return lookup_stage;
     }
-    u32* pinned_results = nullptr;         // MsmStats::SLOTS result blocks of queued MSMs (ug_msm_batch)
+    u32* pinned_results = nullptr;         // MSM_QUEUE_DEPTH result blocks of MSM_PENDING_WORDS words: the queued products' (pending_msm)
     std::vector<void*> deferred_free;      // staging memory of queued set-up work: hipFree waits for the whole device, so it is
                                            // freed the next time the stream is idle anyway (ug_ctx_sync, destroy)
     void free_deferred() { for (void* p : deferred_free) hipFree(p); deferred_free.clear(); }
@@ -358,6 +358,39 @@ void sync_and_resolve(ug_ctx* c) {
     resolve_spans(c);
     c->free_deferred();
 }
+// The product queue of a context: ug_ctx::pending_msm, slot k of which owns block k of ug_ctx::pinned_results. An enqueue call
+// takes its slots at the end of the queue through this object, which gives them back unless commit() is reached: nothing of a
+// failed call stays queued.
+struct QueueSlots {
+    ug_ctx* c; const size_t first; bool committed = false;
+    QueueSlots(ug_ctx* c_, int n) : c(c_), first(c_->pending_msm.size()) {            // (takes nothing yet: add)
+        if (n < 0 || first + (size_t)n > (size_t)MSM_QUEUE_DEPTH)
+            throw std::invalid_argument("at most " + std::to_string(MSM_QUEUE_DEPTH) + " products may be queued before ug_ctx_collect");
+    }
+    QueueSlots(const QueueSlots&) = delete;
+    QueueSlots& operator=(const QueueSlots&) = delete;
+    ~QueueSlots() { if (!committed) c->pending_msm.resize(first); }
+    // the next slot, for a product whose records go to `out`: its pinned result block
+    u32* add(void* out, bool g2) {
+        c->pending_msm.push_back(ug_ctx::QueuedMsm{MsmPending(), out, g2});
+        return c->pinned_results + (c->pending_msm.size() - 1) * MSM_PENDING_WORDS;
+    }
+    // pend[k]: what msm_enqueue said about the k-th slot added
+    void commit(const MsmPending* pend) {
+        for (size_t k = first; k < c->pending_msm.size(); k++) c->pending_msm[k].pend = pend[k - first];
+        committed = true;
+    }
+};
+// MsmCall::Product::delta: the schedule's scalar i multiplies record i + delta of the set
+int64_t schedule_delta(const ug_schedule* s, const ug_bases* b, int64_t index_shift = 0) { return (int64_t)s->first - index_shift - (int64_t)b->global_first; }
+// the call of a base group's K products, results in the next K slots of the queue
+MsmCall group_call(QueueSlots& slots, const ug_bases* group, const ug_schedule* s, void* const* outs) {
+    MsmCall call;
+    call.count = call.group = group->members;
+    call.products[0] = {group->pts, group->slots, schedule_delta(s, group), nullptr};
+    for (int m = 0; m < call.count; m++) call.products[m].host = slots.add(outs[m], false);
+    return call;
+}
 template <class F> void store_mont256(uint8_t* out, const F& v);
 template <> void store_mont256<Fq>(uint8_t* out, const Fq& v) { u32 w[8]; to_mont256(w, v); memcpy(out, w, 32); }
 }  // namespace
@@ -391,7 +424,7 @@ int ug_ctx_create_priority(ug_ctx** out, int device, int priority_class) {
     }
     UG_HIP(hipEventCreateWithFlags(&c->order_event, hipEventDisableTiming));
     for (int k = 0; k < 4; k++) c->stats[k].create();
-    UG_HIP(hipHostMalloc((void**)&c->pinned_results, (size_t)MsmStats::MAX_BATCH * MSM_PENDING_WORDS * 4, hipHostMallocDefault));
+    UG_HIP(hipHostMalloc((void**)&c->pinned_results, (size_t)MSM_QUEUE_DEPTH * MSM_PENDING_WORDS * 4, hipHostMallocDefault));
     *out = c;
     UG_CATCH
 }
@@ -1357,39 +1390,17 @@ static void check_tables(const ug_bases* b, const ug_schedule* s) {
         throw std::invalid_argument("schedule built for window tables of stride " + std::to_string(s->sched.geo.stride) +
                                     " but the bases hold tables of stride " + std::to_string(b->table_stride));
 }
-int ug_msm_g1(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_shift, void* out) {
+// One product, synchronously: ug_msm_batch of one set, after the curve check
+static int msm_single(ug_ctx* c, const ug_bases* b, bool g2, const ug_schedule* s, int64_t index_shift, void* out) {
     UG_TRY
     if (!c || !b || !s || !out) throw std::invalid_argument("null argument");
-    if (b->g2) throw std::invalid_argument("ug_msm_g1 called with G2 bases");
-    if (b->members > 1) throw std::invalid_argument("a base group is multiplied with ug_msm_group_enqueue");
-    check_tables(b, s);
-    if (s->sched.geo.vectors > 1) return ug_msm_batch(c, 1, &b, s, &index_shift, &out);      // (V records)
-    c->use();
-    ScopedTimer tm(c, &c->msm_ms);
-    int64_t delta = (int64_t)s->first - index_shift - (int64_t)b->global_first;
+    if (b->g2 != g2) throw std::invalid_argument(g2 ? "ug_msm_g2 called with G1 bases" : "ug_msm_g1 called with G2 bases");
     if (!c->pending_msm.empty()) throw std::logic_error("collect the queued MSMs first (ug_ctx_collect)");
-    G1XYZZ r = msm_g1(s->sched, c->ws_g1, b->pts, b->empty ? 0 : b->n, delta, c->stream, c->stat(0));      // synchronises the stream
-    tm.stop();
-    sync_and_resolve(c);
-    affine_out_g1((uint8_t*)out, r);
+    return ug_msm_batch(c, 1, &b, s, &index_shift, &out);
     UG_CATCH
 }
-int ug_msm_g2(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_shift, void* out) {
-    UG_TRY
-    if (!c || !b || !s || !out) throw std::invalid_argument("null argument");
-    if (!b->g2) throw std::invalid_argument("ug_msm_g2 called with G1 bases");
-    check_tables(b, s);
-    if (s->sched.geo.vectors > 1) return ug_msm_batch(c, 1, &b, s, &index_shift, &out);      // (V records)
-    c->use();
-    ScopedTimer tm(c, &c->msm_ms);
-    int64_t delta = (int64_t)s->first - index_shift - (int64_t)b->global_first;
-    if (!c->pending_msm.empty()) throw std::logic_error("collect the queued MSMs first (ug_ctx_collect)");
-    G2XYZZ r = msm_g2(s->sched, c->ws_g2, b->pts, b->empty ? 0 : b->n, delta, c->stream, c->stat(1));      // synchronises the stream
-    tm.stop();
-    sync_and_resolve(c);
-    affine_out_g2((uint8_t*)out, r);
-    UG_CATCH
-}
+int ug_msm_g1(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_shift, void* out) { return msm_single(c, b, false, s, index_shift, out); }
+int ug_msm_g2(ug_ctx* c, const ug_bases* b, const ug_schedule* s, int64_t index_shift, void* out) { return msm_single(c, b, true, s, index_shift, out); }
 
 // Several MSMs over one schedule, queued back to back on the stream with ONE host synchronisation at the end: the
 // latency-bound tail of one product (bucket reduction, tree sums, result copy) no longer leaves the device idle while the
@@ -1398,8 +1409,7 @@ int ug_msm_batch_enqueue(ug_ctx* c, int count, const ug_bases* const* bases, con
                          void* const* outs) {
     UG_TRY
     if (!c || !s || (count && (!bases || !outs))) throw std::invalid_argument("null argument");
-    if (count < 0 || c->pending_msm.size() + (size_t)count > (size_t)MsmStats::MAX_BATCH)
-        throw std::invalid_argument("at most 8 products may be queued before ug_ctx_collect");
+    QueueSlots slots(c, count);
     for (int k = 0; k < count; k++) {
         if (!bases[k] || !outs[k]) throw std::invalid_argument("null argument");
         if (bases[k]->members > 1) throw std::invalid_argument("a base group is multiplied with ug_msm_group_enqueue");
@@ -1409,37 +1419,27 @@ int ug_msm_batch_enqueue(ug_ctx* c, int count, const ug_bases* const* bases, con
     ScopedTimer tm(c, &c->msm_ms);
     // the G1 products of the call form one batch, the G2 products another (msm.hip: msm_enqueue_multi): one accumulation
     // launch per product, the tail kernels once per batch; within a curve the caller's order is kept
-    const size_t first_slot = c->pending_msm.size();
-    for (int k = 0; k < count; k++) {
-        ug_ctx::QueuedMsm q;
-        q.g2 = bases[k]->g2; q.out = outs[k];
-        c->pending_msm.push_back(q);
-    }
-    try {
+    u32* host[MSM_QUEUE_DEPTH]; MsmPending pend[MSM_QUEUE_DEPTH];
+    for (int k = 0; k < count; k++) host[k] = slots.add(outs[k], bases[k]->g2);
     for (int g2 = 0; g2 < 2; g2++) {
-        int idx[MSM_BATCH_MAX], n = 0;
+        MsmCall call; int idx[MSM_BATCH_WIDTH];
         auto flush = [&] {
-            if (!n) return;
-            const u32* pts[MSM_BATCH_MAX]; u64 nb[MSM_BATCH_MAX]; int64_t delta[MSM_BATCH_MAX]; u32* host[MSM_BATCH_MAX]; MsmPending pend[MSM_BATCH_MAX];
-            for (int q = 0; q < n; q++) {
-                const ug_bases* b = bases[idx[q]];
-                pts[q] = b->pts; nb[q] = b->empty ? 0 : b->n;      // (an all-infinity set takes no part: msm_enqueue_multi)
-                delta[q] = (int64_t)s->first - (index_shifts ? index_shifts[idx[q]] : 0) - (int64_t)b->global_first;
-                host[q] = c->pinned_results + (first_slot + idx[q]) * MSM_PENDING_WORDS;
-            }
-            if (g2) msm_enqueue_batch_g2(s->sched, c->ws_g2, n, pts, nb, delta, c->stream, c->stat(1), host, pend);
-            else msm_enqueue_batch_g1(s->sched, c->ws_g1, n, pts, nb, delta, c->stream, c->stat(0), host, pend);
-            for (int q = 0; q < n; q++) c->pending_msm[first_slot + idx[q]].pend = pend[q];
-            n = 0;
+            if (!call.count) return;
+            MsmPending part[MSM_BATCH_WIDTH];
+            msm_enqueue(g2, s->sched, g2 ? c->ws_g2 : c->ws_g1, call, c->stream, c->stat(g2), part);
+            for (int q = 0; q < call.count; q++) pend[idx[q]] = part[q];
+            call.count = 0;
         };
         for (int k = 0; k < count; k++) {
-            if ((bases[k]->g2 ? 1 : 0) != g2) continue;
-            idx[n++] = k;
-            if (n == MSM_BATCH_MAX) flush();
+            const ug_bases* b = bases[k];
+            if ((b->g2 ? 1 : 0) != g2) continue;
+            idx[call.count] = k;                  // (an all-infinity set takes no part: msm_enqueue_multi)
+            call.products[call.count++] = {b->pts, b->empty ? 0 : b->n, schedule_delta(s, b, index_shifts ? index_shifts[k] : 0), host[k]};
+            if (call.count == MSM_BATCH_WIDTH) flush();
         }
         flush();
     }
-    } catch (...) { c->pending_msm.resize(first_slot); throw; }      // nothing of a failed call stays queued
+    slots.commit(pend);
     tm.stop();
     UG_CATCH
 }
@@ -1450,24 +1450,14 @@ int ug_msm_group_enqueue(ug_ctx* c, const ug_bases* group, const ug_schedule* s,
     if (!c || !group || !s || !outs) throw std::invalid_argument("null argument");
     if (group->members < 2) throw std::invalid_argument("not a base group");
     const int K = group->members;
-    if (c->pending_msm.size() + (size_t)K > (size_t)MsmStats::MAX_BATCH) throw std::invalid_argument("at most 8 products may be queued before ug_ctx_collect");
+    QueueSlots slots(c, K);
     for (int m = 0; m < K; m++) if (!outs[m]) throw std::invalid_argument("null argument");
     check_tables(group, s);
     c->use();
     ScopedTimer tm(c, &c->msm_ms);
-    const size_t first_slot = c->pending_msm.size();
-    for (int m = 0; m < K; m++) {
-        ug_ctx::QueuedMsm q;
-        q.g2 = false; q.out = outs[m];
-        c->pending_msm.push_back(q);
-    }
-    try {
-        u32* host[MSM_BATCH_MAX]; MsmPending pend[MSM_BATCH_MAX];
-        for (int m = 0; m < K; m++) host[m] = c->pinned_results + (first_slot + m) * MSM_PENDING_WORDS;
-        const int64_t delta = (int64_t)s->first - (int64_t)group->global_first;
-        msm_enqueue_group_g1(s->sched, c->ws_g1, K, group->pts, group->slots, delta, c->stream, c->stat(3), host, pend);
-        for (int m = 0; m < K; m++) c->pending_msm[first_slot + m].pend = pend[m];
-    } catch (...) { c->pending_msm.resize(first_slot); throw; }
+    MsmPending pend[MSM_BATCH_WIDTH];
+    msm_enqueue(false, s->sched, c->ws_g1, group_call(slots, group, s, outs), c->stream, c->stat(3), pend);
+    slots.commit(pend);
     tm.stop();
     UG_CATCH
 }
@@ -1482,7 +1472,7 @@ int ug_msm_witness_enqueue(ug_ctx* c, const ug_bases* group, const ug_bases* g2s
     if (!c || !group || !g2set || !s || !outs_group || !out_g2) throw std::invalid_argument("null argument");
     if (group->members < 2 || !g2set->g2 || g2set->members > 1) throw std::invalid_argument("a base group and a G2 set are expected");
     const int K = group->members;
-    if (c->pending_msm.size() + (size_t)K + 1 > (size_t)MsmStats::MAX_BATCH) throw std::invalid_argument("at most 8 products may be queued before ug_ctx_collect");
+    QueueSlots slots(c, K + 1);
     for (int m = 0; m < K; m++) if (!outs_group[m]) throw std::invalid_argument("null argument");
     check_tables(group, s); check_tables(g2set, s);
     c->use();
@@ -1492,36 +1482,25 @@ int ug_msm_witness_enqueue(ug_ctx* c, const ug_bases* group, const ug_bases* g2s
         UG_HIP(hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming));
     }
     ScopedTimer tm(c, &c->msm_ms);
-    const size_t first_slot = c->pending_msm.size();
-    for (int m = 0; m <= K; m++) {
-        ug_ctx::QueuedMsm q;
-        q.g2 = m == K; q.out = m == K ? out_g2 : outs_group[m];
-        c->pending_msm.push_back(q);
-    }
     try {
-        u32* host[MSM_BATCH_MAX]; MsmPending pend[MSM_BATCH_MAX];
-        for (int m = 0; m < K; m++) host[m] = c->pinned_results + (first_slot + m) * MSM_PENDING_WORDS;
-        u32* host2[1] = {c->pinned_results + (first_slot + K) * MSM_PENDING_WORDS};
-        MsmPending pend2[1];
-        const int64_t delta = (int64_t)s->first - (int64_t)group->global_first;
-        const u32* pts2[1] = {g2set->pts};
-        const u64 nb2[1] = {g2set->empty ? 0 : g2set->n};
-        const int64_t delta2[1] = {(int64_t)s->first - (int64_t)g2set->global_first};
+        MsmPending pend[MSM_BATCH_WIDTH + 1];      // the group's, then the G2 product's
+        const MsmCall g1 = group_call(slots, group, s, outs_group);
+        MsmCall g2;
+        g2.count = 1;
+        g2.products[0] = {g2set->pts, g2set->empty ? 0 : g2set->n, schedule_delta(s, g2set), slots.add(out_g2, true)};
         // both accumulations, back to back
-        msm_enqueue_group_g1(s->sched, c->ws_g1, K, group->pts, group->slots, delta, c->stream, c->stat(3), host, pend, MSM_PHASE_ACCUMULATE);
-        msm_enqueue_batch_g2(s->sched, c->ws_g2, 1, pts2, nb2, delta2, c->stream, c->stat(1), host2, pend2, MSM_PHASE_ACCUMULATE);
+        msm_enqueue(false, s->sched, c->ws_g1, g1, c->stream, c->stat(3), pend, MSM_PHASE_ACCUMULATE);
+        msm_enqueue(true, s->sched, c->ws_g2, g2, c->stream, c->stat(1), pend + K, MSM_PHASE_ACCUMULATE);
         // the G2 tail on the side stream, the G1 tail on the context's, then the context's stream waits for the side
         UG_HIP(hipEventRecord(c->side_fork, c->stream));
         UG_HIP(hipStreamWaitEvent(c->side_stream, c->side_fork, 0));
-        msm_enqueue_batch_g2(s->sched, c->ws_g2, 1, pts2, nb2, delta2, c->side_stream, nullptr, host2, pend2, MSM_PHASE_TAIL);
-        msm_enqueue_group_g1(s->sched, c->ws_g1, K, group->pts, group->slots, delta, c->stream, nullptr, host, pend, MSM_PHASE_TAIL);
+        msm_enqueue(true, s->sched, c->ws_g2, g2, c->side_stream, nullptr, pend + K, MSM_PHASE_TAIL);
+        msm_enqueue(false, s->sched, c->ws_g1, g1, c->stream, nullptr, pend, MSM_PHASE_TAIL);
         UG_HIP(hipEventRecord(c->side_join, c->side_stream));
         UG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-        for (int m = 0; m < K; m++) c->pending_msm[first_slot + m].pend = pend[m];
-        c->pending_msm[first_slot + K].pend = pend2[0];
+        slots.commit(pend);
     } catch (...) {
-        c->pending_msm.resize(first_slot);
-        if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
+        (void)hipStreamSynchronize(c->side_stream);      // (whatever the side stream got reads the schedule and the workspace)
         throw;
     }
     tm.stop();
