@@ -36,6 +36,10 @@
  *                                                 never (default) | 1 field range and curve equation | 2 also the G2 points'
  *                                                 membership of the order-r subgroup (include/prover.h: a bad key is refused)
  *                                                 (any other value fails the creation)
+ *                      ULTRAGROTH_VERIFY_JUDGE=0|1  ug_groth16_verify_batch / ug_ultra_groth_verify_batch: 1 = the suspects of a rejected
+ *                                                 batch are decided by their own equations on the device (include/verifier.h, the
+ *                                                 judge; the same verdicts) | 0 / unset: searched and verified on the host (default)
+ *                                                 (any other value fails the call)
  *                      ULTRAGROTH_TABLES=0|1|2    fixed-base window tables: never | created provers (default) | one-shot calls too
  *                      ULTRAGROTH_OVERLAP=0|1|2   H branch behind / beside (default since round 5) the witness products on one device
  *                                                 (0: one kernel on the chip at a time, for clean per-kernel times)

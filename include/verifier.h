@@ -42,7 +42,10 @@ int ultra_groth_verify(const char *proof, const char *inputs, const char *verifi
  * device < 0: the same protocol on host threads, no GPU needed.
  * Returns VERIFIER_ERROR for null arguments, count < 0, a key that does not parse (the single call's messages) or a device
  * error; verdicts is then untouched. Else VERIFIER_VALID_PROOF when every verdict is, else VERIFIER_INVALID_PROOF with
- * error_msg = "proof <first bad index>: <reason>". count == 0 is valid. stats may be NULL. */
+ * error_msg = "proof <first bad index>: <reason>". count == 0 is valid. stats may be NULL.
+ * These two calls take their options from the environment: ULTRAGROTH_VERIFY_JUDGE=1 switches the judge (below) on with the
+ * library's search_width and judge_min, unset or 0 leaves everything as described here; any other value fails the call with
+ * a message that names the variable. They write the 40 bytes of ug_verify_batch_stats, whatever the setting. */
 typedef struct {
     unsigned long long batch_checks;   /* final exponentiations of batch equations (1 per accepted pass)              */
     unsigned long long single_checks;  /* proofs handed to the single-proof verifier                                  */
@@ -55,15 +58,54 @@ int ug_groth16_verify_batch(int device, int count, const char *const *proofs, co
 int ug_ultra_groth_verify_batch(int device, int count, const char *const *proofs, const char *const *inputs,
                                 const char *verification_key, int *verdicts, ug_verify_batch_stats *stats,
                                 char *error_msg, unsigned long error_msg_maxsize);
+
+/* ---- the judge: suspect proofs decided on the device ------------------------------------------------------------------
+ * The search of a rejected pass and the single-proof verifier behind it are host work whose amount the sender of the
+ * proofs decides (1 % bad proofs among 2^14: ~1200 batch checks and ~2600 single verifications). With the judge on,
+ *   1. a rejected pass is searched breadth first with the same batch checks, from the root: while the failing nodes cover
+ *      more than 16 proofs each and number at most search_width, both children of every failing node are checked and the
+ *      failing ones kept; then every proof under a failing node is a suspect (search_width = 0: the whole pass);
+ *   2. the proofs whose pi_b is outside the subgroup are suspects as well;
+ *   3. when the call has at least judge_min suspects, each is decided by its OWN equation -- the single verifier's, no
+ *      random scalar, a pi_b outside the subgroup judged as groth16_verify judges it -- one lane per suspect in launches of
+ *      up to 65536 (judge_kernel of pairing.hip; the final exponentiation is code shared with the host, pairing.hpp). With
+ *      fewer suspects they go to the single-proof verifier on the host, as with the judge off.
+ * device < 0: the same policy with the judge on host threads. A key the batch refuses (a point off its curve, a G2 point
+ * outside the subgroup) keeps its path: the single-proof verifier decides every proof.
+ * Verdicts, the result code and error_msg are those of the judge-off call on the same inputs: the single verifier's.
+ * judge = 0 is exactly the path of ug_groth16_verify_batch without ULTRAGROTH_VERIFY_JUDGE, stats included. */
+typedef struct {
+    unsigned size;                     /* sizeof(ug_verify_batch_options)                                              */
+    int judge;                         /* 0 = off, 1 = on                                                              */
+    int search_width;                  /* failing nodes the host search may hold per level; < 0: the library's (2)     */
+    int judge_min;                     /* suspects of a call from which the judge decides them; < 0: the library's (256)*/
+} ug_verify_batch_options;
+typedef struct {
+    ug_verify_batch_stats base;
+    unsigned long long judged;         /* proofs decided by the judge                                                  */
+    unsigned long long judge_launches; /* launches of judge_kernel (0 with device < 0)                                 */
+    double judge_ms;                   /* wall time of the judge's device work, part of base.device_ms                 */
+} ug_verify_batch_stats_ex;
+/* options == NULL: as the calls above (the judge from the environment). */
+int ug_groth16_verify_batch_opt(int device, int count, const char *const *proofs, const char *const *inputs,
+                                const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
+                                ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+int ug_ultra_groth_verify_batch_opt(int device, int count, const char *const *proofs, const char *const *inputs,
+                                    const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
+                                    ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+
 /* milliseconds of the last device pass of this process: miller_batch_kernel, the Fq12 tree, the G1 tree */
 void ug_verify_batch_kernel_ms(double ms[3]);
 
 /* Test hooks, live only in a process started with ULTRAGROTH_TEST_HOOKS=1 (else they return 1 and write nothing).
  * ug_test_verify_batch_trace: for proof `index` of the last batch call, if it was batched, its scalar r (128 bits) and
  * f = miller(pi_b, r pi_a) as 12 x 9 limbs of 29 bits (canonical, Montgomery radix 2^261). ug_test_miller: the host's
- * Miller loop of one pair given as zkey records (Montgomery radix 2^256), in the same form. */
+ * Miller loop of one pair given as zkey records (Montgomery radix 2^256), in the same form. ug_test_final_exp: the final
+ * exponentiation's is-one test of f in that form -- g = (f^(p^2) f)^((p^4 - p^2 + 1)/r), the value after the hard part, and
+ * *is_one = whether f^((p^12 - 1)/r) is 1 -- on the host for device < 0, else by a one-lane launch of the device code. */
 int ug_test_verify_batch_trace(int index, unsigned int scalar[4], unsigned int f[108]);
 int ug_test_miller(const unsigned char g1[64], const unsigned char g2[128], unsigned int f[108]);
+int ug_test_final_exp(int device, const unsigned int f[108], unsigned int g[108], int *is_one);
 
 #ifdef __cplusplus
 }

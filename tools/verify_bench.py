@@ -8,6 +8,12 @@ still gets its own scalar, Miller loop and tree leaf, so the work is that of N d
 profiles/verify_batch.txt) and writes it to --out.
 
     python tools/verify_bench.py --out out/verify_batch.txt [--sizes 10,14,16] [--host-sizes 10,14]
+
+--judge 1 runs the batches through ug_groth16_verify_batch_opt with the judge on (--search-width / --judge-min, default the
+library's); --judge both runs every batch that holds bad proofs with the judge off and on in turn, --repeat times, so that the
+two are compared within one session (profiles/verify_judge.txt). With --judge the batches "50 % bad" and "every pi_b off the
+subgroup" are added at 2^14 and "1 % bad" at 2^16. --sweep W1,W2,..:M1,M2,.. repeats "one bad" and "1 % bad" at 2^14 for every
+search_width W and judge_min M.
 """
 import argparse
 import ctypes as C
@@ -35,9 +41,17 @@ def main():
     ap.add_argument("--single-sample", type=int, default=512, help="proofs timed through groth16_verify on 16 threads")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--judge", default="0", choices=["0", "1", "both"])
+    ap.add_argument("--search-width", type=int, default=-1, help="below zero: the library's default")
+    ap.add_argument("--judge-min", type=int, default=-1, help="below zero: the library's default")
+    ap.add_argument("--repeat", type=int, default=1, help="runs of every batch with bad proofs")
+    ap.add_argument("--sweep", default=None, help="search widths : judge minima, e.g. 0,2,4,8,16:16,64,256")
+    ap.add_argument("--skip-valid", action="store_true", help="only the batches with bad proofs")
+    ap.add_argument("--batches", default="none,one,1pct,50pct,offsub", help="with --skip-valid: which of these batches run")
     a = ap.parse_args()
     import ultragroth_amd as ug
-    from ultragroth_amd._lib import VerifyBatchStats
+    from ultragroth_amd._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsEx
+    from oracle import pairing as PR
     L = ug.load()
     vk = read("groth16_vkey.json", "r").encode()
     zkey, wtns = read("groth16.zkey"), read("groth16.wtns")
@@ -52,19 +66,49 @@ def main():
         print(text, flush=True)
         lines.append(text)
 
-    def run(n, device, bad=()):
+    def off_subgroup_b():
+        """a point of the twist with x = 1: on the curve, outside the subgroup of order r (its cofactor is ~2^254)"""
+        q = PR.P
+        a = PR.f2_add((1, 0), PR.f2_muls(PR.f2_inv(PR.XI), 3))
+        a1 = PR.f2_pow(a, (q - 3) // 4)
+        x0 = PR.f2_mul(a1, a)
+        alpha = PR.f2_mul(a1, x0)
+        y = PR.f2_mul((0, 1), x0) if alpha == (q - 1, 0) else PR.f2_mul(PR.f2_pow(PR.f2_add((1, 0), alpha), (q - 1) // 2), x0)
+        assert PR.f2_mul(y, y) == a
+        return [["1", "0"], [str(y[0]), str(y[1])], ["1", "0"]]
+
+    def run(n, device, bad=(), judge=None, off_subgroup=False, width=None, jmin=None):
+        """judge None: the plain entry point; 0 / 1: ug_groth16_verify_batch_opt. off_subgroup: every proof's pi_b replaced"""
         proofs = [pool[i % len(pool)][0] for i in range(n)]
         pubs = [pool[i % len(pool)][1] for i in range(n)]
         for i in bad:
             s = json.loads(pubs[i])
             s[0] = str(int(s[0]) + 1)
             pubs[i] = json.dumps(s).encode()
+        if off_subgroup:
+            b, moved = off_subgroup_b(), {}
+            for i in range(n):
+                if proofs[i] not in moved:
+                    pr = json.loads(proofs[i])
+                    pr["pi_b"] = b
+                    moved[proofs[i]] = json.dumps(pr).encode()
+                proofs[i] = moved[proofs[i]]
+            bad = range(n)
         pa, ia = (C.c_char_p * n)(*proofs), (C.c_char_p * n)(*pubs)
-        verdicts, stats, err = (C.c_int * n)(), VerifyBatchStats(), C.create_string_buffer(256)
+        verdicts, err = (C.c_int * n)(), C.create_string_buffer(256)
         t0 = time.perf_counter()
-        rc = getattr(L, "ug_groth16_verify_batch")(device, n, pa, ia, vk, verdicts, C.byref(stats), err, 255)
+        if judge is None:
+            stats = VerifyBatchStats()
+            rc = L.ug_groth16_verify_batch(device, n, pa, ia, vk, verdicts, C.byref(stats), err, 255)
+        else:
+            opt = VerifyBatchOptions(C.sizeof(VerifyBatchOptions), judge, a.search_width if width is None else width, a.judge_min if jmin is None else jmin)
+            ex = VerifyBatchStatsEx()
+            rc = L.ug_groth16_verify_batch_opt(device, n, pa, ia, vk, verdicts, C.byref(opt), C.byref(ex), err, 255)
+            stats = ex.base
+            stats.judged, stats.judge_ms = ex.judged, ex.judge_ms
         dt = time.perf_counter() - t0
-        wrong = [i for i in range(n) if (verdicts[i] != 0) != (i in set(bad))]
+        bad = set(bad)
+        wrong = [i for i in range(n) if (verdicts[i] != 0) != (i in bad)]
         if rc == 2 or wrong:
             raise RuntimeError("verify_batch: rc %d, %s, %d wrong verdicts" % (rc, err.value.decode(), len(wrong)))
         ms = (C.c_double * 3)()
@@ -74,8 +118,33 @@ def main():
     say("# batch verification, Groth16, tests/golden/trapdoor/groth16 (%d distinct proofs repeated to fill N)" % len(pool))
     run(64, a.device)                                                  # warm-up: code objects, the context
     host_sizes = {int(s) for s in a.host_sizes.split(",") if s}
+    modes = {"0": [None], "1": [1], "both": [0, 1]}[a.judge]
+
+    def bad_lines(lg, label, **kw):
+        n = 1 << lg
+        for rep in range(a.repeat):
+            for judge in modes:
+                dt, st, _ = run(n, a.device, judge=judge, **kw)
+                tail = "" if judge is None else "  judge %s judged %d judge_ms %.1f" % ("on " if judge else "off", st.judged, st.judge_ms)
+                say("N=2^%d device, %-22s %9.0f proofs/s  wall %8.1f ms  batch_checks %d single_checks %d%s"
+                    % (lg, label, n / dt, dt * 1e3, st.batch_checks, st.single_checks, tail))
+
     for lg in [int(s) for s in a.sizes.split(",")]:
         n = 1 << lg
+        one_pct = list(range(5, n, 100))[:n // 100]
+        if a.skip_valid:
+            want = a.batches.split(",")
+            if lg == 14 and "none" in want:
+                bad_lines(lg, "no bad", bad=[])
+            if lg == 14 and "one" in want:
+                bad_lines(lg, "one bad", bad=[n // 3])
+            if "1pct" in want:
+                bad_lines(lg, "1%% bad (%d)" % len(one_pct), bad=one_pct)
+            if lg == 14 and "50pct" in want:
+                bad_lines(lg, "50%% bad (%d)" % (n // 2), bad=list(range(1, n, 2)))
+            if lg == 14 and "offsub" in want:
+                bad_lines(lg, "every pi_b off subgroup", off_subgroup=True)
+            continue
         dt, st, ms = run(n, a.device)
         say("N=2^%d device      %9.0f proofs/s  wall %8.1f ms  device_ms %8.1f host_ms %8.1f  kernels: miller %.1f  f12 tree %.1f  g1 tree %.1f ms  batch_checks %d"
             % (lg, n / dt, dt * 1e3, st.device_ms, st.host_ms, ms[0], ms[1], ms[2], st.batch_checks))
@@ -83,11 +152,24 @@ def main():
             dt, st, _ = run(n, -1)
             say("N=2^%d device=-1   %9.0f proofs/s  wall %8.1f ms  (16 host threads)" % (lg, n / dt, dt * 1e3))
         if lg == 14:
-            for label, bad in (("one bad", [n // 3]), ("1%% bad (%d)" % (n // 100), list(range(5, n, 100))[:n // 100])):
-                dt, st, ms = run(n, a.device, bad)
-                say("N=2^14 device, %-14s %9.0f proofs/s  wall %8.1f ms  batch_checks %d single_checks %d" % (label, n / dt, dt * 1e3, st.batch_checks, st.single_checks))
+            bad_lines(lg, "one bad", bad=[n // 3])
+            bad_lines(lg, "1%% bad (%d)" % len(one_pct), bad=one_pct)
+            if a.judge != "0":
+                bad_lines(lg, "50%% bad (%d)" % (n // 2), bad=list(range(1, n, 2)))
+                bad_lines(lg, "every pi_b off subgroup", off_subgroup=True)
             dt, st, _ = run(n, -1, [n // 3])
             say("N=2^14 device=-1, one bad      %9.0f proofs/s  wall %8.1f ms  batch_checks %d single_checks %d" % (n / dt, dt * 1e3, st.batch_checks, st.single_checks))
+    if a.sweep:
+        widths, minima = [[int(v) for v in part.split(",")] for part in a.sweep.split(":")]
+        n = 1 << 14
+        one_pct = list(range(5, n, 100))[:n // 100]
+        say("# sweep at N=2^14, judge on: wall ms of 'one bad' and '1% bad' per (search_width, judge_min)")
+        for w in widths:
+            for m in minima:
+                t1, s1, _ = run(n, a.device, [n // 3], judge=1, width=w, jmin=m)
+                t2, s2, _ = run(n, a.device, one_pct, judge=1, width=w, jmin=m)
+                say("search_width %2d judge_min %3d   one bad %8.1f ms (checks %d singles %d judged %d)   1%% bad %8.1f ms (checks %d singles %d judged %d judge_ms %.1f)"
+                    % (w, m, t1 * 1e3, s1.batch_checks, s1.single_checks, s1.judged, t2 * 1e3, s2.batch_checks, s2.single_checks, s2.judged, s2.judge_ms))
     m = min(a.single_sample, len(pool))
     one = lambda i: L.groth16_verify(pool[i][0], pool[i][1], vk, None, 0)
     with ThreadPoolExecutor(16) as ex:

@@ -153,9 +153,9 @@ def ultra_groth_verify(proof, inputs, verification_key):
     return _verify(load().ultra_groth_verify, proof, inputs, verification_key)
 
 
-def _verify_batch(name, proofs, inputs, verification_key, device):
+def _verify_batch(name, proofs, inputs, verification_key, device, judge=None, search_width=None, judge_min=None):
     import json
-    from ._lib import VerifyBatchStats
+    from ._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsEx
     enc = lambda v: v if isinstance(v, bytes) else (v if isinstance(v, str) else json.dumps(v)).encode()
     if len(proofs) != len(inputs):
         raise ValueError("as many inputs as proofs")
@@ -163,23 +163,37 @@ def _verify_batch(name, proofs, inputs, verification_key, device):
     pa = (C.c_char_p * max(n, 1))(*[enc(p) for p in proofs])
     ia = (C.c_char_p * max(n, 1))(*[enc(p) for p in inputs])
     verdicts = (C.c_int * max(n, 1))(*([-1] * max(n, 1)))
-    stats, err = VerifyBatchStats(), C.create_string_buffer(512)
-    rc = getattr(load(), name)(device, n, pa, ia, enc(verification_key), verdicts, C.byref(stats), err, 511)
+    err = C.create_string_buffer(512)
+    if judge is None and search_width is None and judge_min is None:
+        stats = VerifyBatchStats()
+        rc = getattr(load(), name)(device, n, pa, ia, enc(verification_key), verdicts, C.byref(stats), err, 511)
+        out = {f: getattr(stats, f) for f, _ in VerifyBatchStats._fields_}
+    else:
+        dflt = lambda v: -1 if v is None else int(v)
+        opt = VerifyBatchOptions(C.sizeof(VerifyBatchOptions), int(bool(judge)), dflt(search_width), dflt(judge_min))
+        stats = VerifyBatchStatsEx()
+        rc = getattr(load(), name + "_opt")(device, n, pa, ia, enc(verification_key), verdicts, C.byref(opt), C.byref(stats), err, 511)
+        out = {f: getattr(stats.base, f) for f, _ in VerifyBatchStats._fields_}
+        out.update({f: getattr(stats, f) for f in ("judged", "judge_launches", "judge_ms")})
     if rc == VERIFIER_ERROR:
         raise VerifierError(err.value.decode(errors="replace"))
-    return list(verdicts[:n]), {f: getattr(stats, f) for f, _ in VerifyBatchStats._fields_}
+    return list(verdicts[:n]), out
 
 
-def groth16_verify_batch(proofs, inputs, verification_key, device=0):
+def groth16_verify_batch(proofs, inputs, verification_key, device=0, judge=None, search_width=None, judge_min=None):
     """ug_groth16_verify_batch (include/verifier.h): many proofs under one key, one Miller loop each on `device` (host threads for
     device < 0) and one final exponentiation for a batch that holds. Returns (verdicts, stats): verdicts[i] is VERIFIER_VALID_PROOF,
     VERIFIER_INVALID_PROOF or VERIFIER_ERROR, what groth16_verify says of proof i alone; stats is the call's ug_verify_batch_stats
-    as a dict. VerifierError for a key that does not parse or a device error."""
-    return _verify_batch("ug_groth16_verify_batch", proofs, inputs, verification_key, device)
+    as a dict. VerifierError for a key that does not parse or a device error.
+    judge / search_width / judge_min: ug_groth16_verify_batch_opt. judge=True has the suspects of a rejected batch decided by
+    their own equations on the device instead of searched and verified one by one on the host; search_width and judge_min None
+    are the library's defaults. With any of the three given, stats also carries judged, judge_launches and judge_ms; with none,
+    the call is the plain one (ULTRAGROTH_VERIFY_JUDGE in the environment decides)."""
+    return _verify_batch("ug_groth16_verify_batch", proofs, inputs, verification_key, device, judge, search_width, judge_min)
 
 
-def ultra_groth_verify_batch(proofs, inputs, verification_key, device=0):
-    return _verify_batch("ug_ultra_groth_verify_batch", proofs, inputs, verification_key, device)
+def ultra_groth_verify_batch(proofs, inputs, verification_key, device=0, judge=None, search_width=None, judge_min=None):
+    return _verify_batch("ug_ultra_groth_verify_batch", proofs, inputs, verification_key, device, judge, search_width, judge_min)
 
 
 class _ProverBase:

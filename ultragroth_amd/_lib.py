@@ -36,12 +36,24 @@ INNER_SYMBOLS = [
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/verifier.h
                     "ug_groth16_verify_batch", "ug_ultra_groth_verify_batch", "ug_verify_batch_kernel_ms",
-                    "ug_test_verify_batch_trace", "ug_test_miller"]
+                    "ug_groth16_verify_batch_opt", "ug_ultra_groth_verify_batch_opt",
+                    "ug_test_verify_batch_trace", "ug_test_miller", "ug_test_final_exp"]
 
 
 class VerifyBatchStats(C.Structure):
     _fields_ = [("batch_checks", C.c_ulonglong), ("single_checks", C.c_ulonglong), ("off_subgroup", C.c_ulonglong),
                 ("device_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+class VerifyBatchOptions(C.Structure):
+    """ug_verify_batch_options: size = sizeof, judge 0 / 1, search_width and judge_min below zero = the library's defaults"""
+    _fields_ = [("size", C.c_uint), ("judge", C.c_int), ("search_width", C.c_int), ("judge_min", C.c_int)]
+
+
+class VerifyBatchStatsEx(C.Structure):
+    _fields_ = [("base", VerifyBatchStats), ("judged", C.c_ulonglong), ("judge_launches", C.c_ulonglong), ("judge_ms", C.c_double)]
+
+
 OUTER_SYMBOLS = [
     "groth16_public_size_for_zkey_buf", "ultra_groth_public_size_for_zkey_buf",
     "groth16_public_size_for_zkey_file", "ultra_groth_public_size_for_zkey_file",
@@ -212,6 +224,9 @@ def load():
         getattr(L, n).argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_ulong]
     for n in ("ug_groth16_verify_batch", "ug_ultra_groth_verify_batch"):
         getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_char_p, vp, vp, C.c_char_p, C.c_ulong]
+    for n in ("ug_groth16_verify_batch_opt", "ug_ultra_groth_verify_batch_opt"):
+        getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+    L.ug_test_final_exp.argtypes = [C.c_int, vp, vp, vp]
     L.ug_verify_batch_kernel_ms.argtypes = [vp]; L.ug_verify_batch_kernel_ms.restype = None
     L.ug_test_verify_batch_trace.argtypes = [C.c_int, vp, vp]
     L.ug_test_miller.argtypes = [vp, vp, vp]

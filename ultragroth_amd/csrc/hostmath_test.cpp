@@ -245,4 +245,15 @@ int ugt_miller(uint32_t out[108], const uint8_t g1[64], const uint8_t g2[128]) {
     return 0;
 }
 
+// the final exponentiation's is-one test under the same assertions: f as 12 x 9 canonical limbs, g = the value after the hard
+// part in that form; returns the verdict (1 = f^((p^12 - 1)/r) is one)
+int ugt_final_exp(uint32_t g[108], const uint32_t f[108]) {
+    static const pr::FinalExpConsts kc = pr::final_exp_consts();
+    pr::F12 x, hard;
+    pr::f12_load(x, f);
+    const bool one = pr::final_exp_is_one(kc, x, hard);
+    pr::f12_store(g, hard);
+    return one ? 1 : 0;
+}
+
 }  // extern "C"

@@ -5,12 +5,19 @@
 // f12_tree_kernel       one level of the binary tree over the f_i: node j = node 2j * node 2j+1 of the level below, an odd last
 // g1_tree_kernel        node copied up; the G1 twin adds. One launch per level; every level stays in HBM, so that a rejected
 //                       batch can be searched from the root without the device.
+// vkx_mul_kernel        the judge of a rejected pass, first step: lane (i, c) = column c of suspect i's vkX, scalar_ic * IC_c by the
+// vkx_sum_kernel        256-bit ladder; then one block per suspect adds its columns (lanes stride the columns, a tree over the 64
+//                       partial sums in LDS) and leaves -vkX_i as an affine G1 record.
+// judge_kernel          lane i: suspect i's own equation -- the Miller loops of its three (four) pairs times miller(beta, -alpha),
+//                       the final exponentiation's is-one test, one verdict word. No random scalar: the single verifier's answer.
+// final_exp_kernel      one lane of the final exponentiation alone (ug_test_final_exp).
 //
 // Registers: an Fq12 value is 108 words, a product holds three and a column sum. The coefficient loops of pairing.hpp are
 // kept as loops, so the values are indexed at run time and live in private (scratch) memory; the column products (81
 // multiply-adds for 18 words read) run from registers. Every kernel asks for one wave per SIMD -- the whole 512-entry
 // file -- so that nothing else is pushed out; tools/kernel_regs.py prints what the compiler made of it
 // (profiles/verify_batch.txt).
+#include <algorithm>
 #include "dev_common.hpp"
 #include "pairing_dev.hpp"
 
@@ -44,6 +51,51 @@ __global__ __launch_bounds__(64) void g1_tree_kernel(const u32* __restrict__ src
     const size_t j = t / k, s = t % k;
     g1_node(src + (2 * j * k + s) * XYZZ_WORDS, 2 * j + 1 < (size_t)n_src ? src + ((2 * j + 1) * k + s) * XYZZ_WORDS : nullptr,
             dst + (j * k + s) * XYZZ_WORDS);
+}
+
+__global__ __launch_bounds__(64) void vkx_mul_kernel(const u32* __restrict__ points, const u32* __restrict__ scalars, size_t lanes, int cols,
+                                                     u32* __restrict__ terms) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= lanes) return;
+    u32 kw[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) kw[j] = scalars[t * 8 + j];
+    vkx_term(points + (t % cols) * G1_WORDS, kw, terms + t * XYZZ_WORDS);
+}
+
+// one block per suspect (the grid is exactly the suspects: no lane leaves before the barriers)
+__global__ __launch_bounds__(64) void vkx_sum_kernel(const u32* __restrict__ terms, int cols, u32* __restrict__ neg_vkx) {
+    __shared__ u32 part[64 * XYZZ_WORDS];
+    const size_t i = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const u32* t = terms + i * cols * XYZZ_WORDS;
+    G1XYZZ acc = xyzz_inf<Fq>();
+    for (int c = lane; c < cols; c += 64) acc = xyzz_add(acc, xyzz_load(t + (size_t)c * XYZZ_WORDS));
+    xyzz_store(part + lane * XYZZ_WORDS, acc);
+    for (int half = 32; half >= 1; half >>= 1) {
+        __syncthreads();
+        if (lane < half) {
+            acc = xyzz_add(acc, xyzz_load(part + (lane + half) * XYZZ_WORDS));
+            xyzz_store(part + lane * XYZZ_WORDS, acc);
+        }
+    }
+    if (lane == 0) vkx_finish(acc, neg_vkx + i * G1_WORDS);
+}
+
+__global__ UG_ONE_WAVE void judge_kernel(FinalExpConsts kc, const u32* __restrict__ a, const u32* __restrict__ b, const u32* __restrict__ neg_vkx,
+                                         const u32* __restrict__ g, const u32* __restrict__ key_g2, const u32* __restrict__ f_ab, int n, int k,
+                                         u32* __restrict__ verdict) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    verdict[i] = judge_proof(kc, a + i * G1_WORDS, b + i * G2_WORDS, neg_vkx + i * G1_WORDS, g + i * k * G1_WORDS, k, key_g2, f_ab) ? 1u : 0u;
+}
+
+__global__ UG_ONE_WAVE void final_exp_kernel(FinalExpConsts kc, const u32* __restrict__ f_in, u32* __restrict__ g_out, u32* __restrict__ is_one) {
+    if (blockIdx.x || threadIdx.x) return;
+    F12 f, g;
+    f12_load(f, f_in);
+    is_one[0] = final_exp_is_one(kc, f, g) ? 1u : 0u;
+    f12_store(g_out, g);
 }
 
 struct DevBuf {
@@ -97,6 +149,55 @@ void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb)
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
     UG_HIP(hipEventElapsedTime(&ms[2], t2.e, t3.e));
     for (int i = 0; i < 3; i++) pb.kernel_ms[i] = ms[i];
+}
+
+// the vkx step keeps at most this many XYZZ products on the device at a time (144 bytes each)
+constexpr size_t VKX_CHUNK_TERMS = (size_t)1 << 20;
+
+void pairing_judge_device(int device, const FinalExpConsts& kc, PairingJudge& pj) {
+    if (pj.n <= 0 || pj.n > PAIRING_PASS || (pj.k != 1 && pj.k != 2) || pj.cols <= 0) throw std::invalid_argument("pairing_judge_device: bad shape");
+    UG_HIP(hipSetDevice(device));
+    const size_t n = (size_t)pj.n, k = (size_t)pj.k, cols = (size_t)pj.cols;
+    const size_t chunk = std::min(n, std::max<size_t>(1, VKX_CHUNK_TERMS / cols));           // suspects per launch of the vkx step
+    DevBuf a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), points(cols * G1_WORDS), key((1 + k) * G2_WORDS), fab(F12_WORDS);
+    DevBuf scalars(chunk * cols * 8), terms(chunk * cols * XYZZ_WORDS), nvkx(n * G1_WORDS), verdict(n);
+    Event t0, t1, t2;
+    UG_HIP(hipMemcpy(a.p, pj.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(b.p, pj.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(g.p, pj.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(points.p, pj.points, cols * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(key.p, pj.key_g2, (1 + k) * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(fab.p, pj.f_alpha_beta, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipEventRecord(t0.e, nullptr));
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t m = std::min(chunk, n - first);
+        UG_HIP(hipMemcpy(scalars.p, pj.scalars + first * cols * 8, m * cols * 8 * sizeof(u32), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(vkx_mul_kernel, dim3(blocks(m * cols)), dim3(64), 0, nullptr, points.p, scalars.p, m * cols, pj.cols, terms.p);
+        UG_KERNEL_CHECK();
+        hipLaunchKernelGGL(vkx_sum_kernel, dim3((unsigned)m), dim3(64), 0, nullptr, terms.p, pj.cols, nvkx.p + first * G1_WORDS);
+        UG_KERNEL_CHECK();
+    }
+    UG_HIP(hipEventRecord(t1.e, nullptr));
+    hipLaunchKernelGGL(judge_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.p, b.p, nvkx.p, g.p, key.p, fab.p, pj.n, pj.k, verdict.p);
+    UG_KERNEL_CHECK();
+    UG_HIP(hipEventRecord(t2.e, nullptr));
+    UG_HIP(hipMemcpy(pj.verdict, verdict.p, n * sizeof(u32), hipMemcpyDeviceToHost));
+    float ms[2] = {0, 0};
+    UG_HIP(hipEventElapsedTime(&ms[0], t0.e, t1.e));
+    UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
+    for (int i = 0; i < 2; i++) pj.kernel_ms[i] = ms[i];
+}
+
+void final_exp_device(int device, const FinalExpConsts& kc, const u32* f, u32* g, int* is_one) {
+    UG_HIP(hipSetDevice(device));
+    DevBuf in(F12_WORDS), out(F12_WORDS), flag(1);
+    UG_HIP(hipMemcpy(in.p, f, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(final_exp_kernel, dim3(1), dim3(64), 0, nullptr, kc, in.p, out.p, flag.p);
+    UG_KERNEL_CHECK();
+    u32 one = 0;
+    UG_HIP(hipMemcpy(g, out.p, F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(&one, flag.p, sizeof(u32), hipMemcpyDeviceToHost));
+    *is_one = (int)one;
 }
 
 }  // namespace ug

@@ -7,7 +7,9 @@
 // on where it was computed: the device's f equals the host's limb for limb.
 //
 // The small constants the formulas need (3, 9, 18, 82 and the Frobenius coefficients of the twist) travel in a
-// PairingConsts: a kernel argument on the device, part of consts() on the host.
+// PairingConsts: a kernel argument on the device, part of consts() on the host. The second half of a pairing -- the final
+// exponentiation's is-one test -- adds the twelve gamma^k and the hard exponent: a FinalExpConsts, which the kernels that
+// decide an equation take in its place.
 #pragma once
 #include "ec.hpp"
 
@@ -54,6 +56,13 @@ struct PairingConsts {
     F1 g22, g23;           // xi^((p^2-1)/3), xi^((p^2-1)/2) (both in Fq)
 };
 
+// (p^4 - p^2 + 1) / r, 761 bits, little-endian words
+constexpr int HARD_BITS = 761;
+struct FinalExpConsts : PairingConsts {
+    F1 gamma[12];          // gamma^k, gamma = 82^((p-1)/6): the p^2 Frobenius maps w^k to gamma^k w^k
+    u32 hard[24];
+};
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 // the constants on the host: a decimal literal -> value mod q
 inline F1 f1_from_digits(const char* s) {
@@ -71,6 +80,19 @@ inline PairingConsts pairing_consts() {
                f1_from_digits("3505843767911556378687030309984248845540243509899259641013678093033130930403")};
     k.g22 = f1_from_digits("21888242871839275220042445260109153167277707414472061641714758635765020556616");
     k.g23 = f1_from_digits("21888242871839275222246405745257275088696311157297823662689037894645226208582");
+    return k;
+}
+inline FinalExpConsts final_exp_consts() {
+    static const u32 HARD_EXPONENT[24] = {
+        0xccdf42b1u, 0xe81bb482u, 0xf49c36d4u, 0x5abf5cc4u, 0x1da014fdu, 0xf1154e7eu, 0x87cdbacfu, 0xdcc7b44cu,
+        0x954bcf8au, 0xaaa441e3u, 0xd5095f23u, 0x6b887d56u, 0xf3fd90c6u, 0x79581e16u, 0xd189227du, 0x3b1b1355u,
+        0x61876f6bu, 0x4e529a58u, 0xd5b12278u, 0x6c0eb522u, 0x83177fafu, 0x331ec151u, 0x0b0759adu, 0x01baaa71u};
+    FinalExpConsts k;
+    static_cast<PairingConsts&>(k) = pairing_consts();
+    const F1 g = f1_from_digits("21888242871839275220042445260109153167277707414472061641714758635765020556617");
+    k.gamma[0] = f1_one();
+    for (int i = 1; i < 12; i++) k.gamma[i] = k.gamma[i - 1] * g;
+    for (int i = 0; i < 24; i++) k.hard[i] = HARD_EXPONENT[i];
     return k;
 }
 #endif
@@ -204,6 +226,34 @@ UG_HD F12 miller(const PairingConsts& kc, const G2A& q, const G1A& pt) {
     return f;
 }
 
+// ---- final exponentiation: is f^((p^12 - 1)/r) one? --------------------------------------------------------------------
+// With G = (f^(p^2) f)^((p^4 - p^2 + 1)/r) the full power equals conj(G)/G (conj = the p^6 Frobenius, w -> -w), which is 1
+// exactly when G lies in Fq6, i.e. when its odd coefficients vanish: one 761-bit exponentiation, no Fq12 inversion.
+UG_HD bool is0(const F12& f) {
+    bool zero = true;
+    for (int i = 0; i < 12; i++) zero = zero && is0(f.c[i]);
+    return zero;
+}
+UG_HD F12 final_exp_hard(const FinalExpConsts& kc, const F12& f) {
+    F12 base;
+    for (int i = 0; i < 12; i++) base.c[i] = f.c[i] * kc.gamma[i];
+    base = f12_mul(kc, base, f);
+    F12 g = base;                                                   // bit HARD_BITS - 1, the leading one
+#pragma unroll 1
+    for (int i = HARD_BITS - 2; i >= 0; i--) {
+        g = f12_sqr(kc, g);
+        if ((kc.hard[i >> 5] >> (i & 31)) & 1) g = f12_mul(kc, g, base);
+    }
+    return g;
+}
+// g = G (zero for f = 0, which is not one)
+UG_HD bool final_exp_is_one(const FinalExpConsts& kc, const F12& f, F12& g) {
+    if (is0(f)) { g = f; return false; }
+    g = final_exp_hard(kc, f);
+    for (int i = 1; i < 12; i += 2) if (!is0(g.c[i])) return false;
+    return true;
+}
+
 // ---- batch verification (verifier_api.cpp, pairing.hip) ----------------------------------------------------------------
 // Records in memory: an Fq value is its 9 limbs; a G1 point 18 words (x, y; canonical; all zero = infinity), a G2 point 36
 // (x.a, x.b, y.a, y.b), an XYZZ sum 36 (x, y, zz, zzz as ec.hpp leaves them), an Fq12 value 108.
@@ -242,6 +292,53 @@ UG_HD void batch_leaf(const PairingConsts& kc, const u32* a, const u32* b, const
     }
     f12_store(f_out, f);
 }
+
+// ---- one proof's own equation (the judge of a rejected pass) -----------------------------------------------------------
+UG_HD G1A g1_load(const u32* p, bool negate) {
+    if (words_all_zero(p, G1_WORDS)) return G1A{f1_zero(), f1_zero(), true};
+    const F1 y = f1_load(p + NL);
+    return G1A{f1_load(p), negate ? -y : y, false};
+}
+UG_HD G2A g2_load(const u32* p) {
+    if (words_all_zero(p, G2_WORDS)) return g2_inf();
+    return G2A{F2{f1_load(p), f1_load(p + NL)}, F2{f1_load(p + 2 * NL), f1_load(p + 3 * NL)}, false};
+}
+// the rule of pairingCheck (src/groth16.cpp:679-681): a pair with a point at infinity is skipped
+UG_HD bool pair_live(const G1A& p, const G2A& q) { return !p.inf && !q.inf; }
+
+// column c of vkX: scalar * point as an XYZZ record; the scalar is a plain 256-bit integer, used as the single verifier's
+// inputs_combination uses it (all 256 bits, no reduction beyond the parser's)
+UG_HD void vkx_term(const u32* point, const u32* scalar, u32* out) {
+    G1XYZZ acc = xyzz_inf<Fq>();
+    if (!words_all_zero(point, G1_WORDS))
+        acc = xyzz_mul_scalar(xyzz_from_affine(fp_from<FqParams>(point), fp_from<FqParams>(point + NL)), scalar, 256);
+    xyzz_store(out, acc);
+}
+// -sum as an affine G1 record
+UG_HD void vkx_finish(const G1XYZZ& sum, u32* out) {
+    if (is_inf(sum)) { for (int i = 0; i < G1_WORDS; i++) out[i] = 0; return; }
+    Fq x, y;
+    xyzz_to_affine(x, y, sum);
+    fq_store(out, x);
+    fq_store(out + NL, (-F1{y}).v);
+}
+// e(A, B) e(-alpha, beta) e(-vkX, gamma) e(-G_s, delta_s) == 1 for one proof: a, b, its k points g as parsed, neg_vkx from
+// vkx_finish, key_g2 = gamma, delta_0 [, delta_1], f_ab = miller(beta, -alpha) (one when that pair is skipped)
+UG_HD bool judge_proof(const FinalExpConsts& kc, const u32* a, const u32* b, const u32* neg_vkx, const u32* g, int k, const u32* key_g2,
+                       const u32* f_ab) {
+    F12 acc;
+    f12_load(acc, f_ab);
+#pragma unroll 1
+    for (int s = 0; s < k + 2; s++) {
+        const G1A p = g1_load(s == 0 ? a : s == 1 ? neg_vkx : g + (s - 2) * G1_WORDS, s >= 2);
+        const G2A q = g2_load(s == 0 ? b : key_g2 + (s - 1) * G2_WORDS);
+        if (!pair_live(p, q)) continue;
+        acc = f12_mul(kc, acc, miller(kc, q, p));
+    }
+    F12 hard;
+    return final_exp_is_one(kc, acc, hard);
+}
+
 // a node of the product tree: the product of its two children, or the left one alone (right == nullptr: an odd last node)
 UG_HD void f12_node(const PairingConsts& kc, const u32* left, const u32* right, u32* out) {
     F12 x;

@@ -21,4 +21,24 @@ constexpr int PAIRING_PASS = 1 << 16;
 // Runs the kernels of pairing.hip on `device` and brings both trees back. Throws on a device error.
 void pairing_batch_device(int device, const pr::PairingConsts& kc, PairingBatch& pb);
 
+// The suspects of a rejected pass, each judged by its own equation (pairing.hpp: judge_proof), one lane per suspect.
+struct PairingJudge {
+    int n = 0;                  // suspects of this launch, at most PAIRING_PASS
+    int k = 1;                  // G1 points per proof besides A, as in PairingBatch
+    int cols = 0;               // columns of vkX: IC_0, IC_1 .. IC_nPublic [, IC_rand]
+    const u32* a = nullptr;     // n x G1_WORDS
+    const u32* b = nullptr;     // n x G2_WORDS
+    const u32* g = nullptr;     // n x k x G1_WORDS
+    const u32* scalars = nullptr;   // n x cols x 8: plain 256-bit integers; column 0 is 1, then the signals [, the challenge]
+    const u32* points = nullptr;    // cols x G1_WORDS: the key's points of the columns
+    const u32* key_g2 = nullptr;    // (1 + k) x G2_WORDS: gamma, then the delta of each of the k points
+    const u32* f_alpha_beta = nullptr;   // F12_WORDS: miller(beta, -alpha), computed once per call on the host
+    u32* verdict = nullptr;     // out: n words, 1 = the equation holds
+    double kernel_ms[2] = {0, 0};   // out: the vkx step (both kernels), judge_kernel
+};
+void pairing_judge_device(int device, const pr::FinalExpConsts& consts, PairingJudge& pj);
+
+// One lane of the device's final exponentiation (test hook): g = the value after the hard part, is_one = the verdict.
+void final_exp_device(int device, const pr::FinalExpConsts& consts, const u32* f, u32* g, int* is_one);
+
 }  // namespace ug

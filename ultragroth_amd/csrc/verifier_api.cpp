@@ -14,7 +14,8 @@
 // G2 steps, the two Frobenius lines at the end. The result is a yes/no, so any correct pairing gives the reference's
 // answer. Final exponentiation: with G = (f^(p^2) f)^((p^4 - p^2 + 1)/r) the full power f^((p^12-1)/r) equals
 // conj(G)/G (conj = the p^6 Frobenius, w -> -w), which is 1 exactly when G lies in Fq6, i.e. when its odd coefficients
-// vanish: one 761-bit exponentiation, no Fq12 inversion.
+// vanish: one 761-bit exponentiation, no Fq12 inversion. Like the Miller loop it lives in pairing.hpp, compiled for the
+// host here and for the device in pairing.hip.
 #include <sys/random.h>
 #include <algorithm>
 #include <atomic>
@@ -63,49 +64,18 @@ bool g2_on_curve(const G2A& q) {
     return q.y * q.y == q.x * q.x * q.x + b;
 }
 
-struct Consts : PairingConsts {
-    F1 gamma[12];          // gamma^k, gamma = 82^((p-1)/6): the p^2 Frobenius maps w^k to gamma^k w^k
-    Consts() : PairingConsts(pairing_consts()) {
-        F1 g = f1_from_decimal("21888242871839275220042445260109153167277707414472061641714758635765020556617");
-        gamma[0] = f1_one();
-        for (int k = 1; k < 12; k++) gamma[k] = gamma[k - 1] * g;
-    }
-};
-const Consts& consts() { static const Consts c; return c; }
-
-// (p^4 - p^2 + 1) / r, 761 bits, little-endian words
-const u32 HARD_EXPONENT[24] = {
-    0xccdf42b1u, 0xe81bb482u, 0xf49c36d4u, 0x5abf5cc4u, 0x1da014fdu, 0xf1154e7eu, 0x87cdbacfu, 0xdcc7b44cu,
-    0x954bcf8au, 0xaaa441e3u, 0xd5095f23u, 0x6b887d56u, 0xf3fd90c6u, 0x79581e16u, 0xd189227du, 0x3b1b1355u,
-    0x61876f6bu, 0x4e529a58u, 0xd5b12278u, 0x6c0eb522u, 0x83177fafu, 0x331ec151u, 0x0b0759adu, 0x01baaa71u};
-
-// f^((p^12 - 1)/r) == 1 ?  (see the header comment)
+// the constants of the Miller loop and of the final exponentiation's is-one test (pairing.hpp, shared with the device)
+const FinalExpConsts& consts() { static const FinalExpConsts c = final_exp_consts(); return c; }
 bool final_exponentiation_is_one(const F12& f) {
-    bool zero = true;
-    for (const auto& x : f.c) zero = zero && is0(x);
-    if (zero) return false;
-    const Consts& k = consts();
-    F12 fp2;
-    for (int i = 0; i < 12; i++) fp2.c[i] = f.c[i] * k.gamma[i];
-    const F12 base = f12_mul(k, fp2, f);
-    F12 g = f12_one();
-    bool started = false;
-    for (int i = 760; i >= 0; i--) {
-        if (started) g = f12_sqr(k, g);
-        if ((HARD_EXPONENT[i >> 5] >> (i & 31)) & 1) {
-            g = started ? f12_mul(k, g, base) : base;
-            started = true;
-        }
-    }
-    for (int i = 1; i < 12; i += 2) if (!is0(g.c[i])) return false;
-    return true;
+    F12 hard;
+    return final_exp_is_one(consts(), f, hard);
 }
 
 // the four / five Miller loops are independent: one host thread each
 bool pairing_check(const std::vector<G1A>& a, const std::vector<G2A>& b) {
     std::vector<std::future<F12>> parts;
     for (size_t i = 0; i < a.size(); i++) {
-        if (a[i].inf || b[i].inf) continue;                         // src/groth16.cpp:679-681
+        if (!pair_live(a[i], b[i])) continue;                       // src/groth16.cpp:679-681
         parts.push_back(std::async(std::launch::async, [&, i] { return miller(consts(), b[i], a[i]); }));
     }
     F12 acc = f12_one();
@@ -449,9 +419,32 @@ int ultra_groth_verify(const char* proof, const char* inputs, const char* verifi
 // which go to the single-proof verifier. Proofs whose B is outside the order-r subgroup never enter the batch (the pairing
 // is not bilinear in the scalar there); the single verifier judges them, as it does every proof when the key itself has a
 // point off its curve or a G2 point outside the subgroup.
+//
+// The judge (ug_verify_batch_options.judge, ULTRAGROTH_VERIFY_JUDGE=1; off by default). The search above costs the host two
+// batch checks per level and bad proof and a single verification per proof of a failing leaf node, so the sender of the proofs
+// decides what a call costs. With the judge on, a rejected pass is searched breadth first only while its failing nodes number
+// at most search_width; every proof under a failing node is then a suspect, as are the proofs whose B is outside the subgroup,
+// and when the call has at least judge_min suspects they are decided by their own equations -- judge_proof of pairing.hpp, the
+// single verifier's arithmetic -- one lane each in launches of up to 65536 (pairing.hip; host threads for device < 0).
 namespace {
 
 constexpr size_t LEAF = 16;
+// The library's defaults, from the sweep of profiles/verify_judge.txt. A launch of the judge takes ~170 ms whether it holds 16 or
+// 16384 suspects (one lane's latency), what the single verifier needs for ~256 proofs on 16 threads: below that the host is
+// quicker. Every level the search opens costs up to 2 * width checks of ~7 ms before the same launch; width 2 is the smallest
+// of the sweep that still follows ONE bad proof to its leaf, where judge on and off do the same work.
+constexpr int DEFAULT_SEARCH_WIDTH = 2, DEFAULT_JUDGE_MIN = 256;
+
+struct BatchOptions { bool judge = false; int search_width = DEFAULT_SEARCH_WIDTH, judge_min = DEFAULT_JUDGE_MIN; };
+
+// ULTRAGROTH_VERIFY_JUDGE: unset, empty or 0 = off, 1 = on; anything else fails the call (a mistyped setting must not leave the
+// judge off without a word, as ULTRAGROTH_VALIDATE)
+bool judge_from_environment() {
+    const char* e = getenv("ULTRAGROTH_VERIFY_JUDGE");
+    if (!e || !e[0]) return false;
+    if (e[1] || (e[0] != '0' && e[0] != '1')) throw std::invalid_argument(std::string("ULTRAGROTH_VERIFY_JUDGE must be 0 or 1, not \"") + e + "\"");
+    return e[0] == '1';
+}
 
 template <class Fn> void parallel_for(size_t n, const Fn& fn) {
     const size_t threads = std::min<size_t>(n, std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency())));
@@ -554,6 +547,28 @@ struct Pass {
         for (size_t c = 2 * j; c <= 2 * j + 1; c++)
             if (!node_ok(level - 1, c)) walk(level - 1, c, suspects);
     }
+    // Node j of `level` failed, judge on: breadth first while the failing nodes still cover more than LEAF proofs each and
+    // number at most `width`. Every proof under a failing node is a suspect.
+    void search(size_t level, size_t j, size_t width, std::vector<size_t>& suspects) {
+        std::vector<size_t> failing{j};                            // all on `level`
+        auto whole = [&](size_t node) { for (size_t i = node << level, hi = std::min(m, (node + 1) << level); i < hi; i++) suspects.push_back(i); };
+        for (;;) {
+            std::vector<size_t> open;                              // (only the last node of a level can be smaller than the others)
+            for (size_t node : failing) {
+                if (level == 0 || std::min(m, (node + 1) << level) - (node << level) <= LEAF) whole(node);
+                else open.push_back(node);
+            }
+            if (open.size() > width) { for (size_t node : open) whole(node); return; }
+            if (open.empty()) return;
+            failing.clear();
+            for (size_t node : open) {
+                if (2 * node + 1 >= level_size[level - 1]) { failing.push_back(2 * node); continue; }      // copied up: the same value
+                for (size_t c = 2 * node; c <= 2 * node + 1; c++)
+                    if (!node_ok(level - 1, c)) failing.push_back(c);
+            }
+            level--;
+        }
+    }
     void host_trees(const u32* a, const u32* b, const u32* g, const u32* r) {
         const PairingConsts& kc = consts();
         parallel_for(m, [&](size_t i) {
@@ -585,13 +600,67 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// The suspects of a call, each decided by judge_proof: on `device` in launches of at most PAIRING_PASS, on host threads for
+// device < 0. valid[s] answers suspect s.
+void judge_suspects(const BatchKey& key, int device, const std::vector<const BatchProof*>& sus, std::vector<char>& valid,
+                    ug_verify_batch_stats_ex& stats) {
+    const size_t n = sus.size(), k = (size_t)key.k(), cols = key.ic.size() + (key.ultra ? 1 : 0);
+    std::vector<u32> points(cols * G1_WORDS), key_g2((1 + k) * G2_WORDS), f_ab(F12_WORDS);
+    for (size_t c = 0; c < key.ic.size(); c++) g1_words(&points[c * G1_WORDS], key.ic[c]);
+    if (key.ultra) g1_words(&points[(cols - 1) * G1_WORDS], key.ic_rand);
+    g2_words(&key_g2[0], key.gamma);
+    for (size_t s = 0; s < k; s++) g2_words(&key_g2[(1 + s) * G2_WORDS], key.delta[s]);
+    const G1A nalpha = g1_neg(key.alpha);
+    f12_store(f_ab.data(), pair_live(nalpha, key.beta) ? miller(consts(), key.beta, nalpha) : f12_one());
+    valid.assign(n, 0);
+    for (size_t first = 0; first < n; first += PAIRING_PASS) {
+        const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
+        std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS), scalars(m * cols * 8, 0), verdict(m, 0);
+        parallel_for(m, [&](size_t i) {
+            const BatchProof& p = *sus[first + i];
+            g1_words(&a[i * G1_WORDS], p.a);
+            g2_words(&b[i * G2_WORDS], p.b);
+            for (size_t s = 0; s < k; s++) g1_words(&g[(i * k + s) * G1_WORDS], p.g[s]);
+            u32* sc = &scalars[i * cols * 8];
+            sc[0] = 1;                                              // IC_0 itself
+            for (size_t c = 0; c < p.in.plain.size(); c++) memcpy(sc + (1 + c) * 8, p.in.plain[c].data(), 8 * sizeof(u32));
+            if (key.ultra) memcpy(sc + (cols - 1) * 8, p.challenge, 8 * sizeof(u32));
+        });
+        if (device < 0) {
+            parallel_for(m, [&](size_t i) {
+                G1XYZZ sum = xyzz_inf<Fq>();
+                u32 term[XYZZ_WORDS], nvkx[G1_WORDS];
+                for (size_t c = 0; c < cols; c++) {
+                    vkx_term(&points[c * G1_WORDS], &scalars[(i * cols + c) * 8], term);
+                    sum = xyzz_add(sum, xyzz_load(term));
+                }
+                vkx_finish(sum, nvkx);
+                verdict[i] = judge_proof(consts(), &a[i * G1_WORDS], &b[i * G2_WORDS], nvkx, &g[i * k * G1_WORDS], (int)k, key_g2.data(), f_ab.data());
+            });
+        } else {
+            const auto t0 = std::chrono::steady_clock::now();
+            PairingJudge pj;
+            pj.n = (int)m; pj.k = (int)k; pj.cols = (int)cols; pj.a = a.data(); pj.b = b.data(); pj.g = g.data(); pj.scalars = scalars.data();
+            pj.points = points.data(); pj.key_g2 = key_g2.data(); pj.f_alpha_beta = f_ab.data(); pj.verdict = verdict.data();
+            pairing_judge_device(device, consts(), pj);
+            const double ms = ms_since(t0);
+            stats.base.device_ms += ms;
+            stats.judge_ms += ms;
+            stats.judge_launches++;
+        }
+        for (size_t i = 0; i < m; i++) valid[first + i] = verdict[i] != 0;
+    }
+    stats.judged += n;
+}
+
 int verify_batch(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
-                 int* verdicts, ug_verify_batch_stats* stats_out, char* error_msg, unsigned long error_msg_maxsize) {
+                 int* verdicts, const BatchOptions& opt, ug_verify_batch_stats_ex* stats_out, char* error_msg, unsigned long error_msg_maxsize) {
     try {
         const auto t_start = std::chrono::steady_clock::now();
         if (count < 0 || !verification_key || (count > 0 && (!proofs || !inputs || !verdicts))) throw std::invalid_argument("null argument");
         auto single = ultra ? ultra_groth_verify : groth16_verify;
-        ug_verify_batch_stats stats = {0, 0, 0, 0.0, 0.0};
+        ug_verify_batch_stats_ex stats_ex = {{0, 0, 0, 0.0, 0.0}, 0, 0, 0.0};
+        ug_verify_batch_stats& stats = stats_ex.base;
         BatchKey key;
         key.ultra = ultra;
         if (ultra) {
@@ -702,14 +771,26 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
             }
             const size_t top = pass.level_size.size() - 1;
             std::vector<size_t> suspects;
-            if (!pass.node_ok(top, 0)) pass.walk(top, 0, suspects);
+            if (!pass.node_ok(top, 0)) {
+                if (opt.judge) pass.search(top, 0, (size_t)opt.search_width, suspects);
+                else pass.walk(top, 0, suspects);
+            }
             for (size_t i = 0; i < m; i++) { verdict[idx[first + i]] = VERIFIER_VALID_PROOF; state[idx[first + i]] = DONE; }
             for (size_t s : suspects) state[idx[first + s]] = SINGLE;
             stats.batch_checks += pass.checks;
         }
-        // 4. whatever is left to the single verifier, on the host threads
+        // 4. whatever is left: to the judge when it is on and the suspects are many enough (never under a key the batch refused),
+        //    else to the single verifier on the host threads
         std::vector<size_t> singles;
         for (size_t i = 0; i < n; i++) if (state[i] == SINGLE) singles.push_back(i);
+        if (opt.judge && key_ok && !singles.empty() && singles.size() >= (size_t)opt.judge_min) {
+            std::vector<const BatchProof*> sus;
+            for (size_t i : singles) sus.push_back(&parsed[i]);
+            std::vector<char> valid;
+            judge_suspects(key, device, sus, valid, stats_ex);
+            for (size_t s = 0; s < singles.size(); s++) verdict[singles[s]] = valid[s] ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
+            singles.clear();
+        }
         parallel_for(singles.size(), [&](size_t s) {
             const size_t i = singles[s];
             char msg[256] = {0};
@@ -728,7 +809,7 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
             }
         }
         stats.host_ms = ms_since(t_start) - stats.device_ms;
-        if (stats_out) *stats_out = stats;
+        if (stats_out) *stats_out = stats_ex;
         return rc;
     } catch (std::exception& e) {
         copy_error(error_msg, error_msg_maxsize, e.what());
@@ -743,13 +824,51 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
 
 extern "C" {
 
+// the existing calls: options from the environment, the 40-byte stats
+static int verify_batch_env(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                            int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    BatchOptions opt;
+    try { opt.judge = judge_from_environment(); }
+    catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return VERIFIER_ERROR; }
+    ug_verify_batch_stats_ex ex;
+    const int rc = verify_batch(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats ? &ex : nullptr, error_msg, error_msg_maxsize);
+    if (stats && rc != VERIFIER_ERROR) *stats = ex.base;
+    return rc;
+}
+static int verify_batch_opt(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                            int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                            unsigned long error_msg_maxsize) {
+    BatchOptions opt;
+    try {
+        if (!options) opt.judge = judge_from_environment();
+        else {
+            if (options->size < sizeof(ug_verify_batch_options)) throw std::invalid_argument("ug_verify_batch_options: size is smaller than the struct");
+            if (options->judge != 0 && options->judge != 1) throw std::invalid_argument("ug_verify_batch_options: judge must be 0 or 1");
+            opt.judge = options->judge == 1;
+            if (options->search_width >= 0) opt.search_width = options->search_width;
+            if (options->judge_min >= 0) opt.judge_min = options->judge_min;
+        }
+    } catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return VERIFIER_ERROR; }
+    return verify_batch(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
+}
+
 int ug_groth16_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                             int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    return verify_batch(false, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+    return verify_batch_env(false, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
 }
 int ug_ultra_groth_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                                 int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    return verify_batch(true, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+    return verify_batch_env(true, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+}
+int ug_groth16_verify_batch_opt(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                                int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                                unsigned long error_msg_maxsize) {
+    return verify_batch_opt(false, device, count, proofs, inputs, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_ultra_groth_verify_batch_opt(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                                    int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                                    unsigned long error_msg_maxsize) {
+    return verify_batch_opt(true, device, count, proofs, inputs, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
 }
 
 void ug_verify_batch_kernel_ms(double ms[3]) {
@@ -778,6 +897,22 @@ int ug_test_miller(const unsigned char g1[64], const unsigned char g2[128], unsi
     const G2A q{F2{ld(16), ld(24)}, F2{ld(32), ld(40)}, false};
     f12_store(f, miller(consts(), q, pt));
     return 0;
+}
+
+// the final exponentiation of one value: g = the value after the hard part, *is_one = the verdict; device < 0: the host
+int ug_test_final_exp(int device, const unsigned int f[108], unsigned int g[108], int* is_one) {
+    if (!ughost::testHooksEnabled() || !f || !g || !is_one) return 1;
+    try {
+        if (device < 0) {
+            F12 x, hard;
+            f12_load(x, f);
+            *is_one = final_exp_is_one(consts(), x, hard) ? 1 : 0;
+            f12_store(g, hard);
+        } else {
+            final_exp_device(device, consts(), f, g, is_one);
+        }
+        return 0;
+    } catch (...) { return 1; }
 }
 
 }  // extern "C"
