@@ -211,6 +211,11 @@ typedef struct { uint64_t index; int reason; } ug_point_fault;
  * UG_OK when the check ran (out->reason = UG_POINT_OK: every point passed; else the LOWEST bad index and the first rule it
  * breaks); UG_ERROR only for bad arguments / device errors. Keeps nothing resident. */
 int  ug_points_check(ug_ctx* ctx, int g2, const void* host_points, uint64_t n, int level, ug_point_fault* out);
+/* The mask form: the same rules, order, record format and level, answered for EVERY record in one pass. reasons[i] (n bytes, host
+ * memory) is UG_POINT_OK or the first rule record i breaks; the lowest i with a non-zero reason, and that reason, are what
+ * ug_points_check reports for the same buffer. The records are staged in the same 64 MiB pieces, the status bytes downloaded
+ * per piece. Batch verification uses it to drop every pi_b outside the subgroup with one call. */
+int  ug_points_check_mask(ug_ctx* ctx, int g2, const void* host_points, uint64_t n, int level, uint8_t* reasons);
 /* As ug_ctx_defer_tables: after ug_ctx_check_points(ctx, level), every ug_bases_create_* / ug_bases_create_group_* on this
  * context checks its records at that level (0 = off, the default), each upload chunk behind its own DMA and before its
  * conversion. A bad point fails the creation with UG_ERROR, ug_last_error() = "point <global index>: <reason text>" (global

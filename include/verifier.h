@@ -94,8 +94,52 @@ int ug_ultra_groth_verify_batch_opt(int device, int count, const char *const *pr
                                     const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
                                     ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
 
+/* ---- packed proof records ------------------------------------------------------------------------------------------------
+ * Services that verify in bulk hold proofs as fixed-size binary records; these calls take them as they are. A coordinate is
+ * a plain (non-Montgomery) 256-bit little-endian integer of 32 bytes, in the order of proof.json:
+ *   Groth16     pi_a.x, pi_a.y, pi_b.x.c0, pi_b.x.c1, pi_b.y.c0, pi_b.y.c1, pi_c.x, pi_c.y            256 bytes
+ *   UltraGroth  pi_a (64) | pi_b (128) | pi_f (64) | pi_r (64)                                        320 bytes
+ * and the public inputs of all proofs are count x n_pub x 32 contiguous bytes in the same integer form. A record STANDS FOR
+ * the proof.json whose decimal strings are its integers (ug_proof_unpack writes that text), an input block for that
+ * public.json: coordinates are taken mod q and inputs mod r as the JSON parsers take them, and (0, 0) is infinity. Other
+ * byte orders (EVM calldata) are the caller's to convert.
+ * verdicts[i] is what groth16_verify / ultra_groth_verify returns for the unpacked texts of record i, up to the 2^-128 of the
+ * batch; a record cannot fail to parse, so it is VERIFIER_VALID_PROOF or VERIFIER_INVALID_PROOF. VERIFIER_ERROR, verdicts
+ * untouched: null arguments or count < 0 ("null argument"), n_pub <= 0 ("invalid inputs data"), a key that does not parse,
+ * n_pub + 1 != len(vk.IC) (the single call's length message), a device error. Options (NULL: the judge from the environment),
+ * result code, error_msg and stats are those of the _opt calls; a key the batch refuses sends every proof to the single
+ * verifier, as there.
+ * device >= 0: the raw records of a pass of up to 65536 cross PCIe once. records_ingest_kernel (pairing.hip) reduces every
+ * coordinate, sets the infinity flags, checks the curve equations and writes the arrays the Miller kernel reads; the
+ * subgroup ladder answers for every pi_b in one launch (ug_points_check_mask's kernel); records that leave the batch -- a
+ * point off its curve: INVALID; pi_b outside the subgroup: the single verifier or the judge -- are compacted away by a gather
+ * kernel, and the Miller and tree kernels run on the resident arrays. The host draws the scalars, reduces the inputs and
+ * keeps their prefix sums, derives the UltraGroth challenge from pi_r, makes the root check and the search; suspects are
+ * rebuilt from their raw records. device < 0: the same protocol on host threads. */
+int ug_groth16_verify_batch_records(int device, int count, const void *records, const void *inputs, int n_pub,
+                                    const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
+                                    ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+int ug_ultra_groth_verify_batch_records(int device, int count, const void *records, const void *inputs, int n_pub,
+                                        const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
+                                        ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+/* proof.json -> record (256 / 320 bytes). 0 = ok; 1 = the text does not parse as a proof of that protocol, or a value is >= 2^256 */
+int ug_proof_pack(int ultra, const char *proof_json, void *record);
+/* public.json -> n_pub x 32 bytes. 0 = ok; 1 = parse error, a value >= 2^256 or another count than n_pub */
+int ug_inputs_pack(const char *inputs_json, void *out, int n_pub);
+/* the text a record / an input block stands for, NUL-terminated. 0 = ok; 1 = maxsize is too small (1100 bytes hold any Groth16
+ * record, 1400 any UltraGroth record, 81 * n_pub + 3 any input block) or a null argument */
+int ug_proof_unpack(int ultra, const void *record, char *json, unsigned long maxsize);
+int ug_inputs_unpack(const void *in, int n_pub, char *json, unsigned long maxsize);
+
 /* milliseconds of the last device pass of this process: miller_batch_kernel, the Fq12 tree, the G1 tree */
 void ug_verify_batch_kernel_ms(double ms[3]);
+/* where the wall time of the last batch call of this process went, in milliseconds:
+ *   [0] the key   [1] step 1: parsing the texts, the curve checks (records on a device: the inputs and the challenge only)
+ *   [2] step 2: the pi_b as records and the subgroup check (records on a device: upload, ingest kernel, ladder, status bytes)
+ *   [3] the scalars, the inputs times the scalars, the prefix sums   [4] packing the word arrays (none for resident records)
+ *   [5] the pass: uploads, the three kernels (ug_verify_batch_kernel_ms), the trees' download
+ *   [6] the root check and the search   [7] the judge and the single verifier */
+void ug_verify_batch_phase_ms(double ms[8]);
 
 /* Test hooks, live only in a process started with ULTRAGROTH_TEST_HOOKS=1 (else they return 1 and write nothing).
  * ug_test_verify_batch_trace: for proof `index` of the last batch call, if it was batched, its scalar r (128 bits) and
@@ -106,6 +150,9 @@ void ug_verify_batch_kernel_ms(double ms[3]);
 int ug_test_verify_batch_trace(int index, unsigned int scalar[4], unsigned int f[108]);
 int ug_test_miller(const unsigned char g1[64], const unsigned char g2[128], unsigned int f[108]);
 int ug_test_final_exp(int device, const unsigned int f[108], unsigned int g[108], int *is_one);
+/* the passes of the last records call on a device: [0] those that used the resident arrays in place, [1] those that compacted
+ * them through the gather kernel first */
+int ug_test_verify_records_passes(unsigned long long passes[2]);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,8 @@ library's); --judge both runs every batch that holds bad proofs with the judge o
 two are compared within one session (profiles/verify_judge.txt). With --judge the batches "50 % bad" and "every pi_b off the
 subgroup" are added at 2^14 and "1 % bad" at 2^16. --sweep W1,W2,..:M1,M2,.. repeats "one bad" and "1 % bad" at 2^14 for every
 search_width W and judge_min M.
+
+--records compares the JSON call with ug_groth16_verify_batch_records on the same valid batches (profiles/verify_records.txt).
 """
 import argparse
 import ctypes as C
@@ -33,6 +35,58 @@ def read(name, mode="rb"):
         return f.read()
 
 
+PHASES = ("key", "parse+curve", "subgroup", "scalars+prefix", "packing", "pass", "root+search", "judge+single")
+
+
+def records_report(a, L, vk, pool, run, say):
+    """--records: the same valid batches through ug_groth16_verify_batch (texts) and ug_groth16_verify_batch_records (the same proofs
+    packed ONCE, outside the timed call), --runs runs of each in turn; then the host split of both calls at the largest size, and the
+    batch whose every pi_b is off the subgroup through the JSON call, judge off and on."""
+    from ultragroth_amd._lib import VerifyBatchStatsEx
+    import ultragroth_amd as ug
+    n_pub = len(json.loads(pool[0][1]))
+    packed = [(ug.proof_pack(pr), ug.inputs_pack(pub, n_pub)) for pr, pub in pool]
+
+    def phases():
+        ms = (C.c_double * 8)()
+        L.ug_verify_batch_phase_ms(ms)
+        return "  ".join("%s %.1f" % (name, v) for name, v in zip(PHASES, ms))
+
+    def run_records(n):
+        recs = b"".join(packed[i % len(packed)][0] for i in range(n))
+        ins = b"".join(packed[i % len(packed)][1] for i in range(n))
+        verdicts, err, ex = (C.c_int * n)(), C.create_string_buffer(256), VerifyBatchStatsEx()
+        t0 = time.perf_counter()
+        rc = L.ug_groth16_verify_batch_records(a.device, n, recs, ins, n_pub, vk, verdicts, None, C.byref(ex), err, 255)
+        dt = time.perf_counter() - t0
+        if rc != 0 or any(verdicts):
+            raise RuntimeError("verify_batch_records: rc %d, %s" % (rc, err.value.decode()))
+        ms = (C.c_double * 3)()
+        L.ug_verify_batch_kernel_ms(ms)
+        return dt, ex.base, list(ms)
+
+    run_records(64)
+    sizes = [int(s) for s in a.sizes.split(",")]
+    for lg in sizes:
+        n = 1 << lg
+        for rep in range(a.runs):
+            for name, fn in (("json   ", lambda: run(n, a.device)), ("records", lambda: run_records(n))):
+                dt, st, ms = fn()
+                say("N=2^%d %s run %d  %9.0f proofs/s  wall %8.1f ms  device_ms %8.1f host_ms %8.1f  kernels: miller %.1f  f12 tree %.1f  g1 tree %.1f ms"
+                    % (lg, name, rep, n / dt, dt * 1e3, st.device_ms, st.host_ms, ms[0], ms[1], ms[2]))
+                if lg == max(sizes) and rep == a.runs - 1:
+                    say("N=2^%d %s split (ms): %s" % (lg, name, phases()))
+    if a.offsub_size:
+        n = 1 << a.offsub_size
+        for rep in range(a.runs):
+            for judge in (0, 1):
+                dt, st, _ = run(n, a.device, judge=judge, off_subgroup=True)
+                say("N=2^%d json, every pi_b off the subgroup, judge %s  wall %9.1f ms  device_ms %8.1f host_ms %9.1f  single_checks %d judged %d"
+                    % (a.offsub_size, "on " if judge else "off", dt * 1e3, st.device_ms, st.host_ms, st.single_checks, st.judged))
+                if rep == a.runs - 1:
+                    say("    split (ms): %s" % phases())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="10,14,16")
@@ -48,6 +102,9 @@ def main():
     ap.add_argument("--sweep", default=None, help="search widths : judge minima, e.g. 0,2,4,8,16:16,64,256")
     ap.add_argument("--skip-valid", action="store_true", help="only the batches with bad proofs")
     ap.add_argument("--batches", default="none,one,1pct,50pct,offsub", help="with --skip-valid: which of these batches run")
+    ap.add_argument("--records", action="store_true", help="the JSON call and the packed-records call side by side, --runs times each")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--offsub-size", type=int, default=12, help="--records: log2 size of the batch whose every pi_b is off the subgroup (0: skip)")
     a = ap.parse_args()
     import ultragroth_amd as ug
     from ultragroth_amd._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsEx
@@ -117,6 +174,13 @@ def main():
 
     say("# batch verification, Groth16, tests/golden/trapdoor/groth16 (%d distinct proofs repeated to fill N)" % len(pool))
     run(64, a.device)                                                  # warm-up: code objects, the context
+    if a.records:
+        records_report(a, L, vk, pool, run, say)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     host_sizes = {int(s) for s in a.host_sizes.split(",") if s}
     modes = {"0": [None], "1": [1], "both": [0, 1]}[a.judge]
 

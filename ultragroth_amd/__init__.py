@@ -196,6 +196,90 @@ def ultra_groth_verify_batch(proofs, inputs, verification_key, device=0, judge=N
     return _verify_batch("ug_ultra_groth_verify_batch", proofs, inputs, verification_key, device, judge, search_width, judge_min)
 
 
+# ---- packed proof records (include/verifier.h) ----
+def _enc_json(v):
+    import json
+    return v if isinstance(v, bytes) else (v if isinstance(v, str) else json.dumps(v)).encode()
+
+
+def proof_pack(proof, ultra=False):
+    """ug_proof_pack: proof.json (text or parsed) -> its 256-byte (UltraGroth: 320-byte) record. ValueError for a text that is no
+    proof of that protocol or holds a value >= 2^256."""
+    rec = C.create_string_buffer(320 if ultra else 256)
+    if load().ug_proof_pack(1 if ultra else 0, _enc_json(proof), rec) != 0:
+        raise ValueError("not a proof that a record can hold")
+    return rec.raw
+
+
+def proof_unpack(record, ultra=False):
+    """ug_proof_unpack: the proof.json text a record stands for"""
+    if len(record) != (320 if ultra else 256):
+        raise ValueError("a record is %d bytes" % (320 if ultra else 256))
+    out = C.create_string_buffer(1400)
+    if load().ug_proof_unpack(1 if ultra else 0, bytes(record), out, 1400) != 0:
+        raise ValueError("record does not unpack")
+    return out.value.decode()
+
+
+def inputs_pack(inputs, n_pub=None):
+    """ug_inputs_pack: public.json (text or list) -> n_pub x 32 bytes; n_pub None: as many as the list holds"""
+    import json
+    if n_pub is None:
+        n_pub = len(json.loads(inputs) if isinstance(inputs, (str, bytes)) else inputs)
+    out = C.create_string_buffer(max(1, 32 * n_pub))
+    if load().ug_inputs_pack(_enc_json(inputs), out, n_pub) != 0:
+        raise ValueError("not %d inputs below 2^256" % n_pub)
+    return out.raw[:32 * n_pub]
+
+
+def inputs_unpack(block, n_pub=None):
+    """ug_inputs_unpack: the public.json text of one proof's input block"""
+    if n_pub is None:
+        n_pub = len(block) // 32
+    if n_pub <= 0 or len(block) != 32 * n_pub:
+        raise ValueError("an input block is n_pub x 32 bytes")
+    out = C.create_string_buffer(81 * n_pub + 3)
+    if load().ug_inputs_unpack(bytes(block), n_pub, out, 81 * n_pub + 3) != 0:
+        raise ValueError("inputs do not unpack")
+    return out.value.decode()
+
+
+def _verify_batch_records(name, ultra, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min):
+    from ._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsEx
+    size = 320 if ultra else 256
+    records, inputs = bytes(records), bytes(inputs)
+    if len(records) % size:
+        raise ValueError("records: a multiple of %d bytes" % size)
+    n = len(records) // size
+    if n_pub > 0 and len(inputs) != n * n_pub * 32:
+        raise ValueError("inputs: count x n_pub x 32 bytes")
+    verdicts = (C.c_int * max(n, 1))(*([-1] * max(n, 1)))
+    err = C.create_string_buffer(512)
+    opt = None
+    if not (judge is None and search_width is None and judge_min is None):
+        dflt = lambda v: -1 if v is None else int(v)
+        opt = C.byref(VerifyBatchOptions(C.sizeof(VerifyBatchOptions), int(bool(judge)), dflt(search_width), dflt(judge_min)))
+    stats = VerifyBatchStatsEx()
+    rc = getattr(load(), name)(device, n, records or b"\0", inputs or b"\0", n_pub, _enc_json(verification_key), verdicts, opt, C.byref(stats), err, 511)
+    if rc == VERIFIER_ERROR:
+        raise VerifierError(err.value.decode(errors="replace"))
+    out = {f: getattr(stats.base, f) for f, _ in VerifyBatchStats._fields_}
+    out.update({f: getattr(stats, f) for f in ("judged", "judge_launches", "judge_ms")})
+    return list(verdicts[:n]), out
+
+
+def groth16_verify_batch_records(records, inputs, n_pub, verification_key, device=0, judge=None, search_width=None, judge_min=None):
+    """ug_groth16_verify_batch_records (include/verifier.h): as groth16_verify_batch for proofs held as packed records -- `records`
+    count x 256 bytes (proof_pack), `inputs` count x n_pub x 32 bytes (inputs_pack). On a device the raw records are uploaded once
+    and reduced, checked and converted there; device < 0 is the same protocol on host threads. Returns (verdicts, stats) with the
+    judge's counters always present; judge None takes it from the environment."""
+    return _verify_batch_records("ug_groth16_verify_batch_records", False, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min)
+
+
+def ultra_groth_verify_batch_records(records, inputs, n_pub, verification_key, device=0, judge=None, search_width=None, judge_min=None):
+    return _verify_batch_records("ug_ultra_groth_verify_batch_records", True, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min)
+
+
 class _ProverBase:
     _create = _prove = _destroy = _public_size_fn = None
     _proof_size = staticmethod(groth16_proof_size)
@@ -798,6 +882,12 @@ class Device:
         f = _PointFault()
         _check(self._L.ug_points_check(self._h, 1 if g2 else 0, points, n, level, C.byref(f)))
         return None if f.reason == UG_POINT_OK else (f.index, f.reason)
+
+    def points_check_mask(self, points, n, g2=False, level=1):
+        """ug_points_check_mask over n zkey-format records: n bytes, byte i = UG_POINT_OK or the first rule record i breaks"""
+        out = C.create_string_buffer(max(1, n))
+        _check(self._L.ug_points_check_mask(self._h, 1 if g2 else 0, points, n, level, out))
+        return out.raw[:n]
 
     def check_on_create(self, level):
         """ug_ctx_check_points: the sets created on this device from now on check their records (0: off)"""

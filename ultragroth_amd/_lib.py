@@ -32,12 +32,15 @@ INNER_SYMBOLS = [
     "ug_bases_precompute_strided", "ug_schedule_build_tables_strided", "ug_bases_tables_bytes_strided", "ug_bases_table_stride",
     "ug_plan_window_tables", "ug_schedule_build_vectors", "ug_dvec_gather_index_at", "ug_plan_proof_batch",
     "ug_plan_proof_batch_aux", "ug_fr_lookup_tables", "ug_dvec_apply_lookup_vectors", "ug_dvec_complete_lookup_vectors",
-    "ug_lookup_vectors_bytes", "ug_points_check", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
+    "ug_lookup_vectors_bytes", "ug_points_check", "ug_points_check_mask", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/verifier.h
                     "ug_groth16_verify_batch", "ug_ultra_groth_verify_batch", "ug_verify_batch_kernel_ms",
                     "ug_groth16_verify_batch_opt", "ug_ultra_groth_verify_batch_opt",
-                    "ug_test_verify_batch_trace", "ug_test_miller", "ug_test_final_exp"]
+                    "ug_test_verify_batch_trace", "ug_test_miller", "ug_test_final_exp",
+                    "ug_groth16_verify_batch_records", "ug_ultra_groth_verify_batch_records",
+                    "ug_proof_pack", "ug_inputs_pack", "ug_proof_unpack", "ug_inputs_unpack", "ug_test_verify_records_passes",
+                    "ug_verify_batch_phase_ms"]
 
 
 class VerifyBatchStats(C.Structure):
@@ -162,6 +165,7 @@ def load():
     L.ug_bases_precompute.argtypes = [vp, C.c_int]
     L.ug_ctx_mem_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.ug_points_check.argtypes = [vp, C.c_int, vp, u64, C.c_int, vp]
+    L.ug_points_check_mask.argtypes = [vp, C.c_int, vp, u64, C.c_int, vp]
     L.ug_ctx_check_points.argtypes = [vp, C.c_int]
     L.ug_ctx_last_point_fault.argtypes = [vp, vp, vp]
     L.ug_point_reason_text.argtypes = [C.c_int]; L.ug_point_reason_text.restype = C.c_char_p
@@ -226,6 +230,14 @@ def load():
         getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_char_p, vp, vp, C.c_char_p, C.c_ulong]
     for n in ("ug_groth16_verify_batch_opt", "ug_ultra_groth_verify_batch_opt"):
         getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+    for n in ("ug_groth16_verify_batch_records", "ug_ultra_groth_verify_batch_records"):
+        getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+    L.ug_proof_pack.argtypes = [C.c_int, C.c_char_p, vp]
+    L.ug_inputs_pack.argtypes = [C.c_char_p, vp, C.c_int]
+    L.ug_proof_unpack.argtypes = [C.c_int, vp, vp, C.c_ulong]
+    L.ug_inputs_unpack.argtypes = [vp, C.c_int, vp, C.c_ulong]
+    L.ug_test_verify_records_passes.argtypes = [vp]
+    L.ug_verify_batch_phase_ms.argtypes = [vp]; L.ug_verify_batch_phase_ms.restype = None
     L.ug_test_final_exp.argtypes = [C.c_int, vp, vp, vp]
     L.ug_verify_batch_kernel_ms.argtypes = [vp]; L.ug_verify_batch_kernel_ms.restype = None
     L.ug_test_verify_batch_trace.argtypes = [C.c_int, vp, vp]

@@ -17,6 +17,8 @@
 //
 // Result: one 64-bit word, all ones = clean; every bad lane does atomicMin(word, index << 2 | reason), so the lowest bad index
 // wins, and a lane reports the first rule its point breaks. A plain vector atomic: no early exit, no host read-back per launch.
+// The mask form (check_points_mask) runs the same rules and stores one status byte per record instead, clean records included, so
+// one pass answers for every point: batch verification drops every pi_b outside the subgroup after ONE call.
 #include "dev_common.hpp"
 #include "internal.hpp"
 #include "../../include/ultragroth_hip.h"
@@ -43,11 +45,25 @@ __device__ __forceinline__ bool raw_ge_q(const u32* w) {
 // raw zkey coordinate below q -> canonical device form
 __device__ __forceinline__ Fq coord(const u32* w) { return cond_sub_q(from_mont256<FqParams>(w)); }
 
-__device__ __forceinline__ void report(unsigned long long* fault, u64 index, int reason) {
-    atomicMin(fault, (unsigned long long)((index << 2) | (u64)reason));
-}
+// The two reporters. The kernels below hand every lane's verdict (0 = clean) to one of them; nothing else differs between the forms.
+// FaultWord: one 64-bit word for the whole call, the lowest bad index wins (ug_points_check, the creation switch).
+struct FaultWord {
+    unsigned long long* fault;
+    u64 index0;                       // the global index of the launch's first record
+    __device__ __forceinline__ void operator()(u64 i, int reason) const {
+        if (reason) atomicMin(fault, (unsigned long long)(((index0 + i) << 2) | (u64)reason));
+    }
+};
+// StatusBytes: one byte per record of the launch, clean ones included (ug_points_check_mask): a plain vector store per lane.
+struct StatusBytes {
+    uint8_t* status;
+    __device__ __forceinline__ void operator()(u64 i, int reason) const { status[i] = (uint8_t)reason; }
+};
 
-__global__ __launch_bounds__(256) void check_g1_kernel(const u32* __restrict__ pts, u64 n, u64 index0, CurveB k, unsigned long long* fault) {
+// The rules hand a lane's verdict to the reporter where it falls, so that the fault-word form compiles to what it was before the
+// mask form existed (a constant reason at every site: the clean ones vanish).
+template <class Report>
+__global__ __launch_bounds__(256) void check_g1_kernel(const u32* __restrict__ pts, u64 n, CurveB k, Report report) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u32 w[16];
@@ -55,18 +71,19 @@ __global__ __launch_bounds__(256) void check_g1_kernel(const u32* __restrict__ p
     u32 o = 0;
 #pragma unroll
     for (int j = 0; j < 16; j++) o |= w[j];
-    if (o == 0) return;                                        // infinity
-    if (raw_ge_q(w) || raw_ge_q(w + 8)) { report(fault, index0 + i, UG_POINT_UNREDUCED); return; }
+    if (o == 0) { report(i, UG_POINT_OK); return; }            // infinity
+    if (raw_ge_q(w) || raw_ge_q(w + 8)) { report(i, UG_POINT_UNREDUCED); return; }
     const Fq x = coord(w), y = coord(w + 8);
     const Fq rhs = add(mul(sqr(x), x), fp_from<FqParams>(k.g1));      // < 3q
-    if (!equal(sqr(y), rhs)) report(fault, index0 + i, UG_POINT_OFF_CURVE);
+    if (!equal(sqr(y), rhs)) report(i, UG_POINT_OFF_CURVE);
+    else report(i, UG_POINT_OK);
 }
 
 // LADDER = false: rules 1-2, a memory-bound pass. LADDER = true: rule 3 as well, ~355 Fq2 group operations per point: the register
 // picture of window_tables_kernel<G2Cfg> (an XYZZ point over Fq2 is 72 words, the formulas' temporaries as many again), so the
 // same block of 128 and no occupancy demand that would force spills on the ladder's inner loop (DESIGN.md has the figures).
-template <bool LADDER>
-__global__ __launch_bounds__(LADDER ? 128 : 256) void check_g2_kernel(const u32* __restrict__ pts, u64 n, u64 index0, CurveB k, unsigned long long* fault) {
+template <bool LADDER, class Report>
+__global__ __launch_bounds__(LADDER ? 128 : 256) void check_g2_kernel(const u32* __restrict__ pts, u64 n, CurveB k, Report report) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     u32 w[32];
@@ -75,8 +92,8 @@ __global__ __launch_bounds__(LADDER ? 128 : 256) void check_g2_kernel(const u32*
     u32 o = 0;
 #pragma unroll
     for (int j = 0; j < 32; j++) o |= w[j];
-    if (o == 0) return;                                        // infinity
-    if (raw_ge_q(w) || raw_ge_q(w + 8) || raw_ge_q(w + 16) || raw_ge_q(w + 24)) { report(fault, index0 + i, UG_POINT_UNREDUCED); return; }
+    if (o == 0) { report(i, UG_POINT_OK); return; }            // infinity
+    if (raw_ge_q(w) || raw_ge_q(w + 8) || raw_ge_q(w + 16) || raw_ge_q(w + 24)) { report(i, UG_POINT_UNREDUCED); return; }
     Fq2 x, y, b;
     x.a = coord(w); x.b = coord(w + 8); y.a = coord(w + 16); y.b = coord(w + 24);
     b.a = fp_from<FqParams>(k.g2a); b.b = fp_from<FqParams>(k.g2b);
@@ -84,7 +101,7 @@ __global__ __launch_bounds__(LADDER ? 128 : 256) void check_g2_kernel(const u32*
     u32 d = 0;
 #pragma unroll
     for (int j = 0; j < NL; j++) d |= (lhs.a.l[j] ^ rhs.a.l[j]) | (lhs.b.l[j] ^ rhs.b.l[j]);
-    if (d) { report(fault, index0 + i, UG_POINT_OFF_CURVE); return; }
+    if (d) { report(i, UG_POINT_OFF_CURVE); return; }
     if (LADDER) {
         XYZZ<Fq2> acc = xyzz_from_affine(x, y);                // the top bit of r
 #pragma unroll 1
@@ -92,8 +109,9 @@ __global__ __launch_bounds__(LADDER ? 128 : 256) void check_g2_kernel(const u32*
             acc = xyzz_dbl(acc);
             if ((k.r[bit >> 5] >> (bit & 31)) & 1) acc = xyzz_madd(acc, x, y);
         }
-        if (!is_inf(acc)) report(fault, index0 + i, UG_POINT_OFF_SUBGROUP);
+        if (!is_inf(acc)) { report(i, UG_POINT_OFF_SUBGROUP); return; }
     }
+    report(i, UG_POINT_OK);
 }
 
 const CurveB& curve_b() {
@@ -112,18 +130,25 @@ const CurveB& curve_b() {
     return k;
 }
 
-}  // namespace
-
-void check_points(bool g2, const u32* pts, u64 n, u64 index0, int level, unsigned long long* fault, hipStream_t stream) {
+template <class Report> void launch_checks(bool g2, const u32* pts, u64 n, int level, const Report& report, hipStream_t stream) {
     if (!n) return;
     const CurveB& k = curve_b();
     if (!g2)
-        hipLaunchKernelGGL(check_g1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, pts, n, index0, k, fault);
+        hipLaunchKernelGGL(check_g1_kernel<Report>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, pts, n, k, report);
     else if (level < 2)
-        hipLaunchKernelGGL(check_g2_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, pts, n, index0, k, fault);
+        hipLaunchKernelGGL((check_g2_kernel<false, Report>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, pts, n, k, report);
     else
-        hipLaunchKernelGGL(check_g2_kernel<true>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, stream, pts, n, index0, k, fault);
+        hipLaunchKernelGGL((check_g2_kernel<true, Report>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, stream, pts, n, k, report);
     UG_KERNEL_CHECK();
+}
+
+}  // namespace
+
+void check_points(bool g2, const u32* pts, u64 n, u64 index0, int level, unsigned long long* fault, hipStream_t stream) {
+    launch_checks(g2, pts, n, level, FaultWord{fault, index0}, stream);
+}
+void check_points_mask(bool g2, const u32* pts, u64 n, int level, uint8_t* status, hipStream_t stream) {
+    launch_checks(g2, pts, n, level, StatusBytes{status}, stream);
 }
 
 }  // namespace ug

@@ -300,6 +300,8 @@ void synth_points(bool g2, u32* out_dev, const u32* gen_record_host, u64 seed, u
 // n RAW zkey records on the device (before convert_points_*): every bad one does atomicMin(*fault, (index0 + i) << 2 | reason),
 // reason = the first of UG_POINT_UNREDUCED / _OFF_CURVE / _OFF_SUBGROUP (G2, level 2 only) it breaks. *fault starts as all ones.
 void check_points(bool g2, const u32* pts, u64 n, u64 index0, int level, unsigned long long* fault, hipStream_t stream);
+// The same rules, one answer per record: status[i] = UG_POINT_OK or the first rule record i of this launch breaks (device memory, n bytes).
+void check_points_mask(bool g2, const u32* pts, u64 n, int level, uint8_t* status, hipStream_t stream);
 
 // ---- hpoly.hip ----------------------------------------------------------------------------------------
 struct CoefMatrix {

@@ -11,6 +11,8 @@
 // judge_kernel          lane i: suspect i's own equation -- the Miller loops of its three (four) pairs times miller(beta, -alpha),
 //                       the final exponentiation's is-one test, one verdict word. No random scalar: the single verifier's answer.
 // final_exp_kernel      one lane of the final exponentiation alone (ug_test_final_exp).
+// records_ingest_kernel the packed records of ug_*_verify_batch_records -> the arrays above, one record per lane: reduction mod q,
+// gather_rows_kernel    infinity flags, curve equations, limb form; the gather compacts the arrays when records were dropped.
 //
 // Registers: an Fq12 value is 108 words, a product holds three and a column sum. The coefficient loops of pairing.hpp are
 // kept as loops, so the values are indexed at run time and live in private (scratch) memory; the column products (81
@@ -18,8 +20,11 @@
 // file -- so that nothing else is pushed out; tools/kernel_regs.py prints what the compiler made of it
 // (profiles/verify_batch.txt).
 #include <algorithm>
+#include <vector>
 #include "dev_common.hpp"
+#include "internal.hpp"
 #include "pairing_dev.hpp"
+#include "../../include/ultragroth_hip.h"
 
 namespace ug {
 
@@ -98,6 +103,64 @@ __global__ UG_ONE_WAVE void final_exp_kernel(FinalExpConsts kc, const u32* __res
     f12_store(g_out, g);
 }
 
+// The packed proof records of include/verifier.h (plain 256-bit integers, 32 bytes a coordinate: pi_a | pi_b | the k other G1
+// points), ONE RECORD PER LANE: a lane needs all of a point's coordinates for its curve equation, and the 8 (10) reductions of a
+// record are nothing beside the Miller loop that follows, so the coalesced coordinate-per-lane mapping and its exchange through LDS
+// were not worth having; a lane reads its record with 16-byte loads. Every coordinate is reduced mod q (from_normal takes any
+// 256-bit value) into the canonical limb form, (0, 0) is infinity as in the JSON parsers, and the lane writes
+//   a / b / g     the G1_WORDS / G2_WORDS arrays miller_batch_kernel reads, in record order (all zero = infinity),
+//   bz            pi_b once more as a zkey record (Montgomery radix 2^256), what the subgroup ladder of check.hip reads; infinity
+//                 for a record that failed here, so that the ladder passes over it,
+//   status        UG_POINT_OK, or UG_POINT_OFF_CURVE when any of its points is off its curve.
+struct IngestConsts { F1 b1; F2 b2; };     // the curves' constant terms: 3 and 3 / (9 + u)
+
+__device__ __forceinline__ F1 ingest_coord(const u32* p) {
+    u32 w[8];
+    load8(w, p);
+    return F1{canon(from_normal<FqParams>(w))};
+}
+__device__ __forceinline__ bool ingest_g1(const u32* rec, const IngestConsts& c, u32* out) {
+    const F1 x = ingest_coord(rec), y = ingest_coord(rec + 8);
+    if (is0(x) && is0(y)) {
+        for (int j = 0; j < G1_WORDS; j++) out[j] = 0;
+        return true;
+    }
+    fq_store(out, x.v); fq_store(out + NL, y.v);
+    return y * y == x * x * x + c.b1;
+}
+
+__global__ __launch_bounds__(64) void records_ingest_kernel(const u32* __restrict__ records, int n, int k, IngestConsts c, u32* __restrict__ a,
+                                                            u32* __restrict__ b, u32* __restrict__ g, u32* __restrict__ bz,
+                                                            uint8_t* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const u32* rec = records + i * (size_t)(48 + 16 * k);
+    bool ok = ingest_g1(rec, c, a + i * G1_WORDS);
+    for (int s = 0; s < k; s++) ok = ingest_g1(rec + 48 + 16 * s, c, g + (i * k + s) * G1_WORDS) && ok;
+    const F2 x{ingest_coord(rec + 16), ingest_coord(rec + 24)}, y{ingest_coord(rec + 32), ingest_coord(rec + 40)};
+    const bool inf = is0(x) && is0(y);
+    u32* bo = b + i * G2_WORDS;
+    if (inf) { for (int j = 0; j < G2_WORDS; j++) bo[j] = 0; }
+    else {
+        fq_store(bo, x.a.v); fq_store(bo + NL, x.b.v); fq_store(bo + 2 * NL, y.a.v); fq_store(bo + 3 * NL, y.b.v);
+        ok = (y * y == x * x * x + c.b2) && ok;
+    }
+    u32 z[32];
+    if (inf || !ok) { for (int j = 0; j < 32; j++) z[j] = 0; }
+    else { to_mont256(z, x.a.v); to_mont256(z + 8, x.b.v); to_mont256(z + 16, y.a.v); to_mont256(z + 24, y.b.v); }
+    for (int j = 0; j < 4; j++) store8(bz + i * 32 + j * 8, z + j * 8);
+    status[i] = ok ? (uint8_t)UG_POINT_OK : (uint8_t)UG_POINT_OFF_CURVE;
+}
+
+// records were dropped: row t of dst = row index[t] of src (rows of `words` words), so that the Miller kernel sees a dense array
+__global__ __launch_bounds__(256) void gather_rows_kernel(const u32* __restrict__ src, const u32* __restrict__ index, size_t m, int words,
+                                                          u32* __restrict__ dst) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m * (size_t)words) return;
+    const size_t row = t / (size_t)words, w = t - row * (size_t)words;
+    dst[t] = src[(size_t)index[row] * (size_t)words + w];
+}
+
 struct DevBuf {
     u32* p = nullptr;
     explicit DevBuf(size_t words) { UG_HIP(hipMalloc(&p, words * sizeof(u32))); }
@@ -114,18 +177,14 @@ unsigned blocks(size_t lanes) { return (unsigned)((lanes + 63) / 64); }
 
 }  // namespace
 
-void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb) {
-    if (pb.n <= 0 || pb.n > PAIRING_PASS || (pb.k != 1 && pb.k != 2)) throw std::invalid_argument("pairing_batch_device: bad shape");
-    UG_HIP(hipSetDevice(device));
-    const size_t n = (size_t)pb.n, k = (size_t)pb.k, nodes = tree_nodes(n);
-    DevBuf a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), r(n * 4), f(nodes * F12_WORDS), s(nodes * k * XYZZ_WORDS);
+// the kernels of a pass over arrays that are on the device already; both trees come back to the host
+static void run_pass(const PairingConsts& kc, const u32* a, const u32* b, const u32* g, const u32* r, int n_, int k_, u32* f_tree, u32* g_tree,
+                     double kernel_ms[3]) {
+    const size_t n = (size_t)n_, k = (size_t)k_, nodes = tree_nodes(n);
+    DevBuf f(nodes * F12_WORDS), s(nodes * k * XYZZ_WORDS);
     Event t0, t1, t2, t3;
-    UG_HIP(hipMemcpy(a.p, pb.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(b.p, pb.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(g.p, pb.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(r.p, pb.r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipEventRecord(t0.e, nullptr));
-    hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.p, b.p, g.p, r.p, pb.n, pb.k, f.p, s.p);
+    hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a, b, g, r, n_, k_, f.p, s.p);
     UG_KERNEL_CHECK();
     UG_HIP(hipEventRecord(t1.e, nullptr));
     size_t off = 0;
@@ -137,18 +196,83 @@ void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb)
     UG_HIP(hipEventRecord(t2.e, nullptr));
     off = 0;
     for (size_t m = n; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(g1_tree_kernel, dim3(blocks(((m + 1) / 2) * k)), dim3(64), 0, nullptr, s.p + off * k * XYZZ_WORDS, (int)m, pb.k, s.p + (off + m) * k * XYZZ_WORDS);
+        hipLaunchKernelGGL(g1_tree_kernel, dim3(blocks(((m + 1) / 2) * k)), dim3(64), 0, nullptr, s.p + off * k * XYZZ_WORDS, (int)m, k_, s.p + (off + m) * k * XYZZ_WORDS);
         UG_KERNEL_CHECK();
         off += m;
     }
     UG_HIP(hipEventRecord(t3.e, nullptr));
-    UG_HIP(hipMemcpy(pb.f_tree, f.p, nodes * F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
-    UG_HIP(hipMemcpy(pb.g_tree, s.p, nodes * k * XYZZ_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(f_tree, f.p, nodes * F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(g_tree, s.p, nodes * k * XYZZ_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
     float ms[3] = {0, 0, 0};
     UG_HIP(hipEventElapsedTime(&ms[0], t0.e, t1.e));
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
     UG_HIP(hipEventElapsedTime(&ms[2], t2.e, t3.e));
-    for (int i = 0; i < 3; i++) pb.kernel_ms[i] = ms[i];
+    for (int i = 0; i < 3; i++) kernel_ms[i] = ms[i];
+}
+
+void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb) {
+    if (pb.n <= 0 || pb.n > PAIRING_PASS || (pb.k != 1 && pb.k != 2)) throw std::invalid_argument("pairing_batch_device: bad shape");
+    UG_HIP(hipSetDevice(device));
+    const size_t n = (size_t)pb.n, k = (size_t)pb.k;
+    DevBuf a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), r(n * 4);
+    UG_HIP(hipMemcpy(a.p, pb.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(b.p, pb.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(g.p, pb.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(r.p, pb.r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
+    run_pass(kc, a.p, b.p, g.p, r.p, pb.n, pb.k, pb.f_tree, pb.g_tree, pb.kernel_ms);
+}
+
+// ---- the resident form: the pass's raw records cross PCIe once and its arrays never leave the device ---------------------
+struct ResidentBatch::Impl {
+    int device, n, k;
+    DevBuf records, a, b, g, bz, status;
+    Impl(int device_, int n_, int k_)
+        : device(device_), n(n_), k(k_), records((size_t)n_ * (48 + 16 * k_)), a((size_t)n_ * G1_WORDS), b((size_t)n_ * G2_WORDS),
+          g((size_t)n_ * k_ * G1_WORDS), bz((size_t)n_ * 32), status(((size_t)n_ + 3) / 4 * 2) {}      // status: n bytes from each check
+};
+ResidentBatch::ResidentBatch(int device, int n, int k) {
+    if (n <= 0 || n > PAIRING_PASS || (k != 1 && k != 2)) throw std::invalid_argument("ResidentBatch: bad shape");
+    UG_HIP(hipSetDevice(device));
+    impl = new Impl(device, n, k);
+}
+ResidentBatch::~ResidentBatch() { delete impl; }
+
+void ResidentBatch::ingest(const void* records, unsigned char* status) {
+    Impl& m = *impl;
+    UG_HIP(hipSetDevice(m.device));
+    static const IngestConsts c{f1_small(3), f2_scale(f2_inv(F2{f1_small(9), f1_small(1)}), f1_small(3))};
+    const size_t n = (size_t)m.n, room = (n + 3) / 4 * 4;
+    uint8_t* curve = reinterpret_cast<uint8_t*>(m.status.p);
+    uint8_t* subgroup = curve + room;
+    UG_HIP(hipMemcpy(m.records.p, records, n * (48 + 16 * (size_t)m.k) * sizeof(u32), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(records_ingest_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, c, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+    UG_KERNEL_CHECK();
+    check_points_mask(true, m.bz.p, n, 2, subgroup, nullptr);      // (a record that failed above is infinity here: it passes)
+    std::vector<uint8_t> both(2 * room);
+    UG_HIP(hipMemcpy(both.data(), curve, 2 * room, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) status[i] = both[i] ? both[i] : both[room + i];
+}
+
+void ResidentBatch::run(const PairingConsts& kc, const u32* keep, int kept, const u32* r, u32* f_tree, u32* g_tree, double kernel_ms[3]) {
+    Impl& m = *impl;
+    if (kept <= 0 || kept > m.n || (!keep && kept != m.n)) throw std::invalid_argument("ResidentBatch: bad shape");
+    UG_HIP(hipSetDevice(m.device));
+    const size_t n = (size_t)kept, k = (size_t)m.k;
+    DevBuf rd(n * 4);
+    UG_HIP(hipMemcpy(rd.p, r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
+    if (!keep) { run_pass(kc, m.a.p, m.b.p, m.g.p, rd.p, kept, m.k, f_tree, g_tree, kernel_ms); return; }
+    for (size_t i = 0; i < n; i++)                                  // the gather reads row keep[i]: inside the pass, ascending
+        if (keep[i] >= (u32)m.n || (i && keep[i] <= keep[i - 1])) throw std::invalid_argument("ResidentBatch: bad index list");
+    DevBuf index(n), a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS);
+    UG_HIP(hipMemcpy(index.p, keep, n * sizeof(u32), hipMemcpyHostToDevice));
+    auto gather = [&](const u32* src, int words, u32* dst) {
+        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * (size_t)words + 255) / 256)), dim3(256), 0, nullptr, src, index.p, n, words, dst);
+        UG_KERNEL_CHECK();
+    };
+    gather(m.a.p, G1_WORDS, a.p);
+    gather(m.b.p, G2_WORDS, b.p);
+    gather(m.g.p, (int)k * G1_WORDS, g.p);
+    run_pass(kc, a.p, b.p, g.p, rd.p, kept, m.k, f_tree, g_tree, kernel_ms);
 }
 
 // the vkx step keeps at most this many XYZZ products on the device at a time (144 bytes each)

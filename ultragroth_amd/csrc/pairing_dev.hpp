@@ -21,6 +21,24 @@ constexpr int PAIRING_PASS = 1 << 16;
 // Runs the kernels of pairing.hip on `device` and brings both trees back. Throws on a device error.
 void pairing_batch_device(int device, const pr::PairingConsts& kc, PairingBatch& pb);
 
+// The resident form, for packed proof records (include/verifier.h): the raw records of a pass are uploaded once, and the arrays the
+// Miller kernel reads are made on the device and stay there.
+//   ingest   records_ingest_kernel, then the subgroup ladder of check.hip in its mask form over the pi_b that passed;
+//            status[i] = UG_POINT_OK, UG_POINT_OFF_CURVE (any point of record i) or UG_POINT_OFF_SUBGROUP (its pi_b).
+//   run      the kernels of pairing_batch_device over the records keep[0..kept) (ascending positions within the pass), compacted by a
+//            gather kernel first; keep == nullptr: all n records, the arrays used in place. r: kept x 4 words.
+class ResidentBatch {
+public:
+    ResidentBatch(int device, int n, int k);
+    ~ResidentBatch();
+    ResidentBatch(const ResidentBatch&) = delete;
+    void ingest(const void* records, unsigned char* status);
+    void run(const pr::PairingConsts& kc, const u32* keep, int kept, const u32* r, u32* f_tree, u32* g_tree, double kernel_ms[3]);
+private:
+    struct Impl;
+    Impl* impl = nullptr;
+};
+
 // The suspects of a rejected pass, each judged by its own equation (pairing.hpp: judge_proof), one lane per suspect.
 struct PairingJudge {
     int n = 0;                  // suspects of this launch, at most PAIRING_PASS

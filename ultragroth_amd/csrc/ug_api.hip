@@ -636,6 +636,36 @@ int ug_points_check(ug_ctx* c, int g2, const void* host_points, uint64_t n, int 
     if (!c->check_level) check_release(c);                     // nothing stays resident
     UG_CATCH
 }
+// The mask form: the same pieces, the status bytes of each piece downloaded behind it.
+int ug_points_check_mask(ug_ctx* c, int g2, const void* host_points, uint64_t n, int level, uint8_t* reasons) {
+    UG_TRY
+    if (!c || (n && (!host_points || !reasons))) throw std::invalid_argument("null argument");
+    if (level != 1 && level != 2) throw std::invalid_argument("check level must be 1 or 2");
+    c->use();
+    if (!n) return UG_OK;
+    const size_t rec = g2 ? 128 : 64;
+    const u64 piece = ((u64)64 << 20) / rec;                   // 64 MiB of records at a time
+    const u64 room = n < piece ? n : piece;
+    u32* buf = nullptr;
+    uint8_t* status = nullptr;
+    if (hipMalloc(&buf, (size_t)room * rec) != hipSuccess || hipMalloc(&status, (size_t)room) != hipSuccess) {
+        (void)hipGetLastError();
+        if (buf) hipFree(buf);
+        throw std::runtime_error("not enough device memory for the point check");
+    }
+    try {
+        const bool is_g2 = g2 != 0;
+        for (u64 done = 0; done < n; done += piece) {
+            const u64 m = n - done < piece ? n - done : piece;
+            host_to_device(c, buf, static_cast<const uint8_t*>(host_points) + done * rec, (size_t)m * rec,
+                           [=](size_t off, size_t len, hipStream_t st) { check_points_mask(is_g2, buf + off / 4, len / rec, level, status + off / rec, st); },
+                           /*fresh*/ true);      // (every upload returns with its kernels done)
+            UG_HIP(hipMemcpy(reasons + done, status, (size_t)m, hipMemcpyDeviceToHost));
+        }
+    } catch (...) { hipFree(buf); hipFree(status); throw; }
+    hipFree(buf); hipFree(status);
+    UG_CATCH
+}
 const char* ug_point_reason_text(int reason) {
     return reason == UG_POINT_UNREDUCED ? "coordinate not below the field modulus"
          : reason == UG_POINT_OFF_CURVE ? "not on the curve"

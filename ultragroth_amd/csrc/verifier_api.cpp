@@ -420,6 +420,10 @@ int ultra_groth_verify(const char* proof, const char* inputs, const char* verifi
 // is not bilinear in the scalar there); the single verifier judges them, as it does every proof when the key itself has a
 // point off its curve or a G2 point outside the subgroup.
 //
+// The proofs of a call are JSON texts or packed records (include/verifier.h), a `Source` either way. Records on a device take the
+// resident path: the raw records are uploaded, reduced, checked and converted there (pairing.hip: records_ingest_kernel), and the
+// host reads of them only what the prefix sums and the UltraGroth challenge need.
+//
 // The judge (ug_verify_batch_options.judge, ULTRAGROTH_VERIFY_JUDGE=1; off by default). The search above costs the host two
 // batch checks per level and bad proof and a single verification per proof of a failing leaf node, so the sender of the proofs
 // decides what a call costs. With the judge on, a rejected pass is searched breadth first only while its failing nodes number
@@ -492,6 +496,8 @@ struct BatchTrace {
     double kernel_ms[3] = {0, 0, 0};       // the last device pass of the process: Miller kernel, Fq12 tree, G1 tree
     std::vector<int> index;                // ULTRAGROTH_TEST_HOOKS=1: the last call's batched proofs, their scalars and f_i
     std::vector<u32> r, f;
+    double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last call: ug_verify_batch_phase_ms
+    unsigned long long in_place = 0, gathered = 0;      // ... and its passes over packed records: arrays used in place / compacted first
 } g_trace;
 
 // one pass: the proofs idx[0..m) of the call, their trees and prefix sums
@@ -653,12 +659,123 @@ void judge_suspects(const BatchKey& key, int device, const std::vector<const Bat
     stats.judged += n;
 }
 
-int verify_batch(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+// ---- packed proof records (include/verifier.h) --------------------------------------------------------------------------------
+// A record is the proof.json whose decimal strings are its integers; these are the two directions of that sentence.
+constexpr size_t record_bytes(bool ultra) { return ultra ? 320 : 256; }
+
+// decimal string -> 256-bit integer, little-endian; false for anything but digits and for a value >= 2^256
+bool u256_from_decimal(uint8_t out[32], const std::string& s) {
+    if (s.empty()) return false;
+    u32 w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (char ch : s) {
+        if (ch < '0' || ch > '9') return false;
+        uint64_t carry = (uint64_t)(ch - '0');
+        for (int k = 0; k < 8; k++) { const uint64_t v = (uint64_t)w[k] * 10 + carry; w[k] = (u32)v; carry = v >> 32; }
+        if (carry) return false;
+    }
+    memcpy(out, w, 32);
+    return true;
+}
+std::string u256_to_decimal(const uint8_t in[32]) {
+    u32 w[8];
+    memcpy(w, in, 32);
+    std::vector<u32> chunks;                                        // base 10^9, lowest first
+    u32 any;
+    do {
+        uint64_t rem = 0;
+        any = 0;
+        for (int k = 7; k >= 0; k--) { const uint64_t v = (rem << 32) | w[k]; w[k] = (u32)(v / 1000000000u); rem = v % 1000000000u; any |= w[k]; }
+        chunks.push_back((u32)rem);
+    } while (any);
+    char buf[16];
+    snprintf(buf, sizeof buf, "%u", chunks.back());
+    std::string digits = buf;
+    for (size_t c = chunks.size() - 1; c-- > 0;) { snprintf(buf, sizeof buf, "%09u", chunks[c]); digits += buf; }
+    return digits;
+}
+F1 f1_from_u256(const uint8_t* p) {                                 // any 256-bit value, reduced mod q as f1_from_decimal reduces
+    u32 w[8];
+    memcpy(w, p, 32);
+    return F1{canon(from_normal<FqParams>(w))};
+}
+G1A g1_from_record(const uint8_t* p) {
+    G1A a{f1_from_u256(p), f1_from_u256(p + 32), false};
+    a.inf = is0(a.x) && is0(a.y);
+    return a;
+}
+G2A g2_from_record(const uint8_t* p) {
+    G2A q{F2{f1_from_u256(p), f1_from_u256(p + 32)}, F2{f1_from_u256(p + 64), f1_from_u256(p + 96)}, false};
+    q.inf = is0(q.x) && is0(q.y);
+    return q;
+}
+std::string record_to_json(bool ultra, const uint8_t* rec) {
+    auto g1 = [&](size_t at) { return "[\"" + u256_to_decimal(rec + at) + "\",\"" + u256_to_decimal(rec + at + 32) + "\",\"1\"]"; };
+    std::string t = "{\"pi_a\":" + g1(0) + ",\"pi_b\":[[\"" + u256_to_decimal(rec + 64) + "\",\"" + u256_to_decimal(rec + 96) + "\"],[\"" +
+                    u256_to_decimal(rec + 128) + "\",\"" + u256_to_decimal(rec + 160) + "\"],[\"1\",\"0\"]],";
+    if (ultra) t += "\"pi_f\":" + g1(192) + ",\"pi_r\":" + g1(256) + ",\"protocol\":\"ultragroth\"";
+    else t += "\"pi_c\":" + g1(192) + ",\"protocol\":\"groth16\"";
+    return t + ",\"curve\":\"bn128\"}";
+}
+std::string inputs_to_json(const uint8_t* in, size_t n_pub) {
+    std::string t = "[";
+    for (size_t c = 0; c < n_pub; c++) t += (c ? ",\"" : "\"") + u256_to_decimal(in + c * 32) + "\"";
+    return t + "]";
+}
+
+// Where the proofs of a call come from: JSON texts or packed records. parse() is step 1 of the batch for proof i and throws what the
+// single call would say; single() is the single-proof verifier on the same proof.
+struct Source {
+    bool ultra = false;
+    virtual ~Source() {}
+    // points = false: only what the host needs of a proof that stays on the device -- the inputs and the challenge
+    virtual void parse(size_t i, BatchProof& p, size_t ic_size, bool points) const = 0;
+    virtual int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const = 0;
+    virtual const uint8_t* raw() const { return nullptr; }          // packed records, for the device to ingest
+    virtual size_t inputs_per_proof() const { return 0; }           // records: the call's n_pub, the same for every proof
+};
+struct JsonSource : Source {
+    const char* const* proofs = nullptr;
+    const char* const* inputs = nullptr;
+    void parse(size_t i, BatchProof& p, size_t ic_size, bool) const override {
+        if (!proofs[i] || !inputs[i]) throw std::invalid_argument("null argument");
+        if (ultra) { UltraProof u = parse_ultra_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.final_commit; p.g[1] = u.round_commit; }
+        else { Groth16Proof u = parse_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.c; p.g[1] = G1A{f1_zero(), f1_zero(), true}; }
+        p.in = parse_inputs(inputs[i]);
+        if (p.in.plain.size() + 1 != ic_size) throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
+    }
+    int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const override {
+        return (ultra ? ultra_groth_verify : groth16_verify)(proofs[i], inputs[i], verification_key, msg, cap);
+    }
+};
+struct RecordSource : Source {
+    const uint8_t* records = nullptr;
+    const uint8_t* inputs = nullptr;
+    size_t n_pub = 0;
+    void parse(size_t i, BatchProof& p, size_t, bool points) const override {
+        const uint8_t* rec = records + i * record_bytes(ultra);
+        p.g[1] = ultra ? g1_from_record(rec + 256) : G1A{f1_zero(), f1_zero(), true};
+        if (points) { p.a = g1_from_record(rec); p.b = g2_from_record(rec + 64); p.g[0] = g1_from_record(rec + 192); }
+        p.in.plain.assign(n_pub, std::vector<u32>(8));
+        for (size_t c = 0; c < n_pub; c++) {                        // reduced mod r, as fr_plain_from_decimal
+            u32 w[8];
+            memcpy(w, inputs + (i * n_pub + c) * 32, 32);
+            to_normal(p.in.plain[c].data(), from_normal<FrParams>(w));
+        }
+    }
+    int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const override {
+        const std::string proof = record_to_json(ultra, records + i * record_bytes(ultra)), in = inputs_to_json(inputs + i * n_pub * 32, n_pub);
+        return (ultra ? ultra_groth_verify : groth16_verify)(proof.c_str(), in.c_str(), verification_key, msg, cap);
+    }
+    const uint8_t* raw() const override { return records; }
+    size_t inputs_per_proof() const override { return n_pub; }
+};
+
+int verify_batch(const Source& src, int device, int count, const char* verification_key,
                  int* verdicts, const BatchOptions& opt, ug_verify_batch_stats_ex* stats_out, char* error_msg, unsigned long error_msg_maxsize) {
     try {
         const auto t_start = std::chrono::steady_clock::now();
-        if (count < 0 || !verification_key || (count > 0 && (!proofs || !inputs || !verdicts))) throw std::invalid_argument("null argument");
-        auto single = ultra ? ultra_groth_verify : groth16_verify;
+        const bool ultra = src.ultra;
+        if (count < 0 || !verification_key || (count > 0 && !verdicts)) throw std::invalid_argument("null argument");
         ug_verify_batch_stats_ex stats_ex = {{0, 0, 0, 0.0, 0.0}, 0, 0, 0.0};
         ug_verify_batch_stats& stats = stats_ex.base;
         BatchKey key;
@@ -672,6 +789,11 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
             key.alpha = k.alpha; key.ic_rand = G1A{f1_zero(), f1_zero(), true}; key.beta = k.beta; key.gamma = k.gamma;
             key.delta[0] = k.delta; key.delta[1] = k.delta; key.ic = k.ic;
         }
+        if (src.inputs_per_proof() && src.inputs_per_proof() + 1 != key.ic.size())      // (texts: checked per proof, in parse)
+            throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
+        double phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};                // where the call's time goes (ug_verify_batch_phase_ms)
+        auto t_lap = t_start;
+        auto lap = [&](int k) { const auto now = std::chrono::steady_clock::now(); phase[k] += std::chrono::duration<double, std::milli>(now - t_lap).count(); t_lap = now; };
         bool key_ok = g1_on_curve(key.alpha) && g1_on_curve(key.ic_rand);
         for (const G1A& p : key.ic) key_ok = key_ok && g1_on_curve(p);
         for (const G2A* q : {&key.beta, &key.gamma, &key.delta[0], &key.delta[1]}) key_ok = key_ok && g2_on_curve(*q) && g2_in_subgroup(*q);
@@ -681,24 +803,69 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
         std::vector<State> state(n, key_ok ? BATCH : SINGLE);
         std::vector<BatchProof> parsed(key_ok ? n : 0);
         std::vector<std::string> message(n);
+        const bool hooks = ughost::testHooksEnabled();
+        if (hooks) { std::lock_guard<std::mutex> lock(g_trace.m); g_trace.index.clear(); g_trace.r.clear(); g_trace.f.clear(); g_trace.in_place = g_trace.gathered = 0; }
+        // the scalars of a pass and the prefix sums of its proofs idx[0..m)
+        auto draw_scalars = [&](Pass& pass, const size_t* idx, std::vector<u32>& r) {
+            const size_t m = pass.m;
+            r.resize(m * 4);
+            for (size_t got = 0; got < r.size() * sizeof(u32);) {
+                const ssize_t w = getrandom((uint8_t*)r.data() + got, r.size() * sizeof(u32) - got, 0);
+                if (w <= 0) throw std::runtime_error("getrandom failed");
+                got += (size_t)w;
+            }
+            for (size_t i = 0; i < m; i++) if (!(r[4 * i] | r[4 * i + 1] | r[4 * i + 2] | r[4 * i + 3])) r[4 * i] = 1;       // (2^-128)
+            pass.prefix.assign((m + 1) * pass.cols, fp_zero<FrParams>());
+            std::vector<Fr> term(m * pass.cols);
+            parallel_for(m, [&](size_t i) {
+                const BatchProof& p = parsed[idx[i]];
+                const u32 rw[8] = {r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], 0, 0, 0, 0};
+                const Fr rf = fr_from_plain(rw);
+                Fr* t = &term[i * pass.cols];
+                t[0] = rf;
+                for (size_t c = 0; c < p.in.plain.size(); c++) t[1 + c] = canon(mul(rf, fr_from_plain(p.in.plain[c].data())));
+                if (ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
+            });
+            for (size_t i = 0; i < m; i++)
+                for (size_t c = 0; c < pass.cols; c++)
+                    pass.prefix[(i + 1) * pass.cols + c] = canon(add(pass.prefix[i * pass.cols + c], term[i * pass.cols + c]));
+        };
+        // the trees of a pass are there: the root check, the search of a rejected pass, the verdicts
+        auto settle = [&](Pass& pass, const size_t* idx, const std::vector<u32>& r) {
+            const size_t m = pass.m;
+            if (hooks) {
+                std::lock_guard<std::mutex> lock(g_trace.m);
+                for (size_t i = 0; i < m; i++) g_trace.index.push_back((int)idx[i]);
+                g_trace.r.insert(g_trace.r.end(), r.begin(), r.end());
+                g_trace.f.insert(g_trace.f.end(), pass.f_tree.begin(), pass.f_tree.begin() + m * F12_WORDS);
+            }
+            const size_t top = pass.level_size.size() - 1;
+            std::vector<size_t> suspects;
+            if (!pass.node_ok(top, 0)) {
+                if (opt.judge) pass.search(top, 0, (size_t)opt.search_width, suspects);
+                else pass.walk(top, 0, suspects);
+            }
+            for (size_t i = 0; i < m; i++) { verdict[idx[i]] = VERIFIER_VALID_PROOF; state[idx[i]] = DONE; }
+            for (size_t s : suspects) state[idx[s]] = SINGLE;
+            stats.batch_checks += pass.checks;
+        };
+        const bool resident = key_ok && device >= 0 && src.raw();
+        lap(0);
         // 1. parse; what the single call would answer before any pairing is answered here
-        if (key_ok) parallel_for(n, [&](size_t i) {
+        if (key_ok && !resident) parallel_for(n, [&](size_t i) {
             state[i] = DONE;
             try {
-                if (!proofs[i] || !inputs[i]) throw std::invalid_argument("null argument");
                 BatchProof& p = parsed[i];
-                if (ultra) { UltraProof u = parse_ultra_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.final_commit; p.g[1] = u.round_commit; }
-                else { Groth16Proof u = parse_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.c; p.g[1] = G1A{f1_zero(), f1_zero(), true}; }
-                p.in = parse_inputs(inputs[i]);
-                if (p.in.plain.size() + 1 != key.ic.size()) throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
+                src.parse(i, p, key.ic.size(), true);
                 if (!g1_on_curve(p.a) || !g1_on_curve(p.g[0]) || !g1_on_curve(p.g[1]) || !g2_on_curve(p.b)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
                 if (ultra) derive_challenge_plain(p.challenge, p.g[1]);
                 state[i] = BATCH;
             } catch (std::exception& e) { message[i] = e.what(); }
         });
+        lap(1);
         // 2. B outside the subgroup: out of the batch
         std::vector<size_t> cand;
-        for (size_t i = 0; i < n; i++) if (state[i] == BATCH) cand.push_back(i);
+        if (!resident) for (size_t i = 0; i < n; i++) if (state[i] == BATCH) cand.push_back(i);
         if (device < 0) {
             parallel_for(cand.size(), [&](size_t c) { if (!g2_in_subgroup(parsed[cand[c]].b)) state[cand[c]] = SINGLE; });
         } else if (!cand.empty()) {
@@ -711,48 +878,29 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
                 to_mont256(&rec[c * 32 + 16], q.y.a.v); to_mont256(&rec[c * 32 + 24], q.y.b.v);
             });
             Ctx ctx(device);
-            for (size_t start = 0; start < cand.size();) {         // the check names the lowest bad index: go on behind it
-                ug_point_fault fault = {0, UG_POINT_OK};
-                if (ug_points_check(ctx.c, 1, &rec[start * 32], cand.size() - start, 2, &fault) != UG_OK) throw std::runtime_error(ug_last_error());
-                if (fault.reason == UG_POINT_OK) break;
-                state[cand[start + fault.index]] = SINGLE;
-                start += fault.index + 1;
-            }
+            std::vector<uint8_t> reasons(cand.size(), UG_POINT_OK);            // one call answers for every point
+            if (ug_points_check_mask(ctx.c, 1, rec.data(), cand.size(), 2, reasons.data()) != UG_OK) throw std::runtime_error(ug_last_error());
+            for (size_t c = 0; c < cand.size(); c++) if (reasons[c] != UG_POINT_OK) state[cand[c]] = SINGLE;
             stats.device_ms += ms_since(t0);
         }
         std::vector<size_t> idx;
         for (size_t i : cand) { if (state[i] == BATCH) idx.push_back(i); else stats.off_subgroup++; }
+        lap(2);
         // 3. the batch, in passes
-        const bool hooks = ughost::testHooksEnabled();
-        if (hooks) { std::lock_guard<std::mutex> lock(g_trace.m); g_trace.index.clear(); g_trace.r.clear(); g_trace.f.clear(); }
         for (size_t first = 0; first < idx.size(); first += PAIRING_PASS) {
             const size_t m = std::min<size_t>(PAIRING_PASS, idx.size() - first);
             Pass pass(key, m);
             const int k = pass.k;
-            std::vector<u32> r(m * 4), a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS);
-            for (size_t got = 0; got < r.size() * sizeof(u32);) {
-                const ssize_t w = getrandom((uint8_t*)r.data() + got, r.size() * sizeof(u32) - got, 0);
-                if (w <= 0) throw std::runtime_error("getrandom failed");
-                got += (size_t)w;
-            }
-            for (size_t i = 0; i < m; i++) if (!(r[4 * i] | r[4 * i + 1] | r[4 * i + 2] | r[4 * i + 3])) r[4 * i] = 1;       // (2^-128)
-            pass.prefix.assign((m + 1) * pass.cols, fp_zero<FrParams>());
-            std::vector<Fr> term(m * pass.cols);
+            std::vector<u32> r, a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS);
+            draw_scalars(pass, &idx[first], r);
+            lap(3);
             parallel_for(m, [&](size_t i) {
                 const BatchProof& p = parsed[idx[first + i]];
                 g1_words(&a[i * G1_WORDS], p.a);
                 g2_words(&b[i * G2_WORDS], p.b);
                 for (int s = 0; s < k; s++) g1_words(&g[(i * k + s) * G1_WORDS], p.g[s]);
-                const u32 rw[8] = {r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], 0, 0, 0, 0};
-                const Fr rf = fr_from_plain(rw);
-                Fr* t = &term[i * pass.cols];
-                t[0] = rf;
-                for (size_t c = 0; c < p.in.plain.size(); c++) t[1 + c] = canon(mul(rf, fr_from_plain(p.in.plain[c].data())));
-                if (ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
             });
-            for (size_t i = 0; i < m; i++)
-                for (size_t c = 0; c < pass.cols; c++)
-                    pass.prefix[(i + 1) * pass.cols + c] = canon(add(pass.prefix[i * pass.cols + c], term[i * pass.cols + c]));
+            lap(4);
             if (device < 0) pass.host_trees(a.data(), b.data(), g.data(), r.data());
             else {
                 const auto t0 = std::chrono::steady_clock::now();
@@ -763,27 +911,59 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
                 stats.device_ms += ms_since(t0);
                 { std::lock_guard<std::mutex> lock(g_trace.m); for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = pb.kernel_ms[t]; }
             }
-            if (hooks) {
+            lap(5);
+            settle(pass, &idx[first], r);
+            lap(6);
+        }
+        // 1-3 for packed records on a device, per pass of PAIRING_PASS records: the raw records cross PCIe once, the device reduces
+        // and checks them and keeps the arrays of the Miller kernel; the host reads no coordinate of a proof that stays in the
+        // batch (UltraGroth: pi_r, for the challenge). Off its curve: INVALID; pi_b off the subgroup: SINGLE, as in step 2.
+        for (size_t first = 0; resident && first < n; first += PAIRING_PASS) {
+            const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
+            const int k = key.k();
+            parallel_for(m, [&](size_t i) {
+                BatchProof& p = parsed[first + i];
+                src.parse(first + i, p, key.ic.size(), false);
+                if (ultra) derive_challenge_plain(p.challenge, p.g[1]);
+            });
+            lap(1);
+            auto t0 = std::chrono::steady_clock::now();
+            ResidentBatch rb(device, (int)m, k);
+            std::vector<uint8_t> status(m);
+            rb.ingest(src.raw() + first * record_bytes(ultra), status.data());
+            stats.device_ms += ms_since(t0);
+            std::vector<size_t> kept;
+            std::vector<u32> keep;
+            for (size_t i = 0; i < m; i++) {
+                if (status[i] == UG_POINT_OK) { kept.push_back(first + i); keep.push_back((u32)i); state[first + i] = BATCH; }
+                else if (status[i] == UG_POINT_OFF_SUBGROUP) { state[first + i] = SINGLE; stats.off_subgroup++; }
+                else { state[first + i] = DONE; verdict[first + i] = VERIFIER_INVALID_PROOF; }
+            }
+            lap(2);
+            if (kept.empty()) continue;
+            Pass pass(key, kept.size());
+            std::vector<u32> r;
+            draw_scalars(pass, kept.data(), r);
+            lap(3);
+            t0 = std::chrono::steady_clock::now();
+            double kernel_ms[3];
+            rb.run(consts(), kept.size() == m ? nullptr : keep.data(), (int)kept.size(), r.data(), pass.f_tree.data(), pass.g_tree.data(), kernel_ms);
+            stats.device_ms += ms_since(t0);
+            {
                 std::lock_guard<std::mutex> lock(g_trace.m);
-                for (size_t i = 0; i < m; i++) g_trace.index.push_back((int)idx[first + i]);
-                g_trace.r.insert(g_trace.r.end(), r.begin(), r.end());
-                g_trace.f.insert(g_trace.f.end(), pass.f_tree.begin(), pass.f_tree.begin() + m * F12_WORDS);
+                for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = kernel_ms[t];
+                if (hooks) (kept.size() == m ? g_trace.in_place : g_trace.gathered)++;
             }
-            const size_t top = pass.level_size.size() - 1;
-            std::vector<size_t> suspects;
-            if (!pass.node_ok(top, 0)) {
-                if (opt.judge) pass.search(top, 0, (size_t)opt.search_width, suspects);
-                else pass.walk(top, 0, suspects);
-            }
-            for (size_t i = 0; i < m; i++) { verdict[idx[first + i]] = VERIFIER_VALID_PROOF; state[idx[first + i]] = DONE; }
-            for (size_t s : suspects) state[idx[first + s]] = SINGLE;
-            stats.batch_checks += pass.checks;
+            lap(5);
+            settle(pass, kept.data(), r);
+            lap(6);
         }
         // 4. whatever is left: to the judge when it is on and the suspects are many enough (never under a key the batch refused),
         //    else to the single verifier on the host threads
         std::vector<size_t> singles;
         for (size_t i = 0; i < n; i++) if (state[i] == SINGLE) singles.push_back(i);
         if (opt.judge && key_ok && !singles.empty() && singles.size() >= (size_t)opt.judge_min) {
+            if (resident) parallel_for(singles.size(), [&](size_t s) { src.parse(singles[s], parsed[singles[s]], key.ic.size(), true); });   // rebuilt from the raw records
             std::vector<const BatchProof*> sus;
             for (size_t i : singles) sus.push_back(&parsed[i]);
             std::vector<char> valid;
@@ -794,10 +974,12 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
         parallel_for(singles.size(), [&](size_t s) {
             const size_t i = singles[s];
             char msg[256] = {0};
-            verdict[i] = single(proofs[i], inputs[i], verification_key, msg, sizeof msg - 1);
+            verdict[i] = src.single(i, verification_key, msg, sizeof msg - 1);
             if (verdict[i] == VERIFIER_ERROR) message[i] = msg;
         });
         stats.single_checks = singles.size();
+        lap(7);
+        { std::lock_guard<std::mutex> lock(g_trace.m); for (int k = 0; k < 8; k++) g_trace.phase_ms[k] = phase[k]; }
         int rc = VERIFIER_VALID_PROOF;
         for (size_t i = 0; i < n; i++) {
             verdicts[i] = verdict[i];
@@ -824,6 +1006,14 @@ int verify_batch(bool ultra, int device, int count, const char* const* proofs, c
 
 extern "C" {
 
+// the JSON calls: null arrays fail the call as a null key does
+static int verify_batch_json(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                             int* verdicts, const BatchOptions& opt, ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    if (count > 0 && (!proofs || !inputs)) { copy_error(error_msg, error_msg_maxsize, "null argument"); return VERIFIER_ERROR; }
+    JsonSource src;
+    src.ultra = ultra; src.proofs = proofs; src.inputs = inputs;
+    return verify_batch(src, device, count, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
+}
 // the existing calls: options from the environment, the 40-byte stats
 static int verify_batch_env(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                             int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
@@ -831,14 +1021,11 @@ static int verify_batch_env(bool ultra, int device, int count, const char* const
     try { opt.judge = judge_from_environment(); }
     catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return VERIFIER_ERROR; }
     ug_verify_batch_stats_ex ex;
-    const int rc = verify_batch(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats ? &ex : nullptr, error_msg, error_msg_maxsize);
+    const int rc = verify_batch_json(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats ? &ex : nullptr, error_msg, error_msg_maxsize);
     if (stats && rc != VERIFIER_ERROR) *stats = ex.base;
     return rc;
 }
-static int verify_batch_opt(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
-                            int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
-                            unsigned long error_msg_maxsize) {
-    BatchOptions opt;
+static bool read_options(BatchOptions& opt, const ug_verify_batch_options* options, char* error_msg, unsigned long error_msg_maxsize) {
     try {
         if (!options) opt.judge = judge_from_environment();
         else {
@@ -848,8 +1035,26 @@ static int verify_batch_opt(bool ultra, int device, int count, const char* const
             if (options->search_width >= 0) opt.search_width = options->search_width;
             if (options->judge_min >= 0) opt.judge_min = options->judge_min;
         }
-    } catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return VERIFIER_ERROR; }
-    return verify_batch(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
+        return true;
+    } catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return false; }
+}
+static int verify_batch_opt(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
+                            int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                            unsigned long error_msg_maxsize) {
+    BatchOptions opt;
+    if (!read_options(opt, options, error_msg, error_msg_maxsize)) return VERIFIER_ERROR;
+    return verify_batch_json(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
+}
+static int verify_batch_records(bool ultra, int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
+                                int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                                unsigned long error_msg_maxsize) {
+    BatchOptions opt;
+    if (!read_options(opt, options, error_msg, error_msg_maxsize)) return VERIFIER_ERROR;
+    if (count < 0 || !verification_key || (count > 0 && (!records || !inputs || !verdicts))) { copy_error(error_msg, error_msg_maxsize, "null argument"); return VERIFIER_ERROR; }
+    if (n_pub <= 0) { copy_error(error_msg, error_msg_maxsize, "invalid inputs data"); return VERIFIER_ERROR; }
+    RecordSource src;
+    src.ultra = ultra; src.records = static_cast<const uint8_t*>(records); src.inputs = static_cast<const uint8_t*>(inputs); src.n_pub = (size_t)n_pub;
+    return verify_batch(src, device, count, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
 }
 
 int ug_groth16_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
@@ -871,6 +1076,75 @@ int ug_ultra_groth_verify_batch_opt(int device, int count, const char* const* pr
     return verify_batch_opt(true, device, count, proofs, inputs, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
 }
 
+int ug_groth16_verify_batch_records(int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
+                                    int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                                    unsigned long error_msg_maxsize) {
+    return verify_batch_records(false, device, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_ultra_groth_verify_batch_records(int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
+                                        int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
+                                        unsigned long error_msg_maxsize) {
+    return verify_batch_records(true, device, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+
+int ug_proof_pack(int ultra, const char* proof_json, void* record) {
+    if (!proof_json || !record) return 1;
+    try {
+        const JVal j = JParser(proof_json).parse_document();
+        if (j.at("protocol").string() != (ultra ? "ultragroth" : "groth16")) return 1;
+        uint8_t rec[320];
+        bool ok = true;
+        auto g1 = [&](const char* name, size_t at) {
+            const JVal& v = j.at(name);
+            ok = ok && u256_from_decimal(rec + at, v.at((size_t)0).string()) && u256_from_decimal(rec + at + 32, v.at((size_t)1).string());
+        };
+        g1("pi_a", 0);
+        const JVal& b = j.at("pi_b");
+        for (size_t c = 0; c < 4; c++) ok = ok && u256_from_decimal(rec + 64 + c * 32, b.at(c >> 1).at(c & 1).string());
+        if (ultra) { g1("pi_f", 192); g1("pi_r", 256); } else g1("pi_c", 192);
+        if (!ok) return 1;
+        memcpy(record, rec, record_bytes(ultra != 0));
+        return 0;
+    } catch (...) { return 1; }
+}
+int ug_inputs_pack(const char* inputs_json, void* out, int n_pub) {
+    if (!inputs_json || !out || n_pub <= 0) return 1;
+    try {
+        const JVal j = JParser(inputs_json).parse_document();
+        if (j.type != JVal::Array || j.arr.size() != (size_t)n_pub) return 1;
+        std::vector<uint8_t> buf((size_t)n_pub * 32);
+        for (size_t c = 0; c < j.arr.size(); c++) if (!u256_from_decimal(&buf[c * 32], j.arr[c].string())) return 1;
+        memcpy(out, buf.data(), buf.size());
+        return 0;
+    } catch (...) { return 1; }
+}
+static int copy_text(const std::string& t, char* json, unsigned long maxsize) {
+    if (!json || t.size() + 1 > maxsize) return 1;
+    memcpy(json, t.c_str(), t.size() + 1);
+    return 0;
+}
+int ug_proof_unpack(int ultra, const void* record, char* json, unsigned long maxsize) {
+    if (!record) return 1;
+    try { return copy_text(record_to_json(ultra != 0, static_cast<const uint8_t*>(record)), json, maxsize); } catch (...) { return 1; }
+}
+int ug_inputs_unpack(const void* in, int n_pub, char* json, unsigned long maxsize) {
+    if (!in || n_pub <= 0) return 1;
+    try { return copy_text(inputs_to_json(static_cast<const uint8_t*>(in), (size_t)n_pub), json, maxsize); } catch (...) { return 1; }
+}
+
+// ULTRAGROTH_TEST_HOOKS=1 only: the passes of the last records call on a device that used the resident arrays in place, and those that
+// compacted them through the gather kernel first
+int ug_test_verify_records_passes(unsigned long long passes[2]) {
+    if (!ughost::testHooksEnabled() || !passes) return 1;
+    std::lock_guard<std::mutex> lock(g_trace.m);
+    passes[0] = g_trace.in_place; passes[1] = g_trace.gathered;
+    return 0;
+}
+
+void ug_verify_batch_phase_ms(double ms[8]) {
+    std::lock_guard<std::mutex> lock(g_trace.m);
+    for (int k = 0; k < 8; k++) ms[k] = g_trace.phase_ms[k];
+}
 void ug_verify_batch_kernel_ms(double ms[3]) {
     std::lock_guard<std::mutex> lock(g_trace.m);
     for (int t = 0; t < 3; t++) ms[t] = g_trace.kernel_ms[t];
