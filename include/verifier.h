@@ -101,8 +101,8 @@ int ug_ultra_groth_verify_batch_opt(int device, int count, const char *const *pr
  *   UltraGroth  pi_a (64) | pi_b (128) | pi_f (64) | pi_r (64)                                        320 bytes
  * and the public inputs of all proofs are count x n_pub x 32 contiguous bytes in the same integer form. A record STANDS FOR
  * the proof.json whose decimal strings are its integers (ug_proof_unpack writes that text), an input block for that
- * public.json: coordinates are taken mod q and inputs mod r as the JSON parsers take them, and (0, 0) is infinity. Other
- * byte orders (EVM calldata) are the caller's to convert.
+ * public.json: coordinates are taken mod q and inputs mod r as the JSON parsers take them, and (0, 0) is infinity. That is the
+ * PLAIN layout; the _fmt calls below take two more.
  * verdicts[i] is what groth16_verify / ultra_groth_verify returns for the unpacked texts of record i, up to the 2^-128 of the
  * batch; a record cannot fail to parse, so it is VERIFIER_VALID_PROOF or VERIFIER_INVALID_PROOF. VERIFIER_ERROR, verdicts
  * untouched: null arguments or count < 0 ("null argument"), n_pub <= 0 ("invalid inputs data"), a key that does not parse,
@@ -122,6 +122,51 @@ int ug_groth16_verify_batch_records(int device, int count, const void *records, 
 int ug_ultra_groth_verify_batch_records(int device, int count, const void *records, const void *inputs, int n_pub,
                                         const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
                                         ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+
+/* ---- record layouts ------------------------------------------------------------------------------------------------------
+ * UG_RECORDS_PLAIN       the layout above.
+ * UG_RECORDS_EVM         the same sizes, 256 / 320 bytes, in the order of the EVM pairing precompile's calldata: every 32-byte
+ *                        coordinate is big-endian, and an Fq2 coordinate is stored imaginary part first, pi_b = x.c1, x.c0, y.c1,
+ *                        y.c0. The input block is big-endian too. Everything else follows PLAIN: values are taken mod q / mod r,
+ *                        and (0, 0) is infinity.
+ * UG_RECORDS_COMPRESSED  one x coordinate and a sign bit per point: 128 bytes for Groth16 (pi_a 32 | pi_b 64 | pi_c 32), 160 for
+ *                        UltraGroth (pi_a | pi_b | pi_f | pi_r). A G1 point is x as a 32-byte little-endian integer, a G2 point
+ *                        x.c0 | x.c1, 64 bytes. The two top bits of the point's LAST byte are flags: bit 6 (0x40) means infinity --
+ *                        the point is infinity whatever its other bits say -- and bit 7 (0x80) says that y is the larger of the two
+ *                        roots, y > -y. For Fq "larger" means y > (q - 1) / 2 as an integer; for Fq2 c1 is compared first: if
+ *                        c1 != 0, larger means c1 > (q - 1) / 2, and if c1 = 0 it means c0 > (q - 1) / 2. The remaining 254 bits
+ *                        are x (for G2: of x.c1, with x.c0 a full word), taken mod q like every other coordinate here. The input
+ *                        block is the PLAIN one.
+ * A record of any layout STANDS FOR the plain record it converts to (ug_proof_record_convert), and through it for the proof.json
+ * of ug_proof_unpack: its verdict is the single verifier's on that text, up to the batch's 2^-128. A compressed point whose x has
+ * no y on the curve converts to nothing: such a record is VERIFIER_INVALID_PROOF, handled exactly like a point off its curve --
+ * the same status and reason text, no pairing.
+ * The _fmt calls are the records calls above with the layout as an argument; format = UG_RECORDS_PLAIN IS those calls, on the
+ * same code path. An unknown format fails the call with VERIFIER_ERROR, "format: not one of UG_RECORDS_PLAIN, UG_RECORDS_EVM,
+ * UG_RECORDS_COMPRESSED". device >= 0: the ingest kernel reads the layout itself -- EVM by loading a coordinate's words reversed,
+ * COMPRESSED by taking the square roots in the lane that ingests the record (one Fq root per G1 point, up to three for pi_b:
+ * fixed-exponent powers, pairing.hpp) -- and writes the same arrays, so everything after it is unchanged. The UltraGroth
+ * challenge of a compressed record is derived from the pi_r the device decompressed; the host takes no root per proof. Suspects
+ * and singles are rebuilt on the host from their raw records, those few only. device < 0: every record is converted on the host
+ * threads. */
+enum { UG_RECORDS_PLAIN = 0, UG_RECORDS_EVM = 1, UG_RECORDS_COMPRESSED = 2 };
+/* bytes of one proof record: 256 / 320, or 128 / 160 compressed; 0 for an unknown format */
+unsigned long ug_proof_record_bytes(int ultra, int format);
+int ug_groth16_verify_batch_records_fmt(int device, int format, int count, const void *records, const void *inputs, int n_pub,
+                                        const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
+                                        ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+int ug_ultra_groth_verify_batch_records_fmt(int device, int format, int count, const void *records, const void *inputs, int n_pub,
+                                            const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
+                                            ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+/* One record from one layout to another, every coordinate reduced mod q on the way (from == to: the record reduced). 0 = converted;
+ * 1 = the source holds no point to convert -- from COMPRESSED an x with no root, to COMPRESSED a point that is not on its curve,
+ * since a sign bit cannot stand for it; 2 = a null argument or an unknown format. `to` is written only on 0. PLAIN <-> EVM never
+ * returns 1, and COMPRESSED -> PLAIN of PLAIN -> COMPRESSED of a record is that record with every coordinate reduced. */
+int ug_proof_record_convert(int ultra, int from_format, const void *from, int to_format, void *to);
+/* One proof's input block, n_pub x 32 bytes, from the byte order of one layout to that of another: a byte reversal of every value
+ * between EVM and the other two, else a copy; values are not reduced. 0 = ok; 2 = a null argument, n_pub <= 0 or an unknown format. */
+int ug_inputs_convert(int from_format, const void *from, int n_pub, int to_format, void *to);
+
 /* proof.json -> record (256 / 320 bytes). 0 = ok; 1 = the text does not parse as a proof of that protocol, or a value is >= 2^256 */
 int ug_proof_pack(int ultra, const char *proof_json, void *record);
 /* public.json -> n_pub x 32 bytes. 0 = ok; 1 = parse error, a value >= 2^256 or another count than n_pub */
@@ -153,6 +198,13 @@ int ug_test_final_exp(int device, const unsigned int f[108], unsigned int g[108]
 /* the passes of the last records call on a device: [0] those that used the resident arrays in place, [1] those that compacted
  * them through the gather kernel first */
 int ug_test_verify_records_passes(unsigned long long passes[2]);
+/* Upload and ingest only, count records of `format`: plain_out gets, per record, the plain 256 / 320 bytes that the device's arrays
+ * hold afterwards -- coordinates reduced, infinity as zeros, a point that failed (no root, off its curve) as zeros -- and status the
+ * record's UG_POINT_* byte. device < 0: the host's reading of the same records. */
+int ug_test_records_ingest(int device, int format, int ultra, int count, const void *records, void *plain_out, unsigned char *status);
+/* f2_sqrt (pairing.hpp) of count values, each 64 bytes plain little-endian c0 | c1: out gets the root that is NOT the larger one in
+ * the same form (zeros when there is none), has_root one byte each. One lane per element on a device; device < 0: the host's code. */
+int ug_test_fq2_sqrt(int device, int count, const void *in, void *out, unsigned char *has_root);
 
 #ifdef __cplusplus
 }

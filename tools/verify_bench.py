@@ -16,6 +16,10 @@ subgroup" are added at 2^14 and "1 % bad" at 2^16. --sweep W1,W2,..:M1,M2,.. rep
 search_width W and judge_min M.
 
 --records compares the JSON call with ug_groth16_verify_batch_records on the same valid batches (profiles/verify_records.txt).
+--records --format evm|compressed|all compares the record layouts instead (profiles/verify_record_formats.txt): the same valid
+batches, converted ONCE outside the timed call, through ug_groth16_verify_batch_records (plain) and ug_groth16_verify_batch_records_fmt,
+--runs runs of each in turn, with the ingest step of each call (ug_verify_batch_phase_ms [2]: upload, ingest kernel, ladder, status
+bytes). --parent-lib PATH loads another build of the library beside this one and runs its plain records call in the same turns.
 """
 import argparse
 import ctypes as C
@@ -87,6 +91,59 @@ def records_report(a, L, vk, pool, run, say):
                     say("    split (ms): %s" % phases())
 
 
+FORMATS = {"plain": 0, "evm": 1, "compressed": 2}
+
+
+def formats_report(a, L, vk, pool, say):
+    """--records --format: see the module docstring"""
+    from ultragroth_amd._lib import VerifyBatchStatsEx
+    import ultragroth_amd as ug
+    n_pub = len(json.loads(pool[0][1]))
+    names = {"all": ["evm", "compressed"], "plain": []}.get(a.format, [a.format])     # plain alone: this build beside --parent-lib
+    packed = {"plain": [(ug.proof_pack(pr), ug.inputs_pack(pub, n_pub)) for pr, pub in pool]}
+    for name in names:
+        f = FORMATS[name]
+        packed[name] = [(ug.proof_record_convert(r, ug.RECORDS_PLAIN, f), ug.inputs_convert(b, ug.RECORDS_PLAIN, f)) for r, b in packed["plain"]]
+    parent = None
+    if a.parent_lib:
+        parent = C.CDLL(os.path.abspath(a.parent_lib))
+        vp = C.c_void_p
+        parent.ug_groth16_verify_batch_records.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+        parent.ug_verify_batch_phase_ms.argtypes = [vp]
+        parent.ug_verify_batch_phase_ms.restype = None
+        parent.ug_verify_batch_kernel_ms.argtypes = [vp]
+        parent.ug_verify_batch_kernel_ms.restype = None
+
+    def run_one(lib, name, n):
+        src = packed[name]
+        recs = b"".join(src[i % len(src)][0] for i in range(n))
+        ins = b"".join(src[i % len(src)][1] for i in range(n))
+        verdicts, err, ex = (C.c_int * n)(), C.create_string_buffer(256), VerifyBatchStatsEx()
+        t0 = time.perf_counter()
+        if name == "plain":
+            rc = lib.ug_groth16_verify_batch_records(a.device, n, recs, ins, n_pub, vk, verdicts, None, C.byref(ex), err, 255)
+        else:
+            rc = lib.ug_groth16_verify_batch_records_fmt(a.device, FORMATS[name], n, recs, ins, n_pub, vk, verdicts, None, C.byref(ex), err, 255)
+        dt = time.perf_counter() - t0
+        if rc != 0 or any(verdicts):
+            raise RuntimeError("verify_batch_records (%s): rc %d, %s" % (name, rc, err.value.decode()))
+        phase, ms = (C.c_double * 8)(), (C.c_double * 3)()
+        lib.ug_verify_batch_phase_ms(phase)
+        lib.ug_verify_batch_kernel_ms(ms)
+        return dt, ex.base, list(phase), list(ms)
+
+    turns = ([("parent plain", parent, "plain")] if parent else []) + [("plain", L, "plain")] + [(name, L, name) for name in names]
+    for lg in [int(s) for s in a.sizes.split(",")]:
+        n = 1 << lg
+        for label, lib, name in turns:
+            run_one(lib, name, n)                                                  # warm-up of every code path at this size, not timed
+        for rep in range(a.runs):
+            for label, lib, name in turns[rep % len(turns):] + turns[:rep % len(turns)]:       # a turn starts with another call each time
+                dt, st, phase, ms = run_one(lib, name, n)
+                say("N=2^%d %-12s run %d  %9.0f proofs/s  wall %8.1f ms  device_ms %8.1f host_ms %8.1f  ingest step %6.2f ms  miller kernel %.1f ms"
+                    % (lg, label, rep, n / dt, dt * 1e3, st.device_ms, st.host_ms, phase[2], ms[0]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="10,14,16")
@@ -104,6 +161,8 @@ def main():
     ap.add_argument("--batches", default="none,one,1pct,50pct,offsub", help="with --skip-valid: which of these batches run")
     ap.add_argument("--records", action="store_true", help="the JSON call and the packed-records call side by side, --runs times each")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--format", default="plain", choices=["plain", "evm", "compressed", "all"], help="--records: the record layouts side by side")
+    ap.add_argument("--parent-lib", default=None, help="--records --format: another build of the library, its plain records call in the same turns")
     ap.add_argument("--offsub-size", type=int, default=12, help="--records: log2 size of the batch whose every pi_b is off the subgroup (0: skip)")
     a = ap.parse_args()
     import ultragroth_amd as ug
@@ -175,7 +234,10 @@ def main():
     say("# batch verification, Groth16, tests/golden/trapdoor/groth16 (%d distinct proofs repeated to fill N)" % len(pool))
     run(64, a.device)                                                  # warm-up: code objects, the context
     if a.records:
-        records_report(a, L, vk, pool, run, say)
+        if a.format != "plain" or a.parent_lib:
+            formats_report(a, L, vk, pool, say)
+        else:
+            records_report(a, L, vk, pool, run, say)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:

@@ -244,9 +244,42 @@ def inputs_unpack(block, n_pub=None):
     return out.value.decode()
 
 
-def _verify_batch_records(name, ultra, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min):
+# the record layouts of include/verifier.h (UG_RECORDS_*), described there
+RECORDS_PLAIN, RECORDS_EVM, RECORDS_COMPRESSED = 0, 1, 2
+
+
+def _record_bytes(ultra, format):
+    size = load().ug_proof_record_bytes(1 if ultra else 0, int(format))
+    if not size:
+        raise ValueError("format: not one of RECORDS_PLAIN, RECORDS_EVM, RECORDS_COMPRESSED")
+    return size
+
+
+def proof_record_convert(record, from_format, to_format, ultra=False):
+    """ug_proof_record_convert: one record from one layout to another, coordinates reduced mod q. ValueError when the source holds no
+    point to convert: a compressed x without a y on the curve, or a point off its curve on the way to RECORDS_COMPRESSED."""
+    if len(record) != _record_bytes(ultra, from_format):
+        raise ValueError("a record of this layout is %d bytes" % _record_bytes(ultra, from_format))
+    out = C.create_string_buffer(_record_bytes(ultra, to_format))
+    rc = load().ug_proof_record_convert(1 if ultra else 0, int(from_format), bytes(record), int(to_format), out)
+    if rc:
+        raise ValueError("the record holds a point that does not convert" if rc == 1 else "record does not convert")
+    return out.raw
+
+
+def inputs_convert(block, from_format, to_format):
+    """ug_inputs_convert: one proof's input block (n_pub x 32 bytes) from the byte order of one layout to that of another"""
+    if not block or len(block) % 32:
+        raise ValueError("an input block is n_pub x 32 bytes")
+    out = C.create_string_buffer(len(block))
+    if load().ug_inputs_convert(int(from_format), bytes(block), len(block) // 32, int(to_format), out) != 0:
+        raise ValueError("format: not one of RECORDS_PLAIN, RECORDS_EVM, RECORDS_COMPRESSED")
+    return out.raw
+
+
+def _verify_batch_records(name, ultra, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min, format=RECORDS_PLAIN):
     from ._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsEx
-    size = 320 if ultra else 256
+    size = _record_bytes(ultra, format)
     records, inputs = bytes(records), bytes(inputs)
     if len(records) % size:
         raise ValueError("records: a multiple of %d bytes" % size)
@@ -260,7 +293,11 @@ def _verify_batch_records(name, ultra, records, inputs, n_pub, verification_key,
         dflt = lambda v: -1 if v is None else int(v)
         opt = C.byref(VerifyBatchOptions(C.sizeof(VerifyBatchOptions), int(bool(judge)), dflt(search_width), dflt(judge_min)))
     stats = VerifyBatchStatsEx()
-    rc = getattr(load(), name)(device, n, records or b"\0", inputs or b"\0", n_pub, _enc_json(verification_key), verdicts, opt, C.byref(stats), err, 511)
+    if format == RECORDS_PLAIN:                                     # the existing symbol
+        rc = getattr(load(), name)(device, n, records or b"\0", inputs or b"\0", n_pub, _enc_json(verification_key), verdicts, opt, C.byref(stats), err, 511)
+    else:
+        rc = getattr(load(), name + "_fmt")(device, int(format), n, records or b"\0", inputs or b"\0", n_pub, _enc_json(verification_key), verdicts, opt,
+                                            C.byref(stats), err, 511)
     if rc == VERIFIER_ERROR:
         raise VerifierError(err.value.decode(errors="replace"))
     out = {f: getattr(stats.base, f) for f, _ in VerifyBatchStats._fields_}
@@ -268,16 +305,21 @@ def _verify_batch_records(name, ultra, records, inputs, n_pub, verification_key,
     return list(verdicts[:n]), out
 
 
-def groth16_verify_batch_records(records, inputs, n_pub, verification_key, device=0, judge=None, search_width=None, judge_min=None):
+def groth16_verify_batch_records(records, inputs, n_pub, verification_key, device=0, judge=None, search_width=None, judge_min=None,
+                                 format=RECORDS_PLAIN):
     """ug_groth16_verify_batch_records (include/verifier.h): as groth16_verify_batch for proofs held as packed records -- `records`
     count x 256 bytes (proof_pack), `inputs` count x n_pub x 32 bytes (inputs_pack). On a device the raw records are uploaded once
     and reduced, checked and converted there; device < 0 is the same protocol on host threads. Returns (verdicts, stats) with the
-    judge's counters always present; judge None takes it from the environment."""
-    return _verify_batch_records("ug_groth16_verify_batch_records", False, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min)
+    judge's counters always present; judge None takes it from the environment. format: the layout of `records` and the byte order of
+    `inputs`, RECORDS_PLAIN (the default), RECORDS_EVM or RECORDS_COMPRESSED (count x 128 bytes), as include/verifier.h describes them."""
+    return _verify_batch_records("ug_groth16_verify_batch_records", False, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min,
+                                 format)
 
 
-def ultra_groth_verify_batch_records(records, inputs, n_pub, verification_key, device=0, judge=None, search_width=None, judge_min=None):
-    return _verify_batch_records("ug_ultra_groth_verify_batch_records", True, records, inputs, n_pub, verification_key, device, judge, search_width, judge_min)
+def ultra_groth_verify_batch_records(records, inputs, n_pub, verification_key, device=0, judge=None, search_width=None, judge_min=None,
+                                     format=RECORDS_PLAIN):
+    return _verify_batch_records("ug_ultra_groth_verify_batch_records", True, records, inputs, n_pub, verification_key, device, judge, search_width,
+                                 judge_min, format)
 
 
 class _ProverBase:

@@ -40,7 +40,9 @@ VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/ver
                     "ug_test_verify_batch_trace", "ug_test_miller", "ug_test_final_exp",
                     "ug_groth16_verify_batch_records", "ug_ultra_groth_verify_batch_records",
                     "ug_proof_pack", "ug_inputs_pack", "ug_proof_unpack", "ug_inputs_unpack", "ug_test_verify_records_passes",
-                    "ug_verify_batch_phase_ms"]
+                    "ug_verify_batch_phase_ms",
+                    "ug_proof_record_bytes", "ug_groth16_verify_batch_records_fmt", "ug_ultra_groth_verify_batch_records_fmt",
+                    "ug_proof_record_convert", "ug_inputs_convert", "ug_test_records_ingest", "ug_test_fq2_sqrt"]
 
 
 class VerifyBatchStats(C.Structure):
@@ -232,6 +234,13 @@ def load():
         getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
     for n in ("ug_groth16_verify_batch_records", "ug_ultra_groth_verify_batch_records"):
         getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+    for n in ("ug_groth16_verify_batch_records_fmt", "ug_ultra_groth_verify_batch_records_fmt"):
+        getattr(L, n).argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+    L.ug_proof_record_bytes.argtypes = [C.c_int, C.c_int]; L.ug_proof_record_bytes.restype = C.c_ulong
+    L.ug_proof_record_convert.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp]
+    L.ug_inputs_convert.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp]
+    L.ug_test_records_ingest.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.ug_test_fq2_sqrt.argtypes = [C.c_int, C.c_int, vp, vp, vp]
     L.ug_proof_pack.argtypes = [C.c_int, C.c_char_p, vp]
     L.ug_inputs_pack.argtypes = [C.c_char_p, vp, C.c_int]
     L.ug_proof_unpack.argtypes = [C.c_int, vp, vp, C.c_ulong]

@@ -13,6 +13,10 @@
 // final_exp_kernel      one lane of the final exponentiation alone (ug_test_final_exp).
 // records_ingest_kernel the packed records of ug_*_verify_batch_records -> the arrays above, one record per lane: reduction mod q,
 // gather_rows_kernel    infinity flags, curve equations, limb form; the gather compacts the arrays when records were dropped.
+//                       The layout is a template parameter: plain little-endian coordinates or the big-endian EVM order.
+// records_decompress_kernel   the same arrays from compressed records (x and a sign bit per point): the lane takes the square
+//                       roots -- f1_sqrt / f2_sqrt of pairing.hpp, fixed-exponent powers -- and a point without one is off its curve.
+// fq2_sqrt_kernel       one lane per element of f2_sqrt alone (ug_test_fq2_sqrt).
 //
 // Registers: an Fq12 value is 108 words, a product holds three and a column sum. The coefficient loops of pairing.hpp are
 // kept as loops, so the values are indexed at run time and live in private (scratch) memory; the column products (81
@@ -112,15 +116,20 @@ __global__ UG_ONE_WAVE void final_exp_kernel(FinalExpConsts kc, const u32* __res
 //   bz            pi_b once more as a zkey record (Montgomery radix 2^256), what the subgroup ladder of check.hip reads; infinity
 //                 for a record that failed here, so that the ladder passes over it,
 //   status        UG_POINT_OK, or UG_POINT_OFF_CURVE when any of its points is off its curve.
-struct IngestConsts { F1 b1; F2 b2; };     // the curves' constant terms: 3 and 3 / (9 + u)
-
-__device__ __forceinline__ F1 ingest_coord(const u32* p) {
+// The EVM layout (FORMAT = RECORDS_EVM) differs in how a coordinate is loaded -- big-endian: the words in reverse order, each
+// byte-reversed -- and in where the halves of an Fq2 coordinate lie (the imaginary part first); IngestConsts are pairing.hpp's.
+template <int FORMAT> __device__ __forceinline__ F1 ingest_coord(const u32* p) {
     u32 w[8];
     load8(w, p);
+    if constexpr (FORMAT == RECORDS_EVM) {
+        u32 v[8];
+        for (int j = 0; j < 8; j++) v[j] = __builtin_bswap32(w[7 - j]);
+        return F1{canon(from_normal<FqParams>(v))};
+    }
     return F1{canon(from_normal<FqParams>(w))};
 }
-__device__ __forceinline__ bool ingest_g1(const u32* rec, const IngestConsts& c, u32* out) {
-    const F1 x = ingest_coord(rec), y = ingest_coord(rec + 8);
+template <int FORMAT> __device__ __forceinline__ bool ingest_g1(const u32* rec, const IngestConsts& c, u32* out) {
+    const F1 x = ingest_coord<FORMAT>(rec), y = ingest_coord<FORMAT>(rec + 8);
     if (is0(x) && is0(y)) {
         for (int j = 0; j < G1_WORDS; j++) out[j] = 0;
         return true;
@@ -129,15 +138,17 @@ __device__ __forceinline__ bool ingest_g1(const u32* rec, const IngestConsts& c,
     return y * y == x * x * x + c.b1;
 }
 
+template <int FORMAT>
 __global__ __launch_bounds__(64) void records_ingest_kernel(const u32* __restrict__ records, int n, int k, IngestConsts c, u32* __restrict__ a,
                                                             u32* __restrict__ b, u32* __restrict__ g, u32* __restrict__ bz,
                                                             uint8_t* __restrict__ status) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n) return;
     const u32* rec = records + i * (size_t)(48 + 16 * k);
-    bool ok = ingest_g1(rec, c, a + i * G1_WORDS);
-    for (int s = 0; s < k; s++) ok = ingest_g1(rec + 48 + 16 * s, c, g + (i * k + s) * G1_WORDS) && ok;
-    const F2 x{ingest_coord(rec + 16), ingest_coord(rec + 24)}, y{ingest_coord(rec + 32), ingest_coord(rec + 40)};
+    bool ok = ingest_g1<FORMAT>(rec, c, a + i * G1_WORDS);
+    for (int s = 0; s < k; s++) ok = ingest_g1<FORMAT>(rec + 48 + 16 * s, c, g + (i * k + s) * G1_WORDS) && ok;
+    constexpr int RE = FORMAT == RECORDS_EVM ? 8 : 0, IM = 8 - RE;  // where the real and the imaginary half of an Fq2 coordinate lie
+    const F2 x{ingest_coord<FORMAT>(rec + 16 + RE), ingest_coord<FORMAT>(rec + 16 + IM)}, y{ingest_coord<FORMAT>(rec + 32 + RE), ingest_coord<FORMAT>(rec + 32 + IM)};
     const bool inf = is0(x) && is0(y);
     u32* bo = b + i * G2_WORDS;
     if (inf) { for (int j = 0; j < G2_WORDS; j++) bo[j] = 0; }
@@ -150,6 +161,71 @@ __global__ __launch_bounds__(64) void records_ingest_kernel(const u32* __restric
     else { to_mont256(z, x.a.v); to_mont256(z + 8, x.b.v); to_mont256(z + 16, y.a.v); to_mont256(z + 24, y.b.v); }
     for (int j = 0; j < 4; j++) store8(bz + i * 32 + j * 8, z + j * 8);
     status[i] = ok ? (uint8_t)UG_POINT_OK : (uint8_t)UG_POINT_OFF_CURVE;
+}
+
+// Compressed records (include/verifier.h): a G1 point is x in 32 little-endian bytes, pi_b is x.c0 | x.c1, and the two top bits
+// of a point's last byte say "infinity" (0x40) and "y is the larger root" (0x80); 24 + 8 k words a record: pi_a | pi_b | the k
+// other G1 points. The mapping and the outputs are those of records_ingest_kernel. A point whose x^3 + b has no root is written
+// as zeros and makes the record UG_POINT_OFF_CURVE; a point that has one is on its curve by construction (root^2 is compared).
+// One copy of the Fq root serves pi_a and the k points (the loop is kept), pi_b has its own three inside f2_sqrt.
+__device__ __forceinline__ bool decompress_g1(const u32* rec, const DecompressConsts& c, u32* out) {
+    u32 w[8];
+    load8(w, rec);
+    const bool inf = (w[7] >> 30) & 1, larger = (w[7] >> 31) != 0;
+    w[7] &= 0x3fffffffu;
+    const F1 x{canon(from_normal<FqParams>(w))};
+    F1 y = f1_zero();
+    const bool ok = inf || g1_decompress(c, x, larger, y);
+    if (inf || !ok) { for (int j = 0; j < G1_WORDS; j++) out[j] = 0; }
+    else { fq_store(out, x.v); fq_store(out + NL, y.v); }
+    return ok;
+}
+
+__global__ __launch_bounds__(64) void records_decompress_kernel(const u32* __restrict__ records, int n, int k, DecompressConsts c,
+                                                                u32* __restrict__ a, u32* __restrict__ b, u32* __restrict__ g,
+                                                                u32* __restrict__ bz, uint8_t* __restrict__ status) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const u32* rec = records + i * (size_t)(24 + 8 * k);
+    bool ok = true;
+#pragma unroll 1
+    for (int s = 0; s <= k; s++)                                    // s = 0: pi_a, s >= 1: the other G1 points
+        ok = decompress_g1(s ? rec + 24 + 8 * (s - 1) : rec, c, s ? g + (i * k + (s - 1)) * G1_WORDS : a + i * G1_WORDS) && ok;
+    u32 w0[8], w1[8];
+    load8(w0, rec + 8);
+    load8(w1, rec + 16);
+    const bool inf = (w1[7] >> 30) & 1, larger = (w1[7] >> 31) != 0;
+    w1[7] &= 0x3fffffffu;
+    const F2 x{F1{canon(from_normal<FqParams>(w0))}, F1{canon(from_normal<FqParams>(w1))}};
+    F2 y = f2_zero();
+    const bool live = !inf && g2_decompress(c, x, larger, y);
+    ok = ok && (inf || live);
+    u32* bo = b + i * G2_WORDS;
+    if (!live) { for (int j = 0; j < G2_WORDS; j++) bo[j] = 0; }
+    else { fq_store(bo, x.a.v); fq_store(bo + NL, x.b.v); fq_store(bo + 2 * NL, y.a.v); fq_store(bo + 3 * NL, y.b.v); }
+    u32 z[32];
+    if (!live || !ok) { for (int j = 0; j < 32; j++) z[j] = 0; }
+    else { to_mont256(z, x.a.v); to_mont256(z + 8, x.b.v); to_mont256(z + 16, y.a.v); to_mont256(z + 24, y.b.v); }
+    for (int j = 0; j < 4; j++) store8(bz + i * 32 + j * 8, z + j * 8);
+    status[i] = ok ? (uint8_t)UG_POINT_OK : (uint8_t)UG_POINT_OFF_CURVE;
+}
+
+// in: n x 16 words, plain c0 | c1 (any 256-bit values); out: the root that is not the larger one, plain and canonical (zeros when
+// there is none); has_root: one byte each
+__global__ __launch_bounds__(64) void fq2_sqrt_kernel(DecompressConsts c, const u32* __restrict__ in, int n, u32* __restrict__ out,
+                                                      uint8_t* __restrict__ has_root) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const F2 v{ingest_coord<RECORDS_PLAIN>(in + i * 16), ingest_coord<RECORDS_PLAIN>(in + i * 16 + 8)};
+    F2 r;
+    const bool ok = f2_sqrt(c, v, r);
+    if (ok && f2_larger(c, r)) r = -r;
+    u32 w[16];
+    to_normal(w, r.a.v);
+    to_normal(w + 8, r.b.v);
+    store8(out + i * 16, w);
+    store8(out + i * 16 + 8, w + 8);
+    has_root[i] = ok ? 1 : 0;
 }
 
 // records were dropped: row t of dst = row index[t] of src (rows of `words` words), so that the Miller kernel sees a dense array
@@ -224,33 +300,49 @@ void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb)
 
 // ---- the resident form: the pass's raw records cross PCIe once and its arrays never leave the device ---------------------
 struct ResidentBatch::Impl {
-    int device, n, k;
+    int device, n, k, format;
     DevBuf records, a, b, g, bz, status;
-    Impl(int device_, int n_, int k_)
-        : device(device_), n(n_), k(k_), records((size_t)n_ * (48 + 16 * k_)), a((size_t)n_ * G1_WORDS), b((size_t)n_ * G2_WORDS),
+    Impl(int device_, int n_, int k_, int format_)
+        : device(device_), n(n_), k(k_), format(format_), records((size_t)n_ * record_words(k_, format_)), a((size_t)n_ * G1_WORDS), b((size_t)n_ * G2_WORDS),
           g((size_t)n_ * k_ * G1_WORDS), bz((size_t)n_ * 32), status(((size_t)n_ + 3) / 4 * 2) {}      // status: n bytes from each check
 };
-ResidentBatch::ResidentBatch(int device, int n, int k) {
+ResidentBatch::ResidentBatch(int device, int n, int k, int format) {
     if (n <= 0 || n > PAIRING_PASS || (k != 1 && k != 2)) throw std::invalid_argument("ResidentBatch: bad shape");
+    if (format != RECORDS_PLAIN && format != RECORDS_EVM && format != RECORDS_COMPRESSED) throw std::invalid_argument("ResidentBatch: unknown format");
     UG_HIP(hipSetDevice(device));
-    impl = new Impl(device, n, k);
+    impl = new Impl(device, n, k, format);
 }
 ResidentBatch::~ResidentBatch() { delete impl; }
 
 void ResidentBatch::ingest(const void* records, unsigned char* status) {
     Impl& m = *impl;
     UG_HIP(hipSetDevice(m.device));
-    static const IngestConsts c{f1_small(3), f2_scale(f2_inv(F2{f1_small(9), f1_small(1)}), f1_small(3))};
+    static const DecompressConsts c = decompress_consts();         // the plain and EVM kernels take its IngestConsts part
+    const IngestConsts& ci = c;
     const size_t n = (size_t)m.n, room = (n + 3) / 4 * 4;
     uint8_t* curve = reinterpret_cast<uint8_t*>(m.status.p);
     uint8_t* subgroup = curve + room;
-    UG_HIP(hipMemcpy(m.records.p, records, n * (48 + 16 * (size_t)m.k) * sizeof(u32), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(records_ingest_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, c, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+    UG_HIP(hipMemcpy(m.records.p, records, n * record_words(m.k, m.format) * sizeof(u32), hipMemcpyHostToDevice));
+    if (m.format == RECORDS_COMPRESSED)
+        hipLaunchKernelGGL(records_decompress_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, c, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+    else if (m.format == RECORDS_EVM)
+        hipLaunchKernelGGL(records_ingest_kernel<RECORDS_EVM>, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, ci, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+    else
+        hipLaunchKernelGGL(records_ingest_kernel<RECORDS_PLAIN>, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, ci, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
     UG_KERNEL_CHECK();
     check_points_mask(true, m.bz.p, n, 2, subgroup, nullptr);      // (a record that failed above is infinity here: it passes)
     std::vector<uint8_t> both(2 * room);
     UG_HIP(hipMemcpy(both.data(), curve, 2 * room, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) status[i] = both[i] ? both[i] : both[room + i];
+}
+
+void ResidentBatch::download(u32* a, u32* b, u32* g) {
+    Impl& m = *impl;
+    UG_HIP(hipSetDevice(m.device));
+    const size_t n = (size_t)m.n;
+    if (a) UG_HIP(hipMemcpy(a, m.a.p, n * G1_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    if (b) UG_HIP(hipMemcpy(b, m.b.p, n * G2_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    if (g) UG_HIP(hipMemcpy(g, m.g.p, n * (size_t)m.k * G1_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
 }
 
 void ResidentBatch::run(const PairingConsts& kc, const u32* keep, int kept, const u32* r, u32* f_tree, u32* g_tree, double kernel_ms[3]) {
@@ -310,6 +402,18 @@ void pairing_judge_device(int device, const FinalExpConsts& kc, PairingJudge& pj
     UG_HIP(hipEventElapsedTime(&ms[0], t0.e, t1.e));
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
     for (int i = 0; i < 2; i++) pj.kernel_ms[i] = ms[i];
+}
+
+void fq2_sqrt_device(int device, const DecompressConsts& c, int count, const u32* in, u32* out, unsigned char* has_root) {
+    if (count <= 0) return;
+    UG_HIP(hipSetDevice(device));
+    const size_t n = (size_t)count;
+    DevBuf din(n * 16), dout(n * 16), flag((n + 3) / 4);
+    UG_HIP(hipMemcpy(din.p, in, n * 16 * sizeof(u32), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(fq2_sqrt_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, c, din.p, count, dout.p, reinterpret_cast<uint8_t*>(flag.p));
+    UG_KERNEL_CHECK();
+    UG_HIP(hipMemcpy(out, dout.p, n * 16 * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(has_root, flag.p, n, hipMemcpyDeviceToHost));
 }
 
 void final_exp_device(int device, const FinalExpConsts& kc, const u32* f, u32* g, int* is_one) {

@@ -254,6 +254,78 @@ UG_HD bool final_exp_is_one(const FinalExpConsts& kc, const F12& f, F12& g) {
     return true;
 }
 
+// ---- square roots and point decompression (the compressed records of include/verifier.h) ----------------------------------
+// q = 3 mod 4, so a^((q + 1)/4) is a square root of a whenever a has one: a fixed-exponent power, squared once more to tell.
+// Over u^2 = -1 the complex method takes it from there: the norm's root s, then (a.c0 +- s)/2 -- one of the two is a square
+// when a is -- its root x0, and x1 = a.c1 / (2 x0). Every result is checked by squaring, and values are canonical, so the
+// device and the host return the same limbs. IngestConsts are the curves' constant terms, what the ingest of plain records
+// needs; DecompressConsts add 1/2, the exponent and the bound of the sign rule. Kernel arguments on the device, as PairingConsts.
+constexpr int ROOT_BITS = 252;                                      // (q + 1) / 4
+struct IngestConsts { F1 b1; F2 b2; };                              // 3 and 3 / (9 + u)
+struct DecompressConsts : IngestConsts {
+    F1 half;                                                        // 1 / 2
+    u32 root_exp[8];                                                // (q + 1) / 4, little-endian words
+    u32 half_q[8];                                                  // (q - 1) / 2: y is "the larger root" when y > (q - 1) / 2
+};
+// (host functions; plain inline so that the host code of pairing.hip may call them as well)
+inline IngestConsts ingest_consts() { return IngestConsts{f1_small(3), f2_scale(f2_inv(F2{f1_small(9), f1_small(1)}), f1_small(3))}; }
+inline DecompressConsts decompress_consts() {
+    static const u32 ROOT_EXPONENT[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
+    static const u32 HALF_Q[8] = {0x6c3e7ea3u, 0x9e10460bu, 0xb438e546u, 0xcbc0b548u, 0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};
+    DecompressConsts c;
+    static_cast<IngestConsts&>(c) = ingest_consts();
+    c.half = f1_inv(f1_small(2));
+    for (int i = 0; i < 8; i++) { c.root_exp[i] = ROOT_EXPONENT[i]; c.half_q[i] = HALF_Q[i]; }
+    return c;
+}
+// root = a^((q + 1)/4); true when that is a square root of a (a = 0: root 0)
+UG_HD bool f1_sqrt(const DecompressConsts& c, const F1& a, F1& root) {
+    F1 r = a;                                                       // bit ROOT_BITS - 1, the leading one
+#pragma unroll 1
+    for (int i = ROOT_BITS - 2; i >= 0; i--) {
+        r = r * r;
+        if ((c.root_exp[i >> 5] >> (i & 31)) & 1) r = r * a;
+    }
+    root = r;
+    return r * r == a;
+}
+// the sign rule of the compressed layout: y > -y as integers. Fq2 compares c1, and c0 when c1 is zero.
+UG_HD bool f1_larger(const DecompressConsts& c, const F1& y) {
+    u32 w[8];
+    to_normal(w, y.v);
+    for (int i = 7; i >= 0; i--) if (w[i] != c.half_q[i]) return w[i] > c.half_q[i];
+    return false;
+}
+UG_HD bool f2_larger(const DecompressConsts& c, const F2& y) { return is0(y.b) ? f1_larger(c, y.a) : f1_larger(c, y.b); }
+// a root of a in Fq2, or false when a is no square (root is then zero)
+UG_HD bool f2_sqrt(const DecompressConsts& c, const F2& a, F2& root) {
+    root = f2_zero();
+    F1 s, x0;
+    if (is0(a.b)) {                                                 // a in Fq: a real root, or an imaginary one since -1 is no square
+        if (f1_sqrt(c, a.a, s)) { root.a = s; return true; }
+        if (f1_sqrt(c, -a.a, s)) { root.b = s; return true; }
+        return false;
+    }
+    if (!f1_sqrt(c, a.a * a.a + a.b * a.b, s)) return false;        // the norm is no square in Fq: a is none in Fq2
+    if (!f1_sqrt(c, (a.a + s) * c.half, x0) && !f1_sqrt(c, (a.a - s) * c.half, x0)) return false;
+    if (is0(x0)) return false;                                      // (x0 = 0 needs a.c1 = 0, handled above: never divide by it)
+    const F2 r{x0, a.b * c.half * f1_inv(x0)};
+    if (!(r * r == a)) return false;
+    root = r;
+    return true;
+}
+// y of the curve point with this x whose sign is `larger`; false when x^3 + b has no root
+UG_HD bool g1_decompress(const DecompressConsts& c, const F1& x, bool larger, F1& y) {
+    if (!f1_sqrt(c, x * x * x + c.b1, y)) return false;
+    if (f1_larger(c, y) != larger) y = -y;
+    return true;
+}
+UG_HD bool g2_decompress(const DecompressConsts& c, const F2& x, bool larger, F2& y) {
+    if (!f2_sqrt(c, x * x * x + c.b2, y)) return false;
+    if (f2_larger(c, y) != larger) y = -y;
+    return true;
+}
+
 // ---- batch verification (verifier_api.cpp, pairing.hip) ----------------------------------------------------------------
 // Records in memory: an Fq value is its 9 limbs; a G1 point 18 words (x, y; canonical; all zero = infinity), a G2 point 36
 // (x.a, x.b, y.a, y.b), an XYZZ sum 36 (x, y, zz, zzz as ec.hpp leaves them), an Fq12 value 108.

@@ -472,6 +472,7 @@ struct BatchProof {
     G2A b;
     Inputs in;
     u32 challenge[8];
+    bool no_point = false;                 // a compressed record whose x has no y on the curve: INVALID like a point off its curve
 };
 enum State { DONE, SINGLE, BATCH };
 
@@ -661,7 +662,14 @@ void judge_suspects(const BatchKey& key, int device, const std::vector<const Bat
 
 // ---- packed proof records (include/verifier.h) --------------------------------------------------------------------------------
 // A record is the proof.json whose decimal strings are its integers; these are the two directions of that sentence.
-constexpr size_t record_bytes(bool ultra) { return ultra ? 320 : 256; }
+// The layouts (UG_RECORDS_*): plain little-endian coordinates, the big-endian EVM order with the imaginary half of an Fq2
+// coordinate first, and compressed -- x and two flag bits per point. Every layout is read into the same points and written from
+// them, so a conversion is a read and a write, and a record of any layout stands for the plain record it converts to.
+constexpr bool known_format(int format) { return format == RECORDS_PLAIN || format == RECORDS_EVM || format == RECORDS_COMPRESSED; }
+constexpr size_t record_bytes(bool ultra, int format = RECORDS_PLAIN) { return record_words(ultra ? 2 : 1, format) * sizeof(u32); }
+constexpr size_t g1_bytes(int format) { return format == RECORDS_COMPRESSED ? 32 : 64; }      // a G2 point takes twice that
+static_assert((int)UG_RECORDS_PLAIN == (int)RECORDS_PLAIN && (int)UG_RECORDS_EVM == (int)RECORDS_EVM && (int)UG_RECORDS_COMPRESSED == (int)RECORDS_COMPRESSED, "layouts");
+const DecompressConsts& root_consts() { static const DecompressConsts c = decompress_consts(); return c; }
 
 // decimal string -> 256-bit integer, little-endian; false for anything but digits and for a value >= 2^256
 bool u256_from_decimal(uint8_t out[32], const std::string& s) {
@@ -708,6 +716,114 @@ G2A g2_from_record(const uint8_t* p) {
     q.inf = is0(q.x) && is0(q.y);
     return q;
 }
+void reverse32(uint8_t* out, const uint8_t* in) { for (int i = 0; i < 32; i++) out[i] = in[31 - i]; }
+F1 f1_from_be256(const uint8_t* p) {
+    uint8_t le[32];
+    reverse32(le, p);
+    return f1_from_u256(le);
+}
+void f1_to_le256(uint8_t* p, const F1& a) {
+    u32 w[8];
+    f1_to_plain(w, a);
+    memcpy(p, w, 32);
+}
+void f1_to_be256(uint8_t* p, const F1& a) {
+    uint8_t le[32];
+    f1_to_le256(le, a);
+    reverse32(p, le);
+}
+// One point of a record in `format`. false: a compressed x without a y on the curve; the point is then left at infinity.
+bool g1_from_layout(int format, const uint8_t* p, G1A& out) {
+    if (format == RECORDS_PLAIN) { out = g1_from_record(p); return true; }
+    if (format == RECORDS_EVM) {
+        out = G1A{f1_from_be256(p), f1_from_be256(p + 32), false};
+        out.inf = is0(out.x) && is0(out.y);
+        return true;
+    }
+    uint8_t x[32];
+    memcpy(x, p, 32);
+    const bool inf = (x[31] & 0x40) != 0, larger = (x[31] & 0x80) != 0;
+    x[31] &= 0x3f;
+    out = G1A{f1_zero(), f1_zero(), true};
+    if (inf) return true;
+    const F1 xv = f1_from_u256(x);
+    F1 y;
+    if (!g1_decompress(root_consts(), xv, larger, y)) return false;
+    out = G1A{xv, y, false};
+    return true;
+}
+bool g2_from_layout(int format, const uint8_t* p, G2A& out) {
+    if (format == RECORDS_PLAIN) { out = g2_from_record(p); return true; }
+    if (format == RECORDS_EVM) {                                    // x.c1, x.c0, y.c1, y.c0
+        out = G2A{F2{f1_from_be256(p + 32), f1_from_be256(p)}, F2{f1_from_be256(p + 96), f1_from_be256(p + 64)}, false};
+        out.inf = is0(out.x) && is0(out.y);
+        return true;
+    }
+    uint8_t x1[32];
+    memcpy(x1, p + 32, 32);
+    const bool inf = (x1[31] & 0x40) != 0, larger = (x1[31] & 0x80) != 0;
+    x1[31] &= 0x3f;
+    out = g2_inf();
+    if (inf) return true;
+    const F2 xv{f1_from_u256(p), f1_from_u256(x1)};
+    F2 y;
+    if (!g2_decompress(root_consts(), xv, larger, y)) return false;
+    out = G2A{xv, y, false};
+    return true;
+}
+// ... and the way back, every coordinate reduced. false: a point off its curve has no compressed form (a sign bit cannot stand for it).
+bool g1_to_layout(int format, const G1A& pt, uint8_t* p) {
+    memset(p, 0, g1_bytes(format));
+    if (format == RECORDS_COMPRESSED) {
+        if (pt.inf) { p[31] = 0x40; return true; }
+        if (!g1_on_curve(pt)) return false;
+        f1_to_le256(p, pt.x);
+        if (f1_larger(root_consts(), pt.y)) p[31] |= 0x80;
+        return true;
+    }
+    if (pt.inf) return true;
+    if (format == RECORDS_EVM) { f1_to_be256(p, pt.x); f1_to_be256(p + 32, pt.y); }
+    else { f1_to_le256(p, pt.x); f1_to_le256(p + 32, pt.y); }
+    return true;
+}
+bool g2_to_layout(int format, const G2A& q, uint8_t* p) {
+    memset(p, 0, 2 * g1_bytes(format));
+    if (format == RECORDS_COMPRESSED) {
+        if (q.inf) { p[63] = 0x40; return true; }
+        if (!g2_on_curve(q)) return false;
+        f1_to_le256(p, q.x.a); f1_to_le256(p + 32, q.x.b);
+        if (f2_larger(root_consts(), q.y)) p[63] |= 0x80;
+        return true;
+    }
+    if (q.inf) return true;
+    if (format == RECORDS_EVM) { f1_to_be256(p, q.x.b); f1_to_be256(p + 32, q.x.a); f1_to_be256(p + 64, q.y.b); f1_to_be256(p + 96, q.y.a); }
+    else { f1_to_le256(p, q.x.a); f1_to_le256(p + 32, q.x.b); f1_to_le256(p + 64, q.y.a); f1_to_le256(p + 96, q.y.b); }
+    return true;
+}
+// a whole record: pi_a | pi_b | the one or two other G1 points. ok[0..3] say which of a, b, g[0], g[1] the record held.
+struct RecordPoints { G1A a, g[2]; G2A b; bool ok[4]; };
+bool record_read(int format, bool ultra, const uint8_t* rec, RecordPoints& pts) {
+    const size_t w = g1_bytes(format);
+    pts.g[1] = G1A{f1_zero(), f1_zero(), true};
+    pts.ok[0] = g1_from_layout(format, rec, pts.a);
+    pts.ok[1] = g2_from_layout(format, rec + w, pts.b);
+    pts.ok[2] = g1_from_layout(format, rec + 3 * w, pts.g[0]);
+    pts.ok[3] = !ultra || g1_from_layout(format, rec + 4 * w, pts.g[1]);
+    return pts.ok[0] && pts.ok[1] && pts.ok[2] && pts.ok[3];
+}
+bool record_write(int format, bool ultra, const RecordPoints& pts, uint8_t* rec) {
+    const size_t w = g1_bytes(format);
+    bool ok = g1_to_layout(format, pts.a, rec);
+    ok = g2_to_layout(format, pts.b, rec + w) && ok;
+    ok = g1_to_layout(format, pts.g[0], rec + 3 * w) && ok;
+    if (ultra) ok = g1_to_layout(format, pts.g[1], rec + 4 * w) && ok;
+    return ok;
+}
+// an input block of n_pub values in the byte order of `format` -> plain little-endian (EVM: every value byte-reversed)
+void inputs_to_plain(int format, const uint8_t* in, size_t n_pub, uint8_t* out) {
+    if (format != RECORDS_EVM) { memmove(out, in, n_pub * 32); return; }
+    for (size_t c = 0; c < n_pub; c++) { uint8_t t[32]; reverse32(t, in + c * 32); memcpy(out + c * 32, t, 32); }
+}
 std::string record_to_json(bool ultra, const uint8_t* rec) {
     auto g1 = [&](size_t at) { return "[\"" + u256_to_decimal(rec + at) + "\",\"" + u256_to_decimal(rec + at + 32) + "\",\"1\"]"; };
     std::string t = "{\"pi_a\":" + g1(0) + ",\"pi_b\":[[\"" + u256_to_decimal(rec + 64) + "\",\"" + u256_to_decimal(rec + 96) + "\"],[\"" +
@@ -731,6 +847,7 @@ struct Source {
     virtual void parse(size_t i, BatchProof& p, size_t ic_size, bool points) const = 0;
     virtual int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const = 0;
     virtual const uint8_t* raw() const { return nullptr; }          // packed records, for the device to ingest
+    virtual int raw_format() const { return RECORDS_PLAIN; }        // ... and their layout
     virtual size_t inputs_per_proof() const { return 0; }           // records: the call's n_pub, the same for every proof
 };
 struct JsonSource : Source {
@@ -751,22 +868,47 @@ struct RecordSource : Source {
     const uint8_t* records = nullptr;
     const uint8_t* inputs = nullptr;
     size_t n_pub = 0;
+    int format = RECORDS_PLAIN;
+    // points = false reads pi_r only (the challenge); not even that of a compressed record, whose pi_r the device's ingest leaves
     void parse(size_t i, BatchProof& p, size_t, bool points) const override {
-        const uint8_t* rec = records + i * record_bytes(ultra);
-        p.g[1] = ultra ? g1_from_record(rec + 256) : G1A{f1_zero(), f1_zero(), true};
-        if (points) { p.a = g1_from_record(rec); p.b = g2_from_record(rec + 64); p.g[0] = g1_from_record(rec + 192); }
+        const uint8_t* rec = records + i * record_bytes(ultra, format);
+        const size_t w = g1_bytes(format);
+        bool held = true;
+        p.g[1] = G1A{f1_zero(), f1_zero(), true};
+        if (ultra && (points || format != RECORDS_COMPRESSED)) held = g1_from_layout(format, rec + 4 * w, p.g[1]);
+        if (points) {
+            held = g1_from_layout(format, rec, p.a) && held;
+            held = g2_from_layout(format, rec + w, p.b) && held;
+            held = g1_from_layout(format, rec + 3 * w, p.g[0]) && held;
+        }
+        p.no_point = !held;
         p.in.plain.assign(n_pub, std::vector<u32>(8));
         for (size_t c = 0; c < n_pub; c++) {                        // reduced mod r, as fr_plain_from_decimal
-            u32 w[8];
-            memcpy(w, inputs + (i * n_pub + c) * 32, 32);
-            to_normal(p.in.plain[c].data(), from_normal<FrParams>(w));
+            uint8_t le[32];
+            inputs_to_plain(format, inputs + (i * n_pub + c) * 32, 1, le);
+            u32 v[8];
+            memcpy(v, le, 32);
+            to_normal(p.in.plain[c].data(), from_normal<FrParams>(v));
         }
     }
     int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const override {
-        const std::string proof = record_to_json(ultra, records + i * record_bytes(ultra)), in = inputs_to_json(inputs + i * n_pub * 32, n_pub);
+        const uint8_t* rec = records + i * record_bytes(ultra, format);
+        const uint8_t* block = inputs + i * n_pub * 32;
+        uint8_t plain[320];
+        std::vector<uint8_t> plain_in;
+        if (format != RECORDS_PLAIN) {                              // the plain record and block this one stands for
+            RecordPoints pts;
+            if (!record_read(format, ultra, rec, pts)) return VERIFIER_INVALID_PROOF;
+            record_write(RECORDS_PLAIN, ultra, pts, plain);
+            plain_in.resize(n_pub * 32);
+            inputs_to_plain(format, block, n_pub, plain_in.data());
+            rec = plain; block = plain_in.data();
+        }
+        const std::string proof = record_to_json(ultra, rec), in = inputs_to_json(block, n_pub);
         return (ultra ? ultra_groth_verify : groth16_verify)(proof.c_str(), in.c_str(), verification_key, msg, cap);
     }
     const uint8_t* raw() const override { return records; }
+    int raw_format() const override { return format; }
     size_t inputs_per_proof() const override { return n_pub; }
 };
 
@@ -857,7 +999,7 @@ int verify_batch(const Source& src, int device, int count, const char* verificat
             try {
                 BatchProof& p = parsed[i];
                 src.parse(i, p, key.ic.size(), true);
-                if (!g1_on_curve(p.a) || !g1_on_curve(p.g[0]) || !g1_on_curve(p.g[1]) || !g2_on_curve(p.b)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
+                if (p.no_point || !g1_on_curve(p.a) || !g1_on_curve(p.g[0]) || !g1_on_curve(p.g[1]) || !g2_on_curve(p.b)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
                 if (ultra) derive_challenge_plain(p.challenge, p.g[1]);
                 state[i] = BATCH;
             } catch (std::exception& e) { message[i] = e.what(); }
@@ -920,17 +1062,28 @@ int verify_batch(const Source& src, int device, int count, const char* verificat
         // batch (UltraGroth: pi_r, for the challenge). Off its curve: INVALID; pi_b off the subgroup: SINGLE, as in step 2.
         for (size_t first = 0; resident && first < n; first += PAIRING_PASS) {
             const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
-            const int k = key.k();
+            const int k = key.k(), format = src.raw_format();
+            const bool late_challenge = ultra && format == RECORDS_COMPRESSED;     // pi_r.y is the device's to find: no host root per proof
             parallel_for(m, [&](size_t i) {
                 BatchProof& p = parsed[first + i];
                 src.parse(first + i, p, key.ic.size(), false);
-                if (ultra) derive_challenge_plain(p.challenge, p.g[1]);
+                if (ultra && !late_challenge) derive_challenge_plain(p.challenge, p.g[1]);
             });
             lap(1);
             auto t0 = std::chrono::steady_clock::now();
-            ResidentBatch rb(device, (int)m, k);
+            ResidentBatch rb(device, (int)m, k, format);
             std::vector<uint8_t> status(m);
-            rb.ingest(src.raw() + first * record_bytes(ultra), status.data());
+            rb.ingest(src.raw() + first * record_bytes(ultra, format), status.data());
+            if (late_challenge) {                                   // the rows of pi_r as the ingest decompressed them
+                std::vector<u32> g(m * (size_t)k * G1_WORDS);
+                rb.download(nullptr, nullptr, g.data());
+                parallel_for(m, [&](size_t i) {
+                    if (status[i] == UG_POINT_OFF_CURVE) return;
+                    BatchProof& p = parsed[first + i];
+                    p.g[1] = g1_load(&g[(i * k + 1) * G1_WORDS], false);
+                    derive_challenge_plain(p.challenge, p.g[1]);
+                });
+            }
             stats.device_ms += ms_since(t0);
             std::vector<size_t> kept;
             std::vector<u32> keep;
@@ -1045,15 +1198,17 @@ static int verify_batch_opt(bool ultra, int device, int count, const char* const
     if (!read_options(opt, options, error_msg, error_msg_maxsize)) return VERIFIER_ERROR;
     return verify_batch_json(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
 }
-static int verify_batch_records(bool ultra, int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
-                                int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
-                                unsigned long error_msg_maxsize) {
+static int verify_batch_records(bool ultra, int device, int format, int count, const void* records, const void* inputs, int n_pub,
+                                const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
+                                ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
     BatchOptions opt;
     if (!read_options(opt, options, error_msg, error_msg_maxsize)) return VERIFIER_ERROR;
+    if (!known_format(format)) { copy_error(error_msg, error_msg_maxsize, "format: not one of UG_RECORDS_PLAIN, UG_RECORDS_EVM, UG_RECORDS_COMPRESSED"); return VERIFIER_ERROR; }
     if (count < 0 || !verification_key || (count > 0 && (!records || !inputs || !verdicts))) { copy_error(error_msg, error_msg_maxsize, "null argument"); return VERIFIER_ERROR; }
     if (n_pub <= 0) { copy_error(error_msg, error_msg_maxsize, "invalid inputs data"); return VERIFIER_ERROR; }
     RecordSource src;
     src.ultra = ultra; src.records = static_cast<const uint8_t*>(records); src.inputs = static_cast<const uint8_t*>(inputs); src.n_pub = (size_t)n_pub;
+    src.format = format;
     return verify_batch(src, device, count, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
 }
 
@@ -1079,12 +1234,42 @@ int ug_ultra_groth_verify_batch_opt(int device, int count, const char* const* pr
 int ug_groth16_verify_batch_records(int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
                                     int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
                                     unsigned long error_msg_maxsize) {
-    return verify_batch_records(false, device, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return verify_batch_records(false, device, RECORDS_PLAIN, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
 }
 int ug_ultra_groth_verify_batch_records(int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
                                         int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
                                         unsigned long error_msg_maxsize) {
-    return verify_batch_records(true, device, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return verify_batch_records(true, device, RECORDS_PLAIN, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_groth16_verify_batch_records_fmt(int device, int format, int count, const void* records, const void* inputs, int n_pub,
+                                        const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
+                                        ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    return verify_batch_records(false, device, format, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_ultra_groth_verify_batch_records_fmt(int device, int format, int count, const void* records, const void* inputs, int n_pub,
+                                            const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
+                                            ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    return verify_batch_records(true, device, format, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+
+unsigned long ug_proof_record_bytes(int ultra, int format) { return known_format(format) ? (unsigned long)record_bytes(ultra != 0, format) : 0; }
+int ug_proof_record_convert(int ultra, int from_format, const void* from, int to_format, void* to) {
+    if (!from || !to || !known_format(from_format) || !known_format(to_format)) return 2;
+    try {
+        RecordPoints pts;
+        uint8_t out[320];
+        if (!record_read(from_format, ultra != 0, static_cast<const uint8_t*>(from), pts)) return 1;
+        if (!record_write(to_format, ultra != 0, pts, out)) return 1;
+        memcpy(to, out, record_bytes(ultra != 0, to_format));
+        return 0;
+    } catch (...) { return 2; }
+}
+int ug_inputs_convert(int from_format, const void* from, int n_pub, int to_format, void* to) {
+    if (!from || !to || n_pub <= 0 || !known_format(from_format) || !known_format(to_format)) return 2;
+    // one byte order to the other, or a copy: the block of a compressed record is the plain one
+    inputs_to_plain((from_format == RECORDS_EVM) != (to_format == RECORDS_EVM) ? RECORDS_EVM : RECORDS_PLAIN,
+                    static_cast<const uint8_t*>(from), (size_t)n_pub, static_cast<uint8_t*>(to));
+    return 0;
 }
 
 int ug_proof_pack(int ultra, const char* proof_json, void* record) {
@@ -1139,6 +1324,78 @@ int ug_test_verify_records_passes(unsigned long long passes[2]) {
     std::lock_guard<std::mutex> lock(g_trace.m);
     passes[0] = g_trace.in_place; passes[1] = g_trace.gathered;
     return 0;
+}
+
+// ULTRAGROTH_TEST_HOOKS=1 only: upload and ingest alone. plain_out: per record the plain 256 / 320 bytes the arrays hold after the
+// ingest -- coordinates reduced, infinity and a point that failed (no root, off its curve) as zeros; status: ResidentBatch::ingest's
+// byte. device < 0: the host's reading of the same records.
+int ug_test_records_ingest(int device, int format, int ultra_, int count, const void* records, void* plain_out, unsigned char* status) {
+    if (!ughost::testHooksEnabled() || !records || !plain_out || !status || count < 0 || !known_format(format)) return 1;
+    try {
+        const bool ultra = ultra_ != 0;
+        const int k = ultra ? 2 : 1;
+        const uint8_t* rec = static_cast<const uint8_t*>(records);
+        uint8_t* out = static_cast<uint8_t*>(plain_out);
+        const size_t stride = record_bytes(ultra, format), plain = record_bytes(ultra);
+        auto leave = [&](size_t i, RecordPoints& pts) {            // what failed is zeros
+            if (!g1_on_curve(pts.a)) pts.a = G1A{f1_zero(), f1_zero(), true};
+            if (!g2_on_curve(pts.b)) pts.b = g2_inf();
+            for (int s = 0; s < 2; s++) if (!g1_on_curve(pts.g[s])) pts.g[s] = G1A{f1_zero(), f1_zero(), true};
+            record_write(RECORDS_PLAIN, ultra, pts, out + i * plain);
+        };
+        for (size_t first = 0; first < (size_t)count; first += PAIRING_PASS) {
+            const size_t m = std::min<size_t>(PAIRING_PASS, (size_t)count - first);
+            if (device < 0) {
+                parallel_for(m, [&](size_t j) {
+                    const size_t i = first + j;
+                    RecordPoints pts;
+                    bool ok = record_read(format, ultra, rec + i * stride, pts);
+                    ok = ok && g1_on_curve(pts.a) && g2_on_curve(pts.b) && g1_on_curve(pts.g[0]) && g1_on_curve(pts.g[1]);
+                    status[i] = !ok ? UG_POINT_OFF_CURVE : g2_in_subgroup(pts.b) ? UG_POINT_OK : UG_POINT_OFF_SUBGROUP;
+                    leave(i, pts);
+                });
+                continue;
+            }
+            ResidentBatch rb(device, (int)m, k, format);
+            rb.ingest(rec + first * stride, status + first);
+            std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * (size_t)k * G1_WORDS);
+            rb.download(a.data(), b.data(), g.data());
+            parallel_for(m, [&](size_t j) {
+                RecordPoints pts;
+                pts.a = g1_load(&a[j * G1_WORDS], false);
+                pts.b = g2_load(&b[j * G2_WORDS]);
+                pts.g[0] = g1_load(&g[j * k * G1_WORDS], false);
+                pts.g[1] = ultra ? g1_load(&g[(j * k + 1) * G1_WORDS], false) : G1A{f1_zero(), f1_zero(), true};
+                leave(first + j, pts);
+            });
+        }
+        return 0;
+    } catch (...) { return 1; }
+}
+// ULTRAGROTH_TEST_HOOKS=1 only: f2_sqrt of count values given as plain c0 | c1 (64 bytes each). out: the root that is NOT the larger
+// one, in the same form (zeros when there is none); has_root: one byte each. device < 0: the host's code.
+int ug_test_fq2_sqrt(int device, int count, const void* in, void* out, unsigned char* has_root) {
+    if (!ughost::testHooksEnabled() || !in || !out || !has_root || count < 0) return 1;
+    try {
+        if (device >= 0) {
+            std::vector<u32> wi((size_t)count * 16), wo((size_t)count * 16);
+            memcpy(wi.data(), in, wi.size() * sizeof(u32));
+            fq2_sqrt_device(device, root_consts(), count, wi.data(), wo.data(), has_root);
+            memcpy(out, wo.data(), wo.size() * sizeof(u32));
+            return 0;
+        }
+        const uint8_t* p = static_cast<const uint8_t*>(in);
+        uint8_t* o = static_cast<uint8_t*>(out);
+        for (size_t i = 0; i < (size_t)count; i++) {
+            const F2 v{f1_from_u256(p + i * 64), f1_from_u256(p + i * 64 + 32)};
+            F2 r;
+            const bool ok = f2_sqrt(root_consts(), v, r);
+            if (ok && f2_larger(root_consts(), r)) r = -r;
+            f1_to_le256(o + i * 64, r.a); f1_to_le256(o + i * 64 + 32, r.b);
+            has_root[i] = ok ? 1 : 0;
+        }
+        return 0;
+    } catch (...) { return 1; }
 }
 
 void ug_verify_batch_phase_ms(double ms[8]) {
