@@ -141,6 +141,37 @@ typedef struct { int section; unsigned long long index; int reason; } ug_zkey_fa
 int ug_zkey_check(const void *zkey_buffer, unsigned long long zkey_size, int device, int level, ug_zkey_fault *fault,
                   char *error_msg, unsigned long long error_msg_maxsize);
 
+/* REFUSING A BAD WITNESS. The zkey cannot say whether a witness satisfies the circuit (its section 4 holds the A and B matrices only);
+ * the circuit's .r1cs can (layout and rules: include/ultragroth_hip.h, "WITNESS CHECK"). ug_witness_check is the stand-alone form,
+ * like ug_zkey_check: it makes a context of its own and keeps nothing.
+ *   PROVER_OK                       every constraint holds
+ *   PROVER_ERROR                    "witness: constraint <k> does not hold (<n> of <m> fail)", k the lowest failing constraint, and
+ *                                   *fault = the count, k, and the values A.w, B.w, C.w of constraint k (plain little-endian, mod r)
+ *   PROVER_INVALID_WITNESS_LENGTH   the .wtns holds another count than nWires
+ *   PROVER_ERROR                    with the loaders' messages and fault->failed = 0 for a file that does not parse
+ * device < 0 runs the same check on host threads (no GPU needed); device and host agree on failed, first, a, b, c. */
+typedef struct { unsigned long long failed, first; unsigned char a[32], b[32], c[32]; } ug_witness_fault;
+int ug_witness_check(const void *r1cs, unsigned long long r1cs_size, const void *wtns, unsigned long long wtns_size,
+                     int device, ug_witness_fault *fault, char *error_msg, unsigned long long error_msg_maxsize);
+/* ug_prover_attach_r1cs gives a created prover its circuit's .r1cs (size = 0 detaches); from then on EVERY proof call of the handle
+ * checks its witness on the device -- prove, prove_resident, run, prove_batch (one check per witness) -- beside the proof's own
+ * kernels, its result read where the call waits for the device anyway: a good witness costs no extra host wait. A witness that
+ * breaks a constraint fails the call with PROVER_ERROR and the message above (a batch prefixes "witness <b>: "); no proof or
+ * public buffer is written and the prover stays usable. Groth16 queues the check once the witness is resident, UltraGroth after
+ * the lookup completion and before the final round (its batched call proves one witness after the other while attached). Under
+ * ULTRAGROTH_GRAPH=1 the check is queued eagerly, outside the recorded sequence. The phase calls that make a proof in pieces
+ * (run_witness_msm, witness_msm_begin, run_h_msm, hpoly_chain, hpoly_combine) are refused while an .r1cs is attached.
+ * Supported on a created, unsharded, one-device Groth16 or UltraGroth prover. It fails, and nothing is attached, for:
+ *   "r1cs: not this circuit: <which>"   nWires != nVars, nPubOut + nPubIn != nPublic, nConstraints + nPublic + 1 > domainSize
+ *   "r1cs: not this circuit: matrix <A|B> row <k> differs from the zkey"   the probe of ug_r1cs_match_hpoly (C is not in a zkey:
+ *                                        an .r1cs with a wrong C cannot be told apart here)
+ *   "witness check: not available on this kind of prover"   a sharded, ULTRAGROTH_DEVICES or registry handle
+ * ULTRAGROTH_R1CS=<path> attaches that file in every creation of a supported prover, the CLIs and the one-shot calls included; an
+ * unreadable or mismatching file, or a kind of prover that cannot check, fails the creation. Unset, nothing changes.
+ * Known follow-up, not done: an attached prover computes A.w and B.w twice, here and in the H block. */
+int ug_prover_attach_r1cs(void *prover_object, const void *r1cs, unsigned long long size, char *error_msg,
+                          unsigned long long error_msg_maxsize);
+
 /* BATCHED PROOFS: `count` witnesses (wtns / uwtns file buffers) proved in one call; proof_buffers[b] / public_buffers[b] receive
  * what groth16_prover_prove (ultra_groth_prover_prove for an UltraGroth handle) returns for witness b, byte for byte, sized as
  * there (proof_sizes[b], public_sizes[b]). A bad witness fails the whole call with the code and message the single prove gives

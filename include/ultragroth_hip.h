@@ -36,6 +36,10 @@
  *                                                 never (default) | 1 field range and curve equation | 2 also the G2 points'
  *                                                 membership of the order-r subgroup (include/prover.h: a bad key is refused)
  *                                                 (any other value fails the creation)
+ *                      ULTRAGROTH_R1CS=<path>     every prover made by the reference's create calls attaches that .r1cs and checks the
+ *                                                 witness of every proof against it (include/prover.h: ug_prover_attach_r1cs); an
+ *                                                 unreadable or mismatching file, or a prover that cannot check, fails the creation
+ *                                                 (unset / empty: nothing changes)
  *                      ULTRAGROTH_VERIFY_JUDGE=0|1  ug_groth16_verify_batch / ug_ultra_groth_verify_batch: 1 = the suspects of a rejected
  *                                                 batch are decided by their own equations on the device (include/verifier.h, the
  *                                                 judge; the same verdicts) | 0 / unset: searched and verified on the host (default)
@@ -425,6 +429,57 @@ int  ug_hpoly_combine(ug_hpoly* hp, const ug_dvec* a, const ug_dvec* b, const ug
 /* optional: also return the three coset evaluation vectors (reference Montgomery form), for tests */
 int  ug_hpoly_debug_abc(ug_hpoly* hp, void* host_a, void* host_b, void* host_c);
 void ug_hpoly_destroy(ug_hpoly* hp);
+
+/* WITNESS CHECK AGAINST THE CIRCUIT'S .r1cs (r1cs.hip; no reference counterpart: the reference proves whatever witness it is
+ * given, and the host tool for the question, `snarkjs wtns check`, takes minutes at the sizes this prover is used for).
+ * A zkey's section 4 holds the A and B matrices only -- the prover sets c = a o b itself --, so the C matrix comes from the .r1cs.
+ *
+ * THE FILE LAYOUT read here. No .r1cs from a real compiler was at hand when this was written: the layout is pinned by this
+ * restatement only, and the parser (host_util.cpp) and the test writer (ultragroth_amd/synth.py: r1cs_file) are both written from it.
+ * The iden3 binfile container (magic[4] | u32 version | u32 nSections | { u32 id, u64 size, bytes }*) with magic "r1cs", version 1:
+ *   section 1 (header)       u32 n8 (must be 32) | prime[n8] little-endian (must be the BN254 scalar modulus r) | u32 nWires |
+ *                            u32 nPubOut | u32 nPubIn | u32 nPrvIn | u64 nLabels | u32 nConstraints
+ *   section 2 (constraints)  nConstraints records, each three linear combinations A, B, C; a linear combination is u32 nTerms and
+ *                            nTerms x (u32 wire | coef[n8]); coef is a PLAIN little-endian integer (not Montgomery). The constraint
+ *                            holds when (A.w)(B.w) = C.w mod r. nTerms = 0 is the value 0; a wire may repeat inside a combination
+ *                            (the terms add).
+ *   section 3 (wire -> label, nWires x u64) is not read; any other section id (custom gates) is ignored; sections are found by id,
+ *   their order in the file does not matter.
+ * A call fails, the message prefixed "r1cs: ", for: a missing or short section 1 or 2; n8 != 32; another prime ("not over the BN254
+ * scalar field"); wire >= nWires ("constraint <k>: wire <id> out of range"); a coefficient >= r ("constraint <k>: coefficient not
+ * below the field modulus"); a record that runs past the section; trailing bytes in section 2; nWires == 0; more than 2^32 - 1 terms
+ * in one matrix (the offsets are u32, as in the zkey's coefficient matrix).
+ *
+ * ug_r1cs: the three matrices resident in HBM as CSR triples. The check runs one lane per constraint; the witness is plain 32-byte
+ * integers, ANY value below 2^256, taken mod r by the products exactly as the prover takes it (the H block's rule); both sides of
+ * the comparison are fully reduced first. report: failed = constraints that do not hold, first = the lowest of them, a / b / c = the
+ * values A.w, B.w, C.w of constraint `first` (plain little-endian, mod r; filled only when failed > 0), device_ms = the check
+ * kernel's time (ug_r1cs_check only).
+ * ug_r1cs_match_hpoly answers whether the .r1cs is the circuit a zkey was made for, by probing both with one vector z of nWires
+ * random field elements: A_zkey.z = A_r1cs.z and B_zkey.z = B_r1cs.z on every row below nConstraints; rows nConstraints + s,
+ * 0 <= s <= n_public, of the zkey's A evaluate to z[s] (snarkjs' public rows); every other row of the zkey's A and B is empty.
+ * *matrix = -1: they match; else the lowest differing row and, on that row, the first differing matrix (0 = A, 1 = B). Two
+ * different rows agree on a random z with probability about 1/r. C IS NOT IN A ZKEY: an .r1cs with a wrong C matches all the same.
+ * Sizes that cannot belong together (nWires != the zkey's nVars, nConstraints + n_public + 1 > domain) fail the call with
+ * "r1cs: not this circuit: ...". */
+typedef struct ug_r1cs ug_r1cs;
+typedef struct { uint32_t n_wires, n_pub_out, n_pub_in, n_prv_in, n_constraints; uint64_t n_labels, terms[3]; } ug_r1cs_info;
+typedef struct { uint64_t failed, first; uint8_t a[32], b[32], c[32]; double device_ms; } ug_r1cs_report;
+int  ug_r1cs_parse_info(const void* r1cs, uint64_t size, ug_r1cs_info* out);       /* host only, no device */
+/* parses (every rule above, before the first device byte), uploads through the context's staging and converts the coefficients;
+ * a failed create leaves no device memory behind */
+int  ug_r1cs_create(ug_ctx* ctx, const void* r1cs, uint64_t size, ug_r1cs** out);
+int  ug_r1cs_get_info(const ug_r1cs* r, ug_r1cs_info* out);
+/* witness[first, first + n_wires) (a shorter vector: UG_ERROR); mask: n_constraints host bytes (0 holds, 1 fails) or NULL.
+ * One launch, one host wait (a failing witness: one more one-lane launch for a, b, c). */
+int  ug_r1cs_check(ug_r1cs* r, const ug_dvec* witness, uint64_t first, ug_r1cs_report* out, uint8_t* mask);
+/* queue only, no host wait: the result words stay on their way until ug_r1cs_check_collect, which waits for this slot's check
+ * alone; may be queued on `via`'s stream (NULL: the object's context). The witness must stay as it is until the collect.
+ * Slots 0 .. UG_BATCH_MAX - 1; never on a stream that is being recorded (ug_graph_begin). */
+int  ug_r1cs_check_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, int slot, ug_ctx* via);
+int  ug_r1cs_check_collect(ug_r1cs* r, int slot, ug_r1cs_report* out);
+int  ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* matrix, uint64_t* row);
+void ug_r1cs_destroy(ug_r1cs* r);
 
 /* In-place size-2^logn transform of a host buffer of Montgomery Fr elements, natural order in and out.
  * inverse != 0 also scales by 1/n. */

@@ -126,6 +126,53 @@ def zkey_check(zkey, level=2, device=0):
 
 
 # ---------------------------------------------------------------------------------------------------
+# witness check against the circuit's .r1cs (include/prover.h: ug_witness_check; include/ultragroth_hip.h: ug_r1cs_*)
+class _WitnessFault(C.Structure):
+    _fields_ = [("failed", C.c_ulonglong), ("first", C.c_ulonglong), ("a", C.c_ubyte * 32), ("b", C.c_ubyte * 32), ("c", C.c_ubyte * 32)]
+
+
+class _R1csInfo(C.Structure):
+    _fields_ = [("n_wires", C.c_uint32), ("n_pub_out", C.c_uint32), ("n_pub_in", C.c_uint32), ("n_prv_in", C.c_uint32),
+                ("n_constraints", C.c_uint32), ("n_labels", C.c_uint64), ("terms", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {"n_wires": self.n_wires, "n_pub_out": self.n_pub_out, "n_pub_in": self.n_pub_in, "n_prv_in": self.n_prv_in,
+                "n_constraints": self.n_constraints, "n_labels": self.n_labels, "terms": tuple(self.terms)}
+
+
+class _R1csReport(C.Structure):
+    _fields_ = [("failed", C.c_uint64), ("first", C.c_uint64), ("a", C.c_ubyte * 32), ("b", C.c_ubyte * 32), ("c", C.c_ubyte * 32),
+                ("device_ms", C.c_double)]
+
+
+def _le(arr):
+    return int.from_bytes(bytes(arr), "little")
+
+
+def witness_check(r1cs, wtns, device=0):
+    """ug_witness_check: None for a witness that satisfies every constraint of the .r1cs, else (failed, first, a, b, c, message) --
+    the count of failing constraints, the lowest of them and its values A.w, B.w, C.w as integers mod r. device=-1 runs the check
+    on host threads (no GPU). A file that does not parse raises ProverError with the loaders' message."""
+    fault = _WitnessFault()
+    err = C.create_string_buffer(1024)
+    rc = load().ug_witness_check(r1cs, len(r1cs), wtns, len(wtns), device, C.byref(fault), err, len(err) - 1)
+    if rc == PROVER_OK:
+        return None
+    msg = err.value.decode(errors="replace")
+    if fault.failed == 0:
+        raise ProverError(rc, msg)
+    return fault.failed, fault.first, _le(fault.a), _le(fault.b), _le(fault.c), msg
+
+
+def r1cs_info(r1cs):
+    """ug_r1cs_parse_info (host only): the header fields and the term counts of A, B, C as a dict; DeviceError for a file that
+    breaks a rule of the layout"""
+    info = _R1csInfo()
+    _check(load().ug_r1cs_parse_info(r1cs, len(r1cs), C.byref(info)))
+    return info.as_dict()
+
+
+# ---------------------------------------------------------------------------------------------------
 # verifier mirror (src/verifier.h)
 VERIFIER_VALID_PROOF, VERIFIER_INVALID_PROOF, VERIFIER_ERROR = 0, 1, 2
 
@@ -408,6 +455,16 @@ class _ProverBase:
         if rc != PROVER_OK:
             raise ProverError(rc, err.value.decode(errors="replace"))
         return proof.raw.split(b"\0", 1)[0].decode(), pub.raw.split(b"\0", 1)[0].decode()
+
+    def attach_r1cs(self, r1cs):
+        """ug_prover_attach_r1cs: from now on every proof of this prover checks its witness against the circuit's .r1cs and fails
+        with "witness: constraint <k> does not hold (<n> of <m> fail)" when it breaks one; None detaches. ProverError when the
+        file is not this zkey's circuit or the prover is of a kind that cannot check (nothing is attached then)."""
+        err = C.create_string_buffer(1024)
+        data = bytes(r1cs) if r1cs else None
+        rc = load().ug_prover_attach_r1cs(self._h, data, len(data) if data else 0, err, len(err) - 1)
+        if rc != PROVER_OK:
+            raise ProverError(rc, err.value.decode(errors="replace"))
 
     def last_timings(self):
         """(msm_ms, fft_ms, total_ms) of the last prove: device time of the MSM and H-polynomial parts, host wall time."""
@@ -1134,6 +1191,12 @@ class Device:
         _check(self._L.ug_hpoly_create(self._h, coefs, ncoefs, domain, nvars, C.byref(h)))
         return _HPoly(h, self, domain)
 
+    def r1cs(self, data):
+        """ug_r1cs_create: the three matrices of an .r1cs resident on this device"""
+        h = C.c_void_p()
+        _check(self._L.ug_r1cs_create(self._h, data, len(data), C.byref(h)))
+        return _R1cs(h, self)
+
     def timings(self, reset=False):
         a, b = C.c_double(), C.c_double()
         _check(self._L.ug_ctx_timings(self._h, C.byref(a), C.byref(b), 1 if reset else 0))
@@ -1195,6 +1258,41 @@ class _HPoly(_Handle):
 
 
 HPoly = _HPoly
+
+
+class _R1cs(_Handle):
+    def __init__(self, h, dev):
+        super().__init__(h, dev._L.ug_r1cs_destroy, dev)
+        self.dev = dev
+
+    def info(self):
+        info = _R1csInfo()
+        _check(self.dev._L.ug_r1cs_get_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def check(self, dvec, first=0, want_mask=False):
+        """ug_r1cs_check of the witness at elements [first, first + n_wires) of a device vector: a dict with failed, first, a, b, c
+        (integers; a, b, c None when nothing fails), device_ms, and mask (bytes, one per constraint: 0 holds, 1 fails) if asked for"""
+        rep = _R1csReport()
+        mask = C.create_string_buffer(max(1, self.info()["n_constraints"])) if want_mask else None
+        _check(self.dev._L.ug_r1cs_check(self.h, dvec.h, first, C.byref(rep), mask))
+        out = {"failed": rep.failed, "first": rep.first if rep.failed else None, "device_ms": rep.device_ms,
+               "a": _le(rep.a) if rep.failed else None, "b": _le(rep.b) if rep.failed else None, "c": _le(rep.c) if rep.failed else None}
+        if want_mask:
+            out["mask"] = mask.raw[:self.info()["n_constraints"]]
+        return out
+
+    def match(self, hpoly, n_public):
+        """ug_r1cs_match_hpoly: None when the .r1cs is the circuit of the zkey whose coefficient matrix `hpoly` holds, else
+        (matrix, row) of the lowest differing row (matrix 0 = A, 1 = B)"""
+        m, row = C.c_int(), C.c_uint64()
+        _check(self.dev._L.ug_r1cs_match_hpoly(self.h, hpoly.h, n_public, C.byref(m), C.byref(row)))
+        return None if m.value < 0 else (m.value, row.value)
+
+    def close(self):
+        if self.h:
+            self._destroy(self.h)
+            self.h = None
 
 
 def hpoly_vectors_bytes(domain, group):

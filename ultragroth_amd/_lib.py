@@ -32,6 +32,8 @@ INNER_SYMBOLS = [
     "ug_bases_precompute_strided", "ug_schedule_build_tables_strided", "ug_bases_tables_bytes_strided", "ug_bases_table_stride",
     "ug_plan_window_tables", "ug_schedule_build_vectors", "ug_dvec_gather_index_at", "ug_plan_proof_batch",
     "ug_plan_proof_batch_aux", "ug_fr_lookup_tables", "ug_dvec_apply_lookup_vectors", "ug_dvec_complete_lookup_vectors",
+    "ug_r1cs_parse_info", "ug_r1cs_create", "ug_r1cs_get_info", "ug_r1cs_check", "ug_r1cs_check_enqueue", "ug_r1cs_check_collect",
+    "ug_r1cs_match_hpoly", "ug_r1cs_destroy",
     "ug_lookup_vectors_bytes", "ug_points_check", "ug_points_check_mask", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/verifier.h
@@ -84,7 +86,7 @@ OUTER_SYMBOLS = [
     "ug_groth16_prover_run_witness_msm", "ug_groth16_prover_run_h_msm", "ug_groth16_prover_hpoly_chain",
     "ug_groth16_prover_hpoly_combine", "ug_groth16_prover_h_range",
     "ug_groth16_prover_witness_msm_begin", "ug_groth16_prover_witness_msm_end",
-    "ug_groth16_prover_prove_batch", "ug_zkey_check",
+    "ug_groth16_prover_prove_batch", "ug_zkey_check", "ug_witness_check", "ug_prover_attach_r1cs",
 ]
 
 
@@ -221,6 +223,16 @@ def load():
     L.ug_hpoly_combine.argtypes = [vp, vp, vp, vp, u64, u64, vp]
     L.ug_hpoly_debug_abc.argtypes = [vp, vp, vp, vp]
     L.ug_hpoly_destroy.argtypes = [vp]; L.ug_hpoly_destroy.restype = None
+    L.ug_r1cs_parse_info.argtypes = [vp, u64, vp]
+    L.ug_r1cs_create.argtypes = [vp, vp, u64, pp]
+    L.ug_r1cs_get_info.argtypes = [vp, vp]
+    L.ug_r1cs_check.argtypes = [vp, vp, u64, vp, vp]
+    L.ug_r1cs_check_enqueue.argtypes = [vp, vp, u64, C.c_int, vp]
+    L.ug_r1cs_check_collect.argtypes = [vp, C.c_int, vp]
+    L.ug_r1cs_match_hpoly.argtypes = [vp, vp, u32, C.POINTER(C.c_int), C.POINTER(u64)]
+    L.ug_r1cs_destroy.argtypes = [vp]; L.ug_r1cs_destroy.restype = None
+    L.ug_witness_check.argtypes = [vp, ull, vp, ull, C.c_int, vp, vp, ull]
+    L.ug_prover_attach_r1cs.argtypes = [vp, vp, ull, vp, ull]
     L.ug_fr_ntt.argtypes = [vp, vp, C.c_int, C.c_int]
     L.ug_field_op.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, u64]
     L.ug_synth_points.argtypes = [vp, C.c_int, vp, u64, u64, vp]

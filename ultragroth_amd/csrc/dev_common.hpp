@@ -93,6 +93,36 @@ template <class P> __device__ __forceinline__ Fp<P> contract(const Fp<P>& a) {
     return r;
 }
 
+// The sum of one row of a CSR coefficient matrix times the witness (hpoly.hip: rows r < domain: matrix A, the others: matrix B;
+// r1cs.hip: one matrix of an .r1cs per triple). val: coef * 2^522 packed, wtns: plain 32-byte integers; the sum is w * coef in
+// device Montgomery form, strict, < 2.01 q.
+__device__ __forceinline__ Fr matvec_row(u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns) {
+    u32 s = row_ptr[r], e = row_ptr[r + 1];
+    Fr acc = fp_zero<FrParams>();
+    u32 since = 0;
+    // four entries at a time: their signal ids first, then the four 32-byte witness gathers and the four coefficients all in
+    // flight together, then the products (one entry per turn left every gather's latency -- a DRAM row miss -- exposed: 69 %
+    // of the kernel's wave cycles were waits)
+    for (u32 p = s; p < e; p += 4) {
+        const u32 cnt = e - p < 4 ? e - p : 4;
+        u32 sg[4], wr[4][8], vr[4][8];
+#pragma unroll
+        for (int k = 0; k < 4; k++) sg[k] = (u32)k < cnt ? sig[p + k] : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if ((u32)k < cnt) { load8(wr[k], wtns + (size_t)sg[k] * 8); load8(vr[k], val + (size_t)(p + k) * 8); }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if ((u32)k < cnt) {
+                acc = add(acc, mul(unpack256<FrParams>(wr[k]), unpack256<FrParams>(vr[k])));      // + < 2q  (w: plain integer, any value < 2^256)
+                if (++since == 24) { acc = contract(acc); since = 0; }                              // keep below 64 q
+            }
+        }
+    }
+    return contract(acc);
+}
+
 __host__ __device__ __forceinline__ u32 bit_reverse(u32 x, int bits) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return bits ? (__brev(x) >> (32 - bits)) : 0;

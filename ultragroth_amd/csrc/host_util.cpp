@@ -126,6 +126,87 @@ WtnsHeader loadWtnsHeader(const BinFile& f) {
     return h;
 }
 
+// ---- .r1cs --------------------------------------------------------------------------------------------------
+const uint8_t BN254_R_BYTES[32] = {
+    0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
+    0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+
+namespace {
+struct R1csError : public std::invalid_argument {
+    explicit R1csError(const std::string& m) : std::invalid_argument("r1cs: " + m) {}
+};
+bool belowModulus(const uint8_t* le) {
+    for (int i = 31; i >= 0; i--) {
+        if (le[i] < BN254_R_LE[i]) return true;
+        if (le[i] > BN254_R_LE[i]) return false;
+    }
+    return false;
+}
+// One walk of section 2. fill == nullptr: the validating pass (terms[] counted). Otherwise the triples are written; the first
+// pass has then vouched for every bound, which are checked again all the same (the cursor never leaves the section).
+void walkR1cs(const uint8_t* p, uint64_t left, const R1csHeader& h, uint64_t terms[3], R1csMatrix* fill) {
+    uint64_t at[3] = {0, 0, 0};
+    for (uint32_t k = 0; k < h.nConstraints; k++) {
+        for (int m = 0; m < 3; m++) {
+            if (left < 4) throw R1csError("constraint " + std::to_string(k) + ": record runs past the section");
+            const uint32_t n = rd32(p);
+            p += 4; left -= 4;
+            if (n > left / 36) throw R1csError("constraint " + std::to_string(k) + ": record runs past the section");
+            if (at[m] + n > 0xffffffffull) throw R1csError(std::string("more than 2^32 - 1 terms in matrix ") + "ABC"[m]);
+            if (fill) fill[m].rowPtr[k] = (uint32_t)at[m];
+            for (uint32_t t = 0; t < n; t++, p += 36) {
+                const uint32_t wire = rd32(p);
+                if (wire >= h.nWires) throw R1csError("constraint " + std::to_string(k) + ": wire " + std::to_string(wire) + " out of range");
+                if (!belowModulus(p + 4)) throw R1csError("constraint " + std::to_string(k) + ": coefficient not below the field modulus");
+                if (fill) {
+                    fill[m].sig[at[m] + t] = wire;
+                    memcpy(&fill[m].val[(at[m] + t) * 32], p + 4, 32);
+                }
+            }
+            left -= (uint64_t)n * 36;
+            at[m] += n;
+        }
+    }
+    if (left) throw R1csError("trailing bytes in section 2");
+    for (int m = 0; m < 3; m++) {
+        terms[m] = at[m];
+        if (fill) fill[m].rowPtr[h.nConstraints] = (uint32_t)at[m];
+    }
+}
+}  // namespace
+
+R1csHeader loadR1csHeader(const BinFile& f) {
+    if (!f.hasSection(1)) throw R1csError("section 1 (header) is missing");
+    const uint8_t* p = f.sectionData(1);
+    const uint64_t size = f.sectionSize(1);
+    R1csHeader h;
+    if (size < 4) throw R1csError("section 1 (header) is too short");
+    h.n8 = rd32(p);
+    if (h.n8 != 32) throw R1csError("n8 is " + std::to_string(h.n8) + ", not 32");
+    if (size < 4 + 32 + 16 + 8 + 4) throw R1csError("section 1 (header) is too short");
+    if (memcmp(p + 4, BN254_R_LE, 32) != 0) throw R1csError("not over the BN254 scalar field");
+    h.nWires = rd32(p + 36); h.nPubOut = rd32(p + 40); h.nPubIn = rd32(p + 44); h.nPrvIn = rd32(p + 48);
+    h.nLabels = rd64(p + 52);
+    h.nConstraints = rd32(p + 60);
+    if (h.nWires == 0) throw R1csError("nWires is 0");
+    return h;
+}
+void countR1csTerms(const BinFile& f, const R1csHeader& h, uint64_t terms[3]) {
+    if (!f.hasSection(2)) throw R1csError("section 2 (constraints) is missing");
+    walkR1cs(f.sectionData(2), f.sectionSize(2), h, terms, nullptr);
+}
+void loadR1cs(const BinFile& f, R1cs& out) {
+    out.hdr = loadR1csHeader(f);
+    countR1csTerms(f, out.hdr, out.terms);
+    for (int m = 0; m < 3; m++) {
+        out.m[m].rowPtr.assign((size_t)out.hdr.nConstraints + 1, 0);
+        out.m[m].sig.assign((size_t)out.terms[m], 0);
+        out.m[m].val.assign((size_t)out.terms[m] * 32, 0);
+    }
+    uint64_t again[3];
+    walkR1cs(f.sectionData(2), f.sectionSize(2), out.hdr, again, out.m);
+}
+
 // ---- decimal ---------------------------------------------------------------------------------------------
 std::string toDecimal(const uint8_t le[32]) {
     uint32_t w[8];

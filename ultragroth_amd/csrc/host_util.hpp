@@ -57,6 +57,30 @@ ZkeyHeader loadZkeyHeader(const BinFile& f, bool ultra);
 struct WtnsHeader { uint32_t n8 = 0, nVars = 0; bool primeIsBn254 = false; };
 WtnsHeader loadWtnsHeader(const BinFile& f);
 
+// ---- .r1cs (iden3 binfile, magic "r1cs", version 1; the layout is restated in include/ultragroth_hip.h) ----
+// Every failure is a C++ exception whose message starts with "r1cs: ".
+struct R1csHeader {
+    uint32_t n8 = 0, nWires = 0, nPubOut = 0, nPubIn = 0, nPrvIn = 0, nConstraints = 0;
+    uint64_t nLabels = 0;
+};
+R1csHeader loadR1csHeader(const BinFile& f);
+// one of the matrices A, B, C in CSR form: row k holds the terms [rowPtr[k], rowPtr[k + 1]), term p is coefficient
+// val[32 p, 32 p + 32) (plain little-endian integer below r, as the file has it) of wire sig[p]; the file's order is kept
+struct R1csMatrix {
+    std::vector<uint32_t> rowPtr, sig;
+    std::vector<uint8_t> val;
+};
+struct R1cs {
+    R1csHeader hdr;
+    uint64_t terms[3] = {0, 0, 0};
+    R1csMatrix m[3];
+};
+// first pass over section 2: bounds, wire ids and coefficients checked, the terms of each matrix counted
+void countR1csTerms(const BinFile& f, const R1csHeader& h, uint64_t terms[3]);
+// both passes: the header, the first pass, then the three CSR triples
+void loadR1cs(const BinFile& f, R1cs& out);
+extern const uint8_t BN254_R_BYTES[32];      // the scalar modulus r, little-endian
+
 // 32-byte little-endian plain integer -> decimal string
 std::string toDecimal(const uint8_t le[32]);
 

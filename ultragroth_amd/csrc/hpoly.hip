@@ -49,34 +49,7 @@ __global__ void row_ptr_kernel(const u32* keys, u64 ncoefs, u32 nrows, u32* row_
     row_ptr[r] = (u32)lo;
 }
 
-// the sum of one row of the coefficient matrix times the witness (rows r < domain: matrix A, the others: matrix B)
-__device__ __forceinline__ Fr matvec_row(u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns) {
-    u32 s = row_ptr[r], e = row_ptr[r + 1];
-    Fr acc = fp_zero<FrParams>();
-    u32 since = 0;
-    // four entries at a time: their signal ids first, then the four 32-byte witness gathers and the four coefficients all in
-    // flight together, then the products (one entry per turn left every gather's latency -- a DRAM row miss -- exposed: 69 %
-    // of the kernel's wave cycles were waits)
-    for (u32 p = s; p < e; p += 4) {
-        const u32 cnt = e - p < 4 ? e - p : 4;
-        u32 sg[4], wr[4][8], vr[4][8];
-#pragma unroll
-        for (int k = 0; k < 4; k++) sg[k] = (u32)k < cnt ? sig[p + k] : 0u;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if ((u32)k < cnt) { load8(wr[k], wtns + (size_t)sg[k] * 8); load8(vr[k], val + (size_t)(p + k) * 8); }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if ((u32)k < cnt) {
-                acc = add(acc, mul(unpack256<FrParams>(wr[k]), unpack256<FrParams>(vr[k])));      // + < 2q  (w: plain integer, any value < 2^256)
-                if (++since == 24) { acc = contract(acc); since = 0; }                              // keep below 64 q
-            }
-        }
-    }
-    return contract(acc);
-}
-
+// (matvec_row, the sum of one row of the coefficient matrix times the witness: dev_common.hpp -- shared with r1cs.hip)
 // one lane per row, the result stored at the row's bit-reversed place (domains below 2^8)
 __global__ __launch_bounds__(256) void matvec_kernel(u32* a_br, u32* b_br, const u32* row_ptr, const u32* sig,
                                                      const u32* val, const u32* wtns, u32 domain, int logn, int mask) {

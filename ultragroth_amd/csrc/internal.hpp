@@ -351,4 +351,24 @@ void lookup_tables_vectors(u32* stage, const LookupVec* vec_dev, int vectors, u6
 void apply_lookup_vectors(u32* dst, u64 stride, u32* last_scratch, const u32* stage, const LookupVec* vec_dev, int vectors, u64 max_n,
                           hipStream_t stream);
 
+
+// ---- r1cs.hip -----------------------------------------------------------------------------------------
+// the three matrices A, B, C of an .r1cs on the device, each a CSR triple of CoefMatrix's form over `rows` constraints
+// (val = coef * 2^522 packed); passed to the kernels by value
+struct R1csDev {
+    u32 rows = 0;
+    const u32* row_ptr[3] = {nullptr, nullptr, nullptr};
+    const u32* sig[3] = {nullptr, nullptr, nullptr};
+    const u32* val[3] = {nullptr, nullptr, nullptr};
+};
+// n plain coefficients below r (32 bytes each, as the file has them) -> packed coef * 2^522, in place
+void r1cs_convert_coefs(u32* val, u64 n, hipStream_t stream);
+// queues the check of one witness (plain integers, n_wires elements): words[0] = failing constraints, words[1] = ~(lowest failing
+// index), both zeroed first on the stream; mask: rows device bytes (0 holds, 1 fails) or null
+void r1cs_check(const R1csDev& m, const u32* wtns, unsigned long long* words, uint8_t* mask, hipStream_t stream);
+// the values A.w, B.w, C.w of constraint k as canonical plain integers (24 device words), one lane
+void r1cs_row_values(const R1csDev& m, const u32* wtns, u32 k, u32* out24, hipStream_t stream);
+// the probe against a zkey's coefficient matrix over z (n_wires plain values): *word = the lowest failing 2 * row + matrix, or all ones
+void r1cs_match(const R1csDev& m, const CoefMatrix& zk, u32 n_public, const u32* z, unsigned long long* word, hipStream_t stream);
+
 }  // namespace ug

@@ -122,6 +122,16 @@ void validateOnCreate(ug_ctx* ctx, ug_ctx* ctx2, const ZkeyHeader& h, bool ultra
     if (headerPointFault(ctx, h, ultra, level, &which, &reason)) throw ZkeyPointFault(headerFaultMessage(which, reason));
 }
 
+// ---- the witness check of an attached .r1cs (ug_prover_attach_r1cs, ULTRAGROTH_R1CS; r1cs.hip) --------------------------------------
+class WitnessFault : public std::invalid_argument {
+public:
+    explicit WitnessFault(const std::string& m) : std::invalid_argument(m) {}
+};
+std::string witnessFaultMessage(const ug_r1cs_report& rep, uint32_t rows) {
+    return "witness: constraint " + std::to_string(rep.first) + " does not hold (" + std::to_string(rep.failed) + " of " + std::to_string(rows) + " fail)";
+}
+const char* const R1CS_UNAVAILABLE = "witness check: not available on this kind of prover";
+
 // Work queued on the prover's contexts must not outlive a failing call: the queued MSMs hold pointers into the caller's
 // stack frame and the kernels read the leased witness buffer. Armed while a call has work in flight; on unwind it waits
 // for the device and drops what was queued (ug_ctx_abandon), before the witness lease and the turn are given back.
@@ -336,7 +346,9 @@ struct DeviceProver {
                                  // (written once, under the prover's slot lock; the device part reads Groth16Prover::wCur_)
     ug_schedule *sw = nullptr, *sh = nullptr, *saux = nullptr;
     ug_index *roundIdx = nullptr, *finalIdx = nullptr;      // UltraGroth: zkey sections 10 and 11, resident
+    ug_r1cs* r1cs = nullptr;     // the circuit's .r1cs, when one is attached: every proof checks its witness against it
     ~DeviceProver() {
+        ug_r1cs_destroy(r1cs);
         ug_index_destroy(roundIdx); ug_index_destroy(finalIdx); ug_index_destroy(bIdx);
         ug_schedule_destroy(sw); ug_schedule_destroy(sh); ug_schedule_destroy(saux); ug_schedule_destroy(sB);
         ug_dvec_destroy(w); ug_dvec_destroy(w2); ug_dvec_destroy(h); ug_dvec_destroy(aux); ug_dvec_destroy(wB);
@@ -856,6 +868,13 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
     virtual void hRange(unsigned long long*, unsigned long long*, unsigned long long*) const { noPhase(); }
     virtual void finish(const uint8_t*, std::string&, std::string&) { noPhase(); }
     virtual void proveResident(std::string&, std::string&) { noPhase(); }
+    // the circuit's .r1cs for the witness check of every proof (size 0: none); only a created, unsharded, one-device prover takes one
+    virtual void attachR1cs(const void*, unsigned long long) { throw std::invalid_argument(R1CS_UNAVAILABLE); }
+    virtual bool r1csAttached() const { return false; }
+    // the phase calls that make a proof in pieces pass no witness check: an attached prover refuses them
+    void noPhaseWhenAttached() const {
+        if (r1csAttached()) throw std::invalid_argument("witness check: this phase call is not available while an .r1cs is attached");
+    }
     virtual void roundCommit(uint8_t*) { noPhase(); }
     virtual void roundFinish(const uint8_t*, uint8_t*) { noPhase(); }
     virtual void applyCommitment(const uint8_t*) { noPhase(); }
@@ -1038,6 +1057,47 @@ public:
     }
     uint64_t batchKeep_ = 0;                        // bytes a pass plan leaves aside (reserveForPass asks what a group would cost the pass)
     int hpolyGroup_ = 1;                            // the launch group d_.hp holds workspaces for
+
+    // ---- the attached .r1cs ----
+    bool attachable_ = false;                       // a created, unsharded prover on one device (newGroth16Prover / newUltraGrothProver)
+    bool r1csAttached() const override { return d_.r1cs != nullptr; }
+    void attachR1cs(const void* data, unsigned long long size) override {
+        if (!attachable_ || !haveHpoly_) throw std::invalid_argument(R1CS_UNAVAILABLE);
+        std::unique_lock<std::mutex> turn = takeTurn(false);
+        if (!size) { ug_r1cs_destroy(d_.r1cs); d_.r1cs = nullptr; return; }
+        if (!data) throw std::invalid_argument("Null r1cs buffer");
+        ug_r1cs_info info;
+        ugCheck(ug_r1cs_parse_info(data, size, &info));
+        const std::string no = "r1cs: not this circuit: ";
+        if (info.n_wires != hdr_.nVars) throw std::invalid_argument(no + "nWires " + std::to_string(info.n_wires) + ", the zkey has nVars " + std::to_string(hdr_.nVars));
+        if ((uint64_t)info.n_pub_out + info.n_pub_in != hdr_.nPublic)
+            throw std::invalid_argument(no + "nPubOut + nPubIn " + std::to_string((uint64_t)info.n_pub_out + info.n_pub_in) + ", the zkey has nPublic " + std::to_string(hdr_.nPublic));
+        if ((uint64_t)info.n_constraints + hdr_.nPublic + 1 > hdr_.domainSize)
+            throw std::invalid_argument(no + "nConstraints + nPublic + 1 = " + std::to_string((uint64_t)info.n_constraints + hdr_.nPublic + 1) +
+                                        " above the zkey's domainSize " + std::to_string(hdr_.domainSize));
+        struct Fresh { ug_r1cs* p = nullptr; ~Fresh() { ug_r1cs_destroy(p); } } fresh;      // on failure nothing is attached, the old one stays
+        ugCheck(ug_r1cs_create(d_.ctx2, data, size, &fresh.p));
+        int matrix = -1;
+        uint64_t row = 0;
+        ugCheck(ug_r1cs_match_hpoly(fresh.p, d_.hp, hdr_.nPublic, &matrix, &row));
+        if (matrix >= 0)
+            throw std::invalid_argument(no + "matrix " + (matrix ? "B" : "A") + " row " + std::to_string(row) + " differs from the zkey");
+        std::swap(d_.r1cs, fresh.p);
+        r1csRows_ = info.n_constraints;
+    }
+    // the check of the witness at elements [first, first + nVars) of w queued on the H branch's stream beside the proof's kernels
+    // (eagerly: never part of a recorded sequence); nothing when no .r1cs is attached
+    void queueWitnessCheck(const ug_dvec* w, uint64_t first = 0, int slot = 0) {
+        if (d_.r1cs) ugCheck(ug_r1cs_check_enqueue(d_.r1cs, w, first, slot, d_.ctx2));
+    }
+    // ... and its result, read where the call has waited for the device anyway: a witness that breaks a constraint fails the call
+    void collectWitnessCheck(int slot = 0) {
+        if (!d_.r1cs) return;
+        ug_r1cs_report rep;
+        ugCheck(ug_r1cs_check_collect(d_.r1cs, slot, &rep));
+        if (rep.failed) throw WitnessFault(witnessFaultMessage(rep, r1csRows_));
+    }
+    uint32_t r1csRows_ = 0;
 
 protected:
     virtual void requireWitnessForH() const = 0;
@@ -1699,9 +1759,11 @@ public:
             uint8_t hpart[UG_GROTH16_PARTIALS_SIZE];
             runWitnessMsm(partials, /*standalone*/ false);
             QueueGuard hBranch(d_.ctx2);
+            queueWitnessCheck(wCur_);
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));                                          // S5-S9 :66-148
             runHMsmImpl(hpart, false);                                                         // S10   :154
             hBranch.done();
+            try { collectWitnessCheck(); } catch (...) { memset(partials, 0, UG_GROTH16_PARTIALS_SIZE); throw; }
             memcpy(partials + 320, hpart + 320, 64);
             collectTimings(3);
             return;
@@ -1715,6 +1777,7 @@ public:
         memset(partials, 0, UG_GROTH16_PARTIALS_SIZE);
         memset(runParts_, 0, sizeof runParts_);
         QueueGuard inFlight(d_.ctx, d_.ctx2);                   // from here to the collects below work is queued on both streams
+        queueWitnessCheck(wCur_);                               // (an attached .r1cs: ahead of the H branch, outside any recorded sequence)
         // the whole device part: queued eagerly, or -- ULTRAGROTH_GRAPH=1 -- recorded once per witness buffer and replayed (the
         // queued products write to runParts_, a member, so that a replay finds the same addresses)
         auto queueAll = [&] {
@@ -1752,6 +1815,7 @@ public:
             ugCheck(ug_ctx_collect(d_.ctx));                    // (... this one returns at once unless the streams overlap)
         }
         inFlight.done();
+        collectWitnessCheck();                                  // (the device has been waited for: the result words are there)
         memcpy(partials, runParts_, UG_GROTH16_PARTIALS_SIZE);
         collectTimings(3);
     }
@@ -1872,10 +1936,12 @@ public:
         stage(*lease, c.wtns[b], c.sizes[b]);
         std::unique_lock<std::mutex> turn = takeTurn(true);
         adopt(*lease);
-        proveLoaded(c.proofs[(size_t)b], c.pubs[(size_t)b], [&] {
-            c.msm += m1_ + m2_; c.fft += f1_ + f2_;
-            turn.unlock();
-        });
+        try {
+            proveLoaded(c.proofs[(size_t)b], c.pubs[(size_t)b], [&] {
+                c.msm += m1_ + m2_; c.fft += f1_ + f2_;
+                turn.unlock();
+            });
+        } catch (WitnessFault& e) { throw WitnessFault("witness " + std::to_string(b) + ": " + e.what()); }
     }
     // witnesses per device pass for up to `requested` (proveMutex held: the schedules' current table plan)
     int perPass(const BatchCall&, int requested, int /*b0*/) {
@@ -1899,7 +1965,7 @@ public:
         if (d_.Bc2) BatchBuffers::ensure(batch_.wB, d_.ctx, (uint64_t)V * nB_);
     }
     void stagePass(const BatchCall& c, int b0, int V) { batch_.stage(d_.ctx, witness_.stageMutex, c.data.data() + b0, V, hdr_.nVars); }
-    BatchPass runPass(BatchCall& c, int /*b0*/, int V) {
+    BatchPass runPass(BatchCall& c, int b0, int V) {
         BatchPass p;
         p.r.resize((size_t)V * 32); p.s.resize((size_t)V * 32); p.parts.resize((size_t)V * UG_GROTH16_PARTIALS_SIZE);
         for (int v = 0; v < V; v++) { drawBlinding(&p.r[(size_t)v * 32]); drawBlinding(&p.s[(size_t)v * 32]); }      // S11, in witness order
@@ -1907,7 +1973,7 @@ public:
             const uint8_t *r = &p.r[(size_t)v * 32], *s = &p.s[(size_t)v * 32];      // (by value: `p` may move when it is returned, its buffers stay)
             p.terms.push_back(std::async(std::launch::async, [this, r, s] { return blindingTerms(hdr_, r, s); }));
         }
-        runBatch(V, p.parts.data());                    // (the futures join in their destructors if this throws)
+        runBatch(V, p.parts.data(), b0);                // (the futures join in their destructors if this throws)
         c.msm += m1_ + m2_; c.fft += f1_ + f2_;
         return p;
     }
@@ -1920,7 +1986,7 @@ public:
         }
     }
     // one device pass of the V staged witnesses; parts = V blocks A | B1 | B2 | C | H as run() leaves them
-    void runBatch(int V, uint8_t* parts) {
+    void runBatch(int V, uint8_t* parts, int b0) {
         const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize, nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
         const char* ov = getenv("ULTRAGROTH_OVERLAP");
         const int overlap = ov ? atoi(ov) : 1;
@@ -1933,6 +1999,7 @@ public:
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), outC.data(), (int64_t)hdr_.nPublic + 1,
                                    overlap == 2, batch_.w, V, nv, batch_.wB);
             if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
+            for (int v = 0; v < V; v++) queueWitnessCheck(batch_.w, (uint64_t)v * nv, v);       // (an attached .r1cs: one check per witness, in slots)
             hpolyOfBatch(views, V);                                                             // S5-S9 of the V witnesses
             ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
             if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
@@ -1943,6 +2010,13 @@ public:
             ugCheck(ug_ctx_collect(d_.ctx));
             inFlight.done();
         }
+        // every slot is read, so that none stays queued; the lowest failing witness fails the call
+        std::exception_ptr bad;
+        for (int v = 0; v < V; v++) {
+            try { atWitness(b0 + v, [&] { collectWitnessCheck(v); }); }
+            catch (...) { if (!bad) bad = std::current_exception(); }
+        }
+        if (bad) std::rethrow_exception(bad);
         collectTimings(3);
         for (int v = 0; v < V; v++) {
             uint8_t* p = parts + (size_t)v * UG_GROTH16_PARTIALS_SIZE;
@@ -2370,6 +2444,7 @@ public:
         if (trace_) {                                    // phase by phase, with a host wait (and a line on stderr) after each
             uint8_t hpart[UG_GROTH16_PARTIALS_SIZE];
             runWitnessMsm(sums);
+            queueWitnessCheck(wCur_);
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));                                       // FFT block :243-320
             mark("H polynomial");
             runHMsm(hpart);
@@ -2384,6 +2459,7 @@ public:
             queueFinalRoundProducts(sums);
             const char* ov = getenv("ULTRAGROTH_OVERLAP");
             if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));      // (default: beside, as for Groth16)
+            queueWitnessCheck(wCur_);                    // (an attached .r1cs: the lookup completion has written the witness, the final round follows)
             ugCheck(ug_hpoly_run(d_.hp, wCur_, d_.h));
             buildSchedule(d_.sh, d_.h, hr_.lo, hr_.hi - hr_.lo, planH_.c, planH_.stride);
             const ug_bases* setH[1] = {d_.H};
@@ -2394,6 +2470,7 @@ public:
             collectTimings(3);
         }
         inFlight.done();
+        collectWitnessCheck();
         finishWith(sums, r, s, terms.get(), proof, pub);
     }
 
@@ -2416,7 +2493,8 @@ public:
     };
     void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
                     std::vector<std::string>& pubs) override {
-        if (!batchable_ || !haveHpoly_) { ProverBase::proveBatch(k, wtns, sizes, proofs, pubs); return; }
+        // (an attached .r1cs: one proof after the other, each with its check -- the batched pass has none of its own yet)
+        if (!batchable_ || !haveHpoly_ || r1csAttached()) { ProverBase::proveBatch(k, wtns, sizes, proofs, pubs); return; }
         BatchCall c{wtns, sizes, proofs, pubs, std::vector<StagedWitness>((size_t)k), std::vector<const uint8_t*>((size_t)k)};
         proveBatchInPasses(*this, c, k);
     }
@@ -3087,16 +3165,42 @@ public:
     unsigned long long publicBufferMinSize() const override { return publicMin((unsigned long long)nPublic_ - 1); }
 };
 
+// ULTRAGROTH_R1CS=<path>: every prover made by the reference's create calls (the CLIs and the one-shot calls among them) attaches
+// that file. An unreadable or mismatching file fails the creation, and so does a kind of prover that cannot check: never silently
+// unchecked. Unset or empty: nothing changes.
+const char* r1csFromEnv() {
+    const char* e = getenv("ULTRAGROTH_R1CS");
+    return e && e[0] ? e : nullptr;
+}
+void attachFromEnv(ProverBase& p) {
+    const char* path = r1csFromEnv();
+    if (!path) return;
+    std::unique_ptr<FileMap> m;
+    try { m.reset(new FileMap(path)); }
+    catch (std::exception& e) { throw std::invalid_argument(std::string("ULTRAGROTH_R1CS: cannot read ") + path + ": " + e.what()); }
+    if (!m->size()) throw std::invalid_argument(std::string("ULTRAGROTH_R1CS: ") + path + " is empty");
+    p.attachR1cs(m->data(), m->size());
+}
+
 ProverBase* newUltraGrothProver(const void* zkey, unsigned long long size) {
     const std::vector<int> devices = devicesFromEnv();
+    if (devices.size() > 1 && r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);
     if (devices.size() > 1) return new MultiUltraGrothProver(zkey, size, devices);
-    return new UltraGrothProver(zkey, size, devices.size() == 1 ? devices[0] : deviceFromEnv());
+    if (devices.size() == 1 && r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (a ULTRAGROTH_DEVICES handle, even of one device)
+    std::unique_ptr<UltraGrothProver> p(new UltraGrothProver(zkey, size, devices.size() == 1 ? devices[0] : deviceFromEnv()));
+    p->attachable_ = devices.empty();
+    attachFromEnv(*p);
+    return p.release();
 }
 ProverBase* newGroth16Prover(const void* zkey, unsigned long long size) {
     const std::vector<int> devices = devicesFromEnv();
+    if (!devices.empty() && r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (a ULTRAGROTH_DEVICES handle, even of one device)
     if (devices.size() > 1) return new MultiGroth16Prover(zkey, size, devices);
     struct Flag { Flag() { g_deferTables = true; } ~Flag() { g_deferTables = false; } } deferred;
-    return new Groth16Prover(zkey, size, devices.size() == 1 ? devices[0] : deviceFromEnv(), 0, 1);
+    std::unique_ptr<Groth16Prover> p(new Groth16Prover(zkey, size, devices.size() == 1 ? devices[0] : deviceFromEnv(), 0, 1));
+    p->attachable_ = devices.empty();
+    attachFromEnv(*p);
+    return p.release();
 }
 
 // =================================================================================================================
@@ -3124,6 +3228,7 @@ public:
         return f.substr(0, f.find_last_of('.'));
     }
     void load(const std::string& name, const void* zkey, uint64_t size, const std::string& path) {
+        if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
         std::lock_guard<std::mutex> lock(mutex_);
         if (name.empty()) throw std::invalid_argument("empty circuit name");
         {
@@ -3321,6 +3426,55 @@ private:
     return PROVER_OK;
 
 namespace {
+// ---- the witness check on host threads (ug_witness_check with device < 0): ff.hpp's host build, the arithmetic of matvec_row ----
+// One row of an .r1cs matrix times the witness, canonical, in the device's Montgomery form (x * 2^261): every term is
+// mul(w plain, coef * 2^522) as on the device; the sum is reduced after every term instead of every 24th, which changes the
+// representative on the way and not the residue.
+Fr r1csRowHost(const R1csMatrix& m, uint32_t k, const uint8_t* w) {
+    Fr acc = fp_zero<FrParams>();
+    for (uint32_t p = m.rowPtr[k]; p < m.rowPtr[k + 1]; p++) {
+        u32 cw[8], ww[8];
+        memcpy(cw, &m.val[(size_t)p * 32], 32);
+        memcpy(ww, w + (size_t)m.sig[p] * 32, 32);
+        const Fr val = cond_sub_q(mul(from_normal<FrParams>(cw), fp_from<FrParams>(FrParams::r2)));
+        const Fr sum = norm_strict(add(acc, mul(unpack256<FrParams>(ww), val)));     // < q + 2q
+        acc = cond_sub_q(cond_sub_q(sum));
+    }
+    return acc;
+}
+bool sameLimbs(const Fr& x, const Fr& y) {
+    u32 o = 0;
+    for (int i = 0; i < NL; i++) o |= x.l[i] ^ y.l[i];
+    return o == 0;
+}
+void r1csCheckHost(const R1cs& cs, const uint8_t* w, ug_r1cs_report* out) {
+    memset(out, 0, sizeof *out);
+    const uint32_t rows = cs.hdr.nConstraints;
+    unsigned hw = std::thread::hardware_concurrency();
+    const uint32_t T = std::max<uint32_t>(1, std::min<uint32_t>({hw ? hw : 1u, 16u, rows / 1024 + 1}));
+    std::vector<uint64_t> failed(T, 0), first(T, ~(uint64_t)0);
+    auto work = [&](uint32_t t) {
+        const uint32_t lo = (uint32_t)((uint64_t)rows * t / T), hi = (uint32_t)((uint64_t)rows * (t + 1) / T);
+        for (uint32_t k = lo; k < hi; k++) {
+            const Fr a = r1csRowHost(cs.m[0], k, w), b = r1csRowHost(cs.m[1], k, w), c = r1csRowHost(cs.m[2], k, w);
+            if (sameLimbs(canon(mul(a, b)), c)) continue;
+            if (!failed[t]++) first[t] = k;
+        }
+    };
+    std::vector<std::thread> th;
+    for (uint32_t t = 1; t < T; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+    for (uint32_t t = 0; t < T; t++) out->failed += failed[t];
+    uint64_t lowest = ~(uint64_t)0;
+    for (uint32_t t = 0; t < T; t++) lowest = std::min(lowest, first[t]);
+    if (!out->failed) return;
+    out->first = lowest;
+    const Fr v[3] = {r1csRowHost(cs.m[0], (uint32_t)lowest, w), r1csRowHost(cs.m[1], (uint32_t)lowest, w), r1csRowHost(cs.m[2], (uint32_t)lowest, w)};
+    uint8_t* dst[3] = {out->a, out->b, out->c};
+    for (int t = 0; t < 3; t++) { u32 o[8]; to_normal(o, v[t]); memcpy(dst[t], o, 32); }
+}
+
 int proveImpl(void* prover_object, const void* wtns_buffer, unsigned long long wtns_size, char* proof_buffer,
               unsigned long long* proof_size, char* public_buffer, unsigned long long* public_size, char* error_msg,
               unsigned long long error_msg_maxsize) {
@@ -3566,6 +3720,57 @@ int ug_zkey_check(const void* zkey_buffer, unsigned long long zkey_size, int dev
     API_CATCH
 }
 
+// The standalone witness check: no prover, nothing kept. Both files are parsed first (the loaders' messages); device >= 0 runs
+// the check kernel on a context of its own, device < 0 the same arithmetic on host threads.
+int ug_witness_check(const void* r1cs, unsigned long long r1cs_size, const void* wtns, unsigned long long wtns_size, int device,
+                     ug_witness_fault* fault, char* error_msg, unsigned long long error_msg_maxsize) {
+    if (fault) memset(fault, 0, sizeof *fault);
+    API_TRY
+    if (r1cs == NULL) throw std::invalid_argument("Null r1cs buffer");
+    if (wtns == NULL) throw std::invalid_argument("Null witness buffer");
+    BinFile rf(r1cs, r1cs_size, "r1cs", 1);
+    const R1csHeader rh = loadR1csHeader(rf);
+    uint64_t terms[3];
+    countR1csTerms(rf, rh, terms);
+    BinFile wf(wtns, wtns_size, "wtns", 2);
+    const WtnsHeader wh = loadWtnsHeader(wf);
+    if (wh.nVars != rh.nWires)
+        throw InvalidWitnessLengthException("Invalid witness length. Circuit: " + std::to_string(rh.nWires) + ", witness: " + std::to_string(wh.nVars));
+    if (!wh.primeIsBn254) throw std::invalid_argument("different wtns curve");
+    const uint8_t* w = checkedSection(wf, 2, (uint64_t)rh.nWires * 32);
+    ug_r1cs_report rep;
+    if (device < 0) {
+        R1cs cs;
+        loadR1cs(rf, cs);
+        r1csCheckHost(cs, w, &rep);
+    } else {
+        struct Dev {
+            ug_ctx* c = nullptr; ug_r1cs* r = nullptr; ug_dvec* v = nullptr;
+            ~Dev() { ug_dvec_destroy(v); ug_r1cs_destroy(r); ug_ctx_destroy(c); }
+        } d;
+        ugCheck(ug_ctx_create(&d.c, device));
+        ugCheck(ug_r1cs_create(d.c, r1cs, r1cs_size, &d.r));
+        ugCheck(ug_dvec_create(d.c, rh.nWires, &d.v));
+        ugCheck(ug_dvec_upload(d.v, w, rh.nWires));
+        ugCheck(ug_r1cs_check(d.r, d.v, 0, &rep, nullptr));
+    }
+    if (rep.failed) {
+        if (fault) {
+            fault->failed = rep.failed; fault->first = rep.first;
+            memcpy(fault->a, rep.a, 32); memcpy(fault->b, rep.b, 32); memcpy(fault->c, rep.c, 32);
+        }
+        throw WitnessFault(witnessFaultMessage(rep, rh.nConstraints));
+    }
+    API_CATCH
+}
+
+int ug_prover_attach_r1cs(void* prover_object, const void* r1cs, unsigned long long size, char* error_msg, unsigned long long error_msg_maxsize) {
+    API_TRY
+    if (prover_object == NULL) throw std::invalid_argument("Null prover object");
+    static_cast<ProverBase*>(prover_object)->attachR1cs(r1cs, size);
+    API_CATCH
+}
+
 int ug_registry_create(void** registry, int device, unsigned long long hbm_budget_bytes, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
     if (registry == NULL) throw std::invalid_argument("Null registry pointer");
@@ -3653,6 +3858,7 @@ int ug_prover_last_upload_ms(void* prover_object, double* upload_ms) {
 int ug_groth16_prover_create_sharded(void** prover_object, const void* zkey_buffer, unsigned long long zkey_size, int device,
                                      int shard_rank, int shard_count, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
+    if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
     if (prover_object == NULL) throw std::invalid_argument("Null prover object");
     if (zkey_buffer == NULL) throw std::invalid_argument("Null zkey buffer");
     *prover_object = static_cast<ProverBase*>(new Groth16Prover(zkey_buffer, zkey_size, device, shard_rank, shard_count));
@@ -3662,6 +3868,7 @@ int ug_groth16_prover_create_sharded_range(void** prover_object, const void* zke
                                            int shard_rank, int shard_count, unsigned long long witness_first,
                                            unsigned long long witness_end, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
+    if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
     if (prover_object == NULL) throw std::invalid_argument("Null prover object");
     if (zkey_buffer == NULL) throw std::invalid_argument("Null zkey buffer");
     Range wr{witness_first, witness_end};
@@ -3696,6 +3903,7 @@ int ug_groth16_prover_create_sharded_layout(void** prover_object, const void* zk
                                             const unsigned long long slice_bytes[5], int device, int shard_rank, int shard_count,
                                             const unsigned long long layout[12], char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
+    if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
     if (prover_object == NULL) throw std::invalid_argument("Null prover object");
     if (zkey_header == NULL) throw std::invalid_argument("Null zkey buffer");
     if (slice_bytes == NULL) throw std::invalid_argument("Null slice sizes");
@@ -3729,6 +3937,7 @@ int ug_groth16_prover_create_sharded_slices(void** prover_object, const void* zk
                                             int shard_count, const unsigned long long* witness_range, char* error_msg,
                                             unsigned long long error_msg_maxsize) {
     API_TRY
+    if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
     if (prover_object == NULL) throw std::invalid_argument("Null prover object");
     if (zkey_header == NULL) throw std::invalid_argument("Null zkey buffer");
     if (slice_bytes == NULL) throw std::invalid_argument("Null slice sizes");
@@ -3782,12 +3991,14 @@ int ug_groth16_prover_run(void* prover_object, void* partials_out, char* error_m
 int ug_groth16_prover_run_witness_msm(void* prover_object, void* partials_out, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
     if (prover_object == NULL || partials_out == NULL) throw std::invalid_argument("Null argument");
+    static_cast<ProverBase*>(prover_object)->noPhaseWhenAttached();
     static_cast<ProverBase*>(prover_object)->runWitnessMsm(static_cast<uint8_t*>(partials_out));
     API_CATCH
 }
 int ug_groth16_prover_witness_msm_begin(void* prover_object, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
     if (prover_object == NULL) throw std::invalid_argument("Null argument");
+    static_cast<ProverBase*>(prover_object)->noPhaseWhenAttached();
     static_cast<ProverBase*>(prover_object)->witnessMsmBegin();
     API_CATCH
 }
@@ -3800,12 +4011,14 @@ int ug_groth16_prover_witness_msm_end(void* prover_object, void* partials_out, c
 int ug_groth16_prover_run_h_msm(void* prover_object, void* partials_out, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
     if (prover_object == NULL || partials_out == NULL) throw std::invalid_argument("Null argument");
+    static_cast<ProverBase*>(prover_object)->noPhaseWhenAttached();
     static_cast<ProverBase*>(prover_object)->runHMsm(static_cast<uint8_t*>(partials_out));
     API_CATCH
 }
 int ug_groth16_prover_hpoly_chain(void* prover_object, int which, void* device_out, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
     if (prover_object == NULL || device_out == NULL) throw std::invalid_argument("Null argument");
+    static_cast<ProverBase*>(prover_object)->noPhaseWhenAttached();
     static_cast<ProverBase*>(prover_object)->hpolyChain(which, device_out);
     API_CATCH
 }
@@ -3813,6 +4026,7 @@ int ug_groth16_prover_hpoly_combine(void* prover_object, void* device_a, void* d
                                     unsigned long long error_msg_maxsize) {
     API_TRY
     if (prover_object == NULL || !device_a || !device_b || !device_c) throw std::invalid_argument("Null argument");
+    static_cast<ProverBase*>(prover_object)->noPhaseWhenAttached();
     static_cast<ProverBase*>(prover_object)->hpolyCombine(device_a, device_b, device_c);
     API_CATCH
 }
@@ -3824,6 +4038,7 @@ int ug_groth16_prover_h_range(void* prover_object, unsigned long long* first, un
 int ug_ultra_groth_prover_create_sharded(void** prover_object, const void* zkey_buffer, unsigned long long zkey_size, int device,
                                          int shard_rank, int shard_count, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
+    if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
     if (prover_object == NULL) throw std::invalid_argument("Null prover object");
     if (zkey_buffer == NULL) throw std::invalid_argument("Null zkey buffer");
     *prover_object = static_cast<ProverBase*>(new UltraGrothProver(zkey_buffer, zkey_size, device, shard_rank, shard_count));
@@ -3845,6 +4060,7 @@ int ug_ultra_groth_prover_create_sharded_slices(void** prover_object, const void
                                                 const unsigned long long slice_bytes[8], int device, int shard_rank, int shard_count,
                                                 char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY
+    if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
     if (prover_object == NULL) throw std::invalid_argument("Null prover object");
     if (zkey_header == NULL) throw std::invalid_argument("Null zkey buffer");
     if (slice_bytes == NULL) throw std::invalid_argument("Null slice sizes");

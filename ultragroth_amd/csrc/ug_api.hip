@@ -16,6 +16,7 @@
 #include <exception>
 #include "dev_common.hpp"
 #include "internal.hpp"
+#include "host_util.hpp"
 #include "../../include/ultragroth_hip.h"
 
 using namespace ug;
@@ -198,6 +199,30 @@ struct ug_hpoly {
                                                                                    // group works on [g * domain, (g + 1) * domain)
     int group = 1;            // vectors side by side that the workspaces hold (ug_hpoly_reserve_vectors)
     int last_group = 0;       // largest launch group of the last ug_hpoly_run_vectors call (0: none yet)
+};
+
+// The three matrices of an .r1cs on the device (r1cs.hip) and the result words of the checks queued on it: slot k (one per witness
+// of a batched pass, the last one ug_r1cs_check's own) has two device words -- failing constraints, ~(lowest failing index) --
+// whose copy in pinned memory is complete once the slot's event has passed.
+struct ug_r1cs {
+    static constexpr int SLOTS = UG_BATCH_MAX + 1;
+    ug_ctx* ctx = nullptr;
+    ughost::R1csHeader hdr;
+    u64 terms[3] = {0, 0, 0};
+    u32 *row_ptr[3] = {nullptr, nullptr, nullptr}, *sig[3] = {nullptr, nullptr, nullptr}, *val[3] = {nullptr, nullptr, nullptr};
+    unsigned long long* words = nullptr;        // device: 2 per slot, then the word of the probe (ug_r1cs_match_hpoly)
+    unsigned long long* words_host = nullptr;   // pinned: the same
+    u32* row_values = nullptr;                  // device: A.w, B.w, C.w of one constraint (24 words) ...
+    u32* row_values_host = nullptr;             // ... and pinned
+    hipEvent_t done[SLOTS] = {};
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    struct Queued { const u32* wtns = nullptr; hipStream_t stream = nullptr; bool on = false; } queued[SLOTS];
+    R1csDev dev() const {
+        R1csDev d;
+        d.rows = hdr.nConstraints;
+        for (int t = 0; t < 3; t++) { d.row_ptr[t] = row_ptr[t]; d.sig[t] = sig[t]; d.val[t] = val[t]; }
+        return d;
+    }
 };
 
 // A fixed launch sequence of one or two contexts of a device, captured once and replayed (ug_graph_*). It owns the event pairs
@@ -1828,6 +1853,179 @@ void ug_hpoly_destroy(ug_hpoly* hp) {
     hipFree(hp->a); hipFree(hp->b); hipFree(hp->c); hipFree(hp->t); hipFree(hp->t2);
     hp->mat.release(); hp->ntt.release();
     delete hp;
+}
+
+// ---- .r1cs: witness check and circuit probe (r1cs.hip) ----------------------------------------------------------------------
+namespace {
+void r1cs_info_of(const ughost::R1csHeader& h, const u64 terms[3], ug_r1cs_info* out) {
+    out->n_wires = h.nWires; out->n_pub_out = h.nPubOut; out->n_pub_in = h.nPubIn; out->n_prv_in = h.nPrvIn;
+    out->n_constraints = h.nConstraints; out->n_labels = h.nLabels;
+    for (int t = 0; t < 3; t++) out->terms[t] = terms[t];
+}
+const u32* r1cs_witness(const ug_r1cs* r, const ug_dvec* w, u64 first) {
+    if (w->ctx->device != r->ctx->device) throw std::invalid_argument("r1cs: the witness lives on another device");
+    if (first > w->n || w->n - first < r->hdr.nWires)
+        throw std::invalid_argument("r1cs: the witness vector is shorter than first + n_wires (" + std::to_string(r->hdr.nWires) + " wires)");
+    return w->data + first * 8;
+}
+// the check of one witness queued on `stream`, its two result words on their way to pinned memory behind it
+void r1cs_queue(ug_r1cs* r, const u32* wtns, int slot, hipStream_t stream, uint8_t* mask_dev, bool timed) {
+    if (timed) UG_HIP(hipEventRecord(r->t0, stream));
+    r1cs_check(r->dev(), wtns, r->words + 2 * slot, mask_dev, stream);
+    if (timed) UG_HIP(hipEventRecord(r->t1, stream));
+    UG_HIP(hipMemcpyAsync(r->words_host + 2 * slot, r->words + 2 * slot, 16, hipMemcpyDeviceToHost, stream));
+    UG_HIP(hipEventRecord(r->done[slot], stream));
+    r->queued[slot].wtns = wtns; r->queued[slot].stream = stream; r->queued[slot].on = true;
+}
+// the slot's result; a failing witness costs a one-lane launch for the three values of its first failing constraint
+void r1cs_read(ug_r1cs* r, int slot, ug_r1cs_report* out) {
+    ug_r1cs::Queued& q = r->queued[slot];
+    if (!q.on) throw std::invalid_argument("r1cs: no check is queued in slot " + std::to_string(slot));
+    q.on = false;
+    UG_HIP(hipEventSynchronize(r->done[slot]));
+    memset(out, 0, sizeof *out);
+    out->failed = r->words_host[2 * slot];
+    if (!out->failed) return;
+    out->first = ~r->words_host[2 * slot + 1];
+    r1cs_row_values(r->dev(), q.wtns, (u32)out->first, r->row_values, q.stream);
+    UG_HIP(hipMemcpyAsync(r->row_values_host, r->row_values, 96, hipMemcpyDeviceToHost, q.stream));
+    UG_HIP(hipStreamSynchronize(q.stream));
+    memcpy(out->a, r->row_values_host, 32); memcpy(out->b, r->row_values_host + 8, 32); memcpy(out->c, r->row_values_host + 16, 32);
+}
+}  // namespace
+
+int ug_r1cs_parse_info(const void* r1cs, uint64_t size, ug_r1cs_info* out) {
+    UG_TRY
+    if (!r1cs || !out) throw std::invalid_argument("null argument");
+    ughost::BinFile f(r1cs, size, "r1cs", 1);
+    const ughost::R1csHeader h = ughost::loadR1csHeader(f);
+    u64 terms[3];
+    ughost::countR1csTerms(f, h, terms);
+    r1cs_info_of(h, terms, out);
+    UG_CATCH
+}
+int ug_r1cs_create(ug_ctx* c, const void* r1cs, uint64_t size, ug_r1cs** out) {
+    UG_TRY
+    if (!c || !r1cs || !out) throw std::invalid_argument("null argument");
+    ughost::BinFile f(r1cs, size, "r1cs", 1);
+    ughost::R1cs host;
+    ughost::loadR1cs(f, host);                                  // every rule of the layout before the first device byte
+    c->use();
+    std::unique_ptr<ug_r1cs, void (*)(ug_r1cs*)> r(new ug_r1cs(), ug_r1cs_destroy);      // frees everything on any throw below
+    r->ctx = c; r->hdr = host.hdr;
+    const size_t rows = host.hdr.nConstraints;
+    for (int t = 0; t < 3; t++) {
+        const size_t n = (size_t)host.terms[t];
+        r->terms[t] = host.terms[t];
+        UG_HIP(hipMalloc(&r->row_ptr[t], (rows + 1) * 4));
+        UG_HIP(hipMalloc(&r->sig[t], n ? n * 4 : 4));
+        UG_HIP(hipMalloc(&r->val[t], n ? n * 32 : 32));
+        host_to_device(c, r->row_ptr[t], host.m[t].rowPtr.data(), (rows + 1) * 4);
+        host_to_device(c, r->sig[t], host.m[t].sig.data(), n * 4);
+        // (the conversion of a chunk's coefficients runs behind that chunk's copy, on the copy's stream)
+        u32* val = r->val[t];
+        host_to_device(c, val, host.m[t].val.data(), n * 32,
+                       [val](size_t off, size_t bytes, hipStream_t st) { r1cs_convert_coefs(val + off / 4, bytes / 32, st); });
+    }
+    const size_t words = ((size_t)ug_r1cs::SLOTS * 2 + 1) * 8;
+    UG_HIP(hipMalloc(&r->words, words));
+    UG_HIP(hipHostMalloc((void**)&r->words_host, words, hipHostMallocDefault));
+    UG_HIP(hipMalloc(&r->row_values, 96));
+    UG_HIP(hipHostMalloc((void**)&r->row_values_host, 96, hipHostMallocDefault));
+    for (int k = 0; k < ug_r1cs::SLOTS; k++) UG_HIP(hipEventCreateWithFlags(&r->done[k], hipEventDisableTiming));
+    UG_HIP(hipEventCreate(&r->t0)); UG_HIP(hipEventCreate(&r->t1));
+    UG_HIP(hipStreamSynchronize(c->stream));
+    *out = r.release();
+    UG_CATCH
+}
+int ug_r1cs_get_info(const ug_r1cs* r, ug_r1cs_info* out) {
+    UG_TRY
+    if (!r || !out) throw std::invalid_argument("null argument");
+    r1cs_info_of(r->hdr, r->terms, out);
+    UG_CATCH
+}
+int ug_r1cs_check(ug_r1cs* r, const ug_dvec* witness, uint64_t first, ug_r1cs_report* out, uint8_t* mask) {
+    UG_TRY
+    if (!r || !witness || !out) throw std::invalid_argument("null argument");
+    ug_ctx* c = r->ctx;
+    c->use();
+    if (c->recording) throw std::invalid_argument("r1cs: no check while the context's stream is being recorded");
+    const u32* w = r1cs_witness(r, witness, first);
+    const size_t rows = r->hdr.nConstraints;
+    struct Mask { uint8_t* p = nullptr; ~Mask() { if (p) hipFree(p); } } md;
+    if (mask && rows) UG_HIP(hipMalloc(&md.p, rows));
+    const int slot = ug_r1cs::SLOTS - 1;
+    r1cs_queue(r, w, slot, c->stream, md.p, /*timed*/ true);
+    if (md.p) UG_HIP(hipMemcpyAsync(mask, md.p, rows, hipMemcpyDeviceToHost, c->stream));
+    UG_HIP(hipStreamSynchronize(c->stream));                    // the one host wait of a witness that holds
+    r1cs_read(r, slot, out);
+    float ms = 0;
+    UG_HIP(hipEventElapsedTime(&ms, r->t0, r->t1));
+    out->device_ms = ms;
+    UG_CATCH
+}
+int ug_r1cs_check_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, int slot, ug_ctx* via) {
+    UG_TRY
+    if (!r || !witness) throw std::invalid_argument("null argument");
+    if (slot < 0 || slot >= UG_BATCH_MAX) throw std::invalid_argument("r1cs: slot outside 0 .. UG_BATCH_MAX - 1");
+    ug_ctx* c = via ? via : r->ctx;
+    if (c->device != r->ctx->device) throw std::invalid_argument("r1cs: the queueing context is on another device");
+    if (c->recording) throw std::invalid_argument("r1cs: no check while the context's stream is being recorded");
+    c->use();
+    r1cs_queue(r, r1cs_witness(r, witness, first), slot, c->stream, nullptr, /*timed*/ false);
+    UG_CATCH
+}
+int ug_r1cs_check_collect(ug_r1cs* r, int slot, ug_r1cs_report* out) {
+    UG_TRY
+    if (!r || !out) throw std::invalid_argument("null argument");
+    if (slot < 0 || slot >= UG_BATCH_MAX) throw std::invalid_argument("r1cs: slot outside 0 .. UG_BATCH_MAX - 1");
+    r->ctx->use();
+    r1cs_read(r, slot, out);
+    UG_CATCH
+}
+int ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* matrix, uint64_t* row) {
+    UG_TRY
+    if (!r || !hp || !matrix || !row) throw std::invalid_argument("null argument");
+    ug_ctx* c = r->ctx;
+    if (hp->ctx->device != c->device) throw std::invalid_argument("r1cs: the coefficient matrix lives on another device");
+    if (hp->nvars != r->hdr.nWires)
+        throw std::invalid_argument("r1cs: not this circuit: " + std::to_string(r->hdr.nWires) + " wires, the zkey has " + std::to_string(hp->nvars));
+    if ((u64)n_public + 1 > r->hdr.nWires)
+        throw std::invalid_argument("r1cs: not this circuit: " + std::to_string(n_public) + " public signals, " + std::to_string(r->hdr.nWires) + " wires");
+    if ((u64)r->hdr.nConstraints + n_public + 1 > hp->domain)
+        throw std::invalid_argument("r1cs: not this circuit: " + std::to_string(r->hdr.nConstraints) + " constraints and " +
+                                    std::to_string(n_public) + " public signals do not fit the zkey's domain of " + std::to_string(hp->domain));
+    c->use();
+    UG_HIP(hipStreamSynchronize(hp->ctx->stream));              // (the matrix may have been built on another context's stream)
+    const size_t n = r->hdr.nWires;
+    std::vector<uint8_t> z(n * 32);
+    ughost::randomBytes(z.data(), z.size());
+    for (size_t i = 0; i < n; i++) z[i * 32 + 31] &= 0x1f;      // below 2^253 < r
+    struct Dev { u32* p = nullptr; ~Dev() { if (p) hipFree(p); } } zd;
+    UG_HIP(hipMalloc(&zd.p, n * 32));
+    host_to_device(c, zd.p, z.data(), n * 32);
+    unsigned long long* word = r->words + 2 * ug_r1cs::SLOTS;
+    unsigned long long* word_host = r->words_host + 2 * ug_r1cs::SLOTS;
+    r1cs_match(r->dev(), hp->mat, n_public, zd.p, word, c->stream);
+    UG_HIP(hipMemcpyAsync(word_host, word, 8, hipMemcpyDeviceToHost, c->stream));
+    UG_HIP(hipStreamSynchronize(c->stream));
+    if (*word_host == ~0ull) { *matrix = -1; *row = 0; }
+    else { *matrix = (int)(*word_host & 1); *row = *word_host >> 1; }
+    UG_CATCH
+}
+void ug_r1cs_destroy(ug_r1cs* r) {
+    if (!r) return;
+    hipSetDevice(r->ctx->device);
+    for (int k = 0; k < ug_r1cs::SLOTS; k++)                    // a check that was queued and never collected may still be running
+        if (r->queued[k].on) hipEventSynchronize(r->done[k]);
+    for (int t = 0; t < 3; t++) { hipFree(r->row_ptr[t]); hipFree(r->sig[t]); hipFree(r->val[t]); }
+    hipFree(r->words); hipFree(r->row_values);
+    if (r->words_host) hipHostFree(r->words_host);
+    if (r->row_values_host) hipHostFree(r->row_values_host);
+    for (int k = 0; k < ug_r1cs::SLOTS; k++) if (r->done[k]) hipEventDestroy(r->done[k]);
+    if (r->t0) hipEventDestroy(r->t0);
+    if (r->t1) hipEventDestroy(r->t1);
+    delete r;
 }
 
 int ug_fr_ntt(ug_ctx* c, void* host_data, int logn, int inverse) {

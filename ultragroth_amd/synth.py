@@ -362,3 +362,21 @@ def build_ultra_circuit(dev, log_domain, mix="C", seed=0x5EED0005, lookup_log=8,
     info = dict(domainSize=domain, nVars=nvars, nPublic=n_public, randIndx=rand_indx, nC1=len(idx1), nC2=len(idx2),
                 lookup=lookup, chunks=n_chunks)
     return zkey, wtns, info
+
+
+def r1cs_file(n_wires, n_pub_out, n_pub_in, rows, n_prv_in=None, n_labels=None, section_order=(1, 2, 3), extra_sections=()):
+    """An .r1cs in the layout of include/ultragroth_hip.h ("WITNESS CHECK"): rows = one (A, B, C) per constraint, each a
+    {wire: coefficient} dict -- or, for a combination that repeats a wire, a list of (wire, coefficient) pairs; the terms are written
+    in the order given. section_order / extra_sections ((id, bytes) pairs, appended) exist for the tests of the reader."""
+    def lc(terms):
+        terms = list(terms.items()) if isinstance(terms, dict) else list(terms)
+        return struct.pack("<I", len(terms)) + b"".join(struct.pack("<I", w) + int(c).to_bytes(32, "little") for w, c in terms)
+
+    if n_prv_in is None:
+        n_prv_in = max(0, n_wires - 1 - n_pub_out - n_pub_in)
+    body = {1: struct.pack("<I", 32) + R_MOD.to_bytes(32, "little") +
+               struct.pack("<IIIIQI", n_wires, n_pub_out, n_pub_in, n_prv_in, n_wires if n_labels is None else n_labels, len(rows)),
+            2: b"".join(lc(a) + lc(b) + lc(c) for a, b, c in rows),
+            3: b"".join(struct.pack("<Q", i) for i in range(n_wires))}
+    secs = [(i, body[i]) for i in section_order] + list(extra_sections)
+    return b"r1cs" + struct.pack("<II", 1, len(secs)) + b"".join(_section(i, p) for i, p in secs)
