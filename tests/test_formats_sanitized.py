@@ -26,7 +26,7 @@ def harness(tmp_path_factory):
     exe = str(tmp / "record_formats_main")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wno-unknown-pragmas", "-I", CSRC,
            os.path.join(ROOT, "tests", "native", "record_formats_main.cpp"), os.path.join(CSRC, "verifier_api.cpp"),
-           os.path.join(CSRC, "host_util.cpp"), "-o", exe]
+           os.path.join(CSRC, "verifier_records.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     return exe

@@ -1,4 +1,5 @@
-// pairing_dev.hpp -- the device pass of batch verification (pairing.hip) as the host code of verifier_api.cpp sees it.
+// pairing_dev.hpp -- the device pass of batch verification (pairing.hip) as the host code of verifier_api.cpp sees it (BatchCall
+// and the test hooks; the record layouts also name the formats that verifier_records.cpp reads on the host).
 #pragma once
 #include <cstddef>
 #include "pairing.hpp"

@@ -16,6 +16,7 @@
 // conj(G)/G (conj = the p^6 Frobenius, w -> -w), which is 1 exactly when G lies in Fq6, i.e. when its odd coefficients
 // vanish: one 761-bit exponentiation, no Fq12 inversion. Like the Miller loop it lives in pairing.hpp, compiled for the
 // host here and for the device in pairing.hip.
+// The JSON parser is json_min.hpp; the packed proof records and their conversions are verifier_records.cpp.
 #include <sys/random.h>
 #include <algorithm>
 #include <atomic>
@@ -32,195 +33,43 @@
 #include <vector>
 #include "ec.hpp"
 #include "host_util.hpp"
+#include "json_min.hpp"
 #include "pairing.hpp"
 #include "pairing_dev.hpp"
+#include "verifier_records.hpp"
 #include "../../include/ultragroth_hip.h"
 #include "../../include/verifier.h"
 
-using namespace ug;
-using namespace ug::pr;
+using namespace ugv;
 using ughost::keccak256;
 
 namespace {
 
-// ---- field wrappers, Fq12, G2 steps and the Miller loop: pairing.hpp (shared with the device) -------------------------
-// decimal string -> value mod q (E.f1.fromString); anything but digits is an error
-F1 f1_from_decimal(const std::string& s) {
-    if (s.empty()) throw std::invalid_argument("not a number");
-    const F1 ten = f1_small(10);
-    F1 acc = f1_zero();
-    for (char ch : s) {
-        if (ch < '0' || ch > '9') throw std::invalid_argument("not a number");
-        acc = acc * ten + f1_small((u32)(ch - '0'));
-    }
-    return acc;
-}
-void f1_to_plain(u32 out[8], const F1& a) { to_normal(out, a.v); }
-
-bool g1_on_curve(const G1A& p) { return p.inf || p.y * p.y == p.x * p.x * p.x + f1_small(3); }
-bool g2_on_curve(const G2A& q) {
-    if (q.inf) return true;
-    static const F2 b = f2_scale(f2_inv(F2{f1_small(9), f1_small(1)}), f1_small(3));     // 3 / (9 + u)
-    return q.y * q.y == q.x * q.x * q.x + b;
-}
-
-// the constants of the Miller loop and of the final exponentiation's is-one test (pairing.hpp, shared with the device)
+// ---- field wrappers, Fq12, G2 steps, the Miller loop, the final exponentiation's is-one test and their constants: pairing.hpp ----
 const FinalExpConsts& consts() { static const FinalExpConsts c = final_exp_consts(); return c; }
-bool final_exponentiation_is_one(const F12& f) {
-    F12 hard;
-    return final_exp_is_one(consts(), f, hard);
-}
 
-// the four / five Miller loops are independent: one host thread each
-bool pairing_check(const std::vector<G1A>& a, const std::vector<G2A>& b) {
+// start * prod_i miller(g2[i], g1[i]) is one after the final exponentiation. The Miller loops are independent: one host thread each.
+// Pairs with a point at infinity are skipped (src/groth16.cpp:679-681).
+bool pairing_product_is_one(const F12& start, const std::vector<G1A>& g1, const std::vector<G2A>& g2) {
     std::vector<std::future<F12>> parts;
-    for (size_t i = 0; i < a.size(); i++) {
-        if (!pair_live(a[i], b[i])) continue;                       // src/groth16.cpp:679-681
-        parts.push_back(std::async(std::launch::async, [&, i] { return miller(consts(), b[i], a[i]); }));
+    for (size_t i = 0; i < g1.size(); i++) {
+        if (!pair_live(g1[i], g2[i])) continue;
+        parts.push_back(std::async(std::launch::async, [&, i] { return miller(consts(), g2[i], g1[i]); }));
     }
-    F12 acc = f12_one();
+    F12 acc = start, hard;
     for (auto& p : parts) acc = f12_mul(consts(), acc, p.get());
-    return final_exponentiation_is_one(acc);
+    return final_exp_is_one(consts(), acc, hard);
 }
 
 // ---- G1 arithmetic for vkX (ec.hpp, host) -------------------------------------------------------------------------------
 G1XYZZ to_xyzz(const G1A& p) { return p.inf ? xyzz_inf<Fq>() : xyzz_from_affine(p.x.v, p.y.v); }
 G1A from_xyzz(const G1XYZZ& p) {
-    if (is_inf(p)) return G1A{f1_zero(), f1_zero(), true};
+    if (is_inf(p)) return g1_inf();
     Fq x, y;
     xyzz_to_affine(x, y, p);
     return G1A{F1{x}, F1{y}, false};
 }
 G1A g1_neg(const G1A& p) { return p.inf ? p : G1A{p.x, -p.y, false}; }
-
-// ---- minimal JSON (objects, arrays, strings, numbers, literals): what nlohmann::json::parse accepts of it --------------
-struct JVal {
-    enum Type { Null, Bool, Number, String, Array, Object } type = Null;
-    std::string str;                       // String: the text; Number: its literal
-    bool integral = false;
-    std::vector<JVal> arr;
-    std::vector<std::pair<std::string, JVal>> obj;
-    const JVal& at(const char* key) const {
-        if (type != Object) throw std::invalid_argument("not an object");
-        const JVal* hit = nullptr;
-        for (const auto& kv : obj) if (kv.first == key) hit = &kv.second;          // later duplicates win, as nlohmann
-        if (!hit) throw std::invalid_argument("missing key");
-        return *hit;
-    }
-    const JVal& at(size_t i) const {
-        if (type != Array || i >= arr.size()) throw std::invalid_argument("not an array element");
-        return arr[i];
-    }
-    const std::string& string() const {
-        if (type != String) throw std::invalid_argument("not a string");
-        return str;
-    }
-};
-struct JParser {
-    const char* p;
-    explicit JParser(const char* s) : p(s) {}
-    void ws() { while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r') p++; }
-    [[noreturn]] void bad() { throw std::invalid_argument("malformed json"); }
-    JVal parse_document() {
-        JVal v = value(0);
-        ws();
-        if (*p) bad();
-        return v;
-    }
-    JVal value(int depth) {
-        if (depth > 64) bad();
-        ws();
-        JVal v;
-        if (*p == '{') {
-            v.type = JVal::Object; p++; ws();
-            if (*p == '}') { p++; return v; }
-            for (;;) {
-                ws();
-                if (*p != '"') bad();
-                std::string key = string_literal();
-                ws();
-                if (*p != ':') bad();
-                p++;
-                v.obj.emplace_back(std::move(key), value(depth + 1));
-                ws();
-                if (*p == ',') { p++; continue; }
-                if (*p == '}') { p++; return v; }
-                bad();
-            }
-        }
-        if (*p == '[') {
-            v.type = JVal::Array; p++; ws();
-            if (*p == ']') { p++; return v; }
-            for (;;) {
-                v.arr.push_back(value(depth + 1));
-                ws();
-                if (*p == ',') { p++; continue; }
-                if (*p == ']') { p++; return v; }
-                bad();
-            }
-        }
-        if (*p == '"') { v.type = JVal::String; v.str = string_literal(); return v; }
-        if (!strncmp(p, "true", 4)) { p += 4; v.type = JVal::Bool; return v; }
-        if (!strncmp(p, "false", 5)) { p += 5; v.type = JVal::Bool; return v; }
-        if (!strncmp(p, "null", 4)) { p += 4; return v; }
-        if (*p == '-' || (*p >= '0' && *p <= '9')) {
-            const char* s = p;
-            if (*p == '-') p++;
-            if (*p == '0') p++;
-            else if (*p >= '1' && *p <= '9') while (*p >= '0' && *p <= '9') p++;
-            else bad();
-            v.integral = true;
-            if (*p == '.') { v.integral = false; p++; if (*p < '0' || *p > '9') bad(); while (*p >= '0' && *p <= '9') p++; }
-            if (*p == 'e' || *p == 'E') {
-                v.integral = false; p++;
-                if (*p == '+' || *p == '-') p++;
-                if (*p < '0' || *p > '9') bad();
-                while (*p >= '0' && *p <= '9') p++;
-            }
-            v.type = JVal::Number; v.str.assign(s, p);
-            return v;
-        }
-        bad();
-    }
-    std::string string_literal() {
-        std::string out;
-        p++;                                                        // opening quote
-        for (;;) {
-            unsigned char ch = (unsigned char)*p;
-            if (ch == 0 || ch < 0x20) bad();
-            if (ch == '"') { p++; return out; }
-            if (ch == '\\') {
-                p++;
-                switch (*p) {
-                    case '"': out += '"'; break;   case '\\': out += '\\'; break; case '/': out += '/'; break;
-                    case 'b': out += '\b'; break;  case 'f': out += '\f'; break;  case 'n': out += '\n'; break;
-                    case 'r': out += '\r'; break;  case 't': out += '\t'; break;
-                    case 'u': {
-                        unsigned cp = 0;
-                        for (int i = 1; i <= 4; i++) {
-                            char h = p[i];
-                            cp <<= 4;
-                            if (h >= '0' && h <= '9') cp |= (unsigned)(h - '0');
-                            else if (h >= 'a' && h <= 'f') cp |= (unsigned)(h - 'a' + 10);
-                            else if (h >= 'A' && h <= 'F') cp |= (unsigned)(h - 'A' + 10);
-                            else bad();
-                        }
-                        p += 4;
-                        if (cp < 0x80) out += (char)cp;
-                        else if (cp < 0x800) { out += (char)(0xc0 | (cp >> 6)); out += (char)(0x80 | (cp & 0x3f)); }
-                        else { out += (char)(0xe0 | (cp >> 12)); out += (char)(0x80 | ((cp >> 6) & 0x3f)); out += (char)(0x80 | (cp & 0x3f)); }
-                        break;
-                    }
-                    default: bad();
-                }
-                p++;
-                continue;
-            }
-            out += (char)ch;
-            p++;
-        }
-    }
-};
 
 // G1PointAffineFromJson / G2PointAffineFromJson (src/groth16.cpp:254-268): x and y only; (0, 0) is the point at infinity
 G1A g1_from_json(const JVal& v) {
@@ -235,21 +84,22 @@ G2A g2_from_json(const JVal& v) {
     return q;
 }
 
-// decimal string -> value mod r as a plain 256-bit integer (E.fr.fromString, then fromMontgomery in verify())
-void fr_plain_from_decimal(u32 out[8], const std::string& s) {
-    if (s.empty()) throw std::invalid_argument("not a number");
-    u32 ten[8] = {10, 0, 0, 0, 0, 0, 0, 0};
-    const Fr t = from_normal<FrParams>(ten);
-    Fr acc = fp_zero<FrParams>();
-    for (char ch : s) {
-        if (ch < '0' || ch > '9') throw std::invalid_argument("not a number");
-        u32 d[8] = {(u32)(ch - '0'), 0, 0, 0, 0, 0, 0, 0};
-        acc = canon(add(canon(mul(acc, t)), from_normal<FrParams>(d)));
-    }
-    to_normal(out, acc);
-}
-
+// ---- one key and one proof for both protocols ---------------------------------------------------------------------------------
 struct Inputs { std::vector<std::vector<u32>> plain; };
+struct Key {
+    bool ultra = false;
+    G1A alpha, ic_rand;                    // ic_rand: infinity for Groth16
+    G2A beta, gamma, delta[2];             // delta[s] pairs with the proofs' G1 point s: (C) or (pi_f, pi_r)
+    std::vector<G1A> ic;
+    int k() const { return ultra ? 2 : 1; }
+    size_t cols() const { return ic.size() + (ultra ? 1 : 0); }    // columns of vkX: IC_0 .. IC_nPublic [, IC_rand]
+};
+struct BatchProof : Points {
+    Inputs in;
+    u32 challenge[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // UltraGroth, set by the batch: derive_challenge of pi_r
+    bool no_point = false;                 // a compressed record whose x has no y on the curve: INVALID like a point off its curve
+};
+
 Inputs parse_inputs(const char* text) {                             // src/verifier.cpp:59-86
     Inputs in;
     try {
@@ -263,66 +113,48 @@ Inputs parse_inputs(const char* text) {                             // src/verif
     } catch (...) { throw std::invalid_argument("invalid inputs data"); }
     return in;
 }
-
-struct Groth16Proof { G1A a, c; G2A b; };
-struct Groth16Key { G1A alpha; G2A beta, gamma, delta; std::vector<G1A> ic; };
-struct UltraProof { G1A a, final_commit, round_commit; G2A b; };
-struct UltraKey { G1A alpha, ic_rand; G2A beta, gamma, final_delta, round_delta; std::vector<G1A> ic; };
-
-Groth16Proof parse_proof(const char* text) {                        // :16-36
+Points parse_proof(const char* text, bool ultra) {                  // :16-57
     try {
         JVal j = JParser(text).parse_document();
-        if (j.at("protocol").string() != "groth16") throw std::invalid_argument("invalid proof data");
-        return Groth16Proof{g1_from_json(j.at("pi_a")), g1_from_json(j.at("pi_c")), g2_from_json(j.at("pi_b"))};
+        if (j.at("protocol").string() != (ultra ? "ultragroth" : "groth16")) throw std::invalid_argument("invalid proof data");
+        Points p;
+        p.a = g1_from_json(j.at("pi_a"));
+        p.b = g2_from_json(j.at("pi_b"));
+        p.g[0] = g1_from_json(j.at(ultra ? "pi_f" : "pi_c"));
+        p.g[1] = ultra ? g1_from_json(j.at("pi_r")) : g1_inf();
+        return p;
     } catch (...) { throw std::invalid_argument("invalid proof data"); }
 }
-UltraProof parse_ultra_proof(const char* text) {                    // :38-57
+Key parse_key(const char* text, bool ultra) {                       // :88-146, src/ultra_groth.cpp:543-563
     try {
         JVal j = JParser(text).parse_document();
-        if (j.at("protocol").string() != "ultragroth") throw std::invalid_argument("invalid proof data");
-        return UltraProof{g1_from_json(j.at("pi_a")), g1_from_json(j.at("pi_f")), g1_from_json(j.at("pi_r")), g2_from_json(j.at("pi_b"))};
-    } catch (...) { throw std::invalid_argument("invalid proof data"); }
-}
-void check_key_header(const JVal& j, const char* protocol) {
-    const JVal& np = j.at("nPublic");
-    if (np.type != JVal::Number) throw std::invalid_argument("nPublic");
-    if (j.at("protocol").string() != protocol || j.at("curve").string() != "bn128") throw std::invalid_argument("protocol");
-}
-std::vector<G1A> parse_ic(const JVal& j) {
-    std::vector<G1A> ic;
-    const JVal& a = j.at("IC");
-    if (a.type == JVal::Array) for (const JVal& e : a.arr) ic.push_back(g1_from_json(e));
-    else if (a.type == JVal::Object) for (const auto& kv : a.obj) ic.push_back(g1_from_json(kv.second));   // json::items()
-    if (ic.empty()) throw std::invalid_argument("IC");
-    return ic;
-}
-Groth16Key parse_key(const char* text) {                            // :88-116
-    try {
-        JVal j = JParser(text).parse_document();
-        check_key_header(j, "groth16");
-        Groth16Key k{g1_from_json(j.at("vk_alpha_1")), g2_from_json(j.at("vk_beta_2")), g2_from_json(j.at("vk_gamma_2")),
-                     g2_from_json(j.at("vk_delta_2")), {}};
-        k.ic = parse_ic(j);
+        if (j.at("nPublic").type != JVal::Number) throw std::invalid_argument("nPublic");
+        if (j.at("protocol").string() != (ultra ? "ultragroth" : "groth16") || j.at("curve").string() != "bn128") throw std::invalid_argument("protocol");
+        Key k;
+        k.ultra = ultra;
+        k.alpha = g1_from_json(j.at("vk_alpha_1"));
+        k.beta = g2_from_json(j.at("vk_beta_2"));
+        k.gamma = g2_from_json(j.at("vk_gamma_2"));
+        k.delta[0] = g2_from_json(j.at(ultra ? "vk_delta_c2_2" : "vk_delta_2"));
+        k.delta[1] = ultra ? g2_from_json(j.at("vk_delta_c1_2")) : k.delta[0];
+        const JVal& a = j.at("IC");
+        if (a.type == JVal::Array) for (const JVal& e : a.arr) k.ic.push_back(g1_from_json(e));
+        else if (a.type == JVal::Object) for (const auto& kv : a.obj) k.ic.push_back(g1_from_json(kv.second));   // json::items()
+        if (k.ic.empty()) throw std::invalid_argument("IC");
+        k.ic_rand = ultra ? g1_from_json(j.at("IC_rand")) : g1_inf();
         return k;
     } catch (...) { throw std::invalid_argument("invalid verification key data"); }
 }
-UltraKey parse_ultra_key(const char* text) {                        // :118-146, src/ultra_groth.cpp:543-563
-    try {
-        JVal j = JParser(text).parse_document();
-        check_key_header(j, "ultragroth");
-        UltraKey k{g1_from_json(j.at("vk_alpha_1")), {}, g2_from_json(j.at("vk_beta_2")), g2_from_json(j.at("vk_gamma_2")),
-                   g2_from_json(j.at("vk_delta_c2_2")), g2_from_json(j.at("vk_delta_c1_2")), {}};
-        k.ic = parse_ic(j);
-        k.ic_rand = g1_from_json(j.at("IC_rand"));
-        return k;
-    } catch (...) { throw std::invalid_argument("invalid verification key data"); }
+// the proof and the inputs of one proof from their texts, with what the single call says of them
+BatchProof parse_texts(const char* proof, const char* inputs, bool ultra) {
+    if (!proof || !inputs) throw std::invalid_argument("null argument");
+    BatchProof p;
+    static_cast<Points&>(p) = parse_proof(proof, ultra);
+    p.in = parse_inputs(inputs);
+    return p;
 }
-
-// sum_i input_i IC[i+1]  (the loops at src/groth16.cpp:322-332, src/ultra_groth.cpp:589-601)
-G1XYZZ inputs_combination(const Inputs& in, const std::vector<G1A>& ic) {
-    G1XYZZ acc = xyzz_inf<Fq>();
-    for (size_t i = 0; i < in.plain.size(); i++) acc = xyzz_add(acc, xyzz_mul_scalar(to_xyzz(ic[i + 1]), in.plain[i].data(), 256));
-    return acc;
+void check_length(size_t inputs, size_t ic_size, bool ultra) {      // src/groth16.cpp:318-320, src/ultra_groth.cpp:585-587
+    if (inputs + 1 != ic_size) throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
 }
 
 // derive_challenge (src/ultra_groth.cpp:33-58): keccak256(x_BE32 || y_BE32) of the round commitment as a big-endian
@@ -341,14 +173,55 @@ void derive_challenge_plain(u32 out[8], const G1A& commit) {
     to_normal(out, from_normal<FrParams>(w));                       // from_normal reduces values >= r
 }
 
-bool all_on_curve(std::initializer_list<const G1A*> g1, std::initializer_list<const G2A*> g2) {
-    for (const G1A* p : g1) if (!g1_on_curve(*p)) return false;
-    for (const G2A* q : g2) if (!g2_on_curve(*q)) return false;
-    return true;
+bool proof_on_curve(const BatchProof& p) {
+    return !p.no_point && g1_on_curve(p.a) && g1_on_curve(p.g[0]) && g1_on_curve(p.g[1]) && g2_on_curve(p.b);
+}
+bool key_on_curve(const Key& key) {
+    bool ok = g1_on_curve(key.alpha) && g1_on_curve(key.ic_rand);
+    for (const G1A& p : key.ic) ok = ok && g1_on_curve(p);
+    for (const G2A* q : {&key.beta, &key.gamma, &key.delta[0], &key.delta[1]}) ok = ok && g2_on_curve(*q);
+    return ok;
+}
+
+// The single-proof verifier on parsed values (p.in already has the key's length): VALID or INVALID.
+// Points that are not on their curve can only come from malformed data: no pairing is defined for them.
+int verify_one(const Key& key, const BatchProof& p) {
+    if (!proof_on_curve(p) || !key_on_curve(key)) return VERIFIER_INVALID_PROOF;
+    G1XYZZ vk = to_xyzz(key.ic[0]);                                 // the loops at src/groth16.cpp:322-332, src/ultra_groth.cpp:589-612
+    for (size_t i = 0; i < p.in.plain.size(); i++) vk = xyzz_add(vk, xyzz_mul_scalar(to_xyzz(key.ic[i + 1]), p.in.plain[i].data(), 256));
+    if (key.ultra) {
+        u32 rand[8];
+        derive_challenge_plain(rand, p.g[1]);
+        vk = xyzz_add(vk, xyzz_mul_scalar(to_xyzz(key.ic_rand), rand, 256));
+    }
+    std::vector<G1A> g1{p.a, g1_neg(key.alpha), g1_neg(from_xyzz(vk))};
+    std::vector<G2A> g2{p.b, key.beta, key.gamma};
+    for (int s = 0; s < key.k(); s++) { g1.push_back(g1_neg(p.g[s])); g2.push_back(key.delta[s]); }
+    return pairing_product_is_one(f12_one(), g1, g2) ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
 }
 
 void copy_error(char* dst, unsigned long cap, const char* msg) {
     if (dst && cap) strncpy(dst, msg, cap);                         // as the reference: no terminator added beyond strncpy's
+}
+// what a call returns; whatever it throws is VERIFIER_ERROR and its text
+template <class Fn> int guarded(char* error_msg, unsigned long error_msg_maxsize, const Fn& call) {
+    try {
+        return call();
+    } catch (std::exception& e) {
+        copy_error(error_msg, error_msg_maxsize, e.what());
+    } catch (...) {
+        copy_error(error_msg, error_msg_maxsize, "unknown error");
+    }
+    return VERIFIER_ERROR;
+}
+int verify_texts(bool ultra, const char* proof, const char* inputs, const char* verification_key, char* error_msg, unsigned long error_msg_maxsize) {
+    return guarded(error_msg, error_msg_maxsize, [&] {
+        if (!verification_key) throw std::invalid_argument("null argument");
+        const BatchProof p = parse_texts(proof, inputs, ultra);
+        const Key key = parse_key(verification_key, ultra);
+        check_length(p.in.plain.size(), key.ic.size(), ultra);
+        return verify_one(key, p);
+    });
 }
 
 }  // namespace
@@ -357,53 +230,11 @@ extern "C" {
 
 int groth16_verify(const char* proof, const char* inputs, const char* verification_key, char* error_msg,
                    unsigned long error_msg_maxsize) {
-    try {
-        if (!proof || !inputs || !verification_key) throw std::invalid_argument("null argument");
-        Groth16Proof pr = parse_proof(proof);
-        Inputs in = parse_inputs(inputs);
-        Groth16Key key = parse_key(verification_key);
-        if (in.plain.size() + 1 != key.ic.size()) throw std::invalid_argument("len(inputs)+1 != len(vk.IC)");     // src/groth16.cpp:318-320
-        // points that are not on their curve can only come from malformed data: no pairing is defined for them
-        if (!all_on_curve({&pr.a, &pr.c, &key.alpha}, {&pr.b, &key.beta, &key.gamma, &key.delta})) return VERIFIER_INVALID_PROOF;
-        for (const G1A& p : key.ic) if (!g1_on_curve(p)) return VERIFIER_INVALID_PROOF;
-        G1A vkx = from_xyzz(xyzz_add(inputs_combination(in, key.ic), to_xyzz(key.ic[0])));
-        bool ok = pairing_check({pr.a, g1_neg(key.alpha), g1_neg(vkx), g1_neg(pr.c)}, {pr.b, key.beta, key.gamma, key.delta});
-        return ok ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
-    } catch (std::exception& e) {
-        copy_error(error_msg, error_msg_maxsize, e.what());
-        return VERIFIER_ERROR;
-    } catch (...) {
-        copy_error(error_msg, error_msg_maxsize, "unknown error");
-        return VERIFIER_ERROR;
-    }
+    return verify_texts(false, proof, inputs, verification_key, error_msg, error_msg_maxsize);
 }
-
 int ultra_groth_verify(const char* proof, const char* inputs, const char* verification_key, char* error_msg,
                        unsigned long error_msg_maxsize) {
-    try {
-        if (!proof || !inputs || !verification_key) throw std::invalid_argument("null argument");
-        UltraProof pr = parse_ultra_proof(proof);
-        Inputs in = parse_inputs(inputs);
-        UltraKey key = parse_ultra_key(verification_key);
-        if (in.plain.size() + 1 != key.ic.size()) throw std::invalid_argument("len(inputs) != len(vk.IC)");       // src/ultra_groth.cpp:585-587
-        if (!all_on_curve({&pr.a, &pr.final_commit, &pr.round_commit, &key.alpha, &key.ic_rand},
-                          {&pr.b, &key.beta, &key.gamma, &key.final_delta, &key.round_delta})) return VERIFIER_INVALID_PROOF;
-        for (const G1A& p : key.ic) if (!g1_on_curve(p)) return VERIFIER_INVALID_PROOF;
-        u32 rand[8];
-        derive_challenge_plain(rand, pr.round_commit);                                                             // :603-609
-        G1XYZZ vk = xyzz_add(inputs_combination(in, key.ic), to_xyzz(key.ic[0]));
-        vk = xyzz_add(vk, xyzz_mul_scalar(to_xyzz(key.ic_rand), rand, 256));                                       // :609-612
-        G1A vkx = from_xyzz(vk);
-        bool ok = pairing_check({pr.a, g1_neg(key.alpha), g1_neg(vkx), g1_neg(pr.final_commit), g1_neg(pr.round_commit)},
-                                {pr.b, key.beta, key.gamma, key.final_delta, key.round_delta});
-        return ok ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
-    } catch (std::exception& e) {
-        copy_error(error_msg, error_msg_maxsize, e.what());
-        return VERIFIER_ERROR;
-    } catch (...) {
-        copy_error(error_msg, error_msg_maxsize, "unknown error");
-        return VERIFIER_ERROR;
-    }
+    return verify_texts(true, proof, inputs, verification_key, error_msg, error_msg_maxsize);
 }
 
 }  // extern "C"
@@ -460,20 +291,6 @@ template <class Fn> void parallel_for(size_t n, const Fn& fn) {
     for (auto& t : pool) t.join();
 }
 
-struct BatchKey {
-    bool ultra = false;
-    G1A alpha, ic_rand;
-    G2A beta, gamma, delta[2];             // delta[s] pairs with the proofs' G1 point s: (C) or (pi_f, pi_r)
-    std::vector<G1A> ic;
-    int k() const { return ultra ? 2 : 1; }
-};
-struct BatchProof {
-    G1A a, g[2];
-    G2A b;
-    Inputs in;
-    u32 challenge[8];
-    bool no_point = false;                 // a compressed record whose x has no y on the curve: INVALID like a point off its curve
-};
 enum State { DONE, SINGLE, BATCH };
 
 bool g2_in_subgroup(const G2A& q) {
@@ -503,7 +320,7 @@ struct BatchTrace {
 
 // one pass: the proofs idx[0..m) of the call, their trees and prefix sums
 struct Pass {
-    const BatchKey& key;
+    const Key& key;
     size_t m, cols;
     int k;
     std::vector<u32> f_tree, g_tree;
@@ -511,7 +328,7 @@ struct Pass {
     std::vector<size_t> level_off, level_size;
     unsigned long long checks = 0;
 
-    Pass(const BatchKey& key_, size_t m_) : key(key_), m(m_), cols(key_.ic.size() + (key_.ultra ? 1 : 0)), k(key_.k()) {
+    Pass(const Key& key_, size_t m_) : key(key_), m(m_), cols(key_.cols()), k(key_.k()) {
         size_t off = 0;
         for (size_t n = m;; n = (n + 1) / 2) { level_off.push_back(off); level_size.push_back(n); off += n; if (n <= 1) break; }
         f_tree.resize(off * F12_WORDS);
@@ -523,28 +340,18 @@ struct Pass {
         const size_t lo = j << level, hi = std::min(m, (j + 1) << level), node = level_off[level] + j;
         std::vector<std::vector<u32>> sc(cols, std::vector<u32>(8));
         for (size_t c = 0; c < cols; c++) to_normal(sc[c].data(), sub<1>(prefix[hi * cols + c], prefix[lo * cols + c]));
-        std::vector<G1A> g1;
-        std::vector<G2A> g2;
-        g1.push_back(g1_neg(from_xyzz(xyzz_mul_scalar_w4(to_xyzz(key.alpha), sc[0].data()))));
-        g2.push_back(key.beta);
         G1XYZZ vkx = xyzz_mul_scalar_w4(to_xyzz(key.ic[0]), sc[0].data());
         for (size_t c = 1; c < key.ic.size(); c++) vkx = xyzz_add(vkx, xyzz_mul_scalar_w4(to_xyzz(key.ic[c]), sc[c].data()));
         if (key.ultra) vkx = xyzz_add(vkx, xyzz_mul_scalar_w4(to_xyzz(key.ic_rand), sc[cols - 1].data()));
-        g1.push_back(g1_neg(from_xyzz(vkx)));
-        g2.push_back(key.gamma);
+        std::vector<G1A> g1{g1_neg(from_xyzz(xyzz_mul_scalar_w4(to_xyzz(key.alpha), sc[0].data()))), g1_neg(from_xyzz(vkx))};
+        std::vector<G2A> g2{key.beta, key.gamma};
         for (int s = 0; s < k; s++) {
             g1.push_back(g1_neg(from_xyzz(xyzz_load(&g_tree[(node * k + s) * XYZZ_WORDS]))));
             g2.push_back(key.delta[s]);
         }
-        std::vector<std::future<F12>> parts;
-        for (size_t i = 0; i < g1.size(); i++) {
-            if (g1[i].inf || g2[i].inf) continue;
-            parts.push_back(std::async(std::launch::async, [&, i] { return miller(consts(), g2[i], g1[i]); }));
-        }
-        F12 acc;
-        f12_load(acc, &f_tree[node * F12_WORDS]);
-        for (auto& p : parts) acc = f12_mul(consts(), acc, p.get());
-        return final_exponentiation_is_one(acc);
+        F12 f;                                                      // the product of the node's miller(B_i, r_i A_i)
+        f12_load(f, &f_tree[node * F12_WORDS]);
+        return pairing_product_is_one(f, g1, g2);
     }
     // node j of `level` failed: the positions (within the pass) that the single verifier has to judge
     void walk(size_t level, size_t j, std::vector<size_t>& suspects) {
@@ -607,11 +414,21 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// The suspects of a call, each decided by judge_proof: on `device` in launches of at most PAIRING_PASS, on host threads for
-// device < 0. valid[s] answers suspect s.
-void judge_suspects(const BatchKey& key, int device, const std::vector<const BatchProof*>& sus, std::vector<char>& valid,
+// The arrays of a pass or of a launch of the judge (pairing_dev.hpp) from the proofs idx[0..m) of `proofs`; idx == nullptr: its first m.
+void pack_points(const std::vector<BatchProof>& proofs, const size_t* idx, size_t m, int k, u32* a, u32* b, u32* g) {
+    parallel_for(m, [&](size_t i) {
+        const Points& p = proofs[idx ? idx[i] : i];
+        g1_words(a + i * G1_WORDS, p.a);
+        g2_words(b + i * G2_WORDS, p.b);
+        for (int s = 0; s < k; s++) g1_words(g + (i * k + s) * G1_WORDS, p.g[s]);
+    });
+}
+
+// The suspects sus[] of a call (positions in `proofs`), each decided by judge_proof: on `device` in launches of at most PAIRING_PASS,
+// on host threads for device < 0. valid[s] answers suspect s.
+void judge_suspects(const Key& key, int device, const std::vector<BatchProof>& proofs, const std::vector<size_t>& sus, std::vector<char>& valid,
                     ug_verify_batch_stats_ex& stats) {
-    const size_t n = sus.size(), k = (size_t)key.k(), cols = key.ic.size() + (key.ultra ? 1 : 0);
+    const size_t n = sus.size(), k = (size_t)key.k(), cols = key.cols();
     std::vector<u32> points(cols * G1_WORDS), key_g2((1 + k) * G2_WORDS), f_ab(F12_WORDS);
     for (size_t c = 0; c < key.ic.size(); c++) g1_words(&points[c * G1_WORDS], key.ic[c]);
     if (key.ultra) g1_words(&points[(cols - 1) * G1_WORDS], key.ic_rand);
@@ -623,11 +440,9 @@ void judge_suspects(const BatchKey& key, int device, const std::vector<const Bat
     for (size_t first = 0; first < n; first += PAIRING_PASS) {
         const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
         std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS), scalars(m * cols * 8, 0), verdict(m, 0);
+        pack_points(proofs, &sus[first], m, (int)k, a.data(), b.data(), g.data());
         parallel_for(m, [&](size_t i) {
-            const BatchProof& p = *sus[first + i];
-            g1_words(&a[i * G1_WORDS], p.a);
-            g2_words(&b[i * G2_WORDS], p.b);
-            for (size_t s = 0; s < k; s++) g1_words(&g[(i * k + s) * G1_WORDS], p.g[s]);
+            const BatchProof& p = proofs[sus[first + i]];
             u32* sc = &scalars[i * cols * 8];
             sc[0] = 1;                                              // IC_0 itself
             for (size_t c = 0; c < p.in.plain.size(); c++) memcpy(sc + (1 + c) * 8, p.in.plain[c].data(), 8 * sizeof(u32));
@@ -660,228 +475,47 @@ void judge_suspects(const BatchKey& key, int device, const std::vector<const Bat
     stats.judged += n;
 }
 
-// ---- packed proof records (include/verifier.h) --------------------------------------------------------------------------------
-// A record is the proof.json whose decimal strings are its integers; these are the two directions of that sentence.
-// The layouts (UG_RECORDS_*): plain little-endian coordinates, the big-endian EVM order with the imaginary half of an Fq2
-// coordinate first, and compressed -- x and two flag bits per point. Every layout is read into the same points and written from
-// them, so a conversion is a read and a write, and a record of any layout stands for the plain record it converts to.
-constexpr bool known_format(int format) { return format == RECORDS_PLAIN || format == RECORDS_EVM || format == RECORDS_COMPRESSED; }
-constexpr size_t record_bytes(bool ultra, int format = RECORDS_PLAIN) { return record_words(ultra ? 2 : 1, format) * sizeof(u32); }
-constexpr size_t g1_bytes(int format) { return format == RECORDS_COMPRESSED ? 32 : 64; }      // a G2 point takes twice that
-static_assert((int)UG_RECORDS_PLAIN == (int)RECORDS_PLAIN && (int)UG_RECORDS_EVM == (int)RECORDS_EVM && (int)UG_RECORDS_COMPRESSED == (int)RECORDS_COMPRESSED, "layouts");
-const DecompressConsts& root_consts() { static const DecompressConsts c = decompress_consts(); return c; }
-
-// decimal string -> 256-bit integer, little-endian; false for anything but digits and for a value >= 2^256
-bool u256_from_decimal(uint8_t out[32], const std::string& s) {
-    if (s.empty()) return false;
-    u32 w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (char ch : s) {
-        if (ch < '0' || ch > '9') return false;
-        uint64_t carry = (uint64_t)(ch - '0');
-        for (int k = 0; k < 8; k++) { const uint64_t v = (uint64_t)w[k] * 10 + carry; w[k] = (u32)v; carry = v >> 32; }
-        if (carry) return false;
-    }
-    memcpy(out, w, 32);
-    return true;
-}
-std::string u256_to_decimal(const uint8_t in[32]) {
-    u32 w[8];
-    memcpy(w, in, 32);
-    std::vector<u32> chunks;                                        // base 10^9, lowest first
-    u32 any;
-    do {
-        uint64_t rem = 0;
-        any = 0;
-        for (int k = 7; k >= 0; k--) { const uint64_t v = (rem << 32) | w[k]; w[k] = (u32)(v / 1000000000u); rem = v % 1000000000u; any |= w[k]; }
-        chunks.push_back((u32)rem);
-    } while (any);
-    char buf[16];
-    snprintf(buf, sizeof buf, "%u", chunks.back());
-    std::string digits = buf;
-    for (size_t c = chunks.size() - 1; c-- > 0;) { snprintf(buf, sizeof buf, "%09u", chunks[c]); digits += buf; }
-    return digits;
-}
-F1 f1_from_u256(const uint8_t* p) {                                 // any 256-bit value, reduced mod q as f1_from_decimal reduces
-    u32 w[8];
-    memcpy(w, p, 32);
-    return F1{canon(from_normal<FqParams>(w))};
-}
-G1A g1_from_record(const uint8_t* p) {
-    G1A a{f1_from_u256(p), f1_from_u256(p + 32), false};
-    a.inf = is0(a.x) && is0(a.y);
-    return a;
-}
-G2A g2_from_record(const uint8_t* p) {
-    G2A q{F2{f1_from_u256(p), f1_from_u256(p + 32)}, F2{f1_from_u256(p + 64), f1_from_u256(p + 96)}, false};
-    q.inf = is0(q.x) && is0(q.y);
-    return q;
-}
-void reverse32(uint8_t* out, const uint8_t* in) { for (int i = 0; i < 32; i++) out[i] = in[31 - i]; }
-F1 f1_from_be256(const uint8_t* p) {
-    uint8_t le[32];
-    reverse32(le, p);
-    return f1_from_u256(le);
-}
-void f1_to_le256(uint8_t* p, const F1& a) {
-    u32 w[8];
-    f1_to_plain(w, a);
-    memcpy(p, w, 32);
-}
-void f1_to_be256(uint8_t* p, const F1& a) {
-    uint8_t le[32];
-    f1_to_le256(le, a);
-    reverse32(p, le);
-}
-// One point of a record in `format`. false: a compressed x without a y on the curve; the point is then left at infinity.
-bool g1_from_layout(int format, const uint8_t* p, G1A& out) {
-    if (format == RECORDS_PLAIN) { out = g1_from_record(p); return true; }
-    if (format == RECORDS_EVM) {
-        out = G1A{f1_from_be256(p), f1_from_be256(p + 32), false};
-        out.inf = is0(out.x) && is0(out.y);
-        return true;
-    }
-    uint8_t x[32];
-    memcpy(x, p, 32);
-    const bool inf = (x[31] & 0x40) != 0, larger = (x[31] & 0x80) != 0;
-    x[31] &= 0x3f;
-    out = G1A{f1_zero(), f1_zero(), true};
-    if (inf) return true;
-    const F1 xv = f1_from_u256(x);
-    F1 y;
-    if (!g1_decompress(root_consts(), xv, larger, y)) return false;
-    out = G1A{xv, y, false};
-    return true;
-}
-bool g2_from_layout(int format, const uint8_t* p, G2A& out) {
-    if (format == RECORDS_PLAIN) { out = g2_from_record(p); return true; }
-    if (format == RECORDS_EVM) {                                    // x.c1, x.c0, y.c1, y.c0
-        out = G2A{F2{f1_from_be256(p + 32), f1_from_be256(p)}, F2{f1_from_be256(p + 96), f1_from_be256(p + 64)}, false};
-        out.inf = is0(out.x) && is0(out.y);
-        return true;
-    }
-    uint8_t x1[32];
-    memcpy(x1, p + 32, 32);
-    const bool inf = (x1[31] & 0x40) != 0, larger = (x1[31] & 0x80) != 0;
-    x1[31] &= 0x3f;
-    out = g2_inf();
-    if (inf) return true;
-    const F2 xv{f1_from_u256(p), f1_from_u256(x1)};
-    F2 y;
-    if (!g2_decompress(root_consts(), xv, larger, y)) return false;
-    out = G2A{xv, y, false};
-    return true;
-}
-// ... and the way back, every coordinate reduced. false: a point off its curve has no compressed form (a sign bit cannot stand for it).
-bool g1_to_layout(int format, const G1A& pt, uint8_t* p) {
-    memset(p, 0, g1_bytes(format));
-    if (format == RECORDS_COMPRESSED) {
-        if (pt.inf) { p[31] = 0x40; return true; }
-        if (!g1_on_curve(pt)) return false;
-        f1_to_le256(p, pt.x);
-        if (f1_larger(root_consts(), pt.y)) p[31] |= 0x80;
-        return true;
-    }
-    if (pt.inf) return true;
-    if (format == RECORDS_EVM) { f1_to_be256(p, pt.x); f1_to_be256(p + 32, pt.y); }
-    else { f1_to_le256(p, pt.x); f1_to_le256(p + 32, pt.y); }
-    return true;
-}
-bool g2_to_layout(int format, const G2A& q, uint8_t* p) {
-    memset(p, 0, 2 * g1_bytes(format));
-    if (format == RECORDS_COMPRESSED) {
-        if (q.inf) { p[63] = 0x40; return true; }
-        if (!g2_on_curve(q)) return false;
-        f1_to_le256(p, q.x.a); f1_to_le256(p + 32, q.x.b);
-        if (f2_larger(root_consts(), q.y)) p[63] |= 0x80;
-        return true;
-    }
-    if (q.inf) return true;
-    if (format == RECORDS_EVM) { f1_to_be256(p, q.x.b); f1_to_be256(p + 32, q.x.a); f1_to_be256(p + 64, q.y.b); f1_to_be256(p + 96, q.y.a); }
-    else { f1_to_le256(p, q.x.a); f1_to_le256(p + 32, q.x.b); f1_to_le256(p + 64, q.y.a); f1_to_le256(p + 96, q.y.b); }
-    return true;
-}
-// a whole record: pi_a | pi_b | the one or two other G1 points. ok[0..3] say which of a, b, g[0], g[1] the record held.
-struct RecordPoints { G1A a, g[2]; G2A b; bool ok[4]; };
-bool record_read(int format, bool ultra, const uint8_t* rec, RecordPoints& pts) {
-    const size_t w = g1_bytes(format);
-    pts.g[1] = G1A{f1_zero(), f1_zero(), true};
-    pts.ok[0] = g1_from_layout(format, rec, pts.a);
-    pts.ok[1] = g2_from_layout(format, rec + w, pts.b);
-    pts.ok[2] = g1_from_layout(format, rec + 3 * w, pts.g[0]);
-    pts.ok[3] = !ultra || g1_from_layout(format, rec + 4 * w, pts.g[1]);
-    return pts.ok[0] && pts.ok[1] && pts.ok[2] && pts.ok[3];
-}
-bool record_write(int format, bool ultra, const RecordPoints& pts, uint8_t* rec) {
-    const size_t w = g1_bytes(format);
-    bool ok = g1_to_layout(format, pts.a, rec);
-    ok = g2_to_layout(format, pts.b, rec + w) && ok;
-    ok = g1_to_layout(format, pts.g[0], rec + 3 * w) && ok;
-    if (ultra) ok = g1_to_layout(format, pts.g[1], rec + 4 * w) && ok;
-    return ok;
-}
-// an input block of n_pub values in the byte order of `format` -> plain little-endian (EVM: every value byte-reversed)
-void inputs_to_plain(int format, const uint8_t* in, size_t n_pub, uint8_t* out) {
-    if (format != RECORDS_EVM) { memmove(out, in, n_pub * 32); return; }
-    for (size_t c = 0; c < n_pub; c++) { uint8_t t[32]; reverse32(t, in + c * 32); memcpy(out + c * 32, t, 32); }
-}
-std::string record_to_json(bool ultra, const uint8_t* rec) {
-    auto g1 = [&](size_t at) { return "[\"" + u256_to_decimal(rec + at) + "\",\"" + u256_to_decimal(rec + at + 32) + "\",\"1\"]"; };
-    std::string t = "{\"pi_a\":" + g1(0) + ",\"pi_b\":[[\"" + u256_to_decimal(rec + 64) + "\",\"" + u256_to_decimal(rec + 96) + "\"],[\"" +
-                    u256_to_decimal(rec + 128) + "\",\"" + u256_to_decimal(rec + 160) + "\"],[\"1\",\"0\"]],";
-    if (ultra) t += "\"pi_f\":" + g1(192) + ",\"pi_r\":" + g1(256) + ",\"protocol\":\"ultragroth\"";
-    else t += "\"pi_c\":" + g1(192) + ",\"protocol\":\"groth16\"";
-    return t + ",\"curve\":\"bn128\"}";
-}
-std::string inputs_to_json(const uint8_t* in, size_t n_pub) {
-    std::string t = "[";
-    for (size_t c = 0; c < n_pub; c++) t += (c ? ",\"" : "\"") + u256_to_decimal(in + c * 32) + "\"";
-    return t + "]";
-}
-
-// Where the proofs of a call come from: JSON texts or packed records. parse() is step 1 of the batch for proof i and throws what the
-// single call would say; single() is the single-proof verifier on the same proof.
+// Where the proofs of a call come from: JSON texts or packed records (verifier_records.cpp). check() is the call's test of its
+// arguments; parse() is step 1 of the batch for proof i and throws what the single call would say.
 struct Source {
     bool ultra = false;
     virtual ~Source() {}
+    // null_argument: count, key or verdicts already are one. The order of the tests is the order of the messages.
+    virtual void check(int count, bool null_argument) const = 0;
     // points = false: only what the host needs of a proof that stays on the device -- the inputs and the challenge
     virtual void parse(size_t i, BatchProof& p, size_t ic_size, bool points) const = 0;
-    virtual int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const = 0;
-    virtual const uint8_t* raw() const { return nullptr; }          // packed records, for the device to ingest
-    virtual int raw_format() const { return RECORDS_PLAIN; }        // ... and their layout
-    virtual size_t inputs_per_proof() const { return 0; }           // records: the call's n_pub, the same for every proof
+    const uint8_t* records = nullptr;      // packed records, for the device to ingest (texts: none)
+    int format = RECORDS_PLAIN;            // ... their layout
+    size_t n_pub = 0;                      // ... and their inputs per proof, the same for every proof
 };
 struct JsonSource : Source {
-    const char* const* proofs = nullptr;
-    const char* const* inputs = nullptr;
-    void parse(size_t i, BatchProof& p, size_t ic_size, bool) const override {
-        if (!proofs[i] || !inputs[i]) throw std::invalid_argument("null argument");
-        if (ultra) { UltraProof u = parse_ultra_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.final_commit; p.g[1] = u.round_commit; }
-        else { Groth16Proof u = parse_proof(proofs[i]); p.a = u.a; p.b = u.b; p.g[0] = u.c; p.g[1] = G1A{f1_zero(), f1_zero(), true}; }
-        p.in = parse_inputs(inputs[i]);
-        if (p.in.plain.size() + 1 != ic_size) throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
+    const char* const* proofs;
+    const char* const* inputs;
+    JsonSource(bool ultra_, const char* const* proofs_, const char* const* inputs_) : proofs(proofs_), inputs(inputs_) { ultra = ultra_; }
+    void check(int count, bool null_argument) const override {     // null arrays fail the call as a null key does
+        if (null_argument || (count > 0 && (!proofs || !inputs))) throw std::invalid_argument("null argument");
     }
-    int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const override {
-        return (ultra ? ultra_groth_verify : groth16_verify)(proofs[i], inputs[i], verification_key, msg, cap);
+    void parse(size_t i, BatchProof& p, size_t ic_size, bool) const override {
+        p = parse_texts(proofs[i], inputs[i], ultra);
+        check_length(p.in.plain.size(), ic_size, ultra);
     }
 };
 struct RecordSource : Source {
-    const uint8_t* records = nullptr;
-    const uint8_t* inputs = nullptr;
-    size_t n_pub = 0;
-    int format = RECORDS_PLAIN;
+    const uint8_t* inputs;
+    RecordSource(bool ultra_, int format_, const void* records_, const void* inputs_, int n_pub_) : inputs(static_cast<const uint8_t*>(inputs_)) {
+        ultra = ultra_; format = format_; records = static_cast<const uint8_t*>(records_); n_pub = (size_t)std::max(n_pub_, 0);
+    }
+    void check(int count, bool null_argument) const override {
+        if (!known_format(format)) throw std::invalid_argument("format: not one of UG_RECORDS_PLAIN, UG_RECORDS_EVM, UG_RECORDS_COMPRESSED");
+        if (null_argument || (count > 0 && (!records || !inputs))) throw std::invalid_argument("null argument");
+        if (!n_pub) throw std::invalid_argument("invalid inputs data");
+    }
     // points = false reads pi_r only (the challenge); not even that of a compressed record, whose pi_r the device's ingest leaves
     void parse(size_t i, BatchProof& p, size_t, bool points) const override {
         const uint8_t* rec = records + i * record_bytes(ultra, format);
-        const size_t w = g1_bytes(format);
-        bool held = true;
-        p.g[1] = G1A{f1_zero(), f1_zero(), true};
-        if (ultra && (points || format != RECORDS_COMPRESSED)) held = g1_from_layout(format, rec + 4 * w, p.g[1]);
-        if (points) {
-            held = g1_from_layout(format, rec, p.a) && held;
-            held = g2_from_layout(format, rec + w, p.b) && held;
-            held = g1_from_layout(format, rec + 3 * w, p.g[0]) && held;
-        }
-        p.no_point = !held;
+        p.g[1] = g1_inf();
+        p.no_point = points && !record_read(format, ultra, rec, p);
+        if (!points && ultra && format != RECORDS_COMPRESSED) record_read_pi_r(format, rec, p.g[1]);
         p.in.plain.assign(n_pub, std::vector<u32>(8));
         for (size_t c = 0; c < n_pub; c++) {                        // reduced mod r, as fr_plain_from_decimal
             uint8_t le[32];
@@ -891,123 +525,78 @@ struct RecordSource : Source {
             to_normal(p.in.plain[c].data(), from_normal<FrParams>(v));
         }
     }
-    int single(size_t i, const char* verification_key, char* msg, unsigned long cap) const override {
-        const uint8_t* rec = records + i * record_bytes(ultra, format);
-        const uint8_t* block = inputs + i * n_pub * 32;
-        uint8_t plain[320];
-        std::vector<uint8_t> plain_in;
-        if (format != RECORDS_PLAIN) {                              // the plain record and block this one stands for
-            RecordPoints pts;
-            if (!record_read(format, ultra, rec, pts)) return VERIFIER_INVALID_PROOF;
-            record_write(RECORDS_PLAIN, ultra, pts, plain);
-            plain_in.resize(n_pub * 32);
-            inputs_to_plain(format, block, n_pub, plain_in.data());
-            rec = plain; block = plain_in.data();
-        }
-        const std::string proof = record_to_json(ultra, rec), in = inputs_to_json(block, n_pub);
-        return (ultra ? ultra_groth_verify : groth16_verify)(proof.c_str(), in.c_str(), verification_key, msg, cap);
-    }
-    const uint8_t* raw() const override { return records; }
-    int raw_format() const override { return format; }
-    size_t inputs_per_proof() const override { return n_pub; }
 };
 
-int verify_batch(const Source& src, int device, int count, const char* verification_key,
-                 int* verdicts, const BatchOptions& opt, ug_verify_batch_stats_ex* stats_out, char* error_msg, unsigned long error_msg_maxsize) {
-    try {
-        const auto t_start = std::chrono::steady_clock::now();
-        const bool ultra = src.ultra;
-        if (count < 0 || !verification_key || (count > 0 && !verdicts)) throw std::invalid_argument("null argument");
-        ug_verify_batch_stats_ex stats_ex = {{0, 0, 0, 0.0, 0.0}, 0, 0, 0.0};
-        ug_verify_batch_stats& stats = stats_ex.base;
-        BatchKey key;
-        key.ultra = ultra;
-        if (ultra) {
-            UltraKey k = parse_ultra_key(verification_key);
-            key.alpha = k.alpha; key.ic_rand = k.ic_rand; key.beta = k.beta; key.gamma = k.gamma;
-            key.delta[0] = k.final_delta; key.delta[1] = k.round_delta; key.ic = k.ic;
-        } else {
-            Groth16Key k = parse_key(verification_key);
-            key.alpha = k.alpha; key.ic_rand = G1A{f1_zero(), f1_zero(), true}; key.beta = k.beta; key.gamma = k.gamma;
-            key.delta[0] = k.delta; key.delta[1] = k.delta; key.ic = k.ic;
-        }
-        if (src.inputs_per_proof() && src.inputs_per_proof() + 1 != key.ic.size())      // (texts: checked per proof, in parse)
-            throw std::invalid_argument(ultra ? "len(inputs) != len(vk.IC)" : "len(inputs)+1 != len(vk.IC)");
-        double phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};                // where the call's time goes (ug_verify_batch_phase_ms)
-        auto t_lap = t_start;
-        auto lap = [&](int k) { const auto now = std::chrono::steady_clock::now(); phase[k] += std::chrono::duration<double, std::milli>(now - t_lap).count(); t_lap = now; };
-        bool key_ok = g1_on_curve(key.alpha) && g1_on_curve(key.ic_rand);
-        for (const G1A& p : key.ic) key_ok = key_ok && g1_on_curve(p);
-        for (const G2A* q : {&key.beta, &key.gamma, &key.delta[0], &key.delta[1]}) key_ok = key_ok && g2_on_curve(*q) && g2_in_subgroup(*q);
+// where a call's time goes: the indices of ug_verify_batch_phase_ms
+enum Phase { PHASE_KEY, PHASE_PARSE, PHASE_SUBGROUP, PHASE_SCALARS, PHASE_PACKING, PHASE_PASS, PHASE_SEARCH, PHASE_SINGLES, PHASES };
+static_assert(PHASES == 8, "ug_verify_batch_phase_ms writes 8 values");
 
-        const size_t n = (size_t)count;
-        std::vector<int> verdict(n, VERIFIER_ERROR);
-        std::vector<State> state(n, key_ok ? BATCH : SINGLE);
-        std::vector<BatchProof> parsed(key_ok ? n : 0);
-        std::vector<std::string> message(n);
-        const bool hooks = ughost::testHooksEnabled();
+// One call of the batch verifier. Proofs that are not packed records on a device are gathered: (1) parsed on the host, (2) those with
+// B outside the subgroup set aside, (3) the rest packed into the arrays of a pass. Packed records on a device are resident: 1-3 happen
+// there, per pass. Either way a pass ends in run_pass, and (4) what the passes left undecided goes to the judge or to verify_one.
+struct BatchCall {
+    const Source& src;
+    const int device;
+    const BatchOptions opt;
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    const Key key;
+    const size_t n;
+    const bool key_ok;                     // else no batching: every proof that parses is verify_one's
+    const bool resident, hooks;
+    std::vector<State> state;
+    std::vector<int> verdict;
+    std::vector<BatchProof> parsed;
+    std::vector<std::string> message;      // of the proofs whose verdict stays VERIFIER_ERROR
+    ug_verify_batch_stats_ex stats = {{0, 0, 0, 0.0, 0.0}, 0, 0, 0.0};
+    double phase[PHASES] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::chrono::steady_clock::time_point t_lap = t_start;
+
+    BatchCall(const Source& src_, int device_, size_t count, const char* verification_key, const BatchOptions& opt_)
+        : src(src_), device(device_), opt(opt_), key(parse_key(verification_key, src_.ultra)), n(count), key_ok(batchable(key)),
+          resident(key_ok && device_ >= 0 && src_.records), hooks(ughost::testHooksEnabled()), state(count, SINGLE), verdict(count, VERIFIER_ERROR),
+          parsed(count), message(count) {
+        if (src.records) check_length(src.n_pub, key.ic.size(), key.ultra);      // (texts: checked per proof, in parse)
         if (hooks) { std::lock_guard<std::mutex> lock(g_trace.m); g_trace.index.clear(); g_trace.r.clear(); g_trace.f.clear(); g_trace.in_place = g_trace.gathered = 0; }
-        // the scalars of a pass and the prefix sums of its proofs idx[0..m)
-        auto draw_scalars = [&](Pass& pass, const size_t* idx, std::vector<u32>& r) {
-            const size_t m = pass.m;
-            r.resize(m * 4);
-            for (size_t got = 0; got < r.size() * sizeof(u32);) {
-                const ssize_t w = getrandom((uint8_t*)r.data() + got, r.size() * sizeof(u32) - got, 0);
-                if (w <= 0) throw std::runtime_error("getrandom failed");
-                got += (size_t)w;
-            }
-            for (size_t i = 0; i < m; i++) if (!(r[4 * i] | r[4 * i + 1] | r[4 * i + 2] | r[4 * i + 3])) r[4 * i] = 1;       // (2^-128)
-            pass.prefix.assign((m + 1) * pass.cols, fp_zero<FrParams>());
-            std::vector<Fr> term(m * pass.cols);
-            parallel_for(m, [&](size_t i) {
-                const BatchProof& p = parsed[idx[i]];
-                const u32 rw[8] = {r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], 0, 0, 0, 0};
-                const Fr rf = fr_from_plain(rw);
-                Fr* t = &term[i * pass.cols];
-                t[0] = rf;
-                for (size_t c = 0; c < p.in.plain.size(); c++) t[1 + c] = canon(mul(rf, fr_from_plain(p.in.plain[c].data())));
-                if (ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
-            });
-            for (size_t i = 0; i < m; i++)
-                for (size_t c = 0; c < pass.cols; c++)
-                    pass.prefix[(i + 1) * pass.cols + c] = canon(add(pass.prefix[i * pass.cols + c], term[i * pass.cols + c]));
-        };
-        // the trees of a pass are there: the root check, the search of a rejected pass, the verdicts
-        auto settle = [&](Pass& pass, const size_t* idx, const std::vector<u32>& r) {
-            const size_t m = pass.m;
-            if (hooks) {
-                std::lock_guard<std::mutex> lock(g_trace.m);
-                for (size_t i = 0; i < m; i++) g_trace.index.push_back((int)idx[i]);
-                g_trace.r.insert(g_trace.r.end(), r.begin(), r.end());
-                g_trace.f.insert(g_trace.f.end(), pass.f_tree.begin(), pass.f_tree.begin() + m * F12_WORDS);
-            }
-            const size_t top = pass.level_size.size() - 1;
-            std::vector<size_t> suspects;
-            if (!pass.node_ok(top, 0)) {
-                if (opt.judge) pass.search(top, 0, (size_t)opt.search_width, suspects);
-                else pass.walk(top, 0, suspects);
-            }
-            for (size_t i = 0; i < m; i++) { verdict[idx[i]] = VERIFIER_VALID_PROOF; state[idx[i]] = DONE; }
-            for (size_t s : suspects) state[idx[s]] = SINGLE;
-            stats.batch_checks += pass.checks;
-        };
-        const bool resident = key_ok && device >= 0 && src.raw();
-        lap(0);
-        // 1. parse; what the single call would answer before any pairing is answered here
-        if (key_ok && !resident) parallel_for(n, [&](size_t i) {
-            state[i] = DONE;
+        lap(PHASE_KEY);
+    }
+    static bool batchable(const Key& key) {                         // every point on its curve, every G2 point in the subgroup
+        bool ok = key_on_curve(key);
+        for (const G2A* q : {&key.beta, &key.gamma, &key.delta[0], &key.delta[1]}) ok = ok && g2_in_subgroup(*q);
+        return ok;
+    }
+    void lap(Phase p) {
+        const auto now = std::chrono::steady_clock::now();
+        phase[p] += std::chrono::duration<double, std::milli>(now - t_lap).count();
+        t_lap = now;
+    }
+
+    int run(int* verdicts, char* error_msg, unsigned long error_msg_maxsize) {
+        if (resident) resident_passes();
+        else { parse_all(); gathered_passes(set_aside_off_subgroup()); }
+        decide_singles();
+        return finish(verdicts, error_msg, error_msg_maxsize);
+    }
+
+    // 1. parse; what the single call would answer before any pairing is answered here. Under a key the batch refuses the parse is
+    //    the first step of the single verifier, which every proof is then handed to.
+    void parse_all() {
+        parallel_for(n, [&](size_t i) {
+            state[i] = key_ok ? DONE : SINGLE;
             try {
                 BatchProof& p = parsed[i];
                 src.parse(i, p, key.ic.size(), true);
-                if (p.no_point || !g1_on_curve(p.a) || !g1_on_curve(p.g[0]) || !g1_on_curve(p.g[1]) || !g2_on_curve(p.b)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
-                if (ultra) derive_challenge_plain(p.challenge, p.g[1]);
+                if (!key_ok) return;
+                if (!proof_on_curve(p)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
+                if (key.ultra) derive_challenge_plain(p.challenge, p.g[1]);
                 state[i] = BATCH;
             } catch (std::exception& e) { message[i] = e.what(); }
         });
-        lap(1);
-        // 2. B outside the subgroup: out of the batch
-        std::vector<size_t> cand;
-        if (!resident) for (size_t i = 0; i < n; i++) if (state[i] == BATCH) cand.push_back(i);
+        lap(PHASE_PARSE);
+    }
+    // 2. B outside the subgroup: out of the batch. Returns the proofs that stay in it.
+    std::vector<size_t> set_aside_off_subgroup() {
+        std::vector<size_t> cand, idx;
+        for (size_t i = 0; i < n; i++) if (state[i] == BATCH) cand.push_back(i);
         if (device < 0) {
             parallel_for(cand.size(), [&](size_t c) { if (!g2_in_subgroup(parsed[cand[c]].b)) state[cand[c]] = SINGLE; });
         } else if (!cand.empty()) {
@@ -1023,57 +612,111 @@ int verify_batch(const Source& src, int device, int count, const char* verificat
             std::vector<uint8_t> reasons(cand.size(), UG_POINT_OK);            // one call answers for every point
             if (ug_points_check_mask(ctx.c, 1, rec.data(), cand.size(), 2, reasons.data()) != UG_OK) throw std::runtime_error(ug_last_error());
             for (size_t c = 0; c < cand.size(); c++) if (reasons[c] != UG_POINT_OK) state[cand[c]] = SINGLE;
-            stats.device_ms += ms_since(t0);
+            stats.base.device_ms += ms_since(t0);
         }
-        std::vector<size_t> idx;
-        for (size_t i : cand) { if (state[i] == BATCH) idx.push_back(i); else stats.off_subgroup++; }
-        lap(2);
-        // 3. the batch, in passes
+        for (size_t i : cand) { if (state[i] == BATCH) idx.push_back(i); else stats.base.off_subgroup++; }
+        lap(PHASE_SUBGROUP);
+        return idx;
+    }
+    // the scalars of a pass and the prefix sums of its proofs idx[0..m)
+    void draw_scalars(Pass& pass, const size_t* idx, std::vector<u32>& r) {
+        const size_t m = pass.m;
+        r.resize(m * 4);
+        for (size_t got = 0; got < r.size() * sizeof(u32);) {
+            const ssize_t w = getrandom((uint8_t*)r.data() + got, r.size() * sizeof(u32) - got, 0);
+            if (w <= 0) throw std::runtime_error("getrandom failed");
+            got += (size_t)w;
+        }
+        for (size_t i = 0; i < m; i++) if (!(r[4 * i] | r[4 * i + 1] | r[4 * i + 2] | r[4 * i + 3])) r[4 * i] = 1;       // (2^-128)
+        pass.prefix.assign((m + 1) * pass.cols, fp_zero<FrParams>());
+        std::vector<Fr> term(m * pass.cols);
+        parallel_for(m, [&](size_t i) {
+            const BatchProof& p = parsed[idx[i]];
+            const u32 rw[8] = {r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], 0, 0, 0, 0};
+            const Fr rf = fr_from_plain(rw);
+            Fr* t = &term[i * pass.cols];
+            t[0] = rf;
+            for (size_t c = 0; c < p.in.plain.size(); c++) t[1 + c] = canon(mul(rf, fr_from_plain(p.in.plain[c].data())));
+            if (key.ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
+        });
+        for (size_t i = 0; i < m; i++)
+            for (size_t c = 0; c < pass.cols; c++)
+                pass.prefix[(i + 1) * pass.cols + c] = canon(add(pass.prefix[i * pass.cols + c], term[i * pass.cols + c]));
+    }
+    // the trees of a pass are there: the root check, the search of a rejected pass, the verdicts
+    void settle(Pass& pass, const size_t* idx) {
+        const size_t top = pass.level_size.size() - 1;
+        std::vector<size_t> suspects;
+        if (!pass.node_ok(top, 0)) {
+            if (opt.judge) pass.search(top, 0, (size_t)opt.search_width, suspects);
+            else pass.walk(top, 0, suspects);
+        }
+        for (size_t i = 0; i < pass.m; i++) { verdict[idx[i]] = VERIFIER_VALID_PROOF; state[idx[i]] = DONE; }
+        for (size_t s : suspects) state[idx[s]] = SINGLE;
+        stats.base.batch_checks += pass.checks;
+    }
+    // One pass over the proofs idx[0..pass.m) of the call: scalars and prefix sums, the trees from make_trees(r, kernel_ms) -- host_trees,
+    // pairing_batch_device or ResidentBatch::run --, then the checks. The one place that accounts a pass's device time and leaves its
+    // kernel times and, for the test hooks, its scalars and leaves (hook_counter: which kind of resident pass it was).
+    template <class MakeTrees> void run_pass(Pass& pass, const size_t* idx, unsigned long long* hook_counter, const MakeTrees& make_trees) {
+        std::vector<u32> r;
+        draw_scalars(pass, idx, r);
+        lap(PHASE_SCALARS);
+        const auto t0 = std::chrono::steady_clock::now();
+        double kernel_ms[3] = {0, 0, 0};
+        make_trees(r.data(), kernel_ms);
+        if (device >= 0) stats.base.device_ms += ms_since(t0);
+        {
+            std::lock_guard<std::mutex> lock(g_trace.m);
+            if (device >= 0) for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = kernel_ms[t];
+            if (hooks) {
+                for (size_t i = 0; i < pass.m; i++) g_trace.index.push_back((int)idx[i]);
+                g_trace.r.insert(g_trace.r.end(), r.begin(), r.end());
+                g_trace.f.insert(g_trace.f.end(), pass.f_tree.begin(), pass.f_tree.begin() + pass.m * F12_WORDS);
+                if (hook_counter) ++*hook_counter;
+            }
+        }
+        lap(PHASE_PASS);
+        settle(pass, idx);
+        lap(PHASE_SEARCH);
+    }
+    // 3. the batch, in passes
+    void gathered_passes(const std::vector<size_t>& idx) {
         for (size_t first = 0; first < idx.size(); first += PAIRING_PASS) {
             const size_t m = std::min<size_t>(PAIRING_PASS, idx.size() - first);
             Pass pass(key, m);
             const int k = pass.k;
-            std::vector<u32> r, a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS);
-            draw_scalars(pass, &idx[first], r);
-            lap(3);
-            parallel_for(m, [&](size_t i) {
-                const BatchProof& p = parsed[idx[first + i]];
-                g1_words(&a[i * G1_WORDS], p.a);
-                g2_words(&b[i * G2_WORDS], p.b);
-                for (int s = 0; s < k; s++) g1_words(&g[(i * k + s) * G1_WORDS], p.g[s]);
-            });
-            lap(4);
-            if (device < 0) pass.host_trees(a.data(), b.data(), g.data(), r.data());
-            else {
-                const auto t0 = std::chrono::steady_clock::now();
+            std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS);
+            pack_points(parsed, &idx[first], m, k, a.data(), b.data(), g.data());
+            lap(PHASE_PACKING);
+            run_pass(pass, &idx[first], nullptr, [&](const u32* r, double kernel_ms[3]) {
+                if (device < 0) { pass.host_trees(a.data(), b.data(), g.data(), r); return; }
                 PairingBatch pb;
-                pb.n = (int)m; pb.k = k; pb.a = a.data(); pb.b = b.data(); pb.g = g.data(); pb.r = r.data();
+                pb.n = (int)m; pb.k = k; pb.a = a.data(); pb.b = b.data(); pb.g = g.data(); pb.r = r;
                 pb.f_tree = pass.f_tree.data(); pb.g_tree = pass.g_tree.data();
                 pairing_batch_device(device, consts(), pb);
-                stats.device_ms += ms_since(t0);
-                { std::lock_guard<std::mutex> lock(g_trace.m); for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = pb.kernel_ms[t]; }
-            }
-            lap(5);
-            settle(pass, &idx[first], r);
-            lap(6);
+                for (int t = 0; t < 3; t++) kernel_ms[t] = pb.kernel_ms[t];
+            });
         }
-        // 1-3 for packed records on a device, per pass of PAIRING_PASS records: the raw records cross PCIe once, the device reduces
-        // and checks them and keeps the arrays of the Miller kernel; the host reads no coordinate of a proof that stays in the
-        // batch (UltraGroth: pi_r, for the challenge). Off its curve: INVALID; pi_b off the subgroup: SINGLE, as in step 2.
-        for (size_t first = 0; resident && first < n; first += PAIRING_PASS) {
+    }
+    // 1-3 for packed records on a device, per pass of PAIRING_PASS records: the raw records cross PCIe once, the device reduces
+    // and checks them and keeps the arrays of the Miller kernel; the host reads no coordinate of a proof that stays in the
+    // batch (UltraGroth: pi_r, for the challenge). Off its curve: INVALID; pi_b off the subgroup: SINGLE, as in step 2.
+    void resident_passes() {
+        const int k = key.k(), format = src.format;
+        const bool late_challenge = key.ultra && format == RECORDS_COMPRESSED;     // pi_r.y is the device's to find: no host root per proof
+        for (size_t first = 0; first < n; first += PAIRING_PASS) {
             const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
-            const int k = key.k(), format = src.raw_format();
-            const bool late_challenge = ultra && format == RECORDS_COMPRESSED;     // pi_r.y is the device's to find: no host root per proof
             parallel_for(m, [&](size_t i) {
                 BatchProof& p = parsed[first + i];
                 src.parse(first + i, p, key.ic.size(), false);
-                if (ultra && !late_challenge) derive_challenge_plain(p.challenge, p.g[1]);
+                if (key.ultra && !late_challenge) derive_challenge_plain(p.challenge, p.g[1]);
             });
-            lap(1);
-            auto t0 = std::chrono::steady_clock::now();
+            lap(PHASE_PARSE);
+            const auto t0 = std::chrono::steady_clock::now();
             ResidentBatch rb(device, (int)m, k, format);
             std::vector<uint8_t> status(m);
-            rb.ingest(src.raw() + first * record_bytes(ultra, format), status.data());
+            rb.ingest(src.records + first * record_bytes(key.ultra, format), status.data());
             if (late_challenge) {                                   // the rows of pi_r as the ingest decompressed them
                 std::vector<u32> g(m * (size_t)k * G1_WORDS);
                 rb.download(nullptr, nullptr, g.data());
@@ -1084,55 +727,46 @@ int verify_batch(const Source& src, int device, int count, const char* verificat
                     derive_challenge_plain(p.challenge, p.g[1]);
                 });
             }
-            stats.device_ms += ms_since(t0);
+            stats.base.device_ms += ms_since(t0);
             std::vector<size_t> kept;
             std::vector<u32> keep;
             for (size_t i = 0; i < m; i++) {
                 if (status[i] == UG_POINT_OK) { kept.push_back(first + i); keep.push_back((u32)i); state[first + i] = BATCH; }
-                else if (status[i] == UG_POINT_OFF_SUBGROUP) { state[first + i] = SINGLE; stats.off_subgroup++; }
+                else if (status[i] == UG_POINT_OFF_SUBGROUP) { state[first + i] = SINGLE; stats.base.off_subgroup++; }
                 else { state[first + i] = DONE; verdict[first + i] = VERIFIER_INVALID_PROOF; }
             }
-            lap(2);
+            lap(PHASE_SUBGROUP);
             if (kept.empty()) continue;
             Pass pass(key, kept.size());
-            std::vector<u32> r;
-            draw_scalars(pass, kept.data(), r);
-            lap(3);
-            t0 = std::chrono::steady_clock::now();
-            double kernel_ms[3];
-            rb.run(consts(), kept.size() == m ? nullptr : keep.data(), (int)kept.size(), r.data(), pass.f_tree.data(), pass.g_tree.data(), kernel_ms);
-            stats.device_ms += ms_since(t0);
-            {
-                std::lock_guard<std::mutex> lock(g_trace.m);
-                for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = kernel_ms[t];
-                if (hooks) (kept.size() == m ? g_trace.in_place : g_trace.gathered)++;
-            }
-            lap(5);
-            settle(pass, kept.data(), r);
-            lap(6);
+            const bool in_place = kept.size() == m;
+            run_pass(pass, kept.data(), in_place ? &g_trace.in_place : &g_trace.gathered, [&](const u32* r, double kernel_ms[3]) {
+                rb.run(consts(), in_place ? nullptr : keep.data(), (int)kept.size(), r, pass.f_tree.data(), pass.g_tree.data(), kernel_ms);
+            });
         }
-        // 4. whatever is left: to the judge when it is on and the suspects are many enough (never under a key the batch refused),
-        //    else to the single verifier on the host threads
+    }
+    // 4. whatever is left: to the judge when it is on and the suspects are many enough (never under a key the batch refused),
+    //    else to verify_one on the host threads. Proofs that stayed on the device are rebuilt from the raw records first.
+    void decide_singles() {
         std::vector<size_t> singles;
         for (size_t i = 0; i < n; i++) if (state[i] == SINGLE) singles.push_back(i);
+        if (resident) parallel_for(singles.size(), [&](size_t s) { src.parse(singles[s], parsed[singles[s]], key.ic.size(), true); });
         if (opt.judge && key_ok && !singles.empty() && singles.size() >= (size_t)opt.judge_min) {
-            if (resident) parallel_for(singles.size(), [&](size_t s) { src.parse(singles[s], parsed[singles[s]], key.ic.size(), true); });   // rebuilt from the raw records
-            std::vector<const BatchProof*> sus;
-            for (size_t i : singles) sus.push_back(&parsed[i]);
             std::vector<char> valid;
-            judge_suspects(key, device, sus, valid, stats_ex);
+            judge_suspects(key, device, parsed, singles, valid, stats);
             for (size_t s = 0; s < singles.size(); s++) verdict[singles[s]] = valid[s] ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
             singles.clear();
         }
         parallel_for(singles.size(), [&](size_t s) {
             const size_t i = singles[s];
-            char msg[256] = {0};
-            verdict[i] = src.single(i, verification_key, msg, sizeof msg - 1);
-            if (verdict[i] == VERIFIER_ERROR) message[i] = msg;
+            if (!message[i].empty()) return;                        // (it did not parse)
+            try { verdict[i] = verify_one(key, parsed[i]); }
+            catch (std::exception& e) { message[i] = e.what(); }
         });
-        stats.single_checks = singles.size();
-        lap(7);
-        { std::lock_guard<std::mutex> lock(g_trace.m); for (int k = 0; k < 8; k++) g_trace.phase_ms[k] = phase[k]; }
+        stats.base.single_checks = singles.size();
+        lap(PHASE_SINGLES);
+    }
+    int finish(int* verdicts, char* error_msg, unsigned long error_msg_maxsize) {
+        { std::lock_guard<std::mutex> lock(g_trace.m); for (int k = 0; k < PHASES; k++) g_trace.phase_ms[k] = phase[k]; }
         int rc = VERIFIER_VALID_PROOF;
         for (size_t i = 0; i < n; i++) {
             verdicts[i] = verdict[i];
@@ -1143,178 +777,78 @@ int verify_batch(const Source& src, int device, int count, const char* verificat
                 copy_error(error_msg, error_msg_maxsize, text);
             }
         }
-        stats.host_ms = ms_since(t_start) - stats.device_ms;
-        if (stats_out) *stats_out = stats_ex;
+        stats.base.host_ms = ms_since(t_start) - stats.base.device_ms;
         return rc;
-    } catch (std::exception& e) {
-        copy_error(error_msg, error_msg_maxsize, e.what());
-        return VERIFIER_ERROR;
-    } catch (...) {
-        copy_error(error_msg, error_msg_maxsize, "unknown error");
-        return VERIFIER_ERROR;
     }
+};
+
+// ULTRAGROTH_VERIFY_JUDGE when the caller gives no options (the calls without an options argument never do)
+BatchOptions read_options(const ug_verify_batch_options* options) {
+    BatchOptions opt;
+    if (!options) { opt.judge = judge_from_environment(); return opt; }
+    if (options->size < sizeof(ug_verify_batch_options)) throw std::invalid_argument("ug_verify_batch_options: size is smaller than the struct");
+    if (options->judge != 0 && options->judge != 1) throw std::invalid_argument("ug_verify_batch_options: judge must be 0 or 1");
+    opt.judge = options->judge == 1;
+    if (options->search_width >= 0) opt.search_width = options->search_width;
+    if (options->judge_min >= 0) opt.judge_min = options->judge_min;
+    return opt;
+}
+// The one route of the exported batch calls. stats / legacy_stats: the call's statistics and their first 40 bytes, the struct of the
+// calls without options; either may be null, and neither is written by a call that fails.
+int batch_entry(int device, const Source& src, int count, const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
+                ug_verify_batch_stats_ex* stats, ug_verify_batch_stats* legacy_stats, char* error_msg, unsigned long error_msg_maxsize) {
+    return guarded(error_msg, error_msg_maxsize, [&] {
+        const BatchOptions opt = read_options(options);
+        src.check(count, count < 0 || !verification_key || (count > 0 && !verdicts));
+        BatchCall call(src, device, (size_t)count, verification_key, opt);
+        const int rc = call.run(verdicts, error_msg, error_msg_maxsize);
+        if (stats) *stats = call.stats;
+        if (legacy_stats) *legacy_stats = call.stats.base;
+        return rc;
+    });
 }
 
 }  // namespace
 
 extern "C" {
 
-// the JSON calls: null arrays fail the call as a null key does
-static int verify_batch_json(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
-                             int* verdicts, const BatchOptions& opt, ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    if (count > 0 && (!proofs || !inputs)) { copy_error(error_msg, error_msg_maxsize, "null argument"); return VERIFIER_ERROR; }
-    JsonSource src;
-    src.ultra = ultra; src.proofs = proofs; src.inputs = inputs;
-    return verify_batch(src, device, count, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
-}
-// the existing calls: options from the environment, the 40-byte stats
-static int verify_batch_env(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
-                            int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    BatchOptions opt;
-    try { opt.judge = judge_from_environment(); }
-    catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return VERIFIER_ERROR; }
-    ug_verify_batch_stats_ex ex;
-    const int rc = verify_batch_json(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats ? &ex : nullptr, error_msg, error_msg_maxsize);
-    if (stats && rc != VERIFIER_ERROR) *stats = ex.base;
-    return rc;
-}
-static bool read_options(BatchOptions& opt, const ug_verify_batch_options* options, char* error_msg, unsigned long error_msg_maxsize) {
-    try {
-        if (!options) opt.judge = judge_from_environment();
-        else {
-            if (options->size < sizeof(ug_verify_batch_options)) throw std::invalid_argument("ug_verify_batch_options: size is smaller than the struct");
-            if (options->judge != 0 && options->judge != 1) throw std::invalid_argument("ug_verify_batch_options: judge must be 0 or 1");
-            opt.judge = options->judge == 1;
-            if (options->search_width >= 0) opt.search_width = options->search_width;
-            if (options->judge_min >= 0) opt.judge_min = options->judge_min;
-        }
-        return true;
-    } catch (std::exception& e) { copy_error(error_msg, error_msg_maxsize, e.what()); return false; }
-}
-static int verify_batch_opt(bool ultra, int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
-                            int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
-                            unsigned long error_msg_maxsize) {
-    BatchOptions opt;
-    if (!read_options(opt, options, error_msg, error_msg_maxsize)) return VERIFIER_ERROR;
-    return verify_batch_json(ultra, device, count, proofs, inputs, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
-}
-static int verify_batch_records(bool ultra, int device, int format, int count, const void* records, const void* inputs, int n_pub,
-                                const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
-                                ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    BatchOptions opt;
-    if (!read_options(opt, options, error_msg, error_msg_maxsize)) return VERIFIER_ERROR;
-    if (!known_format(format)) { copy_error(error_msg, error_msg_maxsize, "format: not one of UG_RECORDS_PLAIN, UG_RECORDS_EVM, UG_RECORDS_COMPRESSED"); return VERIFIER_ERROR; }
-    if (count < 0 || !verification_key || (count > 0 && (!records || !inputs || !verdicts))) { copy_error(error_msg, error_msg_maxsize, "null argument"); return VERIFIER_ERROR; }
-    if (n_pub <= 0) { copy_error(error_msg, error_msg_maxsize, "invalid inputs data"); return VERIFIER_ERROR; }
-    RecordSource src;
-    src.ultra = ultra; src.records = static_cast<const uint8_t*>(records); src.inputs = static_cast<const uint8_t*>(inputs); src.n_pub = (size_t)n_pub;
-    src.format = format;
-    return verify_batch(src, device, count, verification_key, verdicts, opt, stats, error_msg, error_msg_maxsize);
-}
-
 int ug_groth16_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                             int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    return verify_batch_env(false, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, JsonSource(false, proofs, inputs), count, verification_key, verdicts, nullptr, nullptr, stats, error_msg, error_msg_maxsize);
 }
 int ug_ultra_groth_verify_batch(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                                 int* verdicts, ug_verify_batch_stats* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    return verify_batch_env(true, device, count, proofs, inputs, verification_key, verdicts, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, JsonSource(true, proofs, inputs), count, verification_key, verdicts, nullptr, nullptr, stats, error_msg, error_msg_maxsize);
 }
 int ug_groth16_verify_batch_opt(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                                 int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
                                 unsigned long error_msg_maxsize) {
-    return verify_batch_opt(false, device, count, proofs, inputs, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, JsonSource(false, proofs, inputs), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
 }
 int ug_ultra_groth_verify_batch_opt(int device, int count, const char* const* proofs, const char* const* inputs, const char* verification_key,
                                     int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
                                     unsigned long error_msg_maxsize) {
-    return verify_batch_opt(true, device, count, proofs, inputs, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, JsonSource(true, proofs, inputs), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
 }
-
 int ug_groth16_verify_batch_records(int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
                                     int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
                                     unsigned long error_msg_maxsize) {
-    return verify_batch_records(false, device, RECORDS_PLAIN, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, RecordSource(false, RECORDS_PLAIN, records, inputs, n_pub), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
 }
 int ug_ultra_groth_verify_batch_records(int device, int count, const void* records, const void* inputs, int n_pub, const char* verification_key,
                                         int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_ex* stats, char* error_msg,
                                         unsigned long error_msg_maxsize) {
-    return verify_batch_records(true, device, RECORDS_PLAIN, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, RecordSource(true, RECORDS_PLAIN, records, inputs, n_pub), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
 }
 int ug_groth16_verify_batch_records_fmt(int device, int format, int count, const void* records, const void* inputs, int n_pub,
                                         const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
                                         ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    return verify_batch_records(false, device, format, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
+    return batch_entry(device, RecordSource(false, format, records, inputs, n_pub), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
 }
 int ug_ultra_groth_verify_batch_records_fmt(int device, int format, int count, const void* records, const void* inputs, int n_pub,
                                             const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
                                             ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
-    return verify_batch_records(true, device, format, count, records, inputs, n_pub, verification_key, verdicts, options, stats, error_msg, error_msg_maxsize);
-}
-
-unsigned long ug_proof_record_bytes(int ultra, int format) { return known_format(format) ? (unsigned long)record_bytes(ultra != 0, format) : 0; }
-int ug_proof_record_convert(int ultra, int from_format, const void* from, int to_format, void* to) {
-    if (!from || !to || !known_format(from_format) || !known_format(to_format)) return 2;
-    try {
-        RecordPoints pts;
-        uint8_t out[320];
-        if (!record_read(from_format, ultra != 0, static_cast<const uint8_t*>(from), pts)) return 1;
-        if (!record_write(to_format, ultra != 0, pts, out)) return 1;
-        memcpy(to, out, record_bytes(ultra != 0, to_format));
-        return 0;
-    } catch (...) { return 2; }
-}
-int ug_inputs_convert(int from_format, const void* from, int n_pub, int to_format, void* to) {
-    if (!from || !to || n_pub <= 0 || !known_format(from_format) || !known_format(to_format)) return 2;
-    // one byte order to the other, or a copy: the block of a compressed record is the plain one
-    inputs_to_plain((from_format == RECORDS_EVM) != (to_format == RECORDS_EVM) ? RECORDS_EVM : RECORDS_PLAIN,
-                    static_cast<const uint8_t*>(from), (size_t)n_pub, static_cast<uint8_t*>(to));
-    return 0;
-}
-
-int ug_proof_pack(int ultra, const char* proof_json, void* record) {
-    if (!proof_json || !record) return 1;
-    try {
-        const JVal j = JParser(proof_json).parse_document();
-        if (j.at("protocol").string() != (ultra ? "ultragroth" : "groth16")) return 1;
-        uint8_t rec[320];
-        bool ok = true;
-        auto g1 = [&](const char* name, size_t at) {
-            const JVal& v = j.at(name);
-            ok = ok && u256_from_decimal(rec + at, v.at((size_t)0).string()) && u256_from_decimal(rec + at + 32, v.at((size_t)1).string());
-        };
-        g1("pi_a", 0);
-        const JVal& b = j.at("pi_b");
-        for (size_t c = 0; c < 4; c++) ok = ok && u256_from_decimal(rec + 64 + c * 32, b.at(c >> 1).at(c & 1).string());
-        if (ultra) { g1("pi_f", 192); g1("pi_r", 256); } else g1("pi_c", 192);
-        if (!ok) return 1;
-        memcpy(record, rec, record_bytes(ultra != 0));
-        return 0;
-    } catch (...) { return 1; }
-}
-int ug_inputs_pack(const char* inputs_json, void* out, int n_pub) {
-    if (!inputs_json || !out || n_pub <= 0) return 1;
-    try {
-        const JVal j = JParser(inputs_json).parse_document();
-        if (j.type != JVal::Array || j.arr.size() != (size_t)n_pub) return 1;
-        std::vector<uint8_t> buf((size_t)n_pub * 32);
-        for (size_t c = 0; c < j.arr.size(); c++) if (!u256_from_decimal(&buf[c * 32], j.arr[c].string())) return 1;
-        memcpy(out, buf.data(), buf.size());
-        return 0;
-    } catch (...) { return 1; }
-}
-static int copy_text(const std::string& t, char* json, unsigned long maxsize) {
-    if (!json || t.size() + 1 > maxsize) return 1;
-    memcpy(json, t.c_str(), t.size() + 1);
-    return 0;
-}
-int ug_proof_unpack(int ultra, const void* record, char* json, unsigned long maxsize) {
-    if (!record) return 1;
-    try { return copy_text(record_to_json(ultra != 0, static_cast<const uint8_t*>(record)), json, maxsize); } catch (...) { return 1; }
-}
-int ug_inputs_unpack(const void* in, int n_pub, char* json, unsigned long maxsize) {
-    if (!in || n_pub <= 0) return 1;
-    try { return copy_text(inputs_to_json(static_cast<const uint8_t*>(in), (size_t)n_pub), json, maxsize); } catch (...) { return 1; }
+    return batch_entry(device, RecordSource(true, format, records, inputs, n_pub), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
 }
 
 // ULTRAGROTH_TEST_HOOKS=1 only: the passes of the last records call on a device that used the resident arrays in place, and those that
@@ -1337,36 +871,31 @@ int ug_test_records_ingest(int device, int format, int ultra_, int count, const 
         const uint8_t* rec = static_cast<const uint8_t*>(records);
         uint8_t* out = static_cast<uint8_t*>(plain_out);
         const size_t stride = record_bytes(ultra, format), plain = record_bytes(ultra);
-        auto leave = [&](size_t i, RecordPoints& pts) {            // what failed is zeros
-            if (!g1_on_curve(pts.a)) pts.a = G1A{f1_zero(), f1_zero(), true};
-            if (!g2_on_curve(pts.b)) pts.b = g2_inf();
-            for (int s = 0; s < 2; s++) if (!g1_on_curve(pts.g[s])) pts.g[s] = G1A{f1_zero(), f1_zero(), true};
-            record_write(RECORDS_PLAIN, ultra, pts, out + i * plain);
-        };
         for (size_t first = 0; first < (size_t)count; first += PAIRING_PASS) {
             const size_t m = std::min<size_t>(PAIRING_PASS, (size_t)count - first);
-            if (device < 0) {
-                parallel_for(m, [&](size_t j) {
-                    const size_t i = first + j;
-                    RecordPoints pts;
-                    bool ok = record_read(format, ultra, rec + i * stride, pts);
-                    ok = ok && g1_on_curve(pts.a) && g2_on_curve(pts.b) && g1_on_curve(pts.g[0]) && g1_on_curve(pts.g[1]);
-                    status[i] = !ok ? UG_POINT_OFF_CURVE : g2_in_subgroup(pts.b) ? UG_POINT_OK : UG_POINT_OFF_SUBGROUP;
-                    leave(i, pts);
-                });
-                continue;
-            }
-            ResidentBatch rb(device, (int)m, k, format);
-            rb.ingest(rec + first * stride, status + first);
             std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * (size_t)k * G1_WORDS);
-            rb.download(a.data(), b.data(), g.data());
-            parallel_for(m, [&](size_t j) {
-                RecordPoints pts;
+            if (device < 0) {
+                std::vector<BatchProof> read(m);
+                parallel_for(m, [&](size_t j) {
+                    BatchProof& p = read[j];
+                    p.no_point = !record_read(format, ultra, rec + (first + j) * stride, p);
+                    status[first + j] = !proof_on_curve(p) ? UG_POINT_OFF_CURVE : g2_in_subgroup(p.b) ? UG_POINT_OK : UG_POINT_OFF_SUBGROUP;
+                });
+                pack_points(read, nullptr, m, k, a.data(), b.data(), g.data());
+            } else {
+                ResidentBatch rb(device, (int)m, k, format);
+                rb.ingest(rec + first * stride, status + first);
+                rb.download(a.data(), b.data(), g.data());
+            }
+            parallel_for(m, [&](size_t j) {                         // the arrays as plain records; what failed is zeros
+                Points pts;
                 pts.a = g1_load(&a[j * G1_WORDS], false);
                 pts.b = g2_load(&b[j * G2_WORDS]);
-                pts.g[0] = g1_load(&g[j * k * G1_WORDS], false);
-                pts.g[1] = ultra ? g1_load(&g[(j * k + 1) * G1_WORDS], false) : G1A{f1_zero(), f1_zero(), true};
-                leave(first + j, pts);
+                for (int s = 0; s < 2; s++) pts.g[s] = s < k ? g1_load(&g[(j * k + s) * G1_WORDS], false) : g1_inf();
+                if (!g1_on_curve(pts.a)) pts.a = g1_inf();
+                if (!g2_on_curve(pts.b)) pts.b = g2_inf();
+                for (int s = 0; s < 2; s++) if (!g1_on_curve(pts.g[s])) pts.g[s] = g1_inf();
+                record_write(RECORDS_PLAIN, ultra, pts, out + (first + j) * plain);
             });
         }
         return 0;
