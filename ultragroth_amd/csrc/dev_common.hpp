@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <utility>
 #include <stdexcept>
 #include <string>
 #include "ec.hpp"
@@ -21,6 +22,16 @@ struct HipError : public std::runtime_error {
     } while (0)
 
 #define UG_KERNEL_CHECK() UG_HIP(hipGetLastError())
+
+// An owned HIP event (move-only); timing = false: an ordering-only event (hipEventDisableTiming). A default one is empty.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    explicit Event(bool timing) { UG_HIP(timing ? hipEventCreate(&e) : hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+};
 
 // An event recorded INSIDE a stream capture so that every launch of the resulting graph records it again (timed spans of a
 // captured launch sequence): an explicit event-record node behind the stream's current capture dependencies, which then becomes

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <vector>
 #include "ec.hpp"
+#include "stream_timer.hpp"
 
 namespace ug {
 
@@ -44,10 +45,10 @@ struct NttPlan {
     void release();
     // DIT transform; see ntt.hip for the buffer rules. post / post_const are optional multipliers
     // applied in the last pass: out[i] *= post[i], or out[i] *= *post_const.
-    // stats (optional): every pass launch is bracketed with an event pair (KernelStats::collect after a stream sync).
+    // stats (optional): every pass launch is a timed section of it (stream_timer.hpp).
     // fuse (optional): see NttFusion.
     void transform(u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
-                   const u32* post, const u32* post_const, hipStream_t stream, struct MsmStats* stats = nullptr,
+                   const u32* post, const u32* post_const, hipStream_t stream, LaunchTimer stats = LaunchTimer(),
                    const struct NttFusion* fuse = nullptr, int vectors = 1, u64 out_stride = 0, u64 in_stride = 0) const;
     // the same in two steps, for callers that run several transforms of this size side by side: passes() fills `list`
     // (NTT_MAX_PASSES entries) and returns the pass count -- the same for every transform of the plan --, launch() runs pass
@@ -57,7 +58,7 @@ struct NttPlan {
     // vectors = 1 is the launch of a single transform, the strides unread.
     int passes(NttPass* list, u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
                const u32* post, const u32* post_const, const struct NttFusion* fuse = nullptr, u64 out_stride = 0, u64 in_stride = 0) const;
-    void launch(const NttPass* const* lists, int count, int p, hipStream_t stream, struct MsmStats* stats = nullptr, int vectors = 1) const;
+    void launch(const NttPass* const* lists, int count, int p, hipStream_t stream, LaunchTimer stats = LaunchTimer(), int vectors = 1) const;
     ~NttPlan() { release(); }
 };
 
@@ -66,6 +67,8 @@ struct NttPlan {
 // it stood when the capture ended.
 uint64_t alloc_epoch();
 void alloc_epoch_bump();
+// (re)allocation of such a buffer (msm.hip, sort.hip)
+template <class T> void epoch_alloc(T*& p, size_t bytes) { alloc_epoch_bump(); if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
 
 // ---- msm.hip ------------------------------------------------------------------------------------------
 // Bucket classes (many-device provers, DESIGN.md section 7: the witness products sharded by BUCKET instead of by base point).
@@ -221,29 +224,6 @@ struct MsmWorkspace {
     ~MsmWorkspace() { release(); }
 };
 
-// An event pair recorded INSIDE a captured launch sequence (dev_common.hpp record_in_capture: an event-record
-// node of the graph, re-recorded by every launch of it), with what the elapsed time is accounted to once a launch has completed.
-struct CapturedSpan { hipEvent_t e0 = nullptr, e1 = nullptr; u64 units = 0; };
-
-struct MsmStats {                 // HIP-event timing of one kernel's launches (bucket accumulation G1 / G2, NTT passes)
-    static constexpr int SLOTS = 64;                // launches that may be in flight before collect()
-    hipEvent_t ev0[SLOTS] = {}, ev1[SLOTS] = {};
-    u64 slot_entries[SLOTS] = {};
-    int pending = 0;
-    double accumulate_ms = 0; u64 launches = 0; u64 entries = 0;
-    // while the stream is being captured into a graph (ug_graph_begin .. _end) the pairs go here instead, as external event
-    // records that belong to the graph; account() adds one completed launch of the graph
-    std::vector<CapturedSpan>* capture = nullptr;
-    void account(const std::vector<CapturedSpan>& spans);
-    void create();
-    void destroy();
-    void collect();                                 // after the stream has been synchronised
-    void collect_ready();                           // the launches that have finished, without waiting
-    int begin(hipStream_t stream, u64 units);       // records the start event; returns the slot (-1: none free, untimed)
-    void end(int slot, hipStream_t stream);
-};
-typedef MsmStats KernelStats;
-
 // An MSM whose kernels and result copy are queued on the stream; the window sums arrive in `host` (pinned memory,
 // bucket_windows * PT_WORDS words) once the stream is synchronised. Several may be queued back to back: the stream
 // orders their use of the shared workspace.
@@ -276,7 +256,9 @@ struct MsmCall {
 constexpr int MSM_PHASE_ALL = 0, MSM_PHASE_ACCUMULATE = 1, MSM_PHASE_TAIL = 2;
 // queues the call's kernels and result copies: one accumulation launch per product (one in all for a group), the latency-bound
 // tail kernels once for all of them; pend[j] describes product j's result block for msm_collect_*
-void msm_enqueue(bool g2, const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, MsmStats* stats, MsmPending* pend,
+// stats: every accumulation launch is a timed section of it (stream_timer.hpp: LaunchTimer; units = the entries the launch
+// walks). A sample is never dropped: when 64 pairs are outstanding and none has finished, the timer's pool grows.
+void msm_enqueue(bool g2, const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, LaunchTimer stats, MsmPending* pend,
                  int phase = MSM_PHASE_ALL);
 // 64-byte records of one member set -> record (slot0 + i) * members + member of a group array
 void interleave_points_g1(u32* dst, const u32* src, u64 n, int members, int member, u64 slot0, hipStream_t stream);

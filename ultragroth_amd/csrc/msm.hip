@@ -817,7 +817,6 @@ int reduce_chunk(const MsmGeometry& g, int sets = 1, bool g2 = false) {
     return chunk;
 }
 
-template <class T> void dev_alloc(T*& p, size_t bytes) { alloc_epoch_bump(); if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
 template <class T> void dev_free(T*& p) { if (p) { alloc_epoch_bump(); hipFree(p); } p = nullptr; }
 std::atomic<uint64_t> g_alloc_epoch{1};
 
@@ -940,24 +939,24 @@ void MsmSchedule::reserve(const MsmGeometry& g) {
     u64 total = g.n * g.windows;
     if (total > capacity_n) {
         u64 padded = total + ((u64)64 << LOG_SEG);          // room for the lane-transposed copy's last tile
-        dev_alloc(keys_a, padded * 4); dev_alloc(keys_b, padded * 4);
-        dev_alloc(vals_a, padded * 4); dev_alloc(vals_b, padded * 4);
+        epoch_alloc(keys_a, padded * 4); epoch_alloc(keys_b, padded * 4);
+        epoch_alloc(vals_a, padded * 4); epoch_alloc(vals_b, padded * 4);
         dev_free(sort_tmp); sort_tmp_bytes = 0;                // (the library sort's scratch is sized on its first use)
         sorter.reserve(total, 12);
         capacity_n = total;
     }
     if (g.total_buckets() > capacity_buckets) {
-        dev_alloc(bucket_start, g.total_buckets() * 4);
-        dev_alloc(bucket_count, g.total_buckets() * 4);
-        dev_alloc(small_list, g.total_buckets() * 4);
+        epoch_alloc(bucket_start, g.total_buckets() * 4);
+        epoch_alloc(bucket_count, g.total_buckets() * 4);
+        epoch_alloc(small_list, g.total_buckets() * 4);
         capacity_buckets = g.total_buckets();
     }
     u64 hcap = (total >> 5) / (FIX_MAX - 1) + 2;         // a listed bucket covers at least FIX_MAX - 1 whole segments (>= 2^5 entries each)
     if (hcap > heavy_cap) {
-        dev_alloc(heavy_list, 4 * hcap * 4); dev_alloc(medium_list, 4 * hcap * 4); dev_alloc(heavy_offsets, (hcap + 1) * 4);
+        epoch_alloc(heavy_list, 4 * hcap * 4); epoch_alloc(medium_list, 4 * hcap * 4); epoch_alloc(heavy_offsets, (hcap + 1) * 4);
         heavy_cap = (u32)hcap;
     }
-    if (!meta) dev_alloc(meta, 32);
+    if (!meta) epoch_alloc(meta, 32);
 }
 
 void MsmSchedule::build(const u32* scalars_dev, const MsmGeometry& g, hipStream_t stream) {
@@ -995,7 +994,7 @@ void MsmSchedule::build(const u32* scalars_dev, const MsmGeometry& g, hipStream_
         if (!sort_tmp_bytes) {
             size_t need = 0;
             UG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, dk, dv, (int)total, 0, 32));
-            dev_alloc(sort_tmp, need); sort_tmp_bytes = need;
+            epoch_alloc(sort_tmp, need); sort_tmp_bytes = need;
         }
         size_t tmp = sort_tmp_bytes;
         UG_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, tmp, dk, dv, (int)total, 0, end_bit, stream));
@@ -1046,15 +1045,15 @@ void MsmSchedule::release() {
 void MsmWorkspace::reserve(const MsmGeometry& g, bool g2, u64 n_segments, u32 n_heavy_tasks, int sets) {
     size_t ptw = (size_t)(g2 ? G2Cfg::PT_WORDS : G1Cfg::PT_WORDS) * (size_t)sets;      // the products of a batch lie one after the other
     size_t need = (size_t)g.total_buckets() * ptw * 4;
-    if (need > bucket_bytes) { dev_alloc(bucket_pts, need); bucket_bytes = need; }
+    if (need > bucket_bytes) { epoch_alloc(bucket_pts, need); bucket_bytes = need; }
     const int chunk = reduce_chunk(g, sets, g2);           // the chunk the launch uses (msm_enqueue_multi): same arguments, same value
     // (bucket classes: the chunks' plain sums S0 beside their weighted sums, and the specials' sums behind both)
     size_t cneed = ((size_t)(g.cls.on() ? 2 : 1) * g.bucket_windows() * (g.buckets / chunk) + (size_t)g.window_sets()) * ptw * 4;
-    if (cneed > chunk_bytes) { dev_alloc(chunk_pts, cneed); dev_alloc(chunk_pts2, cneed); chunk_bytes = cneed; }
+    if (cneed > chunk_bytes) { epoch_alloc(chunk_pts, cneed); epoch_alloc(chunk_pts2, cneed); chunk_bytes = cneed; }
     size_t sneed = (size_t)n_segments * 2 * ptw * 4;
-    if (sneed > slot_bytes) { dev_alloc(slot_pts, sneed); slot_bytes = sneed; }
+    if (sneed > slot_bytes) { epoch_alloc(slot_pts, sneed); slot_bytes = sneed; }
     size_t tneed = (size_t)n_heavy_tasks * ptw * 4;
-    if (tneed > task_bytes) { dev_alloc(task_pts, tneed); task_bytes = tneed; }
+    if (tneed > task_bytes) { epoch_alloc(task_pts, tneed); task_bytes = tneed; }
 }
 void MsmWorkspace::release() {
     dev_free(bucket_pts); dev_free(chunk_pts); dev_free(chunk_pts2); dev_free(slot_pts); dev_free(task_pts);
@@ -1076,7 +1075,7 @@ namespace {
 // (the accumulation launches) and MSM_PHASE_TAIL (everything behind them, possibly on another stream that has been ordered behind
 // the accumulation): ug_msm_witness_enqueue runs the G1 and the G2 tails of a proof side by side
 template <class Cfg>
-void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, MsmStats* stats, MsmPending* pend, int phase) {
+void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, LaunchTimer stats, MsmPending* pend, int phase) {
     const int count = call.count, group = call.group;
     const MsmCall::Product* const p = call.products;
     const bool do_acc = phase != MSM_PHASE_TAIL, do_tail = phase != MSM_PHASE_ACCUMULATE;
@@ -1116,7 +1115,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
 #else
 #define UG_FOLD_ARG
 #endif
-            int slot = stats ? stats->begin(stream, g.n * g.windows * (u64)group) : -1;
+            StreamTimer::Scope timed = stats.time(stream, g.n * g.windows * (u64)group);
             if (nseg) {
                 const dim3 grid((unsigned)((nseg + 255) / 256)), block(256);
 #define UG_GROUP_LAUNCH(K_) hipLaunchKernelGGL((segment_accumulate_group_kernel<K_>), grid, block, 0, stream, p[0].bases, p[0].n_bases, \
@@ -1129,19 +1128,19 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
 #undef UG_FOLD_ARG
                 UG_KERNEL_CHECK();
             }
-            if (stats) stats->end(slot, stream);
+            timed.stop();
         }
     } else if (group) throw std::logic_error("msm: groups are G1 only");
     for (int q = 0; q < (group || !do_acc ? 0 : k); q++) {
         const int j = live[q];
-        int slot = stats ? stats->begin(stream, g.n * g.windows) : -1;
+        StreamTimer::Scope timed = stats.time(stream, g.n * g.windows);
         if (nseg) {
             hipLaunchKernelGGL(segment_accumulate_kernel<Cfg>, dim3((unsigned)((nseg + ACC_BLOCK - 1) / ACC_BLOCK)), dim3(ACC_BLOCK), 0, stream,
                                p[j].bases, p[j].n_bases, p[j].delta, s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail,
                                ws.bucket_pts + q * bucket_stride, ws.slot_pts + q * slot_stride);
             UG_KERNEL_CHECK();
         }
-        if (stats) stats->end(slot, stream);
+        timed.stop();
     }
     if (!do_tail) return;
     if (nseg > 1) {
@@ -1252,66 +1251,7 @@ XYZZ<typename Cfg::F> msm_collect(const MsmPending& p, int vector = 0) {
 }
 }  // namespace
 
-void MsmStats::create() { for (int i = 0; i < SLOTS; i++) { UG_HIP(hipEventCreate(&ev0[i])); UG_HIP(hipEventCreate(&ev1[i])); } }
-void MsmStats::destroy() { for (int i = 0; i < SLOTS; i++) { if (ev0[i]) hipEventDestroy(ev0[i]); if (ev1[i]) hipEventDestroy(ev1[i]); ev0[i] = ev1[i] = nullptr; } }
-// launches whose end event has already fired are accounted and their slots freed (no host wait)
-void MsmStats::collect_ready() {
-    int keep = 0;
-    for (int i = 0; i < pending; i++) {
-        if (hipEventQuery(ev1[i]) == hipSuccess) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev0[i], ev1[i]) == hipSuccess) { accumulate_ms += ms; launches++; entries += slot_entries[i]; }
-        } else {
-            if (keep != i) { std::swap(ev0[keep], ev0[i]); std::swap(ev1[keep], ev1[i]); slot_entries[keep] = slot_entries[i]; }
-            keep++;
-        }
-    }
-    (void)hipGetLastError();                       // hipEventQuery reports hipErrorNotReady through the error state
-    pending = keep;
-}
-int MsmStats::begin(hipStream_t stream, u64 units) {
-    if (capture) {                                 // the stream is being captured: an event pair of the graph's own
-        CapturedSpan sp;
-        sp.units = units;
-        UG_HIP(hipEventCreate(&sp.e0));
-        if (hipEventCreate(&sp.e1) != hipSuccess) { hipEventDestroy(sp.e0); throw HipError("HIP error: hipEventCreate"); }
-        capture->push_back(sp);
-        record_in_capture(sp.e0, stream);
-        return SLOTS + (int)capture->size() - 1;
-    }
-    if (pending == SLOTS) collect_ready();
-    if (pending == SLOTS) return -1;               // a caller that never waits: this launch goes untimed
-    int slot = pending++;
-    slot_entries[slot] = units;
-    UG_HIP(hipEventRecord(ev0[slot], stream));
-    return slot;
-}
-void MsmStats::end(int slot, hipStream_t stream) {
-    if (slot >= SLOTS) {
-        if (!capture || (size_t)(slot - SLOTS) >= capture->size()) throw std::logic_error("kernel statistics: captured slot without a capture");
-        record_in_capture((*capture)[slot - SLOTS].e1, stream);
-        return;
-    }
-    if (slot >= 0) UG_HIP(hipEventRecord(ev1[slot], stream));
-}
-// one completed launch of a graph that holds these pairs
-void MsmStats::account(const std::vector<CapturedSpan>& spans) {
-    for (const CapturedSpan& sp : spans) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, sp.e0, sp.e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-        accumulate_ms += ms; launches++; entries += sp.units;
-    }
-}
-void MsmStats::collect() {
-    for (int i = 0; i < pending; i++) {
-        float ms = 0;
-        UG_HIP(hipEventElapsedTime(&ms, ev0[i], ev1[i]));
-        accumulate_ms += ms; launches++; entries += slot_entries[i];
-    }
-    pending = 0;
-}
-
-void msm_enqueue(bool g2, const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, MsmStats* stats, MsmPending* pend,
+void msm_enqueue(bool g2, const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& call, hipStream_t stream, LaunchTimer stats, MsmPending* pend,
                  int phase) {
     if (call.group && (call.group < 2 || call.group > 3 || call.count != call.group)) throw std::invalid_argument("msm: a base group has 2 or 3 members");
     if (!g2) msm_enqueue_multi<G1Cfg>(s, ws, call, stream, stats, pend, phase);

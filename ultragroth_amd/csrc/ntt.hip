@@ -492,7 +492,7 @@ int NttPlan::passes(NttPass* list, u32* out, const u32* in, bool inverse, bool g
 
 // pass `p` of up to three transforms of this plan's size in ONE launch (their pass lists share the geometry); vectors > 1: of
 // that many vectors of each transform (the lists' strides), same geometry, blockIdx.z the vector
-void NttPlan::launch(const NttPass* const* lists, int count, int p, hipStream_t stream, MsmStats* stats, int vectors) const {
+void NttPlan::launch(const NttPass* const* lists, int count, int p, hipStream_t stream, LaunchTimer stats, int vectors) const {
     if (count < 1 || count > 3) throw std::logic_error("ntt: batch size");
     if (vectors < 1 || vectors > 65535) throw std::logic_error("ntt: vector count");
     PassBatchVectors bv;
@@ -514,7 +514,7 @@ void NttPlan::launch(const NttPass* const* lists, int count, int p, hipStream_t 
     unsigned blocks = (unsigned)(((u64)1 << logn) >> (a.k + a.j));
     int threads = E / 4 > NTT_THREADS ? NTT_THREADS : (E / 4 < 64 ? 64 : E / 4);
     size_t lds = (size_t)E * NL * 4;
-    int slot = stats ? stats->begin(stream, ((u64)1 << logn) * (u64)count * (u64)vectors) : -1;
+    StreamTimer::Scope timed = stats.time(stream, ((u64)1 << logn) * (u64)count * (u64)vectors);
     if (vectors > 1) {
         const dim3 grid(blocks, (unsigned)count, (unsigned)vectors);
         if (shoup) hipLaunchKernelGGL((ntt_pass_kernel<true, true>), grid, dim3(threads), lds, stream, bv);
@@ -522,11 +522,11 @@ void NttPlan::launch(const NttPass* const* lists, int count, int p, hipStream_t 
     } else if (shoup) hipLaunchKernelGGL((ntt_pass_kernel<true, false>), dim3(blocks, (unsigned)count), dim3(threads), lds, stream, b);
     else hipLaunchKernelGGL((ntt_pass_kernel<false, false>), dim3(blocks, (unsigned)count), dim3(threads), lds, stream, b);
     UG_KERNEL_CHECK();
-    if (stats) stats->end(slot, stream);
+    timed.stop();
 }
 
 void NttPlan::transform(u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
-                        const u32* post, const u32* post_const, hipStream_t stream, MsmStats* stats, const NttFusion* fuse,
+                        const u32* post, const u32* post_const, hipStream_t stream, LaunchTimer stats, const NttFusion* fuse,
                         int vectors, u64 out_stride, u64 in_stride) const {
     if (logn == 0) {
         if (fuse && (fuse->in2 || fuse->fin_a)) throw std::invalid_argument("ntt: fused forms need at least two points");

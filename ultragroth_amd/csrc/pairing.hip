@@ -243,12 +243,6 @@ struct DevBuf {
     ~DevBuf() { if (p) hipFree(p); }
     DevBuf(const DevBuf&) = delete;
 };
-struct Event {
-    hipEvent_t e = nullptr;
-    Event() { UG_HIP(hipEventCreate(&e)); }
-    ~Event() { if (e) hipEventDestroy(e); }
-    Event(const Event&) = delete;
-};
 unsigned blocks(size_t lanes) { return (unsigned)((lanes + 63) / 64); }
 
 }  // namespace
@@ -258,7 +252,7 @@ static void run_pass(const PairingConsts& kc, const u32* a, const u32* b, const 
                      double kernel_ms[3]) {
     const size_t n = (size_t)n_, k = (size_t)k_, nodes = tree_nodes(n);
     DevBuf f(nodes * F12_WORDS), s(nodes * k * XYZZ_WORDS);
-    Event t0, t1, t2, t3;
+    Event t0(true), t1(true), t2(true), t3(true);
     UG_HIP(hipEventRecord(t0.e, nullptr));
     hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a, b, g, r, n_, k_, f.p, s.p);
     UG_KERNEL_CHECK();
@@ -377,7 +371,7 @@ void pairing_judge_device(int device, const FinalExpConsts& kc, PairingJudge& pj
     const size_t chunk = std::min(n, std::max<size_t>(1, VKX_CHUNK_TERMS / cols));           // suspects per launch of the vkx step
     DevBuf a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), points(cols * G1_WORDS), key((1 + k) * G2_WORDS), fab(F12_WORDS);
     DevBuf scalars(chunk * cols * 8), terms(chunk * cols * XYZZ_WORDS), nvkx(n * G1_WORDS), verdict(n);
-    Event t0, t1, t2;
+    Event t0(true), t1(true), t2(true);
     UG_HIP(hipMemcpy(a.p, pj.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(b.p, pj.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(g.p, pj.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));

@@ -363,8 +363,6 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_pass_kernel(SortPassArgs a
     }      // the next tile
 }
 
-template <class T> void sort_alloc(T*& p, size_t bytes) { alloc_epoch_bump(); if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
-
 }  // namespace
 
 // pass plan for keys below 2^bits: ceil(bits / 8) passes of nearly equal width, low bits first, the narrower digits first (the
@@ -391,10 +389,10 @@ void RadixSorter::reserve(u64 n_pairs, int ipt_min) {
     // (later passes move the pair count rounded up to the FIRST pass's tile, at most SORT_THREADS * 16 - 1 = 8 191 pairs more, in tiles of their own)
     const u64 tiles = (n_pairs + (u64)SORT_THREADS * SORT_MAX_IPT) / ((u64)SORT_THREADS * (u64)(ipt_min < 1 ? 1 : ipt_min)) + 2;
     if (tiles > tiles_cap) {
-        sort_alloc(lookback, (size_t)tiles * SORT_MAX_BINS * 4);
+        epoch_alloc(lookback, (size_t)tiles * SORT_MAX_BINS * 4);
         tiles_cap = tiles;
     }
-    if (!small) sort_alloc(small, (4 * SORT_MAX_BINS + 16) * 4);
+    if (!small) epoch_alloc(small, (4 * SORT_MAX_BINS + 16) * 4);
 }
 void RadixSorter::release() {
     if (lookback || small) alloc_epoch_bump();

@@ -116,23 +116,22 @@ struct ug_ctx {
     StagedUploader uploader;
     hipStream_t stream = nullptr;
     MsmWorkspace ws_g1, ws_g2;
-    MsmStats stats[4];                     // [0] G1, [1] G2 bucket-accumulation launches, [2] NTT pass launches, [3] G1 group accumulation
+    // Stream-time accounting without host waits (stream_timer.hpp): the timed sections are resolved the next time the stream is
+    // known to be idle -- ug_ctx_collect, ug_ctx_timings, ug_ctx_sync. msm | fft: the split of ug_ctx_timings; kernel: the launches
+    // of one kernel class -- [0] G1, [1] G2 bucket accumulation, [2] NTT passes, [3] G1 group accumulation (ug_ctx_kernel_stats)
+    StreamTimer timer;
+    TimeSink msm, fft, kernel[4];
     // Per-kernel statistics are OFF until somebody asks for them (ug_ctx_kernel_stats with reset != 0 switches them on for the
     // context): an event pair around a launch costs 10-25 us of idle device on this runtime (rocprofv3 trace of a 2^20 proof,
     // profiles/r05_variants_ab.txt item 1) -- 0.2 ms per proof that only a measuring caller should pay.
     bool kernel_stats_on = false;
-    MsmStats* stat(int k) { return kernel_stats_on ? &stats[k] : nullptr; }
-    double msm_ms = 0, fft_ms = 0;
-    // stream-time accounting without host waits: every timed span is an event pair that is resolved (elapsed time added
-    // to its accumulator) the next time the stream is known to be idle -- ug_ctx_collect, ug_ctx_timings, ug_ctx_sync
-    struct Span { hipEvent_t e0, e1; double* acc; };
-    std::vector<Span> spans_free, spans_pending;
+    LaunchTimer stat(int k) { return LaunchTimer{&timer, kernel_stats_on ? &kernel[k] : nullptr}; }
     // the product queue: MSMs queued by ug_msm_*_enqueue whose results are still on their way (pinned_results block k <-> pending_msm[k])
     struct QueuedMsm { MsmPending pend; void* out; bool g2; };
     std::vector<QueuedMsm> pending_msm;
-    hipEvent_t order_event = nullptr;      // ug_ctx_wait
+    Event order_event{false};              // ug_ctx_wait
     hipStream_t side_stream = nullptr;     // ug_msm_witness_enqueue: the G2 tail runs here beside the G1 tail
-    hipEvent_t side_fork = nullptr, side_join = nullptr;
+    Event side_fork, side_join;            // (created with the side stream)
     bool defer_tables = false;             // ug_ctx_defer_tables: sets are created with room for their window tables, which are
                                            // then built piece by piece (ug_bases_tables_step)
     int check_level = 0;                   // ug_ctx_check_points: the sets created on this context check their records (check.hip)
@@ -141,7 +140,7 @@ struct ug_ctx {
     ug_point_fault last_fault = {0, UG_POINT_OK};   // what the last creation on this context found (ug_ctx_last_point_fault) ...
     int last_fault_member = -1;                      // ... and in which member of a group (-1: a plain set)
     ug_graph* recording = nullptr;         // the stream is being captured into this graph (ug_graph_begin .. ug_graph_end)
-    std::vector<ug_graph*> launched;       // graphs launched on this stream whose event pairs are not accounted yet (resolve_spans)
+    std::vector<ug_graph*> launched;       // graphs launched on this stream whose event pairs are not accounted yet (resolve_timer)
     NttPlan raw_ntt;                       // cache for ug_fr_ntt
     u32* lookup_last = nullptr; u64 lookup_last_n = 0;   // zeroed scratch of ug_dvec_apply_lookup
     u32* lookup_stage = nullptr; size_t lookup_stage_bytes = 0;   // staging of the lookup calls (kept: two allocations and
@@ -233,9 +232,7 @@ struct ug_graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     std::vector<ug_ctx::QueuedMsm> pend[2];
-    struct Timed { hipEvent_t e0, e1; double* acc; };
-    std::vector<Timed> spans;
-    std::vector<CapturedSpan> cap[2][4];       // per context and kernel class (ug_ctx::stats)
+    std::vector<StreamTimer::Pair> pairs[2];   // recorded through context q's timer; each pair knows its sink
     uint64_t epoch = 0;                        // alloc_epoch() when the capture ended
     size_t nodes = 0;
     bool capturing = false;
@@ -305,82 +302,17 @@ void trace_step(const char* what) {
     static const auto origin = std::chrono::steady_clock::now();
     fprintf(stderr, "[ug_api] %9.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - origin).count(), what);
 }
-struct ScopedTimer {       // stream time between construction and stop() goes to *acc -- later: see ug_ctx::Span
-    ug_ctx* c; ug_ctx::Span span; bool stopped = false, captured = false;
-    ScopedTimer(const ScopedTimer&) = delete;
-    ScopedTimer& operator=(const ScopedTimer&) = delete;
-    ~ScopedTimer() {                                                      // the timed section threw: the event pair goes back unused
-        if (stopped) return;
-        if (captured) { hipEventDestroy(span.e0); hipEventDestroy(span.e1); }
-        else c->spans_free.push_back(span);
-    }
-    ScopedTimer(ug_ctx* c_, double* acc_) : c(c_) {
-        if (c->recording) {                          // a pair of the graph's own, recorded by every launch of it
-            span = ug_ctx::Span{nullptr, nullptr, acc_};
-            UG_HIP(hipEventCreate(&span.e0));
-            if (hipEventCreate(&span.e1) != hipSuccess) { hipEventDestroy(span.e0); throw HipError("HIP error: hipEventCreate"); }
-            captured = true;
-            try { record_in_capture(span.e0, c->stream); }
-            catch (...) { hipEventDestroy(span.e0); hipEventDestroy(span.e1); stopped = true; throw; }
-            return;
-        }
-        if (c->spans_pending.size() >= 64) {        // a caller that never waits: account what has finished, without waiting
-            std::vector<ug_ctx::Span> still;
-            for (auto& sp : c->spans_pending) {
-                float ms = 0;
-                if (hipEventQuery(sp.e1) == hipSuccess && hipEventElapsedTime(&ms, sp.e0, sp.e1) == hipSuccess) { *sp.acc += ms; c->spans_free.push_back(sp); }
-                else still.push_back(sp);
-            }
-            (void)hipGetLastError();
-            c->spans_pending.swap(still);
-        }
-        if (c->spans_free.empty()) {
-            ug_ctx::Span sp{nullptr, nullptr, nullptr};
-            UG_HIP(hipEventCreate(&sp.e0)); UG_HIP(hipEventCreate(&sp.e1));
-            c->spans_free.push_back(sp);
-        }
-        span = c->spans_free.back();
-        span.acc = acc_;
-        UG_HIP(hipEventRecord(span.e0, c->stream));
-        c->spans_free.pop_back();
-    }
-    void stop() {
-        if (captured) {
-            record_in_capture(span.e1, c->stream);
-            c->recording->spans.push_back(ug_graph::Timed{span.e0, span.e1, span.acc});
-            stopped = true;
-            return;
-        }
-        UG_HIP(hipEventRecord(span.e1, c->stream));
-        c->spans_pending.push_back(span);
-        stopped = true;
-    }
-};
-// after the stream has been synchronised: account the finished spans and the kernel statistics
-void resolve_spans(ug_ctx* c) {
-    for (auto& sp : c->spans_pending) {
-        float ms = 0;
-        UG_HIP(hipEventElapsedTime(&ms, sp.e0, sp.e1));
-        *sp.acc += ms;
-        c->spans_free.push_back(sp);
-    }
-    c->spans_pending.clear();
-    for (int k = 0; k < 4; k++) c->stats[k].collect();
+// after the stream has been synchronised: account the finished sections
+void resolve_timer(ug_ctx* c) {
+    c->timer.resolve();
     // graphs launched on this stream have completed as well: one launch of each is accounted (their event pairs are re-recorded
     // by every launch, so a graph is resolved before it is launched again: ug_graph_launch sees to that)
-    for (ug_graph* g : c->launched) {
-        for (const ug_graph::Timed& t : g->spans) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, t.e0, t.e1) == hipSuccess) *t.acc += ms; else (void)hipGetLastError();
-        }
-        for (int q = 0; q < 2; q++)
-            if (g->c[q]) for (int k = 0; k < 4; k++) g->c[q]->stats[k].account(g->cap[q][k]);
-    }
+    for (ug_graph* g : c->launched) for (int q = 0; q < 2; q++) StreamTimer::account(g->pairs[q]);
     c->launched.clear();
 }
 void sync_and_resolve(ug_ctx* c) {
     UG_HIP(hipStreamSynchronize(c->stream));
-    resolve_spans(c);
+    resolve_timer(c);
     c->free_deferred();
 }
 // The product queue of a context: ug_ctx::pending_msm, slot k of which owns block k of ug_ctx::pinned_results. An enqueue call
@@ -437,9 +369,10 @@ int ug_ctx_create_priority(ug_ctx** out, int device, int priority_class) {
     int n = 0;
     UG_HIP(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) throw std::invalid_argument("no such HIP device: " + std::to_string(device));
-    ug_ctx* c = new ug_ctx();
+    UG_HIP(hipSetDevice(device));               // (the context's events are created with it)
+    std::unique_ptr<ug_ctx, void (*)(ug_ctx*)> hold(new ug_ctx(), ug_ctx_destroy);
+    ug_ctx* c = hold.get();
     c->device = device;
-    c->use();
     if (priority_class) {
         int least = 0, greatest = 0;                // (numerically: greatest priority = lowest number)
         UG_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -447,31 +380,23 @@ int ug_ctx_create_priority(ug_ctx** out, int device, int priority_class) {
     } else {
         UG_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     }
-    UG_HIP(hipEventCreateWithFlags(&c->order_event, hipEventDisableTiming));
-    for (int k = 0; k < 4; k++) c->stats[k].create();
     UG_HIP(hipHostMalloc((void**)&c->pinned_results, (size_t)MSM_QUEUE_DEPTH * MSM_PENDING_WORDS * 4, hipHostMallocDefault));
-    *out = c;
+    *out = hold.release();
     UG_CATCH
 }
 void ug_ctx_destroy(ug_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
+    if (c->stream) hipStreamSynchronize(c->stream);
     c->free_deferred();
     c->ws_g1.release(); c->ws_g2.release(); c->raw_ntt.release(); c->uploader.release();
     if (c->lookup_last) hipFree(c->lookup_last);
     if (c->lookup_stage) hipFree(c->lookup_stage);
     check_release(c);
-    for (auto& sp : c->spans_free) { hipEventDestroy(sp.e0); hipEventDestroy(sp.e1); }
-    for (auto& sp : c->spans_pending) { hipEventDestroy(sp.e0); hipEventDestroy(sp.e1); }
-    if (c->order_event) hipEventDestroy(c->order_event);
     if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
-    if (c->side_fork) hipEventDestroy(c->side_fork);
-    if (c->side_join) hipEventDestroy(c->side_join);
-    for (int k = 0; k < 4; k++) c->stats[k].destroy();
     if (c->pinned_results) hipHostFree(c->pinned_results);
-    hipStreamDestroy(c->stream);
-    delete c;
+    if (c->stream) hipStreamDestroy(c->stream);
+    delete c;                                   // (with the events of the timer and of the context)
 }
 int ug_ctx_sync(ug_ctx* c) {
     UG_TRY
@@ -487,8 +412,8 @@ int ug_ctx_wait(ug_ctx* waiter, ug_ctx* signal) {
     if (!waiter || !signal) throw std::invalid_argument("null argument");
     if (waiter->device != signal->device) throw std::invalid_argument("contexts on different devices");
     waiter->use();
-    UG_HIP(hipEventRecord(signal->order_event, signal->stream));
-    UG_HIP(hipStreamWaitEvent(waiter->stream, signal->order_event, 0));
+    UG_HIP(hipEventRecord(signal->order_event.e, signal->stream));
+    UG_HIP(hipStreamWaitEvent(waiter->stream, signal->order_event.e, 0));
     UG_CATCH
 }
 
@@ -1341,7 +1266,7 @@ int ug_schedule_build(ug_schedule* s, const ug_dvec* scalars, uint64_t first, ui
     ug_ctx* c = s->ctx;
     c->use();
     fault_point(UG_FAULT_SCHEDULE_BUILD);
-    ScopedTimer tm(c, &c->msm_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->msm);
     s->first = first;
     MsmGeometry g = MsmGeometry::choose(count);
     g.set_classes(s->classes_for(first, count));
@@ -1361,7 +1286,7 @@ int ug_schedule_build_tables_strided(ug_schedule* s, const ug_dvec* scalars, uin
     fault_point(UG_FAULT_SCHEDULE_BUILD);
     MsmGeometry g = MsmGeometry::choose_tables(count, c, stride);
     g.set_classes(s->classes_for(first, count));
-    ScopedTimer tm(ctx, &ctx->msm_ms);
+    StreamTimer::Scope tm = ctx->timer.time(ctx->stream, &ctx->msm);
     s->first = first;
     s->sched.build(scalars->data + first * 8, g, ctx->stream);
     tm.stop();
@@ -1388,7 +1313,7 @@ int ug_schedule_build_vectors(ug_schedule* s, const ug_dvec* scalars, uint64_t f
     fault_point(UG_FAULT_SCHEDULE_BUILD);
     MsmGeometry g = table_c ? MsmGeometry::choose_tables(count, table_c, stride) : MsmGeometry::choose(count);
     g.set_vectors(vectors, vector_stride);
-    ScopedTimer tm(ctx, &ctx->msm_ms);
+    StreamTimer::Scope tm = ctx->timer.time(ctx->stream, &ctx->msm);
     s->first = first;
     s->sched.build(scalars->data + first * 8, g, ctx->stream);
     tm.stop();
@@ -1471,7 +1396,7 @@ int ug_msm_batch_enqueue(ug_ctx* c, int count, const ug_bases* const* bases, con
         check_tables(bases[k], s);
     }
     c->use();
-    ScopedTimer tm(c, &c->msm_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->msm);
     // the G1 products of the call form one batch, the G2 products another (msm.hip: msm_enqueue_multi): one accumulation
     // launch per product, the tail kernels once per batch; within a curve the caller's order is kept
     u32* host[MSM_QUEUE_DEPTH]; MsmPending pend[MSM_QUEUE_DEPTH];
@@ -1509,7 +1434,7 @@ int ug_msm_group_enqueue(ug_ctx* c, const ug_bases* group, const ug_schedule* s,
     for (int m = 0; m < K; m++) if (!outs[m]) throw std::invalid_argument("null argument");
     check_tables(group, s);
     c->use();
-    ScopedTimer tm(c, &c->msm_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->msm);
     MsmPending pend[MSM_BATCH_WIDTH];
     msm_enqueue(false, s->sched, c->ws_g1, group_call(slots, group, s, outs), c->stream, c->stat(3), pend);
     slots.commit(pend);
@@ -1533,10 +1458,9 @@ int ug_msm_witness_enqueue(ug_ctx* c, const ug_bases* group, const ug_bases* g2s
     c->use();
     if (!c->side_stream) {
         UG_HIP(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-        UG_HIP(hipEventCreateWithFlags(&c->side_fork, hipEventDisableTiming));
-        UG_HIP(hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming));
+        c->side_fork = Event(false); c->side_join = Event(false);
     }
-    ScopedTimer tm(c, &c->msm_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->msm);
     try {
         MsmPending pend[MSM_BATCH_WIDTH + 1];      // the group's, then the G2 product's
         const MsmCall g1 = group_call(slots, group, s, outs_group);
@@ -1547,12 +1471,12 @@ int ug_msm_witness_enqueue(ug_ctx* c, const ug_bases* group, const ug_bases* g2s
         msm_enqueue(false, s->sched, c->ws_g1, g1, c->stream, c->stat(3), pend, MSM_PHASE_ACCUMULATE);
         msm_enqueue(true, s->sched, c->ws_g2, g2, c->stream, c->stat(1), pend + K, MSM_PHASE_ACCUMULATE);
         // the G2 tail on the side stream, the G1 tail on the context's, then the context's stream waits for the side
-        UG_HIP(hipEventRecord(c->side_fork, c->stream));
-        UG_HIP(hipStreamWaitEvent(c->side_stream, c->side_fork, 0));
-        msm_enqueue(true, s->sched, c->ws_g2, g2, c->side_stream, nullptr, pend + K, MSM_PHASE_TAIL);
-        msm_enqueue(false, s->sched, c->ws_g1, g1, c->stream, nullptr, pend, MSM_PHASE_TAIL);
-        UG_HIP(hipEventRecord(c->side_join, c->side_stream));
-        UG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
+        UG_HIP(hipEventRecord(c->side_fork.e, c->stream));
+        UG_HIP(hipStreamWaitEvent(c->side_stream, c->side_fork.e, 0));
+        msm_enqueue(true, s->sched, c->ws_g2, g2, c->side_stream, LaunchTimer(), pend + K, MSM_PHASE_TAIL);
+        msm_enqueue(false, s->sched, c->ws_g1, g1, c->stream, LaunchTimer(), pend, MSM_PHASE_TAIL);
+        UG_HIP(hipEventRecord(c->side_join.e, c->side_stream));
+        UG_HIP(hipStreamWaitEvent(c->stream, c->side_join.e, 0));
         slots.commit(pend);
     } catch (...) {
         (void)hipStreamSynchronize(c->side_stream);      // (whatever the side stream got reads the schedule and the workspace)
@@ -1579,7 +1503,8 @@ int ug_ctx_collect(ug_ctx* c) {
 }
 // A caller that queued work (ug_msm_batch_enqueue, schedules, ug_hpoly_run) and then failed before ug_ctx_collect: waits for
 // whatever is still running on the context -- the kernels read the caller's witness buffer and write the pinned result
-// blocks -- and forgets the queued products, whose `out` pointers may be gone with the caller's stack frame. Never throws.
+// blocks -- and forgets the queued products, whose `out` pointers may be gone with the caller's stack frame, and with them the
+// timed sections that are still pending: the time of abandoned work is not reported. Never throws.
 void ug_ctx_abandon(ug_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -1587,7 +1512,8 @@ void ug_ctx_abandon(ug_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipGetLastError();
     c->pending_msm.clear();
-    try { resolve_spans(c); } catch (...) { c->spans_pending.clear(); }
+    c->timer.drop_pending();
+    c->launched.clear();
 }
 // the pass plan of the schedule sort for keys below 2^bits (sort.hip: radix_plan): host arithmetic only, for the CPU test-suite
 int ug_sort_plan(int bits, int shift[4], int bins_log[4]) {
@@ -1701,7 +1627,7 @@ int ug_hpoly_run(ug_hpoly* hp, const ug_dvec* w, ug_dvec* h_out) {
     ug_ctx* c = hp->ctx;
     c->use();
     fault_point(UG_FAULT_HPOLY_RUN);
-    ScopedTimer tm(c, &c->fft_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->fft);
     hpoly_queue(hp, w->data, 0, h_out->data, 0, 1);
     tm.stop();
     UG_CATCH
@@ -1719,7 +1645,7 @@ int ug_hpoly_run_vectors(ug_hpoly* hp, const ug_dvec* w, uint64_t witness_stride
     if (!hp->group) throw std::runtime_error("the H-polynomial handle has no workspaces (a reservation failed): reserve again");
     ug_ctx* c = hp->ctx;
     c->use();
-    ScopedTimer tm(c, &c->fft_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->fft);
     hp->last_group = vectors < hp->group ? vectors : hp->group;
     for (int v0 = 0; v0 < vectors; v0 += hp->group) {
         const int g = vectors - v0 < hp->group ? vectors - v0 : hp->group;
@@ -1789,7 +1715,7 @@ int ug_hpoly_chain(ug_hpoly* hp, const ug_dvec* w, int which, ug_dvec* out) {
     if (!hp->group) throw std::runtime_error("the H-polynomial handle has no workspaces (a reservation failed): reserve again");
     ug_ctx* c = hp->ctx;
     c->use();
-    ScopedTimer tm(c, &c->fft_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->fft);
     hipStream_t st = c->stream;
     u64 n = hp->domain;
     if (which == 2 && hp->mat.logn == 0) {
@@ -1821,7 +1747,7 @@ int ug_hpoly_combine(ug_hpoly* hp, const ug_dvec* a, const ug_dvec* b, const ug_
     if (first + count > h_out->n) throw std::invalid_argument("h slice outside the h vector");
     ug_ctx* c = hp ? hp->ctx : h_out->ctx;      // (a rank that runs no chain keeps no ug_hpoly: the combine needs none)
     c->use();
-    ScopedTimer tm(c, &c->fft_ms);
+    StreamTimer::Scope tm = c->timer.time(c->stream, &c->fft);
     fr_h_final(h_out->data + first * 8, a->data, b->data, cc->data, count, c->stream);
     tm.stop();
     UG_CATCH
@@ -2111,12 +2037,12 @@ int ug_graph_begin(ug_ctx* c, ug_ctx* c2) {
     g->capturing = true;
     ug_graph* raw = g.release();
     c->recording = raw;
-    for (int k = 0; k < 4; k++) c->stats[k].capture = &raw->cap[0][k];
+    c->timer.capture_into(&raw->pairs[0]);
     if (c2) {
         c2->recording = raw;
-        for (int k = 0; k < 4; k++) c2->stats[k].capture = &raw->cap[1][k];
-        hipError_t e = hipEventRecord(c->order_event, c->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c2->stream, c->order_event, 0);      // ctx2's stream joins the capture
+        c2->timer.capture_into(&raw->pairs[1]);
+        hipError_t e = hipEventRecord(c->order_event.e, c->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c2->stream, c->order_event.e, 0);      // ctx2's stream joins the capture
         if (e != hipSuccess) { ug_graph_abort(c); UG_HIP(e); }
     }
     UG_CATCH
@@ -2125,7 +2051,7 @@ static void graph_unhook(ug_graph* g) {
     for (int q = 0; q < 2; q++) {
         if (!g->c[q]) continue;
         g->c[q]->recording = nullptr;
-        for (int k = 0; k < 4; k++) g->c[q]->stats[k].capture = nullptr;
+        g->c[q]->timer.capture_into(nullptr);
     }
 }
 void ug_graph_abort(ug_ctx* c) {
@@ -2151,8 +2077,8 @@ int ug_graph_end(ug_ctx* c, ug_graph** out) {
     c->use();
     try {
         if (g->c[1]) {                                     // join: the first stream waits for everything queued on the second
-            UG_HIP(hipEventRecord(g->c[1]->order_event, g->c[1]->stream));
-            UG_HIP(hipStreamWaitEvent(c->stream, g->c[1]->order_event, 0));
+            UG_HIP(hipEventRecord(g->c[1]->order_event.e, g->c[1]->stream));
+            UG_HIP(hipStreamWaitEvent(c->stream, g->c[1]->order_event.e, 0));
         }
         hipError_t e = hipStreamEndCapture(c->stream, &g->graph);
         g->capturing = false;
@@ -2199,10 +2125,8 @@ void ug_graph_destroy(ug_graph* g) {
     }
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     if (g->graph) (void)hipGraphDestroy(g->graph);
-    for (auto& t : g->spans) { hipEventDestroy(t.e0); hipEventDestroy(t.e1); }
-    for (int q = 0; q < 2; q++) for (int k = 0; k < 4; k++) for (auto& sp : g->cap[q][k]) { if (sp.e0) hipEventDestroy(sp.e0); if (sp.e1) hipEventDestroy(sp.e1); }
+    delete g;                                   // (with its event pairs)
     (void)hipGetLastError();
-    delete g;
 }
 
 int ug_ctx_timings(ug_ctx* c, double* msm_ms, double* fft_ms, int reset) {
@@ -2210,9 +2134,9 @@ int ug_ctx_timings(ug_ctx* c, double* msm_ms, double* fft_ms, int reset) {
     if (!c) throw std::invalid_argument("null argument");
     c->use();
     sync_and_resolve(c);
-    if (msm_ms) *msm_ms = c->msm_ms;
-    if (fft_ms) *fft_ms = c->fft_ms;
-    if (reset) { c->msm_ms = 0; c->fft_ms = 0; }
+    if (msm_ms) *msm_ms = c->msm.ms;
+    if (fft_ms) *fft_ms = c->fft.ms;
+    if (reset) { c->msm = TimeSink(); c->fft = TimeSink(); }
     UG_CATCH
 }
 int ug_ctx_kernel_stats(ug_ctx* c, int which, double* avg_ms, uint64_t* launches, uint64_t* entries, int reset) {
@@ -2221,11 +2145,11 @@ int ug_ctx_kernel_stats(ug_ctx* c, int which, double* avg_ms, uint64_t* launches
     if (which < 0 || which > 3) throw std::invalid_argument("kernel stats: 0 = G1 accumulation, 1 = G2 accumulation, 2 = NTT pass, 3 = G1 group accumulation");
     c->use();
     sync_and_resolve(c);
-    MsmStats& st = c->stats[which];
-    if (avg_ms) *avg_ms = st.launches ? st.accumulate_ms / (double)st.launches : 0.0;
+    TimeSink& st = c->kernel[which];
+    if (avg_ms) *avg_ms = st.launches ? st.ms / (double)st.launches : 0.0;
     if (launches) *launches = st.launches;
-    if (entries) *entries = st.entries;
-    if (reset) { st.accumulate_ms = 0; st.launches = 0; st.entries = 0; c->kernel_stats_on = true; }
+    if (entries) *entries = st.units;
+    if (reset) { st = TimeSink(); c->kernel_stats_on = true; }
     UG_CATCH
 }
 
