@@ -74,6 +74,7 @@
  *                      UG_REDUCE_G1_LOG, UG_REDUCE_G2_LOG   lanes the bucket reduction keeps busy (default 17, 16)
  *                      UG_UPLOAD_PRIORITY=l|n|h   stream class of the witness staging lanes (default l)
  *                      UG_NTT_SHOUP=0             Montgomery-form twiddle products in the NTT passes (default: Shoup form, ff.hpp mul_shoup)
+ *                      UG_SETUP_WINDOW_G1, UG_SETUP_WINDOW_G2   window width (4 .. 16) of the development setup's generator tables
  *   test hooks         ULTRAGROTH_TEST_HOOKS=1 enables ug_test_set_blinding / ULTRAGROTH_TEST_BLINDING and ug_test_inject_fault;
  *                      without it those calls fail and the variables are ignored
  *   measurement        NOT in this library: UG_SORT=cub (library sort, links hipcub), UG_GROUP_FOLD_LOG (gathers folded into
@@ -480,6 +481,60 @@ int  ug_r1cs_check_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, i
 int  ug_r1cs_check_collect(ug_r1cs* r, int slot, ug_r1cs_report* out);
 int  ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* matrix, uint64_t* row);
 void ug_r1cs_destroy(ug_r1cs* r);
+
+/* DEVELOPMENT SETUP: .r1cs + a KNOWN trapdoor -> a proving key and its verification key (setup.hip, setup_host.cpp; no reference
+ * counterpart: the reference starts from a .zkey somebody else made). THE KEY IS A TEST KEY: whoever knows tau, alpha, beta,
+ * gamma and the deltas forges proofs for it. It is for benchmarks, integration tests and CI, where a key must be structurally
+ * real for a circuit today; it is never a substitute for a ceremony.
+ *
+ * The protocol is that of tests/golden/make_trapdoor_fixtures.py, which is the specification. Domain N = 2^log_domain (0: the
+ * smallest that holds nConstraints + nPublic + 1 rows; at most 2^27); rows nConstraints + s, 0 <= s <= nPublic = nPubOut + nPubIn,
+ * are snarkjs' public rows (A = {s: 1}). With L_k the Lagrange basis of the domain of omega = 5^((r-1)/N), per wire s:
+ * u_s = sum_k A[k,s] L_k(tau), v_s, w_s likewise from B and C, K_s = beta u_s + alpha v_s + w_s;
+ *   A_s = u_s G1, B1_s = v_s G1, B2_s = v_s G2, IC_s = K_s / gamma G1 (s <= nPublic),
+ *   protocol 1:    C_s = K_s / delta_final G1 (s > nPublic);
+ *   protocol 1337: C1 = K_s / delta_round G1 over round_signals, C2 = K_s / delta_final G1 over final_signals -- the two lists
+ *                  must partition nPublic + 1 .. nVars - 1 --, rand_indx a public signal;
+ *   H_k = L_k(tau / g) (tau^N - 1) / (-2 delta_final) G1, g = omega_2N.
+ * A scalar of 0 gives the all-zero record. Section 4: one record per (matrix, row, wire), row first, A before B, wire ascending,
+ * value coef * 2^512 mod r; repeated wires of a combination are added, a sum of 0 is left out; the public rows are included.
+ * The verification key is JSON with the fields of snarkjs (protocol 1337: nPublic without the rand signal, IC without it, IC_rand).
+ *
+ * A call fails, the message prefixed "setup: " (or "r1cs: ", from the loader), for: tau^(2N) = 1 (tau or tau / g lies in the
+ * domain); alpha, beta, gamma or a delta that is 0 mod r; a value not below r; a log_domain too small or above 27; lists that do
+ * not partition the private signals; sizes that cannot be represented. Errors come back in error_msg, as in include/prover.h.
+ *
+ * device >= 0: Lagrange evaluation, the transposed sparse products and the fixed-base multiplications run as kernels on that
+ * device; device = -1: the same steps on host threads (the comparator, and what a program without a GPU has). Both give the
+ * same bytes. The six trapdoor values are plain 32-byte little-endian integers. */
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_setup_options) */
+    uint32_t protocol;                  /* 1 Groth16, 1337 UltraGroth */
+    uint32_t log_domain;                /* 0: the smallest domain that fits */
+    uint32_t rand_indx;                 /* protocol 1337 only */
+    uint8_t  tau[32], alpha[32], beta[32], gamma[32], delta_round[32], delta_final[32];     /* protocol 1 reads delta_final only */
+    const uint32_t* round_signals; uint64_t n_round;        /* protocol 1337 only */
+    const uint32_t* final_signals; uint64_t n_final;
+} ug_setup_options;
+#define UG_SETUP_PHASES 6   /* parse + index (+ upload) | Lagrange | transposed products | G1 mult. | G2 mult. | download + assembly */
+/* fills the six trapdoor values from OS entropy: uniform below r, never 0 */
+int  ug_setup_draw_trapdoor(ug_setup_options* opt, char* error_msg, unsigned long long error_msg_maxsize);
+/* host only: the exact size of the zkey the run writes, and an upper bound of the verification key's JSON with its final 0 */
+int  ug_setup_size(const ug_setup_options* opt, const void* r1cs, uint64_t r1cs_size, uint64_t* zkey_bytes, uint64_t* vkey_bytes_max,
+                   char* error_msg, unsigned long long error_msg_maxsize);
+/* fills zkey (zkey_capacity >= the size query's answer) and vkey_json (0-terminated; *vkey_bytes = its length without the 0);
+ * phase_ms: UG_SETUP_PHASES doubles, milliseconds per phase (device phases by stream events), or NULL */
+int  ug_setup_run(const ug_setup_options* opt, const void* r1cs, uint64_t r1cs_size, int device, void* zkey, uint64_t zkey_capacity,
+                  uint64_t* zkey_bytes, char* vkey_json, uint64_t vkey_capacity, uint64_t* vkey_bytes, double* phase_ms, char* error_msg,
+                  unsigned long long error_msg_maxsize);
+/* Test tooling, in the spirit of ug_fr_ntt / ug_field_op. ug_generator_mul: out[i] = scalars[i] * G as zkey-format affine records
+ * (64 bytes for G1, 128 for G2), scalars plain 32-byte integers below r, host buffers; window: the width of the signed-digit
+ * window tables, 4 .. 16, 0 = the default; kernel_ms (may be NULL): two doubles, the milliseconds of the table build and of the
+ * multiplication kernels (host threads: 0 and the whole call).
+ * ug_lagrange_at: out[k] = L_k(x) (coset != 0: L_k(x / omega_2N)) of the size-2^log_n domain, N plain 32-byte integers. */
+int  ug_generator_mul(int device, int g2, const void* scalars, uint64_t n, int window, void* out, double* kernel_ms, char* error_msg,
+                      unsigned long long error_msg_maxsize);
+int  ug_lagrange_at(int device, int log_n, const void* x, int coset, void* out, char* error_msg, unsigned long long error_msg_maxsize);
 
 /* In-place size-2^logn transform of a host buffer of Montgomery Fr elements, natural order in and out.
  * inverse != 0 also scales by 1/n. */

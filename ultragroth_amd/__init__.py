@@ -173,6 +173,130 @@ def r1cs_info(r1cs):
 
 
 # ---------------------------------------------------------------------------------------------------
+# development setup (include/ultragroth_hip.h: ug_setup_*): a TEST key from an .r1cs and a known trapdoor
+R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+TRAPDOOR_KEYS = ("tau", "alpha", "beta", "gamma", "delta_round", "delta_final")
+SETUP_PHASES = ("parse", "lagrange", "products", "g1", "g2", "assembly")
+
+
+class SetupError(RuntimeError):
+    pass
+
+
+class _SetupOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("protocol", C.c_uint32), ("log_domain", C.c_uint32), ("rand_indx", C.c_uint32)] + \
+               [(k, C.c_ubyte * 32) for k in TRAPDOOR_KEYS] + \
+               [("round_signals", C.POINTER(C.c_uint32)), ("n_round", C.c_uint64),
+                ("final_signals", C.POINTER(C.c_uint32)), ("n_final", C.c_uint64)]
+
+
+def _setup_call(fn, *args):
+    err = C.create_string_buffer(1024)
+    if fn(*args, err, len(err) - 1) != 0:
+        raise SetupError(err.value.decode(errors="replace"))
+
+
+def _le32(value, what):
+    value = int(value)
+    if not 0 <= value < 1 << 256:
+        raise SetupError("setup: %s is not below the field modulus" % what)
+    return (C.c_ubyte * 32)(*value.to_bytes(32, "little"))
+
+
+def _setup_options(trapdoor, protocol, log_domain, ultra):
+    """(options struct, the arrays it points into) of dev_setup's arguments; trapdoor None: drawn from OS entropy"""
+    opt = _SetupOptions()
+    opt.size = C.sizeof(_SetupOptions)
+    if protocol in ("groth16", 1):
+        opt.protocol = 1
+    elif protocol in ("ultragroth", 1337):
+        opt.protocol = 1337
+    else:
+        raise SetupError("setup: protocol %r is neither groth16 nor ultragroth" % (protocol,))
+    opt.log_domain = log_domain
+    if trapdoor is None:
+        _setup_call(load().ug_setup_draw_trapdoor, C.byref(opt))
+    else:
+        for k in TRAPDOOR_KEYS:
+            if k not in trapdoor and not (k == "delta_round" and opt.protocol == 1):
+                raise SetupError("setup: the trapdoor has no %s" % k)
+            setattr(opt, k, _le32(trapdoor.get(k, 0), k))
+    keep = []
+    if opt.protocol == 1337:
+        if ultra is None:
+            raise SetupError("setup: protocol 1337 needs rand_indx and the round and final signal lists")
+        opt.rand_indx = int(ultra["rand_indx"])
+        for name, count in (("round_signals", "n_round"), ("final_signals", "n_final")):
+            arr = (C.c_uint32 * max(1, len(ultra[name])))(*ultra[name])
+            keep.append(arr)
+            setattr(opt, name, C.cast(arr, C.POINTER(C.c_uint32)))
+            setattr(opt, count, len(ultra[name]))
+    return opt, keep
+
+
+def dev_setup(r1cs, trapdoor=None, protocol="groth16", log_domain=0, device=0, ultra=None, timings=None):
+    """ug_setup_run: a development setup. Returns (zkey_bytes, vkey_dict, trapdoor_dict) for the circuit of the .r1cs bytes.
+
+    THE RESULT IS A TEST KEY: whoever knows the trapdoor forges proofs for it. It is for benchmarks, integration tests and CI.
+
+    trapdoor: a dict with TRAPDOOR_KEYS (integers or decimal strings, the form of tests/golden/trapdoor/trapdoor.json); None
+    draws one from OS entropy. The dict returned holds the values used, as decimal strings. protocol: "groth16" (1) or
+    "ultragroth" (1337); the latter takes ultra = {"rand_indx": n, "round_signals": [...], "final_signals": [...]}.
+    log_domain 0 is the smallest domain that fits. device=-1 runs on host threads and gives the same bytes.
+    timings: a dict that receives the milliseconds of SETUP_PHASES. Refusals raise SetupError ("setup: ..." / "r1cs: ...")."""
+    import json
+    L = load()
+    opt, keep = _setup_options(trapdoor, protocol, log_domain, ultra)
+    r1cs = bytes(r1cs)
+    zbytes, vmax = C.c_uint64(), C.c_uint64()
+    _setup_call(L.ug_setup_size, C.byref(opt), r1cs, len(r1cs), C.byref(zbytes), C.byref(vmax))
+    zkey = C.create_string_buffer(zbytes.value)
+    vkey = C.create_string_buffer(vmax.value)
+    wrote, vlen = C.c_uint64(), C.c_uint64()
+    ms = (C.c_double * len(SETUP_PHASES))()
+    _setup_call(L.ug_setup_run, C.byref(opt), r1cs, len(r1cs), device, zkey, zbytes.value, C.byref(wrote), vkey, vmax.value, C.byref(vlen), ms)
+    if timings is not None:
+        timings.update(zip(SETUP_PHASES, ms))
+    used = {k: str(_le(getattr(opt, k))) for k in TRAPDOOR_KEYS}
+    return zkey.raw[:wrote.value], json.loads(vkey.raw[:vlen.value].decode()), used
+
+
+def dev_setup_size(r1cs, trapdoor, protocol="groth16", log_domain=0, ultra=None):
+    """ug_setup_size (host only): the exact length of the zkey dev_setup returns for these arguments"""
+    opt, keep = _setup_options(trapdoor, protocol, log_domain, ultra)
+    r1cs = bytes(r1cs)
+    zbytes, vmax = C.c_uint64(), C.c_uint64()
+    _setup_call(load().ug_setup_size, C.byref(opt), r1cs, len(r1cs), C.byref(zbytes), C.byref(vmax))
+    return zbytes.value
+
+
+def generator_mul(scalars, g2=False, device=0, window=0, timing=None):
+    """ug_generator_mul (test tooling): [scalar * G] as zkey-format affine records (64 bytes for G1, 128 for G2; a scalar of 0
+    gives the all-zero record) for integers below r. window: the signed-digit window width, 0 = the default. device=-1: host
+    threads. timing: a list that receives (table build ms, multiplication ms)."""
+    scalars = [int(s) for s in scalars]
+    for s in scalars:
+        if not 0 <= s < 1 << 256:
+            raise SetupError("setup: a scalar is not below the field modulus")
+    data = b"".join(s.to_bytes(32, "little") for s in scalars)
+    rec = 128 if g2 else 64
+    out = C.create_string_buffer(max(1, rec * len(scalars)))
+    ms = (C.c_double * 2)()
+    _setup_call(load().ug_generator_mul, device, 1 if g2 else 0, data, len(scalars), window, out, ms)
+    if timing is not None:
+        timing.append((ms[0], ms[1]))
+    return [out.raw[rec * i:rec * i + rec] for i in range(len(scalars))]
+
+
+def lagrange_at(x, log_n, coset=False, device=0):
+    """ug_lagrange_at (test tooling): [L_k(x)] (coset: L_k(x / omega_2N)) of the size-2^log_n domain, as integers"""
+    n = 1 << log_n if 0 <= log_n < 32 else 0
+    out = C.create_string_buffer(max(1, 32 * n))
+    _setup_call(load().ug_lagrange_at, device, log_n, int(x).to_bytes(32, "little"), 1 if coset else 0, out)
+    return [int.from_bytes(out.raw[32 * k:32 * k + 32], "little") for k in range(n)]
+
+
+# ---------------------------------------------------------------------------------------------------
 # verifier mirror (src/verifier.h)
 VERIFIER_VALID_PROOF, VERIFIER_INVALID_PROOF, VERIFIER_ERROR = 0, 1, 2
 
