@@ -536,6 +536,79 @@ int  ug_generator_mul(int device, int g2, const void* scalars, uint64_t n, int w
                       unsigned long long error_msg_maxsize);
 int  ug_lagrange_at(int device, int log_n, const void* x, int coset, void* out, char* error_msg, unsigned long long error_msg_maxsize);
 
+/* PHASE-2 SETUP FROM A PREPARED POWERS-OF-TAU FILE: .r1cs + .ptau -> a Groth16 (protocol 1) proving key and its verification key
+ * (setup_ptau.cpp, setup_points.hip; what `snarkjs zkey new` does, then optionally ONE delta contribution). No trapdoor is known
+ * to this code: tau, alpha and beta stay inside the points of the ceremony.
+ * OUT OF SCOPE: UltraGroth keys (protocol 1337); contribution transcripts (the zkey's section 10 is written empty, so
+ * `snarkjs zkey verify` does not accept a key made here); beacons; verifying the .ptau's own ceremony. A key made without a
+ * contribution has delta = 1: ANYONE forges proofs for it. A key made with a drawn delta is a single-party phase 2: it is sound
+ * only if that run's delta is gone and the .ptau is honest.
+ *
+ * The .ptau layout, AS REMEMBERED of snarkjs' format. NO FILE OF A REAL CEREMONY HAS BEEN READ YET: this restatement is the only
+ * pin, as it was for .r1cs; the reader (host_util.cpp) and the test writer (ultragroth_amd/synth.py: ptau_file) are written from it.
+ * The iden3 binfile container with magic "ptau", version 1; sections are found by id, their order does not matter:
+ *   section 1 (header)        u32 n8 (must be 32) | prime[n8] little-endian (must be the BN254 BASE modulus q) | u32 power |
+ *                             u32 ceremonyPower
+ *   section 2  tauG1          2^(power+1) - 1 G1 points     section 3  tauG2       2^power G2 points
+ *   section 4  alphaTauG1     2^power G1 points             section 5  betaTauG1   2^power G1 points
+ *   section 6  betaG2         1 G2 point                    section 7  contributions: not read
+ *   A point is the zkey's own affine record: 64 bytes (G1) or 128 bytes (G2), coordinates little-endian in Montgomery form
+ *   (R = 2^256); all-zero is infinity.
+ *   sections 12, 13, 14, 15   the Lagrange forms of sections 2, 3, 4, 5, present only after `powersoftau prepare phase2`:
+ *                             levels p = 0 .. power concatenated, level p = the 2^p points [L_k^(2^p)(tau)] X, so level p starts
+ *                             at record 2^p - 1. Section 12 alone has one more level, p = power + 1, made from the 2^(power+1) - 1
+ *                             powers the ceremony has with infinity in place of the missing top power: its point j is
+ *                             [L_j(tau) - c_j tau^(2^(power+1) - 1)] G1, c_j the leading coefficient of L_j.
+ * Read, for a circuit of domain N = 2^n (n chosen as ug_setup_run chooses it, or log_domain; n <= power): level n of sections
+ * 12 - 15, the odd records of level n + 1 of section 12, record 0 of sections 4 and 5, section 6. Nothing else is touched and
+ * nothing is copied whole: the call takes a (mapped) buffer.
+ * A call fails, the message prefixed "ptau: ", for: a missing or short section 1; n8 != 32; another prime; sections 12 - 15 absent
+ * ("not prepared for phase 2"); "power <p> is below the circuit's <n>"; a section shorter than the slices need; sizes that cannot
+ * be represented (a power above 28). Every such rule fires before the first device byte. The slices then go through the point
+ * check (ug_points_check: validate = 1 field range and curve, the default of the tools; 2 the G2 subgroup as well; 0 none):
+ * "ptau: section <id> point <index>: <reason>", index counted in the section.
+ *
+ * The key. T, T2, aT, bT = the level-n slices of sections 12, 13, 14, 15; rows as in ug_setup_run (row nConstraints + s carries
+ * A = {s: 1}); per wire s:
+ *   A_s = sum_{A terms (k,s)} coef T[k]     B1_s = sum_{B terms} coef T[k]     B2_s = sum_{B terms} coef T2[k]
+ *   K_s = sum_{A terms} coef bT[k] + sum_{B terms} coef aT[k] + sum_{C terms} coef T[k]
+ *   IC_s = K_s (s <= nPublic), C_s = (1/delta) K_s (s > nPublic), H_k = (1/delta) (record 2k+1 of section 12, level n + 1)
+ *   alpha1 = section 4 [0], beta1 = section 5 [0], beta2 = section 6, gamma2 = G2, delta1 = delta G1, delta2 = delta G2
+ * delta = 1 without a contribution (what `zkey new` writes). A wire on no side and a sum that is the neutral element give the
+ * all-zero record. Section 4, the headers, the section order and the JSON are ug_setup_run's. For a .ptau made from a known
+ * (tau, alpha, beta) the key equals, byte for byte, ug_setup_run's for the trapdoor (tau, alpha, beta, gamma = 1, delta).
+ * device >= 0: the per-wire point combinations and the delta step run as kernels; device = -1: host threads, the same bytes. */
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_setup_ptau_options) */
+    uint32_t log_domain;                /* 0: the smallest domain that fits */
+    uint32_t validate;                  /* 0 no point check, 1 field range + curve, 2 the G2 subgroup as well */
+    uint32_t contribute;                /* 0: delta = 1; 1: delta[] is applied; 2: a delta is drawn from OS entropy, applied, wiped and
+                                           never returned or logged */
+    uint8_t  delta[32];                 /* contribute = 1: plain little-endian, below r, not 0 */
+} ug_setup_ptau_options;
+#define UG_SETUP_PTAU_PHASES 6   /* parse + index | point check | G1 combinations | G2 combination | delta step | assembly */
+typedef struct { uint32_t power, ceremony_power, prepared, max_log_domain; } ug_ptau_info;
+/* host only: the header; prepared = sections 12 - 15 are there; max_log_domain = the largest domain the file serves (0: none) */
+int  ug_ptau_parse_info(const void* ptau, uint64_t ptau_size, ug_ptau_info* out, char* error_msg, unsigned long long error_msg_maxsize);
+/* host only: every rule of both files, the exact size of the zkey and an upper bound of the JSON with its final 0 */
+int  ug_setup_ptau_size(const ug_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
+                        uint64_t* zkey_bytes, uint64_t* vkey_bytes_max, char* error_msg, unsigned long long error_msg_maxsize);
+/* phase_ms: UG_SETUP_PTAU_PHASES doubles or NULL */
+int  ug_setup_ptau_run(const ug_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
+                       int device, void* zkey, uint64_t zkey_capacity, uint64_t* zkey_bytes, char* vkey_json, uint64_t vkey_capacity,
+                       uint64_t* vkey_bytes, double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize);
+/* Test tooling for the two heavy steps, host buffers, device >= 0 or -1 (host threads); messages prefixed "setup: ".
+ * ug_points_combine: out[c] = sum over the terms [col_ptr[c], col_ptr[c + 1]) of coefs[t] * points[index[t]], one zkey-format
+ * record per column (64 bytes for G1, 128 for G2); col_ptr: n_cols + 1 offsets from 0, ascending; coefs plain 32-byte integers
+ * below r; points: n_points zkey-format records (not validated here: ug_points_check does that). kernel_ms (may be NULL): two
+ * doubles, the per-term products and the per-column sums.
+ * ug_points_scale: out[i] = scalar * points[i] over n G1 records; kernel_ms (may be NULL): one double. */
+int  ug_points_combine(int device, int g2, const uint32_t* col_ptr, uint64_t n_cols, const uint32_t* index, const void* coefs,
+                       const void* points, uint64_t n_points, void* out, double* kernel_ms, char* error_msg,
+                       unsigned long long error_msg_maxsize);
+int  ug_points_scale(int device, const void* scalar, const void* points, uint64_t n, void* out, double* kernel_ms, char* error_msg,
+                     unsigned long long error_msg_maxsize);
+
 /* In-place size-2^logn transform of a host buffer of Montgomery Fr elements, natural order in and out.
  * inverse != 0 also scales by 1/n. */
 int  ug_fr_ntt(ug_ctx* ctx, void* host_data, int logn, int inverse);

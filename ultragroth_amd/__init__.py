@@ -297,6 +297,140 @@ def lagrange_at(x, log_n, coset=False, device=0):
 
 
 # ---------------------------------------------------------------------------------------------------
+# phase-2 setup from a prepared powers-of-tau file (include/ultragroth_hip.h: ug_setup_ptau_*): a Groth16 key from an .r1cs
+# and a .ptau, optionally with one delta contribution. No trapdoor is known to this code.
+SETUP_PTAU_PHASES = ("parse", "point_check", "g1", "g2", "delta", "assembly")
+
+
+class _SetupPtauOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_domain", C.c_uint32), ("validate", C.c_uint32), ("contribute", C.c_uint32),
+                ("delta", C.c_ubyte * 32)]
+
+
+class _PtauInfo(C.Structure):
+    _fields_ = [("power", C.c_uint32), ("ceremony_power", C.c_uint32), ("prepared", C.c_uint32), ("max_log_domain", C.c_uint32)]
+
+
+class _Mapped:
+    """bytes, a memoryview / mmap, or a path (mapped here, read-only) as (address, length) for a C call that only reads;
+    nothing is copied"""
+
+    def __init__(self, src):
+        import mmap
+        import os
+        import numpy as np
+        self._close = []
+        if isinstance(src, (str, os.PathLike)):
+            f = open(src, "rb")
+            self._close.append(f)
+            if os.fstat(f.fileno()).st_size == 0:
+                src = b""
+            else:
+                src = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+                self._close.insert(0, src)
+        self._keep = np.frombuffer(src, dtype=np.uint8)
+        self.length = int(self._keep.size)
+        self.address = C.c_void_p(self._keep.ctypes.data if self.length else 0)
+
+    def close(self):
+        self._keep = None                           # (an mmap cannot close while a view of it is alive)
+        for c in self._close:
+            c.close()
+
+
+def ptau_info(ptau):
+    """ug_ptau_parse_info (host only): {"power", "ceremony_power", "prepared", "max_log_domain"} of a .ptau given as bytes, a
+    memoryview / mmap or a path. The layout is restated in include/ultragroth_hip.h; no file of a real ceremony has been read yet."""
+    m = _Mapped(ptau)
+    try:
+        info = _PtauInfo()
+        _setup_call(load().ug_ptau_parse_info, m.address, m.length, C.byref(info))
+    finally:
+        m.close()
+    return {"power": info.power, "ceremony_power": info.ceremony_power, "prepared": bool(info.prepared), "max_log_domain": info.max_log_domain}
+
+
+def setup_from_ptau(r1cs, ptau, delta=None, log_domain=0, device=0, validate=1, timings=None):
+    """ug_setup_ptau_run: a Groth16 proving key and verification key from a circuit's .r1cs and a .ptau prepared for phase 2
+    (what `snarkjs zkey new` does). Returns (zkey_bytes, vkey_dict, phase_ms_dict).
+
+    ptau: bytes, a memoryview / mmap, or a path that is mapped here; only the slices the circuit's domain needs are read.
+    delta: None writes delta = 1 -- ANYONE forges proofs for such a key until a contribution is applied; an integer below r applies
+    that delta; "draw" draws one from OS entropy, applies and wipes it (a single-party phase 2 with no transcript: sound only if
+    that delta is gone and the .ptau is honest; `snarkjs zkey verify` does not accept the key).
+    validate: 0 none, 1 field range and curve of every point read, 2 the G2 subgroup as well. device=-1 runs on host threads and
+    gives the same bytes. UltraGroth keys, transcripts, beacons and verifying the .ptau's ceremony are out of scope.
+    Refusals raise SetupError ("ptau: ..." / "r1cs: ..." / "setup: ...")."""
+    import json
+    L = load()
+    opt = _SetupPtauOptions()
+    opt.size = C.sizeof(_SetupPtauOptions)
+    opt.log_domain, opt.validate = log_domain, validate
+    if delta is None:
+        opt.contribute = 0
+    elif isinstance(delta, str):
+        if delta != "draw":
+            raise SetupError("setup: delta is None, an integer or \"draw\"")
+        opt.contribute = 2
+    else:
+        opt.contribute = 1
+        opt.delta = _le32(delta, "delta")
+    r1cs = bytes(r1cs)
+    m = _Mapped(ptau)
+    try:
+        zbytes, vmax = C.c_uint64(), C.c_uint64()
+        _setup_call(L.ug_setup_ptau_size, C.byref(opt), r1cs, len(r1cs), m.address, m.length, C.byref(zbytes), C.byref(vmax))
+        zkey = C.create_string_buffer(zbytes.value)
+        vkey = C.create_string_buffer(vmax.value)
+        wrote, vlen = C.c_uint64(), C.c_uint64()
+        ms = (C.c_double * len(SETUP_PTAU_PHASES))()
+        _setup_call(L.ug_setup_ptau_run, C.byref(opt), r1cs, len(r1cs), m.address, m.length, device, zkey, zbytes.value, C.byref(wrote), vkey,
+                    vmax.value, C.byref(vlen), ms)
+    finally:
+        m.close()
+    phase_ms = dict(zip(SETUP_PTAU_PHASES, ms))
+    if timings is not None:
+        timings.update(phase_ms)
+    return zkey.raw[:wrote.value], json.loads(vkey.raw[:vlen.value].decode()), phase_ms
+
+
+def points_combine(col_ptr, index, coefs, points, g2=False, device=0, timing=None):
+    """ug_points_combine (test tooling): one zkey-format record per column, the sum over the column's terms of coefs[t] *
+    points[index[t]]. col_ptr: n_cols + 1 ascending offsets from 0; coefs: integers below r; points: zkey-format records (64
+    bytes for G1, 128 for G2; all-zero is infinity). device=-1: host threads. timing: a list that receives (product ms, sum ms)."""
+    rec = 128 if g2 else 64
+    n_cols = len(col_ptr) - 1
+    for c in coefs:
+        if not 0 <= int(c) < 1 << 256:
+            raise SetupError("setup: a coefficient is not below the field modulus")
+    cp = (C.c_uint32 * (n_cols + 1))(*col_ptr)
+    ix = (C.c_uint32 * max(1, len(index)))(*index)
+    co = b"".join(int(c).to_bytes(32, "little") for c in coefs)
+    pts = b"".join(points)
+    if len(pts) != rec * len(points):
+        raise SetupError("setup: a point record of another size")
+    out = C.create_string_buffer(max(1, rec * n_cols))
+    ms = (C.c_double * 2)()
+    _setup_call(load().ug_points_combine, device, 1 if g2 else 0, cp, n_cols, ix, co, pts, len(points), out, ms)
+    if timing is not None:
+        timing.append((ms[0], ms[1]))
+    return [out.raw[rec * i:rec * i + rec] for i in range(n_cols)]
+
+
+def points_scale(scalar, points, device=0, timing=None):
+    """ug_points_scale (test tooling): [scalar * P] for G1 records P (64 bytes, all-zero is infinity), scalar an integer below r"""
+    pts = b"".join(points)
+    if len(pts) != 64 * len(points):
+        raise SetupError("setup: a point record of another size")
+    out = C.create_string_buffer(max(1, 64 * len(points)))
+    ms = (C.c_double * 1)()
+    _setup_call(load().ug_points_scale, device, bytes(_le32(scalar, "scalar")), pts, len(points), out, ms)
+    if timing is not None:
+        timing.append(ms[0])
+    return [out.raw[64 * i:64 * i + 64] for i in range(len(points))]
+
+
+# ---------------------------------------------------------------------------------------------------
 # verifier mirror (src/verifier.h)
 VERIFIER_VALID_PROOF, VERIFIER_INVALID_PROOF, VERIFIER_ERROR = 0, 1, 2
 

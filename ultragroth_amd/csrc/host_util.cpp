@@ -207,6 +207,63 @@ void loadR1cs(const BinFile& f, R1cs& out) {
     walkR1cs(f.sectionData(2), f.sectionSize(2), out.hdr, again, out.m);
 }
 
+// ---- .ptau --------------------------------------------------------------------------------------------------
+const uint8_t BN254_Q_LE[32] = {
+    0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
+    0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+
+namespace {
+struct PtauError : public std::invalid_argument {
+    explicit PtauError(const std::string& m) : std::invalid_argument("ptau: " + m) {}
+};
+constexpr uint32_t PTAU_MAX_POWER = 28;        // the two-adicity of r: no ceremony over BN254 is larger
+// the first `records` records of `rec` bytes of section id; the count is compared with the section's own, never multiplied up
+const uint8_t* ptauRecords(const BinFile& f, uint32_t id, uint64_t records, uint64_t rec) {
+    if (!f.hasSection(id)) throw PtauError("section " + std::to_string(id) + " is missing");
+    if (f.sectionSize(id) / rec < records)
+        throw PtauError("section " + std::to_string(id) + " is too short: " + std::to_string(records) + " records of " + std::to_string(rec) +
+                        " bytes are needed, it has " + std::to_string(f.sectionSize(id)) + " bytes");
+    return f.sectionData(id);
+}
+}  // namespace
+
+PtauHeader loadPtauHeader(const BinFile& f) {
+    if (!f.hasSection(1)) throw PtauError("section 1 (header) is missing");
+    const uint8_t* p = f.sectionData(1);
+    const uint64_t size = f.sectionSize(1);
+    PtauHeader h;
+    if (size < 4) throw PtauError("section 1 (header) is too short");
+    h.n8 = rd32(p);
+    if (h.n8 != 32) throw PtauError("n8 is " + std::to_string(h.n8) + ", not 32");
+    if (size < 4 + 32 + 8) throw PtauError("section 1 (header) is too short");
+    if (memcmp(p + 4, BN254_Q_LE, 32) != 0) throw PtauError("not over the BN254 base field");
+    h.power = rd32(p + 36);
+    h.ceremonyPower = rd32(p + 40);
+    if (h.power > PTAU_MAX_POWER) throw PtauError("sizes that cannot be represented: power " + std::to_string(h.power) + " is above " + std::to_string(PTAU_MAX_POWER));
+    h.prepared = f.hasSection(12) && f.hasSection(13) && f.hasSection(14) && f.hasSection(15);
+    return h;
+}
+
+PtauSlices loadPtauSlices(const BinFile& f, const PtauHeader& h, uint32_t logN) {
+    if (!h.prepared) throw PtauError("not prepared for phase 2 (sections 12 - 15, the Lagrange forms, are absent)");
+    if (h.power < logN) throw PtauError("power " + std::to_string(h.power) + " is below the circuit's " + std::to_string(logN));
+    // (logN <= power <= 28: no count below passes 2^30, no byte offset 2^37)
+    PtauSlices s;
+    s.n = 1ull << logN;
+    s.first = s.n - 1;
+    s.firstTop = 2 * s.n - 1;
+    const uint8_t* s12 = ptauRecords(f, 12, 4 * s.n - 1, 64);         // levels 0 .. logN + 1
+    s.tau1 = s12 + s.first * 64;
+    s.top = s12 + s.firstTop * 64;
+    s.tau2 = ptauRecords(f, 13, 2 * s.n - 1, 128) + s.first * 128;     // levels 0 .. logN
+    s.alphaTau1 = ptauRecords(f, 14, 2 * s.n - 1, 64) + s.first * 64;
+    s.betaTau1 = ptauRecords(f, 15, 2 * s.n - 1, 64) + s.first * 64;
+    s.alpha1 = ptauRecords(f, 4, 1, 64);
+    s.beta1 = ptauRecords(f, 5, 1, 64);
+    s.beta2 = ptauRecords(f, 6, 1, 128);
+    return s;
+}
+
 // ---- decimal ---------------------------------------------------------------------------------------------
 std::string toDecimal(const uint8_t le[32]) {
     uint32_t w[8];

@@ -81,6 +81,27 @@ void countR1csTerms(const BinFile& f, const R1csHeader& h, uint64_t terms[3]);
 void loadR1cs(const BinFile& f, R1cs& out);
 extern const uint8_t BN254_R_BYTES[32];      // the scalar modulus r, little-endian
 
+// ---- .ptau (iden3 binfile, magic "ptau", version 1; the layout is restated in include/ultragroth_hip.h -- from memory of
+// snarkjs' format: no file of a real ceremony has been read yet) ----
+// Every failure is a C++ exception whose message starts with "ptau: ". Nothing here walks a section: a 2^28 file is hundreds of GB.
+struct PtauHeader {
+    uint32_t n8 = 0, power = 0, ceremonyPower = 0;
+    bool prepared = false;                    // sections 12 - 15 (the Lagrange forms) are all there
+};
+PtauHeader loadPtauHeader(const BinFile& f);
+// what a phase-2 setup of domain 2^logN reads: level logN of sections 12 (tauG1), 13 (tauG2), 14 (alphaTauG1), 15 (betaTauG1),
+// level logN + 1 of section 12, record 0 of sections 4 and 5, section 6. first12 / firstTop: the index of a slice's first record
+// in its section. Every size is checked (compared before it is added or multiplied) before a pointer is formed.
+struct PtauSlices {
+    uint64_t n = 0;                           // 2^logN
+    const uint8_t *tau1 = nullptr, *tau2 = nullptr, *alphaTau1 = nullptr, *betaTau1 = nullptr;      // n records each
+    const uint8_t* top = nullptr;             // 2 n records of section 12: level logN + 1
+    const uint8_t *alpha1 = nullptr, *beta1 = nullptr, *beta2 = nullptr;
+    uint64_t first = 0, firstTop = 0;         // n - 1 and 2 n - 1
+};
+PtauSlices loadPtauSlices(const BinFile& f, const PtauHeader& h, uint32_t logN);
+extern const uint8_t BN254_Q_LE[32];          // the base modulus q, little-endian
+
 // 32-byte little-endian plain integer -> decimal string
 std::string toDecimal(const uint8_t le[32]);
 

@@ -12,33 +12,26 @@
 //                          additions from the tables, KPL results of a lane converted to affine with one shared inversion
 // This is a translation unit of its own: no kernel of the prover or the verifier is compiled differently because it exists.
 // Plain C++ and vector stores only. DESIGN.md section 5.8 has the registers, the column-split rule and the window choice.
-#include "dev_common.hpp"
+#include "setup_dev.hpp"
 #include "stream_timer.hpp"
 #include "setup_host.hpp"
 
 #include <chrono>
 #include <memory>
-#include <type_traits>
 
 namespace ug {
+
+// setup_points.hip
+void device_points_combine(hipStream_t stream, StreamTimer& timer, bool g2, u64 nCols, const u32* colPtr, const u32* index,
+                           const uint8_t* coefs, const ughost::setup::PointSegs& pts, uint8_t* out, double* ms);
+void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms);
+
 namespace {
 
 using ughost::setup::Piece;
 using ughost::setup::SPLIT_PIECE;
 using ughost::setup::SPLIT_THRESHOLD;
-
-inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
-
-// compile-time loops: every index is a constant, so per-lane arrays stay in registers (a `#pragma unroll` the optimizer
-// declines leaves them indexed at run time, i.e. in scratch)
-template <int I, int N> struct Static {
-    template <class Fn> static __device__ __forceinline__ void up(Fn&& f) { f(std::integral_constant<int, I>()); Static<I + 1, N>::up(f); }
-    template <class Fn> static __device__ __forceinline__ void down(Fn&& f) { Static<I + 1, N>::down(f); f(std::integral_constant<int, I>()); }
-};
-template <int N> struct Static<N, N> {
-    template <class Fn> static __device__ __forceinline__ void up(Fn&&) {}
-    template <class Fn> static __device__ __forceinline__ void down(Fn&&) {}
-};
+using namespace sdev;
 
 struct FrWords { u32 w[8]; };                   // a canonical Fr value in device form, packed: kernel arguments by value
 __device__ __forceinline__ Fr fr_arg(const FrWords& a) { return unpack256<FrParams>(a.w); }
@@ -181,43 +174,6 @@ __global__ void h_scalars_kernel(u32* out, const u32* lag, u64 n, FrWords scale)
     store8(out + i * 8, w);
 }
 
-// ---- curve configurations of this file ----
-struct S1 {
-    typedef Fq F;
-    static constexpr int AFF_WORDS = 16, KPL = 2, BLOCK = 128;
-    static __device__ __forceinline__ void load(const u32* p, F& x, F& y) {
-        x = ld_packed<FqParams>(p); y = ld_packed<FqParams>(p + 8);
-    }
-    static __device__ __forceinline__ void store_packed(u32* o, const F& x, const F& y) { st_packed(o, x); st_packed(o + 8, y); }
-    static __device__ __forceinline__ void store_mont(u32* o, const F& x, const F& y) {
-        u32 w[8];
-        to_mont256(w, x); store8(o, w);
-        to_mont256(w, y); store8(o + 8, w);
-    }
-};
-struct S2 {
-    typedef Fq2 F;
-    static constexpr int AFF_WORDS = 32, KPL = 1, BLOCK = 64;
-    static __device__ __forceinline__ void load(const u32* p, F& x, F& y) {
-        x.a = ld_packed<FqParams>(p); x.b = ld_packed<FqParams>(p + 8); y.a = ld_packed<FqParams>(p + 16); y.b = ld_packed<FqParams>(p + 24);
-    }
-    static __device__ __forceinline__ void store_packed(u32* o, const F& x, const F& y) {
-        st_packed(o, x.a); st_packed(o + 8, x.b); st_packed(o + 16, y.a); st_packed(o + 24, y.b);
-    }
-    static __device__ __forceinline__ void store_mont(u32* o, const F& x, const F& y) {
-        u32 w[8];
-        to_mont256(w, x.a); store8(o, w);
-        to_mont256(w, x.b); store8(o + 8, w);
-        to_mont256(w, y.a); store8(o + 16, w);
-        to_mont256(w, y.b); store8(o + 24, w);
-    }
-};
-template <int WORDS> __device__ __forceinline__ void zero_record(u32* o) {
-    uint4* q = reinterpret_cast<uint4*>(o);
-#pragma unroll
-    for (int i = 0; i < WORDS / 4; i++) q[i] = make_uint4(0, 0, 0, 0);
-}
-
 // ---- window tables of a generator ----
 // table: tables * half records, affine, canonical device form; record (j, d - 1) = d * 2^(c j) * G, d = 1 .. half = 2^(c-1).
 // First the bases 2^(c j) * G, one lane per table (the walk of synth_points_kernel's table, on the device): c j doublings.
@@ -351,17 +307,6 @@ __global__ __launch_bounds__(Cfg::BLOCK) void gen_mul_kernel(const u32* scalars,
 }
 
 // ---- host side ----
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    explicit DevBuf(u64 n) { alloc(n); }
-    void alloc(u64 n) { release(); if (n) UG_HIP(hipMalloc((void**)&p, n * sizeof(T))); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    ~DevBuf() { release(); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
-
 FrWords words_of(const Fr& a) {
     FrWords w;
     pack256(w.w, a);
@@ -422,6 +367,15 @@ public:
         UG_HIP(hipStreamSynchronize(stream_));
         timer_.resolve();
         if (ms) { ms[0] = build.ms; ms[1] = mul.ms; }
+    }
+
+    // (the point combinations of the phase-2 setup: setup_points.hip, on this backend's stream and timer)
+    void combine(bool g2, u64 nCols, const u32* colPtr, const u32* index, const uint8_t* coefs, const PointSegs& pts, uint8_t* out,
+                 double* ms) override {
+        device_points_combine(stream_, timer_, g2, nCols, colPtr, index, coefs, pts, out, ms);
+    }
+    void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) override {
+        device_points_scale(stream_, timer_, scalar, points, n, out, ms);
     }
 
     void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>& pieces, uint8_t* a, uint8_t* b1, uint8_t* b2, uint8_t* k,

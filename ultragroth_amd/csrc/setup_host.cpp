@@ -20,11 +20,11 @@ using namespace ug;
 
 DeviceBackendFactory deviceBackendFactory = nullptr;
 
-namespace {
-
 double nowMs() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+namespace {
 
 unsigned threadCount(u64 n, u64 grain) {
     unsigned hw = std::thread::hardware_concurrency();
@@ -71,6 +71,65 @@ void frToPlain(uint8_t* le, const Fr& a) {
     memcpy(le, w, 32);
 }
 
+bool belowR(const uint8_t* le) {
+    for (int i = 31; i >= 0; i--) {
+        if (le[i] < BN254_R_BYTES[i]) return true;
+        if (le[i] > BN254_R_BYTES[i]) return false;
+    }
+    return false;
+}
+
+bool coefMagnitude(const uint8_t* le, u32 mag[8]) {
+    u32 c[8], d[8];
+    memcpy(c, le, 32);
+    // d = r - c; negate when d < c, i.e. c > r / 2 (r is odd: never equal)
+    int64_t borrow = 0;
+    for (int i = 0; i < 8; i++) {
+        const int64_t v = (int64_t)FrParams::q32[i] - (int64_t)c[i] + borrow;
+        d[i] = (u32)v;
+        borrow = v >> 32;
+    }
+    bool less = false;                          // d < c, decided by the highest differing word
+    for (int i = 0; i < 8; i++)
+        if (d[i] != c[i]) less = d[i] < c[i];
+    memcpy(mag, less ? d : c, 32);
+    return less;
+}
+
+int recodeWnaf(const uint8_t* le, int w, int8_t digit[256]) {
+    u32 k[9] = {0};
+    memcpy(k, le, 32);
+    memset(digit, 0, 256);
+    int top = -1;
+    const int full = 1 << w, half = full >> 1;
+    for (int i = 0; i < 256; i++) {
+        if (k[0] & 1) {
+            int d = (int)(k[0] & (u32)(full - 1));
+            if (d >= half) d -= full;
+            digit[i] = (int8_t)d;
+            top = i;
+            // k -= d
+            int64_t carry = -(int64_t)d;
+            for (int j = 0; j < 9 && carry; j++) {
+                const int64_t v = (int64_t)k[j] + carry;
+                k[j] = (u32)v;
+                carry = v >> 32;
+            }
+        }
+        for (int j = 0; j < 8; j++) k[j] = (k[j] >> 1) | (k[j + 1] << 31);
+        k[8] >>= 1;
+    }
+    return top;
+}
+
+void columnPieces(const u32* colPtr, u64 nCols, u32 m, std::vector<Piece>& pieces) {
+    for (u64 s = 0; s < nCols; s++) {
+        const u32 lo = colPtr[s], hi = colPtr[s + 1];
+        if (hi - lo <= SPLIT_THRESHOLD) continue;
+        for (u64 f = lo; f < hi; f += SPLIT_PIECE) pieces.push_back({m, (u32)s, (u32)f, (u32)std::min<u64>(hi, f + SPLIT_PIECE)});
+    }
+}
+
 namespace {
 
 Fr frSmall(u32 v) {
@@ -97,14 +156,6 @@ Fr rootOfUnity(int k) {
     return cond_sub_q(pow256(frSmall(FrParams::generator), e));
 }
 
-bool belowR(const uint8_t* le) {
-    for (int i = 31; i >= 0; i--) {
-        if (le[i] < BN254_R_BYTES[i]) return true;
-        if (le[i] > BN254_R_BYTES[i]) return false;
-    }
-    return false;
-}
-
 // ---- the generators, affine, canonical device form ----
 const u32 G2_WORDS[4][8] = {
     {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu},
@@ -126,6 +177,15 @@ template <> struct Gen<Fq> {
         to_mont256(w, x); to_mont256(w + 8, y);
         memcpy(o, w, 64);
     }
+    static bool load(const uint8_t* rec, Fq& x, Fq& y) {      // false: the all-zero record, infinity
+        u32 w[16];
+        memcpy(w, rec, 64);
+        u32 o = 0;
+        for (int i = 0; i < 16; i++) o |= w[i];
+        if (!o) return false;
+        x = cond_sub_q(from_mont256<FqParams>(w)); y = cond_sub_q(from_mont256<FqParams>(w + 8));
+        return true;
+    }
 };
 template <> struct Gen<Fq2> {
     static constexpr int REC = 128;
@@ -136,6 +196,16 @@ template <> struct Gen<Fq2> {
         u32 w[32];
         to_mont256(w, x.a); to_mont256(w + 8, x.b); to_mont256(w + 16, y.a); to_mont256(w + 24, y.b);
         memcpy(o, w, 128);
+    }
+    static bool load(const uint8_t* rec, Fq2& x, Fq2& y) {
+        u32 w[32];
+        memcpy(w, rec, 128);
+        u32 o = 0;
+        for (int i = 0; i < 32; i++) o |= w[i];
+        if (!o) return false;
+        x.a = cond_sub_q(from_mont256<FqParams>(w)); x.b = cond_sub_q(from_mont256<FqParams>(w + 8));
+        y.a = cond_sub_q(from_mont256<FqParams>(w + 16)); y.b = cond_sub_q(from_mont256<FqParams>(w + 24));
+        return true;
     }
 };
 
@@ -217,6 +287,55 @@ void checkScalars(const uint8_t* scalars, u64 n) {
         if (!belowR(scalars + i * 32)) throw SetupError("scalar " + std::to_string(i) + " is not below the field modulus");
 }
 
+// results of a piece of work -> zkey records, one shared inversion
+template <class F> void storeAffine(std::vector<XYZZ<F>>& acc, uint8_t* out) {
+    std::vector<F> ax, ay;
+    std::vector<char> live;
+    batchAffine(acc, ax, ay, live);
+    for (size_t i = 0; i < acc.size(); i++) {
+        if (live[i]) Gen<F>::store(out + i * Gen<F>::REC, ax[i], ay[i]);
+        else memset(out + i * Gen<F>::REC, 0, Gen<F>::REC);
+    }
+}
+
+// The per-column point combination, one column at a time (a long column stays with one thread, as in points() below). A unit
+// coefficient is a mixed addition; every other one goes through the host's 4-bit signed-window product of its magnitude.
+template <class F>
+void hostCombine(u64 nCols, const u32* colPtr, const u32* index, const uint8_t* coefs, const PointSegs& pts, uint8_t* out) {
+    constexpr int REC = Gen<F>::REC;
+    parallelFor(nCols, 64, [&](u64 lo, u64 hi) {
+        std::vector<XYZZ<F>> acc(hi - lo);
+        for (u64 s = lo; s < hi; s++) {
+            XYZZ<F> a = xyzz_inf<F>();
+            for (u32 q = colPtr[s]; q < colPtr[s + 1]; q++) {
+                u32 mag[8];
+                const bool negate = coefMagnitude(coefs + (size_t)q * 32, mag);
+                const int bits = bitLength(mag);
+                F x, y;
+                if (!bits || !Gen<F>::load(pts.base[index[q] / pts.count] + (index[q] % pts.count) * REC, x, y)) continue;
+                if (negate) y = canon(neg<1>(y));
+                if (bits == 1) a = xyzz_madd(a, x, y);
+                else a = xyzz_add(a, xyzz_mul_scalar_w4(xyzz_from_affine(x, y), mag));
+            }
+            acc[s - lo] = a;
+        }
+        storeAffine(acc, out + lo * REC);
+    });
+}
+
+void hostScale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out) {
+    u32 k[8];
+    memcpy(k, scalar, 32);
+    parallelFor(n, 64, [&](u64 lo, u64 hi) {
+        std::vector<XYZZ<Fq>> acc(hi - lo);
+        for (u64 i = lo; i < hi; i++) {
+            Fq x, y;
+            acc[i - lo] = Gen<Fq>::load(points + i * 64, x, y) ? xyzz_mul_scalar_w4(xyzz_from_affine(x, y), k) : xyzz_inf<Fq>();
+        }
+        storeAffine(acc, out + lo * 64);
+    });
+}
+
 // ---- the host-thread backend ----
 class HostBackend : public Backend {
 public:
@@ -249,6 +368,18 @@ public:
         if (g2) hostGeneratorMul<Fq2>(scalars, n, out);
         else hostGeneratorMul<Fq>(scalars, n, out);
         if (ms) { ms[0] = 0; ms[1] = nowMs() - t0; }
+    }
+    void combine(bool g2, u64 nCols, const u32* colPtr, const u32* index, const uint8_t* coefs, const PointSegs& pts, uint8_t* out,
+                 double* ms) override {
+        const double t0 = nowMs();
+        if (g2) hostCombine<Fq2>(nCols, colPtr, index, coefs, pts, out);
+        else hostCombine<Fq>(nCols, colPtr, index, coefs, pts, out);
+        if (ms) { ms[0] = 0; ms[1] = nowMs() - t0; }
+    }
+    void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) override {
+        const double t0 = nowMs();
+        hostScale(scalar, points, n, out);
+        if (ms) ms[0] = nowMs() - t0;
     }
     void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>&, uint8_t* a, uint8_t* b1, uint8_t* b2, uint8_t* k,
                 uint8_t* h, double ms[PHASES]) override {
@@ -291,7 +422,31 @@ public:
     }
 };
 
+}  // namespace
+
 // ---- options -> plan ----
+void planSizes(const R1csHeader& h, u32 logDomain, Plan& p) {
+    p.nVars = h.nWires; p.nConstraints = h.nConstraints;
+    const u64 nPublic = (u64)h.nPubOut + h.nPubIn;
+    if (nPublic + 1 > h.nWires) throw SetupError("nPubOut + nPubIn + 1 exceeds nWires");
+    p.nPublic = (u32)nPublic;
+    const u64 rows = (u64)h.nConstraints + nPublic + 1;
+    int need = 0;
+    while ((1ull << need) < rows) need++;
+    if (need > MAX_LOG_DOMAIN) throw SetupError("sizes that cannot be represented: " + std::to_string(rows) + " rows need a domain above 2^" + std::to_string(MAX_LOG_DOMAIN));
+    if (logDomain == 0) p.logN = std::max(need, 1);
+    else {
+        if (logDomain > (u32)MAX_LOG_DOMAIN) throw SetupError("log_domain " + std::to_string(logDomain) + " is above the prover's largest domain, 2^" + std::to_string(MAX_LOG_DOMAIN));
+        if ((int)logDomain < need) throw SetupError("log_domain " + std::to_string(logDomain) + " is too small for " + std::to_string(rows) + " rows");
+        p.logN = (int)logDomain;
+    }
+    p.N = 1u << p.logN;
+    p.cls.assign(p.nVars, 2);
+    for (u32 s = 0; s <= p.nPublic; s++) p.cls[s] = 0;
+}
+
+namespace {
+
 struct Named { const char* name; const uint8_t* v; bool nonzero; };
 
 void makePlan(const ug_setup_options* o, const R1csHeader& h, Plan& p) {
@@ -307,23 +462,7 @@ void makePlan(const ug_setup_options* o, const R1csHeader& h, Plan& p) {
         if (!belowR(n.v)) throw SetupError(std::string(n.name) + " is not below the field modulus");
         if (n.nonzero && frIsZero(frFromPlain(n.v))) throw SetupError(std::string(n.name) + " is 0 mod r");
     }
-    p.nVars = h.nWires; p.nConstraints = h.nConstraints;
-    const u64 nPublic = (u64)h.nPubOut + h.nPubIn;
-    if (nPublic + 1 > h.nWires) throw SetupError("nPubOut + nPubIn + 1 exceeds nWires");
-    p.nPublic = (u32)nPublic;
-    const u64 rows = (u64)h.nConstraints + nPublic + 1;
-    int need = 0;
-    while ((1ull << need) < rows) need++;
-    if (need > MAX_LOG_DOMAIN) throw SetupError("sizes that cannot be represented: " + std::to_string(rows) + " rows need a domain above 2^" + std::to_string(MAX_LOG_DOMAIN));
-    if (o->log_domain == 0) p.logN = std::max(need, 1);
-    else {
-        if (o->log_domain > (u32)MAX_LOG_DOMAIN) throw SetupError("log_domain " + std::to_string(o->log_domain) + " is above the prover's largest domain, 2^" + std::to_string(MAX_LOG_DOMAIN));
-        if ((int)o->log_domain < need) throw SetupError("log_domain " + std::to_string(o->log_domain) + " is too small for " + std::to_string(rows) + " rows");
-        p.logN = (int)o->log_domain;
-    }
-    p.N = 1u << p.logN;
-    p.cls.assign(p.nVars, 2);
-    for (u32 s = 0; s <= p.nPublic; s++) p.cls[s] = 0;
+    planSizes(h, o->log_domain, p);
     if (p.ultra) {
         if (o->rand_indx < 1 || o->rand_indx > p.nPublic) throw SetupError("rand_indx " + std::to_string(o->rand_indx) + " is not a public signal");
         p.randIndx = o->rand_indx;
@@ -360,6 +499,8 @@ void makePlan(const ug_setup_options* o, const R1csHeader& h, Plan& p) {
     p.hScale = frMul(frSub(tauN, one), frInv(minus2d));
 }
 
+}  // namespace
+
 // ---- the column index: a counting sort of each matrix's terms by wire, rows ascending inside a column ----
 void buildColumns(const R1cs& cs, const Plan& p, ColMatrix cm[3], std::vector<Piece>& pieces) {
     uint8_t oneLe[32] = {1};
@@ -386,13 +527,11 @@ void buildColumns(const R1cs& cs, const Plan& p, ColMatrix cm[3], std::vector<Pi
             c.row[pos] = p.nConstraints + (u32)s;
             memcpy(&c.val[(size_t)pos * 32], oneLe, 32);
         }
-        for (u32 s = 0; s < p.nVars; s++) {
-            const u32 lo = c.colPtr[s], hi = c.colPtr[s + 1];
-            if (hi - lo <= SPLIT_THRESHOLD) continue;
-            for (u32 f = lo; f < hi; f += SPLIT_PIECE) pieces.push_back({(u32)m, s, f, std::min(hi, f + SPLIT_PIECE)});
-        }
+        columnPieces(c.colPtr.data(), p.nVars, (u32)m, pieces);
     }
 }
+
+namespace {
 
 // ---- section 4: one record per (matrix, row, wire), row first, A before B, wire ascending; repeated wires added, sums of 0 left out ----
 struct CoefTerm { u32 wire; Fr v; };
@@ -413,6 +552,7 @@ void mergedRow(const R1csMatrix& m, u32 k, std::vector<CoefTerm>& out) {
 }
 // per piece of 4096 rows: the records of the constraint rows (the public rows add nPublic + 1 at the end)
 constexpr u64 COEF_GRAIN = 4096;
+}  // namespace
 void countCoefs(const R1cs& cs, std::vector<u64>& perPiece) {
     const u64 rows = cs.hdr.nConstraints;
     perPiece.assign((size_t)((rows + COEF_GRAIN - 1) / COEF_GRAIN), 0);
@@ -424,6 +564,7 @@ void countCoefs(const R1cs& cs, std::vector<u64>& perPiece) {
         perPiece[(size_t)(lo / COEF_GRAIN)] = n;
     });
 }
+namespace {
 void putCoef(uint8_t* o, u32 m, u32 row, u32 wire, const Fr& v) {
     memcpy(o, &m, 4); memcpy(o + 4, &row, 4); memcpy(o + 8, &wire, 4);
     // coef * 2^512 mod r as a plain integer: twice "to the reference's Montgomery form", the first result read as plain again
@@ -448,16 +589,14 @@ void fillCoefs(const R1cs& cs, const Plan& p, const std::vector<u64>& perPiece, 
     for (u32 s = 0; s <= p.nPublic; s++, o += 44) putCoef(o, 0, p.nConstraints + s, s, fp_one<FrParams>());
 }
 
+}  // namespace
+
 // ---- file layout ----
-struct Layout {
-    u64 nCoefs = 0, total = 0;
-    std::vector<std::pair<u32, u64>> sections;      // id, payload size, in file order
-    u64 offsetOf(u32 id) const {                    // of the payload
-        u64 at = 12;
-        for (auto& s : sections) { at += 12; if (s.first == id) return at; at += s.second; }
-        throw SetupError("internal: no section " + std::to_string(id));
-    }
-};
+u64 Layout::offsetOf(u32 id) const {
+    u64 at = 12;
+    for (auto& s : sections) { at += 12; if (s.first == id) return at; at += s.second; }
+    throw SetupError("internal: no section " + std::to_string(id));
+}
 Layout makeLayout(const Plan& p, u64 nCoefs) {
     if (nCoefs > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 records in section 4");
     Layout l;
@@ -475,6 +614,8 @@ Layout makeLayout(const Plan& p, u64 nCoefs) {
     for (auto& s : l.sections) l.total += 12 + s.second;
     return l;
 }
+
+namespace {
 
 const uint8_t BN254_Q_BYTES[32] = {
     0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
@@ -501,8 +642,6 @@ std::string jsonG2(const uint8_t* rec) {
     return "[[\"" + fqDecimal(rec) + "\", \"" + fqDecimal(rec + 32) + "\"], [\"" + fqDecimal(rec + 64) + "\", \"" + fqDecimal(rec + 96) +
            "\"], [\"1\", \"0\"]]";
 }
-struct HeaderPoints { uint8_t g1[4][64], g2[4][128]; };        // alpha, beta, round delta, final delta | beta, gamma, round delta, final delta
-
 std::string vkeyJson(const Plan& p, const HeaderPoints& hp, const uint8_t* ic) {
     std::string s = "{\n";
     s += std::string(" \"protocol\": \"") + (p.ultra ? "ultragroth" : "groth16") + "\",\n \"curve\": \"bn128\",\n";
@@ -521,6 +660,15 @@ std::string vkeyJson(const Plan& p, const HeaderPoints& hp, const uint8_t* ic) {
     if (p.ultra) s += ",\n \"IC_rand\": " + jsonG1(ic + (size_t)p.randIndx * 64);
     return s + "\n}\n";
 }
+
+
+// every message of this interface starts with "setup: ", or with "r1cs: " when the loader wrote it
+std::string prefixed(const std::string& m) {
+    return m.rfind("setup: ", 0) == 0 || m.rfind("r1cs: ", 0) == 0 ? m : "setup: " + m;
+}
+
+}  // namespace
+
 // an upper bound of the JSON's length: 78 characters per coordinate leave room for any value below 2^256 and the punctuation
 u64 vkeyBound(const Plan& p) { return 512 + 84ull * (2 + 4 * 4 + 2 * ((u64)p.nPublic + 2)) + 16ull * (p.nPublic + 8); }
 
@@ -528,11 +676,6 @@ void copyErr(char* dst, unsigned long long max, const char* msg) {
     if (!dst || !max) return;
     strncpy(dst, msg, max);
     dst[max - 1] = 0;
-}
-
-// every message of this interface starts with "setup: ", or with "r1cs: " when the loader wrote it
-std::string prefixed(const std::string& m) {
-    return m.rfind("setup: ", 0) == 0 || m.rfind("r1cs: ", 0) == 0 ? m : "setup: " + m;
 }
 
 Backend& backendFor(int device, std::unique_ptr<Backend>& owned) {
@@ -548,7 +691,40 @@ void loadCircuit(const void* r1cs, u64 size, std::unique_ptr<BinFile>& f, R1csHe
     h = loadR1csHeader(*f);
 }
 
-}  // namespace
+void writeContainer(uint8_t* zkey, const Layout& lay) {
+    uint8_t* o = zkey;
+    putBytes(o, "zkey", 4); put32(o, 1); put32(o, (u32)lay.sections.size());
+    for (auto& s : lay.sections) { put32(o, s.first); put64(o, s.second); o += s.second; }
+}
+
+void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vector<u64>& perPiece, const HeaderPoints& hp,
+               const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey) {
+    const u64 M = p.nVars, pub = (u64)p.nPublic + 1;
+    uint8_t* o = zkey + lay.offsetOf(1);
+    put32(o, p.ultra ? 1337 : 1);
+    o = zkey + lay.offsetOf(2);
+    put32(o, 32); putBytes(o, BN254_Q_BYTES, 32); put32(o, 32); putBytes(o, BN254_R_BYTES, 32);
+    put32(o, p.nVars); put32(o, p.nPublic); put32(o, p.N);
+    if (p.ultra) { put32(o, (u32)p.roundSignals.size()); put32(o, (u32)p.finalSignals.size()); put32(o, p.randIndx); }
+    putBytes(o, hp.g1[0], 64); putBytes(o, hp.g1[1], 64); putBytes(o, hp.g2[0], 128); putBytes(o, hp.g2[1], 128);
+    if (p.ultra) { putBytes(o, hp.g1[2], 64); putBytes(o, hp.g2[2], 128); }
+    putBytes(o, hp.g1[3], 64); putBytes(o, hp.g2[3], 128);
+    memcpy(zkey + lay.offsetOf(3), krec.data(), pub * 64);
+    o = zkey + lay.offsetOf(4);
+    put32(o, (u32)lay.nCoefs);
+    fillCoefs(cs, p, perPiece, o);
+    if (p.ultra) {
+        uint8_t* c1 = zkey + lay.offsetOf(8);
+        uint8_t* c2 = zkey + lay.offsetOf(9);
+        for (size_t i = 0; i < p.roundSignals.size(); i++) memcpy(c1 + i * 64, &krec[(size_t)p.roundSignals[i] * 64], 64);
+        for (size_t i = 0; i < p.finalSignals.size(); i++) memcpy(c2 + i * 64, &krec[(size_t)p.finalSignals[i] * 64], 64);
+        if (!p.roundSignals.empty()) memcpy(zkey + lay.offsetOf(10), p.roundSignals.data(), 4 * p.roundSignals.size());
+        if (!p.finalSignals.empty()) memcpy(zkey + lay.offsetOf(11), p.finalSignals.data(), 4 * p.finalSignals.size());
+    } else if (M > pub) {
+        memcpy(zkey + lay.offsetOf(8), &krec[pub * 64], (M - pub) * 64);
+    }
+    if (vkey) *vkey = vkeyJson(p, hp, krec.data());
+}
 
 Backend& hostBackend() {
     static HostBackend b;
@@ -595,11 +771,8 @@ u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uin
     buildColumns(cs, p, cm, pieces);
     ms[0] += nowMs() - t;
 
-    // container and section headers
-    uint8_t* o = zkey;
-    putBytes(o, "zkey", 4); put32(o, 1); put32(o, (u32)lay.sections.size());
-    for (auto& s : lay.sections) { put32(o, s.first); put64(o, s.second); o += s.second; }
-    const u64 M = p.nVars, pub = (u64)p.nPublic + 1;
+    writeContainer(zkey, lay);
+    const u64 M = p.nVars;
     std::vector<uint8_t> krec(M * 64);
     be.points(p, cm, pieces, zkey + lay.offsetOf(5), zkey + lay.offsetOf(6), zkey + lay.offsetOf(7), krec.data(),
               zkey + lay.offsetOf(p.ultra ? 12 : 9), ms);
@@ -614,30 +787,7 @@ u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uin
         memcpy(sc[0], p.opt.beta, 32); memcpy(sc[1], p.opt.gamma, 32);
         hostBackend().generatorMul(true, sc[0], 4, 0, hp.g2[0], nullptr);
     }
-    o = zkey + lay.offsetOf(1);
-    put32(o, p.ultra ? 1337 : 1);
-    o = zkey + lay.offsetOf(2);
-    put32(o, 32); putBytes(o, BN254_Q_BYTES, 32); put32(o, 32); putBytes(o, BN254_R_BYTES, 32);
-    put32(o, p.nVars); put32(o, p.nPublic); put32(o, p.N);
-    if (p.ultra) { put32(o, (u32)p.roundSignals.size()); put32(o, (u32)p.finalSignals.size()); put32(o, p.randIndx); }
-    putBytes(o, hp.g1[0], 64); putBytes(o, hp.g1[1], 64); putBytes(o, hp.g2[0], 128); putBytes(o, hp.g2[1], 128);
-    if (p.ultra) { putBytes(o, hp.g1[2], 64); putBytes(o, hp.g2[2], 128); }
-    putBytes(o, hp.g1[3], 64); putBytes(o, hp.g2[3], 128);
-    memcpy(zkey + lay.offsetOf(3), krec.data(), pub * 64);
-    o = zkey + lay.offsetOf(4);
-    put32(o, (u32)nCoefs);
-    fillCoefs(cs, p, perPiece, o);
-    if (p.ultra) {
-        uint8_t* c1 = zkey + lay.offsetOf(8);
-        uint8_t* c2 = zkey + lay.offsetOf(9);
-        for (size_t i = 0; i < p.roundSignals.size(); i++) memcpy(c1 + i * 64, &krec[(size_t)p.roundSignals[i] * 64], 64);
-        for (size_t i = 0; i < p.finalSignals.size(); i++) memcpy(c2 + i * 64, &krec[(size_t)p.finalSignals[i] * 64], 64);
-        if (!p.roundSignals.empty()) memcpy(zkey + lay.offsetOf(10), p.roundSignals.data(), 4 * p.roundSignals.size());
-        if (!p.finalSignals.empty()) memcpy(zkey + lay.offsetOf(11), p.finalSignals.data(), 4 * p.finalSignals.size());
-    } else if (M > pub) {
-        memcpy(zkey + lay.offsetOf(8), &krec[pub * 64], (M - pub) * 64);
-    }
-    if (vkey) *vkey = vkeyJson(p, hp, krec.data());
+    finishKey(cs, p, lay, perPiece, hp, krec, zkey, vkey);
     ms[5] += nowMs() - t;
     return lay.total;
 }

@@ -7,9 +7,14 @@
 // has), the device backend of setup.hip runs them as kernels. Both compute the same residues, and every record is canonical,
 // so the two give the same bytes.
 // Every failure is a C++ exception whose message starts with "setup: " (or with "r1cs: ", from the loader).
+//
+// The phase-2 setup from a prepared powers-of-tau file (setup_ptau.cpp: ug_setup_ptau_*) shares all of this. It has no scalars
+// to multiply the generator by: its two heavy steps combine POINTS per wire and multiply many points by one scalar, and sit
+// behind the same Backend (combine, scale). The parts of run() it needs are declared at the end of this header.
 #pragma once
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -60,6 +65,14 @@ struct Plan {
     Fr omega, alpha, beta, inv[3], hScale;      // inv: 1 / gamma, 1 / delta_round, 1 / delta_final; hScale: (tau^N - 1) / (-2 delta_final)
 };
 
+// the point arrays a combination indexes: `n` segments of `count` zkey-format records each, point (seg, k) has index seg * count + k
+struct PointSegs {
+    const uint8_t* base[3] = {nullptr, nullptr, nullptr};
+    u64 count = 0;
+    int n = 0;
+    u64 total() const { return count * (u64)n; }
+};
+
 // phase times in ms: parse + index (+ upload), Lagrange, transposed products, G1 multiplications, G2 multiplications,
 // download + assembly
 constexpr int PHASES = 6;
@@ -75,6 +88,14 @@ public:
     // the point sections: a, b1, k (64 nVars bytes each), b2 (128 nVars), h (64 N). k[s] = (K_s / the divisor of cls[s]) * G1.
     virtual void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>& pieces, uint8_t* a, uint8_t* b1, uint8_t* b2,
                         uint8_t* k, uint8_t* h, double ms[PHASES]) = 0;
+    // out[c] = sum over the terms [colPtr[c], colPtr[c + 1]) of coef * point[index], a zkey-format affine record (64 bytes for G1,
+    // 128 for G2); coefs plain, below r; points zkey-format records that passed the point check, all-zero = infinity. An empty
+    // column and a sum that is the neutral element give the all-zero record. ms (may be null): two values, the per-term
+    // products and the per-column sums (host threads: 0 and the whole)
+    virtual void combine(bool g2, u64 nCols, const u32* colPtr, const u32* index, const uint8_t* coefs, const PointSegs& pts, uint8_t* out,
+                         double* ms) = 0;
+    // out[i] = scalar * point[i] over n G1 records; scalar plain, below r; infinity in gives infinity out. ms (may be null): one value
+    virtual void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) = 0;
 };
 Backend& hostBackend();
 // the generator of G1 (16 words) or G2 (32 words): affine, canonical device form, packed
@@ -91,6 +112,44 @@ inline Fr frAdd(const Fr& a, const Fr& b) { return ug::cond_sub_q(ug::norm_stric
 inline Fr frSub(const Fr& a, const Fr& b) { return ug::cond_sub_q(ug::norm_strict(ug::sub<1>(a, b))); }
 
 void parallelFor(u64 n, u64 grain, const std::function<void(u64, u64)>& fn);
+
+// ---- what a point combination's two backends share ----
+// A coefficient above r / 2 is taken as the negated point times r - coef: mag = min(coef, r - coef) as 8 plain words, the return
+// value says whether the point is negated. coef plain, below r.
+bool coefMagnitude(const uint8_t* le, u32 mag[8]);
+inline int bitLength(const u32 w[8]) {
+    for (int i = 7; i >= 0; i--)
+        if (w[i]) return 32 * i + 32 - __builtin_clz(w[i]);
+    return 0;
+}
+// the pieces of every column of colPtr with more than SPLIT_THRESHOLD terms, appended (the split rule of buildColumns)
+void columnPieces(const u32* colPtr, u64 nCols, u32 m, std::vector<Piece>& pieces);
+// width-w non-adjacent form of a scalar below 2^255: digit[i] is 0 or odd with |digit[i]| < 2^(w-1), scalar = sum digit[i] 2^i.
+// Returns the index of the top non-zero digit, -1 for the scalar 0.
+constexpr int SCALE_WINDOW = 4;                // the device's width: odd multiples 1, 3, 5, 7 in registers
+int recodeWnaf(const uint8_t* le, int w, int8_t digit[256]);
+
+// ---- the parts of a key that do not depend on where its points come from (setup_host.cpp), for setup_ptau.cpp ----
+bool belowR(const uint8_t* le);
+void planSizes(const R1csHeader& h, u32 logDomain, Plan& p);       // nVars .. N and cls (all wires of protocol 1) from the header
+void loadCircuit(const void* r1cs, u64 size, std::unique_ptr<BinFile>& f, R1csHeader& h);
+void buildColumns(const R1cs& cs, const Plan& p, ColMatrix cm[3], std::vector<Piece>& pieces);
+void countCoefs(const R1cs& cs, std::vector<u64>& perPiece);
+struct Layout {
+    u64 nCoefs = 0, total = 0;
+    std::vector<std::pair<u32, u64>> sections;      // id, payload size, in file order
+    u64 offsetOf(u32 id) const;                     // of the payload
+};
+Layout makeLayout(const Plan& p, u64 nCoefs);
+u64 vkeyBound(const Plan& p);
+struct HeaderPoints { uint8_t g1[4][64], g2[4][128]; };        // alpha, beta, round delta, final delta | beta, gamma, round delta, final delta
+void writeContainer(uint8_t* zkey, const Layout& lay);            // magic, version, the section headers
+// sections 1 - 4 and the C sections from krec (one K record per wire), and the verification key's JSON
+void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vector<u64>& perPiece, const HeaderPoints& hp,
+               const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey);
+Backend& backendFor(int device, std::unique_ptr<Backend>& owned);
+void copyErr(char* dst, unsigned long long max, const char* msg);
+double nowMs();
 
 }  // namespace setup
 }  // namespace ughost

@@ -380,3 +380,32 @@ def r1cs_file(n_wires, n_pub_out, n_pub_in, rows, n_prv_in=None, n_labels=None, 
             3: b"".join(struct.pack("<Q", i) for i in range(n_wires))}
     secs = [(i, body[i]) for i in section_order] + list(extra_sections)
     return b"r1cs" + struct.pack("<II", 1, len(secs)) + b"".join(_section(i, p) for i, p in secs)
+
+
+def ptau_file(power, tau, alpha, beta, prepared=True, device=-1):
+    """A powers-of-tau file in the layout of include/ultragroth_hip.h ("PHASE-2 SETUP FROM A PREPARED POWERS-OF-TAU FILE") for a
+    KNOWN (tau, alpha, beta): test tooling, the writer that goes with the reader. Sections 2 - 6 hold the powers, section 7 is
+    empty; prepared adds sections 12 - 15, the Lagrange forms of every level 0 .. power and, in section 12 alone, the padded level
+    power + 1: [L_j(tau) - c_j tau^(2^(power+1) - 1)] G1 with c_j = omega^j / 2^(power+1), the leading coefficient of L_j.
+    Every point is made with generator_mul, every Lagrange value with lagrange_at (device = -1: host threads)."""
+    from . import generator_mul, lagrange_at
+    n = 1 << power
+    g1 = lambda scalars: b"".join(generator_mul([s % R_MOD for s in scalars], g2=False, device=device))
+    g2 = lambda scalars: b"".join(generator_mul([s % R_MOD for s in scalars], g2=True, device=device))
+    powers = [1]
+    for _ in range(2 * n - 2):
+        powers.append(powers[-1] * tau % R_MOD)
+    secs = [(1, struct.pack("<I", 32) + Q_MOD.to_bytes(32, "little") + struct.pack("<II", power, power)),
+            (2, g1(powers)), (3, g2(powers[:n])), (4, g1([alpha * t for t in powers[:n]])), (5, g1([beta * t for t in powers[:n]])),
+            (6, g2([beta])), (7, struct.pack("<I", 0))]
+    if prepared:
+        levels = [[1]] + [lagrange_at(tau, p, device=device) for p in range(1, power + 1)]
+        flat = [v for level in levels for v in level]
+        top_n = 2 * n
+        omega, c, missing = pow(5, (R_MOD - 1) // top_n, R_MOD), pow(top_n, -1, R_MOD), pow(tau, top_n - 1, R_MOD)
+        top = []
+        for v in lagrange_at(tau, power + 1, device=device):
+            top.append((v - c * missing) % R_MOD)
+            c = c * omega % R_MOD
+        secs += [(12, g1(flat + top)), (13, g2(flat)), (14, g1([alpha * v for v in flat])), (15, g1([beta * v for v in flat]))]
+    return b"ptau" + struct.pack("<II", 1, len(secs)) + b"".join(_section(i, p) for i, p in secs)
