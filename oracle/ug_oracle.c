@@ -272,10 +272,15 @@ static void power_table(fe *t, const fe *w, size_t count) {
 /* In-place radix-2 transform, natural order in and out.
  * inverse = 0:  X[k] = sum_j x[j] w^(jk),  w = omega_n
  * inverse = 1:  x[j] = n^-1 sum_k X[k] w^(-jk)      (reference: fft->fft / fft->ifft,
- *               src/groth16.cpp:112,120) */
+ *               src/groth16.cpp:112,120)
+ * Any 256-bit word is accepted, as ug_fr_ntt accepts it: words >= r are reduced first (2^256 < 6 r), since fe_add and
+ * fe_sub take canonical operands. The output is canonical. */
 void ugo_fr_ntt(uint64_t *data, int logn, int inverse) {
     size_t n = (size_t)1 << logn;
     fe *x = (fe *)data;
+#pragma omp parallel for schedule(static) if (n >= 4096)
+    for (size_t i = 0; i < n; i++)
+        while (fe_geq_q(x[i].v, &UGO_FR)) limbs_sub(x[i].v, x[i].v, UGO_FR.q);
     fe w; ugo_fr_root_of_unity(w.v, logn);
     if (inverse) fe_inv(&w, &w, &UGO_FR);
     /* twiddles w^0 .. w^(n/2-1) */

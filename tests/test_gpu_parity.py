@@ -37,6 +37,30 @@ def test_field_ops_bit_exact(device, field, mod):
         for i in range(n):
             exp = O.f_op(name, field, a[i], b[i])
             assert O.from_le(got[32 * i:32 * i + 32]) == exp, (name, i)
+    got = device.field_op(field, ug.OP_SQR, ab, bb)                 # (the square of a: b is not read)
+    for i in range(n):
+        assert O.from_le(got[32 * i:32 * i + 32]) == O.f_op("mul", field, a[i], a[i]), ("sqr", i)
+
+
+@pytest.mark.parametrize("field,mod", [(O.FR, O.R_MOD), (O.FQ, O.Q_MOD)])
+def test_field_ops_edge_grid_and_unreduced_operands(device, field, mod):
+    """every pair of the edge values -- (r-1)(r-1), (r-1) + (r-1), 0 - (r-1), the two halves of the field -- and operands in
+    [mod, 2^256), which ug_field_op reduces, for all four operations; expected values from Python integers: the stored words are
+    Montgomery values, so the product of the words a, b is a b / 2^256 and sums and differences are those of the words"""
+    import ultragroth_amd as ug
+    edge = [0, 1, 2, mod - 1, mod - 2, (1 << 256) % mod, (1 << 255) % mod, mod // 2, mod // 2 + 1]
+    above = [mod, mod + 1, 2 * mod - 1, 2 * mod, 3 * mod + 7, 4 * mod + mod // 2, 5 * mod, 5 * mod + mod // 4, 1 << 255, (1 << 256) - 1]
+    assert all(mod <= v < 1 << 256 for v in above)
+    vals = edge + above
+    pairs = [(x, y) for x in vals for y in vals]
+    ab = b"".join(O.to_le(x) for x, _ in pairs)
+    bb = b"".join(O.to_le(y) for _, y in pairs)
+    rinv = pow(1 << 256, -1, mod)
+    ops = ((ug.OP_MUL, lambda x, y: x * y * rinv % mod), (ug.OP_ADD, lambda x, y: (x + y) % mod),
+           (ug.OP_SUB, lambda x, y: (x - y) % mod), (ug.OP_SQR, lambda x, y: x * x * rinv % mod))
+    for op, f in ops:
+        got = device.field_op(field, op, ab, bb)
+        assert [O.from_le(got[32 * i:32 * i + 32]) for i in range(len(pairs))] == [f(x, y) for x, y in pairs], op
 
 
 @pytest.mark.parametrize("logn", [0, 1, 2, 5, 10, 11, 12, 14, 17])
