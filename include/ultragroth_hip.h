@@ -609,6 +609,50 @@ int  ug_points_combine(int device, int g2, const uint32_t* col_ptr, uint64_t n_c
 int  ug_points_scale(int device, const void* scalar, const void* points, uint64_t n, void* out, double* kernel_ms, char* error_msg,
                      unsigned long long error_msg_maxsize);
 
+/* PREPARING A POWERS-OF-TAU FILE FOR PHASE 2: sections 2 - 5 -> sections 12 - 15 (ptau_prepare.cpp, ptau_prepare.hip; what
+ * `snarkjs powersoftau prepare phase2` does), and the check that a file's sections 12 - 15 ARE the Lagrange forms of its sections
+ * 2 - 5, which ug_setup_ptau_run takes on trust. The layout is the one restated above, AS REMEMBERED of snarkjs' format: NO FILE OF
+ * A REAL CEREMONY HAS BEEN READ YET, and that caveat carries over unchanged to the sections this writes.
+ * OUT OF SCOPE: contribution transcripts, beacons, verifying the ceremony's own contributions (section 7 is copied, not read).
+ *
+ * The transform. For a level p with N = 2^p, omega = 5^((r - 1) / N) and the points P_0 .. P_(N-1) = the first N records of a
+ * section:  out[k] = (1 / N) sum_j omega^(-j k) P_j,  which is the level's point k, [L_k^(2^p)(tau)] X, when P_j = [tau^j] X.
+ * Section 12's padded level power + 1 is the same transform of the 2^(power+1) - 1 records of section 2 with infinity as the last
+ * input. device >= 0: a decimation-in-time radix-2 transform, one launch per stage, every butterfly a full-length product of a
+ * point by a twiddle; sections 12, 14, 15 of a level share the launches. device = -1: host threads, the same bytes (affine records
+ * are canonical).
+ * Prepare (mode 0). The output is the input's sections other than 12 - 15, in the input's order, then 12, 13, 14, 15 in the layout
+ * above; sections 12 - 15 of the input are dropped and made again. power = p' below the file's own cuts the file first: sections
+ * 2 - 5 to their first 2^(p'+1) - 1, 2^p', 2^p', 2^p' records, the header's power to p' (ceremonyPower stays), every other section
+ * copied; the padded level of the cut file is made from the cut section 2 with infinity in the last place, as for any file.
+ * Check (mode 1). Nothing is written (out may be NULL). The call succeeds when all four sections equal the recomputed ones, and
+ * fails with "ptau: section <id> point <index>: does not match the powers" for the first mismatch, in section order, index
+ * counted in the section; "ptau: not prepared for phase 2" when the sections are absent. A check is of the file's own power.
+ * A call fails, the message prefixed "ptau: ", for: every header rule of ug_setup_ptau_run; a section 2 - 5 (in a check also
+ * 12 - 15) that is missing or shorter than its record count needs; "power <p'> is above the file's <p>"; a power of 28 (the
+ * padded level would be a transform of 2^29 points, and r - 1 has only 28 factors of 2: cut such a file); an output buffer that is
+ * too small -- all of these before the first device byte, and all of them by ug_ptau_prepare_size, which is host only; a level that
+ * does not fit the device's free memory, "ptau: level <p> needs <bytes> on the device", before the first kernel of that level.
+ * The records of sections 2 - 5 that are read go through the point check (ug_points_check) with ug_setup_ptau_run's message. */
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_ptau_prepare_options) */
+    uint32_t power;                     /* 0: the file's own; p' below the file's: the file is cut to p' first */
+    uint32_t validate;                  /* 0 | 1 | 2 as ug_setup_ptau_options.validate, over the records of sections 2 - 5 that are read */
+    uint32_t mode;                      /* 0 prepare: write a file; 1 check: recompute sections 12 - 15 and compare with the file's own */
+} ug_ptau_prepare_options;
+#define UG_PTAU_PREPARE_PHASES 5 /* parse + copied sections | point check | G1 levels (12, 14, 15) | G2 levels (13) | comparison (a check only:
+                                    the comparisons run after each level, their time is taken out of the levels' phases) */
+/* host only: every rule that needs no point; out_bytes: the size of the prepared file (0 for a check) */
+int  ug_ptau_prepare_size(const ug_ptau_prepare_options* opt, const void* ptau, uint64_t ptau_size, uint64_t* out_bytes, char* error_msg,
+                          unsigned long long error_msg_maxsize);
+/* phase_ms: UG_PTAU_PREPARE_PHASES doubles or NULL; the levels' times are wall times with their uploads and downloads */
+int  ug_ptau_prepare_run(const ug_ptau_prepare_options* opt, const void* ptau, uint64_t ptau_size, int device, void* out,
+                         uint64_t out_capacity, uint64_t* out_bytes, double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize);
+/* Test tooling: ONE transform of size 2^log_n (log_n <= 28) over n_given <= 2^log_n zkey-format records, the rest infinity; out:
+ * 2^log_n records (64 bytes for G1, 128 for G2). kernel_ms (may be NULL): two doubles, the 1 / N products and the stages. */
+int  ug_points_intt(int device, int g2, int log_n, const void* points, uint64_t n_given, void* out, double* kernel_ms, char* error_msg,
+                    unsigned long long error_msg_maxsize);
+
 /* In-place size-2^logn transform of a host buffer of Montgomery Fr elements, natural order in and out.
  * inverse != 0 also scales by 1/n. */
 int  ug_fr_ntt(ug_ctx* ctx, void* host_data, int logn, int inverse);

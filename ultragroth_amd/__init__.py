@@ -430,6 +430,92 @@ def points_scale(scalar, points, device=0, timing=None):
     return [out.raw[64 * i:64 * i + 64] for i in range(len(points))]
 
 
+PTAU_PREPARE_PHASES = ("parse", "point_check", "g1", "g2", "compare")
+
+
+class _PtauPrepareOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("power", C.c_uint32), ("validate", C.c_uint32), ("mode", C.c_uint32)]
+
+
+def _ptau_prepare_options(power, validate, mode):
+    opt = _PtauPrepareOptions()
+    opt.size = C.sizeof(_PtauPrepareOptions)
+    for name, value in (("power", power), ("validate", validate)):
+        if not 0 <= int(value) < 1 << 32:
+            raise SetupError("setup: %s %d cannot be represented" % (name, value))
+    opt.power, opt.validate, opt.mode = int(power), int(validate), mode
+    return opt
+
+
+def ptau_prepare(ptau, power=0, device=0, validate=1, timings=None):
+    """ug_ptau_prepare_run: the .ptau prepared for phase 2 (what `snarkjs powersoftau prepare phase2` does), as bytes: the input's
+    sections other than 12 - 15 in their order, then sections 12 - 15, the Lagrange forms of the powers of sections 2 - 5, made by
+    an inverse transform over the points. Sections 12 - 15 already there are dropped and made again.
+
+    ptau: bytes, a memoryview / mmap, or a path that is mapped here. power: 0 the file's own; a smaller one cuts the file to it
+    first (the header's power changes, ceremonyPower stays). validate: as setup_from_ptau, over the records of sections 2 - 5 that
+    are read. device=-1 runs on host threads and gives the same bytes. timings: a dict that receives the phase times in ms.
+    Transcripts, beacons and verifying the ceremony's own contributions are out of scope. Refusals raise SetupError ("ptau: ...")."""
+    L = load()
+    opt = _ptau_prepare_options(power, validate, 0)
+    m = _Mapped(ptau)
+    try:
+        size = C.c_uint64()
+        _setup_call(L.ug_ptau_prepare_size, C.byref(opt), m.address, m.length, C.byref(size))
+        out = C.create_string_buffer(max(1, size.value))
+        wrote = C.c_uint64()
+        ms = (C.c_double * len(PTAU_PREPARE_PHASES))()
+        _setup_call(L.ug_ptau_prepare_run, C.byref(opt), m.address, m.length, device, out, size.value, C.byref(wrote), ms)
+    finally:
+        m.close()
+    if timings is not None:
+        timings.update(zip(PTAU_PREPARE_PHASES, ms))
+    return out.raw[:wrote.value]
+
+
+def ptau_check(ptau, device=0, validate=1):
+    """ug_ptau_prepare_run in check mode: sections 12 - 15 of a prepared .ptau are made again from its sections 2 - 5 and compared
+    with the file's own, which setup_from_ptau takes on trust. None when all four agree; (section, index, message) for the first
+    record that differs, in section order, the index counted in the section. Every other refusal (an unprepared file among
+    them) raises SetupError."""
+    import re
+    L = load()
+    opt = _ptau_prepare_options(0, validate, 1)
+    m = _Mapped(ptau)
+    try:
+        _setup_call(L.ug_ptau_prepare_size, C.byref(opt), m.address, m.length, None)
+        try:
+            _setup_call(L.ug_ptau_prepare_run, C.byref(opt), m.address, m.length, device, None, 0, None, None)
+        except SetupError as e:
+            hit = re.fullmatch(r"ptau: section (\d+) point (\d+): does not match the powers", str(e))
+            if not hit:
+                raise
+            return int(hit.group(1)), int(hit.group(2)), str(e)
+    finally:
+        m.close()
+    return None
+
+
+def points_intt(points, log_n, g2=False, device=0, timing=None):
+    """ug_points_intt (test tooling): ONE inverse transform of size N = 2^log_n over points: out[k] = (1 / N) sum_j omega^(-j k)
+    points[j] with omega = 5^((r - 1) / N); points: at most N zkey-format records (64 bytes for G1, 128 for G2; all-zero is
+    infinity), the rest taken as infinity. Returns N records. device=-1: host threads. timing: a list that receives
+    (ms of the 1 / N products, ms of the stages)."""
+    rec = 128 if g2 else 64
+    pts = b"".join(points)
+    if len(pts) != rec * len(points):
+        raise SetupError("setup: a point record of another size")
+    if not 0 <= int(log_n) <= 28:
+        raise SetupError("setup: log_n %d is not in 0 .. 28" % log_n)
+    n = 1 << int(log_n)
+    out = C.create_string_buffer(rec * n)
+    ms = (C.c_double * 2)()
+    _setup_call(load().ug_points_intt, device, 1 if g2 else 0, int(log_n), pts, len(points), out, ms)
+    if timing is not None:
+        timing.append((ms[0], ms[1]))
+    return [out.raw[rec * i:rec * i + rec] for i in range(n)]
+
+
 # ---------------------------------------------------------------------------------------------------
 # verifier mirror (src/verifier.h)
 VERIFIER_VALID_PROOF, VERIFIER_INVALID_PROOF, VERIFIER_ERROR = 0, 1, 2

@@ -36,6 +36,7 @@ INNER_SYMBOLS = [
     "ug_r1cs_match_hpoly", "ug_r1cs_destroy",
     "ug_setup_draw_trapdoor", "ug_setup_size", "ug_setup_run", "ug_generator_mul", "ug_lagrange_at",
     "ug_ptau_parse_info", "ug_setup_ptau_size", "ug_setup_ptau_run", "ug_points_combine", "ug_points_scale",
+    "ug_ptau_prepare_size", "ug_ptau_prepare_run", "ug_points_intt",
     "ug_lookup_vectors_bytes", "ug_points_check", "ug_points_check_mask", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/verifier.h
@@ -245,6 +246,9 @@ def load():
     L.ug_setup_ptau_run.argtypes = [vp, vp, u64, vp, u64, C.c_int, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), C.POINTER(C.c_double), vp, ull]
     L.ug_points_combine.argtypes = [C.c_int, C.c_int, vp, u64, vp, vp, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_points_scale.argtypes = [C.c_int, vp, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
+    L.ug_ptau_prepare_size.argtypes = [vp, vp, u64, C.POINTER(u64), vp, ull]
+    L.ug_ptau_prepare_run.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(C.c_double), vp, ull]
+    L.ug_points_intt.argtypes = [C.c_int, C.c_int, C.c_int, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_fr_ntt.argtypes = [vp, vp, C.c_int, C.c_int]
     L.ug_field_op.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, u64]
     L.ug_synth_points.argtypes = [vp, C.c_int, vp, u64, u64, vp]

@@ -46,6 +46,7 @@ BinFile::BinFile(const void* data, uint64_t size, const std::string& type, uint3
                                    (sSize > UINT64_MAX - pos ? "beyond 2^64" : std::to_string(pos + sSize)) +
                                    " but should end before " + std::to_string(size) + ".");
         sections_[sType].push_back(Section{p + pos, sSize});
+        order_.emplace_back(sType, Section{p + pos, sSize});
         pos += sSize;
     }
 }
@@ -261,6 +262,30 @@ PtauSlices loadPtauSlices(const BinFile& f, const PtauHeader& h, uint32_t logN) 
     s.alpha1 = ptauRecords(f, 4, 1, 64);
     s.beta1 = ptauRecords(f, 5, 1, 64);
     s.beta2 = ptauRecords(f, 6, 1, 128);
+    return s;
+}
+
+PtauPowers loadPtauPowers(const BinFile& f, const PtauHeader& h, uint32_t power) {
+    if (power > h.power) throw PtauError("power " + std::to_string(power) + " is above the file's " + std::to_string(h.power));
+    // (power <= 28: no count below passes 2^29, no byte offset 2^36)
+    PtauPowers s;
+    s.power = power ? power : h.power;
+    s.n = 1ull << s.power;
+    s.tau1 = ptauRecords(f, 2, 2 * s.n - 1, 64);
+    s.tau2 = ptauRecords(f, 3, s.n, 128);
+    s.alphaTau1 = ptauRecords(f, 4, s.n, 64);
+    s.betaTau1 = ptauRecords(f, 5, s.n, 64);
+    return s;
+}
+
+PtauLagrange loadPtauLagrange(const BinFile& f, const PtauHeader& h) {
+    if (!h.prepared) throw PtauError("not prepared for phase 2 (sections 12 - 15, the Lagrange forms, are absent)");
+    const uint64_t n = 1ull << h.power;
+    PtauLagrange s;
+    s.sec[0] = ptauRecords(f, 12, 4 * n - 1, 64);
+    s.sec[1] = ptauRecords(f, 13, 2 * n - 1, 128);
+    s.sec[2] = ptauRecords(f, 14, 2 * n - 1, 64);
+    s.sec[3] = ptauRecords(f, 15, 2 * n - 1, 64);
     return s;
 }
 

@@ -26,9 +26,12 @@ public:
     const uint8_t* sectionData(uint32_t id, uint32_t pos = 0) const;
     uint64_t sectionSize(uint32_t id, uint32_t pos = 0) const;
     bool hasSection(uint32_t id) const { return sections_.count(id) != 0; }
+    // every section as the file has them, in its order: (id, payload)
+    const std::vector<std::pair<uint32_t, Section>>& inOrder() const { return order_; }
 private:
     const Section& find(uint32_t id, uint32_t pos) const;
     std::map<uint32_t, std::vector<Section>> sections_;
+    std::vector<std::pair<uint32_t, Section>> order_;
 };
 
 class FileMap {           // read-only mmap of a whole file
@@ -100,6 +103,21 @@ struct PtauSlices {
     uint64_t first = 0, firstTop = 0;         // n - 1 and 2 n - 1
 };
 PtauSlices loadPtauSlices(const BinFile& f, const PtauHeader& h, uint32_t logN);
+// what preparing the file for phase 2 at `power` reads (power = 0: the file's own; below the file's: the file cut to it): the
+// first 2^(power+1) - 1 records of section 2 (tauG1) and the first 2^power of sections 3 (tauG2), 4 (alphaTauG1), 5 (betaTauG1).
+// Counts are compared with the sections' own sizes before anything is multiplied.
+struct PtauPowers {
+    uint32_t power = 0;
+    uint64_t n = 0;                           // 2^power
+    const uint8_t *tau1 = nullptr, *tau2 = nullptr, *alphaTau1 = nullptr, *betaTau1 = nullptr;      // 2 n - 1, n, n, n records
+};
+PtauPowers loadPtauPowers(const BinFile& f, const PtauHeader& h, uint32_t power);
+// sections 12 - 15 whole, for a comparison with recomputed ones: 4 n - 1 records of section 12 (levels 0 .. power + 1), 2 n - 1 of
+// sections 13, 14, 15 (levels 0 .. power), n = 2^power of the header
+struct PtauLagrange {
+    const uint8_t* sec[4] = {nullptr, nullptr, nullptr, nullptr};      // 12, 13, 14, 15
+};
+PtauLagrange loadPtauLagrange(const BinFile& f, const PtauHeader& h);
 extern const uint8_t BN254_Q_LE[32];          // the base modulus q, little-endian
 
 // 32-byte little-endian plain integer -> decimal string

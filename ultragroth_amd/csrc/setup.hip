@@ -25,6 +25,9 @@ namespace ug {
 void device_points_combine(hipStream_t stream, StreamTimer& timer, bool g2, u64 nCols, const u32* colPtr, const u32* index,
                            const uint8_t* coefs, const ughost::setup::PointSegs& pts, uint8_t* out, double* ms);
 void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms);
+// ptau_prepare.hip
+void device_points_intt(hipStream_t stream, StreamTimer& timer, bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven,
+                        uint8_t* const* out, double* ms);
 
 namespace {
 
@@ -376,6 +379,10 @@ public:
     }
     void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) override {
         device_points_scale(stream_, timer_, scalar, points, n, out, ms);
+    }
+    // (the inverse transform over points that prepares a .ptau: ptau_prepare.hip)
+    void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) override {
+        device_points_intt(stream_, timer_, g2, logN, nVec, in, nGiven, out, ms);
     }
 
     void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>& pieces, uint8_t* a, uint8_t* b1, uint8_t* b2, uint8_t* k,

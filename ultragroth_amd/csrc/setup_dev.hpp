@@ -1,6 +1,6 @@
 // setup_dev.hpp -- what the two device translation units of the setups share (setup.hip: the development setup; setup_points.hip:
-// the point combinations of the phase-2 setup): compile-time loops, the curve configurations, the all-zero record, an owned
-// device buffer.
+// the point combinations of the phase-2 setup): compile-time loops, the curve configurations, the all-zero record, the per-lane
+// double-and-add walk (ptau_prepare.hip's butterflies use it too), an owned device buffer.
 #pragma once
 #include "dev_common.hpp"
 
@@ -57,6 +57,43 @@ template <int WORDS> __device__ __forceinline__ void zero_record(u32* o) {
     uint4* q = reinterpret_cast<uint4*>(o);
 #pragma unroll
     for (int i = 0; i < WORDS / 4; i++) q[i] = make_uint4(0, 0, 0, 0);
+}
+
+template <class F> __device__ __forceinline__ bool affine_is_inf(const F& x, const F& y) { return limbs_all_zero(x) && limbs_all_zero(y); }
+
+// ---- k * (x, y) by double-and-add, one lane ----
+// s: the 8 plain words of k, 1 <= k < 2^255 (destroyed); (x, y) affine, canonical, not infinity. The words are shifted up until the
+// top bit of k sits at bit 255, then one bit at a time: no register array is indexed by a run-time value. Every addition is a
+// mixed one of the affine base. For a base of order r and k < r the accumulator never meets the base or its negative.
+template <class F> __device__ __forceinline__ XYZZ<F> walk_product(u32 (&s)[8], const F& x, const F& y) {
+    int top = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        if (s[i]) top = 32 * i + 31 - __clz(s[i]);
+    const int wsh = 7 - (top >> 5), bsh = 31 - (top & 31);
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        if (k < wsh) {
+#pragma unroll
+            for (int i = 7; i > 0; i--) s[i] = s[i - 1];
+            s[0] = 0;
+        }
+    }
+    if (bsh) {
+#pragma unroll
+        for (int i = 7; i > 0; i--) s[i] = (s[i] << bsh) | (s[i - 1] >> (32 - bsh));
+        s[0] <<= bsh;
+    }
+    XYZZ<F> acc = xyzz_from_affine(x, y);        // the top bit
+#pragma unroll 1
+    for (int b = 0; b < top; b++) {
+#pragma unroll
+        for (int i = 7; i > 0; i--) s[i] = (s[i] << 1) | (s[i - 1] >> 31);
+        s[0] <<= 1;
+        acc = xyzz_dbl(acc);
+        if (s[7] >> 31) acc = xyzz_madd(acc, x, y);
+    }
+    return acc;
 }
 
 // ---- host side ----

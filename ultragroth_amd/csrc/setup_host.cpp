@@ -336,6 +336,73 @@ void hostScale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out
     });
 }
 
+// The inverse transform over points, the stages of ptau_prepare.hip on host threads: (1 / N) P_i to the bit-reversed index, then
+// one pass per stage over the butterflies, the records affine in `out` between the passes; a piece of butterflies shares one
+// inversion. The products go through the host's 4-bit signed-window form.
+template <class F> XYZZ<F> foldedProduct(const u32 folded[8], F x, F y) {
+    u32 mag[8];
+    memcpy(mag, folded, 32);
+    if (mag[7] >> 31) y = canon(neg<1>(y));
+    mag[7] &= 0x7fffffffu;
+    return xyzz_mul_scalar_w4(xyzz_from_affine(x, y), mag);
+}
+template <class F> void hostIntt(int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out) {
+    constexpr int REC = Gen<F>::REC;
+    const u64 N = 1ull << logN, half = N / 2;
+    std::vector<u32> tw;
+    inttTwiddles(logN, tw);
+    u32 c[8];
+    inttScale(logN, c);
+    for (int v = 0; v < nVec; v++) {
+        const uint8_t* src = in[v];
+        uint8_t* dst = out[v];
+        parallelFor(N, 64, [&](u64 lo, u64 hi) {
+            std::vector<XYZZ<F>> acc(hi - lo);
+            for (u64 i = lo; i < hi; i++) {
+                F x, y;
+                acc[i - lo] = i < nGiven && Gen<F>::load(src + i * REC, x, y) ? foldedProduct(c, x, y) : xyzz_inf<F>();
+            }
+            std::vector<F> ax, ay;
+            std::vector<char> live;
+            batchAffine(acc, ax, ay, live);
+            for (u64 i = lo; i < hi; i++) {
+                u64 j = 0;
+                for (int b = 0; b < logN; b++) j |= ((i >> b) & 1) << (logN - 1 - b);
+                if (live[i - lo]) Gen<F>::store(dst + j * REC, ax[i - lo], ay[i - lo]);
+                else memset(dst + j * REC, 0, REC);
+            }
+        });
+        for (int s = 0; s < logN; s++) {
+            parallelFor(half, 32, [&](u64 lo, u64 hi) {
+                std::vector<XYZZ<F>> res(2 * (hi - lo));
+                std::vector<uint8_t*> at(2 * (hi - lo));
+                for (u64 t = lo; t < hi; t++) {
+                    const u64 j = t & ((1ull << s) - 1);
+                    uint8_t* pa = dst + (((t >> s) << (s + 1)) + j) * REC;
+                    uint8_t* pb = pa + ((u64)REC << s);
+                    F ax, ay, bx, by;
+                    XYZZ<F> tv = xyzz_inf<F>();
+                    if (Gen<F>::load(pb, bx, by)) tv = j ? foldedProduct(&tw[(size_t)(j << (logN - 1 - s)) * 8], bx, by) : xyzz_from_affine(bx, by);
+                    XYZZ<F> sum = tv, dif = xyzz_neg(tv);
+                    if (Gen<F>::load(pa, ax, ay)) {
+                        sum = xyzz_madd(tv, ax, ay);
+                        dif = xyzz_neg(xyzz_madd(tv, ax, canon(neg<1>(ay))));       // a - t = -(t - a)
+                    }
+                    res[2 * (t - lo)] = sum; at[2 * (t - lo)] = pa;
+                    res[2 * (t - lo) + 1] = dif; at[2 * (t - lo) + 1] = pb;
+                }
+                std::vector<F> x, y;
+                std::vector<char> live;
+                batchAffine(res, x, y, live);
+                for (size_t i = 0; i < res.size(); i++) {
+                    if (live[i]) Gen<F>::store(at[i], x[i], y[i]);
+                    else memset(at[i], 0, REC);
+                }
+            });
+        }
+    }
+}
+
 // ---- the host-thread backend ----
 class HostBackend : public Backend {
 public:
@@ -380,6 +447,14 @@ public:
         const double t0 = nowMs();
         hostScale(scalar, points, n, out);
         if (ms) ms[0] = nowMs() - t0;
+    }
+    void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) override {
+        const double t0 = nowMs();
+        if (!inttTrivial(g2, logN, nVec, in, nGiven, out)) {
+            if (g2) hostIntt<Fq2>(logN, nVec, in, nGiven, out);
+            else hostIntt<Fq>(logN, nVec, in, nGiven, out);
+        }
+        if (ms) { ms[0] = 0; ms[1] = nowMs() - t0; }
     }
     void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>&, uint8_t* a, uint8_t* b1, uint8_t* b2, uint8_t* k,
                 uint8_t* h, double ms[PHASES]) override {
@@ -668,6 +743,42 @@ std::string prefixed(const std::string& m) {
 }
 
 }  // namespace
+
+void inttTwiddles(int logN, std::vector<u32>& tw) {
+    const u64 half = logN ? 1ull << (logN - 1) : 0;
+    tw.assign((size_t)half * 8, 0);
+    const Fr wi = frInv(rootOfUnity(logN));
+    parallelFor(half, 4096, [&](u64 lo, u64 hi) {
+        Fr w = fp_one<FrParams>(), b = wi;         // omega^(-lo) by square and multiply, then a running product
+        for (u64 e = lo; e; e >>= 1) { if (e & 1) w = frMul(w, b); b = frMul(b, b); }
+        for (u64 j = lo; j < hi; j++) {
+            uint8_t le[32];
+            u32 mag[8];
+            frToPlain(le, w);
+            if (coefMagnitude(le, mag)) mag[7] |= 0x80000000u;
+            memcpy(&tw[(size_t)j * 8], mag, 32);
+            w = frMul(w, wi);
+        }
+    });
+}
+
+void inttScale(int logN, u32 folded[8]) {       // N * (r - 1) / N = -1 mod r
+    for (int i = 0; i < 8; i++) folded[i] = FrParams::q32[i];
+    folded[0] -= 1;
+    for (int s = 0; s < logN; s++)
+        for (int i = 0; i < 8; i++) folded[i] = (folded[i] >> 1) | (i + 1 < 8 ? folded[i + 1] << 31 : 0u);
+    folded[7] |= 0x80000000u;
+}
+
+bool inttTrivial(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out) {
+    if (logN) return false;
+    const size_t rec = g2 ? 128 : 64;
+    for (int v = 0; v < nVec; v++) {
+        if (nGiven) memcpy(out[v], in[v], rec);
+        else memset(out[v], 0, rec);
+    }
+    return true;
+}
 
 // an upper bound of the JSON's length: 78 characters per coordinate leave room for any value below 2^256 and the punctuation
 u64 vkeyBound(const Plan& p) { return 512 + 84ull * (2 + 4 * 4 + 2 * ((u64)p.nPublic + 2)) + 16ull * (p.nPublic + 8); }

@@ -11,6 +11,7 @@
 // The phase-2 setup from a prepared powers-of-tau file (setup_ptau.cpp: ug_setup_ptau_*) shares all of this. It has no scalars
 // to multiply the generator by: its two heavy steps combine POINTS per wire and multiply many points by one scalar, and sit
 // behind the same Backend (combine, scale). The parts of run() it needs are declared at the end of this header.
+// Preparing a .ptau for phase 2 (ptau_prepare.cpp: ug_ptau_prepare_*) has one heavy step, an inverse transform over points: Backend::intt.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -96,6 +97,11 @@ public:
                          double* ms) = 0;
     // out[i] = scalar * point[i] over n G1 records; scalar plain, below r; infinity in gives infinity out. ms (may be null): one value
     virtual void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) = 0;
+    // The inverse transform over points that prepares a .ptau (ptau_prepare.cpp). N = 2^logN, omega = 5^((r - 1) / N):
+    // out[v][k] = (1 / N) sum_j omega^(-j k) in[v][j] for each of the nVec vectors; in[v]: nGiven <= N zkey-format records, the rest
+    // of the N taken as infinity; out[v]: N records, which do not overlap any input. ms (may be null): two values, the 1 / N
+    // products and the stages (host threads: 0 and the whole)
+    virtual void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) = 0;
 };
 Backend& hostBackend();
 // the generator of G1 (16 words) or G2 (32 words): affine, canonical device form, packed
@@ -128,6 +134,31 @@ void columnPieces(const u32* colPtr, u64 nCols, u32 m, std::vector<Piece>& piece
 // Returns the index of the top non-zero digit, -1 for the scalar 0.
 constexpr int SCALE_WINDOW = 4;                // the device's width: odd multiples 1, 3, 5, 7 in registers
 int recodeWnaf(const uint8_t* le, int w, int8_t digit[256]);
+
+// ---- what the inverse transform's two backends share ----
+// A folded scalar: 8 plain words of a magnitude below 2^255, bit 255 set when the point is negated (coefMagnitude's fold).
+// tw: the 2^(logN-1) twiddles omega^(-j), folded, 8 words each (stage s of the transform reads every 2^(logN-1-s)-th).
+void inttTwiddles(int logN, std::vector<u32>& tw);
+// 1 / 2^logN, folded: the negated point times (r - 1) / 2^logN
+void inttScale(int logN, u32 folded[8]);
+// a transform of one point (logN = 0) is the point itself: true when it was done here
+bool inttTrivial(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out);
+// the point check of a .ptau's records through ug_points_check (device >= 0) or on host threads, with the messages of
+// ug_setup_ptau_run: n records of section `id`; record i is the section's record first + stride * i. level 0 checks nothing.
+class PtauPointCheck {
+public:
+    PtauPointCheck(int device, int level);
+    ~PtauPointCheck();
+    void operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const;
+    PtauPointCheck(const PtauPointCheck&) = delete;
+    PtauPointCheck& operator=(const PtauPointCheck&) = delete;
+private:
+    int device_, level_;
+    ug_ctx* ctx_ = nullptr;
+};
+struct PtauError : public std::invalid_argument {
+    explicit PtauError(const std::string& m) : std::invalid_argument("ptau: " + m) {}
+};
 
 // ---- the parts of a key that do not depend on where its points come from (setup_host.cpp), for setup_ptau.cpp ----
 bool belowR(const uint8_t* le);

@@ -30,8 +30,6 @@ using namespace ughost::setup;
 struct P1 : S1 { static constexpr int PIECE_BLOCK = 256; };      // 36 limbs of an XYZZ point x 256 lanes: 36 KiB of LDS
 struct P2 : S2 { static constexpr int PIECE_BLOCK = 64; };       // 72 limbs x 64 lanes: 18 KiB
 
-template <class F> __device__ __forceinline__ bool affine_is_inf(const F& x, const F& y) { return limbs_all_zero(x) && limbs_all_zero(y); }
-
 // an XYZZ point in HBM: four packed coordinates, canonical (a packed value must be below 2^256; X may reach 7 q)
 template <class Cfg> __device__ __forceinline__ void ld_xyzz(const u32* p, XYZZ<typename Cfg::F>& r) {
     Cfg::load(p, r.x, r.y);
@@ -44,8 +42,7 @@ template <class Cfg> __device__ __forceinline__ void st_xyzz(u32* p, const XYZZ<
 
 // ---- per-term products ----
 // slot_coef: 8 words per slot, |coef| plain (2 <= |coef| <= (r - 1) / 2 < 2^253), bit 255 set when the base is negated.
-// The words are shifted up until the top bit of |coef| sits at bit 255, then one bit at a time: no register array is indexed
-// by a run-time value.
+// The bit walk itself is setup_dev.hpp's walk_product, which the butterflies of ptau_prepare.hip share.
 template <class Cfg>
 __global__ __launch_bounds__(Cfg::BLOCK) void term_products_kernel(const u32* __restrict__ pts, const u32* __restrict__ slot_index,
                                                                    const u32* __restrict__ slot_coef, u32 n, u32* __restrict__ prod) {
@@ -61,33 +58,7 @@ __global__ __launch_bounds__(Cfg::BLOCK) void term_products_kernel(const u32* __
     u32* o = prod + (size_t)t * 2 * Cfg::AFF_WORDS;
     if (affine_is_inf(x, y)) { zero_record<2 * Cfg::AFF_WORDS>(o); return; }
     if (negate) y = neg<1>(y);                   // q - y: y is canonical
-    int top = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (s[i]) top = 32 * i + 31 - __clz(s[i]);
-    const int wsh = 7 - (top >> 5), bsh = 31 - (top & 31);
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        if (k < wsh) {
-#pragma unroll
-            for (int i = 7; i > 0; i--) s[i] = s[i - 1];
-            s[0] = 0;
-        }
-    }
-    if (bsh) {
-#pragma unroll
-        for (int i = 7; i > 0; i--) s[i] = (s[i] << bsh) | (s[i - 1] >> (32 - bsh));
-        s[0] <<= bsh;
-    }
-    XYZZ<F> acc = xyzz_from_affine(x, y);        // the top bit
-#pragma unroll 1
-    for (int b = 0; b < top; b++) {
-#pragma unroll
-        for (int i = 7; i > 0; i--) s[i] = (s[i] << 1) | (s[i - 1] >> 31);
-        s[0] <<= 1;
-        acc = xyzz_dbl(acc);
-        if (s[7] >> 31) acc = xyzz_madd(acc, x, y);
-    }
+    const XYZZ<F> acc = walk_product(s, x, y);
     st_xyzz<Cfg>(o, acc);
 }
 

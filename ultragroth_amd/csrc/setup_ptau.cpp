@@ -19,10 +19,6 @@ using namespace ug;
 
 namespace {
 
-struct PtauError : public std::invalid_argument {
-    explicit PtauError(const std::string& m) : std::invalid_argument("ptau: " + m) {}
-};
-
 constexpr int PTAU_PHASES = UG_SETUP_PTAU_PHASES;
 
 // ---- the point check on host threads (device = -1): the rules of check.hip, in its order ----
@@ -77,31 +73,26 @@ ug_point_fault hostCheck(bool g2, const uint8_t* rec, u64 n, int level) {
     return ug_point_fault{0, UG_POINT_OK};
 }
 
+}  // namespace
+
 // the device's check, through the library's own entry (ug_points_check uploads in bounded pieces and leaves nothing resident)
-struct Ctx {
-    ug_ctx* c = nullptr;
-    explicit Ctx(int device) { if (ug_ctx_create(&c, device) != UG_OK) throw SetupError(ug_last_error()); }
-    ~Ctx() { ug_ctx_destroy(c); }
-};
-struct Checker {
-    int device, level;
-    std::unique_ptr<Ctx> ctx;
-    Checker(int device_, int level_) : device(device_), level(level_) {
-        if (level && device >= 0) ctx.reset(new Ctx(device));
+PtauPointCheck::PtauPointCheck(int device, int level) : device_(device), level_(level) {
+    if (level_ && device_ >= 0 && ug_ctx_create(&ctx_, device_) != UG_OK) throw SetupError(ug_last_error());
+}
+PtauPointCheck::~PtauPointCheck() { if (ctx_) ug_ctx_destroy(ctx_); }
+void PtauPointCheck::operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const {
+    if (!level_ || !n) return;
+    ug_point_fault f{0, UG_POINT_OK};
+    if (device_ < 0) f = hostCheck(g2, rec, n, level_);
+    else if (ug_points_check(ctx_, g2 ? 1 : 0, rec, n, level_, &f) != UG_OK) throw SetupError(ug_last_error());
+    if (f.reason) {
+        const char* text = f.reason == UG_POINT_UNREDUCED ? "coordinate not below the field modulus"
+                         : f.reason == UG_POINT_OFF_CURVE ? "not on the curve" : "not in the subgroup of order r";
+        throw PtauError("section " + std::to_string(id) + " point " + std::to_string(first + stride * f.index) + ": " + text);
     }
-    // n records of section `id`; record i is the section's record first + stride * i
-    void operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const {
-        if (!level || !n) return;
-        ug_point_fault f{0, UG_POINT_OK};
-        if (device < 0) f = hostCheck(g2, rec, n, level);
-        else if (ug_points_check(ctx->c, g2 ? 1 : 0, rec, n, level, &f) != UG_OK) throw SetupError(ug_last_error());
-        if (f.reason) {
-            const char* text = f.reason == UG_POINT_UNREDUCED ? "coordinate not below the field modulus"
-                             : f.reason == UG_POINT_OFF_CURVE ? "not on the curve" : "not in the subgroup of order r";
-            throw PtauError("section " + std::to_string(id) + " point " + std::to_string(first + stride * f.index) + ": " + text);
-        }
-    }
-};
+}
+
+namespace {
 
 void checkOptions(const ug_setup_ptau_options* o) {
     if (!o) throw SetupError("null options");
@@ -222,7 +213,7 @@ u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, co
     lap(0);
 
     {
-        const Checker check(device, (int)opt->validate);
+        const PtauPointCheck check(device, (int)opt->validate);
         check(false, sl.tau1, N, 12, sl.first, 1);
         check(true, sl.tau2, N, 13, sl.first, 1);
         check(false, sl.alphaTau1, N, 14, sl.first, 1);
