@@ -609,6 +609,72 @@ int  ug_points_combine(int device, int g2, const uint32_t* col_ptr, uint64_t n_c
 int  ug_points_scale(int device, const void* scalar, const void* points, uint64_t n, void* out, double* kernel_ms, char* error_msg,
                      unsigned long long error_msg_maxsize);
 
+/* CHECKING A KEY AGAINST ITS CIRCUIT AND POWERS OF TAU (zkey_verify.cpp, zkey_verify.hip; what `snarkjs zkey verify` answers about
+ * the key's POINTS; no reference counterpart: the reference starts from a .zkey somebody else made). Given a circuit's .r1cs, a
+ * .ptau prepared for phase 2 and a Groth16 (protocol 1) .zkey, the call says whether sections 2 - 9 of the key are the ones
+ * ug_setup_ptau_run gives for these files under ONE delta, which is not known to this code: the key is then A phase-2 descendant
+ * of `zkey new` for SOME delta. OUT OF SCOPE: who contributed -- section 10's transcript, beacons, the .ptau's own ceremony
+ * (ug_ptau_prepare_run's check mode covers sections 12 - 15 against 2 - 5) -- and UltraGroth keys, which are refused with
+ * "zkey: protocol 1337 keys are not checked".
+ *
+ * The relations (notation of ug_setup_ptau_run, P = level n + 1 of section 12). rho: one weight below 2^128
+ * per wire, sigma: one per row of the domain, drawn from getrandom in every call and never derived from the inputs; rho^pub = rho on
+ * wires 0 .. nPublic, rho^priv the rest; a^m = A rho^m, b^m = B rho^m, c^m = C rho^m over the rows (the public rows in a^pub);
+ * K^m = MSM(a^m, bT) + MSM(b^m, aT) + MSM(c^m, T); a = a^pub + a^priv, b likewise. In this order:
+ *   0  section 2   alpha1, beta1, beta2 are the .ptau's section 4 [0], 5 [0], 6 by bytes; delta1, delta2, gamma2 are not infinity;
+ *                  e(delta1, G2) = e(G1, delta2)                          "zkey: header: <field> ..."
+ *   1  section 4   byte for byte the section ug_setup_run writes for the .r1cs     "zkey: section 4 record <i>: does not match the circuit"
+ *   2  section 5   MSM(rho, A) = MSM(a, T)                    3  section 6   MSM(rho, B1) = MSM(b, T)
+ *   4  section 7   MSM(rho, B2) = MSM(b, T2)                  5  section 3   e(MSM(rho^pub, IC), gamma2) = e(K^pub, G2)
+ *   6  section 8   e(MSM(rho^priv, C), delta2) = e(K^priv, G2)
+ *   7  section 9   e(MSM(sigma, H), delta2) = e(MSM(sigma, odd records of P), G2)
+ * with "zkey: section <id>: does not match the circuit and the powers of tau" for sections 3, 5, 6, 7 and the same plus " under the
+ * key's delta" for 8 and 9. gamma2 is the key's own (snarkjs writes G2; ug_setup_run's keys have any gamma). All relations are
+ * evaluated even after one fails; error_msg holds the message of the first that fails in the order above, first_failed its section.
+ * A deviating section is accepted with probability at most 2^-128 per relation, GIVEN that every point lies in its group of order r:
+ * so every point of the key and of the slices goes through the point check first (ug_points_check; host threads for device = -1),
+ * the G2 points at level `validate`. validate = 2 (the tool's default) checks the G2 subgroup; validate = 1 is for timing and its
+ * report says subgroup_checked = 0: an answer of UG_OK is then NOT "valid".
+ *
+ * Returns UG_OK: valid; UG_ZKEY_INVALID: failed_sections has bit <id> set for every failing section 2 - 9; UG_ERROR: refused --
+ * a file that cannot be read, sizes that do not belong together (the loaders' texts under "r1cs: " / "ptau: " / "zkey: "; "zkey:
+ * header: nVars ..." and the like), or a bad point, with ug_zkey_check's message for the key ("zkey: section <id> point <i>:
+ * <reason>", "zkey: header point <name>: <reason>") and ug_setup_ptau_run's for the .ptau. Every size and header rule fires before
+ * the first device byte. device >= 0: the fold and the MSMs run on the device, one section's bases resident at a time;
+ * device = -1: the same relations on host threads (the comparator, and what a machine without a GPU has). The pairings run on
+ * host threads either way. The files are only read: the call takes (mapped) buffers. */
+#define UG_ZKEY_INVALID 2
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_zkey_verify_options) */
+    uint32_t validate;                  /* 2: field range, curve and G2 subgroup of every point; 1: without the subgroup (timing only) */
+} ug_zkey_verify_options;
+typedef struct {
+    uint32_t failed_sections;           /* bit <id> for every section 2 - 9 that fails */
+    int32_t  first_failed;              /* the section of the first failing relation in the order above, 0: none */
+    uint32_t subgroup_checked;          /* 1: the G2 points passed the subgroup rule (validate = 2) */
+    uint32_t reserved;
+    uint64_t peak_device_bytes;         /* device memory in use at its peak, above what was in use when the call began (device >= 0) */
+    double   fold_kernel_ms;            /* the fold kernel alone (host threads: the fold's wall time) */
+} ug_zkey_verify_report;
+#define UG_ZKEY_VERIFY_PHASES 8  /* parse + header + section 4 | point check | weights | fold | slice products | key products | H products | pairings */
+int  ug_zkey_verify_run(const ug_zkey_verify_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
+                        const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out, double* phase_ms, char* error_msg,
+                        unsigned long long error_msg_maxsize);
+/* Test tooling for the fold, host buffers, device >= 0 or -1 (host threads); messages prefixed "r1cs: ". rho: nWires plain 32-byte
+ * integers, ANY value below 2^256, taken mod r as a witness is; log_domain 0: the smallest domain that fits. out: SIX vectors of
+ * N = 2^log_domain plain canonical integers, a^pub, b^pub, c^pub, a^priv, b^priv, c^priv: row k < nConstraints holds the sums of
+ * its A, B, C terms times rho over the wires 0 .. nPublic and over the others; row nConstraints + s, s <= nPublic, holds rho_s mod r
+ * in a^pub and 0 elsewhere; the rows above hold 0. kernel_ms (may be NULL): the kernel's time. */
+int  ug_r1cs_fold(const void* r1cs, uint64_t r1cs_size, const void* rho, uint32_t log_domain, int device, void* out, double* kernel_ms,
+                  char* error_msg, unsigned long long error_msg_maxsize);
+/* The device forms the check is made of. ug_r1cs_fold_dvec: the fold of a resident circuit over a resident rho into `out`, EIGHT
+ * vectors of 2^log_domain elements: the six above, then a = a^pub + a^priv and b, each an MSM scalar vector where it lies
+ * (ug_schedule_build over its range); one launch, one host wait. ug_bases_create_every_g1: the G1 set of the records first,
+ * first + step, ... of n_records host records (H's sources are the odd records of a level: first 1, step 2), gathered on the device. */
+int  ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32_t log_domain, ug_dvec* out, double* kernel_ms);
+int  ug_bases_create_every_g1(ug_ctx* ctx, const void* host_points, uint64_t n_records, uint64_t first, uint64_t step, uint64_t global_first,
+                              ug_bases** out);
+
 /* PREPARING A POWERS-OF-TAU FILE FOR PHASE 2: sections 2 - 5 -> sections 12 - 15 (ptau_prepare.cpp, ptau_prepare.hip; what
  * `snarkjs powersoftau prepare phase2` does), and the check that a file's sections 12 - 15 ARE the Lagrange forms of its sections
  * 2 - 5, which ug_setup_ptau_run takes on trust. The layout is the one restated above, AS REMEMBERED of snarkjs' format: NO FILE OF

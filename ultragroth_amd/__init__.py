@@ -517,6 +517,89 @@ def points_intt(points, log_n, g2=False, device=0, timing=None):
 
 
 # ---------------------------------------------------------------------------------------------------
+# a Groth16 key against its circuit and a prepared powers-of-tau file (include/ultragroth_hip.h: ug_zkey_verify_run, ug_r1cs_fold)
+ZKEY_VERIFY_PHASES = ("parse", "point_check", "weights", "fold", "slice_msm", "key_msm", "h_msm", "pairing")
+UG_ZKEY_INVALID = 2
+
+
+class _ZkeyVerifyOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("validate", C.c_uint32)]
+
+
+class _ZkeyVerifyReport(C.Structure):
+    _fields_ = [("failed_sections", C.c_uint32), ("first_failed", C.c_int32), ("subgroup_checked", C.c_uint32), ("reserved", C.c_uint32),
+                ("peak_device_bytes", C.c_uint64), ("fold_kernel_ms", C.c_double)]
+
+
+def zkey_verify(r1cs, ptau, zkey, device=0, validate=2, timings=None):
+    """ug_zkey_verify_run: is this Groth16 key the one `setup_from_ptau(r1cs, ptau)` gives under ONE delta, which nobody has to
+    know? None when it is; (first_section, failed_sections, message) when not -- the sections 2 - 9 whose relation fails, in
+    ascending order, and the section and message of the first failing relation. Refusals -- a file that cannot be read, sizes
+    that do not belong together, a bad point, an UltraGroth key -- raise SetupError ("r1cs: ..." / "ptau: ..." / "zkey: ...").
+
+    ptau and zkey: bytes, a memoryview / mmap, or a path that is mapped here. validate: 2 checks every point's field range and
+    curve and every G2 point's subgroup; 1 leaves the subgroup out and is for timing only -- the relations' soundness needs the
+    subgroup check, timings["subgroup_checked"] says False then. device=-1 evaluates the same relations on host threads.
+    timings: a dict that receives the milliseconds of ZKEY_VERIFY_PHASES, "fold_kernel" and "peak_device_bytes".
+    Who contributed (section 10's transcript, beacons, the .ptau's own ceremony) is not checked."""
+    L = load()
+    opt = _ZkeyVerifyOptions()
+    opt.size = C.sizeof(_ZkeyVerifyOptions)
+    if not 0 <= int(validate) < 1 << 32:
+        raise SetupError("zkey: validate %d is not 1 or 2" % validate)
+    opt.validate = int(validate)
+    r1cs = bytes(r1cs)
+    mp, mz = _Mapped(ptau), None
+    try:
+        mz = _Mapped(zkey)
+        rep = _ZkeyVerifyReport()
+        ms = (C.c_double * len(ZKEY_VERIFY_PHASES))()
+        err = C.create_string_buffer(1024)
+        rc = L.ug_zkey_verify_run(C.byref(opt), r1cs, len(r1cs), mp.address, mp.length, mz.address, mz.length, device, C.byref(rep), ms,
+                                  err, len(err) - 1)
+    finally:
+        mp.close()
+        if mz is not None:
+            mz.close()
+    msg = err.value.decode(errors="replace")
+    if rc not in (0, UG_ZKEY_INVALID):
+        raise SetupError(msg)
+    if timings is not None:
+        timings.update(zip(ZKEY_VERIFY_PHASES, ms))
+        timings.update(fold_kernel=rep.fold_kernel_ms, peak_device_bytes=rep.peak_device_bytes, subgroup_checked=bool(rep.subgroup_checked))
+    if rc == 0:
+        return None
+    return rep.first_failed, [i for i in range(2, 10) if rep.failed_sections >> i & 1], msg
+
+
+def r1cs_fold(r1cs, rho, log_domain=0, device=0, timing=None):
+    """ug_r1cs_fold (test tooling): the fold of a key check. rho: one integer below 2^256 per wire, taken mod r. Returns six lists
+    of N = 2^log_domain integers, (a_pub, b_pub, c_pub, a_priv, b_priv, c_priv): per row the sums of its A, B, C terms times rho
+    over the wires 0 .. nPublic and over the others; the public rows carry rho_s in a_pub. log_domain 0: the smallest domain
+    that fits. device=-1: host threads. timing: a list that receives the kernel's milliseconds."""
+    r1cs = bytes(r1cs)
+    try:
+        info = r1cs_info(r1cs)
+    except DeviceError as e:
+        raise SetupError(str(e) if str(e).startswith("r1cs: ") else "r1cs: " + str(e))
+    rho = [int(x) for x in rho]
+    if len(rho) != info["n_wires"] or any(not 0 <= x < 1 << 256 for x in rho):
+        raise SetupError("r1cs: rho takes one integer below 2^256 per wire (%d wires)" % info["n_wires"])
+    rows = info["n_constraints"] + info["n_pub_out"] + info["n_pub_in"] + 1
+    log_n = int(log_domain) if log_domain else max(1, (rows - 1).bit_length())
+    if not 0 < log_n <= 27:
+        raise SetupError("r1cs: log_domain %d is not in 1 .. 27" % log_n)
+    n = 1 << log_n
+    out = C.create_string_buffer(6 * 32 * n)
+    ms = C.c_double()
+    _setup_call(load().ug_r1cs_fold, r1cs, len(r1cs), b"".join(x.to_bytes(32, "little") for x in rho), log_n, device, out, C.byref(ms))
+    if timing is not None:
+        timing.append(ms.value)
+    raw = out.raw
+    return tuple([int.from_bytes(raw[32 * (v * n + k):32 * (v * n + k) + 32], "little") for k in range(n)] for v in range(6))
+
+
+# ---------------------------------------------------------------------------------------------------
 # verifier mirror (src/verifier.h)
 VERIFIER_VALID_PROOF, VERIFIER_INVALID_PROOF, VERIFIER_ERROR = 0, 1, 2
 

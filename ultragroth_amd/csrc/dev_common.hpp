@@ -107,9 +107,13 @@ template <class P> __device__ __forceinline__ Fp<P> contract(const Fp<P>& a) {
 // The sum of one row of a CSR coefficient matrix times the witness (hpoly.hip: rows r < domain: matrix A, the others: matrix B;
 // r1cs.hip: one matrix of an .r1cs per triple). val: coef * 2^522 packed, wtns: plain 32-byte integers; the sum is w * coef in
 // device Montgomery form, strict, < 2.01 q.
-__device__ __forceinline__ Fr matvec_row(u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns) {
+// The walk itself takes the number of sums as a parameter: with SUMS = 2 (the fold of zkey_verify.hip) an entry whose signal id
+// is above `split` goes to acc[1], every other one to acc[0]; with SUMS = 1 there is one sum and `split` is not read.
+template <int SUMS>
+__device__ __forceinline__ void matvec_walk(u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns, u32 split, Fr (&acc)[SUMS]) {
     u32 s = row_ptr[r], e = row_ptr[r + 1];
-    Fr acc = fp_zero<FrParams>();
+#pragma unroll
+    for (int a = 0; a < SUMS; a++) acc[a] = fp_zero<FrParams>();
     u32 since = 0;
     // four entries at a time: their signal ids first, then the four 32-byte witness gathers and the four coefficients all in
     // flight together, then the products (one entry per turn left every gather's latency -- a DRAM row miss -- exposed: 69 %
@@ -126,12 +130,24 @@ __device__ __forceinline__ Fr matvec_row(u32 r, const u32* row_ptr, const u32* s
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if ((u32)k < cnt) {
-                acc = add(acc, mul(unpack256<FrParams>(wr[k]), unpack256<FrParams>(vr[k])));      // + < 2q  (w: plain integer, any value < 2^256)
-                if (++since == 24) { acc = contract(acc); since = 0; }                              // keep below 64 q
+                const Fr term = mul(unpack256<FrParams>(wr[k]), unpack256<FrParams>(vr[k]));       // < 2q  (w: plain integer, any value < 2^256)
+                if (SUMS == 2 && sg[k] > split) acc[SUMS - 1] = add(acc[SUMS - 1], term);
+                else acc[0] = add(acc[0], term);
+                if (++since == 24) {                                                                // keep below 64 q
+#pragma unroll
+                    for (int a = 0; a < SUMS; a++) acc[a] = contract(acc[a]);
+                    since = 0;
+                }
             }
         }
     }
-    return contract(acc);
+#pragma unroll
+    for (int a = 0; a < SUMS; a++) acc[a] = contract(acc[a]);
+}
+__device__ __forceinline__ Fr matvec_row(u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns) {
+    Fr acc[1];
+    matvec_walk<1>(r, row_ptr, sig, val, wtns, 0, acc);
+    return acc[0];
 }
 
 __host__ __device__ __forceinline__ u32 bit_reverse(u32 x, int bits) {

@@ -353,4 +353,13 @@ void r1cs_row_values(const R1csDev& m, const u32* wtns, u32 k, u32* out24, hipSt
 // the probe against a zkey's coefficient matrix over z (n_wires plain values): *word = the lowest failing 2 * row + matrix, or all ones
 void r1cs_match(const R1csDev& m, const CoefMatrix& zk, u32 n_public, const u32* z, unsigned long long* word, hipStream_t stream);
 
+// ---- zkey_verify.hip ----------------------------------------------------------------------------------
+// The fold of a key check: one lane per row of the domain, rho (n_wires plain integers) in the witness's place, two sums per
+// matrix -- wires 0 .. n_public and the others. out: eight vectors of `domain` canonical plain integers, a^pub, b^pub, c^pub,
+// a^priv, b^priv, c^priv, a = a^pub + a^priv, b; rows m.rows + s, s <= n_public, carry rho_s mod r in a^pub and a, rows above
+// them zeros. The caller vouches for m.rows + n_public + 1 <= domain and n_public < n_wires.
+void r1cs_fold(const R1csDev& m, const u32* rho, u32 n_public, u32 domain, u32* out, hipStream_t stream);
+// dst[i] = src[first + i * step] over `count` G1 records of 64 bytes (any form: the records are copied, not read)
+void points_take_every(u32* dst, const u32* src, u64 first, u64 step, u64 count, hipStream_t stream);
+
 }  // namespace ug

@@ -665,6 +665,7 @@ void fillCoefs(const R1cs& cs, const Plan& p, const std::vector<u64>& perPiece, 
 }
 
 }  // namespace
+void writeCoefs(const R1cs& cs, const Plan& p, const std::vector<u64>& perPiece, uint8_t* out) { fillCoefs(cs, p, perPiece, out); }
 
 // ---- file layout ----
 u64 Layout::offsetOf(u32 id) const {

@@ -150,6 +150,9 @@ public:
     PtauPointCheck(int device, int level);
     ~PtauPointCheck();
     void operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const;
+    // the same check for a caller with messages of its own (zkey_verify.cpp): the lowest bad record and the first rule it breaks
+    ug_point_fault find(bool g2, const uint8_t* rec, u64 n) const;
+    static const char* reasonText(int reason);
     PtauPointCheck(const PtauPointCheck&) = delete;
     PtauPointCheck& operator=(const PtauPointCheck&) = delete;
 private:
@@ -166,6 +169,8 @@ void planSizes(const R1csHeader& h, u32 logDomain, Plan& p);       // nVars .. N
 void loadCircuit(const void* r1cs, u64 size, std::unique_ptr<BinFile>& f, R1csHeader& h);
 void buildColumns(const R1cs& cs, const Plan& p, ColMatrix cm[3], std::vector<Piece>& pieces);
 void countCoefs(const R1cs& cs, std::vector<u64>& perPiece);
+// section 4's records (44 bytes each, without the count in front): the sum of perPiece for the constraints, then nPublic + 1
+void writeCoefs(const R1cs& cs, const Plan& p, const std::vector<u64>& perPiece, uint8_t* out);
 struct Layout {
     u64 nCoefs = 0, total = 0;
     std::vector<std::pair<u32, u64>> sections;      // id, payload size, in file order

@@ -80,16 +80,20 @@ PtauPointCheck::PtauPointCheck(int device, int level) : device_(device), level_(
     if (level_ && device_ >= 0 && ug_ctx_create(&ctx_, device_) != UG_OK) throw SetupError(ug_last_error());
 }
 PtauPointCheck::~PtauPointCheck() { if (ctx_) ug_ctx_destroy(ctx_); }
-void PtauPointCheck::operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const {
-    if (!level_ || !n) return;
+ug_point_fault PtauPointCheck::find(bool g2, const uint8_t* rec, u64 n) const {
     ug_point_fault f{0, UG_POINT_OK};
+    if (!level_ || !n) return f;
     if (device_ < 0) f = hostCheck(g2, rec, n, level_);
     else if (ug_points_check(ctx_, g2 ? 1 : 0, rec, n, level_, &f) != UG_OK) throw SetupError(ug_last_error());
-    if (f.reason) {
-        const char* text = f.reason == UG_POINT_UNREDUCED ? "coordinate not below the field modulus"
-                         : f.reason == UG_POINT_OFF_CURVE ? "not on the curve" : "not in the subgroup of order r";
-        throw PtauError("section " + std::to_string(id) + " point " + std::to_string(first + stride * f.index) + ": " + text);
-    }
+    return f;
+}
+const char* PtauPointCheck::reasonText(int reason) {
+    return reason == UG_POINT_UNREDUCED ? "coordinate not below the field modulus"
+         : reason == UG_POINT_OFF_CURVE ? "not on the curve" : "not in the subgroup of order r";
+}
+void PtauPointCheck::operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const {
+    const ug_point_fault f = find(g2, rec, n);
+    if (f.reason) throw PtauError("section " + std::to_string(id) + " point " + std::to_string(first + stride * f.index) + ": " + reasonText(f.reason));
 }
 
 namespace {

@@ -482,6 +482,29 @@ int ug_bases_create_tables_strided_g1(ug_ctx* c, const void* host, uint64_t n, u
 int ug_bases_create_tables_strided_g2(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, int table_c, int stride, ug_bases** out) {
     return bases_create(c, host, n, gf, true, table_c, stride, out);
 }
+// The n_records host records go up and are converted as one plain set; the records first, first + step, ... are then copied side
+// by side on the device into the set that is returned, and the upload is freed.
+int ug_bases_create_every_g1(ug_ctx* c, const void* host, uint64_t n_records, uint64_t first, uint64_t step, uint64_t gf, ug_bases** out) {
+    if (!c || !out || !host || !step || first >= n_records) return fail("ug_bases_create_every_g1: null argument, step 0 or no record to take");
+    ug_bases* all = nullptr;
+    if (bases_create(c, host, n_records, 0, false, 0, 1, &all) != UG_OK) return UG_ERROR;
+    std::unique_ptr<ug_bases, void (*)(ug_bases*)> hold(all, ug_bases_destroy);
+    UG_TRY
+    const u64 count = (n_records - first + step - 1) / step;
+    std::unique_ptr<ug_bases> b(new ug_bases{c, false, count, gf, nullptr, 0});
+    b->empty = true;
+    for (u64 i = 0; i < count && b->empty; i++) b->empty = host_all_zero(static_cast<const unsigned char*>(host) + (first + i * step) * 64, 64);
+    if (hipMalloc(&b->pts, (size_t)count * 64) != hipSuccess) {
+        (void)hipGetLastError();
+        throw std::runtime_error("not enough device memory for the base points");
+    }
+    try {
+        points_take_every(b->pts, all->pts, first, step, count, c->stream);
+        UG_HIP(hipStreamSynchronize(c->stream));
+    } catch (...) { hipFree(b->pts); throw; }
+    *out = b.release();
+    UG_CATCH
+}
 
 // A group of `members` (2 or 3) G1 sets that are always multiplied by the same scalars, as ONE array of members-point
 // records (msm.hip: segment_accumulate_group_kernel). Member m brings n[m] points; its first point belongs to the scalar
@@ -1937,6 +1960,32 @@ int ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* 
     UG_HIP(hipStreamSynchronize(c->stream));
     if (*word_host == ~0ull) { *matrix = -1; *row = 0; }
     else { *matrix = (int)(*word_host & 1); *row = *word_host >> 1; }
+    UG_CATCH
+}
+int ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32_t log_domain, ug_dvec* out, double* kernel_ms) {
+    UG_TRY
+    if (!r || !rho || !out) throw std::invalid_argument("null argument");
+    ug_ctx* c = r->ctx;
+    if (rho->ctx->device != c->device || out->ctx->device != c->device) throw std::invalid_argument("r1cs: a vector lives on another device");
+    if (c->recording) throw std::invalid_argument("r1cs: no fold while the context's stream is being recorded");
+    if (log_domain > 27) throw std::invalid_argument("r1cs: log_domain " + std::to_string(log_domain) + " is above 27");
+    const u64 N = (u64)1 << log_domain;
+    if (rho->n < r->hdr.nWires) throw std::invalid_argument("r1cs: the weight vector is shorter than n_wires (" + std::to_string(r->hdr.nWires) + " wires)");
+    if ((u64)n_public + 1 > r->hdr.nWires) throw std::invalid_argument("r1cs: " + std::to_string(n_public) + " public signals, " + std::to_string(r->hdr.nWires) + " wires");
+    if ((u64)r->hdr.nConstraints + n_public + 1 > N)
+        throw std::invalid_argument("r1cs: " + std::to_string(r->hdr.nConstraints) + " constraints and " + std::to_string(n_public) +
+                                    " public signals do not fit a domain of " + std::to_string(N));
+    if (out->n < 8 * N) throw std::invalid_argument("r1cs: the output vector is shorter than 8 * 2^log_domain");
+    c->use();
+    UG_HIP(hipStreamSynchronize(rho->ctx->stream));             // (the weights may have been queued on another context's stream)
+    if (out->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(out->ctx->stream));
+    UG_HIP(hipEventRecord(r->t0, c->stream));
+    r1cs_fold(r->dev(), rho->data, n_public, (u32)N, out->data, c->stream);
+    UG_HIP(hipEventRecord(r->t1, c->stream));
+    UG_HIP(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    UG_HIP(hipEventElapsedTime(&ms, r->t0, r->t1));
+    if (kernel_ms) *kernel_ms = ms;
     UG_CATCH
 }
 void ug_r1cs_destroy(ug_r1cs* r) {
