@@ -12,20 +12,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
-#include <fstream>
 #include <string>
 #include <vector>
+#include "fuzz_kit.hpp"
 #include "host_util.hpp"
 
 using namespace ughost;
-
-static uint64_t rng_state;
-static uint64_t rnd() {                       // splitmix64
-    uint64_t z = (rng_state += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
+using namespace fuzz;
 
 static volatile uint8_t sink;
 static void touch(const BinFile& f, uint32_t id) {
@@ -56,46 +49,28 @@ static int parse(const std::vector<uint8_t>& buf, bool zkey) {
 
 int main(int argc, char** argv) {
     if (argc < 5) { fprintf(stderr, "usage: fuzz_parsers <file> <zkey|wtns> <iterations> <seed>\n"); return 2; }
-    std::ifstream in(argv[1], std::ios::binary);
-    std::vector<uint8_t> orig((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    const std::vector<uint8_t> orig = readFile(argv[1]);
     const bool zkey = std::string(argv[2]) == "zkey";
     const long iters = atol(argv[3]);
     rng_state = strtoull(argv[4], nullptr, 10);
     if (parse(orig, zkey) != 0) { fprintf(stderr, "the unmodified file does not parse\n"); return 3; }
-    // offsets of the section headers of the original file (type u32, size u64 at +4)
-    std::vector<size_t> hdrs;
-    {
-        uint32_t n; memcpy(&n, orig.data() + 8, 4);
-        size_t pos = 12;
-        for (uint32_t i = 0; i < n && pos + 12 <= orig.size(); i++) {
-            hdrs.push_back(pos);
-            uint64_t sz; memcpy(&sz, orig.data() + pos + 4, 8);
-            pos += 12 + sz;
-        }
-    }
+    const std::vector<size_t> hdrs = headerOffsets(walkSections(orig));
     const uint64_t extremes[] = {0, 1, 0xffffffffull, 0x100000000ull, 0x7fffffffffffffffull, 0x8000000000000000ull,
                                  0xffffffffffffffffull, 0xfffffffffffffff4ull, 0xffffffffffffffe8ull};
-    long ok = 0, rejected = 0;
-    for (long it = 0; it < iters; it++) {
-        std::vector<uint8_t> buf = orig;
+    mutateAndParse(orig, iters, [&](std::vector<uint8_t>& buf) {
         switch (rnd() % 5) {
             case 0: {                                  // bit flips near the start (magic, version, counts, first headers)
                 int k = 1 + (int)(rnd() % 4);
                 for (int j = 0; j < k; j++) { size_t o = rnd() % (buf.size() < 4096 ? buf.size() : 4096); buf[o] ^= (uint8_t)(1u << (rnd() % 8)); }
                 break;
             }
-            case 1: {                                  // bit flips inside a section header
+            case 1: {                                  // a bit flip inside a section header
                 size_t h = hdrs[rnd() % hdrs.size()];
-                buf[h + rnd() % 12] ^= (uint8_t)(1u << (rnd() % 8));
+                flipBit(buf, h, 12);
                 break;
             }
-            case 2: buf.resize(rnd() % (buf.size() + 1)); break;           // truncation
-            case 3: {                                  // a section size replaced by an extreme value (+- a small offset)
-                size_t h = hdrs[rnd() % hdrs.size()];
-                uint64_t v = extremes[rnd() % (sizeof extremes / sizeof extremes[0])] + (rnd() % 3) - 1;
-                memcpy(buf.data() + h + 4, &v, 8);
-                break;
-            }
+            case 2: truncate(buf); break;
+            case 3: replaceSectionSize(buf, hdrs, extremes); break;
             default: {                                 // header fields of the first payload section (n8, counts)
                 if (hdrs.size() > 1) {
                     size_t h = hdrs[1] + 12;
@@ -104,8 +79,6 @@ int main(int argc, char** argv) {
                 break;
             }
         }
-        if (parse(buf, zkey) == 0) ok++; else rejected++;
-    }
-    printf("%ld parsed, %ld rejected, 0 crashed\n", ok, rejected);
+    }, [&](const std::vector<uint8_t>& buf) { return parse(buf, zkey); });
     return 0;
 }

@@ -13,21 +13,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
-#include <fstream>
-#include <iterator>
-#include <memory>
 #include <vector>
+#include "fuzz_kit.hpp"
 #include "host_util.hpp"
 
 using namespace ughost;
-
-static uint64_t rng_state;
-static uint64_t rnd() {                       // splitmix64
-    uint64_t z = (rng_state += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
+using namespace fuzz;
 
 static volatile uint64_t sink;
 
@@ -63,75 +54,38 @@ static int parse(const uint8_t* data, size_t size) {
 }
 
 static int parse(const std::vector<uint8_t>& buf) {
-    std::unique_ptr<uint8_t[]> exact(new uint8_t[buf.size() ? buf.size() : 1]);
-    if (!buf.empty()) memcpy(exact.get(), buf.data(), buf.size());
-    return parse(exact.get(), buf.size());
+    const Exact exact(buf);
+    return parse(exact.p.get(), exact.n);
 }
 
 int main(int argc, char** argv) {
     if (argc < 4) { fprintf(stderr, "usage: fuzz_ptau <file> <iterations> <seed>\n"); return 2; }
-    std::ifstream in(argv[1], std::ios::binary);
-    std::vector<uint8_t> orig((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    const std::vector<uint8_t> orig = readFile(argv[1]);
     const long iters = atol(argv[2]);
     rng_state = strtoull(argv[3], nullptr, 10);
     if (orig.size() < 12 || parse(orig) != 0) { fprintf(stderr, "the unmodified file does not parse\n"); return 3; }
-    std::vector<size_t> hdrs;                   // offsets of the section headers (id u32, size u64 at +4)
-    size_t s1 = 0;
-    {
-        uint32_t n; memcpy(&n, orig.data() + 8, 4);
-        size_t pos = 12;
-        for (uint32_t i = 0; i < n && pos + 12 <= orig.size(); i++) {
-            hdrs.push_back(pos);
-            uint32_t id; memcpy(&id, orig.data() + pos, 4);
-            uint64_t sz; memcpy(&sz, orig.data() + pos + 4, 8);
-            if (id == 1) s1 = pos + 12;
-            pos += 12 + sz;
-        }
-    }
-    if (!s1 || hdrs.empty()) { fprintf(stderr, "section 1 not found\n"); return 3; }
+    const std::vector<SectionAt> secs = walkSections(orig);
+    const std::vector<size_t> hdrs = headerOffsets(secs);
+    const SectionAt* sec1 = findSection(secs, 1);
+    if (!sec1) { fprintf(stderr, "section 1 not found\n"); return 3; }
+    const size_t s1 = sec1->header + 12;
     const uint64_t extremes[] = {0, 1, 63, 64, 127, 128, 0xffffffffull, 0x100000000ull, 0x7fffffffffffffffull, 0x8000000000000000ull,
                                  0xffffffffffffffffull, 0xfffffffffffffff4ull, 0xffffffffffffffc0ull};
     const uint32_t extremes32[] = {0, 1, 5, 6, 7, 27, 28, 29, 31, 32, 63, 64, 0x7fffffffu, 0x80000000u, 0xffffffffu};
-    long ok = 0, rejected = 0;
-    for (long it = 0; it < iters; it++) {
-        std::vector<uint8_t> buf = orig;
+    mutateAndParse(orig, iters, [&](std::vector<uint8_t>& buf) {
         switch (rnd() % 7) {
-            case 0: {                                  // bit flips in the header section (n8, prime, power, ceremonyPower)
-                int k = 1 + (int)(rnd() % 3);
-                for (int j = 0; j < k; j++) buf[s1 + rnd() % 44] ^= (uint8_t)(1u << (rnd() % 8));
-                break;
-            }
-            case 1: {                                  // bit flips anywhere (the reader never looks inside a point)
-                int k = 1 + (int)(rnd() % 4);
-                for (int j = 0; j < k; j++) buf[12 + rnd() % (buf.size() - 12)] ^= (uint8_t)(1u << (rnd() % 8));
-                break;
-            }
-            case 2: buf.resize(rnd() % (buf.size() + 1)); break;           // truncation
-            case 3: {                                  // a section size replaced by an extreme value (+- a small offset)
-                size_t h = hdrs[rnd() % hdrs.size()];
-                uint64_t v = extremes[rnd() % (sizeof extremes / sizeof extremes[0])] + (rnd() % 3) - 1;
-                memcpy(buf.data() + h + 4, &v, 8);
-                break;
-            }
+            case 0: flipBits(buf, s1, 44, 3); break;                       // in the header section (n8, prime, power, ceremonyPower)
+            case 1: flipBits(buf, 12, buf.size() - 12, 4); break;          // anywhere (the reader never looks inside a point)
+            case 2: truncate(buf); break;
+            case 3: replaceSectionSize(buf, hdrs, extremes); break;
             case 4: {                                  // the power or the ceremony power replaced
                 uint32_t v = extremes32[rnd() % (sizeof extremes32 / sizeof extremes32[0])];
                 memcpy(buf.data() + s1 + (rnd() % 2 ? 36 : 40), &v, 4);
                 break;
             }
-            case 5: {                                  // a section id replaced: a section goes missing, another appears twice
-                size_t h = hdrs[rnd() % hdrs.size()];
-                uint32_t v = (uint32_t)(rnd() % 18);
-                memcpy(buf.data() + h, &v, 4);
-                break;
-            }
-            default: {                                 // the section count replaced
-                uint32_t v = extremes32[rnd() % (sizeof extremes32 / sizeof extremes32[0])];
-                memcpy(buf.data() + 8, &v, 4);
-                break;
-            }
+            case 5: replaceSectionId(buf, hdrs); break;                    // a section goes missing, another appears twice
+            default: replaceWord(buf, 8, extremes32); break;               // the section count
         }
-        if (parse(buf) == 0) ok++; else rejected++;
-    }
-    printf("%ld parsed, %ld rejected, 0 crashed\n", ok, rejected);
+    }, [](const std::vector<uint8_t>& buf) { return parse(buf); });
     return 0;
 }

@@ -12,20 +12,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
-#include <fstream>
 #include <string>
 #include <vector>
+#include "fuzz_kit.hpp"
 #include "host_util.hpp"
 
 using namespace ughost;
-
-static uint64_t rng_state;
-static uint64_t rnd() {                       // splitmix64
-    uint64_t z = (rng_state += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
+using namespace fuzz;
 
 static volatile uint64_t sink;
 
@@ -55,51 +48,25 @@ static int parse(const std::vector<uint8_t>& buf) {
 
 int main(int argc, char** argv) {
     if (argc < 4) { fprintf(stderr, "usage: fuzz_r1cs <file> <iterations> <seed>\n"); return 2; }
-    std::ifstream in(argv[1], std::ios::binary);
-    std::vector<uint8_t> orig((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    const std::vector<uint8_t> orig = readFile(argv[1]);
     const long iters = atol(argv[2]);
     rng_state = strtoull(argv[3], nullptr, 10);
     if (parse(orig) != 0) { fprintf(stderr, "the unmodified file does not parse\n"); return 3; }
-    // offsets of the section headers of the original file (type u32, size u64 at +4) and the payload of sections 1 and 2
-    std::vector<size_t> hdrs;
-    size_t s1 = 0, s2 = 0, s2len = 0;
-    {
-        uint32_t n; memcpy(&n, orig.data() + 8, 4);
-        size_t pos = 12;
-        for (uint32_t i = 0; i < n && pos + 12 <= orig.size(); i++) {
-            hdrs.push_back(pos);
-            uint32_t id; memcpy(&id, orig.data() + pos, 4);
-            uint64_t sz; memcpy(&sz, orig.data() + pos + 4, 8);
-            if (id == 1) s1 = pos + 12;
-            if (id == 2) { s2 = pos + 12; s2len = (size_t)sz; }
-            pos += 12 + sz;
-        }
-    }
-    if (!s1 || !s2 || s2len < 16) { fprintf(stderr, "sections 1 and 2 not found\n"); return 3; }
+    // the section headers of the original file and the payload of sections 1 and 2
+    const std::vector<SectionAt> secs = walkSections(orig);
+    const std::vector<size_t> hdrs = headerOffsets(secs);
+    const SectionAt *sec1 = findSection(secs, 1), *sec2 = findSection(secs, 2);
+    if (!sec1 || !sec2 || sec2->size < 16) { fprintf(stderr, "sections 1 and 2 not found\n"); return 3; }
+    const size_t s1 = sec1->header + 12, s2 = sec2->header + 12, s2len = (size_t)sec2->size;
     const uint64_t extremes[] = {0, 1, 0xffffffffull, 0x100000000ull, 0x7fffffffffffffffull, 0x8000000000000000ull,
                                  0xffffffffffffffffull, 0xfffffffffffffff4ull, 0xffffffffffffffe8ull};
     const uint32_t extremes32[] = {0, 1, 0x7fffffffu, 0x80000000u, 0xffffffffu, 0x071c71c7u, 0x071c71c8u};      // (2^32 / 36 and its neighbour)
-    long ok = 0, rejected = 0;
-    for (long it = 0; it < iters; it++) {
-        std::vector<uint8_t> buf = orig;
+    mutateAndParse(orig, iters, [&](std::vector<uint8_t>& buf) {
         switch (rnd() % 6) {
-            case 0: {                                  // bit flips in the header section (n8, prime, counts)
-                int k = 1 + (int)(rnd() % 3);
-                for (int j = 0; j < k; j++) buf[s1 + rnd() % 64] ^= (uint8_t)(1u << (rnd() % 8));
-                break;
-            }
-            case 1: {                                  // bit flips anywhere in the constraints (term counts, wire ids, coefficients)
-                int k = 1 + (int)(rnd() % 4);
-                for (int j = 0; j < k; j++) buf[s2 + rnd() % s2len] ^= (uint8_t)(1u << (rnd() % 8));
-                break;
-            }
-            case 2: buf.resize(rnd() % (buf.size() + 1)); break;           // truncation
-            case 3: {                                  // a section size replaced by an extreme value (+- a small offset)
-                size_t h = hdrs[rnd() % hdrs.size()];
-                uint64_t v = extremes[rnd() % (sizeof extremes / sizeof extremes[0])] + (rnd() % 3) - 1;
-                memcpy(buf.data() + h + 4, &v, 8);
-                break;
-            }
+            case 0: flipBits(buf, s1, 64, 3); break;               // in the header section (n8, prime, counts)
+            case 1: flipBits(buf, s2, s2len, 4); break;            // anywhere in the constraints (term counts, wire ids, coefficients)
+            case 2: truncate(buf); break;
+            case 3: replaceSectionSize(buf, hdrs, extremes); break;
             case 4: {                                  // a header count (nWires .. nConstraints) replaced by an extreme value
                 uint32_t v = extremes32[rnd() % (sizeof extremes32 / sizeof extremes32[0])] + (uint32_t)(rnd() % 3) - 1;
                 const size_t field[] = {36, 40, 44, 48, 60};
@@ -114,8 +81,6 @@ int main(int argc, char** argv) {
                 break;
             }
         }
-        if (parse(buf) == 0) ok++; else rejected++;
-    }
-    printf("%ld parsed, %ld rejected, 0 crashed\n", ok, rejected);
+    }, [](const std::vector<uint8_t>& buf) { return parse(buf); });
     return 0;
 }

@@ -17,6 +17,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "fuzz_kit.hpp"
 #include "pairing_dev.hpp"
 #include "../../include/ultragroth_hip.h"
 #include "../../include/verifier.h"
@@ -39,13 +40,8 @@ void ug_ctx_destroy(ug_ctx*) {}
 int ug_points_check_mask(ug_ctx*, int, const void*, uint64_t, int, uint8_t*) { return UG_ERROR; }
 }
 
-static uint64_t rng_state;
-static uint64_t rnd() {                       // splitmix64
-    uint64_t z = (rng_state += 0x9e3779b97f4a7c15ull);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
+using fuzz::rnd;
+using fuzz::rng_state;
 static void fill(uint8_t* p, size_t n) { for (size_t i = 0; i < n; i++) p[i] = (uint8_t)rnd(); }
 static void fail(const char* what) { fprintf(stderr, "record_formats_main: %s\n", what); exit(1); }
 

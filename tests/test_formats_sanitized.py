@@ -3,33 +3,19 @@ verifier_api.cpp's conversions, hooks and device = -1 batch path, called by a st
 (tests/native/record_formats_main.cpp, built as tests/test_parsers_sanitized.py builds its harness). Records are a service's
 untrusted bytes: a conversion ends in one of its return codes, a batch call in verdicts."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-from conftest import GOLDEN, ROOT
-
-CSRC = os.path.join(ROOT, "ultragroth_amd", "csrc")
+from conftest import GOLDEN
+import sanitized_build
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    tmp = tmp_path_factory.mktemp("formats")
-    probe = tmp / "probe.cpp"                                                     # is there a sanitizer runtime at all? only that may skip
-    probe.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp / "probe")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    exe = str(tmp / "record_formats_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wno-unknown-pragmas", "-I", CSRC,
-           os.path.join(ROOT, "tests", "native", "record_formats_main.cpp"), os.path.join(CSRC, "verifier_api.cpp"),
-           os.path.join(CSRC, "verifier_records.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return sanitized_build.build(tmp_path_factory.mktemp("formats"), "record_formats_main",
+                                 ["record_formats_main.cpp", "verifier_api.cpp", "verifier_records.cpp", "host_util.cpp"],
+                                 flags=("-O1", "-pthread", "-Wno-unknown-pragmas"), need_gxx=False)
 
 
 def test_record_layouts_run_clean(harness):

@@ -4,28 +4,17 @@ must end in a normal return or a C++ exception, never in an out-of-bounds access
 .wtns buffer of a proving service is untrusted input; the reference's reader accepts a section size that wraps its cursor
 (src/binfile_utils.cpp:60-66)."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
-from conftest import GOLDEN, ROOT
-
-CSRC = os.path.join(ROOT, "ultragroth_amd", "csrc")
+from conftest import GOLDEN
+import sanitized_build
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("fuzz") / "fuzz_parsers")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
-           os.path.join(ROOT, "tests", "native", "fuzz_parsers.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    assert r.returncode == 0, r.stderr
-    return exe
+    return sanitized_build.build(tmp_path_factory.mktemp("fuzz"), "fuzz_parsers", ["fuzz_parsers.cpp", "host_util.cpp"], need_gxx=False)
 
 
 @pytest.mark.parametrize("name,kind", [("circuit_final.zkey", "zkey"), ("witness.wtns", "wtns"),

@@ -4,7 +4,6 @@ sanitizer, and the ptau_prepare tool. Every comparison is byte for byte: a trans
 the transformed integers, and the prepared file of a synthesized unprepared one must be the file the test writer makes from
 Lagrange values of the known tau."""
 import os
-import shutil
 import struct
 import subprocess
 
@@ -12,6 +11,7 @@ import pytest
 
 import oracle as O
 from conftest import ROOT
+import sanitized_build
 import r1cs_cases as RC
 import setup_cases as SC
 import setup_ptau_cases as PC
@@ -176,19 +176,7 @@ def test_refusals():
 # ------------------------------------------------------------------------------------------- native
 @pytest.fixture(scope="module")
 def fuzz_prepare(tmp_path_factory):
-    assert shutil.which("g++"), "no g++: the library's own Makefile needs one"
-    tmp = tmp_path_factory.mktemp("fuzz_ptau_prepare")
-    probe = tmp / "probe.cpp"                      # is there a sanitizer runtime at all? only that may skip
-    probe.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp / "probe")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    exe = str(tmp / "fuzz_ptau_prepare")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
-           os.path.join(ROOT, "tests", "native", "fuzz_ptau_prepare.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return sanitized_build.build(tmp_path_factory.mktemp("fuzz_ptau_prepare"), "fuzz_ptau_prepare", ["fuzz_ptau_prepare.cpp", "host_util.cpp"])
 
 
 def test_mutated_ptau_never_crashes_the_reader(fuzz_prepare, tmp_path):

@@ -3,29 +3,17 @@ thousand times with a fixed seed -- bit flips, truncations, counts and sizes nea
 normal return or a C++ exception every time, never in an out-of-bounds access (tests/native/fuzz_r1cs.cpp: a stand-alone
 program of host code only, run directly)."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
 import r1cs_cases as K
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "ultragroth_amd", "csrc")
+import sanitized_build
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("fuzz") / "fuzz_r1cs")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
-           os.path.join(ROOT, "tests", "native", "fuzz_r1cs.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    assert r.returncode == 0, r.stderr
-    return exe
+    return sanitized_build.build(tmp_path_factory.mktemp("fuzz"), "fuzz_r1cs", ["fuzz_r1cs.cpp", "host_util.cpp"], need_gxx=False)
 
 
 def test_mutated_r1cs_never_crashes_the_reader(harness, tmp_path):

@@ -3,7 +3,6 @@ through ultragroth_amd.dev_setup / generator_mul / lagrange_at. The keys it make
 Every comparison is byte for byte: against the committed trapdoor fixtures, the CPU oracle and Python integers."""
 import json
 import os
-import shutil
 import struct
 import subprocess
 
@@ -12,6 +11,7 @@ import pytest
 import oracle as O
 from oracle import pairing
 from conftest import ROOT
+import sanitized_build
 import r1cs_cases as RC
 import setup_cases as SC
 
@@ -174,20 +174,9 @@ def test_irregular_circuit_against_python_integers(n_pub_out, n_pub_in):
 
 @pytest.fixture(scope="module")
 def setup_main(tmp_path_factory):
-    assert shutil.which("g++"), "no g++: the library's own Makefile needs one"
     tmp = tmp_path_factory.mktemp("setup_main")
-    probe = tmp / "probe.cpp"                      # is there a sanitizer runtime at all? only that may skip
-    probe.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp / "probe")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    exe = str(tmp / "setup_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wno-unknown-pragmas",
-           "-I", CSRC, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "native", "setup_main.cpp"),
-           os.path.join(CSRC, "setup_host.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe, tmp
+    return sanitized_build.build(tmp, "setup_main", ["setup_main.cpp", "setup_host.cpp", "host_util.cpp"],
+                                 flags=("-O1", "-pthread", "-Wno-unknown-pragmas")), tmp
 
 
 def test_host_path_runs_clean_under_sanitizers(setup_main):

@@ -4,7 +4,6 @@ points_combine / points_scale, and the test writer synth.ptau_file. Every compar
 the fixture's (tau, alpha, beta) must give the key dev_setup gives for the trapdoor (tau, alpha, beta, gamma = 1, delta)."""
 import json
 import os
-import shutil
 import struct
 import subprocess
 
@@ -13,6 +12,7 @@ import pytest
 import oracle as O
 from oracle import pairing
 from conftest import ROOT
+import sanitized_build
 import r1cs_cases as RC
 import setup_cases as SC
 import setup_ptau_cases as PC
@@ -225,19 +225,7 @@ def test_points_scale_on_host_threads(n):
 # ------------------------------------------------------------------------------------------- native
 @pytest.fixture(scope="module")
 def fuzz_ptau(tmp_path_factory):
-    assert shutil.which("g++"), "no g++: the library's own Makefile needs one"
-    tmp = tmp_path_factory.mktemp("fuzz_ptau")
-    probe = tmp / "probe.cpp"                      # is there a sanitizer runtime at all? only that may skip
-    probe.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp / "probe")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    exe = str(tmp / "fuzz_ptau")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
-           os.path.join(ROOT, "tests", "native", "fuzz_ptau.cpp"), os.path.join(CSRC, "host_util.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return sanitized_build.build(tmp_path_factory.mktemp("fuzz_ptau"), "fuzz_ptau", ["fuzz_ptau.cpp", "host_util.cpp"])
 
 
 def test_mutated_ptau_never_crashes_the_reader(fuzz_ptau, tmp_path):

@@ -2,12 +2,12 @@
 include/ultragroth_hip.h ug_zkey_verify_run and ug_r1cs_fold through ultragroth_amd.zkey_verify / r1cs_fold, and the tool. The
 cases and what each of them must answer are tests/zkey_verify_cases.py's; test_gpu_zkey_verify.py asks the device the same."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
 from conftest import ROOT
+import sanitized_build
 import r1cs_cases as RC
 import setup_cases as SC
 import setup_ptau_cases as PC
@@ -134,20 +134,9 @@ def test_cli_exit_codes(tmp_path):
 # ------------------------------------------------------------------------------------------- native
 @pytest.fixture(scope="module")
 def fuzz_verify(tmp_path_factory):
-    assert shutil.which("g++"), "no g++: the library's own Makefile needs one"
-    tmp = tmp_path_factory.mktemp("fuzz_zkey_verify")
-    probe = tmp / "probe.cpp"                      # is there a sanitizer runtime at all? only that may skip
-    probe.write_text("int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp / "probe")], capture_output=True, text=True)
-    if r.returncode != 0:
-        pytest.skip("this g++ has no sanitizer runtime: " + r.stderr[-200:])
-    exe = str(tmp / "fuzz_zkey_verify")
-    cmd = ["g++", "-std=c++17", "-O2", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wno-unknown-pragmas",
-           "-I", CSRC, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "native", "fuzz_zkey_verify.cpp")] + \
-          [os.path.join(CSRC, f) for f in ("zkey_verify.cpp", "setup_ptau.cpp", "setup_host.cpp", "host_util.cpp")] + ["-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+    return sanitized_build.build(tmp_path_factory.mktemp("fuzz_zkey_verify"), "fuzz_zkey_verify",
+                                 ["fuzz_zkey_verify.cpp", "zkey_verify_host.cpp", "setup_ptau.cpp", "point_check.cpp", "setup_host.cpp", "host_util.cpp"],
+                                 flags=("-O2", "-pthread", "-Wno-unknown-pragmas"))
 
 
 def test_mutated_files_never_crash_the_check(fuzz_verify, tmp_path):

@@ -313,7 +313,7 @@ class _PtauInfo(C.Structure):
 
 class _Mapped:
     """bytes, a memoryview / mmap, or a path (mapped here, read-only) as (address, length) for a C call that only reads;
-    nothing is copied"""
+    nothing is copied. A context manager: the mapping closes with the block."""
 
     def __init__(self, src):
         import mmap
@@ -337,16 +337,27 @@ class _Mapped:
         for c in self._close:
             c.close()
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _joined(points, rec):
+    """the records joined, every one of `rec` bytes"""
+    data = b"".join(points)
+    if len(data) != rec * len(points):
+        raise SetupError("setup: a point record of another size")
+    return data
+
 
 def ptau_info(ptau):
     """ug_ptau_parse_info (host only): {"power", "ceremony_power", "prepared", "max_log_domain"} of a .ptau given as bytes, a
     memoryview / mmap or a path. The layout is restated in include/ultragroth_hip.h; no file of a real ceremony has been read yet."""
-    m = _Mapped(ptau)
-    try:
-        info = _PtauInfo()
+    info = _PtauInfo()
+    with _Mapped(ptau) as m:
         _setup_call(load().ug_ptau_parse_info, m.address, m.length, C.byref(info))
-    finally:
-        m.close()
     return {"power": info.power, "ceremony_power": info.ceremony_power, "prepared": bool(info.prepared), "max_log_domain": info.max_log_domain}
 
 
@@ -376,8 +387,7 @@ def setup_from_ptau(r1cs, ptau, delta=None, log_domain=0, device=0, validate=1, 
         opt.contribute = 1
         opt.delta = _le32(delta, "delta")
     r1cs = bytes(r1cs)
-    m = _Mapped(ptau)
-    try:
+    with _Mapped(ptau) as m:
         zbytes, vmax = C.c_uint64(), C.c_uint64()
         _setup_call(L.ug_setup_ptau_size, C.byref(opt), r1cs, len(r1cs), m.address, m.length, C.byref(zbytes), C.byref(vmax))
         zkey = C.create_string_buffer(zbytes.value)
@@ -386,8 +396,6 @@ def setup_from_ptau(r1cs, ptau, delta=None, log_domain=0, device=0, validate=1, 
         ms = (C.c_double * len(SETUP_PTAU_PHASES))()
         _setup_call(L.ug_setup_ptau_run, C.byref(opt), r1cs, len(r1cs), m.address, m.length, device, zkey, zbytes.value, C.byref(wrote), vkey,
                     vmax.value, C.byref(vlen), ms)
-    finally:
-        m.close()
     phase_ms = dict(zip(SETUP_PTAU_PHASES, ms))
     if timings is not None:
         timings.update(phase_ms)
@@ -406,9 +414,7 @@ def points_combine(col_ptr, index, coefs, points, g2=False, device=0, timing=Non
     cp = (C.c_uint32 * (n_cols + 1))(*col_ptr)
     ix = (C.c_uint32 * max(1, len(index)))(*index)
     co = b"".join(int(c).to_bytes(32, "little") for c in coefs)
-    pts = b"".join(points)
-    if len(pts) != rec * len(points):
-        raise SetupError("setup: a point record of another size")
+    pts = _joined(points, rec)
     out = C.create_string_buffer(max(1, rec * n_cols))
     ms = (C.c_double * 2)()
     _setup_call(load().ug_points_combine, device, 1 if g2 else 0, cp, n_cols, ix, co, pts, len(points), out, ms)
@@ -419,9 +425,7 @@ def points_combine(col_ptr, index, coefs, points, g2=False, device=0, timing=Non
 
 def points_scale(scalar, points, device=0, timing=None):
     """ug_points_scale (test tooling): [scalar * P] for G1 records P (64 bytes, all-zero is infinity), scalar an integer below r"""
-    pts = b"".join(points)
-    if len(pts) != 64 * len(points):
-        raise SetupError("setup: a point record of another size")
+    pts = _joined(points, 64)
     out = C.create_string_buffer(max(1, 64 * len(points)))
     ms = (C.c_double * 1)()
     _setup_call(load().ug_points_scale, device, bytes(_le32(scalar, "scalar")), pts, len(points), out, ms)
@@ -458,16 +462,13 @@ def ptau_prepare(ptau, power=0, device=0, validate=1, timings=None):
     Transcripts, beacons and verifying the ceremony's own contributions are out of scope. Refusals raise SetupError ("ptau: ...")."""
     L = load()
     opt = _ptau_prepare_options(power, validate, 0)
-    m = _Mapped(ptau)
-    try:
+    with _Mapped(ptau) as m:
         size = C.c_uint64()
         _setup_call(L.ug_ptau_prepare_size, C.byref(opt), m.address, m.length, C.byref(size))
         out = C.create_string_buffer(max(1, size.value))
         wrote = C.c_uint64()
         ms = (C.c_double * len(PTAU_PREPARE_PHASES))()
         _setup_call(L.ug_ptau_prepare_run, C.byref(opt), m.address, m.length, device, out, size.value, C.byref(wrote), ms)
-    finally:
-        m.close()
     if timings is not None:
         timings.update(zip(PTAU_PREPARE_PHASES, ms))
     return out.raw[:wrote.value]
@@ -481,8 +482,7 @@ def ptau_check(ptau, device=0, validate=1):
     import re
     L = load()
     opt = _ptau_prepare_options(0, validate, 1)
-    m = _Mapped(ptau)
-    try:
+    with _Mapped(ptau) as m:
         _setup_call(L.ug_ptau_prepare_size, C.byref(opt), m.address, m.length, None)
         try:
             _setup_call(L.ug_ptau_prepare_run, C.byref(opt), m.address, m.length, device, None, 0, None, None)
@@ -491,8 +491,6 @@ def ptau_check(ptau, device=0, validate=1):
             if not hit:
                 raise
             return int(hit.group(1)), int(hit.group(2)), str(e)
-    finally:
-        m.close()
     return None
 
 
@@ -502,9 +500,7 @@ def points_intt(points, log_n, g2=False, device=0, timing=None):
     infinity), the rest taken as infinity. Returns N records. device=-1: host threads. timing: a list that receives
     (ms of the 1 / N products, ms of the stages)."""
     rec = 128 if g2 else 64
-    pts = b"".join(points)
-    if len(pts) != rec * len(points):
-        raise SetupError("setup: a point record of another size")
+    pts = _joined(points, rec)
     if not 0 <= int(log_n) <= 28:
         raise SetupError("setup: log_n %d is not in 0 .. 28" % log_n)
     n = 1 << int(log_n)
@@ -549,18 +545,12 @@ def zkey_verify(r1cs, ptau, zkey, device=0, validate=2, timings=None):
         raise SetupError("zkey: validate %d is not 1 or 2" % validate)
     opt.validate = int(validate)
     r1cs = bytes(r1cs)
-    mp, mz = _Mapped(ptau), None
-    try:
-        mz = _Mapped(zkey)
+    with _Mapped(ptau) as mp, _Mapped(zkey) as mz:
         rep = _ZkeyVerifyReport()
         ms = (C.c_double * len(ZKEY_VERIFY_PHASES))()
         err = C.create_string_buffer(1024)
         rc = L.ug_zkey_verify_run(C.byref(opt), r1cs, len(r1cs), mp.address, mp.length, mz.address, mz.length, device, C.byref(rep), ms,
                                   err, len(err) - 1)
-    finally:
-        mp.close()
-        if mz is not None:
-            mz.close()
     msg = err.value.decode(errors="replace")
     if rc not in (0, UG_ZKEY_INVALID):
         raise SetupError(msg)

@@ -23,6 +23,9 @@ struct HipError : public std::runtime_error {
 
 #define UG_KERNEL_CHECK() UG_HIP(hipGetLastError())
 
+// blocks of `block` lanes that cover n
+inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
+
 // An owned HIP event (move-only); timing = false: an ordering-only event (hipEventDisableTiming). A default one is empty.
 struct Event {
     hipEvent_t e = nullptr;

@@ -61,6 +61,15 @@ const Section& BinFile::find(uint32_t id, uint32_t pos) const {
 const uint8_t* BinFile::sectionData(uint32_t id, uint32_t pos) const { return find(id, pos).start; }
 uint64_t BinFile::sectionSize(uint32_t id, uint32_t pos) const { return find(id, pos).size; }
 
+std::unique_ptr<BinFile> openBinFile(const void* data, uint64_t size, const char* type, const std::string& prefix, const char* nullMessage) {
+    if (!data) throw std::invalid_argument(prefix + nullMessage);
+    try {
+        return std::unique_ptr<BinFile>(new BinFile(data, size, type, 1));
+    } catch (const std::exception& e) {
+        throw std::invalid_argument(prefix + e.what());
+    }
+}
+
 // ---- FileMap ---------------------------------------------------------------------------------------------
 FileMap::FileMap(const std::string& path) {
     fd_ = open(path.c_str(), O_RDONLY);

@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -33,6 +34,10 @@ private:
     std::map<uint32_t, std::vector<Section>> sections_;
     std::vector<std::pair<uint32_t, Section>> order_;
 };
+
+// A version-1 BinFile of `type` over (data, size) for an interface whose messages carry the prefix of the file they are about:
+// a null buffer is refused as prefix + nullMessage, the container's own errors are rethrown as prefix + their text.
+std::unique_ptr<BinFile> openBinFile(const void* data, uint64_t size, const char* type, const std::string& prefix, const char* nullMessage);
 
 class FileMap {           // read-only mmap of a whole file
 public:

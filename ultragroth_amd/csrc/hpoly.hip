@@ -365,7 +365,6 @@ __global__ void lookup_clear_vec_kernel(u32* last, const u32* stage, const Looku
 }
 
 template <class T> void dev_alloc(T*& p, size_t bytes) { if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
-inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
 
 }  // namespace
 

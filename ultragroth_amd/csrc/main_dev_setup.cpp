@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "cli_util.hpp"
 #include "host_util.hpp"
 #include "json_min.hpp"
 #include "../../include/ultragroth_hip.h"
@@ -51,11 +52,6 @@ std::vector<uint32_t> listOf(const ugv::JVal& v, const char* what) {
     for (const ugv::JVal& e : v.arr) out.push_back(numberOf(e, what));
     return out;
 }
-void writeFile(const std::string& path, const void* data, size_t n) {
-    std::ofstream f(path, std::ios::binary);
-    f.write((const char*)data, (std::streamsize)n);
-    if (!f) throw std::runtime_error("cannot write " + path);
-}
 
 }  // namespace
 
@@ -64,27 +60,17 @@ int main(int argc, char** argv) {
     fputs("dev_setup: this makes a TEST key from a known trapdoor. Whoever knows the trapdoor forges proofs: never use it where a proof must mean anything.\n", stderr);
     std::vector<std::string> pos;
     std::string trapdoorPath, ultraPath;
-    unsigned logDomain = 0;
-    for (int i = 1; i < argc; i++) {
-        const std::string a = argv[i];
-        if (a == "--trapdoor" && i + 1 < argc) trapdoorPath = argv[++i];
-        else if (a == "--ultra" && i + 1 < argc) ultraPath = argv[++i];
-        else if (a == "--log-domain" && i + 1 < argc) {
-            char* end = nullptr;
-            const unsigned long v = strtoul(argv[++i], &end, 10);
-            if (!*argv[i] || *end || argv[i][0] == '-' || v > 64) { fputs("Error: --log-domain takes a number\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-            logDomain = (unsigned)v;
-        }
-        else if (a.rfind("--", 0) == 0) { fputs(usage, stderr); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
+    long logDomain = 0;
+    const std::vector<ugcli::Option> options = {ugcli::textOption("--trapdoor", &trapdoorPath), ugcli::textOption("--ultra", &ultraPath),
+                                                ugcli::numberOption("--log-domain", &logDomain, 0, 64, "Error: --log-domain takes a number\n", true)};
+    if (!ugcli::parseArgs(argc, argv, options, usage, pos)) return EXIT_FAILURE;
     if (pos.size() != 3) { fputs("Invalid number of parameters\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
     try {
         ug_setup_options opt;
         memset(&opt, 0, sizeof opt);
         opt.size = sizeof opt;
         opt.protocol = 1;
-        opt.log_domain = logDomain;
+        opt.log_domain = (uint32_t)logDomain;
         uint8_t* vals[6] = {opt.tau, opt.alpha, opt.beta, opt.gamma, opt.delta_round, opt.delta_final};
         char message[1024] = {0};
         if (!trapdoorPath.empty()) {
@@ -96,7 +82,7 @@ int main(int argc, char** argv) {
             std::string out = "{\n";
             for (int i = 0; i < 6; i++) out += std::string(" \"") + NAMES[i] + "\": \"" + ughost::toDecimal(vals[i]) + "\"" + (i < 5 ? ",\n" : "\n");
             out += "}\n";
-            writeFile(pos[1] + ".trapdoor.json", out.data(), out.size());
+            ugcli::writeFile(pos[1] + ".trapdoor.json", out.data(), out.size());
             fprintf(stderr, "dev_setup: the trapdoor (the toxic waste of this TEST key) is in %s.trapdoor.json\n", pos[1].c_str());
         }
         std::vector<uint32_t> roundSignals, finalSignals;
@@ -115,14 +101,13 @@ int main(int argc, char** argv) {
         if (ug_setup_size(&opt, r1cs.data(), r1cs.size(), &zbytes, &vmax, message, sizeof(message) - 1) != UG_OK) throw std::runtime_error(message);
         std::vector<uint8_t> zkey(zbytes);
         std::vector<char> vkey(vmax);
-        const char* e = getenv("ULTRAGROTH_DEVICE");
         double ms[UG_SETUP_PHASES];
         uint64_t vlen = 0;
-        if (ug_setup_run(&opt, r1cs.data(), r1cs.size(), e ? atoi(e) : 0, zkey.data(), zkey.size(), &zbytes, vkey.data(), vkey.size(), &vlen, ms, message,
+        if (ug_setup_run(&opt, r1cs.data(), r1cs.size(), (int)ugcli::defaultDevice(), zkey.data(), zkey.size(), &zbytes, vkey.data(), vkey.size(), &vlen, ms, message,
                          sizeof(message) - 1) != UG_OK)
             throw std::runtime_error(message);
-        writeFile(pos[1], zkey.data(), zbytes);
-        writeFile(pos[2], vkey.data(), vlen);
+        ugcli::writeFile(pos[1], zkey.data(), zbytes);
+        ugcli::writeFile(pos[2], vkey.data(), vlen);
         printf("test key written: %llu bytes (parse %.1f | lagrange %.1f | products %.1f | G1 %.1f | G2 %.1f | assembly %.1f ms)\n",
                (unsigned long long)zbytes, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
         return EXIT_SUCCESS;

@@ -18,18 +18,11 @@
 #include <system_error>
 #include <unistd.h>
 #include <vector>
+#include "cli_util.hpp"
 #include "host_util.hpp"
 #include "../../include/ultragroth_hip.h"
 
 namespace {
-
-bool numberArg(const char* s, long lo, long hi, long& out) {
-    char* end = nullptr;
-    const long v = strtol(s, &end, 10);
-    if (!*s || *end || v < lo || v > hi) return false;
-    out = v;
-    return true;
-}
 
 // true when both paths name one existing file: creating the output would truncate the input under its own mapping
 bool sameFile(const std::string& a, const std::string& b) {
@@ -74,21 +67,12 @@ int main(int argc, char** argv) {
     const char* usage = "Usage: ptau_prepare <in.ptau> <out.ptau> [--power p] [--validate 0|1|2] [--device d]\n"
                         "       ptau_prepare --check <prepared.ptau> [--validate 0|1|2] [--device d]\n";
     std::vector<std::string> pos;
-    long power = 0, validate = 1, device = 0;
+    long power = 0, validate = 1, device = ugcli::defaultDevice();
     bool check = false;
-    if (const char* e = getenv("ULTRAGROTH_DEVICE")) device = atoi(e);
-    for (int i = 1; i < argc; i++) {
-        const std::string a = argv[i];
-        if (a == "--check") check = true;
-        else if (a == "--power" && i + 1 < argc) {
-            if (!numberArg(argv[++i], 1, 28, power)) { fputs("Error: --power takes a power from 1 to 28\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-        } else if (a == "--validate" && i + 1 < argc) {
-            if (!numberArg(argv[++i], 0, 2, validate)) { fputs("Error: --validate takes 0, 1 or 2\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-        } else if (a == "--device" && i + 1 < argc) {
-            if (!numberArg(argv[++i], -1, 1024, device)) { fputs("Error: --device takes a device number, or -1 for host threads\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-        } else if (a.rfind("--", 0) == 0) { fputs(usage, stderr); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
+    const std::vector<ugcli::Option> options = {ugcli::flagOption("--check", &check),
+                                                ugcli::numberOption("--power", &power, 1, 28, "Error: --power takes a power from 1 to 28\n"),
+                                                ugcli::validateOption(&validate, 0, "Error: --validate takes 0, 1 or 2\n"), ugcli::deviceOption(&device)};
+    if (!ugcli::parseArgs(argc, argv, options, usage, pos)) return EXIT_FAILURE;
     if (pos.size() != (check ? 1u : 2u)) { fputs("Invalid number of parameters\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
     try {
         ug_ptau_prepare_options opt;

@@ -9,48 +9,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "cli_util.hpp"
 #include "host_util.hpp"
 #include "../../include/ultragroth_hip.h"
-
-namespace {
-
-bool numberArg(const char* s, long lo, long hi, long& out) {
-    char* end = nullptr;
-    const long v = strtol(s, &end, 10);
-    if (!*s || *end || v < lo || v > hi) return false;
-    out = v;
-    return true;
-}
-void writeFile(const std::string& path, const void* data, size_t n) {
-    std::ofstream f(path, std::ios::binary);
-    f.write((const char*)data, (std::streamsize)n);
-    if (!f) throw std::runtime_error("cannot write " + path);
-}
-
-}  // namespace
 
 int main(int argc, char** argv) {
     const char* usage = "Usage: zkey_new <circuit.r1cs> <prepared.ptau> <out.zkey> <out_vkey.json> [--delta draw|<file>] [--log-domain n] [--validate 0|1|2] [--device d]\n";
     std::vector<std::string> pos;
     std::string delta;
-    long logDomain = 0, validate = 1, device = 0;
-    if (const char* e = getenv("ULTRAGROTH_DEVICE")) device = atoi(e);
-    for (int i = 1; i < argc; i++) {
-        const std::string a = argv[i];
-        if (a == "--delta" && i + 1 < argc) delta = argv[++i];
-        else if (a == "--log-domain" && i + 1 < argc) {
-            if (!numberArg(argv[++i], 0, 64, logDomain)) { fputs("Error: --log-domain takes a number\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-        } else if (a == "--validate" && i + 1 < argc) {
-            if (!numberArg(argv[++i], 0, 2, validate)) { fputs("Error: --validate takes 0, 1 or 2\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-        } else if (a == "--device" && i + 1 < argc) {
-            if (!numberArg(argv[++i], -1, 1024, device)) { fputs("Error: --device takes a device number, or -1 for host threads\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
-        } else if (a.rfind("--", 0) == 0) { fputs(usage, stderr); return EXIT_FAILURE; }
-        else pos.push_back(a);
-    }
+    long logDomain = 0, validate = 1, device = ugcli::defaultDevice();
+    const std::vector<ugcli::Option> options = {ugcli::textOption("--delta", &delta),
+                                                ugcli::numberOption("--log-domain", &logDomain, 0, 64, "Error: --log-domain takes a number\n"),
+                                                ugcli::validateOption(&validate, 0, "Error: --validate takes 0, 1 or 2\n"), ugcli::deviceOption(&device)};
+    if (!ugcli::parseArgs(argc, argv, options, usage, pos)) return EXIT_FAILURE;
     if (pos.size() != 4) { fputs("Invalid number of parameters\n", stderr); fputs(usage, stderr); return EXIT_FAILURE; }
     try {
         ug_setup_ptau_options opt;
@@ -85,8 +59,8 @@ int main(int argc, char** argv) {
         volatile uint8_t* w = opt.delta;
         for (int i = 0; i < 32; i++) w[i] = 0;
         if (rc != UG_OK) throw std::runtime_error(message);
-        writeFile(pos[2], zkey.data(), zbytes);
-        writeFile(pos[3], vkey.data(), vlen);
+        ugcli::writeFile(pos[2], zkey.data(), zbytes);
+        ugcli::writeFile(pos[3], vkey.data(), vlen);
         printf("key written: %llu bytes (parse %.1f | point check %.1f | G1 combinations %.1f | G2 combination %.1f | delta %.1f | assembly %.1f ms)\n",
                (unsigned long long)zbytes, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
         return EXIT_SUCCESS;

@@ -12,35 +12,16 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "cli_util.hpp"
 #include "host_util.hpp"
 #include "../../include/ultragroth_hip.h"
-
-namespace {
-
-bool numberArg(const char* s, long lo, long hi, long& out) {
-    char* end = nullptr;
-    const long v = strtol(s, &end, 10);
-    if (!*s || *end || v < lo || v > hi) return false;
-    out = v;
-    return true;
-}
-
-}  // namespace
 
 int main(int argc, char** argv) {
     const char* usage = "Usage: zkey_verify <circuit.r1cs> <prepared.ptau> <key.zkey> [--validate 1|2] [--device d]\n";
     std::vector<std::string> pos;
-    long validate = 2, device = 0;
-    if (const char* e = getenv("ULTRAGROTH_DEVICE")) device = atoi(e);
-    for (int i = 1; i < argc; i++) {
-        const std::string a = argv[i];
-        if (a == "--validate" && i + 1 < argc) {
-            if (!numberArg(argv[++i], 1, 2, validate)) { fputs("Error: --validate takes 1 or 2\n", stderr); fputs(usage, stderr); return 2; }
-        } else if (a == "--device" && i + 1 < argc) {
-            if (!numberArg(argv[++i], -1, 1024, device)) { fputs("Error: --device takes a device number, or -1 for host threads\n", stderr); fputs(usage, stderr); return 2; }
-        } else if (a.rfind("--", 0) == 0) { fputs(usage, stderr); return 2; }
-        else pos.push_back(a);
-    }
+    long validate = 2, device = ugcli::defaultDevice();
+    const std::vector<ugcli::Option> options = {ugcli::validateOption(&validate, 1, "Error: --validate takes 1 or 2\n"), ugcli::deviceOption(&device)};
+    if (!ugcli::parseArgs(argc, argv, options, usage, pos)) return 2;
     if (pos.size() != 3) { fputs("Invalid number of parameters\n", stderr); fputs(usage, stderr); return 2; }
     try {
         ug_zkey_verify_options opt;

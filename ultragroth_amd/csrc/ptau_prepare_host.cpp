@@ -1,9 +1,9 @@
-// ptau_prepare.cpp -- preparing a powers-of-tau file for phase 2 (include/ultragroth_hip.h: ug_ptau_prepare_*, ug_points_intt):
+// ptau_prepare_host.cpp -- preparing a powers-of-tau file for phase 2 (include/ultragroth_hip.h: ug_ptau_prepare_*, ug_points_intt):
 // sections 12 - 15, the Lagrange forms, from sections 2 - 5, the powers; and the check that a file's sections 12 - 15 are those of
 // its own powers, which ug_setup_ptau_run takes on trust. What `snarkjs powersoftau prepare phase2` does. Out of scope:
 // contribution transcripts, beacons, verifying the ceremony's own contributions.
 //
-// The reader is host_util.cpp's (loadPtauHeader, loadPtauPowers, loadPtauLagrange), the point check is setup_ptau.cpp's. The one
+// The reader is host_util.cpp's (loadPtauHeader, loadPtauPowers, loadPtauLagrange), the point check is point_check.cpp's. The one
 // heavy step, an inverse transform whose elements are points, sits behind Backend::intt: host threads (setup_host.cpp) or kernels
 // (ptau_prepare.hip). A level p is one call of it over the first 2^p records; sections 12, 14 and 15 of a level go in one call.
 #include "setup_host.hpp"
@@ -37,21 +37,14 @@ struct Prepared {
 };
 
 void checkOptions(const ug_ptau_prepare_options* o) {
-    if (!o) throw SetupError("null options");
-    if (o->size != sizeof(ug_ptau_prepare_options)) throw SetupError("options struct of another size (" + std::to_string(o->size) + ")");
-    if (o->validate > 2) throw SetupError("validate " + std::to_string(o->validate) + " is not 0, 1 or 2");
+    checkOptionsHead<SetupError>(o, 0, 2, "0, 1 or 2");
     if (o->mode > 1) throw SetupError("mode " + std::to_string(o->mode) + " is not 0 or 1");
 }
 
 // every rule that needs no point
 void plan(const ug_ptau_prepare_options* opt, const void* ptau, u64 ptauSize, std::unique_ptr<BinFile>& f, Prepared& p) {
     checkOptions(opt);
-    if (!ptau) throw PtauError("null ptau buffer");
-    try {
-        f.reset(new BinFile(ptau, ptauSize, "ptau", 1));
-    } catch (const std::exception& e) {
-        throw PtauError(e.what());
-    }
+    f = openBinFile(ptau, ptauSize, "ptau", "ptau: ", "null ptau buffer");
     p.hdr = loadPtauHeader(*f);
     if (opt->mode == 1 && opt->power && opt->power != p.hdr.power)
         throw PtauError("power " + std::to_string(opt->power) + ": a check is of the file's own power " + std::to_string(p.hdr.power));
@@ -81,14 +74,10 @@ void plan(const ug_ptau_prepare_options* opt, const void* ptau, u64 ptauSize, st
     p.total = at;
 }
 
-void put32(uint8_t*& o, u32 v) { memcpy(o, &v, 4); o += 4; }
-void put64(uint8_t*& o, u64 v) { memcpy(o, &v, 8); o += 8; }
-
 // the container and every copied section; the header's power is the cut one
 void writeKept(const Prepared& p, uint8_t* out) {
     uint8_t* o = out;
-    memcpy(o, "ptau", 4); o += 4;
-    put32(o, 1); put32(o, (u32)p.kept.size() + 4);
+    putBytes(o, "ptau", 4); put32(o, 1); put32(o, (u32)p.kept.size() + 4);
     bool headerDone = false;
     for (const auto& s : p.kept) {
         put32(o, s.first); put64(o, s.second.size);
@@ -116,9 +105,8 @@ u64 firstMismatch(const uint8_t* a, const uint8_t* b, u64 n, u64 rec) {
 
 u64 runPrepare(const ug_ptau_prepare_options* opt, const void* ptau, u64 ptauSize, int device, uint8_t* out, u64 outCap, double ms[PREP_PHASES],
                bool sizeOnly) {
-    double t = nowMs();
-    auto lap = [&](int phase) { const double n = nowMs(); ms[phase] += n - t; t = n; };
     for (int i = 0; i < PREP_PHASES; i++) ms[i] = 0;
+    PhaseClock clock(ms);
     std::unique_ptr<BinFile> f;
     Prepared p;
     plan(opt, ptau, ptauSize, f, p);
@@ -133,17 +121,17 @@ u64 runPrepare(const ug_ptau_prepare_options* opt, const void* ptau, u64 ptauSiz
     std::unique_ptr<Backend> owned;
     Backend& be = backendFor(device, owned);
     if (!check) writeKept(p, out);
-    lap(0);
+    clock.lap(0);
 
     const u64 n = p.pw.n;
     {
-        const PtauPointCheck pointCheck(device, (int)opt->validate);
+        const PointCheck pointCheck(device, (int)opt->validate);
         pointCheck(false, p.pw.tau1, 2 * n - 1, 2, 0, 1);
         pointCheck(true, p.pw.tau2, n, 3, 0, 1);
         pointCheck(false, p.pw.alphaTau1, n, 4, 0, 1);
         pointCheck(false, p.pw.betaTau1, n, 5, 0, 1);
     }
-    lap(1);
+    clock.lap(1);
 
     // where a level's records go: the output's sections, or (a check) a scratch level that is compared and dropped
     u64 bad[4] = {~0ull, ~0ull, ~0ull, ~0ull};   // the first mismatch of each section
@@ -162,7 +150,7 @@ u64 runPrepare(const ug_ptau_prepare_options* opt, const void* ptau, u64 ptauSiz
         compareMs += nowMs() - t0;
     };
     auto lapLevels = [&](int phase) {
-        lap(phase);
+        clock.lap(phase);
         ms[phase] -= compareMs; ms[PREP_PHASES - 1] += compareMs;
         compareMs = 0;
     };
@@ -196,12 +184,8 @@ u64 runPrepare(const ug_ptau_prepare_options* opt, const void* ptau, u64 ptauSiz
     }
     lapLevels(3);
     for (int sec = 1; sec < 4; sec++) refuse(sec);
-    lap(4);
+    clock.lap(4);
     return check ? 0 : p.total;
-}
-
-std::string prefixed(const std::string& m) {
-    return m.rfind("setup: ", 0) == 0 || m.rfind("ptau: ", 0) == 0 ? m : "setup: " + m;
 }
 
 }  // namespace
@@ -211,45 +195,39 @@ std::string prefixed(const std::string& m) {
 // =====================================================================================================================
 using namespace ughost::setup;
 
-#define PREP_TRY try {
-#define PREP_CATCH                                                                         \
-    } catch (std::exception& e) { copyErr(error_msg, error_msg_maxsize, prefixed(e.what()).c_str()); return UG_ERROR; } \
-    catch (...) { copyErr(error_msg, error_msg_maxsize, "setup: unknown error"); return UG_ERROR; }   \
-    return UG_OK;
-
 extern "C" {
 
 int ug_ptau_prepare_size(const ug_ptau_prepare_options* opt, const void* ptau, uint64_t ptau_size, uint64_t* out_bytes, char* error_msg,
                          unsigned long long error_msg_maxsize) {
-    PREP_TRY
-    double ms[PREP_PHASES];
-    const u64 total = runPrepare(opt, ptau, ptau_size, -1, nullptr, 0, ms, true);
-    if (out_bytes) *out_bytes = total;
-    PREP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        double ms[PREP_PHASES];
+        const u64 total = runPrepare(opt, ptau, ptau_size, -1, nullptr, 0, ms, true);
+        if (out_bytes) *out_bytes = total;
+    });
 }
 
 int ug_ptau_prepare_run(const ug_ptau_prepare_options* opt, const void* ptau, uint64_t ptau_size, int device, void* out, uint64_t out_capacity,
                         uint64_t* out_bytes, double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize) {
-    PREP_TRY
-    double ms[PREP_PHASES];
-    const u64 total = runPrepare(opt, ptau, ptau_size, device, (uint8_t*)out, out_capacity, ms, false);
-    if (out_bytes) *out_bytes = total;
-    if (phase_ms) for (int i = 0; i < PREP_PHASES; i++) phase_ms[i] = ms[i];
-    PREP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        double ms[PREP_PHASES];
+        const u64 total = runPrepare(opt, ptau, ptau_size, device, (uint8_t*)out, out_capacity, ms, false);
+        if (out_bytes) *out_bytes = total;
+        if (phase_ms) for (int i = 0; i < PREP_PHASES; i++) phase_ms[i] = ms[i];
+    });
 }
 
 int ug_points_intt(int device, int g2, int log_n, const void* points, uint64_t n_given, void* out, double* kernel_ms, char* error_msg,
                    unsigned long long error_msg_maxsize) {
-    PREP_TRY
-    if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
-    if (log_n < 0 || (u32)log_n > MAX_INTT_LOG) throw SetupError("log_n " + std::to_string(log_n) + " is not in 0 .. " + std::to_string(MAX_INTT_LOG));
-    if (n_given > (1ull << log_n)) throw SetupError(std::to_string(n_given) + " points are more than 2^" + std::to_string(log_n));
-    if (!out || (n_given && !points)) throw SetupError("null buffer");
-    const uint8_t* in[1] = {(const uint8_t*)points};
-    uint8_t* o[1] = {(uint8_t*)out};
-    std::unique_ptr<Backend> owned;
-    backendFor(device, owned).intt(g2 != 0, log_n, 1, in, n_given, o, kernel_ms);
-    PREP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
+        if (log_n < 0 || (u32)log_n > MAX_INTT_LOG) throw SetupError("log_n " + std::to_string(log_n) + " is not in 0 .. " + std::to_string(MAX_INTT_LOG));
+        if (n_given > (1ull << log_n)) throw SetupError(std::to_string(n_given) + " points are more than 2^" + std::to_string(log_n));
+        if (!out || (n_given && !points)) throw SetupError("null buffer");
+        const uint8_t* in[1] = {(const uint8_t*)points};
+        uint8_t* o[1] = {(uint8_t*)out};
+        std::unique_ptr<Backend> owned;
+        backendFor(device, owned).intt(g2 != 0, log_n, 1, in, n_given, o, kernel_ms);
+    });
 }
 
 }  // extern "C"

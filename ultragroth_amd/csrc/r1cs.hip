@@ -13,8 +13,6 @@ namespace ug {
 
 namespace {
 
-inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
-
 // plain coefficients (as the file has them, below r) -> coef * 2^522, packed, in place: from_normal gives coef * 2^261 and the
 // product with r2 = 2^522 another factor 2^261 (a zkey's section 4 stores coef * 2^512 instead: coef_gather_kernel, hpoly.hip)
 __global__ void r1cs_coef_kernel(u32* val, u64 n) {

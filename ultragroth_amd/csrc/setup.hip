@@ -16,7 +16,6 @@
 #include "stream_timer.hpp"
 #include "setup_host.hpp"
 
-#include <chrono>
 #include <memory>
 
 namespace ug {
@@ -315,7 +314,6 @@ FrWords words_of(const Fr& a) {
     pack256(w.w, a);
     return w;
 }
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 int env_window(const char* name, int fallback) {
     const char* e = getenv(name);                // tuning knob: every width in range gives the same bytes
     const int v = e ? atoi(e) : 0;
@@ -388,7 +386,7 @@ public:
     void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>& pieces, uint8_t* a, uint8_t* b1, uint8_t* b2, uint8_t* k,
                 uint8_t* h, double ms[PHASES]) override {
         const u64 N = p.N, M = p.nVars;
-        double t0 = now_ms();
+        double t0 = nowMs();
         // upload: the column index, coefficients to device form
         DevBuf<u32> colPtr[3], row[3], val[3];
         ColDev cd;
@@ -411,7 +409,7 @@ public:
         UG_HIP(hipMemcpyAsync(cls.p, p.cls.data(), M, hipMemcpyHostToDevice, stream_));
         DevBuf<u32> lag(N * 8), lagCoset(N * 8), sa(M * 8), sb(M * 8), sk(M * 8), sh(N * 8);
         UG_HIP(hipStreamSynchronize(stream_));
-        ms[0] += now_ms() - t0;
+        ms[0] += nowMs() - t0;
 
         TimeSink sinks[4];
         {
@@ -467,14 +465,14 @@ public:
         }
         timer_.resolve();
         for (int i = 0; i < 4; i++) ms[1 + i] += sinks[i].ms;
-        t0 = now_ms();
+        t0 = nowMs();
         UG_HIP(hipMemcpyAsync(a, oa.p, M * 64, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipMemcpyAsync(b1, ob1.p, M * 64, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipMemcpyAsync(b2, ob2.p, M * 128, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipMemcpyAsync(k, ok.p, M * 64, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipMemcpyAsync(h, oh.p, N * 64, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipStreamSynchronize(stream_));
-        ms[5] += now_ms() - t0;
+        ms[5] += nowMs() - t0;
     }
 
 private:

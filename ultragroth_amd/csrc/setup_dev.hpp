@@ -9,8 +9,6 @@
 namespace ug {
 namespace sdev {
 
-inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
-
 // compile-time loops: every index is a constant, so per-lane arrays stay in registers (a `#pragma unroll` the optimizer
 // declines leaves them indexed at run time, i.e. in scratch)
 template <int I, int N> struct Static {

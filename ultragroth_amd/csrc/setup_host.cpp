@@ -458,13 +458,12 @@ public:
     }
     void points(const Plan& p, const ColMatrix cm[3], const std::vector<Piece>&, uint8_t* a, uint8_t* b1, uint8_t* b2, uint8_t* k,
                 uint8_t* h, double ms[PHASES]) override {
-        double t = nowMs();
-        auto lap = [&](int phase) { const double n = nowMs(); ms[phase] += n - t; t = n; };
+        PhaseClock clock(ms);
         const u64 N = p.N, M = p.nVars;
         std::vector<uint8_t> lag(N * 32), lagCoset(N * 32);
         lagrange(p.logN, p.x[0], p.lagScale[0], p.omega, lag.data());
         lagrange(p.logN, p.x[1], p.lagScale[1], p.omega, lagCoset.data());
-        lap(1);
+        clock.lap(1);
         // the transposed products: one wire at a time over its column (a long column stays with one thread here: the pieces
         // are the device's answer to a lane that would otherwise walk a million terms alone)
         std::vector<uint8_t> sa(M * 32), sb(M * 32), sk(M * 32), sh(N * 32);
@@ -486,14 +485,14 @@ public:
         parallelFor(N, 4096, [&](u64 lo, u64 hi) {
             for (u64 i = lo; i < hi; i++) frToPlain(&sh[i * 32], frMul(frFromPlain(&lagCoset[i * 32]), p.hScale));
         });
-        lap(2);
+        clock.lap(2);
         hostGeneratorMul<Fq>(sa.data(), M, a);
         hostGeneratorMul<Fq>(sb.data(), M, b1);
         hostGeneratorMul<Fq>(sk.data(), M, k);
         hostGeneratorMul<Fq>(sh.data(), N, h);
-        lap(3);
+        clock.lap(3);
         hostGeneratorMul<Fq2>(sb.data(), M, b2);
-        lap(4);
+        clock.lap(4);
     }
 };
 
@@ -628,7 +627,7 @@ void mergedRow(const R1csMatrix& m, u32 k, std::vector<CoefTerm>& out) {
 // per piece of 4096 rows: the records of the constraint rows (the public rows add nPublic + 1 at the end)
 constexpr u64 COEF_GRAIN = 4096;
 }  // namespace
-void countCoefs(const R1cs& cs, std::vector<u64>& perPiece) {
+u64 countCoefs(const R1cs& cs, std::vector<u64>& perPiece) {
     const u64 rows = cs.hdr.nConstraints;
     perPiece.assign((size_t)((rows + COEF_GRAIN - 1) / COEF_GRAIN), 0);
     parallelFor(rows, COEF_GRAIN, [&](u64 lo, u64 hi) {
@@ -638,6 +637,9 @@ void countCoefs(const R1cs& cs, std::vector<u64>& perPiece) {
             for (int m = 0; m < 2; m++) { mergedRow(cs.m[m], (u32)k, t); n += t.size(); }
         perPiece[(size_t)(lo / COEF_GRAIN)] = n;
     });
+    u64 total = 0;
+    for (u64 n : perPiece) total += n;
+    return total;
 }
 namespace {
 void putCoef(uint8_t* o, u32 m, u32 row, u32 wire, const Fr& v) {
@@ -693,14 +695,6 @@ Layout makeLayout(const Plan& p, u64 nCoefs) {
 
 namespace {
 
-const uint8_t BN254_Q_BYTES[32] = {
-    0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
-    0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-
-void put32(uint8_t*& o, u32 v) { memcpy(o, &v, 4); o += 4; }
-void put64(uint8_t*& o, u64 v) { memcpy(o, &v, 8); o += 8; }
-void putBytes(uint8_t*& o, const void* s, size_t n) { memcpy(o, s, n); o += n; }
-
 // ---- verification key ----
 std::string fqDecimal(const uint8_t* mont) {
     u32 w[8], plain[8];
@@ -709,9 +703,7 @@ std::string fqDecimal(const uint8_t* mont) {
     return toDecimal((const uint8_t*)plain);
 }
 std::string jsonG1(const uint8_t* rec) {
-    bool zero = true;
-    for (int i = 0; i < 64; i++) zero &= rec[i] == 0;
-    if (zero) return "[\"0\", \"1\", \"0\"]";
+    if (allZero(rec, 64)) return "[\"0\", \"1\", \"0\"]";
     return "[\"" + fqDecimal(rec) + "\", \"" + fqDecimal(rec + 32) + "\", \"1\"]";
 }
 std::string jsonG2(const uint8_t* rec) {
@@ -735,12 +727,6 @@ std::string vkeyJson(const Plan& p, const HeaderPoints& hp, const uint8_t* ic) {
     s += "\n ]";
     if (p.ultra) s += ",\n \"IC_rand\": " + jsonG1(ic + (size_t)p.randIndx * 64);
     return s + "\n}\n";
-}
-
-
-// every message of this interface starts with "setup: ", or with "r1cs: " when the loader wrote it
-std::string prefixed(const std::string& m) {
-    return m.rfind("setup: ", 0) == 0 || m.rfind("r1cs: ", 0) == 0 ? m : "setup: " + m;
 }
 
 }  // namespace
@@ -790,6 +776,26 @@ void copyErr(char* dst, unsigned long long max, const char* msg) {
     dst[max - 1] = 0;
 }
 
+std::string underPrefix(const PrefixRule& rule, const std::string& m) {
+    for (const char* k : rule.keep)
+        if (k && m.rfind(k, 0) == 0) return m;
+    return rule.put + (rule.dropSetup && m.rfind("setup: ", 0) == 0 ? m.substr(7) : m);
+}
+
+void copyVkey(const std::string& vkey, char* dst, u64 capacity, uint64_t* bytes) {
+    if (bytes) *bytes = vkey.size();
+    if (!dst) return;
+    if (capacity < vkey.size() + 1) throw SetupError("the verification-key buffer is too small: " + std::to_string(vkey.size() + 1) + " bytes are needed");
+    memcpy(dst, vkey.c_str(), vkey.size() + 1);
+}
+
+void drawNonZeroScalar(uint8_t le[32]) {
+    do {
+        randomBytes(le, 32);
+        le[31] &= 0x3f;
+    } while (allZero(le, 32) || !belowR(le));
+}
+
 Backend& backendFor(int device, std::unique_ptr<Backend>& owned) {
     if (device < 0) return hostBackend();
     if (!deviceBackendFactory) throw SetupError("this program has no device path: use device = -1 (host threads)");
@@ -798,8 +804,7 @@ Backend& backendFor(int device, std::unique_ptr<Backend>& owned) {
 }
 
 void loadCircuit(const void* r1cs, u64 size, std::unique_ptr<BinFile>& f, R1csHeader& h) {
-    if (!r1cs) throw SetupError("null r1cs buffer");
-    f.reset(new BinFile(r1cs, size, "r1cs", 1));
+    f = openBinFile(r1cs, size, "r1cs", "setup: ", "null r1cs buffer");
     h = loadR1csHeader(*f);
 }
 
@@ -815,7 +820,7 @@ void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vect
     uint8_t* o = zkey + lay.offsetOf(1);
     put32(o, p.ultra ? 1337 : 1);
     o = zkey + lay.offsetOf(2);
-    put32(o, 32); putBytes(o, BN254_Q_BYTES, 32); put32(o, 32); putBytes(o, BN254_R_BYTES, 32);
+    put32(o, 32); putBytes(o, BN254_Q_LE, 32); put32(o, 32); putBytes(o, BN254_R_BYTES, 32);
     put32(o, p.nVars); put32(o, p.nPublic); put32(o, p.N);
     if (p.ultra) { put32(o, (u32)p.roundSignals.size()); put32(o, (u32)p.finalSignals.size()); put32(o, p.randIndx); }
     putBytes(o, hp.g1[0], 64); putBytes(o, hp.g1[1], 64); putBytes(o, hp.g2[0], 128); putBytes(o, hp.g2[1], 128);
@@ -858,8 +863,8 @@ void generatorWords(bool g2, u32* out) {
 // the whole setup; returns the zkey's size, writes the JSON to vkey
 u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uint8_t* zkey, u64 zkeyCap, std::string* vkey, double ms[PHASES],
         bool sizeOnly, u64* vkeyMax) {
-    double t = nowMs();
     for (int i = 0; i < PHASES; i++) ms[i] = 0;
+    PhaseClock clock(ms);
     std::unique_ptr<BinFile> f;
     R1cs cs;
     loadCircuit(r1cs, size, f, cs.hdr);
@@ -867,10 +872,7 @@ u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uin
     makePlan(opt, cs.hdr, p);                    // (every check of the options before the constraints are walked)
     loadR1cs(*f, cs);
     std::vector<u64> perPiece;
-    countCoefs(cs, perPiece);
-    u64 nCoefs = (u64)p.nPublic + 1;
-    for (u64 n : perPiece) nCoefs += n;
-    const Layout lay = makeLayout(p, nCoefs);
+    const Layout lay = makeLayout(p, (u64)p.nPublic + 1 + countCoefs(cs, perPiece));
     if (vkeyMax) *vkeyMax = vkeyBound(p);
     if (sizeOnly) return lay.total;
     if (!zkey) throw SetupError("null zkey buffer");
@@ -881,14 +883,14 @@ u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uin
     ColMatrix cm[3];
     std::vector<Piece> pieces;
     buildColumns(cs, p, cm, pieces);
-    ms[0] += nowMs() - t;
+    clock.lap(0);
 
     writeContainer(zkey, lay);
     const u64 M = p.nVars;
     std::vector<uint8_t> krec(M * 64);
     be.points(p, cm, pieces, zkey + lay.offsetOf(5), zkey + lay.offsetOf(6), zkey + lay.offsetOf(7), krec.data(),
               zkey + lay.offsetOf(p.ultra ? 12 : 9), ms);
-    t = nowMs();
+    clock.restart();
     // the eight header points, on host threads whatever the backend
     HeaderPoints hp;
     {
@@ -900,7 +902,7 @@ u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uin
         hostBackend().generatorMul(true, sc[0], 4, 0, hp.g2[0], nullptr);
     }
     finishKey(cs, p, lay, perPiece, hp, krec, zkey, vkey);
-    ms[5] += nowMs() - t;
+    clock.lap(5);
     return lay.total;
 }
 
@@ -910,85 +912,66 @@ u64 run(const ug_setup_options* opt, const void* r1cs, u64 size, int device, uin
 // =====================================================================================================================
 using namespace ughost::setup;
 
-#define SETUP_TRY try {
-#define SETUP_CATCH                                                                        \
-    } catch (std::exception& e) { copyErr(error_msg, error_msg_maxsize, prefixed(e.what()).c_str()); return UG_ERROR; } \
-    catch (...) { copyErr(error_msg, error_msg_maxsize, "setup: unknown error"); return UG_ERROR; }   \
-    return UG_OK;
-
 extern "C" {
 
 int ug_setup_draw_trapdoor(ug_setup_options* opt, char* error_msg, unsigned long long error_msg_maxsize) {
-    SETUP_TRY
-    if (!opt) throw SetupError("null options");
-    uint8_t* dst[6] = {opt->tau, opt->alpha, opt->beta, opt->gamma, opt->delta_round, opt->delta_final};
-    for (uint8_t* d : dst) {
-        for (;;) {                               // uniform below r, never 0: 254 random bits, drawn again when out of range
-            ughost::randomBytes(d, 32);
-            d[31] &= 0x3f;
-            bool zero = true;
-            for (int i = 0; i < 32; i++) zero &= d[i] == 0;
-            if (!zero && belowR(d)) break;
-        }
-    }
-    SETUP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        if (!opt) throw SetupError("null options");
+        for (uint8_t* d : {opt->tau, opt->alpha, opt->beta, opt->gamma, opt->delta_round, opt->delta_final}) drawNonZeroScalar(d);
+    });
 }
 
 int ug_setup_size(const ug_setup_options* opt, const void* r1cs, uint64_t r1cs_size, uint64_t* zkey_bytes, uint64_t* vkey_bytes_max,
                   char* error_msg, unsigned long long error_msg_maxsize) {
-    SETUP_TRY
-    double ms[PHASES];
-    u64 vmax = 0;
-    const u64 total = run(opt, r1cs, r1cs_size, -1, nullptr, 0, nullptr, ms, true, &vmax);
-    if (zkey_bytes) *zkey_bytes = total;
-    if (vkey_bytes_max) *vkey_bytes_max = vmax;
-    SETUP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        double ms[PHASES];
+        u64 vmax = 0;
+        const u64 total = run(opt, r1cs, r1cs_size, -1, nullptr, 0, nullptr, ms, true, &vmax);
+        if (zkey_bytes) *zkey_bytes = total;
+        if (vkey_bytes_max) *vkey_bytes_max = vmax;
+    });
 }
 
 int ug_setup_run(const ug_setup_options* opt, const void* r1cs, uint64_t r1cs_size, int device, void* zkey, uint64_t zkey_capacity,
                  uint64_t* zkey_bytes, char* vkey_json, uint64_t vkey_capacity, uint64_t* vkey_bytes, double* phase_ms, char* error_msg,
                  unsigned long long error_msg_maxsize) {
-    SETUP_TRY
-    double ms[PHASES];
-    std::string vkey;
-    const u64 total = run(opt, r1cs, r1cs_size, device, (uint8_t*)zkey, zkey_capacity, &vkey, ms, false, nullptr);
-    if (zkey_bytes) *zkey_bytes = total;
-    if (vkey_bytes) *vkey_bytes = vkey.size();
-    if (vkey_json) {
-        if (vkey_capacity < vkey.size() + 1) throw SetupError("the verification-key buffer is too small: " + std::to_string(vkey.size() + 1) + " bytes are needed");
-        memcpy(vkey_json, vkey.c_str(), vkey.size() + 1);
-    }
-    if (phase_ms) for (int i = 0; i < PHASES; i++) phase_ms[i] = ms[i];
-    SETUP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        double ms[PHASES];
+        std::string vkey;
+        const u64 total = run(opt, r1cs, r1cs_size, device, (uint8_t*)zkey, zkey_capacity, &vkey, ms, false, nullptr);
+        if (zkey_bytes) *zkey_bytes = total;
+        copyVkey(vkey, vkey_json, vkey_capacity, vkey_bytes);
+        if (phase_ms) for (int i = 0; i < PHASES; i++) phase_ms[i] = ms[i];
+    });
 }
 
 int ug_generator_mul(int device, int g2, const void* scalars, uint64_t n, int window, void* out, double* kernel_ms, char* error_msg,
                      unsigned long long error_msg_maxsize) {
-    SETUP_TRY
-    if (n && (!scalars || !out)) throw SetupError("null buffer");
-    if (window && (window < WINDOW_MIN || window > WINDOW_MAX))
-        throw SetupError("window " + std::to_string(window) + " is outside " + std::to_string(WINDOW_MIN) + " .. " + std::to_string(WINDOW_MAX));
-    checkScalars((const uint8_t*)scalars, n);
-    if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
-    if (!n) return UG_OK;
-    std::unique_ptr<Backend> owned;
-    backendFor(device, owned).generatorMul(g2 != 0, (const uint8_t*)scalars, n, window, (uint8_t*)out, kernel_ms);
-    SETUP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        if (n && (!scalars || !out)) throw SetupError("null buffer");
+        if (window && (window < WINDOW_MIN || window > WINDOW_MAX))
+            throw SetupError("window " + std::to_string(window) + " is outside " + std::to_string(WINDOW_MIN) + " .. " + std::to_string(WINDOW_MAX));
+        checkScalars((const uint8_t*)scalars, n);
+        if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
+        if (!n) return;
+        std::unique_ptr<Backend> owned;
+        backendFor(device, owned).generatorMul(g2 != 0, (const uint8_t*)scalars, n, window, (uint8_t*)out, kernel_ms);
+    });
 }
 
 int ug_lagrange_at(int device, int log_n, const void* x, int coset, void* out, char* error_msg, unsigned long long error_msg_maxsize) {
-    SETUP_TRY
-    if (!x || !out) throw SetupError("null buffer");
-    if (log_n < 1 || log_n > MAX_LOG_DOMAIN) throw SetupError("log_n " + std::to_string(log_n) + " is outside 1 .. " + std::to_string(MAX_LOG_DOMAIN));
-    if (!belowR((const uint8_t*)x)) throw SetupError("x is not below the field modulus");
-    Fr v = frFromPlain((const uint8_t*)x);
-    if (coset) v = frMul(v, frInv(rootOfUnity(log_n + 1)));
-    const Fr vN = frPow2k(v, log_n);
-    if (frIsOne(vN)) throw SetupError("x lies in the evaluation domain");
-    const Fr scale = frMul(frSub(vN, ug::fp_one<ug::FrParams>()), frInv(frSmall(1u << log_n)));
-    std::unique_ptr<Backend> owned;
-    backendFor(device, owned).lagrange(log_n, v, scale, rootOfUnity(log_n), (uint8_t*)out);
-    SETUP_CATCH
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        if (!x || !out) throw SetupError("null buffer");
+        if (log_n < 1 || log_n > MAX_LOG_DOMAIN) throw SetupError("log_n " + std::to_string(log_n) + " is outside 1 .. " + std::to_string(MAX_LOG_DOMAIN));
+        if (!belowR((const uint8_t*)x)) throw SetupError("x is not below the field modulus");
+        Fr v = frFromPlain((const uint8_t*)x);
+        if (coset) v = frMul(v, frInv(rootOfUnity(log_n + 1)));
+        const Fr vN = frPow2k(v, log_n);
+        if (frIsOne(vN)) throw SetupError("x lies in the evaluation domain");
+        const Fr scale = frMul(frSub(vN, ug::fp_one<ug::FrParams>()), frInv(frSmall(1u << log_n)));
+        std::unique_ptr<Backend> owned;
+        backendFor(device, owned).lagrange(log_n, v, scale, rootOfUnity(log_n), (uint8_t*)out);
+    });
 }
 
 }  // extern "C"

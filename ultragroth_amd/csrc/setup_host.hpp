@@ -11,7 +11,9 @@
 // The phase-2 setup from a prepared powers-of-tau file (setup_ptau.cpp: ug_setup_ptau_*) shares all of this. It has no scalars
 // to multiply the generator by: its two heavy steps combine POINTS per wire and multiply many points by one scalar, and sit
 // behind the same Backend (combine, scale). The parts of run() it needs are declared at the end of this header.
-// Preparing a .ptau for phase 2 (ptau_prepare.cpp: ug_ptau_prepare_*) has one heavy step, an inverse transform over points: Backend::intt.
+// Preparing a .ptau for phase 2 (ptau_prepare_host.cpp: ug_ptau_prepare_*) has one heavy step, an inverse transform over points: Backend::intt.
+// The key check (zkey_verify_host.cpp) shares the circuit, section 4 and the point check. What all four have in common besides --
+// the guard of the extern "C" entries, the phase clock, the small byte helpers -- is declared at the end of this header.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -97,7 +99,7 @@ public:
                          double* ms) = 0;
     // out[i] = scalar * point[i] over n G1 records; scalar plain, below r; infinity in gives infinity out. ms (may be null): one value
     virtual void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) = 0;
-    // The inverse transform over points that prepares a .ptau (ptau_prepare.cpp). N = 2^logN, omega = 5^((r - 1) / N):
+    // The inverse transform over points that prepares a .ptau (ptau_prepare_host.cpp). N = 2^logN, omega = 5^((r - 1) / N):
     // out[v][k] = (1 / N) sum_j omega^(-j k) in[v][j] for each of the nVec vectors; in[v]: nGiven <= N zkey-format records, the rest
     // of the N taken as infinity; out[v]: N records, which do not overlap any input. ms (may be null): two values, the 1 / N
     // products and the stages (host threads: 0 and the whole)
@@ -143,32 +145,40 @@ void inttTwiddles(int logN, std::vector<u32>& tw);
 void inttScale(int logN, u32 folded[8]);
 // a transform of one point (logN = 0) is the point itself: true when it was done here
 bool inttTrivial(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out);
-// the point check of a .ptau's records through ug_points_check (device >= 0) or on host threads, with the messages of
-// ug_setup_ptau_run: n records of section `id`; record i is the section's record first + stride * i. level 0 checks nothing.
-class PtauPointCheck {
+struct PtauError : public std::invalid_argument {
+    explicit PtauError(const std::string& m) : std::invalid_argument("ptau: " + m) {}
+};
+
+// ---- the point check of a file's records (point_check.cpp; it names the library's device entries, so a host-only program that
+// links it supplies them) ----
+// Through ug_points_check (device >= 0) or on host threads, with the messages of ug_setup_ptau_run: n records of section `id`;
+// record i is the section's record first + stride * i. level 0 checks nothing.
+class PointCheck {
 public:
-    PtauPointCheck(int device, int level);
-    ~PtauPointCheck();
+    PointCheck(int device, int level);
+    ~PointCheck();
     void operator()(bool g2, const uint8_t* rec, u64 n, u32 id, u64 first, u64 stride) const;
-    // the same check for a caller with messages of its own (zkey_verify.cpp): the lowest bad record and the first rule it breaks
+    // the same check for a caller with messages of its own (zkey_verify_host.cpp): the lowest bad record and the first rule it breaks
     ug_point_fault find(bool g2, const uint8_t* rec, u64 n) const;
     static const char* reasonText(int reason);
-    PtauPointCheck(const PtauPointCheck&) = delete;
-    PtauPointCheck& operator=(const PtauPointCheck&) = delete;
+    PointCheck(const PointCheck&) = delete;
+    PointCheck& operator=(const PointCheck&) = delete;
 private:
     int device_, level_;
     ug_ctx* ctx_ = nullptr;
 };
-struct PtauError : public std::invalid_argument {
-    explicit PtauError(const std::string& m) : std::invalid_argument("ptau: " + m) {}
-};
+// H's sources side by side: out[k] = record 2 k + 1 of sl.top, k < sl.n
+void gatherOddTop(const PtauSlices& sl, uint8_t* out);
+// every point a phase-2 setup of sl's domain reads: the four level-n slices, the odd records of the padded level (gathered: hOdd),
+// record 0 of sections 4 and 5, section 6
+void checkSlices(const PointCheck& check, const PtauSlices& sl, const uint8_t* hOdd);
 
 // ---- the parts of a key that do not depend on where its points come from (setup_host.cpp), for setup_ptau.cpp ----
 bool belowR(const uint8_t* le);
 void planSizes(const R1csHeader& h, u32 logDomain, Plan& p);       // nVars .. N and cls (all wires of protocol 1) from the header
 void loadCircuit(const void* r1cs, u64 size, std::unique_ptr<BinFile>& f, R1csHeader& h);
 void buildColumns(const R1cs& cs, const Plan& p, ColMatrix cm[3], std::vector<Piece>& pieces);
-void countCoefs(const R1cs& cs, std::vector<u64>& perPiece);
+u64 countCoefs(const R1cs& cs, std::vector<u64>& perPiece);        // returns the sum of perPiece: the records of the constraint rows
 // section 4's records (44 bytes each, without the count in front): the sum of perPiece for the constraints, then nPublic + 1
 void writeCoefs(const R1cs& cs, const Plan& p, const std::vector<u64>& perPiece, uint8_t* out);
 struct Layout {
@@ -184,8 +194,61 @@ void writeContainer(uint8_t* zkey, const Layout& lay);            // magic, vers
 void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vector<u64>& perPiece, const HeaderPoints& hp,
                const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey);
 Backend& backendFor(int device, std::unique_ptr<Backend>& owned);
-void copyErr(char* dst, unsigned long long max, const char* msg);
+// the verification key's JSON into the caller's buffer (may be null: only the length is reported), with its terminating 0
+void copyVkey(const std::string& vkey, char* dst, u64 capacity, uint64_t* bytes);
+// uniform below r, never 0: 254 random bits, drawn again when out of range
+void drawNonZeroScalar(uint8_t le[32]);
+
+// ---- small helpers of all four host files ----
+inline bool allZero(const uint8_t* p, size_t n) {
+    uint8_t o = 0;
+    for (size_t i = 0; i < n; i++) o |= p[i];
+    return o == 0;
+}
+inline void put32(uint8_t*& o, u32 v) { memcpy(o, &v, 4); o += 4; }
+inline void put64(uint8_t*& o, u64 v) { memcpy(o, &v, 8); o += 8; }
+inline void putBytes(uint8_t*& o, const void* s, size_t n) { memcpy(o, s, n); o += n; }
 double nowMs();
+// phase times: lap(i) adds the time since the last lap (or since restart()) to ms[i]
+class PhaseClock {
+public:
+    explicit PhaseClock(double* ms) : ms_(ms), t_(nowMs()) {}
+    void lap(int phase) { const double n = nowMs(); ms_[phase] += n - t_; t_ = n; }
+    void restart() { t_ = nowMs(); }
+private:
+    double* ms_;
+    double t_;
+};
+// what every options struct starts with: refuses a null pointer, another size, and a `validate` outside lo .. hi ("is not " + words)
+template <class Err, class Opt> void checkOptionsHead(const Opt* o, u32 lo, u32 hi, const char* words) {
+    if (!o) throw Err("null options");
+    if (o->size != sizeof(Opt)) throw Err("options struct of another size (" + std::to_string(o->size) + ")");
+    if (o->validate < lo || o->validate > hi) throw Err("validate " + std::to_string(o->validate) + " is not " + words);
+}
+
+// ---- the guard of every extern "C" entry ----
+// A path's prefix rule: a message that starts with one of `keep` stays as it is; any other gets `put` in front, after a leading
+// "setup: " is dropped where `dropSetup` says so (the key check reports a shared helper's refusal under the file it read).
+struct PrefixRule {
+    const char* put;
+    const char* keep[3];
+    bool dropSetup;
+};
+constexpr PrefixRule SETUP_RULE = {"setup: ", {"setup: ", "r1cs: ", "ptau: "}, false};
+std::string underPrefix(const PrefixRule& rule, const std::string& m);
+void copyErr(char* dst, unsigned long long max, const char* msg);
+// runs body(); an exception becomes UG_ERROR with its message, under the rule, in error_msg
+template <class Body> int guarded(const PrefixRule& rule, char* error_msg, unsigned long long error_msg_maxsize, Body&& body) {
+    try {
+        body();
+        return UG_OK;
+    } catch (std::exception& e) {
+        copyErr(error_msg, error_msg_maxsize, underPrefix(rule, e.what()).c_str());
+    } catch (...) {
+        copyErr(error_msg, error_msg_maxsize, (std::string(rule.put) + "unknown error").c_str());
+    }
+    return UG_ERROR;
+}
 
 }  // namespace setup
 }  // namespace ughost

@@ -1,4 +1,4 @@
-// zkey_verify.hip -- the device side of the key check (zkey_verify.cpp, include/ultragroth_hip.h: ug_zkey_verify_run, ug_r1cs_fold).
+// zkey_verify.hip -- the device side of the key check (zkey_verify_host.cpp, include/ultragroth_hip.h: ug_zkey_verify_run, ug_r1cs_fold).
 //
 // Two kernels are new. The fold is the witness check's row walk (matvec_walk, dev_common.hpp) with the random weights rho in the
 // witness's place and two sums per matrix, stored as canonical plain integers where ug_schedule_build reads MSM scalars. The
@@ -17,8 +17,6 @@
 namespace ug {
 
 namespace {
-
-inline unsigned grid_for(u64 n, int block) { return (unsigned)((n + block - 1) / block); }
 
 __global__ __launch_bounds__(256) void r1cs_fold_kernel(R1csDev m, const u32* rho, u32 n_public, u32 domain, u32* out) {
     const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -131,15 +129,13 @@ void foldOn(Dev& d, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, u64
 }
 
 void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
-    using ughost::setup::nowMs;
-    double t = nowMs();
-    auto lap = [&](int i) { const double n = nowMs(); st.ms[i] += n - t; t = n; };
+    ughost::setup::PhaseClock clock(st.ms);
     const u64 N = in.N, M = in.M, pub = in.pub;
     Dev d;
     openDevice(d, device);
     foldOn(d, in.r1cs, in.r1csSize, in.rho, M, (uint32_t)(pub - 1), (uint32_t)in.logN, &st.foldKernelMs);
     must(ug_schedule_create(d.c, &d.s));
-    lap(0);
+    clock.lap(0);
 
     // the slices: T, T2, aT, bT stay until the scalar side is done. Scalar i of a schedule built at `first` multiplies record i.
     must(ug_bases_create_g1(d.c, in.T, N, 0, &d.set[0]));
@@ -175,7 +171,7 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
     ug_dvec_destroy(d.fold);
     d.fold = nullptr;
     must(ug_schedule_trim(d.s));
-    lap(1);
+    clock.lap(1);
 
     // the key's sections under rho, one at a time
     must(ug_schedule_build(d.s, d.rho, 0, M));
@@ -201,7 +197,7 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
     } else {
         memset(out.keyC, 0, 64);
     }
-    lap(2);
+    clock.lap(2);
 
     // sigma over H and over the odd records of the padded level: one schedule, two base sets
     must(ug_dvec_create(d.c, N, &d.sigma));
@@ -216,7 +212,7 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
         must(ug_msm_batch(d.c, 2, both, d.s, nullptr, outs));
     }
     d.sample();
-    lap(3);
+    clock.lap(3);
     st.peakDeviceBytes = d.peak;
 }
 

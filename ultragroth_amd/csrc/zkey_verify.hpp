@@ -1,5 +1,5 @@
-// zkey_verify.hpp -- what the check of a Groth16 key against its circuit and powers of tau (zkey_verify.cpp) hands to the code
-// that evaluates the twelve sums of its relations: host threads (zkey_verify.cpp) or the device (zkey_verify.hip).
+// zkey_verify.hpp -- what the check of a Groth16 key against its circuit and powers of tau (zkey_verify_host.cpp) hands to the code
+// that evaluates the twelve sums of its relations: host threads (zkey_verify_host.cpp) or the device (zkey_verify.hip).
 #pragma once
 #include <cstdint>
 #include "host_util.hpp"

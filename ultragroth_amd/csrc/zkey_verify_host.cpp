@@ -1,4 +1,4 @@
-// zkey_verify.cpp -- is this Groth16 key the one its circuit and a prepared powers-of-tau file give under ONE delta?
+// zkey_verify_host.cpp -- is this Groth16 key the one its circuit and a prepared powers-of-tau file give under ONE delta?
 // (include/ultragroth_hip.h: ug_zkey_verify_run, ug_r1cs_fold). No trapdoor and no delta is known here. Out of scope: who
 // contributed -- section 10's transcript, beacons, the .ptau's own ceremony -- and UltraGroth keys.
 //
@@ -43,15 +43,16 @@ struct R1csRefusal : public std::invalid_argument {
     explicit R1csRefusal(const std::string& m) : std::invalid_argument("r1cs: " + m) {}
 };
 
-bool known(const std::string& m) { return m.rfind("r1cs: ", 0) == 0 || m.rfind("ptau: ", 0) == 0 || m.rfind("zkey: ", 0) == 0; }
-std::string stripSetup(const std::string& m) { return m.rfind("setup: ", 0) == 0 ? m.substr(7) : m; }
-// a loader's text under the prefix of the file it read
-std::string under(const char* prefix, const std::string& m) { return known(m) ? m : prefix + stripSetup(m); }
-
-bool allZero(const uint8_t* p, size_t n) {
-    uint8_t o = 0;
-    for (size_t i = 0; i < n; i++) o |= p[i];
-    return o == 0;
+// a loader's text under the prefix of the file it read: a shared helper's "setup: " goes, the three files' own prefixes stay
+constexpr PrefixRule R1CS_RULE = {"r1cs: ", {"r1cs: ", "ptau: ", "zkey: "}, true};
+constexpr PrefixRule ZKEY_RULE = {"zkey: ", {"r1cs: ", "ptau: ", "zkey: "}, true};
+// body() with its refusals under the rule
+template <class Body> void under(const PrefixRule& rule, Body&& body) {
+    try {
+        body();
+    } catch (const std::exception& e) {
+        throw std::invalid_argument(underPrefix(rule, e.what()));
+    }
 }
 
 // ---- the weights: fresh from the OS for every call, never derived from the inputs (as verifier_api.cpp's batch scalars) ----
@@ -128,13 +129,13 @@ void hostMsm(bool g2, const uint8_t* scalars, const uint8_t* points, u64 n, uint
 }
 
 void hostSums(const Inputs& in, const uint8_t* hOdd, Sums& out, SumsStats& st) {
-    double t = nowMs();
-    auto lap = [&](int i) { const double n = nowMs(); st.ms[i] += n - t; t = n; };
+    PhaseClock clock(st.ms);
+    const double t0 = nowMs();
     const u64 N = in.N, M = in.M, pub = in.pub;
     std::vector<uint8_t> f((size_t)N * 32 * 8);
     hostFold(*in.cs, in.rho, (u32)(pub - 1), N, f.data());
-    st.foldKernelMs = nowMs() - t;
-    lap(0);
+    st.foldKernelMs = nowMs() - t0;
+    clock.lap(0);
     auto vec = [&](int v) { return f.data() + (size_t)v * N * 32; };
     hostMsm(false, vec(6), in.T, N, out.aT);
     hostMsm(false, vec(7), in.T, N, out.bT);
@@ -144,16 +145,16 @@ void hostSums(const Inputs& in, const uint8_t* hOdd, Sums& out, SumsStats& st) {
     three.base[0] = in.bT; three.base[1] = in.aT; three.base[2] = in.T;
     hostMsm(false, vec(0), three, out.kPub);
     hostMsm(false, vec(3), three, out.kPriv);
-    lap(1);
+    clock.lap(1);
     hostMsm(false, in.rho, in.a, M, out.keyA);
     hostMsm(false, in.rho, in.b1, M, out.keyB1);
     hostMsm(true, in.rho, in.b2, M, out.keyB2);
     hostMsm(false, in.rho, in.ic, pub, out.keyIC);
     hostMsm(false, in.rho + pub * 32, in.c, M - pub, out.keyC);
-    lap(2);
+    clock.lap(2);
     hostMsm(false, in.sigma, in.h, N, out.keyH);
     hostMsm(false, in.sigma, hOdd, N, out.hP);
-    lap(3);
+    clock.lap(3);
 }
 
 // ---- pairings (pairing.hpp, host threads) ----
@@ -188,14 +189,14 @@ bool samePairing(const G1A& p1, const G2A& q1, const G1A& p2, const G2A& q2) {
 
 // ---- the point check of the key, with ug_zkey_check's messages ----
 const char* const HEADER_NAMES[6] = {"alpha1", "beta1", "beta2", "gamma2", "delta1", "delta2"};
-void checkKeyPoints(const PtauPointCheck& check, const ZkeyHeader& h, const Inputs& in) {
+void checkKeyPoints(const PointCheck& check, const ZkeyHeader& h, const Inputs& in) {
     const uint8_t* hp[6] = {h.alpha1, h.beta1, h.beta2, h.gamma2, h.delta1, h.delta2};
     const bool hg2[6] = {false, false, true, true, false, true};
     for (int i = 0; i < 6; i++) {
         uint8_t rec[128];                        // (the header's points sit at any alignment)
         memcpy(rec, hp[i], hg2[i] ? 128 : 64);
         const ug_point_fault f = check.find(hg2[i], rec, 1);
-        if (f.reason) throw ZkeyError(std::string("header point ") + HEADER_NAMES[i] + ": " + PtauPointCheck::reasonText(f.reason));
+        if (f.reason) throw ZkeyError(std::string("header point ") + HEADER_NAMES[i] + ": " + PointCheck::reasonText(f.reason));
     }
     struct Sec { u32 id; bool g2; const uint8_t* p; u64 n; };
     const Sec secs[6] = {{3, false, in.ic, in.pub}, {5, false, in.a, in.M}, {6, false, in.b1, in.M}, {7, true, in.b2, in.M},
@@ -203,7 +204,7 @@ void checkKeyPoints(const PtauPointCheck& check, const ZkeyHeader& h, const Inpu
     for (const Sec& s : secs) {
         const ug_point_fault f = check.find(s.g2, s.p, s.n);
         if (f.reason)
-            throw ZkeyError("section " + std::to_string(s.id) + " point " + std::to_string(f.index) + ": " + PtauPointCheck::reasonText(f.reason));
+            throw ZkeyError("section " + std::to_string(s.id) + " point " + std::to_string(f.index) + ": " + PointCheck::reasonText(f.reason));
     }
 }
 
@@ -223,43 +224,32 @@ const uint8_t* sectionOf(const BinFile& f, u32 id, u64 need) {
 }
 
 void checkOptions(const ug_zkey_verify_options* o) {
-    if (!o) throw ZkeyError("null options");
-    if (o->size != sizeof(ug_zkey_verify_options)) throw ZkeyError("options struct of another size (" + std::to_string(o->size) + ")");
-    if (o->validate != 1 && o->validate != 2) throw ZkeyError("validate " + std::to_string(o->validate) + " is not 1 or 2");
+    checkOptionsHead<ZkeyError>(o, 1, 2, "1 or 2");
 }
 
 // 0: valid, UG_ZKEY_INVALID: *v says which sections fail; a refusal is an exception
 int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, const void* zkey, u64 zkeySize,
         int device, ug_zkey_verify_report* rep, double ms[PHASES], Verdict& v) {
-    double t = nowMs();
-    auto lap = [&](int phase) { const double n = nowMs(); ms[phase] += n - t; t = n; };
+    PhaseClock clock(ms);
     checkOptions(opt);
     if (device >= 0 && !deviceSums) throw ZkeyError("this program has no device path: use device = -1 (host threads)");
     // ---- every size and header rule of the three files, before the first device byte ----
     std::unique_ptr<BinFile> rf;
     R1cs cs;
-    try {
-        loadCircuit(r1cs, r1csSize, rf, cs.hdr);
-    } catch (const std::exception& e) {
-        throw std::invalid_argument(under("r1cs: ", e.what()));
-    }
+    under(R1CS_RULE, [&] { loadCircuit(r1cs, r1csSize, rf, cs.hdr); });
     const u64 M = cs.hdr.nWires, nPublic = (u64)cs.hdr.nPubOut + cs.hdr.nPubIn, pub = nPublic + 1;
     if (pub > M) throw R1csRefusal("nPubOut + nPubIn + 1 exceeds nWires");
     const u64 rows = (u64)cs.hdr.nConstraints + pub;
 
-    if (!zkey) throw ZkeyError("null zkey buffer");
-    std::unique_ptr<BinFile> zf;
+    const std::unique_ptr<BinFile> zf = openBinFile(zkey, zkeySize, "zkey", "zkey: ", "null zkey buffer");
     ZkeyHeader zh;
-    try {
-        zf.reset(new BinFile(zkey, zkeySize, "zkey", 1));
+    under(ZKEY_RULE, [&] {
         if (zf->sectionSize(1) < 4) throw ZkeyError("section 1 is too short");
         u32 protocol = 0;
         memcpy(&protocol, zf->sectionData(1), 4);
         if (protocol == 1337) throw ZkeyError("protocol 1337 keys are not checked");
         zh = loadZkeyHeader(*zf, false);
-    } catch (const std::exception& e) {
-        throw std::invalid_argument(under("zkey: ", e.what()));
-    }
+    });
     if (!zh.rIsBn254) throw ZkeyError("zkey curve not supported");
     if (memcmp(zf->sectionData(2) + 4, BN254_Q_LE, 32) != 0) throw ZkeyError("header: q is not the BN254 base modulus");
     if (zh.nVars != M) throw ZkeyError("header: nVars " + std::to_string(zh.nVars) + ", the circuit has " + std::to_string(M) + " wires");
@@ -275,7 +265,7 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
     in.r1cs = r1cs; in.r1csSize = r1csSize; in.cs = &cs;
     const uint8_t* coefs = nullptr;
     u64 keyCoefs = 0;
-    try {
+    under(ZKEY_RULE, [&] {
         in.ic = sectionOf(*zf, 3, pub * 64);
         coefs = sectionOf(*zf, 4, 4);
         u32 n32 = 0;
@@ -287,52 +277,31 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
         in.b2 = sectionOf(*zf, 7, M * 128);
         in.c = sectionOf(*zf, 8, (M - pub) * 64);
         in.h = sectionOf(*zf, 9, N * 64);
-    } catch (const std::exception& e) {
-        throw std::invalid_argument(under("zkey: ", e.what()));
-    }
+    });
 
-    if (!ptau) throw PtauError("null ptau buffer");
-    std::unique_ptr<BinFile> pf;
-    try {
-        pf.reset(new BinFile(ptau, ptauSize, "ptau", 1));
-    } catch (const std::exception& e) {
-        throw std::invalid_argument(under("ptau: ", e.what()));
-    }
+    const std::unique_ptr<BinFile> pf = openBinFile(ptau, ptauSize, "ptau", "ptau: ", "null ptau buffer");
     const PtauHeader ph = loadPtauHeader(*pf);
     const PtauSlices sl = loadPtauSlices(*pf, ph, (u32)logN);
     in.T = sl.tau1; in.T2 = sl.tau2; in.aT = sl.alphaTau1; in.bT = sl.betaTau1; in.top = sl.top;
-    try {
-        loadR1cs(*rf, cs);
-    } catch (const std::exception& e) {
-        throw std::invalid_argument(under("r1cs: ", e.what()));
-    }
+    under(R1CS_RULE, [&] { loadR1cs(*rf, cs); });
     std::vector<uint8_t> hOdd((size_t)N * 64);  // H's sources side by side (the host twin's bases, and what the point check reads)
-    parallelFor(N, 4096, [&](u64 lo, u64 hi) {
-        for (u64 k = lo; k < hi; k++) memcpy(&hOdd[(size_t)k * 64], sl.top + (2 * k + 1) * 64, 64);
-    });
-    lap(0);
+    gatherOddTop(sl, hOdd.data());
+    clock.lap(0);
 
     // ---- every point of the key and of the slices, before any relation: a bad point is a refusal, not a verdict ----
     {
-        const PtauPointCheck check(device, (int)opt->validate);
-        check(false, sl.tau1, N, 12, sl.first, 1);
-        check(true, sl.tau2, N, 13, sl.first, 1);
-        check(false, sl.alphaTau1, N, 14, sl.first, 1);
-        check(false, sl.betaTau1, N, 15, sl.first, 1);
-        check(false, hOdd.data(), N, 12, sl.firstTop + 1, 2);
-        check(false, sl.alpha1, 1, 4, 0, 1);
-        check(false, sl.beta1, 1, 5, 0, 1);
-        check(true, sl.beta2, 1, 6, 0, 1);
+        const PointCheck check(device, (int)opt->validate);
+        checkSlices(check, sl, hOdd.data());
         checkKeyPoints(check, zh, in);
     }
     rep->subgroup_checked = opt->validate >= 2 ? 1 : 0;
-    lap(1);
+    clock.lap(1);
 
     std::vector<uint8_t> rho, sigma;
     drawWeights(rho, M);
     drawWeights(sigma, N);
     in.rho = rho.data(); in.sigma = sigma.data();
-    lap(2);
+    clock.lap(2);
 
     // ---- relation 0: the header ----
     const G1A g1 = g1Generator();
@@ -355,9 +324,7 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
     // ---- relation 1: section 4 is the one setup_host.cpp writes for this circuit ----
     {
         std::vector<u64> perPiece;
-        countCoefs(cs, perPiece);
-        u64 nCoefs = pub;
-        for (u64 n : perPiece) nCoefs += n;
+        const u64 nCoefs = pub + countCoefs(cs, perPiece);
         Plan p;
         planSizes(cs.hdr, (u32)logN, p);
         std::vector<uint8_t> want((size_t)nCoefs * 44);
@@ -369,7 +336,7 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
         if (bad < common || nCoefs != keyCoefs || zf->sectionSize(4) != 4 + keyCoefs * 44)
             v.fail(4, "zkey: section 4 record " + std::to_string(bad) + ": does not match the circuit");
     }
-    lap(0);
+    clock.lap(0);
 
     // ---- the sums of relations 2 - 7 ----
     Sums s;
@@ -380,7 +347,7 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
     for (int i = 0; i < 4; i++) ms[3 + i] += st.ms[i];
     rep->fold_kernel_ms = st.foldKernelMs;
     rep->peak_device_bytes = st.peakDeviceBytes;
-    t = nowMs();
+    clock.restart();
 
     const char* const TEXT = ": does not match the circuit and the powers of tau";
     auto secFail = [&](int id, bool delta) { v.fail(id, "zkey: section " + std::to_string(id) + TEXT + (delta ? " under the key's delta" : "")); };
@@ -395,7 +362,7 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
     if (!ok3) secFail(3, false);
     if (!ok8) secFail(8, true);
     if (!ok9) secFail(9, true);
-    lap(7);
+    clock.lap(7);
     rep->failed_sections = v.failed;
     rep->first_failed = v.first;
     return v.failed ? UG_ZKEY_INVALID : UG_OK;
@@ -407,7 +374,6 @@ int run(const ug_zkey_verify_options* opt, const void* r1cs, u64 r1csSize, const
 
 // =====================================================================================================================
 using namespace ughost::zkv;
-using ughost::setup::copyErr;
 
 extern "C" {
 
@@ -418,18 +384,12 @@ int ug_zkey_verify_run(const ug_zkey_verify_options* opt, const void* r1cs, uint
     memset(&rep, 0, sizeof rep);
     double ms[UG_ZKEY_VERIFY_PHASES] = {0};
     int rc = UG_ERROR;
-    try {
-        Verdict v;
-        rc = run(opt, r1cs, r1cs_size, ptau, ptau_size, zkey, zkey_size, device, &rep, ms, v);
-        copyErr(error_msg, error_msg_maxsize, v.message.c_str());
-    } catch (std::exception& e) {
-        const std::string m = e.what();
-        copyErr(error_msg, error_msg_maxsize, (known(m) ? m : "zkey: " + stripSetup(m)).c_str());
-        memset(&rep, 0, sizeof rep);
-        rc = UG_ERROR;
-    } catch (...) {
-        copyErr(error_msg, error_msg_maxsize, "zkey: unknown error");
-        memset(&rep, 0, sizeof rep);
+    if (guarded(ZKEY_RULE, error_msg, error_msg_maxsize, [&] {
+            Verdict v;
+            rc = run(opt, r1cs, r1cs_size, ptau, ptau_size, zkey, zkey_size, device, &rep, ms, v);
+            copyErr(error_msg, error_msg_maxsize, v.message.c_str());
+        }) != UG_OK) {
+        memset(&rep, 0, sizeof rep);              // (a refusal reports nothing)
         rc = UG_ERROR;
     }
     if (out) *out = rep;
@@ -439,36 +399,29 @@ int ug_zkey_verify_run(const ug_zkey_verify_options* opt, const void* r1cs, uint
 
 int ug_r1cs_fold(const void* r1cs, uint64_t r1cs_size, const void* rho, uint32_t log_domain, int device, void* out, double* kernel_ms,
                  char* error_msg, unsigned long long error_msg_maxsize) {
-    try {
+    return guarded(R1CS_RULE, error_msg, error_msg_maxsize, [&] {
         if (kernel_ms) *kernel_ms = 0;
         if (!r1cs || !rho || !out) throw R1csRefusal("null buffer");
-        ughost::BinFile f(r1cs, r1cs_size, "r1cs", 1);
+        const std::unique_ptr<ughost::BinFile> f = ughost::openBinFile(r1cs, r1cs_size, "r1cs", "r1cs: ", "null buffer");
         ughost::R1cs cs;
-        ughost::loadR1cs(f, cs);
+        ughost::loadR1cs(*f, cs);
         const uint64_t nPublic = (uint64_t)cs.hdr.nPubOut + cs.hdr.nPubIn;
         if (nPublic + 1 > cs.hdr.nWires) throw R1csRefusal("nPubOut + nPubIn + 1 exceeds nWires");
-        ughost::setup::Plan p;
-        ughost::setup::planSizes(cs.hdr, log_domain, p);
+        Plan p;
+        planSizes(cs.hdr, log_domain, p);
         std::vector<uint8_t> all((size_t)p.N * 32 * 8);
         double ms = 0;
         if (device < 0) {
-            const double t0 = ughost::setup::nowMs();
+            const double t0 = nowMs();
             hostFold(cs, (const uint8_t*)rho, (uint32_t)nPublic, p.N, all.data());
-            ms = ughost::setup::nowMs() - t0;
+            ms = nowMs() - t0;
         } else {
             if (!deviceFold) throw R1csRefusal("this program has no device path: use device = -1 (host threads)");
             deviceFold(device, r1cs, r1cs_size, (const uint8_t*)rho, (uint32_t)nPublic, (uint32_t)p.logN, all.data(), &ms);
         }
         memcpy(out, all.data(), (size_t)p.N * 32 * 6);
         if (kernel_ms) *kernel_ms = ms;
-    } catch (std::exception& e) {
-        copyErr(error_msg, error_msg_maxsize, under("r1cs: ", e.what()).c_str());
-        return UG_ERROR;
-    } catch (...) {
-        copyErr(error_msg, error_msg_maxsize, "r1cs: unknown error");
-        return UG_ERROR;
-    }
-    return UG_OK;
+    });
 }
 
 }  // extern "C"
