@@ -539,7 +539,7 @@ int  ug_lagrange_at(int device, int log_n, const void* x, int coset, void* out, 
 /* PHASE-2 SETUP FROM A PREPARED POWERS-OF-TAU FILE: .r1cs + .ptau -> a Groth16 (protocol 1) proving key and its verification key
  * (setup_ptau.cpp, setup_points.hip; what `snarkjs zkey new` does, then optionally ONE delta contribution). No trapdoor is known
  * to this code: tau, alpha and beta stay inside the points of the ceremony.
- * OUT OF SCOPE: UltraGroth keys (protocol 1337); contribution transcripts (the zkey's section 10 is written empty, so
+ * OUT OF SCOPE here: UltraGroth keys (protocol 1337), which ug_ultra_setup_ptau_run below makes; in both: contribution transcripts (the zkey's section 10 is written empty, so
  * `snarkjs zkey verify` does not accept a key made here); beacons; verifying the .ptau's own ceremony. A key made without a
  * contribution has delta = 1: ANYONE forges proofs for it. A key made with a drawn delta is a single-party phase 2: it is sound
  * only if that run's delta is gone and the .ptau is honest.
@@ -609,6 +609,65 @@ int  ug_points_combine(int device, int g2, const uint32_t* col_ptr, uint64_t n_c
 int  ug_points_scale(int device, const void* scalar, const void* points, uint64_t n, void* out, double* kernel_ms, char* error_msg,
                      unsigned long long error_msg_maxsize);
 
+/* PHASE-2 SETUP OF AN ULTRAGROTH KEY FROM A PREPARED POWERS-OF-TAU FILE: .r1cs + .ptau + the commitment rounds -> a protocol-1337
+ * proving key and its verification key (setup_ptau.cpp, setup_points.hip), optionally with ONE contribution to each of the two
+ * deltas. ug_setup_ptau_run beside it stays what it is; everything it says about the .ptau, its layout ("AS REMEMBERED"), its
+ * rules and messages, the point check and what is OUT OF SCOPE (transcripts, beacons, the .ptau's own ceremony) holds here.
+ * contribute = 0 leaves BOTH deltas 1: ANYONE forges proofs for such a key. contribute = 2 is a single-party phase 2 with no
+ * transcript: the key is sound only if that run's two deltas are gone and the .ptau is honest.
+ *
+ * Which signal is committed in which round is what UltraGroth's soundness rests on, and this call takes it from the caller:
+ * rand_indx, a public signal (1 .. nPublic), carries the challenge; round_signals are committed before it, final_signals after;
+ * the two lists must partition the private signals nPublic + 1 .. nVars - 1 (an empty list is legal). The rules and their
+ * messages are ug_setup_run's for protocol 1337. A delta must be below r and not 0 ("setup: delta_round is 0 mod r", "setup:
+ * delta_final is not below the field modulus"). Every rule of the options and of both files fires before the first device byte.
+ *
+ * The key, in ug_setup_ptau_run's notation (T, T2, aT, bT, K_s; P = level n + 1 of section 12):
+ *   sections 5, 6, 7   A, B1, B2 as for Groth16
+ *   section 3          IC_s = K_s for every s <= nPublic, the rand signal included
+ *   section 8          C1[i] = (1 / delta_round) K_(round_signals[i])      section 10   round_signals, in the order given
+ *   section 9          C2[i] = (1 / delta_final) K_(final_signals[i])      section 11   final_signals, in the order given
+ *   section 12         H_k = (1 / delta_final) P[2k + 1]                   section 13   contributions: empty
+ *   header             alpha1, beta1, beta2 from the .ptau; gamma2 = G2; delta_c1 = delta_round (G1, G2); delta_c2 = delta_final (G1, G2)
+ * The container, the section order and the JSON (nPublic without the rand signal, IC without it, IC_rand, vk_delta_c1_2,
+ * vk_delta_c2_2) are ug_setup_run's for protocol 1337. For a .ptau made from a known (tau, alpha, beta) the key and the JSON
+ * equal, byte for byte, ug_setup_run's for protocol 1337 and the trapdoor (tau, alpha, beta, gamma = 1, delta_round, delta_final).
+ * device >= 0: the point combinations run as ug_setup_ptau_run's kernels and the whole delta step -- C1, C2 and H, gathered
+ * through the two lists -- is ONE launch (scale_segments_kernel); device = -1: host threads, the same bytes. */
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_ultra_setup_ptau_options) */
+    uint32_t log_domain;                /* 0: the smallest domain that fits */
+    uint32_t validate;                  /* 0 no point check, 1 field range + curve, 2 the G2 subgroup as well */
+    uint32_t contribute;                /* 0: both deltas 1; 1: delta_round[] and delta_final[] are applied; 2: both are drawn
+                                           independently from OS entropy, applied, wiped and never returned or logged */
+    uint8_t  delta_round[32], delta_final[32];              /* contribute = 1: plain little-endian, below r, not 0 */
+    uint32_t rand_indx;
+    uint32_t reserved;                  /* 0 */
+    const uint32_t* round_signals; uint64_t n_round;
+    const uint32_t* final_signals; uint64_t n_final;
+} ug_ultra_setup_ptau_options;
+/* host only: every rule of the options and of both files, the exact size of the zkey and an upper bound of the JSON with its final 0 */
+int  ug_ultra_setup_ptau_size(const ug_ultra_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                              uint64_t ptau_size, uint64_t* zkey_bytes, uint64_t* vkey_bytes_max, char* error_msg,
+                              unsigned long long error_msg_maxsize);
+/* phase_ms: UG_SETUP_PTAU_PHASES doubles (the phases of ug_setup_ptau_run) or NULL */
+int  ug_ultra_setup_ptau_run(const ug_ultra_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                             uint64_t ptau_size, int device, void* zkey, uint64_t zkey_capacity, uint64_t* zkey_bytes, char* vkey_json,
+                             uint64_t vkey_capacity, uint64_t* vkey_bytes, double* phase_ms, char* error_msg,
+                             unsigned long long error_msg_maxsize);
+/* Test tooling for the delta step of an UltraGroth key, host buffers, device >= 0 or -1 (host threads); messages prefixed "setup: ".
+ * n_segments <= 3 segments over ONE array of n_points G1 records: segment s writes count records, scalar * points[index[i]], or
+ * scalar * points[i] when index is NULL (count <= n_points then); every index must be below n_points. out: the segments' records
+ * one segment after the other. A scalar (plain, below r) of 1 copies the gathered records, 0 gives all-zero records; infinity in
+ * gives infinity out. On the device all segments are one launch; kernel_ms (may be NULL): one double. */
+typedef struct {
+    const void* scalar;
+    const uint32_t* index;              /* count indexes into points, or NULL */
+    uint64_t count;
+} ug_scale_segment;
+int  ug_points_scale_segments(int device, int n_segments, const ug_scale_segment* segments, const void* points, uint64_t n_points,
+                              void* out, double* kernel_ms, char* error_msg, unsigned long long error_msg_maxsize);
+
 /* CHECKING A KEY AGAINST ITS CIRCUIT AND POWERS OF TAU (zkey_verify.cpp, zkey_verify.hip; what `snarkjs zkey verify` answers about
  * the key's POINTS; no reference counterpart: the reference starts from a .zkey somebody else made). Given a circuit's .r1cs, a
  * .ptau prepared for phase 2 and a Groth16 (protocol 1) .zkey, the call says whether sections 2 - 9 of the key are the ones
@@ -667,6 +726,49 @@ int  ug_zkey_verify_run(const ug_zkey_verify_options* opt, const void* r1cs, uin
  * in a^pub and 0 elsewhere; the rows above hold 0. kernel_ms (may be NULL): the kernel's time. */
 int  ug_r1cs_fold(const void* r1cs, uint64_t r1cs_size, const void* rho, uint32_t log_domain, int device, void* out, double* kernel_ms,
                   char* error_msg, unsigned long long error_msg_maxsize);
+/* CHECKING AN ULTRAGROTH KEY (protocol 1337) against its circuit and powers of tau: ug_zkey_verify_run's question for the keys
+ * ug_ultra_setup_ptau_run makes, beside it (a Groth16 key is refused here with "zkey: zkey file is not ultragroth", as an UltraGroth
+ * key is refused there). Valid: sections 2 - 12 are the ones ug_ultra_setup_ptau_run gives for these files under ONE delta_round and
+ * ONE delta_final, neither known to this code. OUT OF SCOPE: transcripts, beacons, the .ptau's own ceremony, and -- when no spec is
+ * given -- WHO CHOSE THE ROUNDS: the key's own lists are then taken as they are, and which signal is committed before the challenge
+ * is what the protocol's soundness rests on.
+ * rho, sigma as in ug_zkey_verify_run. The wires fall in three classes: pub = 0 .. nPublic, round = the key's section 10, final = its
+ * section 11; a^m, b^m, c^m, K^m as there for m in {pub, round, final}; a = a^pub + a^round + a^final. In this order, all evaluated:
+ *   0  section 2    alpha1, beta1, beta2 are the .ptau's by bytes; gamma2, delta_c1, delta_c2 (G1 and G2 parts) are not infinity;
+ *                   e(delta_c1_1, G2) = e(G1, delta_c1_2) and the same for delta_c2            "zkey: header: ..."
+ *   1  section 4    byte for byte, as for Groth16
+ *   2  10, 11       with a spec (check_spec = 1): rand_indx and each list equal the spec's     "zkey: header: rand_indx does not match the
+ *                   spec", "zkey: section 10: does not match the spec" (likewise 11)
+ *   3 - 5  5, 6, 7  as for Groth16                      6  section 3   e(MSM(rho^pub, IC), gamma2) = e(K^pub, G2)
+ *   7  section 8    e(MSM(rho[round_signals[i]], C1[i]), delta_c1_2) = e(K^round, G2)           "... under the key's round delta"
+ *   8  section 9    the same over the final list with delta_c2_2                                "... under the key's final delta"
+ *   9  section 12   e(MSM(sigma, H), delta_c2_2) = e(MSM(sigma, odd records of P), G2)          "... under the key's final delta"
+ * An empty list: its relation holds trivially and K^m must be infinity. REFUSED (UG_ERROR), before the first device byte: every
+ * refusal of ug_zkey_verify_run; a rand_indx that is not public, lists that do not partition the private signals (ug_setup_run's
+ * texts under "zkey: "; n_indexes_c1 + n_indexes_c2 = nVars - nPublic - 1 is part of that rule). Every point of the key and of
+ * the slices goes through the point check first ("zkey: header point delta_c1_2: ..."); validate = 1 reports subgroup_checked = 0
+ * and is not "valid". failed_sections has bit <id> set for the sections 2 - 12. device >= 0: the fold (r1cs_fold_classes_kernel) and
+ * the MSMs run on the device, one section's bases resident at a time; the weights of a list's signals are gathered on the host (32
+ * bytes per private signal); device = -1: host threads. Pairings run on host threads either way. phase_ms: UG_ZKEY_VERIFY_PHASES. */
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_ultra_zkey_verify_options) */
+    uint32_t validate;                  /* 2 | 1 as ug_zkey_verify_options.validate */
+    uint32_t check_spec;                /* 1: the key's rand_indx and lists must equal the ones below; 0: they are not read */
+    uint32_t rand_indx;
+    const uint32_t* round_signals; uint64_t n_round;
+    const uint32_t* final_signals; uint64_t n_final;
+} ug_ultra_zkey_verify_options;
+int  ug_ultra_zkey_verify_run(const ug_ultra_zkey_verify_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                              uint64_t ptau_size, const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out,
+                              double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize);
+/* Test tooling for the fold with a class per wire; as ug_r1cs_fold, but cls: nWires bytes, each 0, 1 or 2 (any map: the public
+ * wires need not be class 0 here), and out: ELEVEN vectors of N integers: vector 3 m + t is the sum of matrix t (A, B, C) over the
+ * wires of class m; vector 9 is a, 10 is b (the sums over all wires). The public rows hold rho_s in vectors 0 and 9.
+ * ug_r1cs_fold_classes_dvec: the device form; cls: the class bytes packed 32 to an element; out: 11 * 2^log_domain elements. */
+int  ug_r1cs_fold_classes(const void* r1cs, uint64_t r1cs_size, const void* rho, const void* cls, uint32_t log_domain, int device, void* out,
+                          double* kernel_ms, char* error_msg, unsigned long long error_msg_maxsize);
+int  ug_r1cs_fold_classes_dvec(ug_r1cs* r, const ug_dvec* rho, const ug_dvec* cls, uint32_t n_public, uint32_t log_domain, ug_dvec* out,
+                               double* kernel_ms);
 /* The device forms the check is made of. ug_r1cs_fold_dvec: the fold of a resident circuit over a resident rho into `out`, EIGHT
  * vectors of 2^log_domain elements: the six above, then a = a^pub + a^priv and b, each an MSM scalar vector where it lies
  * (ug_schedule_build over its range); one launch, one host wait. ug_bases_create_every_g1: the G1 set of the records first,

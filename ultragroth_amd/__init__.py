@@ -434,6 +434,100 @@ def points_scale(scalar, points, device=0, timing=None):
     return [out.raw[64 * i:64 * i + 64] for i in range(len(points))]
 
 
+class _UltraSetupPtauOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_domain", C.c_uint32), ("validate", C.c_uint32), ("contribute", C.c_uint32),
+                ("delta_round", C.c_ubyte * 32), ("delta_final", C.c_ubyte * 32), ("rand_indx", C.c_uint32), ("reserved", C.c_uint32),
+                ("round_signals", C.POINTER(C.c_uint32)), ("n_round", C.c_uint64),
+                ("final_signals", C.POINTER(C.c_uint32)), ("n_final", C.c_uint64)]
+
+
+class _ScaleSegment(C.Structure):
+    _fields_ = [("scalar", C.c_void_p), ("index", C.POINTER(C.c_uint32)), ("count", C.c_uint64)]
+
+
+def ultra_setup_from_ptau(r1cs, ptau, ultra, delta=None, log_domain=0, device=0, validate=1, timings=None):
+    """ug_ultra_setup_ptau_run: an UltraGroth (protocol 1337) proving key and verification key from a circuit's .r1cs, a .ptau
+    prepared for phase 2 and the commitment rounds. Returns (zkey_bytes, vkey_dict, phase_ms_dict) as setup_from_ptau does.
+
+    ultra: {"rand_indx": n, "round_signals": [...], "final_signals": [...]}, dev_setup's spec: the public signal that carries the
+    challenge and the private signals committed before and after it; the lists must partition the private signals and go into
+    the key in the order given. Which signal sits in which round is what the protocol's soundness rests on: it is the caller's.
+    delta: None writes delta_round = delta_final = 1 -- ANYONE forges proofs for such a key until a contribution is applied; a pair
+    (d_round, d_final) of integers below r applies those; "draw" draws both independently from OS entropy, applies and wipes them
+    (a single-party phase 2 with no transcript: sound only if both are gone and the .ptau is honest).
+    ptau, validate, device, timings: as setup_from_ptau. Transcripts, beacons and verifying the .ptau's ceremony are out of scope.
+    Refusals raise SetupError ("ptau: ..." / "r1cs: ..." / "setup: ...")."""
+    import json
+    L = load()
+    opt = _UltraSetupPtauOptions()
+    opt.size = C.sizeof(_UltraSetupPtauOptions)
+    opt.log_domain, opt.validate = log_domain, validate
+    if ultra is None:
+        raise SetupError("setup: an UltraGroth key needs ultra = {rand_indx, round_signals, final_signals}")
+    keep = _ultra_lists(opt, ultra, "setup: ")
+    if delta is None:
+        opt.contribute = 0
+    elif isinstance(delta, str):
+        if delta != "draw":
+            raise SetupError("setup: delta is None, a pair of integers or \"draw\"")
+        opt.contribute = 2
+    else:
+        try:
+            d_round, d_final = delta
+        except (TypeError, ValueError):
+            raise SetupError("setup: delta is None, a pair of integers or \"draw\"")
+        opt.contribute = 1
+        opt.delta_round = _le32(d_round, "delta_round")
+        opt.delta_final = _le32(d_final, "delta_final")
+    r1cs = bytes(r1cs)
+    with _Mapped(ptau) as m:
+        zbytes, vmax = C.c_uint64(), C.c_uint64()
+        _setup_call(L.ug_ultra_setup_ptau_size, C.byref(opt), r1cs, len(r1cs), m.address, m.length, C.byref(zbytes), C.byref(vmax))
+        zkey = C.create_string_buffer(zbytes.value)
+        vkey = C.create_string_buffer(vmax.value)
+        wrote, vlen = C.c_uint64(), C.c_uint64()
+        ms = (C.c_double * len(SETUP_PTAU_PHASES))()
+        _setup_call(L.ug_ultra_setup_ptau_run, C.byref(opt), r1cs, len(r1cs), m.address, m.length, device, zkey, zbytes.value, C.byref(wrote),
+                    vkey, vmax.value, C.byref(vlen), ms)
+    phase_ms = dict(zip(SETUP_PTAU_PHASES, ms))
+    if timings is not None:
+        timings.update(phase_ms)
+    return zkey.raw[:wrote.value], json.loads(vkey.raw[:vlen.value].decode()), phase_ms
+
+
+def points_scale_segments(segments, points, device=0, timing=None):
+    """ug_points_scale_segments (test tooling): the delta step of an UltraGroth key. segments: at most three (scalar, index, count),
+    scalar an integer below r, index a list of count indexes into points or None (the first count records); points: G1 records
+    (64 bytes, all-zero is infinity). Returns one list of records per segment: [scalar * points[index[i]]]. On the device all
+    segments are one launch. device=-1: host threads. timing: a list that receives the kernel's ms."""
+    pts = _joined(points, 64)
+    segs = (_ScaleSegment * max(1, len(segments)))()
+    keep = []
+    total = 0
+    for i, (scalar, index, count) in enumerate(segments):
+        sc = C.create_string_buffer(bytes(_le32(scalar, "scalar")), 32)
+        keep.append(sc)
+        segs[i].scalar = C.cast(sc, C.c_void_p)
+        if index is not None:
+            if len(index) != count:
+                raise SetupError("setup: an index list of another length")
+            arr = (C.c_uint32 * max(1, count))(*index)
+            keep.append(arr)
+            segs[i].index = C.cast(arr, C.POINTER(C.c_uint32))
+        segs[i].count = count
+        total += count
+    out = C.create_string_buffer(max(1, 64 * total))
+    ms = (C.c_double * 1)()
+    _setup_call(load().ug_points_scale_segments, device, len(segments), segs, pts, len(points), out, ms)
+    if timing is not None:
+        timing.append(ms[0])
+    res, at = [], 0
+    for _, _, count in segments:
+        res.append([out.raw[64 * (at + i):64 * (at + i) + 64] for i in range(count)])
+        at += count
+    return res
+
+
 PTAU_PREPARE_PHASES = ("parse", "point_check", "g1", "g2", "compare")
 
 
@@ -560,6 +654,98 @@ def zkey_verify(r1cs, ptau, zkey, device=0, validate=2, timings=None):
     if rc == 0:
         return None
     return rep.first_failed, [i for i in range(2, 10) if rep.failed_sections >> i & 1], msg
+
+
+class _UltraZkeyVerifyOptions(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("validate", C.c_uint32), ("check_spec", C.c_uint32), ("rand_indx", C.c_uint32),
+                ("round_signals", C.POINTER(C.c_uint32)), ("n_round", C.c_uint64),
+                ("final_signals", C.POINTER(C.c_uint32)), ("n_final", C.c_uint64)]
+
+
+def _ultra_lists(opt, ultra, prefix):
+    """rand_indx and the two lists of a spec into an options struct; returns the arrays it points into"""
+    try:
+        rand, lists = int(ultra["rand_indx"]), [[int(x) for x in ultra[k]] for k in ("round_signals", "final_signals")]
+    except (KeyError, TypeError, ValueError):
+        raise SetupError(prefix + "ultra is {rand_indx, round_signals, final_signals}")
+    if not all(0 <= x < 1 << 32 for x in [rand] + lists[0] + lists[1]):
+        raise SetupError(prefix + "a signal of the spec is not below 2^32")
+    opt.rand_indx = rand
+    keep = []
+    for name, count, lst in (("round_signals", "n_round", lists[0]), ("final_signals", "n_final", lists[1])):
+        arr = (C.c_uint32 * max(1, len(lst)))(*lst)
+        keep.append(arr)
+        setattr(opt, name, C.cast(arr, C.POINTER(C.c_uint32)))
+        setattr(opt, count, len(lst))
+    return keep
+
+
+def ultra_zkey_verify(r1cs, ptau, zkey, ultra=None, device=0, validate=2, timings=None):
+    """ug_ultra_zkey_verify_run: is this UltraGroth key the one `ultra_setup_from_ptau(r1cs, ptau, ...)` gives under ONE delta_round
+    and ONE delta_final, which nobody has to know? The report has zkey_verify's shape: None when it is; (first_section,
+    failed_sections, message) when not, sections 2 - 12. Refusals -- zkey_verify's, a Groth16 key, a rand_indx that is not public,
+    lists that do not partition the private signals -- raise SetupError.
+
+    ultra: a spec {"rand_indx", "round_signals", "final_signals"} the key's own rounds must equal; None takes the key's rounds as
+    they are -- WHO CHOSE THEM IS THEN NOT CHECKED, and which signal is committed before the challenge is what the protocol's
+    soundness rests on. ptau, zkey, validate, device, timings: as zkey_verify. Transcripts, beacons and the .ptau's own ceremony
+    are not checked."""
+    L = load()
+    opt = _UltraZkeyVerifyOptions()
+    opt.size = C.sizeof(_UltraZkeyVerifyOptions)
+    if not 0 <= int(validate) < 1 << 32:
+        raise SetupError("zkey: validate %d is not 1 or 2" % validate)
+    opt.validate = int(validate)
+    keep = []
+    if ultra is not None:
+        opt.check_spec = 1
+        keep = _ultra_lists(opt, ultra, "zkey: ")
+    r1cs = bytes(r1cs)
+    with _Mapped(ptau) as mp, _Mapped(zkey) as mz:
+        rep = _ZkeyVerifyReport()
+        ms = (C.c_double * len(ZKEY_VERIFY_PHASES))()
+        err = C.create_string_buffer(1024)
+        rc = L.ug_ultra_zkey_verify_run(C.byref(opt), r1cs, len(r1cs), mp.address, mp.length, mz.address, mz.length, device, C.byref(rep), ms,
+                                        err, len(err) - 1)
+    del keep
+    msg = err.value.decode(errors="replace")
+    if rc not in (0, UG_ZKEY_INVALID):
+        raise SetupError(msg)
+    if timings is not None:
+        timings.update(zip(ZKEY_VERIFY_PHASES, ms))
+        timings.update(fold_kernel=rep.fold_kernel_ms, peak_device_bytes=rep.peak_device_bytes, subgroup_checked=bool(rep.subgroup_checked))
+    if rc == 0:
+        return None
+    return rep.first_failed, [i for i in range(2, 13) if rep.failed_sections >> i & 1], msg
+
+
+def r1cs_fold_classes(r1cs, rho, cls, log_domain=0, device=0, timing=None):
+    """ug_r1cs_fold_classes (test tooling): the fold of an UltraGroth key check. rho as r1cs_fold; cls: one class 0, 1 or 2 per wire.
+    Returns eleven lists of N integers: (a, b, c) over class 0, over class 1, over class 2, then a and b over all wires."""
+    r1cs = bytes(r1cs)
+    try:
+        info = r1cs_info(r1cs)
+    except DeviceError as e:
+        raise SetupError(str(e) if str(e).startswith("r1cs: ") else "r1cs: " + str(e))
+    rho = [int(x) for x in rho]
+    cls = [int(x) for x in cls]
+    if len(rho) != info["n_wires"] or any(not 0 <= x < 1 << 256 for x in rho):
+        raise SetupError("r1cs: rho takes one integer below 2^256 per wire (%d wires)" % info["n_wires"])
+    if len(cls) != info["n_wires"] or any(not 0 <= x < 256 for x in cls):
+        raise SetupError("r1cs: cls takes one class per wire (%d wires)" % info["n_wires"])
+    rows = info["n_constraints"] + info["n_pub_out"] + info["n_pub_in"] + 1
+    log_n = int(log_domain) if log_domain else max(1, (rows - 1).bit_length())
+    if not 0 < log_n <= 27:
+        raise SetupError("r1cs: log_domain %d is not in 1 .. 27" % log_n)
+    n = 1 << log_n
+    out = C.create_string_buffer(11 * 32 * n)
+    ms = C.c_double()
+    _setup_call(load().ug_r1cs_fold_classes, r1cs, len(r1cs), b"".join(x.to_bytes(32, "little") for x in rho), bytes(cls), log_n, device, out,
+                C.byref(ms))
+    if timing is not None:
+        timing.append(ms.value)
+    raw = out.raw
+    return tuple([int.from_bytes(raw[32 * (v * n + k):32 * (v * n + k) + 32], "little") for k in range(n)] for v in range(11))
 
 
 def r1cs_fold(r1cs, rho, log_domain=0, device=0, timing=None):

@@ -36,6 +36,8 @@ INNER_SYMBOLS = [
     "ug_r1cs_match_hpoly", "ug_r1cs_destroy",
     "ug_setup_draw_trapdoor", "ug_setup_size", "ug_setup_run", "ug_generator_mul", "ug_lagrange_at",
     "ug_ptau_parse_info", "ug_setup_ptau_size", "ug_setup_ptau_run", "ug_points_combine", "ug_points_scale",
+    "ug_ultra_setup_ptau_size", "ug_ultra_setup_ptau_run", "ug_points_scale_segments",
+    "ug_ultra_zkey_verify_run", "ug_r1cs_fold_classes", "ug_r1cs_fold_classes_dvec",
     "ug_ptau_prepare_size", "ug_ptau_prepare_run", "ug_points_intt",
     "ug_zkey_verify_run", "ug_r1cs_fold", "ug_r1cs_fold_dvec", "ug_bases_create_every_g1",
     "ug_lookup_vectors_bytes", "ug_points_check", "ug_points_check_mask", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
@@ -247,11 +249,17 @@ def load():
     L.ug_setup_ptau_run.argtypes = [vp, vp, u64, vp, u64, C.c_int, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), C.POINTER(C.c_double), vp, ull]
     L.ug_points_combine.argtypes = [C.c_int, C.c_int, vp, u64, vp, vp, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_points_scale.argtypes = [C.c_int, vp, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
+    L.ug_ultra_setup_ptau_size.argtypes = L.ug_setup_ptau_size.argtypes
+    L.ug_ultra_setup_ptau_run.argtypes = L.ug_setup_ptau_run.argtypes
+    L.ug_points_scale_segments.argtypes = [C.c_int, C.c_int, vp, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_ptau_prepare_size.argtypes = [vp, vp, u64, C.POINTER(u64), vp, ull]
     L.ug_ptau_prepare_run.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(C.c_double), vp, ull]
     L.ug_points_intt.argtypes = [C.c_int, C.c_int, C.c_int, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_zkey_verify_run.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.c_int, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_r1cs_fold.argtypes = [vp, u64, vp, u32, C.c_int, vp, C.POINTER(C.c_double), vp, ull]
+    L.ug_ultra_zkey_verify_run.argtypes = L.ug_zkey_verify_run.argtypes
+    L.ug_r1cs_fold_classes.argtypes = [vp, u64, vp, vp, u32, C.c_int, vp, C.POINTER(C.c_double), vp, ull]
+    L.ug_r1cs_fold_classes_dvec.argtypes = [vp, vp, vp, u32, u32, vp, C.POINTER(C.c_double)]
     L.ug_r1cs_fold_dvec.argtypes = [vp, vp, u32, u32, vp, C.POINTER(C.c_double)]
     L.ug_bases_create_every_g1.argtypes = [vp, vp, u64, u64, u64, u64, pp]
     L.ug_fr_ntt.argtypes = [vp, vp, C.c_int, C.c_int]

@@ -359,6 +359,8 @@ void r1cs_match(const R1csDev& m, const CoefMatrix& zk, u32 n_public, const u32*
 // a^priv, b^priv, c^priv, a = a^pub + a^priv, b; rows m.rows + s, s <= n_public, carry rho_s mod r in a^pub and a, rows above
 // them zeros. The caller vouches for m.rows + n_public + 1 <= domain and n_public < n_wires.
 void r1cs_fold(const R1csDev& m, const u32* rho, u32 n_public, u32 domain, u32* out, hipStream_t stream);
+// the same with a class byte per wire (0, 1 or 2) and three sums per matrix: eleven vectors (zkey_verify.hip)
+void r1cs_fold_classes(const R1csDev& m, const u32* rho, const uint8_t* cls, u32 n_public, u32 domain, u32* out, hipStream_t stream);
 // dst[i] = src[first + i * step] over `count` G1 records of 64 bytes (any form: the records are copied, not read)
 void points_take_every(u32* dst, const u32* src, u64 first, u64 step, u64 count, hipStream_t stream);
 

@@ -16,18 +16,13 @@
 #include <vector>
 #include "cli_util.hpp"
 #include "host_util.hpp"
-#include "json_min.hpp"
+#include "cli_spec.hpp"
 #include "../../include/ultragroth_hip.h"
 
 namespace {
 
 const char* const NAMES[6] = {"tau", "alpha", "beta", "gamma", "delta_round", "delta_final"};
 
-std::string slurp(const std::string& path) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    return std::string((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
 // decimal -> 32-byte little-endian, exactly: a value of 2^256 or more is an error, not a residue
 void decimalToLe(uint8_t out[32], const std::string& s, const char* what) {
     if (s.empty()) throw std::invalid_argument(std::string(what) + ": not a number");
@@ -39,18 +34,6 @@ void decimalToLe(uint8_t out[32], const std::string& s, const char* what) {
         if (carry) throw std::invalid_argument(std::string(what) + ": not below 2^256");
     }
     memcpy(out, w, 32);
-}
-uint32_t numberOf(const ugv::JVal& v, const char* what) {
-    if (v.type != ugv::JVal::Number || !v.integral || v.str.empty() || v.str[0] == '-') throw std::invalid_argument(std::string(what) + ": not an index");
-    const unsigned long long x = strtoull(v.str.c_str(), nullptr, 10);
-    if (x > 0xffffffffull) throw std::invalid_argument(std::string(what) + ": not an index");
-    return (uint32_t)x;
-}
-std::vector<uint32_t> listOf(const ugv::JVal& v, const char* what) {
-    if (v.type != ugv::JVal::Array) throw std::invalid_argument(std::string(what) + ": not a list");
-    std::vector<uint32_t> out;
-    for (const ugv::JVal& e : v.arr) out.push_back(numberOf(e, what));
-    return out;
 }
 
 }  // namespace
@@ -74,7 +57,7 @@ int main(int argc, char** argv) {
         uint8_t* vals[6] = {opt.tau, opt.alpha, opt.beta, opt.gamma, opt.delta_round, opt.delta_final};
         char message[1024] = {0};
         if (!trapdoorPath.empty()) {
-            const std::string text = slurp(trapdoorPath);
+            const std::string text = ugcli::slurp(trapdoorPath);
             const ugv::JVal j = ugv::JParser(text.c_str()).parse_document();
             for (int i = 0; i < 6; i++) decimalToLe(vals[i], j.at(NAMES[i]).string(), NAMES[i]);
         } else {
@@ -85,16 +68,13 @@ int main(int argc, char** argv) {
             ugcli::writeFile(pos[1] + ".trapdoor.json", out.data(), out.size());
             fprintf(stderr, "dev_setup: the trapdoor (the toxic waste of this TEST key) is in %s.trapdoor.json\n", pos[1].c_str());
         }
-        std::vector<uint32_t> roundSignals, finalSignals;
+        ugcli::UltraSpec spec;
         if (!ultraPath.empty()) {
-            const std::string text = slurp(ultraPath);
-            const ugv::JVal j = ugv::JParser(text.c_str()).parse_document();
+            spec = ugcli::readUltraSpec(ultraPath);
             opt.protocol = 1337;
-            opt.rand_indx = numberOf(j.at("rand_indx"), "rand_indx");
-            roundSignals = listOf(j.at("round_signals"), "round_signals");
-            finalSignals = listOf(j.at("final_signals"), "final_signals");
-            opt.round_signals = roundSignals.data(); opt.n_round = roundSignals.size();
-            opt.final_signals = finalSignals.data(); opt.n_final = finalSignals.size();
+            opt.rand_indx = spec.randIndx;
+            opt.round_signals = spec.roundSignals.data(); opt.n_round = spec.roundSignals.size();
+            opt.final_signals = spec.finalSignals.data(); opt.n_final = spec.finalSignals.size();
         }
         ughost::FileMap r1cs(pos[0]);
         uint64_t zbytes = 0, vmax = 0;

@@ -6,6 +6,10 @@
 //                    answer is "valid"); 1 leaves the subgroup out, for timing: the line then says so
 //   --device d       -1 runs on host threads (default: ULTRAGROTH_DEVICE, else 0)
 // Not checked: who contributed (section 10's transcript, beacons, the .ptau's own ceremony); UltraGroth keys are refused.
+//
+// Built with -DUG_ULTRA: `zkey_verify_ultra <circuit.r1cs> <prepared.ptau> <key.zkey> [--spec spec.json] [the same options]`, the
+// same question for an UltraGroth key (ug_ultra_zkey_verify_run), sections 2 - 12. --spec: dev_setup --ultra's file; the key's
+// rand_indx and lists must then equal it. Without it the key's own rounds are taken as they are: who chose them is not checked.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,32 +19,62 @@
 #include "cli_util.hpp"
 #include "host_util.hpp"
 #include "../../include/ultragroth_hip.h"
+#ifdef UG_ULTRA
+#include "cli_spec.hpp"
+#define TOOL "zkey_verify_ultra"
+#define SPEC_USAGE " [--spec spec.json]"
+constexpr int LAST_SECTION = 12;
+#else
+#define TOOL "zkey_verify"
+#define SPEC_USAGE ""
+constexpr int LAST_SECTION = 9;
+#endif
 
 int main(int argc, char** argv) {
-    const char* usage = "Usage: zkey_verify <circuit.r1cs> <prepared.ptau> <key.zkey> [--validate 1|2] [--device d]\n";
+    const char* usage = "Usage: " TOOL " <circuit.r1cs> <prepared.ptau> <key.zkey>" SPEC_USAGE " [--validate 1|2] [--device d]\n";
     std::vector<std::string> pos;
     long validate = 2, device = ugcli::defaultDevice();
-    const std::vector<ugcli::Option> options = {ugcli::validateOption(&validate, 1, "Error: --validate takes 1 or 2\n"), ugcli::deviceOption(&device)};
+    std::vector<ugcli::Option> options = {ugcli::validateOption(&validate, 1, "Error: --validate takes 1 or 2\n"), ugcli::deviceOption(&device)};
+#ifdef UG_ULTRA
+    std::string specPath;
+    options.push_back(ugcli::textOption("--spec", &specPath));
+#endif
     if (!ugcli::parseArgs(argc, argv, options, usage, pos)) return 2;
     if (pos.size() != 3) { fputs("Invalid number of parameters\n", stderr); fputs(usage, stderr); return 2; }
     try {
+#ifdef UG_ULTRA
+        ug_ultra_zkey_verify_options opt;
+        const auto runCall = ug_ultra_zkey_verify_run;
+#else
         ug_zkey_verify_options opt;
+        const auto runCall = ug_zkey_verify_run;
+#endif
         memset(&opt, 0, sizeof opt);
         opt.size = sizeof opt;
         opt.validate = (uint32_t)validate;
+#ifdef UG_ULTRA
+        ugcli::UltraSpec spec;
+        if (!specPath.empty()) {
+            spec = ugcli::readUltraSpec(specPath);
+            opt.check_spec = 1;
+            opt.rand_indx = spec.randIndx;
+            opt.round_signals = spec.roundSignals.data(); opt.n_round = spec.roundSignals.size();
+            opt.final_signals = spec.finalSignals.data(); opt.n_final = spec.finalSignals.size();
+        }
+#endif
         char message[1024] = {0};
         ughost::FileMap r1cs(pos[0]), ptau(pos[1]), zkey(pos[2]);
         ug_zkey_verify_report rep;
         double ms[UG_ZKEY_VERIFY_PHASES];
-        const int rc = ug_zkey_verify_run(&opt, r1cs.data(), r1cs.size(), ptau.data(), ptau.size(), zkey.data(), zkey.size(), (int)device, &rep, ms,
-                                          message, sizeof(message) - 1);
+        const int rc = runCall(&opt, r1cs.data(), r1cs.size(), ptau.data(), ptau.size(), zkey.data(), zkey.size(), (int)device, &rep, ms, message,
+                               sizeof(message) - 1);
         if (rc == UG_ERROR) {
             printf("refused\n");
             fprintf(stderr, "Error: %s\n", message);
             return 2;
         }
         std::string sections;
-        for (int id = 2; id <= 9; id++)
+        for (int id = 2; id <= LAST_SECTION; id++)
             if (rep.failed_sections & (1u << id)) sections += (sections.empty() ? "" : ", ") + std::to_string(id);
         const std::string verdict = rc == UG_ZKEY_INVALID ? "invalid: sections " + sections
                                   : rep.subgroup_checked ? std::string("valid") : std::string("relations hold, subgroup not checked");

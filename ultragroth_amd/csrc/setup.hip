@@ -24,6 +24,7 @@ namespace ug {
 void device_points_combine(hipStream_t stream, StreamTimer& timer, bool g2, u64 nCols, const u32* colPtr, const u32* index,
                            const uint8_t* coefs, const ughost::setup::PointSegs& pts, uint8_t* out, double* ms);
 void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms);
+void device_points_scale_segments(hipStream_t stream, StreamTimer& timer, const ughost::setup::ScaleSeg* segs, int n, double* ms);
 // ptau_prepare.hip
 void device_points_intt(hipStream_t stream, StreamTimer& timer, bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven,
                         uint8_t* const* out, double* ms);
@@ -378,6 +379,7 @@ public:
     void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) override {
         device_points_scale(stream_, timer_, scalar, points, n, out, ms);
     }
+    void scaleSegments(const ScaleSeg* segs, int n, double* ms) override { device_points_scale_segments(stream_, timer_, segs, n, ms); }
     // (the inverse transform over points that prepares a .ptau: ptau_prepare.hip)
     void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) override {
         device_points_intt(stream_, timer_, g2, logN, nVec, in, nGiven, out, ms);

@@ -336,6 +336,26 @@ void hostScale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out
     });
 }
 
+// The delta step of an UltraGroth key, a segment at a time: the gather, then hostScale (1: the gathered records as they are)
+void hostScaleSegments(const ScaleSeg* segs, int n) {
+    const uint8_t one[32] = {1};
+    for (int s = 0; s < n; s++) {
+        const ScaleSeg& g = segs[s];
+        if (!g.count) continue;
+        const uint8_t* in = g.src;
+        std::vector<uint8_t> gathered;
+        if (g.index) {
+            gathered.resize((size_t)g.count * 64);
+            parallelFor(g.count, 4096, [&](u64 lo, u64 hi) {
+                for (u64 i = lo; i < hi; i++) memcpy(&gathered[(size_t)i * 64], g.src + (size_t)g.index[i] * 64, 64);
+            });
+            in = gathered.data();
+        }
+        if (!memcmp(g.scalar, one, 32)) { if (in != g.out) memcpy(g.out, in, (size_t)g.count * 64); }
+        else hostScale(g.scalar, in, g.count, g.out);
+    }
+}
+
 // The inverse transform over points, the stages of ptau_prepare.hip on host threads: (1 / N) P_i to the bit-reversed index, then
 // one pass per stage over the butterflies, the records affine in `out` between the passes; a piece of butterflies shares one
 // inversion. The products go through the host's 4-bit signed-window form.
@@ -448,6 +468,11 @@ public:
         hostScale(scalar, points, n, out);
         if (ms) ms[0] = nowMs() - t0;
     }
+    void scaleSegments(const ScaleSeg* segs, int n, double* ms) override {
+        const double t0 = nowMs();
+        hostScaleSegments(segs, n);
+        if (ms) ms[0] = nowMs() - t0;
+    }
     void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) override {
         const double t0 = nowMs();
         if (!inttTrivial(g2, logN, nVec, in, nGiven, out)) {
@@ -519,6 +544,25 @@ void planSizes(const R1csHeader& h, u32 logDomain, Plan& p) {
     for (u32 s = 0; s <= p.nPublic; s++) p.cls[s] = 0;
 }
 
+void planLists(Plan& p, u32 randIndx, const u32* roundSignals, u64 nRound, const u32* finalSignals, u64 nFinal) {
+    p.ultra = true;
+    if (randIndx < 1 || randIndx > p.nPublic) throw SetupError("rand_indx " + std::to_string(randIndx) + " is not a public signal");
+    p.randIndx = randIndx;
+    if ((nRound && !roundSignals) || (nFinal && !finalSignals)) throw SetupError("null signal list");
+    if (nRound + nFinal != (u64)p.nVars - p.nPublic - 1)
+        throw SetupError("the round and final signal lists do not partition the private signals " + std::to_string(p.nPublic + 1) + " .. " + std::to_string(p.nVars - 1));
+    p.roundSignals.assign(roundSignals, roundSignals + nRound);
+    p.finalSignals.assign(finalSignals, finalSignals + nFinal);
+    std::vector<uint8_t> seen(p.nVars, 0);
+    for (int which = 0; which < 2; which++)
+        for (u32 s : which ? p.finalSignals : p.roundSignals) {
+            if (s <= p.nPublic || s >= p.nVars || seen[s])
+                throw SetupError("the round and final signal lists do not partition the private signals: signal " + std::to_string(s));
+            seen[s] = 1;
+            p.cls[s] = which ? 2 : 1;
+        }
+}
+
 namespace {
 
 struct Named { const char* name; const uint8_t* v; bool nonzero; };
@@ -537,23 +581,7 @@ void makePlan(const ug_setup_options* o, const R1csHeader& h, Plan& p) {
         if (n.nonzero && frIsZero(frFromPlain(n.v))) throw SetupError(std::string(n.name) + " is 0 mod r");
     }
     planSizes(h, o->log_domain, p);
-    if (p.ultra) {
-        if (o->rand_indx < 1 || o->rand_indx > p.nPublic) throw SetupError("rand_indx " + std::to_string(o->rand_indx) + " is not a public signal");
-        p.randIndx = o->rand_indx;
-        if ((o->n_round && !o->round_signals) || (o->n_final && !o->final_signals)) throw SetupError("null signal list");
-        if (o->n_round + o->n_final != (u64)p.nVars - p.nPublic - 1)
-            throw SetupError("the round and final signal lists do not partition the private signals " + std::to_string(p.nPublic + 1) + " .. " + std::to_string(p.nVars - 1));
-        p.roundSignals.assign(o->round_signals, o->round_signals + o->n_round);
-        p.finalSignals.assign(o->final_signals, o->final_signals + o->n_final);
-        std::vector<uint8_t> seen(p.nVars, 0);
-        for (int which = 0; which < 2; which++)
-            for (u32 s : which ? p.finalSignals : p.roundSignals) {
-                if (s <= p.nPublic || s >= p.nVars || seen[s])
-                    throw SetupError("the round and final signal lists do not partition the private signals: signal " + std::to_string(s));
-                seen[s] = 1;
-                p.cls[s] = which ? 2 : 1;
-            }
-    }
+    if (p.ultra) planLists(p, o->rand_indx, o->round_signals, o->n_round, o->final_signals, o->n_final);
     // field constants
     const Fr tau = frFromPlain(o->tau), one = fp_one<FrParams>();
     const Fr tauN = frPow2k(tau, p.logN);
@@ -815,7 +843,7 @@ void writeContainer(uint8_t* zkey, const Layout& lay) {
 }
 
 void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vector<u64>& perPiece, const HeaderPoints& hp,
-               const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey) {
+               const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey, bool cPointsDone) {
     const u64 M = p.nVars, pub = (u64)p.nPublic + 1;
     uint8_t* o = zkey + lay.offsetOf(1);
     put32(o, p.ultra ? 1337 : 1);
@@ -831,13 +859,15 @@ void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vect
     put32(o, (u32)lay.nCoefs);
     fillCoefs(cs, p, perPiece, o);
     if (p.ultra) {
-        uint8_t* c1 = zkey + lay.offsetOf(8);
-        uint8_t* c2 = zkey + lay.offsetOf(9);
-        for (size_t i = 0; i < p.roundSignals.size(); i++) memcpy(c1 + i * 64, &krec[(size_t)p.roundSignals[i] * 64], 64);
-        for (size_t i = 0; i < p.finalSignals.size(); i++) memcpy(c2 + i * 64, &krec[(size_t)p.finalSignals[i] * 64], 64);
+        if (!cPointsDone) {
+            uint8_t* c1 = zkey + lay.offsetOf(8);
+            uint8_t* c2 = zkey + lay.offsetOf(9);
+            for (size_t i = 0; i < p.roundSignals.size(); i++) memcpy(c1 + i * 64, &krec[(size_t)p.roundSignals[i] * 64], 64);
+            for (size_t i = 0; i < p.finalSignals.size(); i++) memcpy(c2 + i * 64, &krec[(size_t)p.finalSignals[i] * 64], 64);
+        }
         if (!p.roundSignals.empty()) memcpy(zkey + lay.offsetOf(10), p.roundSignals.data(), 4 * p.roundSignals.size());
         if (!p.finalSignals.empty()) memcpy(zkey + lay.offsetOf(11), p.finalSignals.data(), 4 * p.finalSignals.size());
-    } else if (M > pub) {
+    } else if (M > pub && !cPointsDone) {
         memcpy(zkey + lay.offsetOf(8), &krec[pub * 64], (M - pub) * 64);
     }
     if (vkey) *vkey = vkeyJson(p, hp, krec.data());

@@ -76,6 +76,18 @@ struct PointSegs {
     u64 total() const { return count * (u64)n; }
 };
 
+// one segment of the delta step of an UltraGroth key (Backend::scaleSegments): out[i] = scalar * src[index ? index[i] : i], i < count;
+// src: nSrc zkey-format G1 records, every index below nSrc (the caller has checked); scalar plain, below r
+struct ScaleSeg {
+    const uint8_t* scalar = nullptr;
+    const uint8_t* src = nullptr;
+    u64 nSrc = 0;
+    const u32* index = nullptr;
+    u64 count = 0;
+    uint8_t* out = nullptr;
+};
+constexpr int MAX_SCALE_SEGS = 3;              // C1, C2 and H
+
 // phase times in ms: parse + index (+ upload), Lagrange, transposed products, G1 multiplications, G2 multiplications,
 // download + assembly
 constexpr int PHASES = 6;
@@ -99,6 +111,11 @@ public:
                          double* ms) = 0;
     // out[i] = scalar * point[i] over n G1 records; scalar plain, below r; infinity in gives infinity out. ms (may be null): one value
     virtual void scale(const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms) = 0;
+    // the whole delta step of an UltraGroth key: n <= MAX_SCALE_SEGS segments, each with a scalar of its own and an optional index
+    // list into its source records (the device: one launch for all of them). A scalar of 1 copies the gathered records, 0 gives
+    // all-zero records, infinity in gives infinity out. An output may be its own segment's source only without an index list.
+    // ms (may be null): one value
+    virtual void scaleSegments(const ScaleSeg* segs, int n, double* ms) = 0;
     // The inverse transform over points that prepares a .ptau (ptau_prepare_host.cpp). N = 2^logN, omega = 5^((r - 1) / N):
     // out[v][k] = (1 / N) sum_j omega^(-j k) in[v][j] for each of the nVec vectors; in[v]: nGiven <= N zkey-format records, the rest
     // of the N taken as infinity; out[v]: N records, which do not overlap any input. ms (may be null): two values, the 1 / N
@@ -176,6 +193,9 @@ void checkSlices(const PointCheck& check, const PtauSlices& sl, const uint8_t* h
 // ---- the parts of a key that do not depend on where its points come from (setup_host.cpp), for setup_ptau.cpp ----
 bool belowR(const uint8_t* le);
 void planSizes(const R1csHeader& h, u32 logDomain, Plan& p);       // nVars .. N and cls (all wires of protocol 1) from the header
+// protocol 1337 on a plan whose sizes are set: rand_indx is a public signal, the two lists partition the private signals (an empty
+// list is legal); fills ultra, randIndx, the lists and cls. The rules and messages of ug_setup_run.
+void planLists(Plan& p, u32 randIndx, const u32* roundSignals, u64 nRound, const u32* finalSignals, u64 nFinal);
 void loadCircuit(const void* r1cs, u64 size, std::unique_ptr<BinFile>& f, R1csHeader& h);
 void buildColumns(const R1cs& cs, const Plan& p, ColMatrix cm[3], std::vector<Piece>& pieces);
 u64 countCoefs(const R1cs& cs, std::vector<u64>& perPiece);        // returns the sum of perPiece: the records of the constraint rows
@@ -190,9 +210,10 @@ Layout makeLayout(const Plan& p, u64 nCoefs);
 u64 vkeyBound(const Plan& p);
 struct HeaderPoints { uint8_t g1[4][64], g2[4][128]; };        // alpha, beta, round delta, final delta | beta, gamma, round delta, final delta
 void writeContainer(uint8_t* zkey, const Layout& lay);            // magic, version, the section headers
-// sections 1 - 4 and the C sections from krec (one K record per wire), and the verification key's JSON
+// sections 1 - 4 and the C sections from krec (one K record per wire), and the verification key's JSON. cPointsDone: the C point
+// sections are in place already (a delta step that gathered them: Backend::scaleSegments), only the index sections are written
 void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vector<u64>& perPiece, const HeaderPoints& hp,
-               const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey);
+               const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey, bool cPointsDone = false);
 Backend& backendFor(int device, std::unique_ptr<Backend>& owned);
 // the verification key's JSON into the caller's buffer (may be null: only the length is reported), with its terminating 0
 void copyVkey(const std::string& vkey, char* dst, u64 capacity, uint64_t* bytes);

@@ -189,20 +189,16 @@ __global__ __launch_bounds__(Cfg::BLOCK) void column_points_kernel(ColArgs a, u3
 // loads), so the whole launch takes the same branch at every step. xyzz_add handles every exceptional case, and a point of
 // order r meets none before the last step.
 struct WnafArgs { int8_t digit[256]; int top; };
-__global__ __launch_bounds__(128) void scale_kernel(const u32* __restrict__ pts, u64 n, WnafArgs a, u32* __restrict__ out) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fq x, y;
-    S1::load(pts + i * 16, x, y);
-    u32* o = out + i * 16;
-    if (a.top < 0 || affine_is_inf(x, y)) { zero_record<16>(o); return; }
+// the walk both scale kernels share: digits top .. 0 of one scalar (top >= 0) over the affine point (x, y), which is not infinity;
+// the result leaves as a canonical zkey record
+__device__ __forceinline__ void scale_walk(const int8_t* digit, int top, const Fq& x, const Fq& y, u32* o) {
     const XYZZ<Fq> d2 = xyzz_dbl_affine(x, y);
     const XYZZ<Fq> t3 = xyzz_madd(d2, x, y), t5 = xyzz_add(t3, d2), t7 = xyzz_add(t5, d2);
     XYZZ<Fq> acc = xyzz_inf<Fq>();
 #pragma unroll 1
-    for (int b = a.top; b >= 0; b--) {
+    for (int b = top; b >= 0; b--) {
         acc = xyzz_dbl(acc);
-        const int d = a.digit[b];
+        const int d = digit[b];
         if (d == 0) continue;
         const int m = d < 0 ? -d : d;
         if (m == 1) {
@@ -217,6 +213,51 @@ __global__ __launch_bounds__(128) void scale_kernel(const u32* __restrict__ pts,
     Fq ax, ay;
     xyzz_to_affine(ax, ay, acc);
     S1::store_mont(o, ax, ay);
+}
+__global__ __launch_bounds__(128) void scale_kernel(const u32* __restrict__ pts, u64 n, WnafArgs a, u32* __restrict__ out) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fq x, y;
+    S1::load(pts + i * 16, x, y);
+    u32* o = out + i * 16;
+    if (a.top < 0 || affine_is_inf(x, y)) { zero_record<16>(o); return; }
+    scale_walk(a.digit, a.top, x, y, o);
+}
+
+// ---- the delta step of an UltraGroth key: up to three segments (C1, C2, H), each with a scalar of its own ----
+// A segment starts at a workgroup boundary (first_block) and its digit string is chosen by blockIdx alone, so a whole workgroup
+// -- every wave of the launch, in fact, within a segment -- takes the same branch at every step, as in scale_kernel. A lane
+// gathers its source record through the segment's index list (null: record i). top = -1: the scalar 0, all-zero records;
+// top = -2: the scalar 1, the gathered record as it is, no walk.
+constexpr int SEG_BLOCK = 128;
+struct SegArgs {
+    const u32* src;                              // the segment's source records, device form
+    const u32* index;                            // count indexes into src, or null
+    u32* out;
+    u32 count, first_block;
+    int top;
+};
+struct SegmentsArgs {
+    SegArgs seg[MAX_SCALE_SEGS];
+    int8_t digit[MAX_SCALE_SEGS][256];
+    int n;
+};
+__global__ __launch_bounds__(SEG_BLOCK) void scale_segments_kernel(SegmentsArgs a) {
+    int s = 0;
+#pragma unroll
+    for (int k = 1; k < MAX_SCALE_SEGS; k++)
+        if (k < a.n && blockIdx.x >= a.seg[k].first_block) s = k;
+    const SegArgs& g = a.seg[s];
+    const u32 i = (blockIdx.x - g.first_block) * SEG_BLOCK + threadIdx.x;
+    if (i >= g.count) return;
+    u32* o = g.out + (size_t)i * 16;
+    if (g.top == -1) { zero_record<16>(o); return; }
+    const size_t from = g.index ? g.index[i] : i;
+    Fq x, y;
+    S1::load(g.src + from * 16, x, y);
+    if (affine_is_inf(x, y)) { zero_record<16>(o); return; }
+    if (g.top == -2) { S1::store_mont(o, x, y); return; }
+    scale_walk(a.digit[s], g.top, x, y, o);
 }
 
 // ---- host side ----
@@ -362,6 +403,59 @@ void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* 
     timer.resolve();
     volatile int8_t* w = a.digit;                // (the digits are 1 / delta)
     for (int i = 0; i < 256; i++) w[i] = 0;
+    if (ms) ms[0] = sink.ms;
+}
+
+// One launch for all segments. Segments that name the same source array share one upload (C1 and C2 both gather from the K
+// records); every index was checked against nSrc by the caller.
+void device_points_scale_segments(hipStream_t stream, StreamTimer& timer, const ScaleSeg* segs, int n, double* ms) {
+    if (ms) ms[0] = 0;
+    if (n < 0 || n > MAX_SCALE_SEGS) throw SetupError("internal: " + std::to_string(n) + " segments");
+    SegmentsArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n;
+    const uint8_t one[32] = {1};
+    DevBuf<u32> dSrc[MAX_SCALE_SEGS], dIndex[MAX_SCALE_SEGS], dOut[MAX_SCALE_SEGS];
+    u64 blocks = 0;
+    for (int s = 0; s < n; s++) {
+        const ScaleSeg& g = segs[s];
+        if (g.count > 0xffffffffull || g.nSrc > 0xffffffffull || blocks + grid_for(g.count, SEG_BLOCK) > 0x7fffffffull)
+            throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+        a.seg[s].count = (u32)g.count;
+        a.seg[s].first_block = (u32)blocks;
+        blocks += grid_for(g.count, SEG_BLOCK);
+        a.seg[s].top = !memcmp(g.scalar, one, 32) ? -2 : recodeWnaf(g.scalar, SCALE_WINDOW, a.digit[s]);
+        if (!g.count) continue;
+        int same = -1;
+        for (int t = 0; t < s; t++)
+            if (segs[t].count && segs[t].src == g.src && segs[t].nSrc == g.nSrc) { same = t; break; }
+        if (same >= 0) a.seg[s].src = a.seg[same].src;
+        else {
+            dSrc[s].alloc(std::max<u64>(g.nSrc, 1) * 16);
+            if (g.nSrc) UG_HIP(hipMemcpyAsync(dSrc[s].p, g.src, g.nSrc * 64, hipMemcpyHostToDevice, stream));
+            convert_points_g1(dSrc[s].p, g.nSrc, stream);
+            a.seg[s].src = dSrc[s].p;
+        }
+        if (g.index) {
+            upload(dIndex[s], g.index, g.count, stream);
+            a.seg[s].index = dIndex[s].p;
+        }
+        dOut[s].alloc(g.count * 16);
+        a.seg[s].out = dOut[s].p;
+    }
+    TimeSink sink;
+    if (blocks) {
+        StreamTimer::Scope sc = timer.time(stream, &sink);
+        hipLaunchKernelGGL(scale_segments_kernel, dim3((unsigned)blocks), dim3(SEG_BLOCK), 0, stream, a);
+        UG_KERNEL_CHECK();
+        sc.stop();
+    }
+    for (int s = 0; s < n; s++)
+        if (segs[s].count) UG_HIP(hipMemcpyAsync(segs[s].out, dOut[s].p, segs[s].count * 64, hipMemcpyDeviceToHost, stream));
+    UG_HIP(hipStreamSynchronize(stream));
+    timer.resolve();
+    volatile int8_t* w = &a.digit[0][0];         // (the digits are 1 / delta)
+    for (int i = 0; i < MAX_SCALE_SEGS * 256; i++) w[i] = 0;
     if (ms) ms[0] = sink.ms;
 }
 

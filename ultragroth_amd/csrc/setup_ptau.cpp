@@ -1,12 +1,14 @@
 // setup_ptau.cpp -- the phase-2 setup from a prepared powers-of-tau file (include/ultragroth_hip.h: ug_ptau_parse_info,
 // ug_setup_ptau_*, ug_points_combine, ug_points_scale): what `snarkjs zkey new` does for a Groth16 circuit, then optionally one
-// delta contribution. No trapdoor is known here. Out of scope: UltraGroth keys, contribution transcripts, beacons, verifying the
+// delta contribution; and the same for an UltraGroth key (ug_ultra_setup_ptau_*, ug_points_scale_segments): two deltas, the C points
+// in two sections by the caller's lists. No trapdoor is known here. Out of scope: contribution transcripts, beacons, verifying the
 // .ptau's own ceremony.
 //
 // The .ptau reader is host_util.cpp's, the point check point_check.cpp's; the circuit, the column index, section 4, the headers and the JSON are setup_host.cpp's,
 // shared, not copied. What is new is the order of work: a real setup has no scalars per wire, it combines POINTS per wire
-// (Backend::combine) and multiplies the private C points and H by 1 / delta (Backend::scale). K_s is one combination over the
-// three level-n slices side by side: an A term (k, s) names bT[k], a B term aT[k], a C term T[k].
+// (Backend::combine) and multiplies the private C points and H by 1 / delta (Backend::scale; an UltraGroth key: C1 by 1 / delta_round,
+// C2 and H by 1 / delta_final, gathered through the lists, Backend::scaleSegments). K_s is one combination over the three level-n
+// slices side by side: an A term (k, s) names bT[k], a B term aT[k], a C term T[k].
 #include "setup_host.hpp"
 
 #include <algorithm>
@@ -21,12 +23,32 @@ namespace {
 
 constexpr int PTAU_PHASES = UG_SETUP_PTAU_PHASES;
 
+// what a run reads of either options struct; ultra: null for a Groth16 key
+struct Request {
+    u32 logDomain, validate, contribute;
+    const uint8_t* deltaRound;                   // (an UltraGroth key only)
+    const uint8_t* deltaFinal;
+    const ug_ultra_setup_ptau_options* ultra;
+};
+
 void checkOptions(const ug_setup_ptau_options* o) {
     checkOptionsHead<SetupError>(o, 0, 2, "0, 1 or 2");
     if (o->contribute > 2) throw SetupError("contribute " + std::to_string(o->contribute) + " is not 0, 1 or 2");
     if (o->contribute == 1) {
         if (!belowR(o->delta)) throw SetupError("delta is not below the field modulus");
         if (allZero(o->delta, 32)) throw SetupError("delta is 0 mod r");
+    }
+}
+
+void checkOptions(const ug_ultra_setup_ptau_options* o) {
+    checkOptionsHead<SetupError>(o, 0, 2, "0, 1 or 2");
+    if (o->contribute > 2) throw SetupError("contribute " + std::to_string(o->contribute) + " is not 0, 1 or 2");
+    if (o->contribute == 1) {
+        const struct { const char* name; const uint8_t* v; } deltas[2] = {{"delta_round", o->delta_round}, {"delta_final", o->delta_final}};
+        for (const auto& d : deltas) {
+            if (!belowR(d.v)) throw SetupError(std::string(d.name) + " is not below the field modulus");
+            if (allZero(d.v, 32)) throw SetupError(std::string(d.name) + " is 0 mod r");
+        }
     }
 }
 
@@ -57,6 +79,10 @@ struct Delta {
         set(d);
         wipe(d);
     }
+    void contribute(u32 how, const uint8_t* given) {
+        if (how == 1) set(given);
+        else if (how == 2) draw();
+    }
 };
 
 // K's columns: wire s lists its A terms (points bT, segment 2), its B terms (aT, segment 1) and its C terms (T, segment 0)
@@ -84,16 +110,15 @@ void mergedColumns(const ColMatrix cm[3], u64 M, u64 N, std::vector<u32>& colPtr
     });
 }
 
-u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
+u64 runPtau(const Request& rq, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
             u64 zkeyCap, std::string* vkey, double ms[PTAU_PHASES], bool sizeOnly, u64* vkeyMax) {
-    for (int i = 0; i < PTAU_PHASES; i++) ms[i] = 0;
     PhaseClock clock(ms);
-    checkOptions(opt);
     std::unique_ptr<BinFile> f;
     R1cs cs;
     loadCircuit(r1cs, r1csSize, f, cs.hdr);
     Plan p;
-    planSizes(cs.hdr, opt->log_domain, p);
+    planSizes(cs.hdr, rq.logDomain, p);
+    if (rq.ultra) planLists(p, rq.ultra->rand_indx, rq.ultra->round_signals, rq.ultra->n_round, rq.ultra->final_signals, rq.ultra->n_final);
     // every rule of the .ptau before the constraints are walked, and before the first device byte
     const std::unique_ptr<BinFile> pf = openBinFile(ptau, ptauSize, "ptau", "ptau: ", "null ptau buffer");
     const PtauHeader ph = loadPtauHeader(*pf);
@@ -112,12 +137,12 @@ u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, co
     buildColumns(cs, p, cm, pieces);
     const u64 N = p.N, M = p.nVars, pub = (u64)p.nPublic + 1;
     // H's sources: the odd records of level n + 1, side by side
-    uint8_t* hOut = zkey + lay.offsetOf(9);
+    uint8_t* hOut = zkey + lay.offsetOf(p.ultra ? 12 : 9);
     writeContainer(zkey, lay);
     gatherOddTop(sl, hOut);
     clock.lap(0);
 
-    checkSlices(PointCheck(device, (int)opt->validate), sl, hOut);
+    checkSlices(PointCheck(device, (int)rq.validate), sl, hOut);
     clock.lap(1);
 
     double kms[2];
@@ -141,10 +166,18 @@ u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, co
     be.combine(true, M, cm[1].colPtr.data(), cm[1].row.data(), cm[1].val.data(), one, zkey + lay.offsetOf(7), kms);
     clock.lap(3);
 
-    Delta delta;
-    if (opt->contribute == 1) delta.set(opt->delta);
-    else if (opt->contribute == 2) delta.draw();
-    if (!delta.one) {                            // the private C points and H, one launch: (1 / delta) * each
+    Delta delta, deltaRound;                     // (the final delta: the only one of a Groth16 key)
+    delta.contribute(rq.contribute, rq.deltaFinal);
+    if (p.ultra) {                               // C1, C2 and H, one launch: the gather through the lists and (1 / its delta) * each
+        deltaRound.contribute(rq.contribute, rq.deltaRound);
+        ScaleSeg segs[3];
+        segs[0].scalar = deltaRound.inverse; segs[0].src = krec.data(); segs[0].nSrc = M;
+        segs[0].index = p.roundSignals.data(); segs[0].count = p.roundSignals.size(); segs[0].out = zkey + lay.offsetOf(8);
+        segs[1].scalar = delta.inverse; segs[1].src = krec.data(); segs[1].nSrc = M;
+        segs[1].index = p.finalSignals.data(); segs[1].count = p.finalSignals.size(); segs[1].out = zkey + lay.offsetOf(9);
+        segs[2].scalar = delta.inverse; segs[2].src = hOut; segs[2].nSrc = N; segs[2].count = N; segs[2].out = hOut;
+        be.scaleSegments(segs, 3, kms);
+    } else if (!delta.one) {                     // the private C points and H, one launch: (1 / delta) * each
         const u64 nc = M - pub;
         std::vector<uint8_t> in((nc + N) * 64), out((nc + N) * 64);
         if (nc) memcpy(in.data(), &krec[pub * 64], nc * 64);
@@ -158,20 +191,40 @@ u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, co
     HeaderPoints hp;
     memset(&hp, 0, sizeof hp);
     {
-        uint8_t sc[2][32];
+        uint8_t sc[3][32];
         memset(sc, 0, sizeof sc);
         sc[0][0] = 1;                            // gamma = 1: the generator
         memcpy(sc[1], delta.value, 32);
-        uint8_t g1[2][64], g2[2][128];
-        hostBackend().generatorMul(false, sc[0], 2, 0, g1[0], nullptr);
-        hostBackend().generatorMul(true, sc[0], 2, 0, g2[0], nullptr);
+        memcpy(sc[2], deltaRound.value, 32);
+        uint8_t g1[3][64], g2[3][128];
+        const u64 nsc = p.ultra ? 3 : 2;
+        hostBackend().generatorMul(false, sc[0], nsc, 0, g1[0], nullptr);
+        hostBackend().generatorMul(true, sc[0], nsc, 0, g2[0], nullptr);
         Delta::wipe(sc[1]);
+        Delta::wipe(sc[2]);
         memcpy(hp.g1[0], sl.alpha1, 64); memcpy(hp.g1[1], sl.beta1, 64); memcpy(hp.g1[3], g1[1], 64);
         memcpy(hp.g2[0], sl.beta2, 128); memcpy(hp.g2[1], g2[0], 128); memcpy(hp.g2[3], g2[1], 128);
+        if (p.ultra) { memcpy(hp.g1[2], g1[2], 64); memcpy(hp.g2[2], g2[2], 128); }
     }
-    finishKey(cs, p, lay, perPiece, hp, krec, zkey, vkey);
+    finishKey(cs, p, lay, perPiece, hp, krec, zkey, vkey, p.ultra);
     clock.lap(5);
     return lay.total;
+}
+
+// every rule of the options, then the run
+u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
+            u64 zkeyCap, std::string* vkey, double ms[PTAU_PHASES], bool sizeOnly, u64* vkeyMax) {
+    for (int i = 0; i < PTAU_PHASES; i++) ms[i] = 0;
+    checkOptions(opt);
+    const Request rq = {opt->log_domain, opt->validate, opt->contribute, nullptr, opt->delta, nullptr};
+    return runPtau(rq, r1cs, r1csSize, ptau, ptauSize, device, zkey, zkeyCap, vkey, ms, sizeOnly, vkeyMax);
+}
+u64 runPtau(const ug_ultra_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
+            u64 zkeyCap, std::string* vkey, double ms[PTAU_PHASES], bool sizeOnly, u64* vkeyMax) {
+    for (int i = 0; i < PTAU_PHASES; i++) ms[i] = 0;
+    checkOptions(opt);
+    const Request rq = {opt->log_domain, opt->validate, opt->contribute, opt->delta_round, opt->delta_final, opt};
+    return runPtau(rq, r1cs, r1csSize, ptau, ptauSize, device, zkey, zkeyCap, vkey, ms, sizeOnly, vkeyMax);
 }
 
 void checkColumns(const u32* colPtr, u64 nCols, const u32* index, const uint8_t* coefs, u64 nPoints) {
@@ -235,6 +288,32 @@ int ug_setup_ptau_run(const ug_setup_ptau_options* opt, const void* r1cs, uint64
     });
 }
 
+int ug_ultra_setup_ptau_size(const ug_ultra_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                             uint64_t ptau_size, uint64_t* zkey_bytes, uint64_t* vkey_bytes_max, char* error_msg,
+                             unsigned long long error_msg_maxsize) {
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        double ms[PTAU_PHASES];
+        u64 vmax = 0;
+        const u64 total = runPtau(opt, r1cs, r1cs_size, ptau, ptau_size, -1, nullptr, 0, nullptr, ms, true, &vmax);
+        if (zkey_bytes) *zkey_bytes = total;
+        if (vkey_bytes_max) *vkey_bytes_max = vmax;
+    });
+}
+
+int ug_ultra_setup_ptau_run(const ug_ultra_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                            uint64_t ptau_size, int device, void* zkey, uint64_t zkey_capacity, uint64_t* zkey_bytes, char* vkey_json,
+                            uint64_t vkey_capacity, uint64_t* vkey_bytes, double* phase_ms, char* error_msg,
+                            unsigned long long error_msg_maxsize) {
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        double ms[PTAU_PHASES];
+        std::string vkey;
+        const u64 total = runPtau(opt, r1cs, r1cs_size, ptau, ptau_size, device, (uint8_t*)zkey, zkey_capacity, &vkey, ms, false, nullptr);
+        if (zkey_bytes) *zkey_bytes = total;
+        copyVkey(vkey, vkey_json, vkey_capacity, vkey_bytes);
+        if (phase_ms) for (int i = 0; i < PTAU_PHASES; i++) phase_ms[i] = ms[i];
+    });
+}
+
 int ug_points_combine(int device, int g2, const uint32_t* col_ptr, uint64_t n_cols, const uint32_t* index, const void* coefs,
                       const void* points, uint64_t n_points, void* out, double* kernel_ms, char* error_msg,
                       unsigned long long error_msg_maxsize) {
@@ -261,6 +340,36 @@ int ug_points_scale(int device, const void* scalar, const void* points, uint64_t
         if (!n) return;
         std::unique_ptr<Backend> owned;
         backendFor(device, owned).scale((const uint8_t*)scalar, (const uint8_t*)points, n, (uint8_t*)out, kernel_ms);
+    });
+}
+
+int ug_points_scale_segments(int device, int n_segments, const ug_scale_segment* segments, const void* points, uint64_t n_points,
+                             void* out, double* kernel_ms, char* error_msg, unsigned long long error_msg_maxsize) {
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        if (kernel_ms) kernel_ms[0] = 0;
+        if (n_segments < 0 || n_segments > MAX_SCALE_SEGS) throw SetupError(std::to_string(n_segments) + " segments: at most " + std::to_string(MAX_SCALE_SEGS));
+        if (n_segments && !segments) throw SetupError("null buffer");
+        if (n_points > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+        ScaleSeg segs[MAX_SCALE_SEGS];
+        u64 total = 0;
+        for (int s = 0; s < n_segments; s++) {
+            const ug_scale_segment& g = segments[s];
+            if (!g.scalar) throw SetupError("null buffer");
+            if (!belowR((const uint8_t*)g.scalar)) throw SetupError("segment " + std::to_string(s) + ": scalar is not below the field modulus");
+            if (g.count > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+            if (!g.index && g.count > n_points) throw SetupError("segment " + std::to_string(s) + ": " + std::to_string(g.count) + " records of " + std::to_string(n_points));
+            if (g.index)
+                for (u64 i = 0; i < g.count; i++)
+                    if (g.index[i] >= n_points)
+                        throw SetupError("segment " + std::to_string(s) + " index " + std::to_string(i) + ": point " + std::to_string(g.index[i]) + " out of range");
+            segs[s].scalar = (const uint8_t*)g.scalar; segs[s].src = (const uint8_t*)points; segs[s].nSrc = n_points;
+            segs[s].index = g.index; segs[s].count = g.count; segs[s].out = (uint8_t*)out + total * 64;
+            total += g.count;
+        }
+        if (!total) return;
+        if (!out || !points) throw SetupError("null buffer");
+        std::unique_ptr<Backend> owned;
+        backendFor(device, owned).scaleSegments(segs, n_segments, kernel_ms);
     });
 }
 

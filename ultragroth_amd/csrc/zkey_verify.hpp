@@ -1,5 +1,5 @@
 // zkey_verify.hpp -- what the check of a Groth16 key against its circuit and powers of tau (zkey_verify_host.cpp) hands to the code
-// that evaluates the twelve sums of its relations: host threads (zkey_verify_host.cpp) or the device (zkey_verify.hip).
+// that evaluates the twelve sums of its relations (fourteen for an UltraGroth key, ug_ultra_zkey_verify_run): host threads (zkey_verify_host.cpp) or the device (zkey_verify.hip).
 #pragma once
 #include <cstdint>
 #include "host_util.hpp"
@@ -19,6 +19,13 @@ struct Inputs {
     const uint8_t* top = nullptr;                 // level n + 1 of section 12: 2 N records, H's sources are the odd ones
     const uint8_t* rho = nullptr;                 // M plain 32-byte integers below 2^128
     const uint8_t* sigma = nullptr;               // N of them
+    // An UltraGroth key (ug_ultra_zkey_verify_run): c is section 8 (C1, n1 records), c2 section 9 (C2, n2), h section 12; cls has one
+    // byte per wire, 0 public, 1 round, 2 final; rhoRound[i] = rho[round list[i]], rhoFinal likewise (the gather is a host step)
+    bool ultra = false;
+    const uint8_t* c2 = nullptr;
+    uint64_t n1 = 0, n2 = 0;
+    const uint8_t* cls = nullptr;
+    const uint8_t *rhoRound = nullptr, *rhoFinal = nullptr;
 };
 
 // the sums of the relations as zkey-format records (all-zero = infinity); canonical, so both evaluators give the same bytes
@@ -27,6 +34,7 @@ struct Sums {
     uint8_t aT[64], bT[64], bT2[128];                                            // MSM(a, T), MSM(b, T), MSM(b, T2)
     uint8_t kPub[64], kPriv[64];                                                 // K^pub, K^priv
     uint8_t hP[64];                                                              // MSM(sigma, odd records of P)
+    uint8_t keyC2[64], kFinal[64];               // an UltraGroth key: keyC, kPriv are C1's and K^round, these C2's and K^final
 };
 
 // ms: fold (circuit upload + kernel), slice products, key products, H products; fold_kernel_ms: the kernel alone
@@ -38,6 +46,11 @@ typedef void (*DeviceFold)(int device, const void* r1cs, uint64_t r1csSize, cons
 // set by zkey_verify.hip when that is linked in (null in a host-only program)
 extern DeviceSums deviceSums;
 extern DeviceFold deviceFold;
+// the same for an UltraGroth key: the fold with a class per wire (eleven vectors: a^m, b^m, c^m for m = pub, round, final, then a, b)
+typedef void (*DeviceFoldClasses)(int device, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, const uint8_t* cls, uint32_t nPublic,
+                                  uint32_t logN, uint8_t* out11, double* kernelMs);
+extern DeviceSums deviceUltraSums;
+extern DeviceFoldClasses deviceFoldClasses;
 
 }  // namespace zkv
 }  // namespace ughost
