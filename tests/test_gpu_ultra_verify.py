@@ -50,6 +50,15 @@ def test_invalid_keys_get_the_host_path_s_verdict(device, case_id):
     assert got == ug.ultra_zkey_verify(r1cs, ptau, zkey, ultra=spec, device=-1)
 
 
+@pytest.mark.parametrize("case_id", UC.COMPOUND_IDS + UC.HEADER_ORDER_IDS)
+def test_several_planted_changes_and_the_header_rules_order(device, case_id):
+    import ultragroth_amd as ug
+    r1cs, ptau, zkey, spec, failing, first, message = UC.invalid_cases()[case_id]
+    got = ug.ultra_zkey_verify(r1cs, ptau, zkey, ultra=spec, device=0)
+    assert got == (first, failing, message)
+    assert got == ug.ultra_zkey_verify(r1cs, ptau, zkey, ultra=spec, device=-1)
+
+
 @pytest.mark.parametrize("case_id", UC.REFUSAL_IDS)
 def test_refusals(device, case_id):
     import ultragroth_amd as ug

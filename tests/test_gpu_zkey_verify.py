@@ -60,6 +60,15 @@ def test_one_planted_change_fails_exactly_its_sections(case):
     assert got == ug.zkey_verify(r1cs, ptau, zkey, device=-1)
 
 
+@pytest.mark.parametrize("case", ZC.COMPOUND_IDS + ZC.HEADER_ORDER_IDS)
+def test_several_planted_changes_and_the_header_rules_order(case):
+    ug = _ug()
+    r1cs, ptau, zkey, failing, first, message = ZC.invalid_cases()[case]
+    got = ug.zkey_verify(r1cs, ptau, zkey, device=0)
+    assert got == (first, failing, message)
+    assert got == ug.zkey_verify(r1cs, ptau, zkey, device=-1)
+
+
 @pytest.mark.parametrize("case", ZC.REFUSAL_IDS)
 def test_refusals(case):
     ug = _ug()

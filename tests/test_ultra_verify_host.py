@@ -75,6 +75,21 @@ def test_invalid_keys_fail_exactly_the_named_sections(case_id):
     assert ug.ultra_zkey_verify(r1cs, ptau, zkey, ultra=spec, device=-1) == (first, failing, message)
 
 
+@pytest.mark.parametrize("case_id", UC.COMPOUND_IDS)
+def test_several_planted_changes_report_every_section_and_the_first_relation(case_id):
+    ug = _ug()
+    r1cs, ptau, zkey, spec, failing, first, message = UC.invalid_cases()[case_id]
+    assert ug.ultra_zkey_verify(r1cs, ptau, zkey, ultra=spec, device=-1) == (first, failing, message)
+
+
+@pytest.mark.parametrize("case_id", UC.HEADER_ORDER_IDS)
+def test_header_rules_are_tried_in_their_order(case_id):
+    """two header rules broken at once: the message is the earlier rule's -- gamma2 at infinity comes before the deltas"""
+    ug = _ug()
+    r1cs, ptau, zkey, spec, failing, first, message = UC.invalid_cases()[case_id]
+    assert ug.ultra_zkey_verify(r1cs, ptau, zkey, ultra=spec, device=-1) == (first, failing, message)
+
+
 @pytest.mark.parametrize("case_id", UC.REFUSAL_IDS)
 def test_refusals(case_id):
     ug = _ug()

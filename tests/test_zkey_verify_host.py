@@ -73,6 +73,29 @@ def test_one_planted_change_fails_exactly_its_sections(case):
     assert ug.zkey_verify(r1cs, ptau, zkey, device=-1) == (first, failing, message)
 
 
+@pytest.mark.parametrize("case", ZC.COMPOUND_IDS)
+def test_several_planted_changes_report_every_section_and_the_first_relation(case):
+    ug = _ug()
+    r1cs, ptau, zkey, failing, first, message = ZC.invalid_cases()[case]
+    assert ug.zkey_verify(r1cs, ptau, zkey, device=-1) == (first, failing, message)
+
+
+@pytest.mark.parametrize("case", ZC.HEADER_ORDER_IDS)
+def test_header_rules_are_tried_in_their_order(case):
+    """two header rules broken at once: the message is the earlier rule's -- delta1 / delta2 at infinity come before gamma2"""
+    ug = _ug()
+    r1cs, ptau, zkey, failing, first, message = ZC.invalid_cases()[case]
+    assert ug.zkey_verify(r1cs, ptau, zkey, device=-1) == (first, failing, message)
+
+
+def test_a_circuit_of_public_wires_only_has_an_empty_section_8():
+    ug = _ug()
+    r1cs, ptau, zkey = ZC.all_public_case()
+    assert ug.zkey_verify(r1cs, ptau, zkey, device=-1) is None
+    secs = dict(RC.sections(zkey))
+    assert ug.zkey_verify(r1cs, ptau, PC.with_sections(zkey, {3: ZC.swapped(secs[3], 64)}), device=-1) == (3, [3], ZC.section_message(3))
+
+
 @pytest.mark.parametrize("case", ZC.REFUSAL_IDS)
 def test_refusals(case):
     ug = _ug()

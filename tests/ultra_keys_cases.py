@@ -146,6 +146,7 @@ def fold_classes_reference(rows, n_public, rho, cls, log_n):
 SECTION_TEXT = "zkey: section %d: does not match the circuit and the powers of tau"
 ULTRA_HEADER_POINTS = 4 + 32 + 4 + 32 + 12 + 12  # section 2 of a protocol-1337 key: ..., nVars, nPublic, domain, n1, n2, rand_indx; then the points
 DELTA_C1 = ULTRA_HEADER_POINTS + 64 + 64 + 128 + 128
+GAMMA2 = ULTRA_HEADER_POINTS + 64 + 64 + 128
 
 
 def section_message(sid):
@@ -237,12 +238,29 @@ def invalid_cases():
     other = irregular("descending")[1]
     add("spec-lists-differ", [10, 11], 10, "zkey: section 10: does not match the spec", use_spec=other)
     add("spec-rand-indx-differs", [2], 2, "zkey: header: rand_indx does not match the spec", use_spec=dict(spec, rand_indx=2))
+    # ---- several planted changes in one key (COMPOUND_IDS): every failing section is reported, the first relation in the check's
+    # order -- header, section 4, the spec (2, 10, 11), then 5, 6, 7, 3, 8, 9, 12 -- gives `first` and the message
+    record = 17
+    coefs = bytearray(secs[4])
+    assert len(coefs) > 4 + 44 * (record + 1)
+    coefs[4 + 44 * record + 12 + 5] ^= 0x10
+    add("section-4-byte-c2-swapped-h-under-delta-round-other-spec", [4, 9, 10, 11, 12], 4, "zkey: section 4 record %d: does not match the circuit" % record,
+        PC.with_sections(key, {4: bytes(coefs), 9: ZC.swapped(secs[9], 64), 12: both_round[12]}), use_spec=other)
+    add("c1-under-delta-final-h-under-delta-round", [8, 12], 8, section_message(8), PC.with_sections(key, {8: both_final[8], 12: both_round[12]}))
+    # ---- the header's rules in their order (HEADER_ORDER_IDS): gamma2 is tried before the deltas. The point check lets an all-zero
+    # record (infinity) through; gamma2 at infinity also fails section 3, delta_c1's G1 point is in no relation but the header's own
+    header = bytearray(secs[2])
+    header[GAMMA2:GAMMA2 + 128] = bytes(128)
+    header[DELTA_C1:DELTA_C1 + 64] = bytes(64)
+    add("gamma2-and-delta-c1-at-infinity", [2, 3], 2, "zkey: header: gamma2 is the point at infinity", PC.with_sections(key, {2: bytes(header)}))
     return out
 
 
 INVALID_IDS = ("c1-records-swapped", "section-10-entries-swapped", "section-10-entries-swapped-with-spec", "signal-moved-to-the-final-round",
                "signal-moved-to-the-final-round-with-spec", "c1-under-delta-final", "h-under-delta-round", "delta-c1-pair-disagrees",
                "r1cs-c-coefficient", "spec-lists-differ", "spec-rand-indx-differs")
+COMPOUND_IDS = ("section-4-byte-c2-swapped-h-under-delta-round-other-spec", "c1-under-delta-final-h-under-delta-round")
+HEADER_ORDER_IDS = ("gamma2-and-delta-c1-at-infinity",)
 
 
 @functools.lru_cache(maxsize=None)

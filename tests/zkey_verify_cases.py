@@ -4,7 +4,8 @@ include/ultragroth_hip.h ug_zkey_verify_run / ug_r1cs_fold through ultragroth_am
 The references: for the fold, Python integers over the case builders' rows; for a verdict, how the key was made -- a key of
 setup_from_ptau (pinned byte for byte against dev_setup by test_setup_ptau_host.py) or dev_setup's own is valid, and every
 invalid key is ONE planted change to such a key whose effect on each relation is known in advance, so the exact set of failing
-sections and the message are asserted. Every builder is deterministic (but for the drawn delta, which nobody reads) and cached:
+sections and the message are asserted (COMPOUND_IDS and HEADER_ORDER_IDS plant several such changes in one key: the sections add
+up, the first relation in the check's order gives the message). Every builder is deterministic (but for the drawn delta, which nobody reads) and cached:
 the two files share one copy, which nobody changes. Every key and every .ptau is made on host threads."""
 import functools
 import random
@@ -130,6 +131,7 @@ def valid_case(case_id):
 # ------------------------------------------------------------------------------------------- planted changes
 HEADER_POINTS = 4 + 32 + 4 + 32 + 12             # section 2: n8q, q, n8r, r, nVars, nPublic, domain; then the points
 ALPHA1, BETA1, DELTA1 = HEADER_POINTS, HEADER_POINTS + 64, HEADER_POINTS + 64 + 64 + 128 + 128
+GAMMA2 = HEADER_POINTS + 64 + 64 + 128
 SECTION_RECORD = {3: 64, 5: 64, 6: 64, 7: 128, 8: 64, 9: 64}
 
 
@@ -225,12 +227,40 @@ def invalid_cases():
     n_rows = len(SC.odd_circuit(12, 1, 2)[1])
     add("r1cs-c-coefficient-private", [8], 8, section_message(8), r1cs=c_coefficient_changed(r1cs, 3, 0))
     add("r1cs-c-coefficient-public", [3], 3, section_message(3), r1cs=c_coefficient_changed(r1cs, n_rows - 1, 0))
+    # ---- several planted changes in one key (COMPOUND_IDS): every failing section is reported, the first relation in the check's
+    # order -- header, section 4, then 5, 6, 7, 3, 8, 9 -- gives `first` and the message
+    swap3, swap5 = swapped(secs[3], 64), swapped(secs[5], 64)
+    add("section-4-byte-swap-3-other-delta-9", [3, 4, 9], 4, "zkey: section 4 record %d: does not match the circuit" % record,
+        PC.with_sections(key, {4: bytes(coefs), 3: swap3, 9: other_secs[9]}))
+    add("swap-3-and-5", [3, 5], 5, section_message(5), PC.with_sections(key, {3: swap3, 5: swap5}))
+    # ---- the header's rules in their order (HEADER_ORDER_IDS). The point check lets an all-zero record (infinity) through. gamma2 at
+    # infinity also fails section 3, whose relation stands under gamma2; delta1 is in no relation but the header's own
+    zero = lambda sec, at, size: sec[:at] + bytes(size) + sec[at + size:]
+    add("gamma2-and-delta1-at-infinity", [2, 3], 2, "zkey: header: delta1 is the point at infinity",
+        PC.with_sections(key, {2: zero(zero(secs[2], GAMMA2, 128), DELTA1, 64)}))
+    header = secs[2][:ALPHA1] + secs[2][BETA1:BETA1 + 64] + secs[2][ALPHA1 + 64:DELTA1] + other_secs[2][DELTA1:DELTA1 + 64] + secs[2][DELTA1 + 64:]
+    add("alpha1-is-beta1-and-delta1-of-another-key", [2], 2, "zkey: header: alpha1 is not the powers of tau's", PC.with_sections(key, {2: header}))
     return out
 
 
 INVALID_IDS = tuple("swap-%d" % s for s in (5, 6, 7, 3, 8, 9)) + (
     "plus-minus-5", "other-delta-8", "other-delta-9", "delta1-of-another-key", "alpha1-is-beta1", "section-4-byte",
     "dev-setup-against-power-5", "ptau-of-tau-plus-1", "r1cs-c-coefficient-private", "r1cs-c-coefficient-public")
+COMPOUND_IDS = ("section-4-byte-swap-3-other-delta-9", "swap-3-and-5")
+HEADER_ORDER_IDS = ("gamma2-and-delta1-at-infinity", "alpha1-is-beta1-and-delta1-of-another-key")
+
+
+@functools.lru_cache(maxsize=None)
+def all_public_case():
+    """(r1cs, ptau, zkey): a circuit whose every wire is public (nVars = nPublic + 1), so the key's section 8 is empty; its key is
+    setup_from_ptau's and valid"""
+    import ultragroth_amd as ug
+    rows = [({1: 1}, {2: 1}, {3: 1}), ({3: 1, 0: R - 1}, {1: 1}, {2: 5, 0: 7})]
+    r1cs = synth.r1cs_file(4, 1, 2, rows)
+    ptau = PC.ptau(6)
+    zkey = ug.setup_from_ptau(r1cs, ptau, delta=FIXED_DELTA, device=-1)[0]
+    assert SC.zkey_header(zkey)[:2] == (4, 3) and dict(RC.sections(zkey))[8] == b""
+    return r1cs, ptau, zkey
 
 
 @functools.lru_cache(maxsize=None)

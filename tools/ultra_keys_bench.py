@@ -8,14 +8,16 @@ records.
                                                                      on the keys just made; then the delta step's kernel alone
                                                                      (scale_segments_kernel over the key's three segments,
                                                                      stream events) beside scale_kernel
-    python tools/ultra_keys_bench.py groth16 <mix> <log> <out.json>  ONE run of the Groth16 calls this change must leave alone,
-                                                                     setup_from_ptau then zkey_verify, with the package and
-                                                                     library of the checkout that ULTRAGROTH_TREE names (default:
-                                                                     this one): times and the outputs' SHA-256
+    python tools/ultra_keys_bench.py one <mix> <log> <out.json>      ONE run of both protocols' calls, setup_from_ptau then
+                                                                     zkey_verify and ultra_setup_from_ptau then ultra_zkey_verify
+                                                                     (validate 1), with the package and library of the checkout
+                                                                     that ULTRAGROTH_TREE names (default: this one): times, the
+                                                                     keys' SHA-256, the verdicts and the checks' peak device bytes
     python tools/ultra_keys_bench.py ab <mix> <log> <tree_a> <tree_b> [runs]
-                                                                     the `groth16` run in fresh child processes, two built
+                                                                     the `one` run in fresh child processes, two built
                                                                      checkouts (a parent commit's and this one) alternating,
-                                                                     `runs` (3) times each
+                                                                     `runs` (3) times each; says per protocol whether the key,
+                                                                     the verdict and the peak device bytes agree across all runs
 
 The circuit, the coefficient mixes and the .ptau are setup_ptau_bench's (the squaring chain; a .ptau of valid points that is
 not a ceremony's). The spec: rand_indx = 1 (the chain's one public signal), the private wires alternating between the rounds."""
@@ -66,6 +68,18 @@ def groth16_options():
     return opt
 
 
+def ultra_options(log_n):
+    """the options of the UltraGroth setup and the two lists they point into (keep them alive)"""
+    private = np.arange(2, 1 << log_n, dtype=np.uint32)
+    lists = (np.ascontiguousarray(private[1::2]), np.ascontiguousarray(private[0::2]))
+    uopt = ug._UltraSetupPtauOptions()
+    uopt.size, uopt.validate, uopt.contribute, uopt.rand_indx = C.sizeof(uopt), 1, 1, 1
+    uopt.delta_round, uopt.delta_final = ug._le32(DELTAS[0], "d"), ug._le32(DELTAS[1], "d")
+    uopt.round_signals = lists[0].ctypes.data_as(C.POINTER(C.c_uint32)); uopt.n_round = lists[0].size
+    uopt.final_signals = lists[1].ctypes.data_as(C.POINTER(C.c_uint32)); uopt.n_final = lists[1].size
+    return uopt, lists
+
+
 def setup(mix, logs):
     dev = ug.Device(0)
     L = ug.load()
@@ -74,14 +88,7 @@ def setup(mix, logs):
     for log_n in logs:
         r1cs = mixed_chain(log_n, mix)
         ptau = fake_ptau(dev, log_n)
-        n_wires = (1 << log_n)
-        private = np.arange(2, n_wires, dtype=np.uint32)
-        lists = (np.ascontiguousarray(private[1::2]), np.ascontiguousarray(private[0::2]))
-        uopt = ug._UltraSetupPtauOptions()
-        uopt.size, uopt.validate, uopt.contribute, uopt.rand_indx = C.sizeof(uopt), 1, 1, 1
-        uopt.delta_round, uopt.delta_final = ug._le32(DELTAS[0], "d"), ug._le32(DELTAS[1], "d")
-        uopt.round_signals = lists[0].ctypes.data_as(C.POINTER(C.c_uint32)); uopt.n_round = lists[0].size
-        uopt.final_signals = lists[1].ctypes.data_as(C.POINTER(C.c_uint32)); uopt.n_final = lists[1].size
+        uopt, lists = ultra_options(log_n)
         keys = {}
         for name, opt, fns in (("ultra_setup_from_ptau", uopt, (L.ug_ultra_setup_ptau_size, L.ug_ultra_setup_ptau_run)),
                                ("setup_from_ptau", groth16_options(), (L.ug_setup_ptau_size, L.ug_setup_ptau_run)),
@@ -137,22 +144,34 @@ def setup(mix, logs):
     dev.close()
 
 
-def groth16(mix, log_n, out_path):
+def one(mix, log_n, out_path):
     dev = ug.Device(0)
     L = ug.load()
     r1cs = mixed_chain(log_n, mix)
     ptau = fake_ptau(dev, log_n)
-    whole, raw, zkey = run_setup(L, groth16_options(), L.ug_setup_ptau_size, L.ug_setup_ptau_run, r1cs, ptau, 0)
-    timings = {}
-    t0 = time.time()
-    verdict = ug.zkey_verify(r1cs, memoryview(ptau), memoryview(zkey), device=0, validate=1, timings=timings)
-    verify_ms = (time.time() - t0) * 1e3
-    res = {"tree": os.path.dirname(os.path.dirname(os.path.abspath(ug.__file__))), "setup_ms": whole, "setup_phases": raw, "zkey_sha256": hashlib.sha256(zkey.tobytes()).hexdigest(),
-           "verify_ms": verify_ms, "verify_phases": [timings[k] for k in ug.ZKEY_VERIFY_PHASES],
-           "verdict": None if verdict is None else [verdict[0], list(verdict[1])]}
+    uopt, lists = ultra_options(log_n)
+    res = {"tree": os.path.dirname(os.path.dirname(os.path.abspath(ug.__file__)))}
+    for name, opt, fns, check in (
+            ("groth16", groth16_options(), (L.ug_setup_ptau_size, L.ug_setup_ptau_run),
+             lambda key, t: ug.zkey_verify(r1cs, memoryview(ptau), memoryview(key), device=0, validate=1, timings=t)),
+            ("ultra", uopt, (L.ug_ultra_setup_ptau_size, L.ug_ultra_setup_ptau_run),
+             lambda key, t: ug.ultra_zkey_verify(r1cs, memoryview(ptau), memoryview(key), device=0, validate=1, timings=t))):
+        whole, raw, zkey = run_setup(L, opt, fns[0], fns[1], r1cs, ptau, 0)
+        timings = {}
+        t0 = time.time()
+        verdict = check(zkey, timings)
+        verify_ms = (time.time() - t0) * 1e3
+        res[name] = {"setup_ms": whole, "setup_phases": raw, "zkey_sha256": hashlib.sha256(zkey.tobytes()).hexdigest(),
+                     "verify_ms": verify_ms, "verify_phases": [timings[k] for k in ug.ZKEY_VERIFY_PHASES],
+                     "peak_device_bytes": int(timings["peak_device_bytes"]),
+                     "verdict": None if verdict is None else [verdict[0], list(verdict[1]), verdict[2]]}
+        del zkey
     with open(out_path, "w") as f:
         json.dump(res, f)
     dev.close()
+
+
+SAME = ("zkey_sha256", "verdict", "peak_device_bytes")      # what both checkouts must agree on, per protocol
 
 
 def ab(mix, log_n, lib_a, lib_b, runs):
@@ -162,27 +181,33 @@ def ab(mix, log_n, lib_a, lib_b, runs):
     for turn in range(runs):
         for lib in (lib_a, lib_b):
             env = dict(os.environ, ULTRAGROTH_TREE=os.path.abspath(lib))
-            subprocess.run([sys.executable, os.path.abspath(__file__), "groth16", mix, str(log_n), path], env=env, check=True, timeout=900)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "one", mix, str(log_n), path], env=env, check=True, timeout=900)
             res = json.load(open(path))
             assert os.path.samefile(res["tree"], lib), res["tree"]
             rows[lib].append(res)
-            print("turn %d %-60s setup %9.1f ms  verify %9.1f ms  zkey %s  verdict %s" % (
-                turn, lib[-60:], res["setup_ms"], res["verify_ms"], res["zkey_sha256"][:16], res["verdict"]), flush=True)
-    for lib in (lib_a, lib_b):
-        s = [r["setup_ms"] for r in rows[lib]]
-        v = [r["verify_ms"] for r in rows[lib]]
-        print("%-60s setup min %.1f max %.1f | verify min %.1f max %.1f" % (lib[-60:], min(s), max(s), min(v), max(v)))
-    same = len({r["zkey_sha256"] for lib in rows for r in rows[lib]}) == 1 and len({json.dumps(r["verdict"]) for lib in rows for r in rows[lib]}) == 1
+            for proto in ("groth16", "ultra"):
+                r = res[proto]
+                print("turn %d %-40s %-7s setup %9.1f ms  verify %9.1f ms  zkey %s  verdict %s  peak %d bytes" % (
+                    turn, lib[-40:], proto, r["setup_ms"], r["verify_ms"], r["zkey_sha256"][:16], r["verdict"], r["peak_device_bytes"]), flush=True)
+                print("        setup phases  %s" % " ".join("%.1f" % v for v in r["setup_phases"]))
+                print("        verify phases %s" % " ".join("%.1f" % v for v in r["verify_phases"]), flush=True)
+    for proto in ("groth16", "ultra"):
+        for lib in (lib_a, lib_b):
+            s = [r[proto]["setup_ms"] for r in rows[lib]]
+            v = [r[proto]["verify_ms"] for r in rows[lib]]
+            print("%-40s %-7s setup min %.1f max %.1f | verify min %.1f max %.1f" % (lib[-40:], proto, min(s), max(s), min(v), max(v)))
+        for what in SAME:
+            same = len({json.dumps(r[proto][what]) for lib in rows for r in rows[lib]}) == 1
+            print("%-7s %s identical across both checkouts and all runs: %s" % (proto, what, same))
     os.unlink(path)
-    print("outputs byte-identical across both checkouts and all runs: %s" % same)
 
 
 if __name__ == "__main__":
     a = sys.argv[1:]
     if len(a) >= 3 and a[0] == "setup" and a[1] in MIXES:
         setup(a[1], [int(x) for x in a[2:]])
-    elif len(a) == 4 and a[0] == "groth16" and a[1] in MIXES:
-        groth16(a[1], int(a[2]), a[3])
+    elif len(a) == 4 and a[0] == "one" and a[1] in MIXES:
+        one(a[1], int(a[2]), a[3])
     elif len(a) in (5, 6) and a[0] == "ab" and a[1] in MIXES:
         ab(a[1], int(a[2]), a[3], a[4], int(a[5]) if len(a) == 6 else 3)
     else:

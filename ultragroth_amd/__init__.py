@@ -372,7 +372,6 @@ def setup_from_ptau(r1cs, ptau, delta=None, log_domain=0, device=0, validate=1, 
     validate: 0 none, 1 field range and curve of every point read, 2 the G2 subgroup as well. device=-1 runs on host threads and
     gives the same bytes. UltraGroth keys, transcripts, beacons and verifying the .ptau's ceremony are out of scope.
     Refusals raise SetupError ("ptau: ..." / "r1cs: ..." / "setup: ...")."""
-    import json
     L = load()
     opt = _SetupPtauOptions()
     opt.size = C.sizeof(_SetupPtauOptions)
@@ -386,16 +385,22 @@ def setup_from_ptau(r1cs, ptau, delta=None, log_domain=0, device=0, validate=1, 
     else:
         opt.contribute = 1
         opt.delta = _le32(delta, "delta")
+    return _setup_ptau_call(L.ug_setup_ptau_size, L.ug_setup_ptau_run, opt, r1cs, ptau, device, timings)
+
+
+def _setup_ptau_call(size_fn, run_fn, opt, r1cs, ptau, device, timings):
+    """the size entry, buffers of that size, the run entry: (zkey_bytes, vkey_dict, phase_ms_dict)"""
+    import json
     r1cs = bytes(r1cs)
     with _Mapped(ptau) as m:
         zbytes, vmax = C.c_uint64(), C.c_uint64()
-        _setup_call(L.ug_setup_ptau_size, C.byref(opt), r1cs, len(r1cs), m.address, m.length, C.byref(zbytes), C.byref(vmax))
+        _setup_call(size_fn, C.byref(opt), r1cs, len(r1cs), m.address, m.length, C.byref(zbytes), C.byref(vmax))
         zkey = C.create_string_buffer(zbytes.value)
         vkey = C.create_string_buffer(vmax.value)
         wrote, vlen = C.c_uint64(), C.c_uint64()
         ms = (C.c_double * len(SETUP_PTAU_PHASES))()
-        _setup_call(L.ug_setup_ptau_run, C.byref(opt), r1cs, len(r1cs), m.address, m.length, device, zkey, zbytes.value, C.byref(wrote), vkey,
-                    vmax.value, C.byref(vlen), ms)
+        _setup_call(run_fn, C.byref(opt), r1cs, len(r1cs), m.address, m.length, device, zkey, zbytes.value, C.byref(wrote), vkey, vmax.value,
+                    C.byref(vlen), ms)
     phase_ms = dict(zip(SETUP_PTAU_PHASES, ms))
     if timings is not None:
         timings.update(phase_ms)
@@ -457,7 +462,6 @@ def ultra_setup_from_ptau(r1cs, ptau, ultra, delta=None, log_domain=0, device=0,
     (a single-party phase 2 with no transcript: sound only if both are gone and the .ptau is honest).
     ptau, validate, device, timings: as setup_from_ptau. Transcripts, beacons and verifying the .ptau's ceremony are out of scope.
     Refusals raise SetupError ("ptau: ..." / "r1cs: ..." / "setup: ...")."""
-    import json
     L = load()
     opt = _UltraSetupPtauOptions()
     opt.size = C.sizeof(_UltraSetupPtauOptions)
@@ -479,20 +483,9 @@ def ultra_setup_from_ptau(r1cs, ptau, ultra, delta=None, log_domain=0, device=0,
         opt.contribute = 1
         opt.delta_round = _le32(d_round, "delta_round")
         opt.delta_final = _le32(d_final, "delta_final")
-    r1cs = bytes(r1cs)
-    with _Mapped(ptau) as m:
-        zbytes, vmax = C.c_uint64(), C.c_uint64()
-        _setup_call(L.ug_ultra_setup_ptau_size, C.byref(opt), r1cs, len(r1cs), m.address, m.length, C.byref(zbytes), C.byref(vmax))
-        zkey = C.create_string_buffer(zbytes.value)
-        vkey = C.create_string_buffer(vmax.value)
-        wrote, vlen = C.c_uint64(), C.c_uint64()
-        ms = (C.c_double * len(SETUP_PTAU_PHASES))()
-        _setup_call(L.ug_ultra_setup_ptau_run, C.byref(opt), r1cs, len(r1cs), m.address, m.length, device, zkey, zbytes.value, C.byref(wrote),
-                    vkey, vmax.value, C.byref(vlen), ms)
-    phase_ms = dict(zip(SETUP_PTAU_PHASES, ms))
-    if timings is not None:
-        timings.update(phase_ms)
-    return zkey.raw[:wrote.value], json.loads(vkey.raw[:vlen.value].decode()), phase_ms
+    res = _setup_ptau_call(L.ug_ultra_setup_ptau_size, L.ug_ultra_setup_ptau_run, opt, r1cs, ptau, device, timings)
+    del keep
+    return res
 
 
 def points_scale_segments(segments, points, device=0, timing=None):
@@ -632,19 +625,26 @@ def zkey_verify(r1cs, ptau, zkey, device=0, validate=2, timings=None):
     subgroup check, timings["subgroup_checked"] says False then. device=-1 evaluates the same relations on host threads.
     timings: a dict that receives the milliseconds of ZKEY_VERIFY_PHASES, "fold_kernel" and "peak_device_bytes".
     Who contributed (section 10's transcript, beacons, the .ptau's own ceremony) is not checked."""
-    L = load()
-    opt = _ZkeyVerifyOptions()
-    opt.size = C.sizeof(_ZkeyVerifyOptions)
+    return _zkey_verify_call(load().ug_zkey_verify_run, _zkey_verify_options(_ZkeyVerifyOptions, validate), 9, r1cs, ptau, zkey, device, timings)
+
+
+def _zkey_verify_options(struct, validate):
+    opt = struct()
+    opt.size = C.sizeof(struct)
     if not 0 <= int(validate) < 1 << 32:
         raise SetupError("zkey: validate %d is not 1 or 2" % validate)
     opt.validate = int(validate)
+    return opt
+
+
+def _zkey_verify_call(entry, opt, last_section, r1cs, ptau, zkey, device, timings):
+    """one key check through `entry`: None, or (first_section, failed_sections, message) over the sections 2 .. last_section"""
     r1cs = bytes(r1cs)
     with _Mapped(ptau) as mp, _Mapped(zkey) as mz:
         rep = _ZkeyVerifyReport()
         ms = (C.c_double * len(ZKEY_VERIFY_PHASES))()
         err = C.create_string_buffer(1024)
-        rc = L.ug_zkey_verify_run(C.byref(opt), r1cs, len(r1cs), mp.address, mp.length, mz.address, mz.length, device, C.byref(rep), ms,
-                                  err, len(err) - 1)
+        rc = entry(C.byref(opt), r1cs, len(r1cs), mp.address, mp.length, mz.address, mz.length, device, C.byref(rep), ms, err, len(err) - 1)
     msg = err.value.decode(errors="replace")
     if rc not in (0, UG_ZKEY_INVALID):
         raise SetupError(msg)
@@ -653,7 +653,7 @@ def zkey_verify(r1cs, ptau, zkey, device=0, validate=2, timings=None):
         timings.update(fold_kernel=rep.fold_kernel_ms, peak_device_bytes=rep.peak_device_bytes, subgroup_checked=bool(rep.subgroup_checked))
     if rc == 0:
         return None
-    return rep.first_failed, [i for i in range(2, 10) if rep.failed_sections >> i & 1], msg
+    return rep.first_failed, [i for i in range(2, last_section + 1) if rep.failed_sections >> i & 1], msg
 
 
 class _UltraZkeyVerifyOptions(C.Structure):
@@ -690,62 +690,20 @@ def ultra_zkey_verify(r1cs, ptau, zkey, ultra=None, device=0, validate=2, timing
     they are -- WHO CHOSE THEM IS THEN NOT CHECKED, and which signal is committed before the challenge is what the protocol's
     soundness rests on. ptau, zkey, validate, device, timings: as zkey_verify. Transcripts, beacons and the .ptau's own ceremony
     are not checked."""
-    L = load()
-    opt = _UltraZkeyVerifyOptions()
-    opt.size = C.sizeof(_UltraZkeyVerifyOptions)
-    if not 0 <= int(validate) < 1 << 32:
-        raise SetupError("zkey: validate %d is not 1 or 2" % validate)
-    opt.validate = int(validate)
+    opt = _zkey_verify_options(_UltraZkeyVerifyOptions, validate)
     keep = []
     if ultra is not None:
         opt.check_spec = 1
         keep = _ultra_lists(opt, ultra, "zkey: ")
-    r1cs = bytes(r1cs)
-    with _Mapped(ptau) as mp, _Mapped(zkey) as mz:
-        rep = _ZkeyVerifyReport()
-        ms = (C.c_double * len(ZKEY_VERIFY_PHASES))()
-        err = C.create_string_buffer(1024)
-        rc = L.ug_ultra_zkey_verify_run(C.byref(opt), r1cs, len(r1cs), mp.address, mp.length, mz.address, mz.length, device, C.byref(rep), ms,
-                                        err, len(err) - 1)
+    res = _zkey_verify_call(load().ug_ultra_zkey_verify_run, opt, 12, r1cs, ptau, zkey, device, timings)
     del keep
-    msg = err.value.decode(errors="replace")
-    if rc not in (0, UG_ZKEY_INVALID):
-        raise SetupError(msg)
-    if timings is not None:
-        timings.update(zip(ZKEY_VERIFY_PHASES, ms))
-        timings.update(fold_kernel=rep.fold_kernel_ms, peak_device_bytes=rep.peak_device_bytes, subgroup_checked=bool(rep.subgroup_checked))
-    if rc == 0:
-        return None
-    return rep.first_failed, [i for i in range(2, 13) if rep.failed_sections >> i & 1], msg
+    return res
 
 
 def r1cs_fold_classes(r1cs, rho, cls, log_domain=0, device=0, timing=None):
     """ug_r1cs_fold_classes (test tooling): the fold of an UltraGroth key check. rho as r1cs_fold; cls: one class 0, 1 or 2 per wire.
     Returns eleven lists of N integers: (a, b, c) over class 0, over class 1, over class 2, then a and b over all wires."""
-    r1cs = bytes(r1cs)
-    try:
-        info = r1cs_info(r1cs)
-    except DeviceError as e:
-        raise SetupError(str(e) if str(e).startswith("r1cs: ") else "r1cs: " + str(e))
-    rho = [int(x) for x in rho]
-    cls = [int(x) for x in cls]
-    if len(rho) != info["n_wires"] or any(not 0 <= x < 1 << 256 for x in rho):
-        raise SetupError("r1cs: rho takes one integer below 2^256 per wire (%d wires)" % info["n_wires"])
-    if len(cls) != info["n_wires"] or any(not 0 <= x < 256 for x in cls):
-        raise SetupError("r1cs: cls takes one class per wire (%d wires)" % info["n_wires"])
-    rows = info["n_constraints"] + info["n_pub_out"] + info["n_pub_in"] + 1
-    log_n = int(log_domain) if log_domain else max(1, (rows - 1).bit_length())
-    if not 0 < log_n <= 27:
-        raise SetupError("r1cs: log_domain %d is not in 1 .. 27" % log_n)
-    n = 1 << log_n
-    out = C.create_string_buffer(11 * 32 * n)
-    ms = C.c_double()
-    _setup_call(load().ug_r1cs_fold_classes, r1cs, len(r1cs), b"".join(x.to_bytes(32, "little") for x in rho), bytes(cls), log_n, device, out,
-                C.byref(ms))
-    if timing is not None:
-        timing.append(ms.value)
-    raw = out.raw
-    return tuple([int.from_bytes(raw[32 * (v * n + k):32 * (v * n + k) + 32], "little") for k in range(n)] for v in range(11))
+    return _r1cs_fold_call(11, r1cs, rho, cls, log_domain, device, timing)
 
 
 def r1cs_fold(r1cs, rho, log_domain=0, device=0, timing=None):
@@ -753,26 +711,39 @@ def r1cs_fold(r1cs, rho, log_domain=0, device=0, timing=None):
     of N = 2^log_domain integers, (a_pub, b_pub, c_pub, a_priv, b_priv, c_priv): per row the sums of its A, B, C terms times rho
     over the wires 0 .. nPublic and over the others; the public rows carry rho_s in a_pub. log_domain 0: the smallest domain
     that fits. device=-1: host threads. timing: a list that receives the kernel's milliseconds."""
+    return _r1cs_fold_call(6, r1cs, rho, None, log_domain, device, timing)
+
+
+def _r1cs_fold_call(vectors, r1cs, rho, cls, log_domain, device, timing):
+    """a fold entry: `vectors` lists of N integers; cls: the class list of ug_r1cs_fold_classes, None for ug_r1cs_fold"""
     r1cs = bytes(r1cs)
     try:
         info = r1cs_info(r1cs)
     except DeviceError as e:
         raise SetupError(str(e) if str(e).startswith("r1cs: ") else "r1cs: " + str(e))
     rho = [int(x) for x in rho]
+    if cls is not None:
+        cls = [int(x) for x in cls]
     if len(rho) != info["n_wires"] or any(not 0 <= x < 1 << 256 for x in rho):
         raise SetupError("r1cs: rho takes one integer below 2^256 per wire (%d wires)" % info["n_wires"])
+    if cls is not None and (len(cls) != info["n_wires"] or any(not 0 <= x < 256 for x in cls)):
+        raise SetupError("r1cs: cls takes one class per wire (%d wires)" % info["n_wires"])
     rows = info["n_constraints"] + info["n_pub_out"] + info["n_pub_in"] + 1
     log_n = int(log_domain) if log_domain else max(1, (rows - 1).bit_length())
     if not 0 < log_n <= 27:
         raise SetupError("r1cs: log_domain %d is not in 1 .. 27" % log_n)
     n = 1 << log_n
-    out = C.create_string_buffer(6 * 32 * n)
+    out = C.create_string_buffer(vectors * 32 * n)
     ms = C.c_double()
-    _setup_call(load().ug_r1cs_fold, r1cs, len(r1cs), b"".join(x.to_bytes(32, "little") for x in rho), log_n, device, out, C.byref(ms))
+    weights = b"".join(x.to_bytes(32, "little") for x in rho)
+    if cls is None:
+        _setup_call(load().ug_r1cs_fold, r1cs, len(r1cs), weights, log_n, device, out, C.byref(ms))
+    else:
+        _setup_call(load().ug_r1cs_fold_classes, r1cs, len(r1cs), weights, bytes(cls), log_n, device, out, C.byref(ms))
     if timing is not None:
         timing.append(ms.value)
     raw = out.raw
-    return tuple([int.from_bytes(raw[32 * (v * n + k):32 * (v * n + k) + 32], "little") for k in range(n)] for v in range(6))
+    return tuple([int.from_bytes(raw[32 * (v * n + k):32 * (v * n + k) + 32], "little") for k in range(n)] for v in range(vectors))
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -31,25 +31,26 @@ struct Request {
     const ug_ultra_setup_ptau_options* ultra;
 };
 
-void checkOptions(const ug_setup_ptau_options* o) {
-    checkOptionsHead<SetupError>(o, 0, 2, "0, 1 or 2");
-    if (o->contribute > 2) throw SetupError("contribute " + std::to_string(o->contribute) + " is not 0, 1 or 2");
-    if (o->contribute == 1) {
-        if (!belowR(o->delta)) throw SetupError("delta is not below the field modulus");
-        if (allZero(o->delta, 32)) throw SetupError("delta is 0 mod r");
+// the contribution rule of both options structs: a given delta (contribute = 1) is below r and not 0, under the struct's name for it
+struct NamedDelta { const char* name; const uint8_t* v; };
+void checkContribution(u32 contribute, std::initializer_list<NamedDelta> deltas) {
+    if (contribute > 2) throw SetupError("contribute " + std::to_string(contribute) + " is not 0, 1 or 2");
+    if (contribute != 1) return;
+    for (const NamedDelta& d : deltas) {
+        if (!belowR(d.v)) throw SetupError(std::string(d.name) + " is not below the field modulus");
+        if (allZero(d.v, 32)) throw SetupError(std::string(d.name) + " is 0 mod r");
     }
 }
-
-void checkOptions(const ug_ultra_setup_ptau_options* o) {
+// every rule of the options, then what a run reads of them
+Request requestOf(const ug_setup_ptau_options* o) {
     checkOptionsHead<SetupError>(o, 0, 2, "0, 1 or 2");
-    if (o->contribute > 2) throw SetupError("contribute " + std::to_string(o->contribute) + " is not 0, 1 or 2");
-    if (o->contribute == 1) {
-        const struct { const char* name; const uint8_t* v; } deltas[2] = {{"delta_round", o->delta_round}, {"delta_final", o->delta_final}};
-        for (const auto& d : deltas) {
-            if (!belowR(d.v)) throw SetupError(std::string(d.name) + " is not below the field modulus");
-            if (allZero(d.v, 32)) throw SetupError(std::string(d.name) + " is 0 mod r");
-        }
-    }
+    checkContribution(o->contribute, {{"delta", o->delta}});
+    return {o->log_domain, o->validate, o->contribute, nullptr, o->delta, nullptr};
+}
+Request requestOf(const ug_ultra_setup_ptau_options* o) {
+    checkOptionsHead<SetupError>(o, 0, 2, "0, 1 or 2");
+    checkContribution(o->contribute, {{"delta_round", o->delta_round}, {"delta_final", o->delta_final}});
+    return {o->log_domain, o->validate, o->contribute, o->delta_round, o->delta_final, o};
 }
 
 // a delta and its inverse that are wiped when they go
@@ -211,20 +212,30 @@ u64 runPtau(const Request& rq, const void* r1cs, u64 r1csSize, const void* ptau,
     return lay.total;
 }
 
-// every rule of the options, then the run
-u64 runPtau(const ug_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
-            u64 zkeyCap, std::string* vkey, double ms[PTAU_PHASES], bool sizeOnly, u64* vkeyMax) {
-    for (int i = 0; i < PTAU_PHASES; i++) ms[i] = 0;
-    checkOptions(opt);
-    const Request rq = {opt->log_domain, opt->validate, opt->contribute, nullptr, opt->delta, nullptr};
-    return runPtau(rq, r1cs, r1csSize, ptau, ptauSize, device, zkey, zkeyCap, vkey, ms, sizeOnly, vkeyMax);
+// the size entry and the run entry of either protocol
+template <class Options>
+int sizeEntry(const Options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, uint64_t* zkeyBytes, uint64_t* vkeyBytesMax,
+              char* errorMsg, unsigned long long errorMsgMax) {
+    return guarded(SETUP_RULE, errorMsg, errorMsgMax, [&] {
+        double ms[PTAU_PHASES] = {0};
+        u64 vmax = 0;
+        const u64 total = runPtau(requestOf(opt), r1cs, r1csSize, ptau, ptauSize, -1, nullptr, 0, nullptr, ms, true, &vmax);
+        if (zkeyBytes) *zkeyBytes = total;
+        if (vkeyBytesMax) *vkeyBytesMax = vmax;
+    });
 }
-u64 runPtau(const ug_ultra_setup_ptau_options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
-            u64 zkeyCap, std::string* vkey, double ms[PTAU_PHASES], bool sizeOnly, u64* vkeyMax) {
-    for (int i = 0; i < PTAU_PHASES; i++) ms[i] = 0;
-    checkOptions(opt);
-    const Request rq = {opt->log_domain, opt->validate, opt->contribute, opt->delta_round, opt->delta_final, opt};
-    return runPtau(rq, r1cs, r1csSize, ptau, ptauSize, device, zkey, zkeyCap, vkey, ms, sizeOnly, vkeyMax);
+template <class Options>
+int runEntry(const Options* opt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, void* zkey, u64 zkeyCap,
+             uint64_t* zkeyBytes, char* vkeyJson, u64 vkeyCap, uint64_t* vkeyBytes, double* phaseMs, char* errorMsg,
+             unsigned long long errorMsgMax) {
+    return guarded(SETUP_RULE, errorMsg, errorMsgMax, [&] {
+        double ms[PTAU_PHASES] = {0};
+        std::string vkey;
+        const u64 total = runPtau(requestOf(opt), r1cs, r1csSize, ptau, ptauSize, device, (uint8_t*)zkey, zkeyCap, &vkey, ms, false, nullptr);
+        if (zkeyBytes) *zkeyBytes = total;
+        copyVkey(vkey, vkeyJson, vkeyCap, vkeyBytes);
+        if (phaseMs) for (int i = 0; i < PTAU_PHASES; i++) phaseMs[i] = ms[i];
+    });
 }
 
 void checkColumns(const u32* colPtr, u64 nCols, const u32* index, const uint8_t* coefs, u64 nPoints) {
@@ -266,52 +277,28 @@ int ug_ptau_parse_info(const void* ptau, uint64_t ptau_size, ug_ptau_info* out, 
 
 int ug_setup_ptau_size(const ug_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
                        uint64_t* zkey_bytes, uint64_t* vkey_bytes_max, char* error_msg, unsigned long long error_msg_maxsize) {
-    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
-        double ms[PTAU_PHASES];
-        u64 vmax = 0;
-        const u64 total = runPtau(opt, r1cs, r1cs_size, ptau, ptau_size, -1, nullptr, 0, nullptr, ms, true, &vmax);
-        if (zkey_bytes) *zkey_bytes = total;
-        if (vkey_bytes_max) *vkey_bytes_max = vmax;
-    });
+    return sizeEntry(opt, r1cs, r1cs_size, ptau, ptau_size, zkey_bytes, vkey_bytes_max, error_msg, error_msg_maxsize);
 }
 
 int ug_setup_ptau_run(const ug_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
                       int device, void* zkey, uint64_t zkey_capacity, uint64_t* zkey_bytes, char* vkey_json, uint64_t vkey_capacity,
                       uint64_t* vkey_bytes, double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize) {
-    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
-        double ms[PTAU_PHASES];
-        std::string vkey;
-        const u64 total = runPtau(opt, r1cs, r1cs_size, ptau, ptau_size, device, (uint8_t*)zkey, zkey_capacity, &vkey, ms, false, nullptr);
-        if (zkey_bytes) *zkey_bytes = total;
-        copyVkey(vkey, vkey_json, vkey_capacity, vkey_bytes);
-        if (phase_ms) for (int i = 0; i < PTAU_PHASES; i++) phase_ms[i] = ms[i];
-    });
+    return runEntry(opt, r1cs, r1cs_size, ptau, ptau_size, device, zkey, zkey_capacity, zkey_bytes, vkey_json, vkey_capacity, vkey_bytes, phase_ms,
+                    error_msg, error_msg_maxsize);
 }
 
 int ug_ultra_setup_ptau_size(const ug_ultra_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
                              uint64_t ptau_size, uint64_t* zkey_bytes, uint64_t* vkey_bytes_max, char* error_msg,
                              unsigned long long error_msg_maxsize) {
-    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
-        double ms[PTAU_PHASES];
-        u64 vmax = 0;
-        const u64 total = runPtau(opt, r1cs, r1cs_size, ptau, ptau_size, -1, nullptr, 0, nullptr, ms, true, &vmax);
-        if (zkey_bytes) *zkey_bytes = total;
-        if (vkey_bytes_max) *vkey_bytes_max = vmax;
-    });
+    return sizeEntry(opt, r1cs, r1cs_size, ptau, ptau_size, zkey_bytes, vkey_bytes_max, error_msg, error_msg_maxsize);
 }
 
 int ug_ultra_setup_ptau_run(const ug_ultra_setup_ptau_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
                             uint64_t ptau_size, int device, void* zkey, uint64_t zkey_capacity, uint64_t* zkey_bytes, char* vkey_json,
                             uint64_t vkey_capacity, uint64_t* vkey_bytes, double* phase_ms, char* error_msg,
                             unsigned long long error_msg_maxsize) {
-    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
-        double ms[PTAU_PHASES];
-        std::string vkey;
-        const u64 total = runPtau(opt, r1cs, r1cs_size, ptau, ptau_size, device, (uint8_t*)zkey, zkey_capacity, &vkey, ms, false, nullptr);
-        if (zkey_bytes) *zkey_bytes = total;
-        copyVkey(vkey, vkey_json, vkey_capacity, vkey_bytes);
-        if (phase_ms) for (int i = 0; i < PTAU_PHASES; i++) phase_ms[i] = ms[i];
-    });
+    return runEntry(opt, r1cs, r1cs_size, ptau, ptau_size, device, zkey, zkey_capacity, zkey_bytes, vkey_json, vkey_capacity, vkey_bytes, phase_ms,
+                    error_msg, error_msg_maxsize);
 }
 
 int ug_points_combine(int device, int g2, const uint32_t* col_ptr, uint64_t n_cols, const uint32_t* index, const void* coefs,

@@ -1962,25 +1962,31 @@ int ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* 
     else { *matrix = (int)(*word_host & 1); *row = *word_host >> 1; }
     UG_CATCH
 }
-int ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32_t log_domain, ug_dvec* out, double* kernel_ms) {
+// what the two folds share: the argument rules, the waits on the vectors' streams, the event pair around `launch` and its time.
+// classes: the entry takes a class vector (cls); vectors: how many of 2^log_domain elements `out` takes
+static int r1cs_fold_call(ug_r1cs* r, const ug_dvec* rho, bool classes, const ug_dvec* cls, uint32_t n_public, uint32_t log_domain,
+                          int vectors, ug_dvec* out, double* kernel_ms, const std::function<void(u32 domain)>& launch) {
     UG_TRY
-    if (!r || !rho || !out) throw std::invalid_argument("null argument");
+    if (!r || !rho || (classes && !cls) || !out) throw std::invalid_argument("null argument");
     ug_ctx* c = r->ctx;
-    if (rho->ctx->device != c->device || out->ctx->device != c->device) throw std::invalid_argument("r1cs: a vector lives on another device");
+    if (rho->ctx->device != c->device || (classes && cls->ctx->device != c->device) || out->ctx->device != c->device)
+        throw std::invalid_argument("r1cs: a vector lives on another device");
     if (c->recording) throw std::invalid_argument("r1cs: no fold while the context's stream is being recorded");
     if (log_domain > 27) throw std::invalid_argument("r1cs: log_domain " + std::to_string(log_domain) + " is above 27");
     const u64 N = (u64)1 << log_domain;
     if (rho->n < r->hdr.nWires) throw std::invalid_argument("r1cs: the weight vector is shorter than n_wires (" + std::to_string(r->hdr.nWires) + " wires)");
+    if (classes && cls->n * 32 < r->hdr.nWires) throw std::invalid_argument("r1cs: the class vector holds fewer than n_wires bytes");
     if ((u64)n_public + 1 > r->hdr.nWires) throw std::invalid_argument("r1cs: " + std::to_string(n_public) + " public signals, " + std::to_string(r->hdr.nWires) + " wires");
     if ((u64)r->hdr.nConstraints + n_public + 1 > N)
         throw std::invalid_argument("r1cs: " + std::to_string(r->hdr.nConstraints) + " constraints and " + std::to_string(n_public) +
                                     " public signals do not fit a domain of " + std::to_string(N));
-    if (out->n < 8 * N) throw std::invalid_argument("r1cs: the output vector is shorter than 8 * 2^log_domain");
+    if (out->n < (u64)vectors * N) throw std::invalid_argument("r1cs: the output vector is shorter than " + std::to_string(vectors) + " * 2^log_domain");
     c->use();
     UG_HIP(hipStreamSynchronize(rho->ctx->stream));             // (the weights may have been queued on another context's stream)
+    if (classes && cls->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(cls->ctx->stream));
     if (out->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(out->ctx->stream));
     UG_HIP(hipEventRecord(r->t0, c->stream));
-    r1cs_fold(r->dev(), rho->data, n_public, (u32)N, out->data, c->stream);
+    launch((u32)N);
     UG_HIP(hipEventRecord(r->t1, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));
     float ms = 0;
@@ -1988,36 +1994,16 @@ int ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32_
     if (kernel_ms) *kernel_ms = ms;
     UG_CATCH
 }
-
+int ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32_t log_domain, ug_dvec* out, double* kernel_ms) {
+    return r1cs_fold_call(r, rho, false, nullptr, n_public, log_domain, 8, out, kernel_ms, [&](u32 domain) {
+        r1cs_fold(r->dev(), rho->data, n_public, domain, out->data, r->ctx->stream);
+    });
+}
 int ug_r1cs_fold_classes_dvec(ug_r1cs* r, const ug_dvec* rho, const ug_dvec* cls, uint32_t n_public, uint32_t log_domain, ug_dvec* out,
                               double* kernel_ms) {
-    UG_TRY
-    if (!r || !rho || !cls || !out) throw std::invalid_argument("null argument");
-    ug_ctx* c = r->ctx;
-    if (rho->ctx->device != c->device || cls->ctx->device != c->device || out->ctx->device != c->device)
-        throw std::invalid_argument("r1cs: a vector lives on another device");
-    if (c->recording) throw std::invalid_argument("r1cs: no fold while the context's stream is being recorded");
-    if (log_domain > 27) throw std::invalid_argument("r1cs: log_domain " + std::to_string(log_domain) + " is above 27");
-    const u64 N = (u64)1 << log_domain;
-    if (rho->n < r->hdr.nWires) throw std::invalid_argument("r1cs: the weight vector is shorter than n_wires (" + std::to_string(r->hdr.nWires) + " wires)");
-    if (cls->n * 32 < r->hdr.nWires) throw std::invalid_argument("r1cs: the class vector holds fewer than n_wires bytes");
-    if ((u64)n_public + 1 > r->hdr.nWires) throw std::invalid_argument("r1cs: " + std::to_string(n_public) + " public signals, " + std::to_string(r->hdr.nWires) + " wires");
-    if ((u64)r->hdr.nConstraints + n_public + 1 > N)
-        throw std::invalid_argument("r1cs: " + std::to_string(r->hdr.nConstraints) + " constraints and " + std::to_string(n_public) +
-                                    " public signals do not fit a domain of " + std::to_string(N));
-    if (out->n < 11 * N) throw std::invalid_argument("r1cs: the output vector is shorter than 11 * 2^log_domain");
-    c->use();
-    UG_HIP(hipStreamSynchronize(rho->ctx->stream));
-    if (cls->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(cls->ctx->stream));
-    if (out->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(out->ctx->stream));
-    UG_HIP(hipEventRecord(r->t0, c->stream));
-    r1cs_fold_classes(r->dev(), rho->data, reinterpret_cast<const uint8_t*>(cls->data), n_public, (u32)N, out->data, c->stream);
-    UG_HIP(hipEventRecord(r->t1, c->stream));
-    UG_HIP(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    UG_HIP(hipEventElapsedTime(&ms, r->t0, r->t1));
-    if (kernel_ms) *kernel_ms = ms;
-    UG_CATCH
+    return r1cs_fold_call(r, rho, true, cls, n_public, log_domain, 11, out, kernel_ms, [&](u32 domain) {
+        r1cs_fold_classes(r->dev(), rho->data, reinterpret_cast<const uint8_t*>(cls->data), n_public, domain, out->data, r->ctx->stream);
+    });
 }
 void ug_r1cs_destroy(ug_r1cs* r) {
     if (!r) return;

@@ -8,6 +8,8 @@
 // uploaded, so the peak of device memory is the slices with the fold's vectors, or H with the padded level -- not the whole key.
 // An UltraGroth key (ug_ultra_zkey_verify_run) takes the same route with r1cs_fold_classes_kernel: a class byte per wire, three
 // sums per matrix, eleven vectors; its two C sections stand under weights that the host gathers through the key's lists.
+// The host part below is one evaluator (sumsOn) and one fold helper (foldOn) for both: the class count and the list of C sections
+// come with the Inputs (zkey_verify.hpp), and a Groth16 key's one C section still reads the device's rho in place.
 // No LDS, no scratch; plain C++ and vector stores only.
 #include "dev_common.hpp"
 #include "internal.hpp"
@@ -195,25 +197,39 @@ void openDevice(Dev& d, int device) {
     must(ug_ctx_create(&d.c, device));
     d.base = d.used();
 }
-// the circuit, the weights and the eight vectors of the fold on the device
-void foldOn(Dev& d, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, u64 M, uint32_t nPublic, uint32_t logN, double* kernelMs) {
-    const u64 N = 1ull << logN;
+// the circuit, the weights and the 3 K + 2 vectors of the fold on the device. cls null: a Groth16 key's two classes, eight vectors;
+// cls a byte per wire: an UltraGroth key's three, eleven vectors, the bytes packed 32 to a vector element and gone after the kernel
+void foldOn(Dev& d, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, const uint8_t* cls, u64 M, uint32_t nPublic, uint32_t logN,
+            double* kernelMs) {
+    const u64 N = 1ull << logN, vectors = cls ? 11 : 8;
     must(ug_r1cs_create(d.c, r1cs, r1csSize, &d.r));
     must(ug_dvec_create(d.c, M, &d.rho));
     must(ug_dvec_upload(d.rho, rho, M));
-    must(ug_dvec_create(d.c, 8 * N, &d.fold));
-    must(ug_r1cs_fold_dvec(d.r, d.rho, nPublic, logN, d.fold, kernelMs));
+    if (cls) {
+        const u64 words = (M + 31) / 32;
+        std::vector<uint8_t> padded(words * 32, 0);
+        memcpy(padded.data(), cls, M);
+        must(ug_dvec_create(d.c, words, &d.cls));
+        must(ug_dvec_upload(d.cls, padded.data(), words));
+    }
+    must(ug_dvec_create(d.c, vectors * N, &d.fold));
+    must(cls ? ug_r1cs_fold_classes_dvec(d.r, d.rho, d.cls, nPublic, logN, d.fold, kernelMs)
+             : ug_r1cs_fold_dvec(d.r, d.rho, nPublic, logN, d.fold, kernelMs));
     d.sample();
     ug_r1cs_destroy(d.r);
     d.r = nullptr;
+    ug_dvec_destroy(d.cls);
+    d.cls = nullptr;
 }
 
 void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
     ughost::setup::PhaseClock clock(st.ms);
     const u64 N = in.N, M = in.M, pub = in.pub;
+    const int K = in.K;
+    const u64 a = 3 * (u64)K * N, b = a + N;                         // where the fold's a and b start
     Dev d;
     openDevice(d, device);
-    foldOn(d, in.r1cs, in.r1csSize, in.rho, M, (uint32_t)(pub - 1), (uint32_t)in.logN, &st.foldKernelMs);
+    foldOn(d, in.r1cs, in.r1csSize, in.rho, in.cls, M, (uint32_t)(pub - 1), (uint32_t)in.logN, &st.foldKernelMs);
     must(ug_schedule_create(d.c, &d.s));
     clock.lap(0);
 
@@ -223,16 +239,16 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
     must(ug_bases_create_g1(d.c, in.aT, N, 0, &d.set[2]));
     must(ug_bases_create_g1(d.c, in.bT, N, 0, &d.set[3]));
     d.sample();
-    must(ug_schedule_build(d.s, d.fold, 6 * N, N));                  // a
-    must(ug_msm_g1(d.c, d.set[0], d.s, (int64_t)(6 * N), out.aT));
+    must(ug_schedule_build(d.s, d.fold, a, N));                      // a
+    must(ug_msm_g1(d.c, d.set[0], d.s, (int64_t)a, out.aT));
     {
-        must(ug_schedule_build(d.s, d.fold, 7 * N, N));              // b over T and, in G2, T2: one schedule, two base sets
+        must(ug_schedule_build(d.s, d.fold, b, N));                  // b over T and, in G2, T2: one schedule, two base sets
         const ug_bases* both[2] = {d.set[0], d.set[1]};
-        const int64_t shifts[2] = {(int64_t)(7 * N), (int64_t)(7 * N)};
+        const int64_t shifts[2] = {(int64_t)b, (int64_t)b};
         void* outs[2] = {out.bT, out.bT2};
         must(ug_msm_batch(d.c, 2, both, d.s, shifts, outs));
     }
-    for (int m = 0; m < 2; m++) {                                    // K^m = MSM(a^m, bT) + MSM(b^m, aT) + MSM(c^m, T)
+    for (int m = 0; m < K; m++) {                                    // K^m = MSM(a^m, bT) + MSM(b^m, aT) + MSM(c^m, T)
         uint8_t part[3][64];
         const ug_bases* over[3] = {d.set[3], d.set[2], d.set[0]};
         for (int v = 0; v < 3; v++) {
@@ -244,10 +260,10 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
         uint8_t ones[3][32] = {{1}, {1}, {1}};
         ughost::setup::PointSegs p;
         p.base[0] = part[0]; p.count = 3; p.n = 1;
-        ughost::setup::hostBackend().combine(false, 1, colPtr, index, ones[0], p, m ? out.kPriv : out.kPub, nullptr);
+        ughost::setup::hostBackend().combine(false, 1, colPtr, index, ones[0], p, out.k[m], nullptr);
     }
     d.sample();
-    for (ug_bases*& b : d.set) Dev::drop(b);
+    for (ug_bases*& bs : d.set) Dev::drop(bs);
     ug_dvec_destroy(d.fold);
     d.fold = nullptr;
     must(ug_schedule_trim(d.s));
@@ -268,14 +284,23 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
     must(ug_bases_create_g1(d.c, in.ic, pub, 0, &d.set[0]));
     must(ug_msm_g1(d.c, d.set[0], d.s, 0, out.keyIC));
     Dev::drop(d.set[0]);
-    if (M > pub) {                                                   // rho^priv over C: record 0 is wire nPublic + 1
-        must(ug_schedule_build(d.s, d.rho, pub, M - pub));
-        must(ug_bases_create_g1(d.c, in.c, M - pub, pub, &d.set[0]));
+    for (int i = 0; i < K - 1; i++) {                                // each C section under its weights
+        const CSection& sc = in.c[i];
+        memset(out.keyC[i], 0, 64);
+        if (!sc.n) continue;
+        if (sc.rhoFirst >= 0) {                                      // rho's own run, in place: record 0 is wire rhoFirst
+            must(ug_schedule_build(d.s, d.rho, (u64)sc.rhoFirst, sc.n));
+        } else {                                                     // the weights of a list's signals, gathered on the host
+            must(ug_dvec_create(d.c, sc.n, &d.rhoList));
+            must(ug_dvec_upload(d.rhoList, sc.weights, sc.n));
+            must(ug_schedule_build(d.s, d.rhoList, 0, sc.n));
+        }
+        must(ug_bases_create_g1(d.c, sc.points, sc.n, sc.rhoFirst >= 0 ? (u64)sc.rhoFirst : 0, &d.set[0]));
         d.sample();
-        must(ug_msm_g1(d.c, d.set[0], d.s, 0, out.keyC));
+        must(ug_msm_g1(d.c, d.set[0], d.s, 0, out.keyC[i]));
         Dev::drop(d.set[0]);
-    } else {
-        memset(out.keyC, 0, 64);
+        ug_dvec_destroy(d.rhoList);
+        d.rhoList = nullptr;
     }
     clock.lap(2);
 
@@ -296,142 +321,18 @@ void sumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
     st.peakDeviceBytes = d.peak;
 }
 
-// ---- an UltraGroth key ----
-// the circuit, the weights, the class bytes (packed 32 to a vector element) and the eleven vectors of the fold on the device
-void foldClassesOn(Dev& d, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, const uint8_t* cls, u64 M, uint32_t nPublic, uint32_t logN,
-                   double* kernelMs) {
-    const u64 N = 1ull << logN, words = (M + 31) / 32;
-    std::vector<uint8_t> padded(words * 32, 0);
-    memcpy(padded.data(), cls, M);
-    must(ug_r1cs_create(d.c, r1cs, r1csSize, &d.r));
-    must(ug_dvec_create(d.c, M, &d.rho));
-    must(ug_dvec_upload(d.rho, rho, M));
-    must(ug_dvec_create(d.c, words, &d.cls));
-    must(ug_dvec_upload(d.cls, padded.data(), words));
-    must(ug_dvec_create(d.c, 11 * N, &d.fold));
-    must(ug_r1cs_fold_classes_dvec(d.r, d.rho, d.cls, nPublic, logN, d.fold, kernelMs));
-    d.sample();
-    ug_r1cs_destroy(d.r);
-    d.r = nullptr;
-    ug_dvec_destroy(d.cls);
-    d.cls = nullptr;
-}
-
-// sumsOn for protocol 1337: three classes on the scalar side; sections 8 and 9 under the weights gathered through their lists
-void ultraSumsOn(int device, const Inputs& in, Sums& out, SumsStats& st) {
-    ughost::setup::PhaseClock clock(st.ms);
-    const u64 N = in.N, M = in.M, pub = in.pub;
-    Dev d;
-    openDevice(d, device);
-    foldClassesOn(d, in.r1cs, in.r1csSize, in.rho, in.cls, M, (uint32_t)(pub - 1), (uint32_t)in.logN, &st.foldKernelMs);
-    must(ug_schedule_create(d.c, &d.s));
-    clock.lap(0);
-
-    must(ug_bases_create_g1(d.c, in.T, N, 0, &d.set[0]));
-    must(ug_bases_create_g2(d.c, in.T2, N, 0, &d.set[1]));
-    must(ug_bases_create_g1(d.c, in.aT, N, 0, &d.set[2]));
-    must(ug_bases_create_g1(d.c, in.bT, N, 0, &d.set[3]));
-    d.sample();
-    must(ug_schedule_build(d.s, d.fold, 9 * N, N));                  // a
-    must(ug_msm_g1(d.c, d.set[0], d.s, (int64_t)(9 * N), out.aT));
-    {
-        must(ug_schedule_build(d.s, d.fold, 10 * N, N));             // b over T and T2
-        const ug_bases* both[2] = {d.set[0], d.set[1]};
-        const int64_t shifts[2] = {(int64_t)(10 * N), (int64_t)(10 * N)};
-        void* outs[2] = {out.bT, out.bT2};
-        must(ug_msm_batch(d.c, 2, both, d.s, shifts, outs));
-    }
-    uint8_t* const kOut[3] = {out.kPub, out.kPriv, out.kFinal};
-    for (int m = 0; m < 3; m++) {                                    // K^m = MSM(a^m, bT) + MSM(b^m, aT) + MSM(c^m, T)
-        uint8_t part[3][64];
-        const ug_bases* over[3] = {d.set[3], d.set[2], d.set[0]};
-        for (int v = 0; v < 3; v++) {
-            const u64 first = (u64)(3 * m + v) * N;
-            must(ug_schedule_build(d.s, d.fold, first, N));
-            must(ug_msm_g1(d.c, over[v], d.s, (int64_t)first, part[v]));
-        }
-        const uint32_t colPtr[2] = {0, 3}, index[3] = {0, 1, 2};
-        uint8_t ones[3][32] = {{1}, {1}, {1}};
-        ughost::setup::PointSegs p;
-        p.base[0] = part[0]; p.count = 3; p.n = 1;
-        ughost::setup::hostBackend().combine(false, 1, colPtr, index, ones[0], p, kOut[m], nullptr);
-    }
-    d.sample();
-    for (ug_bases*& b : d.set) Dev::drop(b);
-    ug_dvec_destroy(d.fold);
-    d.fold = nullptr;
-    must(ug_schedule_trim(d.s));
-    clock.lap(1);
-
-    must(ug_schedule_build(d.s, d.rho, 0, M));
-    struct Sec { const uint8_t* p; bool g2; uint8_t* out; };
-    const Sec secs[3] = {{in.a, false, out.keyA}, {in.b1, false, out.keyB1}, {in.b2, true, out.keyB2}};
-    for (const Sec& sc : secs) {
-        must(sc.g2 ? ug_bases_create_g2(d.c, sc.p, M, 0, &d.set[0]) : ug_bases_create_g1(d.c, sc.p, M, 0, &d.set[0]));
-        d.sample();
-        must(sc.g2 ? ug_msm_g2(d.c, d.set[0], d.s, 0, sc.out) : ug_msm_g1(d.c, d.set[0], d.s, 0, sc.out));
-        d.sample();
-        Dev::drop(d.set[0]);
-    }
-    must(ug_schedule_build(d.s, d.rho, 0, pub));                     // rho^pub over IC
-    must(ug_bases_create_g1(d.c, in.ic, pub, 0, &d.set[0]));
-    must(ug_msm_g1(d.c, d.set[0], d.s, 0, out.keyIC));
-    Dev::drop(d.set[0]);
-    struct CSec { const uint8_t* p; const uint8_t* rho; u64 n; uint8_t* out; };
-    const CSec csecs[2] = {{in.c, in.rhoRound, in.n1, out.keyC}, {in.c2, in.rhoFinal, in.n2, out.keyC2}};
-    for (const CSec& sc : csecs) {                                   // the weights of a list's signals over its C section
-        memset(sc.out, 0, 64);
-        if (!sc.n) continue;
-        must(ug_dvec_create(d.c, sc.n, &d.rhoList));
-        must(ug_dvec_upload(d.rhoList, sc.rho, sc.n));
-        must(ug_schedule_build(d.s, d.rhoList, 0, sc.n));
-        must(ug_bases_create_g1(d.c, sc.p, sc.n, 0, &d.set[0]));
-        d.sample();
-        must(ug_msm_g1(d.c, d.set[0], d.s, 0, sc.out));
-        Dev::drop(d.set[0]);
-        ug_dvec_destroy(d.rhoList);
-        d.rhoList = nullptr;
-    }
-    clock.lap(2);
-
-    must(ug_dvec_create(d.c, N, &d.sigma));
-    must(ug_dvec_upload(d.sigma, in.sigma, N));
-    must(ug_schedule_build(d.s, d.sigma, 0, N));
-    must(ug_bases_create_g1(d.c, in.h, N, 0, &d.set[0]));
-    must(ug_bases_create_every_g1(d.c, in.top, 2 * N, 1, 2, 0, &d.set[1]));
-    d.sample();
-    {
-        const ug_bases* both[2] = {d.set[0], d.set[1]};
-        void* outs[2] = {out.keyH, out.hP};
-        must(ug_msm_batch(d.c, 2, both, d.s, nullptr, outs));
-    }
-    d.sample();
-    clock.lap(3);
-    st.peakDeviceBytes = d.peak;
-}
-
-void foldClassesDevice(int device, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, const uint8_t* cls, uint32_t nPublic, uint32_t logN,
-                       uint8_t* out11, double* kernelMs) {
+void foldDevice(int device, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, const uint8_t* cls, uint32_t nPublic, uint32_t logN,
+                uint8_t* out, double* kernelMs) {
     ug_r1cs_info info;
     must(ug_r1cs_parse_info(r1cs, r1csSize, &info));
     Dev d;
     openDevice(d, device);
-    foldClassesOn(d, r1cs, r1csSize, rho, cls, info.n_wires, nPublic, logN, kernelMs);
-    must(ug_dvec_download(d.fold, out11, 0, 11ull << logN));
-}
-
-void foldDevice(int device, const void* r1cs, uint64_t r1csSize, const uint8_t* rho, uint32_t nPublic, uint32_t logN, uint8_t* out8,
-                double* kernelMs) {
-    ug_r1cs_info info;
-    must(ug_r1cs_parse_info(r1cs, r1csSize, &info));
-    Dev d;
-    openDevice(d, device);
-    foldOn(d, r1cs, r1csSize, rho, info.n_wires, nPublic, logN, kernelMs);
-    must(ug_dvec_download(d.fold, out8, 0, 8ull << logN));
+    foldOn(d, r1cs, r1csSize, rho, cls, info.n_wires, nPublic, logN, kernelMs);
+    must(ug_dvec_download(d.fold, out, 0, (cls ? 11ull : 8ull) << logN));
 }
 
 struct Register {
-    Register() { deviceSums = sumsOn; deviceFold = foldDevice; deviceUltraSums = ultraSumsOn; deviceFoldClasses = foldClassesDevice; }
+    Register() { deviceSums = sumsOn; deviceFold = foldDevice; }
 } registerDevice;
 
 }  // namespace
