@@ -36,6 +36,44 @@ struct Event {
     ~Event() { if (e) (void)hipEventDestroy(e); }
 };
 
+// Owned device memory: n elements of T (move-only, empty by default). The only owner of device memory in csrc: members and
+// locals are DevBuf, kernels and kernel argument structs get the raw pointer (get()). A request for 0 elements allocates 4 bytes:
+// a buffer that was allocated is never null. The destructor frees, and hipFree waits for the whole device: where the place of a
+// free matters, release() says so at that place.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    explicit DevBuf(size_t n) { alloc(n); }
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }      // (the old memory goes with o)
+    ~DevBuf() { release(); }
+    void alloc(size_t n) { release(); UG_HIP(hipMalloc((void**)&p, n ? n * sizeof(T) : 4)); }      // frees what it held first
+    // for the callers that turn a failed allocation into a message of their own: false, and HIP's sticky error is cleared
+    bool try_alloc(size_t n) {
+        release();
+        if (hipMalloc((void**)&p, n ? n * sizeof(T) : 4) == hipSuccess) return true;
+        (void)hipGetLastError();
+        p = nullptr;
+        return false;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+    T* get() const { return p; }
+    T* take() { T* r = p; p = nullptr; return r; }      // gives up ownership
+    void adopt(T* raw) { release(); p = raw; }          // ... and takes that of memory from hipMalloc (the C interface's void*)
+};
+// Pinned host memory, the same way.
+template <class T> struct PinnedBuf {
+    T* p = nullptr;
+    PinnedBuf() = default;
+    explicit PinnedBuf(size_t n) { alloc(n); }
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { std::swap(p, o.p); return *this; }
+    ~PinnedBuf() { release(); }
+    void alloc(size_t n) { release(); UG_HIP(hipHostMalloc((void**)&p, n ? n * sizeof(T) : 4, hipHostMallocDefault)); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; }
+    T* get() const { return p; }
+};
+
 // An event recorded INSIDE a stream capture so that every launch of the resulting graph records it again (timed spans of a
 // captured launch sequence): an explicit event-record node behind the stream's current capture dependencies, which then becomes
 // the stream's dependency. (hipEventRecordWithFlags(.., hipEventRecordExternal) is the same thing in one call on ROCm 7.2, but

@@ -364,8 +364,6 @@ __global__ void lookup_clear_vec_kernel(u32* last, const u32* stage, const Looku
     if (i < d.n) last[(u64)blockIdx.y * stride + stage[d.w_off + i]] = 0;
 }
 
-template <class T> void dev_alloc(T*& p, size_t bytes) { if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
-
 }  // namespace
 
 bool CoefMatrix::build(const uint8_t* raw44_dev, u64 ncoefs_, u32 domain_, u32 nvars, hipStream_t stream) {
@@ -375,59 +373,52 @@ bool CoefMatrix::build(const uint8_t* raw44_dev, u64 ncoefs_, u32 domain_, u32 n
     while ((1u << logn) < domain) logn++;
     if (ncoefs >= ((u64)1 << 31)) throw std::invalid_argument("coefficient count exceeds 2^31");
     u32 nrows = 2 * domain;
-    u32 *keys_a = nullptr, *keys_b = nullptr, *idx_a = nullptr, *idx_b = nullptr, *bad = nullptr;
     const u64 padded = ncoefs + 8192;                  // the sort moves whole tiles
-    dev_alloc(keys_a, padded * 4); dev_alloc(keys_b, padded * 4);
-    dev_alloc(idx_a, padded * 4); dev_alloc(idx_b, padded * 4);
-    u32* flag = nullptr;
-    dev_alloc(flag, 4);
+    DevBuf<u32> keys_a(padded), keys_b(padded), idx_a(padded), idx_b(padded), flag(1);
     RadixSorter sorter;
-    dev_alloc(bad, 4);
-    dev_alloc(row_ptr, ((size_t)nrows + 1) * 4);
-    dev_alloc(sig, ncoefs * 4);
-    dev_alloc(val, ncoefs * 32);
-    UG_HIP(hipMemsetAsync(bad, 0, 4, stream));
+    DevBuf<u32> bad(1);
+    row_ptr.alloc((size_t)nrows + 1);
+    sig.alloc(ncoefs);
+    val.alloc(ncoefs * 8);
+    UG_HIP(hipMemsetAsync(bad.get(), 0, 4, stream));
     u32 bad_host = 0, sort_failed = 0;
     if (ncoefs) {
-        hipLaunchKernelGGL(coef_keys_kernel, dim3(grid_for(ncoefs, 256)), dim3(256), 0, stream, raw44_dev, ncoefs, domain, nvars, keys_a, idx_a, bad);
+        hipLaunchKernelGGL(coef_keys_kernel, dim3(grid_for(ncoefs, 256)), dim3(256), 0, stream, raw44_dev, ncoefs, domain, nvars, keys_a.get(), idx_a.get(), bad.get());
         UG_KERNEL_CHECK();
         int end_bit = 1;
         while (((u64)1 << end_bit) < nrows) end_bit++;
-        UG_HIP(hipMemsetAsync(flag, 0, 4, stream));
-        u32* const bk[2] = {keys_a, keys_b};
-        u32* const bv[2] = {idx_a, idx_b};
-        const int at = sorter.sort(nullptr, MsmGeometry(), 0, ncoefs, end_bit, bk, bv, flag, stream);      // pair form: (row key, record index)
-        hipLaunchKernelGGL(coef_gather_kernel, dim3(grid_for(ncoefs, 256)), dim3(256), 0, stream, raw44_dev, ncoefs, bv[at], sig, val);
+        UG_HIP(hipMemsetAsync(flag.get(), 0, 4, stream));
+        u32* const bk[2] = {keys_a.get(), keys_b.get()};
+        u32* const bv[2] = {idx_a.get(), idx_b.get()};
+        const int at = sorter.sort(nullptr, MsmGeometry(), 0, ncoefs, end_bit, bk, bv, flag.get(), stream);      // pair form: (row key, record index)
+        hipLaunchKernelGGL(coef_gather_kernel, dim3(grid_for(ncoefs, 256)), dim3(256), 0, stream, raw44_dev, ncoefs, bv[at], sig.get(), val.get());
         UG_KERNEL_CHECK();
-        hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for((u64)nrows + 1, 256)), dim3(256), 0, stream, bk[at], ncoefs, nrows, row_ptr);
+        hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for((u64)nrows + 1, 256)), dim3(256), 0, stream, bk[at], ncoefs, nrows, row_ptr.get());
         UG_KERNEL_CHECK();
-        UG_HIP(hipMemcpyAsync(&bad_host, bad, 4, hipMemcpyDeviceToHost, stream));
-        UG_HIP(hipMemcpyAsync(&sort_failed, flag, 4, hipMemcpyDeviceToHost, stream));
+        UG_HIP(hipMemcpyAsync(&bad_host, bad.get(), 4, hipMemcpyDeviceToHost, stream));
+        UG_HIP(hipMemcpyAsync(&sort_failed, flag.get(), 4, hipMemcpyDeviceToHost, stream));
     } else {
-        UG_HIP(hipMemsetAsync(row_ptr, 0, ((size_t)nrows + 1) * 4, stream));
+        UG_HIP(hipMemsetAsync(row_ptr.get(), 0, ((size_t)nrows + 1) * 4, stream));
     }
     UG_HIP(hipStreamSynchronize(stream));
-    hipFree(keys_a); hipFree(keys_b); hipFree(idx_a); hipFree(idx_b); hipFree(bad); hipFree(flag);
+    keys_a.release(); keys_b.release(); idx_a.release(); idx_b.release(); bad.release(); flag.release();
     sorter.release();
     if (sort_failed) throw std::runtime_error("coefficient matrix: the sort gave up waiting for a tile (look-back timeout)");
     return bad_host == 0;
 }
 
 void CoefMatrix::release() {
-    if (row_ptr) hipFree(row_ptr);
-    if (sig) hipFree(sig);
-    if (val) hipFree(val);
-    row_ptr = sig = val = nullptr;
+    row_ptr.release(); sig.release(); val.release();
 }
 
 void coef_matvec(u32* a_br, u32* b_br, const CoefMatrix& m, const u32* wtns_dev, int mask, hipStream_t stream) {
     static const bool tiled = !(measure_env("UG_MATVEC_TILED") && atoi(measure_env("UG_MATVEC_TILED")) == 0);      // A/B switch (-DUG_MEASURE)
     if (m.logn >= 8 && tiled)
         hipLaunchKernelGGL(matvec_tiled_kernel, dim3(2 * (m.domain >> 8)), dim3(256), 0, stream,
-                           a_br, b_br, m.row_ptr, m.sig, m.val, wtns_dev, m.domain, m.logn, mask);
+                           a_br, b_br, m.row_ptr.get(), m.sig.get(), m.val.get(), wtns_dev, m.domain, m.logn, mask);
     else
         hipLaunchKernelGGL(matvec_kernel, dim3(grid_for((u64)2 * m.domain, 256)), dim3(256), 0, stream,
-                           a_br, b_br, m.row_ptr, m.sig, m.val, wtns_dev, m.domain, m.logn, mask);
+                           a_br, b_br, m.row_ptr.get(), m.sig.get(), m.val.get(), wtns_dev, m.domain, m.logn, mask);
     UG_KERNEL_CHECK();
 }
 void coef_matvec_vectors(u32* a_br, u32* b_br, u64 out_stride, const CoefMatrix& m, const u32* wtns_dev, u64 wtns_stride, int vectors,
@@ -436,10 +427,10 @@ void coef_matvec_vectors(u32* a_br, u32* b_br, u64 out_stride, const CoefMatrix&
     const unsigned tiles = (unsigned)((vectors + MATVEC_VT - 1) / MATVEC_VT);
     if (m.logn >= 8)
         hipLaunchKernelGGL(matvec_tiled_vectors_kernel<MATVEC_VT>, dim3(2 * (m.domain >> 8), tiles), dim3(256), 0, stream,
-                           a_br, b_br, out_stride * 8, m.row_ptr, m.sig, m.val, wtns_dev, wtns_stride * 8, vectors, m.domain, m.logn);
+                           a_br, b_br, out_stride * 8, m.row_ptr.get(), m.sig.get(), m.val.get(), wtns_dev, wtns_stride * 8, vectors, m.domain, m.logn);
     else
         hipLaunchKernelGGL(matvec_vectors_kernel<MATVEC_VT>, dim3(grid_for((u64)2 * m.domain, 256), tiles), dim3(256), 0, stream,
-                           a_br, b_br, out_stride * 8, m.row_ptr, m.sig, m.val, wtns_dev, wtns_stride * 8, vectors, m.domain, m.logn);
+                           a_br, b_br, out_stride * 8, m.row_ptr.get(), m.sig.get(), m.val.get(), wtns_dev, wtns_stride * 8, vectors, m.domain, m.logn);
     UG_KERNEL_CHECK();
 }
 void fr_mul_pointwise(u32* out, const u32* x, const u32* y, u64 n, hipStream_t stream) {

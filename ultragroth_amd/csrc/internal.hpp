@@ -4,7 +4,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <vector>
-#include "ec.hpp"
+#include "dev_common.hpp"
 #include "stream_timer.hpp"
 
 namespace ug {
@@ -35,14 +35,14 @@ constexpr int NTT_MAX_PASSES = 8;
 
 struct NttPlan {
     int logn = -1;
-    u32* tw_fwd = nullptr;    // stage-major twiddles omega_{2^(s+1)}^j (ntt.hip: 12-word Montgomery or 20-word Shoup entries)
-    u32* tw_inv = nullptr;    // omega_n^-i,  i < n/2
-    u32* twist = nullptr;     // n^-1 * omega_{2n}^i at place bitrev(i), i < n   (coset twist with the ifft scale folded in; in the
+    DevBuf<u32> tw_fwd;       // stage-major twiddles omega_{2^(s+1)}^j (ntt.hip: 12-word Montgomery or 20-word Shoup entries)
+    DevBuf<u32> tw_inv;       // omega_n^-i,  i < n/2
+    DevBuf<u32> twist;        // n^-1 * omega_{2n}^i at place bitrev(i), i < n   (coset twist with the ifft scale folded in; in the
                               // order of the scattering pass that applies it)
-    u32* ninv = nullptr;      // n^-1 (one element)
+    DevBuf<u32> ninv;         // n^-1 (one element)
     bool shoup = true;        // twiddle tables hold (w, floor(w 2^261 / q)) pairs and the butterflies make Shoup products (ntt.hip)
     void init(int logn, hipStream_t stream);
-    void release();
+    void release();           // (ug_ctx_trim; the destructor needs no help)
     // DIT transform; see ntt.hip for the buffer rules. post / post_const are optional multipliers
     // applied in the last pass: out[i] *= post[i], or out[i] *= *post_const.
     // stats (optional): every pass launch is a timed section of it (stream_timer.hpp).
@@ -59,7 +59,6 @@ struct NttPlan {
     int passes(NttPass* list, u32* out, const u32* in, bool inverse, bool gather_bitrev, bool scatter_bitrev,
                const u32* post, const u32* post_const, const struct NttFusion* fuse = nullptr, u64 out_stride = 0, u64 in_stride = 0) const;
     void launch(const NttPass* const* lists, int count, int p, hipStream_t stream, LaunchTimer stats = LaunchTimer(), int vectors = 1) const;
-    ~NttPlan() { release(); }
 };
 
 // Every allocation or release of a per-proof device buffer (schedules, MSM workspaces, the sort's tables) moves this counter: a
@@ -68,7 +67,9 @@ struct NttPlan {
 uint64_t alloc_epoch();
 void alloc_epoch_bump();
 // (re)allocation of such a buffer (msm.hip, sort.hip)
-template <class T> void epoch_alloc(T*& p, size_t bytes) { alloc_epoch_bump(); if (p) hipFree(p); p = nullptr; UG_HIP(hipMalloc(&p, bytes ? bytes : 4)); }
+template <class T> void epoch_alloc(DevBuf<T>& b, size_t n) { alloc_epoch_bump(); b.alloc(n); }
+// ... and its release: a buffer that was never allocated moves nothing
+template <class T> void epoch_free(DevBuf<T>& b) { if (b.get()) alloc_epoch_bump(); b.release(); }
 
 // ---- msm.hip ------------------------------------------------------------------------------------------
 // Bucket classes (many-device provers, DESIGN.md section 7: the witness products sharded by BUCKET instead of by base point).
@@ -170,8 +171,8 @@ int radix_plan(int bits, int* shift, int* bins_log);          // passes; low bit
 // the unsorted pair form: keys / vals [w * n + i] = window w of scalar i (only for scalars of more than 16 windows, i.e. tiny MSMs)
 void digit_pairs(const u32* scalars, const DigitPlan& plan, u32* keys, u32* vals, hipStream_t stream);
 struct RadixSorter {
-    u32* lookback = nullptr;      // tiles x 256 status words of the pass in flight
-    u32* small = nullptr;         // 4 x 256 bin counts / starts, one tile counter per pass
+    DevBuf<u32> lookback;         // tiles x 256 status words of the pass in flight
+    DevBuf<u32> small;            // 4 x 256 bin counts / starts, one tile counter per pass
     u64 tiles_cap = 0;
     void reserve(u64 n_pairs, int ipt_min);
     void release();
@@ -179,7 +180,7 @@ struct RadixSorter {
     int sort(const u32* scalars, const MsmGeometry& geo, u32 sentinel, u64 n_pairs, int bits,
              u32* const buf_keys[2], u32* const buf_vals[2], u32* error_flag, hipStream_t stream, u32* n_valid_out = nullptr,
              bool* dropped_out = nullptr);
-    ~RadixSorter() { release(); }
+    ~RadixSorter() { release(); }      // (the release moves the epoch: the members' own destructors would not)
 };
 
 // Signed-digit decomposition of n scalars, grouped by (window, bucket): shared by every base set that
@@ -190,20 +191,20 @@ struct MsmSchedule {
     const u32* vals = nullptr;    // sorted entries: scalar index | table << 27 | sign << 31
     const u32* tkeys = nullptr;   // lane-transposed copies of keys / vals (see msm.hip: transposed_index)
     const u32* tvals = nullptr;
-    u32* bucket_start = nullptr;  // per bucket: first entry
-    u32* bucket_count = nullptr;  // per bucket: number of entries
-    u32* small_list = nullptr;    // buckets cut into 2 .. 32 segment pieces (meta[4] of them), any order
+    DevBuf<u32> bucket_start;     // per bucket: first entry
+    DevBuf<u32> bucket_count;     // per bucket: number of entries
+    DevBuf<u32> small_list;       // buckets cut into 2 .. 32 segment pieces (meta[4] of them), any order
     int log_seg = 0;              // entries per lane of the segmented accumulation = 2^log_seg ...
     int log_seg_tail = 0;         // ... and 2^log_seg_tail for the segments of the last eighth of the entries (msm.hip: SegMap)
-    u32* heavy_list = nullptr;    // device: HeavyBucket[heavy_cap]
+    DevBuf<u32> heavy_list;       // device: HeavyBucket[heavy_cap]
     u32 heavy_cap = 0;
-    u32* medium_list = nullptr;   // device: HeavyBucket[heavy_cap] for buckets of FIX_MAX < pieces <= MEDIUM_MAX
-    u32* heavy_offsets = nullptr; // device: first task of each heavy bucket (n_heavy + 1 entries)
-    u32* meta = nullptr;          // device: [n_heavy, n_valid, n_heavy_tasks, n_medium, n_small, ., ., sort failure flag] -- read by the
+    DevBuf<u32> medium_list;      // device: HeavyBucket[heavy_cap] for buckets of FIX_MAX < pieces <= MEDIUM_MAX
+    DevBuf<u32> heavy_offsets;    // device: first task of each heavy bucket (n_heavy + 1 entries)
+    DevBuf<u32> meta;             // device: [n_heavy, n_valid, n_heavy_tasks, n_medium, n_small, ., ., sort failure flag] -- read by the
                                   // kernels; the flag travels to the host with every product's result block
     // workspace
-    u32 *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr;
-    void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;       // (the library sort's scratch: UG_SORT=cub, kept for A/B runs)
+    DevBuf<u32> keys_a, keys_b, vals_a, vals_b;
+    DevBuf<uint8_t> sort_tmp; size_t sort_tmp_bytes = 0;       // (the library sort's scratch: UG_SORT=cub, kept for A/B runs)
     RadixSorter sorter;
     u64 capacity_n = 0; u64 capacity_buckets = 0;
     void reserve(const MsmGeometry& g);
@@ -213,11 +214,11 @@ struct MsmSchedule {
 };
 
 struct MsmWorkspace {
-    u32* bucket_pts = nullptr;   // total_buckets XYZZ records
-    u32* chunk_pts = nullptr;    // reduction scratch
-    u32* chunk_pts2 = nullptr;
-    u32* slot_pts = nullptr;     // two partial sums per segment of the accumulation
-    u32* task_pts = nullptr;     // partial sums of the heavy-bucket tasks
+    DevBuf<u32> bucket_pts;      // total_buckets XYZZ records
+    DevBuf<u32> chunk_pts;       // reduction scratch
+    DevBuf<u32> chunk_pts2;
+    DevBuf<u32> slot_pts;        // two partial sums per segment of the accumulation
+    DevBuf<u32> task_pts;        // partial sums of the heavy-bucket tasks
     size_t bucket_bytes = 0, chunk_bytes = 0, slot_bytes = 0, task_bytes = 0;
     void reserve(const MsmGeometry& g, bool g2, u64 n_segments, u32 n_heavy_tasks, int sets = 1);
     void release();
@@ -288,15 +289,14 @@ void check_points_mask(bool g2, const u32* pts, u64 n, int level, uint8_t* statu
 // ---- hpoly.hip ----------------------------------------------------------------------------------------
 struct CoefMatrix {
     u64 ncoefs = 0; u32 domain = 0; int logn = 0;
-    u32* row_ptr = nullptr;     // 2*domain + 1 offsets, rows = m * domain + c
-    u32* sig = nullptr;         // signal index per entry
-    u32* val = nullptr;         // packed coefficient per entry (device form, pre-scaled so that
+    DevBuf<u32> row_ptr;        // 2*domain + 1 offsets, rows = m * domain + c
+    DevBuf<u32> sig;            // signal index per entry
+    DevBuf<u32> val;            // packed coefficient per entry (device form, pre-scaled so that
                                 //   mul(w_plain, val) = w * coef in device Montgomery form)
     // raw44: ncoefs packed 44-byte records {u32 m, u32 c, u32 s, 32-byte coef} already on the device
     // (src/groth16.hpp:41-49). Returns false when a record is out of range.
     bool build(const uint8_t* raw44_dev, u64 ncoefs, u32 domain, u32 nvars, hipStream_t stream);
     void release();
-    ~CoefMatrix() { release(); }
 };
 
 // a_br[bitrev(c)] = sum coef * w  over m = 0 rows, b_br likewise for m = 1 (device form, packed)

@@ -817,7 +817,6 @@ int reduce_chunk(const MsmGeometry& g, int sets = 1, bool g2 = false) {
     return chunk;
 }
 
-template <class T> void dev_free(T*& p) { if (p) { alloc_epoch_bump(); hipFree(p); } p = nullptr; }
 std::atomic<uint64_t> g_alloc_epoch{1};
 
 }  // namespace
@@ -939,24 +938,24 @@ void MsmSchedule::reserve(const MsmGeometry& g) {
     u64 total = g.n * g.windows;
     if (total > capacity_n) {
         u64 padded = total + ((u64)64 << LOG_SEG);          // room for the lane-transposed copy's last tile
-        epoch_alloc(keys_a, padded * 4); epoch_alloc(keys_b, padded * 4);
-        epoch_alloc(vals_a, padded * 4); epoch_alloc(vals_b, padded * 4);
-        dev_free(sort_tmp); sort_tmp_bytes = 0;                // (the library sort's scratch is sized on its first use)
+        epoch_alloc(keys_a, padded); epoch_alloc(keys_b, padded);
+        epoch_alloc(vals_a, padded); epoch_alloc(vals_b, padded);
+        epoch_free(sort_tmp); sort_tmp_bytes = 0;               // (the library sort's scratch is sized on its first use)
         sorter.reserve(total, 12);
         capacity_n = total;
     }
     if (g.total_buckets() > capacity_buckets) {
-        epoch_alloc(bucket_start, g.total_buckets() * 4);
-        epoch_alloc(bucket_count, g.total_buckets() * 4);
-        epoch_alloc(small_list, g.total_buckets() * 4);
+        epoch_alloc(bucket_start, g.total_buckets());
+        epoch_alloc(bucket_count, g.total_buckets());
+        epoch_alloc(small_list, g.total_buckets());
         capacity_buckets = g.total_buckets();
     }
     u64 hcap = (total >> 5) / (FIX_MAX - 1) + 2;         // a listed bucket covers at least FIX_MAX - 1 whole segments (>= 2^5 entries each)
     if (hcap > heavy_cap) {
-        epoch_alloc(heavy_list, 4 * hcap * 4); epoch_alloc(medium_list, 4 * hcap * 4); epoch_alloc(heavy_offsets, (hcap + 1) * 4);
+        epoch_alloc(heavy_list, 4 * hcap); epoch_alloc(medium_list, 4 * hcap); epoch_alloc(heavy_offsets, hcap + 1);
         heavy_cap = (u32)hcap;
     }
-    if (!meta) epoch_alloc(meta, 32);
+    if (!meta.get()) epoch_alloc(meta, 8);
 }
 
 void MsmSchedule::build(const u32* scalars_dev, const MsmGeometry& g, hipStream_t stream) {
@@ -977,7 +976,7 @@ void MsmSchedule::build(const u32* scalars_dev, const MsmGeometry& g, hipStream_
     u32 sentinel = nb;
     int end_bit = 1;
     while (((u64)1 << end_bit) <= sentinel) end_bit++;
-    UG_HIP(hipMemsetAsync(meta, 0, 32, stream));
+    UG_HIP(hipMemsetAsync(meta.get(), 0, 32, stream));
     // the hand-written partition of sort.hip, whose first pass reads the scalars themselves (pairs in unsorted form are written
     // only when a scalar has more than 16 windows). -DUG_MEASURE builds: UG_SORT=cub takes the library sort of rounds 1-2 (A/B runs)
 #ifdef UG_MEASURE
@@ -987,56 +986,56 @@ void MsmSchedule::build(const u32* scalars_dev, const MsmGeometry& g, hipStream_
 #endif
     const bool pairs_first = use_cub || g.windows > 16;
     bool dropped = false;                 // the sort left out the zero digits and wrote the entry count to meta[1] itself
-    if (pairs_first) digit_pairs(scalars_dev, g.digit_plan(), keys_a, vals_a, stream);
+    if (pairs_first) digit_pairs(scalars_dev, g.digit_plan(), keys_a.get(), vals_a.get(), stream);
 #ifdef UG_MEASURE
     if (use_cub) {
-        hipcub::DoubleBuffer<u32> dk(keys_a, keys_b), dv(vals_a, vals_b);
+        hipcub::DoubleBuffer<u32> dk(keys_a.get(), keys_b.get()), dv(vals_a.get(), vals_b.get());
         if (!sort_tmp_bytes) {
             size_t need = 0;
             UG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, dk, dv, (int)total, 0, 32));
             epoch_alloc(sort_tmp, need); sort_tmp_bytes = need;
         }
         size_t tmp = sort_tmp_bytes;
-        UG_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, tmp, dk, dv, (int)total, 0, end_bit, stream));
+        UG_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), tmp, dk, dv, (int)total, 0, end_bit, stream));
         keys = dk.Current();
         vals = dv.Current();
     } else
 #endif
     {
-        u32* const bk[2] = {keys_a, keys_b};
-        u32* const bv[2] = {vals_a, vals_b};
-        const int at = sorter.sort(pairs_first ? nullptr : scalars_dev, g, sentinel, total, end_bit, bk, bv, meta + 7, stream, meta + 1, &dropped);
+        u32* const bk[2] = {keys_a.get(), keys_b.get()};
+        u32* const bv[2] = {vals_a.get(), vals_b.get()};
+        const int at = sorter.sort(pairs_first ? nullptr : scalars_dev, g, sentinel, total, end_bit, bk, bv, meta.get() + 7, stream, meta.get() + 1, &dropped);
         keys = bk[at];
         vals = bv[at];
     }
-    UG_HIP(hipMemsetAsync(bucket_start, 0, (size_t)nb * 4, stream));
-    UG_HIP(hipMemsetAsync(bucket_count, 0, (size_t)nb * 4, stream));
+    UG_HIP(hipMemsetAsync(bucket_start.get(), 0, (size_t)nb * 4, stream));
+    UG_HIP(hipMemsetAsync(bucket_count.get(), 0, (size_t)nb * 4, stream));
     hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, stream,
-                       keys, total, sentinel, bucket_start, bucket_count, meta, dropped ? 1 : 0);
+                       keys, total, sentinel, bucket_start.get(), bucket_count.get(), meta.get(), dropped ? 1 : 0);
     UG_KERNEL_CHECK();
-    hipLaunchKernelGGL(bucket_counts_kernel, dim3((nb + 1023) / 1024), dim3(1024), 0, stream, bucket_start, bucket_count, nb,
-                       log_seg, log_seg_tail, meta, heavy_list, medium_list, heavy_cap, small_list);
+    hipLaunchKernelGGL(bucket_counts_kernel, dim3((nb + 1023) / 1024), dim3(1024), 0, stream, bucket_start.get(), bucket_count.get(), nb,
+                       log_seg, log_seg_tail, meta.get(), heavy_list.get(), medium_list.get(), heavy_cap, small_list.get());
     UG_KERNEL_CHECK();
-    hipLaunchKernelGGL(heavy_plan_kernel, dim3(1), dim3(1024), 0, stream, (const HeavyBucket*)heavy_list, heavy_cap, meta, heavy_offsets);
+    hipLaunchKernelGGL(heavy_plan_kernel, dim3(1), dim3(1024), 0, stream, (const HeavyBucket*)heavy_list.get(), heavy_cap, meta.get(), heavy_offsets.get());
     UG_KERNEL_CHECK();
     // No read-back of the counts: every later launch is sized by an upper bound derived from n * windows and reads the
     // true counts (meta) on the device, so a schedule costs the host no synchronisation.
     // lane-transposed copy of the valid entries into the sort's spare buffers
     u64 n_tiles = (SegMap::max_segments(total, log_seg, log_seg_tail) + 63) / 64;
-    u32* tk = (keys == keys_a) ? keys_b : keys_a;
-    u32* tv = (vals == vals_a) ? vals_b : vals_a;
+    u32* tk = (keys == keys_a.get()) ? keys_b.get() : keys_a.get();
+    u32* tv = (vals == vals_a.get()) ? vals_b.get() : vals_a.get();
     {
         size_t lds = (size_t)2 * 64 * (((size_t)1 << log_seg) + 1) * 4;
         hipLaunchKernelGGL(transpose_entries_kernel, dim3((unsigned)n_tiles), dim3(1024), lds, stream,
-                           keys, vals, meta, sentinel, log_seg, log_seg_tail, tk, tv);
+                           keys, vals, meta.get(), sentinel, log_seg, log_seg_tail, tk, tv);
         UG_KERNEL_CHECK();
     }
     tkeys = tk; tvals = tv;
 }
 
 void MsmSchedule::release() {
-    dev_free(keys_a); dev_free(keys_b); dev_free(vals_a); dev_free(vals_b); dev_free(sort_tmp);
-    dev_free(bucket_start); dev_free(bucket_count); dev_free(small_list); dev_free(heavy_list); dev_free(medium_list); dev_free(heavy_offsets); dev_free(meta);
+    epoch_free(keys_a); epoch_free(keys_b); epoch_free(vals_a); epoch_free(vals_b); epoch_free(sort_tmp);
+    epoch_free(bucket_start); epoch_free(bucket_count); epoch_free(small_list); epoch_free(heavy_list); epoch_free(medium_list); epoch_free(heavy_offsets); epoch_free(meta);
     sorter.release();
     capacity_n = capacity_buckets = 0; sort_tmp_bytes = 0; vals = nullptr; keys = nullptr; heavy_cap = 0;
 }
@@ -1045,18 +1044,18 @@ void MsmSchedule::release() {
 void MsmWorkspace::reserve(const MsmGeometry& g, bool g2, u64 n_segments, u32 n_heavy_tasks, int sets) {
     size_t ptw = (size_t)(g2 ? G2Cfg::PT_WORDS : G1Cfg::PT_WORDS) * (size_t)sets;      // the products of a batch lie one after the other
     size_t need = (size_t)g.total_buckets() * ptw * 4;
-    if (need > bucket_bytes) { epoch_alloc(bucket_pts, need); bucket_bytes = need; }
+    if (need > bucket_bytes) { epoch_alloc(bucket_pts, need / 4); bucket_bytes = need; }
     const int chunk = reduce_chunk(g, sets, g2);           // the chunk the launch uses (msm_enqueue_multi): same arguments, same value
     // (bucket classes: the chunks' plain sums S0 beside their weighted sums, and the specials' sums behind both)
     size_t cneed = ((size_t)(g.cls.on() ? 2 : 1) * g.bucket_windows() * (g.buckets / chunk) + (size_t)g.window_sets()) * ptw * 4;
-    if (cneed > chunk_bytes) { epoch_alloc(chunk_pts, cneed); epoch_alloc(chunk_pts2, cneed); chunk_bytes = cneed; }
+    if (cneed > chunk_bytes) { epoch_alloc(chunk_pts, cneed / 4); epoch_alloc(chunk_pts2, cneed / 4); chunk_bytes = cneed; }
     size_t sneed = (size_t)n_segments * 2 * ptw * 4;
-    if (sneed > slot_bytes) { epoch_alloc(slot_pts, sneed); slot_bytes = sneed; }
+    if (sneed > slot_bytes) { epoch_alloc(slot_pts, sneed / 4); slot_bytes = sneed; }
     size_t tneed = (size_t)n_heavy_tasks * ptw * 4;
-    if (tneed > task_bytes) { epoch_alloc(task_pts, tneed); task_bytes = tneed; }
+    if (tneed > task_bytes) { epoch_alloc(task_pts, tneed / 4); task_bytes = tneed; }
 }
 void MsmWorkspace::release() {
-    dev_free(bucket_pts); dev_free(chunk_pts); dev_free(chunk_pts2); dev_free(slot_pts); dev_free(task_pts);
+    epoch_free(bucket_pts); epoch_free(chunk_pts); epoch_free(chunk_pts2); epoch_free(slot_pts); epoch_free(task_pts);
     bucket_bytes = chunk_bytes = slot_bytes = task_bytes = 0;
 }
 
@@ -1119,7 +1118,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
             if (nseg) {
                 const dim3 grid((unsigned)((nseg + 255) / 256)), block(256);
 #define UG_GROUP_LAUNCH(K_) hipLaunchKernelGGL((segment_accumulate_group_kernel<K_>), grid, block, 0, stream, p[0].bases, p[0].n_bases, \
-                                                   p[0].delta, s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail, ws.bucket_pts, ws.slot_pts,   \
+                                                   p[0].delta, s.keys, s.tkeys, s.tvals, s.meta.get(), s.log_seg, s.log_seg_tail, ws.bucket_pts.get(), ws.slot_pts.get(),   \
                                                    bucket_stride, slot_stride UG_FOLD_ARG)
                 if (group == 3) UG_GROUP_LAUNCH(3);
                 else if (group == 2) UG_GROUP_LAUNCH(2);
@@ -1136,8 +1135,8 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
         StreamTimer::Scope timed = stats.time(stream, g.n * g.windows);
         if (nseg) {
             hipLaunchKernelGGL(segment_accumulate_kernel<Cfg>, dim3((unsigned)((nseg + ACC_BLOCK - 1) / ACC_BLOCK)), dim3(ACC_BLOCK), 0, stream,
-                               p[j].bases, p[j].n_bases, p[j].delta, s.keys, s.tkeys, s.tvals, s.meta, s.log_seg, s.log_seg_tail,
-                               ws.bucket_pts + q * bucket_stride, ws.slot_pts + q * slot_stride);
+                               p[j].bases, p[j].n_bases, p[j].delta, s.keys, s.tkeys, s.tvals, s.meta.get(), s.log_seg, s.log_seg_tail,
+                               ws.bucket_pts.get() + q * bucket_stride, ws.slot_pts.get() + q * slot_stride);
             UG_KERNEL_CHECK();
         }
         timed.stop();
@@ -1146,21 +1145,21 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
     if (nseg > 1) {
         const u64 small_max = std::min<u64>(g.total_buckets(), nseg);       // a listed bucket crosses a segment boundary of its own
         hipLaunchKernelGGL(bucket_fixup_kernel<Cfg>, dim3((unsigned)((small_max + 127) / 128), k), dim3(128), 0, stream,
-                           s.small_list, s.meta, s.bucket_start, s.bucket_count, s.log_seg, s.log_seg_tail, ws.slot_pts, ws.bucket_pts,
+                           s.small_list.get(), s.meta.get(), s.bucket_start.get(), s.bucket_count.get(), s.log_seg, s.log_seg_tail, ws.slot_pts.get(), ws.bucket_pts.get(),
                            slot_stride, bucket_stride);
         UG_KERNEL_CHECK();
         if (nseg > FIX_MAX) {
             hipLaunchKernelGGL(medium_bucket_kernel<Cfg>, dim3(std::min<u32>((medium_max + 3) / 4, 2048), k), dim3(256), 0, stream,
-                               (const HeavyBucket*)s.medium_list, s.meta, medium_max, ws.slot_pts, ws.bucket_pts, slot_stride, bucket_stride);
+                               (const HeavyBucket*)s.medium_list.get(), s.meta.get(), medium_max, ws.slot_pts.get(), ws.bucket_pts.get(), slot_stride, bucket_stride);
             UG_KERNEL_CHECK();
         }
         if (nseg > MEDIUM_MAX) {
             hipLaunchKernelGGL(heavy_partial_kernel<Cfg>, dim3(tasks_max, k), dim3(Cfg::BLOCK), 0, stream,
-                               (const HeavyBucket*)s.heavy_list, s.heavy_offsets, s.meta, heavy_max, ws.slot_pts, ws.task_pts,
+                               (const HeavyBucket*)s.heavy_list.get(), s.heavy_offsets.get(), s.meta.get(), heavy_max, ws.slot_pts.get(), ws.task_pts.get(),
                                slot_stride, task_stride);
             UG_KERNEL_CHECK();
             hipLaunchKernelGGL(heavy_final_kernel<Cfg>, dim3(heavy_max, k), dim3(Cfg::BLOCK), 0, stream,
-                               (const HeavyBucket*)s.heavy_list, s.heavy_offsets, s.meta, heavy_max, ws.task_pts, ws.bucket_pts,
+                               (const HeavyBucket*)s.heavy_list.get(), s.heavy_offsets.get(), s.meta.get(), heavy_max, ws.task_pts.get(), ws.bucket_pts.get(),
                                task_stride, bucket_stride);
             UG_KERNEL_CHECK();
         }
@@ -1174,11 +1173,11 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
     u32 nchunks = cpw * bw;
     // with bucket classes the chunks' plain sums (S0) lie behind their weighted sums and go through the same tree: 2 bw sets
     hipLaunchKernelGGL(bucket_chunk_reduce_kernel<Cfg>, dim3((nchunks + 127) / 128), dim3(128), 0, stream,
-                       ws.bucket_pts, s.bucket_count, g.buckets, chunk, nchunks, g.c, ws.chunk_pts, (u32)windows,
-                       classes ? ws.chunk_pts + (size_t)nchunks * Cfg::PT_WORDS : (u32*)nullptr, (size_t)g.total_buckets());
+                       ws.bucket_pts.get(), s.bucket_count.get(), g.buckets, chunk, nchunks, g.c, ws.chunk_pts.get(), (u32)windows,
+                       classes ? ws.chunk_pts.get() + (size_t)nchunks * Cfg::PT_WORDS : (u32*)nullptr, (size_t)g.total_buckets());
     UG_KERNEL_CHECK();
     const int tree_sets = classes ? 2 * bw : bw;
-    u32* cur = ws.chunk_pts; u32* nxt = ws.chunk_pts2;
+    u32* cur = ws.chunk_pts.get(); u32* nxt = ws.chunk_pts2.get();
     while (cpw > 1) {
         // a lane per output (16 serial additions) while that still fills the chip, then a wave per output
         if ((u64)(cpw / 16) * tree_sets >= 8192) {
@@ -1199,7 +1198,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
     const int wsets = g.window_sets();
     const bool specials = classes && g.cls.specials;
     if (specials) {
-        hipLaunchKernelGGL(special_sum_kernel<Cfg>, dim3((unsigned)wsets, (unsigned)k), dim3(64), 0, stream, ws.bucket_pts, s.bucket_count,
+        hipLaunchKernelGGL(special_sum_kernel<Cfg>, dim3((unsigned)wsets, (unsigned)k), dim3(64), 0, stream, ws.bucket_pts.get(), s.bucket_count.get(),
                            (u32)((u64)windows * g.buckets), g.cls.specials, bucket_stride, cur + (size_t)tree_sets * Cfg::PT_WORDS, (u32)wsets);
         UG_KERNEL_CHECK();
     }
@@ -1210,7 +1209,7 @@ void msm_enqueue_multi(const MsmSchedule& s, MsmWorkspace& ws, const MsmCall& ca
         if (classes) UG_HIP(hipMemcpyAsync(host + set_words, cur + ((size_t)bw + (size_t)q * windows) * Cfg::PT_WORDS, set_words * 4, hipMemcpyDeviceToHost, stream));
         if (specials) UG_HIP(hipMemcpyAsync(host + 2 * set_words, cur + ((size_t)tree_sets + (size_t)q * wsets) * Cfg::PT_WORDS,
                                             (size_t)wsets * Cfg::PT_WORDS * 4, hipMemcpyDeviceToHost, stream));
-        UG_HIP(hipMemcpyAsync(host + MSM_PENDING_WORDS - 1, s.meta + 7, 4, hipMemcpyDeviceToHost, stream));
+        UG_HIP(hipMemcpyAsync(host + MSM_PENDING_WORDS - 1, s.meta.get() + 7, 4, hipMemcpyDeviceToHost, stream));
     }
 }
 
@@ -1283,13 +1282,11 @@ void synth_points_run(u32* out_dev, const u32* gen_record_host, u64 seed, u64 n,
         Cfg::store_affine_packed(table.data() + (size_t)j * Cfg::AFF_WORDS, ax, ay);
         p = xyzz_dbl(p);
     }
-    u32* d_table = nullptr;
-    UG_HIP(hipMalloc(&d_table, table.size() * 4));
-    UG_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(synth_points_kernel<Cfg>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, stream, d_table, seed, n, out_dev);
+    DevBuf<u32> d_table(table.size());
+    UG_HIP(hipMemcpyAsync(d_table.get(), table.data(), table.size() * 4, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(synth_points_kernel<Cfg>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, stream, d_table.get(), seed, n, out_dev);
     UG_KERNEL_CHECK();
     UG_HIP(hipStreamSynchronize(stream));
-    hipFree(d_table);
 }
 }  // namespace
 

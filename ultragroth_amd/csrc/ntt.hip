@@ -387,10 +387,10 @@ void NttPlan::init(int logn_, hipStream_t stream) {
     // lanes of a wave touch consecutive 32-byte entries at every stage (a single table of omega_n^i indexed with a
     // stage-dependent stride makes the late stages hit one L2 channel with 64 KiB strides).
     u64 entries = n > 1 ? n - 1 : 1;
-    UG_HIP(hipMalloc(&tw_fwd, entries * tw_words * 4));
-    UG_HIP(hipMalloc(&tw_inv, entries * tw_words * 4));
-    UG_HIP(hipMalloc(&twist, n * 32));
-    UG_HIP(hipMalloc(&ninv, 32));
+    tw_fwd.alloc(entries * tw_words);
+    tw_inv.alloc(entries * tw_words);
+    twist.alloc(n * 8);
+    ninv.alloc(8);
     Fr w2n = fr_root_of_unity(logn + 1);
     Fr n_inverse = cond_sub_q(inv(host_fr_from_u64(n)));
     Fr one = cond_sub_q(fp_one<FrParams>());
@@ -401,9 +401,9 @@ void NttPlan::init(int logn_, hipStream_t stream) {
         pack256(consts.data() + (size_t)(3 + 2 * st) * 8, w);
         pack256(consts.data() + (size_t)(4 + 2 * st) * 8, cond_sub_q(inv(w)));
     }
-    u32* d_consts;
-    UG_HIP(hipMalloc(&d_consts, consts.size() * 4));
-    UG_HIP(hipMemcpyAsync(d_consts, consts.data(), consts.size() * 4, hipMemcpyHostToDevice, stream));
+    DevBuf<u32> consts_dev(consts.size());
+    const u32* d_consts = consts_dev.get();
+    UG_HIP(hipMemcpyAsync(consts_dev.get(), consts.data(), consts.size() * 4, hipMemcpyHostToDevice, stream));
     auto launch = [&](u32* table, int base_i, int scale_i, u64 count, int unpacked) {
         u64 threads = (count + POW_RUN - 1) / POW_RUN;
         unsigned blocks = (unsigned)((threads + 255) / 256);
@@ -412,28 +412,21 @@ void NttPlan::init(int logn_, hipStream_t stream) {
     };
     for (int st = 0; st < logn; st++) {
         u64 off = ((u64)1 << st) - 1;
-        launch(tw_fwd + off * tw_words, 3 + 2 * st, 2, (u64)1 << st, shoup ? 2 : 1);
-        launch(tw_inv + off * tw_words, 4 + 2 * st, 2, (u64)1 << st, shoup ? 2 : 1);
+        launch(tw_fwd.get() + off * tw_words, 3 + 2 * st, 2, (u64)1 << st, shoup ? 2 : 1);
+        launch(tw_inv.get() + off * tw_words, 4 + 2 * st, 2, (u64)1 << st, shoup ? 2 : 1);
     }
     // n^-1 * omega_{2n}^i (packed: one product per element, in the last pass of the inverse transform), stored at bitrev(i):
     // that pass scatters element i to place bitrev(i) and multiplies there
-    u32* natural = nullptr;
-    UG_HIP(hipMalloc(&natural, n * 32));
-    launch(natural, 0, 1, n, 0);
-    hipLaunchKernelGGL(bitrev_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, twist, natural, logn);
+    DevBuf<u32> natural(n * 8);
+    launch(natural.get(), 0, 1, n, 0);
+    hipLaunchKernelGGL(bitrev_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, twist.get(), natural.get(), logn);
     UG_KERNEL_CHECK();
-    UG_HIP(hipMemcpyAsync(ninv, d_consts + 8, 32, hipMemcpyDeviceToDevice, stream));
+    UG_HIP(hipMemcpyAsync(ninv.get(), d_consts + 8, 32, hipMemcpyDeviceToDevice, stream));
     UG_HIP(hipStreamSynchronize(stream));
-    UG_HIP(hipFree(natural));
-    UG_HIP(hipFree(d_consts));
 }
 
 void NttPlan::release() {
-    if (tw_fwd) hipFree(tw_fwd);
-    if (tw_inv) hipFree(tw_inv);
-    if (twist) hipFree(twist);
-    if (ninv) hipFree(ninv);
-    tw_fwd = tw_inv = twist = ninv = nullptr;
+    tw_fwd.release(); tw_inv.release(); twist.release(); ninv.release();
 }
 
 // The passes of one DIT transform. `in` holds the input in bit-reversed order unless gather_bitrev is set (then
@@ -478,7 +471,7 @@ int NttPlan::passes(NttPass* list, u32* out, const u32* in, bool inverse, bool g
         a.in2_stride = a.in2 ? fuse->in2_stride : 0;
         a.fin_a_stride = a.fin_a ? fuse->fin_a_stride : 0;
         a.fin_b_stride = a.fin_b ? fuse->fin_b_stride : 0;
-        a.tw = inverse ? tw_inv : tw_fwd; a.logn = logn; a.s0 = s0; a.k = stages[p];
+        a.tw = inverse ? tw_inv.get() : tw_fwd.get(); a.logn = logn; a.s0 = s0; a.k = stages[p];
         a.j = nj[p];
         if (s0 > 0 && a.j > s0) a.j = s0;
         a.gather_bitrev = (p == 0 && gather_bitrev) ? 1 : 0;

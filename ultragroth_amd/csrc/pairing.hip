@@ -237,12 +237,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const u32* __restrict_
     dst[t] = src[(size_t)index[row] * (size_t)words + w];
 }
 
-struct DevBuf {
-    u32* p = nullptr;
-    explicit DevBuf(size_t words) { UG_HIP(hipMalloc(&p, words * sizeof(u32))); }
-    ~DevBuf() { if (p) hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-};
 unsigned blocks(size_t lanes) { return (unsigned)((lanes + 63) / 64); }
 
 }  // namespace
@@ -251,28 +245,28 @@ unsigned blocks(size_t lanes) { return (unsigned)((lanes + 63) / 64); }
 static void run_pass(const PairingConsts& kc, const u32* a, const u32* b, const u32* g, const u32* r, int n_, int k_, u32* f_tree, u32* g_tree,
                      double kernel_ms[3]) {
     const size_t n = (size_t)n_, k = (size_t)k_, nodes = tree_nodes(n);
-    DevBuf f(nodes * F12_WORDS), s(nodes * k * XYZZ_WORDS);
+    DevBuf<u32> f(nodes * F12_WORDS), s(nodes * k * XYZZ_WORDS);
     Event t0(true), t1(true), t2(true), t3(true);
     UG_HIP(hipEventRecord(t0.e, nullptr));
-    hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a, b, g, r, n_, k_, f.p, s.p);
+    hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a, b, g, r, n_, k_, f.get(), s.get());
     UG_KERNEL_CHECK();
     UG_HIP(hipEventRecord(t1.e, nullptr));
     size_t off = 0;
     for (size_t m = n; m > 1; m = (m + 1) / 2) {                    // level of m nodes at `off` -> (m + 1) / 2 nodes behind it
-        hipLaunchKernelGGL(f12_tree_kernel, dim3(blocks((m + 1) / 2)), dim3(64), 0, nullptr, kc, f.p + off * F12_WORDS, (int)m, f.p + (off + m) * F12_WORDS);
+        hipLaunchKernelGGL(f12_tree_kernel, dim3(blocks((m + 1) / 2)), dim3(64), 0, nullptr, kc, f.get() + off * F12_WORDS, (int)m, f.get() + (off + m) * F12_WORDS);
         UG_KERNEL_CHECK();
         off += m;
     }
     UG_HIP(hipEventRecord(t2.e, nullptr));
     off = 0;
     for (size_t m = n; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(g1_tree_kernel, dim3(blocks(((m + 1) / 2) * k)), dim3(64), 0, nullptr, s.p + off * k * XYZZ_WORDS, (int)m, k_, s.p + (off + m) * k * XYZZ_WORDS);
+        hipLaunchKernelGGL(g1_tree_kernel, dim3(blocks(((m + 1) / 2) * k)), dim3(64), 0, nullptr, s.get() + off * k * XYZZ_WORDS, (int)m, k_, s.get() + (off + m) * k * XYZZ_WORDS);
         UG_KERNEL_CHECK();
         off += m;
     }
     UG_HIP(hipEventRecord(t3.e, nullptr));
-    UG_HIP(hipMemcpy(f_tree, f.p, nodes * F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
-    UG_HIP(hipMemcpy(g_tree, s.p, nodes * k * XYZZ_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(f_tree, f.get(), nodes * F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(g_tree, s.get(), nodes * k * XYZZ_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
     float ms[3] = {0, 0, 0};
     UG_HIP(hipEventElapsedTime(&ms[0], t0.e, t1.e));
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
@@ -284,18 +278,18 @@ void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb)
     if (pb.n <= 0 || pb.n > PAIRING_PASS || (pb.k != 1 && pb.k != 2)) throw std::invalid_argument("pairing_batch_device: bad shape");
     UG_HIP(hipSetDevice(device));
     const size_t n = (size_t)pb.n, k = (size_t)pb.k;
-    DevBuf a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), r(n * 4);
-    UG_HIP(hipMemcpy(a.p, pb.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(b.p, pb.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(g.p, pb.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(r.p, pb.r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
-    run_pass(kc, a.p, b.p, g.p, r.p, pb.n, pb.k, pb.f_tree, pb.g_tree, pb.kernel_ms);
+    DevBuf<u32> a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), r(n * 4);
+    UG_HIP(hipMemcpy(a.get(), pb.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(b.get(), pb.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(g.get(), pb.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(r.get(), pb.r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
+    run_pass(kc, a.get(), b.get(), g.get(), r.get(), pb.n, pb.k, pb.f_tree, pb.g_tree, pb.kernel_ms);
 }
 
 // ---- the resident form: the pass's raw records cross PCIe once and its arrays never leave the device ---------------------
 struct ResidentBatch::Impl {
     int device, n, k, format;
-    DevBuf records, a, b, g, bz, status;
+    DevBuf<u32> records, a, b, g, bz, status;
     Impl(int device_, int n_, int k_, int format_)
         : device(device_), n(n_), k(k_), format(format_), records((size_t)n_ * record_words(k_, format_)), a((size_t)n_ * G1_WORDS), b((size_t)n_ * G2_WORDS),
           g((size_t)n_ * k_ * G1_WORDS), bz((size_t)n_ * 32), status(((size_t)n_ + 3) / 4 * 2) {}      // status: n bytes from each check
@@ -314,17 +308,17 @@ void ResidentBatch::ingest(const void* records, unsigned char* status) {
     static const DecompressConsts c = decompress_consts();         // the plain and EVM kernels take its IngestConsts part
     const IngestConsts& ci = c;
     const size_t n = (size_t)m.n, room = (n + 3) / 4 * 4;
-    uint8_t* curve = reinterpret_cast<uint8_t*>(m.status.p);
+    uint8_t* curve = reinterpret_cast<uint8_t*>(m.status.get());
     uint8_t* subgroup = curve + room;
-    UG_HIP(hipMemcpy(m.records.p, records, n * record_words(m.k, m.format) * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(m.records.get(), records, n * record_words(m.k, m.format) * sizeof(u32), hipMemcpyHostToDevice));
     if (m.format == RECORDS_COMPRESSED)
-        hipLaunchKernelGGL(records_decompress_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, c, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+        hipLaunchKernelGGL(records_decompress_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.get(), m.n, m.k, c, m.a.get(), m.b.get(), m.g.get(), m.bz.get(), curve);
     else if (m.format == RECORDS_EVM)
-        hipLaunchKernelGGL(records_ingest_kernel<RECORDS_EVM>, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, ci, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+        hipLaunchKernelGGL(records_ingest_kernel<RECORDS_EVM>, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.get(), m.n, m.k, ci, m.a.get(), m.b.get(), m.g.get(), m.bz.get(), curve);
     else
-        hipLaunchKernelGGL(records_ingest_kernel<RECORDS_PLAIN>, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.p, m.n, m.k, ci, m.a.p, m.b.p, m.g.p, m.bz.p, curve);
+        hipLaunchKernelGGL(records_ingest_kernel<RECORDS_PLAIN>, dim3(blocks(n)), dim3(64), 0, nullptr, m.records.get(), m.n, m.k, ci, m.a.get(), m.b.get(), m.g.get(), m.bz.get(), curve);
     UG_KERNEL_CHECK();
-    check_points_mask(true, m.bz.p, n, 2, subgroup, nullptr);      // (a record that failed above is infinity here: it passes)
+    check_points_mask(true, m.bz.get(), n, 2, subgroup, nullptr);      // (a record that failed above is infinity here: it passes)
     std::vector<uint8_t> both(2 * room);
     UG_HIP(hipMemcpy(both.data(), curve, 2 * room, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) status[i] = both[i] ? both[i] : both[room + i];
@@ -334,9 +328,9 @@ void ResidentBatch::download(u32* a, u32* b, u32* g) {
     Impl& m = *impl;
     UG_HIP(hipSetDevice(m.device));
     const size_t n = (size_t)m.n;
-    if (a) UG_HIP(hipMemcpy(a, m.a.p, n * G1_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
-    if (b) UG_HIP(hipMemcpy(b, m.b.p, n * G2_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
-    if (g) UG_HIP(hipMemcpy(g, m.g.p, n * (size_t)m.k * G1_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    if (a) UG_HIP(hipMemcpy(a, m.a.get(), n * G1_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    if (b) UG_HIP(hipMemcpy(b, m.b.get(), n * G2_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    if (g) UG_HIP(hipMemcpy(g, m.g.get(), n * (size_t)m.k * G1_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
 }
 
 void ResidentBatch::run(const PairingConsts& kc, const u32* keep, int kept, const u32* r, u32* f_tree, u32* g_tree, double kernel_ms[3]) {
@@ -344,21 +338,21 @@ void ResidentBatch::run(const PairingConsts& kc, const u32* keep, int kept, cons
     if (kept <= 0 || kept > m.n || (!keep && kept != m.n)) throw std::invalid_argument("ResidentBatch: bad shape");
     UG_HIP(hipSetDevice(m.device));
     const size_t n = (size_t)kept, k = (size_t)m.k;
-    DevBuf rd(n * 4);
-    UG_HIP(hipMemcpy(rd.p, r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
-    if (!keep) { run_pass(kc, m.a.p, m.b.p, m.g.p, rd.p, kept, m.k, f_tree, g_tree, kernel_ms); return; }
+    DevBuf<u32> rd(n * 4);
+    UG_HIP(hipMemcpy(rd.get(), r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
+    if (!keep) { run_pass(kc, m.a.get(), m.b.get(), m.g.get(), rd.get(), kept, m.k, f_tree, g_tree, kernel_ms); return; }
     for (size_t i = 0; i < n; i++)                                  // the gather reads row keep[i]: inside the pass, ascending
         if (keep[i] >= (u32)m.n || (i && keep[i] <= keep[i - 1])) throw std::invalid_argument("ResidentBatch: bad index list");
-    DevBuf index(n), a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS);
-    UG_HIP(hipMemcpy(index.p, keep, n * sizeof(u32), hipMemcpyHostToDevice));
+    DevBuf<u32> index(n), a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS);
+    UG_HIP(hipMemcpy(index.get(), keep, n * sizeof(u32), hipMemcpyHostToDevice));
     auto gather = [&](const u32* src, int words, u32* dst) {
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * (size_t)words + 255) / 256)), dim3(256), 0, nullptr, src, index.p, n, words, dst);
+        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n * (size_t)words + 255) / 256)), dim3(256), 0, nullptr, src, index.get(), n, words, dst);
         UG_KERNEL_CHECK();
     };
-    gather(m.a.p, G1_WORDS, a.p);
-    gather(m.b.p, G2_WORDS, b.p);
-    gather(m.g.p, (int)k * G1_WORDS, g.p);
-    run_pass(kc, a.p, b.p, g.p, rd.p, kept, m.k, f_tree, g_tree, kernel_ms);
+    gather(m.a.get(), G1_WORDS, a.get());
+    gather(m.b.get(), G2_WORDS, b.get());
+    gather(m.g.get(), (int)k * G1_WORDS, g.get());
+    run_pass(kc, a.get(), b.get(), g.get(), rd.get(), kept, m.k, f_tree, g_tree, kernel_ms);
 }
 
 // the vkx step keeps at most this many XYZZ products on the device at a time (144 bytes each)
@@ -369,29 +363,29 @@ void pairing_judge_device(int device, const FinalExpConsts& kc, PairingJudge& pj
     UG_HIP(hipSetDevice(device));
     const size_t n = (size_t)pj.n, k = (size_t)pj.k, cols = (size_t)pj.cols;
     const size_t chunk = std::min(n, std::max<size_t>(1, VKX_CHUNK_TERMS / cols));           // suspects per launch of the vkx step
-    DevBuf a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), points(cols * G1_WORDS), key((1 + k) * G2_WORDS), fab(F12_WORDS);
-    DevBuf scalars(chunk * cols * 8), terms(chunk * cols * XYZZ_WORDS), nvkx(n * G1_WORDS), verdict(n);
+    DevBuf<u32> a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), points(cols * G1_WORDS), key((1 + k) * G2_WORDS), fab(F12_WORDS);
+    DevBuf<u32> scalars(chunk * cols * 8), terms(chunk * cols * XYZZ_WORDS), nvkx(n * G1_WORDS), verdict(n);
     Event t0(true), t1(true), t2(true);
-    UG_HIP(hipMemcpy(a.p, pj.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(b.p, pj.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(g.p, pj.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(points.p, pj.points, cols * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(key.p, pj.key_g2, (1 + k) * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(fab.p, pj.f_alpha_beta, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(a.get(), pj.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(b.get(), pj.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(g.get(), pj.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(points.get(), pj.points, cols * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(key.get(), pj.key_g2, (1 + k) * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(fab.get(), pj.f_alpha_beta, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipEventRecord(t0.e, nullptr));
     for (size_t first = 0; first < n; first += chunk) {
         const size_t m = std::min(chunk, n - first);
-        UG_HIP(hipMemcpy(scalars.p, pj.scalars + first * cols * 8, m * cols * 8 * sizeof(u32), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(vkx_mul_kernel, dim3(blocks(m * cols)), dim3(64), 0, nullptr, points.p, scalars.p, m * cols, pj.cols, terms.p);
+        UG_HIP(hipMemcpy(scalars.get(), pj.scalars + first * cols * 8, m * cols * 8 * sizeof(u32), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(vkx_mul_kernel, dim3(blocks(m * cols)), dim3(64), 0, nullptr, points.get(), scalars.get(), m * cols, pj.cols, terms.get());
         UG_KERNEL_CHECK();
-        hipLaunchKernelGGL(vkx_sum_kernel, dim3((unsigned)m), dim3(64), 0, nullptr, terms.p, pj.cols, nvkx.p + first * G1_WORDS);
+        hipLaunchKernelGGL(vkx_sum_kernel, dim3((unsigned)m), dim3(64), 0, nullptr, terms.get(), pj.cols, nvkx.get() + first * G1_WORDS);
         UG_KERNEL_CHECK();
     }
     UG_HIP(hipEventRecord(t1.e, nullptr));
-    hipLaunchKernelGGL(judge_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.p, b.p, nvkx.p, g.p, key.p, fab.p, pj.n, pj.k, verdict.p);
+    hipLaunchKernelGGL(judge_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.get(), b.get(), nvkx.get(), g.get(), key.get(), fab.get(), pj.n, pj.k, verdict.get());
     UG_KERNEL_CHECK();
     UG_HIP(hipEventRecord(t2.e, nullptr));
-    UG_HIP(hipMemcpy(pj.verdict, verdict.p, n * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(pj.verdict, verdict.get(), n * sizeof(u32), hipMemcpyDeviceToHost));
     float ms[2] = {0, 0};
     UG_HIP(hipEventElapsedTime(&ms[0], t0.e, t1.e));
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
@@ -402,23 +396,23 @@ void fq2_sqrt_device(int device, const DecompressConsts& c, int count, const u32
     if (count <= 0) return;
     UG_HIP(hipSetDevice(device));
     const size_t n = (size_t)count;
-    DevBuf din(n * 16), dout(n * 16), flag((n + 3) / 4);
-    UG_HIP(hipMemcpy(din.p, in, n * 16 * sizeof(u32), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(fq2_sqrt_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, c, din.p, count, dout.p, reinterpret_cast<uint8_t*>(flag.p));
+    DevBuf<u32> din(n * 16), dout(n * 16), flag((n + 3) / 4);
+    UG_HIP(hipMemcpy(din.get(), in, n * 16 * sizeof(u32), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(fq2_sqrt_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, c, din.get(), count, dout.get(), reinterpret_cast<uint8_t*>(flag.get()));
     UG_KERNEL_CHECK();
-    UG_HIP(hipMemcpy(out, dout.p, n * 16 * sizeof(u32), hipMemcpyDeviceToHost));
-    UG_HIP(hipMemcpy(has_root, flag.p, n, hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(out, dout.get(), n * 16 * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(has_root, flag.get(), n, hipMemcpyDeviceToHost));
 }
 
 void final_exp_device(int device, const FinalExpConsts& kc, const u32* f, u32* g, int* is_one) {
     UG_HIP(hipSetDevice(device));
-    DevBuf in(F12_WORDS), out(F12_WORDS), flag(1);
-    UG_HIP(hipMemcpy(in.p, f, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(final_exp_kernel, dim3(1), dim3(64), 0, nullptr, kc, in.p, out.p, flag.p);
+    DevBuf<u32> in(F12_WORDS), out(F12_WORDS), flag(1);
+    UG_HIP(hipMemcpy(in.get(), f, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(final_exp_kernel, dim3(1), dim3(64), 0, nullptr, kc, in.get(), out.get(), flag.get());
     UG_KERNEL_CHECK();
     u32 one = 0;
-    UG_HIP(hipMemcpy(g, out.p, F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
-    UG_HIP(hipMemcpy(&one, flag.p, sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(g, out.get(), F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
+    UG_HIP(hipMemcpy(&one, flag.get(), sizeof(u32), hipMemcpyDeviceToHost));
     *is_one = (int)one;
 }
 

@@ -130,14 +130,14 @@ void intt_on_device(hipStream_t stream, StreamTimer& timer, int logN, int nVec, 
     inttScale(logN, c.w);
     DevBuf<u32> dSrc(std::max<u64>((u64)nVec * nGiven, 1) * Cfg::AFF_WORDS), dWork((u64)nVec * N * Cfg::AFF_WORDS), dTw(half * 8);
     for (int v = 0; v < nVec; v++)
-        if (nGiven) UG_HIP(hipMemcpyAsync(dSrc.p + (u64)v * nGiven * Cfg::AFF_WORDS, in[v], nGiven * REC, hipMemcpyHostToDevice, stream));
-    UG_HIP(hipMemcpyAsync(dTw.p, tw.data(), half * 32, hipMemcpyHostToDevice, stream));
-    if (std::is_same<typename Cfg::F, Fq2>::value) convert_points_g2(dSrc.p, (u64)nVec * nGiven, stream);
-    else convert_points_g1(dSrc.p, (u64)nVec * nGiven, stream);
+        if (nGiven) UG_HIP(hipMemcpyAsync(dSrc.get() + (u64)v * nGiven * Cfg::AFF_WORDS, in[v], nGiven * REC, hipMemcpyHostToDevice, stream));
+    UG_HIP(hipMemcpyAsync(dTw.get(), tw.data(), half * 32, hipMemcpyHostToDevice, stream));
+    if (std::is_same<typename Cfg::F, Fq2>::value) convert_points_g2(dSrc.get(), (u64)nVec * nGiven, stream);
+    else convert_points_g1(dSrc.get(), (u64)nVec * nGiven, stream);
     TimeSink scale, stages;
     {
         StreamTimer::Scope sc = timer.time(stream, &scale);
-        hipLaunchKernelGGL(intt_scale_kernel<Cfg>, dim3(grid_for(N, Cfg::BLOCK), nVec), dim3(Cfg::BLOCK), 0, stream, dSrc.p, dWork.p, (u32)logN,
+        hipLaunchKernelGGL(intt_scale_kernel<Cfg>, dim3(grid_for(N, Cfg::BLOCK), nVec), dim3(Cfg::BLOCK), 0, stream, dSrc.get(), dWork.get(), (u32)logN,
                            (u32)nGiven, c);
         UG_KERNEL_CHECK();
         sc.stop();
@@ -146,13 +146,13 @@ void intt_on_device(hipStream_t stream, StreamTimer& timer, int logN, int nVec, 
         StreamTimer::Scope sc = timer.time(stream, &stages);
         const dim3 grid(grid_for(half, Cfg::BLOCK), nVec), block(Cfg::BLOCK);
         for (int s = 0; s < logN; s++) {
-            if (s == logN - 1) hipLaunchKernelGGL((intt_stage_kernel<Cfg, true>), grid, block, 0, stream, dWork.p, dTw.p, (u32)logN, (u32)s);
-            else hipLaunchKernelGGL((intt_stage_kernel<Cfg, false>), grid, block, 0, stream, dWork.p, dTw.p, (u32)logN, (u32)s);
+            if (s == logN - 1) hipLaunchKernelGGL((intt_stage_kernel<Cfg, true>), grid, block, 0, stream, dWork.get(), dTw.get(), (u32)logN, (u32)s);
+            else hipLaunchKernelGGL((intt_stage_kernel<Cfg, false>), grid, block, 0, stream, dWork.get(), dTw.get(), (u32)logN, (u32)s);
             UG_KERNEL_CHECK();
         }
         sc.stop();
     }
-    for (int v = 0; v < nVec; v++) UG_HIP(hipMemcpyAsync(out[v], dWork.p + (u64)v * N * Cfg::AFF_WORDS, N * REC, hipMemcpyDeviceToHost, stream));
+    for (int v = 0; v < nVec; v++) UG_HIP(hipMemcpyAsync(out[v], dWork.get() + (u64)v * N * Cfg::AFF_WORDS, N * REC, hipMemcpyDeviceToHost, stream));
     UG_HIP(hipStreamSynchronize(stream));
     timer.resolve();
     if (ms) { ms[0] = scale.ms; ms[1] = stages.ms; }

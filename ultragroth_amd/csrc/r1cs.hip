@@ -107,7 +107,7 @@ void r1cs_row_values(const R1csDev& m, const u32* wtns, u32 k, u32* out24, hipSt
 }
 void r1cs_match(const R1csDev& m, const CoefMatrix& zk, u32 n_public, const u32* z, unsigned long long* word, hipStream_t stream) {
     UG_HIP(hipMemsetAsync(word, 0xff, 8, stream));
-    hipLaunchKernelGGL(r1cs_match_kernel, dim3(grid_for(zk.domain, 256), 2), dim3(256), 0, stream, m, zk.row_ptr, zk.sig, zk.val, zk.domain,
+    hipLaunchKernelGGL(r1cs_match_kernel, dim3(grid_for(zk.domain, 256), 2), dim3(256), 0, stream, m, zk.row_ptr.get(), zk.sig.get(), zk.val.get(), zk.domain,
                        n_public, z, word);
     UG_KERNEL_CHECK();
 }

@@ -341,10 +341,10 @@ public:
     void lagrange(int logN, const Fr& x, const Fr& scale, const Fr& omega, uint8_t* out) override {
         const u64 N = 1ull << logN;
         DevBuf<u32> d(N * 8);
-        launchLagrange(d.p, logN, x, scale, omega);
-        hipLaunchKernelGGL(fr_to_plain_kernel, dim3(grid_for(N, 256)), dim3(256), 0, stream_, d.p, N);
+        launchLagrange(d.get(), logN, x, scale, omega);
+        hipLaunchKernelGGL(fr_to_plain_kernel, dim3(grid_for(N, 256)), dim3(256), 0, stream_, d.get(), N);
         UG_KERNEL_CHECK();
-        UG_HIP(hipMemcpyAsync(out, d.p, N * 32, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(out, d.get(), N * 32, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipStreamSynchronize(stream_));
     }
 
@@ -352,7 +352,7 @@ public:
         if (n > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 scalars");
         const int rec = g2 ? 128 : 64;
         DevBuf<u32> s(n * 8), o(n * (rec / 4)), idx(n), count(1);
-        UG_HIP(hipMemcpyAsync(s.p, scalars, n * 32, hipMemcpyHostToDevice, stream_));
+        UG_HIP(hipMemcpyAsync(s.get(), scalars, n * 32, hipMemcpyHostToDevice, stream_));
         TimeSink build, mul;
         Table t;
         {
@@ -362,10 +362,10 @@ public:
         }
         {
             StreamTimer::Scope sc = timer_.time(stream_, &mul);
-            mulSet(t, s.p, n, idx.p, count.p, true, o.p);
+            mulSet(t, s.get(), n, idx.get(), count.get(), true, o.get());
             sc.stop();
         }
-        UG_HIP(hipMemcpyAsync(out, o.p, n * rec, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(out, o.get(), n * rec, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipStreamSynchronize(stream_));
         timer_.resolve();
         if (ms) { ms[0] = build.ms; ms[1] = mul.ms; }
@@ -395,20 +395,20 @@ public:
         for (int m = 0; m < 3; m++) {
             const u64 terms = cm[m].terms();
             colPtr[m].alloc(M + 1); row[m].alloc(terms); val[m].alloc(terms * 8);
-            UG_HIP(hipMemcpyAsync(colPtr[m].p, cm[m].colPtr.data(), (M + 1) * 4, hipMemcpyHostToDevice, stream_));
+            UG_HIP(hipMemcpyAsync(colPtr[m].get(), cm[m].colPtr.data(), (M + 1) * 4, hipMemcpyHostToDevice, stream_));
             if (terms) {
-                UG_HIP(hipMemcpyAsync(row[m].p, cm[m].row.data(), terms * 4, hipMemcpyHostToDevice, stream_));
-                UG_HIP(hipMemcpyAsync(val[m].p, cm[m].val.data(), terms * 32, hipMemcpyHostToDevice, stream_));
-                hipLaunchKernelGGL(fr_from_plain_kernel, dim3(grid_for(terms, 256)), dim3(256), 0, stream_, val[m].p, terms);
+                UG_HIP(hipMemcpyAsync(row[m].get(), cm[m].row.data(), terms * 4, hipMemcpyHostToDevice, stream_));
+                UG_HIP(hipMemcpyAsync(val[m].get(), cm[m].val.data(), terms * 32, hipMemcpyHostToDevice, stream_));
+                hipLaunchKernelGGL(fr_from_plain_kernel, dim3(grid_for(terms, 256)), dim3(256), 0, stream_, val[m].get(), terms);
                 UG_KERNEL_CHECK();
             }
-            cd.col_ptr[m] = colPtr[m].p; cd.row[m] = row[m].p; cd.val[m] = val[m].p;
+            cd.col_ptr[m] = colPtr[m].get(); cd.row[m] = row[m].get(); cd.val[m] = val[m].get();
         }
         DevBuf<Piece> dPieces(pieces.size());
         DevBuf<u32> partial(pieces.size() * 8);
         DevBuf<uint8_t> cls(M);
-        if (!pieces.empty()) UG_HIP(hipMemcpyAsync(dPieces.p, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, stream_));
-        UG_HIP(hipMemcpyAsync(cls.p, p.cls.data(), M, hipMemcpyHostToDevice, stream_));
+        if (!pieces.empty()) UG_HIP(hipMemcpyAsync(dPieces.get(), pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, stream_));
+        UG_HIP(hipMemcpyAsync(cls.get(), p.cls.data(), M, hipMemcpyHostToDevice, stream_));
         DevBuf<u32> lag(N * 8), lagCoset(N * 8), sa(M * 8), sb(M * 8), sk(M * 8), sh(N * 8);
         UG_HIP(hipStreamSynchronize(stream_));
         ms[0] += nowMs() - t0;
@@ -416,8 +416,8 @@ public:
         TimeSink sinks[4];
         {
             StreamTimer::Scope sc = timer_.time(stream_, &sinks[0]);
-            launchLagrange(lag.p, p.logN, p.x[0], p.lagScale[0], p.omega);
-            launchLagrange(lagCoset.p, p.logN, p.x[1], p.lagScale[1], p.omega);
+            launchLagrange(lag.get(), p.logN, p.x[0], p.lagScale[0], p.omega);
+            launchLagrange(lagCoset.get(), p.logN, p.x[1], p.lagScale[1], p.omega);
             sc.stop();
         }
         {
@@ -433,12 +433,12 @@ public:
             }
             wa.piece_first[3] = at;
             if (!pieces.empty()) {
-                hipLaunchKernelGGL(column_pieces_kernel, dim3((unsigned)pieces.size()), dim3(256), 0, stream_, cd, dPieces.p, (u32)pieces.size(), lag.p, partial.p);
+                hipLaunchKernelGGL(column_pieces_kernel, dim3((unsigned)pieces.size()), dim3(256), 0, stream_, cd, dPieces.get(), (u32)pieces.size(), lag.get(), partial.get());
                 UG_KERNEL_CHECK();
             }
-            hipLaunchKernelGGL(wire_sums_kernel, dim3(grid_for(M, 256)), dim3(256), 0, stream_, cd, dPieces.p, partial.p, lag.p, cls.p, wa, sa.p, sb.p, sk.p);
+            hipLaunchKernelGGL(wire_sums_kernel, dim3(grid_for(M, 256)), dim3(256), 0, stream_, cd, dPieces.get(), partial.get(), lag.get(), cls.get(), wa, sa.get(), sb.get(), sk.get());
             UG_KERNEL_CHECK();
-            hipLaunchKernelGGL(h_scalars_kernel, dim3(grid_for(N, 256)), dim3(256), 0, stream_, sh.p, lagCoset.p, N, words_of(p.hScale));
+            hipLaunchKernelGGL(h_scalars_kernel, dim3(grid_for(N, 256)), dim3(256), 0, stream_, sh.get(), lagCoset.get(), N, words_of(p.hScale));
             UG_KERNEL_CHECK();
             sc.stop();
         }
@@ -450,10 +450,10 @@ public:
             StreamTimer::Scope sc = timer_.time(stream_, &sinks[2]);
             Table t;
             buildTable(t, false, env_window("UG_SETUP_WINDOW_G1", WINDOW_G1));
-            mulSet(t, sa.p, M, idx.p, count.p, true, oa.p);
-            mulSet(t, sk.p, M, idx.p, count.p, true, ok.p);
-            mulSet(t, sh.p, N, idx.p, count.p, true, oh.p);
-            mulSet(t, sb.p, M, idxB.p, countB.p, true, ob1.p, ob2.p);
+            mulSet(t, sa.get(), M, idx.get(), count.get(), true, oa.get());
+            mulSet(t, sk.get(), M, idx.get(), count.get(), true, ok.get());
+            mulSet(t, sh.get(), N, idx.get(), count.get(), true, oh.get());
+            mulSet(t, sb.get(), M, idxB.get(), countB.get(), true, ob1.get(), ob2.get());
             sc.stop();
             UG_HIP(hipStreamSynchronize(stream_));      // (the table is freed when t goes)
         }
@@ -461,18 +461,18 @@ public:
             StreamTimer::Scope sc = timer_.time(stream_, &sinks[3]);
             Table t;
             buildTable(t, true, env_window("UG_SETUP_WINDOW_G2", WINDOW_G2));
-            mulSet(t, sb.p, M, idxB.p, countB.p, false, ob2.p);
+            mulSet(t, sb.get(), M, idxB.get(), countB.get(), false, ob2.get());
             sc.stop();
             UG_HIP(hipStreamSynchronize(stream_));
         }
         timer_.resolve();
         for (int i = 0; i < 4; i++) ms[1 + i] += sinks[i].ms;
         t0 = nowMs();
-        UG_HIP(hipMemcpyAsync(a, oa.p, M * 64, hipMemcpyDeviceToHost, stream_));
-        UG_HIP(hipMemcpyAsync(b1, ob1.p, M * 64, hipMemcpyDeviceToHost, stream_));
-        UG_HIP(hipMemcpyAsync(b2, ob2.p, M * 128, hipMemcpyDeviceToHost, stream_));
-        UG_HIP(hipMemcpyAsync(k, ok.p, M * 64, hipMemcpyDeviceToHost, stream_));
-        UG_HIP(hipMemcpyAsync(h, oh.p, N * 64, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(a, oa.get(), M * 64, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(b1, ob1.get(), M * 64, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(b2, ob2.get(), M * 128, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(k, ok.get(), M * 64, hipMemcpyDeviceToHost, stream_));
+        UG_HIP(hipMemcpyAsync(h, oh.get(), N * 64, hipMemcpyDeviceToHost, stream_));
         UG_HIP(hipStreamSynchronize(stream_));
         ms[5] += nowMs() - t0;
     }
@@ -495,16 +495,16 @@ private:
         u32 gen[32];
         generatorWords(g2, gen);
         DevBuf<u32> dGen(words);
-        UG_HIP(hipMemcpyAsync(dGen.p, gen, words * 4, hipMemcpyHostToDevice, stream_));
+        UG_HIP(hipMemcpyAsync(dGen.get(), gen, words * 4, hipMemcpyHostToDevice, stream_));
         const u64 rest = (u64)t.tables * (t.half - 1);
         if (g2) {
-            hipLaunchKernelGGL(gen_table_bases_kernel<S2>, dim3(1), dim3(64), 0, stream_, t.rec.p, dGen.p, c, t.tables, t.half);
+            hipLaunchKernelGGL(gen_table_bases_kernel<S2>, dim3(1), dim3(64), 0, stream_, t.rec.get(), dGen.get(), c, t.tables, t.half);
             UG_KERNEL_CHECK();
-            hipLaunchKernelGGL(gen_table_fill_kernel<S2>, dim3(grid_for(rest, 128)), dim3(128), 0, stream_, t.rec.p, t.tables, t.half);
+            hipLaunchKernelGGL(gen_table_fill_kernel<S2>, dim3(grid_for(rest, 128)), dim3(128), 0, stream_, t.rec.get(), t.tables, t.half);
         } else {
-            hipLaunchKernelGGL(gen_table_bases_kernel<S1>, dim3(1), dim3(64), 0, stream_, t.rec.p, dGen.p, c, t.tables, t.half);
+            hipLaunchKernelGGL(gen_table_bases_kernel<S1>, dim3(1), dim3(64), 0, stream_, t.rec.get(), dGen.get(), c, t.tables, t.half);
             UG_KERNEL_CHECK();
-            hipLaunchKernelGGL(gen_table_fill_kernel<S1>, dim3(grid_for(rest, 128)), dim3(128), 0, stream_, t.rec.p, t.tables, t.half);
+            hipLaunchKernelGGL(gen_table_fill_kernel<S1>, dim3(grid_for(rest, 128)), dim3(128), 0, stream_, t.rec.get(), t.tables, t.half);
         }
         UG_KERNEL_CHECK();
         UG_HIP(hipStreamSynchronize(stream_));          // (dGen goes here)
@@ -520,10 +520,10 @@ private:
         }
         if (t.g2) {
             hipLaunchKernelGGL(gen_mul_kernel<S2>, dim3(grid_for((n + S2::KPL - 1) / S2::KPL, S2::BLOCK)), dim3(S2::BLOCK), 0, stream_, scalars, idx, count, n,
-                               t.rec.p, t.c, t.tables, t.half, out);
+                               t.rec.get(), t.c, t.tables, t.half, out);
         } else {
             hipLaunchKernelGGL(gen_mul_kernel<S1>, dim3(grid_for((n + S1::KPL - 1) / S1::KPL, S1::BLOCK)), dim3(S1::BLOCK), 0, stream_, scalars, idx, count, n,
-                               t.rec.p, t.c, t.tables, t.half, out);
+                               t.rec.get(), t.c, t.tables, t.half, out);
         }
         UG_KERNEL_CHECK();
     }

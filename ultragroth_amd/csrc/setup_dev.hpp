@@ -1,6 +1,6 @@
 // setup_dev.hpp -- what the two device translation units of the setups share (setup.hip: the development setup; setup_points.hip:
 // the point combinations of the phase-2 setup): compile-time loops, the curve configurations, the all-zero record, the per-lane
-// double-and-add walk (ptau_prepare.hip's butterflies use it too), an owned device buffer.
+// double-and-add walk (ptau_prepare.hip's butterflies use it too).
 #pragma once
 #include "dev_common.hpp"
 
@@ -93,18 +93,6 @@ template <class F> __device__ __forceinline__ XYZZ<F> walk_product(u32 (&s)[8], 
     }
     return acc;
 }
-
-// ---- host side ----
-template <class T> struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    explicit DevBuf(u64 n) { alloc(n); }
-    void alloc(u64 n) { release(); if (n) UG_HIP(hipMalloc((void**)&p, n * sizeof(T))); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    ~DevBuf() { release(); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-};
 
 }  // namespace sdev
 }  // namespace ug

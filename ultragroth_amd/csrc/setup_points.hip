@@ -311,7 +311,7 @@ void classify(u64 terms, const u32* index, const uint8_t* coefs, Classes& c) {
 
 template <class T> void upload(DevBuf<T>& d, const T* src, u64 n, hipStream_t stream) {
     d.alloc(n);
-    if (n) UG_HIP(hipMemcpyAsync(d.p, src, n * sizeof(T), hipMemcpyHostToDevice, stream));
+    if (n) UG_HIP(hipMemcpyAsync(d.get(), src, n * sizeof(T), hipMemcpyHostToDevice, stream));
 }
 
 template <class Cfg>
@@ -336,20 +336,20 @@ void combine_on_device(hipStream_t stream, StreamTimer& timer, u64 nCols, const 
     upload(dPieces, pieces.data(), (u64)pieces.size(), stream);
     DevBuf<u32> dPts(std::max<u64>(pts.total(), 1) * Cfg::AFF_WORDS);
     for (int s = 0; s < pts.n; s++)
-        if (pts.count) UG_HIP(hipMemcpyAsync(dPts.p + (u64)s * pts.count * Cfg::AFF_WORDS, pts.base[s], pts.count * REC, hipMemcpyHostToDevice, stream));
-    if (std::is_same<typename Cfg::F, Fq2>::value) convert_points_g2(dPts.p, pts.total(), stream);
-    else convert_points_g1(dPts.p, pts.total(), stream);
+        if (pts.count) UG_HIP(hipMemcpyAsync(dPts.get() + (u64)s * pts.count * Cfg::AFF_WORDS, pts.base[s], pts.count * REC, hipMemcpyHostToDevice, stream));
+    if (std::is_same<typename Cfg::F, Fq2>::value) convert_points_g2(dPts.get(), pts.total(), stream);
+    else convert_points_g1(dPts.get(), pts.total(), stream);
     DevBuf<u32> dProd((u64)cls.slots * 2 * Cfg::AFF_WORDS), dPartial((u64)pieces.size() * 2 * Cfg::AFF_WORDS), dOut(nCols * Cfg::AFF_WORDS);
 
     ColArgs a;
-    a.col_ptr = dColPtr.p; a.index = dIndex.p; a.code = dCode.p; a.pts = dPts.p; a.prod = dProd.p; a.partial = dPartial.p;
-    a.pieces = dPieces.p; a.n_cols = (u32)nCols; a.n_pieces = (u32)pieces.size();
+    a.col_ptr = dColPtr.get(); a.index = dIndex.get(); a.code = dCode.get(); a.pts = dPts.get(); a.prod = dProd.get(); a.partial = dPartial.get();
+    a.pieces = dPieces.get(); a.n_cols = (u32)nCols; a.n_pieces = (u32)pieces.size();
     TimeSink products, sums;
     {
         StreamTimer::Scope sc = timer.time(stream, &products);
         if (cls.slots) {
-            hipLaunchKernelGGL(term_products_kernel<Cfg>, dim3(grid_for(cls.slots, Cfg::BLOCK)), dim3(Cfg::BLOCK), 0, stream, dPts.p, dSlotIndex.p,
-                               dSlotCoef.p, cls.slots, dProd.p);
+            hipLaunchKernelGGL(term_products_kernel<Cfg>, dim3(grid_for(cls.slots, Cfg::BLOCK)), dim3(Cfg::BLOCK), 0, stream, dPts.get(), dSlotIndex.get(),
+                               dSlotCoef.get(), cls.slots, dProd.get());
             UG_KERNEL_CHECK();
         }
         sc.stop();
@@ -357,14 +357,14 @@ void combine_on_device(hipStream_t stream, StreamTimer& timer, u64 nCols, const 
     {
         StreamTimer::Scope sc = timer.time(stream, &sums);
         if (!pieces.empty()) {
-            hipLaunchKernelGGL(piece_points_kernel<Cfg>, dim3((unsigned)pieces.size()), dim3(Cfg::PIECE_BLOCK), 0, stream, a, dPartial.p);
+            hipLaunchKernelGGL(piece_points_kernel<Cfg>, dim3((unsigned)pieces.size()), dim3(Cfg::PIECE_BLOCK), 0, stream, a, dPartial.get());
             UG_KERNEL_CHECK();
         }
-        hipLaunchKernelGGL(column_points_kernel<Cfg>, dim3(grid_for((nCols + Cfg::KPL - 1) / Cfg::KPL, Cfg::BLOCK)), dim3(Cfg::BLOCK), 0, stream, a, dOut.p);
+        hipLaunchKernelGGL(column_points_kernel<Cfg>, dim3(grid_for((nCols + Cfg::KPL - 1) / Cfg::KPL, Cfg::BLOCK)), dim3(Cfg::BLOCK), 0, stream, a, dOut.get());
         UG_KERNEL_CHECK();
         sc.stop();
     }
-    UG_HIP(hipMemcpyAsync(out, dOut.p, nCols * REC, hipMemcpyDeviceToHost, stream));
+    UG_HIP(hipMemcpyAsync(out, dOut.get(), nCols * REC, hipMemcpyDeviceToHost, stream));
     UG_HIP(hipStreamSynchronize(stream));
     timer.resolve();
     if (ms) { ms[0] = products.ms; ms[1] = sums.ms; }
@@ -389,16 +389,16 @@ void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* 
     WnafArgs a;
     a.top = recodeWnaf(scalar, SCALE_WINDOW, a.digit);
     DevBuf<u32> dPts(n * 16), dOut(n * 16);
-    UG_HIP(hipMemcpyAsync(dPts.p, points, n * 64, hipMemcpyHostToDevice, stream));
-    convert_points_g1(dPts.p, n, stream);
+    UG_HIP(hipMemcpyAsync(dPts.get(), points, n * 64, hipMemcpyHostToDevice, stream));
+    convert_points_g1(dPts.get(), n, stream);
     TimeSink sink;
     {
         StreamTimer::Scope sc = timer.time(stream, &sink);
-        hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, 128)), dim3(128), 0, stream, dPts.p, n, a, dOut.p);
+        hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, 128)), dim3(128), 0, stream, dPts.get(), n, a, dOut.get());
         UG_KERNEL_CHECK();
         sc.stop();
     }
-    UG_HIP(hipMemcpyAsync(out, dOut.p, n * 64, hipMemcpyDeviceToHost, stream));
+    UG_HIP(hipMemcpyAsync(out, dOut.get(), n * 64, hipMemcpyDeviceToHost, stream));
     UG_HIP(hipStreamSynchronize(stream));
     timer.resolve();
     volatile int8_t* w = a.digit;                // (the digits are 1 / delta)
@@ -432,16 +432,16 @@ void device_points_scale_segments(hipStream_t stream, StreamTimer& timer, const 
         if (same >= 0) a.seg[s].src = a.seg[same].src;
         else {
             dSrc[s].alloc(std::max<u64>(g.nSrc, 1) * 16);
-            if (g.nSrc) UG_HIP(hipMemcpyAsync(dSrc[s].p, g.src, g.nSrc * 64, hipMemcpyHostToDevice, stream));
-            convert_points_g1(dSrc[s].p, g.nSrc, stream);
-            a.seg[s].src = dSrc[s].p;
+            if (g.nSrc) UG_HIP(hipMemcpyAsync(dSrc[s].get(), g.src, g.nSrc * 64, hipMemcpyHostToDevice, stream));
+            convert_points_g1(dSrc[s].get(), g.nSrc, stream);
+            a.seg[s].src = dSrc[s].get();
         }
         if (g.index) {
             upload(dIndex[s], g.index, g.count, stream);
-            a.seg[s].index = dIndex[s].p;
+            a.seg[s].index = dIndex[s].get();
         }
         dOut[s].alloc(g.count * 16);
-        a.seg[s].out = dOut[s].p;
+        a.seg[s].out = dOut[s].get();
     }
     TimeSink sink;
     if (blocks) {
@@ -451,7 +451,7 @@ void device_points_scale_segments(hipStream_t stream, StreamTimer& timer, const 
         sc.stop();
     }
     for (int s = 0; s < n; s++)
-        if (segs[s].count) UG_HIP(hipMemcpyAsync(segs[s].out, dOut[s].p, segs[s].count * 64, hipMemcpyDeviceToHost, stream));
+        if (segs[s].count) UG_HIP(hipMemcpyAsync(segs[s].out, dOut[s].get(), segs[s].count * 64, hipMemcpyDeviceToHost, stream));
     UG_HIP(hipStreamSynchronize(stream));
     timer.resolve();
     volatile int8_t* w = &a.digit[0][0];         // (the digits are 1 / delta)

@@ -389,16 +389,15 @@ void RadixSorter::reserve(u64 n_pairs, int ipt_min) {
     // (later passes move the pair count rounded up to the FIRST pass's tile, at most SORT_THREADS * 16 - 1 = 8 191 pairs more, in tiles of their own)
     const u64 tiles = (n_pairs + (u64)SORT_THREADS * SORT_MAX_IPT) / ((u64)SORT_THREADS * (u64)(ipt_min < 1 ? 1 : ipt_min)) + 2;
     if (tiles > tiles_cap) {
-        epoch_alloc(lookback, (size_t)tiles * SORT_MAX_BINS * 4);
+        epoch_alloc(lookback, (size_t)tiles * SORT_MAX_BINS);
         tiles_cap = tiles;
     }
-    if (!small) epoch_alloc(small, (4 * SORT_MAX_BINS + 16) * 4);
+    if (!small.get()) epoch_alloc(small, 4 * SORT_MAX_BINS + 16);
 }
 void RadixSorter::release() {
-    if (lookback || small) alloc_epoch_bump();
-    if (lookback) hipFree(lookback);
-    if (small) hipFree(small);
-    lookback = small = nullptr; tiles_cap = 0;
+    if (lookback.get() || small.get()) alloc_epoch_bump();
+    lookback.release(); small.release();
+    tiles_cap = 0;
 }
 
 // Sorts the schedule's pairs by key. scalars != nullptr and windows <= 16: the pairs are made from the scalars inside the
@@ -435,9 +434,9 @@ int RadixSorter::sort(const u32* scalars, const MsmGeometry& geo, u32 sentinel, 
     if (fused) { spl = env_spl < 1 ? 1 : env_spl; while (spl > 1 && spl * windows > SORT_MAX_IPT) spl--; }
     const int ipt_first = fused ? windows * spl : ipt_pairs;
     reserve(n_pairs, fused ? std::min(windows * spl, ipt_pairs) : ipt_pairs);
-    u32* hist = small;                         // passes x 256
-    u32* counters = small + 4 * SORT_MAX_BINS; // one tile counter per pass
-    UG_HIP(hipMemsetAsync(small, 0, (4 * SORT_MAX_BINS + 16) * 4, stream));
+    u32* hist = small.get();                       // passes x 256
+    u32* counters = hist + 4 * SORT_MAX_BINS; // one tile counter per pass
+    UG_HIP(hipMemsetAsync(hist, 0, (4 * SORT_MAX_BINS + 16) * 4, stream));
     // padded pair count: whole tiles of the FIRST pass (later passes see the same pairs: their last tile is padded on the fly)
     const u64 T0 = (u64)SORT_THREADS * (u64)ipt_first;
     const u64 tiles0 = (n_pairs + T0 - 1) / T0;
@@ -483,12 +482,12 @@ int RadixSorter::sort(const u32* scalars, const MsmGeometry& geo, u32 sentinel, 
         a.shift = shift[p]; a.bins_log = bins_log[p];
         a.bin_base = hist + p * SORT_MAX_BINS;
         a.n_valid = drop ? n_valid_out : nullptr; a.drop = drop ? 1 : 0;
-        a.lookback = lookback; a.tile_counter = counters + p; a.error_flag = error_flag;
+        a.lookback = lookback.get(); a.tile_counter = counters + p; a.error_flag = error_flag;
         const u64 T = (u64)SORT_THREADS * (u64)a.ipt;
         const u64 tiles = (moved + T - 1) / T;
         a.n_tiles = (u32)tiles;
         if (tiles > tiles_cap) throw std::logic_error("radix sort: look-back table too small");
-        UG_HIP(hipMemsetAsync(lookback, 0, (size_t)tiles * ((size_t)1 << bins_log[p]) * 4, stream));
+        UG_HIP(hipMemsetAsync(lookback.get(), 0, (size_t)tiles * ((size_t)1 << bins_log[p]) * 4, stream));
         const size_t lds = (2 * T + SORT_WAVES * SORT_MAX_BINS + 2 * SORT_MAX_BINS + 16) * 4;
         const unsigned grid = (unsigned)std::min<u64>(tiles, SORT_MAX_GRID);
         // the fused first pass with the window width as a compile-time constant where the provers' sizes use it

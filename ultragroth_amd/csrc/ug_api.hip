@@ -42,7 +42,7 @@ struct StagedUploader {
     static constexpr size_t CHUNK = (size_t)8 << 20;
     static constexpr int MAX_LANES = 8, DEPTH = 2;
     static constexpr size_t MIN_BYTES = (size_t)32 << 20;      // below this a plain copy is as fast
-    struct Lane { hipStream_t stream = nullptr; uint8_t* buf[DEPTH] = {nullptr, nullptr}; hipEvent_t done[DEPTH] = {nullptr, nullptr}; };
+    struct Lane { hipStream_t stream = nullptr; PinnedBuf<uint8_t> buf[DEPTH]; Event done[DEPTH]; };
     Lane lanes[MAX_LANES];
     int n_lanes = 0;
     std::mutex turn;            // one upload at a time: the lanes' pinned buffers are the uploader's (a witness staged for the
@@ -67,8 +67,8 @@ struct StagedUploader {
             const int prio = (pe && pe[0] == 'h') ? greatest : (pe && pe[0] == 'n') ? 0 : least;
             UG_HIP(hipStreamCreateWithPriority(&lanes[l].stream, hipStreamNonBlocking, prio));
             for (int d = 0; d < DEPTH; d++) {
-                UG_HIP(hipHostMalloc((void**)&lanes[l].buf[d], CHUNK, hipHostMallocDefault));
-                UG_HIP(hipEventCreateWithFlags(&lanes[l].done[d], hipEventDisableTiming));
+                lanes[l].buf[d].alloc(CHUNK);
+                lanes[l].done[d] = Event(false);
             }
             n_lanes = l + 1;
         }
@@ -85,11 +85,11 @@ struct StagedUploader {
                 size_t turn = 0;
                 for (size_t c = (size_t)l; c < n_chunks; c += (size_t)n_lanes, turn++) {
                     const int d = (int)(turn % DEPTH);
-                    if (turn >= DEPTH) UG_HIP(hipEventSynchronize(ln.done[d]));      // the DMA out of this buffer has finished
+                    if (turn >= DEPTH) UG_HIP(hipEventSynchronize(ln.done[d].e));      // the DMA out of this buffer has finished
                     const size_t off = c * CHUNK, len = bytes - off < CHUNK ? bytes - off : CHUNK;
-                    memcpy(ln.buf[d], static_cast<const uint8_t*>(src) + off, len);
-                    UG_HIP(hipMemcpyAsync(static_cast<uint8_t*>(dst) + off, ln.buf[d], len, hipMemcpyHostToDevice, ln.stream));
-                    UG_HIP(hipEventRecord(ln.done[d], ln.stream));
+                    memcpy(ln.buf[d].get(), static_cast<const uint8_t*>(src) + off, len);
+                    UG_HIP(hipMemcpyAsync(static_cast<uint8_t*>(dst) + off, ln.buf[d].get(), len, hipMemcpyHostToDevice, ln.stream));
+                    UG_HIP(hipEventRecord(ln.done[d].e, ln.stream));
                     if (after) after(off, len, ln.stream);
                 }
                 UG_HIP(hipStreamSynchronize(ln.stream));
@@ -103,9 +103,8 @@ struct StagedUploader {
     }
     void release() {
         for (int l = 0; l < n_lanes; l++) {
-            for (int d = 0; d < DEPTH; d++) { if (lanes[l].buf[d]) hipHostFree(lanes[l].buf[d]); if (lanes[l].done[d]) hipEventDestroy(lanes[l].done[d]); }
             if (lanes[l].stream) hipStreamDestroy(lanes[l].stream);
-            lanes[l] = Lane();
+            lanes[l] = Lane();                  // (its pinned buffers and events go here)
         }
         n_lanes = 0;
     }
@@ -135,33 +134,31 @@ struct ug_ctx {
     bool defer_tables = false;             // ug_ctx_defer_tables: sets are created with room for their window tables, which are
                                            // then built piece by piece (ug_bases_tables_step)
     int check_level = 0;                   // ug_ctx_check_points: the sets created on this context check their records (check.hip)
-    unsigned long long* check_word = nullptr;   // ... the fault word of the check in flight (device memory) and the stream it is
+    DevBuf<unsigned long long> check_word;      // ... the fault word of the check in flight (device memory) and the stream it is
     hipStream_t check_stream = nullptr;         //     armed and read on: the context's own may hold the previous set's table build
     ug_point_fault last_fault = {0, UG_POINT_OK};   // what the last creation on this context found (ug_ctx_last_point_fault) ...
     int last_fault_member = -1;                      // ... and in which member of a group (-1: a plain set)
     ug_graph* recording = nullptr;         // the stream is being captured into this graph (ug_graph_begin .. ug_graph_end)
     std::vector<ug_graph*> launched;       // graphs launched on this stream whose event pairs are not accounted yet (resolve_timer)
     NttPlan raw_ntt;                       // cache for ug_fr_ntt
-    u32* lookup_last = nullptr; u64 lookup_last_n = 0;   // zeroed scratch of ug_dvec_apply_lookup
-    u32* lookup_stage = nullptr; size_t lookup_stage_bytes = 0;   // staging of the lookup calls (kept: two allocations and
+    DevBuf<u32> lookup_last; u64 lookup_last_n = 0;      // zeroed scratch of ug_dvec_apply_lookup
+    DevBuf<u32> lookup_stage; size_t lookup_stage_bytes = 0;      // staging of the lookup calls (kept: two allocations and
                                                                   // two frees -- each a device-wide wait -- per proof otherwise)
     u32* stage_for_lookup(size_t bytes) {
         if (bytes > lookup_stage_bytes) {
-            if (lookup_stage) hipFree(lookup_stage);
-            lookup_stage = nullptr; lookup_stage_bytes = 0;
-            UG_HIP(hipMalloc(&lookup_stage, bytes));
+            lookup_stage_bytes = 0;
+            lookup_stage.alloc((bytes + 3) / 4);
             lookup_stage_bytes = bytes;
         }
-        return lookup_stage;
+        return lookup_stage.get();
     }
-    u32* pinned_results = nullptr;         // MSM_QUEUE_DEPTH result blocks of MSM_PENDING_WORDS words: the queued products' (pending_msm)
-    std::vector<void*> deferred_free;      // staging memory of queued set-up work: hipFree waits for the whole device, so it is
+    PinnedBuf<u32> pinned_results;         // MSM_QUEUE_DEPTH result blocks of MSM_PENDING_WORDS words: the queued products' (pending_msm)
+    std::vector<DevBuf<u32>> deferred_free;      // staging memory of queued set-up work: hipFree waits for the whole device, so it is
                                            // freed the next time the stream is idle anyway (ug_ctx_sync, destroy)
-    void free_deferred() { for (void* p : deferred_free) hipFree(p); deferred_free.clear(); }
     void use() const { UG_HIP(hipSetDevice(device)); }
 };
 struct ug_bases {
-    ug_ctx* ctx; bool g2; u64 n; u64 global_first; u32* pts;
+    ug_ctx* ctx; bool g2; u64 n; u64 global_first; DevBuf<u32> pts = {};
     int table_c = 0;          // window width of the precomputed tables (0: none, pts holds the n points only)
     int table_stride = 1;     // ... and their stride: table j = 2^(stride c j) P (MsmGeometry::stride)
     int members = 1;          // > 1: a group -- n = slots * members records, record slot * members + m is member m's point of
@@ -174,10 +171,12 @@ struct ug_bases {
     bool tables_usable() const { return !table_c || tables_built >= n; }
 };
 struct ug_dvec {
-    ug_ctx* ctx; u64 n; u32* data; bool owns;
+    ug_ctx* ctx; u64 n; DevBuf<u32> data; bool owns = true;      // owns == false (ug_dvec_wrap): data is the caller's memory
+    ug_dvec(ug_ctx* c, u64 n_) : ctx(c), n(n_) {}
+    ~ug_dvec() { if (!owns) (void)data.take(); }
 };
 struct ug_index {
-    ug_ctx* ctx; u64 n; u32* data;
+    ug_ctx* ctx; u64 n; DevBuf<u32> data = {};
 };
 struct ug_schedule {
     ug_ctx* ctx; MsmSchedule sched; u64 first = 0;
@@ -194,7 +193,7 @@ struct ug_schedule {
 };
 struct ug_hpoly {
     ug_ctx* ctx; CoefMatrix mat; NttPlan ntt; u32 domain = 0, nvars = 0;
-    u32 *a = nullptr, *b = nullptr, *c = nullptr, *t = nullptr, *t2 = nullptr;     // group * domain elements each: vector g of a launch
+    DevBuf<u32> a, b, c, t, t2;                                                    // group * domain elements each: vector g of a launch
                                                                                    // group works on [g * domain, (g + 1) * domain)
     int group = 1;            // vectors side by side that the workspaces hold (ug_hpoly_reserve_vectors)
     int last_group = 0;       // largest launch group of the last ug_hpoly_run_vectors call (0: none yet)
@@ -208,18 +207,18 @@ struct ug_r1cs {
     ug_ctx* ctx = nullptr;
     ughost::R1csHeader hdr;
     u64 terms[3] = {0, 0, 0};
-    u32 *row_ptr[3] = {nullptr, nullptr, nullptr}, *sig[3] = {nullptr, nullptr, nullptr}, *val[3] = {nullptr, nullptr, nullptr};
-    unsigned long long* words = nullptr;        // device: 2 per slot, then the word of the probe (ug_r1cs_match_hpoly)
-    unsigned long long* words_host = nullptr;   // pinned: the same
-    u32* row_values = nullptr;                  // device: A.w, B.w, C.w of one constraint (24 words) ...
-    u32* row_values_host = nullptr;             // ... and pinned
-    hipEvent_t done[SLOTS] = {};
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    DevBuf<u32> row_ptr[3], sig[3], val[3];
+    DevBuf<unsigned long long> words;           // device: 2 per slot, then the word of the probe (ug_r1cs_match_hpoly)
+    PinnedBuf<unsigned long long> words_host;   // pinned: the same
+    DevBuf<u32> row_values;                     // device: A.w, B.w, C.w of one constraint (24 words) ...
+    PinnedBuf<u32> row_values_host;             // ... and pinned
+    Event done[SLOTS];
+    Event t0, t1;
     struct Queued { const u32* wtns = nullptr; hipStream_t stream = nullptr; bool on = false; } queued[SLOTS];
     R1csDev dev() const {
         R1csDev d;
         d.rows = hdr.nConstraints;
-        for (int t = 0; t < 3; t++) { d.row_ptr[t] = row_ptr[t]; d.sig[t] = sig[t]; d.val[t] = val[t]; }
+        for (int t = 0; t < 3; t++) { d.row_ptr[t] = row_ptr[t].get(); d.sig[t] = sig[t].get(); d.val[t] = val[t].get(); }
         return d;
     }
 };
@@ -263,14 +262,14 @@ void host_to_device(ug_ctx* c, void* dst, const void* src, size_t bytes, const S
 // all ones = clean; returns when the word is set (the upload lanes' kernels that follow run on other streams)
 void check_arm(ug_ctx* c) {
     if (!c->check_stream) UG_HIP(hipStreamCreateWithFlags(&c->check_stream, hipStreamNonBlocking));
-    if (!c->check_word) UG_HIP(hipMalloc(&c->check_word, 8));
-    UG_HIP(hipMemsetAsync(c->check_word, 0xff, 8, c->check_stream));
+    if (!c->check_word.get()) c->check_word.alloc(1);
+    UG_HIP(hipMemsetAsync(c->check_word.get(), 0xff, 8, c->check_stream));
     UG_HIP(hipStreamSynchronize(c->check_stream));
 }
 // after every kernel that may have written the word has completed
 ug_point_fault check_read(ug_ctx* c) {
     unsigned long long w = 0;
-    UG_HIP(hipMemcpyAsync(&w, c->check_word, 8, hipMemcpyDeviceToHost, c->check_stream));
+    UG_HIP(hipMemcpyAsync(&w, c->check_word.get(), 8, hipMemcpyDeviceToHost, c->check_stream));
     UG_HIP(hipStreamSynchronize(c->check_stream));
     ug_point_fault f;
     f.index = w == ~0ull ? 0 : (uint64_t)(w >> 2);
@@ -278,9 +277,9 @@ ug_point_fault check_read(ug_ctx* c) {
     return f;
 }
 void check_release(ug_ctx* c) {
-    if (c->check_word) hipFree(c->check_word);
+    c->check_word.release();
     if (c->check_stream) hipStreamDestroy(c->check_stream);
-    c->check_word = nullptr; c->check_stream = nullptr;
+    c->check_stream = nullptr;
 }
 // Test hook (ug_test_inject_fault): the `after`-th next pass through fault point `site` throws. Only in processes started
 // with ULTRAGROTH_TEST_HOOKS=1 (the same gate as the blinding hook); otherwise fault_point() is one relaxed load.
@@ -313,7 +312,7 @@ void resolve_timer(ug_ctx* c) {
 void sync_and_resolve(ug_ctx* c) {
     UG_HIP(hipStreamSynchronize(c->stream));
     resolve_timer(c);
-    c->free_deferred();
+    c->deferred_free.clear();
 }
 // The product queue of a context: ug_ctx::pending_msm, slot k of which owns block k of ug_ctx::pinned_results. An enqueue call
 // takes its slots at the end of the queue through this object, which gives them back unless commit() is reached: nothing of a
@@ -330,7 +329,7 @@ struct QueueSlots {
     // the next slot, for a product whose records go to `out`: its pinned result block
     u32* add(void* out, bool g2) {
         c->pending_msm.push_back(ug_ctx::QueuedMsm{MsmPending(), out, g2});
-        return c->pinned_results + (c->pending_msm.size() - 1) * MSM_PENDING_WORDS;
+        return c->pinned_results.get() + (c->pending_msm.size() - 1) * MSM_PENDING_WORDS;
     }
     // pend[k]: what msm_enqueue said about the k-th slot added
     void commit(const MsmPending* pend) {
@@ -344,7 +343,7 @@ int64_t schedule_delta(const ug_schedule* s, const ug_bases* b, int64_t index_sh
 MsmCall group_call(QueueSlots& slots, const ug_bases* group, const ug_schedule* s, void* const* outs) {
     MsmCall call;
     call.count = call.group = group->members;
-    call.products[0] = {group->pts, group->slots, schedule_delta(s, group), nullptr};
+    call.products[0] = {group->pts.get(), group->slots, schedule_delta(s, group), nullptr};
     for (int m = 0; m < call.count; m++) call.products[m].host = slots.add(outs[m], false);
     return call;
 }
@@ -380,7 +379,7 @@ int ug_ctx_create_priority(ug_ctx** out, int device, int priority_class) {
     } else {
         UG_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     }
-    UG_HIP(hipHostMalloc((void**)&c->pinned_results, (size_t)MSM_QUEUE_DEPTH * MSM_PENDING_WORDS * 4, hipHostMallocDefault));
+    c->pinned_results.alloc((size_t)MSM_QUEUE_DEPTH * MSM_PENDING_WORDS);
     *out = hold.release();
     UG_CATCH
 }
@@ -388,15 +387,11 @@ void ug_ctx_destroy(ug_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    c->free_deferred();
-    c->ws_g1.release(); c->ws_g2.release(); c->raw_ntt.release(); c->uploader.release();
-    if (c->lookup_last) hipFree(c->lookup_last);
-    if (c->lookup_stage) hipFree(c->lookup_stage);
+    c->uploader.release();
     check_release(c);
     if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
-    if (c->pinned_results) hipHostFree(c->pinned_results);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;                                   // (with the events of the timer and of the context)
+    delete c;                                   // (with its device and pinned memory -- the workspaces move the epoch -- and its events)
 }
 int ug_ctx_sync(ug_ctx* c) {
     UG_TRY
@@ -439,37 +434,33 @@ static int bases_create(ug_ctx* c, const void* host, u64 n, u64 global_first, bo
         windows = MsmGeometry::table_count(table_c, MsmGeometry::choose_tables(n, table_c, stride).stride);      // validates width and stride
         if (n > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("window tables need at most 2^27 points per set");
     }
-    ug_bases* b = new ug_bases{c, g2, n, global_first, nullptr, 0};
+    std::unique_ptr<ug_bases> hold(new ug_bases{c, g2, n, global_first});
+    ug_bases* b = hold.get();
     const size_t rec = g2 ? 128 : 64, bytes = (size_t)n * rec;
     b->empty = n != 0 && host_all_zero(host, bytes);          // (stops at the first point that is not infinity: the first record, normally)
     const bool defer = table_c && c->defer_tables;            // the room for the tables comes later too (ug_bases_tables_alloc / _adopt):
     if (defer) windows = 1;                                   // a first allocation of tens of GiB can take a second by itself
-    if (hipMalloc(&b->pts, bytes ? bytes * (size_t)windows : 4) != hipSuccess) {
-        (void)hipGetLastError();
-        delete b;
+    if (!b->pts.try_alloc(bytes / 4 * (size_t)windows))
         throw std::runtime_error(table_c ? "not enough device memory for the window tables" : "not enough device memory for the base points");
-    }
     if (n) {
         // each chunk's records are converted to the device form behind its own DMA (chunks are whole records: 8 MiB / 128)
-        u32* pts = b->pts;
-        try {
-            const int level = c->check_level;                  // (0: exactly the path without the check)
-            unsigned long long* word = nullptr;
-            if (level) { check_arm(c); word = c->check_word; }
-            host_to_device(c, pts, host, bytes, [pts, rec, g2, level, word, global_first](size_t off, size_t len, hipStream_t st) {
-                u32* p = pts + off / 4;
-                if (level) check_points(g2, p, len / rec, global_first + off / rec, level, word, st);      // the raw records, before they are reduced
-                if (g2) convert_points_g2(p, len / rec, st); else convert_points_g1(p, len / rec, st);
-            }, /*fresh*/ true);
-            if (level) {                                       // (the upload has waited for every chunk: one read, and no table build for a bad set)
-                const ug_point_fault f = check_read(c);
-                if (f.reason != UG_POINT_OK) throw_point_fault(c, -1, f);
-            }
-            if (table_c && !defer) build_window_tables(g2, pts, n, table_c * stride, windows, c->stream);
-        } catch (...) { hipFree(b->pts); delete b; throw; }
+        u32* pts = b->pts.get();
+        const int level = c->check_level;                  // (0: exactly the path without the check)
+        unsigned long long* word = nullptr;
+        if (level) { check_arm(c); word = c->check_word.get(); }
+        host_to_device(c, pts, host, bytes, [pts, rec, g2, level, word, global_first](size_t off, size_t len, hipStream_t st) {
+            u32* p = pts + off / 4;
+            if (level) check_points(g2, p, len / rec, global_first + off / rec, level, word, st);      // the raw records, before they are reduced
+            if (g2) convert_points_g2(p, len / rec, st); else convert_points_g1(p, len / rec, st);
+        }, /*fresh*/ true);
+        if (level) {                                       // (the upload has waited for every chunk: one read, and no table build for a bad set)
+            const ug_point_fault f = check_read(c);
+            if (f.reason != UG_POINT_OK) throw_point_fault(c, -1, f);
+        }
+        if (table_c && !defer) build_window_tables(g2, pts, n, table_c * stride, windows, c->stream);
     }
     if (defer) { b->deferred_c = table_c; b->deferred_stride = stride; } else if (table_c) { b->table_c = table_c; b->table_stride = stride; }
-    *out = b;
+    *out = hold.release();
     UG_CATCH
 }
 int ug_bases_create_g1(ug_ctx* c, const void* host, uint64_t n, uint64_t gf, ug_bases** out) { return bases_create(c, host, n, gf, false, 0, 1, out); }
@@ -491,17 +482,12 @@ int ug_bases_create_every_g1(ug_ctx* c, const void* host, uint64_t n_records, ui
     std::unique_ptr<ug_bases, void (*)(ug_bases*)> hold(all, ug_bases_destroy);
     UG_TRY
     const u64 count = (n_records - first + step - 1) / step;
-    std::unique_ptr<ug_bases> b(new ug_bases{c, false, count, gf, nullptr, 0});
+    std::unique_ptr<ug_bases> b(new ug_bases{c, false, count, gf});
     b->empty = true;
     for (u64 i = 0; i < count && b->empty; i++) b->empty = host_all_zero(static_cast<const unsigned char*>(host) + (first + i * step) * 64, 64);
-    if (hipMalloc(&b->pts, (size_t)count * 64) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error("not enough device memory for the base points");
-    }
-    try {
-        points_take_every(b->pts, all->pts, first, step, count, c->stream);
-        UG_HIP(hipStreamSynchronize(c->stream));
-    } catch (...) { hipFree(b->pts); throw; }
+    if (!b->pts.try_alloc((size_t)count * 16)) throw std::runtime_error("not enough device memory for the base points");
+    points_take_every(b->pts.get(), all->pts.get(), first, step, count, c->stream);
+    UG_HIP(hipStreamSynchronize(c->stream));
     *out = b.release();
     UG_CATCH
 }
@@ -525,53 +511,49 @@ int ug_bases_create_group_strided_g1(ug_ctx* c, int members, const void* const* 
     int windows = 1;
     if (table_c) windows = MsmGeometry::table_count(table_c, MsmGeometry::choose_tables(slots, table_c, stride).stride);      // validates width and stride
     if (slots > ((u64)1 << TABLE_INDEX_BITS)) throw std::invalid_argument("a base group holds at most 2^27 scalars");
-    ug_bases* b = new ug_bases{c, false, slots * (u64)members, group_first, nullptr, 0};
+    std::unique_ptr<ug_bases> hold(new ug_bases{c, false, slots * (u64)members, group_first});
+    ug_bases* b = hold.get();
     b->members = members; b->slots = slots;
     const bool defer = table_c && c->defer_tables;            // (as bases_create)
     if (defer) windows = 1;
     const size_t bytes = (size_t)b->n * 64;
     u64 most = 0;
     for (int m = 0; m < members; m++) most = n[m] > most ? n[m] : most;
-    u32* stage = nullptr;
+    DevBuf<u32> stage_own;
     trace_step("group: allocating");
-    if (hipMalloc(&b->pts, bytes ? bytes * (size_t)windows : 4) != hipSuccess || hipMalloc(&stage, most ? (size_t)most * 64 : 4) != hipSuccess) {
-        (void)hipGetLastError();
-        if (b->pts) hipFree(b->pts);
-        delete b;
+    if (!b->pts.try_alloc(bytes / 4 * (size_t)windows) || !stage_own.try_alloc((size_t)most * 16))
         throw std::runtime_error(table_c ? "not enough device memory for the window tables" : "not enough device memory for the base points");
+    u32* const stage = stage_own.get();
+    trace_step("group: allocated");
+    if (bytes) {
+        UG_HIP(hipMemsetAsync(b->pts.get(), 0, bytes, c->stream));            // slots without a point: infinity
+        UG_HIP(hipStreamSynchronize(c->stream));
     }
-    try {
-        trace_step("group: allocated");
-        if (bytes) {
-            UG_HIP(hipMemsetAsync(b->pts, 0, bytes, c->stream));            // slots without a point: infinity
-            UG_HIP(hipStreamSynchronize(c->stream));
+    trace_step("group: table 0 cleared");
+    u32* pts = b->pts.get();
+    const int level = c->check_level;
+    for (int m = 0; m < members; m++) {
+        trace_step("group: member upload");
+        // chunks of whole records: converted to the device form and moved to their slots behind their own DMA
+        if (!n[m]) continue;
+        const u64 slot0 = first[m] - group_first, first_m = first[m];
+        unsigned long long* word = nullptr;
+        if (level) { check_arm(c); word = c->check_word.get(); }
+        host_to_device(c, stage, host[m], (size_t)n[m] * 64, [=](size_t off, size_t len, hipStream_t st) {
+            if (level) check_points(false, stage + off / 4, len / 64, first_m + off / 64, level, word, st);
+            convert_points_g1(stage + off / 4, len / 64, st);
+            interleave_points_g1(pts, stage + off / 4, len / 64, members, m, slot0 + off / 64, st);
+        }, /*fresh*/ true);
+        if (level) {                                       // per member (its upload has waited for every chunk), so that the member can be named
+            const ug_point_fault f = check_read(c);
+            if (f.reason != UG_POINT_OK) throw_point_fault(c, m, f);
         }
-        trace_step("group: table 0 cleared");
-        u32* pts = b->pts;
-        const int level = c->check_level;
-        for (int m = 0; m < members; m++) {
-            trace_step("group: member upload");
-            // chunks of whole records: converted to the device form and moved to their slots behind their own DMA
-            if (!n[m]) continue;
-            const u64 slot0 = first[m] - group_first, first_m = first[m];
-            unsigned long long* word = nullptr;
-            if (level) { check_arm(c); word = c->check_word; }
-            host_to_device(c, stage, host[m], (size_t)n[m] * 64, [=](size_t off, size_t len, hipStream_t st) {
-                if (level) check_points(false, stage + off / 4, len / 64, first_m + off / 64, level, word, st);
-                convert_points_g1(stage + off / 4, len / 64, st);
-                interleave_points_g1(pts, stage + off / 4, len / 64, members, m, slot0 + off / 64, st);
-            }, /*fresh*/ true);
-            if (level) {                                       // per member (its upload has waited for every chunk), so that the member can be named
-                const ug_point_fault f = check_read(c);
-                if (f.reason != UG_POINT_OK) throw_point_fault(c, m, f);
-            }
-        }
-        if (table_c && b->n && !defer) build_window_tables(false, pts, b->n, table_c * stride, windows, c->stream);
-    } catch (...) { hipFree(stage); hipFree(b->pts); delete b; throw; }
-    c->deferred_free.push_back(stage);      // (not hipFree here: it would wait for the table build just queued, and the caller's next
-                                            // section could no longer be uploaded beside it)
+    }
+    if (table_c && b->n && !defer) build_window_tables(false, pts, b->n, table_c * stride, windows, c->stream);
+    c->deferred_free.push_back(std::move(stage_own));      // (not freed here: that would wait for the table build just queued, and the
+                                                           // caller's next section could no longer be uploaded beside it)
     if (defer) { b->deferred_c = table_c; b->deferred_stride = stride; } else if (table_c) { b->table_c = table_c; b->table_stride = stride; }
-    *out = b;
+    *out = hold.release();
     UG_CATCH
 }
 int ug_bases_create_group_g1(ug_ctx* c, int members, const void* const* host, const uint64_t* n, const uint64_t* first,
@@ -591,22 +573,21 @@ int ug_points_check(ug_ctx* c, int g2, const void* host_points, uint64_t n, int 
     if (!n) return UG_OK;
     const size_t rec = g2 ? 128 : 64;
     const u64 piece = ((u64)64 << 20) / rec;                   // 64 MiB of records at a time
-    u32* buf = nullptr;
-    if (hipMalloc(&buf, (size_t)(n < piece ? n : piece) * rec) != hipSuccess) { (void)hipGetLastError(); throw std::runtime_error("not enough device memory for the point check"); }
-    try {
-        check_arm(c);
-        unsigned long long* word = c->check_word;
-        const bool is_g2 = g2 != 0;
-        for (u64 done = 0; done < n; done += piece) {
-            const u64 m = n - done < piece ? n - done : piece;
-            host_to_device(c, buf, static_cast<const uint8_t*>(host_points) + done * rec, (size_t)m * rec,
-                           [=](size_t off, size_t len, hipStream_t st) { check_points(is_g2, buf + off / 4, len / rec, done + off / rec, level, word, st); },
-                           /*fresh*/ true);      // (buf is this call's own, and every upload returns with its kernels done)
-        }
-        *out = check_read(c);
-    } catch (...) { hipFree(buf); if (!c->check_level) check_release(c); throw; }
-    hipFree(buf);
-    if (!c->check_level) check_release(c);                     // nothing stays resident
+    // nothing stays resident: the fault word goes when the call ends, however it ends, unless it is the context's (check_level)
+    struct WordScope { ug_ctx* c; ~WordScope() { if (!c->check_level) check_release(c); } } word_scope{c};
+    DevBuf<u32> buf_own;
+    if (!buf_own.try_alloc((size_t)(n < piece ? n : piece) * (rec / 4))) throw std::runtime_error("not enough device memory for the point check");
+    u32* const buf = buf_own.get();
+    check_arm(c);
+    unsigned long long* word = c->check_word.get();
+    const bool is_g2 = g2 != 0;
+    for (u64 done = 0; done < n; done += piece) {
+        const u64 m = n - done < piece ? n - done : piece;
+        host_to_device(c, buf, static_cast<const uint8_t*>(host_points) + done * rec, (size_t)m * rec,
+                       [=](size_t off, size_t len, hipStream_t st) { check_points(is_g2, buf + off / 4, len / rec, done + off / rec, level, word, st); },
+                       /*fresh*/ true);      // (buf is this call's own, and every upload returns with its kernels done)
+    }
+    *out = check_read(c);
     UG_CATCH
 }
 // The mask form: the same pieces, the status bytes of each piece downloaded behind it.
@@ -619,24 +600,19 @@ int ug_points_check_mask(ug_ctx* c, int g2, const void* host_points, uint64_t n,
     const size_t rec = g2 ? 128 : 64;
     const u64 piece = ((u64)64 << 20) / rec;                   // 64 MiB of records at a time
     const u64 room = n < piece ? n : piece;
-    u32* buf = nullptr;
-    uint8_t* status = nullptr;
-    if (hipMalloc(&buf, (size_t)room * rec) != hipSuccess || hipMalloc(&status, (size_t)room) != hipSuccess) {
-        (void)hipGetLastError();
-        if (buf) hipFree(buf);
-        throw std::runtime_error("not enough device memory for the point check");
+    DevBuf<u32> buf_own;
+    DevBuf<uint8_t> status_own;
+    if (!buf_own.try_alloc((size_t)room * (rec / 4)) || !status_own.try_alloc((size_t)room)) throw std::runtime_error("not enough device memory for the point check");
+    u32* const buf = buf_own.get();
+    uint8_t* const status = status_own.get();
+    const bool is_g2 = g2 != 0;
+    for (u64 done = 0; done < n; done += piece) {
+        const u64 m = n - done < piece ? n - done : piece;
+        host_to_device(c, buf, static_cast<const uint8_t*>(host_points) + done * rec, (size_t)m * rec,
+                       [=](size_t off, size_t len, hipStream_t st) { check_points_mask(is_g2, buf + off / 4, len / rec, level, status + off / rec, st); },
+                       /*fresh*/ true);      // (every upload returns with its kernels done)
+        UG_HIP(hipMemcpy(reasons + done, status, (size_t)m, hipMemcpyDeviceToHost));
     }
-    try {
-        const bool is_g2 = g2 != 0;
-        for (u64 done = 0; done < n; done += piece) {
-            const u64 m = n - done < piece ? n - done : piece;
-            host_to_device(c, buf, static_cast<const uint8_t*>(host_points) + done * rec, (size_t)m * rec,
-                           [=](size_t off, size_t len, hipStream_t st) { check_points_mask(is_g2, buf + off / 4, len / rec, level, status + off / rec, st); },
-                           /*fresh*/ true);      // (every upload returns with its kernels done)
-            UG_HIP(hipMemcpy(reasons + done, status, (size_t)m, hipMemcpyDeviceToHost));
-        }
-    } catch (...) { hipFree(buf); hipFree(status); throw; }
-    hipFree(buf); hipFree(status);
     UG_CATCH
 }
 const char* ug_point_reason_text(int reason) {
@@ -812,17 +788,14 @@ int ug_bases_precompute_strided(ug_bases* b, int c, int stride) {
     ctx->use();
     if (b->n) {
         size_t rec = b->g2 ? 128 : 64;
-        u32* all = nullptr;
-        if (hipMalloc(&all, (size_t)tables * b->n * rec) != hipSuccess) {
-            (void)hipGetLastError();
-            throw std::runtime_error("not enough device memory for the window tables");
-        }
-        UG_HIP(hipMemcpyAsync(all, b->pts, (size_t)b->n * rec, hipMemcpyDeviceToDevice, ctx->stream));
-        build_window_tables(b->g2, all, b->n, c * g.stride, tables, ctx->stream);
+        DevBuf<u32> all;                             // (the set's only after the last call that can throw)
+        if (!all.try_alloc((size_t)tables * b->n * (rec / 4))) throw std::runtime_error("not enough device memory for the window tables");
+        UG_HIP(hipMemcpyAsync(all.get(), b->pts.get(), (size_t)b->n * rec, hipMemcpyDeviceToDevice, ctx->stream));
+        build_window_tables(b->g2, all.get(), b->n, c * g.stride, tables, ctx->stream);
         UG_HIP(hipStreamSynchronize(ctx->stream));
         alloc_epoch_bump();                          // (captured launch sequences that read the old array are stale now)
-        hipFree(b->pts);
-        b->pts = all;
+        b->pts.release();
+        b->pts = std::move(all);
     }
     b->table_c = c;
     b->table_stride = stride;
@@ -838,12 +811,11 @@ int ug_bases_drop_tables(ug_bases* b) {
     ctx->use();
     UG_HIP(hipStreamSynchronize(ctx->stream));
     size_t bytes = (size_t)b->n * (b->g2 ? 128 : 64);
-    u32* small = nullptr;
-    UG_HIP(hipMalloc(&small, bytes ? bytes : 4));
-    if (bytes) UG_HIP(hipMemcpy(small, b->pts, bytes, hipMemcpyDeviceToDevice));
+    DevBuf<u32> small(bytes / 4);
+    if (bytes) UG_HIP(hipMemcpy(small.get(), b->pts.get(), bytes, hipMemcpyDeviceToDevice));
     alloc_epoch_bump();
-    hipFree(b->pts);
-    b->pts = small;
+    b->pts.release();
+    b->pts = std::move(small);
     b->table_c = 0;
     b->table_stride = 1;
     UG_CATCH
@@ -871,26 +843,24 @@ int ug_bases_tables_alloc(ug_bases* b, void** mem) {
     if (!b->deferred_c || !b->n) return UG_OK;                       // nothing deferred (or nothing to build)
     b->ctx->use();
     const int windows = MsmGeometry::table_count(b->deferred_c, b->deferred_stride);
-    if (hipMalloc(mem, (size_t)windows * b->n * (b->g2 ? 128 : 64)) != hipSuccess) {
-        (void)hipGetLastError();
-        *mem = nullptr;
-        throw std::runtime_error("not enough device memory for the window tables");
-    }
+    DevBuf<u32> room;
+    if (!room.try_alloc((size_t)windows * b->n * (b->g2 ? 32 : 16))) throw std::runtime_error("not enough device memory for the window tables");
+    *mem = room.take();                                              // the caller's until ug_bases_tables_adopt
     UG_CATCH
 }
 int ug_bases_tables_adopt(ug_bases* b, void* mem) {
     UG_TRY
     if (!b) throw std::invalid_argument("null argument");
-    if (!b->deferred_c) { if (mem) hipFree(mem); return UG_OK; }
+    // (mem stays the caller's until it is swapped in: a failing call leaves it with them, as ug_bases_tables_alloc handed it over)
+    if (!b->deferred_c) { DevBuf<u32> unused; unused.adopt(static_cast<u32*>(mem)); return UG_OK; }      // nothing deferred any more: freed here
     ug_ctx* c = b->ctx;
     c->use();
     if (b->n) {
         if (!mem) throw std::invalid_argument("null argument");
-        UG_HIP(hipMemcpyAsync(mem, b->pts, (size_t)b->n * (b->g2 ? 128 : 64), hipMemcpyDeviceToDevice, c->stream));
+        UG_HIP(hipMemcpyAsync(mem, b->pts.get(), (size_t)b->n * (b->g2 ? 128 : 64), hipMemcpyDeviceToDevice, c->stream));
         UG_HIP(hipStreamSynchronize(c->stream));
         alloc_epoch_bump();                          // (captured launch sequences that read the old array are stale now)
-        hipFree(b->pts);
-        b->pts = static_cast<u32*>(mem);
+        b->pts.adopt(static_cast<u32*>(mem));        // (frees the old array here, then owns the new one)
     }
     b->table_c = b->deferred_c;
     b->table_stride = b->deferred_stride;
@@ -911,7 +881,7 @@ int ug_bases_tables_step(ug_bases* b, uint64_t max_points, uint64_t* remaining) 
         // (a group is one array of n = slots * members records; a lane of the table kernel carries 4 (G1) / 2 (G2) consecutive
         // points, so pieces start at multiples of 4)
         const u64 take = count >= b->n - first ? b->n - first : (count + 3) / 4 * 4;
-        build_window_tables(b->g2, b->pts, b->n, b->table_c * b->table_stride, windows, c->stream, first, take);
+        build_window_tables(b->g2, b->pts.get(), b->n, b->table_c * b->table_stride, windows, c->stream, first, take);
         UG_HIP(hipStreamSynchronize(c->stream));
         b->tables_built = first + take >= b->n ? ~(u64)0 : first + take;
     }
@@ -934,8 +904,8 @@ int ug_ctx_trim(ug_ctx* c) {
     c->use();
     UG_HIP(hipStreamSynchronize(c->stream));
     c->ws_g1.release(); c->ws_g2.release(); c->raw_ntt.release();
-    if (c->lookup_last) { hipFree(c->lookup_last); c->lookup_last = nullptr; c->lookup_last_n = 0; }
-    if (c->lookup_stage) { hipFree(c->lookup_stage); c->lookup_stage = nullptr; c->lookup_stage_bytes = 0; }
+    c->lookup_last.release(); c->lookup_last_n = 0;
+    c->lookup_stage.release(); c->lookup_stage_bytes = 0;
     UG_CATCH
 }
 int ug_ctx_mem_info(ug_ctx* c, uint64_t* free_bytes, uint64_t* total_bytes) {
@@ -952,7 +922,6 @@ void ug_bases_destroy(ug_bases* b) {
     if (!b) return;
     hipSetDevice(b->ctx->device);
     alloc_epoch_bump();
-    hipFree(b->pts);
     delete b;
 }
 
@@ -960,9 +929,9 @@ int ug_dvec_create(ug_ctx* c, uint64_t n, ug_dvec** out) {
     UG_TRY
     if (!c || !out) throw std::invalid_argument("null argument");
     c->use();
-    ug_dvec* v = new ug_dvec{c, n, nullptr, true};
-    UG_HIP(hipMalloc(&v->data, n ? (size_t)n * 32 : 32));
-    *out = v;
+    std::unique_ptr<ug_dvec> v(new ug_dvec(c, n));
+    v->data.alloc((size_t)n * 8);
+    *out = v.release();
     UG_CATCH
 }
 int ug_dvec_upload(ug_dvec* v, const void* host, uint64_t n) {
@@ -970,7 +939,7 @@ int ug_dvec_upload(ug_dvec* v, const void* host, uint64_t n) {
     if (!v || (!host && n)) throw std::invalid_argument("null argument");
     if (n > v->n) throw std::invalid_argument("upload larger than the vector");
     v->ctx->use();
-    host_to_device(v->ctx, v->data, host, (size_t)n * 32);
+    host_to_device(v->ctx, v->data.get(), host, (size_t)n * 32);
     UG_CATCH
 }
 int ug_dvec_upload_range(ug_dvec* v, const void* host, uint64_t first, uint64_t n, ug_ctx* via) {
@@ -980,7 +949,7 @@ int ug_dvec_upload_range(ug_dvec* v, const void* host, uint64_t first, uint64_t 
     ug_ctx* c = via ? via : v->ctx;
     if (c->device != v->ctx->device) throw std::invalid_argument("upload context on another device");
     c->use();
-    host_to_device(c, v->data + first * 8, host, (size_t)n * 32);
+    host_to_device(c, v->data.get() + first * 8, host, (size_t)n * 32);
     UG_CATCH
 }
 int ug_dvec_upload_idle(ug_dvec* v, const void* host, uint64_t n) {
@@ -990,7 +959,7 @@ int ug_dvec_upload_idle(ug_dvec* v, const void* host, uint64_t n) {
     v->ctx->use();
     // the caller vouches that nothing queued on the device reads or writes v: the copy runs on the uploader's own streams and
     // neither waits for the context's stream nor touches it (a proof may be running there)
-    host_to_device(v->ctx, v->data, host, (size_t)n * 32, StagedUploader::After(), /*fresh*/ true);
+    host_to_device(v->ctx, v->data.get(), host, (size_t)n * 32, StagedUploader::After(), /*fresh*/ true);
     UG_CATCH
 }
 int ug_dvec_download(const ug_dvec* v, void* host, uint64_t first, uint64_t n) {
@@ -998,7 +967,7 @@ int ug_dvec_download(const ug_dvec* v, void* host, uint64_t first, uint64_t n) {
     if (!v || (!host && n)) throw std::invalid_argument("null argument");
     if (first + n > v->n) throw std::invalid_argument("download outside the vector");
     v->ctx->use();
-    if (n) UG_HIP(hipMemcpyAsync(host, v->data + first * 8, (size_t)n * 32, hipMemcpyDeviceToHost, v->ctx->stream));
+    if (n) UG_HIP(hipMemcpyAsync(host, v->data.get() + first * 8, (size_t)n * 32, hipMemcpyDeviceToHost, v->ctx->stream));
     UG_HIP(hipStreamSynchronize(v->ctx->stream));
     UG_CATCH
 }
@@ -1008,12 +977,10 @@ int ug_dvec_gather(ug_dvec* out, const ug_dvec* src, const uint32_t* host_index,
     if (n > out->n) throw std::invalid_argument("gather larger than the output vector");
     ug_ctx* c = out->ctx;
     c->use();
-    u32* idx = nullptr;
-    UG_HIP(hipMalloc(&idx, n ? (size_t)n * 4 : 4));
-    if (n) UG_HIP(hipMemcpyAsync(idx, host_index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    gather_elements(out->data, src->data, idx, n, src->n, c->stream);
+    DevBuf<u32> idx(n);
+    if (n) UG_HIP(hipMemcpyAsync(idx.get(), host_index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    gather_elements(out->data.get(), src->data.get(), idx.get(), n, src->n, c->stream);
     UG_HIP(hipStreamSynchronize(c->stream));
-    hipFree(idx);
     UG_CATCH
 }
 // index lists that stay on the device (UltraGroth's round_indexes / final_round_indexes are part of the zkey)
@@ -1021,17 +988,16 @@ int ug_index_create(ug_ctx* c, const uint32_t* host_index, uint64_t n, ug_index*
     UG_TRY
     if (!c || !out || (!host_index && n)) throw std::invalid_argument("null argument");
     c->use();
-    ug_index* ix = new ug_index{c, n, nullptr};
-    UG_HIP(hipMalloc(&ix->data, n ? (size_t)n * 4 : 4));
-    if (n) UG_HIP(hipMemcpyAsync(ix->data, host_index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    std::unique_ptr<ug_index> ix(new ug_index{c, n});
+    ix->data.alloc(n);
+    if (n) UG_HIP(hipMemcpyAsync(ix->data.get(), host_index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));
-    *out = ix;
+    *out = ix.release();
     UG_CATCH
 }
 void ug_index_destroy(ug_index* ix) {
     if (!ix) return;
     hipSetDevice(ix->ctx->device);
-    hipFree(ix->data);
     delete ix;
 }
 int ug_dvec_gather_index(ug_dvec* out, const ug_dvec* src, const ug_index* index) {
@@ -1040,7 +1006,7 @@ int ug_dvec_gather_index(ug_dvec* out, const ug_dvec* src, const ug_index* index
     if (index->n > out->n) throw std::invalid_argument("gather larger than the output vector");
     ug_ctx* c = out->ctx;
     c->use();
-    gather_elements(out->data, src->data, index->data, index->n, src->n, c->stream);      // queued; the stream orders its users
+    gather_elements(out->data.get(), src->data.get(), index->data.get(), index->n, src->n, c->stream);      // queued; the stream orders its users
     UG_CATCH
 }
 int ug_dvec_gather_index_at(ug_dvec* out, uint64_t out_first, const ug_dvec* src, const ug_index* index) {
@@ -1049,7 +1015,7 @@ int ug_dvec_gather_index_at(ug_dvec* out, uint64_t out_first, const ug_dvec* src
     if (out_first > out->n || index->n > out->n - out_first) throw std::invalid_argument("gather outside the output vector");
     ug_ctx* c = out->ctx;
     c->use();
-    gather_elements(out->data + out_first * 8, src->data, index->data, index->n, src->n, c->stream);
+    gather_elements(out->data.get() + out_first * 8, src->data.get(), index->data.get(), index->n, src->n, c->stream);
     UG_CATCH
 }
 int ug_dvec_scatter(ug_dvec* dst, const uint32_t* host_index, const void* host_values, uint64_t n) {
@@ -1057,16 +1023,13 @@ int ug_dvec_scatter(ug_dvec* dst, const uint32_t* host_index, const void* host_v
     if (!dst || ((!host_index || !host_values) && n)) throw std::invalid_argument("null argument");
     ug_ctx* c = dst->ctx;
     c->use();
-    u32 *idx = nullptr, *val = nullptr;
-    UG_HIP(hipMalloc(&idx, n ? (size_t)n * 4 : 4));
-    UG_HIP(hipMalloc(&val, n ? (size_t)n * 32 : 32));
+    DevBuf<u32> idx(n), val((size_t)n * 8);
     if (n) {
-        UG_HIP(hipMemcpyAsync(idx, host_index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        UG_HIP(hipMemcpyAsync(val, host_values, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+        UG_HIP(hipMemcpyAsync(idx.get(), host_index, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        UG_HIP(hipMemcpyAsync(val.get(), host_values, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
     }
-    scatter_elements(dst->data, idx, val, n, dst->n, c->stream);
+    scatter_elements(dst->data.get(), idx.get(), val.get(), n, dst->n, c->stream);
     UG_HIP(hipStreamSynchronize(c->stream));
-    hipFree(idx); hipFree(val);
     UG_CATCH
 }
 int ug_dvec_apply_lookup(ug_dvec* dst, const uint32_t* w_idx, const uint32_t* p_idx, uint64_t n, const uint32_t* chunks,
@@ -1083,10 +1046,9 @@ int ug_dvec_apply_lookup(ug_dvec* dst, const uint32_t* w_idx, const uint32_t* p_
     ug_ctx* c = dst->ctx;
     c->use();
     if (c->lookup_last_n < dst->n) {
-        if (c->lookup_last) hipFree(c->lookup_last);
-        c->lookup_last = nullptr; c->lookup_last_n = 0;
-        UG_HIP(hipMalloc(&c->lookup_last, (size_t)dst->n * 4));
-        UG_HIP(hipMemsetAsync(c->lookup_last, 0, (size_t)dst->n * 4, c->stream));
+        c->lookup_last_n = 0;
+        c->lookup_last.alloc((size_t)dst->n);
+        UG_HIP(hipMemsetAsync(c->lookup_last.get(), 0, (size_t)dst->n * 4, c->stream));
         c->lookup_last_n = dst->n;
     }
     // one staging allocation: w_idx | p_idx | chunks | table
@@ -1097,7 +1059,7 @@ int ug_dvec_apply_lookup(ug_dvec* dst, const uint32_t* w_idx, const uint32_t* p_
     UG_HIP(hipMemcpyAsync(d_p, p_idx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (n_chunks) UG_HIP(hipMemcpyAsync(d_c, chunks, (size_t)n_chunks * 4, hipMemcpyHostToDevice, c->stream));
     UG_HIP(hipMemcpyAsync(d_t, table, tbytes, hipMemcpyHostToDevice, c->stream));
-    apply_lookup(dst->data, c->lookup_last, d_w, d_p, n, d_c, n_chunks, d_t, c->stream);
+    apply_lookup(dst->data.get(), c->lookup_last.get(), d_w, d_p, n, d_c, n_chunks, d_t, c->stream);
     UG_HIP(hipStreamSynchronize(c->stream));
     UG_CATCH
 }
@@ -1176,17 +1138,16 @@ void lookup_vectors(ug_ctx* c, ug_dvec* dst, uint64_t stride, int V, const void*
         if (d.n_chunks) memcpy(&host[d.c_off], l.chunks, (size_t)d.n_chunks * 4);
     }
     if (dst && max_n && c->lookup_last_n < (uint64_t)V * stride) {
-        if (c->lookup_last) hipFree(c->lookup_last);
-        c->lookup_last = nullptr; c->lookup_last_n = 0;
-        UG_HIP(hipMalloc(&c->lookup_last, (size_t)V * stride * 4));
-        UG_HIP(hipMemsetAsync(c->lookup_last, 0, (size_t)V * stride * 4, c->stream));
+        c->lookup_last_n = 0;
+        c->lookup_last.alloc((size_t)V * stride);
+        UG_HIP(hipMemsetAsync(c->lookup_last.get(), 0, (size_t)V * stride * 4, c->stream));
         c->lookup_last_n = (uint64_t)V * stride;
     }
     u32* stage = c->stage_for_lookup((size_t)std::max(at, upWords) * 4);
     const LookupVec* vecDev = reinterpret_cast<const LookupVec*>(stage);
     UG_HIP(hipMemcpyAsync(stage, host.data(), (size_t)upWords * 4, hipMemcpyHostToDevice, c->stream));
     if (rands) lookup_tables_vectors(stage, vecDev, V, max_L, c->stream);
-    if (dst) apply_lookup_vectors(dst->data, stride, c->lookup_last, stage, vecDev, V, max_n, c->stream);
+    if (dst) apply_lookup_vectors(dst->data.get(), stride, c->lookup_last.get(), stage, vecDev, V, max_n, c->stream);
     std::vector<u32> back;
     if (tables_out && rands) {
         back.resize((size_t)tablesWords);
@@ -1226,7 +1187,7 @@ uint64_t ug_lookup_vectors_bytes(uint64_t vector_stride, const ug_lookup_lists* 
     return bytes;
 }
 uint64_t ug_dvec_size(const ug_dvec* v) { return v ? v->n : 0; }
-void* ug_dvec_device_ptr(const ug_dvec* v) { return v ? v->data : nullptr; }
+void* ug_dvec_device_ptr(const ug_dvec* v) { return v ? v->data.get() : nullptr; }
 // dst[dst_first .. + count) = src[src_first .. + count); the vectors may live on different devices of the node (peer copy over
 // xGMI, or through the host when peer access is not there: hipMemcpyPeer decides). Blocking; both vectors' earlier work must be
 // complete (the phase calls that produce them are).
@@ -1245,7 +1206,7 @@ int ug_dvec_copy_via(ug_dvec* dst, uint64_t dst_first, const ug_dvec* src, uint6
     c->use();
     const size_t bytes = (size_t)count * 32;
     if (src->ctx->device == c->device)
-        UG_HIP(hipMemcpyAsync(dst->data + dst_first * 8, src->data + src_first * 8, bytes, hipMemcpyDeviceToDevice, c->stream));
+        UG_HIP(hipMemcpyAsync(dst->data.get() + dst_first * 8, src->data.get() + src_first * 8, bytes, hipMemcpyDeviceToDevice, c->stream));
     else {
         // two devices of the node: direct access over xGMI is switched on once per ordered pair (the copy works without it, staged
         // by the runtime; "already enabled" and "not supported" are not errors here)
@@ -1256,7 +1217,7 @@ int ug_dvec_copy_via(ug_dvec* dst, uint64_t dst_first, const ug_dvec* src, uint6
             if (hipDeviceCanAccessPeer(&can, a, b) == hipSuccess && can) (void)hipDeviceEnablePeerAccess(b, 0);      // (current device is a: c->use())
             (void)hipGetLastError();
         }
-        UG_HIP(hipMemcpyPeerAsync(dst->data + dst_first * 8, c->device, src->data + src_first * 8, src->ctx->device, bytes, c->stream));
+        UG_HIP(hipMemcpyPeerAsync(dst->data.get() + dst_first * 8, c->device, src->data.get() + src_first * 8, src->ctx->device, bytes, c->stream));
     }
     UG_HIP(hipStreamSynchronize(c->stream));
     UG_CATCH
@@ -1265,12 +1226,15 @@ int ug_dvec_wrap(ug_ctx* c, void* device_ptr, uint64_t n, ug_dvec** out) {
     UG_TRY
     if (!c || !out || (!device_ptr && n)) throw std::invalid_argument("null argument");
     if ((uintptr_t)device_ptr & 15) throw std::invalid_argument("device pointer must be 16-byte aligned");
-    *out = new ug_dvec{c, n, static_cast<u32*>(device_ptr), false};
+    std::unique_ptr<ug_dvec> v(new ug_dvec(c, n));
+    v->owns = false;
+    v->data.adopt(static_cast<u32*>(device_ptr));
+    *out = v.release();
     UG_CATCH
 }
 void ug_dvec_destroy(ug_dvec* v) {
     if (!v) return;
-    if (v->owns) { hipSetDevice(v->ctx->device); alloc_epoch_bump(); hipFree(v->data); }
+    if (v->owns) { hipSetDevice(v->ctx->device); alloc_epoch_bump(); }
     delete v;
 }
 
@@ -1293,7 +1257,7 @@ int ug_schedule_build(ug_schedule* s, const ug_dvec* scalars, uint64_t first, ui
     s->first = first;
     MsmGeometry g = MsmGeometry::choose(count);
     g.set_classes(s->classes_for(first, count));
-    s->sched.build(scalars->data + first * 8, g, c->stream);
+    s->sched.build(scalars->data.get() + first * 8, g, c->stream);
     tm.stop();
     UG_CATCH
 }
@@ -1311,7 +1275,7 @@ int ug_schedule_build_tables_strided(ug_schedule* s, const ug_dvec* scalars, uin
     g.set_classes(s->classes_for(first, count));
     StreamTimer::Scope tm = ctx->timer.time(ctx->stream, &ctx->msm);
     s->first = first;
-    s->sched.build(scalars->data + first * 8, g, ctx->stream);
+    s->sched.build(scalars->data.get() + first * 8, g, ctx->stream);
     tm.stop();
     UG_CATCH
 }
@@ -1338,7 +1302,7 @@ int ug_schedule_build_vectors(ug_schedule* s, const ug_dvec* scalars, uint64_t f
     g.set_vectors(vectors, vector_stride);
     StreamTimer::Scope tm = ctx->timer.time(ctx->stream, &ctx->msm);
     s->first = first;
-    s->sched.build(scalars->data + first * 8, g, ctx->stream);
+    s->sched.build(scalars->data.get() + first * 8, g, ctx->stream);
     tm.stop();
     UG_CATCH
 }
@@ -1437,7 +1401,7 @@ int ug_msm_batch_enqueue(ug_ctx* c, int count, const ug_bases* const* bases, con
             const ug_bases* b = bases[k];
             if ((b->g2 ? 1 : 0) != g2) continue;
             idx[call.count] = k;                  // (an all-infinity set takes no part: msm_enqueue_multi)
-            call.products[call.count++] = {b->pts, b->empty ? 0 : b->n, schedule_delta(s, b, index_shifts ? index_shifts[k] : 0), host[k]};
+            call.products[call.count++] = {b->pts.get(), b->empty ? 0 : b->n, schedule_delta(s, b, index_shifts ? index_shifts[k] : 0), host[k]};
             if (call.count == MSM_BATCH_WIDTH) flush();
         }
         flush();
@@ -1489,7 +1453,7 @@ int ug_msm_witness_enqueue(ug_ctx* c, const ug_bases* group, const ug_bases* g2s
         const MsmCall g1 = group_call(slots, group, s, outs_group);
         MsmCall g2;
         g2.count = 1;
-        g2.products[0] = {g2set->pts, g2set->empty ? 0 : g2set->n, schedule_delta(s, g2set), slots.add(out_g2, true)};
+        g2.products[0] = {g2set->pts.get(), g2set->empty ? 0 : g2set->n, schedule_delta(s, g2set), slots.add(out_g2, true)};
         // both accumulations, back to back
         msm_enqueue(false, s->sched, c->ws_g1, g1, c->stream, c->stat(3), pend, MSM_PHASE_ACCUMULATE);
         msm_enqueue(true, s->sched, c->ws_g2, g2, c->stream, c->stat(1), pend + K, MSM_PHASE_ACCUMULATE);
@@ -1564,19 +1528,13 @@ int ug_hpoly_create(ug_ctx* c, const void* host_coefs, uint64_t n_coefs, uint32_
     c->use();
     std::unique_ptr<ug_hpoly, void (*)(ug_hpoly*)> hp(new ug_hpoly(), ug_hpoly_destroy);   // frees everything on any throw below
     hp->ctx = c; hp->domain = domain; hp->nvars = n_vars;
-    uint8_t* raw = nullptr;
-    UG_HIP(hipMalloc(&raw, n_coefs ? (size_t)n_coefs * 44 : 4));
-    bool ok = false;
-    try {
-        host_to_device(c, raw, host_coefs, (size_t)n_coefs * 44);
-        ok = hp->mat.build(raw, n_coefs, domain, n_vars, c->stream);
-    } catch (...) { hipFree(raw); throw; }
-    hipFree(raw);
+    DevBuf<uint8_t> raw((size_t)n_coefs * 44);
+    host_to_device(c, raw.get(), host_coefs, (size_t)n_coefs * 44);
+    const bool ok = hp->mat.build(raw.get(), n_coefs, domain, n_vars, c->stream);
+    raw.release();                               // (before the plan and the workspaces are allocated)
     if (!ok) throw std::invalid_argument("coefficient record out of range (m, row or signal index)");
     hp->ntt.init(hp->mat.logn, c->stream);
-    size_t bytes = (size_t)domain * 32;
-    UG_HIP(hipMalloc(&hp->a, bytes)); UG_HIP(hipMalloc(&hp->b, bytes));
-    UG_HIP(hipMalloc(&hp->c, bytes)); UG_HIP(hipMalloc(&hp->t, bytes)); UG_HIP(hipMalloc(&hp->t2, bytes));
+    for (DevBuf<u32>* w : {&hp->a, &hp->b, &hp->c, &hp->t, &hp->t2}) w->alloc((size_t)domain * 8);
     *out = hp.release();
     UG_CATCH
 }
@@ -1590,36 +1548,36 @@ void hpoly_queue(ug_hpoly* hp, const u32* w, u64 w_stride, u32* h, u64 h_stride,
     hipStream_t st = c->stream;
     const u64 n = hp->domain;
     // S5-S6: a = A.w, b = B.w   (rows stored bit-reversed)            src/groth16.cpp:66-99
-    coef_matvec_vectors(hp->a, hp->b, n, hp->mat, w, w_stride, g, st);
+    coef_matvec_vectors(hp->a.get(), hp->b.get(), n, hp->mat, w, w_stride, g, st);
     if (hp->mat.logn == 0) {
         // one-point domain: every transform is the identity (n^-1 = 1, omega_2^0 = 1), nothing to fold into
-        fr_mul_pointwise(hp->c, hp->a, hp->b, n * (u64)g, st);             // (the g slices of a, b and c are adjacent)
-        if (g == 1) fr_h_final(h, hp->a, hp->b, hp->c, n, st);
-        else fr_h_final_vectors(h, h_stride, hp->a, hp->b, hp->c, n, n, g, st);
+        fr_mul_pointwise(hp->c.get(), hp->a.get(), hp->b.get(), n * (u64)g, st);             // (the g slices of a, b and c are adjacent)
+        if (g == 1) fr_h_final(h, hp->a.get(), hp->b.get(), hp->c.get(), n, st);
+        else fr_h_final_vectors(h, h_stride, hp->a.get(), hp->b.get(), hp->c.get(), n, n, g, st);
         return;
     }
     static const bool batched = !(measure_env("UG_NTT_BATCH") && atoi(measure_env("UG_NTT_BATCH")) == 0);      // A/B switch (-DUG_MEASURE)
     NttPass pa[NTT_MAX_PASSES], pb[NTT_MAX_PASSES], pc[NTT_MAX_PASSES];
-    NttFusion cinv; cinv.in2 = hp->b; cinv.work = hp->c; cinv.in2_stride = n; cinv.work_stride = n;
-    NttFusion cfwd; cfwd.work = hp->c; cfwd.fin_a = hp->a; cfwd.fin_b = hp->b; cfwd.work_stride = n; cfwd.fin_a_stride = n; cfwd.fin_b_stride = n;
-    const int np = hp->ntt.passes(pc, hp->t2, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, &cinv, n, n);
+    NttFusion cinv; cinv.in2 = hp->b.get(); cinv.work = hp->c.get(); cinv.in2_stride = n; cinv.work_stride = n;
+    NttFusion cfwd; cfwd.work = hp->c.get(); cfwd.fin_a = hp->a.get(); cfwd.fin_b = hp->b.get(); cfwd.work_stride = n; cfwd.fin_a_stride = n; cfwd.fin_b_stride = n;
+    const int np = hp->ntt.passes(pc, hp->t2.get(), hp->a.get(), /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist.get(), nullptr, &cinv, n, n);
     if (batched && np > 1) {
         // The three chains side by side, pass by pass: ONE launch per pass index holds the same pass of all three transforms
         // (blockIdx.y), 7 launches instead of 18 for a three-pass size, and the ends of the launches fill with the other
         // chains' workgroups. Buffers: every first pass only READS a and b (chain c's forms a o b from them, S7 :100-108), so
         // chains a and b take their intermediate passes to work buffers (hp->t and the h vector, which is written last of
         // all) and scatter their twisted coefficients back into a and b; chain c works on hp->c and leaves them in hp->t2.
-        NttFusion wa; wa.work = hp->t; wa.work_stride = n;
+        NttFusion wa; wa.work = hp->t.get(); wa.work_stride = n;
         NttFusion wb; wb.work = h; wb.work_stride = h_stride;
-        hp->ntt.passes(pa, hp->a, hp->a, true, false, true, hp->ntt.twist, nullptr, &wa, n, n);      // S8 ifft + twist :110-128
-        hp->ntt.passes(pb, hp->b, hp->b, true, false, true, hp->ntt.twist, nullptr, &wb, n, n);
+        hp->ntt.passes(pa, hp->a.get(), hp->a.get(), true, false, true, hp->ntt.twist.get(), nullptr, &wa, n, n);      // S8 ifft + twist :110-128
+        hp->ntt.passes(pb, hp->b.get(), hp->b.get(), true, false, true, hp->ntt.twist.get(), nullptr, &wb, n, n);
         const NttPass* inv3[3] = {pa, pb, pc};
         for (int p = 0; p < np; p++) hp->ntt.launch(inv3, 3, p, st, c->stat(2), g);
         // S8 fft :130-140, in place on a and b; chain c's last pass also forms h = a o b - c (S9 :142-148) from the FINISHED
         // a and b, so it goes after theirs
-        hp->ntt.passes(pa, hp->a, hp->a, false, false, false, nullptr, nullptr, nullptr, n, n);
-        hp->ntt.passes(pb, hp->b, hp->b, false, false, false, nullptr, nullptr, nullptr, n, n);
-        hp->ntt.passes(pc, h, hp->t2, false, false, false, nullptr, nullptr, &cfwd, h_stride, n);
+        hp->ntt.passes(pa, hp->a.get(), hp->a.get(), false, false, false, nullptr, nullptr, nullptr, n, n);
+        hp->ntt.passes(pb, hp->b.get(), hp->b.get(), false, false, false, nullptr, nullptr, nullptr, n, n);
+        hp->ntt.passes(pc, h, hp->t2.get(), false, false, false, nullptr, nullptr, &cfwd, h_stride, n);
         const NttPass* fwd3[3] = {pa, pb, pc};
         for (int p = 0; p + 1 < np; p++) hp->ntt.launch(fwd3, 3, p, st, c->stat(2), g);
         hp->ntt.launch(fwd3, 2, np - 1, st, c->stat(2), g);
@@ -1628,15 +1586,15 @@ void hpoly_queue(ug_hpoly* hp, const u32* w, u64 w_stride, u32* h, u64 h_stride,
     } else {
         // S7 + the inverse half of the third chain: c = a o b is formed inside the first pass of its ifft (:100-108), whose
         // passes run on hp->c so that a and b stay intact; the twisted coefficients wait in hp->t2
-        hp->ntt.transform(hp->t2, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2), &cinv, g, n, n);
+        hp->ntt.transform(hp->t2.get(), hp->a.get(), /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist.get(), nullptr, st, c->stat(2), &cinv, g, n, n);
         // S8: ifft, twist by omega_2n^i (with 1/n folded in), fft          :110-140
-        u32* polys[2] = {hp->a, hp->b};
+        u32* polys[2] = {hp->a.get(), hp->b.get()};
         for (int p = 0; p < 2; p++) {
-            hp->ntt.transform(hp->t, polys[p], /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2), nullptr, g, n, n);
-            hp->ntt.transform(polys[p], hp->t, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), nullptr, g, n, n);
+            hp->ntt.transform(hp->t.get(), polys[p], /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist.get(), nullptr, st, c->stat(2), nullptr, g, n, n);
+            hp->ntt.transform(polys[p], hp->t.get(), /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), nullptr, g, n, n);
         }
         // the forward half of the third chain, with S9 (h = a o b - c, to plain integers, :142-148) inside its last pass
-        hp->ntt.transform(h, hp->t2, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), &cfwd, g, h_stride, n);
+        hp->ntt.transform(h, hp->t2.get(), /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2), &cfwd, g, h_stride, n);
     }
 }
 }  // namespace
@@ -1651,7 +1609,7 @@ int ug_hpoly_run(ug_hpoly* hp, const ug_dvec* w, ug_dvec* h_out) {
     c->use();
     fault_point(UG_FAULT_HPOLY_RUN);
     StreamTimer::Scope tm = c->timer.time(c->stream, &c->fft);
-    hpoly_queue(hp, w->data, 0, h_out->data, 0, 1);
+    hpoly_queue(hp, w->data.get(), 0, h_out->data.get(), 0, 1);
     tm.stop();
     UG_CATCH
 }
@@ -1673,7 +1631,7 @@ int ug_hpoly_run_vectors(ug_hpoly* hp, const ug_dvec* w, uint64_t witness_stride
     for (int v0 = 0; v0 < vectors; v0 += hp->group) {
         const int g = vectors - v0 < hp->group ? vectors - v0 : hp->group;
         for (int v = 0; v < g; v++) fault_point(UG_FAULT_HPOLY_RUN);            // (once per witness, as a loop of ug_hpoly_run)
-        hpoly_queue(hp, w->data + (u64)v0 * witness_stride * 8, witness_stride, h_out->data + (u64)v0 * h_stride * 8, h_stride, g);
+        hpoly_queue(hp, w->data.get() + (u64)v0 * witness_stride * 8, witness_stride, h_out->data.get() + (u64)v0 * h_stride * 8, h_stride, g);
     }
     tm.stop();
     UG_CATCH
@@ -1693,36 +1651,28 @@ int ug_hpoly_reserve_vectors(ug_hpoly* hp, int group) {
     ug_ctx* c = hp->ctx;
     c->use();
     if (c->recording) throw std::invalid_argument("no reservation while a launch sequence is being recorded");
-    const size_t bytes = (size_t)group * hp->domain * 32;
-    u32** held[5] = {&hp->a, &hp->b, &hp->c, &hp->t, &hp->t2};
+    const size_t words = (size_t)group * hp->domain * 8;
+    DevBuf<u32>* held[5] = {&hp->a, &hp->b, &hp->c, &hp->t, &hp->t2};
     const bool shrink = group < hp->group;
     if (shrink) {
         UG_HIP(hipStreamSynchronize(c->stream));               // whatever was queued on the old workspaces has finished
         alloc_epoch_bump();                                    // (recorded launch sequences point into them)
-        for (int k = 0; k < 5; k++) { hipFree(*held[k]); *held[k] = nullptr; }
+        for (int k = 0; k < 5; k++) held[k]->release();
         hp->group = 0;                                         // (no workspaces until the five below exist: the run calls refuse)
     }
-    u32* fresh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    try {
-        for (int k = 0; k < 5; k++) {
-            if (hipMalloc(&fresh[k], bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                fresh[k] = nullptr;
-                throw std::runtime_error("H-polynomial workspaces for " + std::to_string(group) + " vectors (" +
-                                         std::to_string(ug_hpoly_vectors_bytes(hp->domain, group)) + " bytes) do not fit the device memory");
-            }
-            if (k == 2) fault_point(UG_FAULT_HPOLY_RESERVE);           // (test hook: a failure with part of the workspaces allocated)
-        }
-    } catch (...) {
-        for (u32* f : fresh) if (f) hipFree(f);
-        throw;
+    DevBuf<u32> fresh[5];                                      // (a failure below frees what it got)
+    for (int k = 0; k < 5; k++) {
+        if (!fresh[k].try_alloc(words))
+            throw std::runtime_error("H-polynomial workspaces for " + std::to_string(group) + " vectors (" +
+                                     std::to_string(ug_hpoly_vectors_bytes(hp->domain, group)) + " bytes) do not fit the device memory");
+        if (k == 2) fault_point(UG_FAULT_HPOLY_RESERVE);           // (test hook: a failure with part of the workspaces allocated)
     }
     if (!shrink) {
         UG_HIP(hipStreamSynchronize(c->stream));
         alloc_epoch_bump();
-        for (int k = 0; k < 5; k++) hipFree(*held[k]);
+        for (int k = 0; k < 5; k++) held[k]->release();
     }
-    for (int k = 0; k < 5; k++) *held[k] = fresh[k];
+    for (int k = 0; k < 5; k++) *held[k] = std::move(fresh[k]);
     hp->group = group;
     UG_CATCH
 }
@@ -1742,21 +1692,21 @@ int ug_hpoly_chain(ug_hpoly* hp, const ug_dvec* w, int which, ug_dvec* out) {
     hipStream_t st = c->stream;
     u64 n = hp->domain;
     if (which == 2 && hp->mat.logn == 0) {
-        coef_matvec(hp->a, hp->b, hp->mat, w->data, 3, st);
-        fr_mul_pointwise(out->data, hp->a, hp->b, n, st);                // one-point domain: the chain is the identity
+        coef_matvec(hp->a.get(), hp->b.get(), hp->mat, w->data.get(), 3, st);
+        fr_mul_pointwise(out->data.get(), hp->a.get(), hp->b.get(), n, st);                // one-point domain: the chain is the identity
         tm.stop();
         return UG_OK;
     }
     if (which == 2) {
-        coef_matvec(hp->a, hp->b, hp->mat, w->data, 3, st);
-        NttFusion cinv; cinv.in2 = hp->b; cinv.work = hp->c;             // c = a o b inside the first pass
-        hp->ntt.transform(hp->t, hp->a, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2), &cinv);
+        coef_matvec(hp->a.get(), hp->b.get(), hp->mat, w->data.get(), 3, st);
+        NttFusion cinv; cinv.in2 = hp->b.get(); cinv.work = hp->c.get();             // c = a o b inside the first pass
+        hp->ntt.transform(hp->t.get(), hp->a.get(), /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist.get(), nullptr, st, c->stat(2), &cinv);
     } else {
-        coef_matvec(hp->a, hp->b, hp->mat, w->data, 1 << which, st);
-        u32* src = which ? hp->b : hp->a;
-        hp->ntt.transform(hp->t, src, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist, nullptr, st, c->stat(2));
+        coef_matvec(hp->a.get(), hp->b.get(), hp->mat, w->data.get(), 1 << which, st);
+        u32* src = which ? hp->b.get() : hp->a.get();
+        hp->ntt.transform(hp->t.get(), src, /*inverse*/ true, false, /*scatter_bitrev*/ true, hp->ntt.twist.get(), nullptr, st, c->stat(2));
     }
-    hp->ntt.transform(out->data, hp->t, /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2));
+    hp->ntt.transform(out->data.get(), hp->t.get(), /*inverse*/ false, false, false, nullptr, nullptr, st, c->stat(2));
     tm.stop();
     sync_and_resolve(c);                         // the caller hands the buffer to other libraries (RCCL): complete on return
     UG_CATCH
@@ -1771,7 +1721,7 @@ int ug_hpoly_combine(ug_hpoly* hp, const ug_dvec* a, const ug_dvec* b, const ug_
     ug_ctx* c = hp ? hp->ctx : h_out->ctx;      // (a rank that runs no chain keeps no ug_hpoly: the combine needs none)
     c->use();
     StreamTimer::Scope tm = c->timer.time(c->stream, &c->fft);
-    fr_h_final(h_out->data + first * 8, a->data, b->data, cc->data, count, c->stream);
+    fr_h_final(h_out->data.get() + first * 8, a->data.get(), b->data.get(), cc->data.get(), count, c->stream);
     tm.stop();
     UG_CATCH
 }
@@ -1783,13 +1733,13 @@ int ug_hpoly_debug_abc(ug_hpoly* hp, void* ha, void* hb, void* hc) {
     ug_ctx* c = hp->ctx;
     c->use();
     void* host[3] = {ha, hb, hc};
-    u32* dev[3] = {hp->a, hp->b, hp->c};
+    u32* dev[3] = {hp->a.get(), hp->b.get(), hp->c.get()};
     // ug_hpoly_run folds the third chain's last pass into h; its coset evaluations are re-made from the twisted coefficients
-    if (hc) hp->ntt.transform(hp->c, hp->t2, /*inverse*/ false, false, false, nullptr, nullptr, c->stream);
+    if (hc) hp->ntt.transform(hp->c.get(), hp->t2.get(), /*inverse*/ false, false, false, nullptr, nullptr, c->stream);
     for (int p = 0; p < 3; p++) {
         if (!host[p]) continue;
-        fr_to_mont256(hp->t, dev[p], hp->domain, c->stream);
-        UG_HIP(hipMemcpyAsync(host[p], hp->t, (size_t)hp->domain * 32, hipMemcpyDeviceToHost, c->stream));
+        fr_to_mont256(hp->t.get(), dev[p], hp->domain, c->stream);
+        UG_HIP(hipMemcpyAsync(host[p], hp->t.get(), (size_t)hp->domain * 32, hipMemcpyDeviceToHost, c->stream));
         UG_HIP(hipStreamSynchronize(c->stream));
     }
     UG_CATCH
@@ -1799,8 +1749,6 @@ void ug_hpoly_destroy(ug_hpoly* hp) {
     if (!hp) return;
     hipSetDevice(hp->ctx->device);
     alloc_epoch_bump();
-    hipFree(hp->a); hipFree(hp->b); hipFree(hp->c); hipFree(hp->t); hipFree(hp->t2);
-    hp->mat.release(); hp->ntt.release();
     delete hp;
 }
 
@@ -1815,15 +1763,15 @@ const u32* r1cs_witness(const ug_r1cs* r, const ug_dvec* w, u64 first) {
     if (w->ctx->device != r->ctx->device) throw std::invalid_argument("r1cs: the witness lives on another device");
     if (first > w->n || w->n - first < r->hdr.nWires)
         throw std::invalid_argument("r1cs: the witness vector is shorter than first + n_wires (" + std::to_string(r->hdr.nWires) + " wires)");
-    return w->data + first * 8;
+    return w->data.get() + first * 8;
 }
 // the check of one witness queued on `stream`, its two result words on their way to pinned memory behind it
 void r1cs_queue(ug_r1cs* r, const u32* wtns, int slot, hipStream_t stream, uint8_t* mask_dev, bool timed) {
-    if (timed) UG_HIP(hipEventRecord(r->t0, stream));
-    r1cs_check(r->dev(), wtns, r->words + 2 * slot, mask_dev, stream);
-    if (timed) UG_HIP(hipEventRecord(r->t1, stream));
-    UG_HIP(hipMemcpyAsync(r->words_host + 2 * slot, r->words + 2 * slot, 16, hipMemcpyDeviceToHost, stream));
-    UG_HIP(hipEventRecord(r->done[slot], stream));
+    if (timed) UG_HIP(hipEventRecord(r->t0.e, stream));
+    r1cs_check(r->dev(), wtns, r->words.get() + 2 * slot, mask_dev, stream);
+    if (timed) UG_HIP(hipEventRecord(r->t1.e, stream));
+    UG_HIP(hipMemcpyAsync(r->words_host.get() + 2 * slot, r->words.get() + 2 * slot, 16, hipMemcpyDeviceToHost, stream));
+    UG_HIP(hipEventRecord(r->done[slot].e, stream));
     r->queued[slot].wtns = wtns; r->queued[slot].stream = stream; r->queued[slot].on = true;
 }
 // the slot's result; a failing witness costs a one-lane launch for the three values of its first failing constraint
@@ -1831,15 +1779,15 @@ void r1cs_read(ug_r1cs* r, int slot, ug_r1cs_report* out) {
     ug_r1cs::Queued& q = r->queued[slot];
     if (!q.on) throw std::invalid_argument("r1cs: no check is queued in slot " + std::to_string(slot));
     q.on = false;
-    UG_HIP(hipEventSynchronize(r->done[slot]));
+    UG_HIP(hipEventSynchronize(r->done[slot].e));
     memset(out, 0, sizeof *out);
-    out->failed = r->words_host[2 * slot];
+    out->failed = r->words_host.get()[2 * slot];
     if (!out->failed) return;
-    out->first = ~r->words_host[2 * slot + 1];
-    r1cs_row_values(r->dev(), q.wtns, (u32)out->first, r->row_values, q.stream);
-    UG_HIP(hipMemcpyAsync(r->row_values_host, r->row_values, 96, hipMemcpyDeviceToHost, q.stream));
+    out->first = ~r->words_host.get()[2 * slot + 1];
+    r1cs_row_values(r->dev(), q.wtns, (u32)out->first, r->row_values.get(), q.stream);
+    UG_HIP(hipMemcpyAsync(r->row_values_host.get(), r->row_values.get(), 96, hipMemcpyDeviceToHost, q.stream));
     UG_HIP(hipStreamSynchronize(q.stream));
-    memcpy(out->a, r->row_values_host, 32); memcpy(out->b, r->row_values_host + 8, 32); memcpy(out->c, r->row_values_host + 16, 32);
+    memcpy(out->a, r->row_values_host.get(), 32); memcpy(out->b, r->row_values_host.get() + 8, 32); memcpy(out->c, r->row_values_host.get() + 16, 32);
 }
 }  // namespace
 
@@ -1866,23 +1814,23 @@ int ug_r1cs_create(ug_ctx* c, const void* r1cs, uint64_t size, ug_r1cs** out) {
     for (int t = 0; t < 3; t++) {
         const size_t n = (size_t)host.terms[t];
         r->terms[t] = host.terms[t];
-        UG_HIP(hipMalloc(&r->row_ptr[t], (rows + 1) * 4));
-        UG_HIP(hipMalloc(&r->sig[t], n ? n * 4 : 4));
-        UG_HIP(hipMalloc(&r->val[t], n ? n * 32 : 32));
-        host_to_device(c, r->row_ptr[t], host.m[t].rowPtr.data(), (rows + 1) * 4);
-        host_to_device(c, r->sig[t], host.m[t].sig.data(), n * 4);
+        r->row_ptr[t].alloc(rows + 1);
+        r->sig[t].alloc(n);
+        r->val[t].alloc(n * 8);
+        host_to_device(c, r->row_ptr[t].get(), host.m[t].rowPtr.data(), (rows + 1) * 4);
+        host_to_device(c, r->sig[t].get(), host.m[t].sig.data(), n * 4);
         // (the conversion of a chunk's coefficients runs behind that chunk's copy, on the copy's stream)
-        u32* val = r->val[t];
+        u32* val = r->val[t].get();
         host_to_device(c, val, host.m[t].val.data(), n * 32,
                        [val](size_t off, size_t bytes, hipStream_t st) { r1cs_convert_coefs(val + off / 4, bytes / 32, st); });
     }
-    const size_t words = ((size_t)ug_r1cs::SLOTS * 2 + 1) * 8;
-    UG_HIP(hipMalloc(&r->words, words));
-    UG_HIP(hipHostMalloc((void**)&r->words_host, words, hipHostMallocDefault));
-    UG_HIP(hipMalloc(&r->row_values, 96));
-    UG_HIP(hipHostMalloc((void**)&r->row_values_host, 96, hipHostMallocDefault));
-    for (int k = 0; k < ug_r1cs::SLOTS; k++) UG_HIP(hipEventCreateWithFlags(&r->done[k], hipEventDisableTiming));
-    UG_HIP(hipEventCreate(&r->t0)); UG_HIP(hipEventCreate(&r->t1));
+    const size_t words = (size_t)ug_r1cs::SLOTS * 2 + 1;
+    r->words.alloc(words);
+    r->words_host.alloc(words);
+    r->row_values.alloc(24);
+    r->row_values_host.alloc(24);
+    for (int k = 0; k < ug_r1cs::SLOTS; k++) r->done[k] = Event(false);
+    r->t0 = Event(true); r->t1 = Event(true);
     UG_HIP(hipStreamSynchronize(c->stream));
     *out = r.release();
     UG_CATCH
@@ -1901,15 +1849,15 @@ int ug_r1cs_check(ug_r1cs* r, const ug_dvec* witness, uint64_t first, ug_r1cs_re
     if (c->recording) throw std::invalid_argument("r1cs: no check while the context's stream is being recorded");
     const u32* w = r1cs_witness(r, witness, first);
     const size_t rows = r->hdr.nConstraints;
-    struct Mask { uint8_t* p = nullptr; ~Mask() { if (p) hipFree(p); } } md;
-    if (mask && rows) UG_HIP(hipMalloc(&md.p, rows));
+    DevBuf<uint8_t> md;
+    if (mask && rows) md.alloc(rows);
     const int slot = ug_r1cs::SLOTS - 1;
-    r1cs_queue(r, w, slot, c->stream, md.p, /*timed*/ true);
-    if (md.p) UG_HIP(hipMemcpyAsync(mask, md.p, rows, hipMemcpyDeviceToHost, c->stream));
+    r1cs_queue(r, w, slot, c->stream, md.get(), /*timed*/ true);
+    if (md.get()) UG_HIP(hipMemcpyAsync(mask, md.get(), rows, hipMemcpyDeviceToHost, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));                    // the one host wait of a witness that holds
     r1cs_read(r, slot, out);
     float ms = 0;
-    UG_HIP(hipEventElapsedTime(&ms, r->t0, r->t1));
+    UG_HIP(hipEventElapsedTime(&ms, r->t0.e, r->t1.e));
     out->device_ms = ms;
     UG_CATCH
 }
@@ -1950,12 +1898,11 @@ int ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* 
     std::vector<uint8_t> z(n * 32);
     ughost::randomBytes(z.data(), z.size());
     for (size_t i = 0; i < n; i++) z[i * 32 + 31] &= 0x1f;      // below 2^253 < r
-    struct Dev { u32* p = nullptr; ~Dev() { if (p) hipFree(p); } } zd;
-    UG_HIP(hipMalloc(&zd.p, n * 32));
-    host_to_device(c, zd.p, z.data(), n * 32);
-    unsigned long long* word = r->words + 2 * ug_r1cs::SLOTS;
-    unsigned long long* word_host = r->words_host + 2 * ug_r1cs::SLOTS;
-    r1cs_match(r->dev(), hp->mat, n_public, zd.p, word, c->stream);
+    DevBuf<u32> zd(n * 8);
+    host_to_device(c, zd.get(), z.data(), n * 32);
+    unsigned long long* word = r->words.get() + 2 * ug_r1cs::SLOTS;
+    unsigned long long* word_host = r->words_host.get() + 2 * ug_r1cs::SLOTS;
+    r1cs_match(r->dev(), hp->mat, n_public, zd.get(), word, c->stream);
     UG_HIP(hipMemcpyAsync(word_host, word, 8, hipMemcpyDeviceToHost, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));
     if (*word_host == ~0ull) { *matrix = -1; *row = 0; }
@@ -1985,38 +1932,31 @@ static int r1cs_fold_call(ug_r1cs* r, const ug_dvec* rho, bool classes, const ug
     UG_HIP(hipStreamSynchronize(rho->ctx->stream));             // (the weights may have been queued on another context's stream)
     if (classes && cls->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(cls->ctx->stream));
     if (out->ctx != rho->ctx) UG_HIP(hipStreamSynchronize(out->ctx->stream));
-    UG_HIP(hipEventRecord(r->t0, c->stream));
+    UG_HIP(hipEventRecord(r->t0.e, c->stream));
     launch((u32)N);
-    UG_HIP(hipEventRecord(r->t1, c->stream));
+    UG_HIP(hipEventRecord(r->t1.e, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));
     float ms = 0;
-    UG_HIP(hipEventElapsedTime(&ms, r->t0, r->t1));
+    UG_HIP(hipEventElapsedTime(&ms, r->t0.e, r->t1.e));
     if (kernel_ms) *kernel_ms = ms;
     UG_CATCH
 }
 int ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32_t log_domain, ug_dvec* out, double* kernel_ms) {
     return r1cs_fold_call(r, rho, false, nullptr, n_public, log_domain, 8, out, kernel_ms, [&](u32 domain) {
-        r1cs_fold(r->dev(), rho->data, n_public, domain, out->data, r->ctx->stream);
+        r1cs_fold(r->dev(), rho->data.get(), n_public, domain, out->data.get(), r->ctx->stream);
     });
 }
 int ug_r1cs_fold_classes_dvec(ug_r1cs* r, const ug_dvec* rho, const ug_dvec* cls, uint32_t n_public, uint32_t log_domain, ug_dvec* out,
                               double* kernel_ms) {
     return r1cs_fold_call(r, rho, true, cls, n_public, log_domain, 11, out, kernel_ms, [&](u32 domain) {
-        r1cs_fold_classes(r->dev(), rho->data, reinterpret_cast<const uint8_t*>(cls->data), n_public, domain, out->data, r->ctx->stream);
+        r1cs_fold_classes(r->dev(), rho->data.get(), reinterpret_cast<const uint8_t*>(cls->data.get()), n_public, domain, out->data.get(), r->ctx->stream);
     });
 }
 void ug_r1cs_destroy(ug_r1cs* r) {
     if (!r) return;
     hipSetDevice(r->ctx->device);
     for (int k = 0; k < ug_r1cs::SLOTS; k++)                    // a check that was queued and never collected may still be running
-        if (r->queued[k].on) hipEventSynchronize(r->done[k]);
-    for (int t = 0; t < 3; t++) { hipFree(r->row_ptr[t]); hipFree(r->sig[t]); hipFree(r->val[t]); }
-    hipFree(r->words); hipFree(r->row_values);
-    if (r->words_host) hipHostFree(r->words_host);
-    if (r->row_values_host) hipHostFree(r->row_values_host);
-    for (int k = 0; k < ug_r1cs::SLOTS; k++) if (r->done[k]) hipEventDestroy(r->done[k]);
-    if (r->t0) hipEventDestroy(r->t0);
-    if (r->t1) hipEventDestroy(r->t1);
+        if (r->queued[k].on) hipEventSynchronize(r->done[k].e);
     delete r;
 }
 
@@ -2027,16 +1967,15 @@ int ug_fr_ntt(ug_ctx* c, void* host_data, int logn, int inverse) {
     c->use();
     if (c->raw_ntt.logn != logn) c->raw_ntt.init(logn, c->stream);
     size_t bytes = ((size_t)1 << logn) * 32;
-    u32 *x = nullptr, *y = nullptr;
-    UG_HIP(hipMalloc(&x, bytes)); UG_HIP(hipMalloc(&y, bytes));
+    DevBuf<u32> x_own(bytes / 4), y_own(bytes / 4);
+    u32 *const x = x_own.get(), *const y = y_own.get();
     UG_HIP(hipMemcpyAsync(x, host_data, bytes, hipMemcpyHostToDevice, c->stream));
     fr_from_mont256(x, x, (u64)1 << logn, c->stream);
     if (logn == 0) UG_HIP(hipMemcpyAsync(y, x, bytes, hipMemcpyDeviceToDevice, c->stream));
-    else c->raw_ntt.transform(y, x, inverse != 0, /*gather_bitrev*/ true, false, nullptr, inverse ? c->raw_ntt.ninv : nullptr, c->stream);
+    else c->raw_ntt.transform(y, x, inverse != 0, /*gather_bitrev*/ true, false, nullptr, inverse ? c->raw_ntt.ninv.get() : nullptr, c->stream);
     fr_to_mont256(y, y, (u64)1 << logn, c->stream);
     UG_HIP(hipMemcpyAsync(host_data, y, bytes, hipMemcpyDeviceToHost, c->stream));
     UG_HIP(hipStreamSynchronize(c->stream));
-    hipFree(x); hipFree(y);
     UG_CATCH
 }
 
@@ -2047,8 +1986,8 @@ int ug_field_op(ug_ctx* c, int field, int op, void* out, const void* a, const vo
     if (op < 0 || op > 3) throw std::invalid_argument("unknown op");
     c->use();
     size_t bytes = (size_t)n * 32;
-    u32 *da = nullptr, *db = nullptr, *dout = nullptr;
-    UG_HIP(hipMalloc(&da, bytes ? bytes : 4)); UG_HIP(hipMalloc(&db, bytes ? bytes : 4)); UG_HIP(hipMalloc(&dout, bytes ? bytes : 4));
+    DevBuf<u32> da_own(bytes / 4), db_own(bytes / 4), dout_own(bytes / 4);
+    u32 *const da = da_own.get(), *const db = db_own.get(), *const dout = dout_own.get();
     if (n) {
         UG_HIP(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, c->stream));
         UG_HIP(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, c->stream));
@@ -2056,7 +1995,6 @@ int ug_field_op(ug_ctx* c, int field, int op, void* out, const void* a, const vo
         UG_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     UG_HIP(hipStreamSynchronize(c->stream));
-    hipFree(da); hipFree(db); hipFree(dout);
     UG_CATCH
 }
 
@@ -2068,14 +2006,13 @@ int ug_synth_points(ug_ctx* c, int g2, const void* generator_record, uint64_t se
     u32 gen[32];
     memcpy(gen, generator_record, rec);
     const u64 CH = (u64)1 << 22;                       // stage through a bounded device buffer
-    u32* dev = nullptr;
-    UG_HIP(hipMalloc(&dev, (size_t)(n < CH ? (n ? n : 1) : CH) * rec));
+    DevBuf<u32> dev_own((size_t)(n < CH ? (n ? n : 1) : CH) * (rec / 4));
+    u32* const dev = dev_own.get();
     for (u64 done = 0; done < n; done += CH) {
         u64 m = n - done < CH ? n - done : CH;
         synth_points(g2 != 0, dev, gen, seed + done, m, c->stream);
         UG_HIP(hipMemcpy((uint8_t*)host_out + done * rec, dev, (size_t)m * rec, hipMemcpyDeviceToHost));
     }
-    hipFree(dev);
     UG_CATCH
 }
 
