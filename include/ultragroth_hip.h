@@ -777,6 +777,94 @@ int  ug_r1cs_fold_dvec(ug_r1cs* r, const ug_dvec* rho, uint32_t n_public, uint32
 int  ug_bases_create_every_g1(ug_ctx* ctx, const void* host_points, uint64_t n_records, uint64_t first, uint64_t step, uint64_t global_first,
                               ug_bases** out);
 
+/* NAMING THE WRONG RECORDS OF A FAILING SECTION (zkey_verify_host.cpp; setup_points.hip: ratio_block_sums_kernel; pairing.hip:
+ * ratio_judge_kernel). ug_zkey_verify_run answers "invalid: sections 8, 9" and nothing finer.
+ * ug_zkey_locate_run / ug_ultra_zkey_locate_run sit BESIDE the two verify entries, which keep their signatures, struct sizes,
+ * refusals, messages and verdicts: on the same files they give the same return code, ug_zkey_verify_report and error_msg
+ * (first_failed and the first failing relation's message included), and in addition a ug_zkey_locate_report with one entry per
+ * failing POINT section -- 3, 5, 6, 7, each C section and H -- in that order. Locating starts after the verdict is known: a valid key,
+ * or one whose only failures are sections 2, 4, 10 or 11, costs nothing extra and reports n_sections = 0. Section 4 already names its
+ * record and the header has no records: neither gets an entry. Expected records are made only for sections that failed, one
+ * section at a time (made, tested, freed).
+ *   sections 5, 6, 7       method UG_LOCATE_BYTES: the expected records are the combination of the circuit's columns over T and T2
+ *                          (ug_points_combine's), canonical, so a byte comparison names every wrong record: exact = 1 always,
+ *                          bad_records the full count, bad_blocks = resolved_blocks = the blocks that hold one.
+ *   section 3, C sections  method UG_LOCATE_RATIO: record X_s against K_s = the combination over (bT, aT, T) through A, B, C, with
+ *                          e(X_s, Q) = e(K_s, G2); Q = the key's gamma2 for section 3 (ug_setup_run's keys have any gamma), the
+ *                          section's delta (G2 part) for a C section.
+ *   H (9, or 12)           method UG_LOCATE_RATIO: H_i against the odd record 2 i + 1 of P, Q = the last delta.
+ * A ratio section whose Q is the point at infinity (a header failure) gets no entry.
+ * An index is the record's place IN ITS SECTION: for section 3, 5, 6, 7 the wire; for a Groth16 key's section 8 record i is wire
+ * nPublic + 1 + i; for an UltraGroth key's section 8 record i is wire round_signals[i] (section 10), for its section 9 wire
+ * final_signals[i] (section 11); for H the row.
+ *
+ * The ratio test (ug_points_ratio_mask is the test tooling for it alone, device >= 0 or -1, messages prefixed "setup: "): given n
+ * pairs (X_i, Y_i) of G1 records that passed the point check (all-zero = infinity) and a G2 record Q, not infinity and in the
+ * subgroup, it finds every i with e(X_i, Q) != e(Y_i, G2). Both infinity holds, exactly one is wrong. Two levels:
+ *   blocks    256 consecutive records (the last may be short); one weight below 2^128 per record from getrandom, fresh in every call
+ *             and never derived from the inputs; block j HOLDS when e(sum w_i X_i, Q) = e(sum w_i Y_i, G2). A block with a wrong
+ *             record holds with probability at most 2^-128 (the argument of ug_zkey_verify_run's relations).
+ *   records   only the first max_blocks FAILING blocks are resolved, in index order (0: the default, 64 -- 16 384 records in one
+ *             launch): each of their records by its own two pairings, no weights: exact.
+ * exact = 1: every failing block was resolved and bad_records is the total. exact = 0: more blocks fail than were resolved;
+ * bad_records counts the resolved ones only -- when every resolved block fails in every record, the section belongs to another
+ * delta or tau, not to a few bad records. device = -1 runs both levels on host threads and gives the same answers.
+ * ug_points_ratio_mask: record_mask (capacity n bytes) receives one byte per record of the resolved blocks, block after block
+ * (resolved_records of them; 1 = wrong), block_mask one byte per block (1 = the block fails). */
+#define UG_RATIO_LISTED 16
+typedef struct {
+    uint64_t blocks, bad_blocks, resolved_blocks;
+    uint64_t bad_records;               /* over the resolved blocks; the total when exact */
+    uint64_t resolved_records;          /* bytes written to record_mask */
+    uint32_t exact;
+    uint32_t n_listed;                  /* the first wrong records, ascending: at most UG_RATIO_LISTED */
+    uint64_t index[UG_RATIO_LISTED];
+    double   kernel_ms[2];              /* ratio_block_sums_kernel; ratio_judge_kernel over both levels (host threads: wall time) */
+} ug_ratio_report;
+int  ug_points_ratio_mask(int device, const void* x, const void* y, uint64_t n, const void* q, uint64_t max_blocks, void* record_mask,
+                          void* block_mask, ug_ratio_report* out, char* error_msg, unsigned long long error_msg_maxsize);
+
+#define UG_LOCATE_BYTES 0
+#define UG_LOCATE_RATIO 1
+#define UG_ZKEY_LOCATE_SECTIONS 7       /* 3, 5, 6, 7, 8, 9 and, for an UltraGroth key, 12 */
+#define UG_ZKEY_LOCATE_LISTED 1024      /* the largest max_listed */
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_zkey_locate_options) */
+    uint32_t validate;                  /* as ug_zkey_verify_options.validate */
+    uint32_t max_listed;                /* wrong records listed per section; 0: 16; above UG_ZKEY_LOCATE_LISTED: refused */
+    uint32_t max_blocks;                /* failing blocks resolved per ratio section; 0: 64 */
+} ug_zkey_locate_options;
+typedef struct {
+    uint32_t size;                      /* sizeof(ug_ultra_zkey_locate_options) */
+    uint32_t validate, check_spec, rand_indx;                       /* as ug_ultra_zkey_verify_options */
+    const uint32_t* round_signals; uint64_t n_round;
+    const uint32_t* final_signals; uint64_t n_final;
+    uint32_t max_listed, max_blocks;    /* as ug_zkey_locate_options */
+} ug_ultra_zkey_locate_options;
+typedef struct {
+    uint32_t section;                   /* the section's id */
+    uint32_t method;                    /* UG_LOCATE_BYTES | UG_LOCATE_RATIO */
+    uint64_t records;                   /* records of the section */
+    uint64_t blocks, bad_blocks, resolved_blocks, bad_records;
+    uint32_t exact;
+    uint32_t n_listed;                  /* entries of index[]: the first max_listed wrong records, ascending */
+    double   kernel_ms[2];              /* as ug_ratio_report (0 for UG_LOCATE_BYTES) */
+    uint64_t index[UG_ZKEY_LOCATE_LISTED];
+} ug_zkey_locate_section;
+typedef struct {
+    uint32_t n_sections;                /* entries of section[], in the order 3, 5, 6, 7, the C sections, H */
+    uint32_t reserved;
+    double   locate_ms;                 /* everything after the verdict (0 when nothing had to be located) */
+    ug_zkey_locate_section section[UG_ZKEY_LOCATE_SECTIONS];
+} ug_zkey_locate_report;
+/* out, phase_ms, error_msg: exactly ug_zkey_verify_run's / ug_ultra_zkey_verify_run's. located (may not be NULL) is zeroed by a refusal. */
+int  ug_zkey_locate_run(const ug_zkey_locate_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
+                        const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out, ug_zkey_locate_report* located,
+                        double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize);
+int  ug_ultra_zkey_locate_run(const ug_ultra_zkey_locate_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                              uint64_t ptau_size, const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out,
+                              ug_zkey_locate_report* located, double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize);
+
 /* PREPARING A POWERS-OF-TAU FILE FOR PHASE 2: sections 2 - 5 -> sections 12 - 15 (ptau_prepare.cpp, ptau_prepare.hip; what
  * `snarkjs powersoftau prepare phase2` does), and the check that a file's sections 12 - 15 ARE the Lagrange forms of its sections
  * 2 - 5, which ug_setup_ptau_run takes on trust. The layout is the one restated above, AS REMEMBERED of snarkjs' format: NO FILE OF

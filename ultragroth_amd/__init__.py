@@ -439,6 +439,37 @@ def points_scale(scalar, points, device=0, timing=None):
     return [out.raw[64 * i:64 * i + 64] for i in range(len(points))]
 
 
+UG_RATIO_LISTED = 16
+
+
+class _RatioReport(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("bad_blocks", C.c_uint64), ("resolved_blocks", C.c_uint64), ("bad_records", C.c_uint64),
+                ("resolved_records", C.c_uint64), ("exact", C.c_uint32), ("n_listed", C.c_uint32), ("index", C.c_uint64 * UG_RATIO_LISTED),
+                ("kernel_ms", C.c_double * 2)]
+
+
+def points_ratio_mask(x, y, q, device=0, max_blocks=0, timing=None):
+    """ug_points_ratio_mask (test tooling): the ratio test alone. x, y: G1 records (64 bytes, all-zero is infinity) that passed the
+    point check; q: a G2 record (128 bytes), not infinity, in the subgroup. Which i have e(x_i, q) != e(y_i, G2)? Blocks of 256
+    records under fresh 128-bit weights first, then every record of the first max_blocks failing blocks (0: 64) by its own
+    pairings. Returns (record_mask, block_mask, report): one byte per record of the resolved blocks, block after block (1 =
+    wrong), one byte per block (1 = fails), and {"blocks", "bad_blocks", "resolved_blocks", "exact", "bad_records", "index"}:
+    index the first 16 wrong records, ascending. device=-1: host threads, the same answers. timing: a list that receives
+    (block-sums ms, pairings ms)."""
+    if len(x) != len(y):
+        raise SetupError("setup: x and y differ in length")
+    n = len(x)
+    xs, ys, qs = _joined(x, 64), _joined(y, 64), _joined([q], 128)
+    rec_mask, blk_mask = C.create_string_buffer(max(1, n)), C.create_string_buffer(max(1, (n + 255) // 256))
+    rep = _RatioReport()
+    _setup_call(load().ug_points_ratio_mask, device, xs, ys, n, qs, int(max_blocks), rec_mask, blk_mask, C.byref(rep))
+    if timing is not None:
+        timing.append((rep.kernel_ms[0], rep.kernel_ms[1]))
+    report = {"blocks": rep.blocks, "bad_blocks": rep.bad_blocks, "resolved_blocks": rep.resolved_blocks, "exact": rep.exact,
+              "bad_records": rep.bad_records, "index": [rep.index[i] for i in range(rep.n_listed)]}
+    return rec_mask.raw[:rep.resolved_records], blk_mask.raw[:rep.blocks], report
+
+
 class _UltraSetupPtauOptions(C.Structure):
     _fields_ = [("size", C.c_uint32), ("log_domain", C.c_uint32), ("validate", C.c_uint32), ("contribute", C.c_uint32),
                 ("delta_round", C.c_ubyte * 32), ("delta_final", C.c_ubyte * 32), ("rand_indx", C.c_uint32), ("reserved", C.c_uint32),
@@ -696,6 +727,77 @@ def ultra_zkey_verify(r1cs, ptau, zkey, ultra=None, device=0, validate=2, timing
         opt.check_spec = 1
         keep = _ultra_lists(opt, ultra, "zkey: ")
     res = _zkey_verify_call(load().ug_ultra_zkey_verify_run, opt, 12, r1cs, ptau, zkey, device, timings)
+    del keep
+    return res
+
+
+# naming the wrong records of a failing section (include/ultragroth_hip.h: ug_zkey_locate_run, ug_ultra_zkey_locate_run)
+UG_ZKEY_LOCATE_SECTIONS, UG_ZKEY_LOCATE_LISTED = 7, 1024
+LOCATE_METHODS = ("bytes", "ratio")
+
+
+class _ZkeyLocateOptions(C.Structure):
+    _fields_ = _ZkeyVerifyOptions._fields_ + [("max_listed", C.c_uint32), ("max_blocks", C.c_uint32)]
+
+
+class _UltraZkeyLocateOptions(C.Structure):
+    _fields_ = _UltraZkeyVerifyOptions._fields_ + [("max_listed", C.c_uint32), ("max_blocks", C.c_uint32)]
+
+
+class _ZkeyLocateSection(C.Structure):
+    _fields_ = [("section", C.c_uint32), ("method", C.c_uint32), ("records", C.c_uint64), ("blocks", C.c_uint64), ("bad_blocks", C.c_uint64),
+                ("resolved_blocks", C.c_uint64), ("bad_records", C.c_uint64), ("exact", C.c_uint32), ("n_listed", C.c_uint32),
+                ("kernel_ms", C.c_double * 2), ("index", C.c_uint64 * UG_ZKEY_LOCATE_LISTED)]
+
+
+class _ZkeyLocateReport(C.Structure):
+    _fields_ = [("n_sections", C.c_uint32), ("reserved", C.c_uint32), ("locate_ms", C.c_double),
+                ("section", _ZkeyLocateSection * UG_ZKEY_LOCATE_SECTIONS)]
+
+
+def _zkey_locate_call(entry, opt, last_section, r1cs, ptau, zkey, device, max_listed, max_blocks, timings):
+    """one locate call: the verify call's answer with the located dict behind it"""
+    for name, value in (("max_listed", max_listed), ("max_blocks", max_blocks)):
+        if not 0 <= int(value) < 1 << 32:
+            raise SetupError("zkey: %s %d is not below 2^32" % (name, value))
+        setattr(opt, name, int(value))
+    located = _ZkeyLocateReport()
+    res = _zkey_verify_call(lambda *a: entry(*a[:9], C.byref(located), *a[9:]), opt, last_section, r1cs, ptau, zkey, device, timings)
+    if timings is not None:
+        timings.update(locate=located.locate_ms)
+    if res is None:
+        return None
+    out = {}
+    for e in located.section[:located.n_sections]:
+        out[e.section] = {"records": e.records, "method": LOCATE_METHODS[e.method], "blocks": e.blocks, "bad_blocks": e.bad_blocks,
+                          "resolved_blocks": e.resolved_blocks, "exact": e.exact, "bad_records": e.bad_records,
+                          "index": [e.index[i] for i in range(e.n_listed)], "kernel_ms": (e.kernel_ms[0], e.kernel_ms[1])}
+    return res + (out,)
+
+
+def zkey_locate(r1cs, ptau, zkey, device=0, validate=2, max_listed=16, max_blocks=0, timings=None):
+    """ug_zkey_locate_run: zkey_verify's answer, and WHICH RECORDS of every failing point section are wrong. None for a valid key;
+    otherwise (first_section, failed_sections, message, located): the first three are zkey_verify's on the same files, located is
+    a dict keyed by section -- 3, 5, 6, 7, 8, 9 where they fail -- of {"records", "method", "blocks", "bad_blocks",
+    "resolved_blocks", "exact", "bad_records", "index", "kernel_ms"}. method "bytes" (5, 6, 7): the expected records were made and
+    compared, the answer is complete. method "ratio" (3, 8, 9): blocks of 256 records are tested under fresh random weights, then
+    every record of the first max_blocks failing blocks (0: 64) by its own pairings; exact = 0 says that more blocks fail than
+    were resolved, and bad_records then counts the resolved ones only. index: the first max_listed wrong records, ascending, as
+    places in the section (section 8: wire nPublic + 1 + i). A valid key costs what zkey_verify costs. timings also receives
+    "locate", the milliseconds after the verdict."""
+    return _zkey_locate_call(load().ug_zkey_locate_run, _zkey_verify_options(_ZkeyLocateOptions, validate), 9, r1cs, ptau, zkey, device,
+                             max_listed, max_blocks, timings)
+
+
+def ultra_zkey_locate(r1cs, ptau, zkey, ultra=None, device=0, validate=2, max_listed=16, max_blocks=0, timings=None):
+    """ug_ultra_zkey_locate_run: ultra_zkey_verify's answer with zkey_locate's located dict, sections 3, 5, 6, 7, 8, 9 and 12. An
+    index of section 8 is a place in the key's round list (record i is wire round_signals[i]), of section 9 in its final list."""
+    opt = _zkey_verify_options(_UltraZkeyLocateOptions, validate)
+    keep = []
+    if ultra is not None:
+        opt.check_spec = 1
+        keep = _ultra_lists(opt, ultra, "zkey: ")
+    res = _zkey_locate_call(load().ug_ultra_zkey_locate_run, opt, 12, r1cs, ptau, zkey, device, max_listed, max_blocks, timings)
     del keep
     return res
 

@@ -40,6 +40,7 @@ INNER_SYMBOLS = [
     "ug_ultra_zkey_verify_run", "ug_r1cs_fold_classes", "ug_r1cs_fold_classes_dvec",
     "ug_ptau_prepare_size", "ug_ptau_prepare_run", "ug_points_intt",
     "ug_zkey_verify_run", "ug_r1cs_fold", "ug_r1cs_fold_dvec", "ug_bases_create_every_g1",
+    "ug_points_ratio_mask", "ug_zkey_locate_run", "ug_ultra_zkey_locate_run",
     "ug_lookup_vectors_bytes", "ug_points_check", "ug_points_check_mask", "ug_ctx_check_points", "ug_ctx_last_point_fault", "ug_point_reason_text",
 ]
 VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/verifier.h
@@ -257,6 +258,9 @@ def load():
     L.ug_points_intt.argtypes = [C.c_int, C.c_int, C.c_int, vp, u64, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_zkey_verify_run.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.c_int, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_r1cs_fold.argtypes = [vp, u64, vp, u32, C.c_int, vp, C.POINTER(C.c_double), vp, ull]
+    L.ug_points_ratio_mask.argtypes = [C.c_int, vp, vp, u64, vp, u64, vp, vp, vp, vp, ull]
+    L.ug_zkey_locate_run.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.c_int, vp, vp, C.POINTER(C.c_double), vp, ull]
+    L.ug_ultra_zkey_locate_run.argtypes = L.ug_zkey_locate_run.argtypes
     L.ug_ultra_zkey_verify_run.argtypes = L.ug_zkey_verify_run.argtypes
     L.ug_r1cs_fold_classes.argtypes = [vp, u64, vp, vp, u32, C.c_int, vp, C.POINTER(C.c_double), vp, ull]
     L.ug_r1cs_fold_classes_dvec.argtypes = [vp, vp, vp, u32, u32, vp, C.POINTER(C.c_double)]

@@ -10,6 +10,8 @@
 //                       partial sums in LDS) and leaves -vkX_i as an affine G1 record.
 // judge_kernel          lane i: suspect i's own equation -- the Miller loops of its three (four) pairs times miller(beta, -alpha),
 //                       the final exponentiation's is-one test, one verdict word. No random scalar: the single verifier's answer.
+// ratio_judge_kernel    lane i: e(x_i, Q) = e(y_i, G2) for two G1 records of a key -- two Miller loops, the is-one test, one word
+//                       (the ratio test of Backend::ratio).
 // final_exp_kernel      one lane of the final exponentiation alone (ug_test_final_exp).
 // records_ingest_kernel the packed records of ug_*_verify_batch_records -> the arrays above, one record per lane: reduction mod q,
 // gather_rows_kernel    infinity flags, curve equations, limb form; the gather compacts the arrays when records were dropped.
@@ -97,6 +99,15 @@ __global__ UG_ONE_WAVE void judge_kernel(FinalExpConsts kc, const u32* __restric
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n) return;
     verdict[i] = judge_proof(kc, a + i * G1_WORDS, b + i * G2_WORDS, neg_vkx + i * G1_WORDS, g + i * k * G1_WORDS, k, key_g2, f_ab) ? 1u : 0u;
+}
+
+// The ratio test (Backend::ratio): lane i says whether e(x_i, Q) = e(y_i, G2) for two zkey-format G1 records, which it converts
+// itself; q2 = Q, then the generator of G2. Both levels of the test -- the block sums and the records -- go through this kernel.
+__global__ UG_ONE_WAVE void ratio_judge_kernel(FinalExpConsts kc, const u32* __restrict__ x, const u32* __restrict__ y, const u32* __restrict__ q2,
+                                               int n, u32* __restrict__ wrong) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    wrong[i] = ratio_holds(kc, x + i * 16, y + i * 16, q2) ? 0u : 1u;
 }
 
 __global__ UG_ONE_WAVE void final_exp_kernel(FinalExpConsts kc, const u32* __restrict__ f_in, u32* __restrict__ g_out, u32* __restrict__ is_one) {
@@ -390,6 +401,35 @@ void pairing_judge_device(int device, const FinalExpConsts& kc, PairingJudge& pj
     UG_HIP(hipEventElapsedTime(&ms[0], t0.e, t1.e));
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
     for (int i = 0; i < 2; i++) pj.kernel_ms[i] = ms[i];
+}
+
+// The pairings of the ratio test (setup_host.hpp: Backend::ratio; pairing.hpp: ratio_holds), one lane per pair: wrong[i] = 1 unless
+// e(x_i, Q) = e(y_i, G2). x, y: n zkey-format G1 records on the host; q2: Q, then the generator of G2, G2_WORDS each. On the caller's
+// stream and current device, which it waits for; n is cut into launches of PAIRING_PASS lanes. kernel_ms (may be null): the kernel's time.
+void ratio_judge_device(hipStream_t stream, const FinalExpConsts& kc, const uint8_t* x, const uint8_t* y, u64 n, const u32* q2, uint8_t* wrong,
+                        double* kernel_ms) {
+    if (kernel_ms) *kernel_ms = 0;
+    if (!n) return;
+    const size_t pass = std::min<u64>(n, PAIRING_PASS);
+    DevBuf<u32> dx(pass * 16), dy(pass * 16), dq(2 * G2_WORDS), dw(pass);
+    std::vector<u32> w(pass);
+    Event t0(true), t1(true);
+    UG_HIP(hipMemcpyAsync(dq.get(), q2, 2 * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice, stream));
+    for (u64 first = 0; first < n; first += pass) {
+        const size_t m = (size_t)std::min<u64>(pass, n - first);
+        UG_HIP(hipMemcpyAsync(dx.get(), x + first * 64, m * 64, hipMemcpyHostToDevice, stream));
+        UG_HIP(hipMemcpyAsync(dy.get(), y + first * 64, m * 64, hipMemcpyHostToDevice, stream));
+        UG_HIP(hipEventRecord(t0.e, stream));
+        hipLaunchKernelGGL(ratio_judge_kernel, dim3(blocks(m)), dim3(64), 0, stream, kc, dx.get(), dy.get(), dq.get(), (int)m, dw.get());
+        UG_KERNEL_CHECK();
+        UG_HIP(hipEventRecord(t1.e, stream));
+        UG_HIP(hipMemcpyAsync(w.data(), dw.get(), m * sizeof(u32), hipMemcpyDeviceToHost, stream));
+        UG_HIP(hipStreamSynchronize(stream));
+        float ms = 0;
+        UG_HIP(hipEventElapsedTime(&ms, t0.e, t1.e));
+        if (kernel_ms) *kernel_ms += ms;
+        for (size_t i = 0; i < m; i++) wrong[first + i] = w[i] ? 1 : 0;
+    }
 }
 
 void fq2_sqrt_device(int device, const DecompressConsts& c, int count, const u32* in, u32* out, unsigned char* has_root) {

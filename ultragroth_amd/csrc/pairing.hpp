@@ -411,6 +411,30 @@ UG_HD bool judge_proof(const FinalExpConsts& kc, const u32* a, const u32* b, con
     return final_exp_is_one(kc, acc, hard);
 }
 
+// ---- the ratio test of two G1 records (setup_host.hpp: Backend::ratio; pairing.hip: ratio_judge_kernel) ------------------
+// A point of a zkey-format record: coordinates in Montgomery form with radix 2^256, 8 words each, all zero = infinity
+UG_HD F1 record_coord(const u32* w) { return F1{cond_sub_q(from_mont256<FqParams>(w))}; }
+UG_HD G1A g1_from_record(const u32* rec, bool negate) {
+    if (words_all_zero(rec, 16)) return G1A{f1_zero(), f1_zero(), true};
+    const F1 y = record_coord(rec + 8);
+    return G1A{record_coord(rec), negate ? -y : y, false};
+}
+UG_HD G2A g2_from_record(const u32* rec) {
+    if (words_all_zero(rec, 32)) return g2_inf();
+    return G2A{F2{record_coord(rec), record_coord(rec + 8)}, F2{record_coord(rec + 16), record_coord(rec + 24)}, false};
+}
+// e(X, Q) e(-Y, G2) == 1 for the records x and y; q2: Q, then the generator of G2, G2_WORDS each, neither infinity. Both
+// records infinity: holds; exactly one: does not, without a pairing. No random scalar: the answer is exact.
+UG_HD bool ratio_holds(const FinalExpConsts& kc, const u32* x, const u32* y, const u32* q2) {
+    if (words_all_zero(x, 16) || words_all_zero(y, 16)) return words_all_zero(x, 16) && words_all_zero(y, 16);
+    F12 acc = f12_one();
+#pragma unroll 1
+    for (int s = 0; s < 2; s++)                                     // (one copy of the Miller loop, as in judge_proof)
+        acc = f12_mul(kc, acc, miller(kc, g2_load(q2 + s * G2_WORDS), g1_from_record(s ? y : x, s == 1)));
+    F12 hard;
+    return final_exp_is_one(kc, acc, hard);
+}
+
 // a node of the product tree: the product of its two children, or the left one alone (right == nullptr: an odd last node)
 UG_HD void f12_node(const PairingConsts& kc, const u32* left, const u32* right, u32* out) {
     F12 x;

@@ -25,6 +25,11 @@ void device_points_combine(hipStream_t stream, StreamTimer& timer, bool g2, u64 
                            const uint8_t* coefs, const ughost::setup::PointSegs& pts, uint8_t* out, double* ms);
 void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* scalar, const uint8_t* points, u64 n, uint8_t* out, double* ms);
 void device_points_scale_segments(hipStream_t stream, StreamTimer& timer, const ughost::setup::ScaleSeg* segs, int n, double* ms);
+void device_points_ratio_sums(hipStream_t stream, StreamTimer& timer, const uint8_t* x, const uint8_t* y, u64 n, const uint8_t* weights,
+                              uint8_t* sumX, uint8_t* sumY, double* ms);
+// pairing.hip
+void ratio_judge_device(hipStream_t stream, const pr::FinalExpConsts& kc, const uint8_t* x, const uint8_t* y, u64 n, const u32* q2, uint8_t* wrong,
+                        double* kernel_ms);
 // ptau_prepare.hip
 void device_points_intt(hipStream_t stream, StreamTimer& timer, bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven,
                         uint8_t* const* out, double* ms);
@@ -380,6 +385,15 @@ public:
         device_points_scale(stream_, timer_, scalar, points, n, out, ms);
     }
     void scaleSegments(const ScaleSeg* segs, int n, double* ms) override { device_points_scale_segments(stream_, timer_, segs, n, ms); }
+    // (the ratio test: ratio_block_sums_kernel of setup_points.hip, then ratio_judge_kernel of pairing.hip for both levels)
+    void ratio(const uint8_t* x, const uint8_t* y, u64 n, const uint8_t* q, u64 maxBlocks, RatioOut& out) override {
+        if (n > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+        u32 q2[RATIO_Q2_WORDS];
+        ratioG2Words(q, q2);
+        ratioLevels(x, y, n, maxBlocks, out,
+                    [&](const uint8_t* w, uint8_t* sx, uint8_t* sy, double* ms) { device_points_ratio_sums(stream_, timer_, x, y, n, w, sx, sy, ms); },
+                    [&](const uint8_t* px, const uint8_t* py, u64 m, uint8_t* wrong, double* ms) { ratio_judge_device(stream_, ratioConsts(), px, py, m, q2, wrong, ms); });
+    }
     // (the inverse transform over points that prepares a .ptau: ptau_prepare.hip)
     void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) override {
         device_points_intt(stream_, timer_, g2, logN, nVec, in, nGiven, out, ms);

@@ -4,6 +4,7 @@
 //
 // The specification is tests/golden/make_trapdoor_fixtures.py; the file layout follows it byte for byte.
 #include "setup_host.hpp"
+#include "pairing.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -473,6 +474,41 @@ public:
         hostScaleSegments(segs, n);
         if (ms) ms[0] = nowMs() - t0;
     }
+    // the block sums are a combination with one column per block; the pairings are pairing.hpp's on host threads
+    void ratio(const uint8_t* x, const uint8_t* y, u64 n, const uint8_t* q, u64 maxBlocks, RatioOut& out) override {
+        if (n > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+        u32 q2[RATIO_Q2_WORDS];
+        ratioG2Words(q, q2);
+        const pr::FinalExpConsts& kc = ratioConsts();
+        ratioLevels(x, y, n, maxBlocks, out,
+                    [&](const uint8_t* w, uint8_t* sx, uint8_t* sy, double* ms) {
+                        const double t0 = nowMs();
+                        const u64 blocks = (n + RATIO_BLOCK - 1) / RATIO_BLOCK;
+                        std::vector<u32> colPtr((size_t)blocks + 1), index((size_t)n);
+                        std::vector<uint8_t> coefs((size_t)n * 32, 0);
+                        for (u64 j = 0; j <= blocks; j++) colPtr[(size_t)j] = (u32)std::min(n, j * RATIO_BLOCK);
+                        for (u64 i = 0; i < n; i++) { index[(size_t)i] = (u32)i; memcpy(&coefs[(size_t)i * 32], w + i * 16, 16); }
+                        PointSegs p;
+                        p.count = n; p.n = 1;
+                        p.base[0] = x;
+                        hostCombine<Fq>(blocks, colPtr.data(), index.data(), coefs.data(), p, sx);
+                        p.base[0] = y;
+                        hostCombine<Fq>(blocks, colPtr.data(), index.data(), coefs.data(), p, sy);
+                        *ms = nowMs() - t0;
+                    },
+                    [&](const uint8_t* px, const uint8_t* py, u64 m, uint8_t* wrong, double* ms) {
+                        const double t0 = nowMs();
+                        parallelFor(m, 4, [&](u64 lo, u64 hi) {
+                            for (u64 i = lo; i < hi; i++) {
+                                u32 rx[16], ry[16];      // (a file's records sit at any alignment)
+                                memcpy(rx, px + i * 64, 64);
+                                memcpy(ry, py + i * 64, 64);
+                                wrong[i] = pr::ratio_holds(kc, rx, ry, q2) ? 0 : 1;
+                            }
+                        });
+                        *ms = nowMs() - t0;
+                    });
+    }
     void intt(bool g2, int logN, int nVec, const uint8_t* const* in, u64 nGiven, uint8_t* const* out, double* ms) override {
         const double t0 = nowMs();
         if (!inttTrivial(g2, logN, nVec, in, nGiven, out)) {
@@ -822,6 +858,72 @@ void drawNonZeroScalar(uint8_t le[32]) {
         randomBytes(le, 32);
         le[31] &= 0x3f;
     } while (allZero(le, 32) || !belowR(le));
+}
+
+// ---- the ratio test: what both backends share ----
+void drawWeights128(std::vector<uint8_t>& out, u64 n) {
+    out.assign((size_t)n * 16, 0);
+    parallelFor(n, 1 << 16, [&](u64 lo, u64 hi) { randomBytes(&out[(size_t)lo * 16], (size_t)(hi - lo) * 16); });
+}
+
+const pr::FinalExpConsts& ratioConsts() {
+    static const pr::FinalExpConsts c = pr::final_exp_consts();
+    return c;
+}
+
+void ratioG2Words(const uint8_t* q, u32 out[RATIO_Q2_WORDS]) {
+    u32 rec[32], gen[32];
+    memcpy(rec, q, 128);
+    generatorWords(true, gen);
+    const pr::G2A pt = pr::g2_from_record(rec);
+    const Fq c[8] = {pt.x.a.v, pt.x.b.v, pt.y.a.v, pt.y.b.v, cond_sub_q(unpack256<FqParams>(gen)), cond_sub_q(unpack256<FqParams>(gen + 8)),
+                     cond_sub_q(unpack256<FqParams>(gen + 16)), cond_sub_q(unpack256<FqParams>(gen + 24))};
+    for (int i = 0; i < 8; i++) pr::fq_store(out + i * NL, c[i]);
+}
+
+std::vector<u64> RatioOut::listed(u64 n, u64 maxListed) const {
+    std::vector<u64> v;
+    for (size_t b = 0; b < resolved.size() && v.size() < maxListed; b++)
+        for (u64 k = 0; k < RATIO_BLOCK && resolved[b] * RATIO_BLOCK + k < n && v.size() < maxListed; k++)
+            if (recordBad[b * RATIO_BLOCK + k]) v.push_back(resolved[b] * RATIO_BLOCK + k);
+    return v;
+}
+
+void ratioLevels(const uint8_t* x, const uint8_t* y, u64 n, u64 maxBlocks, RatioOut& out, const RatioSums& sums, const RatioJudge& judge) {
+    out = RatioOut();
+    if (!maxBlocks) maxBlocks = RATIO_MAX_BLOCKS;
+    const u64 blocks = (n + RATIO_BLOCK - 1) / RATIO_BLOCK;
+    out.blocks = blocks;
+    if (!n) return;
+    // block level
+    out.blockBad.assign((size_t)blocks, 0);
+    {
+        std::vector<uint8_t> w, sx((size_t)blocks * 64), sy((size_t)blocks * 64);
+        drawWeights128(w, n);
+        sums(w.data(), sx.data(), sy.data(), &out.ms[0]);
+        judge(sx.data(), sy.data(), blocks, out.blockBad.data(), &out.ms[1]);
+    }
+    for (u64 j = 0; j < blocks; j++) {
+        if (!out.blockBad[(size_t)j]) continue;
+        out.badBlocks++;
+        if (out.resolved.size() < maxBlocks) out.resolved.push_back(j);
+    }
+    out.resolvedBlocks = out.resolved.size();
+    out.exact = out.resolvedBlocks == out.badBlocks;
+    if (out.resolved.empty()) return;
+    // record level: the records of the resolved blocks side by side (a short last block is padded with infinity pairs, which hold)
+    const size_t m = out.resolved.size() * (size_t)RATIO_BLOCK;
+    std::vector<uint8_t> gx(m * 64, 0), gy(m * 64, 0);
+    for (size_t b = 0; b < out.resolved.size(); b++) {
+        const u64 first = out.resolved[b] * RATIO_BLOCK, count = std::min(RATIO_BLOCK, n - first);
+        memcpy(&gx[b * RATIO_BLOCK * 64], x + first * 64, (size_t)count * 64);
+        memcpy(&gy[b * RATIO_BLOCK * 64], y + first * 64, (size_t)count * 64);
+    }
+    out.recordBad.assign(m, 0);
+    double ms = 0;
+    judge(gx.data(), gy.data(), m, out.recordBad.data(), &ms);
+    out.ms[1] += ms;
+    for (uint8_t b : out.recordBad) out.badRecords += b;
 }
 
 Backend& backendFor(int device, std::unique_ptr<Backend>& owned) {

@@ -25,6 +25,8 @@
 #include "host_util.hpp"
 #include "../../include/ultragroth_hip.h"
 
+namespace ug { namespace pr { struct FinalExpConsts; } }      // (pairing.hpp)
+
 namespace ughost {
 namespace setup {
 
@@ -88,6 +90,25 @@ struct ScaleSeg {
 };
 constexpr int MAX_SCALE_SEGS = 3;              // C1, C2 and H
 
+// The ratio test (Backend::ratio): which of n pairs (X_i, Y_i) of G1 records have e(X_i, Q) != e(Y_i, G2)?
+// Two levels. Block level: blocks of RATIO_BLOCK consecutive records, one fresh 128-bit weight per record, block j holds when
+// e(sum w_i X_i, Q) = e(sum w_i Y_i, G2): a block with a wrong record holds with probability at most 2^-128. Record level: every
+// record of the first maxBlocks failing blocks is judged by its own pairings, without weights: exact.
+constexpr u64 RATIO_BLOCK = 256;
+constexpr u64 RATIO_MAX_BLOCKS = 64;           // the default of maxBlocks: at most 16 384 records in one launch
+constexpr int RATIO_Q2_WORDS = 72;             // Q, then the generator of G2, in the pairing code's limb form (pairing.hpp: G2_WORDS each)
+struct RatioOut {
+    u64 blocks = 0, badBlocks = 0, resolvedBlocks = 0;
+    u64 badRecords = 0;                         // over the resolved blocks: the total when exact
+    bool exact = true;                          // every failing block was resolved
+    std::vector<uint8_t> blockBad;              // one byte per block: 1 = the block fails
+    std::vector<u64> resolved;                  // the resolved blocks, ascending
+    std::vector<uint8_t> recordBad;             // one byte per record of the resolved blocks, block after block: 1 = wrong
+    double ms[2] = {0, 0};                      // the block sums; the pairings of both levels (host threads: wall time)
+    // the first maxListed wrong records, ascending, as indices into the n pairs
+    std::vector<u64> listed(u64 n, u64 maxListed) const;
+};
+
 // phase times in ms: parse + index (+ upload), Lagrange, transposed products, G1 multiplications, G2 multiplications,
 // download + assembly
 constexpr int PHASES = 6;
@@ -116,6 +137,10 @@ public:
     // all-zero records, infinity in gives infinity out. An output may be its own segment's source only without an index list.
     // ms (may be null): one value
     virtual void scaleSegments(const ScaleSeg* segs, int n, double* ms) = 0;
+    // The ratio test over n pairs of zkey-format G1 records that passed the point check (all-zero = infinity; both infinity holds,
+    // exactly one is wrong). q: a G2 record, not infinity, in the subgroup. maxBlocks 0: RATIO_MAX_BLOCKS. Both backends give the
+    // same answers (their weights differ; the answers do not depend on them).
+    virtual void ratio(const uint8_t* x, const uint8_t* y, u64 n, const uint8_t* q, u64 maxBlocks, RatioOut& out) = 0;
     // The inverse transform over points that prepares a .ptau (ptau_prepare_host.cpp). N = 2^logN, omega = 5^((r - 1) / N):
     // out[v][k] = (1 / N) sum_j omega^(-j k) in[v][j] for each of the nVec vectors; in[v]: nGiven <= N zkey-format records, the rest
     // of the N taken as infinity; out[v]: N records, which do not overlap any input. ms (may be null): two values, the 1 / N
@@ -153,6 +178,21 @@ void columnPieces(const u32* colPtr, u64 nCols, u32 m, std::vector<Piece>& piece
 // Returns the index of the top non-zero digit, -1 for the scalar 0.
 constexpr int SCALE_WINDOW = 4;                // the device's width: odd multiples 1, 3, 5, 7 in registers
 int recodeWnaf(const uint8_t* le, int w, int8_t digit[256]);
+
+// ---- what the ratio test's two backends share ----
+// n values below 2^128, 16 bytes each, from getrandom: fresh in every call, never derived from the inputs
+void drawWeights128(std::vector<uint8_t>& out, u64 n);
+// q (a zkey-format G2 record) and the generator of G2 as the pairing code reads them
+void ratioG2Words(const uint8_t* q, u32 out[RATIO_Q2_WORDS]);
+// the constants of the is-one test, made once by host code (pairing.hpp: final_exp_consts)
+const ug::pr::FinalExpConsts& ratioConsts();
+// sums(weights, sumX, sumY, ms): the two weighted sums of every block as zkey-format records (blocks x 64 bytes each; weights: n x 16 bytes)
+typedef std::function<void(const uint8_t*, uint8_t*, uint8_t*, double*)> RatioSums;
+// judge(x, y, m, wrong, ms): wrong[i] = 1 unless e(x_i, Q) = e(y_i, G2), over m pairs of records
+typedef std::function<void(const uint8_t*, const uint8_t*, u64, uint8_t*, double*)> RatioJudge;
+// the two levels over a backend's two steps: draws the weights, judges the block sums, gathers the records of the first
+// maxBlocks failing blocks and judges them
+void ratioLevels(const uint8_t* x, const uint8_t* y, u64 n, u64 maxBlocks, RatioOut& out, const RatioSums& sums, const RatioJudge& judge);
 
 // ---- what the inverse transform's two backends share ----
 // A folded scalar: 8 plain words of a magnitude below 2^255, bit 255 set when the point is negated (coefMagnitude's fold).
@@ -215,6 +255,10 @@ void writeContainer(uint8_t* zkey, const Layout& lay);            // magic, vers
 void finishKey(const R1cs& cs, const Plan& p, const Layout& lay, const std::vector<u64>& perPiece, const HeaderPoints& hp,
                const std::vector<uint8_t>& krec, uint8_t* zkey, std::string* vkey, bool cPointsDone = false);
 Backend& backendFor(int device, std::unique_ptr<Backend>& owned);
+// (setup_ptau.cpp) the columns of a combination that gives K_s over the three level-n slices side by side [T | aT | bT] of N records
+// each: column i is wire s = wires ? wires[i] : first + i, M columns; an A term (k, s) names bT[k], a B term aT[k], a C term T[k]
+void mergedColumns(const ColMatrix cm[3], const u32* wires, u64 first, u64 M, u64 N, std::vector<u32>& colPtr, std::vector<u32>& index,
+                   std::vector<uint8_t>& coefs);
 // the verification key's JSON into the caller's buffer (may be null: only the length is reported), with its terminating 0
 void copyVkey(const std::string& vkey, char* dst, u64 capacity, uint64_t* bytes);
 // uniform below r, never 0: 254 random bits, drawn again when out of range

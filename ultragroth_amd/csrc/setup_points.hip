@@ -12,6 +12,8 @@
 //                          leave as canonical zkey records
 //   scale_kernel           one scalar times many G1 points: the scalar's width-4 non-adjacent form comes from the host in the
 //                          kernel argument, so every lane of the launch takes the same branch at every step
+//   ratio_block_sums_kernel  the block level of the ratio test (Backend::ratio): one workgroup per block of
+//                          256 pairs of records, a lane walks its 128-bit weight once for both points, the sums leave as records
 // A coefficient above r / 2 is the negated point times r - coef, so 1 and r - 1 cost one addition and r - small costs as small.
 // Plain C++ and vector stores only. DESIGN.md section 5.9 has the registers and what was measured.
 #include "setup_dev.hpp"
@@ -260,6 +262,71 @@ __global__ __launch_bounds__(SEG_BLOCK) void scale_segments_kernel(SegmentsArgs 
     scale_walk(a.digit[s], g.top, x, y, o);
 }
 
+// ---- the block sums of the ratio test (Backend::ratio): sum w_i X_i and sum w_i Y_i over each block of 256 records ----
+// One workgroup per block, one record per lane. The lane walks the 128 bits of its weight once for both points (doubling an
+// accumulator that is still infinity costs nothing, so the leading zero bits are free); a point at infinity stays out. The 256
+// partial sums of each of the two sets are then added by a tree in LDS, the two sets one after the other through the same 36 KiB,
+// and lane 0 converts both sums with one shared inversion. A sum may be infinity: the all-zero record.
+constexpr int RATIO_LANES = 256;
+static_assert(RATIO_LANES == (int)RATIO_BLOCK, "one lane per record of a block");
+__device__ __forceinline__ void ratio_emit(u32* o, const XYZZ<Fq>& p, const Fq& izzz) {
+    if (is_inf(p)) { zero_record<16>(o); return; }
+    const Fq iz = mulk<8>(izzz, p.zz);
+    const Fq izz = sqrk<8>(iz);
+    S1::store_mont(o, mulk<8>(p.x, izz), mulk<8>(p.y, izzz));
+}
+__global__ __launch_bounds__(RATIO_LANES) void ratio_block_sums_kernel(const u32* __restrict__ xs, const u32* __restrict__ ys,
+                                                                       const u32* __restrict__ weights, u32 n, u32* __restrict__ sums) {
+    constexpr int B = RATIO_LANES, FW = NL;
+    __shared__ u32 sh[4 * FW][B];
+    const u32 t = threadIdx.x;
+    const u64 i = (u64)blockIdx.x * B + t;
+    XYZZ<Fq> ax = xyzz_inf<Fq>(), ay = xyzz_inf<Fq>();
+    if (i < n) {                                 // (no lane leaves before the barriers below)
+        Fq x1, y1, x2, y2;
+        S1::load(xs + i * 16, x1, y1);
+        S1::load(ys + i * 16, x2, y2);
+        const bool live1 = !affine_is_inf(x1, y1), live2 = !affine_is_inf(x2, y2);
+        const uint4 wv = reinterpret_cast<const uint4*>(weights)[i];
+        u32 s0 = wv.x, s1 = wv.y, s2 = wv.z, s3 = wv.w;
+#pragma unroll 1
+        for (int b = 0; b < 128; b++) {
+            ax = xyzz_dbl(ax);
+            ay = xyzz_dbl(ay);
+            const bool bit = (s3 >> 31) != 0;
+            s3 = (s3 << 1) | (s2 >> 31); s2 = (s2 << 1) | (s1 >> 31); s1 = (s1 << 1) | (s0 >> 31); s0 <<= 1;
+            if (bit) {
+                if (live1) ax = xyzz_madd(ax, x1, y1);
+                if (live2) ay = xyzz_madd(ay, x2, y2);
+            }
+        }
+    }
+    XYZZ<Fq> sx = ax, sy = ay;
+#pragma unroll 1
+    for (int set = 0; set < 2; set++) {
+        XYZZ<Fq> acc = set ? ay : ax;
+#pragma unroll 1
+        for (u32 off = B / 2; off > 0; off >>= 1) {
+            if (t < 2 * off) { sh_put<B>(sh, 0, t, acc.x); sh_put<B>(sh, FW, t, acc.y); sh_put<B>(sh, 2 * FW, t, acc.zz); sh_put<B>(sh, 3 * FW, t, acc.zzz); }
+            __syncthreads();
+            if (t < off) {
+                XYZZ<Fq> o;
+                sh_get<B>(sh, 0, t + off, o.x); sh_get<B>(sh, FW, t + off, o.y); sh_get<B>(sh, 2 * FW, t + off, o.zz); sh_get<B>(sh, 3 * FW, t + off, o.zzz);
+                acc = xyzz_add(acc, o);
+            }
+            __syncthreads();
+        }
+        if (set) sy = acc; else sx = acc;
+    }
+    if (t != 0) return;
+    const Fq one = field_one((Fq*)0);
+    const Fq zx = is_inf(sx) ? one : sx.zzz, zy = is_inf(sy) ? one : sy.zzz;
+    const Fq irun = inv(mulk<8>(zx, zy));
+    u32* o = sums + (size_t)blockIdx.x * 32;
+    ratio_emit(o, sx, mulk<8>(irun, zy));
+    ratio_emit(o + 16, sy, mulk<8>(irun, zx));
+}
+
 // ---- host side ----
 // The terms of a combination by class. code: one word per term (see ColArgs); the non-unit terms get a slot each, slots in the
 // order of their coefficient's bit length, so a wave of term_products_kernel holds one length or two neighbouring ones.
@@ -403,6 +470,37 @@ void device_points_scale(hipStream_t stream, StreamTimer& timer, const uint8_t* 
     timer.resolve();
     volatile int8_t* w = a.digit;                // (the digits are 1 / delta)
     for (int i = 0; i < 256; i++) w[i] = 0;
+    if (ms) ms[0] = sink.ms;
+}
+
+// The block sums of the ratio test: weights n x 16 bytes; sumX, sumY: one record per block of RATIO_BLOCK records.
+void device_points_ratio_sums(hipStream_t stream, StreamTimer& timer, const uint8_t* x, const uint8_t* y, u64 n, const uint8_t* weights,
+                              uint8_t* sumX, uint8_t* sumY, double* ms) {
+    if (ms) ms[0] = 0;
+    if (!n) return;
+    if (n > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+    const u64 blocks = (n + RATIO_LANES - 1) / RATIO_LANES;
+    DevBuf<u32> dX(n * 16), dY(n * 16), dW(n * 4), dSums(blocks * 32);
+    UG_HIP(hipMemcpyAsync(dX.get(), x, n * 64, hipMemcpyHostToDevice, stream));
+    UG_HIP(hipMemcpyAsync(dY.get(), y, n * 64, hipMemcpyHostToDevice, stream));
+    UG_HIP(hipMemcpyAsync(dW.get(), weights, n * 16, hipMemcpyHostToDevice, stream));
+    convert_points_g1(dX.get(), n, stream);
+    convert_points_g1(dY.get(), n, stream);
+    TimeSink sink;
+    {
+        StreamTimer::Scope sc = timer.time(stream, &sink);
+        hipLaunchKernelGGL(ratio_block_sums_kernel, dim3((unsigned)blocks), dim3(RATIO_LANES), 0, stream, dX.get(), dY.get(), dW.get(), (u32)n, dSums.get());
+        UG_KERNEL_CHECK();
+        sc.stop();
+    }
+    std::vector<uint8_t> both((size_t)blocks * 128);
+    UG_HIP(hipMemcpyAsync(both.data(), dSums.get(), blocks * 128, hipMemcpyDeviceToHost, stream));
+    UG_HIP(hipStreamSynchronize(stream));
+    timer.resolve();
+    for (u64 j = 0; j < blocks; j++) {
+        memcpy(sumX + j * 64, &both[(size_t)j * 128], 64);
+        memcpy(sumY + j * 64, &both[(size_t)j * 128 + 64], 64);
+    }
     if (ms) ms[0] = sink.ms;
 }
 

@@ -1,5 +1,5 @@
 // setup_ptau.cpp -- the phase-2 setup from a prepared powers-of-tau file (include/ultragroth_hip.h: ug_ptau_parse_info,
-// ug_setup_ptau_*, ug_points_combine, ug_points_scale): what `snarkjs zkey new` does for a Groth16 circuit, then optionally one
+// ug_setup_ptau_*, ug_points_combine, ug_points_scale, ug_points_ratio_mask): what `snarkjs zkey new` does for a Groth16 circuit, then optionally one
 // delta contribution; and the same for an UltraGroth key (ug_ultra_setup_ptau_*, ug_points_scale_segments): two deltas, the C points
 // in two sections by the caller's lists. No trapdoor is known here. Out of scope: contribution transcripts, beacons, verifying the
 // .ptau's own ceremony.
@@ -86,22 +86,28 @@ struct Delta {
     }
 };
 
-// K's columns: wire s lists its A terms (points bT, segment 2), its B terms (aT, segment 1) and its C terms (T, segment 0)
-void mergedColumns(const ColMatrix cm[3], u64 M, u64 N, std::vector<u32>& colPtr, std::vector<u32>& index, std::vector<uint8_t>& coefs) {
-    const u64 terms = cm[0].terms() + cm[1].terms() + cm[2].terms();
-    if (terms > 0xfffffff0ull) throw SetupError("sizes that cannot be represented: more than 2^32 - 16 terms in A, B and C together");
+}  // namespace
+
+// K's columns: column i is wire s = wires ? wires[i] : first + i, which lists its A terms (points bT, segment 2), its B terms (aT,
+// segment 1) and its C terms (T, segment 0)
+void mergedColumns(const ColMatrix cm[3], const u32* wires, u64 first, u64 M, u64 N, std::vector<u32>& colPtr, std::vector<u32>& index,
+                   std::vector<uint8_t>& coefs) {
+    auto wire = [&](u64 i) { return wires ? (u64)wires[i] : first + i; };
     colPtr.assign((size_t)M + 1, 0);
-    for (u64 s = 0; s < M; s++) {
-        u64 n = 0;
-        for (int m = 0; m < 3; m++) n += cm[m].colPtr[s + 1] - cm[m].colPtr[s];
-        colPtr[s + 1] = colPtr[s] + (u32)n;
+    u64 terms = 0;
+    for (u64 i = 0; i < M; i++) {
+        const u64 s = wire(i);
+        for (int m = 0; m < 3; m++) terms += cm[m].colPtr[s + 1] - cm[m].colPtr[s];
+        if (terms > 0xfffffff0ull) throw SetupError("sizes that cannot be represented: more than 2^32 - 16 terms in A, B and C together");
+        colPtr[i + 1] = (u32)terms;
     }
     index.resize(terms);
     coefs.resize(terms * 32);
     const u32 seg[3] = {2, 1, 0};
     parallelFor(M, 4096, [&](u64 lo, u64 hi) {
-        for (u64 s = lo; s < hi; s++) {
-            u32 at = colPtr[s];
+        for (u64 i = lo; i < hi; i++) {
+            const u64 s = wire(i);
+            u32 at = colPtr[i];
             for (int m = 0; m < 3; m++)
                 for (u32 q = cm[m].colPtr[s]; q < cm[m].colPtr[s + 1]; q++, at++) {
                     index[at] = (u32)(seg[m] * N + cm[m].row[q]);
@@ -110,6 +116,8 @@ void mergedColumns(const ColMatrix cm[3], u64 M, u64 N, std::vector<u32>& colPtr
         }
     });
 }
+
+namespace {
 
 u64 runPtau(const Request& rq, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, int device, uint8_t* zkey,
             u64 zkeyCap, std::string* vkey, double ms[PTAU_PHASES], bool sizeOnly, u64* vkeyMax) {
@@ -156,7 +164,7 @@ u64 runPtau(const Request& rq, const void* r1cs, u64 r1csSize, const void* ptau,
     {
         std::vector<u32> colPtr, index;
         std::vector<uint8_t> coefs;
-        mergedColumns(cm, M, N, colPtr, index, coefs);
+        mergedColumns(cm, nullptr, 0, M, N, colPtr, index, coefs);
         PointSegs three;
         three.count = N; three.n = 3;
         three.base[0] = sl.tau1; three.base[1] = sl.alphaTau1; three.base[2] = sl.betaTau1;
@@ -327,6 +335,33 @@ int ug_points_scale(int device, const void* scalar, const void* points, uint64_t
         if (!n) return;
         std::unique_ptr<Backend> owned;
         backendFor(device, owned).scale((const uint8_t*)scalar, (const uint8_t*)points, n, (uint8_t*)out, kernel_ms);
+    });
+}
+
+int ug_points_ratio_mask(int device, const void* x, const void* y, uint64_t n, const void* q, uint64_t max_blocks, void* record_mask,
+                         void* block_mask, ug_ratio_report* out, char* error_msg, unsigned long long error_msg_maxsize) {
+    return guarded(SETUP_RULE, error_msg, error_msg_maxsize, [&] {
+        if (out) memset(out, 0, sizeof *out);
+        if (!q || !out || (n && (!x || !y || !record_mask || !block_mask))) throw SetupError("null buffer");
+        if (n > 0xffffffffull) throw SetupError("sizes that cannot be represented: more than 2^32 - 1 points");
+        if (allZero((const uint8_t*)q, 128)) throw SetupError("q is the point at infinity");
+        std::unique_ptr<Backend> owned;
+        RatioOut r;
+        backendFor(device, owned).ratio((const uint8_t*)x, (const uint8_t*)y, n, (const uint8_t*)q, max_blocks, r);
+        if (n) memcpy(block_mask, r.blockBad.data(), (size_t)r.blocks);
+        uint8_t* o = (uint8_t*)record_mask;
+        for (size_t b = 0; b < r.resolved.size(); b++) {         // (a short last block gives only the records it has)
+            const u64 count = std::min<u64>(RATIO_BLOCK, n - r.resolved[b] * RATIO_BLOCK);
+            memcpy(o, &r.recordBad[b * RATIO_BLOCK], (size_t)count);
+            o += count;
+        }
+        out->blocks = r.blocks; out->bad_blocks = r.badBlocks; out->resolved_blocks = r.resolvedBlocks; out->bad_records = r.badRecords;
+        out->resolved_records = (uint64_t)(o - (uint8_t*)record_mask);
+        out->exact = r.exact ? 1 : 0;
+        const std::vector<u64> listed = r.listed(n, UG_RATIO_LISTED);
+        out->n_listed = (uint32_t)listed.size();
+        for (size_t i = 0; i < listed.size(); i++) out->index[i] = listed[i];
+        out->kernel_ms[0] = r.ms[0]; out->kernel_ms[1] = r.ms[1];
     });
 }
 

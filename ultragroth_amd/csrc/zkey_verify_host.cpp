@@ -9,6 +9,10 @@
 // MSMs over the level-n slices stand against one MSM over each section of the key; H needs no matrix at all. The relations and
 // their soundness are in DESIGN.md section 5.11; the notation is ug_setup_ptau_run's.
 //
+// ug_zkey_locate_run / ug_ultra_zkey_locate_run go through the same run() and, once the verdict is known, name the wrong records
+// of every failing point section (locateSections): sections 5, 6, 7 against the combination of the circuit's
+// columns by bytes, section 3, the C sections and H against their delta-free counterparts through Backend::ratio.
+//
 // This file is the host layer and the host twin (device = -1): the files' rules, the point check, relation 0 (header) and
 // relation 1 (section 4, through setup_host.cpp's own writer), the weights, the pairings (pairing.hpp, host threads wherever the
 // sums were made) and the verdict. The sums (twelve, fourteen for an UltraGroth key) come from host threads here or from the
@@ -169,18 +173,15 @@ void hostSums(const Inputs& in, const uint8_t* hOdd, Sums& out, SumsStats& st) {
 
 // ---- pairings (pairing.hpp, host threads) ----
 const FinalExpConsts& consts() { static const FinalExpConsts c = final_exp_consts(); return c; }
-F1 coord(const uint8_t* le) {
-    u32 w[8];
-    memcpy(w, le, 32);
-    return F1{cond_sub_q(from_mont256<FqParams>(w))};
-}
-G1A g1Of(const uint8_t* rec) {
-    if (allZero(rec, 64)) return G1A{f1_zero(), f1_zero(), true};
-    return G1A{coord(rec), coord(rec + 32), false};
+G1A g1Of(const uint8_t* rec) {                  // (pairing.hpp's record forms; a file's records sit at any alignment)
+    u32 w[16];
+    memcpy(w, rec, 64);
+    return g1_from_record(w, false);
 }
 G2A g2Of(const uint8_t* rec) {
-    if (allZero(rec, 128)) return g2_inf();
-    return G2A{F2{coord(rec), coord(rec + 32)}, F2{coord(rec + 64), coord(rec + 96)}, false};
+    u32 w[32];
+    memcpy(w, rec, 128);
+    return g2_from_record(w);
 }
 G1A g1Generator() { return G1A{f1_small(1), f1_small(2), false}; }
 G2A g2Generator() {
@@ -263,10 +264,101 @@ const uint8_t* sectionOf(const BinFile& f, u32 id, u64 need) {
     return f.sectionData(id);
 }
 
-// what a run reads of either options struct; ultra: null for a Groth16 key
+// ---- naming the wrong records of the sections that failed ----
+struct Locate {
+    u32 maxListed, maxBlocks;                    // (the defaults are in place)
+    ug_zkey_locate_report* out;
+};
+ug_zkey_locate_section* newEntry(const Locate& lc, u32 id, u32 method, u64 records) {
+    if (lc.out->n_sections >= UG_ZKEY_LOCATE_SECTIONS) throw ZkeyError("internal: more failing point sections than a report holds");
+    ug_zkey_locate_section* e = &lc.out->section[lc.out->n_sections++];
+    e->section = id; e->method = method; e->records = records;
+    e->blocks = (records + RATIO_BLOCK - 1) / RATIO_BLOCK;
+    return e;
+}
+// Every section in `failed` that holds points, in the order 3, 5, 6, 7, the C sections, H; one section's expected records at a
+// time. list[i]: the signals of an UltraGroth key's C section i (a Groth16 key's C section is the wires from pub on).
+void locateSections(const Locate& lc, u32 failed, const Protocol& pr, const Inputs& in, const uint8_t* gamma2, const R1cs& cs, const Plan& plan,
+                    const uint8_t* hOdd, const std::vector<u32>* list, bool ultra, int device) {
+    const int nC = pr.K - 1;
+    u32 pointSections = (1u << 3) | (1u << 5) | (1u << 6) | (1u << 7) | (1u << pr.hId);
+    for (int i = 0; i < nC; i++) pointSections |= 1u << (8 + i);
+    if (!(failed & pointSections)) return;
+    const double t0 = nowMs();
+    const u64 M = in.M, N = in.N;
+    std::unique_ptr<Backend> owned;
+    Backend& be = backendFor(device, owned);
+    ColMatrix cm[3];
+    bool haveColumns = false;
+    auto columns = [&] {
+        if (haveColumns) return;
+        std::vector<Piece> pieces;
+        buildColumns(cs, plan, cm, pieces);
+        haveColumns = true;
+    };
+    // A, B1, B2 do not depend on a delta: the expected records themselves, compared by bytes
+    auto byBytes = [&](u32 id, bool g2, int m, const uint8_t* slice, const uint8_t* have) {
+        if (!(failed >> id & 1) || !M) return;
+        columns();
+        const u64 rec = g2 ? 128 : 64;
+        std::vector<uint8_t> want((size_t)(M * rec));
+        PointSegs one;
+        one.count = N; one.n = 1; one.base[0] = slice;
+        be.combine(g2, M, cm[m].colPtr.data(), cm[m].row.data(), cm[m].val.data(), one, want.data(), nullptr);
+        ug_zkey_locate_section* e = newEntry(lc, id, UG_LOCATE_BYTES, M);
+        e->exact = 1;
+        u64 lastBlock = ~0ull;
+        for (u64 i = 0; i < M; i++) {
+            if (!memcmp(&want[(size_t)(i * rec)], have + i * rec, (size_t)rec)) continue;
+            e->bad_records++;
+            if (i / RATIO_BLOCK != lastBlock) { lastBlock = i / RATIO_BLOCK; e->bad_blocks++; }
+            if (e->n_listed < lc.maxListed) e->index[e->n_listed++] = i;
+        }
+        e->resolved_blocks = e->bad_blocks;
+    };
+    // X_s d = Y_s for a d nobody knows: the ratio test against d's G2 point
+    auto byRatio = [&](u32 id, const uint8_t* have, const uint8_t* expect, u64 n, const uint8_t* q) {
+        uint8_t qrec[128];                       // (the header's points sit at any alignment)
+        memcpy(qrec, q, 128);
+        if (allZero(qrec, 128)) return;
+        RatioOut r;
+        be.ratio(have, expect, n, qrec, lc.maxBlocks, r);
+        ug_zkey_locate_section* e = newEntry(lc, id, UG_LOCATE_RATIO, n);
+        e->bad_blocks = r.badBlocks; e->resolved_blocks = r.resolvedBlocks; e->bad_records = r.badRecords;
+        e->exact = r.exact ? 1 : 0;
+        const std::vector<u64> listed = r.listed(n, lc.maxListed);
+        e->n_listed = (u32)listed.size();
+        for (size_t i = 0; i < listed.size(); i++) e->index[i] = listed[i];
+        e->kernel_ms[0] = r.ms[0]; e->kernel_ms[1] = r.ms[1];
+    };
+    // K_s of n wires (a list, or a run from `first`): setup_ptau.cpp's combination over [T | aT | bT], before any delta
+    auto byRatioK = [&](u32 id, const uint8_t* have, const u32* wires, u64 first, u64 n, const uint8_t* q) {
+        if (!(failed >> id & 1) || !n) return;
+        columns();
+        std::vector<u32> colPtr, index;
+        std::vector<uint8_t> coefs, k((size_t)n * 64);
+        mergedColumns(cm, wires, first, n, N, colPtr, index, coefs);
+        PointSegs three;
+        three.count = N; three.n = 3;
+        three.base[0] = in.T; three.base[1] = in.aT; three.base[2] = in.bT;
+        be.combine(false, n, colPtr.data(), index.data(), coefs.data(), three, k.data(), nullptr);
+        byRatio(id, have, k.data(), n, q);
+    };
+    byRatioK(3, in.ic, nullptr, 0, in.pub, gamma2);
+    byBytes(5, false, 0, in.T, in.a);
+    byBytes(6, false, 1, in.T, in.b1);
+    byBytes(7, true, 1, in.T2, in.b2);
+    for (int i = 0; i < nC; i++)
+        byRatioK(8 + (u32)i, in.c[i].points, ultra ? list[i].data() : nullptr, in.pub, in.c[i].n, pr.delta2[i]);
+    if (failed >> pr.hId & 1) byRatio(pr.hId, in.h, hOdd, N, pr.delta2[nC - 1]);
+    lc.out->locate_ms = nowMs() - t0;
+}
+
+// what a run reads of either options struct; ultra: null for a Groth16 key; locate: null for a verify entry
 struct Request {
     u32 validate;
     const ug_ultra_zkey_verify_options* ultra;
+    const Locate* locate = nullptr;
 };
 Request checkOptions(const ug_zkey_verify_options* o) {
     checkOptionsHead<ZkeyError>(o, 1, 2, "1 or 2");
@@ -475,6 +567,8 @@ int run(const Request& rq, const void* r1cs, u64 r1csSize, const void* ptau, u64
     clock.lap(7);
     rep->failed_sections = v.failed;
     rep->first_failed = v.first;
+    // ---- the verdict stands; a locate entry now names the wrong records of the point sections that failed ----
+    if (rq.locate && v.failed) locateSections(*rq.locate, v.failed, pr, in, zh.gamma2, cs, plan, hOdd.data(), list, ultra, device);
     return v.failed ? UG_ZKEY_INVALID : UG_OK;
 }
 
@@ -492,6 +586,40 @@ int verifyEntry(const Options* opt, const void* r1cs, u64 r1csSize, const void* 
             copyErr(errorMsg, errorMsgMax, v.message.c_str());
         }) != UG_OK) {
         memset(&rep, 0, sizeof rep);              // (a refusal reports nothing)
+        rc = UG_ERROR;
+    }
+    if (out) *out = rep;
+    if (phaseMs) for (int i = 0; i < PHASES; i++) phaseMs[i] = ms[i];
+    return rc;
+}
+
+// A locate entry: the verify entry's call with the options' common fields, then the located report. vopt: the verify options the
+// locate options stand for (their size is the verify struct's own, so checkOptions' rules and texts are the verify entry's).
+template <class LocateOptions, class VerifyOptions>
+int locateEntry(const LocateOptions* opt, VerifyOptions vopt, const void* r1cs, u64 r1csSize, const void* ptau, u64 ptauSize, const void* zkey,
+                u64 zkeySize, int device, ug_zkey_verify_report* out, ug_zkey_locate_report* located, double* phaseMs, char* errorMsg,
+                unsigned long long errorMsgMax) {
+    ug_zkey_verify_report rep;
+    memset(&rep, 0, sizeof rep);
+    double ms[PHASES] = {0};
+    int rc = UG_ERROR;
+    if (located) memset(located, 0, sizeof *located);
+    if (guarded(ZKEY_RULE, errorMsg, errorMsgMax, [&] {
+            if (!opt) throw ZkeyError("null options");
+            if (opt->size != sizeof(LocateOptions)) throw ZkeyError("options struct of another size (" + std::to_string(opt->size) + ")");
+            if (!located) throw ZkeyError("null locate report");
+            if (opt->max_listed > UG_ZKEY_LOCATE_LISTED)
+                throw ZkeyError("max_listed " + std::to_string(opt->max_listed) + " exceeds " + std::to_string(UG_ZKEY_LOCATE_LISTED));
+            const Locate lc = {opt->max_listed ? opt->max_listed : 16, opt->max_blocks ? opt->max_blocks : (u32)RATIO_MAX_BLOCKS, located};
+            vopt.size = sizeof vopt;
+            Request rq = checkOptions(&vopt);
+            rq.locate = &lc;
+            Verdict v;
+            rc = run(rq, r1cs, r1csSize, ptau, ptauSize, zkey, zkeySize, device, &rep, ms, v);
+            copyErr(errorMsg, errorMsgMax, v.message.c_str());
+        }) != UG_OK) {
+        memset(&rep, 0, sizeof rep);              // (a refusal reports nothing)
+        if (located) memset(located, 0, sizeof *located);
         rc = UG_ERROR;
     }
     if (out) *out = rep;
@@ -552,6 +680,28 @@ int ug_ultra_zkey_verify_run(const ug_ultra_zkey_verify_options* opt, const void
                              uint64_t ptau_size, const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out, double* phase_ms,
                              char* error_msg, unsigned long long error_msg_maxsize) {
     return verifyEntry(opt, r1cs, r1cs_size, ptau, ptau_size, zkey, zkey_size, device, out, phase_ms, error_msg, error_msg_maxsize);
+}
+
+int ug_zkey_locate_run(const ug_zkey_locate_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau, uint64_t ptau_size,
+                       const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out, ug_zkey_locate_report* located,
+                       double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize) {
+    ug_zkey_verify_options v;
+    memset(&v, 0, sizeof v);
+    if (opt) v.validate = opt->validate;
+    return locateEntry(opt, v, r1cs, r1cs_size, ptau, ptau_size, zkey, zkey_size, device, out, located, phase_ms, error_msg, error_msg_maxsize);
+}
+
+int ug_ultra_zkey_locate_run(const ug_ultra_zkey_locate_options* opt, const void* r1cs, uint64_t r1cs_size, const void* ptau,
+                             uint64_t ptau_size, const void* zkey, uint64_t zkey_size, int device, ug_zkey_verify_report* out,
+                             ug_zkey_locate_report* located, double* phase_ms, char* error_msg, unsigned long long error_msg_maxsize) {
+    ug_ultra_zkey_verify_options v;
+    memset(&v, 0, sizeof v);
+    if (opt) {
+        v.validate = opt->validate; v.check_spec = opt->check_spec; v.rand_indx = opt->rand_indx;
+        v.round_signals = opt->round_signals; v.n_round = opt->n_round;
+        v.final_signals = opt->final_signals; v.n_final = opt->n_final;
+    }
+    return locateEntry(opt, v, r1cs, r1cs_size, ptau, ptau_size, zkey, zkey_size, device, out, located, phase_ms, error_msg, error_msg_maxsize);
 }
 
 int ug_r1cs_fold(const void* r1cs, uint64_t r1cs_size, const void* rho, uint32_t log_domain, int device, void* out, double* kernel_ms,
