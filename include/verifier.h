@@ -158,6 +158,58 @@ int ug_groth16_verify_batch_records_fmt(int device, int format, int count, const
 int ug_ultra_groth_verify_batch_records_fmt(int device, int format, int count, const void *records, const void *inputs, int n_pub,
                                             const char *verification_key, int *verdicts, const ug_verify_batch_options *options,
                                             ug_verify_batch_stats_ex *stats, char *error_msg, unsigned long error_msg_maxsize);
+/* ---- several keys in one call --------------------------------------------------------------------------------------------
+ * A service that verifies proofs of many circuits pays the floor of a device pass -- one lane's Miller latency -- once per call,
+ * so once per circuit with the calls above. The Miller loop of a proof does not read the key; only the end of a pass does. These
+ * calls take n_keys key texts and key_of[count], the key of every proof, and make ONE device pass and ONE final exponentiation per
+ * 65536 proofs, whatever the number of keys. One protocol per call: Groth16 and UltraGroth keys do not mix.
+ *   verdicts[i] is what groth16_verify / ultra_groth_verify says of proof i under keys[key_of[i]], up to the batch's 2^-128. Proofs
+ *   arrive in any order, interleaved between keys: the library groups them by key with a stable sort and answers in the caller's
+ *   order; rc and error_msg follow the one-key rule, "proof <first bad index in the caller's order>: <reason>".
+ *   The records calls take the layout as the _fmt calls do, and n_pub[n_keys], the inputs per proof of every key. Their input block
+ *   is ragged: proof i owns n_pub[key_of[i]] x 32 bytes that start where proof i - 1's end, in the caller's order and the byte
+ *   order of `format`.
+ *   options and stats as the _opt calls; stats->ex is their struct. segments: the (pass, key) pairs that were batched; tree_launches:
+ *   launches of the tree kernels (0 with device < 0), at most 2 ceil(log2(largest segment)) per pass; key_checks: the batch checks
+ *   spent above the segments -- the one equation of every pass and the search over the keys --, part of ex.base.batch_checks.
+ * VERIFIER_ERROR, verdicts untouched: an unknown format (the _fmt message); null arguments, count < 0 or n_keys < 0 ("null
+ * argument"; key_of may be null when count == 0); n_keys <= 0 with count > 0; a key_of[i] outside [0, n_keys), "proof <i>: key index
+ * <v> out of range"; n_pub[k] <= 0, "key <k>: invalid inputs data"; a key that does not parse, "key <k>: <the single call's
+ * message>" -- keys that no proof names are parsed as well --; n_pub[k] + 1 != len(IC_k), "key <k>: <the length message>"; a device
+ * error. count == 0 is valid.
+ * A pass holds up to 65536 proofs in key order; the proofs of one key inside a pass are a SEGMENT, and a key whose proofs cross a
+ * pass boundary has a segment in each. Scalars, prefix sums and vkX are per segment, as under one key; the trees are a forest,
+ * one tree per segment, made by one launch per level for all segments. The pass is accepted by one equation, the product over its
+ * segments of root_s e(-S_s alpha_s, beta_s) e(-vkX_s, gamma_s) e(-sum r C, delta_s) ..., and one final exponentiation. A pass that
+ * fails is searched down a binary tree over its segments (both children of a failing node are checked, the failing ones entered),
+ * then inside every failing segment as under one key, its root not checked again:
+ *   batch_checks <= 1 + 2 (failing segments) ceil(log2 S) + sum over them of 2 bad_s ceil(log2(n_s / 16)),  single_checks <= 16 bad
+ * for a pass of S segments. Judge on: the level of the keys follows the search_width rule of the proofs' level, and the suspects
+ * of all keys are judged in ONE launch of up to 65536 (the keyed instantiation of judge_kernel; the cheap vkX step runs per key).
+ * A key the batch refuses -- a point off its curve, a G2 point outside the subgroup -- sends ITS proofs to the single verifier;
+ * the proofs under the other keys are batched as usual. n_keys == 1 gives the one-key call's verdicts, rc, message, batch_checks,
+ * single_checks and off_subgroup on the same inputs, on the same code path: the one-key calls ARE this call with one key (a pass
+ * of one segment keeps the one-key tree kernels and their tree layout, which the forest's is for one segment).
+ * The keys are parsed and checked across the host threads. device < 0: the same protocol with the forest made on host threads. */
+typedef struct {
+    ug_verify_batch_stats_ex ex;
+    unsigned long long segments, tree_launches, key_checks;
+} ug_verify_batch_stats_keys;
+int ug_groth16_verify_batch_keys(int device, int count, const char *const *proofs, const char *const *inputs, int n_keys,
+                                 const char *const *keys, const int *key_of, int *verdicts, const ug_verify_batch_options *options,
+                                 ug_verify_batch_stats_keys *stats, char *error_msg, unsigned long error_msg_maxsize);
+int ug_ultra_groth_verify_batch_keys(int device, int count, const char *const *proofs, const char *const *inputs, int n_keys,
+                                     const char *const *keys, const int *key_of, int *verdicts, const ug_verify_batch_options *options,
+                                     ug_verify_batch_stats_keys *stats, char *error_msg, unsigned long error_msg_maxsize);
+int ug_groth16_verify_batch_records_keys(int device, int format, int count, const void *records, const void *inputs, int n_keys,
+                                         const char *const *keys, const int *key_of, const int *n_pub, int *verdicts,
+                                         const ug_verify_batch_options *options, ug_verify_batch_stats_keys *stats, char *error_msg,
+                                         unsigned long error_msg_maxsize);
+int ug_ultra_groth_verify_batch_records_keys(int device, int format, int count, const void *records, const void *inputs, int n_keys,
+                                             const char *const *keys, const int *key_of, const int *n_pub, int *verdicts,
+                                             const ug_verify_batch_options *options, ug_verify_batch_stats_keys *stats,
+                                             char *error_msg, unsigned long error_msg_maxsize);
+
 /* One record from one layout to another, every coordinate reduced mod q on the way (from == to: the record reduced). 0 = converted;
  * 1 = the source holds no point to convert -- from COMPRESSED an x with no root, to COMPRESSED a point that is not on its curve,
  * since a sign bit cannot stand for it; 2 = a null argument or an unknown format. `to` is written only on 0. PLAIN <-> EVM never
@@ -205,6 +257,13 @@ int ug_test_records_ingest(int device, int format, int ultra, int count, const v
 /* f2_sqrt (pairing.hpp) of count values, each 64 bytes plain little-endian c0 | c1: out gets the root that is NOT the larger one in
  * the same form (zeros when there is none), has_root one byte each. One lane per element on a device; device < 0: the host's code. */
 int ug_test_fq2_sqrt(int device, int count, const void *in, void *out, unsigned char *has_root);
+/* Only the trees over given leaves: n_segments segments of sizes[] leaves each (n in all, at most 65536), leaves_f n x 108 words
+ * and leaves_g n x k x 36 words as the Miller kernel leaves them (canonical limbs; k = 1 or 2 G1 sums per proof). The forest
+ * kernels make them on `device`; device < 0: the host forest. f_tree_out / g_tree_out get the whole forest, nodes x 108 and
+ * nodes x k x 36 words: level 0 is the leaves; level l + 1 holds, in segment order, the (m + 1) / 2 nodes of every segment that has
+ * m > 1 nodes on level l (one segment: the tree of a one-key pass). Values are canonical, so both agree byte for byte. */
+int ug_test_tree_forest(int device, int k, int n_segments, const int *sizes, const unsigned int *leaves_f, const unsigned int *leaves_g,
+                        unsigned int *f_tree_out, unsigned int *g_tree_out);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,10 @@ search_width W and judge_min M.
 batches, converted ONCE outside the timed call, through ug_groth16_verify_batch_records (plain) and ug_groth16_verify_batch_records_fmt,
 --runs runs of each in turn, with the ingest step of each call (ug_verify_batch_phase_ms [2]: upload, ingest kernel, ladder, status
 bytes). --parent-lib PATH loads another build of the library beside this one and runs its plain records call in the same turns.
+
+--keys K1,K2,.. measures the calls under several keys (profiles/verify_keys.txt): K keys x 2^--per-key records as ONE call of
+ug_groth16_verify_batch_records_keys beside K one-key records calls of this build and of --parent-lib, in alternating turns, every
+size warmed up; valid, with one bad record, and with 1 % bad records under every key with the judge on (keys_report).
 """
 import argparse
 import ctypes as C
@@ -144,6 +148,96 @@ def formats_report(a, L, vk, pool, say):
                     % (lg, label, rep, n / dt, dt * 1e3, st.device_ms, st.host_ms, phase[2], ms[0]))
 
 
+def keys_report(a, L, vk, pool, say):
+    """--keys K1,K2,..: K keys x 2^--per-key valid records each, as ONE call of ug_groth16_verify_batch_records_keys beside K calls of
+    ug_groth16_verify_batch_records (of this build, and of --parent-lib), keys parsed inside the timed region in all of them. The K
+    keys are K copies of the fixture's key text: the library does not compare keys, so every copy is parsed, checked and given its
+    own segment, which is the work of K distinct keys; the caller's order interleaves the keys, so the keyed call regroups. Then the
+    same with one bad record under one key, and with 1 % bad records under every key with the judge on."""
+    from ultragroth_amd._lib import VerifyBatchOptions, VerifyBatchStatsEx, VerifyBatchStatsKeys
+    import ultragroth_amd as ug
+    n_pub = len(json.loads(pool[0][1]))
+    packed = [(ug.proof_pack(pr), ug.inputs_pack(pub, n_pub)) for pr, pub in pool]
+    per = 1 << a.per_key
+    vp = C.c_void_p
+    parent = None
+    if a.parent_lib:
+        parent = C.CDLL(os.path.abspath(a.parent_lib))
+        parent.ug_groth16_verify_batch_records.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+        parent.ug_verify_batch_kernel_ms.argtypes = [vp]
+        parent.ug_verify_batch_kernel_ms.restype = None
+
+    def spoiled(block):
+        v = int.from_bytes(block[:32], "little") + 1
+        return v.to_bytes(32, "little") + block[32:]
+
+    def options(judge):
+        return C.byref(VerifyBatchOptions(C.sizeof(VerifyBatchOptions), 1, -1, -1)) if judge else None
+
+    def one_key_calls(lib, K, bad, judge):
+        """K calls, one per key, of per records each; bad: positions (key, index within the key)"""
+        calls = []
+        for q in range(K):
+            blocks = [packed[(q * per + i) % len(packed)][1] for i in range(per)]
+            for kq, i in bad:
+                if kq == q:
+                    blocks[i] = spoiled(blocks[i])
+            calls.append((b"".join(packed[(q * per + i) % len(packed)][0] for i in range(per)), b"".join(blocks)))
+        verdicts, err, ex = (C.c_int * per)(), C.create_string_buffer(256), VerifyBatchStatsEx()
+        checks = singles = judged = 0
+        opt = options(judge)
+        t0 = time.perf_counter()
+        for q, (recs, ins) in enumerate(calls):
+            rc = lib.ug_groth16_verify_batch_records(a.device, per, recs, ins, n_pub, vk, verdicts, opt, C.byref(ex), err, 255)
+            wrong = [i for i in range(per) if (verdicts[i] != 0) != ((q, i) in bad)]
+            if rc == 2 or wrong:
+                raise RuntimeError("verify_batch_records: rc %d, %s, %d wrong verdicts" % (rc, err.value.decode(), len(wrong)))
+            checks += ex.base.batch_checks; singles += ex.base.single_checks; judged += ex.judged
+        dt = time.perf_counter() - t0
+        return dt, "batch_checks %d single_checks %d judged %d" % (checks, singles, judged)
+
+    def keyed_call(K, bad, judge):
+        n = K * per
+        recs, blocks, key_of = [], [], []
+        for i in range(per):                                                       # the caller's order: the keys interleaved
+            for q in range(K):
+                recs.append(packed[(q * per + i) % len(packed)][0])
+                blocks.append(spoiled(packed[(q * per + i) % len(packed)][1]) if (q, i) in bad else packed[(q * per + i) % len(packed)][1])
+                key_of.append(q)
+        recs, ins = b"".join(recs), b"".join(blocks)
+        keys = (C.c_char_p * K)(*([vk] * K))
+        ko, npub = (C.c_int * n)(*key_of), (C.c_int * K)(*([n_pub] * K))
+        verdicts, err, st = (C.c_int * n)(), C.create_string_buffer(256), VerifyBatchStatsKeys()
+        opt = options(judge)
+        t0 = time.perf_counter()
+        rc = L.ug_groth16_verify_batch_records_keys(a.device, 0, n, recs, ins, K, keys, ko, npub, verdicts, opt, C.byref(st), err, 255)
+        dt = time.perf_counter() - t0
+        wrong = [t for t in range(n) if (verdicts[t] != 0) != ((t % K, t // K) in bad)]
+        if rc == 2 or wrong:
+            raise RuntimeError("verify_batch_records_keys: rc %d, %s, %d wrong verdicts" % (rc, err.value.decode(), len(wrong)))
+        phase, ms = (C.c_double * 8)(), (C.c_double * 3)()
+        L.ug_verify_batch_phase_ms(phase)
+        L.ug_verify_batch_kernel_ms(ms)
+        b = st.ex.base
+        text = "batch_checks %d (key level %d) single_checks %d judged %d judge_launches %d segments %d tree_launches %d  kernels: miller %.1f  f12 forest %.2f  g1 forest %.2f ms" \
+            % (b.batch_checks, st.key_checks, b.single_checks, st.ex.judged, st.ex.judge_launches, st.segments, st.tree_launches, ms[0], ms[1], ms[2])
+        return dt, text, "  ".join("%s %.1f" % (name, v) for name, v in zip(PHASES, phase))
+
+    for K in [int(s) for s in a.keys.split(",")]:
+        one_pct = {(q, i) for q in range(K) for i in range(5, per, 100)}
+        for label, bad, judge in (("valid", set(), False), ("one bad record", {(K // 3, per // 3)}, False), ("1%% bad under every key (%d), judge on" % len(one_pct), one_pct, True)):
+            turns = ([("parent, K one-key calls", lambda: one_key_calls(parent, K, bad, judge))] if parent else []) + \
+                [("this build, K one-key calls", lambda: one_key_calls(L, K, bad, judge)), ("this build, ONE keyed call", lambda: keyed_call(K, bad, judge))]
+            for _, fn in turns:
+                fn()                                                               # warm-up of every path at this size, not timed
+            for rep in range(a.runs):
+                for name, fn in turns[rep % len(turns):] + turns[:rep % len(turns)]:
+                    out = fn()
+                    say("K=%d x 2^%d %s | %-28s run %d  wall %8.1f ms  %9.0f proofs/s  %s" % (K, a.per_key, label, name, rep, out[0] * 1e3, K * per / out[0], out[1]))
+                    if len(out) > 2 and rep == a.runs - 1:
+                        say("    split of the keyed call (ms): %s" % out[2])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="10,14,16")
@@ -164,6 +258,8 @@ def main():
     ap.add_argument("--format", default="plain", choices=["plain", "evm", "compressed", "all"], help="--records: the record layouts side by side")
     ap.add_argument("--parent-lib", default=None, help="--records --format: another build of the library, its plain records call in the same turns")
     ap.add_argument("--offsub-size", type=int, default=12, help="--records: log2 size of the batch whose every pi_b is off the subgroup (0: skip)")
+    ap.add_argument("--keys", default=None, help="K1,K2,..: K keys x 2^--per-key records as one keyed call beside K one-key calls (--parent-lib: also the parent's)")
+    ap.add_argument("--per-key", type=int, default=10, help="--keys: log2 of the records per key")
     a = ap.parse_args()
     import ultragroth_amd as ug
     from ultragroth_amd._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsEx
@@ -233,8 +329,10 @@ def main():
 
     say("# batch verification, Groth16, tests/golden/trapdoor/groth16 (%d distinct proofs repeated to fill N)" % len(pool))
     run(64, a.device)                                                  # warm-up: code objects, the context
-    if a.records:
-        if a.format != "plain" or a.parent_lib:
+    if a.records or a.keys:
+        if a.keys:
+            keys_report(a, L, vk, pool, say)
+        elif a.format != "plain" or a.parent_lib:
             formats_report(a, L, vk, pool, say)
         else:
             records_report(a, L, vk, pool, run, say)

@@ -1045,6 +1045,93 @@ def ultra_groth_verify_batch_records(records, inputs, n_pub, verification_key, d
                                  judge_min, format)
 
 
+# ---- several keys in one call (include/verifier.h: the _keys calls) ----
+def _keys_call(name, head, n, keys, key_of, tail, judge, search_width, judge_min):
+    """the shared part of the _keys calls: key texts, key_of, options, stats; `head` / `tail` are the arguments before n_keys and
+    between key_of and verdicts. Returns (verdicts, stats)."""
+    from ._lib import VerifyBatchOptions, VerifyBatchStats, VerifyBatchStatsKeys
+    if len(key_of) != n:
+        raise ValueError("as many key indices as proofs")
+    texts = [_enc_json(k) for k in keys]
+    ka = (C.c_char_p * max(len(texts), 1))(*texts)
+    ko = (C.c_int * max(n, 1))(*[int(q) for q in key_of])
+    verdicts = (C.c_int * max(n, 1))(*([-1] * max(n, 1)))
+    err = C.create_string_buffer(512)
+    opt = None
+    if not (judge is None and search_width is None and judge_min is None):
+        dflt = lambda v: -1 if v is None else int(v)
+        opt = C.byref(VerifyBatchOptions(C.sizeof(VerifyBatchOptions), int(bool(judge)), dflt(search_width), dflt(judge_min)))
+    stats = VerifyBatchStatsKeys()
+    rc = getattr(load(), name)(*(head + [len(texts), ka, ko] + tail + [verdicts, opt, C.byref(stats), err, 511]))
+    if rc == VERIFIER_ERROR:
+        raise VerifierError(err.value.decode(errors="replace"))
+    out = {f: getattr(stats.ex.base, f) for f, _ in VerifyBatchStats._fields_}
+    out.update({f: getattr(stats.ex, f) for f in ("judged", "judge_launches", "judge_ms")})
+    out.update({f: getattr(stats, f) for f in ("segments", "tree_launches", "key_checks")})
+    return list(verdicts[:n]), out
+
+
+def _verify_batch_keys(name, proofs, inputs, keys, key_of, device, judge, search_width, judge_min):
+    if len(proofs) != len(inputs):
+        raise ValueError("as many inputs as proofs")
+    n = len(proofs)
+    pa = (C.c_char_p * max(n, 1))(*[_enc_json(p) for p in proofs])
+    ia = (C.c_char_p * max(n, 1))(*[_enc_json(p) for p in inputs])
+    return _keys_call(name, [device, n, pa, ia], n, keys, key_of, [], judge, search_width, judge_min)
+
+
+def groth16_verify_batch_keys(proofs, inputs, keys, key_of, device=0, judge=None, search_width=None, judge_min=None):
+    """ug_groth16_verify_batch_keys (include/verifier.h): as groth16_verify_batch for proofs under several keys, one device pass and
+    one final exponentiation per 65536 proofs whatever the number of keys. keys: the verification keys (texts or parsed); key_of[i]:
+    the index of proof i's key. Proofs may come in any order; verdicts are in the caller's. Returns (verdicts, stats); stats carries
+    the judge's counters and segments, tree_launches, key_checks. VerifierError for a bad key_of, a key that does not parse
+    ("key <k>: ..."), or a device error."""
+    return _verify_batch_keys("ug_groth16_verify_batch_keys", proofs, inputs, keys, key_of, device, judge, search_width, judge_min)
+
+
+def ultra_groth_verify_batch_keys(proofs, inputs, keys, key_of, device=0, judge=None, search_width=None, judge_min=None):
+    return _verify_batch_keys("ug_ultra_groth_verify_batch_keys", proofs, inputs, keys, key_of, device, judge, search_width, judge_min)
+
+
+def inputs_pack_ragged(inputs, format=RECORDS_PLAIN):
+    """The input block of the records calls under several keys: every proof's inputs (public.json text, list, or an input block of
+    n x 32 plain bytes) one behind the other, each proof as many as its key has, in the byte order of `format`."""
+    out = []
+    for item in inputs:
+        block = bytes(item) if isinstance(item, (bytes, bytearray)) and len(item) % 32 == 0 and len(item) else inputs_pack(item)
+        out.append(block if format == RECORDS_PLAIN else inputs_convert(block, RECORDS_PLAIN, format))
+    return b"".join(out)
+
+
+def _verify_batch_records_keys(name, ultra, records, inputs, keys, key_of, device, format, judge, search_width, judge_min):
+    import json
+    size = _record_bytes(ultra, format)
+    records, inputs = bytes(records), bytes(inputs)
+    if len(records) % size:
+        raise ValueError("records: a multiple of %d bytes" % size)
+    n = len(records) // size
+    n_pub = []
+    for k in keys:                                                  # a key that does not parse is the library's to report
+        try:
+            j = json.loads(k) if isinstance(k, (str, bytes)) else k
+            n_pub.append(max(1, len(j["IC"]) - 1))
+        except (ValueError, KeyError, TypeError):
+            n_pub.append(1)
+    np_arr = (C.c_int * max(len(n_pub), 1))(*n_pub)
+    return _keys_call(name, [device, int(format), n, records or b"\0", inputs or b"\0"], n, keys, key_of, [np_arr], judge, search_width, judge_min)
+
+
+def groth16_verify_batch_records_keys(records, inputs, keys, key_of, device=0, format=RECORDS_PLAIN, judge=None, search_width=None, judge_min=None):
+    """ug_groth16_verify_batch_records_keys: groth16_verify_batch_keys for packed records of `format`. inputs: the ragged block of
+    inputs_pack_ragged -- proof i owns as many 32-byte values as its key has public inputs (len(IC) - 1, read from the key here)."""
+    return _verify_batch_records_keys("ug_groth16_verify_batch_records_keys", False, records, inputs, keys, key_of, device, format, judge, search_width, judge_min)
+
+
+def ultra_groth_verify_batch_records_keys(records, inputs, keys, key_of, device=0, format=RECORDS_PLAIN, judge=None, search_width=None, judge_min=None):
+    return _verify_batch_records_keys("ug_ultra_groth_verify_batch_records_keys", True, records, inputs, keys, key_of, device, format, judge, search_width,
+                                      judge_min)
+
+
 class _ProverBase:
     _create = _prove = _destroy = _public_size_fn = None
     _proof_size = staticmethod(groth16_proof_size)

@@ -51,7 +51,9 @@ VERIFIER_SYMBOLS = ["groth16_verify", "ultra_groth_verify",        # include/ver
                     "ug_proof_pack", "ug_inputs_pack", "ug_proof_unpack", "ug_inputs_unpack", "ug_test_verify_records_passes",
                     "ug_verify_batch_phase_ms",
                     "ug_proof_record_bytes", "ug_groth16_verify_batch_records_fmt", "ug_ultra_groth_verify_batch_records_fmt",
-                    "ug_proof_record_convert", "ug_inputs_convert", "ug_test_records_ingest", "ug_test_fq2_sqrt"]
+                    "ug_proof_record_convert", "ug_inputs_convert", "ug_test_records_ingest", "ug_test_fq2_sqrt",
+                    "ug_groth16_verify_batch_keys", "ug_ultra_groth_verify_batch_keys",
+                    "ug_groth16_verify_batch_records_keys", "ug_ultra_groth_verify_batch_records_keys", "ug_test_tree_forest"]
 
 
 class VerifyBatchStats(C.Structure):
@@ -66,6 +68,11 @@ class VerifyBatchOptions(C.Structure):
 
 class VerifyBatchStatsEx(C.Structure):
     _fields_ = [("base", VerifyBatchStats), ("judged", C.c_ulonglong), ("judge_launches", C.c_ulonglong), ("judge_ms", C.c_double)]
+
+
+class VerifyBatchStatsKeys(C.Structure):
+    """ug_verify_batch_stats_keys: the _keys calls' statistics"""
+    _fields_ = [("ex", VerifyBatchStatsEx), ("segments", C.c_ulonglong), ("tree_launches", C.c_ulonglong), ("key_checks", C.c_ulonglong)]
 
 
 OUTER_SYMBOLS = [
@@ -281,6 +288,11 @@ def load():
         getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
     for n in ("ug_groth16_verify_batch_records_fmt", "ug_ultra_groth_verify_batch_records_fmt"):
         getattr(L, n).argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_char_p, vp, vp, vp, C.c_char_p, C.c_ulong]
+    for n in ("ug_groth16_verify_batch_keys", "ug_ultra_groth_verify_batch_keys"):
+        getattr(L, n).argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_char_p, C.c_ulong]
+    for n in ("ug_groth16_verify_batch_records_keys", "ug_ultra_groth_verify_batch_records_keys"):
+        getattr(L, n).argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_ulong]
+    L.ug_test_tree_forest.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     L.ug_proof_record_bytes.argtypes = [C.c_int, C.c_int]; L.ug_proof_record_bytes.restype = C.c_ulong
     L.ug_proof_record_convert.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp]
     L.ug_inputs_convert.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp]

@@ -5,11 +5,15 @@
 // f12_tree_kernel       one level of the binary tree over the f_i: node j = node 2j * node 2j+1 of the level below, an odd last
 // g1_tree_kernel        node copied up; the G1 twin adds. One launch per level; every level stays in HBM, so that a rejected
 //                       batch can be searched from the root without the device.
+// f12_forest_kernel     the same level for a pass of several keys: every segment (the proofs of one key) has its own tree, and one
+// g1_forest_kernel      launch makes a level of all of them; a lane finds its segment in the step's table (pairing_dev.hpp:
+//                       ForestPlan). Launches per tree: ceil(log2(largest segment)), whatever the number of keys.
 // vkx_mul_kernel        the judge of a rejected pass, first step: lane (i, c) = column c of suspect i's vkX, scalar_ic * IC_c by the
 // vkx_sum_kernel        256-bit ladder; then one block per suspect adds its columns (lanes stride the columns, a tree over the 64
 //                       partial sums in LDS) and leaves -vkX_i as an affine G1 record.
 // judge_kernel          lane i: suspect i's own equation -- the Miller loops of its three (four) pairs times miller(beta, -alpha),
 //                       the final exponentiation's is-one test, one verdict word. No random scalar: the single verifier's answer.
+//                       judge_kernel<true> takes the key's G2 points and miller(beta, -alpha) from a table by a per-suspect index.
 // ratio_judge_kernel    lane i: e(x_i, Q) = e(y_i, G2) for two G1 records of a key -- two Miller loops, the is-one test, one word
 //                       (the ratio test of Backend::ratio).
 // final_exp_kernel      one lane of the final exponentiation alone (ug_test_final_exp).
@@ -64,6 +68,45 @@ __global__ __launch_bounds__(64) void g1_tree_kernel(const u32* __restrict__ src
             dst + (j * k + s) * XYZZ_WORDS);
 }
 
+// The segment-aware forms: one launch makes level l + 1 of EVERY segment of a pass (pairing_dev.hpp: ForestPlan). Lane t writes
+// node dst + t; its segment is the last i with start[i] <= t, found by bisection in the step's table (segs >= 1 entries and the
+// total behind them, so every t < start[segs] has one), and its children are nodes src[i] + 2 j and 2 j + 1 of the level below.
+struct ForestStep {
+    const u32* start;           // segs + 1
+    const u32* src;             // segs: where the segment's nodes of the level below begin
+    const u32* n_src;           // segs: how many there are
+    u32 segs, dst;              // dst: where the level above begins
+};
+__device__ __forceinline__ bool forest_lane(const ForestStep& st, u32 t, size_t& left, bool& pair) {
+    if (t >= st.start[st.segs]) return false;
+    u32 lo = 0, hi = st.segs;
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (st.start[mid] <= t) lo = mid; else hi = mid;
+    }
+    const u32 j = t - st.start[lo];
+    left = (size_t)st.src[lo] + 2 * (size_t)j;
+    pair = 2 * j + 1 < st.n_src[lo];
+    return true;
+}
+
+__global__ UG_ONE_WAVE void f12_forest_kernel(PairingConsts kc, const u32* __restrict__ src, ForestStep st, u32* __restrict__ dst) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    size_t left;
+    bool pair;
+    if (!forest_lane(st, t, left, pair)) return;
+    f12_node(kc, src + left * F12_WORDS, pair ? src + (left + 1) * F12_WORDS : nullptr, dst + ((size_t)st.dst + t) * F12_WORDS);
+}
+
+__global__ __launch_bounds__(64) void g1_forest_kernel(const u32* __restrict__ src, ForestStep st, int k, u32* __restrict__ dst) {
+    const u32 lane = blockIdx.x * blockDim.x + threadIdx.x, t = lane / (u32)k, s = lane % (u32)k;
+    size_t left;
+    bool pair;
+    if (!forest_lane(st, t, left, pair)) return;
+    g1_node(src + (left * k + s) * XYZZ_WORDS, pair ? src + ((left + 1) * k + s) * XYZZ_WORDS : nullptr,
+            dst + (((size_t)st.dst + t) * k + s) * XYZZ_WORDS);
+}
+
 __global__ __launch_bounds__(64) void vkx_mul_kernel(const u32* __restrict__ points, const u32* __restrict__ scalars, size_t lanes, int cols,
                                                      u32* __restrict__ terms) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,11 +136,18 @@ __global__ __launch_bounds__(64) void vkx_sum_kernel(const u32* __restrict__ ter
     if (lane == 0) vkx_finish(acc, neg_vkx + i * G1_WORDS);
 }
 
+// KEYED: key_g2 and f_ab are tables with one entry per key, and key_of[i] says which one suspect i is judged under
+template <bool KEYED>
 __global__ UG_ONE_WAVE void judge_kernel(FinalExpConsts kc, const u32* __restrict__ a, const u32* __restrict__ b, const u32* __restrict__ neg_vkx,
-                                         const u32* __restrict__ g, const u32* __restrict__ key_g2, const u32* __restrict__ f_ab, int n, int k,
-                                         u32* __restrict__ verdict) {
+                                         const u32* __restrict__ g, const u32* __restrict__ key_g2, const u32* __restrict__ f_ab,
+                                         const u32* __restrict__ key_of, int n, int k, u32* __restrict__ verdict) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n) return;
+    if constexpr (KEYED) {
+        const size_t q = key_of[i];
+        key_g2 += q * (size_t)(1 + k) * G2_WORDS;
+        f_ab += q * F12_WORDS;
+    }
     verdict[i] = judge_proof(kc, a + i * G1_WORDS, b + i * G2_WORDS, neg_vkx + i * G1_WORDS, g + i * k * G1_WORDS, k, key_g2, f_ab) ? 1u : 0u;
 }
 
@@ -253,27 +303,72 @@ unsigned blocks(size_t lanes) { return (unsigned)((lanes + 63) / 64); }
 }  // namespace
 
 // the kernels of a pass over arrays that are on the device already; both trees come back to the host
-static void run_pass(const PairingConsts& kc, const u32* a, const u32* b, const u32* g, const u32* r, int n_, int k_, u32* f_tree, u32* g_tree,
-                     double kernel_ms[3]) {
-    const size_t n = (size_t)n_, k = (size_t)k_, nodes = tree_nodes(n);
+// plan: the pass's segments (null: one, the tree kernels; else the forest kernels, whose trees are the plan's forest); leaf_f / leaf_g:
+// the leaves are given (host arrays) and no Miller loop runs. Returns the tree launches.
+static int run_pass(const PairingConsts& kc, const u32* a, const u32* b, const u32* g, const u32* r, int n_, int k_, u32* f_tree, u32* g_tree,
+                    double kernel_ms[3], const ForestPlan* plan = nullptr, const u32* leaf_f = nullptr, const u32* leaf_g = nullptr) {
+    const size_t n = (size_t)n_, k = (size_t)k_, nodes = plan ? plan->nodes : tree_nodes(n);
+    if (plan && (plan->size.empty() || plan->level_base.size() != plan->step.size() + 1 || plan->off.back()[0] + plan->size.back() != n))
+        throw std::invalid_argument("run_pass: the segments do not cover the pass");
+    if ((leaf_f || leaf_g) && !(plan && leaf_f && leaf_g)) throw std::invalid_argument("run_pass: given leaves need both arrays and a plan");
     DevBuf<u32> f(nodes * F12_WORDS), s(nodes * k * XYZZ_WORDS);
     Event t0(true), t1(true), t2(true), t3(true);
+    int launches = 0;
     UG_HIP(hipEventRecord(t0.e, nullptr));
-    hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a, b, g, r, n_, k_, f.get(), s.get());
-    UG_KERNEL_CHECK();
-    UG_HIP(hipEventRecord(t1.e, nullptr));
-    size_t off = 0;
-    for (size_t m = n; m > 1; m = (m + 1) / 2) {                    // level of m nodes at `off` -> (m + 1) / 2 nodes behind it
-        hipLaunchKernelGGL(f12_tree_kernel, dim3(blocks((m + 1) / 2)), dim3(64), 0, nullptr, kc, f.get() + off * F12_WORDS, (int)m, f.get() + (off + m) * F12_WORDS);
+    if (leaf_f) {
+        UG_HIP(hipMemcpy(f.get(), leaf_f, n * F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+        UG_HIP(hipMemcpy(s.get(), leaf_g, n * k * XYZZ_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    } else {
+        hipLaunchKernelGGL(miller_batch_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a, b, g, r, n_, k_, f.get(), s.get());
         UG_KERNEL_CHECK();
-        off += m;
     }
-    UG_HIP(hipEventRecord(t2.e, nullptr));
-    off = 0;
-    for (size_t m = n; m > 1; m = (m + 1) / 2) {
-        hipLaunchKernelGGL(g1_tree_kernel, dim3(blocks(((m + 1) / 2) * k)), dim3(64), 0, nullptr, s.get() + off * k * XYZZ_WORDS, (int)m, k_, s.get() + (off + m) * k * XYZZ_WORDS);
-        UG_KERNEL_CHECK();
-        off += m;
+    UG_HIP(hipEventRecord(t1.e, nullptr));
+    if (plan) {
+        // every step's table in one upload: start (segs + 1), src (segs), n_src (segs)
+        std::vector<u32> table;
+        std::vector<size_t> at;
+        for (const ForestPlan::Step& st : plan->step) {
+            if (st.src.empty() || st.start.size() != st.src.size() + 1 || st.n_src.size() != st.src.size()) throw std::invalid_argument("run_pass: bad forest step");
+            at.push_back(table.size());
+            table.insert(table.end(), st.start.begin(), st.start.end());
+            table.insert(table.end(), st.src.begin(), st.src.end());
+            table.insert(table.end(), st.n_src.begin(), st.n_src.end());
+        }
+        DevBuf<u32> dt(std::max<size_t>(table.size(), 1));
+        if (!table.empty()) UG_HIP(hipMemcpy(dt.get(), table.data(), table.size() * sizeof(u32), hipMemcpyHostToDevice));
+        auto step_of = [&](size_t l) {
+            const u32 segs = (u32)plan->step[l].src.size();
+            const u32* p = dt.get() + at[l];
+            // (the last node a lane of this step may write is level_base[l + 1] + lanes - 1 < nodes, by the plan's construction)
+            return ForestStep{p, p + segs + 1, p + 2 * segs + 1, segs, (u32)plan->level_base[l + 1]};
+        };
+        for (size_t l = 0; l < plan->step.size(); l++) {
+            hipLaunchKernelGGL(f12_forest_kernel, dim3(blocks(plan->step[l].start.back())), dim3(64), 0, nullptr, kc, f.get(), step_of(l), f.get());
+            UG_KERNEL_CHECK();
+            launches++;
+        }
+        UG_HIP(hipEventRecord(t2.e, nullptr));
+        for (size_t l = 0; l < plan->step.size(); l++) {
+            hipLaunchKernelGGL(g1_forest_kernel, dim3(blocks(plan->step[l].start.back() * k)), dim3(64), 0, nullptr, s.get(), step_of(l), k_, s.get());
+            UG_KERNEL_CHECK();
+            launches++;
+        }
+    } else {
+        size_t off = 0;
+        for (size_t m = n; m > 1; m = (m + 1) / 2) {                // level of m nodes at `off` -> (m + 1) / 2 nodes behind it
+            hipLaunchKernelGGL(f12_tree_kernel, dim3(blocks((m + 1) / 2)), dim3(64), 0, nullptr, kc, f.get() + off * F12_WORDS, (int)m, f.get() + (off + m) * F12_WORDS);
+            UG_KERNEL_CHECK();
+            off += m;
+            launches++;
+        }
+        UG_HIP(hipEventRecord(t2.e, nullptr));
+        off = 0;
+        for (size_t m = n; m > 1; m = (m + 1) / 2) {
+            hipLaunchKernelGGL(g1_tree_kernel, dim3(blocks(((m + 1) / 2) * k)), dim3(64), 0, nullptr, s.get() + off * k * XYZZ_WORDS, (int)m, k_, s.get() + (off + m) * k * XYZZ_WORDS);
+            UG_KERNEL_CHECK();
+            off += m;
+            launches++;
+        }
     }
     UG_HIP(hipEventRecord(t3.e, nullptr));
     UG_HIP(hipMemcpy(f_tree, f.get(), nodes * F12_WORDS * sizeof(u32), hipMemcpyDeviceToHost));
@@ -283,18 +378,23 @@ static void run_pass(const PairingConsts& kc, const u32* a, const u32* b, const 
     UG_HIP(hipEventElapsedTime(&ms[1], t1.e, t2.e));
     UG_HIP(hipEventElapsedTime(&ms[2], t2.e, t3.e));
     for (int i = 0; i < 3; i++) kernel_ms[i] = ms[i];
+    return launches;
 }
 
 void pairing_batch_device(int device, const PairingConsts& kc, PairingBatch& pb) {
     if (pb.n <= 0 || pb.n > PAIRING_PASS || (pb.k != 1 && pb.k != 2)) throw std::invalid_argument("pairing_batch_device: bad shape");
     UG_HIP(hipSetDevice(device));
     const size_t n = (size_t)pb.n, k = (size_t)pb.k;
+    if (pb.leaf_f || pb.leaf_g) {                                   // only the forest kernels, over given leaves
+        pb.tree_launches = run_pass(kc, nullptr, nullptr, nullptr, nullptr, pb.n, pb.k, pb.f_tree, pb.g_tree, pb.kernel_ms, pb.plan, pb.leaf_f, pb.leaf_g);
+        return;
+    }
     DevBuf<u32> a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), r(n * 4);
     UG_HIP(hipMemcpy(a.get(), pb.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(b.get(), pb.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(g.get(), pb.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(r.get(), pb.r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
-    run_pass(kc, a.get(), b.get(), g.get(), r.get(), pb.n, pb.k, pb.f_tree, pb.g_tree, pb.kernel_ms);
+    pb.tree_launches = run_pass(kc, a.get(), b.get(), g.get(), r.get(), pb.n, pb.k, pb.f_tree, pb.g_tree, pb.kernel_ms, pb.plan);
 }
 
 // ---- the resident form: the pass's raw records cross PCIe once and its arrays never leave the device ---------------------
@@ -351,7 +451,7 @@ void ResidentBatch::run(const PairingConsts& kc, const u32* keep, int kept, cons
     const size_t n = (size_t)kept, k = (size_t)m.k;
     DevBuf<u32> rd(n * 4);
     UG_HIP(hipMemcpy(rd.get(), r, n * 4 * sizeof(u32), hipMemcpyHostToDevice));
-    if (!keep) { run_pass(kc, m.a.get(), m.b.get(), m.g.get(), rd.get(), kept, m.k, f_tree, g_tree, kernel_ms); return; }
+    if (!keep) { tree_launches = run_pass(kc, m.a.get(), m.b.get(), m.g.get(), rd.get(), kept, m.k, f_tree, g_tree, kernel_ms, plan); return; }
     for (size_t i = 0; i < n; i++)                                  // the gather reads row keep[i]: inside the pass, ascending
         if (keep[i] >= (u32)m.n || (i && keep[i] <= keep[i - 1])) throw std::invalid_argument("ResidentBatch: bad index list");
     DevBuf<u32> index(n), a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS);
@@ -363,37 +463,62 @@ void ResidentBatch::run(const PairingConsts& kc, const u32* keep, int kept, cons
     gather(m.a.get(), G1_WORDS, a.get());
     gather(m.b.get(), G2_WORDS, b.get());
     gather(m.g.get(), (int)k * G1_WORDS, g.get());
-    run_pass(kc, a.get(), b.get(), g.get(), rd.get(), kept, m.k, f_tree, g_tree, kernel_ms);
+    tree_launches = run_pass(kc, a.get(), b.get(), g.get(), rd.get(), kept, m.k, f_tree, g_tree, kernel_ms, plan);
 }
 
 // the vkx step keeps at most this many XYZZ products on the device at a time (144 bytes each)
 constexpr size_t VKX_CHUNK_TERMS = (size_t)1 << 20;
 
 void pairing_judge_device(int device, const FinalExpConsts& kc, PairingJudge& pj) {
-    if (pj.n <= 0 || pj.n > PAIRING_PASS || (pj.k != 1 && pj.k != 2) || pj.cols <= 0) throw std::invalid_argument("pairing_judge_device: bad shape");
+    const bool keyed = pj.n_keys > 1;
+    if (pj.n <= 0 || pj.n > PAIRING_PASS || (pj.k != 1 && pj.k != 2) || pj.n_keys < 1 || (!keyed && pj.cols <= 0) || (keyed && (!pj.key_first || !pj.key_cols)))
+        throw std::invalid_argument("pairing_judge_device: bad shape");
     UG_HIP(hipSetDevice(device));
-    const size_t n = (size_t)pj.n, k = (size_t)pj.k, cols = (size_t)pj.cols;
-    const size_t chunk = std::min(n, std::max<size_t>(1, VKX_CHUNK_TERMS / cols));           // suspects per launch of the vkx step
-    DevBuf<u32> a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), points(cols * G1_WORDS), key((1 + k) * G2_WORDS), fab(F12_WORDS);
-    DevBuf<u32> scalars(chunk * cols * 8), terms(chunk * cols * XYZZ_WORDS), nvkx(n * G1_WORDS), verdict(n);
+    const size_t n = (size_t)pj.n, k = (size_t)pj.k, n_keys = (size_t)pj.n_keys;
+    // per key: its suspects first[q] .. first[q + 1], its columns, and where its points begin; one key: all suspects, pj.cols
+    std::vector<size_t> first(n_keys + 1, 0), kcols(n_keys, 0), point_at(n_keys + 1, 0);
+    std::vector<u32> key_of(n, 0);
+    size_t max_cols = 0;
+    for (size_t q = 0; q < n_keys; q++) {
+        kcols[q] = keyed ? (size_t)std::max(pj.key_cols[q], 0) : (size_t)pj.cols;
+        first[q + 1] = keyed ? (size_t)std::max(pj.key_first[q + 1], 0) : n;
+        if (!kcols[q] || first[q + 1] < first[q] || first[q + 1] > n) throw std::invalid_argument("pairing_judge_device: bad key table");
+        point_at[q + 1] = point_at[q] + kcols[q];
+        max_cols = std::max(max_cols, kcols[q]);
+        for (size_t i = first[q]; i < first[q + 1]; i++) key_of[i] = (u32)q;
+    }
+    if (first[0] != 0 || first[n_keys] != n) throw std::invalid_argument("pairing_judge_device: bad key table");
+    const size_t all_cols = point_at[n_keys];
+    const size_t chunk = std::min(n, std::max<size_t>(1, VKX_CHUNK_TERMS / max_cols));       // suspects per launch of the vkx step
+    DevBuf<u32> a(n * G1_WORDS), b(n * G2_WORDS), g(n * k * G1_WORDS), points(all_cols * G1_WORDS), key(n_keys * (1 + k) * G2_WORDS), fab(n_keys * F12_WORDS);
+    DevBuf<u32> scalars(chunk * max_cols * 8), terms(chunk * max_cols * XYZZ_WORDS), nvkx(n * G1_WORDS), verdict(n), dkey_of(n);
     Event t0(true), t1(true), t2(true);
     UG_HIP(hipMemcpy(a.get(), pj.a, n * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(b.get(), pj.b, n * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipMemcpy(g.get(), pj.g, n * k * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(points.get(), pj.points, cols * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(key.get(), pj.key_g2, (1 + k) * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
-    UG_HIP(hipMemcpy(fab.get(), pj.f_alpha_beta, F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(points.get(), pj.points, all_cols * G1_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(key.get(), pj.key_g2, n_keys * (1 + k) * G2_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    UG_HIP(hipMemcpy(fab.get(), pj.f_alpha_beta, n_keys * F12_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+    if (keyed) UG_HIP(hipMemcpy(dkey_of.get(), key_of.data(), n * sizeof(u32), hipMemcpyHostToDevice));
     UG_HIP(hipEventRecord(t0.e, nullptr));
-    for (size_t first = 0; first < n; first += chunk) {
-        const size_t m = std::min(chunk, n - first);
-        UG_HIP(hipMemcpy(scalars.get(), pj.scalars + first * cols * 8, m * cols * 8 * sizeof(u32), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(vkx_mul_kernel, dim3(blocks(m * cols)), dim3(64), 0, nullptr, points.get(), scalars.get(), m * cols, pj.cols, terms.get());
-        UG_KERNEL_CHECK();
-        hipLaunchKernelGGL(vkx_sum_kernel, dim3((unsigned)m), dim3(64), 0, nullptr, terms.get(), pj.cols, nvkx.get() + first * G1_WORDS);
-        UG_KERNEL_CHECK();
+    const u32* sc = pj.scalars;                                     // the next key's scalars
+    for (size_t q = 0; q < n_keys; q++) {                           // the vkx step, once per key
+        const size_t cols = kcols[q];
+        for (size_t at = first[q]; at < first[q + 1]; at += chunk) {
+            const size_t m = std::min(chunk, first[q + 1] - at);
+            UG_HIP(hipMemcpy(scalars.get(), sc, m * cols * 8 * sizeof(u32), hipMemcpyHostToDevice));
+            sc += m * cols * 8;
+            hipLaunchKernelGGL(vkx_mul_kernel, dim3(blocks(m * cols)), dim3(64), 0, nullptr, points.get() + point_at[q] * G1_WORDS, scalars.get(), m * cols, (int)cols, terms.get());
+            UG_KERNEL_CHECK();
+            hipLaunchKernelGGL(vkx_sum_kernel, dim3((unsigned)m), dim3(64), 0, nullptr, terms.get(), (int)cols, nvkx.get() + at * G1_WORDS);
+            UG_KERNEL_CHECK();
+        }
     }
     UG_HIP(hipEventRecord(t1.e, nullptr));
-    hipLaunchKernelGGL(judge_kernel, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.get(), b.get(), nvkx.get(), g.get(), key.get(), fab.get(), pj.n, pj.k, verdict.get());
+    if (keyed)
+        hipLaunchKernelGGL(judge_kernel<true>, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.get(), b.get(), nvkx.get(), g.get(), key.get(), fab.get(), dkey_of.get(), pj.n, pj.k, verdict.get());
+    else
+        hipLaunchKernelGGL(judge_kernel<false>, dim3(blocks(n)), dim3(64), 0, nullptr, kc, a.get(), b.get(), nvkx.get(), g.get(), key.get(), fab.get(), nullptr, pj.n, pj.k, verdict.get());
     UG_KERNEL_CHECK();
     UG_HIP(hipEventRecord(t2.e, nullptr));
     UG_HIP(hipMemcpy(pj.verdict, verdict.get(), n * sizeof(u32), hipMemcpyDeviceToHost));

@@ -318,40 +318,74 @@ struct BatchTrace {
     unsigned long long in_place = 0, gathered = 0;      // ... and its passes over packed records: arrays used in place / compacted first
 } g_trace;
 
-// one pass: the proofs idx[0..m) of the call, their trees and prefix sums
-struct Pass {
-    const Key& key;
-    size_t m, cols;
+// The trees of one device pass: a forest with one tree per segment -- the proofs of one key, contiguous in the pass
+// (pairing_dev.hpp: ForestPlan). A call under one key has one segment, and the forest is its tree.
+struct Forest {
+    ForestPlan plan;
     int k;
     std::vector<u32> f_tree, g_tree;
+    Forest(const std::vector<u32>& sizes, int k_) : plan(sizes.data(), sizes.size()), k(k_), f_tree(plan.nodes * F12_WORDS), g_tree(plan.nodes * k_ * XYZZ_WORDS) {}
+    // the leaves of the whole pass, one Miller loop each on the host threads
+    void host_leaves(const u32* a, const u32* b, const u32* g, const u32* r) {
+        const PairingConsts& kc = consts();
+        parallel_for(plan.off.back()[0] + plan.size.back(), [&](size_t i) {
+            batch_leaf(kc, a + i * G1_WORDS, b + i * G2_WORDS, g + i * k * G1_WORDS, k, r + i * 4, &f_tree[i * F12_WORDS], &g_tree[i * k * XYZZ_WORDS]);
+        });
+    }
+};
+
+// one segment of a pass: m proofs of one key, a view of their trees in the pass's forest, and their prefix sums
+struct Pass {
+    const Key& key;
+    size_t m, cols, first;                 // first: the position of the segment's first proof in the pass
+    int k;
+    u32* f_tree;                           // the forest's arrays; node j of `level` is node level_off[level] + j of them
+    u32* g_tree;
     std::vector<Fr> prefix;                // (m + 1) x cols: S, t_0 .. t_{nPublic-1}, [t_rand]
     std::vector<size_t> level_off, level_size;
     unsigned long long checks = 0;
 
-    Pass(const Key& key_, size_t m_) : key(key_), m(m_), cols(key_.cols()), k(key_.k()) {
-        size_t off = 0;
-        for (size_t n = m;; n = (n + 1) / 2) { level_off.push_back(off); level_size.push_back(n); off += n; if (n <= 1) break; }
-        f_tree.resize(off * F12_WORDS);
-        g_tree.resize(off * k * XYZZ_WORDS);
+    Pass(const Key& key_, Forest& forest, size_t s)
+        : key(key_), m(forest.plan.size[s]), cols(key_.cols()), first(forest.plan.first[s]), k(key_.k()), f_tree(forest.f_tree.data()), g_tree(forest.g_tree.data()),
+          level_off(forest.plan.off[s]) {
+        for (size_t n = m;; n = (n + 1) / 2) { level_size.push_back(n); if (n <= 1) break; }
     }
-    // the batch equation over the proofs of node j of `level`
-    bool node_ok(size_t level, size_t j) {
-        checks++;
+    // node j of `level`: the product of its proofs' miller(B_i, r_i A_i) in f, and the fixed pairs of its batch equation appended
+    void node_pairs(size_t level, size_t j, F12& f, std::vector<G1A>& g1, std::vector<G2A>& g2) const {
         const size_t lo = j << level, hi = std::min(m, (j + 1) << level), node = level_off[level] + j;
         std::vector<std::vector<u32>> sc(cols, std::vector<u32>(8));
         for (size_t c = 0; c < cols; c++) to_normal(sc[c].data(), sub<1>(prefix[hi * cols + c], prefix[lo * cols + c]));
         G1XYZZ vkx = xyzz_mul_scalar_w4(to_xyzz(key.ic[0]), sc[0].data());
         for (size_t c = 1; c < key.ic.size(); c++) vkx = xyzz_add(vkx, xyzz_mul_scalar_w4(to_xyzz(key.ic[c]), sc[c].data()));
         if (key.ultra) vkx = xyzz_add(vkx, xyzz_mul_scalar_w4(to_xyzz(key.ic_rand), sc[cols - 1].data()));
-        std::vector<G1A> g1{g1_neg(from_xyzz(xyzz_mul_scalar_w4(to_xyzz(key.alpha), sc[0].data()))), g1_neg(from_xyzz(vkx))};
-        std::vector<G2A> g2{key.beta, key.gamma};
+        g1.push_back(g1_neg(from_xyzz(xyzz_mul_scalar_w4(to_xyzz(key.alpha), sc[0].data())))); g2.push_back(key.beta);
+        g1.push_back(g1_neg(from_xyzz(vkx))); g2.push_back(key.gamma);
         for (int s = 0; s < k; s++) {
             g1.push_back(g1_neg(from_xyzz(xyzz_load(&g_tree[(node * k + s) * XYZZ_WORDS]))));
             g2.push_back(key.delta[s]);
         }
-        F12 f;                                                      // the product of the node's miller(B_i, r_i A_i)
         f12_load(f, &f_tree[node * F12_WORDS]);
+    }
+    // the batch equation over the proofs of node j of `level`
+    bool node_ok(size_t level, size_t j) {
+        checks++;
+        F12 f;
+        std::vector<G1A> g1;
+        std::vector<G2A> g2;
+        node_pairs(level, j, f, g1, g2);
         return pairing_product_is_one(f, g1, g2);
+    }
+    // The segment's value in the pass's one equation: its root times the Miller loops of its fixed pairs, on the calling thread
+    // (the segments of a pass are spread over the host threads). The pass holds when the product of these is one after ONE final
+    // exponentiation.
+    F12 root_value() const {
+        F12 f;
+        std::vector<G1A> g1;
+        std::vector<G2A> g2;
+        node_pairs(level_size.size() - 1, 0, f, g1, g2);
+        for (size_t i = 0; i < g1.size(); i++)
+            if (pair_live(g1[i], g2[i])) f = f12_mul(consts(), f, miller(consts(), g2[i], g1[i]));
+        return f;
     }
     // node j of `level` failed: the positions (within the pass) that the single verifier has to judge
     void walk(size_t level, size_t j, std::vector<size_t>& suspects) {
@@ -383,26 +417,32 @@ struct Pass {
             level--;
         }
     }
-    void host_trees(const u32* a, const u32* b, const u32* g, const u32* r) {
+    // the segment's tree above its leaves (Forest::host_leaves), on the host; spread: over the host threads, level by level
+    void host_trees(bool spread) {
         const PairingConsts& kc = consts();
-        parallel_for(m, [&](size_t i) {
-            batch_leaf(kc, a + i * G1_WORDS, b + i * G2_WORDS, g + i * k * G1_WORDS, k, r + i * 4, &f_tree[i * F12_WORDS], &g_tree[i * k * XYZZ_WORDS]);
-        });
         for (size_t l = 0; l + 1 < level_size.size(); l++) {
             const size_t n_src = level_size[l];
             const u32* fs = &f_tree[level_off[l] * F12_WORDS];
             const u32* gs = &g_tree[level_off[l] * k * XYZZ_WORDS];
             u32* fd = &f_tree[level_off[l + 1] * F12_WORDS];
             u32* gd = &g_tree[level_off[l + 1] * k * XYZZ_WORDS];
-            parallel_for(level_size[l + 1], [&](size_t j) {
+            auto node = [&](size_t j) {
                 const bool pair = 2 * j + 1 < n_src;
                 f12_node(kc, fs + 2 * j * F12_WORDS, pair ? fs + (2 * j + 1) * F12_WORDS : nullptr, fd + j * F12_WORDS);
                 for (int s = 0; s < k; s++)
                     g1_node(gs + (2 * j * k + s) * XYZZ_WORDS, pair ? gs + ((2 * j + 1) * k + s) * XYZZ_WORDS : nullptr, gd + (j * k + s) * XYZZ_WORDS);
-            });
+            };
+            if (spread) parallel_for(level_size[l + 1], node);
+            else for (size_t j = 0; j < level_size[l + 1]; j++) node(j);
         }
     }
 };
+// The host forest of a pass (device < 0): the leaves are there; every segment's tree by the loop above. Few segments: each level
+// over the host threads; many: a segment per thread.
+void host_forest(std::vector<Pass>& segs) {
+    if (segs.size() < 16) { for (Pass& p : segs) p.host_trees(true); return; }
+    parallel_for(segs.size(), [&](size_t s) { segs[s].host_trees(false); });
+}
 
 struct Ctx {                               // a device context for the subgroup check of the B points
     ug_ctx* c = nullptr;
@@ -426,44 +466,69 @@ void pack_points(const std::vector<BatchProof>& proofs, const size_t* idx, size_
 
 // The suspects sus[] of a call (positions in `proofs`), each decided by judge_proof: on `device` in launches of at most PAIRING_PASS,
 // on host threads for device < 0. valid[s] answers suspect s.
-void judge_suspects(const Key& key, int device, const std::vector<BatchProof>& proofs, const std::vector<size_t>& sus, std::vector<char>& valid,
-                    ug_verify_batch_stats_ex& stats) {
-    const size_t n = sus.size(), k = (size_t)key.k(), cols = key.cols();
-    std::vector<u32> points(cols * G1_WORDS), key_g2((1 + k) * G2_WORDS), f_ab(F12_WORDS);
-    for (size_t c = 0; c < key.ic.size(); c++) g1_words(&points[c * G1_WORDS], key.ic[c]);
-    if (key.ultra) g1_words(&points[(cols - 1) * G1_WORDS], key.ic_rand);
-    g2_words(&key_g2[0], key.gamma);
-    for (size_t s = 0; s < k; s++) g2_words(&key_g2[(1 + s) * G2_WORDS], key.delta[s]);
-    const G1A nalpha = g1_neg(key.alpha);
-    f12_store(f_ab.data(), pair_live(nalpha, key.beta) ? miller(consts(), key.beta, nalpha) : f12_one());
+// key_of: the key of every proof of the call (empty: keys[0]); sus is ordered by key, so the suspects of a key are contiguous in every
+// launch, and a launch takes the keys it meets as a table (one key: the table is that key, the launch the one-key kernel).
+void judge_suspects(const std::vector<Key>& keys, const std::vector<int>& key_of, int device, const std::vector<BatchProof>& proofs, const std::vector<size_t>& sus,
+                    std::vector<char>& valid, ug_verify_batch_stats_ex& stats) {
+    const size_t n = sus.size(), k = (size_t)keys[0].k();
+    auto key_at = [&](size_t s) { return key_of.empty() ? (size_t)0 : (size_t)key_of[sus[s]]; };
     valid.assign(n, 0);
     for (size_t first = 0; first < n; first += PAIRING_PASS) {
         const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
-        std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS), scalars(m * cols * 8, 0), verdict(m, 0);
+        // the keys of this launch, in order: their suspects, columns, points, G2 points and miller(beta, -alpha)
+        std::vector<size_t> which;
+        std::vector<int> key_first, key_cols;
+        std::vector<size_t> slot(m), sc_at(m + 1, 0), point_at;
+        for (size_t i = 0; i < m; i++) {
+            if (which.empty() || which.back() != key_at(first + i)) { which.push_back(key_at(first + i)); key_first.push_back((int)i); }
+            slot[i] = which.size() - 1;
+            sc_at[i + 1] = sc_at[i] + keys[which.back()].cols() * 8;
+        }
+        key_first.push_back((int)m);
+        const size_t n_keys = which.size();
+        size_t all_cols = 0;
+        for (size_t q : which) { point_at.push_back(all_cols); key_cols.push_back((int)keys[q].cols()); all_cols += keys[q].cols(); }
+        std::vector<u32> points(all_cols * G1_WORDS), key_g2(n_keys * (1 + k) * G2_WORDS), f_ab(n_keys * F12_WORDS);
+        parallel_for(n_keys, [&](size_t q) {
+            const Key& key = keys[which[q]];
+            u32* pt = &points[point_at[q] * G1_WORDS];
+            for (size_t c = 0; c < key.ic.size(); c++) g1_words(pt + c * G1_WORDS, key.ic[c]);
+            if (key.ultra) g1_words(pt + (key.cols() - 1) * G1_WORDS, key.ic_rand);
+            u32* g2 = &key_g2[q * (1 + k) * G2_WORDS];
+            g2_words(g2, key.gamma);
+            for (size_t s = 0; s < k; s++) g2_words(g2 + (1 + s) * G2_WORDS, key.delta[s]);
+            const G1A nalpha = g1_neg(key.alpha);
+            f12_store(&f_ab[q * F12_WORDS], pair_live(nalpha, key.beta) ? miller(consts(), key.beta, nalpha) : f12_one());
+        });
+        std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS), scalars(sc_at[m], 0), verdict(m, 0);
         pack_points(proofs, &sus[first], m, (int)k, a.data(), b.data(), g.data());
         parallel_for(m, [&](size_t i) {
             const BatchProof& p = proofs[sus[first + i]];
-            u32* sc = &scalars[i * cols * 8];
+            const Key& key = keys[which[slot[i]]];
+            u32* sc = &scalars[sc_at[i]];
             sc[0] = 1;                                              // IC_0 itself
             for (size_t c = 0; c < p.in.plain.size(); c++) memcpy(sc + (1 + c) * 8, p.in.plain[c].data(), 8 * sizeof(u32));
-            if (key.ultra) memcpy(sc + (cols - 1) * 8, p.challenge, 8 * sizeof(u32));
+            if (key.ultra) memcpy(sc + (key.cols() - 1) * 8, p.challenge, 8 * sizeof(u32));
         });
         if (device < 0) {
             parallel_for(m, [&](size_t i) {
+                const size_t q = slot[i], cols = (size_t)key_cols[q];
                 G1XYZZ sum = xyzz_inf<Fq>();
                 u32 term[XYZZ_WORDS], nvkx[G1_WORDS];
                 for (size_t c = 0; c < cols; c++) {
-                    vkx_term(&points[c * G1_WORDS], &scalars[(i * cols + c) * 8], term);
+                    vkx_term(&points[(point_at[q] + c) * G1_WORDS], &scalars[sc_at[i] + c * 8], term);
                     sum = xyzz_add(sum, xyzz_load(term));
                 }
                 vkx_finish(sum, nvkx);
-                verdict[i] = judge_proof(consts(), &a[i * G1_WORDS], &b[i * G2_WORDS], nvkx, &g[i * k * G1_WORDS], (int)k, key_g2.data(), f_ab.data());
+                verdict[i] = judge_proof(consts(), &a[i * G1_WORDS], &b[i * G2_WORDS], nvkx, &g[i * k * G1_WORDS], (int)k, &key_g2[q * (1 + k) * G2_WORDS],
+                                         &f_ab[q * F12_WORDS]);
             });
         } else {
             const auto t0 = std::chrono::steady_clock::now();
             PairingJudge pj;
-            pj.n = (int)m; pj.k = (int)k; pj.cols = (int)cols; pj.a = a.data(); pj.b = b.data(); pj.g = g.data(); pj.scalars = scalars.data();
+            pj.n = (int)m; pj.k = (int)k; pj.cols = key_cols[0]; pj.a = a.data(); pj.b = b.data(); pj.g = g.data(); pj.scalars = scalars.data();
             pj.points = points.data(); pj.key_g2 = key_g2.data(); pj.f_alpha_beta = f_ab.data(); pj.verdict = verdict.data();
+            pj.n_keys = (int)n_keys; pj.key_first = key_first.data(); pj.key_cols = key_cols.data();
             pairing_judge_device(device, consts(), pj);
             const double ms = ms_since(t0);
             stats.base.device_ms += ms;
@@ -486,7 +551,17 @@ struct Source {
     virtual void parse(size_t i, BatchProof& p, size_t ic_size, bool points) const = 0;
     const uint8_t* records = nullptr;      // packed records, for the device to ingest (texts: none)
     int format = RECORDS_PLAIN;            // ... their layout
-    size_t n_pub = 0;                      // ... and their inputs per proof, the same for every proof
+    size_t n_pub = 0;                      // ... and their inputs per proof, the same for every proof of a call under one key
+    // several keys: the inputs per proof of every key, and where proof i's begin in the ragged input block (bytes); set by ragged()
+    std::vector<size_t> n_pub_of_key, inputs_at;
+    const int* key_of = nullptr;
+    bool records_call = false, keyed = false;      // the call takes packed records; it is a call under several keys
+    void ragged(const int* key_of_, const int* n_pub_, size_t n_keys, size_t count) {
+        key_of = key_of_;
+        for (size_t q = 0; q < n_keys; q++) n_pub_of_key.push_back((size_t)n_pub_[q]);
+        inputs_at.assign(count + 1, 0);
+        for (size_t i = 0; i < count; i++) inputs_at[i + 1] = inputs_at[i] + n_pub_of_key[(size_t)key_of[i]] * 32;
+    }
 };
 struct JsonSource : Source {
     const char* const* proofs;
@@ -503,12 +578,12 @@ struct JsonSource : Source {
 struct RecordSource : Source {
     const uint8_t* inputs;
     RecordSource(bool ultra_, int format_, const void* records_, const void* inputs_, int n_pub_) : inputs(static_cast<const uint8_t*>(inputs_)) {
-        ultra = ultra_; format = format_; records = static_cast<const uint8_t*>(records_); n_pub = (size_t)std::max(n_pub_, 0);
+        ultra = ultra_; format = format_; records = static_cast<const uint8_t*>(records_); n_pub = (size_t)std::max(n_pub_, 0); records_call = true;
     }
     void check(int count, bool null_argument) const override {
         if (!known_format(format)) throw std::invalid_argument("format: not one of UG_RECORDS_PLAIN, UG_RECORDS_EVM, UG_RECORDS_COMPRESSED");
         if (null_argument || (count > 0 && (!records || !inputs))) throw std::invalid_argument("null argument");
-        if (!n_pub) throw std::invalid_argument("invalid inputs data");
+        if (!n_pub && !keyed) throw std::invalid_argument("invalid inputs data");
     }
     // points = false reads pi_r only (the challenge); not even that of a compressed record, whose pi_r the device's ingest leaves
     void parse(size_t i, BatchProof& p, size_t, bool points) const override {
@@ -516,10 +591,12 @@ struct RecordSource : Source {
         p.g[1] = g1_inf();
         p.no_point = points && !record_read(format, ultra, rec, p);
         if (!points && ultra && format != RECORDS_COMPRESSED) record_read_pi_r(format, rec, p.g[1]);
-        p.in.plain.assign(n_pub, std::vector<u32>(8));
-        for (size_t c = 0; c < n_pub; c++) {                        // reduced mod r, as fr_plain_from_decimal
+        const size_t n_in = keyed ? n_pub_of_key[(size_t)key_of[i]] : n_pub;
+        const uint8_t* in = inputs + (keyed ? inputs_at[i] : i * n_pub * 32);
+        p.in.plain.assign(n_in, std::vector<u32>(8));
+        for (size_t c = 0; c < n_in; c++) {                         // reduced mod r, as fr_plain_from_decimal
             uint8_t le[32];
-            inputs_to_plain(format, inputs + (i * n_pub + c) * 32, 1, le);
+            inputs_to_plain(format, in + c * 32, 1, le);
             u32 v[8];
             memcpy(v, le, 32);
             to_normal(p.in.plain[c].data(), from_normal<FrParams>(v));
@@ -539,25 +616,51 @@ struct BatchCall {
     const int device;
     const BatchOptions opt;
     const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
-    const Key key;
+    // The keys of the call and the key of every proof. A call under one key: one key, key_of empty. A call under several
+    // (the _keys entry points): key_of[i] indexes keys, checked by the entry point; the proofs of a pass are taken in key order
+    // (a stable sort), so that those of one key form a segment, and the verdicts are the caller's order again.
+    std::vector<Key> keys;
+    std::vector<char> key_ok;              // per key; else no batching under it: every proof of it that parses is verify_one's
+    const std::vector<int> key_of;
     const size_t n;
-    const bool key_ok;                     // else no batching: every proof that parses is verify_one's
-    const bool resident, hooks;
+    bool resident = false;
+    const bool hooks;
     std::vector<State> state;
     std::vector<int> verdict;
     std::vector<BatchProof> parsed;
     std::vector<std::string> message;      // of the proofs whose verdict stays VERIFIER_ERROR
     ug_verify_batch_stats_ex stats = {{0, 0, 0, 0.0, 0.0}, 0, 0, 0.0};
+    unsigned long long segments = 0, tree_launches = 0, key_checks = 0;        // ug_verify_batch_stats_keys
     double phase[PHASES] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::chrono::steady_clock::time_point t_lap = t_start;
 
-    BatchCall(const Source& src_, int device_, size_t count, const char* verification_key, const BatchOptions& opt_)
-        : src(src_), device(device_), opt(opt_), key(parse_key(verification_key, src_.ultra)), n(count), key_ok(batchable(key)),
-          resident(key_ok && device_ >= 0 && src_.records), hooks(ughost::testHooksEnabled()), state(count, SINGLE), verdict(count, VERIFIER_ERROR),
-          parsed(count), message(count) {
-        if (src.records) check_length(src.n_pub, key.ic.size(), key.ultra);      // (texts: checked per proof, in parse)
+    // key_texts: n_keys texts. keyed: the call names its keys by index, and says so in what it reports of one ("key <k>: ...").
+    // The keys are parsed and checked -- the subgroup tests are the 8.7 ms of the one-key call -- across the host threads.
+    BatchCall(const Source& src_, int device_, size_t count, const char* const* key_texts, size_t n_keys, bool keyed, const int* key_of_,
+              const BatchOptions& opt_)
+        : src(src_), device(device_), opt(opt_), keys(n_keys), key_ok(n_keys, 0), key_of(key_of_ ? key_of_ : nullptr, key_of_ ? key_of_ + count : nullptr), n(count),
+          hooks(ughost::testHooksEnabled()), state(count, SINGLE), verdict(count, VERIFIER_ERROR), parsed(count), message(count) {
+        std::vector<std::string> failure(n_keys);
+        parallel_for(n_keys, [&](size_t q) {
+            try {
+                keys[q] = parse_key(key_texts[q], src.ultra);
+                if (keyed ? src.records_call : src.records != nullptr) check_length(keyed ? src.n_pub_of_key[q] : src.n_pub, keys[q].ic.size(), src.ultra);      // (texts: checked per proof, in parse)
+                key_ok[q] = batchable(keys[q]);
+            } catch (std::exception& e) { failure[q] = e.what(); }
+        });
+        for (size_t q = 0; q < n_keys; q++)
+            if (!failure[q].empty()) throw std::invalid_argument(keyed ? "key " + std::to_string(q) + ": " + failure[q] : failure[q]);
+        bool any_ok = false;
+        for (char ok : key_ok) any_ok = any_ok || ok;
+        resident = any_ok && device >= 0 && src.records;
         if (hooks) { std::lock_guard<std::mutex> lock(g_trace.m); g_trace.index.clear(); g_trace.r.clear(); g_trace.f.clear(); g_trace.in_place = g_trace.gathered = 0; }
         lap(PHASE_KEY);
+    }
+    size_t key_index(size_t i) const { return key_of.empty() ? 0 : (size_t)key_of[i]; }
+    const Key& key_for(size_t i) const { return keys[key_index(i)]; }
+    // idx (proofs of the call) in key order, the caller's order within a key
+    void group_by_key(std::vector<size_t>& idx) const {
+        if (!key_of.empty()) std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return key_of[x] < key_of[y]; });
     }
     static bool batchable(const Key& key) {                         // every point on its curve, every G2 point in the subgroup
         bool ok = key_on_curve(key);
@@ -572,7 +675,12 @@ struct BatchCall {
 
     int run(int* verdicts, char* error_msg, unsigned long error_msg_maxsize) {
         if (resident) resident_passes();
-        else { parse_all(); gathered_passes(set_aside_off_subgroup()); }
+        else {
+            parse_all();
+            std::vector<size_t> idx = set_aside_off_subgroup();
+            group_by_key(idx);
+            gathered_passes(idx);
+        }
         decide_singles();
         return finish(verdicts, error_msg, error_msg_maxsize);
     }
@@ -581,13 +689,14 @@ struct BatchCall {
     //    the first step of the single verifier, which every proof is then handed to.
     void parse_all() {
         parallel_for(n, [&](size_t i) {
-            state[i] = key_ok ? DONE : SINGLE;
+            const bool ok = key_ok[key_index(i)];
+            state[i] = ok ? DONE : SINGLE;
             try {
                 BatchProof& p = parsed[i];
-                src.parse(i, p, key.ic.size(), true);
-                if (!key_ok) return;
+                src.parse(i, p, key_for(i).ic.size(), true);
+                if (!ok) return;
                 if (!proof_on_curve(p)) { verdict[i] = VERIFIER_INVALID_PROOF; return; }
-                if (key.ultra) derive_challenge_plain(p.challenge, p.g[1]);
+                if (src.ultra) derive_challenge_plain(p.challenge, p.g[1]);
                 state[i] = BATCH;
             } catch (std::exception& e) { message[i] = e.what(); }
         });
@@ -618,9 +727,8 @@ struct BatchCall {
         lap(PHASE_SUBGROUP);
         return idx;
     }
-    // the scalars of a pass and the prefix sums of its proofs idx[0..m)
-    void draw_scalars(Pass& pass, const size_t* idx, std::vector<u32>& r) {
-        const size_t m = pass.m;
+    // the scalars of a pass of m proofs
+    void draw_scalars(size_t m, std::vector<u32>& r) {
         r.resize(m * 4);
         for (size_t got = 0; got < r.size() * sizeof(u32);) {
             const ssize_t w = getrandom((uint8_t*)r.data() + got, r.size() * sizeof(u32) - got, 0);
@@ -628,6 +736,10 @@ struct BatchCall {
             got += (size_t)w;
         }
         for (size_t i = 0; i < m; i++) if (!(r[4 * i] | r[4 * i + 1] | r[4 * i + 2] | r[4 * i + 3])) r[4 * i] = 1;       // (2^-128)
+    }
+    // the prefix sums of a segment: its proofs idx[0..m) and their scalars r
+    void prefix_sums(Pass& pass, const size_t* idx, const u32* r) {
+        const size_t m = pass.m;
         pass.prefix.assign((m + 1) * pass.cols, fp_zero<FrParams>());
         std::vector<Fr> term(m * pass.cols);
         parallel_for(m, [&](size_t i) {
@@ -637,92 +749,171 @@ struct BatchCall {
             Fr* t = &term[i * pass.cols];
             t[0] = rf;
             for (size_t c = 0; c < p.in.plain.size(); c++) t[1 + c] = canon(mul(rf, fr_from_plain(p.in.plain[c].data())));
-            if (key.ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
+            if (src.ultra) t[pass.cols - 1] = canon(mul(rf, fr_from_plain(p.challenge)));
         });
         for (size_t i = 0; i < m; i++)
             for (size_t c = 0; c < pass.cols; c++)
                 pass.prefix[(i + 1) * pass.cols + c] = canon(add(pass.prefix[i * pass.cols + c], term[i * pass.cols + c]));
     }
-    // the trees of a pass are there: the root check, the search of a rejected pass, the verdicts
-    void settle(Pass& pass, const size_t* idx) {
-        const size_t top = pass.level_size.size() - 1;
+    // The trees of a pass are there: the pass's check, the search of a rejected pass, the verdicts. suspects: positions in the pass.
+    // One segment: its root check, then its tree. Several: ONE equation for the pass -- the product of the segments' values
+    // (Pass::root_value, made across the host threads), one final exponentiation. A pass that fails is searched down a binary
+    // tree over the segments, a node's value the product of its segments' values: both children of a failing node are checked and
+    // the failing ones entered (an odd last node copied up has its child's value: no check), and a failing segment is searched as
+    // under one key, its root not checked again. Judge on: the segments' level follows the rule of Pass::search -- breadth first
+    // while the failing nodes number at most search_width, then every proof under a failing node is a suspect.
+    void settle(std::vector<Pass>& segs, const size_t* idx, size_t m) {
         std::vector<size_t> suspects;
-        if (!pass.node_ok(top, 0)) {
-            if (opt.judge) pass.search(top, 0, (size_t)opt.search_width, suspects);
-            else pass.walk(top, 0, suspects);
+        auto enter = [&](Pass& seg) {                               // a segment whose root is known to fail
+            std::vector<size_t> local;
+            if (opt.judge) seg.search(seg.level_size.size() - 1, 0, (size_t)opt.search_width, local);
+            else seg.walk(seg.level_size.size() - 1, 0, local);
+            for (size_t s : local) suspects.push_back(seg.first + s);
+        };
+        if (segs.size() == 1) {
+            key_checks++;
+            if (!segs[0].node_ok(segs[0].level_size.size() - 1, 0)) enter(segs[0]);
+        } else {
+            std::vector<std::vector<F12>> value(1, std::vector<F12>(segs.size()));     // value[l][j]: segments j << l .. (j + 1) << l
+            parallel_for(segs.size(), [&](size_t s) { value[0][s] = segs[s].root_value(); });
+            while (value.back().size() > 1) {
+                const std::vector<F12>& below = value.back();
+                std::vector<F12> above((below.size() + 1) / 2);
+                for (size_t j = 0; j < above.size(); j++) above[j] = 2 * j + 1 < below.size() ? f12_mul(consts(), below[2 * j], below[2 * j + 1]) : below[2 * j];
+                value.push_back(std::move(above));
+            }
+            unsigned long long checks = 0;
+            auto ok = [&](size_t level, size_t j) { checks++; F12 hard; return final_exp_is_one(consts(), value[level][j], hard); };
+            auto whole = [&](size_t level, size_t j) {
+                for (size_t s = j << level; s < std::min(segs.size(), (j + 1) << level); s++)
+                    for (size_t i = 0; i < segs[s].m; i++) suspects.push_back(segs[s].first + i);
+            };
+            size_t level = value.size() - 1;
+            std::vector<size_t> failing;
+            if (!ok(level, 0)) failing.push_back(0);
+            while (!failing.empty() && level > 0) {                 // all of `failing` on `level`
+                if (opt.judge && failing.size() > (size_t)opt.search_width) { for (size_t j : failing) whole(level, j); failing.clear(); break; }
+                std::vector<size_t> next;
+                for (size_t j : failing) {
+                    if (2 * j + 1 >= value[level - 1].size()) { next.push_back(2 * j); continue; }        // copied up: the same value
+                    for (size_t c = 2 * j; c <= 2 * j + 1; c++) if (!ok(level - 1, c)) next.push_back(c);
+                }
+                failing.swap(next);
+                level--;
+            }
+            for (size_t s : failing) enter(segs[s]);                // level 0: the failing segments
+            key_checks += checks;
+            stats.base.batch_checks += checks;
         }
-        for (size_t i = 0; i < pass.m; i++) { verdict[idx[i]] = VERIFIER_VALID_PROOF; state[idx[i]] = DONE; }
+        for (size_t i = 0; i < m; i++) { verdict[idx[i]] = VERIFIER_VALID_PROOF; state[idx[i]] = DONE; }
         for (size_t s : suspects) state[idx[s]] = SINGLE;
-        stats.base.batch_checks += pass.checks;
+        for (const Pass& seg : segs) stats.base.batch_checks += seg.checks;
     }
-    // One pass over the proofs idx[0..pass.m) of the call: scalars and prefix sums, the trees from make_trees(r, kernel_ms) -- host_trees,
-    // pairing_batch_device or ResidentBatch::run --, then the checks. The one place that accounts a pass's device time and leaves its
-    // kernel times and, for the test hooks, its scalars and leaves (hook_counter: which kind of resident pass it was).
-    template <class MakeTrees> void run_pass(Pass& pass, const size_t* idx, unsigned long long* hook_counter, const MakeTrees& make_trees) {
+    // the segments of a pass over the proofs idx[0..m), which are in key order: the sizes of the runs of one key
+    std::vector<u32> segment_sizes(const size_t* idx, size_t m) const {
+        std::vector<u32> sizes;
+        for (size_t i = 0; i < m; i++) {
+            if (i && key_index(idx[i]) == key_index(idx[i - 1])) sizes.back()++;
+            else sizes.push_back(1);
+        }
+        return sizes;
+    }
+    // One pass over the proofs idx[0..m) of the call, in key order: the forest of its segments, scalars and prefix sums, the trees from
+    // make_trees(forest, r, kernel_ms) -- the host forest, pairing_batch_device or ResidentBatch::run; it returns its tree launches --,
+    // then the checks. The one place that accounts a pass's device time and leaves its kernel times and, for the test hooks, its
+    // scalars and leaves (hook_counter: which kind of resident pass it was).
+    template <class MakeTrees> void run_pass(const size_t* idx, size_t m, unsigned long long* hook_counter, const MakeTrees& make_trees) {
+        Forest forest(segment_sizes(idx, m), src.ultra ? 2 : 1);
+        std::vector<Pass> segs;
+        segs.reserve(forest.plan.size.size());
+        for (size_t s = 0; s < forest.plan.size.size(); s++) segs.emplace_back(key_for(idx[forest.plan.first[s]]), forest, s);
+        segments += segs.size();
         std::vector<u32> r;
-        draw_scalars(pass, idx, r);
+        draw_scalars(m, r);
+        for (Pass& seg : segs) prefix_sums(seg, idx + seg.first, &r[seg.first * 4]);
         lap(PHASE_SCALARS);
         const auto t0 = std::chrono::steady_clock::now();
         double kernel_ms[3] = {0, 0, 0};
-        make_trees(r.data(), kernel_ms);
+        tree_launches += (unsigned long long)make_trees(forest, segs, r.data(), kernel_ms);
         if (device >= 0) stats.base.device_ms += ms_since(t0);
         {
             std::lock_guard<std::mutex> lock(g_trace.m);
             if (device >= 0) for (int t = 0; t < 3; t++) g_trace.kernel_ms[t] = kernel_ms[t];
             if (hooks) {
-                for (size_t i = 0; i < pass.m; i++) g_trace.index.push_back((int)idx[i]);
+                for (size_t i = 0; i < m; i++) g_trace.index.push_back((int)idx[i]);
                 g_trace.r.insert(g_trace.r.end(), r.begin(), r.end());
-                g_trace.f.insert(g_trace.f.end(), pass.f_tree.begin(), pass.f_tree.begin() + pass.m * F12_WORDS);
+                g_trace.f.insert(g_trace.f.end(), forest.f_tree.begin(), forest.f_tree.begin() + m * F12_WORDS);
                 if (hook_counter) ++*hook_counter;
             }
         }
         lap(PHASE_PASS);
-        settle(pass, idx);
+        settle(segs, idx, m);
         lap(PHASE_SEARCH);
     }
-    // 3. the batch, in passes
+    // the plan a device pass is given: none for one segment, which keeps the one-key tree kernels and their layout
+    static const ForestPlan* device_plan(const Forest& forest) { return forest.plan.size.size() > 1 ? &forest.plan : nullptr; }
+    // 3. the batch, in passes; idx: the proofs that stay in it, in key order
     void gathered_passes(const std::vector<size_t>& idx) {
         for (size_t first = 0; first < idx.size(); first += PAIRING_PASS) {
             const size_t m = std::min<size_t>(PAIRING_PASS, idx.size() - first);
-            Pass pass(key, m);
-            const int k = pass.k;
+            const int k = src.ultra ? 2 : 1;
             std::vector<u32> a(m * G1_WORDS), b(m * G2_WORDS), g(m * k * G1_WORDS);
             pack_points(parsed, &idx[first], m, k, a.data(), b.data(), g.data());
             lap(PHASE_PACKING);
-            run_pass(pass, &idx[first], nullptr, [&](const u32* r, double kernel_ms[3]) {
-                if (device < 0) { pass.host_trees(a.data(), b.data(), g.data(), r); return; }
+            run_pass(&idx[first], m, nullptr, [&](Forest& forest, std::vector<Pass>& segs, const u32* r, double kernel_ms[3]) {
+                if (device < 0) { forest.host_leaves(a.data(), b.data(), g.data(), r); host_forest(segs); return 0; }
                 PairingBatch pb;
                 pb.n = (int)m; pb.k = k; pb.a = a.data(); pb.b = b.data(); pb.g = g.data(); pb.r = r;
-                pb.f_tree = pass.f_tree.data(); pb.g_tree = pass.g_tree.data();
+                pb.f_tree = forest.f_tree.data(); pb.g_tree = forest.g_tree.data(); pb.plan = device_plan(forest);
                 pairing_batch_device(device, consts(), pb);
                 for (int t = 0; t < 3; t++) kernel_ms[t] = pb.kernel_ms[t];
+                return pb.tree_launches;
             });
         }
     }
     // 1-3 for packed records on a device, per pass of PAIRING_PASS records: the raw records cross PCIe once, the device reduces
     // and checks them and keeps the arrays of the Miller kernel; the host reads no coordinate of a proof that stays in the
     // batch (UltraGroth: pi_r, for the challenge). Off its curve: INVALID; pi_b off the subgroup: SINGLE, as in step 2.
+    // Several keys: the records of a pass are uploaded grouped by key -- reordered on the host before the copy, 16 MB a pass at most
+    // (none when they lie in that order already, as under one key) --, so that ingest, ladder and gather work as they are and what
+    // they keep is in key order. The records of a key the batch refuses are not uploaded: the single verifier's (step 4).
     void resident_passes() {
-        const int k = key.k(), format = src.format;
-        const bool late_challenge = key.ultra && format == RECORDS_COMPRESSED;     // pi_r.y is the device's to find: no host root per proof
-        for (size_t first = 0; first < n; first += PAIRING_PASS) {
-            const size_t m = std::min<size_t>(PAIRING_PASS, n - first);
+        const int k = src.ultra ? 2 : 1, format = src.format;
+        const bool late_challenge = src.ultra && format == RECORDS_COMPRESSED;     // pi_r.y is the device's to find: no host root per proof
+        const size_t stride = record_bytes(src.ultra, format);
+        std::vector<size_t> order;
+        for (size_t i = 0; i < n; i++) if (key_ok[key_index(i)]) order.push_back(i);
+        group_by_key(order);
+        for (size_t first = 0; first < order.size(); first += PAIRING_PASS) {
+            const size_t m = std::min<size_t>(PAIRING_PASS, order.size() - first);
+            const size_t* ids = &order[first];
             parallel_for(m, [&](size_t i) {
-                BatchProof& p = parsed[first + i];
-                src.parse(first + i, p, key.ic.size(), false);
-                if (key.ultra && !late_challenge) derive_challenge_plain(p.challenge, p.g[1]);
+                BatchProof& p = parsed[ids[i]];
+                src.parse(ids[i], p, key_for(ids[i]).ic.size(), false);
+                if (src.ultra && !late_challenge) derive_challenge_plain(p.challenge, p.g[1]);
             });
+            const uint8_t* records = src.records + ids[0] * stride;
+            std::vector<uint8_t> grouped;
+            bool in_order = true;
+            for (size_t i = 1; i < m && in_order; i++) in_order = ids[i] == ids[i - 1] + 1;
+            if (!in_order) {
+                grouped.resize(m * stride);
+                parallel_for((m + 1023) / 1024, [&](size_t c) {
+                    for (size_t i = c * 1024; i < std::min(m, (c + 1) * 1024); i++) memcpy(&grouped[i * stride], src.records + ids[i] * stride, stride);
+                });
+                records = grouped.data();
+            }
             lap(PHASE_PARSE);
             const auto t0 = std::chrono::steady_clock::now();
             ResidentBatch rb(device, (int)m, k, format);
             std::vector<uint8_t> status(m);
-            rb.ingest(src.records + first * record_bytes(key.ultra, format), status.data());
+            rb.ingest(records, status.data());
             if (late_challenge) {                                   // the rows of pi_r as the ingest decompressed them
                 std::vector<u32> g(m * (size_t)k * G1_WORDS);
                 rb.download(nullptr, nullptr, g.data());
                 parallel_for(m, [&](size_t i) {
                     if (status[i] == UG_POINT_OFF_CURVE) return;
-                    BatchProof& p = parsed[first + i];
+                    BatchProof& p = parsed[ids[i]];
                     p.g[1] = g1_load(&g[(i * k + 1) * G1_WORDS], false);
                     derive_challenge_plain(p.challenge, p.g[1]);
                 });
@@ -731,16 +922,18 @@ struct BatchCall {
             std::vector<size_t> kept;
             std::vector<u32> keep;
             for (size_t i = 0; i < m; i++) {
-                if (status[i] == UG_POINT_OK) { kept.push_back(first + i); keep.push_back((u32)i); state[first + i] = BATCH; }
-                else if (status[i] == UG_POINT_OFF_SUBGROUP) { state[first + i] = SINGLE; stats.base.off_subgroup++; }
-                else { state[first + i] = DONE; verdict[first + i] = VERIFIER_INVALID_PROOF; }
+                if (status[i] == UG_POINT_OK) { kept.push_back(ids[i]); keep.push_back((u32)i); state[ids[i]] = BATCH; }
+                else if (status[i] == UG_POINT_OFF_SUBGROUP) { state[ids[i]] = SINGLE; stats.base.off_subgroup++; }
+                else { state[ids[i]] = DONE; verdict[ids[i]] = VERIFIER_INVALID_PROOF; }
             }
             lap(PHASE_SUBGROUP);
             if (kept.empty()) continue;
-            Pass pass(key, kept.size());
             const bool in_place = kept.size() == m;
-            run_pass(pass, kept.data(), in_place ? &g_trace.in_place : &g_trace.gathered, [&](const u32* r, double kernel_ms[3]) {
-                rb.run(consts(), in_place ? nullptr : keep.data(), (int)kept.size(), r, pass.f_tree.data(), pass.g_tree.data(), kernel_ms);
+            run_pass(kept.data(), kept.size(), in_place ? &g_trace.in_place : &g_trace.gathered,
+                     [&](Forest& forest, std::vector<Pass>&, const u32* r, double kernel_ms[3]) {
+                rb.plan = device_plan(forest);
+                rb.run(consts(), in_place ? nullptr : keep.data(), (int)kept.size(), r, forest.f_tree.data(), forest.g_tree.data(), kernel_ms);
+                return rb.tree_launches;
             });
         }
     }
@@ -749,17 +942,20 @@ struct BatchCall {
     void decide_singles() {
         std::vector<size_t> singles;
         for (size_t i = 0; i < n; i++) if (state[i] == SINGLE) singles.push_back(i);
-        if (resident) parallel_for(singles.size(), [&](size_t s) { src.parse(singles[s], parsed[singles[s]], key.ic.size(), true); });
-        if (opt.judge && key_ok && !singles.empty() && singles.size() >= (size_t)opt.judge_min) {
+        if (resident) parallel_for(singles.size(), [&](size_t s) { src.parse(singles[s], parsed[singles[s]], key_for(singles[s]).ic.size(), true); });
+        std::vector<size_t> suspects, rest;                         // suspects: under a key the batch takes; the judge's, all keys in one launch
+        for (size_t i : singles) (key_ok[key_index(i)] ? suspects : rest).push_back(i);
+        if (opt.judge && !suspects.empty() && suspects.size() >= (size_t)opt.judge_min) {
+            group_by_key(suspects);
             std::vector<char> valid;
-            judge_suspects(key, device, parsed, singles, valid, stats);
-            for (size_t s = 0; s < singles.size(); s++) verdict[singles[s]] = valid[s] ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
-            singles.clear();
+            judge_suspects(keys, key_of, device, parsed, suspects, valid, stats);
+            for (size_t s = 0; s < suspects.size(); s++) verdict[suspects[s]] = valid[s] ? VERIFIER_VALID_PROOF : VERIFIER_INVALID_PROOF;
+            singles.swap(rest);
         }
         parallel_for(singles.size(), [&](size_t s) {
             const size_t i = singles[s];
             if (!message[i].empty()) return;                        // (it did not parse)
-            try { verdict[i] = verify_one(key, parsed[i]); }
+            try { verdict[i] = verify_one(key_for(i), parsed[i]); }
             catch (std::exception& e) { message[i] = e.what(); }
         });
         stats.base.single_checks = singles.size();
@@ -800,10 +996,36 @@ int batch_entry(int device, const Source& src, int count, const char* verificati
     return guarded(error_msg, error_msg_maxsize, [&] {
         const BatchOptions opt = read_options(options);
         src.check(count, count < 0 || !verification_key || (count > 0 && !verdicts));
-        BatchCall call(src, device, (size_t)count, verification_key, opt);
+        BatchCall call(src, device, (size_t)count, &verification_key, 1, false, nullptr, opt);
         const int rc = call.run(verdicts, error_msg, error_msg_maxsize);
         if (stats) *stats = call.stats;
         if (legacy_stats) *legacy_stats = call.stats.base;
+        return rc;
+    });
+}
+// The route of the _keys calls: the same call under n_keys keys. n_pub: the records calls' inputs per proof of every key (texts: null).
+// The order of the tests is the order of the messages (include/verifier.h).
+int keys_entry(int device, Source& src, int count, int n_keys, const char* const* keys, const int* key_of, const int* n_pub, int* verdicts,
+               const ug_verify_batch_options* options, ug_verify_batch_stats_keys* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    return guarded(error_msg, error_msg_maxsize, [&] {
+        const BatchOptions opt = read_options(options);
+        src.keyed = true;                                           // (RecordSource::check then asks no n_pub of its own)
+        bool null_argument = count < 0 || n_keys < 0 || (count > 0 && (!verdicts || !key_of)) || (n_keys > 0 && (!keys || (src.records_call && !n_pub)));
+        for (int q = 0; !null_argument && q < n_keys; q++) null_argument = !keys[q];
+        src.check(count, null_argument);
+        if (count > 0 && n_keys <= 0) throw std::invalid_argument("n_keys: a call with proofs needs at least one key");
+        for (int i = 0; i < count; i++)
+            if (key_of[i] < 0 || key_of[i] >= n_keys) throw std::invalid_argument("proof " + std::to_string(i) + ": key index " + std::to_string(key_of[i]) + " out of range");
+        if (src.records_call) {
+            for (int q = 0; q < n_keys; q++) if (n_pub[q] <= 0) throw std::invalid_argument("key " + std::to_string(q) + ": invalid inputs data");
+            src.ragged(key_of, n_pub, (size_t)n_keys, (size_t)count);
+        }
+        BatchCall call(src, device, (size_t)count, keys, (size_t)n_keys, true, count > 0 ? key_of : nullptr, opt);
+        const int rc = call.run(verdicts, error_msg, error_msg_maxsize);
+        if (stats) {
+            stats->ex = call.stats;
+            stats->segments = call.segments; stats->tree_launches = call.tree_launches; stats->key_checks = call.key_checks;
+        }
         return rc;
     });
 }
@@ -849,6 +1071,69 @@ int ug_ultra_groth_verify_batch_records_fmt(int device, int format, int count, c
                                             const char* verification_key, int* verdicts, const ug_verify_batch_options* options,
                                             ug_verify_batch_stats_ex* stats, char* error_msg, unsigned long error_msg_maxsize) {
     return batch_entry(device, RecordSource(true, format, records, inputs, n_pub), count, verification_key, verdicts, options, stats, nullptr, error_msg, error_msg_maxsize);
+}
+
+int ug_groth16_verify_batch_keys(int device, int count, const char* const* proofs, const char* const* inputs, int n_keys, const char* const* keys,
+                                 const int* key_of, int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_keys* stats, char* error_msg,
+                                 unsigned long error_msg_maxsize) {
+    JsonSource src(false, proofs, inputs);
+    return keys_entry(device, src, count, n_keys, keys, key_of, nullptr, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_ultra_groth_verify_batch_keys(int device, int count, const char* const* proofs, const char* const* inputs, int n_keys, const char* const* keys,
+                                     const int* key_of, int* verdicts, const ug_verify_batch_options* options, ug_verify_batch_stats_keys* stats,
+                                     char* error_msg, unsigned long error_msg_maxsize) {
+    JsonSource src(true, proofs, inputs);
+    return keys_entry(device, src, count, n_keys, keys, key_of, nullptr, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_groth16_verify_batch_records_keys(int device, int format, int count, const void* records, const void* inputs, int n_keys, const char* const* keys,
+                                         const int* key_of, const int* n_pub, int* verdicts, const ug_verify_batch_options* options,
+                                         ug_verify_batch_stats_keys* stats, char* error_msg, unsigned long error_msg_maxsize) {
+    RecordSource src(false, format, records, inputs, 0);
+    return keys_entry(device, src, count, n_keys, keys, key_of, n_pub, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+int ug_ultra_groth_verify_batch_records_keys(int device, int format, int count, const void* records, const void* inputs, int n_keys,
+                                             const char* const* keys, const int* key_of, const int* n_pub, int* verdicts,
+                                             const ug_verify_batch_options* options, ug_verify_batch_stats_keys* stats, char* error_msg,
+                                             unsigned long error_msg_maxsize) {
+    RecordSource src(true, format, records, inputs, 0);
+    return keys_entry(device, src, count, n_keys, keys, key_of, n_pub, verdicts, options, stats, error_msg, error_msg_maxsize);
+}
+
+// ULTRAGROTH_TEST_HOOKS=1 only: the forest over given leaves -- n_segments segments of sizes[] leaves, leaves_f n x 108 words and
+// leaves_g n x k x 36 (canonical values, as the Miller kernel leaves them) -- by the forest kernels alone on `device`, by the host
+// forest for device < 0. f_tree_out / g_tree_out: the whole forest in ForestPlan's layout, nodes x 108 and nodes x k x 36 words.
+int ug_test_tree_forest(int device, int k, int n_segments, const int* sizes, const unsigned int* leaves_f, const unsigned int* leaves_g,
+                        unsigned int* f_tree_out, unsigned int* g_tree_out) {
+    if (!ughost::testHooksEnabled() || !sizes || !leaves_f || !leaves_g || !f_tree_out || !g_tree_out || n_segments <= 0 || (k != 1 && k != 2)) return 1;
+    try {
+        std::vector<u32> sz;
+        size_t n = 0;
+        for (int s = 0; s < n_segments; s++) {
+            if (sizes[s] <= 0) return 1;
+            sz.push_back((u32)sizes[s]);
+            n += (size_t)sizes[s];
+        }
+        if (n > (size_t)PAIRING_PASS) return 1;
+        Forest forest(sz, k);
+        if (device < 0) {
+            memcpy(forest.f_tree.data(), leaves_f, n * F12_WORDS * sizeof(u32));
+            memcpy(forest.g_tree.data(), leaves_g, n * (size_t)k * XYZZ_WORDS * sizeof(u32));
+            Key none;                                               // (the trees ask nothing of a key)
+            none.ultra = k == 2;
+            std::vector<Pass> segs;
+            segs.reserve(sz.size());
+            for (size_t s = 0; s < sz.size(); s++) segs.emplace_back(none, forest, s);
+            host_forest(segs);
+        } else {
+            PairingBatch pb;
+            pb.n = (int)n; pb.k = k; pb.plan = &forest.plan; pb.leaf_f = leaves_f; pb.leaf_g = leaves_g;
+            pb.f_tree = forest.f_tree.data(); pb.g_tree = forest.g_tree.data();
+            pairing_batch_device(device, consts(), pb);
+        }
+        memcpy(f_tree_out, forest.f_tree.data(), forest.f_tree.size() * sizeof(u32));
+        memcpy(g_tree_out, forest.g_tree.data(), forest.g_tree.size() * sizeof(u32));
+        return 0;
+    } catch (...) { return 1; }
 }
 
 // ULTRAGROTH_TEST_HOOKS=1 only: the passes of the last records call on a device that used the resident arrays in place, and those that
