@@ -154,20 +154,22 @@ typedef struct { unsigned long long failed, first; unsigned char a[32], b[32], c
 int ug_witness_check(const void *r1cs, unsigned long long r1cs_size, const void *wtns, unsigned long long wtns_size,
                      int device, ug_witness_fault *fault, char *error_msg, unsigned long long error_msg_maxsize);
 /* ug_prover_attach_r1cs gives a created prover its circuit's .r1cs (size = 0 detaches); from then on EVERY proof call of the handle
- * checks its witness on the device -- prove, prove_resident, run, prove_batch (one check per witness) -- beside the proof's own
- * kernels, its result read where the call waits for the device anyway: a good witness costs no extra host wait. A witness that
+ * checks its witness on the device -- prove, prove_resident, run, prove_batch (Groth16: one check per witness; UltraGroth: ONE
+ * check launch for the witnesses of a device pass, include/ultragroth_hip.h: ug_r1cs_check_vectors_enqueue) -- beside the proof's own kernels, its result read where the call waits for the device anyway: a good witness costs no extra host wait. A witness that
  * breaks a constraint fails the call with PROVER_ERROR and the message above (a batch prefixes "witness <b>: "); no proof or
  * public buffer is written and the prover stays usable. Groth16 queues the check once the witness is resident, UltraGroth after
- * the lookup completion and before the final round (its batched call proves one witness after the other while attached). Under
+ * the lookup completion and before the final round (its batched pass: after the ONE lookup completion of the V witnesses). Under
  * ULTRAGROTH_GRAPH=1 the check is queued eagerly, outside the recorded sequence. The phase calls that make a proof in pieces
  * (run_witness_msm, witness_msm_begin, run_h_msm, hpoly_chain, hpoly_combine) are refused while an .r1cs is attached.
- * Supported on a created, unsharded, one-device Groth16 or UltraGroth prover. It fails, and nothing is attached, for:
+ * Supported on a created, unsharded, one-device Groth16 or UltraGroth prover, and on the circuits of a registry through
+ * ug_registry_attach_r1cs (below). It fails, and nothing is attached, for:
  *   "r1cs: not this circuit: <which>"   nWires != nVars, nPubOut + nPubIn != nPublic, nConstraints + nPublic + 1 > domainSize
  *   "r1cs: not this circuit: matrix <A|B> row <k> differs from the zkey"   the probe of ug_r1cs_match_hpoly (C is not in a zkey:
  *                                        an .r1cs with a wrong C cannot be told apart here)
- *   "witness check: not available on this kind of prover"   a sharded, ULTRAGROTH_DEVICES or registry handle
+ *   "witness check: not available on this kind of prover"   a sharded or ULTRAGROTH_DEVICES handle
  * ULTRAGROTH_R1CS=<path> attaches that file in every creation of a supported prover, the CLIs and the one-shot calls included; an
- * unreadable or mismatching file, or a kind of prover that cannot check, fails the creation. Unset, nothing changes.
+ * unreadable or mismatching file, or a kind of prover that cannot check, fails the creation (a registry's loads too: one path
+ * cannot name many circuits). Unset, nothing changes.
  * Known follow-up, not done: an attached prover computes A.w and B.w twice, here and in the H block. */
 int ug_prover_attach_r1cs(void *prover_object, const void *r1cs, unsigned long long size, char *error_msg,
                           unsigned long long error_msg_maxsize);
@@ -186,13 +188,19 @@ int ug_prover_attach_r1cs(void *prover_object, const void *r1cs, unsigned long l
  * ug_schedule_build_vectors, ug_plan_proof_batch). For UltraGroth a pass is: one round-commitment product over the V gathered
  * round sets, the V challenges on the host, ONE lookup completion for all V witnesses (ug_dvec_complete_lookup_vectors), then the
  * final round's products once over V vectors (ug_plan_proof_batch_aux sizes V). Handles that still prove one after the other, with
- * the same outputs: ULTRAGROTH_DEVICES provers of either protocol, sharded ranks, registry circuits.
- * ug_prover_last_timings reports the whole call. */
+ * the same outputs: ULTRAGROTH_DEVICES provers of either protocol, sharded ranks. A registry's circuits are batched through
+ * ug_registry_prove_batch (below).
+ * ug_prover_last_timings reports the whole call.
+ * ug_prover_batch_info: the device passes of the handle's batched calls since creation -- *passes, the witnesses they proved, and
+ * the width of the last pass. A pass of width V proved V witnesses together; a witness that took the single-proof path (a width of
+ * 1, or a handle that proves one after the other) is a pass of width 1. passes < witnesses says that passes were shared. Single
+ * prove calls are not counted. Any pointer may be NULL. */
 int ug_groth16_prover_prove_batch(void *prover_object, int count,
                                   const void *const *wtns_buffers, const unsigned long long *wtns_sizes,
                                   char *const *proof_buffers, unsigned long long *proof_sizes,
                                   char *const *public_buffers, unsigned long long *public_sizes,
                                   char *error_msg, unsigned long long error_msg_maxsize);
+int ug_prover_batch_info(void *prover_object, unsigned long long *passes, unsigned long long *witnesses, int *last_width);
 
 /* Device milliseconds of the last prove on this prover object: MSM part, H-polynomial ("FFT") part, and
  * host wall-clock milliseconds of the whole prove call. */
@@ -240,6 +248,32 @@ int ug_registry_evict(void *registry, const char *circuit, char *error_msg, unsi
  * number of resident circuits (in *state), proofs made. */
 int ug_registry_info(void *registry, const char *circuit, unsigned long long *resident_bytes, int *state,
                      unsigned long long *proofs);
+/* ug_registry_prove_batch: `count` witnesses of one circuit, with the contract of ug_groth16_prover_prove_batch for the circuit's
+ * protocol -- the outputs of ug_registry_prove one by one, byte for byte, the "witness <b>: " prefix, the short-buffer rule, the
+ * blinding order. Under the registry's locks it behaves as ug_registry_prove: an evicted circuit that came from a file is
+ * reloaded, the circuit cannot be trimmed, evicted or replaced during the call, every device pass is one turn on the device,
+ * and memory is given back and tables grown afterwards. The width of a pass is what ug_plan_proof_batch (_aux for UltraGroth)
+ * grants for min(device free, budget - bytes that others hold): the circuit's own workspaces count as room, since the pass reuses
+ * or replaces them. The batch buffers are per-proof workspaces: they count in the circuit's resident bytes and are the second
+ * thing the registry gives back. ug_registry_batch_info: ug_prover_batch_info of the circuit's prover (PROVER_ERROR when it is
+ * not resident; the counters start again when a circuit is reloaded). */
+int ug_registry_prove_batch(void *registry, const char *circuit, int count,
+                            const void *const *wtns_buffers, const unsigned long long *wtns_sizes,
+                            char *const *proof_buffers, unsigned long long *proof_sizes,
+                            char *const *public_buffers, unsigned long long *public_sizes,
+                            char *error_msg, unsigned long long error_msg_maxsize);
+int ug_registry_batch_info(void *registry, const char *circuit, unsigned long long *passes, unsigned long long *witnesses,
+                           int *last_width);
+/* ug_registry_attach_r1cs gives a circuit its .r1cs, with the rules and messages of ug_prover_attach_r1cs (size = 0 detaches);
+ * _file reads it from a path. From then on ug_registry_prove and ug_registry_prove_batch check every witness of the circuit. The
+ * matrices count in the circuit's resident bytes. An attachment outlives the eviction of its circuit: when the circuit comes back
+ * from its file it is attached again before its first proof -- from the path (_file), or from a host copy of the buffer that the
+ * registry keeps -- and when that fails the proof call fails: a circuit that was attached is never proven unchecked. Loading a
+ * zkey under the circuit's name drops the attachment. An evicted, reloadable circuit is brought back by the call. */
+int ug_registry_attach_r1cs(void *registry, const char *circuit, const void *r1cs, unsigned long long size,
+                            char *error_msg, unsigned long long error_msg_maxsize);
+int ug_registry_attach_r1cs_file(void *registry, const char *circuit, const char *r1cs_file_path,
+                                 char *error_msg, unsigned long long error_msg_maxsize);
 void ug_registry_destroy(void *registry);
 
 /* Sharded Groth16 proving, one process per GPU. Rank `shard_rank` of `shard_count` holds the base points

@@ -74,6 +74,7 @@
  *                      UG_REDUCE_G1_LOG, UG_REDUCE_G2_LOG   lanes the bucket reduction keeps busy (default 17, 16)
  *                      UG_UPLOAD_PRIORITY=l|n|h   stream class of the witness staging lanes (default l)
  *                      UG_NTT_SHOUP=0             Montgomery-form twiddle products in the NTT passes (default: Shoup form, ff.hpp mul_shoup)
+ *                      UG_R1CS_VT=1|2|4           witnesses per lane of the batched witness check (default 2; 4 leaves one wave per SIMD)
  *                      UG_SETUP_WINDOW_G1, UG_SETUP_WINDOW_G2   window width (4 .. 16) of the development setup's generator tables
  *   test hooks         ULTRAGROTH_TEST_HOOKS=1 enables ug_test_set_blinding / ULTRAGROTH_TEST_BLINDING and ug_test_inject_fault;
  *                      without it those calls fail and the variables are ignored
@@ -479,6 +480,16 @@ int  ug_r1cs_check(ug_r1cs* r, const ug_dvec* witness, uint64_t first, ug_r1cs_r
  * Slots 0 .. UG_BATCH_MAX - 1; never on a stream that is being recorded (ug_graph_begin). */
 int  ug_r1cs_check_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, int slot, ug_ctx* via);
 int  ug_r1cs_check_collect(ug_r1cs* r, int slot, ug_r1cs_report* out);
+/* The same for the `count` witnesses of a batched pass in ONE launch (r1cs_check_vectors_kernel: a lane takes one constraint for a
+ * group of two witnesses, so the three matrices are walked once per group, not once per witness). Witness v is at elements
+ * first + v * stride of `witness` (a shorter vector: UG_ERROR), its result goes to slot slot0 + v; 1 <= count, slot0 + count <=
+ * UG_BATCH_MAX. Every slot is collected with ug_r1cs_check_collect as before, and every report is the one ug_r1cs_check gives for
+ * that witness alone, bit for bit. */
+int  ug_r1cs_check_vectors_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, uint64_t stride, int count, int slot0, ug_ctx* via);
+/* blocking, for tests and tools: reports[count]; masks: count * n_constraints host bytes (witness v's at v * n_constraints) or NULL;
+ * device_ms of every report is the one launch's time. Uses slots 0 .. count - 1, which must be free. */
+int  ug_r1cs_check_vectors(ug_r1cs* r, const ug_dvec* witness, uint64_t first, uint64_t stride, int count, ug_r1cs_report* reports,
+                           uint8_t* masks);
 int  ug_r1cs_match_hpoly(ug_r1cs* r, const ug_hpoly* hp, uint32_t n_public, int* matrix, uint64_t* row);
 void ug_r1cs_destroy(ug_r1cs* r);
 

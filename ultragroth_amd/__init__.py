@@ -1229,6 +1229,14 @@ class _ProverBase:
         if rc != PROVER_OK:
             raise ProverError(rc, err.value.decode(errors="replace"))
 
+    def batch_info(self):
+        """ug_prover_batch_info: (passes, witnesses, last_width) of this prover's prove_batch calls since creation -- a pass of width V
+        proved V witnesses together, so passes < witnesses says that passes were shared"""
+        a, b, w = C.c_ulonglong(), C.c_ulonglong(), C.c_int()
+        if load().ug_prover_batch_info(self._h, C.byref(a), C.byref(b), C.byref(w)) != PROVER_OK:
+            raise ProverError(PROVER_ERROR, "ug_prover_batch_info failed")
+        return a.value, b.value, w.value
+
     def last_timings(self):
         """(msm_ms, fft_ms, total_ms) of the last prove: device time of the MSM and H-polynomial parts, host wall time."""
         a, b, c = C.c_double(), C.c_double(), C.c_double()
@@ -1352,6 +1360,44 @@ class Registry:
         proof, pub = C.create_string_buffer(psz.value), C.create_string_buffer(qsz.value)
         self._call("ug_registry_prove", circuit.encode(), wtns, len(wtns), proof, C.byref(psz), pub, C.byref(qsz))
         return proof.raw.split(b"\0", 1)[0].decode(), pub.raw.split(b"\0", 1)[0].decode()
+
+    def prove_batch(self, circuit, wtns_list, proof_size=1400, public_size=1 << 16):
+        """ug_registry_prove_batch: [(proof_json, public_json), ...], one pair per witness, each what prove() returns for it; the
+        circuit's prover shares a device pass among as many witnesses as the budget's free room holds"""
+        k = len(wtns_list)
+        keep = [bytes(w) for w in wtns_list]
+        wb = (C.c_char_p * max(k, 1))(*keep)
+        ws = (C.c_ulonglong * max(k, 1))(*[len(w) for w in keep])
+        psz = (C.c_ulonglong * max(k, 1))(*([proof_size] * k))
+        qsz = (C.c_ulonglong * max(k, 1))(*([public_size] * k))
+        proofs = [C.create_string_buffer(max(proof_size, 1)) for _ in range(k)]
+        pubs = [C.create_string_buffer(max(public_size, 1)) for _ in range(k)]
+        pb = (C.c_void_p * max(k, 1))(*[C.cast(b, C.c_void_p) for b in proofs])
+        qb = (C.c_void_p * max(k, 1))(*[C.cast(b, C.c_void_p) for b in pubs])
+        err = C.create_string_buffer(1024)
+        rc = load().ug_registry_prove_batch(self._h, circuit.encode(), k, wb, ws, pb, psz, qb, qsz, err, len(err) - 1)
+        if rc != PROVER_OK:
+            e = ProverError(rc, err.value.decode(errors="replace"))
+            e.proof_sizes, e.public_sizes = list(psz[:k]), list(qsz[:k])
+            raise e
+        return [(p.raw.split(b"\0", 1)[0].decode(), q.raw.split(b"\0", 1)[0].decode()) for p, q in zip(proofs, pubs)]
+
+    def attach_r1cs(self, circuit, r1cs):
+        """ug_registry_attach_r1cs / _file: from now on every proof of the circuit, single or batched, checks its witness against
+        this .r1cs -- bytes (the registry keeps a copy) or a path (str; read again when the circuit comes back after an eviction);
+        None detaches. Rules and messages as Prover.attach_r1cs."""
+        if isinstance(r1cs, str):
+            self._call("ug_registry_attach_r1cs_file", circuit.encode(), r1cs.encode())
+        else:
+            data = bytes(r1cs) if r1cs else None
+            self._call("ug_registry_attach_r1cs", circuit.encode(), data, len(data) if data else 0)
+
+    def batch_info(self, circuit):
+        """ug_registry_batch_info: (passes, witnesses, last_width) of the circuit's prove_batch calls since it was (re)loaded"""
+        a, b, w = C.c_ulonglong(), C.c_ulonglong(), C.c_int()
+        if load().ug_registry_batch_info(self._h, circuit.encode(), C.byref(a), C.byref(b), C.byref(w)) != PROVER_OK:
+            raise ProverError(PROVER_ERROR, "ug_registry_batch_info: circuit not loaded: " + circuit)
+        return a.value, b.value, w.value
 
     def evict(self, circuit):
         self._call("ug_registry_evict", circuit.encode())
@@ -2043,6 +2089,25 @@ class _R1cs(_Handle):
                "a": _le(rep.a) if rep.failed else None, "b": _le(rep.b) if rep.failed else None, "c": _le(rep.c) if rep.failed else None}
         if want_mask:
             out["mask"] = mask.raw[:self.info()["n_constraints"]]
+        return out
+
+    def check_vectors(self, dvec, count, stride=None, first=0, want_masks=False):
+        """ug_r1cs_check_vectors: the `count` witnesses at elements first + v * stride of a device vector (stride None: n_wires)
+        checked in one launch; a list of dicts as check() returns them (device_ms: the one launch's time, in every dict)"""
+        info = self.info()
+        rows = info["n_constraints"]
+        stride = info["n_wires"] if stride is None else stride
+        reps = (_R1csReport * max(count, 1))()
+        masks = C.create_string_buffer(max(1, rows * count)) if want_masks else None
+        _check(self.dev._L.ug_r1cs_check_vectors(self.h, dvec.h, first, stride, count, reps, masks))
+        out = []
+        for v in range(count):
+            rep = reps[v]
+            d = {"failed": rep.failed, "first": rep.first if rep.failed else None, "device_ms": rep.device_ms,
+                 "a": _le(rep.a) if rep.failed else None, "b": _le(rep.b) if rep.failed else None, "c": _le(rep.c) if rep.failed else None}
+            if want_masks:
+                d["mask"] = masks.raw[v * rows:(v + 1) * rows]
+            out.append(d)
         return out
 
     def match(self, hpoly, n_public):

@@ -33,6 +33,7 @@ INNER_SYMBOLS = [
     "ug_plan_window_tables", "ug_schedule_build_vectors", "ug_dvec_gather_index_at", "ug_plan_proof_batch",
     "ug_plan_proof_batch_aux", "ug_fr_lookup_tables", "ug_dvec_apply_lookup_vectors", "ug_dvec_complete_lookup_vectors",
     "ug_r1cs_parse_info", "ug_r1cs_create", "ug_r1cs_get_info", "ug_r1cs_check", "ug_r1cs_check_enqueue", "ug_r1cs_check_collect",
+    "ug_r1cs_check_vectors_enqueue", "ug_r1cs_check_vectors",
     "ug_r1cs_match_hpoly", "ug_r1cs_destroy",
     "ug_setup_draw_trapdoor", "ug_setup_size", "ug_setup_run", "ug_generator_mul", "ug_lagrange_at",
     "ug_ptau_parse_info", "ug_setup_ptau_size", "ug_setup_ptau_run", "ug_points_combine", "ug_points_scale",
@@ -101,6 +102,7 @@ OUTER_SYMBOLS = [
     "ug_groth16_prover_hpoly_combine", "ug_groth16_prover_h_range",
     "ug_groth16_prover_witness_msm_begin", "ug_groth16_prover_witness_msm_end",
     "ug_groth16_prover_prove_batch", "ug_zkey_check", "ug_witness_check", "ug_prover_attach_r1cs",
+    "ug_prover_batch_info", "ug_registry_prove_batch", "ug_registry_attach_r1cs", "ug_registry_attach_r1cs_file", "ug_registry_batch_info",
 ]
 
 
@@ -243,6 +245,8 @@ def load():
     L.ug_r1cs_check.argtypes = [vp, vp, u64, vp, vp]
     L.ug_r1cs_check_enqueue.argtypes = [vp, vp, u64, C.c_int, vp]
     L.ug_r1cs_check_collect.argtypes = [vp, C.c_int, vp]
+    L.ug_r1cs_check_vectors_enqueue.argtypes = [vp, vp, u64, u64, C.c_int, C.c_int, vp]
+    L.ug_r1cs_check_vectors.argtypes = [vp, vp, u64, u64, C.c_int, vp, vp]
     L.ug_r1cs_match_hpoly.argtypes = [vp, vp, u32, C.POINTER(C.c_int), C.POINTER(u64)]
     L.ug_r1cs_destroy.argtypes = [vp]; L.ug_r1cs_destroy.restype = None
     L.ug_witness_check.argtypes = [vp, ull, vp, ull, C.c_int, vp, vp, ull]
@@ -341,6 +345,11 @@ def load():
     L.ug_registry_evict.argtypes = [vp, C.c_char_p, vp, ull]
     L.ug_registry_info.argtypes = [vp, C.c_char_p, pull, C.POINTER(C.c_int), pull]
     L.ug_registry_destroy.argtypes = [vp]; L.ug_registry_destroy.restype = None
+    L.ug_registry_prove_batch.argtypes = [vp, C.c_char_p, C.c_int, vp, vp, vp, vp, vp, vp, vp, ull]
+    L.ug_registry_attach_r1cs.argtypes = [vp, C.c_char_p, vp, ull, vp, ull]
+    L.ug_registry_attach_r1cs_file.argtypes = [vp, C.c_char_p, C.c_char_p, vp, ull]
+    L.ug_registry_batch_info.argtypes = [vp, C.c_char_p, pull, pull, C.POINTER(C.c_int)]
+    L.ug_prover_batch_info.argtypes = [vp, pull, pull, C.POINTER(C.c_int)]
     L.ug_groth16_prover_create_sharded.argtypes = [pp, vp, ull, C.c_int, C.c_int, C.c_int, vp, ull]
     L.ug_ultra_groth_prover_create_sharded.argtypes = [pp, vp, ull, C.c_int, C.c_int, C.c_int, vp, ull]
     L.ug_ultra_groth_prover_round_commit.argtypes = [vp, vp, vp, ull]

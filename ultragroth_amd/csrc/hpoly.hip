@@ -91,60 +91,7 @@ __global__ __launch_bounds__(256) void matvec_tiled_kernel(u32* a_br, u32* b_br,
 }
 
 // ---- the same for the V witnesses of a batched proof (coef_matvec_vectors) ----
-// A lane still owns one row, and now sums it for a tile of VT witnesses: the row's signal ids and coefficients (36 bytes per entry,
-// the larger part of the kernel's traffic) are read and unpacked ONCE per tile, only the 32-byte witness gathers are per witness.
-// Every accumulator sees exactly the additions and contractions that matvec_row makes for its witness -- the same entries in the same
-// order, contracted after every 24th --, so the sums are the same bytes. `live` witnesses of the tile exist (the last tile of a
-// launch may be short); wtns is the tile's first witness, the next one wstride words on.
-// (the loop over the witnesses of a tile, unrolled by construction: a rolled loop would index the accumulators at run time and put
-// them into scratch memory)
-template <int I, int N, class F> __device__ __forceinline__ void for_each_vector(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>()); for_each_vector<I + 1, N>(f); }
-}
-template <int VT>
-__device__ __forceinline__ void matvec_row_vectors(Fr (&acc)[VT], u32 r, const u32* row_ptr, const u32* sig, const u32* val, const u32* wtns,
-                                                   u64 wstride, int live) {
-    u32 s = row_ptr[r], e = row_ptr[r + 1];
-#pragma unroll
-    for (int v = 0; v < VT; v++) acc[v] = fp_zero<FrParams>();
-    u32 since = 0;                                             // additions since the last contraction: a multiple of 4 here
-    for (u32 p = s; p < e; p += 4) {
-        const u32 cnt = e - p < 4 ? e - p : 4;
-        u32 sg[4];
-        Fr vq[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) sg[k] = (u32)k < cnt ? sig[p + k] : 0u;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            u32 vr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if ((u32)k < cnt) load8(vr, val + (size_t)(p + k) * 8);
-            vq[k] = unpack256<FrParams>(vr);
-        }
-        for_each_vector<0, VT>([&](auto vc) __attribute__((always_inline)) {
-            constexpr int v = decltype(vc)::value;
-            if (v < live) {
-                const u32* w = wtns + (size_t)v * wstride;
-                u32 wr[4][8];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    if ((u32)k < cnt) load8(wr[k], w + (size_t)sg[k] * 8);
-                }
-                u32 sn = since;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    if ((u32)k < cnt) {
-                        acc[v] = add(acc[v], mul(unpack256<FrParams>(wr[k]), vq[k]));
-                        if (++sn == 24) { acc[v] = contract(acc[v]); sn = 0; }
-                    }
-                }
-            }
-        });
-        since = (since + cnt) % 24;
-    }
-#pragma unroll
-    for (int v = 0; v < VT; v++) acc[v] = contract(acc[v]);
-}
-
+// (matvec_row_vectors, one row's sum for a tile of VT witnesses: dev_common.hpp, beside matvec_row -- shared with r1cs.hip)
 // one lane per row and tile of witnesses (blockIdx.y), as matvec_kernel; out_stride and wstride in words
 template <int VT>
 __global__ __launch_bounds__(256) void matvec_vectors_kernel(u32* a_br, u32* b_br, u64 out_stride, const u32* row_ptr, const u32* sig,

@@ -348,6 +348,13 @@ void r1cs_convert_coefs(u32* val, u64 n, hipStream_t stream);
 // queues the check of one witness (plain integers, n_wires elements): words[0] = failing constraints, words[1] = ~(lowest failing
 // index), both zeroed first on the stream; mask: rows device bytes (0 holds, 1 fails) or null
 void r1cs_check(const R1csDev& m, const u32* wtns, unsigned long long* words, uint8_t* mask, hipStream_t stream);
+// the same for `vectors` witnesses in ONE launch, witness v at wtns + v * wstride words: its two words at words + 2 v (all zeroed
+// first, one memset), its status bytes at mask + v * rows (or null). A lane takes one constraint for a group of R1CS_VT witnesses
+// (r1cs_vectors_group: one witness alone is a group of one; UG_R1CS_VT = 1, 2 or 4 overrides). Four per lane compile without scratch
+// too, but at one wave per SIMD, and are slower (profiles/registry_batch.txt).
+constexpr int R1CS_VT = 2;
+int r1cs_vectors_group(int vectors);
+void r1cs_check_vectors(const R1csDev& m, const u32* wtns, u64 wstride, int vectors, unsigned long long* words, uint8_t* mask, hipStream_t stream);
 // the values A.w, B.w, C.w of constraint k as canonical plain integers (24 device words), one lane
 void r1cs_row_values(const R1csDev& m, const u32* wtns, u32 k, u32* out24, hipStream_t stream);
 // the probe against a zkey's coefficient matrix over z (n_wires plain values): *word = the lowest failing 2 * row + matrix, or all ones

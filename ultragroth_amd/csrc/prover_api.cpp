@@ -786,11 +786,20 @@ struct ProverBase {        // what the extern "C" layer stores behind the opaque
     // k proofs in one call (ug_groth16_prover_prove_batch): outputs as k proveTurn calls in order. This form proves them one
     // after the other, each witness checked when its proof starts (an error names its position; the proofs before it have run);
     // Groth16Prover and UltraGrothProver check every witness first and run several witnesses per device pass.
+    // `device` and `around` as proveTurn's (the registry): every device pass of the call takes the card and is bracketed on its own.
     virtual void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
-                            std::vector<std::string>& pubs) {
+                            std::vector<std::string>& pubs, std::mutex* device = nullptr, const Around& around = Around()) {
         proofs.assign(k, std::string()); pubs.assign(k, std::string());
-        for (int b = 0; b < k; b++) atWitness(b, [&] { proveTurn(wtns[b], sizes[b], proofs[b], pubs[b]); });
+        for (int b = 0; b < k; b++) atWitness(b, [&] { proveTurn(wtns[b], sizes[b], proofs[b], pubs[b], device, around); notePass(1); });
     }
+    // a cap on what a batched pass plans with, beside the device's free memory (the registry: its budget less what the other
+    // circuits hold); unset: no cap
+    std::function<uint64_t()> batchRoom;
+    // the device passes of the batched calls since creation (ug_prover_batch_info): a pass of width V proved V witnesses together,
+    // a witness that took the single-proof path is a pass of width 1
+    std::atomic<uint64_t> batchPasses{0}, batchWitnesses{0};
+    std::atomic<int> batchLastWidth{0};
+    void notePass(int V) { batchPasses++; batchWitnesses += (uint64_t)V; batchLastWidth = V; }
     virtual unsigned long long proofBufferMinSize() const = 0;
     virtual unsigned long long publicBufferMinSize() const = 0;
     virtual void timings(double* msm, double* fft, double* total) const = 0;
@@ -1090,6 +1099,21 @@ public:
     void queueWitnessCheck(const ug_dvec* w, uint64_t first = 0, int slot = 0) {
         if (d_.r1cs) ugCheck(ug_r1cs_check_enqueue(d_.r1cs, w, first, slot, d_.ctx2));
     }
+    // the checks of the V witnesses of a batched pass (witness v at elements v * nVars of w) as ONE launch, results in slots 0 .. V - 1
+    // (the UltraGroth pass, behind its one lookup completion)
+    void queueWitnessChecks(const ug_dvec* w, int V) {
+        if (d_.r1cs) ugCheck(ug_r1cs_check_vectors_enqueue(d_.r1cs, w, 0, hdr_.nVars, V, 0, d_.ctx2));
+    }
+    // ... and their results: every slot is read, so that none stays queued; the lowest failing witness fails the call
+    void collectWitnessChecks(int b0, int V) {
+        if (!d_.r1cs) return;
+        std::exception_ptr bad;
+        for (int v = 0; v < V; v++) {
+            try { atWitness(b0 + v, [&] { collectWitnessCheck(v); }); }
+            catch (...) { if (!bad) bad = std::current_exception(); }
+        }
+        if (bad) std::rethrow_exception(bad);
+    }
     // ... and its result, read where the call has waited for the device anyway: a witness that breaks a constraint fails the call
     void collectWitnessCheck(int slot = 0) {
         if (!d_.r1cs) return;
@@ -1168,22 +1192,42 @@ void proveBatchInPasses(P& p, typename P::BatchCall& c, int k) {
     for (int b = 0; b < k; b++) atWitness(b, [&] { p.parseForBatch(c, b); });
     c.proofs.assign((size_t)k, std::string()); c.pubs.assign((size_t)k, std::string());
     std::lock_guard<std::mutex> batchLock(p.batch_.mutex);         // the batch buffers belong to one batch call at a time
+    // (a registry circuit: the card's lock before the prover's turn, as proveTurn takes them, and the bracket around what allocates or runs)
+    auto card = [&] { return c.device ? std::unique_lock<std::mutex>(*c.device) : std::unique_lock<std::mutex>(); };
     for (int b0 = 0; b0 < k;) {
         int V = 1;
         {
+            auto onCard = card();
             auto turn = p.takeTurn(false);                          // (allocations only under the turn)
+            AroundGuard bracket(c.around);
+            bracket.begin();
             V = p.perPass(c, k - b0, b0);
             if (V > 1) reserveForPass(p, c, V, b0);
+            bracket.end();
         }
-        if (V <= 1) { p.proveOneOfBatch(c, b0++); continue; }       // the single-proof path
+        if (V <= 1) {                                               // the single-proof path
+            auto onCard = card();
+            AroundGuard bracket(c.around);
+            bracket.begin();
+            p.proveOneOfBatch(c, b0++);
+            p.notePass(1);
+            bracket.end();
+            continue;
+        }
         p.stagePass(c, b0, V);
+        auto onCard = card();
         auto turn = p.takeTurn(true);
+        AroundGuard bracket(c.around);
+        bracket.begin();
         // the table plan may have changed meanwhile (Groth16Prover's tableBuilder): the rest is staged again. A no-op for
         // UltraGrothProver, whose tables never change after create.
         V = std::min(V, p.perPass(c, V, b0));
         if (V <= 1) continue;
         auto pass = p.runPass(c, b0, V);
+        p.notePass(V);
+        bracket.end();
         turn.unlock();
+        onCard = std::unique_lock<std::mutex>();
         p.finishPass(c, b0, V, pass);
         b0 += V;
     }
@@ -1915,6 +1959,7 @@ public:
         const void* const* wtns; const unsigned long long* sizes;
         std::vector<std::string>& proofs; std::vector<std::string>& pubs;
         std::vector<const uint8_t*> data;          // the witness section of every .wtns
+        std::mutex* device; const Around& around;  // (ProverBase::proveBatch)
         double msm = 0, fft = 0;
     };
     struct BatchPass {                             // (terms last: the host threads join before what they read goes)
@@ -1922,8 +1967,8 @@ public:
         std::vector<std::future<BlindingTerms>> terms;
     };
     void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
-                    std::vector<std::string>& pubs) override {
-        BatchCall c{wtns, sizes, proofs, pubs, std::vector<const uint8_t*>((size_t)k)};
+                    std::vector<std::string>& pubs, std::mutex* device = nullptr, const Around& around = Around()) override {
+        BatchCall c{wtns, sizes, proofs, pubs, std::vector<const uint8_t*>((size_t)k), device, around};
         proveBatchInPasses(*this, c, k);
     }
     void parseForBatch(BatchCall& c, int b) const {
@@ -1951,6 +1996,7 @@ public:
         uint64_t freeB = 0, totalB = 0;
         ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
         freeB += batch_.bytesHeld() + hpolyHeldBytes();               // (reused or replaced)
+        if (batchRoom) freeB = std::min<uint64_t>(freeB, batchRoom());     // (a registry circuit: the budget's room, not the card's)
         freeB = freeB > batchKeep_ ? freeB - batchKeep_ : 0;
         const uint64_t pending = pendingTableBytes();                 // (the background builder's tables keep their room)
         freeB = freeB > pending ? freeB - pending : 0;
@@ -1999,7 +2045,10 @@ public:
             enqueueWitnessProducts(d_, d_.ctx, d_.sw, outA.data(), outB1.data(), outB2.data(), outC.data(), (int64_t)hdr_.nPublic + 1,
                                    overlap == 2, batch_.w, V, nv, batch_.wB);
             if (overlap == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
-            for (int v = 0; v < V; v++) queueWitnessCheck(batch_.w, (uint64_t)v * nv, v);       // (an attached .r1cs: one check per witness, in slots)
+            // (an attached .r1cs: one check per witness, in slots. The one-launch form, queueWitnessChecks, measured 4 % slower than
+            // eight of these at 2^22 constraints -- profiles/registry_batch.txt --, so this pass, whose witnesses are resident from
+            // the start, keeps the single launches)
+            for (int v = 0; v < V; v++) queueWitnessCheck(batch_.w, (uint64_t)v * nv, v);
             hpolyOfBatch(views, V);                                                             // S5-S9 of the V witnesses
             ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
             if (overlap == 2) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));
@@ -2010,13 +2059,7 @@ public:
             ugCheck(ug_ctx_collect(d_.ctx));
             inFlight.done();
         }
-        // every slot is read, so that none stays queued; the lowest failing witness fails the call
-        std::exception_ptr bad;
-        for (int v = 0; v < V; v++) {
-            try { atWitness(b0 + v, [&] { collectWitnessCheck(v); }); }
-            catch (...) { if (!bad) bad = std::current_exception(); }
-        }
-        if (bad) std::rethrow_exception(bad);
+        collectWitnessChecks(b0, V);
         collectTimings(3);
         for (int v = 0; v < V; v++) {
             uint8_t* p = parts + (size_t)v * UG_GROTH16_PARTIALS_SIZE;
@@ -2125,7 +2168,7 @@ private:
         const uint64_t M = hdr_.nVars, N = hdr_.domainSize;
         const Ranges rg = shardRanges(M, N, hdr_.numIndexesC1, hdr_.numIndexesC2, rank, count);
         wr_ = rg.w; hr_ = rg.h;
-        batchable_ = count == 1 && !src.sliced && !g_registryCreate;      // (proveBatch: ranks and registry circuits go one by one)
+        batchable_ = count == 1 && !src.sliced;                           // (proveBatch: ranks go one by one)
         const Range c1 = rg.c1, c2 = rg.c2;
         const uint8_t *coefs = src.coefs, *pA = src.pA, *pB1 = src.pB1, *pB2 = src.pB2, *pRoundC = src.pRoundC, *pFinalC = src.pFinalC,
                       *pH = src.pH, *idx1 = src.idx1, *idx2 = src.idx2;
@@ -2477,13 +2520,13 @@ public:
     // ---- batched proofs (ug_groth16_prover_prove_batch) ----
     // As Groth16Prover::proveBatch, proveBatchInPasses with these parts. Parsing also checks a witness's lookup lists, which a
     // single proof checks only when it completes the lookup. The blinding of the whole call is drawn in witness order, rk, r, s
-    // per witness, a pass's scalars up front. Ranks of a sharded prover and registry circuits prove one after the other
-    // (ProverBase::proveBatch).
+    // per witness, a pass's scalars up front. Ranks of a sharded prover prove one after the other (ProverBase::proveBatch).
     struct BatchCall {
         const void* const* wtns; const unsigned long long* sizes;
         std::vector<std::string>& proofs; std::vector<std::string>& pubs;
         std::vector<StagedWitness> in;             // the lists and public signals of every .uwtns (publicPart receives the lookup writes)
         std::vector<const uint8_t*> signals;       // ... and its signals, in the caller's buffer
+        std::mutex* device; const Around& around;  // (ProverBase::proveBatch)
         double msm = 0, fft = 0;
     };
     struct BatchPass {                             // (terms last: the host threads join before what they read goes)
@@ -2492,10 +2535,9 @@ public:
         std::vector<std::future<HostTerms>> terms;
     };
     void proveBatch(int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
-                    std::vector<std::string>& pubs) override {
-        // (an attached .r1cs: one proof after the other, each with its check -- the batched pass has none of its own yet)
-        if (!batchable_ || !haveHpoly_ || r1csAttached()) { ProverBase::proveBatch(k, wtns, sizes, proofs, pubs); return; }
-        BatchCall c{wtns, sizes, proofs, pubs, std::vector<StagedWitness>((size_t)k), std::vector<const uint8_t*>((size_t)k)};
+                    std::vector<std::string>& pubs, std::mutex* device = nullptr, const Around& around = Around()) override {
+        if (!batchable_ || !haveHpoly_) { ProverBase::proveBatch(k, wtns, sizes, proofs, pubs, device, around); return; }
+        BatchCall c{wtns, sizes, proofs, pubs, std::vector<StagedWitness>((size_t)k), std::vector<const uint8_t*>((size_t)k), device, around};
         proveBatchInPasses(*this, c, k);
     }
     void parseForBatch(BatchCall& c, int b) const {
@@ -2506,7 +2548,8 @@ public:
         WitnessLease lease(witness_);
         stage(*lease, c.wtns[b], c.sizes[b]);
         std::lock_guard<std::mutex> turn(proveMutex);
-        proveStaged(*lease, c.proofs[(size_t)b], c.pubs[(size_t)b]);
+        try { proveStaged(*lease, c.proofs[(size_t)b], c.pubs[(size_t)b]); }
+        catch (WitnessFault& e) { throw WitnessFault("witness " + std::to_string(b) + ": " + e.what()); }
         c.msm += m1_ + m2_; c.fft += f1_ + f2_;
     }
     void stagePass(const BatchCall& c, int b0, int V) { batch_.stage(d_.ctx, witness_.stageMutex, &c.signals[(size_t)b0], V, hdr_.nVars); }
@@ -2526,7 +2569,7 @@ public:
             const uint8_t *r = &p.r[(size_t)v * 32], *s = &p.s[(size_t)v * 32];
             p.terms.push_back(std::async(std::launch::async, [this, rk, r, s] { return hostTermsFor(rk, r, s); }));
         }
-        runBatch(V, &c.in[(size_t)b0], p.rkw, p.sums.data(), p.commits.data());      // (the futures join in their destructors if this throws)
+        runBatch(V, &c.in[(size_t)b0], p.rkw, p.sums.data(), p.commits.data(), b0);      // (the futures join in their destructors if this throws)
         c.msm += m1_ + m2_; c.fft += f1_ + f2_;
         return p;
     }
@@ -2555,6 +2598,7 @@ public:
         uint64_t freeB = 0, totalB = 0;
         ugCheck(ug_ctx_mem_info(d_.ctx, &freeB, &totalB));
         freeB += batch_.bytesHeld() + hpolyHeldBytes();               // (reused or replaced)
+        if (batchRoom) freeB = std::min<uint64_t>(freeB, batchRoom());     // (a registry circuit: the budget's room, not the card's)
         freeB = freeB > batchKeep_ ? freeB - batchKeep_ : 0;
         const uint64_t pending = pendingTableBytes();                 // (none today: this prover builds its tables at create)
         freeB = freeB > pending ? freeB - pending : 0;
@@ -2579,7 +2623,7 @@ public:
     }
     // One device pass of the V staged witnesses (proveMutex held). sums = V blocks A | B1 | B2 | C | H as a single proof leaves
     // them, commits = the V blinded round commitments (pi_r); in[v].publicPart receives witness v's lookup writes.
-    void runBatch(int V, StagedWitness* in, const std::vector<std::array<u32, 8>>& rkw, uint8_t* sums, uint8_t* commits) {
+    void runBatch(int V, StagedWitness* in, const std::vector<std::array<u32, 8>>& rkw, uint8_t* sums, uint8_t* commits, int b0) {
         const uint64_t nv = hdr_.nVars, dom = hdr_.domainSize, nw = wr_.hi - wr_.lo, nh = hr_.hi - hr_.lo;
         const uint64_t nC1 = roundIdx_.size(), nC2 = finalIdx_.size();
         ugCheck(ug_ctx_timings(d_.ctx, nullptr, nullptr, 1)); ugCheck(ug_ctx_timings(d_.ctx2, nullptr, nullptr, 1));
@@ -2649,6 +2693,7 @@ public:
         }
         const char* ov = getenv("ULTRAGROTH_OVERLAP");
         if (ov && atoi(ov) == 0) ugCheck(ug_ctx_wait(d_.ctx2, d_.ctx));          // (default: beside, as a single proof)
+        queueWitnessChecks(batch_.w, V);             // (an attached .r1cs: the ONE lookup completion has written the V witnesses, the final round follows)
         hpolyOfBatch(views, V);                                                          // the FFT block of the V witnesses
         ugCheck(ug_schedule_build_vectors(d_.sh, batch_.h, hr_.lo, nh, V, dom, planH_.c, planH_.stride));
         {
@@ -2659,6 +2704,7 @@ public:
         ugCheck(ug_ctx_collect(d_.ctx2));
         ugCheck(ug_ctx_collect(d_.ctx));
         inFlight.done();
+        collectWitnessChecks(b0, V);
         collectTimings(3);
         for (int v = 0; v < V; v++) {
             uint8_t* p = sums + (size_t)v * UG_GROTH16_PARTIALS_SIZE;
@@ -3227,7 +3273,15 @@ public:
         std::string f = path.substr(path.find_last_of("/\\") + 1);
         return f.substr(0, f.find_last_of('.'));
     }
-    void load(const std::string& name, const void* zkey, uint64_t size, const std::string& path) {
+    // an attachment (attachR1cs) outlives the eviction of its circuit: the path of the .r1cs, or the registry's copy of the buffer
+    struct R1csSource {
+        std::string path;
+        std::shared_ptr<const std::vector<uint8_t>> copy;
+        bool any() const { return !path.empty() || copy; }
+    };
+    // `restore`: the attachment of the evicted circuit this load brings back (the reload of prove / proveBatch); a load by the caller
+    // has none, and drops what the name had
+    void load(const std::string& name, const void* zkey, uint64_t size, const std::string& path, const R1csSource* restore = nullptr) {
         if (r1csFromEnv()) throw std::invalid_argument(R1CS_UNAVAILABLE);      // (ULTRAGROTH_R1CS: never silently unchecked)
         std::lock_guard<std::mutex> lock(mutex_);
         if (name.empty()) throw std::invalid_argument("empty circuit name");
@@ -3248,10 +3302,19 @@ public:
         e->name = name; e->path = path; e->ultra = protocol == 1337;
         g_registryCreate = true;
         try {
-            if (e->ultra) e->prover.reset(new UltraGrothProver(zkey, size, device_));
-            else e->prover.reset(new Groth16Prover(zkey, size, device_, 0, 1));
+            RankProver* made = nullptr;
+            if (e->ultra) e->prover.reset(made = new UltraGrothProver(zkey, size, device_));
+            else e->prover.reset(made = new Groth16Prover(zkey, size, device_, 0, 1));
+            made->attachable_ = true;
         } catch (...) { g_registryCreate = false; throw; }
         g_registryCreate = false;
+        // the room of a batched pass: the budget less what everything else holds -- the circuit's own workspaces (batch buffers,
+        // schedules), which the pass reuses or replaces, count as room, as the held batch buffers do for a created prover
+        e->prover->batchRoom = [this, raw = e.get()] {
+            const uint64_t u = used(), own = raw->workBytes, others = u > own ? u - own : 0;
+            return budget_ > others ? budget_ - others : 0;
+        };
+        if (restore) e->r1cs = *restore;               // (attached again before its first proof: acquire)
         e->coreBytes = used() - before;
         e->lastUsed = ++tick_;
         if (e->coreBytes > budget_) throw std::runtime_error("circuit " + name + " does not fit the HBM budget");
@@ -3263,36 +3326,23 @@ public:
         }
         old.reset();                                   // the circuit this one replaces gives its memory back first
         entries_[name] = std::move(e);
-        evictedPaths_.erase(name);                     // a stale path of an earlier, evicted circuit of that name must not come back
+        evicted_.erase(name);                          // a stale path of an earlier, evicted circuit of that name must not come back
         if (!makeRoom(0, raw)) {
             entries_.erase(name);
             throw std::runtime_error("circuit " + name + " does not fit the HBM budget");
         }
         growTables();
     }
-    void loadFile(const std::string& path) {
+    void loadFile(const std::string& path, const R1csSource* restore = nullptr) {
         FileMap m(path);
-        load(circuitName(path), m.data(), m.size(), path);
+        load(circuitName(path), m.data(), m.size(), path, restore);
     }
     void prove(const std::string& name, const void* wtns, uint64_t wtnsSize, std::string& proof, std::string& pub,
                unsigned long long* proofSize, unsigned long long* publicSize) {
         Entry* e = nullptr;
         {
             std::unique_lock<std::mutex> lock(mutex_);
-            auto it = entries_.find(name);
-            if (it == entries_.end()) {
-                auto ev = evictedPaths_.find(name);
-                if (ev == evictedPaths_.end()) throw std::invalid_argument("circuit not loaded: " + name);
-                const std::string path = ev->second;          // evicted under memory pressure: its file brings it back
-                evictedPaths_.erase(ev);
-                lock.unlock();
-                loadFile(path);
-                lock.lock();
-                it = entries_.find(name);
-                if (it == entries_.end()) throw std::runtime_error("circuit could not be reloaded: " + name);
-            }
-            e = it->second.get();
-            e->lastUsed = ++tick_;
+            e = acquire(lock, name);
             checkBufferSizes(e->prover->proofBufferMinSize(), proofSize, e->prover->publicBufferMinSize(), publicSize, "Minimum");
             // room for the proof's workspaces (known after the circuit's first proof; a guess from its size before); when even
             // that cannot be had the proof is still tried -- its own allocations decide, and a failure leaves nothing queued
@@ -3320,11 +3370,77 @@ public:
         makeRoom(0, e);
         growTables();
     }
+    // k proofs of one circuit (ug_registry_prove_batch): as prove under the registry's locks -- reloaded when evicted, busy for the
+    // whole call -- with one turn on the card per device pass of the circuit's prover; checkMin(proofMin, publicMin) is the caller's
+    // test of its buffers against the circuit's minimum sizes
+    void proveBatch(const std::string& name, int k, const void* const* wtns, const unsigned long long* sizes, std::vector<std::string>& proofs,
+                    std::vector<std::string>& pubs, const std::function<void(unsigned long long, unsigned long long)>& checkMin) {
+        Entry* e = nullptr;
+        {
+            std::unique_lock<std::mutex> lock(mutex_);
+            e = acquire(lock, name);
+            checkMin(e->prover->proofBufferMinSize(), e->prover->publicBufferMinSize());
+            (void)makeRoom(e->workBytes ? 0 : e->coreBytes / 2, e);        // (as prove; the passes plan with what is left: batchRoom)
+            e->busy++;
+        }
+        std::exception_ptr failure;
+        try {
+            uint64_t before = 0;
+            e->prover->proveBatch(k, wtns, sizes, proofs, pubs, &deviceMutex_, [&](bool begin) {
+                if (begin) { before = used(); return; }
+                const uint64_t after = used();
+                if (after > before) e->workBytes += after - before;         // (the batch buffers are work bytes: trimWorkspaces gives them back)
+            });
+            e->proofs += (uint64_t)k;
+            proofsTotal_ += (uint64_t)k;
+        } catch (...) { failure = std::current_exception(); }
+        std::lock_guard<std::mutex> lock(mutex_);
+        e->busy--;
+        if (failure) std::rethrow_exception(failure);
+        makeRoom(0, e);
+        growTables();
+    }
+    // the circuit's .r1cs (ug_registry_attach_r1cs*): data / size the buffer (the registry keeps a copy), or `path` the file it is read
+    // from again after an eviction; size 0 and no path: detach. Rules and messages are attachR1cs's; on failure the old one stays.
+    void attachR1cs(const std::string& name, const void* data, uint64_t size, const std::string& path) {
+        std::unique_lock<std::mutex> lock(mutex_);
+        if (!size && path.empty()) {
+            auto it = entries_.find(name);
+            if (it == entries_.end()) {
+                auto ev = evicted_.find(name);
+                if (ev == evicted_.end()) throw std::invalid_argument("circuit not loaded: " + name);
+                ev->second.r1cs = R1csSource();
+                return;
+            }
+            Entry& e = *it->second;
+            e.prover->attachR1cs(nullptr, 0);
+            e.r1cs = R1csSource();
+            e.coreBytes -= std::min(e.coreBytes, e.r1csBytes);
+            e.r1csBytes = 0;
+            return;
+        }
+        Entry* e = acquire(lock, name, /*attach*/ false);
+        R1csSource src;
+        if (path.empty()) src.copy = std::make_shared<const std::vector<uint8_t>>((const uint8_t*)data, (const uint8_t*)data + size);
+        else src.path = path;
+        attachTo(*e, src);
+        e->r1cs = src;
+        makeRoom(0, e);
+    }
+    void batchInfo(const std::string& name, unsigned long long* passes, unsigned long long* witnesses, int* lastWidth) {
+        std::lock_guard<std::mutex> lock(mutex_);
+        auto it = entries_.find(name);
+        if (it == entries_.end()) throw std::invalid_argument("circuit not loaded: " + name);
+        const ProverBase& p = *it->second->prover;
+        if (passes) *passes = p.batchPasses;
+        if (witnesses) *witnesses = p.batchWitnesses;
+        if (lastWidth) *lastWidth = p.batchLastWidth;
+    }
     void evict(const std::string& name) {
         std::lock_guard<std::mutex> lock(mutex_);
         auto it = entries_.find(name);
         if (it != entries_.end() && it->second->busy) throw std::invalid_argument("circuit is proving, it cannot be evicted now: " + name);
-        const size_t resident = entries_.erase(name), remembered = evictedPaths_.erase(name);      // both, unconditionally
+        const size_t resident = entries_.erase(name), remembered = evicted_.erase(name);      // both, unconditionally
         if (!resident && !remembered) throw std::invalid_argument("circuit not loaded: " + name);
     }
     // name empty: totals. state: 0 not loaded, 1 resident without tables, 2 resident with tables, 3 evicted (reloadable)
@@ -3340,7 +3456,7 @@ public:
         if (it == entries_.end()) {
             if (bytes) *bytes = 0;
             if (proofs) *proofs = 0;
-            if (state) *state = evictedPaths_.count(name) ? 3 : 0;
+            if (state) *state = evicted_.count(name) ? 3 : 0;
             return;
         }
         Entry& e = *it->second;
@@ -3358,7 +3474,47 @@ private:
         std::atomic<uint64_t> workBytes{0}, proofs{0};       // written by the proof's bracket callback, outside mutex_
         uint64_t tablesDroppedAt = 0;      // tick at which its tables were taken away (it gets them back only after it was used again)
         int busy = 0;                      // proofs in flight on it: a busy circuit is never trimmed, evicted or replaced
+        R1csSource r1cs;                   // its attachment, when it has one: every proof is checked, the prover attached before the first
+        uint64_t r1csBytes = 0;            // ... and what it holds on the device (part of coreBytes)
     };
+    struct Evicted { std::string path; R1csSource r1cs; };
+    // the resident circuit `name` for a proof call (mutex_ held, released only for the reload of a circuit evicted under memory
+    // pressure: its file brings it back); attach: a circuit that has an attachment and whose prover lost it with the eviction is
+    // attached again here, and a failure fails the call -- it is never proven unchecked
+    Entry* acquire(std::unique_lock<std::mutex>& lock, const std::string& name, bool attach = true) {
+        auto it = entries_.find(name);
+        if (it == entries_.end()) {
+            auto ev = evicted_.find(name);
+            if (ev == evicted_.end()) throw std::invalid_argument("circuit not loaded: " + name);
+            const Evicted was = ev->second;
+            evicted_.erase(ev);
+            lock.unlock();
+            loadFile(was.path, &was.r1cs);
+            lock.lock();
+            it = entries_.find(name);
+            if (it == entries_.end()) throw std::runtime_error("circuit could not be reloaded: " + name);
+        }
+        Entry* e = it->second.get();
+        e->lastUsed = ++tick_;
+        if (attach && e->r1cs.any() && !e->prover->r1csAttached()) attachTo(*e, e->r1cs);
+        return e;
+    }
+    // attaches src to the circuit's prover and counts what it takes (less what an earlier attachment gives back) as resident bytes
+    void attachTo(Entry& e, const R1csSource& src) {
+        const uint64_t before = used();
+        if (src.copy) e.prover->attachR1cs(src.copy->data(), src.copy->size());
+        else {
+            std::unique_ptr<FileMap> m;
+            try { m.reset(new FileMap(src.path)); }
+            catch (std::exception& x) { throw std::invalid_argument("r1cs: cannot read " + src.path + ": " + x.what()); }
+            if (!m->size()) throw std::invalid_argument("r1cs: " + src.path + " is empty");
+            e.prover->attachR1cs(m->data(), m->size());
+        }
+        const uint64_t after = used();
+        const uint64_t now = after > before ? e.r1csBytes + (after - before) : e.r1csBytes - std::min(e.r1csBytes, before - after);
+        e.coreBytes = e.coreBytes - std::min(e.coreBytes, e.r1csBytes) + now;
+        e.r1csBytes = now;
+    }
     uint64_t used() {
         uint64_t freeB = 0, total = 0;
         ugCheck(ug_ctx_mem_info(probe_, &freeB, &total));
@@ -3382,7 +3538,7 @@ private:
             if (e) { e->prover->trimWorkspaces(); e->workBytes = 0; continue; }
             e = lru(keep, [](const Entry&) { return true; });
             if (e) {
-                if (!e->path.empty()) evictedPaths_[e->name] = e->path;
+                if (!e->path.empty()) evicted_[e->name] = Evicted{e->path, e->r1cs};
                 entries_.erase(e->name);
                 continue;
             }
@@ -3412,7 +3568,7 @@ private:
     std::mutex mutex_, deviceMutex_;
     std::atomic<uint64_t> proofsTotal_{0};
     std::map<std::string, std::unique_ptr<Entry>> entries_;
-    std::map<std::string, std::string> evictedPaths_;
+    std::map<std::string, Evicted> evicted_;
 };
 
 // =================================================================================================================
@@ -3583,32 +3739,31 @@ int ultra_groth_prover_prove(void* prover_object, const void* wtns_buffer, unsig
                                        public_size, error_msg, error_msg_maxsize);
 }
 
-int ug_groth16_prover_prove_batch(void* prover_object, int count, const void* const* wtns_buffers, const unsigned long long* wtns_sizes,
-                                  char* const* proof_buffers, unsigned long long* proof_sizes, char* const* public_buffers,
-                                  unsigned long long* public_sizes, char* error_msg, unsigned long long error_msg_maxsize) {
-    API_TRY
-    if (prover_object == NULL) throw std::invalid_argument("Null prover object");
+namespace {
+// The buffer rules of a batched call, shared by ug_groth16_prover_prove_batch and ug_registry_prove_batch.
+void checkBatchArguments(int count, const void* const* wtns_buffers, const unsigned long long* wtns_sizes, char* const* proof_buffers,
+                         unsigned long long* proof_sizes, char* const* public_buffers, unsigned long long* public_sizes) {
     if (count < 0) throw std::invalid_argument("Negative witness count");
     if (count && (!wtns_buffers || !wtns_sizes || !proof_buffers || !proof_sizes || !public_buffers || !public_sizes))
         throw std::invalid_argument("Null batch argument");
     for (int b = 0; b < count; b++)
         if (!wtns_buffers[b] || !proof_buffers[b] || !public_buffers[b])
             throw std::invalid_argument("Null buffer of witness " + std::to_string(b));
-    ProverBase* prover = static_cast<ProverBase*>(prover_object);
-    // the minimum sizes first, for every witness: a short buffer anywhere fails the call with every needed size written back
+}
+// the minimum sizes first, for every witness: a short buffer anywhere fails the call with every needed size written back
+void checkBatchMinimum(int count, unsigned long long* proof_sizes, unsigned long long* public_sizes, unsigned long long proofMin,
+                       unsigned long long publicMin) {
     bool shortMin = false;
-    for (int b = 0; b < count; b++)
-        shortMin |= proof_sizes[b] < prover->proofBufferMinSize() || public_sizes[b] < prover->publicBufferMinSize();
-    if (shortMin) {
-        for (int b = 0; b < count; b++) {
-            proof_sizes[b] = std::max<unsigned long long>(proof_sizes[b], prover->proofBufferMinSize());
-            public_sizes[b] = std::max<unsigned long long>(public_sizes[b], prover->publicBufferMinSize());
-        }
-        throw ShortBufferException("Proof or public buffer is too short. Minimum sizes: " + std::to_string(prover->proofBufferMinSize()) +
-                                   ", " + std::to_string(prover->publicBufferMinSize()));
+    for (int b = 0; b < count; b++) shortMin |= proof_sizes[b] < proofMin || public_sizes[b] < publicMin;
+    if (!shortMin) return;
+    for (int b = 0; b < count; b++) {
+        proof_sizes[b] = std::max<unsigned long long>(proof_sizes[b], proofMin);
+        public_sizes[b] = std::max<unsigned long long>(public_sizes[b], publicMin);
     }
-    std::vector<std::string> proofs, pubs;
-    prover->proveBatch(count, wtns_buffers, wtns_sizes, proofs, pubs);
+    throw ShortBufferException("Proof or public buffer is too short. Minimum sizes: " + std::to_string(proofMin) + ", " + std::to_string(publicMin));
+}
+void returnBatch(int count, const std::vector<std::string>& proofs, const std::vector<std::string>& pubs, char* const* proof_buffers,
+                 unsigned long long* proof_sizes, char* const* public_buffers, unsigned long long* public_sizes) {
     int shortAt = -1;
     for (int b = 0; b < count; b++)
         if (proof_sizes[b] < proofs[(size_t)b].length() || public_sizes[b] < pubs[(size_t)b].length()) { shortAt = b; break; }
@@ -3623,7 +3778,29 @@ int ug_groth16_prover_prove_batch(void* prover_object, int count, const void* co
         std::strncpy(proof_buffers[b], proofs[(size_t)b].c_str(), proof_sizes[b]);
         std::strncpy(public_buffers[b], pubs[(size_t)b].c_str(), public_sizes[b]);
     }
+}
+}  // namespace
+
+int ug_groth16_prover_prove_batch(void* prover_object, int count, const void* const* wtns_buffers, const unsigned long long* wtns_sizes,
+                                  char* const* proof_buffers, unsigned long long* proof_sizes, char* const* public_buffers,
+                                  unsigned long long* public_sizes, char* error_msg, unsigned long long error_msg_maxsize) {
+    API_TRY
+    if (prover_object == NULL) throw std::invalid_argument("Null prover object");
+    checkBatchArguments(count, wtns_buffers, wtns_sizes, proof_buffers, proof_sizes, public_buffers, public_sizes);
+    ProverBase* prover = static_cast<ProverBase*>(prover_object);
+    checkBatchMinimum(count, proof_sizes, public_sizes, prover->proofBufferMinSize(), prover->publicBufferMinSize());
+    std::vector<std::string> proofs, pubs;
+    prover->proveBatch(count, wtns_buffers, wtns_sizes, proofs, pubs);
+    returnBatch(count, proofs, pubs, proof_buffers, proof_sizes, public_buffers, public_sizes);
     API_CATCH
+}
+int ug_prover_batch_info(void* prover_object, unsigned long long* passes, unsigned long long* witnesses, int* last_width) {
+    if (!prover_object) return PROVER_ERROR;
+    const ProverBase* p = static_cast<ProverBase*>(prover_object);
+    if (passes) *passes = p->batchPasses;
+    if (witnesses) *witnesses = p->batchWitnesses;
+    if (last_width) *last_width = p->batchLastWidth;
+    return PROVER_OK;
 }
 
 void groth16_prover_destroy(void* prover_object) { delete static_cast<ProverBase*>(prover_object); }
@@ -3808,6 +3985,43 @@ int ug_registry_prove(void* registry, const char* circuit, const void* wtns_buff
     static_cast<Registry*>(registry)->prove(circuit, wtns_buffer, wtns_size, stringProof, stringPublic, proof_size, public_size);
     returnProof(stringProof, stringPublic, proof_buffer, proof_size, public_buffer, public_size);
     API_CATCH
+}
+int ug_registry_prove_batch(void* registry, const char* circuit, int count, const void* const* wtns_buffers, const unsigned long long* wtns_sizes,
+                            char* const* proof_buffers, unsigned long long* proof_sizes, char* const* public_buffers,
+                            unsigned long long* public_sizes, char* error_msg, unsigned long long error_msg_maxsize) {
+    API_TRY
+    if (registry == NULL) throw std::invalid_argument("Null registry object");
+    if (circuit == NULL) throw std::invalid_argument("Null circuit name");
+    checkBatchArguments(count, wtns_buffers, wtns_sizes, proof_buffers, proof_sizes, public_buffers, public_sizes);
+    std::vector<std::string> proofs, pubs;
+    static_cast<Registry*>(registry)->proveBatch(circuit, count, wtns_buffers, wtns_sizes, proofs, pubs,
+        [&](unsigned long long proofMin, unsigned long long publicMin) { checkBatchMinimum(count, proof_sizes, public_sizes, proofMin, publicMin); });
+    returnBatch(count, proofs, pubs, proof_buffers, proof_sizes, public_buffers, public_sizes);
+    API_CATCH
+}
+int ug_registry_attach_r1cs(void* registry, const char* circuit, const void* r1cs, unsigned long long size, char* error_msg,
+                            unsigned long long error_msg_maxsize) {
+    API_TRY
+    if (registry == NULL) throw std::invalid_argument("Null registry object");
+    if (circuit == NULL) throw std::invalid_argument("Null circuit name");
+    if (size && r1cs == NULL) throw std::invalid_argument("Null r1cs buffer");
+    static_cast<Registry*>(registry)->attachR1cs(circuit, r1cs, size, "");
+    API_CATCH
+}
+int ug_registry_attach_r1cs_file(void* registry, const char* circuit, const char* r1cs_file_path, char* error_msg,
+                                 unsigned long long error_msg_maxsize) {
+    API_TRY
+    if (registry == NULL) throw std::invalid_argument("Null registry object");
+    if (circuit == NULL) throw std::invalid_argument("Null circuit name");
+    if (r1cs_file_path == NULL || !*r1cs_file_path) throw std::invalid_argument("Null r1cs path");
+    static_cast<Registry*>(registry)->attachR1cs(circuit, nullptr, 0, r1cs_file_path);
+    API_CATCH
+}
+int ug_registry_batch_info(void* registry, const char* circuit, unsigned long long* passes, unsigned long long* witnesses, int* last_width) {
+    if (registry == NULL || circuit == NULL) return PROVER_ERROR;
+    try { static_cast<Registry*>(registry)->batchInfo(circuit, passes, witnesses, last_width); }
+    catch (...) { return PROVER_ERROR; }
+    return PROVER_OK;
 }
 int ug_registry_evict(void* registry, const char* circuit, char* error_msg, unsigned long long error_msg_maxsize) {
     API_TRY

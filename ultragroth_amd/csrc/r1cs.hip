@@ -49,6 +49,41 @@ __global__ __launch_bounds__(256) void r1cs_check_kernel(R1csDev m, const u32* w
     }
 }
 
+// The same for the V witnesses of a batched pass: one lane per constraint and group of VT witnesses (blockIdx.y; the last group has
+// live < VT), so a row's signal ids and coefficients are read once per group. The matrices one after the other -- a[VT], b[VT],
+// lhs[v] = canon(mul(a, b)) in a's place, then c[VT] --: matvec_row_vectors gives every accumulator the additions and contractions
+// of matvec_row for its witness, so failed, first and the status bytes of every witness are r1cs_check_kernel's, bit for bit.
+// Witness v at wtns + v * wstride words; its two words at words + 2 v, its status bytes (optional) at mask + v * rows.
+// VT = 1, 2 and 4 compile without scratch, at 159, 214 and 314 + 58 accumulation registers: four witnesses leave one wave per SIMD
+// and measure 1.4x the time of two (profiles/registry_batch.txt), so launches take two per lane (r1cs_vectors_group).
+template <int VT>
+__global__ __launch_bounds__(256) void r1cs_check_vectors_kernel(R1csDev m, const u32* wtns, u64 wstride, int vectors, unsigned long long* words,
+                                                                 uint8_t* mask) {
+    const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m.rows) return;
+    const int v0 = (int)blockIdx.y * VT, live = vectors - v0 < VT ? vectors - v0 : VT;
+    const u32* w0 = wtns + (size_t)v0 * wstride;
+    Fr lhs[VT], x[VT];
+    matvec_row_vectors<VT>(lhs, k, m.row_ptr[0], m.sig[0], m.val[0], w0, wstride, live);
+    matvec_row_vectors<VT>(x, k, m.row_ptr[1], m.sig[1], m.val[1], w0, wstride, live);
+    for_each_vector<0, VT>([&](auto vc) __attribute__((always_inline)) {
+        constexpr int v = decltype(vc)::value;
+        lhs[v] = canon(mul(lhs[v], x[v]));                          // a, b < 2.01 q: (a/q)(b/q) < 169
+    });
+    matvec_row_vectors<VT>(x, k, m.row_ptr[2], m.sig[2], m.val[2], w0, wstride, live);
+    for_each_vector<0, VT>([&](auto vc) __attribute__((always_inline)) {
+        constexpr int v = decltype(vc)::value;
+        if (v < live) {
+            const bool bad = !same_limbs(lhs[v], canon(x[v]));
+            if (mask) mask[(size_t)(v0 + v) * m.rows + k] = bad ? 1 : 0;
+            if (bad) {
+                atomicAdd(&words[2 * (v0 + v)], 1ull);
+                atomicMax(&words[2 * (v0 + v) + 1], ~(unsigned long long)k);
+            }
+        }
+    });
+}
+
 // the three values of constraint k as canonical plain integers: out[0..8) = A.w, [8..16) = B.w, [16..24) = C.w (one lane)
 __global__ void r1cs_row_kernel(R1csDev m, const u32* wtns, u32 k, u32* out) {
     if (blockIdx.x || threadIdx.x || k >= m.rows) return;
@@ -99,6 +134,26 @@ void r1cs_check(const R1csDev& m, const u32* wtns, unsigned long long* words, ui
     UG_HIP(hipMemsetAsync(words, 0, 16, stream));
     if (!m.rows) return;
     hipLaunchKernelGGL(r1cs_check_kernel, dim3(grid_for(m.rows, 256)), dim3(256), 0, stream, m, wtns, words, mask);
+    UG_KERNEL_CHECK();
+}
+template <int VT>
+static void launch_check_vectors(const R1csDev& m, const u32* wtns, u64 wstride, int vectors, unsigned long long* words, uint8_t* mask, hipStream_t stream) {
+    hipLaunchKernelGGL(r1cs_check_vectors_kernel<VT>, dim3(grid_for(m.rows, 256), (unsigned)((vectors + VT - 1) / VT)), dim3(256), 0, stream, m, wtns,
+                       wstride, vectors, words, mask);
+}
+int r1cs_vectors_group(int vectors) {
+    int vt = vectors >= R1CS_VT ? R1CS_VT : 1;
+    if (const char* e = getenv("UG_R1CS_VT")) vt = atoi(e);                // tuning knob: 1, 2 or 4 give the same bytes
+    return vt >= 4 ? 4 : vt >= 2 ? 2 : 1;
+}
+void r1cs_check_vectors(const R1csDev& m, const u32* wtns, u64 wstride, int vectors, unsigned long long* words, uint8_t* mask, hipStream_t stream) {
+    UG_HIP(hipMemsetAsync(words, 0, (size_t)16 * vectors, stream));
+    if (!m.rows) return;
+    switch (r1cs_vectors_group(vectors)) {
+        case 4: launch_check_vectors<4>(m, wtns, wstride, vectors, words, mask, stream); break;
+        case 2: launch_check_vectors<2>(m, wtns, wstride, vectors, words, mask, stream); break;
+        default: launch_check_vectors<1>(m, wtns, wstride, vectors, words, mask, stream);
+    }
     UG_KERNEL_CHECK();
 }
 void r1cs_row_values(const R1csDev& m, const u32* wtns, u32 k, u32* out24, hipStream_t stream) {

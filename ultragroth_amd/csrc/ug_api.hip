@@ -1774,6 +1774,27 @@ void r1cs_queue(ug_r1cs* r, const u32* wtns, int slot, hipStream_t stream, uint8
     UG_HIP(hipEventRecord(r->done[slot].e, stream));
     r->queued[slot].wtns = wtns; r->queued[slot].stream = stream; r->queued[slot].on = true;
 }
+// the checks of `count` witnesses (witness v at wtns + v * stride elements) queued on `stream` as ONE launch, slots slot0 .. slot0 + count - 1;
+// mask_dev: count * rows status bytes or null
+void r1cs_queue_vectors(ug_r1cs* r, const u32* wtns, u64 stride, int count, int slot0, hipStream_t stream, uint8_t* mask_dev, bool timed) {
+    if (timed) UG_HIP(hipEventRecord(r->t0.e, stream));
+    r1cs_check_vectors(r->dev(), wtns, stride * 8, count, r->words.get() + 2 * slot0, mask_dev, stream);
+    if (timed) UG_HIP(hipEventRecord(r->t1.e, stream));
+    UG_HIP(hipMemcpyAsync(r->words_host.get() + 2 * slot0, r->words.get() + 2 * slot0, (size_t)16 * count, hipMemcpyDeviceToHost, stream));
+    for (int v = 0; v < count; v++) {
+        UG_HIP(hipEventRecord(r->done[slot0 + v].e, stream));
+        r->queued[slot0 + v].wtns = wtns + (size_t)v * stride * 8; r->queued[slot0 + v].stream = stream; r->queued[slot0 + v].on = true;
+    }
+}
+// the first of `count` witnesses `stride` elements apart, the last one inside the vector
+const u32* r1cs_witnesses(const ug_r1cs* r, const ug_dvec* w, u64 first, u64 stride, int count, int slot0) {
+    if (count < 1 || count > UG_BATCH_MAX) throw std::invalid_argument("r1cs: count outside 1 .. UG_BATCH_MAX");
+    if (slot0 < 0 || slot0 + count > UG_BATCH_MAX) throw std::invalid_argument("r1cs: slots outside 0 .. UG_BATCH_MAX - 1");
+    const u32* p = r1cs_witness(r, w, first);
+    if (count > 1 && (w->n - first - r->hdr.nWires) / (u64)(count - 1) < stride)
+        throw std::invalid_argument("r1cs: the witness vector is shorter than first + (count - 1) * stride + n_wires (" + std::to_string(r->hdr.nWires) + " wires)");
+    return p;
+}
 // the slot's result; a failing witness costs a one-lane launch for the three values of its first failing constraint
 void r1cs_read(ug_r1cs* r, int slot, ug_r1cs_report* out) {
     ug_r1cs::Queued& q = r->queued[slot];
@@ -1870,6 +1891,37 @@ int ug_r1cs_check_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, in
     if (c->recording) throw std::invalid_argument("r1cs: no check while the context's stream is being recorded");
     c->use();
     r1cs_queue(r, r1cs_witness(r, witness, first), slot, c->stream, nullptr, /*timed*/ false);
+    UG_CATCH
+}
+int ug_r1cs_check_vectors_enqueue(ug_r1cs* r, const ug_dvec* witness, uint64_t first, uint64_t stride, int count, int slot0, ug_ctx* via) {
+    UG_TRY
+    if (!r || !witness) throw std::invalid_argument("null argument");
+    ug_ctx* c = via ? via : r->ctx;
+    if (c->device != r->ctx->device) throw std::invalid_argument("r1cs: the queueing context is on another device");
+    if (c->recording) throw std::invalid_argument("r1cs: no check while the context's stream is being recorded");
+    const u32* w = r1cs_witnesses(r, witness, first, stride, count, slot0);
+    c->use();
+    r1cs_queue_vectors(r, w, stride, count, slot0, c->stream, nullptr, /*timed*/ false);
+    UG_CATCH
+}
+int ug_r1cs_check_vectors(ug_r1cs* r, const ug_dvec* witness, uint64_t first, uint64_t stride, int count, ug_r1cs_report* reports, uint8_t* masks) {
+    UG_TRY
+    if (!r || !witness || !reports) throw std::invalid_argument("null argument");
+    ug_ctx* c = r->ctx;
+    if (c->recording) throw std::invalid_argument("r1cs: no check while the context's stream is being recorded");
+    const u32* w = r1cs_witnesses(r, witness, first, stride, count, 0);
+    for (int v = 0; v < count; v++)
+        if (r->queued[v].on) throw std::invalid_argument("r1cs: a check is still queued in slot " + std::to_string(v));
+    c->use();
+    const size_t rows = r->hdr.nConstraints;
+    DevBuf<uint8_t> md;
+    if (masks && rows) md.alloc(rows * count);
+    r1cs_queue_vectors(r, w, stride, count, 0, c->stream, md.get(), /*timed*/ true);
+    if (md.get()) UG_HIP(hipMemcpyAsync(masks, md.get(), rows * count, hipMemcpyDeviceToHost, c->stream));
+    UG_HIP(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    UG_HIP(hipEventElapsedTime(&ms, r->t0.e, r->t1.e));
+    for (int v = 0; v < count; v++) { r1cs_read(r, v, &reports[v]); reports[v].device_ms = ms; }      // (the one launch's time in every report)
     UG_CATCH
 }
 int ug_r1cs_check_collect(ug_r1cs* r, int slot, ug_r1cs_report* out) {
